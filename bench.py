@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the FlashAttention hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--mode fwd|fwdbwd] [--condition-ms MS]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--mode fwd|fwdbwd] [--dump-outputs DIR]
+                    [--full [--condition-ms MS] [--no-cpu-baseline] [--no-extra]]
     (--config defaults to c2, the single-GPU headline, on one GPU and to c4 -- BASELINE configs[3]: B=64 over 8 GPUs, 8 per GPU, S=8192 -- with --gpus N > 1)
+
+A plain run does what `value` needs and nothing else: set up, W warm-up steps, K timed steps, the outputs of the last timed step
+to DIR/<name>.npy if --dump-outputs is given (float32; a fixed, seeded sample of rows where they exceed the size budget), one
+JSON line.  Everything else the bench measures -- the conditioned "steady_state" leg, the hwmon power / clock sampler, the output
+exchange of N > 1 ranks ("gather"), the other configs and precisions ("extra"), the limiter residencies, the reference harness
+vs SDPA and the CPU baseline -- runs with --full only.
 
 One "step" = one pass of the hot path (aule.flash_attention -> libaule.so -> gfx950
 kernels) over one batch of synthetic [B,H,S,D] tensors already resident in HBM.
@@ -20,12 +27,12 @@ warm-up steps, then EXACTLY K timed steps between barrier + synchronize pairs, t
 it.  MI355X clocks to its power budget: from an idle chip the first two launches of this kernel run at boost clock, launches
 3-8 collapse to ~1.45x the steady time while the power controller overshoots, and it takes ~60 launches (35-40 ms) to settle
 (profiles/r2_dvfs_trace.txt; same curve on every box) -- a 5 + 20 step measurement right after process start sits inside
-that transient.  The number a long-running job sees is therefore measured too and reported SEPARATELY as "steady_state":
+that transient.  The number a long-running job sees is therefore measured too (--full) and reported SEPARATELY as "steady_state":
 the same step repeated for --condition-ms of device time (default 250 ms), then W warm-up + K timed steps again.  (Round 2
 printed the conditioned figure as `value` and the plain one as "cold_start"; the two have swapped places.)  Every timed step
 has its own HIP event pair: mean, median, min and max per launch are in "roofline".
 
-Round 6: every leg is a complete measurement.  A sampler thread reads the hwmon files of the device under test (socket power,
+Round 6 (--full): every leg is a complete measurement.  A sampler thread reads the hwmon files of the device under test (socket power,
 shader clock, power cap) every few milliseconds for the whole process; each leg reports the mean power and the mean / minimum
 clock of ITS timed window next to the per-step mean, median, minimum and maximum ("legs").  A fwd+bwd step carries an event
 between the forward call and `backward()`, so every backward figure (`*_bwd_ms`, `*_bwd_frac`) is the MEDIAN of the backward
@@ -151,12 +158,16 @@ class Telemetry:
     power1_average; microwatts), shader clock (freq1_input; Hz), power cap (power1_cap).  The device is found by its PCI address
     (torch's device properties -> /sys/bus/pci/devices/<domain:bus:device.0>/hwmon/hwmon*): with several cards on a node every
     rank reads its own.  A leg asks for the statistics of a [t0, t1] window of time.perf_counter().  No file, no permission
-    or no samples -> every statistic is None and `source` says why; the bench never fails on telemetry."""
+    or no samples -> every statistic is None and `source` says why; the bench never fails on telemetry.  enabled=False (a plain
+    run): no thread, every statistic None."""
 
     PERIOD_S = 0.004
 
-    def __init__(self, torch, index):
+    def __init__(self, torch, index, enabled=True):
         self.rows, self.hw, self.source, self.cap_w, self.label, self.bdf = [], None, None, None, None, None
+        if not enabled:
+            self.source = "not sampled (plain run; --full samples hwmon)"
+            return
         import glob
         try:
             pr = torch.cuda.get_device_properties(index)
@@ -319,16 +330,46 @@ def step_stats(xs):
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # float32 bytes over all dumped arrays (the files, headers included, stay under 64 MB)
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Writes every (name, tensor) of `arrays` as float32 to directory/<name>.npy.  When all of them fit in `budget` bytes they
+    are written whole, in their own shape; otherwise the budget is shared in proportion to their sizes and each array is
+    written as a fixed, seeded sample of its rows (the last dimension kept whole, rows in ascending order), shape
+    [rows kept, last dim].  The sample depends only on the shapes and `seed`, so two runs with the same arguments write the
+    same elements.  Returns {name: {"shape", "rows", "rows_kept"}}."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    total = 4 * sum(t.numel() for _, t in arrays)
+    written = {}
+    for name, t in arrays:
+        t = t.detach()
+        rows = t.reshape(-1, t.shape[-1])
+        n = rows.shape[0]
+        keep = n if total <= budget else max(1, n * budget // total)
+        if keep < n:
+            idx = np.sort(np.random.RandomState(seed).choice(n, keep, replace=False))
+            a = rows[torch.from_numpy(idx).to(rows.device)].float().cpu().numpy()
+        else:
+            a = t.float().cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written[name] = {"shape": list(t.shape), "rows": n, "rows_kept": keep}
+    return written
+
+
 def workload_string(config, B, mode=None):
     _, Hq, Hkv, Sq, Sk, D, dtype, causal, dmode = CONFIGS[config]
     return "%s: B=%d/GPU Hq=%d Hkv=%d Sq=%d Sk=%d D=%d %s %s %s" % (config, B, Hq, Hkv, Sq, Sk, D, dtype, "causal" if causal else "non-causal", mode or dmode)
 
 
 def self_spawn(args):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it: become `python -m torch.distributed.run --nnodes=1
+    """`python bench.py --gpus N` with N > 1 and no launcher around it: run `python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <the same arguments>` -- the command the driver
-    uses -- by exec, so that rank 0's JSON line is this process's stdout and its exit code this process's.  The device count is
-    checked first: a box with fewer GPUs fails here with that message, not inside a rendezvous."""
+    uses -- as a fresh child process on this process's stdout / stderr, and exit with its status, so that rank 0's JSON line is
+    this process's stdout and its exit code this process's.  The device count is checked first: a box with fewer GPUs fails
+    here with that message, not inside a rendezvous."""
     if not args.dry_run:
         import torch
         n = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -341,7 +382,8 @@ def self_spawn(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))
 
 
 def gather_watchdog(result, rank, limit_s, before_print=None):
@@ -434,10 +476,17 @@ def main():
                     help="default: c2 (BASELINE configs[1], the headline) on one GPU, c4 (configs[3]: B=64 over 8 GPUs -> 8 per GPU, S=8192) with --gpus N > 1")
     ap.add_argument("--mode", default=None, choices=["fwd", "fwdbwd"])
     ap.add_argument("--batch", type=int, default=None, help="override the per-GPU batch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (out; dq, dk, dv in fwdbwd mode; rank 0's "
+                         "shard) as float32 DIR/<name>.npy, a fixed seeded sample of rows where the whole exceeds %d MiB"
+                         % (DUMP_BUDGET_BYTES >> 20))
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside `value`: the conditioned steady_state leg, hwmon telemetry, the output exchange "
+                         "of N > 1 ranks, the extra configs / precisions, the limiter, the reference harness vs SDPA, the CPU baseline")
     ap.add_argument("--condition-ms", type=float, default=250.0,
-                    help="device time spent repeating the step before warm-up (0: none); see the module docstring")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+                    help="(--full) device time spent repeating the step before warm-up (0: none); see the module docstring")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the extra configs / precisions / limiter")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / timing scaffolding only (gloo, no device, no kernels): what tests/test_bench_spawn.py drives")
     args = ap.parse_args()
@@ -491,14 +540,22 @@ def main():
     # autograd on in both modes: the forward then stores LSE (what a training forward, and the reference's, does)
     q.requires_grad_(True); k.requires_grad_(True); v.requires_grad_(True)
 
-    tel = Telemetry(torch, local_rank)
+    tel = Telemetry(torch, local_rank, enabled=args.full)
     dump_steps = bool(os.environ.get("AULE_BENCH_DUMP_STEPS"))
+    # --dump-outputs: the output of the latest step is kept (otherwise it is dropped as soon as the step returns, as before)
+    keep_last = args.dump_outputs is not None
+    last = [None]
 
     def step(mid=None):
         if mode == "fwd":
-            return aule.flash_attention(q, k, v, causal=causal)
+            out = aule.flash_attention(q, k, v, causal=causal)
+            if keep_last:
+                last[0] = out
+            return out
         q.grad = k.grad = v.grad = None
         out = aule.flash_attention(q, k, v, causal=causal)
+        if keep_last:
+            last[0] = out
         if mid is not None:
             mid()
         out.backward(do)
@@ -606,10 +663,17 @@ def main():
     main_leg = leg("value", step, args.steps, 0.0, args.warmup, split_main, f_step, PEAK_TFLOPS[dtype])
     wall, dev_ms = main_leg["_raw"]["wall_s"], main_leg["_raw"]["dev_ms"]
     launches = sorted(main_leg["_raw"]["per_step"])
-    # 2. the same protocol again behind a conditioning phase -> "steady_state" (reported beside `value`, never as it)
-    steady_leg = leg("steady_state", step, args.steps, args.condition_ms, args.warmup, split_main, f_step, PEAK_TFLOPS[dtype])
-    steady_wall, steady_dev_ms = steady_leg["_raw"]["wall_s"], steady_leg["_raw"]["dev_ms"]
-    cond_steps, cond_ms = steady_leg.get("conditioning_steps", 0), steady_leg.get("conditioning_ms", 0.0)
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        # what the caller of the timed path received from its last step: O, and in fwdbwd mode the gradients
+        arrays = [("out", last[0])] + ([("dq", q.grad), ("dk", k.grad), ("dv", v.grad)] if mode == "fwdbwd" else [])
+        dumped = dump_outputs(args.dump_outputs, arrays)
+    last[0] = None
+    if args.full:
+        # 2. the same protocol again behind a conditioning phase -> "steady_state" (reported beside `value`, never as it)
+        steady_leg = leg("steady_state", step, args.steps, args.condition_ms, args.warmup, split_main, f_step, PEAK_TFLOPS[dtype])
+        steady_wall, steady_dev_ms = steady_leg["_raw"]["wall_s"], steady_leg["_raw"]["dev_ms"]
+        cond_steps, cond_ms = steady_leg.get("conditioning_steps", 0), steady_leg.get("conditioning_ms", 0.0)
 
     def launch_stats():
         n = len(launches)
@@ -626,7 +690,20 @@ def main():
     elt = 2 if dtype != "fp32" else 4
     alg_bytes = elt * (2 * B * Hq * Sq * D + 2 * B * Hkv * Sk * D) + 4 * B * Hq * Sq
     hbm_bound = mode == "fwd" and f_step / alg_bytes < RIDGE
-    tel_value, tel_steady = measured_telemetry(main_leg), measured_telemetry(steady_leg)
+    tel_value = measured_telemetry(main_leg)
+    steady = {}        # --full: the conditioned leg's figures beside `value` (top level "steady_state", roofline frac_steady / steady)
+    if args.full:
+        tel_steady = measured_telemetry(steady_leg)
+        frac_steady = f_step / (steady_dev_ms / args.steps * 1e-3) / 1e12 / PEAK_TFLOPS[dtype]
+        steady = {"steady_state": {"value": f_step * n_gpus * args.steps / steady_wall / 1e12, "ms_per_step": steady_wall * 1e3 / args.steps,
+                         "frac": frac_steady,
+                         "ms_per_step_median": steady_leg["ms_median"], "ms_per_step_min": steady_leg["ms_min"], "ms_per_step_max": steady_leg["ms_max"],
+                         "frac_median": steady_leg.get("frac_median"),
+                         "conditioning_ms": cond_ms, "conditioning_steps": cond_steps, **tel_steady,
+                         "note": "the same W + K protocol AFTER repeating the step for --condition-ms of device time: past the MI355X DVFS "
+                                 "transient that follows load onset (~60 launches / 40 ms, profiles/r2_dvfs_trace.txt).  What a long-"
+                                 "running job sees; `value` above is the plain protocol (round 2 called that one cold_start); power_w / "
+                                 "sclk_mhz: hwmon of this device in the timed window of THIS run"}}
 
     result = {
         "metric": "attention TFLOPS/GPU (fwd, fwd+bwd) + % MFMA roofline at S=4096,D=128",
@@ -645,15 +722,7 @@ def main():
             "global_batch": B * n_gpus, "parallelism": "batch-sharded dp%d, no data-path collective" % n_gpus,
             "flop_convention": "4*B*Hq*D*sum_i min(i+1,Sk) (causal), bwd=2.5x fwd",
             "lse": "stored (autograd is on: the forward writes the log-sum-exp like the reference's, triton_flash_amd.py:410-432)"},
-        "steady_state": {"value": f_step * n_gpus * args.steps / steady_wall / 1e12, "ms_per_step": steady_wall * 1e3 / args.steps,
-                         "frac": f_step / (steady_dev_ms / args.steps * 1e-3) / 1e12 / PEAK_TFLOPS[dtype],
-                         "ms_per_step_median": steady_leg["ms_median"], "ms_per_step_min": steady_leg["ms_min"], "ms_per_step_max": steady_leg["ms_max"],
-                         "frac_median": steady_leg.get("frac_median"),
-                         "conditioning_ms": cond_ms, "conditioning_steps": cond_steps, **tel_steady,
-                         "note": "the same W + K protocol AFTER repeating the step for --condition-ms of device time: past the MI355X DVFS "
-                                 "transient that follows load onset (~60 launches / 40 ms, profiles/r2_dvfs_trace.txt).  What a long-"
-                                 "running job sees; `value` above is the plain protocol (round 2 called that one cold_start); power_w / "
-                                 "sclk_mhz: hwmon of this device in the timed window of THIS run"},
+        **steady,
         "world_size": world,
         "per_gpu_tflops": value / n_gpus,
         "telemetry_source": tel.source,
@@ -665,14 +734,14 @@ def main():
                      if hbm_bound else
                      {"bound": "mfma", "achieved": achieved, "peak": PEAK_TFLOPS[dtype], "unit": "TFLOP/s",
                       "frac": achieved / PEAK_TFLOPS[dtype], "traffic": hbm_traffic(args.config, mode),
-                      "frac_steady": f_step / (steady_dev_ms / args.steps * 1e-3) / 1e12 / PEAK_TFLOPS[dtype],
+                      **({"frac_steady": frac_steady} if args.full else {}),
                       "traffic_source": "stored: rocprofv3 PMC passes of the last profiled run of this workload (profiles/hbm_traffic.json, "
                                         "FETCH_SIZE x2 + WRITE_SIZE per launch), not measured in this run",
                       "effective_clock_ghz_profiled": stored_profile(args.config, mode).get("effective_clock_ghz"),
                       # MEASURED in this run (round 6): hwmon socket power / shader clock of this device in the timed window of the
                       # `value` leg and of the conditioned leg; the power cap as hwmon reports it
                       **tel_value,
-                      "steady": tel_steady,
+                      **({"steady": tel_steady} if args.full else {}),
                       "telemetry": "measured: hwmon sampler thread, the timed window of the `value` leg (top level) and of the conditioned leg (`steady`)",
                       # stored: what this chip sustains on N(0,1) operands as a fraction of `peak` -- a RANGE with its sources (round 5):
                       # bare-MFMA loops of two shapes, and the vendor GEMM (hipBLASLt bf16 8192^3) as the control (profiles/r5_ceiling_control.txt)
@@ -683,13 +752,13 @@ def main():
                               "peak assumes 2.4 GHz, sclk_mhz is what hwmon read while the leg ran" % int(alg_bytes)}),
     }
     if split_main:
-        for nm, lg in (("value", main_leg), ("steady_state", steady_leg)):
+        for nm, lg in (("value", main_leg),) + ((("steady_state", steady_leg),) if args.full else ()):
             b = lg["bwd_segment"]["ms_median"]
             result.setdefault("backward", {})[nm] = {"bwd_ms_median": b, "fwd_ms_median": lg["fwd_segment"]["ms_median"],
                                                      "bwd_tflops": 2.5 * f_fwd / (b * 1e-3) / 1e12,
                                                      "bwd_frac": 2.5 * f_fwd / (b * 1e-3) / 1e12 / PEAK_TFLOPS[dtype]}
 
-    if dist is not None and (n_gpus > 1 or os.environ.get("AULE_BENCH_FORCE_GATHER")):
+    if args.full and dist is not None and (n_gpus > 1 or os.environ.get("AULE_BENCH_FORCE_GATHER")):
         # the one exchange of the sharded path: every rank receives every rank's O over xGMI (RCCL), timed separately
         # from `value` (kernel-only scaling): (a) one blocking all-gather behind the whole shard (round 1), (b) the shard
         # in pieces, each piece's all-gather overlapping the next piece's kernels, (c) the same with direct peer sends
@@ -747,7 +816,7 @@ def main():
         section_done.set()
         del gathered
 
-    if rank == 0 and n_gpus == 1 and not args.no_extra and args.config == "c2":
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_extra and args.config == "c2":
         PK = PEAK_TFLOPS["bf16"]
         extra = result["extra"] = {}
         # which limiter holds the clock while the headline kernel runs back to back (documented amdsmi accumulators; one second of launches)
@@ -984,6 +1053,9 @@ def main():
 
     if rank == 0:
         result["legs"] = legs
+        if dumped is not None:
+            result["outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "dtype": "float32",
+                                 "note": "the last timed step's outputs; arrays with rows_kept < rows hold a fixed, seeded sample of rows"}
 
     if rank == 0:
         # the reference harness counts 4*B*H*S^2*D with NO causal discount (tests/benchmark_attention.zig:68-75):
@@ -995,7 +1067,7 @@ def main():
             "formula": "4*B*Hq*Sq*Sk*D (x3.5 fwd+bwd), no causal discount -- counts masked work; NOT achieved throughput",
             "ratio_to_value": f_ref / f_step}
 
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline()
 
     if rank == 0:

@@ -82,3 +82,44 @@ def test_a_hung_exchange_section_still_prints_the_line():
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout
     assert lines[0]["world_size"] == 2 and "error" in lines[0]["gather"], lines[0]
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs' writer: float32 .npy files, whole arrays when they fit the budget, otherwise the same fixed, seeded
+    sample of rows from run to run, the budget shared in proportion to size and never exceeded."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    a = torch.randn(2, 3, 40, 16, generator=g, dtype=torch.float64).to(torch.bfloat16)
+    b = torch.randn(2, 1, 40, 16, generator=g)
+    rec = bench.dump_outputs(str(tmp_path / "whole"), [("a", a), ("b", b)])
+    assert rec["a"] == {"shape": [2, 3, 40, 16], "rows": 240, "rows_kept": 240}
+    for name, t in (("a", a), ("b", b)):
+        x = np.load(str(tmp_path / "whole" / (name + ".npy")))
+        assert x.dtype == np.float32 and x.shape == tuple(t.shape)
+        assert np.array_equal(x, t.float().numpy())
+    budget = 4 * 16 * 100          # room for 100 of the 320 rows
+    rec1 = bench.dump_outputs(str(tmp_path / "s1"), [("a", a), ("b", b)], budget=budget)
+    rec2 = bench.dump_outputs(str(tmp_path / "s2"), [("a", a), ("b", b)], budget=budget)
+    assert rec1 == rec2 and rec1["a"]["rows_kept"] == 75 and rec1["b"]["rows_kept"] == 25
+    total = 0
+    for name, t in (("a", a), ("b", b)):
+        x1, x2 = (np.load(str(tmp_path / d / (name + ".npy"))) for d in ("s1", "s2"))
+        assert x1.dtype == np.float32 and x1.shape == (rec1[name]["rows_kept"], 16) and np.array_equal(x1, x2)
+        rows = t.float().reshape(-1, 16).numpy()
+        # every sampled row is a row of the array, in ascending row order
+        idx = [int(np.flatnonzero((rows == r).all(axis=1))[0]) for r in x1]
+        assert idx == sorted(set(idx))
+        total += x1.nbytes
+    assert total <= budget
+
+
+def test_full_and_dump_outputs_are_options():
+    r = _run("--help")
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+    # the launch scaffolding takes both (a dry run computes nothing, so it writes nothing)
+    r = _run("--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "0", "--full", "--dump-outputs", os.devnull)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(_json_lines(r.stdout)) == 1

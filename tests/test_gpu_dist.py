@@ -24,7 +24,7 @@ def _run(cmd, extra_env=None):
 def test_bench_under_torchrun_one_rank():
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
               "--master-addr", "127.0.0.1", "--master-port", "29517", "bench.py", "--gpus", "1", "--steps", "3",
-              "--warmup", "1", "--batch", "2", "--condition-ms", "20", "--no-cpu-baseline", "--no-extra"],
+              "--warmup", "1", "--batch", "2", "--full", "--condition-ms", "20", "--no-cpu-baseline", "--no-extra"],
              {"AULE_BENCH_FORCE_GATHER": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -93,7 +93,7 @@ def test_bench_watchdog_prints_the_line_when_the_exchange_hangs():
     line -- `value` measured before the section, the legs, the reason under gather.error -- and the process ends with status 0."""
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
               "--master-addr", "127.0.0.1", "--master-port", "29519", "bench.py", "--gpus", "1", "--steps", "3",
-              "--warmup", "1", "--batch", "1", "--condition-ms", "10", "--no-cpu-baseline", "--no-extra"],
+              "--warmup", "1", "--batch", "1", "--full", "--condition-ms", "10", "--no-cpu-baseline", "--no-extra"],
              {"AULE_BENCH_FORCE_GATHER": "1", "AULE_BENCH_TEST_HANG": "1", "AULE_BENCH_GATHER_TIMEOUT": "4"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
