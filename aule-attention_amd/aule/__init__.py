@@ -208,7 +208,8 @@ def scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.
                                  scale=None, enable_gqa=False):
     """Drop-in for torch.nn.functional.scaled_dot_product_attention (same signature as the reference's
     shim, __init__.py:288-297).  Runs the HIP kernels when it can and defers to PyTorch's own SDPA for
-    what the kernels do not cover: attn_mask, dropout, head_dim > 128, non-4-D or non-ROCm tensors,
+    what the kernels do not cover or run slower: attn_mask, dropout, head_dim > 256 or strictly between 128 and 256 (those run
+    zero-padded to 256 here and measured slower than PyTorch's own SDPA: tools/d256_bench.py), non-4-D or non-ROCm tensors,
     dtypes other than fp16/bf16/fp32, and mismatched head counts without enable_gqa (PyTorch raises).
     torch's is_causal mask is top-left aligned, like this library's."""
     import torch
@@ -217,7 +218,7 @@ def scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.
         attn_mask is not None or dropout_p > 0.0
         or not (isinstance(query, torch.Tensor) and query.is_cuda and key.is_cuda and value.is_cuda)
         or query.dim() != 4 or key.dim() != 4 or value.dim() != 4
-        or query.shape[-1] > 128 or key.shape[-1] != query.shape[-1] or value.shape[-1] != query.shape[-1]
+        or (128 < query.shape[-1] < 256) or query.shape[-1] > 256 or key.shape[-1] != query.shape[-1] or value.shape[-1] != query.shape[-1]
         or str(query.dtype) not in _SDPA_DTYPES
         or (query.shape[1] != key.shape[1] and not enable_gqa)
         or key.shape[1] == 0 or query.shape[1] % max(1, key.shape[1]) != 0

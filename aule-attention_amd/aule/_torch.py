@@ -17,7 +17,8 @@ import torch
 from . import _capi
 
 _DTYPES = {torch.float32: _capi.DTYPE_F32, torch.float16: _capi.DTYPE_F16, torch.bfloat16: _capi.DTYPE_BF16}
-SUPPORTED_HEAD_DIMS = (32, 64, 128)
+SUPPORTED_HEAD_DIMS = (32, 64, 128, 256)
+PAGED_HEAD_DIMS = (32, 64, 128)   # paged decode has no D = 256 instance
 
 
 _ALWAYS_AUTOGRAD = os.environ.get("AULE_HIP_ALWAYS_AUTOGRAD", "0") == "1"
@@ -218,8 +219,8 @@ def flash_attention_hip(q, k, v, causal=True, scale=None, window=-1):
     """Device tensors in, device tensor out, autograd-aware.  dtype fp16/bf16/fp32 run
     natively; anything else is computed in fp32 and cast back."""
     D = q.shape[-1]
-    if D > 128:
-        raise ValueError(f"head_dim must be <= 128 for the HIP backend, got {D}")
+    if D > 256:
+        raise ValueError(f"head_dim must be <= 256 for the HIP backend, got {D}")
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     orig_dtype = q.dtype
@@ -328,8 +329,8 @@ def flash_attention_rope_hip(q, k, v, cos, sin, causal=True, scale=None, window=
     """RoPE + attention on device tensors, autograd-aware.  Query i uses table row i (row i + Sk - Sq with
     causal="bottom-right"), key j row j -- the positions of the reference's kernel (triton_flash.py:119, :169)."""
     D = q.shape[-1]
-    if D > 128:
-        raise ValueError(f"head_dim must be <= 128 for the HIP backend, got {D}")
+    if D > 256:
+        raise ValueError(f"head_dim must be <= 256 for the HIP backend, got {D}")
     if D % 2:
         raise ValueError(f"RoPE needs an even head_dim, got {D}")
     if layout not in _ROPE_LAYOUTS:
@@ -387,8 +388,8 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, wi
         raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
     if q.dtype not in (torch.float16, torch.bfloat16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise ValueError("paged decode runs in fp16 or bf16 (query and caches in the same dtype)")
-    if D not in SUPPORTED_HEAD_DIMS:
-        raise ValueError(f"head_dim must be one of {SUPPORTED_HEAD_DIMS} for paged decode, got {D}")
+    if D not in PAGED_HEAD_DIMS:
+        raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS} for paged decode, got {D}")
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     lib = _capi.get_lib()

@@ -6,7 +6,7 @@ method names, argument meaning and error behaviour (AuleError / ValueError), bou
 to libaule.so's legacy symbols (aule_tensor_*, aule_attention_forward_gpu,
 aule_attention_forward_with_lse, aule_attention_backward).
 
-Differences from the Vulkan binding, all widenings: head_dim <= 128 (vulkan.py:707-711
+Differences from the Vulkan binding, all widenings: head_dim <= 256 (vulkan.py:707-711
 caps at 64), and the work runs on the gfx950 MFMA kernels.
 """
 import ctypes
@@ -151,8 +151,8 @@ class Aule:
             raise ValueError(f"Shape mismatch: Q={query.shape}, K={key.shape}")
         if Hq % key.shape[1] != 0:
             raise ValueError(f"Query heads {Hq} must be divisible by KV heads {key.shape[1]}")
-        if D > 128:
-            raise ValueError(f"head_dim must be <= 128, got {D}")
+        if D > 256:
+            raise ValueError(f"head_dim must be <= 256, got {D}")
         q = self.tensor(query.shape)
         k = self.tensor(key.shape)
         v = self.tensor(value.shape)
@@ -190,8 +190,8 @@ class Aule:
             raise ValueError("Inputs must be 4D [batch, heads, seq, dim]")
         if query.shape != key.shape or query.shape != value.shape:
             raise ValueError("Q, K, V must have same shape (training path is MHA, Sq == Sk)")
-        if query.shape[3] > 128:
-            raise ValueError(f"head_dim must be <= 128, got {query.shape[3]}")
+        if query.shape[3] > 256:
+            raise ValueError(f"head_dim must be <= 256, got {query.shape[3]}")
 
     def attention_forward_with_lse(self, query, key, value, causal: bool = False):
         """Returns (output, lse) -- vulkan.py:824-889 / src/lib.zig:765."""

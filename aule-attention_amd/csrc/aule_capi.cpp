@@ -41,7 +41,7 @@ struct DevTensor {
     void* ptr = nullptr;      // device memory, rows padded to `pitch` floats
     uint32_t shape[4] = {0, 0, 0, 0};
     uint64_t count = 0;       // logical element count (B*H*S*D)
-    uint32_t pitch = 0;       // padded head_dim (32 / 64 / 128, or D itself if D > 128)
+    uint32_t pitch = 0;       // padded head_dim (32 / 64 / 128 / 256, or D itself if D > 256)
     bool used = false;
 };
 
@@ -68,6 +68,7 @@ uint32_t pad_dim(uint32_t d) {
     if (d <= 32) return 32;
     if (d <= 64) return 64;
     if (d <= 128) return 128;
+    if (d <= 256) return 256;
     return d;
 }
 
@@ -433,8 +434,8 @@ int32_t aule_attention_forward_gpu(aule_tensor_handle qh, aule_tensor_handle kh,
         set_error("Attention failed: error.ShapeMismatch");
         return -3;
     }
-    if (D > 128) {
-        set_error("Attention failed: error.HeadDimTooLarge (head_dim %u > 128)", D);
+    if (D > 256) {
+        set_error("Attention failed: error.HeadDimTooLarge (head_dim %u > 256)", D);
         return -3;
     }
     if (q->count == 0) return 0;
@@ -510,8 +511,8 @@ static int32_t forward_host(const float* query, const float* key, const float* v
         set_error("Library not initialized. Call aule_init() first.");
         return -1;
     }
-    if (D > 128) {
-        set_error("Attention failed: error.HeadDimTooLarge (head_dim %u > 128)", D);
+    if (D > 256) {
+        set_error("Attention failed: error.HeadDimTooLarge (head_dim %u > 256)", D);
         return -4;
     }
     const size_t rows = (size_t)B * H * S;
@@ -564,8 +565,8 @@ int32_t aule_attention_backward(const float* query, const float* key, const floa
         set_error("Library not initialized. Call aule_init() first.");
         return -1;
     }
-    if (D > 128) {
-        set_error("Backward failed: error.HeadDimTooLarge (head_dim %u > 128)", D);
+    if (D > 256) {
+        set_error("Backward failed: error.HeadDimTooLarge (head_dim %u > 256)", D);
         return -4;
     }
     const size_t rows = (size_t)B * H * S;
@@ -649,8 +650,8 @@ static int check_common(int32_t dtype, uint32_t B, uint32_t Hq, uint32_t Hkv, ui
         set_error("Attention failed: unknown dtype %d", dtype);
         return -3;
     }
-    if (D != 32 && D != 64 && D != 128) {
-        set_error("Attention failed: head_dim %u unsupported (32, 64 or 128; pad to the next size)", D);
+    if (D != 32 && D != 64 && D != 128 && D != 256) {
+        set_error("Attention failed: head_dim %u unsupported (32, 64, 128 or 256; pad to the next size)", D);
         return -3;
     }
     if (Hkv == 0 || Hq % Hkv != 0) {
@@ -1056,7 +1057,7 @@ uint64_t aule_attention_forward_workspace_size(const aule_attn_desc* d) {
     if (d->dtype < 0 || d->dtype > 2 || d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return 0;
     if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0 || d->seq_k == 0) return 0;
     if ((uint64_t)d->batch * d->heads_q * d->seq_q == 0) return 0;
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return 0;
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128 && d->head_dim != 256) return 0;
     if (d->causal == AULE_CAUSAL_BOTTOM_RIGHT && d->seq_k < d->seq_q) return 0;
     FwdArgs a;
     a.q = a.k = a.v = nullptr; a.o = nullptr; a.lse = nullptr;

@@ -1085,7 +1085,7 @@ inline uint64_t delta_bytes(int B, int Hq, int Sq) {
 // AULE_HIP_BWD_DS_CAP_MB (default 8192) bounds the workspace: the batch runs in chunks of as many elements as the caller's buffer holds.
 // What the most recent backward launch of this process ran (aule_hip_debug_last_backward_route; tests pin the mode a shape takes with it)
 std::atomic<int> g_last_bwd_route{0};
-enum { kRouteSpill = 1, kRouteDq4 = 2, kRouteDkv4 = 4, kRouteDqOld = 8, kRouteDkvOld = 16, kRouteF32 = 32, kRouteDkv4K2 = 64 };
+enum { kRouteSpill = 1, kRouteDq4 = 2, kRouteDkv4 = 4, kRouteDqOld = 8, kRouteDkvOld = 16, kRouteF32 = 32, kRouteDkv4K2 = 64, kRouteD256 = 128 };
 
 inline int bwd_mode() {   // 0: auto (by AULE_HIP_BWD_DS_AUTO_MB), 1: recompute, 2: spill wherever applicable
     static const int m = [] {
@@ -1317,6 +1317,8 @@ int set_attr_bwd() {
 
 int launch_bwd_f32(const BwdArgs& a, hipStream_t stream);  // fa_bwd_f32.hip
 int configure_bwd_f32();
+int launch_bwd_d256(const BwdArgs& a, hipStream_t stream);   // fa_bwd_d256_gfx950.hip (head_dim 256, every dtype)
+uint64_t bwd_d256_workspace_bytes(int B, int Hq, int Sq);
 
 // Shared with fa_bwd_f32.hip
 int launch_delta_f32(const BwdArgs& a, hipStream_t stream) {
@@ -1341,12 +1343,14 @@ int launch_delta_f32(const BwdArgs& a, hipStream_t stream) {
 
 // What launch_bwd NEEDS (delta, L', - delta, the head-split partials) ...
 uint64_t bwd_workspace_min_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int causal, int dtype, int device) {
+    if (D == 256) return bwd_d256_workspace_bytes(B, Hq, Sq);
     return bwd_base_bytes(B, Hq, Hkv, Sq, Sk, D, causal, dtype, device);
 }
 // ... and what it WANTS: plus the dS workspace of the 5-matmul backward for as many batch elements as fit the cap (at least one).
 // A caller that passes only the minimum gets the recompute pair.
 // (windowed: the dispatcher keeps windowed problems on the recompute pair -- no dS room is asked for: ADVICE r5)
 uint64_t bwd_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int causal, int dtype, int device, bool windowed) {
+    if (D == 256) return bwd_d256_workspace_bytes(B, Hq, Sq);   // (delta only: no partial planes, no dS workspace)
     uint64_t bytes = bwd_base_bytes(B, Hq, Hkv, Sq, Sk, D, causal, dtype, device);
     const uint64_t pb = windowed ? 0 : spill_bytes_per_batch(B, Hq, Hkv, Sq, Sk, D, causal, dtype);
     if (pb > 0) {
@@ -1360,6 +1364,10 @@ uint64_t bwd_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int 
 int bwd_last_route() { return g_last_bwd_route.load(); }
 
 int launch_bwd(const BwdArgs& a, hipStream_t stream) {
+    if (a.D == 256) {
+        g_last_bwd_route = a.dtype == kF32 ? (kRouteD256 | kRouteF32) : kRouteD256;
+        return launch_bwd_d256(a, stream);
+    }
     if (a.dtype == kF32) { g_last_bwd_route = kRouteF32; return launch_bwd_f32(a, stream); }
     if (a.dtype == kBF16) {
         if (a.D == 128) return launch_bwd_16<Bf16Traits, 128>(a, stream);

@@ -37,6 +37,7 @@ bool fwd_w4_applicable(const FwdArgs& a);
 bool fwd_w4_split_applicable(const FwdArgs& a);            // small grids: pairs cut into key ranges, partials + merge
 int launch_fwd_w4_split(const FwdArgs& a, hipStream_t stream);
 int configure_fwd_w4();
+int launch_fwd_d256(const FwdArgs& a, hipStream_t stream);   // fa_fwd_d256_gfx950.hip (head_dim 256, every dtype)
 
 // AULE_HIP_FWD_KERNEL=pp keeps every tiled problem on the ping-pong kernel (A/B measurements against the one-wave-per-SIMD kernel)
 static int fwd_kernel_choice() {
@@ -98,10 +99,12 @@ static int short_query_route(const FwdArgs& a) {
 // Which kernel launch_fwd() picks for `a` (host logic only, no device work): 0 fp32, 1 ping-pong, 4 split-KV,
 // 5 ping-pong kernel with packed rows + KV splits, 7 one-wave-per-SIMD kernel with every pair of causal Q blocks (every
 // non-causal block) cut into key ranges (small grids; partials + merge), 8 one-wave-per-SIMD kernel (4 x 64 rows)
+// 9 the head_dim 256 kernel (16-bit; fp32 at D = 256 stays route 0, run by the same file's fp32 instance)
 // (2, 3 and 6 were the removed in-wave, lock-step and two-waves-per-SIMD stream kernels).  Lets the tests pin the path a shape
 // exercises.
 int fwd_route(const FwdArgs& a) {
     if (a.dtype == kF32) return 0;
+    if (a.D == 256) return 9;
     const int sq = short_query_route(a);
     if (sq) return sq;
     if (use_w4_split(a)) return 7;
@@ -129,6 +132,7 @@ uint64_t paged_workspace_bytes(PagedArgs a) {
 int launch_fwd(const FwdArgs& a, hipStream_t stream) {
     if (a.query_ws != nullptr) *a.query_ws = 0;
     if (a.rope_cos != nullptr && !fwd_rope_fusable(a)) return -1;   // only the one-wave-per-SIMD kernel rotates Q itself
+    if (a.D == 256) return launch_fwd_d256(a, stream);
     const int sq = a.dtype == kF32 ? 0 : short_query_route(a);
     if (sq == 4) return launch_fwd_splitkv(a, stream);
     if (sq == 5) return launch_fwd_pp_split(a, stream);

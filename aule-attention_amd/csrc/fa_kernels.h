@@ -183,7 +183,7 @@ uint64_t paged_workspace_bytes(PagedArgs a);   // 0 fp32, 1 ping-pong, 2 in-wave
 int launch_bwd(const BwdArgs& a, hipStream_t stream);
 // bit mask of what the most recent launch_bwd of this process ran: 1 the 5-matmul mode (delta pass + spilling dK/dV kernel + dQ = dS K),
 // 2 / 4 the one-wave-per-SIMD dQ / dK/dV kernel, 8 / 16 their two-waves-per-SIMD predecessors, 32 the fp32 kernels, 64 (with 4) the D = 64
-// dK/dV instance with two key blocks per wave; 0 before the first
+// dK/dV instance with two key blocks per wave, 128 the head_dim 256 kernels (fa_bwd_d256_gfx950.hip; with 32 for fp32); 0 before the first
 int bwd_last_route();
 
 // Bytes of device workspace launch_bwd needs: delta [B,Hq,Sq] fp32, plus (16-bit GQA/MQA problems that

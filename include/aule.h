@@ -119,7 +119,7 @@ typedef enum aule_dtype {
 
 /* All tensors row-major contiguous: Q,O,dO,dQ [B,Hq,Sq,D]; K,V,dK,dV [B,Hkv,Sk,D];
  * LSE [B,Hq,Sq] fp32.  Pointers are DEVICE pointers on `device`.
- * head_dim in {32, 64, 128}; heads_q % heads_kv == 0.
+ * head_dim in {32, 64, 128, 256} (paged decode: {32, 64, 128}); heads_q % heads_kv == 0.
  * `causal`: 0 = none; 1 = top-left aligned (query i sees keys j <= i), the rule of
  * every reference implementation; 2 = bottom-right aligned (query i sits at position
  * i + seq_k - seq_q, i.e. the last query sees every key; needs seq_k >= seq_q) --
@@ -259,12 +259,14 @@ uint64_t aule_attention_backward_workspace_size(const aule_attn_bwd_desc* desc);
 /* Build/ABI identification: "aule-hip gfx950 <abi>" */
 const char* aule_hip_build_info(void);
 /* Debug (not part of the drop-in ABI): forward kernel aule_attention_forward_ex would pick for `desc` --        */
-/* 0 fp32, 1 ping-pong, 4 split-KV, 5 tiled split, 7 one wave per SIMD over key-range pieces, 8 one wave per SIMD; -3 bad. */
+/* 0 fp32, 1 ping-pong, 4 split-KV, 5 tiled split, 7 one wave per SIMD over key-range pieces, 8 one wave per SIMD,  */
+/* 9 the head_dim 256 kernel (16-bit); -3 bad.                                                                       */
 /* Host logic only, no aule_init().                                                                                  */
 int32_t aule_hip_debug_forward_route(const aule_attn_desc* desc);
 /* Debug: bit mask of the kernels the most recent backward launch of this process ran -- 1 the 5-matmul mode (delta pass, dK/dV kernel  */
 /* spilling its dS, dQ = dS K), 2 / 4 the one-wave-per-SIMD dQ / dK/dV kernel, 8 / 16 their two-waves-per-SIMD predecessors, 32 the    */
-/* fp32 kernels, 64 (with 4) the D = 64 dK/dV instance with two key blocks per wave; 0 before the first backward.  Lets a test assert  */
+/* fp32 kernels, 64 (with 4) the D = 64 dK/dV instance with two key blocks per wave, 128 the head_dim 256 kernels (with 32 for fp32);  */
+/* 0 before the first backward.  Lets a test assert                                                                                   */
 /* the mode a shape takes by itself.                                                                                      */
 int32_t aule_hip_debug_last_backward_route(void);
 /* Debug: the causal-split plan of route 7 (small causal grids) as integers -- out = {pieces n, pairs, then per pair of   */
