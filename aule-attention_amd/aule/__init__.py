@@ -126,14 +126,19 @@ def flash_attention(query, key, value, rot_cos=None, rot_sin=None, causal=True, 
 attention = flash_attention
 
 
-def flash_attention_paged_amd(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1):
+def flash_attention_paged_amd(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1,
+                              k_scale=None, v_scale=None):
     """PagedAttention for the decode phase (one query token per sequence, vLLM-style block tables); same name,
     arguments and result as the reference's export (python/aule/triton_flash_amd.py:656-737, __init__.py:59):
 
         q [batch, heads_q, head_dim]; k_cache, v_cache [num_blocks, block_size, heads_kv, head_dim];
         block_tables [batch, max_blocks_per_seq]; context_lens [batch]  ->  [batch, heads_q, head_dim]
 
-    window_size > 0 keeps only the last window_size positions of each sequence.  fp16 / bf16 ROCm tensors."""
+    window_size > 0 keeps only the last window_size positions of each sequence.  fp16 / bf16 ROCm tensors.
+
+    The caches may instead both be torch.float8_e4m3fn (OCP FP8; see quantize_kv_cache_fp8) with an fp16 / bf16 query:
+    then K = k_scale[hk] * k_cache and V = v_scale[hk] * v_cache, k_scale / v_scale each None (1.0), a float, a 0-d
+    tensor or a [heads_kv] tensor.  float8_e4m3fnuz / float8_e5m2 caches and scales with a 16-bit cache are ValueErrors."""
     try:
         import torch  # noqa: F401
     except ImportError as e:
@@ -141,7 +146,15 @@ def flash_attention_paged_amd(q, k_cache, v_cache, block_tables, context_lens, s
     if not q.is_cuda:
         raise AuleError("aule (HIP build): paged decode needs ROCm device tensors; there is no CPU fallback")
     from ._torch import paged_decode
-    return paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=scale, window_size=window_size)
+    return paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=scale, window_size=window_size,
+                        k_scale=k_scale, v_scale=v_scale)
+
+
+def quantize_kv_cache_fp8(cache, per_head=True):
+    """(cache_fp8, scale) for the FP8 paged decode: float8_e4m3fn codes and a [heads_kv] fp32 scale = amax / 448 per KV
+    head (per_head=False: one value, repeated), saturating.  Plain torch ops; works on CPU tensors."""
+    from ._torch import quantize_kv_cache_fp8 as impl
+    return impl(cache, per_head=per_head)
 
 
 flash_attention_paged = flash_attention_paged_amd
@@ -334,7 +347,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "quantize_kv_cache_fp8",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

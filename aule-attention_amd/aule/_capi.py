@@ -105,6 +105,14 @@ class PagedDesc(ctypes.Structure):
     ]
 
 
+class PagedFp8Desc(ctypes.Structure):
+    """struct aule_paged_fp8_desc (include/aule.h): aule_paged_desc plus the two per-KV-head scale arrays."""
+    _fields_ = list(PagedDesc._fields_) + [
+        ("k_scale", ctypes.c_void_p),
+        ("v_scale", ctypes.c_void_p),
+    ]
+
+
 class RopeDesc(ctypes.Structure):
     """struct aule_rope_desc (include/aule.h)."""
     _fields_ = [
@@ -194,6 +202,8 @@ SIGNATURES = [
     ("aule_attention_forward_rope_fusable", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(AttnRope)]),
     ("aule_attention_forward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(AttnDesc)]),
     ("aule_attention_paged_decode_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedDesc)]),
+    ("aule_attention_paged_decode_fp8_ex", _I32, [ctypes.POINTER(PagedFp8Desc)]),
+    ("aule_attention_paged_decode_fp8_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedFp8Desc)]),
     ("aule_peer_alloc", _I32, [_I32, _U64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(IpcHandle)]),
     ("aule_peer_free", _I32, [_I32, ctypes.c_void_p]),
     ("aule_peer_open", _I32, [_I32, ctypes.POINTER(IpcHandle), ctypes.POINTER(ctypes.c_void_p)]),

@@ -365,7 +365,43 @@ def flash_attention_rope_hip(q, k, v, cos, sin, causal=True, scale=None, window=
     return out if out.dtype == orig_dtype else out.to(orig_dtype)
 
 
-def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1):
+FP8_MAX = 448.0   # largest finite OCP e4m3fn value
+
+
+def quantize_kv_cache_fp8(cache, per_head=True):
+    """Quantise a [num_blocks, block_size, heads_kv, head_dim] cache to OCP FP8 e4m3fn for the FP8 paged decode:
+    returns (cache_fp8, scale) with scale [heads_kv] fp32 on the cache's device and cache ~= scale[hk] * cache_fp8.
+
+    scale = amax / 448 per KV head (per_head=False: one value from the whole cache, repeated; 1.0 where everything is
+    zero).  Values are divided by the scale and clamped to +-448 BEFORE the cast: torch's cast to float8_e4m3fn does not
+    saturate (465.0 becomes NaN).  Plain torch ops, no kernel; works on CPU tensors."""
+    if cache.dim() != 4:
+        raise ValueError("expected a cache of shape [num_blocks, block_size, heads_kv, head_dim]")
+    x = cache.float()
+    Hkv = x.shape[2]
+    if per_head:
+        amax = x.abs().amax(dim=(0, 1, 3)) if x.numel() else x.new_zeros(Hkv)
+    else:
+        amax = (x.abs().amax() if x.numel() else x.new_zeros(())).expand(Hkv)
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax)).contiguous()
+    y = (x / scale.view(1, 1, Hkv, 1)).clamp_(-FP8_MAX, FP8_MAX)
+    return y.to(torch.float8_e4m3fn), scale
+
+
+def _fp8_scale(s, Hkv, device, name):
+    """None / float / 0-d tensor / [heads_kv] tensor -> [heads_kv] fp32 on `device`, without a device->host copy."""
+    if s is None:
+        s = 1.0
+    if not torch.is_tensor(s):
+        return torch.full((Hkv,), float(s), dtype=torch.float32, device=device)
+    if s.dim() == 0 or s.shape == (1,):
+        return s.to(device=device, dtype=torch.float32).reshape(1).expand(Hkv).contiguous()
+    if s.shape != (Hkv,):
+        raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
+    return s.to(device=device, dtype=torch.float32).contiguous()
+
+
+def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1, k_scale=None, v_scale=None):
     """Paged-KV decode on the HIP backend; counterpart of flash_attention_paged_amd
     (python/aule/triton_flash_amd.py:656-737), same argument meaning:
 
@@ -373,7 +409,12 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, wi
         k_cache      [num_blocks, block_size, heads_kv, head_dim]     v_cache: same
         block_tables [batch, max_blocks_per_seq] integer, context_lens [batch] integer
     Returns [batch, heads_q, head_dim].  No device->host synchronisation (the reference reads
-    context_lens.max() on the host)."""
+    context_lens.max() on the host).
+
+    The caches are either of the query's dtype or both torch.float8_e4m3fn (OCP FP8, the format gfx950 converts in
+    hardware).  Then K = k_scale[hk] * float(k_cache) and V = v_scale[hk] * float(v_cache), with k_scale / v_scale each
+    None (1.0), a float, a 0-d tensor or a [heads_kv] tensor; they reach the kernel as device arrays.  All argument
+    errors are ValueErrors raised before the device is touched."""
     if q.dim() == 4:
         if q.shape[2] != 1:
             raise ValueError("PagedAttention only supports single query token")
@@ -386,10 +427,24 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, wi
         raise ValueError(f"head_dim mismatch: query={D}, cache={Dk}")
     if Hq % Hkv != 0:
         raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
-    if q.dtype not in (torch.float16, torch.bfloat16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise ValueError("paged decode runs in fp16 or bf16 (query and caches in the same dtype)")
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"k_cache ({k_cache.dtype}) and v_cache ({v_cache.dtype}) must have the same dtype")
+    other_fp8 = tuple(t for t in (getattr(torch, n, None) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz"))
+                      if t is not None)
+    if k_cache.dtype in other_fp8:
+        raise ValueError(f"{k_cache.dtype} caches are not supported: the FP8 paged decode takes torch.float8_e4m3fn only "
+                         "(gfx950 converts OCP e4m3fn in hardware; e4m3fnuz is MI300X's encoding, e5m2 is not built)")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if q.dtype not in (torch.float16, torch.bfloat16) or (not fp8 and k_cache.dtype != q.dtype):
+        raise ValueError("paged decode runs in fp16 or bf16 (query and caches in the same dtype, or float8_e4m3fn caches "
+                         "with an fp16 / bf16 query)")
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError("k_scale / v_scale apply to float8_e4m3fn caches only; a 16-bit cache holds the values themselves")
     if D not in PAGED_HEAD_DIMS:
         raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS} for paged decode, got {D}")
+    if fp8:
+        ks = _fp8_scale(k_scale, Hkv, q.device, "k_scale")
+        vs = _fp8_scale(v_scale, Hkv, q.device, "v_scale")
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     lib = _capi.get_lib()
@@ -403,8 +458,8 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, wi
     out = torch.empty_like(q)
     if B * Hq == 0:
         return out
-    d = _capi.PagedDesc()
-    d.struct_size = ctypes.sizeof(_capi.PagedDesc)
+    d = _capi.PagedFp8Desc() if fp8 else _capi.PagedDesc()
+    d.struct_size = ctypes.sizeof(d)
     d.dtype = _DTYPES[q.dtype]
     d.batch, d.heads_q, d.heads_kv, d.head_dim = B, Hq, Hkv, D
     d.block_size, d.max_blocks = block_size, bt.shape[1]
@@ -413,9 +468,14 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, wi
     d.device = q.device.index if q.device.index is not None else torch.cuda.current_device()
     d.stream = _stream_ptr(q.device)
     d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
-    ws = _workspace(lib.aule_attention_paged_decode_workspace_size(ctypes.byref(d)), q.device)
+    ws_size = lib.aule_attention_paged_decode_fp8_workspace_size if fp8 else lib.aule_attention_paged_decode_workspace_size
+    ws = _workspace(ws_size(ctypes.byref(d)), q.device)
     if ws is not None:
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     d.block_tables, d.context_lens = bt.data_ptr(), cl.data_ptr()
-    _capi.check(lib.aule_attention_paged_decode_ex(ctypes.byref(d)), "aule_attention_paged_decode_ex")
+    if fp8:
+        d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
+        _capi.check(lib.aule_attention_paged_decode_fp8_ex(ctypes.byref(d)), "aule_attention_paged_decode_fp8_ex")
+    else:
+        _capi.check(lib.aule_attention_paged_decode_ex(ctypes.byref(d)), "aule_attention_paged_decode_ex")
     return out

@@ -30,6 +30,10 @@ static_assert(sizeof(aule_attn_desc) == 112 && offsetof(aule_attn_desc, lse) == 
               "aule_attn_desc layout is part of the ABI");
 static_assert(sizeof(aule_paged_desc) == 120 && offsetof(aule_paged_desc, workspace) == 104,
               "aule_paged_desc layout is part of the ABI");
+static_assert(sizeof(aule_paged_fp8_desc) == 136 && offsetof(aule_paged_fp8_desc, stream) == 48 &&
+                  offsetof(aule_paged_fp8_desc, workspace) == 104 && offsetof(aule_paged_fp8_desc, k_scale) == 120 &&
+                  offsetof(aule_paged_fp8_desc, v_scale) == 128,
+              "aule_paged_fp8_desc layout is part of the ABI");
 static_assert(sizeof(aule_attn_bwd_desc) == 144, "aule_attn_bwd_desc layout is part of the ABI");
 
 namespace {
@@ -872,6 +876,69 @@ int32_t aule_attention_paged_decode_ex(const aule_paged_desc* d) {
     return 0;
 }
 
+// shape checks shared by the FP8 paged entry and its workspace query (same rules as the 16-bit entry):
+// 0 fine, 1 dtype, 2 head_dim, 3 head ratio, 4 block_size / max_blocks
+static int paged_fp8_shape_error(const aule_paged_fp8_desc* d) {
+    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return 1;
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return 2;
+    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return 3;
+    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return 4;
+    return 0;
+}
+
+static void fill_paged_fp8_args(const aule_paged_fp8_desc* d, aule_hip::PagedArgs& a) {
+    a.q = d->q; a.k_cache = d->k_cache; a.v_cache = d->v_cache; a.out = d->out;
+    a.block_tables = d->block_tables; a.context_lens = d->context_lens;
+    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
+    a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
+    a.scale = resolve_scale(d->scale, d->head_dim);
+    a.window = d->window_size;
+    a.dtype = d->dtype;
+    a.cache_kind = aule_hip::kCacheFp8E4M3;
+    a.k_scale = d->k_scale; a.v_scale = d->v_scale;
+}
+
+int32_t aule_attention_paged_decode_fp8_ex(const aule_paged_fp8_desc* d) {
+    RoctxRange range("aule.paged_decode_fp8");
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_init) {
+        set_error("Library not initialized. Call aule_init() first.");
+        return -1;
+    }
+    if (d == nullptr || d->struct_size != sizeof(aule_paged_fp8_desc)) {
+        set_error("Paged FP8 attention failed: bad descriptor (struct_size mismatch)");
+        return -3;
+    }
+    if (const int bad = paged_fp8_shape_error(d)) {
+        if (bad == 1) set_error("Paged FP8 attention failed: dtype (of q / out) must be fp16 or bf16");
+        else if (bad == 2) set_error("Paged FP8 attention failed: head_dim %u unsupported (32, 64 or 128)", d->head_dim);
+        else if (bad == 3) set_error("Paged FP8 attention failed: heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
+        else set_error("Paged FP8 attention failed: bad block_size / max_blocks");
+        return -3;
+    }
+    if ((uint64_t)d->batch * d->heads_q == 0) return 0;
+    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->out) {
+        set_error("Paged FP8 attention failed: null tensor pointer");
+        return -3;
+    }
+    if (!d->k_scale || !d->v_scale) {
+        set_error("Paged FP8 attention failed: null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)");
+        return -3;
+    }
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    aule_hip::PagedArgs a;
+    fill_paged_fp8_args(d, a);
+    a.ws = d->workspace; a.ws_bytes = d->workspace ? d->workspace_bytes : 0;
+    rc = aule_hip::launch_paged_decode_fp8(a, (hipStream_t)d->stream);
+    if (rc != 0) {
+        set_error("Paged FP8 attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
+        return -4;
+    }
+    return 0;
+}
+
 int32_t aule_rope_ex(const aule_rope_desc* d) {
     RoctxRange range("aule.rope");
     std::lock_guard<std::mutex> lk(g_mu);
@@ -1085,6 +1152,18 @@ uint64_t aule_attention_paged_decode_workspace_size(const aule_paged_desc* d) {
     a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
     a.scale = 1.0f; a.window = d->window_size; a.dtype = d->dtype;
     return aule_hip::paged_workspace_bytes(a);
+}
+
+uint64_t aule_attention_paged_decode_fp8_workspace_size(const aule_paged_fp8_desc* d) {
+    if (d == nullptr || d->struct_size != sizeof(aule_paged_fp8_desc)) return 0;
+    if (paged_fp8_shape_error(d) != 0) return 0;
+    if ((uint64_t)d->batch * d->heads_q == 0) return 0;
+    aule_hip::PagedArgs a;
+    fill_paged_fp8_args(d, a);
+    a.q = a.k_cache = a.v_cache = nullptr; a.out = nullptr; a.block_tables = nullptr; a.context_lens = nullptr;
+    a.k_scale = a.v_scale = nullptr;
+    a.scale = 1.0f;
+    return aule_hip::paged_fp8_workspace_bytes(a);
 }
 
 #ifdef AULE_DEBUG_HOOKS

@@ -204,6 +204,37 @@ int32_t aule_attention_paged_decode_ex(const aule_paged_desc* desc);
 uint64_t aule_attention_forward_workspace_size(const aule_attn_desc* desc);
 uint64_t aule_attention_paged_decode_workspace_size(const aule_paged_desc* desc);
 
+/* Paged-KV decode over an FP8 cache (additive).  k_cache / v_cache hold OCP FP8 e4m3fn codes, one byte per element   */
+/* (the format gfx950 converts in hardware; MI300X's e4m3fnuz and e5m2 are not accepted), q and out stay 16-bit:      */
+/*     K[pos, hk, :] = k_scale[hk] * float(k_cache[block, off, hk, :])    V[pos, hk, :] = v_scale[hk] * float(v_cache[...]) */
+/* and the result is aule_attention_paged_decode_ex's on that K / V.  The scales are device arrays read by the kernel */
+/* (no host synchronisation; safe under graph capture).  Every other field means what it means in aule_paged_desc.   */
+typedef struct aule_paged_fp8_desc {
+    uint32_t struct_size;      /* = sizeof(aule_paged_fp8_desc) = 136 */
+    int32_t dtype;             /* type of q / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 (the caches are e4m3fn by definition) */
+    uint32_t batch, heads_q, heads_kv, head_dim;   /* head_dim 32, 64 or 128 */
+    uint32_t block_size;
+    uint32_t max_blocks;
+    float scale;               /* 0 -> 1/sqrt(head_dim) */
+    int32_t window_size;
+    int32_t device;
+    void* stream;              /* offset 48 */
+    const void* q;             /* [batch, heads_q, head_dim], 16-bit */
+    const void* k_cache;       /* [num_blocks, block_size, heads_kv, head_dim] e4m3fn bytes */
+    const void* v_cache;       /* same layout */
+    const int32_t* block_tables;
+    const int32_t* context_lens;
+    void* out;                 /* [batch, heads_q, head_dim], 16-bit */
+    void* workspace;           /* offset 104; optional, size from aule_attention_paged_decode_fp8_workspace_size() */
+    uint64_t workspace_bytes;
+    const float* k_scale;      /* offset 120; [heads_kv] fp32, device */
+    const float* v_scale;      /* offset 128; [heads_kv] fp32, device */
+} aule_paged_fp8_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments (null scale pointers included); -4 launch failure. */
+int32_t aule_attention_paged_decode_fp8_ex(const aule_paged_fp8_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  Same plan as the 16-bit call of the same shape. */
+uint64_t aule_attention_paged_decode_fp8_workspace_size(const aule_paged_fp8_desc* desc);
+
 /* Rotary position embedding pass (additive; SURVEY.md 8f row N1, second half).  Replaces the rotation the           */
 /* reference fuses into its kernels: python/aule/triton_flash.py:32-52,:112-131,:165-180 (layout HALF) and            */
 /* shaders/attention_f32.comp:98-111,:132-145 (layout INTERLEAVED).  x is [rows_bh, seq, head_dim] with               */

@@ -21,6 +21,7 @@ echo "--- backward alone"
 python tools/bwd_ab.py 2>&1 | grep -v amdgpu
 echo "--- decode / paged decode"
 python tools/bench_paged.py 2>&1 | tail -6
+python tools/bench_paged.py --fp8 2>&1 | grep -v amdgpu   # FP8 (e4m3fn) cache vs 16-bit, alternated
 python tools/bench_decode_ws.py 2>&1 | tail -6
 echo "--- RoPE + attention: fused query rotation vs two passes (tools/rope_ab.py)"
 python tools/rope_ab.py 2>&1 | grep -v amdgpu
