@@ -34,6 +34,10 @@ static_assert(sizeof(aule_paged_fp8_desc) == 136 && offsetof(aule_paged_fp8_desc
                   offsetof(aule_paged_fp8_desc, workspace) == 104 && offsetof(aule_paged_fp8_desc, k_scale) == 120 &&
                   offsetof(aule_paged_fp8_desc, v_scale) == 128,
               "aule_paged_fp8_desc layout is part of the ABI");
+static_assert(offsetof(aule_paged_fp8_desc, q) == offsetof(aule_paged_desc, q) &&
+                  offsetof(aule_paged_fp8_desc, workspace_bytes) == offsetof(aule_paged_desc, workspace_bytes) &&
+                  offsetof(aule_paged_fp8_desc, k_scale) == sizeof(aule_paged_desc),
+              "aule_paged_fp8_desc starts with aule_paged_desc (the paged entry points read both through that prefix)");
 static_assert(sizeof(aule_attn_bwd_desc) == 144, "aule_attn_bwd_desc layout is part of the ABI");
 
 namespace {
@@ -824,42 +828,22 @@ int32_t aule_attention_forward_rope_fusable(const aule_attn_desc* d, const aule_
     return fill_rope_args(rope, d->head_dim, a) && aule_hip::fwd_rope_fusable(a) ? 1 : 0;
 }
 
-int32_t aule_attention_paged_decode_ex(const aule_paged_desc* d) {
-    RoctxRange range("aule.paged_decode");
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_init) {
-        set_error("Library not initialized. Call aule_init() first.");
-        return -1;
-    }
-    if (d == nullptr || d->struct_size != sizeof(aule_paged_desc)) {
-        set_error("Paged attention failed: bad descriptor (struct_size mismatch)");
-        return -3;
-    }
-    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) {
-        set_error("Paged attention failed: dtype must be fp16 or bf16");
-        return -3;
-    }
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) {
-        set_error("Paged attention failed: head_dim %u unsupported (32, 64 or 128)", d->head_dim);
-        return -3;
-    }
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) {
-        set_error("Paged attention failed: heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
-        return -3;
-    }
-    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) {
-        set_error("Paged attention failed: bad block_size / max_blocks");
-        return -3;
-    }
-    if ((uint64_t)d->batch * d->heads_q == 0) return 0;
-    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->out) {
-        set_error("Paged attention failed: null tensor pointer");
-        return -3;
-    }
-    DeviceGuard g(d->device);
-    int rc = ensure_configured();
-    if (rc) return rc;
-    aule_hip::PagedArgs a;
+// The four paged entry points.  aule_paged_fp8_desc is aule_paged_desc field for field plus the two scale pointers (the
+// layout asserts at the top of this file), so both kinds are checked and read through the common prefix.
+static const aule_paged_desc* paged_prefix(const aule_paged_fp8_desc* d) { return reinterpret_cast<const aule_paged_desc*>(d); }
+
+// 0 fine, 1 descriptor, 2 dtype, 3 head_dim, 4 head ratio, 5 block_size / max_blocks
+static int paged_shape_error(const aule_paged_desc* d, bool fp8) {
+    if (d == nullptr || d->struct_size != (fp8 ? sizeof(aule_paged_fp8_desc) : sizeof(aule_paged_desc))) return 1;
+    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return 2;
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return 3;
+    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return 4;
+    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return 5;
+    return 0;
+}
+
+// (`d` passed paged_shape_error: an FP8 descriptor really is one)
+static void fill_paged_args(const aule_paged_desc* d, bool fp8, aule_hip::PagedArgs& a) {
     a.q = d->q; a.k_cache = d->k_cache; a.v_cache = d->v_cache; a.out = d->out;
     a.block_tables = d->block_tables; a.context_lens = d->context_lens;
     a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
@@ -868,75 +852,58 @@ int32_t aule_attention_paged_decode_ex(const aule_paged_desc* d) {
     a.window = d->window_size;
     a.dtype = d->dtype;
     a.ws = d->workspace; a.ws_bytes = d->workspace ? d->workspace_bytes : 0;
+    if (fp8) {
+        const aule_paged_fp8_desc* d8 = reinterpret_cast<const aule_paged_fp8_desc*>(d);
+        a.cache_kind = aule_hip::kCacheFp8E4M3;
+        a.k_scale = d8->k_scale; a.v_scale = d8->v_scale;
+    }
+}
+
+static int32_t paged_decode_impl(const aule_paged_desc* d, bool fp8) {
+    const char* const what = fp8 ? "Paged FP8 attention" : "Paged attention";
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_init) {
+        set_error("Library not initialized. Call aule_init() first.");
+        return -1;
+    }
+    if (const int bad = paged_shape_error(d, fp8)) {
+        if (bad == 1) set_error("%s failed: bad descriptor (struct_size mismatch)", what);
+        else if (bad == 2) set_error("%s failed: dtype%s must be fp16 or bf16", what, fp8 ? " (of q / out)" : "");
+        else if (bad == 3) set_error("%s failed: head_dim %u unsupported (32, 64 or 128)", what, d->head_dim);
+        else if (bad == 4) set_error("%s failed: heads_q (%u) must be divisible by heads_kv (%u)", what, d->heads_q, d->heads_kv);
+        else set_error("%s failed: bad block_size / max_blocks", what);
+        return -3;
+    }
+    if ((uint64_t)d->batch * d->heads_q == 0) return 0;
+    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->out) {
+        set_error("%s failed: null tensor pointer", what);
+        return -3;
+    }
+    aule_hip::PagedArgs a;
+    fill_paged_args(d, fp8, a);
+    if (fp8 && (!a.k_scale || !a.v_scale)) {
+        set_error("%s failed: null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)", what);
+        return -3;
+    }
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
     rc = aule_hip::launch_paged_decode(a, (hipStream_t)d->stream);
     if (rc != 0) {
-        set_error("Paged attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
+        set_error("%s failed: %s", what, rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
         return -4;
     }
     return 0;
 }
 
-// shape checks shared by the FP8 paged entry and its workspace query (same rules as the 16-bit entry):
-// 0 fine, 1 dtype, 2 head_dim, 3 head ratio, 4 block_size / max_blocks
-static int paged_fp8_shape_error(const aule_paged_fp8_desc* d) {
-    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return 1;
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return 2;
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return 3;
-    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return 4;
-    return 0;
-}
-
-static void fill_paged_fp8_args(const aule_paged_fp8_desc* d, aule_hip::PagedArgs& a) {
-    a.q = d->q; a.k_cache = d->k_cache; a.v_cache = d->v_cache; a.out = d->out;
-    a.block_tables = d->block_tables; a.context_lens = d->context_lens;
-    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
-    a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
-    a.scale = resolve_scale(d->scale, d->head_dim);
-    a.window = d->window_size;
-    a.dtype = d->dtype;
-    a.cache_kind = aule_hip::kCacheFp8E4M3;
-    a.k_scale = d->k_scale; a.v_scale = d->v_scale;
+int32_t aule_attention_paged_decode_ex(const aule_paged_desc* d) {
+    RoctxRange range("aule.paged_decode");
+    return paged_decode_impl(d, false);
 }
 
 int32_t aule_attention_paged_decode_fp8_ex(const aule_paged_fp8_desc* d) {
     RoctxRange range("aule.paged_decode_fp8");
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_init) {
-        set_error("Library not initialized. Call aule_init() first.");
-        return -1;
-    }
-    if (d == nullptr || d->struct_size != sizeof(aule_paged_fp8_desc)) {
-        set_error("Paged FP8 attention failed: bad descriptor (struct_size mismatch)");
-        return -3;
-    }
-    if (const int bad = paged_fp8_shape_error(d)) {
-        if (bad == 1) set_error("Paged FP8 attention failed: dtype (of q / out) must be fp16 or bf16");
-        else if (bad == 2) set_error("Paged FP8 attention failed: head_dim %u unsupported (32, 64 or 128)", d->head_dim);
-        else if (bad == 3) set_error("Paged FP8 attention failed: heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
-        else set_error("Paged FP8 attention failed: bad block_size / max_blocks");
-        return -3;
-    }
-    if ((uint64_t)d->batch * d->heads_q == 0) return 0;
-    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->out) {
-        set_error("Paged FP8 attention failed: null tensor pointer");
-        return -3;
-    }
-    if (!d->k_scale || !d->v_scale) {
-        set_error("Paged FP8 attention failed: null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)");
-        return -3;
-    }
-    DeviceGuard g(d->device);
-    int rc = ensure_configured();
-    if (rc) return rc;
-    aule_hip::PagedArgs a;
-    fill_paged_fp8_args(d, a);
-    a.ws = d->workspace; a.ws_bytes = d->workspace ? d->workspace_bytes : 0;
-    rc = aule_hip::launch_paged_decode_fp8(a, (hipStream_t)d->stream);
-    if (rc != 0) {
-        set_error("Paged FP8 attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
-        return -4;
-    }
-    return 0;
+    return paged_decode_impl(paged_prefix(d), true);
 }
 
 int32_t aule_rope_ex(const aule_rope_desc* d) {
@@ -1139,31 +1106,18 @@ uint64_t aule_attention_forward_workspace_size(const aule_attn_desc* d) {
     return aule_hip::fwd_workspace_bytes(a);
 }
 
-uint64_t aule_attention_paged_decode_workspace_size(const aule_paged_desc* d) {
-    if (d == nullptr || d->struct_size != sizeof(aule_paged_desc)) return 0;
-    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return 0;
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return 0;
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return 0;
-    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return 0;
-    if ((uint64_t)d->batch * d->heads_q == 0) return 0;
+// (a dry run of the launcher: it reads the shape, none of the pointers)
+static uint64_t paged_workspace_impl(const aule_paged_desc* d, bool fp8) {
+    if (paged_shape_error(d, fp8) != 0 || (uint64_t)d->batch * d->heads_q == 0) return 0;
     aule_hip::PagedArgs a;
-    a.q = a.k_cache = a.v_cache = nullptr; a.out = nullptr; a.block_tables = nullptr; a.context_lens = nullptr;
-    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
-    a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
-    a.scale = 1.0f; a.window = d->window_size; a.dtype = d->dtype;
+    fill_paged_args(d, fp8, a);
     return aule_hip::paged_workspace_bytes(a);
 }
 
+uint64_t aule_attention_paged_decode_workspace_size(const aule_paged_desc* d) { return paged_workspace_impl(d, false); }
+
 uint64_t aule_attention_paged_decode_fp8_workspace_size(const aule_paged_fp8_desc* d) {
-    if (d == nullptr || d->struct_size != sizeof(aule_paged_fp8_desc)) return 0;
-    if (paged_fp8_shape_error(d) != 0) return 0;
-    if ((uint64_t)d->batch * d->heads_q == 0) return 0;
-    aule_hip::PagedArgs a;
-    fill_paged_fp8_args(d, a);
-    a.q = a.k_cache = a.v_cache = nullptr; a.out = nullptr; a.block_tables = nullptr; a.context_lens = nullptr;
-    a.k_scale = a.v_scale = nullptr;
-    a.scale = 1.0f;
-    return aule_hip::paged_fp8_workspace_bytes(a);
+    return paged_workspace_impl(paged_prefix(d), true);
 }
 
 #ifdef AULE_DEBUG_HOOKS

@@ -122,13 +122,6 @@ uint64_t fwd_workspace_bytes(FwdArgs a) {
     return bytes;
 }
 
-uint64_t paged_workspace_bytes(PagedArgs a) {
-    uint64_t bytes = 0;
-    a.query_ws = &bytes;
-    (void)launch_paged_decode(a, nullptr);
-    return bytes;
-}
-
 int launch_fwd(const FwdArgs& a, hipStream_t stream) {
     if (a.query_ws != nullptr) *a.query_ws = 0;
     if (a.rope_cos != nullptr && !fwd_rope_fusable(a)) return -1;   // only the one-wave-per-SIMD kernel rotates Q itself

@@ -17,6 +17,15 @@
 // Non-causal only (with the reference's top-left causal rule a short query sequence sees only its first Sq keys,
 // which the tiled kernels handle).  Reference semantics: python/aule/triton_flash_amd.py:97-240 (same math,
 // GQA head map :126-127).
+//
+// ONE kernel body serves three K/V sources: contiguous 16-bit K/V (route 4), a paged 16-bit cache and a paged cache of
+// OCP FP8 e4m3fn codes (one byte per element, what gfx950 speaks; MI300X's e4m3fnuz is a different encoding) with one
+// fp32 dequantisation scale per KV head:  K[pos, hk, :] = k_scale[hk] * float(k_cache[block, off, hk, :]), V likewise.
+// Where the rows come from (PAGED: block table, context_lens, window) and what a row holds (Kv16 / KvFp8 below: K load
+// -> MFMA operands with the matching order of d in the Q fragments, V load -> LDS image, the two scale factors) are
+// the only per-source pieces; indexing, softmax step, PV step and the partial store are written once.
+#include <type_traits>
+
 #include "fa_device.h"
 #include "fa_kernels.h"
 
@@ -29,9 +38,9 @@ struct SplitParams {
     const void* v;
     void* o;
     float* lse;
-    float* part;   // [npart][rows_total][D + 2] fp32: O (un-normalised), m (log2 units), l
+    float* part;   // [npart][rows_total][D + 2] fp32: O (un-normalised, v_scale applied), m (log2 units), l
     int B, Hq, Hkv, Sq, Sk;
-    float c;       // |scale| * log2(e); the sign goes into Q
+    float c;       // softmax factor in log2 units: |scale| log2(e) with the sign in Q (KV::kSignInQ), or the signed product
     int negq;
     int nrt;          // 32-row tiles per (batch, kv-head) unit
     int chunk_tiles;  // 32-key tiles per wave
@@ -42,18 +51,91 @@ struct SplitParams {
     const int* context_lens;   // [B] keys per sequence
     int block_size, max_blocks;
     int window;                // > 0: only the last `window` positions (context_len - 1 - pos < window)
+    const float* k_scale;      // [Hkv] fp32, KvFp8 only
+    const float* v_scale;
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t skv_srd(const void* base, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
 }
 
-template <class T, int D, bool PAGED>
+// ---- what a K/V row holds.  A lane always loads 16 bytes; EB bytes per element decide how many elements that is. ----
+
+// K and V in the query's 16-bit type: a 16-byte load is one MFMA operand (8 elements) and one chunk of the LDS image.
+struct Kv16 {
+    static constexpr int EB = 2;
+    static constexpr bool kSignInQ = true;    // softmax factor |scale| log2(e), a negative scale flips the sign of Q
+    // first d of Q fragment ks in lane half hi
+    static __device__ __forceinline__ int q_d0(int ks, int hi) { return 16 * ks + 8 * hi; }
+    // S^T += K.Q^T for one load: 8 elements, one MFMA step against the load's one Q fragment
+    template <class T>
+    static __device__ __forceinline__ f32x16_t qk(u32x4_t kx, const typename T::v8* qf, f32x16_t acc) {
+        return T::mfma(as_v8<T>(kx), qf[0], acc);
+    }
+    template <class T>
+    static __device__ __forceinline__ void stage_v(char* img, u32x4_t x) { *reinterpret_cast<u32x4_t*>(img) = x; }
+    static __device__ __forceinline__ float k_factor(const SplitParams&, int) { return 1.f; }
+    static __device__ __forceinline__ float v_factor(const SplitParams&, int) { return 1.f; }
+};
+
+// sixteen e4m3fn codes (four dwords) -> elements 0..7 and 8..15 in the 16-bit type, exact
+template <class T>
+__device__ __forceinline__ void cvt16(u32x4_t x, u32x4_t& e0, u32x4_t& e1) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[w], false);
+        const f32x2_t b = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[w], true);
+        const unsigned lo = T::pack2(a[0], a[1]), hi = T::pack2(b[0], b[1]);
+        if (w < 2) {
+            e0[2 * w] = lo;
+            e0[2 * w + 1] = hi;
+        } else {
+            e1[2 * w - 4] = lo;
+            e1[2 * w - 3] = hi;
+        }
+    }
+}
+
+// K and V as OCP e4m3fn codes.  Every finite code is exactly representable in fp16 and in bf16, so a code is converted
+// to the query's 16-bit type WITHOUT its scale (v_cvt_pk_f32_fp8 + one pack: exact, NaN codes stay NaN) and the 16-bit
+// MFMAs are kept -- no FP8 MFMA, no quantisation of Q or P.  The scales stay out of the loop: k_scale[hk] multiplies
+// the logits, so it goes into the softmax factor (a unit is one (batch, kv-head)); v_scale[hk] multiplies the
+// un-normalised O, so it is applied once where the partial is written.  Both are fp32 device values: no host
+// synchronisation, capturable.
+struct KvFp8 {
+    static constexpr int EB = 1;
+    static constexpr bool kSignInQ = false;   // softmax factor = the signed scale log2(e) * k_scale[hk]
+    // A 16-byte load carries 16 elements = two MFMA k-slices, so K needs half as many loads: lane (key, hi) loads chunk
+    // 2j + hi and feeds its low / high 8 elements to MFMA steps 2j / 2j + 1 -- the order of d inside the k dimension is
+    // free as long as the Q fragments use the same permutation: qf[2j + e] holds d = 32j + 16hi + 8e .. +7.
+    static __device__ __forceinline__ int q_d0(int ks, int hi) { return 32 * (ks >> 1) + 16 * hi + 8 * (ks & 1); }
+    template <class T>
+    static __device__ __forceinline__ f32x16_t qk(u32x4_t kx, const typename T::v8* qf, f32x16_t acc) {
+        u32x4_t e0, e1;
+        cvt16<T>(kx, e0, e1);
+        return T::mfma(as_v8<T>(e1), qf[1], T::mfma(as_v8<T>(e0), qf[0], acc));
+    }
+    // V is converted before the LDS write (16 bytes of codes -> 32 bytes = two adjacent chunks of the sub-tiled image),
+    // so the image, the transpose reads and the operand maps are the 16-bit ones.
+    template <class T>
+    static __device__ __forceinline__ void stage_v(char* img, u32x4_t x) {
+        u32x4_t e0, e1;
+        cvt16<T>(x, e0, e1);
+        *reinterpret_cast<u32x4_t*>(img) = e0;
+        *reinterpret_cast<u32x4_t*>(img + 16) = e1;
+    }
+    static __device__ __forceinline__ float k_factor(const SplitParams& p, int hk) { return p.k_scale[hk]; }
+    static __device__ __forceinline__ float v_factor(const SplitParams& p, int hk) { return p.v_scale[hk]; }
+};
+
+template <class T, int D, class KV, bool PAGED>
 __global__ void __launch_bounds__(256) fa_fwd_splitkv_kernel(const SplitParams p) {
     using v8 = typename T::v8;
-    constexpr int RB = D * 2, KS = D / 16, DB = D / 32, CPR = RB / 16;
-    constexpr int VT = 32 * RB;           // one wave's V tile
-    constexpr int NV = (32 * CPR) / 64;   // 16-byte chunks per lane and tile
+    constexpr int EB = KV::EB;
+    constexpr int RB = D * EB;            // bytes of a K/V row
+    constexpr int KS = D / 16, DB = D / 32;
+    constexpr int NL = RB / 32;           // 16-byte loads per lane and tile, of K (a row over the two lane halves) and of V (32 rows over 64 lanes)
+    constexpr int VT = 32 * D * 2;        // one wave's V tile in LDS (16-bit)
     __shared__ __attribute__((aligned(16))) char smem[4 * VT];
 
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
@@ -63,7 +145,7 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_kernel(const SplitParams p
     const int g = p.Hq / p.Hkv;
     const int unit = blockIdx.y / p.nrt, rt = blockIdx.y % p.nrt;
     const int b = unit / p.Hkv, hk = unit % p.Hkv;
-    const int Sq = p.Sq;
+    const int Sq = PAGED ? 1 : p.Sq;      // paged decode: one query token per sequence
     // paged: keys of this sequence, read on the device and bounded by what the block table can address (a stale or
     // corrupt scheduler value must not index the table or the cache out of bounds)
     const int Sk = PAGED ? min(max(p.context_lens[b], 0), p.max_blocks * p.block_size) : p.Sk;
@@ -82,27 +164,31 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_kernel(const SplitParams p
         return ((phys * p.block_size + off) * p.Hkv + hk) * (size_t)RB;
     };
 
-    // Q fragments (B operand of S^T = K.Q^T): lane (row, hi) holds d = 16ks + 8hi .. +7; rows beyond the unit are 0
+    // Q fragments (B operand of S^T = K.Q^T): fragment ks of lane (row, hi) holds d = KV::q_d0(ks, hi) .. +7, the k order
+    // of the source's K operands; rows beyond the unit are 0
     v8 qf[KS];
     {
-        const char* qrow = reinterpret_cast<const char*>(p.q) + ((size_t)(b * p.Hq + head) * Sq + qi) * RB;
-        const unsigned flip = p.negq ? 0x80008000u : 0u;
+        const char* qrow = reinterpret_cast<const char*>(p.q) + ((size_t)(b * p.Hq + head) * Sq + qi) * (D * 2);
+        const unsigned flip = (KV::kSignInQ && p.negq) ? 0x80008000u : 0u;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             u32x4_t x = {0u, 0u, 0u, 0u};
-            if (valid) x = *reinterpret_cast<const u32x4_t*>(qrow + (2 * ks + hi) * 16);
+            if (valid) x = *reinterpret_cast<const u32x4_t*>(qrow + KV::q_d0(ks, hi) * 2);
             x[0] ^= flip; x[1] ^= flip; x[2] ^= flip; x[3] ^= flip;
             qf[ks] = as_v8<T>(x);
         }
     }
 
-    // V staging map (sub-tiled image filled linearly by lane id) and transpose-read offset: fa_fwd_pp_gfx950.hip
-    int v_g[NV], v_row[NV], v_col[NV];
+    // V staging map: the wave's 16-byte source chunks u = lane + 64 i fill the sub-tiled 16-bit image linearly
+    // ([kv/4][d/16][4][16 elements]: fa_fwd_pp_gfx950.hip); a sub-tile row of 16 elements is EB source chunks, and chunk
+    // u lands at byte u * 32 / EB of the image.  Transpose-read offset: fa_fwd_pp_gfx950.hip
+    int v_g[NL], v_row[NL], v_col[NL];
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int bidx = (lane >> 3) + 8 * i;  // sub-tile index = kv4 * (D/16) + d16
-        v_row[i] = (bidx / (D / 16)) * 4 + ((lane >> 1) & 3);
-        v_col[i] = ((bidx % (D / 16)) * 2 + (lane & 1)) * 16;
+    for (int i = 0; i < NL; ++i) {
+        const int u = lane + 64 * i;
+        const int bidx = u / (4 * EB);    // sub-tile index = kv4 * (D/16) + d16
+        v_row[i] = (bidx / (D / 16)) * 4 + ((u / EB) & 3);
+        v_col[i] = ((bidx % (D / 16)) * EB + u % EB) * 16;   // byte offset inside the row
         v_g[i] = v_row[i] * RB + v_col[i];
     }
     const int tr_off = hi * (D / 16) * 128 + ((lane >> 4) & 1) * 128 + (lane & 15) * 8;
@@ -110,14 +196,14 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_kernel(const SplitParams p
     const bool pow2 = PAGED && p.block_size >= 8 && (p.block_size & (p.block_size - 1)) == 0;
     const int bs_log2 = PAGED ? 31 - __builtin_clz(p.block_size | 1) : 0;
     const size_t blk_bytes = PAGED ? (size_t)p.block_size * p.Hkv * RB : 0;
-    int k_jb = 0, k_off = 0, v_jb[NV], v_off[NV];
+    int k_jb = 0, k_off = 0, v_jb[NL], v_off[NL];
 #pragma unroll
-    for (int i = 0; i < NV; ++i) { v_jb[i] = 0; v_off[i] = 0; }
+    for (int i = 0; i < NL; ++i) { v_jb[i] = 0; v_off[i] = 0; }
     if (pow2) {
         k_jb = l31 >> bs_log2;
         k_off = ((l31 & (p.block_size - 1)) * p.Hkv + hk) * RB + hi * 16;
 #pragma unroll
-        for (int i = 0; i < NV; ++i) {
+        for (int i = 0; i < NL; ++i) {
             v_jb[i] = v_row[i] >> bs_log2;
             v_off[i] = ((v_row[i] & (p.block_size - 1)) * p.Hkv + hk) * RB + v_col[i];
         }
@@ -129,7 +215,7 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_kernel(const SplitParams p
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
     float m = -INFINITY, l = 0.f;
-    const float c = p.c;
+    const float c = p.c * KV::k_factor(p, hk);   // (FP8: logits = k_scale * (q . codes) * scale, one fp32 factor per unit)
 
     const int ntiles = (Sk + 31) / 32;
     int t0 = (blockIdx.x * 4 + wave) * p.chunk_tiles;
@@ -143,51 +229,53 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_kernel(const SplitParams p
 
     for (int t = t0; t < t1; ++t) {
         const int kv0 = t * 32;
-        u32x4_t ka[KS], vx[NV];
+        // lane (key l31, hi) loads the 16-byte chunks 2j + hi of its K row; V chunk i of the staging map
+        u32x4_t kx[NL], vx[NL];
         if constexpr (PAGED) {
             const u32x4_t zero = {0u, 0u, 0u, 0u};
+            const bool kin = kv0 + l31 < Sk;
             if (pow2) {
                 // power-of-two block sizes >= 8 (the usual 16/32/64/128): the tile's <= 4 logical blocks are looked up
                 // ONCE per tile with wave-uniform (scalar) loads; each lane picks its block with selects and adds a
                 // 32-bit in-block offset computed once per launch -- no per-lane table lookups or 64-bit multiplies
                 const int lb0 = kv0 >> bs_log2;
-                size_t pb[4];
                 const size_t tile_off = (size_t)(kv0 & (p.block_size - 1)) * p.Hkv * RB;   // blocks larger than a tile
-#pragma unroll
-                for (int jb = 0; jb < 4; ++jb) pb[jb] = (size_t)bt[min(lb0 + jb, p.max_blocks - 1)] * blk_bytes + tile_off;
-                auto pick = [&](int jb) -> size_t { return jb == 0 ? pb[0] : (jb == 1 ? pb[1] : (jb == 2 ? pb[2] : pb[3])); };
-                const bool kin = kv0 + l31 < Sk;
+                // (four named values, not an array: the compiler turns selects over an array into an indexed read from scratch)
+                const size_t pb0 = (size_t)bt[min(lb0, p.max_blocks - 1)] * blk_bytes + tile_off;
+                const size_t pb1 = (size_t)bt[min(lb0 + 1, p.max_blocks - 1)] * blk_bytes + tile_off;
+                const size_t pb2 = (size_t)bt[min(lb0 + 2, p.max_blocks - 1)] * blk_bytes + tile_off;
+                const size_t pb3 = (size_t)bt[min(lb0 + 3, p.max_blocks - 1)] * blk_bytes + tile_off;
+                auto pick = [&](int jb) -> size_t { return jb == 0 ? pb0 : (jb == 1 ? pb1 : (jb == 2 ? pb2 : pb3)); };
                 const char* krow = reinterpret_cast<const char*>(p.k) + pick(k_jb) + k_off;
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) ka[ks] = kin ? *reinterpret_cast<const u32x4_t*>(krow + ks * 32) : zero;
+                for (int j = 0; j < NL; ++j) kx[j] = kin ? *reinterpret_cast<const u32x4_t*>(krow + j * 32) : zero;
 #pragma unroll
-                for (int i = 0; i < NV; ++i) {
+                for (int i = 0; i < NL; ++i) {
                     const bool vin = kv0 + v_row[i] < Sk;
                     vx[i] = vin ? *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(p.v) + pick(v_jb[i]) + v_off[i]) : zero;
                 }
             } else {
-            const bool kin = kv0 + l31 < Sk;
-            const char* krow = reinterpret_cast<const char*>(p.k) + (kin ? paged_row(kv0 + l31) : 0);
+                const char* krow = reinterpret_cast<const char*>(p.k) + (kin ? paged_row(kv0 + l31) : 0) + hi * 16;
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) ka[ks] = kin ? *reinterpret_cast<const u32x4_t*>(krow + (2 * ks + hi) * 16) : zero;
+                for (int j = 0; j < NL; ++j) kx[j] = kin ? *reinterpret_cast<const u32x4_t*>(krow + j * 32) : zero;
 #pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const bool vin = kv0 + v_row[i] < Sk;
-                vx[i] = vin ? *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(p.v) + paged_row(kv0 + v_row[i]) + v_col[i]) : zero;
-            }
+                for (int i = 0; i < NL; ++i) {
+                    const bool vin = kv0 + v_row[i] < Sk;
+                    vx[i] = vin ? *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(p.v) + paged_row(kv0 + v_row[i]) + v_col[i]) : zero;
+                }
             }
         } else {
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-                ka[ks] = __builtin_amdgcn_raw_buffer_load_b128(krs, (kv0 + l31) * RB + (2 * ks + hi) * 16, 0, 0);
+            for (int j = 0; j < NL; ++j)
+                kx[j] = __builtin_amdgcn_raw_buffer_load_b128(krs, (kv0 + l31) * RB + (2 * j + hi) * 16, 0, 0);
 #pragma unroll
-            for (int i = 0; i < NV; ++i) vx[i] = __builtin_amdgcn_raw_buffer_load_b128(vrs, v_g[i], kv0 * RB, 0);
+            for (int i = 0; i < NL; ++i) vx[i] = __builtin_amdgcn_raw_buffer_load_b128(vrs, v_g[i], kv0 * RB, 0);
         }
         f32x16_t s;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) s = T::mfma(as_v8<T>(ka[ks]), qf[ks], ks == 0 ? z : s);
+        for (int j = 0; j < NL; ++j) s = KV::template qk<T>(kx[j], &qf[j * (2 / EB)], j == 0 ? z : s);   // (2 / EB fragments per load)
 #pragma unroll
-        for (int i = 0; i < NV; ++i) *reinterpret_cast<u32x4_t*>(Vw + lane * 16 + i * 1024) = vx[i];
+        for (int i = 0; i < NL; ++i) KV::template stage_v<T>(Vw + (lane + 64 * i) * (32 / EB), vx[i]);
 
         // online softmax over this tile's 32 keys (16 per lane half), exp2 domain
         const bool ragged = kv0 + 32 > Sk || (PAGED && p.window > 0 && Sk - 1 - kv0 >= p.window);
@@ -231,7 +319,9 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_kernel(const SplitParams p
             }
     }
 
-    // partial of this wave: O (un-normalised), m, l of the lane's row (both lane halves hold the same row)
+    // partial of this wave: O (un-normalised, times the source's V factor), m, l of the lane's row (both lane halves
+    // hold the same row)
+    const float vs = KV::v_factor(p, hk);
     const float lt = l + xhalf(l);
     const int pi = blockIdx.x * 4 + wave;
     const size_t prow = (size_t)pi * p.rows_total + (size_t)blockIdx.y * 32 + l31;
@@ -240,7 +330,7 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_kernel(const SplitParams p
     for (int d = 0; d < DB; ++d)
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
-            const f32x4_t x = {o[d][4 * g4], o[d][4 * g4 + 1], o[d][4 * g4 + 2], o[d][4 * g4 + 3]};
+            const f32x4_t x = {o[d][4 * g4] * vs, o[d][4 * g4 + 1] * vs, o[d][4 * g4 + 2] * vs, o[d][4 * g4 + 3] * vs};
             *reinterpret_cast<f32x4_t*>(dst + 32 * d + 8 * g4 + 4 * hi) = x;
         }
     if (hi == 0) {
@@ -307,114 +397,6 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_combine(const SplitParams 
     }
 }
 
-template <class T, int D>
-int launch_split(const FwdArgs& a, hipStream_t stream) {
-    SplitParams p;
-    p.q = a.q; p.k = a.k; p.v = a.v; p.o = a.o; p.lse = a.lse;
-    p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = a.Sq; p.Sk = a.Sk;
-    float c = a.scale * kLog2e;
-    p.negq = c < 0.f;
-    p.c = c < 0.f ? -c : c;
-    if (p.c == 0.f) p.c = 1e-30f;
-    const int g = a.Hq / a.Hkv;
-    p.nrt = (g * a.Sq + 31) / 32;
-    const int units = a.B * a.Hkv * p.nrt;
-    const int ntiles = (a.Sk + 31) / 32;
-    const int want_waves = (2048 + units - 1) / units;            // ~8 waves per CU over the whole launch
-    p.chunk_tiles = (ntiles + want_waves - 1) / want_waves;
-    if (p.chunk_tiles < 1) p.chunk_tiles = 1;
-    const int nwaves = (ntiles + p.chunk_tiles - 1) / p.chunk_tiles;
-    const int nsplit = (nwaves + 3) / 4;
-    p.npart = nsplit * 4;
-    p.rows_total = units * 32;
-    p.block_tables = nullptr; p.context_lens = nullptr; p.block_size = 0; p.max_blocks = 0; p.window = 0;
-    const size_t bytes = (size_t)p.npart * p.rows_total * (D + 2) * sizeof(float);
-    if (a.query_ws != nullptr) {
-        *a.query_ws = bytes;
-        return 0;
-    }
-    ScopedWorkspace ws(bytes, a.ws, a.ws_bytes, stream);   // caller's buffer, or stream-ordered (safe with concurrent streams)
-    if (ws.err != hipSuccess) return (int)ws.err;
-    p.part = static_cast<float*>(ws.ptr);
-    hipLaunchKernelGGL((fa_fwd_splitkv_kernel<T, D, false>), dim3((unsigned)nsplit, (unsigned)units), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL((fa_fwd_splitkv_combine<T, D>), dim3((unsigned)p.rows_total), dim3(256), 0, stream, p);
-    return (int)hipGetLastError();
-}
-
-// Paged decode: one query token per sequence, K/V gathered through the block table; the key range is bounded by
-// max_blocks * block_size on the host (no device->host sync for max(context_lens)); waves past a sequence's
-// context_len leave an empty partial.
-template <class T, int D>
-int launch_paged(const PagedArgs& a, hipStream_t stream) {
-    SplitParams p;
-    p.q = a.q; p.k = a.k_cache; p.v = a.v_cache; p.o = a.out; p.lse = nullptr;
-    p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = 1; p.Sk = a.max_blocks * a.block_size;
-    float c = a.scale * kLog2e;
-    p.negq = c < 0.f;
-    p.c = c < 0.f ? -c : c;
-    if (p.c == 0.f) p.c = 1e-30f;
-    const int g = a.Hq / a.Hkv;
-    p.nrt = (g + 31) / 32;
-    const int units = a.B * a.Hkv * p.nrt;
-    const int ntiles = (p.Sk + 31) / 32;
-    const int want_waves = (2048 + units - 1) / units;
-    p.chunk_tiles = (ntiles + want_waves - 1) / want_waves;
-    if (p.chunk_tiles < 1) p.chunk_tiles = 1;
-    const int nwaves = (ntiles + p.chunk_tiles - 1) / p.chunk_tiles;
-    const int nsplit = (nwaves + 3) / 4;
-    p.npart = nsplit * 4;
-    p.rows_total = units * 32;
-    p.block_tables = a.block_tables; p.context_lens = a.context_lens;
-    p.block_size = a.block_size; p.max_blocks = a.max_blocks; p.window = a.window > 0 ? a.window : 0;
-    const size_t bytes = (size_t)p.npart * p.rows_total * (D + 2) * sizeof(float);
-    if (a.query_ws != nullptr) {
-        *a.query_ws = bytes;
-        return 0;
-    }
-    ScopedWorkspace ws(bytes, a.ws, a.ws_bytes, stream);
-    if (ws.err != hipSuccess) return (int)ws.err;
-    p.part = static_cast<float*>(ws.ptr);
-    hipLaunchKernelGGL((fa_fwd_splitkv_kernel<T, D, true>), dim3((unsigned)nsplit, (unsigned)units), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL((fa_fwd_splitkv_combine<T, D>), dim3((unsigned)p.rows_total), dim3(256), 0, stream, p);
-    return (int)hipGetLastError();
-}
-
-}  // namespace
-
-int launch_paged_decode(const PagedArgs& a, hipStream_t stream) {
-    if (a.dtype == kBF16) {
-        if (a.D == 128) return launch_paged<Bf16Traits, 128>(a, stream);
-        if (a.D == 64) return launch_paged<Bf16Traits, 64>(a, stream);
-        if (a.D == 32) return launch_paged<Bf16Traits, 32>(a, stream);
-    } else if (a.dtype == kF16) {
-        if (a.D == 128) return launch_paged<F16Traits, 128>(a, stream);
-        if (a.D == 64) return launch_paged<F16Traits, 64>(a, stream);
-        if (a.D == 32) return launch_paged<F16Traits, 32>(a, stream);
-    }
-    return -1;
-}
-
-#ifndef AULE_SPLITKV_MAX_UNITS
-#define AULE_SPLITKV_MAX_UNITS 128   // (A/B builds override it: tools/split_ab.py)
-#endif
-// Shapes the split-KV path takes over from the tiled kernels: 16-bit, non-causal, no window, short queries against
-// long K/V -- few enough Q blocks that the tiled kernels would leave most CUs idle.
-bool splitkv_applicable(const FwdArgs& a) {
-    if (a.dtype != kBF16 && a.dtype != kF16) return false;
-    if (a.causal || a.window > 0) return false;
-    if (a.D != 32 && a.D != 64 && a.D != 128) return false;
-    if (a.Sq > 64 || a.Sk < 1024) return false;
-    const long long tiled_wgs = (long long)a.B * a.Hq * ((a.Sq + 255) / 256);
-    if (tiled_wgs >= 512) return false;   // two workgroups per CU: the tiled kernel fills the chip
-    // K/V is streamed once per 32-row tile of packed rows, so `units` of them re-read it that many times and every
-    // one adds partials to combine.  Measured (tools/split_grid.py, bf16 D128, Sk 2048 / 8192): units <= 128 wins
-    // in every case (2-8x at B = 1); units = 256 is break-even (-20..25 % at Sk 2048, +4..7 % at 8192); units >= 512
-    // loses (B8 Hq32 Hkv8 Sq64 Sk8192: 318 vs 194 us).
-    const int g = a.Hq / a.Hkv;
-    const long long units = (long long)a.B * a.Hkv * ((g * a.Sq + 31) / 32);
-    return units <= AULE_SPLITKV_MAX_UNITS;
-}
-
 // Combine for FEW partials per row (the tiled kernel's SPLIT instances leave at most a few dozen): one WAVE per packed
 // row, four rows per workgroup, no LDS and no block-wide reduction.  Lane i first weighs partial i (w_i = 2^(m_i - M),
 // M the row's maximum; wave reductions), then every lane accumulates its D/64 columns over the partials with w_i
@@ -477,54 +459,163 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_combine_rows(const SplitPa
     if (lane == 0 && p.lse != nullptr) p.lse[orow] = L > 0.f ? (M + fast_log2(L)) * kLn2 : -INFINITY;
 }
 
-// The combine pass on its own, for partials written by another kernel (fa_fwd_pp_gfx950.hip SPLIT instances) in
-// the same layout: part [npart][B*Hkv*nrt*32][D + 2] fp32, packed row r of a unit = (head r / Sq of the group, query r % Sq).
+// ---- host side ----
+
+// (dtype, D) -> instance: f(traits, std::integral_constant<int, D>), or -1 for a combination this family does not have
+template <class F>
+int for_dtype_d(int dtype, int D, F&& f) {
+    auto by_d = [&](auto t) -> int {
+        if (D == 128) return f(t, std::integral_constant<int, 128>{});
+        if (D == 64) return f(t, std::integral_constant<int, 64>{});
+        if (D == 32) return f(t, std::integral_constant<int, 32>{});
+        return -1;
+    };
+    if (dtype == kBF16) return by_d(Bf16Traits{});
+    if (dtype == kF16) return by_d(F16Traits{});
+    return -1;
+}
+
+// Merge the partials `p` describes.  Same-box A/B (tools/combine_ab.py, two passes): with <= 16 partials per row the
+// wave-per-row kernel is ahead or level (B8 Hq32 Hkv8 Sq64 Sk8192 101 -> 87 us, B4 Sq128 Sk4096 65.5 -> 52.4 us); with
+// >= 32 its serial walk over the partials loses to the kernel that spreads them over thread groups (C5b 21.7 -> 29.0 us,
+// C5c 29.8 -> 36.2 us).  `by_count` = false: the workgroup-per-row kernel whatever the count.
 template <class T, int D>
-static int combine_only(const FwdArgs& a, float* part, int npart, int nrt, hipStream_t stream) {
-    SplitParams p;
-    p.q = a.q; p.k = a.k; p.v = a.v; p.o = a.o; p.lse = a.lse; p.part = part;
-    p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = a.Sq; p.Sk = a.Sk;
-    p.c = 1.f; p.negq = 0; p.nrt = nrt; p.chunk_tiles = 0; p.npart = npart;
-    p.rows_total = a.B * a.Hkv * nrt * 32;
-    p.block_tables = nullptr; p.context_lens = nullptr; p.block_size = 0; p.max_blocks = 0; p.window = 0;
+int launch_combine(const SplitParams& p, bool by_count, hipStream_t stream) {
     static const int lean = [] {   // AULE_HIP_FWD_COMBINE=wg selects the workgroup-per-row kernel (A/B measurements)
         const char* e = getenv("AULE_HIP_FWD_COMBINE");
         return (e != nullptr && e[0] == 'w') ? 0 : 1;
     }();
-    // Same-box A/B (tools/combine_ab.py, two passes): with <= 16 partials per row the wave-per-row kernel is ahead or
-    // level (B8 Hq32 Hkv8 Sq64 Sk8192 101 -> 87 us, B4 Sq128 Sk4096 65.5 -> 52.4 us); with >= 32 its serial walk over the
-    // partials loses to the kernel that spreads them over thread groups (C5b 21.7 -> 29.0 us, C5c 29.8 -> 36.2 us).
-    if (lean && npart <= 16)
+    if (by_count && lean && p.npart <= 16)
         hipLaunchKernelGGL((fa_fwd_splitkv_combine_rows<T, D>), dim3((unsigned)((p.rows_total + 3) / 4)), dim3(256), 0, stream, p);
     else
         hipLaunchKernelGGL((fa_fwd_splitkv_combine<T, D>), dim3((unsigned)p.rows_total), dim3(256), 0, stream, p);
     return (int)hipGetLastError();
 }
 
-int launch_splitkv_combine(const FwdArgs& a, float* part, int npart, int nrt, hipStream_t stream) {
-    if (a.dtype == kBF16) {
-        if (a.D == 128) return combine_only<Bf16Traits, 128>(a, part, npart, nrt, stream);
-        if (a.D == 64) return combine_only<Bf16Traits, 64>(a, part, npart, nrt, stream);
-        if (a.D == 32) return combine_only<Bf16Traits, 32>(a, part, npart, nrt, stream);
-    } else if (a.dtype == kF16) {
-        if (a.D == 128) return combine_only<F16Traits, 128>(a, part, npart, nrt, stream);
-        if (a.D == 64) return combine_only<F16Traits, 64>(a, part, npart, nrt, stream);
-        if (a.D == 32) return combine_only<F16Traits, 32>(a, part, npart, nrt, stream);
+// The wave-per-chunk launch: plan, workspace (or the dry run's answer), split kernel, combine.  `p` arrives with the
+// tensors, B / Hq / Hkv / Sq, the scale and the paged fields set; `Sk` bounds the key range on the host.  The plan:
+// `groups` = B * Hkv units of `rows` packed rows each, cut into 32-row tiles; the key tiles are shared out so that about
+// 2048 waves (~8 per CU) are launched whatever the shape and whatever the bytes per key.
+template <class T, int D, class KV, bool PAGED>
+int launch_wave_chunk(SplitParams p, int Sk, void* user_ws, uint64_t user_ws_bytes, uint64_t* query_ws, bool combine_by_count,
+                      hipStream_t stream) {
+    p.nrt = (p.Hq / p.Hkv * p.Sq + 31) / 32;
+    const int units = p.B * p.Hkv * p.nrt;
+    const int ntiles = (Sk + 31) / 32;
+    const int want_waves = (2048 + units - 1) / units;
+    p.chunk_tiles = (ntiles + want_waves - 1) / want_waves;
+    if (p.chunk_tiles < 1) p.chunk_tiles = 1;
+    const int nwaves = (ntiles + p.chunk_tiles - 1) / p.chunk_tiles;
+    const int nsplit = (nwaves + 3) / 4;
+    p.npart = nsplit * 4;
+    p.rows_total = units * 32;
+    const size_t bytes = (size_t)p.npart * p.rows_total * (D + 2) * sizeof(float);
+    if (query_ws != nullptr) {
+        *query_ws = bytes;
+        return 0;
     }
-    return -1;
+    ScopedWorkspace ws(bytes, user_ws, user_ws_bytes, stream);   // caller's buffer, or stream-ordered (safe with concurrent streams)
+    if (ws.err != hipSuccess) return (int)ws.err;
+    p.part = static_cast<float*>(ws.ptr);
+    hipLaunchKernelGGL((fa_fwd_splitkv_kernel<T, D, KV, PAGED>), dim3((unsigned)nsplit, (unsigned)units), dim3(256), 0, stream, p);
+    const int rc = (int)hipGetLastError();
+    return rc != 0 ? rc : launch_combine<T, D>(p, combine_by_count, stream);
 }
 
+// Scale convention of the 16-bit sources: |scale| log2(e) in the kernel, the sign in Q, 0 replaced by 1e-30.
+void set_abs_scale(SplitParams& p, float scale) {
+    const float c = scale * kLog2e;
+    p.negq = c < 0.f;
+    p.c = c < 0.f ? -c : c;
+    if (p.c == 0.f) p.c = 1e-30f;
+}
+
+template <class T, int D>
+int launch_split(const FwdArgs& a, hipStream_t stream) {
+    SplitParams p = {};
+    p.q = a.q; p.k = a.k; p.v = a.v; p.o = a.o; p.lse = a.lse;
+    p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = a.Sq; p.Sk = a.Sk;
+    set_abs_scale(p, a.scale);
+    return launch_wave_chunk<T, D, Kv16, false>(p, a.Sk, a.ws, a.ws_bytes, a.query_ws, false, stream);
+}
+
+// Paged decode: one query token per sequence, K/V gathered through the block table; the key range is bounded by
+// max_blocks * block_size on the host (no device->host sync for max(context_lens)); waves past a sequence's
+// context_len leave an empty partial.
+template <class T, int D, class KV>
+int launch_paged(const PagedArgs& a, hipStream_t stream) {
+    SplitParams p = {};
+    p.q = a.q; p.k = a.k_cache; p.v = a.v_cache; p.o = a.out; p.lse = nullptr;
+    p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = 1; p.Sk = a.max_blocks * a.block_size;
+    p.block_tables = a.block_tables; p.context_lens = a.context_lens;
+    p.block_size = a.block_size; p.max_blocks = a.max_blocks; p.window = a.window > 0 ? a.window : 0;
+    p.k_scale = a.k_scale; p.v_scale = a.v_scale;
+    // The two cache kinds differ in two places beyond the data format.  Both differences reach the results (the last
+    // bits, or which kernel runs), so each is kept as it was introduced; making them one is a change of its own.
+    //  * scale (KV::kSignInQ): the 16-bit cache takes the contiguous kernel's convention (set_abs_scale); the FP8 cache
+    //    passes the signed product, which the kernel multiplies by k_scale[hk].
+    if (KV::kSignInQ) set_abs_scale(p, a.scale);
+    else p.c = a.scale * kLog2e;
+    //  * combine: the 16-bit cache always merges with the workgroup-per-row kernel; the FP8 cache picks by the number
+    //    of partials (and honours AULE_HIP_FWD_COMBINE), as launch_splitkv_combine does.
+    return launch_wave_chunk<T, D, KV, true>(p, p.Sk, a.ws, a.ws_bytes, a.query_ws, /*combine_by_count=*/std::is_same<KV, KvFp8>::value, stream);
+}
+
+}  // namespace
+
 int launch_fwd_splitkv(const FwdArgs& a, hipStream_t stream) {
-    if (a.dtype == kBF16) {
-        if (a.D == 128) return launch_split<Bf16Traits, 128>(a, stream);
-        if (a.D == 64) return launch_split<Bf16Traits, 64>(a, stream);
-        if (a.D == 32) return launch_split<Bf16Traits, 32>(a, stream);
-    } else if (a.dtype == kF16) {
-        if (a.D == 128) return launch_split<F16Traits, 128>(a, stream);
-        if (a.D == 64) return launch_split<F16Traits, 64>(a, stream);
-        if (a.D == 32) return launch_split<F16Traits, 32>(a, stream);
-    }
-    return -1;
+    return for_dtype_d(a.dtype, a.D, [&](auto t, auto d) { return launch_split<decltype(t), decltype(d)::value>(a, stream); });
+}
+
+// cache_kind selects the K/V source; an FP8 cache needs its two scale arrays (the dry run does not read them)
+int launch_paged_decode(const PagedArgs& a, hipStream_t stream) {
+    const bool fp8 = a.cache_kind == kCacheFp8E4M3;
+    if (fp8 && a.query_ws == nullptr && (a.k_scale == nullptr || a.v_scale == nullptr)) return -1;
+    return for_dtype_d(a.dtype, a.D, [&](auto t, auto d) {
+        using T = decltype(t);
+        constexpr int D = decltype(d)::value;
+        return fp8 ? launch_paged<T, D, KvFp8>(a, stream) : launch_paged<T, D, Kv16>(a, stream);
+    });
+}
+
+// dry run of the launcher above, so that the size query cannot drift from the launch
+uint64_t paged_workspace_bytes(PagedArgs a) {
+    uint64_t bytes = 0;
+    a.query_ws = &bytes;
+    (void)launch_paged_decode(a, nullptr);
+    return bytes;
+}
+
+// The combine pass on its own, for partials written by another kernel (fa_fwd_pp_gfx950.hip SPLIT instances) in
+// the same layout: part [npart][B*Hkv*nrt*32][D + 2] fp32, packed row r of a unit = (head r / Sq of the group, query r % Sq).
+int launch_splitkv_combine(const FwdArgs& a, float* part, int npart, int nrt, hipStream_t stream) {
+    SplitParams p = {};
+    p.o = a.o; p.lse = a.lse; p.part = part;
+    p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = a.Sq; p.Sk = a.Sk;
+    p.nrt = nrt; p.npart = npart;
+    p.rows_total = a.B * a.Hkv * nrt * 32;
+    return for_dtype_d(a.dtype, a.D, [&](auto t, auto d) { return launch_combine<decltype(t), decltype(d)::value>(p, true, stream); });
+}
+
+#ifndef AULE_SPLITKV_MAX_UNITS
+#define AULE_SPLITKV_MAX_UNITS 128   // (A/B builds override it: tools/split_ab.py)
+#endif
+// Shapes the split-KV path takes over from the tiled kernels: 16-bit, non-causal, no window, short queries against
+// long K/V -- few enough Q blocks that the tiled kernels would leave most CUs idle.
+bool splitkv_applicable(const FwdArgs& a) {
+    if (a.dtype != kBF16 && a.dtype != kF16) return false;
+    if (a.causal || a.window > 0) return false;
+    if (a.D != 32 && a.D != 64 && a.D != 128) return false;
+    if (a.Sq > 64 || a.Sk < 1024) return false;
+    const long long tiled_wgs = (long long)a.B * a.Hq * ((a.Sq + 255) / 256);
+    if (tiled_wgs >= 512) return false;   // two workgroups per CU: the tiled kernel fills the chip
+    // K/V is streamed once per 32-row tile of packed rows, so `units` of them re-read it that many times and every
+    // one adds partials to combine.  Measured (tools/split_grid.py, bf16 D128, Sk 2048 / 8192): units <= 128 wins
+    // in every case (2-8x at B = 1); units = 256 is break-even (-20..25 % at Sk 2048, +4..7 % at 8192); units >= 512
+    // loses (B8 Hq32 Hkv8 Sq64 Sk8192: 318 vs 194 us).
+    const int g = a.Hq / a.Hkv;
+    const long long units = (long long)a.B * a.Hkv * ((g * a.Sq + 31) / 32);
+    return units <= AULE_SPLITKV_MAX_UNITS;
 }
 
 }  // namespace aule_hip

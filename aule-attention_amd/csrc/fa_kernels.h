@@ -132,7 +132,7 @@ struct DsLayout {
 // Paged-KV decode (python/aule/triton_flash_amd.py:543-737): one query token per sequence.
 //   q, out : [B, Hq, D]      k_cache, v_cache : [num_blocks, block_size, Hkv, D]   (16-bit dtypes)
 //   block_tables : [B, max_blocks] int32 (physical block of each logical block), context_lens : [B] int32
-// FP8 caches (launch_paged_decode_fp8): k_cache / v_cache hold OCP e4m3fn codes, one byte per element, and
+// FP8 caches (cache_kind = kCacheFp8E4M3): k_cache / v_cache hold OCP e4m3fn codes, one byte per element, and
 //   K = k_scale[hk] * code, V = v_scale[hk] * code with k_scale, v_scale : [Hkv] fp32 on the device; q / out stay 16-bit.
 enum CacheKind : int { kCache16 = 0, kCacheFp8E4M3 = 1 };
 struct PagedArgs {
@@ -172,12 +172,11 @@ int launch_rope(const RopeArgs& a, hipStream_t stream);
 
 // Returns 0 on success, a hipError_t value on launch failure, -1 for an
 // unsupported (dtype, D) combination.
-int launch_paged_decode(const PagedArgs& a, hipStream_t stream);
-int launch_paged_decode_fp8(const PagedArgs& a, hipStream_t stream);   // fa_fwd_splitkv_fp8_gfx950.hip (cache_kind = kCacheFp8E4M3)
+int launch_paged_decode(const PagedArgs& a, hipStream_t stream);   // either cache_kind; kCacheFp8E4M3 with a null scale array is -1
 int launch_fwd(const FwdArgs& a, hipStream_t stream);
 // merge partials [npart][B*Hkv*nrt*32][D+2] fp32 (un-normalised O, m in log2 units, l) into O / LSE (fa_fwd_splitkv_gfx950.hip)
 int launch_splitkv_combine(const FwdArgs& a, float* part, int npart, int nrt, hipStream_t stream);
-int fwd_route(const FwdArgs& a);
+int fwd_route(const FwdArgs& a);   // 0 fp32, 1 ping-pong, 4 split-KV, 5 tiled + packed rows + KV splits, 7 / 8 one-wave-per-SIMD, 9 head_dim 256 (host logic only)
 // launch_fwd honours FwdArgs::rope_* for these arguments (otherwise it refuses them: rotate Q with launch_rope first)
 bool fwd_rope_fusable(const FwdArgs& a);
 // the split plan of route 7 as integers (tests): fwd_split_plan_dump in fa_fwd_w4_gfx950.hip, the plan itself in fa_fwd_split.h
@@ -186,8 +185,7 @@ int fwd_split_plan_dump(const FwdArgs& a, int* out, int cap);
 void work_order_dump(int ranked, int bid, int B, int Hq, int Hkv, int nblk, int flag, int* out4);
 // bytes of workspace launch_fwd / launch_paged_decode would allocate for these arguments (0: single-launch path)
 uint64_t fwd_workspace_bytes(FwdArgs a);
-uint64_t paged_fp8_workspace_bytes(PagedArgs a);
-uint64_t paged_workspace_bytes(PagedArgs a);   // 0 fp32, 1 ping-pong, 2 in-wave, 3 v1, 4 split-KV, 5 tiled + packed rows + KV splits (host logic only)
+uint64_t paged_workspace_bytes(PagedArgs a);
 int launch_bwd(const BwdArgs& a, hipStream_t stream);
 // bit mask of what the most recent launch_bwd of this process ran: 1 the 5-matmul mode (delta pass + spilling dK/dV kernel + dQ = dS K),
 // 2 / 4 the one-wave-per-SIMD dQ / dK/dV kernel, 8 / 16 their two-waves-per-SIMD predecessors, 32 the fp32 kernels, 64 (with 4) the D = 64

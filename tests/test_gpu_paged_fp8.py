@@ -1,5 +1,5 @@
 """Paged decode over an FP8 (OCP e4m3fn) KV cache with per-KV-head scales, on the GPU
-(csrc/fa_fwd_splitkv_fp8_gfx950.hip behind aule.flash_attention_paged_amd / aule_attention_paged_decode_fp8_ex).
+(the KvFp8 instances of csrc/fa_fwd_splitkv_gfx950.hip behind aule.flash_attention_paged_amd / aule_attention_paged_decode_fp8_ex).
 
 The judge is the fp64 oracle `paged_decode_f64` on the DEQUANTISED caches -- scale[hk] * float(code), formed in float64 on
 the host -- and the 16-bit-rounded query; never the kernel under test and never the 16-bit kernel.  The bound is the

@@ -1,6 +1,6 @@
 """FP8 (OCP e4m3fn) paged decode without a GPU: the additive C-ABI (symbols, descriptor layout, workspace query), the
-quantisation helper on CPU tensors, the argument errors of the torch layer, and a resource audit of the compiled FP8
-kernel instances (no scratch, no VGPR or SGPR spill)."""
+quantisation helper on CPU tensors, the argument errors of the torch layer, and a resource audit of the compiled instances
+of the wave-per-chunk kernel, FP8 and 16-bit (no scratch, no VGPR or SGPR spill)."""
 import ctypes
 import os
 import re
@@ -191,8 +191,8 @@ def test_every_finite_code_is_exact_in_both_16_bit_types():
 # ---- resource audit -------------------------------------------------------------------------------------------------
 
 def test_fp8_kernels_neither_spill_nor_use_scratch(tmp_path):
-    src = os.path.join(CSRC, "fa_fwd_splitkv_fp8_gfx950.hip")
-    out = tmp_path / "fp8.o"
+    src = os.path.join(CSRC, "fa_fwd_splitkv_gfx950.hip")
+    out = tmp_path / "splitkv.o"
     r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c",
                         "-Rpass-analysis=kernel-resource-usage", "-o", str(out), src],
                        capture_output=True, text=True, timeout=900, cwd=CSRC)
@@ -207,9 +207,15 @@ def test_fp8_kernels_neither_spill_nor_use_scratch(tmp_path):
         m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/lane\])?: (\d+)", line)
         if m and cur is not None:
             res[cur][m.group(1)] = int(m.group(2))
-    names = [n for n in res if "fa_fwd_paged_fp8_kernel" in n]
-    assert len(names) == 6, names   # fp16, bf16 x D 32, 64, 128
-    for n in names:
+    # fa_fwd_splitkv_kernel<T, D, KV, PAGED>: fp16, bf16 x D 32, 64, 128 per K/V source
+    wave = [n for n in res if "fa_fwd_splitkv_kernel" in n]
+    fp8 = [n for n in wave if "KvFp8" in n]
+    assert len(fp8) == 6, fp8
+    assert all("Lb1" in n for n in fp8), fp8                        # FP8 is a paged source
+    kv16 = [n for n in wave if "Kv16" in n]
+    assert len(kv16) == 12 and len(wave) == 18, wave                # contiguous and paged
+    assert sum("Lb1" in n for n in kv16) == 6, kv16
+    for n in fp8 + kv16:
         r_ = res[n]
         assert r_.get("ScratchSize") == 0, (n, r_)
         assert r_.get("VGPRs Spill") == 0, (n, r_)

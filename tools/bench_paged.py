@@ -8,7 +8,7 @@ block_size 16 are assumed here).  tok/s = batch / time per decode step (one atte
 per-head scales in the same process, alternated round by round, warm; per context the median over the rounds, the
 spread (min .. max) of both, and the ratio.  K+V bytes are the bytes of the cache each call reads.  --rounds N sets the
 number of rounds (default 15), --iters N the calls per round (default 50), --ctx N one context only (for a
-`rocprofv3 --kernel-trace --stats` run of its own: split kernel vs combine, fa_fwd_paged_fp8_kernel vs fa_fwd_splitkv_kernel)."""
+`rocprofv3 --kernel-trace --stats` run of its own: split kernel vs combine, the KvFp8 against the Kv16 instance of fa_fwd_splitkv_kernel)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "aule-attention_amd"))
