@@ -23,6 +23,7 @@
 
 #include <dlfcn.h>
 
+#include "fa_bwd_plan.h"
 #include "fa_kernels.h"
 
 // abi2: optional workspace / workspace_bytes appended to the forward and paged descriptors (96 -> 112, 104 -> 120)
@@ -581,8 +582,14 @@ int32_t aule_attention_backward(const float* query, const float* key, const floa
     if (rows == 0 || D == 0) return 0;
     const uint32_t Dp = pad_dim(D);
     DeviceGuard g(g_device);
+    BwdArgs a{};
+    a.B = (int)B; a.Hq = (int)H; a.Hkv = (int)H; a.Sq = (int)S; a.Sk = (int)S; a.D = (int)Dp;
+    a.scale = 1.0f / std::sqrt((float)D);
+    a.causal = causal != 0;
+    a.dtype = aule_hip::kF32;
+    a.window = -1; a.device = -1;
     Temp q, k, v, o, go, l, dq, dk, dv, ws;
-    const uint64_t wsb = aule_hip::bwd_workspace_bytes((int)B, (int)H, (int)H, (int)S, (int)S, (int)Dp, causal != 0, aule_hip::kF32);
+    const uint64_t wsb = aule_hip::bwd_plan(a).want_bytes;
     if (!q.alloc(rows, Dp) || !k.alloc(rows, Dp) || !v.alloc(rows, Dp) || !o.alloc(rows, Dp) ||
         !go.alloc(rows, Dp) || !l.alloc(rows, 1) || !dq.alloc(rows, Dp) || !dk.alloc(rows, Dp) ||
         !dv.alloc(rows, Dp) || !ws.alloc((wsb + 3) / 4, 1)) {
@@ -596,13 +603,8 @@ int32_t aule_attention_backward(const float* query, const float* key, const floa
         set_error("Upload failed: %s", hipGetErrorString(hipGetLastError()));
         return -3;
     }
-    BwdArgs a;
     a.q = q.ptr; a.k = k.ptr; a.v = v.ptr; a.o = o.ptr; a.dout = go.ptr; a.lse = l.ptr;
     a.dq = dq.ptr; a.dk = dk.ptr; a.dv = dv.ptr; a.delta = ws.ptr;
-    a.B = (int)B; a.Hq = (int)H; a.Hkv = (int)H; a.Sq = (int)S; a.Sk = (int)S; a.D = (int)Dp;
-    a.scale = 1.0f / std::sqrt((float)D);
-    a.causal = causal != 0;
-    a.dtype = aule_hip::kF32;
     int rc = aule_hip::launch_bwd(a, nullptr);
     if (rc == 0) rc = (int)hipDeviceSynchronize();
     if (rc != 0) {
@@ -676,15 +678,6 @@ static int check_common(int32_t dtype, uint32_t B, uint32_t Hq, uint32_t Hkv, ui
     return 0;
 }
 
-// One query at the bottom-right position sees every key: with no window the causal mask masks nothing, and the
-// problem is the non-causal one (which has the faster short-query paths).
-static void drop_trivial_causal(int& causal, int& coff, int Sq, int window) {
-    if (causal && Sq == 1 && coff > 0 && window <= 0) {
-        causal = 0;
-        coff = 0;
-    }
-}
-
 // roctx ranges around the launches (the reference has no tracing at all), so that
 // `rocprofv3 --marker-trace` shows "aule.forward" / "aule.backward" / "aule.paged_decode" / "aule.rope" next to the kernels.
 // Opt-in (AULE_ROCTX=1) and loaded lazily with dlopen: the library keeps its single link dependency (libamdhip64).
@@ -730,12 +723,21 @@ struct RoctxRange {
     RoctxRange& operator=(const RoctxRange&) = delete;
 };
 
+// One query at the bottom-right position sees every key: with no window the causal mask masks nothing, and the
+// problem is the non-causal one (which has the faster short-query paths).
+static void drop_trivial_causal(int& causal, int& coff, int Sq, int window) {
+    if (causal && Sq == 1 && coff > 0 && window <= 0) {
+        causal = 0;
+        coff = 0;
+    }
+}
+
 static float resolve_scale(float scale, uint32_t D) {
     if (scale == 0.0f || std::isnan(scale)) return 1.0f / std::sqrt((float)D);
     return scale;
 }
 
-// Descriptor -> launch arguments (shared by the plain and the fused-rotation entry points; no device work).
+// Descriptor -> launch arguments, once per direction (every entry point that reads a descriptor; no device work, no pointer dereferenced).
 static void fill_fwd_args(const aule_attn_desc* d, FwdArgs& a) {
     a.q = d->q; a.k = d->k; a.v = d->v; a.o = d->out; a.lse = d->lse;
     a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
@@ -748,6 +750,25 @@ static void fill_fwd_args(const aule_attn_desc* d, FwdArgs& a) {
     a.window = (d->window_size > 0 && (uint32_t)d->window_size < d->seq_q + (uint32_t)a.coff) ? d->window_size : -1;
     drop_trivial_causal(a.causal, a.coff, a.Sq, a.window);
     a.ws = d->workspace; a.ws_bytes = d->workspace ? d->workspace_bytes : 0;
+}
+
+// as_launched = false: the problem as the descriptor states it (what aule_attention_backward_workspace_size sizes the workspace for); true: the
+// problem the launch runs inside that workspace -- a causal mask that masks nothing dropped: never more partials, the same dS per element -- with
+// the stated minimum in ws_floor: the call is checked against it and the dS room lies behind it (just the minimum never looks like dS room).
+static void fill_bwd_args(const aule_attn_bwd_desc* d, BwdArgs& a, bool as_launched) {
+    a.q = d->q; a.k = d->k; a.v = d->v; a.o = d->out; a.dout = d->dout; a.lse = d->lse;
+    a.dq = d->dq; a.dk = d->dk; a.dv = d->dv; a.delta = (float*)d->workspace;
+    a.ws_bytes = d->workspace_bytes;
+    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
+    a.Sq = (int)d->seq_q; a.Sk = (int)d->seq_k; a.D = (int)d->head_dim;
+    a.scale = resolve_scale(d->scale, d->head_dim);
+    a.causal = d->causal != 0;
+    a.coff = d->causal == AULE_CAUSAL_BOTTOM_RIGHT ? (int)d->seq_k - (int)d->seq_q : 0;
+    a.dtype = d->dtype; a.device = d->device;
+    a.window = (d->window_size > 0 && (uint32_t)d->window_size < d->seq_q + (uint32_t)a.coff) ? d->window_size : -1;   // as fill_fwd_args
+    if (!as_launched) return;
+    a.ws_floor = aule_hip::bwd_plan(a).min_bytes;
+    drop_trivial_causal(a.causal, a.coff, a.Sq, a.window);
 }
 
 static bool fill_rope_args(const aule_attn_rope* r, uint32_t head_dim, FwdArgs& a) {
@@ -962,11 +983,9 @@ int32_t aule_rope_ex(const aule_rope_desc* d) {
 
 uint64_t aule_attention_backward_workspace_size(const aule_attn_bwd_desc* d) {
     if (d == nullptr) return 0;
-    // (a window that masks something -- the rule of aule_attention_backward_ex -- keeps the call on the recompute pair: no dS workspace then)
-    const int coff = d->causal == AULE_CAUSAL_BOTTOM_RIGHT ? (int)d->seq_k - (int)d->seq_q : 0;
-    const bool windowed = d->window_size > 0 && (long long)d->window_size < (long long)d->seq_q + coff;
-    return aule_hip::bwd_workspace_bytes((int)d->batch, (int)d->heads_q, (int)d->heads_kv, (int)d->seq_q, (int)d->seq_k,
-                                         (int)d->head_dim, d->causal != 0, d->dtype, d->device, windowed);
+    BwdArgs a;
+    fill_bwd_args(d, a, false);
+    return aule_hip::bwd_plan(a).want_bytes;
 }
 
 int32_t aule_attention_backward_ex(const aule_attn_bwd_desc* d) {
@@ -995,8 +1014,9 @@ int32_t aule_attention_backward_ex(const aule_attn_bwd_desc* d) {
     }
     // (aule_attention_backward_workspace_size() also asks for the dS workspace of the 5-matmul backward; a smaller buffer that
     // still holds delta / L' / the partials is accepted and runs the recompute pair)
-    const uint64_t need = aule_hip::bwd_workspace_min_bytes((int)d->batch, (int)d->heads_q, (int)d->heads_kv, (int)d->seq_q,
-                                                            (int)d->seq_k, (int)d->head_dim, d->causal != 0, d->dtype, d->device);
+    BwdArgs a;
+    fill_bwd_args(d, a, true);
+    const uint64_t need = a.ws_floor;
     if (!d->workspace || d->workspace_bytes < need) {
         set_error("Backward failed: workspace too small (%llu < %llu bytes)",
                   (unsigned long long)d->workspace_bytes, (unsigned long long)need);
@@ -1005,19 +1025,6 @@ int32_t aule_attention_backward_ex(const aule_attn_bwd_desc* d) {
     DeviceGuard g(d->device);
     rc = ensure_configured();
     if (rc) return rc;
-    BwdArgs a;
-    a.q = d->q; a.k = d->k; a.v = d->v; a.o = d->out; a.dout = d->dout; a.lse = d->lse;
-    a.dq = d->dq; a.dk = d->dk; a.dv = d->dv; a.delta = (float*)d->workspace;
-    a.ws_bytes = d->workspace_bytes;
-    a.device = d->device;
-    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
-    a.Sq = (int)d->seq_q; a.Sk = (int)d->seq_k; a.D = (int)d->head_dim;
-    a.scale = resolve_scale(d->scale, d->head_dim);
-    a.causal = d->causal != 0;
-    a.coff = d->causal == AULE_CAUSAL_BOTTOM_RIGHT ? (int)d->seq_k - (int)d->seq_q : 0;
-    a.dtype = d->dtype;
-    a.window = (d->window_size > 0 && (uint32_t)d->window_size < d->seq_q + (uint32_t)a.coff) ? d->window_size : -1;
-    drop_trivial_causal(a.causal, a.coff, a.Sq, a.window);
     rc = aule_hip::launch_bwd(a, (hipStream_t)d->stream);
     if (rc != 0) {
         set_error("Backward failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
@@ -1094,15 +1101,7 @@ uint64_t aule_attention_forward_workspace_size(const aule_attn_desc* d) {
     if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128 && d->head_dim != 256) return 0;
     if (d->causal == AULE_CAUSAL_BOTTOM_RIGHT && d->seq_k < d->seq_q) return 0;
     FwdArgs a;
-    a.q = a.k = a.v = nullptr; a.o = nullptr; a.lse = nullptr;
-    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
-    a.Sq = (int)d->seq_q; a.Sk = (int)d->seq_k; a.D = (int)d->head_dim;
-    a.scale = 1.0f;
-    a.causal = d->causal != 0;
-    a.coff = d->causal == AULE_CAUSAL_BOTTOM_RIGHT ? a.Sk - a.Sq : 0;
-    a.dtype = d->dtype; a.device = d->device;
-    a.window = (d->window_size > 0 && (uint32_t)d->window_size < d->seq_q + (uint32_t)a.coff) ? d->window_size : -1;
-    drop_trivial_causal(a.causal, a.coff, a.Sq, a.window);
+    fill_fwd_args(d, a);
     return aule_hip::fwd_workspace_bytes(a);
 }
 
@@ -1131,13 +1130,7 @@ static int32_t backward_timeline(const aule_attn_bwd_desc* d, unsigned long long
     if (!g_init || d == nullptr || d->struct_size != sizeof(aule_attn_bwd_desc) || stamps == nullptr) return -1;
     if (d->dtype != AULE_DTYPE_BF16 || (d->head_dim != 128 && !(d->head_dim == 64 && !dq)) || d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;   // (D = 64: the dK/dV timeline only)
     BwdArgs a;
-    a.q = d->q; a.k = d->k; a.v = d->v; a.o = d->out; a.dout = d->dout; a.lse = d->lse;
-    a.dq = d->dq; a.dk = d->dk; a.dv = d->dv; a.delta = (float*)d->workspace;
-    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
-    a.Sq = (int)d->seq_q; a.Sk = (int)d->seq_k; a.D = (int)d->head_dim;
-    a.scale = resolve_scale(d->scale, d->head_dim);
-    a.causal = d->causal != 0;
-    a.dtype = d->dtype;
+    fill_bwd_args(d, a, true);
     if (dq) a.dbg_dq = stamps; else a.dbg = stamps;
     return aule_hip::launch_bwd(a, (hipStream_t)d->stream);
 }
@@ -1151,40 +1144,40 @@ int32_t aule_hip_debug_backward_timeline_dq(const aule_attn_bwd_desc* d, unsigne
 #endif  // AULE_DEBUG_HOOKS
 
 /* Debug hook (not part of the drop-in ABI): the forward kernel aule_attention_forward_ex would launch for `d`
- * -- 0 fp32, 1 ping-pong, 4 split-KV, 5 ping-pong with packed rows + KV splits, 6 persistent tile stream; -3 for a bad descriptor.  Pure host logic: no
+ * -- the codes of fwd_route() (fa_kernels.h; include/aule.h lists them); -3 for a bad descriptor.  Pure host logic: no
  * device, no aule_init() needed.  Used by the tests to pin which kernel a shape exercises. */
 int32_t aule_hip_debug_forward_route(const aule_attn_desc* d) {
     if (d == nullptr || d->struct_size != sizeof(aule_attn_desc)) return -3;
     if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return -3;
+    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;
     FwdArgs a;
-    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
-    a.Sq = (int)d->seq_q; a.Sk = (int)d->seq_k; a.D = (int)d->head_dim;
-    if (a.Hkv <= 0 || a.Hq % a.Hkv != 0) return -3;
-    a.causal = d->causal != 0;
-    a.coff = d->causal == AULE_CAUSAL_BOTTOM_RIGHT ? a.Sk - a.Sq : 0;
-    a.dtype = d->dtype; a.device = d->device;
-    a.scale = resolve_scale(d->scale, d->head_dim);   // (the sign of the scale picks the kernel: negative scales stay off route 8)
-    a.window = (d->window_size > 0 && (uint32_t)d->window_size < d->seq_q + (uint32_t)a.coff) ? d->window_size : -1;
-    drop_trivial_causal(a.causal, a.coff, a.Sq, a.window);
+    fill_fwd_args(d, a);   // (the sign of the scale picks the kernel: negative scales stay off route 8)
     return aule_hip::fwd_route(a);
 }
 
 /* Debug hook: what the most recent backward launch of this process ran (bit mask, include/aule.h). */
 int32_t aule_hip_debug_last_backward_route(void) { return aule_hip::bwd_last_route(); }
 
+/* Debug hook: the same mask for the call aule_attention_backward_ex(d) would make with d->workspace_bytes bytes of workspace; -3 for a
+ * descriptor it would refuse on shape grounds.  Pure host logic like the forward hook: the plan of the launch, not a launch. */
+int32_t aule_hip_debug_backward_route(const aule_attn_bwd_desc* d) {
+    if (d == nullptr || d->struct_size != sizeof(aule_attn_bwd_desc)) return -3;
+    if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT || (d->causal == AULE_CAUSAL_BOTTOM_RIGHT && d->seq_k < d->seq_q)) return -3;
+    if (d->dtype < 0 || d->dtype > 2 || d->heads_kv == 0 || d->heads_q % d->heads_kv != 0 || (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128 && d->head_dim != 256)) return -3;
+    if ((uint64_t)d->batch * d->heads_q * d->seq_q == 0 && (uint64_t)d->batch * d->heads_kv * d->seq_k == 0) return 0;   // (nothing runs)
+    if (d->seq_k == 0 || d->seq_q == 0) return -3;
+    BwdArgs a;
+    fill_bwd_args(d, a, true);
+    if (d->workspace_bytes < a.ws_floor) return -3;
+    return aule_hip::bwd_plan(a).route;
+}
+
 int32_t aule_hip_debug_forward_split_plan(const aule_attn_desc* d, int32_t* out, int32_t cap) {
     if (d == nullptr || d->struct_size != sizeof(aule_attn_desc)) return -3;
     if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return -3;
+    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;
     FwdArgs a;
-    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
-    a.Sq = (int)d->seq_q; a.Sk = (int)d->seq_k; a.D = (int)d->head_dim;
-    if (a.Hkv <= 0 || a.Hq % a.Hkv != 0) return -3;
-    a.causal = d->causal != 0;
-    a.coff = d->causal == AULE_CAUSAL_BOTTOM_RIGHT ? a.Sk - a.Sq : 0;
-    a.dtype = d->dtype; a.device = d->device;
-    a.scale = resolve_scale(d->scale, d->head_dim);
-    a.window = (d->window_size > 0 && (uint32_t)d->window_size < d->seq_q + (uint32_t)a.coff) ? d->window_size : -1;
-    drop_trivial_causal(a.causal, a.coff, a.Sq, a.window);
+    fill_fwd_args(d, a);
     if (aule_hip::fwd_route(a) != 7) return 0;
     return aule_hip::fwd_split_plan_dump(a, out, cap);
 }
@@ -1207,12 +1200,7 @@ int32_t aule_hip_debug_forward_timeline(const aule_attn_desc* d, unsigned long l
     if (!g_init || d == nullptr || d->struct_size != sizeof(aule_attn_desc) || stamps == nullptr) return -1;
     if (d->dtype != AULE_DTYPE_BF16 || (d->head_dim != 128 && d->head_dim != 64) || d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;
     FwdArgs a;
-    a.q = d->q; a.k = d->k; a.v = d->v; a.o = d->out; a.lse = d->lse;
-    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
-    a.Sq = (int)d->seq_q; a.Sk = (int)d->seq_k; a.D = (int)d->head_dim;
-    a.scale = resolve_scale(d->scale, d->head_dim);
-    a.causal = d->causal != 0;
-    a.dtype = d->dtype; a.device = d->device;
+    fill_fwd_args(d, a);
     if (const char* e = getenv("AULE_TL")) {
         if (e[0] == 'w' && e[1] == '4')  // one wave per SIMD: 4 waves x 2048 tagged stamps (tools/timeline_w4.py)
             return aule_hip::launch_fwd_w4_timeline(a, stamps, (hipStream_t)d->stream);

@@ -13,7 +13,7 @@
 //             GQA / MQA: the workgroup walks every query head of its KV head's group itself (no partial planes, no reduction pass).
 // Masks as the forward (causal with the position offset, sliding window, ragged tails); P is exp2(S c - L log2 e) with L the
 // forward's LSE, and keys a query does not see contribute nothing (rows without any visible key: LSE = -inf, P = 0).
-// The workspace is delta alone: B Hq Sq fp32 (bwd_workspace_bytes at D = 256).
+// The workspace is delta alone: B Hq Sq fp32 (bwd_plan at D = 256).
 #include <cstdlib>
 
 #include "fa_d256_common.h"

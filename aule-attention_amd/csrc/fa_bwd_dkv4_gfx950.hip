@@ -506,24 +506,10 @@ __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(40))) f
 template <int D>
 constexpr int kDkv4Lds = kRing4 * Bw4Asm<Bf16Traits, D>::SLOT;
 
-// Does the D = 64 problem take the two-key-blocks-per-wave instance?  Its work items are 256-key blocks (pairs of them): half as many, each
-// ~1.32 x as long as a 128-key item (twice the MFMAs in ~0.66 of twice the time: profiles/r6_bwd_d64_k2.txt).  Whole rounds of the chip decide:
-// ceil(items / CUs) of either kind, priced.  AULE_HIP_BWD_DKV_K2=0 / 1 pins it (A/B, tests).
+// Work items of a grid of kb-key blocks: (batch, KV head, block -- causal: pair of blocks); the whole GQA group runs inside one.
 inline long long dkv4_items_of(const BwdArgs& a, int kb) {
     const int nkb = (a.Sk + kb - 1) / kb;
     return (long long)a.B * a.Hkv * (a.causal ? (nkb + 1) / 2 : nkb);
-}
-inline bool dkv4_use_k2(const BwdArgs& a) {
-    static const int mode = [] {
-        const char* e = std::getenv("AULE_HIP_BWD_DKV_K2");
-        return e == nullptr ? -1 : (e[0] == '0' ? 0 : 1);
-    }();
-    if (a.D != 64 || a.ds != nullptr || a.dbg != nullptr) return false;   // (the 5-matmul mode and the timeline instances stay on the one-block stream)
-    if (mode >= 0) return mode == 1;
-    const long long cus = device_cu_count(a.device);
-    const long long i1 = dkv4_items_of(a, 128), i2 = dkv4_items_of(a, 256);
-    const long long r1 = (i1 + cus - 1) / cus, r2 = (i2 + cus - 1) / cus;
-    return r2 * 132 < r1 * 100;
 }
 
 template <class T, int D>
@@ -536,7 +522,7 @@ int launch_dkv4(const BwdArgs& a, hipStream_t stream) {
     p.scale = a.scale;
     p.coff = a.causal ? a.coff : 0;
     p.window = a.window > 0 ? a.window : 0;
-    const bool k2 = D == 64 && dkv4_use_k2(a);
+    const bool k2 = D == 64 && a.dkv4_k2;   // (decided by bwd_plan: bwd_dkv4_k2 below)
     const int nkb = k2 ? (a.Sk + 255) / 256 : (a.Sk + kKvBlock4 - 1) / kKvBlock4;
     p.nblk = a.causal ? (nkb + 1) / 2 : nkb;
     const dim3 grid((unsigned)(p.nblk * a.B * a.Hkv)), block(256);
@@ -608,7 +594,7 @@ int launch_dkv4(const BwdArgs& a, hipStream_t stream) {
 }  // namespace
 
 // Shapes the one-wave-per-SIMD dK/dV kernel CAN take: 16-bit, D = 128 or 64, no window, causal offset >= 0, a GQA group's rows inside
-// one 2 GB descriptor.  Whether it is taken: bwd_dkv4_items() against the predecessor's grid, in the dispatcher (fa_bwd_gfx950.hip).
+// one 2 GB descriptor.  Whether it is taken: bwd_dkv4_items() against the predecessor's grid, in bwd_plan (fa_bwd_gfx950.hip).
 bool bwd_dkv4_applicable(const BwdArgs& a) {
     // AULE_HIP_BWD_DKV=old: the two-waves-per-SIMD kernel everywhere (A/B); =new: this kernel wherever it CAN run (tests)
     static const int mode = [] {
@@ -626,14 +612,25 @@ bool bwd_dkv4_applicable(const BwdArgs& a) {
     return true;
 }
 
-// Work items of this kernel's grid: (batch, KV head, 128-key block -- causal: pair of blocks); the whole GQA group runs inside one.
-long long bwd_dkv4_items(const BwdArgs& a) {
-    const int nkb = (a.Sk + kKvBlock4 - 1) / kKvBlock4;
-    return (long long)a.B * a.Hkv * (a.causal ? (nkb + 1) / 2 : nkb);
-}
+// Work items of this kernel's grid of 128-key blocks (bwd_plan's grid rule)
+long long bwd_dkv4_items(const BwdArgs& a) { return dkv4_items_of(a, kKvBlock4); }
 
-// D = 64: does launch_bwd_dkv4 run the two-key-blocks-per-wave instance for this problem?  (the dispatcher's route record)
-bool bwd_dkv4_k2(const BwdArgs& a) { return a.D == 64 && dkv4_use_k2(a); }
+// Does the D = 64 problem take the two-key-blocks-per-wave instance (bwd_plan asks; the plan keeps the 5-matmul mode off it)?  Its work
+// items are 256-key blocks (pairs of them): half as many, each ~1.32 x as long as a 128-key item (twice the MFMAs in ~0.66 of twice the
+// time: profiles/r6_bwd_d64_k2.txt).  Whole rounds of the chip decide: ceil(items / CUs) of either kind, priced.
+// AULE_HIP_BWD_DKV_K2=0 / 1 pins it (A/B, tests).
+bool bwd_dkv4_k2(const BwdArgs& a) {
+    static const int mode = [] {
+        const char* e = std::getenv("AULE_HIP_BWD_DKV_K2");
+        return e == nullptr ? -1 : (e[0] == '0' ? 0 : 1);
+    }();
+    if (a.D != 64 || a.dbg != nullptr) return false;   // (the timeline instances stay on the one-block stream)
+    if (mode >= 0) return mode == 1;
+    const long long cus = device_cu_count(a.device);
+    const long long i1 = dkv4_items_of(a, kKvBlock4), i2 = dkv4_items_of(a, 256);
+    const long long r1 = (i1 + cus - 1) / cus, r2 = (i2 + cus - 1) / cus;
+    return r2 * 132 < r1 * 100;
+}
 
 // AULE_HIP_BWD_DKV=new: take every problem bwd_dkv4_applicable() accepts (tests)
 bool bwd_dkv4_forced() {

@@ -20,31 +20,38 @@
 //                       group reduction is the loop, not an atomic.
 // The softmax is recomputed twice (once per kernel): 7 tile matmuls instead of the
 // 5 of the atomic formulation, in exchange for no fp32 atomics on dQ.
+// Host side: bwd_plan() (fa_bwd_plan.h; below the kernels) states once which kernels a call runs -- these, their one-wave-per-SIMD
+// successors, the 5-matmul mode, the fp32 or head_dim 256 files -- and where each part of the workspace lies; launch_bwd() records
+// plan.route and executes the plan.  The workspace-size queries are the same plan's min_bytes / want_bytes.
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
 #include "fa_device.h"
+#include "fa_bwd_plan.h"
 #include "fa_kernels.h"
 
 namespace aule_hip {
-static bool dkv4_timeline_wanted() { const char* e = std::getenv("AULE_TL"); return e != nullptr && e[0] == 'd' && e[1] == 'k'; }   // AULE_TL=dkv4 (debug library)
 bool bwd_dkv4_applicable(const BwdArgs& a);          // fa_bwd_dkv4_gfx950.hip: the one-wave-per-SIMD dK/dV kernel
 bool bwd_dkv4_forced();
 bool bwd_dkv4_k2(const BwdArgs& a);                    // D = 64: the two-key-blocks-per-wave instance (round 6)
 long long bwd_dkv4_items(const BwdArgs& a);
+int launch_bwd_dkv4(const BwdArgs& a, hipStream_t stream);
+int configure_bwd_dkv4();
 bool bwd_dq4_applicable(const BwdArgs& a);           // fa_bwd_dq4_gfx950.hip: the one-wave-per-SIMD dQ kernel
 int bwd_dq4_mode();
 int launch_bwd_dq4(const BwdArgs& a, float* lse2_out, float* ndelta_out, hipStream_t stream);
 int configure_bwd_dq4();
-int launch_bwd_dkv4(const BwdArgs& a, hipStream_t stream);
-int configure_bwd_dkv4();
 bool bwd_dqs_applicable(const BwdArgs& a);           // fa_bwd_dqs_gfx950.hip: the 5-matmul backward's delta pass and dQ = dS K kernel
 int launch_bwd_delta16(const BwdArgs& a, float* lse2, float* ndelta, hipStream_t stream);
 int launch_bwd_dqs(const BwdArgs& a, hipStream_t stream);
 int configure_bwd_dqs();
 uint64_t bwd_f32_partial_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int causal, int device);   // fa_bwd_f32.hip: planes of its small-grid pieces
+int launch_bwd_f32(const BwdArgs& a, hipStream_t stream);
+int configure_bwd_f32();
+int launch_bwd_d256(const BwdArgs& a, hipStream_t stream);   // fa_bwd_d256_gfx950.hip (head_dim 256, every dtype)
+uint64_t bwd_d256_workspace_bytes(int B, int Hq, int Sq);
 namespace {
 
 // ------------------------------------------------------------------ delta ----
@@ -1056,10 +1063,14 @@ __global__ void __launch_bounds__(256) fa_bwd_reduce_kernel(const ReduceParams p
 // Head split of the dK/dV kernel: a GQA/MQA problem has few (batch, kv-head) units, so the query heads
 // of a group are spread over `gsplit` workgroups (a divisor of g) until the grid covers the chip.
 constexpr int kTargetWorkgroups = 256;  // MI355X: 256 CUs, one 512-thread workgroup each
-inline int dkdv_gsplit(int B, int Hq, int Hkv, int Sk, int causal) {
-    const int g = Hq / Hkv;
-    const int nkb = (Sk + kKvBlock - 1) / kKvBlock;
-    const long long base = (long long)B * Hkv * (causal ? (nkb + 1) / 2 : nkb);
+inline long long dkdv_items(const BwdArgs& a) {   // work items of that kernel before the split: (batch, KV head, 256-key block -- causal: pair)
+    const int nkb = (a.Sk + kKvBlock - 1) / kKvBlock;
+    return (long long)a.B * a.Hkv * (a.causal ? (nkb + 1) / 2 : nkb);
+}
+inline int dkdv_gsplit(const BwdArgs& a) {
+    if (a.Hkv <= 0) return 1;
+    const int g = a.Hq / a.Hkv;
+    const long long base = dkdv_items(a);
     int sp = 1;
     while (sp < g && base * sp < kTargetWorkgroups) {
         int next = sp + 1;
@@ -1083,9 +1094,8 @@ inline uint64_t delta_bytes(int B, int Hq, int Sq) {
 // AULE_HIP_BWD_DS_AUTO_MB (160) and whose dK/dV grid takes the one-wave-per-SIMD kernel anyway, the recompute pair for everything else;
 // AULE_HIP_BWD_MODE=spill | recompute pin either one.
 // AULE_HIP_BWD_DS_CAP_MB (default 8192) bounds the workspace: the batch runs in chunks of as many elements as the caller's buffer holds.
-// What the most recent backward launch of this process ran (aule_hip_debug_last_backward_route; tests pin the mode a shape takes with it)
+// BwdPlan::route of the most recent backward launch of this process (aule_hip_debug_last_backward_route; launch_bwd stores it)
 std::atomic<int> g_last_bwd_route{0};
-enum { kRouteSpill = 1, kRouteDq4 = 2, kRouteDkv4 = 4, kRouteDqOld = 8, kRouteDkvOld = 16, kRouteF32 = 32, kRouteDkv4K2 = 64, kRouteD256 = 128 };
 
 inline int bwd_mode() {   // 0: auto (by AULE_HIP_BWD_DS_AUTO_MB), 1: recompute, 2: spill wherever applicable
     static const int m = [] {
@@ -1095,131 +1105,150 @@ inline int bwd_mode() {   // 0: auto (by AULE_HIP_BWD_DS_AUTO_MB), 1: recompute,
     }();
     return m;
 }
-inline uint64_t bwd_ds_auto_bytes() {
-    static const uint64_t c = [] {
-        const char* e = std::getenv("AULE_HIP_BWD_DS_AUTO_MB");
-        const long long mb = e != nullptr ? std::atoll(e) : 160;
-        return (uint64_t)(mb > 0 ? mb : 0) << 20;
-    }();
-    return c;
+inline uint64_t env_mb(const char* name, long long dflt) {   // a size switch in MB, as bytes
+    const char* e = std::getenv(name);
+    const long long mb = e != nullptr ? std::atoll(e) : dflt;
+    return (uint64_t)(mb > 0 ? mb : 0) << 20;
 }
-inline uint64_t bwd_ds_cap_bytes() {
-    static const uint64_t c = [] {
-        const char* e = std::getenv("AULE_HIP_BWD_DS_CAP_MB");
-        const long long mb = e != nullptr ? std::atoll(e) : 8192;
-        return (uint64_t)(mb > 0 ? mb : 0) << 20;
-    }();
-    return c;
-}
-// does the dispatcher take the one-wave-per-SIMD dK/dV kernel for these sizes?  (the grid rule of launch_bwd_16 below)
-inline bool dkv4_by_grid(int B, int Hq, int Hkv, int Sk, int causal) {
-    if (bwd_dkv4_forced()) return true;
-    const int nkb = (Sk + kKvBlock - 1) / kKvBlock;
-    const long long here = (long long)B * Hkv * (causal ? (nkb + 1) / 2 : nkb) * dkdv_gsplit(B, Hq, Hkv, Sk, causal);
-    const int nkb4 = (Sk + 127) / 128;
-    const long long there = (long long)B * Hkv * (causal ? (nkb4 + 1) / 2 : nkb4);
-    return there >= 192 || there >= here;
-}
-// bytes of dS workspace per batch element if the sizes alone allow the 5-matmul backward, else 0
-inline uint64_t spill_bytes_per_batch(int B, int Hq, int Hkv, int Sq, int Sk, int D, int causal, int dtype) {
-    if (bwd_mode() == 1 || (dtype != kBF16 && dtype != kF16) || (D != 128 && D != 64)) return 0;
-    if (Hkv <= 0 || Hq % Hkv != 0 || Sq <= 0 || Sk <= 0) return 0;
-    BwdArgs t{};
-    t.B = B; t.Hq = Hq; t.Hkv = Hkv; t.Sq = Sq; t.Sk = Sk; t.D = D; t.causal = causal; t.dtype = dtype; t.window = -1; t.coff = 0;
-    if (!bwd_dkv4_applicable(t) || !bwd_dqs_applicable(t) || !dkv4_by_grid(B, Hq, Hkv, Sk, causal)) return 0;
-    const uint64_t pb = (uint64_t)Hkv * (uint64_t)DsLayout::of(Hq, Hkv, Sq, Sk).group_bytes;
-    if (pb > bwd_ds_cap_bytes()) return 0;
-    if (bwd_mode() == 0) {   // auto: only problems whose TOUCHED dS (the causal half) fits the budget.  (The columns are allocated as full
-        // squares -- the address is the stream position -- so a causal problem asks for up to twice the budget of workspace: INTEGRATION.md,
-        // include/aule.h state it; only the touched half travels through the cache.)
-        const uint64_t touched = (uint64_t)B * pb / (causal ? 2 : 1);
-        if (touched > bwd_ds_auto_bytes()) return 0;
-    }
-    return pb;
-}
-inline uint64_t bwd_base_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int causal, int dtype, int device = -1) {
-    uint64_t bytes = delta_bytes(B, Hq, Sq);
-    if (dtype == kF32) bytes += aule_hip::bwd_f32_partial_bytes(B, Hq, Hkv, Sq, Sk, D, causal, device);   // small grids: the key / query range pieces' planes
-    if (dtype != kF32) {
-        bytes += 2 * delta_bytes(B, Hq, Sq);   // L' = LSE log2(e) and - delta, published with delta
-        const int sp = dkdv_gsplit(B, Hq, Hkv, Sk, causal);
-        if (sp > 1) bytes += 2ull * sp * B * Hkv * Sk * D * sizeof(float);
-        bytes = (bytes + 255) / 256 * 256;
-    }
-    return bytes;
+inline uint64_t bwd_ds_auto_bytes() { static const uint64_t c = env_mb("AULE_HIP_BWD_DS_AUTO_MB", 160); return c; }
+inline uint64_t bwd_ds_cap_bytes() { static const uint64_t c = env_mb("AULE_HIP_BWD_DS_CAP_MB", 8192); return c; }
+// The debug inputs of the plan besides BwdArgs::dbg / dbg_dq.  AULE_TL=dkv4: the dK/dV timeline runs the one-wave-per-SIMD kernel whatever
+// the grid.  Debug library only, AULE_DBG_BWD_ONLY=dq / =dkv: one of the two kernels alone (per-kernel times from tools/cbench.cpp without
+// a profiler; the workspace keeps delta / L' of an earlier full call) -- 1 dQ, 2 dK/dV, 0 (anything else) both.
+inline bool dkv4_timeline_wanted() { const char* e = std::getenv("AULE_TL"); return e != nullptr && e[0] == 'd' && e[1] == 'k'; }
+inline int dbg_bwd_only() {
+#ifdef AULE_DEBUG_HOOKS
+    const char* e = std::getenv("AULE_DBG_BWD_ONLY");
+    static const int only = e == nullptr ? 0 : (std::strcmp(e, "dq") == 0 ? 1 : (std::strcmp(e, "dkv") == 0 ? 2 : 0));
+    return only;
+#else
+    return 0;
+#endif
 }
 
+}  // namespace
+
+// ---- the plan: route, workspace layout and sizes of one call (fa_bwd_plan.h).  Every rule of the backward dispatch is stated here, once.
+BwdPlan bwd_plan(const BwdArgs& a) {
+    BwdPlan p;
+    const uint64_t rows = delta_bytes(a.B, a.Hq, a.Sq);
+    if (a.D == 256) {   // (delta only: no partial planes, no dS workspace)
+        p.route = a.dtype == kF32 ? (kRouteD256 | kRouteF32) : kRouteD256;
+        p.min_bytes = p.want_bytes = bwd_d256_workspace_bytes(a.B, a.Hq, a.Sq);
+        return p;
+    }
+    if (a.dtype == kF32) {   // small grids: the key / query range pieces' planes behind delta
+        p.route = kRouteF32;
+        p.min_bytes = p.want_bytes = rows + bwd_f32_partial_bytes(a.B, a.Hq, a.Hkv, a.Sq, a.Sk, a.D, a.causal, a.device);
+        return p;
+    }
+    // 16-bit: L' = LSE log2(e) and - delta are published with delta; the head split's partials; the dS room starts where they end
+    p.gsplit = dkdv_gsplit(a);
+    p.lse2_off = rows; p.ndelta_off = 2 * rows; p.part_off = 3 * rows;
+    uint64_t base = 3 * rows;
+    if (p.gsplit > 1) base += 2ull * p.gsplit * a.B * a.Hkv * a.Sk * a.D * sizeof(float);
+    p.min_bytes = (base + 255) / 256 * 256;
+    p.ds_off = p.want_bytes = p.min_bytes > a.ws_floor ? p.min_bytes : a.ws_floor;
+
+    const bool timeline = dkv4_timeline_wanted();
+    const int only = dbg_bwd_only();
+    // The one-wave-per-SIMD dK/dV kernel (fa_bwd_dkv4_gfx950.hip: 128-key blocks, the whole GQA group inside a workgroup, no head
+    // split / partials / reduce) wherever it covers the chip (>= 192 work items) or has at least as many work items as this
+    // file's kernel would (256-key blocks x head split).  Same box, whole backward, tools/cb_rule.sh: ahead on every shape of the
+    // spread (MHA / GQA, causal or not, ragged, fp16: -0.5 .. -24 %); what stays here is the tiny grid with a big group (fp16 MQA
+    // 32/1 S8192: 32 work items there against 512 here).  AULE_HIP_BWD_DKV=new: wherever it can run.
+    const bool dkv4_can = bwd_dkv4_applicable(a);
+    const auto dkv4_by_grid = [&] {
+        const long long there = bwd_dkv4_items(a);
+        return bwd_dkv4_forced() || there >= 192 || there >= dkdv_items(a) * p.gsplit;
+    };
+
+    // The 5-matmul mode (comment above): where both of its kernels can run, the dK/dV grid takes the one-wave-per-SIMD kernel anyway, no
+    // window masks anything and no debug input asks for something else; in the auto mode only problems whose TOUCHED dS (the causal half)
+    // fits the budget.  (The columns are allocated as full squares -- the address is the stream position -- so a causal problem asks for up
+    // to twice the budget of workspace: INTEGRATION.md, include/aule.h state it; only the touched half travels through the cache.)
+    // The call takes it when the caller's buffer has dS room for at least one batch element, and then runs in chunks of as many as fit.
+    if (bwd_mode() != 1 && only == 0 && a.dbg == nullptr && a.dbg_dq == nullptr && !timeline && a.window <= 0 && a.Sq > 0 && a.Sk > 0 &&
+        dkv4_can && bwd_dqs_applicable(a) && dkv4_by_grid()) {
+        const uint64_t pb = (uint64_t)a.Hkv * (uint64_t)DsLayout::of(a.Hq, a.Hkv, a.Sq, a.Sk).group_bytes;   // dS bytes per batch element
+        const bool fits = pb <= bwd_ds_cap_bytes() && (bwd_mode() == 2 || (uint64_t)a.B * pb / (a.causal ? 2 : 1) <= bwd_ds_auto_bytes());
+        if (fits && pb > 0) {
+            const uint64_t B = (uint64_t)a.B, cap = bwd_ds_cap_bytes() / pb, have = a.ws_bytes > p.ds_off ? (a.ws_bytes - p.ds_off) / pb : 0;
+            p.want_bytes += (cap < B ? cap : B) * pb;
+            p.nb = (int)(have < B ? have : B);
+        }
+    }
+    if (p.nb >= 1) {
+        p.route = kRouteSpill | kRouteDkv4;
+        return p;
+    }
+    // The one-wave-per-SIMD dQ kernel (fa_bwd_dq4_gfx950.hip: 64 query rows per wave, every K / V fragment read feeds two row
+    // blocks; dQ bit-identical to this file's kernel) wherever it can run and the grid has at least 128 work items: ahead or level
+    // on all ten shapes of tools/cb_rule_dq.sh (whole backward -0.2 .. -2.5 %, the 128-item grids level), behind on grids of a few
+    // workgroups (its three-stage stream start and 64-row prologue).  AULE_HIP_BWD_DQ=old|new pin either one.
+    // D = 64 (round 4): ahead on small grids too (16 .. 64 work items: +1.9 .. +7.5 % on the whole backward, profiles/r4_bwd_d64_dkv4.txt) -- no grid rule there.
+    if (only != 2) {
+        const int nqb = (a.Sq + kDqQBlock - 1) / kDqQBlock;
+        const long long dq4_items = (long long)a.B * a.Hq * (a.causal ? (nqb + 1) / 2 : nqb);
+        const bool dq4 = a.dbg_dq == nullptr && bwd_dq4_applicable(a) && (bwd_dq4_mode() == 2 || a.D == 64 || dq4_items >= 128);
+        p.route |= dq4 ? kRouteDq4 : kRouteDqOld;
+    }
+    if (only != 1) {
+        // (timeline instances of the dK/dV kernels: bf16, D = 128 and, round 5, D = 64; stamps without AULE_TL=dkv4 mean this file's kernel)
+        const bool dkv4 = dkv4_can && (timeline || (a.dbg == nullptr && dkv4_by_grid()));
+        p.k2 = dkv4 && bwd_dkv4_k2(a);
+        p.route |= dkv4 ? (p.k2 ? kRouteDkv4 | kRouteDkv4K2 : kRouteDkv4) : kRouteDkvOld;
+    }
+    return p;
+}
+
+namespace {
+
+// ---- executing the plan (16-bit, D <= 128)
+template <class P>
+inline P* ws_at(const BwdArgs& a, uint64_t off) { return reinterpret_cast<P*>(reinterpret_cast<char*>(a.delta) + off); }
+
+// kRouteSpill: delta pass, then per chunk of plan.nb batch elements the spilling dK/dV kernel and dQ = dS K (fa_bwd_dqs_gfx950.hip)
+int launch_bwd_spill(const BwdArgs& a, const BwdPlan& plan, hipStream_t stream) {
+    float* const lse2 = ws_at<float>(a, plan.lse2_off);
+    float* const ndelta = ws_at<float>(a, plan.ndelta_off);
+    int rc = launch_bwd_delta16(a, lse2, ndelta, stream);
+    const size_t rq = (size_t)a.Hq * a.Sq, rk = (size_t)a.Hkv * a.Sk;   // rows per batch element
+    const size_t row = (size_t)a.D * 2;                                 // bytes
+    for (int b0 = 0; rc == 0 && b0 < a.B; b0 += plan.nb) {
+        BwdArgs c = a;
+        c.B = a.B - b0 < plan.nb ? a.B - b0 : plan.nb;
+        c.q = reinterpret_cast<const char*>(a.q) + b0 * rq * row; c.dout = reinterpret_cast<const char*>(a.dout) + b0 * rq * row;
+        c.k = reinterpret_cast<const char*>(a.k) + b0 * rk * row; c.v = reinterpret_cast<const char*>(a.v) + b0 * rk * row;
+        c.dq = reinterpret_cast<char*>(a.dq) + b0 * rq * row;
+        c.dk = reinterpret_cast<char*>(a.dk) + b0 * rk * row; c.dv = reinterpret_cast<char*>(a.dv) + b0 * rk * row;
+        c.lse2 = lse2 + b0 * rq; c.ndelta = ndelta + b0 * rq;
+        c.ds = ws_at<char>(a, plan.ds_off);
+        c.dkv4_k2 = plan.k2;
+        rc = launch_bwd_dkv4(c, stream);
+        if (rc == 0) rc = launch_bwd_dqs(c, stream);
+    }
+    return rc;
+}
+
+// the recompute pair: a dQ kernel (which also publishes delta, L' and - delta), then a dK/dV kernel
 template <class T, int D>
-int launch_bwd_16(const BwdArgs& a, hipStream_t stream) {
-    // (delta = rowsum(O * dO) is computed inside the dQ kernel)
+int launch_bwd_16(const BwdArgs& a, const BwdPlan& plan, hipStream_t stream) {
     BwdParams p;
     p.q = a.q; p.k = a.k; p.v = a.v; p.dout = a.dout; p.lse = a.lse; p.delta = a.delta;
     p.o = a.o; p.delta_out = a.delta;
-    p.lse2_out = reinterpret_cast<float*>(reinterpret_cast<char*>(a.delta) + delta_bytes(a.B, a.Hq, a.Sq));
-    p.ndelta_out = reinterpret_cast<float*>(reinterpret_cast<char*>(a.delta) + 2 * delta_bytes(a.B, a.Hq, a.Sq));
+    p.lse2_out = ws_at<float>(a, plan.lse2_off);
+    p.ndelta_out = ws_at<float>(a, plan.ndelta_off);
     p.dq = a.dq; p.dk = a.dk; p.dv = a.dv;
     p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = a.Sq; p.Sk = a.Sk;
     p.c = a.scale * kLog2e;
     p.scale = a.scale;
     p.window = a.window > 0 ? a.window : 0;
     p.coff = a.causal ? a.coff : 0;
-#ifdef AULE_DEBUG_HOOKS
-    // debug library only: AULE_DBG_BWD_ONLY=dq / =dkv launches one of the two kernels (per-kernel times from tools/cbench.cpp
-    // without a profiler; the workspace keeps delta / L' of an earlier full call)
-    static const int only = [] {
-        const char* e = std::getenv("AULE_DBG_BWD_ONLY");
-        if (e == nullptr) return 0;
-        return std::strcmp(e, "dq") == 0 ? 1 : (std::strcmp(e, "dkv") == 0 ? 2 : 0);   // anything else: both kernels
-    }();
-#else
-    constexpr int only = 0;
-#endif
-    // ---- the 5-matmul backward: no recomputation (see spill_bytes_per_batch above; fa_bwd_dqs_gfx950.hip)
-    if constexpr (D == 128 || D == 64) {
-        const uint64_t pb = (only == 0 && a.dbg == nullptr && a.dbg_dq == nullptr && !dkv4_timeline_wanted() && a.window <= 0 && bwd_dkv4_applicable(a) &&
-                             bwd_dqs_applicable(a))
-                                ? spill_bytes_per_batch(a.B, a.Hq, a.Hkv, a.Sq, a.Sk, D, a.causal, a.dtype) : 0;
-        const uint64_t base = bwd_base_bytes(a.B, a.Hq, a.Hkv, a.Sq, a.Sk, D, a.causal, a.dtype);
-        const uint64_t nb = (pb > 0 && a.ws_bytes > base) ? (a.ws_bytes - base) / pb : 0;
-        if (nb >= 1) {
-            g_last_bwd_route = kRouteSpill | kRouteDkv4;
-            int rc = launch_bwd_delta16(a, p.lse2_out, p.ndelta_out, stream);
-            if (rc) return rc;
-            const size_t rq = (size_t)a.Hq * a.Sq, rk = (size_t)a.Hkv * a.Sk;   // rows per batch element
-            for (int b0 = 0; b0 < a.B; b0 += (int)nb) {
-                BwdArgs c = a;
-                c.B = a.B - b0 < (int)nb ? a.B - b0 : (int)nb;
-                c.q = reinterpret_cast<const char*>(a.q) + b0 * rq * D * 2; c.dout = reinterpret_cast<const char*>(a.dout) + b0 * rq * D * 2;
-                c.k = reinterpret_cast<const char*>(a.k) + b0 * rk * D * 2; c.v = reinterpret_cast<const char*>(a.v) + b0 * rk * D * 2;
-                c.dq = reinterpret_cast<char*>(a.dq) + b0 * rq * D * 2;
-                c.dk = reinterpret_cast<char*>(a.dk) + b0 * rk * D * 2; c.dv = reinterpret_cast<char*>(a.dv) + b0 * rk * D * 2;
-                c.lse2 = p.lse2_out + b0 * rq; c.ndelta = p.ndelta_out + b0 * rq;
-                c.ds = reinterpret_cast<char*>(a.delta) + base;
-                rc = launch_bwd_dkv4(c, stream);
-                if (rc) return rc;
-                rc = launch_bwd_dqs(c, stream);
-                if (rc) return rc;
-            }
-            return 0;
-        }
-    }
-    // The one-wave-per-SIMD dQ kernel (fa_bwd_dq4_gfx950.hip: 64 query rows per wave, every K / V fragment read feeds two row
-    // blocks; dQ bit-identical to this file's kernel) wherever it can run and the grid has at least 128 work items: ahead or level
-    // on all ten shapes of tools/cb_rule_dq.sh (whole backward -0.2 .. -2.5 %, the 128-item grids level), behind on grids of a few
-    // workgroups (its three-stage stream start and 64-row prologue).  AULE_HIP_BWD_DQ=old|new pin either one.
-    const auto dq4_items = [&] {
-        const int nqb = (a.Sq + kDqQBlock - 1) / kDqQBlock;
-        return (long long)a.B * a.Hq * (a.causal ? (nqb + 1) / 2 : nqb);
-    };
-    // D = 64 (round 4): ahead on small grids too (16 .. 64 work items: +1.9 .. +7.5 % on the whole backward, profiles/r4_bwd_d64_dkv4.txt) -- no grid rule there.
-    const bool use_dq4 = (D == 128 || D == 64) && a.dbg_dq == nullptr && bwd_dq4_applicable(a) && (bwd_dq4_mode() == 2 || D == 64 || dq4_items() >= 128);
-    g_last_bwd_route = 0;
-    if (only != 2 && use_dq4) {
-        g_last_bwd_route |= kRouteDq4;
+    if (plan.route & kRouteDq4) {
         int rc = launch_bwd_dq4(a, p.lse2_out, p.ndelta_out, stream);
         if (rc) return rc;
-    } else if (only != 2) {
-        g_last_bwd_route |= kRouteDqOld;
+    } else if (plan.route & kRouteDqOld) {
         const int nqb = (a.Sq + kDqQBlock - 1) / kDqQBlock;
         p.nblk = a.causal ? (nqb + 1) / 2 : nqb;  // causal: one workgroup per Q-block pair (i, n-1-i)
         p.gsplit = 1;
@@ -1245,32 +1274,19 @@ int launch_bwd_16(const BwdArgs& a, hipStream_t stream) {
         int rc = (int)hipGetLastError();
         if (rc) return rc;
     }
-    if (only == 1) return 0;
-    // The one-wave-per-SIMD dK/dV kernel (fa_bwd_dkv4_gfx950.hip: 128-key blocks, the whole GQA group inside a workgroup, no head
-    // split / partials / reduce) wherever it covers the chip (>= 192 work items) or has at least as many work items as this
-    // file's kernel would (256-key blocks x head split).  Same box, whole backward, tools/cb_rule.sh: ahead on every shape of the
-    // spread (MHA / GQA, causal or not, ragged, fp16: -0.5 .. -24 %); what stays here is the tiny grid with a big group (fp16 MQA
-    // 32/1 S8192: 32 work items there against 512 here).
-    const auto use_dkv4 = [&] {
-        if ((D != 128 && D != 64) || !(a.dbg == nullptr || dkv4_timeline_wanted()) || !bwd_dkv4_applicable(a)) return false;   // (timeline instances: bf16, D = 128 and, round 5, D = 64)
-        if (dkv4_timeline_wanted()) return true;
-        return dkv4_by_grid(a.B, a.Hq, a.Hkv, a.Sk, a.causal);   // (ONE statement of the grid rule: the auto mode's workspace plan asks the same helper)
-    };
-    if (use_dkv4())
-    {
-        g_last_bwd_route |= kRouteDkv4;
+    if (plan.route & kRouteDkv4) {
         BwdArgs b = a;
-        if (bwd_dkv4_k2(b)) g_last_bwd_route |= kRouteDkv4K2;
         b.lse2 = p.lse2_out;
         b.ndelta = p.ndelta_out;
+        b.dkv4_k2 = plan.k2;
         return launch_bwd_dkv4(b, stream);
     }
+    if (!(plan.route & kRouteDkvOld)) return 0;   // (AULE_DBG_BWD_ONLY=dq)
     {
-        g_last_bwd_route |= kRouteDkvOld;
         const int nkb = (a.Sk + kKvBlock - 1) / kKvBlock;
         p.nblk = a.causal ? (nkb + 1) / 2 : nkb;  // causal: one workgroup per block pair (i, n-1-i)
-        p.gsplit = dkdv_gsplit(a.B, a.Hq, a.Hkv, a.Sk, a.causal);
-        p.part = reinterpret_cast<float*>(reinterpret_cast<char*>(a.delta) + 3 * delta_bytes(a.B, a.Hq, a.Sq));
+        p.gsplit = plan.gsplit;
+        p.part = ws_at<float>(a, plan.part_off);
         const dim3 grid((unsigned)(p.nblk * a.B * a.Hkv * p.gsplit)), block(512);
         p.dbg = a.dbg;
         bool tl_done = false;
@@ -1315,11 +1331,6 @@ int set_attr_bwd() {
 
 }  // namespace
 
-int launch_bwd_f32(const BwdArgs& a, hipStream_t stream);  // fa_bwd_f32.hip
-int configure_bwd_f32();
-int launch_bwd_d256(const BwdArgs& a, hipStream_t stream);   // fa_bwd_d256_gfx950.hip (head_dim 256, every dtype)
-uint64_t bwd_d256_workspace_bytes(int B, int Hq, int Sq);
-
 // Shared with fa_bwd_f32.hip
 int launch_delta_f32(const BwdArgs& a, hipStream_t stream) {
     DeltaParams dp;
@@ -1341,42 +1352,22 @@ int launch_delta_f32(const BwdArgs& a, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-// What launch_bwd NEEDS (delta, L', - delta, the head-split partials) ...
-uint64_t bwd_workspace_min_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int causal, int dtype, int device) {
-    if (D == 256) return bwd_d256_workspace_bytes(B, Hq, Sq);
-    return bwd_base_bytes(B, Hq, Hkv, Sq, Sk, D, causal, dtype, device);
-}
-// ... and what it WANTS: plus the dS workspace of the 5-matmul backward for as many batch elements as fit the cap (at least one).
-// A caller that passes only the minimum gets the recompute pair.
-// (windowed: the dispatcher keeps windowed problems on the recompute pair -- no dS room is asked for: ADVICE r5)
-uint64_t bwd_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int causal, int dtype, int device, bool windowed) {
-    if (D == 256) return bwd_d256_workspace_bytes(B, Hq, Sq);   // (delta only: no partial planes, no dS workspace)
-    uint64_t bytes = bwd_base_bytes(B, Hq, Hkv, Sq, Sk, D, causal, dtype, device);
-    const uint64_t pb = windowed ? 0 : spill_bytes_per_batch(B, Hq, Hkv, Sq, Sk, D, causal, dtype);
-    if (pb > 0) {
-        uint64_t nb = bwd_ds_cap_bytes() / pb;
-        if (nb > (uint64_t)B) nb = (uint64_t)B;
-        bytes += nb * pb;
-    }
-    return bytes;
-}
-
 int bwd_last_route() { return g_last_bwd_route.load(); }
 
 int launch_bwd(const BwdArgs& a, hipStream_t stream) {
-    if (a.D == 256) {
-        g_last_bwd_route = a.dtype == kF32 ? (kRouteD256 | kRouteF32) : kRouteD256;
-        return launch_bwd_d256(a, stream);
-    }
-    if (a.dtype == kF32) { g_last_bwd_route = kRouteF32; return launch_bwd_f32(a, stream); }
+    const BwdPlan plan = bwd_plan(a);
+    g_last_bwd_route = plan.route;
+    if (plan.route & kRouteD256) return launch_bwd_d256(a, stream);
+    if (plan.route & kRouteF32) return launch_bwd_f32(a, stream);
+    if (plan.route & kRouteSpill) return launch_bwd_spill(a, plan, stream);
     if (a.dtype == kBF16) {
-        if (a.D == 128) return launch_bwd_16<Bf16Traits, 128>(a, stream);
-        if (a.D == 64) return launch_bwd_16<Bf16Traits, 64>(a, stream);
-        if (a.D == 32) return launch_bwd_16<Bf16Traits, 32>(a, stream);
+        if (a.D == 128) return launch_bwd_16<Bf16Traits, 128>(a, plan, stream);
+        if (a.D == 64) return launch_bwd_16<Bf16Traits, 64>(a, plan, stream);
+        if (a.D == 32) return launch_bwd_16<Bf16Traits, 32>(a, plan, stream);
     } else if (a.dtype == kF16) {
-        if (a.D == 128) return launch_bwd_16<F16Traits, 128>(a, stream);
-        if (a.D == 64) return launch_bwd_16<F16Traits, 64>(a, stream);
-        if (a.D == 32) return launch_bwd_16<F16Traits, 32>(a, stream);
+        if (a.D == 128) return launch_bwd_16<F16Traits, 128>(a, plan, stream);
+        if (a.D == 64) return launch_bwd_16<F16Traits, 64>(a, plan, stream);
+        if (a.D == 32) return launch_bwd_16<F16Traits, 32>(a, plan, stream);
     }
     return -1;
 }

@@ -92,7 +92,7 @@ struct BwdArgs {
     void* dq;
     void* dk;
     void* dv;
-    float* delta;  // workspace of bwd_workspace_bytes(): delta [B,Hq,Sq] fp32 first
+    float* delta;  // the workspace (layout and sizes: BwdPlan, fa_bwd_plan.h): delta [B,Hq,Sq] fp32 first
     const float* lse2 = nullptr;   // internal (16-bit path): L' = LSE log2(e) [B,Hq,Sq], published by the dQ kernel behind delta
     const float* ndelta = nullptr; // internal (16-bit path): - delta, behind L' (the C operand the one-wave-per-SIMD dK/dV kernel starts dP from)
     int B, Hq, Hkv, Sq, Sk, D;
@@ -104,7 +104,9 @@ struct BwdArgs {
     unsigned long long* dbg = nullptr;   // debug: s_memtime stamps of the dK/dV kernel's workgroup 0 (bf16 D128 causal)
     unsigned long long* dbg_dq = nullptr;   // ... of the dQ kernel's workgroup 0
     void* ds = nullptr;            // internal (16-bit path, 5-matmul backward): the dS workspace of this call's batch chunk (DsLayout)
-    uint64_t ws_bytes = 0;         // bytes behind `delta` (0 = just bwd_workspace_min_bytes(): the recompute pair runs)
+    uint64_t ws_bytes = 0;         // bytes behind `delta` (0 = just BwdPlan::min_bytes: the recompute pair runs)
+    uint64_t ws_floor = 0;         // the dS room starts no lower than this: the minimum of the problem as the caller stated and sized it (aule_capi.cpp: fill_bwd_args)
+    bool dkv4_k2 = false;          // internal (launch_bwd_dkv4, D = 64): BwdPlan::k2, the two-key-blocks-per-wave instance
     int device = -1;               // the descriptor's device ordinal (-1: the current one): the grid-sizing rules ask THAT device's CU count (as FwdArgs::device)
 };
 
@@ -187,16 +189,7 @@ void work_order_dump(int ranked, int bid, int B, int Hq, int Hkv, int nblk, int 
 uint64_t fwd_workspace_bytes(FwdArgs a);
 uint64_t paged_workspace_bytes(PagedArgs a);
 int launch_bwd(const BwdArgs& a, hipStream_t stream);
-// bit mask of what the most recent launch_bwd of this process ran: 1 the 5-matmul mode (delta pass + spilling dK/dV kernel + dQ = dS K),
-// 2 / 4 the one-wave-per-SIMD dQ / dK/dV kernel, 8 / 16 their two-waves-per-SIMD predecessors, 32 the fp32 kernels, 64 (with 4) the D = 64
-// dK/dV instance with two key blocks per wave, 128 the head_dim 256 kernels (fa_bwd_d256_gfx950.hip; with 32 for fp32); 0 before the first
-int bwd_last_route();
-
-// Bytes of device workspace launch_bwd needs: delta [B,Hq,Sq] fp32, plus (16-bit GQA/MQA problems that
-// do not fill the chip) fp32 dK/dV partials of the head-split dK/dV kernel.
-uint64_t bwd_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int causal, int dtype, int device = -1, bool windowed = false);
-// ... of which launch_bwd cannot do without (the rest is the dS workspace of the 5-matmul backward: fa_bwd_gfx950.hip)
-uint64_t bwd_workspace_min_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int causal, int dtype, int device = -1);
+int bwd_last_route();   // BwdPlan::route of the most recent launch_bwd of this process (fa_bwd_plan.h: the plan, the workspace sizes); 0 before the first
 
 // Set the max-dynamic-LDS attribute on every kernel (call once per device).
 int configure_kernels();

@@ -300,6 +300,11 @@ int32_t aule_hip_debug_forward_route(const aule_attn_desc* desc);
 /* 0 before the first backward.  Lets a test assert                                                                                   */
 /* the mode a shape takes by itself.                                                                                      */
 int32_t aule_hip_debug_last_backward_route(void);
+/* Debug: the same bit mask (BwdRoute, csrc/fa_bwd_plan.h) for the call aule_attention_backward_ex(desc) WOULD make with                */
+/* desc->workspace_bytes bytes of workspace: the launch plan, not a launch.  -3 for a descriptor that call refuses on shape grounds       */
+/* (struct_size, dtype, head_dim, head ratio, causal code, workspace_bytes below the minimum).  Host logic only, no aule_init(), no      */
+/* pointer of the descriptor is read.                                                                                                 */
+int32_t aule_hip_debug_backward_route(const aule_attn_bwd_desc* desc);
 /* Debug: the causal-split plan of route 7 (small causal grids) as integers -- out = {pieces n, pairs, then per pair of   */
 /* Q blocks: tiles of the far block, of the near block, cut positions b[0..8]}; returns the ints written (negative: the */
 /* capacity needed), 0 when the shape does not take that route.  Host logic only.                                       */

@@ -82,6 +82,23 @@ for B, Hq, Hkv, S, D, causal in ((1, 1, 1, 1, 32, 0), (4, 32, 8, 2048, 128, 1), 
     b.dtype = 2
     b.batch, b.heads_q, b.heads_kv, b.seq_q, b.seq_k, b.head_dim, b.causal = B, Hq, Hkv, S, S, D, causal
     assert lib.aule_attention_backward_workspace_size(ctypes.byref(b)) >= 4 * B * Hq * S
+# --- the backward's launch plan (fa_bwd_plan.h) through its pure hook: null, struct_size 0, the sweep of tests/bwd_sweep.py
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
+import bwd_sweep
+assert lib.aule_hip_debug_backward_route(None) == -3
+assert lib.aule_hip_debug_backward_route(ctypes.byref(_capi.AttnBwdDesc())) == -3
+broutes = set()
+for dt, B, hq, hkv, sq, sk, D, c, w in bwd_sweep.cases():
+    b = _capi.AttnBwdDesc()
+    b.struct_size = ctypes.sizeof(_capi.AttnBwdDesc)
+    b.dtype, b.causal, b.window_size = dt, c, w
+    b.batch, b.heads_q, b.heads_kv, b.seq_q, b.seq_k, b.head_dim = B, hq, hkv, sq, sk, D
+    for ws in (lib.aule_attention_backward_workspace_size(ctypes.byref(b)), 0, 2 ** 64 - 1):
+        b.workspace_bytes = ws
+        r = lib.aule_hip_debug_backward_route(ctypes.byref(b))
+        assert r == -3 if ws == 0 else 0 < r < 256, (dt, B, hq, hkv, sq, sk, D, c, w, ws, r)
+        broutes.add(r)
+assert {-3, 5, 6, 24, 32, 70, 128, 160} <= broutes, sorted(broutes)
 print("SANITIZED-OK", n, sorted(routes.items()))
 '''
 

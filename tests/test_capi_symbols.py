@@ -403,3 +403,73 @@ def test_backward_workspace_plans_without_a_device():
     assert auto["F32B"] == rows(4, 8, 512) + 2 * 4 * (4 * 8 * 512) * 64 * 4        # delta + max(dQ planes, dK + dV planes) of 4 pieces
     off = _ws_sizes({"AULE_HIP_F32_SPLIT": "0"})
     assert off["F32F"] == 0 and off["F32B"] == rows(4, 8, 512)
+
+
+def test_backward_workspace_sizes_match_the_recorded_table():
+    """aule_attention_backward_workspace_size over the fixed sweep of tests/bwd_sweep.py, per mode switch, value for value against
+    tests/golden/bwd_workspace_sweep.npz -- recorded from the library as it was before bwd_plan() (fa_bwd_plan.h) became the one
+    statement of the backward's route, workspace layout and sizes.  Without a device the CU count answers 256, the MI355X's own,
+    so the table holds on both machines.  A difference is a bug in the plan, not a table to regenerate."""
+    import numpy as np
+    import bwd_sweep
+    gold = np.load(bwd_sweep.FIXTURE)
+    assert sorted(gold.files) == sorted(bwd_sweep.LEGS) and len(bwd_sweep.cases()) == 5184
+    for leg, env in bwd_sweep.LEGS.items():
+        got = np.asarray(bwd_sweep.run_leg(env)["want"], dtype=np.int64)
+        bad = np.nonzero(got != gold[leg])[0]
+        assert bad.size == 0, (leg, bad.size, [(bwd_sweep.cases()[i], int(got[i]), int(gold[leg][i])) for i in bad[:5]])
+
+
+def test_backward_route_hook_follows_the_dispatch_rules():
+    """aule_hip_debug_backward_route (host logic: the plan of the launch) over the same sweep and switches, with the workspace the
+    size query asks for and with the minimum (the recompute leg of the table: no dS room is ever asked for there)."""
+    import numpy as np
+    import bwd_sweep
+    SPILL, DQ4, DKV4, DQ_OLD, DKV_OLD, F32, K2, D256 = 1, 2, 4, 8, 16, 32, 64, 128
+    gold = np.load(bwd_sweep.FIXTURE)
+    least = [int(x) for x in gold["recompute"]]
+    seen = set()
+    for leg, env in bwd_sweep.LEGS.items():
+        got = bwd_sweep.run_leg(env, extra_ws=least)
+        assert got["want"] == [int(x) for x in gold[leg]]
+        for case, want, lo, r_want, r_least in zip(bwd_sweep.cases(), got["want"], least, got["route_want"], got["route_extra"]):
+            dt, B, hq, hkv, sq, sk, D, c, w = case
+            masks = w > 0 and w < sq + (sk - sq if c == 2 else 0)
+            for r, ws in ((r_want, want), (r_least, lo)):
+                ctx = (leg, case, ws, r)
+                if D == 256:
+                    assert r == (D256 | F32 if dt == 0 else D256), ctx
+                elif dt == 0:
+                    assert r == F32, ctx
+                elif r & SPILL:
+                    assert r == SPILL | DKV4 and D in (64, 128), ctx
+                    assert ws > lo and not masks and leg != "recompute", ctx
+                else:
+                    assert r > 0 and r & ~(DQ4 | DKV4 | DQ_OLD | DKV_OLD | K2) == 0, ctx
+                    assert bool(r & DQ4) != bool(r & DQ_OLD) and bool(r & DKV4) != bool(r & DKV_OLD), ctx
+                    assert not r & K2 or (r & DKV4 and D == 64), ctx
+                    assert D != 32 or r == DQ_OLD | DKV_OLD, ctx
+                seen.add(r)
+            assert not r_least & SPILL, (leg, case)
+    assert {SPILL | DKV4, DQ4 | DKV4, DQ4 | DKV4 | K2, DQ4 | DKV_OLD, DQ_OLD | DKV_OLD, F32, D256, D256 | F32} <= seen, sorted(seen)
+    # the shapes the GPU tests pin through aule_hip_debug_last_backward_route, and one byte less than the minimum
+    pins = [(2, 8, 32, 32, 2048, 2048, 64, 1, -1), (2, 4, 32, 8, 2048, 2048, 128, 1, -1), (2, 1, 8, 8, 2048, 2048, 128, 1, -1)]
+    got = bwd_sweep.run_leg({}, cases=pins)
+    assert got["route_want"][0] == DQ4 | DKV4 | K2 and got["route_want"][1] == DQ4 | DKV4 and got["route_want"][2] & SPILL, got
+    rec = bwd_sweep.run_leg({"AULE_HIP_BWD_MODE": "recompute"}, cases=pins)
+    short = bwd_sweep.run_leg({}, extra_ws=[x - 1 for x in rec["want"]], cases=pins)
+    assert rec["route_want"] == [DQ4 | DKV4 | K2, DQ4 | DKV4, DQ_OLD | DKV4] and short["route_extra"] == [-3, -3, -3], (rec, short)
+    lib = _capi.load()
+    assert lib.aule_hip_debug_backward_route(None) == -3
+    d = _capi.AttnBwdDesc()
+    assert lib.aule_hip_debug_backward_route(ctypes.byref(d)) == -3          # struct_size 0
+    d.struct_size = ctypes.sizeof(_capi.AttnBwdDesc)
+    d.dtype, d.batch, d.heads_q, d.heads_kv, d.seq_q, d.seq_k, d.head_dim, d.workspace_bytes = 2, 1, 8, 8, 256, 256, 128, 1 << 30
+    assert lib.aule_hip_debug_backward_route(ctypes.byref(d)) > 0
+    for field, bad in (("dtype", 3), ("head_dim", 96), ("heads_kv", 3), ("heads_kv", 0), ("causal", 3), ("seq_k", 0)):
+        good = getattr(d, field)
+        setattr(d, field, bad)
+        assert lib.aule_hip_debug_backward_route(ctypes.byref(d)) == -3, field
+        setattr(d, field, good)
+    d.seq_q, d.causal = 512, 2                                               # bottom-right needs seq_k >= seq_q
+    assert lib.aule_hip_debug_backward_route(ctypes.byref(d)) == -3
