@@ -160,6 +160,36 @@ def quantize_kv_cache_fp8(cache, per_head=True):
 flash_attention_paged = flash_attention_paged_amd
 
 
+def paged_kv_append(key, value, k_cache, v_cache, slot_mapping, k_scale=None, v_scale=None, cos=None, sin=None, positions=None):
+    """The write side of the paged KV cache: put the K and V rows of T new tokens into the caches flash_attention_paged_amd
+    reads, in place, with one launch; returns None.
+
+        key, value [T, heads_kv, head_dim] fp16 / bf16 (last dimension contiguous, other strides free);
+        k_cache, v_cache [num_blocks, block_size, heads_kv, head_dim] contiguous, key's dtype or both torch.float8_e4m3fn;
+        slot_mapping [T] integer = block * block_size + offset (see paged_slot_mapping); negative or past the cache: skipped;
+        two tokens with the same slot in one call: which one wins is unspecified.
+
+    FP8 caches: code = cast(clamp(x / scale[hk], -448, 448)) -- quantize_kv_cache_fp8 with given scales, bit for bit --
+    k_scale / v_scale each None (1.0), a float, a 0-d tensor or a [heads_kv] tensor.  cos, sin, positions: rotate K (not V)
+    by table row positions[t] first (half-split pairs; rounded to key's dtype, then quantised: bit-identical to the rotation
+    pass followed by the plain append).  Argument errors are ValueErrors raised before the device is touched; CPU tensors
+    raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_kv_append as impl
+    return impl(key, value, k_cache, v_cache, slot_mapping, k_scale=k_scale, v_scale=v_scale, cos=cos, sin=sin,
+                positions=positions)
+
+
+def paged_slot_mapping(block_tables, positions, block_size, seq_ids=None):
+    """slots[t] = block_tables[seq_ids[t], positions[t] // block_size] * block_size + positions[t] % block_size (int64) for
+    paged_kv_append; seq_ids defaults to arange(T), the decode case; negative positions give -1.  Plain torch; works on CPU."""
+    from ._torch import paged_slot_mapping as impl
+    return impl(block_tables, positions, block_size, seq_ids=seq_ids)
+
+
 # =============================================================================
 # RoPE (SURVEY.md 8f row N1; reference python/aule/triton_flash.py:561-703, exported at __init__.py:72-75)
 # =============================================================================
@@ -347,7 +377,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "quantize_kv_cache_fp8",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

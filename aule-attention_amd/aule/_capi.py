@@ -136,6 +136,39 @@ class RopeDesc(ctypes.Structure):
     ]
 
 
+class KvAppendDesc(ctypes.Structure):
+    """struct aule_kv_append_desc (include/aule.h): the paged KV cache append."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("cache_dtype", ctypes.c_int32),
+        ("num_tokens", ctypes.c_uint32),
+        ("heads_kv", ctypes.c_uint32),
+        ("head_dim", ctypes.c_uint32),
+        ("num_blocks", ctypes.c_uint32),
+        ("block_size", ctypes.c_uint32),
+        ("key_token_stride", ctypes.c_int64),
+        ("key_head_stride", ctypes.c_int64),
+        ("value_token_stride", ctypes.c_int64),
+        ("value_head_stride", ctypes.c_int64),
+        ("table_len", ctypes.c_uint32),
+        ("table_pitch", ctypes.c_uint32),
+        ("device", ctypes.c_int32),
+        ("reserved", ctypes.c_uint32),
+        ("stream", ctypes.c_void_p),
+        ("key", ctypes.c_void_p),
+        ("value", ctypes.c_void_p),
+        ("k_cache", ctypes.c_void_p),
+        ("v_cache", ctypes.c_void_p),
+        ("slot_mapping", ctypes.c_void_p),
+        ("k_scale", ctypes.c_void_p),
+        ("v_scale", ctypes.c_void_p),
+        ("cos", ctypes.c_void_p),
+        ("sin", ctypes.c_void_p),
+        ("positions", ctypes.c_void_p),
+    ]
+
+
 class AttnRope(ctypes.Structure):
     """struct aule_attn_rope (include/aule.h): the query rotation fused into the forward kernel."""
     _fields_ = [
@@ -151,6 +184,7 @@ class AttnRope(ctypes.Structure):
 
 
 ROPE_HALF, ROPE_INTERLEAVED = 0, 1
+KV_CACHE_SAME, KV_CACHE_FP8_E4M3 = 0, 1
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
 
 # Every symbol include/aule.h declares: (name, restype, argtypes)
@@ -198,6 +232,7 @@ SIGNATURES = [
     ("aule_attention_backward_workspace_size", _U64, [ctypes.POINTER(AttnBwdDesc)]),
     ("aule_attention_paged_decode_ex", _I32, [ctypes.POINTER(PagedDesc)]),
     ("aule_rope_ex", _I32, [ctypes.POINTER(RopeDesc)]),
+    ("aule_kv_cache_append_ex", _I32, [ctypes.POINTER(KvAppendDesc)]),
     ("aule_attention_forward_rope_ex", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(AttnRope)]),
     ("aule_attention_forward_rope_fusable", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(AttnRope)]),
     ("aule_attention_forward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(AttnDesc)]),

@@ -479,3 +479,139 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, wi
     else:
         _capi.check(lib.aule_attention_paged_decode_ex(ctypes.byref(d)), "aule_attention_paged_decode_ex")
     return out
+
+
+def paged_slot_mapping(block_tables, positions, block_size, seq_ids=None):
+    """Cache slots of tokens at `positions` of their sequences, for paged_kv_append:
+
+        slots[t] = block_tables[seq_ids[t], positions[t] // block_size] * block_size + positions[t] % block_size
+
+    block_tables [num_seqs, max_blocks] integer, positions [T] integer, seq_ids [T] integer (default arange(T): the
+    decode case, one new token per sequence).  A negative position gives slot -1, which the append skips.  Returns int64
+    on block_tables' device.  Plain torch ops; works on CPU tensors."""
+    block_size = int(block_size)
+    if block_size <= 0:
+        raise ValueError(f"block_size must be positive, got {block_size}")
+    if block_tables.dim() != 2 or positions.dim() != 1:
+        raise ValueError("expected block_tables [num_seqs, max_blocks] and positions [num_tokens]")
+    dev = block_tables.device
+    pos = positions.to(device=dev, dtype=torch.int64)
+    T = pos.shape[0]
+    if seq_ids is None:
+        if T > block_tables.shape[0]:
+            raise ValueError(f"{T} positions for {block_tables.shape[0]} sequences: pass seq_ids for more than one token per sequence")
+        seq = torch.arange(T, device=dev, dtype=torch.int64)
+    else:
+        seq = seq_ids.to(device=dev, dtype=torch.int64)
+        if seq.shape != pos.shape:
+            raise ValueError("seq_ids must have the shape of positions")
+    skip = pos < 0
+    p = torch.where(skip, torch.zeros_like(pos), pos)
+    blk = block_tables[seq, torch.div(p, block_size, rounding_mode="floor")].to(torch.int64)
+    slots = blk * block_size + p % block_size
+    return torch.where(skip, torch.full_like(slots, -1), slots)
+
+
+def paged_kv_append(key, value, k_cache, v_cache, slot_mapping, k_scale=None, v_scale=None, cos=None, sin=None, positions=None):
+    """Write the K and V rows of T new tokens into the paged caches, in place, with one launch (csrc/kv_append_gfx950.hip):
+
+        key, value     [T, heads_kv, head_dim] fp16 / bf16; the last dimension contiguous, token and head strides free
+                       (slices of a fused QKV projection, k[b].transpose(0, 1) of a [B, Hkv, S, D] tensor: no copy)
+        k_cache, v_cache [num_blocks, block_size, heads_kv, head_dim], contiguous: key's dtype (rows are copied bit for
+                       bit) or both torch.float8_e4m3fn (code = cast(clamp(x / scale[hk], -448, 448)), exactly
+                       quantize_kv_cache_fp8 with given scales; k_scale / v_scale as in paged_decode)
+        slot_mapping   [T] integer: block * block_size + offset (paged_slot_mapping); a negative slot or one past the cache
+                       is skipped; two tokens with the same slot in one call: which one wins is unspecified
+        cos, sin, positions: rotate K (never V) first -- half-split pairs, token t uses table row positions[t], the
+                       arithmetic of rope_raw, rounded to key's dtype before any quantisation (bit-identical to rope_raw
+                       followed by the un-rotated append).  A token with a skipped slot needs no valid position; a position
+                       outside the table skips the token.
+    Returns None.  No device->host synchronisation; captures into a graph.  All argument errors are ValueErrors raised
+    before the device is touched; CPU tensors are an AuleError (there is no fallback)."""
+    if key.dim() != 3 or value.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("expected key/value [T,Hkv,D] and k_cache/v_cache [num_blocks, block_size, Hkv, D]")
+    if value.shape != key.shape:
+        raise ValueError(f"key/value shape mismatch: key={tuple(key.shape)}, value={tuple(value.shape)}")
+    if v_cache.shape != k_cache.shape:
+        raise ValueError(f"k_cache/v_cache shape mismatch: k_cache={tuple(k_cache.shape)}, v_cache={tuple(v_cache.shape)}")
+    T, Hkv, D = key.shape
+    num_blocks, block_size, Hc, Dc = k_cache.shape
+    if Dc != D:
+        raise ValueError(f"head_dim mismatch: key={D}, cache={Dc}")
+    if Hc != Hkv:
+        raise ValueError(f"heads_kv mismatch: key={Hkv}, cache={Hc}")
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"k_cache ({k_cache.dtype}) and v_cache ({v_cache.dtype}) must have the same dtype")
+    other_fp8 = tuple(t for t in (getattr(torch, n, None) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz"))
+                      if t is not None)
+    if k_cache.dtype in other_fp8:
+        raise ValueError(f"{k_cache.dtype} caches are not supported: the paged KV append writes torch.float8_e4m3fn only "
+                         "(gfx950 converts OCP e4m3fn in hardware; e4m3fnuz is MI300X's encoding, e5m2 is not built)")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if key.dtype not in (torch.float16, torch.bfloat16) or value.dtype != key.dtype or (not fp8 and k_cache.dtype != key.dtype):
+        raise ValueError("paged KV append runs in fp16 or bf16 (key, value and caches in the same dtype, or float8_e4m3fn "
+                         "caches with fp16 / bf16 key and value)")
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError("k_scale / v_scale apply to float8_e4m3fn caches only; a 16-bit cache holds the values themselves")
+    if D not in PAGED_HEAD_DIMS:
+        raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS} for the paged KV cache, got {D}")
+    if not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise ValueError("k_cache and v_cache must be contiguous: the append writes in place and cannot copy them")
+    if block_size == 0 or Hkv == 0:
+        raise ValueError("block_size and heads_kv must be positive")
+    for name, t in (("key", key), ("value", value)):
+        if t.stride(2) != 1:
+            raise ValueError(f"the last dimension of {name} must be contiguous, got stride {t.stride(2)}")
+        if T > 1 and t.stride(0) < D or Hkv > 1 and t.stride(1) < D:
+            raise ValueError(f"{name}: token / head strides {tuple(t.stride()[:2])} are smaller than a row of {D} elements")
+        if (T > 1 and t.stride(0) % 8) or (Hkv > 1 and t.stride(1) % 8) or t.storage_offset() % 8:
+            raise ValueError(f"{name}: rows must be 16-byte aligned (token / head strides and the storage offset multiples of 8 elements)")
+    if slot_mapping.dim() != 1 or slot_mapping.shape[0] != T or slot_mapping.dtype.is_floating_point or slot_mapping.dtype == torch.bool:
+        raise ValueError(f"slot_mapping must be an integer tensor of shape [{T}]")
+    rope = cos is not None or sin is not None or positions is not None
+    if rope:
+        if cos is None or sin is None:
+            raise ValueError("cos and sin are required for RoPE (both or neither)")
+        if positions is None:
+            raise ValueError("positions are required with cos / sin: token t is rotated by table row positions[t]")
+        if positions.dim() != 1 or positions.shape[0] != T or positions.dtype.is_floating_point or positions.dtype == torch.bool:
+            raise ValueError(f"positions must be an integer tensor of shape [{T}]")
+        if cos.shape[-1] != D // 2 or sin.shape[-1] != D // 2:
+            raise ValueError(f"cos/sin must have shape [..., {D // 2}], got {tuple(cos.shape)} / {tuple(sin.shape)}")
+    if fp8:
+        for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if torch.is_tensor(s) and not (s.dim() == 0 or s.shape == (1,) or s.shape == (Hkv,)):
+                raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
+    if not key.is_cuda:
+        raise _capi.AuleError("aule (HIP build): the paged KV append needs ROCm device tensors; there is no CPU fallback")
+    _same_device("paged KV append", key, value, k_cache, v_cache)
+    if T == 0 or num_blocks == 0:
+        return None
+    lib = _capi.get_lib()
+    dev = key.device
+    slots = slot_mapping.to(device=dev, dtype=torch.int64).contiguous()
+    d = _capi.KvAppendDesc()
+    d.struct_size = ctypes.sizeof(_capi.KvAppendDesc)
+    d.dtype = _DTYPES[key.dtype]
+    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    d.num_tokens, d.heads_kv, d.head_dim, d.num_blocks, d.block_size = T, Hkv, D, num_blocks, block_size
+    # (a stride of a dimension of extent 1 is never used: torch reports anything there)
+    d.key_token_stride = key.stride(0) if T > 1 else Hkv * max(key.stride(1), D)
+    d.key_head_stride = key.stride(1) if Hkv > 1 else D
+    d.value_token_stride = value.stride(0) if T > 1 else Hkv * max(value.stride(1), D)
+    d.value_head_stride = value.stride(1) if Hkv > 1 else D
+    d.device = dev.index if dev.index is not None else torch.cuda.current_device()
+    d.stream = _stream_ptr(dev)
+    d.key, d.value, d.k_cache, d.v_cache = key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
+    d.slot_mapping = slots.data_ptr()
+    if fp8:
+        ks = _fp8_scale(k_scale, Hkv, dev, "k_scale")
+        vs = _fp8_scale(v_scale, Hkv, dev, "v_scale")
+        d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
+    if rope:
+        c, s = _rope_tables(cos, sin, D, dev)
+        pos = positions.to(device=dev, dtype=torch.int64).contiguous()
+        d.table_len, d.table_pitch = c.shape[0], c.stride(0)
+        d.cos, d.sin, d.positions = c.data_ptr(), s.data_ptr(), pos.data_ptr()
+    _capi.check(lib.aule_kv_cache_append_ex(ctypes.byref(d)), "aule_kv_cache_append_ex")
+    return None

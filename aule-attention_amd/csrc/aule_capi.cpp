@@ -40,6 +40,11 @@ static_assert(offsetof(aule_paged_fp8_desc, q) == offsetof(aule_paged_desc, q) &
                   offsetof(aule_paged_fp8_desc, k_scale) == sizeof(aule_paged_desc),
               "aule_paged_fp8_desc starts with aule_paged_desc (the paged entry points read both through that prefix)");
 static_assert(sizeof(aule_attn_bwd_desc) == 144, "aule_attn_bwd_desc layout is part of the ABI");
+static_assert(sizeof(aule_kv_append_desc) == 168 && offsetof(aule_kv_append_desc, key_token_stride) == 32 &&
+                  offsetof(aule_kv_append_desc, table_len) == 64 && offsetof(aule_kv_append_desc, stream) == 80 &&
+                  offsetof(aule_kv_append_desc, k_cache) == 104 && offsetof(aule_kv_append_desc, slot_mapping) == 120 &&
+                  offsetof(aule_kv_append_desc, cos) == 144 && offsetof(aule_kv_append_desc, positions) == 160,
+              "aule_kv_append_desc layout is part of the ABI");
 
 namespace {
 
@@ -976,6 +981,74 @@ int32_t aule_rope_ex(const aule_rope_desc* d) {
     const int rc = aule_hip::launch_rope(r, (hipStream_t)d->stream);
     if (rc != 0) {
         set_error("RoPE failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
+        return -4;
+    }
+    return 0;
+}
+
+// 0 fine, else the reason the descriptor is refused (host logic only: no pointer is dereferenced)
+static const char* kv_append_error(const aule_kv_append_desc* d) {
+    if (d == nullptr || d->struct_size != sizeof(aule_kv_append_desc)) return "bad descriptor (struct_size mismatch)";
+    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return "dtype (of key / value) must be fp16 or bf16";
+    if (d->cache_dtype != AULE_KV_CACHE_SAME && d->cache_dtype != AULE_KV_CACHE_FP8_E4M3)
+        return "cache_dtype must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3";
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return "head_dim unsupported (32, 64 or 128)";
+    if (d->heads_kv == 0 || d->block_size == 0) return "heads_kv and block_size must be positive";
+    const int64_t D = (int64_t)d->head_dim;
+    const int64_t strides[4] = {d->key_token_stride, d->key_head_stride, d->value_token_stride, d->value_head_stride};
+    for (int64_t st : strides) {
+        if (st < D) return "a token / head stride is smaller than a row (head_dim elements)";
+        if (st % 8 != 0) return "token / head strides must be multiples of 8 elements (16-byte loads)";
+    }
+    const bool any_rope = d->cos || d->sin || d->positions || d->table_len || d->table_pitch;
+    const bool all_rope = d->cos && d->sin && d->positions && d->table_len;
+    if (any_rope && !all_rope) return "RoPE group only partly given (cos, sin, positions and table_len go together)";
+    if (all_rope) {
+        if (d->head_dim & 1) return "head_dim must be even for RoPE";
+        if (d->table_pitch != 0 && (d->table_pitch < d->head_dim / 2 || d->table_pitch % 4 != 0))
+            return "table_pitch must be 0 or a multiple of 4 that is >= head_dim/2";
+    }
+    if (d->num_tokens == 0) return nullptr;
+    if (!d->key || !d->value || !d->k_cache || !d->v_cache || !d->slot_mapping) return "null tensor pointer";
+    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
+    if (fp8 && (!d->k_scale || !d->v_scale)) return "null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)";
+    if (!fp8 && (d->k_scale || d->v_scale)) return "k_scale / v_scale apply to FP8 caches only; a 16-bit cache holds the values themselves";
+    const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
+    if (misaligned(d->key) || misaligned(d->value) || misaligned(d->k_cache) || misaligned(d->v_cache) || misaligned(d->cos) || misaligned(d->sin))
+        return "key, value, the caches and the tables must be 16-byte aligned";
+    return nullptr;
+}
+
+int32_t aule_kv_cache_append_ex(const aule_kv_append_desc* d) {
+    RoctxRange range("aule.kv_cache_append");
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_init) {
+        set_error("Library not initialized. Call aule_init() first.");
+        return -1;
+    }
+    if (const char* why = kv_append_error(d)) {
+        set_error("KV cache append failed: %s", why);
+        return -3;
+    }
+    if (d->num_tokens == 0) return 0;
+    aule_hip::KvAppendArgs a;
+    a.key = d->key; a.value = d->value; a.k_cache = d->k_cache; a.v_cache = d->v_cache;
+    a.slot_mapping = reinterpret_cast<const long long*>(d->slot_mapping);
+    a.T = (int)d->num_tokens; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
+    a.num_blocks = (long long)d->num_blocks; a.block_size = (int)d->block_size;
+    a.k_token_stride = d->key_token_stride; a.k_head_stride = d->key_head_stride;
+    a.v_token_stride = d->value_token_stride; a.v_head_stride = d->value_head_stride;
+    a.dtype = d->dtype;
+    if (d->cache_dtype == AULE_KV_CACHE_FP8_E4M3) {
+        a.cache_kind = aule_hip::kCacheFp8E4M3;
+        a.k_scale = d->k_scale; a.v_scale = d->v_scale;
+    }
+    a.cos = d->cos; a.sin = d->sin; a.positions = reinterpret_cast<const long long*>(d->positions);
+    a.table_len = (long long)d->table_len; a.table_pitch = (int)d->table_pitch;
+    DeviceGuard g(d->device);
+    const int rc = aule_hip::launch_kv_append(a, (hipStream_t)d->stream);
+    if (rc != 0) {
+        set_error("KV cache append failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
         return -4;
     }
     return 0;

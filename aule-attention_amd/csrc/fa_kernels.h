@@ -172,6 +172,33 @@ struct RopeArgs {
 };
 int launch_rope(const RopeArgs& a, hipStream_t stream);
 
+// Paged KV cache append (kv_append_gfx950.hip): key / value [T, Hkv, D] 16-bit with free token / head strides (elements, last
+// dimension contiguous) -> row slot_mapping[t] of k_cache / v_cache [num_blocks, block_size, Hkv, D], which hold either the
+// input's dtype (kCache16: a copy) or e4m3fn codes of x / scale[hk] (kCacheFp8E4M3).  cos != null: K is rotated first (half-split
+// pairs, table row positions[t]).  Slots outside [0, num_blocks * block_size) are skipped.  The caller guarantees 16-byte aligned
+// pointers, strides % 8 == 0 and table_pitch % 4 == 0.
+struct KvAppendArgs {
+    const void* key;
+    const void* value;
+    void* k_cache;
+    void* v_cache;
+    const long long* slot_mapping;   // [T] int64
+    int T, Hkv, D;
+    long long num_blocks;
+    int block_size;
+    long long k_token_stride, k_head_stride, v_token_stride, v_head_stride;
+    int dtype;                          // of key / value: kF16 or kBF16
+    int cache_kind = kCache16;
+    const float* k_scale = nullptr;     // kCacheFp8E4M3 only: [Hkv] fp32
+    const float* v_scale = nullptr;
+    const float* cos = nullptr;         // [table_len, D/2] fp32, table_pitch floats per row (0 = D/2)
+    const float* sin = nullptr;
+    const long long* positions = nullptr;   // [T] int64
+    long long table_len = 0;
+    int table_pitch = 0;
+};
+int launch_kv_append(const KvAppendArgs& a, hipStream_t stream);   // -1: unsupported arguments
+
 // Returns 0 on success, a hipError_t value on launch failure, -1 for an
 // unsupported (dtype, D) combination.
 int launch_paged_decode(const PagedArgs& a, hipStream_t stream);   // either cache_kind; kCacheFp8E4M3 with a null scale array is -1

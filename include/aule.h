@@ -262,6 +262,58 @@ typedef struct aule_rope_desc {
 } aule_rope_desc;
 int32_t aule_rope_ex(const aule_rope_desc* desc);
 
+/* Paged KV cache append (additive; the write side of aule_attention_paged_decode_ex / _fp8_ex).  One launch writes the K  */
+/* and V rows of num_tokens new tokens into the [num_blocks, block_size, heads_kv, head_dim] caches:                          */
+/*     row slot_mapping[t] (= block * block_size + offset) of k_cache / v_cache  <-  key[t], value[t]                         */
+/* key / value are [num_tokens, heads_kv, head_dim] fp16 / bf16 with a contiguous last dimension and free token and head      */
+/* strides (in elements, separate for key and value: slices of a fused QKV projection and transposed [B, H, S, D] views need   */
+/* no copy).  A slot that is negative (vLLM's padding) or >= num_blocks * block_size is skipped: that token is neither read   */
+/* nor written.  Two tokens of one call with the same slot: which of them the cache holds afterwards is unspecified.          */
+/* cache_dtype AULE_KV_CACHE_SAME: the caches hold the input's dtype, rows are copied bit for bit; k_scale / v_scale must be   */
+/* NULL.  AULE_KV_CACHE_FP8_E4M3: the caches hold OCP e4m3fn codes,                                                            */
+/*     code = cast_e4m3fn(clamp(x / scale[hk], -448, 448))                                                                    */
+/* -- correctly rounded fp32 division, round to nearest even (subnormals included), saturating, NaN stays a NaN code, -0      */
+/* stays -0 -- with k_scale / v_scale [heads_kv] fp32 DEVICE arrays read by the kernel (no host synchronisation).             */
+/* Optional rotation of K only (all of cos, sin, positions given; all NULL with table_len = table_pitch = 0: none):           */
+/* AULE_ROPE_HALF pairs, token t uses table row positions[t]; aule_rope_ex's arithmetic, rounded once to the input's dtype    */
+/* and only then quantised, so the result equals aule_rope_ex() followed by the un-rotated append bit for bit.  A token        */
+/* whose slot is skipped needs no valid position; a position outside [0, table_len) skips the token.                          */
+/* Alignment: key, value, the caches, cos and sin 16-byte aligned; the four strides multiples of 8; table_pitch % 4 == 0.     */
+/* Asynchronous on `stream`; device pointers; captures into a hipGraph (no allocation, no synchronisation).                  */
+#define AULE_KV_CACHE_SAME 0      /* caches of the input's 16-bit dtype */
+#define AULE_KV_CACHE_FP8_E4M3 1  /* caches of OCP e4m3fn codes + per-KV-head scales */
+typedef struct aule_kv_append_desc {
+    uint32_t struct_size;      /* = sizeof(aule_kv_append_desc) = 168 */
+    int32_t dtype;             /* of key / value: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    int32_t cache_dtype;       /* AULE_KV_CACHE_* */
+    uint32_t num_tokens;       /* 0: returns 0 without a launch */
+    uint32_t heads_kv;
+    uint32_t head_dim;         /* 32, 64 or 128 */
+    uint32_t num_blocks;
+    uint32_t block_size;       /* any value > 0 */
+    int64_t key_token_stride;  /* offset 32; elements, >= head_dim */
+    int64_t key_head_stride;   /* elements, >= head_dim */
+    int64_t value_token_stride;
+    int64_t value_head_stride;
+    uint32_t table_len;        /* offset 64; rows of cos / sin (0 without rotation) */
+    uint32_t table_pitch;      /* floats per table row; 0 = head_dim/2 */
+    int32_t device;            /* HIP device ordinal, -1 = current */
+    uint32_t reserved;         /* 0 */
+    void* stream;              /* offset 80; hipStream_t */
+    const void* key;           /* [num_tokens, heads_kv, head_dim] */
+    const void* value;
+    void* k_cache;             /* offset 104; [num_blocks, block_size, heads_kv, head_dim], contiguous */
+    void* v_cache;
+    const int64_t* slot_mapping;   /* offset 120; [num_tokens] */
+    const float* k_scale;      /* [heads_kv] fp32 (AULE_KV_CACHE_FP8_E4M3), else NULL */
+    const float* v_scale;
+    const float* cos;          /* offset 144; [table_len, head_dim/2] fp32, or NULL */
+    const float* sin;
+    const int64_t* positions;  /* offset 160; [num_tokens], or NULL */
+} aule_kv_append_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_kv_cache_append_ex(const aule_kv_append_desc* desc);
+
 /* Attention with the query rotation fused into the kernel (additive; inference path).  Replaces the Q half of       */
 /* python/aule/triton_flash.py:112-131 (the reference rotates Q in its forward prologue); K must arrive rotated --   */
 /* once per key by aule_rope_ex(), e.g. when it is appended to a KV cache -- because the tiled kernel re-reads every */
