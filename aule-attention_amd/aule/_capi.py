@@ -246,6 +246,8 @@ SIGNATURES = [
     ("aule_peer_copy_async", _I32, [_I32, ctypes.c_void_p, ctypes.c_void_p, _U64, ctypes.c_void_p]),
     ("aule_hip_build_info", ctypes.c_char_p, []),
     ("aule_hip_debug_forward_route", _I32, [ctypes.POINTER(AttnDesc)]),
+    ("aule_hip_debug_last_forward_route", _I32, []),
+    ("aule_hip_debug_forward_plan", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_last_backward_route", _I32, []),
     ("aule_hip_debug_backward_route", _I32, [ctypes.POINTER(AttnBwdDesc)]),
     ("aule_hip_debug_forward_split_plan", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(_I32), _I32]),

@@ -1178,7 +1178,7 @@ uint64_t aule_attention_forward_workspace_size(const aule_attn_desc* d) {
     return aule_hip::fwd_workspace_bytes(a);
 }
 
-// (a dry run of the launcher: it reads the shape, none of the pointers)
+// (the launcher's plan: it reads the shape, none of the pointers)
 static uint64_t paged_workspace_impl(const aule_paged_desc* d, bool fp8) {
     if (paged_shape_error(d, fp8) != 0 || (uint64_t)d->batch * d->heads_q == 0) return 0;
     aule_hip::PagedArgs a;
@@ -1228,6 +1228,21 @@ int32_t aule_hip_debug_forward_route(const aule_attn_desc* d) {
     return aule_hip::fwd_route(a);
 }
 
+/* Debug hook: the route of the most recent forward launch of this process (0 before the first): what ran, where
+ * aule_hip_debug_forward_route says what would. */
+int32_t aule_hip_debug_last_forward_route(void) { return aule_hip::fwd_last_route(); }
+
+/* Debug hook: the whole launch plan of aule_attention_forward_ex(d) as integers (include/aule.h lists them); the contract of
+ * aule_hip_debug_forward_split_plan.  Pure host logic like the route hook. */
+int32_t aule_hip_debug_forward_plan(const aule_attn_desc* d, int32_t* out, int32_t cap) {
+    if (d == nullptr || d->struct_size != sizeof(aule_attn_desc)) return -3;
+    if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return -3;
+    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;
+    FwdArgs a;
+    fill_fwd_args(d, a);
+    return aule_hip::fwd_plan_dump(a, out, cap);
+}
+
 /* Debug hook: what the most recent backward launch of this process ran (bit mask, include/aule.h). */
 int32_t aule_hip_debug_last_backward_route(void) { return aule_hip::bwd_last_route(); }
 
@@ -1251,8 +1266,7 @@ int32_t aule_hip_debug_forward_split_plan(const aule_attn_desc* d, int32_t* out,
     if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;
     FwdArgs a;
     fill_fwd_args(d, a);
-    if (aule_hip::fwd_route(a) != 7) return 0;
-    return aule_hip::fwd_split_plan_dump(a, out, cap);
+    return aule_hip::fwd_split_plan_dump(a, out, cap);   // (0 unless the plan's route is 7)
 }
 
 int32_t aule_hip_debug_work_order(int32_t ranked, int32_t bid, int32_t batch, int32_t heads_q, int32_t heads_kv, int32_t nblk, int32_t flag, int32_t* out4) {

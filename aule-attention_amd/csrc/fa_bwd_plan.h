@@ -1,4 +1,4 @@
-// fa_bwd_plan.h -- the backward decided once, as a value (host only; the backward's counterpart of fwd_route() / fa_fwd_split.h).
+// fa_bwd_plan.h -- the backward decided once, as a value (host only; the backward's counterpart of fa_fwd_plan.h).
 // bwd_plan() is everything launch_bwd and the workspace-size queries need to know about a call.  Pure host logic: it reads the shape,
 // the mask, BwdArgs::ws_bytes / ws_floor, the debug inputs (dbg / dbg_dq; AULE_TL=dkv4, AULE_DBG_BWD_ONLY) and the once-per-process
 // AULE_HIP_BWD_* switches; it dereferences no pointer and asks the device nothing but its (cached) CU count.

@@ -194,7 +194,6 @@ int launch_d256(const FwdArgs& a, hipStream_t stream) {
 
 // launch_fwd's entry for D = 256 (every dtype; single launch, no workspace)
 int launch_fwd_d256(const FwdArgs& a, hipStream_t stream) {
-    if (a.query_ws != nullptr) return 0;
     if (a.D != kD256 || a.rope_cos != nullptr) return -1;
     if (a.dtype == kBF16) return launch_d256<Bf16Traits>(a, stream);
     if (a.dtype == kF16) return launch_d256<F16Traits>(a, stream);

@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "fa_device.h"
+#include "fa_fwd_plan.h"
 #include "fa_kernels.h"
 
 namespace aule_hip {
@@ -281,7 +282,7 @@ inline int f32_pieces(const FwdArgs& a, int nqb) {
 }
 
 template <int D>
-int launch_f32(const FwdArgs& a, hipStream_t stream) {
+int launch_f32(const FwdArgs& a, int pieces, hipStream_t stream) {
     FwdF32Params p;
     p.q = (const float*)a.q; p.k = (const float*)a.k; p.v = (const float*)a.v;
     p.o = (float*)a.o; p.lse = a.lse;
@@ -290,14 +291,9 @@ int launch_f32(const FwdArgs& a, hipStream_t stream) {
     p.nqb = (a.Sq + kQB - 1) / kQB;
     p.window = a.window > 0 ? a.window : 0;
     p.coff = a.causal ? a.coff : 0;
-    p.npiece = f32_pieces(a, p.nqb);
+    p.npiece = pieces;
     p.part = nullptr;
     p.rows = (long long)a.B * a.Hq * a.Sq;
-    const uint64_t bytes = p.npiece > 1 ? (uint64_t)p.npiece * p.rows * (D + 4) * sizeof(float) : 0;
-    if (a.query_ws != nullptr) {
-        *a.query_ws = bytes;
-        return 0;
-    }
     const dim3 grid((unsigned)(p.nqb * a.B * a.Hq * p.npiece)), block(256);
     if (p.npiece == 1) {
         if (a.causal)
@@ -306,7 +302,7 @@ int launch_f32(const FwdArgs& a, hipStream_t stream) {
             hipLaunchKernelGGL((fa_fwd_f32_kernel<D, false>), grid, block, 0, stream, p);
         return (int)hipGetLastError();
     }
-    ScopedWorkspace ws(bytes, a.ws, a.ws_bytes, stream);
+    ScopedWorkspace ws(fwd_f32_workspace_bytes(a, pieces), a.ws, a.ws_bytes, stream);
     if (ws.err != hipSuccess) return (int)ws.err;
     p.part = static_cast<float*>(ws.ptr);
     if (a.causal)
@@ -324,10 +320,19 @@ int launch_f32(const FwdArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-int launch_fwd_f32(const FwdArgs& a, hipStream_t stream) {
-    if (a.D == 128) return launch_f32<128>(a, stream);
-    if (a.D == 64) return launch_f32<64>(a, stream);
-    if (a.D == 32) return launch_f32<32>(a, stream);
+// Route 0's plan: the pieces per Q block (1 for a head size without an instance: the launch refuses it) and their partials.
+int fwd_f32_pieces(const FwdArgs& a) {
+    if (a.D != 128 && a.D != 64 && a.D != 32) return 1;
+    return f32_pieces(a, (a.Sq + kQB - 1) / kQB);
+}
+uint64_t fwd_f32_workspace_bytes(const FwdArgs& a, int pieces) {
+    return pieces > 1 ? (uint64_t)pieces * a.B * a.Hq * a.Sq * (a.D + 4) * sizeof(float) : 0;
+}
+
+int launch_fwd_f32(const FwdArgs& a, int pieces, hipStream_t stream) {
+    if (a.D == 128) return launch_f32<128>(a, pieces, stream);
+    if (a.D == 64) return launch_f32<64>(a, pieces, stream);
+    if (a.D == 32) return launch_f32<32>(a, pieces, stream);
     return -1;
 }
 

@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "fa_device.h"
+#include "fa_fwd_plan.h"
 #include "fa_kernels.h"
 #include "fa_fwd_tile.h"
 
@@ -59,7 +60,7 @@ struct FwdPPParams {
 constexpr int kTLMax = 256;
 
 // Which shapes take the SPLIT instances: to be set from measurements (tools/ppsplit_grid.py); until then every shape
-// that passes the structural tests in pp_split_applicable() does.
+// that passes the structural tests in fwd_pp_split_plan() does.
 #ifndef AULE_PPSPLIT_RULE
 #define AULE_PPSPLIT_RULE true
 #endif
@@ -562,15 +563,6 @@ __global__ void __launch_bounds__(512) fa_fwd_pp_kernel(const FwdPPParams p) {
     }
 }
 
-// AULE_HIP_FWD_SOFTMAX = "raw" (default for bf16) | "classic" (always the online softmax; A/B measurements)
-static bool raw_softmax_enabled() {
-    static const int v = [] {
-        const char* e = getenv("AULE_HIP_FWD_SOFTMAX");
-        return (e != nullptr && e[0] == 'c') ? 0 : 1;
-    }();
-    return v == 1;
-}
-
 template <class T, int D>
 int launch_pp(const FwdArgs& a, hipStream_t stream) {
     FwdPPParams p;
@@ -599,7 +591,7 @@ int launch_pp(const FwdArgs& a, hipStream_t stream) {
         return (int)hipGetLastError();
     }
     if constexpr (std::is_same<T, Bf16Traits>::value) {
-        if (raw_softmax_enabled()) {
+        if (!fwd_softmax_classic()) {   // bf16: the raw softmax unless AULE_HIP_FWD_SOFTMAX=classic
             if (a.causal)
                 hipLaunchKernelGGL((fa_fwd_pp_kernel<T, D, true, false, true>), grid, block, lds, stream, p);
             else
@@ -621,9 +613,9 @@ int launch_pp(const FwdArgs& a, hipStream_t stream) {
 // `nsplit` chunks, one workgroup each, so that B'*nqb'*nsplit workgroups fill the chip; every workgroup leaves an
 // fp32 partial and fa_fwd_splitkv_combine (fa_fwd_splitkv_gfx950.hip) merges them.  Complements the wave-per-chunk
 // split-KV kernel, which wins while a unit has few packed rows (it is HBM-bound; this one is MFMA-bound).
-struct PPSplitPlan {
-    int g, rows, nqb, nbase, ntiles, nsplit, chunk, nrt;
-};
+// The plan sizes its grid by this many workgroups whatever the device: a constant of the measured rule below (MI355X), NOT the
+// device's CU count, which every other forward rule asks device_cu_count() for.
+constexpr int kPPSplitSlots = 256;
 
 static PPSplitPlan pp_split_plan(const FwdArgs& a) {
     PPSplitPlan s;
@@ -632,7 +624,7 @@ static PPSplitPlan pp_split_plan(const FwdArgs& a) {
     s.nqb = (s.rows + kQBlock - 1) / kQBlock;
     s.nbase = a.B * a.Hkv * s.nqb;
     s.ntiles = (a.Sk + kKVTile - 1) / kKVTile;
-    int want = 256 / (s.nbase > 0 ? s.nbase : 1);          // one workgroup per CU (137 KB of LDS each)
+    int want = kPPSplitSlots / (s.nbase > 0 ? s.nbase : 1);   // one workgroup per CU (137 KB of LDS each)
     const int most = s.ntiles / 4;                          // at least 4 tiles per split: the prologue costs ~3
     if (want > most) want = most;
     if (want < 1) want = 1;
@@ -644,8 +636,7 @@ static PPSplitPlan pp_split_plan(const FwdArgs& a) {
 }
 
 template <class T, int D>
-int launch_pp_split(const FwdArgs& a, hipStream_t stream) {
-    const PPSplitPlan s = pp_split_plan(a);
+int launch_pp_split(const FwdArgs& a, const PPSplitPlan& s, hipStream_t stream) {
     FwdPPParams p;
     p.q = a.q; p.k = a.k; p.v = a.v; p.o = nullptr; p.lse = nullptr;
     p.B = a.B * a.Hkv; p.Hq = 1; p.Hkv = 1; p.Sq = s.rows; p.Sk = a.Sk;
@@ -660,12 +651,7 @@ int launch_pp_split(const FwdArgs& a, hipStream_t stream) {
     p.nbase = s.nbase; p.chunk = s.chunk;
     p.prow_per_unit = s.nrt * 32;
     p.part_rows = a.B * a.Hkv * p.prow_per_unit;
-    const size_t bytes = (size_t)s.nsplit * p.part_rows * (D + 2) * sizeof(float);
-    if (a.query_ws != nullptr) {
-        *a.query_ws = bytes;
-        return 0;
-    }
-    ScopedWorkspace ws(bytes, a.ws, a.ws_bytes, stream);   // caller's buffer, or stream-ordered like the split-KV kernel's
+    ScopedWorkspace ws(s.bytes(a.B * a.Hkv, D), a.ws, a.ws_bytes, stream);   // caller's buffer, or stream-ordered like the split-KV kernel's
     if (ws.err != hipSuccess) return (int)ws.err;
     p.part = static_cast<float*>(ws.ptr);
     const dim3 grid((unsigned)(s.nbase * s.nsplit)), block(512);
@@ -677,7 +663,7 @@ int launch_pp_split(const FwdArgs& a, hipStream_t stream) {
     } else {
         bool raw = false;
         if constexpr (std::is_same<T, Bf16Traits>::value) {
-            raw = raw_softmax_enabled();
+            raw = !fwd_softmax_classic();
             if (raw) hipLaunchKernelGGL((fa_fwd_pp_kernel<T, D, false, false, true, false, true>), grid, block, lds, stream, p);
         }
         if (!raw) hipLaunchKernelGGL((fa_fwd_pp_kernel<T, D, false, false, false, false, true>), grid, block, lds, stream, p);
@@ -737,7 +723,7 @@ int launch_fwd_pp_timeline(const FwdArgs& a, unsigned long long* dbg, hipStream_
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
     };
-    if (raw_softmax_enabled()) {
+    if (!fwd_softmax_classic()) {
         if (a.causal) go(&fa_fwd_pp_kernel<Bf16Traits, 128, true, true, true>);
         else go(&fa_fwd_pp_kernel<Bf16Traits, 128, false, true, true>);
     } else {
@@ -762,8 +748,9 @@ int launch_fwd_pp(const FwdArgs& a, hipStream_t stream) {
     return -1;
 }
 
-// Shapes for the SPLIT instances.  AULE_HIP_FWD_PPSPLIT=0 turns the path off (A/B measurements).
-bool pp_split_applicable(const FwdArgs& a) {
+// Shapes for the SPLIT instances, and their plan (`s`, meaningful when the answer is yes).  AULE_HIP_FWD_PPSPLIT=0 turns the path
+// off (A/B measurements).
+bool fwd_pp_split_plan(const FwdArgs& a, PPSplitPlan& s) {
     static const int on = [] {
         const char* e = getenv("AULE_HIP_FWD_PPSPLIT");
         return (e != nullptr && e[0] == '0') ? 0 : 1;
@@ -776,7 +763,7 @@ bool pp_split_applicable(const FwdArgs& a) {
     if (a.causal && !(a.coff == a.Sk - a.Sq && a.coff > 0 && a.Sq <= 256)) return false;
     if (a.D != 32 && a.D != 64 && a.D != 128) return false;
     if ((long long)a.Hq / a.Hkv * a.Sq >= (1 << 24)) return false;
-    const PPSplitPlan s = pp_split_plan(a);
+    s = pp_split_plan(a);
     const long long tiled_wgs = (long long)a.B * a.Hq * ((a.Sq + kQBlock - 1) / kQBlock);
     // worth it when the plain launch leaves most CUs idle or most waves of a Q block without rows, and the split
     // launch does not: at least two splits, or packing alone folds >= 2 heads into one block
@@ -794,15 +781,15 @@ bool pp_split_applicable(const FwdArgs& a) {
     return AULE_PPSPLIT_RULE;
 }
 
-int launch_fwd_pp_split(const FwdArgs& a, hipStream_t stream) {
+int launch_fwd_pp_split(const FwdArgs& a, const PPSplitPlan& s, hipStream_t stream) {
     if (a.dtype == kBF16) {
-        if (a.D == 128) return launch_pp_split<Bf16Traits, 128>(a, stream);
-        if (a.D == 64) return launch_pp_split<Bf16Traits, 64>(a, stream);
-        if (a.D == 32) return launch_pp_split<Bf16Traits, 32>(a, stream);
+        if (a.D == 128) return launch_pp_split<Bf16Traits, 128>(a, s, stream);
+        if (a.D == 64) return launch_pp_split<Bf16Traits, 64>(a, s, stream);
+        if (a.D == 32) return launch_pp_split<Bf16Traits, 32>(a, s, stream);
     } else if (a.dtype == kF16) {
-        if (a.D == 128) return launch_pp_split<F16Traits, 128>(a, stream);
-        if (a.D == 64) return launch_pp_split<F16Traits, 64>(a, stream);
-        if (a.D == 32) return launch_pp_split<F16Traits, 32>(a, stream);
+        if (a.D == 128) return launch_pp_split<F16Traits, 128>(a, s, stream);
+        if (a.D == 64) return launch_pp_split<F16Traits, 64>(a, s, stream);
+        if (a.D == 32) return launch_pp_split<F16Traits, 32>(a, s, stream);
     }
     return -1;
 }

@@ -12,6 +12,7 @@
 // program per 128-row block whatever the problem: python/aule/triton_flash_amd.py:434-445).
 #pragma once
 #include "fa_device.h"
+#include "fa_fwd_plan.h"
 #include "fa_kernels.h"
 #include "fa_fwd_tile.h"
 
@@ -123,12 +124,6 @@ inline int split_min_tiles() {
     return v;
 }
 
-struct SplitPlan {
-    bool ok;
-    int nqb, nwork, n;
-    long long nitems;
-    size_t bytes;
-};
 inline SplitPlan split_plan(const FwdArgs& a, int slots) {
     SplitPlan s{};
     const int pcoff = a.causal ? a.coff : kEverything;

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "fa_device.h"
+#include "fa_fwd_plan.h"
 #include "fa_kernels.h"
 
 namespace aule_hip {
@@ -492,32 +493,15 @@ int launch_combine(const SplitParams& p, bool by_count, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-// The wave-per-chunk launch: plan, workspace (or the dry run's answer), split kernel, combine.  `p` arrives with the
-// tensors, B / Hq / Hkv / Sq, the scale and the paged fields set; `Sk` bounds the key range on the host.  The plan:
-// `groups` = B * Hkv units of `rows` packed rows each, cut into 32-row tiles; the key tiles are shared out so that about
-// 2048 waves (~8 per CU) are launched whatever the shape and whatever the bytes per key.
+// The wave-per-chunk launch: workspace, split kernel, combine.  `p` arrives with the tensors, B / Hq / Hkv / Sq, the scale and
+// the paged fields set; `w` is wave_chunk_plan() of the problem.
 template <class T, int D, class KV, bool PAGED>
-int launch_wave_chunk(SplitParams p, int Sk, void* user_ws, uint64_t user_ws_bytes, uint64_t* query_ws, bool combine_by_count,
-                      hipStream_t stream) {
-    p.nrt = (p.Hq / p.Hkv * p.Sq + 31) / 32;
-    const int units = p.B * p.Hkv * p.nrt;
-    const int ntiles = (Sk + 31) / 32;
-    const int want_waves = (2048 + units - 1) / units;
-    p.chunk_tiles = (ntiles + want_waves - 1) / want_waves;
-    if (p.chunk_tiles < 1) p.chunk_tiles = 1;
-    const int nwaves = (ntiles + p.chunk_tiles - 1) / p.chunk_tiles;
-    const int nsplit = (nwaves + 3) / 4;
-    p.npart = nsplit * 4;
-    p.rows_total = units * 32;
-    const size_t bytes = (size_t)p.npart * p.rows_total * (D + 2) * sizeof(float);
-    if (query_ws != nullptr) {
-        *query_ws = bytes;
-        return 0;
-    }
-    ScopedWorkspace ws(bytes, user_ws, user_ws_bytes, stream);   // caller's buffer, or stream-ordered (safe with concurrent streams)
+int launch_wave_chunk(SplitParams p, const WaveChunkPlan& w, void* user_ws, uint64_t user_ws_bytes, bool combine_by_count, hipStream_t stream) {
+    p.nrt = w.nrt; p.chunk_tiles = w.chunk_tiles; p.npart = w.npart; p.rows_total = w.rows_total;
+    ScopedWorkspace ws(w.bytes(D), user_ws, user_ws_bytes, stream);   // caller's buffer, or stream-ordered (safe with concurrent streams)
     if (ws.err != hipSuccess) return (int)ws.err;
     p.part = static_cast<float*>(ws.ptr);
-    hipLaunchKernelGGL((fa_fwd_splitkv_kernel<T, D, KV, PAGED>), dim3((unsigned)nsplit, (unsigned)units), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((fa_fwd_splitkv_kernel<T, D, KV, PAGED>), dim3((unsigned)w.nsplit, (unsigned)(w.rows_total / 32)), dim3(256), 0, stream, p);
     const int rc = (int)hipGetLastError();
     return rc != 0 ? rc : launch_combine<T, D>(p, combine_by_count, stream);
 }
@@ -531,13 +515,15 @@ void set_abs_scale(SplitParams& p, float scale) {
 }
 
 template <class T, int D>
-int launch_split(const FwdArgs& a, hipStream_t stream) {
+int launch_split(const FwdArgs& a, const WaveChunkPlan& w, hipStream_t stream) {
     SplitParams p = {};
     p.q = a.q; p.k = a.k; p.v = a.v; p.o = a.o; p.lse = a.lse;
     p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = a.Sq; p.Sk = a.Sk;
     set_abs_scale(p, a.scale);
-    return launch_wave_chunk<T, D, Kv16, false>(p, a.Sk, a.ws, a.ws_bytes, a.query_ws, false, stream);
+    return launch_wave_chunk<T, D, Kv16, false>(p, w, a.ws, a.ws_bytes, false, stream);
 }
+
+static WaveChunkPlan paged_plan(const PagedArgs& a) { return wave_chunk_plan(a.B, a.Hq, a.Hkv, 1, a.max_blocks * a.block_size); }
 
 // Paged decode: one query token per sequence, K/V gathered through the block table; the key range is bounded by
 // max_blocks * block_size on the host (no device->host sync for max(context_lens)); waves past a sequence's
@@ -558,19 +544,37 @@ int launch_paged(const PagedArgs& a, hipStream_t stream) {
     else p.c = a.scale * kLog2e;
     //  * combine: the 16-bit cache always merges with the workgroup-per-row kernel; the FP8 cache picks by the number
     //    of partials (and honours AULE_HIP_FWD_COMBINE), as launch_splitkv_combine does.
-    return launch_wave_chunk<T, D, KV, true>(p, p.Sk, a.ws, a.ws_bytes, a.query_ws, /*combine_by_count=*/std::is_same<KV, KvFp8>::value, stream);
+    return launch_wave_chunk<T, D, KV, true>(p, paged_plan(a), a.ws, a.ws_bytes, /*combine_by_count=*/std::is_same<KV, KvFp8>::value, stream);
 }
 
 }  // namespace
 
-int launch_fwd_splitkv(const FwdArgs& a, hipStream_t stream) {
-    return for_dtype_d(a.dtype, a.D, [&](auto t, auto d) { return launch_split<decltype(t), decltype(d)::value>(a, stream); });
+// The plan of the wave-per-chunk launch (route 4, the paged decode and its size query): B * Hkv units of Hq / Hkv * Sq packed rows
+// each, cut into 32-row tiles; the key tiles are shared out so that about 2048 waves (~8 per CU) are launched whatever the shape
+// and whatever the bytes per key.  `Sk` bounds the key range on the host.
+WaveChunkPlan wave_chunk_plan(int B, int Hq, int Hkv, int Sq, int Sk) {
+    WaveChunkPlan w;
+    w.nrt = (Hq / Hkv * Sq + 31) / 32;
+    const int units = B * Hkv * w.nrt;
+    const int ntiles = (Sk + 31) / 32;
+    const int want_waves = (2048 + units - 1) / (units > 0 ? units : 1);   // (units may be 0)
+    w.chunk_tiles = (ntiles + want_waves - 1) / want_waves;
+    if (w.chunk_tiles < 1) w.chunk_tiles = 1;
+    const int nwaves = (ntiles + w.chunk_tiles - 1) / w.chunk_tiles;
+    w.nsplit = (nwaves + 3) / 4;
+    w.npart = w.nsplit * 4;
+    w.rows_total = units * 32;
+    return w;
 }
 
-// cache_kind selects the K/V source; an FP8 cache needs its two scale arrays (the dry run does not read them)
+int launch_fwd_splitkv(const FwdArgs& a, const WaveChunkPlan& w, hipStream_t stream) {
+    return for_dtype_d(a.dtype, a.D, [&](auto t, auto d) { return launch_split<decltype(t), decltype(d)::value>(a, w, stream); });
+}
+
+// cache_kind selects the K/V source; an FP8 cache needs its two scale arrays
 int launch_paged_decode(const PagedArgs& a, hipStream_t stream) {
     const bool fp8 = a.cache_kind == kCacheFp8E4M3;
-    if (fp8 && a.query_ws == nullptr && (a.k_scale == nullptr || a.v_scale == nullptr)) return -1;
+    if (fp8 && (a.k_scale == nullptr || a.v_scale == nullptr)) return -1;
     return for_dtype_d(a.dtype, a.D, [&](auto t, auto d) {
         using T = decltype(t);
         constexpr int D = decltype(d)::value;
@@ -578,12 +582,10 @@ int launch_paged_decode(const PagedArgs& a, hipStream_t stream) {
     });
 }
 
-// dry run of the launcher above, so that the size query cannot drift from the launch
-uint64_t paged_workspace_bytes(PagedArgs a) {
-    uint64_t bytes = 0;
-    a.query_ws = &bytes;
-    (void)launch_paged_decode(a, nullptr);
-    return bytes;
+// the bytes of the plan the launcher above runs (0: a (dtype, D) it refuses)
+uint64_t paged_workspace_bytes(const PagedArgs& a) {
+    if ((a.dtype != kBF16 && a.dtype != kF16) || (a.D != 128 && a.D != 64 && a.D != 32)) return 0;
+    return paged_plan(a).bytes(a.D);
 }
 
 // The combine pass on its own, for partials written by another kernel (fa_fwd_pp_gfx950.hip SPLIT instances) in

@@ -1199,17 +1199,16 @@ static int w4_generic_bodies() {
 }
 
 template <class T, int D, bool TL = false>
-int launch_w4(const FwdArgs& a, hipStream_t stream, unsigned long long* dbg = nullptr) {
+int launch_w4(const FwdArgs& a, const W4Grid& g, hipStream_t stream, unsigned long long* dbg = nullptr) {
     FwdW4Params p;
     p.q = a.q; p.k = a.k; p.v = a.v; p.o = a.o; p.lse = a.lse;
     p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = a.Sq; p.Sk = a.Sk;
     p.c = (a.scale < 0.f ? -a.scale : a.scale) * kLog2e;
     p.negq = a.scale < 0.f ? 1 : 0;
     p.nqb = (a.Sq + kQBlock - 1) / kQBlock;
-    p.pair = a.causal ? 1 : 0;
-    p.nwork = p.pair ? (p.nqb + 1) / 2 : p.nqb;
+    p.pair = g.pair; p.nwork = g.nwork; p.nitems = g.nitems;
+    p.rounds = g.rounds; p.mper = g.mper;
     p.coff = a.causal ? a.coff : 0;
-    p.nitems = p.nwork * a.B * a.Hq;
     p.dbg = dbg;
     p.npiece = 1; p.pcoff = 0; p.magic = 0; p.part = nullptr; p.part_rows = 0;
     p.generic = w4_generic_bodies();
@@ -1229,40 +1228,7 @@ int launch_w4(const FwdArgs& a, hipStream_t stream, unsigned long long* dbg = nu
     }
     p.rcos = a.rope_cos; p.rsin = a.rope_sin;
     p.rrows = a.rope_rows; p.rpitch = a.rope_pitch; p.rpos = a.rope_pos;
-    // one workgroup per CU; more only when a workgroup's list would not fit its part table
-    const long long ncu = device_cu_count(a.device);
-    // Half-empty causal grids (round 5; the reference harness's B 1 H 32 S 2048: 128 pairs on 256 CUs): when every Q block can have
-    // a CU of its own, the blocks are NOT paired -- the launch then lasts as long as its largest block (32 tiles + one part's seam
-    // instead of a pair's 36 tiles + two), on a chip that is ~56 % busy on average.  AULE_HIP_W4_UNPAIR=0 keeps the pairs (A/B).
-    {
-        static const int unpair = [] {
-            const char* e = std::getenv("AULE_HIP_W4_UNPAIR");
-            return (e != nullptr && e[0] == '0') ? 0 : 1;
-        }();
-        // (a sliding window: every block's part has about W / 64 + 4 tiles -- nothing to balance by pairing)
-        if (a.causal && (p.window > 0 || (unpair && p.nqb >= 2 && (long long)p.nqb * a.B * a.Hq <= ncu))) {
-            p.pair = 0;
-            p.nwork = p.nqb;
-            p.nitems = p.nwork * a.B * a.Hq;
-        }
-    }
-    const long long rounds = (p.nitems + ncu * kW4MaxItems - 1) / (ncu * kW4MaxItems);
-    long long G = ncu * rounds;
-    if (G > p.nitems) G = p.nitems;
-    p.rounds = 0;
-    p.mper = 1;
-    {   // round order (w4_body): needs whole rounds -- W a multiple of the heads' Q blocks -- and an even number of them
-        static const char* const e = std::getenv("AULE_HIP_W4_ORDER");   // "pairs": the item order everywhere (A/B)
-        const int units = a.B * a.Hkv, W = (int)(G / 8), g = a.Hq / a.Hkv;
-        if (a.causal && p.window == 0 && !(e != nullptr && e[0] == 'p') && G == ncu && (G & 7) == 0 && (units & 7) == 0 && p.nqb <= W && W % p.nqb == 0) {
-            const int m = W / p.nqb, hx = units / 8 * g;
-            if (hx % (2 * m) == 0 && hx / m <= kW4MaxSlot) {
-                p.rounds = hx / m;
-                p.mper = m;
-            }
-        }
-    }
-    const dim3 grid((unsigned)G), block(256);
+    const dim3 grid((unsigned)g.G), block(256);
     const size_t lds = w4_lds_bytes<D>() + (TL ? 4 * kW4TLLds * 8 : 0);
     if (p.window > 0)
         hipLaunchKernelGGL((w4_kernel_win<T, D>()), grid, block, lds, stream, p);
@@ -1276,12 +1242,7 @@ int launch_w4(const FwdArgs& a, hipStream_t stream, unsigned long long* dbg = nu
 // Small grids: every pair of causal Q blocks (every non-causal block) as n work items of 1/n of its key tiles, partial rows, one
 // merge launch (fa_fwd_split.h; route 7).  One workgroup per item.
 template <class T, int D>
-int launch_w4_split(const FwdArgs& a, hipStream_t stream) {
-    const SplitPlan s = split_plan(a, device_cu_count(a.device));
-    if (a.query_ws != nullptr) {
-        *a.query_ws = s.bytes;
-        return 0;
-    }
+int launch_w4_split(const FwdArgs& a, const SplitPlan& s, hipStream_t stream) {
     ScopedWorkspace ws(s.bytes, a.ws, a.ws_bytes, stream);
     if (ws.err != hipSuccess) return (int)ws.err;
     FwdW4Params p{};
@@ -1361,27 +1322,66 @@ bool fwd_w4_applicable(const FwdArgs& a) {
     return true;
 }
 
-// Small grids the forward cuts along the keys (route 7).
-bool fwd_w4_split_applicable(const FwdArgs& a) {
+// Small grids the forward cuts along the keys (route 7), and the plan of the cut (written to `s` only then).
+bool fwd_w4_split_plan(const FwdArgs& a, SplitPlan& s) {
     if (split_max_pieces() < 2 || a.rope_cos != nullptr || a.window > 0 || !fwd_w4_applicable(a)) return false;
     if ((long long)a.Sk >= 65535LL * kKVTile) return false;                               // tile indices are 16-bit in the part table
     if ((long long)a.Sq * (a.D + kPartPad) * 4 >= (1LL << 32)) return false;              // partial rows of a head: 32-bit offsets
-    return split_plan(a, device_cu_count(a.device)).ok;
+    const SplitPlan plan = split_plan(a, device_cu_count(a.device));
+    if (plan.ok) s = plan;
+    return plan.ok;
 }
 
-int launch_fwd_w4_split(const FwdArgs& a, hipStream_t stream) {
-    if (a.dtype == kBF16 && a.D == 128) return launch_w4_split<Bf16Traits, 128>(a, stream);
-    if (a.dtype == kF16 && a.D == 128) return launch_w4_split<F16Traits, 128>(a, stream);
-    if (a.dtype == kBF16 && a.D == 64) return launch_w4_split<Bf16Traits, 64>(a, stream);
-    if (a.dtype == kF16 && a.D == 64) return launch_w4_split<F16Traits, 64>(a, stream);
+// The grid of the plain launch (route 8): paired or single Q blocks, one workgroup per CU, the round order.
+W4Grid fwd_w4_grid(const FwdArgs& a) {
+    W4Grid g;
+    const int nqb = (a.Sq + kQBlock - 1) / kQBlock, window = a.window > 0 ? a.window : 0;
+    // one workgroup per CU; more only when a workgroup's list would not fit its part table
+    const long long ncu = device_cu_count(a.device);
+    // Half-empty causal grids (round 5; the reference harness's B 1 H 32 S 2048: 128 pairs on 256 CUs): when every Q block can have
+    // a CU of its own, the blocks are NOT paired -- the launch then lasts as long as its largest block (32 tiles + one part's seam
+    // instead of a pair's 36 tiles + two), on a chip that is ~56 % busy on average.  AULE_HIP_W4_UNPAIR=0 keeps the pairs (A/B).
+    static const int unpair = [] {
+        const char* e = std::getenv("AULE_HIP_W4_UNPAIR");
+        return (e != nullptr && e[0] == '0') ? 0 : 1;
+    }();
+    // (a sliding window: every block's part has about W / 64 + 4 tiles -- nothing to balance by pairing)
+    g.pair = a.causal && !(window > 0 || (unpair && nqb >= 2 && (long long)nqb * a.B * a.Hq <= ncu)) ? 1 : 0;
+    g.nwork = g.pair ? (nqb + 1) / 2 : nqb;
+    g.nitems = g.nwork * a.B * a.Hq;
+    const long long launches = (g.nitems + ncu * kW4MaxItems - 1) / (ncu * kW4MaxItems);
+    long long G = ncu * launches;
+    if (G > g.nitems) G = g.nitems;
+    g.G = (int)G;
+    g.rounds = 0;
+    g.mper = 1;
+    // round order (w4_body): needs whole rounds -- W a multiple of the heads' Q blocks -- and an even number of them
+    static const char* const order = std::getenv("AULE_HIP_W4_ORDER");   // "pairs": the item order everywhere (A/B)
+    const int units = a.B * a.Hkv, W = (int)(G / 8), hg = a.Hq / a.Hkv;
+    if (a.causal && window == 0 && !(order != nullptr && order[0] == 'p') && G == ncu && (G & 7) == 0 && (units & 7) == 0 && nqb <= W && W % nqb == 0) {
+        const int m = W / nqb, hx = units / 8 * hg;
+        if (hx % (2 * m) == 0 && hx / m <= kW4MaxSlot) {
+            g.rounds = hx / m;
+            g.mper = m;
+        }
+    }
+    return g;
+}
+
+int launch_fwd_w4_split(const FwdArgs& a, const SplitPlan& s, hipStream_t stream) {
+    if (a.dtype == kBF16 && a.D == 128) return launch_w4_split<Bf16Traits, 128>(a, s, stream);
+    if (a.dtype == kF16 && a.D == 128) return launch_w4_split<F16Traits, 128>(a, s, stream);
+    if (a.dtype == kBF16 && a.D == 64) return launch_w4_split<Bf16Traits, 64>(a, s, stream);
+    if (a.dtype == kF16 && a.D == 64) return launch_w4_split<F16Traits, 64>(a, s, stream);
     return -1;
 }
 
 // Host view of the split plan for the CPU tests (aule_hip_debug_forward_split_plan): out = {n, nwork, then per pair ntf, ntn,
 // b[0 .. kMaxPieces]}; returns the ints written, 0 when the shape does not take the path.
 int fwd_split_plan_dump(const FwdArgs& a, int* out, int cap) {
-    if (!fwd_w4_split_applicable(a)) return 0;
-    const SplitPlan s = split_plan(a, device_cu_count(a.device));
+    const FwdPlan plan = fwd_plan(a);
+    if (plan.route != 7) return 0;
+    const SplitPlan& s = plan.split;
     const int per = 2 + kMaxPieces + 1, need = 2 + s.nwork * per;
     if (out == nullptr || cap < need) return -need;
     out[0] = s.n; out[1] = s.nwork;
@@ -1394,11 +1394,11 @@ int fwd_split_plan_dump(const FwdArgs& a, int* out, int cap) {
     return need;
 }
 
-int launch_fwd_w4(const FwdArgs& a, hipStream_t stream) {
-    if (a.dtype == kBF16 && a.D == 128) return launch_w4<Bf16Traits, 128>(a, stream);
-    if (a.dtype == kF16 && a.D == 128) return launch_w4<F16Traits, 128>(a, stream);
-    if (a.dtype == kBF16 && a.D == 64) return launch_w4<Bf16Traits, 64>(a, stream);
-    if (a.dtype == kF16 && a.D == 64) return launch_w4<F16Traits, 64>(a, stream);
+int launch_fwd_w4(const FwdArgs& a, const W4Grid& g, hipStream_t stream) {
+    if (a.dtype == kBF16 && a.D == 128) return launch_w4<Bf16Traits, 128>(a, g, stream);
+    if (a.dtype == kF16 && a.D == 128) return launch_w4<F16Traits, 128>(a, g, stream);
+    if (a.dtype == kBF16 && a.D == 64) return launch_w4<Bf16Traits, 64>(a, g, stream);
+    if (a.dtype == kF16 && a.D == 64) return launch_w4<F16Traits, 64>(a, g, stream);
     return -1;
 }
 
@@ -1415,7 +1415,7 @@ int launch_fwd_w4_timeline(const FwdArgs& a, unsigned long long* dbg, hipStream_
     const int lds = w4_lds_bytes<kW4TLD>() + 4 * kW4TLLds * 8;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(w4_kernel<Bf16Traits, kW4TLD, true, true>()), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(w4_kernel<Bf16Traits, kW4TLD, false, true>()), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    return launch_w4<Bf16Traits, kW4TLD, true>(a, stream, dbg);
+    return launch_w4<Bf16Traits, kW4TLD, true>(a, fwd_w4_grid(a), stream, dbg);
 }
 #endif
 

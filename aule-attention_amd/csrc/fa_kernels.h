@@ -36,7 +36,6 @@ struct FwdArgs {
     // kernels of a decode step), otherwise a stream-ordered allocation.
     void* ws = nullptr;
     uint64_t ws_bytes = 0;
-    uint64_t* query_ws = nullptr;   // dry run: the launcher stores the bytes it would need and launches nothing
     // Fused query rotation (fwd_rope_fusable() shapes only): Q is rotated on its way into the kernel's registers with the
     // half-split pairs of rope_gfx950.hip; K must arrive rotated.  Tables [rope_rows, rope_pitch] fp32, query i -> row i + rope_pos.
     const float* rope_cos = nullptr;
@@ -149,9 +148,8 @@ struct PagedArgs {
     float scale;
     int window;   // > 0: attend only to the last `window` positions (context_len - 1 - pos < window)
     int dtype;
-    void* ws = nullptr;             // as FwdArgs::ws / ws_bytes / query_ws
+    void* ws = nullptr;             // as FwdArgs::ws / ws_bytes
     uint64_t ws_bytes = 0;
-    uint64_t* query_ws = nullptr;
     int cache_kind = kCache16;          // element type of the caches (dtype is the type of q / out)
     const float* k_scale = nullptr;     // kCacheFp8E4M3 only
     const float* v_scale = nullptr;
@@ -205,7 +203,10 @@ int launch_paged_decode(const PagedArgs& a, hipStream_t stream);   // either cac
 int launch_fwd(const FwdArgs& a, hipStream_t stream);
 // merge partials [npart][B*Hkv*nrt*32][D+2] fp32 (un-normalised O, m in log2 units, l) into O / LSE (fa_fwd_splitkv_gfx950.hip)
 int launch_splitkv_combine(const FwdArgs& a, float* part, int npart, int nrt, hipStream_t stream);
-int fwd_route(const FwdArgs& a);   // 0 fp32, 1 ping-pong, 4 split-KV, 5 tiled + packed rows + KV splits, 7 / 8 one-wave-per-SIMD, 9 head_dim 256 (host logic only)
+// FwdPlan::route of fwd_plan(a) (fa_fwd_plan.h: the plan, the workspace size): 0 fp32, 1 ping-pong, 4 split-KV, 5 tiled + packed rows + KV splits, 7 / 8 one-wave-per-SIMD, 9 head_dim 256
+int fwd_route(const FwdArgs& a);
+int fwd_last_route();   // ... of the most recent launch_fwd of this process; 0 before the first
+int fwd_plan_dump(const FwdArgs& a, int* out, int cap);   // the plan as integers (tests): route, ws_bytes low / high, the route's sub-plan
 // launch_fwd honours FwdArgs::rope_* for these arguments (otherwise it refuses them: rotate Q with launch_rope first)
 bool fwd_rope_fusable(const FwdArgs& a);
 // the split plan of route 7 as integers (tests): fwd_split_plan_dump in fa_fwd_w4_gfx950.hip, the plan itself in fa_fwd_split.h
@@ -213,8 +214,8 @@ int fwd_split_plan_dump(const FwdArgs& a, int* out, int cap);
 // blockIdx -> (batch, kv head, q head, block) of decode_work (ranked = 0) / decode_work_ranked (1) on the host (tests): fa_fwd_f32.hip
 void work_order_dump(int ranked, int bid, int B, int Hq, int Hkv, int nblk, int flag, int* out4);
 // bytes of workspace launch_fwd / launch_paged_decode would allocate for these arguments (0: single-launch path)
-uint64_t fwd_workspace_bytes(FwdArgs a);
-uint64_t paged_workspace_bytes(PagedArgs a);
+uint64_t fwd_workspace_bytes(const FwdArgs& a);
+uint64_t paged_workspace_bytes(const PagedArgs& a);
 int launch_bwd(const BwdArgs& a, hipStream_t stream);
 int bwd_last_route();   // BwdPlan::route of the most recent launch_bwd of this process (fa_bwd_plan.h: the plan, the workspace sizes); 0 before the first
 

@@ -346,6 +346,15 @@ const char* aule_hip_build_info(void);
 /* 9 the head_dim 256 kernel (16-bit); -3 bad.                                                                       */
 /* Host logic only, no aule_init().                                                                                  */
 int32_t aule_hip_debug_forward_route(const aule_attn_desc* desc);
+/* Debug: the route of the most recent forward launch of this process (the same codes); 0 before the first.          */
+int32_t aule_hip_debug_last_forward_route(void);
+/* Debug: the launch plan of aule_attention_forward_ex(desc) (csrc/fa_fwd_plan.h) as integers -- out = {route, workspace */
+/* bytes low 32 bits, high 32 bits, then the chosen route's own plan: 0 {key-range pieces per Q block}; 4 {32-row tiles   */
+/* per unit, key tiles per wave, workgroups along the keys, partials per row, partial rows}; 5 {heads per KV head, packed */
+/* rows, Q blocks, base workgroups, key tiles, KV splits, keys per split, 32-row tiles per unit}; 7 {pieces n, pairs, Q   */
+/* blocks, work items}; 8 {paired, work per head, work items, workgroups, rounds, heads per round}; 1 and 9 nothing}.     */
+/* Returns the ints written (negative: the capacity needed); -3 bad.  Host logic only, no aule_init().                    */
+int32_t aule_hip_debug_forward_plan(const aule_attn_desc* desc, int32_t* out, int32_t cap);
 /* Debug: bit mask of the kernels the most recent backward launch of this process ran -- 1 the 5-matmul mode (delta pass, dK/dV kernel  */
 /* spilling its dS, dQ = dS K), 2 / 4 the one-wave-per-SIMD dQ / dK/dV kernel, 8 / 16 their two-waves-per-SIMD predecessors, 32 the    */
 /* fp32 kernels, 64 (with 4) the D = 64 dK/dV instance with two key blocks per wave, 128 the head_dim 256 kernels (with 32 for fp32);  */

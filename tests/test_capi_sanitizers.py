@@ -38,9 +38,29 @@ lib.aule_tensor_clear_all()
 lib.aule_hip_debug_forward_route.restype = ctypes.c_int32
 lib.aule_hip_debug_forward_route.argtypes = [ctypes.POINTER(_capi.AttnDesc)]
 assert lib.aule_hip_debug_forward_route(None) == -3
+lib.aule_hip_debug_forward_plan.restype = ctypes.c_int32
+lib.aule_hip_debug_forward_plan.argtypes = [ctypes.POINTER(_capi.AttnDesc), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
+assert lib.aule_hip_debug_forward_plan(None, None, 0) == -3 and lib.aule_hip_debug_last_forward_route() >= 0
 d = _capi.AttnDesc()
 assert lib.aule_hip_debug_forward_route(ctypes.byref(d)) == -3          # struct_size 0
 assert lib.aule_attention_forward_ex(ctypes.byref(d)) in (-1, -3)
+# empty extents (batch 0, seq_q 0) reach the plan through the pure hooks, which do not look at the extents: an answer, never a trap
+for dtype, B, Hq, g, Sq, Sk, D, causal in itertools.product((0, 1, 2), (0, 1, 64), (8, 32), (1, 8), (0, 1, 64, 4096), (1, 1024, 8192, 131072),
+                                                          (32, 64, 128, 256), (0, 1, 2)):
+    if B and Sq:
+        continue
+    d = _capi.AttnDesc()
+    d.struct_size = ctypes.sizeof(_capi.AttnDesc)
+    d.dtype, d.causal, d.window_size = dtype, causal, -1
+    d.batch, d.heads_q, d.heads_kv, d.seq_q, d.seq_k, d.head_dim = B, Hq, Hq // g, Sq, Sk, D
+    r = lib.aule_hip_debug_forward_route(ctypes.byref(d))
+    pbuf = (ctypes.c_int32 * 16)()
+    assert r in (0, 1, 4, 5, 7, 8, 9) and lib.aule_hip_debug_forward_plan(ctypes.byref(d), pbuf, 16) >= 3 and pbuf[0] == r, (B, Sq, r)
+    assert lib.aule_hip_debug_forward_split_plan(ctypes.byref(d), None, 0) <= 0
+    assert lib.aule_attention_forward_workspace_size(ctypes.byref(d)) == 0
+if len(sys.argv) > 1 and sys.argv[1] == "empty":   # (one switch leg of tests/fwd_sweep.py: the rest of the sweep runs in the default leg)
+    print("SANITIZED-OK empty extents")
+    sys.exit(0)
 routes = {}
 n = 0
 for dtype, B, Hq, g, Sq, Sk, D, causal, W in itertools.product(
@@ -55,7 +75,7 @@ for dtype, B, Hq, g, Sq, Sk, D, causal, W in itertools.product(
     d.causal, d.window_size, d.scale = causal, W, 0.0
     r = lib.aule_hip_debug_forward_route(ctypes.byref(d))
     routes[r] = routes.get(r, 0) + 1
-    # the launch plans of the two-launch paths (dry runs: no device work, no allocation)
+    # the launch plans of the two-launch paths (host logic: no device work, no allocation)
     ws = lib.aule_attention_forward_workspace_size(ctypes.byref(d))
     assert ws >= 0 and (ws == 0 or r in (0, 4, 5, 7)), (r, ws)   # (0: the fp32 forward's key-range pieces on small grids, round 5)
     if r == 0 and ws:
@@ -68,6 +88,14 @@ for dtype, B, Hq, g, Sq, Sk, D, causal, W in itertools.product(
         assert lib.aule_hip_debug_forward_split_plan(ctypes.byref(d), buf, -need) == -need
         assert lib.aule_hip_debug_forward_split_plan(ctypes.byref(d), buf, -need - 1) == need
         assert ws == buf[0] * B * Hq * Sq * (D + 4) * 4, (ws, buf[0])
+    # the whole launch plan (aule_hip_debug_forward_plan): exact capacity, one int short, and its agreement with the entries above
+    need = -lib.aule_hip_debug_forward_plan(ctypes.byref(d), None, 0)
+    assert need >= 3, need
+    pbuf = (ctypes.c_int32 * need)()
+    assert lib.aule_hip_debug_forward_plan(ctypes.byref(d), pbuf, need) == need
+    assert lib.aule_hip_debug_forward_plan(ctypes.byref(d), pbuf, need - 1) == -need
+    # (the size entry answers 0 for a bottom-right mask with seq_k < seq_q, which the call refuses; the plan hooks do not look)
+    assert pbuf[0] == r and ((pbuf[1] & 0xFFFFFFFF) | (pbuf[2] << 32) == ws or (causal == 2 and Sk < Sq and ws == 0)), (r, ws, list(pbuf))
     # the fused-rotation rule: host logic, the table pointers are never dereferenced
     rp = _capi.AttnRope()
     rp.struct_size = ctypes.sizeof(_capi.AttnRope)
@@ -132,6 +160,15 @@ def test_host_code_under_asan_and_ubsan():
     r = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "SANITIZED-OK" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+    # the empty-extent descriptors under every forward switch leg (a leg changes which rule sees them first)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fwd_sweep
+    for leg, leg_env in fwd_sweep.LEGS.items():
+        if not leg_env:
+            continue
+        r = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}, "empty"], env=dict(env, **leg_env), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and "SANITIZED-OK" in r.stdout, (leg, r.stdout[-1500:], r.stderr[-3000:])
+        assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, (leg, r.stderr[-3000:])
 
 
 def test_aule_backend_env(monkeypatch):

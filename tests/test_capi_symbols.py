@@ -473,3 +473,69 @@ def test_backward_route_hook_follows_the_dispatch_rules():
         setattr(d, field, good)
     d.seq_q, d.causal = 512, 2                                               # bottom-right needs seq_k >= seq_q
     assert lib.aule_hip_debug_backward_route(ctypes.byref(d)) == -3
+
+
+def test_forward_plans_match_the_recorded_table():
+    """Route, workspace size, route 7's split plan and every route's sub-plan over the fixed sweep of tests/fwd_sweep.py, per switch,
+    value for value against tests/golden/fwd_plan_sweep.npz -- recorded from the library as it was before fwd_plan() (fa_fwd_plan.h)
+    became the one statement of the forward's route, workspace and launch plans; the paged workspace sizes with it.  Without a
+    device the CU count answers 256, so the table holds on both machines.  A difference is a bug in the plan, not a table to
+    regenerate.  aule_hip_debug_forward_plan must also agree with the three older entries on every case."""
+    import numpy as np
+    import fwd_sweep
+    gold = np.load(fwd_sweep.FIXTURE)
+    cases = fwd_sweep.cases()
+    assert len(cases) == 48600 and len(fwd_sweep.paged_cases()) == 1296
+    assert sorted(gold.files) == sorted([leg + "." + k for leg in fwd_sweep.LEGS for k in ("route", "ws", "split", "split_off", "sub", "sub_off")] + ["paged"])
+    assert set(np.unique(gold["default.route"])) == {0, 1, 4, 5, 7, 8, 9}                 # every route in the default leg
+    fp32_d256 = np.asarray([dt == 0 and D == 256 for (dt, B, hq, hkv, sq, sk, D, c, w, s) in cases])
+    for leg, env in fwd_sweep.LEGS.items():
+        got = fwd_sweep.run_leg(env, paged=leg == "default")
+        for k in ("route", "ws"):
+            bad = np.nonzero(got[k] != gold[leg + "." + k])[0]
+            assert bad.size == 0, (leg, k, bad.size, [(cases[i], int(got[k][i]), int(gold[leg + "." + k][i])) for i in bad[:5]])
+        assert np.array_equal(got["split_off"], gold[leg + ".split_off"]) and np.array_equal(got["split"], gold[leg + ".split"]), leg
+        if leg == "default":
+            assert np.array_equal(got["paged"], gold["paged"]), np.nonzero(got["paged"] != gold["paged"])[0][:5]
+        # the new hook against the older entries: route, bytes, and n / pairs of route 7's dump
+        plan, off = got["plan"], got["plan_off"][:-1]
+        route = got["route"].astype(np.int64)
+        assert np.array_equal(plan[off], route), leg
+        assert np.array_equal(plan[off + 1].astype(np.uint32).astype(np.int64) | (plan[off + 2].astype(np.uint32).astype(np.int64) << 32), got["ws"]), leg
+        r7 = route == 7
+        assert np.array_equal(plan[off[r7] + 3], got["split"][got["split_off"][:-1][r7]]), leg
+        assert np.array_equal(plan[off[r7] + 4], got["split"][got["split_off"][:-1][r7] + 1]), leg
+        assert np.array_equal(np.diff(got["plan_off"]), 3 + np.asarray([fwd_sweep.SUB_INTS[int(r)] for r in route])), leg
+        # ... and its sub-plans against the table.  (fp32 at head_dim 256 is route 0 run by the head_dim 256 file: one launch, pieces
+        # = 1; the library the table was recorded from computed no piece count there, so the table holds nothing for those cases)
+        sub, sub_off = fwd_sweep.sub_plans(got)
+        assert np.all(sub[sub_off[:-1][fp32_d256]] == 1) and np.all(np.diff(gold[leg + ".sub_off"])[fp32_d256] == 0), leg
+        keep = np.ones(sub.size, bool)
+        keep[sub_off[:-1][fp32_d256]] = False
+        n = np.diff(sub_off) - fp32_d256
+        assert np.array_equal(n, np.diff(gold[leg + ".sub_off"])), leg
+        bad = np.nonzero(sub[keep] != gold[leg + ".sub"])[0]
+        assert bad.size == 0, (leg, bad.size, bad[:5])
+
+
+def test_forward_plan_hook_refuses_bad_descriptors():
+    """aule_hip_debug_forward_plan refuses what aule_hip_debug_forward_route refuses, and follows the capacity contract of
+    aule_hip_debug_forward_split_plan (negative: the ints needed)."""
+    lib = _capi.load()
+    buf = (ctypes.c_int32 * 16)()
+    assert lib.aule_hip_debug_forward_plan(None, buf, 16) == -3 and lib.aule_hip_debug_forward_route(None) == -3
+    d = _capi.AttnDesc()
+    assert lib.aule_hip_debug_forward_plan(ctypes.byref(d), buf, 16) == -3 == lib.aule_hip_debug_forward_route(ctypes.byref(d))   # struct_size 0
+    d.struct_size = ctypes.sizeof(_capi.AttnDesc)
+    d.dtype, d.batch, d.heads_q, d.heads_kv, d.seq_q, d.seq_k, d.head_dim, d.causal = 2, 4, 32, 32, 4096, 4096, 128, 1
+    assert lib.aule_hip_debug_forward_route(ctypes.byref(d)) == 8
+    assert lib.aule_hip_debug_forward_plan(ctypes.byref(d), None, 0) == -9 and lib.aule_hip_debug_forward_plan(ctypes.byref(d), buf, 8) == -9
+    assert lib.aule_hip_debug_forward_plan(ctypes.byref(d), buf, 16) == 9
+    assert list(buf[:9]) == [8, 0, 0, 1, 8, 1024, 256, 8, 2]      # the headline shape: 8 pairs x 128 heads on 256 workgroups, 8 rounds of 2 heads
+    for field, bad in (("heads_kv", 3), ("heads_kv", 0), ("causal", 3), ("causal", -1), ("struct_size", 104)):
+        keep = getattr(d, field)
+        setattr(d, field, bad)
+        assert lib.aule_hip_debug_forward_route(ctypes.byref(d)) == -3, field
+        assert lib.aule_hip_debug_forward_plan(ctypes.byref(d), buf, 16) == -3, field
+        setattr(d, field, keep)
+    assert lib.aule_hip_debug_forward_plan(ctypes.byref(d), buf, 16) == 9
