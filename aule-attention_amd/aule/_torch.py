@@ -54,6 +54,27 @@ def _abi_scale(scale):
     return scale if scale != 0.0 else 1e-30
 
 
+def _window_arg(window):
+    """The descriptors' window_size: the window when it is one (> 0), else -1 (full attention)."""
+    return int(window) if window is not None and window > 0 else -1
+
+
+def _device_index(device):
+    """The HIP ordinal of a torch device; an index-less "cuda" device means the current one at the time of the call."""
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
+def _attn_problem(d, q, k, causal, scale, window):
+    """The problem statement AttnDesc and AttnBwdDesc share, from q [B,Hq,Sq,D] and k [B,Hkv,Sk,D]; returns d."""
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    d.batch, d.heads_q, d.heads_kv, d.seq_q, d.seq_k, d.head_dim = q.shape[0], q.shape[1], k.shape[1], q.shape[2], k.shape[2], q.shape[3]
+    d.scale = scale
+    d.causal = causal_code(causal)
+    d.window_size = _window_arg(window)
+    return d
+
+
 def _same_device(what, ref, *tensors):
     for t in tensors:
         if t.device != ref.device:
@@ -125,19 +146,12 @@ def _fwd_desc(lib, q, k, causal, scale, window):
         cache = _desc_cache.fwd = {}
     # (the key holds VALUES -- a 0-dim tensor or numpy scalar as `scale` / `window` hashes by identity, never hits and stays alive in
     # the cache -- and the RESOLVED device: an index-less "cuda" device means the current one at the time of the call)
-    dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(q.device)
     key = (q.dtype, tuple(q.shape), int(k.shape[1]), int(k.shape[2]), causal_code(causal), None if scale is None else float(scale),
-           int(window) if window is not None and window > 0 else -1, dev)
+           _window_arg(window), dev)
     ent = cache.get(key)
     if ent is None:
-        B, Hq, Sq, D = q.shape
-        d = _capi.AttnDesc()
-        d.struct_size = ctypes.sizeof(_capi.AttnDesc)
-        d.dtype = _DTYPES[q.dtype]
-        d.batch, d.heads_q, d.heads_kv, d.seq_q, d.seq_k, d.head_dim = B, Hq, k.shape[1], Sq, k.shape[2], D
-        d.scale = _abi_scale(scale)
-        d.causal = causal_code(causal)
-        d.window_size = int(window) if window is not None and window > 0 else -1
+        d = _attn_problem(_capi.AttnDesc(), q, k, causal, _abi_scale(scale), window)
         d.device = dev
         if len(cache) >= 512:
             cache.clear()
@@ -147,19 +161,13 @@ def _fwd_desc(lib, q, k, causal, scale, window):
 
 def rope_fusable(q, k, causal, window, cos, sin, q_pos, scale=None):
     """Would the forward kernel rotate Q itself for this problem (aule_attention_forward_rope_fusable)?  Host logic only:
-    no device, no aule_init().  scale: the softmax scale of the call (None = default); it is part of the answer -- the kernel that
-    rotates Q does not take negative scales (round 5: without it, flash_attention_rope(scale < 0) chose the fused form in inference
-    and the launch then refused it; found by tools/fuzz_parity.py split)."""
+    no device, no aule_init().  scale: the softmax scale of the call (None = default); its sign is part of the problem the library
+    plans (negative scales and causal windows of at least two key tiles are rotated in the kernel too since round 6), so the
+    question is asked about the descriptor the launch will see."""
     lib = _capi.load()
     if q.dtype not in _DTYPES or q.numel() == 0 or cos.stride(-1) != 1:
         return False
-    d = _capi.AttnDesc()
-    d.struct_size = ctypes.sizeof(_capi.AttnDesc)
-    d.dtype = _DTYPES[q.dtype]
-    d.batch, d.heads_q, d.heads_kv, d.seq_q, d.seq_k, d.head_dim = q.shape[0], q.shape[1], k.shape[1], q.shape[2], k.shape[2], q.shape[3]
-    d.causal = causal_code(causal)
-    d.window_size = int(window) if window is not None and window > 0 else -1
-    d.scale = 0.0 if scale is None else _abi_scale(scale)
+    d = _attn_problem(_capi.AttnDesc(), q, k, causal, 0.0 if scale is None else _abi_scale(scale), window)
     r = _attn_rope(cos, sin, q_pos)
     return lib.aule_attention_forward_rope_fusable(ctypes.byref(d), ctypes.byref(r)) == 1
 
@@ -167,19 +175,11 @@ def rope_fusable(q, k, causal, window, cos, sin, q_pos, scale=None):
 def bwd_raw(q, k, v, out, dout, lse, causal, scale, window=-1):
     lib = _capi.get_lib()
     _same_device("flash attention backward", q, k, v, out, dout, lse)
-    B, Hq, Sq, D = q.shape
-    Hkv, Sk = k.shape[1], k.shape[2]
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     if q.numel() == 0 or k.numel() == 0:
         return dq.zero_(), dk.zero_(), dv.zero_()
-    d = _capi.AttnBwdDesc()
-    d.struct_size = ctypes.sizeof(_capi.AttnBwdDesc)
-    d.dtype = _DTYPES[q.dtype]
-    d.batch, d.heads_q, d.heads_kv, d.seq_q, d.seq_k, d.head_dim = B, Hq, Hkv, Sq, Sk, D
-    d.scale = _abi_scale(scale)
-    d.causal = causal_code(causal)
-    d.window_size = int(window) if window is not None and window > 0 else -1
-    d.device = q.device.index if q.device.index is not None else torch.cuda.current_device()
+    d = _attn_problem(_capi.AttnBwdDesc(), q, k, causal, _abi_scale(scale), window)
+    d.device = _device_index(q.device)
     d.stream = _stream_ptr(q.device)
     d.q, d.k, d.v, d.out, d.dout, d.lse = (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
                                             dout.data_ptr(), lse.data_ptr())
@@ -285,7 +285,7 @@ def rope_raw(x, cos, sin, layout="half", inverse=False, pos_offset=0, out=None):
     d.rows_bh, d.seq, d.head_dim, d.row_pitch = B * H, S, D, D
     d.table_len, d.table_pitch = cos.shape[0], 0
     d.layout, d.inverse, d.pos_offset = _ROPE_LAYOUTS[layout], 1 if inverse else 0, int(pos_offset)
-    d.device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    d.device = _device_index(x.device)
     d.stream = _stream_ptr(x.device)
     d.in_, d.out, d.cos, d.sin = x.data_ptr(), out.data_ptr(), cos.data_ptr(), sin.data_ptr()
     _capi.check(lib.aule_rope_ex(ctypes.byref(d)), "aule_rope_ex")
@@ -401,6 +401,33 @@ def _fp8_scale(s, Hkv, device, name):
     return s.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _paged_cache_is_fp8(op, inputs, k_cache, v_cache, k_scale, v_scale):
+    """The cache-kind rules paged_decode and paged_kv_append share -- caches of one dtype, torch.float8_e4m3fn the only FP8 encoding,
+    fp16 / bf16 inputs (and 16-bit caches) of one dtype, scales with FP8 caches only, head_dim in PAGED_HEAD_DIMS -- as ValueErrors
+    in that operation's words.  inputs: (q,) or (key, value).  Returns whether the caches are FP8."""
+    name, fp8_use, same, with_fp8, dims_of = {
+        "decode": ("paged decode", "the FP8 paged decode takes", "query and caches", "an fp16 / bf16 query", "paged decode"),
+        "append": ("paged KV append", "the paged KV append writes", "key, value and caches", "fp16 / bf16 key and value", "the paged KV cache"),
+    }[op]
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"k_cache ({k_cache.dtype}) and v_cache ({v_cache.dtype}) must have the same dtype")
+    other_fp8 = tuple(t for t in (getattr(torch, n, None) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz"))
+                      if t is not None)
+    if k_cache.dtype in other_fp8:
+        raise ValueError(f"{k_cache.dtype} caches are not supported: {fp8_use} torch.float8_e4m3fn only "
+                         "(gfx950 converts OCP e4m3fn in hardware; e4m3fnuz is MI300X's encoding, e5m2 is not built)")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    dtype = inputs[0].dtype
+    if dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != dtype for t in inputs[1:]) or (not fp8 and k_cache.dtype != dtype):
+        raise ValueError(f"{name} runs in fp16 or bf16 ({same} in the same dtype, or float8_e4m3fn caches with {with_fp8})")
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError("k_scale / v_scale apply to float8_e4m3fn caches only; a 16-bit cache holds the values themselves")
+    D = inputs[0].shape[-1]
+    if D not in PAGED_HEAD_DIMS:
+        raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS} for {dims_of}, got {D}")
+    return fp8
+
+
 def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1, k_scale=None, v_scale=None):
     """Paged-KV decode on the HIP backend; counterpart of flash_attention_paged_amd
     (python/aule/triton_flash_amd.py:656-737), same argument meaning:
@@ -427,21 +454,7 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, wi
         raise ValueError(f"head_dim mismatch: query={D}, cache={Dk}")
     if Hq % Hkv != 0:
         raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
-    if k_cache.dtype != v_cache.dtype:
-        raise ValueError(f"k_cache ({k_cache.dtype}) and v_cache ({v_cache.dtype}) must have the same dtype")
-    other_fp8 = tuple(t for t in (getattr(torch, n, None) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz"))
-                      if t is not None)
-    if k_cache.dtype in other_fp8:
-        raise ValueError(f"{k_cache.dtype} caches are not supported: the FP8 paged decode takes torch.float8_e4m3fn only "
-                         "(gfx950 converts OCP e4m3fn in hardware; e4m3fnuz is MI300X's encoding, e5m2 is not built)")
-    fp8 = k_cache.dtype == torch.float8_e4m3fn
-    if q.dtype not in (torch.float16, torch.bfloat16) or (not fp8 and k_cache.dtype != q.dtype):
-        raise ValueError("paged decode runs in fp16 or bf16 (query and caches in the same dtype, or float8_e4m3fn caches "
-                         "with an fp16 / bf16 query)")
-    if not fp8 and (k_scale is not None or v_scale is not None):
-        raise ValueError("k_scale / v_scale apply to float8_e4m3fn caches only; a 16-bit cache holds the values themselves")
-    if D not in PAGED_HEAD_DIMS:
-        raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS} for paged decode, got {D}")
+    fp8 = _paged_cache_is_fp8("decode", (q,), k_cache, v_cache, k_scale, v_scale)
     if fp8:
         ks = _fp8_scale(k_scale, Hkv, q.device, "k_scale")
         vs = _fp8_scale(v_scale, Hkv, q.device, "v_scale")
@@ -464,8 +477,8 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, wi
     d.batch, d.heads_q, d.heads_kv, d.head_dim = B, Hq, Hkv, D
     d.block_size, d.max_blocks = block_size, bt.shape[1]
     d.scale = _abi_scale(scale)
-    d.window_size = int(window_size) if window_size is not None and window_size > 0 else -1
-    d.device = q.device.index if q.device.index is not None else torch.cuda.current_device()
+    d.window_size = _window_arg(window_size)
+    d.device = _device_index(q.device)
     d.stream = _stream_ptr(q.device)
     d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
     ws_size = lib.aule_attention_paged_decode_fp8_workspace_size if fp8 else lib.aule_attention_paged_decode_workspace_size
@@ -540,21 +553,7 @@ def paged_kv_append(key, value, k_cache, v_cache, slot_mapping, k_scale=None, v_
         raise ValueError(f"head_dim mismatch: key={D}, cache={Dc}")
     if Hc != Hkv:
         raise ValueError(f"heads_kv mismatch: key={Hkv}, cache={Hc}")
-    if k_cache.dtype != v_cache.dtype:
-        raise ValueError(f"k_cache ({k_cache.dtype}) and v_cache ({v_cache.dtype}) must have the same dtype")
-    other_fp8 = tuple(t for t in (getattr(torch, n, None) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz"))
-                      if t is not None)
-    if k_cache.dtype in other_fp8:
-        raise ValueError(f"{k_cache.dtype} caches are not supported: the paged KV append writes torch.float8_e4m3fn only "
-                         "(gfx950 converts OCP e4m3fn in hardware; e4m3fnuz is MI300X's encoding, e5m2 is not built)")
-    fp8 = k_cache.dtype == torch.float8_e4m3fn
-    if key.dtype not in (torch.float16, torch.bfloat16) or value.dtype != key.dtype or (not fp8 and k_cache.dtype != key.dtype):
-        raise ValueError("paged KV append runs in fp16 or bf16 (key, value and caches in the same dtype, or float8_e4m3fn "
-                         "caches with fp16 / bf16 key and value)")
-    if not fp8 and (k_scale is not None or v_scale is not None):
-        raise ValueError("k_scale / v_scale apply to float8_e4m3fn caches only; a 16-bit cache holds the values themselves")
-    if D not in PAGED_HEAD_DIMS:
-        raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS} for the paged KV cache, got {D}")
+    fp8 = _paged_cache_is_fp8("append", (key, value), k_cache, v_cache, k_scale, v_scale)
     if not k_cache.is_contiguous() or not v_cache.is_contiguous():
         raise ValueError("k_cache and v_cache must be contiguous: the append writes in place and cannot copy them")
     if block_size == 0 or Hkv == 0:
@@ -600,7 +599,7 @@ def paged_kv_append(key, value, k_cache, v_cache, slot_mapping, k_scale=None, v_
     d.key_head_stride = key.stride(1) if Hkv > 1 else D
     d.value_token_stride = value.stride(0) if T > 1 else Hkv * max(value.stride(1), D)
     d.value_head_stride = value.stride(1) if Hkv > 1 else D
-    d.device = dev.index if dev.index is not None else torch.cuda.current_device()
+    d.device = _device_index(dev)
     d.stream = _stream_ptr(dev)
     d.key, d.value, d.k_cache, d.v_cache = key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
     d.slot_mapping = slots.data_ptr()

@@ -40,6 +40,10 @@ static_assert(offsetof(aule_paged_fp8_desc, q) == offsetof(aule_paged_desc, q) &
                   offsetof(aule_paged_fp8_desc, k_scale) == sizeof(aule_paged_desc),
               "aule_paged_fp8_desc starts with aule_paged_desc (the paged entry points read both through that prefix)");
 static_assert(sizeof(aule_attn_bwd_desc) == 144, "aule_attn_bwd_desc layout is part of the ABI");
+static_assert(offsetof(aule_attn_bwd_desc, dtype) == offsetof(aule_attn_desc, dtype) && offsetof(aule_attn_bwd_desc, head_dim) == offsetof(aule_attn_desc, head_dim) &&
+                  offsetof(aule_attn_bwd_desc, scale) == offsetof(aule_attn_desc, scale) && offsetof(aule_attn_bwd_desc, device) == offsetof(aule_attn_desc, device) &&
+                  offsetof(aule_attn_bwd_desc, stream) == 48 && offsetof(aule_attn_desc, stream) == 48 && offsetof(aule_attn_bwd_desc, q) == offsetof(aule_attn_desc, q),
+              "aule_attn_bwd_desc starts with aule_attn_desc's problem statement (both kinds are checked and read through that prefix)");
 static_assert(sizeof(aule_kv_append_desc) == 168 && offsetof(aule_kv_append_desc, key_token_stride) == 32 &&
                   offsetof(aule_kv_append_desc, table_len) == 64 && offsetof(aule_kv_append_desc, stream) == 80 &&
                   offsetof(aule_kv_append_desc, k_cache) == 104 && offsetof(aule_kv_append_desc, slot_mapping) == 120 &&
@@ -76,6 +80,39 @@ void set_error(const char* fmt, ...) {
     if (n < 0) n = 0;
     if ((size_t)n >= sizeof(g_err)) n = sizeof(g_err) - 1;
     g_err_len = (size_t)n;
+}
+
+// (the caller holds g_mu)
+bool initialised() {
+    if (!g_init) set_error("Library not initialized. Call aule_init() first.");
+    return g_init;
+}
+
+// The mask the kernels run, from an entry point's causal code and window and the Sq / Sk already in `a` (FwdArgs or BwdArgs):
+// coff from the code; a window that masks nothing is dropped -- W >= Sq + coff, the last query sits at position Sq - 1 + coff;
+// and one query at the bottom-right position sees every key: with no window the causal mask masks nothing, and the problem is
+// the non-causal one (which has the faster short-query paths).
+template <class Args>
+void set_mask(Args& a, int32_t causal_code, int32_t window, bool drop_trivial_causal = true) {
+    a.causal = causal_code != 0;
+    a.coff = causal_code == AULE_CAUSAL_BOTTOM_RIGHT ? a.Sk - a.Sq : 0;
+    a.window = (window > 0 && (uint32_t)window < (uint32_t)a.Sq + (uint32_t)a.coff) ? window : -1;
+    if (drop_trivial_causal && a.causal && a.Sq == 1 && a.coff > 0 && a.window <= 0) a.causal = a.coff = 0;
+}
+
+float resolve_scale(float scale, uint32_t D) {
+    if (scale == 0.0f || std::isnan(scale)) return 1.0f / std::sqrt((float)D);
+    return scale;
+}
+
+// The problem statement the forward and backward descriptors share (aule_attn_bwd_desc read through its prefix), into FwdArgs or BwdArgs.
+template <class Args>
+void fill_problem(const aule_attn_desc* d, Args& a, bool drop_trivial_causal) {
+    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
+    a.Sq = (int)d->seq_q; a.Sk = (int)d->seq_k; a.D = (int)d->head_dim;
+    a.scale = resolve_scale(d->scale, d->head_dim);
+    a.dtype = d->dtype; a.device = d->device;
+    set_mask(a, d->causal, d->window_size, drop_trivial_causal);
 }
 
 uint32_t pad_dim(uint32_t d) {
@@ -149,11 +186,10 @@ bool download_rows(float* dst, const float* src, uint32_t pitch, size_t rows, ui
 int run_fwd_f32(const float* q, const float* k, const float* v, float* o, float* lse, uint32_t B, uint32_t Hq,
                 uint32_t Hkv, uint32_t Sq, uint32_t Sk, uint32_t Dlogical, uint32_t Dp, int causal, int window = -1) {
     FwdArgs a;
-    a.window = (window > 0 && (uint32_t)window < Sq) ? window : -1;  // W >= Sq masks nothing
     a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse;
     a.B = (int)B; a.Hq = (int)Hq; a.Hkv = (int)Hkv; a.Sq = (int)Sq; a.Sk = (int)Sk; a.D = (int)Dp;
     a.scale = 1.0f / std::sqrt((float)Dlogical);  // attention_pipeline.zig:329
-    a.causal = causal != 0;
+    set_mask(a, causal != 0 ? AULE_CAUSAL_TOP_LEFT : AULE_CAUSAL_NONE, window);   // (the legacy entries: any non-zero `causal` is top-left)
     a.dtype = aule_hip::kF32;
     int rc = aule_hip::launch_fwd(a, nullptr);
     if (rc != 0) return rc;
@@ -521,10 +557,7 @@ int32_t aule_attention_forward_gpu(aule_tensor_handle qh, aule_tensor_handle kh,
 /* ------------------------------------------------------ host-pointer paths */
 static int32_t forward_host(const float* query, const float* key, const float* value, float* output, float* lse,
                             uint32_t B, uint32_t H, uint32_t S, uint32_t D, int32_t causal) {
-    if (!g_init) {
-        set_error("Library not initialized. Call aule_init() first.");
-        return -1;
-    }
+    if (!initialised()) return -1;
     if (D > 256) {
         set_error("Attention failed: error.HeadDimTooLarge (head_dim %u > 256)", D);
         return -4;
@@ -575,10 +608,7 @@ int32_t aule_attention_backward(const float* query, const float* key, const floa
                                 float* grad_value, uint32_t B, uint32_t H, uint32_t S, uint32_t D,
                                 int32_t causal) {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_init) {
-        set_error("Library not initialized. Call aule_init() first.");
-        return -1;
-    }
+    if (!initialised()) return -1;
     if (D > 256) {
         set_error("Backward failed: error.HeadDimTooLarge (head_dim %u > 256)", D);
         return -4;
@@ -651,36 +681,53 @@ int32_t aule_attention_forward_gravity(aule_tensor_handle, aule_tensor_handle, a
 }
 
 /* ------------------------------------------------------------ _ex entries */
-static int check_common(int32_t dtype, uint32_t B, uint32_t Hq, uint32_t Hkv, uint32_t Sq, uint32_t Sk,
-                        uint32_t D, int32_t window, int32_t causal) {
-    if (causal < 0 || causal > AULE_CAUSAL_BOTTOM_RIGHT) {
-        set_error("Attention failed: unknown causal mode %d (0 none, 1 top-left, 2 bottom-right)", causal);
-        return -3;
-    }
-    if (causal == AULE_CAUSAL_BOTTOM_RIGHT && Sk < Sq) {
-        set_error("Attention failed: bottom-right causal alignment needs seq_k (%u) >= seq_q (%u)", Sk, Sq);
-        return -3;
-    }
-    if (dtype < 0 || dtype > 2) {
-        set_error("Attention failed: unknown dtype %d", dtype);
-        return -3;
-    }
-    if (D != 32 && D != 64 && D != 128 && D != 256) {
-        set_error("Attention failed: head_dim %u unsupported (32, 64, 128 or 256; pad to the next size)", D);
-        return -3;
-    }
-    if (Hkv == 0 || Hq % Hkv != 0) {
-        set_error("Attention failed: heads_q (%u) must be divisible by heads_kv (%u)", Hq, Hkv);
-        return -3;
-    }
-    (void)window;  // any value is accepted: <= 0 means full attention
-    // per-head K/V/Q slabs are addressed through 32-bit buffer descriptors (raw SRD, byte offsets)
-    if ((uint64_t)B * Hq * Sq * D >= (1ull << 40) || (uint64_t)Sq * D * 4 >= (1ull << 31) ||
-        (uint64_t)Sk * D * 4 >= (1ull << 31)) {
-        set_error("Attention failed: problem too large");
-        return -3;
-    }
-    return 0;
+// The descriptor checkers, one per kind: pure host logic (no lock, no g_init, no pointer dereferenced).  Each answers nullptr
+// or the reason the descriptor is refused (kv_append_error further down is the model); a reason that carries values is
+// formatted into the caller's Reason.  What has nothing to do is a predicate of its own per kind; null pointers, workspace
+// sizes and the size limits of the launches are rules of the launch entries.
+struct Reason { char text[128]; };
+static const char kBadDescriptor[] = "bad descriptor (struct_size mismatch)";
+
+static const char* reasonf(Reason& r, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(r.text, sizeof(r.text), fmt, ap);
+    va_end(ap);
+    return r.text;
+}
+
+// aule_attn_desc and aule_attn_bwd_desc state the problem in the same leading fields (the layout asserts at the top of this file):
+// both are checked and read through the forward descriptor's; `size` is the kind's own sizeof.
+static const aule_attn_desc* attn_prefix(const aule_attn_bwd_desc* d) { return reinterpret_cast<const aule_attn_desc*>(d); }
+
+// plan_hook: the three forward plan hooks still answer for a bottom-right mask with seq_k < seq_q (tests/test_capi_sanitizers.py
+// pins what they say there); every other reader refuses it like the launch.
+static const char* attn_desc_error(const aule_attn_desc* d, size_t size, Reason& why, bool plan_hook = false) {
+    if (d == nullptr || d->struct_size != size) return kBadDescriptor;
+    if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT)
+        return reasonf(why, "unknown causal mode %d (0 none, 1 top-left, 2 bottom-right)", d->causal);
+    if (d->causal == AULE_CAUSAL_BOTTOM_RIGHT && d->seq_k < d->seq_q && !plan_hook)
+        return reasonf(why, "bottom-right causal alignment needs seq_k (%u) >= seq_q (%u)", d->seq_k, d->seq_q);
+    if (d->dtype < 0 || d->dtype > 2) return reasonf(why, "unknown dtype %d", d->dtype);
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128 && d->head_dim != 256)
+        return reasonf(why, "head_dim %u unsupported (32, 64, 128 or 256; pad to the next size)", d->head_dim);
+    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0)
+        return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
+    return nullptr;   // (window_size: any value is accepted, <= 0 means full attention)
+}
+
+static bool fwd_nothing_to_do(const aule_attn_desc* d) { return (uint64_t)d->batch * d->heads_q * d->seq_q == 0; }  // no output element
+static bool bwd_nothing_to_do(const aule_attn_desc* d) { return fwd_nothing_to_do(d) && (uint64_t)d->batch * d->heads_kv * d->seq_k == 0; }  // ... and no key element
+
+// The launches' size limit: per-head K/V/Q slabs are addressed through 32-bit buffer descriptors (raw SRD, byte offsets).
+static bool attn_too_large(const aule_attn_desc* d) {
+    return (uint64_t)d->batch * d->heads_q * d->seq_q * d->head_dim >= (1ull << 40) || (uint64_t)d->seq_q * d->head_dim * 4 >= (1ull << 31) ||
+           (uint64_t)d->seq_k * d->head_dim * 4 >= (1ull << 31);
+}
+
+// aule_attention_forward_rope_fusable's own limit (it answers without the launch's): extents the plan's int arithmetic holds.
+static bool rope_fusable_too_large(const aule_attn_desc* d) {
+    return d->batch >= (1u << 24) || d->heads_q >= (1u << 24) || d->seq_q >= (1u << 30) || d->seq_k >= (1u << 30);
 }
 
 // roctx ranges around the launches (the reference has no tracing at all), so that
@@ -728,32 +775,10 @@ struct RoctxRange {
     RoctxRange& operator=(const RoctxRange&) = delete;
 };
 
-// One query at the bottom-right position sees every key: with no window the causal mask masks nothing, and the
-// problem is the non-causal one (which has the faster short-query paths).
-static void drop_trivial_causal(int& causal, int& coff, int Sq, int window) {
-    if (causal && Sq == 1 && coff > 0 && window <= 0) {
-        causal = 0;
-        coff = 0;
-    }
-}
-
-static float resolve_scale(float scale, uint32_t D) {
-    if (scale == 0.0f || std::isnan(scale)) return 1.0f / std::sqrt((float)D);
-    return scale;
-}
-
 // Descriptor -> launch arguments, once per direction (every entry point that reads a descriptor; no device work, no pointer dereferenced).
 static void fill_fwd_args(const aule_attn_desc* d, FwdArgs& a) {
     a.q = d->q; a.k = d->k; a.v = d->v; a.o = d->out; a.lse = d->lse;
-    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
-    a.Sq = (int)d->seq_q; a.Sk = (int)d->seq_k; a.D = (int)d->head_dim;
-    a.scale = resolve_scale(d->scale, d->head_dim);
-    a.causal = d->causal != 0;
-    a.coff = d->causal == AULE_CAUSAL_BOTTOM_RIGHT ? (int)d->seq_k - (int)d->seq_q : 0;
-    a.dtype = d->dtype; a.device = d->device;
-    // W >= Sq + coff masks nothing (the last query sits at position Sq - 1 + coff)
-    a.window = (d->window_size > 0 && (uint32_t)d->window_size < d->seq_q + (uint32_t)a.coff) ? d->window_size : -1;
-    drop_trivial_causal(a.causal, a.coff, a.Sq, a.window);
+    fill_problem(d, a, true);
     a.ws = d->workspace; a.ws_bytes = d->workspace ? d->workspace_bytes : 0;
 }
 
@@ -764,16 +789,10 @@ static void fill_bwd_args(const aule_attn_bwd_desc* d, BwdArgs& a, bool as_launc
     a.q = d->q; a.k = d->k; a.v = d->v; a.o = d->out; a.dout = d->dout; a.lse = d->lse;
     a.dq = d->dq; a.dk = d->dk; a.dv = d->dv; a.delta = (float*)d->workspace;
     a.ws_bytes = d->workspace_bytes;
-    a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
-    a.Sq = (int)d->seq_q; a.Sk = (int)d->seq_k; a.D = (int)d->head_dim;
-    a.scale = resolve_scale(d->scale, d->head_dim);
-    a.causal = d->causal != 0;
-    a.coff = d->causal == AULE_CAUSAL_BOTTOM_RIGHT ? (int)d->seq_k - (int)d->seq_q : 0;
-    a.dtype = d->dtype; a.device = d->device;
-    a.window = (d->window_size > 0 && (uint32_t)d->window_size < d->seq_q + (uint32_t)a.coff) ? d->window_size : -1;   // as fill_fwd_args
+    fill_problem(attn_prefix(d), a, false);
     if (!as_launched) return;
     a.ws_floor = aule_hip::bwd_plan(a).min_bytes;
-    drop_trivial_causal(a.causal, a.coff, a.Sq, a.window);
+    set_mask(a, d->causal, d->window_size);
 }
 
 static bool fill_rope_args(const aule_attn_rope* r, uint32_t head_dim, FwdArgs& a) {
@@ -788,18 +807,15 @@ static bool fill_rope_args(const aule_attn_rope* r, uint32_t head_dim, FwdArgs& 
 
 static int32_t forward_impl(const aule_attn_desc* d, const aule_attn_rope* rope) {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_init) {
-        set_error("Library not initialized. Call aule_init() first.");
-        return -1;
-    }
-    if (d == nullptr || d->struct_size != sizeof(aule_attn_desc)) {
-        set_error("Attention failed: bad descriptor (struct_size mismatch)");
+    if (!initialised()) return -1;
+    Reason text;
+    const char* why = attn_desc_error(d, sizeof(aule_attn_desc), text);
+    if (why == nullptr && attn_too_large(d)) why = "problem too large";
+    if (why != nullptr) {
+        set_error("Attention failed: %s", why);
         return -3;
     }
-    int rc = check_common(d->dtype, d->batch, d->heads_q, d->heads_kv, d->seq_q, d->seq_k, d->head_dim,
-                          d->window_size, d->causal);
-    if (rc) return rc;
-    if ((uint64_t)d->batch * d->heads_q * d->seq_q == 0) return 0;  // empty output
+    if (fwd_nothing_to_do(d)) return 0;
     if (d->seq_k == 0) {
         set_error("Attention failed: empty key sequence");
         return -3;
@@ -809,7 +825,7 @@ static int32_t forward_impl(const aule_attn_desc* d, const aule_attn_rope* rope)
         return -3;
     }
     DeviceGuard g(d->device);
-    rc = ensure_configured();
+    int rc = ensure_configured();
     if (rc) return rc;
     FwdArgs a;
     fill_fwd_args(d, a);
@@ -844,11 +860,9 @@ int32_t aule_attention_forward_rope_ex(const aule_attn_desc* d, const aule_attn_
 }
 
 int32_t aule_attention_forward_rope_fusable(const aule_attn_desc* d, const aule_attn_rope* rope) {
-    if (d == nullptr || d->struct_size != sizeof(aule_attn_desc) || rope == nullptr) return 0;
-    if (d->dtype < 0 || d->dtype > 2 || d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return 0;
-    if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT || (d->causal == AULE_CAUSAL_BOTTOM_RIGHT && d->seq_k < d->seq_q)) return 0;
-    if ((uint64_t)d->batch * d->heads_q * d->seq_q == 0 || d->seq_k == 0) return 0;
-    if (d->batch >= (1u << 24) || d->heads_q >= (1u << 24) || d->seq_q >= (1u << 30) || d->seq_k >= (1u << 30)) return 0;
+    Reason text;
+    if (rope == nullptr || attn_desc_error(d, sizeof(aule_attn_desc), text)) return 0;
+    if (fwd_nothing_to_do(d) || d->seq_k == 0 || rope_fusable_too_large(d)) return 0;
     FwdArgs a;
     fill_fwd_args(d, a);
     return fill_rope_args(rope, d->head_dim, a) && aule_hip::fwd_rope_fusable(a) ? 1 : 0;
@@ -858,17 +872,19 @@ int32_t aule_attention_forward_rope_fusable(const aule_attn_desc* d, const aule_
 // layout asserts at the top of this file), so both kinds are checked and read through the common prefix.
 static const aule_paged_desc* paged_prefix(const aule_paged_fp8_desc* d) { return reinterpret_cast<const aule_paged_desc*>(d); }
 
-// 0 fine, 1 descriptor, 2 dtype, 3 head_dim, 4 head ratio, 5 block_size / max_blocks
-static int paged_shape_error(const aule_paged_desc* d, bool fp8) {
-    if (d == nullptr || d->struct_size != (fp8 ? sizeof(aule_paged_fp8_desc) : sizeof(aule_paged_desc))) return 1;
-    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return 2;
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return 3;
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return 4;
-    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return 5;
-    return 0;
+static const char* paged_desc_error(const aule_paged_desc* d, bool fp8, Reason& why) {
+    if (d == nullptr || d->struct_size != (fp8 ? sizeof(aule_paged_fp8_desc) : sizeof(aule_paged_desc))) return kBadDescriptor;
+    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return fp8 ? "dtype (of q / out) must be fp16 or bf16" : "dtype must be fp16 or bf16";
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return reasonf(why, "head_dim %u unsupported (32, 64 or 128)", d->head_dim);
+    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0)
+        return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
+    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return "bad block_size / max_blocks";
+    return nullptr;
 }
 
-// (`d` passed paged_shape_error: an FP8 descriptor really is one)
+static bool paged_nothing_to_do(const aule_paged_desc* d) { return (uint64_t)d->batch * d->heads_q == 0; }
+
+// (`d` passed paged_desc_error: an FP8 descriptor really is one)
 static void fill_paged_args(const aule_paged_desc* d, bool fp8, aule_hip::PagedArgs& a) {
     a.q = d->q; a.k_cache = d->k_cache; a.v_cache = d->v_cache; a.out = d->out;
     a.block_tables = d->block_tables; a.context_lens = d->context_lens;
@@ -888,19 +904,13 @@ static void fill_paged_args(const aule_paged_desc* d, bool fp8, aule_hip::PagedA
 static int32_t paged_decode_impl(const aule_paged_desc* d, bool fp8) {
     const char* const what = fp8 ? "Paged FP8 attention" : "Paged attention";
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_init) {
-        set_error("Library not initialized. Call aule_init() first.");
-        return -1;
-    }
-    if (const int bad = paged_shape_error(d, fp8)) {
-        if (bad == 1) set_error("%s failed: bad descriptor (struct_size mismatch)", what);
-        else if (bad == 2) set_error("%s failed: dtype%s must be fp16 or bf16", what, fp8 ? " (of q / out)" : "");
-        else if (bad == 3) set_error("%s failed: head_dim %u unsupported (32, 64 or 128)", what, d->head_dim);
-        else if (bad == 4) set_error("%s failed: heads_q (%u) must be divisible by heads_kv (%u)", what, d->heads_q, d->heads_kv);
-        else set_error("%s failed: bad block_size / max_blocks", what);
+    if (!initialised()) return -1;
+    Reason text;
+    if (const char* why = paged_desc_error(d, fp8, text)) {
+        set_error("%s failed: %s", what, why);
         return -3;
     }
-    if ((uint64_t)d->batch * d->heads_q == 0) return 0;
+    if (paged_nothing_to_do(d)) return 0;
     if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->out) {
         set_error("%s failed: null tensor pointer", what);
         return -3;
@@ -932,38 +942,30 @@ int32_t aule_attention_paged_decode_fp8_ex(const aule_paged_fp8_desc* d) {
     return paged_decode_impl(paged_prefix(d), true);
 }
 
+static const char* rope_desc_error(const aule_rope_desc* d, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_rope_desc)) return kBadDescriptor;
+    if (d->dtype < 0 || d->dtype > 2) return reasonf(why, "unknown dtype %d", d->dtype);
+    if (d->head_dim == 0 || (d->head_dim & 1) || d->row_pitch < d->head_dim)
+        return reasonf(why, "head_dim (%u) must be even and <= row_pitch (%u)", d->head_dim, d->row_pitch);
+    if (d->layout != AULE_ROPE_HALF && d->layout != AULE_ROPE_INTERLEAVED) return reasonf(why, "unknown layout %d", d->layout);
+    if ((uint64_t)d->seq + d->pos_offset > d->table_len)
+        return reasonf(why, "table too short (%u rows < seq %u + pos_offset %u)", d->table_len, d->seq, d->pos_offset);
+    if (d->table_pitch != 0 && d->table_pitch < d->head_dim / 2) return reasonf(why, "table_pitch (%u) < head_dim/2", d->table_pitch);
+    return nullptr;
+}
+
+static bool rope_nothing_to_do(const aule_rope_desc* d) { return d->rows_bh == 0 || d->seq == 0; }
+
 int32_t aule_rope_ex(const aule_rope_desc* d) {
     RoctxRange range("aule.rope");
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_init) {
-        set_error("Library not initialized. Call aule_init() first.");
-        return -1;
-    }
-    if (d == nullptr || d->struct_size != sizeof(aule_rope_desc)) {
-        set_error("RoPE failed: bad descriptor (struct_size mismatch)");
+    if (!initialised()) return -1;
+    Reason text;
+    if (const char* why = rope_desc_error(d, text)) {
+        set_error("RoPE failed: %s", why);
         return -3;
     }
-    if (d->dtype < 0 || d->dtype > 2) {
-        set_error("RoPE failed: unknown dtype %d", d->dtype);
-        return -3;
-    }
-    if (d->head_dim == 0 || (d->head_dim & 1) || d->row_pitch < d->head_dim) {
-        set_error("RoPE failed: head_dim (%u) must be even and <= row_pitch (%u)", d->head_dim, d->row_pitch);
-        return -3;
-    }
-    if (d->layout != AULE_ROPE_HALF && d->layout != AULE_ROPE_INTERLEAVED) {
-        set_error("RoPE failed: unknown layout %d", d->layout);
-        return -3;
-    }
-    if ((uint64_t)d->seq + d->pos_offset > d->table_len) {
-        set_error("RoPE failed: table too short (%u rows < seq %u + pos_offset %u)", d->table_len, d->seq, d->pos_offset);
-        return -3;
-    }
-    if (d->table_pitch != 0 && d->table_pitch < d->head_dim / 2) {
-        set_error("RoPE failed: table_pitch (%u) < head_dim/2", d->table_pitch);
-        return -3;
-    }
-    if (d->rows_bh == 0 || d->seq == 0) return 0;
+    if (rope_nothing_to_do(d)) return 0;
     if (d->rows_bh * d->seq >= (1ull << 40) || d->seq >= (1u << 30)) {
         set_error("RoPE failed: problem too large");
         return -3;
@@ -986,9 +988,12 @@ int32_t aule_rope_ex(const aule_rope_desc* d) {
     return 0;
 }
 
-// 0 fine, else the reason the descriptor is refused (host logic only: no pointer is dereferenced)
+static bool kv_append_nothing_to_do(const aule_kv_append_desc* d) { return d->num_tokens == 0; }
+
+// 0 fine, else the reason the descriptor is refused (host logic only: no pointer is dereferenced; its only reader is the launch
+// entry, so the pointer rules of a call that has something to do are stated here too)
 static const char* kv_append_error(const aule_kv_append_desc* d) {
-    if (d == nullptr || d->struct_size != sizeof(aule_kv_append_desc)) return "bad descriptor (struct_size mismatch)";
+    if (d == nullptr || d->struct_size != sizeof(aule_kv_append_desc)) return kBadDescriptor;
     if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return "dtype (of key / value) must be fp16 or bf16";
     if (d->cache_dtype != AULE_KV_CACHE_SAME && d->cache_dtype != AULE_KV_CACHE_FP8_E4M3)
         return "cache_dtype must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3";
@@ -1008,7 +1013,7 @@ static const char* kv_append_error(const aule_kv_append_desc* d) {
         if (d->table_pitch != 0 && (d->table_pitch < d->head_dim / 2 || d->table_pitch % 4 != 0))
             return "table_pitch must be 0 or a multiple of 4 that is >= head_dim/2";
     }
-    if (d->num_tokens == 0) return nullptr;
+    if (kv_append_nothing_to_do(d)) return nullptr;
     if (!d->key || !d->value || !d->k_cache || !d->v_cache || !d->slot_mapping) return "null tensor pointer";
     const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
     if (fp8 && (!d->k_scale || !d->v_scale)) return "null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)";
@@ -1022,15 +1027,12 @@ static const char* kv_append_error(const aule_kv_append_desc* d) {
 int32_t aule_kv_cache_append_ex(const aule_kv_append_desc* d) {
     RoctxRange range("aule.kv_cache_append");
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_init) {
-        set_error("Library not initialized. Call aule_init() first.");
-        return -1;
-    }
+    if (!initialised()) return -1;
     if (const char* why = kv_append_error(d)) {
         set_error("KV cache append failed: %s", why);
         return -3;
     }
-    if (d->num_tokens == 0) return 0;
+    if (kv_append_nothing_to_do(d)) return 0;
     aule_hip::KvAppendArgs a;
     a.key = d->key; a.value = d->value; a.k_cache = d->k_cache; a.v_cache = d->v_cache;
     a.slot_mapping = reinterpret_cast<const long long*>(d->slot_mapping);
@@ -1055,7 +1057,8 @@ int32_t aule_kv_cache_append_ex(const aule_kv_append_desc* d) {
 }
 
 uint64_t aule_attention_backward_workspace_size(const aule_attn_bwd_desc* d) {
-    if (d == nullptr) return 0;
+    Reason text;
+    if (attn_desc_error(attn_prefix(d), sizeof(aule_attn_bwd_desc), text)) return 0;
     BwdArgs a;
     fill_bwd_args(d, a, false);
     return aule_hip::bwd_plan(a).want_bytes;
@@ -1064,19 +1067,16 @@ uint64_t aule_attention_backward_workspace_size(const aule_attn_bwd_desc* d) {
 int32_t aule_attention_backward_ex(const aule_attn_bwd_desc* d) {
     RoctxRange range("aule.backward");
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_init) {
-        set_error("Library not initialized. Call aule_init() first.");
-        return -1;
-    }
-    if (d == nullptr || d->struct_size != sizeof(aule_attn_bwd_desc)) {
-        set_error("Backward failed: bad descriptor (struct_size mismatch)");
+    if (!initialised()) return -1;
+    const aule_attn_desc* p = attn_prefix(d);
+    Reason text;
+    const char* why = attn_desc_error(p, sizeof(aule_attn_bwd_desc), text);
+    if (why == nullptr && attn_too_large(p)) why = "problem too large";
+    if (why != nullptr) {   // (the shared rules say "Attention failed" in both directions; only the struct_size text names this one)
+        set_error("%s failed: %s", why == kBadDescriptor ? "Backward" : "Attention", why);
         return -3;
     }
-    int rc = check_common(d->dtype, d->batch, d->heads_q, d->heads_kv, d->seq_q, d->seq_k, d->head_dim,
-                          d->window_size, d->causal);
-    if (rc) return rc;
-    if ((uint64_t)d->batch * d->heads_q * d->seq_q == 0 && (uint64_t)d->batch * d->heads_kv * d->seq_k == 0)
-        return 0;
+    if (bwd_nothing_to_do(p)) return 0;
     if (d->seq_k == 0 || d->seq_q == 0) {
         set_error("Backward failed: empty sequence");
         return -3;
@@ -1096,7 +1096,7 @@ int32_t aule_attention_backward_ex(const aule_attn_bwd_desc* d) {
         return -3;
     }
     DeviceGuard g(d->device);
-    rc = ensure_configured();
+    int rc = ensure_configured();
     if (rc) return rc;
     rc = aule_hip::launch_bwd(a, (hipStream_t)d->stream);
     if (rc != 0) {
@@ -1167,12 +1167,8 @@ int32_t aule_peer_copy_async(int32_t device, void* dst, const void* src, uint64_
 const char* aule_hip_build_info(void) { return "aule-hip gfx950 abi2"; }   // abi2: workspace fields in the fwd / paged descriptors
 
 uint64_t aule_attention_forward_workspace_size(const aule_attn_desc* d) {
-    if (d == nullptr || d->struct_size != sizeof(aule_attn_desc)) return 0;
-    if (d->dtype < 0 || d->dtype > 2 || d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return 0;
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0 || d->seq_k == 0) return 0;
-    if ((uint64_t)d->batch * d->heads_q * d->seq_q == 0) return 0;
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128 && d->head_dim != 256) return 0;
-    if (d->causal == AULE_CAUSAL_BOTTOM_RIGHT && d->seq_k < d->seq_q) return 0;
+    Reason text;
+    if (attn_desc_error(d, sizeof(aule_attn_desc), text) || fwd_nothing_to_do(d) || d->seq_k == 0) return 0;
     FwdArgs a;
     fill_fwd_args(d, a);
     return aule_hip::fwd_workspace_bytes(a);
@@ -1180,7 +1176,8 @@ uint64_t aule_attention_forward_workspace_size(const aule_attn_desc* d) {
 
 // (the launcher's plan: it reads the shape, none of the pointers)
 static uint64_t paged_workspace_impl(const aule_paged_desc* d, bool fp8) {
-    if (paged_shape_error(d, fp8) != 0 || (uint64_t)d->batch * d->heads_q == 0) return 0;
+    Reason text;
+    if (paged_desc_error(d, fp8, text) || paged_nothing_to_do(d)) return 0;
     aule_hip::PagedArgs a;
     fill_paged_args(d, fp8, a);
     return aule_hip::paged_workspace_bytes(a);
@@ -1200,8 +1197,10 @@ uint64_t aule_attention_paged_decode_fp8_workspace_size(const aule_paged_fp8_des
  * otherwise the ordinary kernels run and nothing is written).  Used by tools/timeline_bwd.py. */
 static int32_t backward_timeline(const aule_attn_bwd_desc* d, unsigned long long* stamps, bool dq) {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_init || d == nullptr || d->struct_size != sizeof(aule_attn_bwd_desc) || stamps == nullptr) return -1;
-    if (d->dtype != AULE_DTYPE_BF16 || (d->head_dim != 128 && !(d->head_dim == 64 && !dq)) || d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;   // (D = 64: the dK/dV timeline only)
+    if (!g_init || stamps == nullptr) return -1;
+    Reason text;
+    if (const char* why = attn_desc_error(attn_prefix(d), sizeof(aule_attn_bwd_desc), text)) return why == kBadDescriptor ? -1 : -3;
+    if (d->dtype != AULE_DTYPE_BF16 || (d->head_dim != 128 && !(d->head_dim == 64 && !dq))) return -3;   // the instrumented instances (D = 64: the dK/dV timeline only)
     BwdArgs a;
     fill_bwd_args(d, a, true);
     if (dq) a.dbg_dq = stamps; else a.dbg = stamps;
@@ -1219,13 +1218,16 @@ int32_t aule_hip_debug_backward_timeline_dq(const aule_attn_bwd_desc* d, unsigne
 /* Debug hook (not part of the drop-in ABI): the forward kernel aule_attention_forward_ex would launch for `d`
  * -- the codes of fwd_route() (fa_kernels.h; include/aule.h lists them); -3 for a bad descriptor.  Pure host logic: no
  * device, no aule_init() needed.  Used by the tests to pin which kernel a shape exercises. */
-int32_t aule_hip_debug_forward_route(const aule_attn_desc* d) {
-    if (d == nullptr || d->struct_size != sizeof(aule_attn_desc)) return -3;
-    if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return -3;
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;
-    FwdArgs a;
+static bool plan_hook_args(const aule_attn_desc* d, FwdArgs& a) {   // (the three forward plan hooks)
+    Reason text;
+    if (attn_desc_error(d, sizeof(aule_attn_desc), text, /*plan_hook=*/true)) return false;
     fill_fwd_args(d, a);   // (the sign of the scale picks the kernel: negative scales stay off route 8)
-    return aule_hip::fwd_route(a);
+    return true;
+}
+
+int32_t aule_hip_debug_forward_route(const aule_attn_desc* d) {
+    FwdArgs a;
+    return plan_hook_args(d, a) ? aule_hip::fwd_route(a) : -3;
 }
 
 /* Debug hook: the route of the most recent forward launch of this process (0 before the first): what ran, where
@@ -1235,12 +1237,8 @@ int32_t aule_hip_debug_last_forward_route(void) { return aule_hip::fwd_last_rout
 /* Debug hook: the whole launch plan of aule_attention_forward_ex(d) as integers (include/aule.h lists them); the contract of
  * aule_hip_debug_forward_split_plan.  Pure host logic like the route hook. */
 int32_t aule_hip_debug_forward_plan(const aule_attn_desc* d, int32_t* out, int32_t cap) {
-    if (d == nullptr || d->struct_size != sizeof(aule_attn_desc)) return -3;
-    if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return -3;
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;
     FwdArgs a;
-    fill_fwd_args(d, a);
-    return aule_hip::fwd_plan_dump(a, out, cap);
+    return plan_hook_args(d, a) ? aule_hip::fwd_plan_dump(a, out, cap) : -3;
 }
 
 /* Debug hook: what the most recent backward launch of this process ran (bit mask, include/aule.h). */
@@ -1249,10 +1247,9 @@ int32_t aule_hip_debug_last_backward_route(void) { return aule_hip::bwd_last_rou
 /* Debug hook: the same mask for the call aule_attention_backward_ex(d) would make with d->workspace_bytes bytes of workspace; -3 for a
  * descriptor it would refuse on shape grounds.  Pure host logic like the forward hook: the plan of the launch, not a launch. */
 int32_t aule_hip_debug_backward_route(const aule_attn_bwd_desc* d) {
-    if (d == nullptr || d->struct_size != sizeof(aule_attn_bwd_desc)) return -3;
-    if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT || (d->causal == AULE_CAUSAL_BOTTOM_RIGHT && d->seq_k < d->seq_q)) return -3;
-    if (d->dtype < 0 || d->dtype > 2 || d->heads_kv == 0 || d->heads_q % d->heads_kv != 0 || (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128 && d->head_dim != 256)) return -3;
-    if ((uint64_t)d->batch * d->heads_q * d->seq_q == 0 && (uint64_t)d->batch * d->heads_kv * d->seq_k == 0) return 0;   // (nothing runs)
+    Reason text;
+    if (attn_desc_error(attn_prefix(d), sizeof(aule_attn_bwd_desc), text)) return -3;
+    if (bwd_nothing_to_do(attn_prefix(d))) return 0;   // (nothing runs)
     if (d->seq_k == 0 || d->seq_q == 0) return -3;
     BwdArgs a;
     fill_bwd_args(d, a, true);
@@ -1261,12 +1258,8 @@ int32_t aule_hip_debug_backward_route(const aule_attn_bwd_desc* d) {
 }
 
 int32_t aule_hip_debug_forward_split_plan(const aule_attn_desc* d, int32_t* out, int32_t cap) {
-    if (d == nullptr || d->struct_size != sizeof(aule_attn_desc)) return -3;
-    if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return -3;
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;
     FwdArgs a;
-    fill_fwd_args(d, a);
-    return aule_hip::fwd_split_plan_dump(a, out, cap);   // (0 unless the plan's route is 7)
+    return plan_hook_args(d, a) ? aule_hip::fwd_split_plan_dump(a, out, cap) : -3;   // (0 unless the plan's route is 7)
 }
 
 int32_t aule_hip_debug_work_order(int32_t ranked, int32_t bid, int32_t batch, int32_t heads_q, int32_t heads_kv, int32_t nblk, int32_t flag, int32_t* out4) {
@@ -1284,8 +1277,10 @@ int32_t aule_hip_debug_work_order(int32_t ranked, int32_t bid, int32_t batch, in
  * Used by tools/timeline.py / tools/timeline_w4.py. */
 int32_t aule_hip_debug_forward_timeline(const aule_attn_desc* d, unsigned long long* stamps) {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_init || d == nullptr || d->struct_size != sizeof(aule_attn_desc) || stamps == nullptr) return -1;
-    if (d->dtype != AULE_DTYPE_BF16 || (d->head_dim != 128 && d->head_dim != 64) || d->heads_kv == 0 || d->heads_q % d->heads_kv != 0) return -3;
+    if (!g_init || stamps == nullptr) return -1;
+    Reason text;
+    if (const char* why = attn_desc_error(d, sizeof(aule_attn_desc), text)) return why == kBadDescriptor ? -1 : -3;
+    if (d->dtype != AULE_DTYPE_BF16 || (d->head_dim != 128 && d->head_dim != 64)) return -3;   // the instrumented instances
     FwdArgs a;
     fill_fwd_args(d, a);
     if (const char* e = getenv("AULE_TL")) {

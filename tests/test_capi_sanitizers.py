@@ -127,6 +127,22 @@ for dt, B, hq, hkv, sq, sk, D, c, w in bwd_sweep.cases():
         assert r == -3 if ws == 0 else 0 < r < 256, (dt, B, hq, hkv, sq, sk, D, c, w, ws, r)
         broutes.add(r)
 assert {-3, 5, 6, 24, 32, 70, 128, 160} <= broutes, sorted(broutes)
+# --- every host-only entry over tests/desc_sweep.py: valid bases with one bad or edge field each -- the descriptors the launch refuses
+# (unknown dtype, head_dim 0 / 48 / 512, heads_kv 0, wrong struct_size, ...) get an answer from the checker, never a trap
+import tempfile
+import numpy as np
+import desc_sweep
+with tempfile.TemporaryDirectory() as tmp:
+    desc_sweep.ask_library(os.path.join(tmp, "san.npz"))
+    with np.load(os.path.join(tmp, "san.npz")) as z:
+        fwd, bwd = z["fwd"], z["bwd"]
+refused = 0
+for k, (i, name, fields) in enumerate(desc_sweep.attn_cases()):
+    if name in ("struct_size", "dtype", "head_dim", "heads_kv", "causal"):
+        assert fwd[k][desc_sweep.ROUTE] == fwd[k][desc_sweep.PLAN_RET] == fwd[k][desc_sweep.SPLIT_RET] == -3, (name, fields, fwd[k])
+        assert fwd[k][desc_sweep.FWD_WS] == fwd[k][desc_sweep.FUSABLE] == 0 and list(bwd[k]) == [0, -3, -3], (name, fields, fwd[k], bwd[k])
+        refused += 1
+assert refused == 11 * len(desc_sweep.ATTN_BASES)
 print("SANITIZED-OK", n, sorted(routes.items()))
 '''
 

@@ -539,3 +539,68 @@ def test_forward_plan_hook_refuses_bad_descriptors():
         assert lib.aule_hip_debug_forward_plan(ctypes.byref(d), buf, 16) == -3, field
         setattr(d, field, keep)
     assert lib.aule_hip_debug_forward_plan(ctypes.byref(d), buf, 16) == 9
+
+
+def test_descriptor_contract_matches_the_recorded_table():
+    """Every host-only entry point over tests/desc_sweep.py -- valid base descriptors, each with one field set to a bad or edge value --
+    value for value against tests/golden/capi_desc_contract.npz, recorded from the library as it was before aule_capi.cpp checked each
+    descriptor kind in one place.  The only differences are the descriptors the launch refuses and an entry used to answer for anyway,
+    named here by mutated field and entry point (never by asking the library), each with what the recorded library said and what is
+    required now:
+      * aule_hip_debug_forward_route / _forward_plan / _forward_split_plan, dtype outside 0..2 or head_dim outside {32, 64, 128, 256}: they
+        planned it (a route >= 0, three or more plan ints, split plan 0); now -3.  (Bottom-right with seq_k < seq_q is NOT among them: the
+        sweep of tests/test_capi_sanitizers.py pins that the three hooks answer there, so they still do and the table holds.)
+      * aule_attention_backward_workspace_size, struct_size / dtype / head_dim / heads_kv / causal code / bottom-right with seq_k < seq_q:
+        it planned from the raw fields (the base's size for a wrong struct_size); now 0.  seq_k = 0 on a bottom-right base states that last
+        descriptor too (seq_k < seq_q under causal code 2) and counts as one: told from the base's causal code, two bases have it.
+      * aule_attention_forward_rope_fusable, head_dim outside the set: it reached the plan, which said 0; now 0 from the checker.
+    TRAPPED entries: the recorded library died there of an integer division (forward hooks, the GQA decode base with seq_k = 0, which the
+    launch refuses); the sweep does not ask them."""
+    import numpy as np
+    import desc_sweep as ds
+    gold = np.load(ds.FIXTURE)
+    got = ds.run()
+    cases = ds.attn_cases()
+    assert len(cases) == len(ds.ATTN_BASES) * 22 == gold["fwd"].shape[0] == gold["bwd"].shape[0] and len(ds.paged_cases()) == gold["paged"].size
+    # the table is not trivial: every valid base runs, and the bases see the routes and backward kernels between them
+    base_rows = [n for n, (_, name, _) in enumerate(cases) if name == "none"]
+    routes = {int(gold["fwd"][n][ds.ROUTE]) for n in base_rows}
+    masks = [int(gold["bwd"][n][ds.BWD_ROUTE_BIG]) for n in base_rows]
+    assert min(routes) >= 0 and {0, 1, 7, 8, 9} <= routes and routes & {4, 5}, routes
+    assert min(masks) > 0 and all(any(m & bit for m in masks) for bit in (2, 4, 8 | 16, 32, 128)), masks
+    assert all(gold["bwd"][n][ds.BWD_WS] > 0 and gold["bwd"][n][ds.BWD_ROUTE_0] == -3 for n in base_rows)
+    assert sum(int(gold["fwd"][n][ds.FUSABLE]) for n in base_rows) >= 2 and (gold["paged"] > 0).sum() >= 4 * 7
+    assert int((gold["fwd"] == ds.TRAPPED).sum()) == 3 and not (gold["bwd"] == ds.TRAPPED).any() and not (gold["paged"] == ds.TRAPPED).any()
+    # the excepted cells, from the sweep's definition alone: (table, row, column) -> required value
+    HOOK_FIELDS = ("dtype", "head_dim")
+    BWD_WS_FIELDS = ("struct_size", "dtype", "head_dim", "heads_kv", "causal", "bottom_right")
+    now = {}
+    for n, (i, name, _) in enumerate(cases):
+        if name == "seq_k" and ds.ATTN_BASES[i][ds.ATTN_FIELDS.index("causal")] == 2:
+            name = "bottom_right"
+        if name in HOOK_FIELDS:
+            g = gold["fwd"][n]
+            assert g[ds.ROUTE] >= 0 and g[ds.PLAN_RET] >= 3 and g[ds.PLAN0] == g[ds.ROUTE] and g[ds.SPLIT_RET] == 0, (cases[n], g)   # it planned them
+            for col in (ds.ROUTE, ds.PLAN_RET, ds.SPLIT_RET):
+                now["fwd", n, col] = -3
+            for col in range(ds.PLAN0, ds.PLAN0 + ds.PLAN_CAP):
+                now["fwd", n, col] = 0                       # ... and nothing is written
+        if name == "head_dim":
+            assert gold["fwd"][n][ds.FUSABLE] == 0
+            now["fwd", n, ds.FUSABLE] = 0
+        if name in BWD_WS_FIELDS:
+            assert gold["bwd"][n][ds.BWD_WS] >= 0 and (name != "struct_size" or gold["bwd"][n][ds.BWD_WS] == gold["bwd"][n - n % 22][ds.BWD_WS])
+            now["bwd", n, ds.BWD_WS] = 0
+    per_base = {name: sum(1 for _, m, _ in cases[:22] if m == name) for name in HOOK_FIELDS + BWD_WS_FIELDS}
+    assert per_base == {"struct_size": 2, "dtype": 2, "head_dim": 3, "heads_kv": 2, "causal": 2, "bottom_right": 1}
+    br_bases = sum(1 for b in ds.ATTN_BASES if b[ds.ATTN_FIELDS.index("causal")] == 2)
+    assert br_bases == 2 and len(now) == len(ds.ATTN_BASES) * ((2 + 3) * (3 + ds.PLAN_CAP) + 3 + (2 + 2 + 3 + 2 + 2 + 1)) + br_bases
+    for k in ("fwd", "bwd"):
+        want = gold[k].copy()
+        for (table, n, col), v in now.items():
+            if table == k:
+                want[n][col] = v
+        bad = np.argwhere(got[k] != want)
+        assert got[k].shape == want.shape and bad.size == 0, (k, len(bad), [(cases[n], int(col), int(got[k][n][col]), int(want[n][col])) for n, col in bad[:8]])
+    for k in ("split", "split_off", "paged"):
+        assert np.array_equal(got[k], gold[k]), (k, np.nonzero(got[k] != gold[k])[0][:8] if got[k].shape == gold[k].shape else got[k].shape)
