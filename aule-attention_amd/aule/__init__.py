@@ -150,6 +150,32 @@ def flash_attention_paged_amd(q, k_cache, v_cache, block_tables, context_lens, s
                         k_scale=k_scale, v_scale=v_scale)
 
 
+def flash_attention_paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1,
+                                k_scale=None, v_scale=None, return_lse=False):
+    """PagedAttention for a short multi-token query per sequence: the step that adds more than one token (verifying the
+    k + 1 draft tokens of speculative decoding, multi-token prediction heads, a short prompt tail against a cached prefix).
+    Not in the reference; flash_attention_paged_amd keeps its one-token rule.
+
+        q [batch, heads_q, seq_q, head_dim] fp16 / bf16 with 1 <= seq_q <= 64, the same for every sequence;
+        k_cache, v_cache, block_tables, k_scale, v_scale as in flash_attention_paged_amd (16-bit or float8_e4m3fn caches);
+        context_lens [batch]: the keys in the cache INCLUDING the seq_q new tokens -- append them first (paged_kv_append).
+
+    Query i of sequence b sits at position p = context_lens[b] - seq_q + i and sees key j iff j <= p, and with
+    window_size = W > 0 iff also p - j < W: the rule of flash_attention(causal="bottom-right") on the gathered K / V.  A
+    query at a negative position (a sequence shorter than seq_q) gives a row of zeros.  Returns [batch, heads_q, seq_q,
+    head_dim], or (out, lse) with return_lse=True: lse [batch, heads_q, seq_q] fp32, the natural log of the sum of
+    exp(scaled score) over the visible keys (-inf where there is none).  seq_q = 1 equals flash_attention_paged_amd bit for
+    bit.  Out of scope: seq_q > 64, per-sequence query lengths, head_dim 256.  Argument errors are ValueErrors raised before
+    the device is touched; CPU tensors raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_query
+    return paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=scale, window_size=window_size,
+                       k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
+
+
 def quantize_kv_cache_fp8(cache, per_head=True):
     """(cache_fp8, scale) for the FP8 paged decode: float8_e4m3fn codes and a [heads_kv] fp32 scale = amax / 448 per KV
     head (per_head=False: one value, repeated), saturating.  Plain torch ops; works on CPU tensors."""
@@ -377,7 +403,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

@@ -113,6 +113,15 @@ class PagedFp8Desc(ctypes.Structure):
     ]
 
 
+class PagedQueryDesc(ctypes.Structure):
+    """struct aule_paged_query_desc (include/aule.h): aule_paged_fp8_desc plus lse, seq_q and cache_dtype."""
+    _fields_ = list(PagedFp8Desc._fields_) + [
+        ("lse", ctypes.c_void_p),
+        ("seq_q", ctypes.c_uint32),
+        ("cache_dtype", ctypes.c_int32),
+    ]
+
+
 class RopeDesc(ctypes.Structure):
     """struct aule_rope_desc (include/aule.h)."""
     _fields_ = [
@@ -239,6 +248,8 @@ SIGNATURES = [
     ("aule_attention_paged_decode_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedDesc)]),
     ("aule_attention_paged_decode_fp8_ex", _I32, [ctypes.POINTER(PagedFp8Desc)]),
     ("aule_attention_paged_decode_fp8_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedFp8Desc)]),
+    ("aule_attention_paged_query_ex", _I32, [ctypes.POINTER(PagedQueryDesc)]),
+    ("aule_attention_paged_query_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedQueryDesc)]),
     ("aule_peer_alloc", _I32, [_I32, _U64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(IpcHandle)]),
     ("aule_peer_free", _I32, [_I32, ctypes.c_void_p]),
     ("aule_peer_open", _I32, [_I32, ctypes.POINTER(IpcHandle), ctypes.POINTER(ctypes.c_void_p)]),

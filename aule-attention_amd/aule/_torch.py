@@ -402,12 +402,13 @@ def _fp8_scale(s, Hkv, device, name):
 
 
 def _paged_cache_is_fp8(op, inputs, k_cache, v_cache, k_scale, v_scale):
-    """The cache-kind rules paged_decode and paged_kv_append share -- caches of one dtype, torch.float8_e4m3fn the only FP8 encoding,
+    """The cache-kind rules paged_decode, paged_query and paged_kv_append share -- caches of one dtype, torch.float8_e4m3fn the only FP8 encoding,
     fp16 / bf16 inputs (and 16-bit caches) of one dtype, scales with FP8 caches only, head_dim in PAGED_HEAD_DIMS -- as ValueErrors
     in that operation's words.  inputs: (q,) or (key, value).  Returns whether the caches are FP8."""
     name, fp8_use, same, with_fp8, dims_of = {
         "decode": ("paged decode", "the FP8 paged decode takes", "query and caches", "an fp16 / bf16 query", "paged decode"),
         "append": ("paged KV append", "the paged KV append writes", "key, value and caches", "fp16 / bf16 key and value", "the paged KV cache"),
+        "query": ("paged query", "the FP8 paged query takes", "query and caches", "an fp16 / bf16 query", "the paged query"),
     }[op]
     if k_cache.dtype != v_cache.dtype:
         raise ValueError(f"k_cache ({k_cache.dtype}) and v_cache ({v_cache.dtype}) must have the same dtype")
@@ -492,6 +493,80 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, wi
     else:
         _capi.check(lib.aule_attention_paged_decode_ex(ctypes.byref(d)), "aule_attention_paged_decode_ex")
     return out
+
+
+PAGED_QUERY_MAX_TOKENS = 64   # packed rows of the wave-per-chunk kernel family (csrc/fa_fwd_splitkv_gfx950.hip)
+
+
+def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1, k_scale=None, v_scale=None,
+                return_lse=False):
+    """Paged attention for a short multi-token query per sequence (speculative verify, multi-token heads, a short prompt
+    tail against a cached prefix); the MQ instances of csrc/fa_fwd_splitkv_gfx950.hip behind aule_attention_paged_query_ex:
+
+        q            [batch, heads_q, seq_q, head_dim] fp16 / bf16, 1 <= seq_q <= 64
+        k_cache, v_cache, block_tables, context_lens, k_scale, v_scale: as in paged_decode (16-bit or float8_e4m3fn caches)
+    context_lens[b] counts the keys in the cache INCLUDING the seq_q new tokens (append them first: paged_kv_append).  Query
+    i of sequence b sits at position p = L_b - seq_q + i (L_b: the length, clamped to what the block table addresses) and
+    sees key j iff j <= p, and with window_size = W > 0 iff also p - j < W.  A query with p < 0 gives a row of zeros.
+    Returns out [batch, heads_q, seq_q, head_dim], or (out, lse) with lse [batch, heads_q, seq_q] fp32 -- the natural log
+    of the sum of exp(scaled score) over the visible keys, -inf for a row that sees none -- when return_lse is set.  No
+    device->host synchronisation; captures into a graph.  All argument errors are ValueErrors raised before the device is
+    touched."""
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError("expected q [B,Hq,Sq,D] and k_cache/v_cache [num_blocks, block_size, Hkv, D]")
+    B, Hq, Sq, D = q.shape
+    _, block_size, Hkv, Dk = k_cache.shape
+    if Dk != D:
+        raise ValueError(f"head_dim mismatch: query={D}, cache={Dk}")
+    if Hkv == 0 or Hq % Hkv != 0:
+        raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
+    if not 1 <= Sq <= PAGED_QUERY_MAX_TOKENS:
+        raise ValueError(f"the paged query takes 1 to {PAGED_QUERY_MAX_TOKENS} query tokens per sequence, got {Sq} "
+                         "(longer chunks: gather the pages and call flash_attention(causal='bottom-right'))")
+    fp8 = _paged_cache_is_fp8("query", (q,), k_cache, v_cache, k_scale, v_scale)
+    if block_size == 0:
+        raise ValueError("block_size must be positive")
+    if block_tables.dim() != 2 or block_tables.shape[0] != B or block_tables.shape[1] == 0 or context_lens.shape != (B,):
+        raise ValueError("block_tables must be [batch, max_blocks] and context_lens [batch]")
+    if fp8:
+        for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if torch.is_tensor(s) and not (s.dim() == 0 or s.shape == (1,) or s.shape == (Hkv,)):
+                raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): the paged query needs ROCm device tensors; there is no CPU fallback")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    lib = _capi.get_lib()
+    q, k_cache, v_cache = q.contiguous(), k_cache.contiguous(), v_cache.contiguous()
+    _same_device("paged query", q, k_cache, v_cache)
+    bt = block_tables.to(device=q.device, dtype=torch.int32).contiguous()
+    cl = context_lens.to(device=q.device, dtype=torch.int32).contiguous()
+    out = torch.empty_like(q)
+    lse = torch.empty((B, Hq, Sq), device=q.device, dtype=torch.float32) if return_lse else None
+    if B * Hq == 0:
+        return (out, lse) if return_lse else out
+    d = _capi.PagedQueryDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    d.batch, d.heads_q, d.heads_kv, d.head_dim, d.seq_q = B, Hq, Hkv, D, Sq
+    d.block_size, d.max_blocks = block_size, bt.shape[1]
+    d.scale = _abi_scale(scale)
+    d.window_size = _window_arg(window_size)
+    d.device = _device_index(q.device)
+    d.stream = _stream_ptr(q.device)
+    d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
+    d.lse = lse.data_ptr() if lse is not None else None
+    ws = _workspace(lib.aule_attention_paged_query_workspace_size(ctypes.byref(d)), q.device)
+    if ws is not None:
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    d.block_tables, d.context_lens = bt.data_ptr(), cl.data_ptr()
+    if fp8:
+        ks = _fp8_scale(k_scale, Hkv, q.device, "k_scale")
+        vs = _fp8_scale(v_scale, Hkv, q.device, "v_scale")
+        d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
+    _capi.check(lib.aule_attention_paged_query_ex(ctypes.byref(d)), "aule_attention_paged_query_ex")
+    return (out, lse) if return_lse else out
 
 
 def paged_slot_mapping(block_tables, positions, block_size, seq_ids=None):

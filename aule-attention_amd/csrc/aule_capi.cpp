@@ -39,6 +39,16 @@ static_assert(offsetof(aule_paged_fp8_desc, q) == offsetof(aule_paged_desc, q) &
                   offsetof(aule_paged_fp8_desc, workspace_bytes) == offsetof(aule_paged_desc, workspace_bytes) &&
                   offsetof(aule_paged_fp8_desc, k_scale) == sizeof(aule_paged_desc),
               "aule_paged_fp8_desc starts with aule_paged_desc (the paged entry points read both through that prefix)");
+static_assert(sizeof(aule_paged_query_desc) == 152 && offsetof(aule_paged_query_desc, stream) == 48 &&
+                  offsetof(aule_paged_query_desc, workspace) == 104 && offsetof(aule_paged_query_desc, k_scale) == 120 &&
+                  offsetof(aule_paged_query_desc, v_scale) == 128 && offsetof(aule_paged_query_desc, lse) == 136 &&
+                  offsetof(aule_paged_query_desc, seq_q) == 144 && offsetof(aule_paged_query_desc, cache_dtype) == 148,
+              "aule_paged_query_desc layout is part of the ABI");
+static_assert(offsetof(aule_paged_query_desc, q) == offsetof(aule_paged_fp8_desc, q) &&
+                  offsetof(aule_paged_query_desc, workspace_bytes) == offsetof(aule_paged_fp8_desc, workspace_bytes) &&
+                  offsetof(aule_paged_query_desc, v_scale) == offsetof(aule_paged_fp8_desc, v_scale) &&
+                  offsetof(aule_paged_query_desc, lse) == sizeof(aule_paged_fp8_desc),
+              "aule_paged_query_desc starts with aule_paged_fp8_desc (its launch arguments are filled through that prefix)");
 static_assert(sizeof(aule_attn_bwd_desc) == 144, "aule_attn_bwd_desc layout is part of the ABI");
 static_assert(offsetof(aule_attn_bwd_desc, dtype) == offsetof(aule_attn_desc, dtype) && offsetof(aule_attn_bwd_desc, head_dim) == offsetof(aule_attn_desc, head_dim) &&
                   offsetof(aule_attn_bwd_desc, scale) == offsetof(aule_attn_desc, scale) && offsetof(aule_attn_bwd_desc, device) == offsetof(aule_attn_desc, device) &&
@@ -684,7 +694,8 @@ int32_t aule_attention_forward_gravity(aule_tensor_handle, aule_tensor_handle, a
 // The descriptor checkers, one per kind: pure host logic (no lock, no g_init, no pointer dereferenced).  Each answers nullptr
 // or the reason the descriptor is refused (kv_append_error further down is the model); a reason that carries values is
 // formatted into the caller's Reason.  What has nothing to do is a predicate of its own per kind; null pointers, workspace
-// sizes and the size limits of the launches are rules of the launch entries.
+// sizes and the size limits of the launches are rules of the launch entries (paged_query_desc_error states the pointer rules
+// too, for its launch entry only, as kv_append_error does).
 struct Reason { char text[128]; };
 static const char kBadDescriptor[] = "bad descriptor (struct_size mismatch)";
 
@@ -942,6 +953,59 @@ int32_t aule_attention_paged_decode_fp8_ex(const aule_paged_fp8_desc* d) {
     return paged_decode_impl(paged_prefix(d), true);
 }
 
+// The paged query: aule_paged_fp8_desc field for field, then lse, seq_q and cache_dtype (the layout asserts at the top of this
+// file).  One checker for its two readers; `launch`: the pointer rules of a call that has something to do as well (the size
+// query reads no pointer).
+static bool paged_query_nothing_to_do(const aule_paged_query_desc* d) { return (uint64_t)d->batch * d->heads_q == 0; }
+
+static const char* paged_query_desc_error(const aule_paged_query_desc* d, bool launch, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_paged_query_desc)) return kBadDescriptor;
+    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return "dtype (of q / out) must be fp16 or bf16";
+    if (d->cache_dtype != AULE_KV_CACHE_SAME && d->cache_dtype != AULE_KV_CACHE_FP8_E4M3)
+        return "cache_dtype must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3";
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return reasonf(why, "head_dim %u unsupported (32, 64 or 128)", d->head_dim);
+    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0)
+        return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
+    if (d->seq_q == 0 || d->seq_q > 64) return reasonf(why, "seq_q %u unsupported (1 to 64 query tokens per sequence)", d->seq_q);
+    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return "bad block_size / max_blocks";
+    if (!launch || paged_query_nothing_to_do(d)) return nullptr;
+    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->out) return "null tensor pointer";
+    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
+    if (fp8 && (!d->k_scale || !d->v_scale)) return "null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)";
+    if (!fp8 && (d->k_scale || d->v_scale)) return "k_scale / v_scale apply to FP8 caches only; a 16-bit cache holds the values themselves";
+    return nullptr;
+}
+
+// (`d` passed paged_query_desc_error)
+static void fill_paged_query_args(const aule_paged_query_desc* d, aule_hip::PagedArgs& a) {
+    fill_paged_args(reinterpret_cast<const aule_paged_desc*>(d), d->cache_dtype == AULE_KV_CACHE_FP8_E4M3, a);
+    a.Sq = (int)d->seq_q;
+    a.lse = d->lse;
+}
+
+int32_t aule_attention_paged_query_ex(const aule_paged_query_desc* d) {
+    RoctxRange range("aule.paged_query");
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!initialised()) return -1;
+    Reason text;
+    if (const char* why = paged_query_desc_error(d, true, text)) {
+        set_error("Paged query attention failed: %s", why);
+        return -3;
+    }
+    if (paged_query_nothing_to_do(d)) return 0;
+    aule_hip::PagedArgs a;
+    fill_paged_query_args(d, a);
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    rc = aule_hip::launch_paged_query(a, (hipStream_t)d->stream);
+    if (rc != 0) {
+        set_error("Paged query attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
+        return -4;
+    }
+    return 0;
+}
+
 static const char* rope_desc_error(const aule_rope_desc* d, Reason& why) {
     if (d == nullptr || d->struct_size != sizeof(aule_rope_desc)) return kBadDescriptor;
     if (d->dtype < 0 || d->dtype > 2) return reasonf(why, "unknown dtype %d", d->dtype);
@@ -1187,6 +1251,15 @@ uint64_t aule_attention_paged_decode_workspace_size(const aule_paged_desc* d) { 
 
 uint64_t aule_attention_paged_decode_fp8_workspace_size(const aule_paged_fp8_desc* d) {
     return paged_workspace_impl(paged_prefix(d), true);
+}
+
+// (the same plan as the launch: paged_workspace_bytes reads PagedArgs::Sq)
+uint64_t aule_attention_paged_query_workspace_size(const aule_paged_query_desc* d) {
+    Reason text;
+    if (paged_query_desc_error(d, false, text) || paged_query_nothing_to_do(d)) return 0;
+    aule_hip::PagedArgs a;
+    fill_paged_query_args(d, a);
+    return aule_hip::paged_workspace_bytes(a);
 }
 
 #ifdef AULE_DEBUG_HOOKS

@@ -24,6 +24,11 @@
 // Where the rows come from (PAGED: block table, context_lens, window) and what a row holds (Kv16 / KvFp8 below: K load
 // -> MFMA operands with the matching order of d in the Q fragments, V load -> LDS image, the two scale factors) are
 // the only per-source pieces; indexing, softmax step, PV step and the partial store are written once.
+//
+// MQ instances (fa_fwd_paged_query_kernel: both paged sources): 1 <= Sq <= 64 query tokens per sequence, the LAST Sq positions of
+// the cache (speculative verify, multi-token heads, a short prompt tail).  Query qi sits at position pos = Sk - Sq + qi and sees
+// key kv iff kv <= pos (and pos - kv < window): a per-lane limit, since a lane owns one packed row.  A row may see nothing of a
+// tile -- or nothing at all (pos < 0) -- so the softmax step keeps m = -inf, l = 0, O = 0 for it: an empty partial.
 #include <type_traits>
 
 #include "fa_device.h"
@@ -51,7 +56,7 @@ struct SplitParams {
     const int* block_tables;   // [B, max_blocks] physical block of each logical block
     const int* context_lens;   // [B] keys per sequence
     int block_size, max_blocks;
-    int window;                // > 0: only the last `window` positions (context_len - 1 - pos < window)
+    int window;                // > 0: only the last `window` positions (context_len - 1 - pos < window; MQ: query position - pos < window)
     const float* k_scale;      // [Hkv] fp32, KvFp8 only
     const float* v_scale;
 };
@@ -129,215 +134,20 @@ struct KvFp8 {
     static __device__ __forceinline__ float v_factor(const SplitParams& p, int hk) { return p.v_scale[hk]; }
 };
 
+// The body is fa_fwd_splitkv_body.inc, included by the two kernels: fa_fwd_splitkv_kernel (route 4 and the paged decode) and
+// fa_fwd_paged_query_kernel (the MQ instances, a kernel name of their own).  Text, not a shared inline function: behind a call
+// the compiler optimises the body before it knows the kernel arguments and schedules the decode instances differently; included,
+// they stay the code they were, instruction for instruction.
 template <class T, int D, class KV, bool PAGED>
 __global__ void __launch_bounds__(256) fa_fwd_splitkv_kernel(const SplitParams p) {
-    using v8 = typename T::v8;
-    constexpr int EB = KV::EB;
-    constexpr int RB = D * EB;            // bytes of a K/V row
-    constexpr int KS = D / 16, DB = D / 32;
-    constexpr int NL = RB / 32;           // 16-byte loads per lane and tile, of K (a row over the two lane halves) and of V (32 rows over 64 lanes)
-    constexpr int VT = 32 * D * 2;        // one wave's V tile in LDS (16-bit)
-    __shared__ __attribute__((aligned(16))) char smem[4 * VT];
+    constexpr bool MQ = false;
+#include "fa_fwd_splitkv_body.inc"
+}
 
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    char* const Vw = smem + wave * VT;
-
-    const int g = p.Hq / p.Hkv;
-    const int unit = blockIdx.y / p.nrt, rt = blockIdx.y % p.nrt;
-    const int b = unit / p.Hkv, hk = unit % p.Hkv;
-    const int Sq = PAGED ? 1 : p.Sq;      // paged decode: one query token per sequence
-    // paged: keys of this sequence, read on the device and bounded by what the block table can address (a stale or
-    // corrupt scheduler value must not index the table or the cache out of bounds)
-    const int Sk = PAGED ? min(max(p.context_lens[b], 0), p.max_blocks * p.block_size) : p.Sk;
-    const int row = rt * 32 + l31;                 // packed row of this lane inside the unit
-    const bool valid = row < g * Sq;
-    const int head = hk * g + (valid ? row / Sq : 0), qi = valid ? row % Sq : 0;
-
-    const size_t kvoff = PAGED ? 0 : (size_t)(b * p.Hkv + hk) * Sk * RB;
-    const __amdgpu_buffer_rsrc_t krs = skv_srd(reinterpret_cast<const char*>(p.k) + kvoff, PAGED ? 0u : (unsigned)Sk * RB);
-    const __amdgpu_buffer_rsrc_t vrs = skv_srd(reinterpret_cast<const char*>(p.v) + kvoff, PAGED ? 0u : (unsigned)Sk * RB);
-    // paged: byte address of key/value row `kv` of this unit inside the cache (64-bit: caches exceed 4 GiB)
-    const int* const bt = PAGED ? p.block_tables + (size_t)b * p.max_blocks : nullptr;
-    auto paged_row = [&](int kv) -> size_t {
-        const int lb = kv / p.block_size, off = kv - lb * p.block_size;
-        const size_t phys = (size_t)bt[min(lb, p.max_blocks - 1)];   // (tiles are rounded up: rows past Sk are masked, never out of the table)
-        return ((phys * p.block_size + off) * p.Hkv + hk) * (size_t)RB;
-    };
-
-    // Q fragments (B operand of S^T = K.Q^T): fragment ks of lane (row, hi) holds d = KV::q_d0(ks, hi) .. +7, the k order
-    // of the source's K operands; rows beyond the unit are 0
-    v8 qf[KS];
-    {
-        const char* qrow = reinterpret_cast<const char*>(p.q) + ((size_t)(b * p.Hq + head) * Sq + qi) * (D * 2);
-        const unsigned flip = (KV::kSignInQ && p.negq) ? 0x80008000u : 0u;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            u32x4_t x = {0u, 0u, 0u, 0u};
-            if (valid) x = *reinterpret_cast<const u32x4_t*>(qrow + KV::q_d0(ks, hi) * 2);
-            x[0] ^= flip; x[1] ^= flip; x[2] ^= flip; x[3] ^= flip;
-            qf[ks] = as_v8<T>(x);
-        }
-    }
-
-    // V staging map: the wave's 16-byte source chunks u = lane + 64 i fill the sub-tiled 16-bit image linearly
-    // ([kv/4][d/16][4][16 elements]: fa_fwd_pp_gfx950.hip); a sub-tile row of 16 elements is EB source chunks, and chunk
-    // u lands at byte u * 32 / EB of the image.  Transpose-read offset: fa_fwd_pp_gfx950.hip
-    int v_g[NL], v_row[NL], v_col[NL];
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-        const int u = lane + 64 * i;
-        const int bidx = u / (4 * EB);    // sub-tile index = kv4 * (D/16) + d16
-        v_row[i] = (bidx / (D / 16)) * 4 + ((u / EB) & 3);
-        v_col[i] = ((bidx % (D / 16)) * EB + u % EB) * 16;   // byte offset inside the row
-        v_g[i] = v_row[i] * RB + v_col[i];
-    }
-    const int tr_off = hi * (D / 16) * 128 + ((lane >> 4) & 1) * 128 + (lane & 15) * 8;
-    // paged fast path (power-of-two block size >= 8): block index inside the tile and byte offset inside the block
-    const bool pow2 = PAGED && p.block_size >= 8 && (p.block_size & (p.block_size - 1)) == 0;
-    const int bs_log2 = PAGED ? 31 - __builtin_clz(p.block_size | 1) : 0;
-    const size_t blk_bytes = PAGED ? (size_t)p.block_size * p.Hkv * RB : 0;
-    int k_jb = 0, k_off = 0, v_jb[NL], v_off[NL];
-#pragma unroll
-    for (int i = 0; i < NL; ++i) { v_jb[i] = 0; v_off[i] = 0; }
-    if (pow2) {
-        k_jb = l31 >> bs_log2;
-        k_off = ((l31 & (p.block_size - 1)) * p.Hkv + hk) * RB + hi * 16;
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            v_jb[i] = v_row[i] >> bs_log2;
-            v_off[i] = ((v_row[i] & (p.block_size - 1)) * p.Hkv + hk) * RB + v_col[i];
-        }
-    }
-
-    f32x16_t o[DB];
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    const float c = p.c * KV::k_factor(p, hk);   // (FP8: logits = k_scale * (q . codes) * scale, one fp32 factor per unit)
-
-    const int ntiles = (Sk + 31) / 32;
-    int t0 = (blockIdx.x * 4 + wave) * p.chunk_tiles;
-    const int t1 = min(t0 + p.chunk_tiles, ntiles);
-    if constexpr (PAGED) {
-        if (p.window > 0) t0 = max(t0, max(0, Sk - p.window) / 32);   // tiles entirely before the window
-    }
-    f32x16_t z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.f;
-
-    for (int t = t0; t < t1; ++t) {
-        const int kv0 = t * 32;
-        // lane (key l31, hi) loads the 16-byte chunks 2j + hi of its K row; V chunk i of the staging map
-        u32x4_t kx[NL], vx[NL];
-        if constexpr (PAGED) {
-            const u32x4_t zero = {0u, 0u, 0u, 0u};
-            const bool kin = kv0 + l31 < Sk;
-            if (pow2) {
-                // power-of-two block sizes >= 8 (the usual 16/32/64/128): the tile's <= 4 logical blocks are looked up
-                // ONCE per tile with wave-uniform (scalar) loads; each lane picks its block with selects and adds a
-                // 32-bit in-block offset computed once per launch -- no per-lane table lookups or 64-bit multiplies
-                const int lb0 = kv0 >> bs_log2;
-                const size_t tile_off = (size_t)(kv0 & (p.block_size - 1)) * p.Hkv * RB;   // blocks larger than a tile
-                // (four named values, not an array: the compiler turns selects over an array into an indexed read from scratch)
-                const size_t pb0 = (size_t)bt[min(lb0, p.max_blocks - 1)] * blk_bytes + tile_off;
-                const size_t pb1 = (size_t)bt[min(lb0 + 1, p.max_blocks - 1)] * blk_bytes + tile_off;
-                const size_t pb2 = (size_t)bt[min(lb0 + 2, p.max_blocks - 1)] * blk_bytes + tile_off;
-                const size_t pb3 = (size_t)bt[min(lb0 + 3, p.max_blocks - 1)] * blk_bytes + tile_off;
-                auto pick = [&](int jb) -> size_t { return jb == 0 ? pb0 : (jb == 1 ? pb1 : (jb == 2 ? pb2 : pb3)); };
-                const char* krow = reinterpret_cast<const char*>(p.k) + pick(k_jb) + k_off;
-#pragma unroll
-                for (int j = 0; j < NL; ++j) kx[j] = kin ? *reinterpret_cast<const u32x4_t*>(krow + j * 32) : zero;
-#pragma unroll
-                for (int i = 0; i < NL; ++i) {
-                    const bool vin = kv0 + v_row[i] < Sk;
-                    vx[i] = vin ? *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(p.v) + pick(v_jb[i]) + v_off[i]) : zero;
-                }
-            } else {
-                const char* krow = reinterpret_cast<const char*>(p.k) + (kin ? paged_row(kv0 + l31) : 0) + hi * 16;
-#pragma unroll
-                for (int j = 0; j < NL; ++j) kx[j] = kin ? *reinterpret_cast<const u32x4_t*>(krow + j * 32) : zero;
-#pragma unroll
-                for (int i = 0; i < NL; ++i) {
-                    const bool vin = kv0 + v_row[i] < Sk;
-                    vx[i] = vin ? *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(p.v) + paged_row(kv0 + v_row[i]) + v_col[i]) : zero;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < NL; ++j)
-                kx[j] = __builtin_amdgcn_raw_buffer_load_b128(krs, (kv0 + l31) * RB + (2 * j + hi) * 16, 0, 0);
-#pragma unroll
-            for (int i = 0; i < NL; ++i) vx[i] = __builtin_amdgcn_raw_buffer_load_b128(vrs, v_g[i], kv0 * RB, 0);
-        }
-        f32x16_t s;
-#pragma unroll
-        for (int j = 0; j < NL; ++j) s = KV::template qk<T>(kx[j], &qf[j * (2 / EB)], j == 0 ? z : s);   // (2 / EB fragments per load)
-#pragma unroll
-        for (int i = 0; i < NL; ++i) KV::template stage_v<T>(Vw + (lane + 64 * i) * (32 / EB), vx[i]);
-
-        // online softmax over this tile's 32 keys (16 per lane half), exp2 domain
-        const bool ragged = kv0 + 32 > Sk || (PAGED && p.window > 0 && Sk - 1 - kv0 >= p.window);
-        float mx = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float x = s[r] * c;
-            if (ragged) {
-                const int kv = kv0 + crow(r, hi);
-                if (kv >= Sk || (PAGED && p.window > 0 && Sk - 1 - kv >= p.window)) x = -INFINITY;
-            }
-            s[r] = x;
-            mx = fmaxf(mx, x);
-        }
-        mx = fmaxf(mx, xhalf(mx));
-        const float m_new = fmaxf(m, mx);   // finite: every tile has at least one key < Sk
-        const float alpha = fast_exp2(m - m_new);
-        m = m_new;
-        float ls = 0.f;
-        u32x4_t pu[2];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float p0 = fast_exp2(s[2 * i] - m_new), p1 = fast_exp2(s[2 * i + 1] - m_new);
-            ls += p0 + p1;
-            pu[i >> 2][i & 3] = T::pack2(p0, p1);
-        }
-        l = l * alpha + ls;
-#pragma unroll
-        for (int d = 0; d < DB; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-        // O^T += V^T . P^T  (A by transpose read from the wave's LDS tile; k-slot order = S accumulator order)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int d = 0; d < DB; ++d) {
-                const int off = ((4 * kk) * (D / 16) + 2 * d) * 128;
-                const s16x4_t a0 = lds_tr16(Vw + tr_off + off);
-                const s16x4_t a1 = lds_tr16(Vw + tr_off + off + 2 * (D / 16) * 128);
-                o[d] = T::mfma(as_v8<T>(a0, a1), as_v8<T>(pu[kk]), o[d]);
-            }
-    }
-
-    // partial of this wave: O (un-normalised, times the source's V factor), m, l of the lane's row (both lane halves
-    // hold the same row)
-    const float vs = KV::v_factor(p, hk);
-    const float lt = l + xhalf(l);
-    const int pi = blockIdx.x * 4 + wave;
-    const size_t prow = (size_t)pi * p.rows_total + (size_t)blockIdx.y * 32 + l31;
-    float* dst = p.part + prow * (D + 2);
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const f32x4_t x = {o[d][4 * g4] * vs, o[d][4 * g4 + 1] * vs, o[d][4 * g4 + 2] * vs, o[d][4 * g4 + 3] * vs};
-            *reinterpret_cast<f32x4_t*>(dst + 32 * d + 8 * g4 + 4 * hi) = x;
-        }
-    if (hi == 0) {
-        dst[D] = m;
-        dst[D + 1] = lt;
-    }
+template <class T, int D, class KV>
+__global__ void __launch_bounds__(256) fa_fwd_paged_query_kernel(const SplitParams p) {
+    constexpr bool PAGED = true, MQ = true;
+#include "fa_fwd_splitkv_body.inc"
 }
 
 // One workgroup per packed row: log-sum-exp merge of the row's partials (there can be hundreds -- a serial loop per
@@ -394,7 +204,7 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_combine(const SplitParams 
         u[0] = T::pack2(t[0] * inv, t[1] * inv);
         u[1] = T::pack2(t[2] * inv, t[3] * inv);
         *reinterpret_cast<u32x2_t*>(reinterpret_cast<char*>(p.o) + orow * (D * 2) + tid * 8) = u;
-        if (tid == 0 && p.lse != nullptr) p.lse[orow] = (M + fast_log2(Lt)) * kLn2;
+        if (tid == 0 && p.lse != nullptr) p.lse[orow] = Lt > 0.f ? (M + fast_log2(Lt)) * kLn2 : -INFINITY;   // (a row that sees no key)
     }
 }
 
@@ -495,13 +305,15 @@ int launch_combine(const SplitParams& p, bool by_count, hipStream_t stream) {
 
 // The wave-per-chunk launch: workspace, split kernel, combine.  `p` arrives with the tensors, B / Hq / Hkv / Sq, the scale and
 // the paged fields set; `w` is wave_chunk_plan() of the problem.
-template <class T, int D, class KV, bool PAGED>
+template <class T, int D, class KV, bool PAGED, bool MQ = false>
 int launch_wave_chunk(SplitParams p, const WaveChunkPlan& w, void* user_ws, uint64_t user_ws_bytes, bool combine_by_count, hipStream_t stream) {
     p.nrt = w.nrt; p.chunk_tiles = w.chunk_tiles; p.npart = w.npart; p.rows_total = w.rows_total;
     ScopedWorkspace ws(w.bytes(D), user_ws, user_ws_bytes, stream);   // caller's buffer, or stream-ordered (safe with concurrent streams)
     if (ws.err != hipSuccess) return (int)ws.err;
     p.part = static_cast<float*>(ws.ptr);
-    hipLaunchKernelGGL((fa_fwd_splitkv_kernel<T, D, KV, PAGED>), dim3((unsigned)w.nsplit, (unsigned)(w.rows_total / 32)), dim3(256), 0, stream, p);
+    const dim3 grid((unsigned)w.nsplit, (unsigned)(w.rows_total / 32));
+    if constexpr (MQ) hipLaunchKernelGGL((fa_fwd_paged_query_kernel<T, D, KV>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((fa_fwd_splitkv_kernel<T, D, KV, PAGED>), grid, dim3(256), 0, stream, p);
     const int rc = (int)hipGetLastError();
     return rc != 0 ? rc : launch_combine<T, D>(p, combine_by_count, stream);
 }
@@ -523,16 +335,17 @@ int launch_split(const FwdArgs& a, const WaveChunkPlan& w, hipStream_t stream) {
     return launch_wave_chunk<T, D, Kv16, false>(p, w, a.ws, a.ws_bytes, false, stream);
 }
 
-static WaveChunkPlan paged_plan(const PagedArgs& a) { return wave_chunk_plan(a.B, a.Hq, a.Hkv, 1, a.max_blocks * a.block_size); }
+// (PagedArgs::Sq is 1 for the decode; the launch and the size query of either paged call plan here)
+static WaveChunkPlan paged_plan(const PagedArgs& a) { return wave_chunk_plan(a.B, a.Hq, a.Hkv, a.Sq, a.max_blocks * a.block_size); }
 
 // Paged decode: one query token per sequence, K/V gathered through the block table; the key range is bounded by
 // max_blocks * block_size on the host (no device->host sync for max(context_lens)); waves past a sequence's
-// context_len leave an empty partial.
-template <class T, int D, class KV>
+// context_len leave an empty partial.  MQ: the paged query, PagedArgs::Sq tokens per sequence and an optional LSE.
+template <class T, int D, class KV, bool MQ>
 int launch_paged(const PagedArgs& a, hipStream_t stream) {
     SplitParams p = {};
-    p.q = a.q; p.k = a.k_cache; p.v = a.v_cache; p.o = a.out; p.lse = nullptr;
-    p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = 1; p.Sk = a.max_blocks * a.block_size;
+    p.q = a.q; p.k = a.k_cache; p.v = a.v_cache; p.o = a.out; p.lse = MQ ? a.lse : nullptr;
+    p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.Sq = MQ ? a.Sq : 1; p.Sk = a.max_blocks * a.block_size;
     p.block_tables = a.block_tables; p.context_lens = a.context_lens;
     p.block_size = a.block_size; p.max_blocks = a.max_blocks; p.window = a.window > 0 ? a.window : 0;
     p.k_scale = a.k_scale; p.v_scale = a.v_scale;
@@ -544,7 +357,18 @@ int launch_paged(const PagedArgs& a, hipStream_t stream) {
     else p.c = a.scale * kLog2e;
     //  * combine: the 16-bit cache always merges with the workgroup-per-row kernel; the FP8 cache picks by the number
     //    of partials (and honours AULE_HIP_FWD_COMBINE), as launch_splitkv_combine does.
-    return launch_wave_chunk<T, D, KV, true>(p, paged_plan(a), a.ws, a.ws_bytes, /*combine_by_count=*/std::is_same<KV, KvFp8>::value, stream);
+    return launch_wave_chunk<T, D, KV, true, MQ>(p, paged_plan(a), a.ws, a.ws_bytes, /*combine_by_count=*/std::is_same<KV, KvFp8>::value, stream);
+}
+
+template <bool MQ>
+int launch_paged_kind(const PagedArgs& a, hipStream_t stream) {
+    const bool fp8 = a.cache_kind == kCacheFp8E4M3;
+    if (fp8 && (a.k_scale == nullptr || a.v_scale == nullptr)) return -1;
+    return for_dtype_d(a.dtype, a.D, [&](auto t, auto d) {
+        using T = decltype(t);
+        constexpr int D = decltype(d)::value;
+        return fp8 ? launch_paged<T, D, KvFp8, MQ>(a, stream) : launch_paged<T, D, Kv16, MQ>(a, stream);
+    });
 }
 
 }  // namespace
@@ -572,19 +396,17 @@ int launch_fwd_splitkv(const FwdArgs& a, const WaveChunkPlan& w, hipStream_t str
 }
 
 // cache_kind selects the K/V source; an FP8 cache needs its two scale arrays
-int launch_paged_decode(const PagedArgs& a, hipStream_t stream) {
-    const bool fp8 = a.cache_kind == kCacheFp8E4M3;
-    if (fp8 && (a.k_scale == nullptr || a.v_scale == nullptr)) return -1;
-    return for_dtype_d(a.dtype, a.D, [&](auto t, auto d) {
-        using T = decltype(t);
-        constexpr int D = decltype(d)::value;
-        return fp8 ? launch_paged<T, D, KvFp8>(a, stream) : launch_paged<T, D, Kv16>(a, stream);
-    });
+int launch_paged_decode(const PagedArgs& a, hipStream_t stream) { return launch_paged_kind<false>(a, stream); }
+
+// PagedArgs::Sq query tokens per sequence (1 .. 64: the packed-row bound of this kernel family), PagedArgs::lse optional
+int launch_paged_query(const PagedArgs& a, hipStream_t stream) {
+    if (a.Sq < 1 || a.Sq > 64) return -1;
+    return launch_paged_kind<true>(a, stream);
 }
 
-// the bytes of the plan the launcher above runs (0: a (dtype, D) it refuses)
+// the bytes of the plan the two launchers above run (0: a (dtype, D, Sq) they refuse)
 uint64_t paged_workspace_bytes(const PagedArgs& a) {
-    if ((a.dtype != kBF16 && a.dtype != kF16) || (a.D != 128 && a.D != 64 && a.D != 32)) return 0;
+    if ((a.dtype != kBF16 && a.dtype != kF16) || (a.D != 128 && a.D != 64 && a.D != 32) || a.Sq < 1 || a.Sq > 64) return 0;
     return paged_plan(a).bytes(a.D);
 }
 

@@ -153,6 +153,11 @@ struct PagedArgs {
     int cache_kind = kCache16;          // element type of the caches (dtype is the type of q / out)
     const float* k_scale = nullptr;     // kCacheFp8E4M3 only
     const float* v_scale = nullptr;
+    // launch_paged_query only (launch_paged_decode reads neither): Sq query tokens per sequence, q / out [B, Hq, Sq, D], the last Sq
+    // positions of each sequence -- query i at position context_len - Sq + i sees the keys at or before it (and inside the window
+    // measured from there); a query at a negative position gives zeros.  lse [B, Hq, Sq] fp32 or null (-inf where no key is seen)
+    int Sq = 1;
+    float* lse = nullptr;
 };
 
 // Rotary embedding pass (rope_gfx950.hip): x [nheads, S, D] with `pitch` elements per row, tables [>= S + pos_offset, D/2]
@@ -200,6 +205,7 @@ int launch_kv_append(const KvAppendArgs& a, hipStream_t stream);   // -1: unsupp
 // Returns 0 on success, a hipError_t value on launch failure, -1 for an
 // unsupported (dtype, D) combination.
 int launch_paged_decode(const PagedArgs& a, hipStream_t stream);   // either cache_kind; kCacheFp8E4M3 with a null scale array is -1
+int launch_paged_query(const PagedArgs& a, hipStream_t stream);    // ... with PagedArgs::Sq in 1 .. 64 tokens per sequence (else -1)
 int launch_fwd(const FwdArgs& a, hipStream_t stream);
 // merge partials [npart][B*Hkv*nrt*32][D+2] fp32 (un-normalised O, m in log2 units, l) into O / LSE (fa_fwd_splitkv_gfx950.hip)
 int launch_splitkv_combine(const FwdArgs& a, float* part, int npart, int nrt, hipStream_t stream);
@@ -213,7 +219,7 @@ bool fwd_rope_fusable(const FwdArgs& a);
 int fwd_split_plan_dump(const FwdArgs& a, int* out, int cap);
 // blockIdx -> (batch, kv head, q head, block) of decode_work (ranked = 0) / decode_work_ranked (1) on the host (tests): fa_fwd_f32.hip
 void work_order_dump(int ranked, int bid, int B, int Hq, int Hkv, int nblk, int flag, int* out4);
-// bytes of workspace launch_fwd / launch_paged_decode would allocate for these arguments (0: single-launch path)
+// bytes of workspace launch_fwd / launch_paged_decode (Sq = 1) or launch_paged_query would allocate for these arguments (0: single-launch path)
 uint64_t fwd_workspace_bytes(const FwdArgs& a);
 uint64_t paged_workspace_bytes(const PagedArgs& a);
 int launch_bwd(const BwdArgs& a, hipStream_t stream);

@@ -235,6 +235,48 @@ int32_t aule_attention_paged_decode_fp8_ex(const aule_paged_fp8_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  Same plan as the 16-bit call of the same shape. */
 uint64_t aule_attention_paged_decode_fp8_workspace_size(const aule_paged_fp8_desc* desc);
 
+/* Paged attention for SHORT MULTI-TOKEN queries (additive): the step that adds seq_q > 1 tokens per sequence -- verifying the */
+/* k + 1 draft tokens of speculative decoding, multi-token prediction heads, a short tail chunk of a prompt against a cached   */
+/* prefix.  q and out are [batch, heads_q, seq_q, head_dim] fp16 / bf16 with 1 <= seq_q <= 64 (the same for every sequence);   */
+/* the caches are either of that dtype (cache_dtype AULE_KV_CACHE_SAME, k_scale / v_scale NULL) or OCP e4m3fn codes with the   */
+/* [heads_kv] fp32 device scales of aule_paged_fp8_desc (AULE_KV_CACHE_FP8_E4M3).  Cache layout, block-table rules and the     */
+/* on-device clamp of context_lens are those of aule_attention_paged_decode_ex.  context_lens[b] counts the keys in the cache  */
+/* INCLUDING the seq_q new tokens (append them first: aule_kv_cache_append_ex).  With L_b the clamped length, query i of       */
+/* sequence b sits at position p = L_b - seq_q + i and sees key j iff j <= p, and with window_size = W > 0 iff also p - j < W   */
+/* -- the bottom-right rule of AULE_CAUSAL_BOTTOM_RIGHT.  A query with p < 0 (a sequence shorter than seq_q) gives an output    */
+/* row of zeros.  lse (optional) is [batch, heads_q, seq_q] fp32: the natural log of the sum of exp(scaled score) over the     */
+/* visible keys, k_scale included; -inf for a row that sees no key.  seq_q = 1 gives aule_attention_paged_decode_ex /          */
+/* _fp8_ex bit for bit.  Not built: seq_q > 64, per-sequence query lengths, head_dim 256.  No host synchronisation, and no     */
+/* allocation when a workspace is passed: captures into a hipGraph.                                                            */
+typedef struct aule_paged_query_desc {
+    uint32_t struct_size;      /* = sizeof(aule_paged_query_desc) = 152 */
+    int32_t dtype;             /* type of q / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    uint32_t batch, heads_q, heads_kv, head_dim;   /* head_dim 32, 64 or 128 */
+    uint32_t block_size;
+    uint32_t max_blocks;
+    float scale;               /* 0 -> 1/sqrt(head_dim) */
+    int32_t window_size;       /* > 0: query at position p sees only the keys j with p - j < window_size */
+    int32_t device;
+    void* stream;              /* offset 48 */
+    const void* q;             /* [batch, heads_q, seq_q, head_dim], 16-bit */
+    const void* k_cache;       /* [num_blocks, block_size, heads_kv, head_dim]: 16-bit of q's dtype, or e4m3fn bytes */
+    const void* v_cache;       /* same layout */
+    const int32_t* block_tables;   /* [batch, max_blocks] */
+    const int32_t* context_lens;   /* [batch]: keys per sequence, the seq_q new ones included */
+    void* out;                 /* [batch, heads_q, seq_q, head_dim], 16-bit */
+    void* workspace;           /* offset 104; optional, size from aule_attention_paged_query_workspace_size() */
+    uint64_t workspace_bytes;
+    const float* k_scale;      /* offset 120; [heads_kv] fp32, device (AULE_KV_CACHE_FP8_E4M3), else NULL */
+    const float* v_scale;      /* offset 128 */
+    float* lse;                /* offset 136; optional (NULL to skip): [batch, heads_q, seq_q] fp32 */
+    uint32_t seq_q;            /* offset 144; 1 .. 64 */
+    int32_t cache_dtype;       /* offset 148; AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3 */
+} aule_paged_query_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_paged_query_ex(const aule_paged_query_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses on shape grounds. */
+uint64_t aule_attention_paged_query_workspace_size(const aule_paged_query_desc* desc);
+
 /* Rotary position embedding pass (additive; SURVEY.md 8f row N1, second half).  Replaces the rotation the           */
 /* reference fuses into its kernels: python/aule/triton_flash.py:32-52,:112-131,:165-180 (layout HALF) and            */
 /* shaders/attention_f32.comp:98-111,:132-145 (layout INTERLEAVED).  x is [rows_bh, seq, head_dim] with               */
