@@ -263,6 +263,7 @@ SIGNATURES = [
     ("aule_hip_debug_backward_route", _I32, [ctypes.POINTER(AttnBwdDesc)]),
     ("aule_hip_debug_forward_split_plan", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_work_order", _I32, [_I32] * 7 + [ctypes.POINTER(_I32)]),
+    ("aule_hip_debug_switches", _U64, [ctypes.c_char_p, _U64]),
 ]
 
 _lib = None

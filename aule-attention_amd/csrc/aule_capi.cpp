@@ -25,6 +25,7 @@
 
 #include "fa_bwd_plan.h"
 #include "fa_kernels.h"
+#include "fa_switches.h"
 
 // abi2: optional workspace / workspace_bytes appended to the forward and paged descriptors (96 -> 112, 104 -> 120)
 static_assert(sizeof(aule_attn_desc) == 112 && offsetof(aule_attn_desc, lse) == 88 && offsetof(aule_attn_desc, workspace) == 96,
@@ -749,8 +750,7 @@ struct RoctxRange {
     using PopFn = int (*)();
     static PushFn push_fn() {
         static const PushFn fn = [] {
-            const char* e = getenv("AULE_ROCTX");
-            if (e == nullptr || e[0] != '1') return (PushFn) nullptr;
+            if (!aule_hip::switches().roctx) return (PushFn) nullptr;
             // rocprofv3 intercepts the rocprofiler-sdk flavour; libroctx64 is the legacy (roctracer) one
             void* h = nullptr;
             for (const char* name : {"librocprofiler-sdk-roctx.so", "/opt/rocm/lib/librocprofiler-sdk-roctx.so", "libroctx64.so",
@@ -1344,6 +1344,11 @@ int32_t aule_hip_debug_work_order(int32_t ranked, int32_t bid, int32_t batch, in
     return 0;
 }
 
+/* Debug hook: the run-time switches this process runs under (csrc/fa_switches.h), one line per name, NAME=<resolved value>, the unset
+ * default spelt like a set one.  Returns the bytes the text needs (NUL included) and writes at most `cap` of them.  No lock, no device,
+ * no aule_init() needed; the first call of this or of any plan reads the environment, once. */
+uint64_t aule_hip_debug_switches(char* buf, uint64_t cap) { return aule_hip::print_switches(aule_hip::switches(), buf, cap); }
+
 #ifdef AULE_DEBUG_HOOKS
 /* Debug hook (debug library only): bf16 D=128 forward with per-phase s_memtime stamps of workgroup 0 written to
  * `stamps` (device pointer; 8 * 256 uint64 for the ping-pong kernel, 8 * 2048 with AULE_TL=ps for the tile stream).
@@ -1356,10 +1361,8 @@ int32_t aule_hip_debug_forward_timeline(const aule_attn_desc* d, unsigned long l
     if (d->dtype != AULE_DTYPE_BF16 || (d->head_dim != 128 && d->head_dim != 64)) return -3;   // the instrumented instances
     FwdArgs a;
     fill_fwd_args(d, a);
-    if (const char* e = getenv("AULE_TL")) {
-        if (e[0] == 'w' && e[1] == '4')  // one wave per SIMD: 4 waves x 2048 tagged stamps (tools/timeline_w4.py)
-            return aule_hip::launch_fwd_w4_timeline(a, stamps, (hipStream_t)d->stream);
-    }
+    if (aule_hip::switches().tl == aule_hip::Timeline::w4)   // AULE_TL=w4, one wave per SIMD: 4 waves x 2048 tagged stamps (tools/timeline_w4.py)
+        return aule_hip::launch_fwd_w4_timeline(a, stamps, (hipStream_t)d->stream);
     return aule_hip::launch_fwd_pp_timeline(a, stamps, (hipStream_t)d->stream);
 }
 #endif  // AULE_DEBUG_HOOKS

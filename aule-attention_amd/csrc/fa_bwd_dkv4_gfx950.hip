@@ -32,6 +32,7 @@
 
 #include "fa_device.h"
 #include "fa_kernels.h"
+#include "fa_switches.h"
 #include "fa_fwd_tile.h"
 
 namespace aule_hip {
@@ -597,11 +598,7 @@ int launch_dkv4(const BwdArgs& a, hipStream_t stream) {
 // one 2 GB descriptor.  Whether it is taken: bwd_dkv4_items() against the predecessor's grid, in bwd_plan (fa_bwd_gfx950.hip).
 bool bwd_dkv4_applicable(const BwdArgs& a) {
     // AULE_HIP_BWD_DKV=old: the two-waves-per-SIMD kernel everywhere (A/B); =new: this kernel wherever it CAN run (tests)
-    static const int mode = [] {
-        const char* e = std::getenv("AULE_HIP_BWD_DKV");
-        return e == nullptr ? 0 : (e[0] == 'o' ? 1 : (e[0] == 'n' ? 2 : 0));
-    }();
-    if (mode == 1) return false;
+    if (switches().bwd_dkv == Pick::old_kernel) return false;
     if (a.dtype != kBF16 && a.dtype != kF16) return false;
     if (a.D != 128 && a.D != 64) return false;
     if (a.window > 0 && !a.causal) return false;      // (round 5: causal sliding windows run here too; a window without the causal rule stays on the predecessor)
@@ -620,25 +617,12 @@ long long bwd_dkv4_items(const BwdArgs& a) { return dkv4_items_of(a, kKvBlock4);
 // time: profiles/r6_bwd_d64_k2.txt).  Whole rounds of the chip decide: ceil(items / CUs) of either kind, priced.
 // AULE_HIP_BWD_DKV_K2=0 / 1 pins it (A/B, tests).
 bool bwd_dkv4_k2(const BwdArgs& a) {
-    static const int mode = [] {
-        const char* e = std::getenv("AULE_HIP_BWD_DKV_K2");
-        return e == nullptr ? -1 : (e[0] == '0' ? 0 : 1);
-    }();
     if (a.D != 64 || a.dbg != nullptr) return false;   // (the timeline instances stay on the one-block stream)
-    if (mode >= 0) return mode == 1;
+    if (switches().bwd_dkv_k2 != K2::rule) return switches().bwd_dkv_k2 == K2::always;
     const long long cus = device_cu_count(a.device);
     const long long i1 = dkv4_items_of(a, kKvBlock4), i2 = dkv4_items_of(a, 256);
     const long long r1 = (i1 + cus - 1) / cus, r2 = (i2 + cus - 1) / cus;
     return r2 * 132 < r1 * 100;
-}
-
-// AULE_HIP_BWD_DKV=new: take every problem bwd_dkv4_applicable() accepts (tests)
-bool bwd_dkv4_forced() {
-    static const int v = [] {
-        const char* e = std::getenv("AULE_HIP_BWD_DKV");
-        return (e != nullptr && e[0] == 'n') ? 1 : 0;
-    }();
-    return v == 1;
 }
 
 int launch_bwd_dkv4(const BwdArgs& a, hipStream_t stream) {

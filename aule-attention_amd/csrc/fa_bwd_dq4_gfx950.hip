@@ -28,6 +28,7 @@
 
 #include "fa_device.h"
 #include "fa_kernels.h"
+#include "fa_switches.h"
 #include "fa_fwd_tile.h"
 
 namespace aule_hip {
@@ -332,16 +333,8 @@ int launch_dq4(const BwdArgs& a, float* lse2_out, float* ndelta_out, hipStream_t
 // Shapes the one-wave-per-SIMD dQ kernel can take: 16-bit, D = 128 or 64, no window, causal offset >= 0, offsets inside 2 GB
 // descriptors.  AULE_HIP_BWD_DQ=new takes it wherever it can run, =old never (A/B, tests); default: the dispatcher's grid rule
 // (fa_bwd_gfx950.hip).
-int bwd_dq4_mode() {
-    static const int mode = [] {
-        const char* e = std::getenv("AULE_HIP_BWD_DQ");
-        return e == nullptr ? 0 : (e[0] == 'o' ? 1 : (e[0] == 'n' ? 2 : 0));
-    }();
-    return mode;
-}
-
 bool bwd_dq4_applicable(const BwdArgs& a) {
-    if (bwd_dq4_mode() == 1) return false;
+    if (switches().bwd_dq == Pick::old_kernel) return false;
     if (a.dtype != kBF16 && a.dtype != kF16) return false;
     if (a.D != 128 && a.D != 64) return false;
     if (a.window > 0 && !a.causal) return false;      // (round 5: causal sliding windows run here; a window without the causal rule stays on the predecessor)

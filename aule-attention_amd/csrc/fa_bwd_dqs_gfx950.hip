@@ -26,6 +26,7 @@
 
 #include "fa_device.h"
 #include "fa_kernels.h"
+#include "fa_switches.h"
 #include "fa_fwd_tile.h"
 
 namespace aule_hip {
@@ -326,11 +327,7 @@ int launch_dqs(const BwdArgs& a, hipStream_t stream) {
     // of its own, the blocks are not paired)
     p.pair = (a.causal && (long long)nqb * a.B * a.Hq > (long long)DQS_OCC * device_cu_count(-1)) ? 1 : 0;
     p.nblk = (a.causal && p.pair) ? (nqb + 1) / 2 : nqb;
-    static const int rev = [] {
-        const char* e = std::getenv("AULE_HIP_DQS_REV");
-        return e != nullptr ? std::atoi(e) : 1;
-    }();
-    p.rev = rev;
+    p.rev = switches().dqs_rev;   // AULE_HIP_DQS_REV=0: forwards (A/B)
     const dim3 grid((unsigned)(p.nblk * a.B * a.Hq)), block(256);
     if (a.causal)
         hipLaunchKernelGGL((fa_bwd_dqs_kernel<T, D, true>), grid, block, DqsCfg<D>::LDS, stream, p);

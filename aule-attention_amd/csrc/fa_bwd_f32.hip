@@ -14,6 +14,7 @@
 
 #include "fa_device.h"
 #include "fa_kernels.h"
+#include "fa_switches.h"
 
 namespace aule_hip {
 
@@ -393,11 +394,7 @@ __global__ void __launch_bounds__(256) fa_bwd_f32_sum(const SumF32Params p) {
 // Pieces per block for grids that leave most of the chip idle (the reference's Zig benchmark shape, tests/benchmark_attention.zig:18-21:
 // B4 H8 S512 D64 = 128 workgroups for 512 slots): as many as fill the slots, at least two tiles each, at most 8.  AULE_HIP_F32_SPLIT=0: off.
 inline int f32_bwd_pieces(long long items, int tiles, int D, int device) {
-    static const int on = [] {
-        const char* e = std::getenv("AULE_HIP_F32_SPLIT");
-        return (e != nullptr && e[0] == '0') ? 0 : 1;
-    }();
-    if (!on) return 1;
+    if (!switches().f32_split) return 1;
     const long long slots = (D <= 64 ? 2LL : 1LL) * device_cu_count(device);
     if (items <= 0 || items * 2 > slots) return 1;
     long long n = slots / items;

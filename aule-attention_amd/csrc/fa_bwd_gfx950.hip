@@ -31,16 +31,15 @@
 #include "fa_device.h"
 #include "fa_bwd_plan.h"
 #include "fa_kernels.h"
+#include "fa_switches.h"
 
 namespace aule_hip {
 bool bwd_dkv4_applicable(const BwdArgs& a);          // fa_bwd_dkv4_gfx950.hip: the one-wave-per-SIMD dK/dV kernel
-bool bwd_dkv4_forced();
 bool bwd_dkv4_k2(const BwdArgs& a);                    // D = 64: the two-key-blocks-per-wave instance (round 6)
 long long bwd_dkv4_items(const BwdArgs& a);
 int launch_bwd_dkv4(const BwdArgs& a, hipStream_t stream);
 int configure_bwd_dkv4();
 bool bwd_dq4_applicable(const BwdArgs& a);           // fa_bwd_dq4_gfx950.hip: the one-wave-per-SIMD dQ kernel
-int bwd_dq4_mode();
 int launch_bwd_dq4(const BwdArgs& a, float* lse2_out, float* ndelta_out, hipStream_t stream);
 int configure_bwd_dq4();
 bool bwd_dqs_applicable(const BwdArgs& a);           // fa_bwd_dqs_gfx950.hip: the 5-matmul backward's delta pass and dQ = dS K kernel
@@ -1097,34 +1096,6 @@ inline uint64_t delta_bytes(int B, int Hq, int Sq) {
 // BwdPlan::route of the most recent backward launch of this process (aule_hip_debug_last_backward_route; launch_bwd stores it)
 std::atomic<int> g_last_bwd_route{0};
 
-inline int bwd_mode() {   // 0: auto (by AULE_HIP_BWD_DS_AUTO_MB), 1: recompute, 2: spill wherever applicable
-    static const int m = [] {
-        const char* e = std::getenv("AULE_HIP_BWD_MODE");
-        if (e == nullptr) return 0;
-        return e[0] == 'r' ? 1 : (e[0] == 's' ? 2 : 0);
-    }();
-    return m;
-}
-inline uint64_t env_mb(const char* name, long long dflt) {   // a size switch in MB, as bytes
-    const char* e = std::getenv(name);
-    const long long mb = e != nullptr ? std::atoll(e) : dflt;
-    return (uint64_t)(mb > 0 ? mb : 0) << 20;
-}
-inline uint64_t bwd_ds_auto_bytes() { static const uint64_t c = env_mb("AULE_HIP_BWD_DS_AUTO_MB", 160); return c; }
-inline uint64_t bwd_ds_cap_bytes() { static const uint64_t c = env_mb("AULE_HIP_BWD_DS_CAP_MB", 8192); return c; }
-// The debug inputs of the plan besides BwdArgs::dbg / dbg_dq.  AULE_TL=dkv4: the dK/dV timeline runs the one-wave-per-SIMD kernel whatever
-// the grid.  Debug library only, AULE_DBG_BWD_ONLY=dq / =dkv: one of the two kernels alone (per-kernel times from tools/cbench.cpp without
-// a profiler; the workspace keeps delta / L' of an earlier full call) -- 1 dQ, 2 dK/dV, 0 (anything else) both.
-inline bool dkv4_timeline_wanted() { const char* e = std::getenv("AULE_TL"); return e != nullptr && e[0] == 'd' && e[1] == 'k'; }
-inline int dbg_bwd_only() {
-#ifdef AULE_DEBUG_HOOKS
-    const char* e = std::getenv("AULE_DBG_BWD_ONLY");
-    static const int only = e == nullptr ? 0 : (std::strcmp(e, "dq") == 0 ? 1 : (std::strcmp(e, "dkv") == 0 ? 2 : 0));
-    return only;
-#else
-    return 0;
-#endif
-}
 
 }  // namespace
 
@@ -1150,8 +1121,12 @@ BwdPlan bwd_plan(const BwdArgs& a) {
     p.min_bytes = (base + 255) / 256 * 256;
     p.ds_off = p.want_bytes = p.min_bytes > a.ws_floor ? p.min_bytes : a.ws_floor;
 
-    const bool timeline = dkv4_timeline_wanted();
-    const int only = dbg_bwd_only();
+    // The debug inputs of the plan besides BwdArgs::dbg / dbg_dq.  AULE_TL=dkv4: the dK/dV timeline runs the one-wave-per-SIMD kernel whatever
+    // the grid.  Debug library only, AULE_DBG_BWD_ONLY=dq / =dkv: one of the two kernels alone (per-kernel times from tools/cbench.cpp without
+    // a profiler; the workspace keeps delta / L' of an earlier full call).
+    const Switches& sw = switches();
+    const bool timeline = sw.tl == Timeline::dkv4;
+    const BwdOnly only = sw.dbg_bwd_only;
     // The one-wave-per-SIMD dK/dV kernel (fa_bwd_dkv4_gfx950.hip: 128-key blocks, the whole GQA group inside a workgroup, no head
     // split / partials / reduce) wherever it covers the chip (>= 192 work items) or has at least as many work items as this
     // file's kernel would (256-key blocks x head split).  Same box, whole backward, tools/cb_rule.sh: ahead on every shape of the
@@ -1160,7 +1135,7 @@ BwdPlan bwd_plan(const BwdArgs& a) {
     const bool dkv4_can = bwd_dkv4_applicable(a);
     const auto dkv4_by_grid = [&] {
         const long long there = bwd_dkv4_items(a);
-        return bwd_dkv4_forced() || there >= 192 || there >= dkdv_items(a) * p.gsplit;
+        return sw.bwd_dkv == Pick::new_kernel || there >= 192 || there >= dkdv_items(a) * p.gsplit;
     };
 
     // The 5-matmul mode (comment above): where both of its kernels can run, the dK/dV grid takes the one-wave-per-SIMD kernel anyway, no
@@ -1168,12 +1143,12 @@ BwdPlan bwd_plan(const BwdArgs& a) {
     // fits the budget.  (The columns are allocated as full squares -- the address is the stream position -- so a causal problem asks for up
     // to twice the budget of workspace: INTEGRATION.md, include/aule.h state it; only the touched half travels through the cache.)
     // The call takes it when the caller's buffer has dS room for at least one batch element, and then runs in chunks of as many as fit.
-    if (bwd_mode() != 1 && only == 0 && a.dbg == nullptr && a.dbg_dq == nullptr && !timeline && a.window <= 0 && a.Sq > 0 && a.Sk > 0 &&
+    if (sw.bwd_mode != BwdMode::recompute && only == BwdOnly::both && a.dbg == nullptr && a.dbg_dq == nullptr && !timeline && a.window <= 0 && a.Sq > 0 && a.Sk > 0 &&
         dkv4_can && bwd_dqs_applicable(a) && dkv4_by_grid()) {
         const uint64_t pb = (uint64_t)a.Hkv * (uint64_t)DsLayout::of(a.Hq, a.Hkv, a.Sq, a.Sk).group_bytes;   // dS bytes per batch element
-        const bool fits = pb <= bwd_ds_cap_bytes() && (bwd_mode() == 2 || (uint64_t)a.B * pb / (a.causal ? 2 : 1) <= bwd_ds_auto_bytes());
+        const bool fits = pb <= sw.bwd_ds_cap_bytes && (sw.bwd_mode == BwdMode::spill || (uint64_t)a.B * pb / (a.causal ? 2 : 1) <= sw.bwd_ds_auto_bytes);
         if (fits && pb > 0) {
-            const uint64_t B = (uint64_t)a.B, cap = bwd_ds_cap_bytes() / pb, have = a.ws_bytes > p.ds_off ? (a.ws_bytes - p.ds_off) / pb : 0;
+            const uint64_t B = (uint64_t)a.B, cap = sw.bwd_ds_cap_bytes / pb, have = a.ws_bytes > p.ds_off ? (a.ws_bytes - p.ds_off) / pb : 0;
             p.want_bytes += (cap < B ? cap : B) * pb;
             p.nb = (int)(have < B ? have : B);
         }
@@ -1187,13 +1162,13 @@ BwdPlan bwd_plan(const BwdArgs& a) {
     // on all ten shapes of tools/cb_rule_dq.sh (whole backward -0.2 .. -2.5 %, the 128-item grids level), behind on grids of a few
     // workgroups (its three-stage stream start and 64-row prologue).  AULE_HIP_BWD_DQ=old|new pin either one.
     // D = 64 (round 4): ahead on small grids too (16 .. 64 work items: +1.9 .. +7.5 % on the whole backward, profiles/r4_bwd_d64_dkv4.txt) -- no grid rule there.
-    if (only != 2) {
+    if (only != BwdOnly::dkv) {
         const int nqb = (a.Sq + kDqQBlock - 1) / kDqQBlock;
         const long long dq4_items = (long long)a.B * a.Hq * (a.causal ? (nqb + 1) / 2 : nqb);
-        const bool dq4 = a.dbg_dq == nullptr && bwd_dq4_applicable(a) && (bwd_dq4_mode() == 2 || a.D == 64 || dq4_items >= 128);
+        const bool dq4 = a.dbg_dq == nullptr && bwd_dq4_applicable(a) && (sw.bwd_dq == Pick::new_kernel || a.D == 64 || dq4_items >= 128);
         p.route |= dq4 ? kRouteDq4 : kRouteDqOld;
     }
-    if (only != 1) {
+    if (only != BwdOnly::dq) {
         // (timeline instances of the dK/dV kernels: bf16, D = 128 and, round 5, D = 64; stamps without AULE_TL=dkv4 mean this file's kernel)
         const bool dkv4 = dkv4_can && (timeline || (a.dbg == nullptr && dkv4_by_grid()));
         p.k2 = dkv4 && bwd_dkv4_k2(a);

@@ -20,6 +20,7 @@
 #include "fa_device.h"
 #include "fa_fwd_plan.h"
 #include "fa_kernels.h"
+#include "fa_switches.h"
 
 namespace aule_hip {
 namespace {
@@ -266,11 +267,7 @@ __global__ void __launch_bounds__(256) fa_fwd_f32_combine(const CombineF32Params
 // 18-21: B4 H8 S512 D64 = 128 workgroups for 512 slots): as many as fill the slots, at least two key tiles each, at most 8.
 // AULE_HIP_F32_SPLIT=0 turns it off (A/B).
 inline int f32_pieces(const FwdArgs& a, int nqb) {
-    static const int on = [] {
-        const char* e = std::getenv("AULE_HIP_F32_SPLIT");
-        return (e != nullptr && e[0] == '0') ? 0 : 1;
-    }();
-    if (!on) return 1;
+    if (!switches().f32_split) return 1;
     const long long items = (long long)nqb * a.B * a.Hq, slots = 2LL * device_cu_count(a.device);
     if (items <= 0 || items * 2 > slots) return 1;
     const int kv_hi = a.causal ? (a.Sk < a.Sq + a.coff ? a.Sk : a.Sq + a.coff) : a.Sk;   // the largest block's keys

@@ -26,35 +26,12 @@
 #include "fa_device.h"
 #include "fa_fwd_plan.h"
 #include "fa_kernels.h"
+#include "fa_switches.h"
 
 namespace aule_hip {
 int configure_fwd_f32();   // fa_fwd_f32.hip
 int configure_fwd_pp();    // fa_fwd_pp_gfx950.hip
 int configure_fwd_w4();    // fa_fwd_w4_gfx950.hip
-
-// AULE_HIP_FWD_KERNEL=pp keeps every tiled problem on the ping-pong kernel (A/B measurements against the one-wave-per-SIMD kernel)
-static int fwd_kernel_choice() {
-    static const int v = [] {
-        const char* e = getenv("AULE_HIP_FWD_KERNEL");
-        if (e == nullptr || e[0] == 0) return 0;
-        if (e[0] == 'p' && e[1] == 'p' && e[2] == 0) return 4;
-        if (e[0] == 'w' && e[1] == '4' && e[2] == 0) return 0;
-        // ("ps" named the persistent tile stream retired in round 4 and used to be ignored silently: an A/B run then
-        // measured the default kernel twice)
-        fprintf(stderr, "libaule: WARNING: AULE_HIP_FWD_KERNEL=%s is not a kernel of this build (known: pp, w4) -- the default dispatch runs\n", e);
-        return 0;
-    }();
-    return v;
-}
-
-// AULE_HIP_FWD_SPLITKV=0 keeps short-query shapes on the tiled kernels (A/B measurements)
-static bool splitkv_enabled() {
-    static const int v = [] {
-        const char* e = getenv("AULE_HIP_FWD_SPLITKV");
-        return (e != nullptr && e[0] == '0') ? 0 : 1;
-    }();
-    return v == 1;
-}
 
 // Non-causal problems that the plain tiled launch would run badly (few workgroups, or Q blocks mostly without rows):
 // 4 = wave-per-chunk split-KV kernel, 5 = tiled kernel with packed rows + KV splits (`pp` is its plan then), 0 = neither.
@@ -64,7 +41,7 @@ static bool splitkv_enabled() {
 // it is 10-15 % ahead at D = 128 and 35-55 % at D = 64.  Differences below ~8 % on these kernels are noise.
 static int short_query_route(const FwdArgs& a, PPSplitPlan& pp) {
     if (a.window > 0) return 0;
-    const bool wave_ok = !a.causal && splitkv_enabled() && splitkv_applicable(a);   // (the wave kernel has no mask)
+    const bool wave_ok = !a.causal && switches().fwd_splitkv && splitkv_applicable(a);   // (the wave kernel has no mask; AULE_HIP_FWD_SPLITKV=0: A/B)
     PPSplitPlan s;
     const bool tiled_ok = fwd_pp_split_plan(a, s);
     int route = wave_ok ? 4 : (tiled_ok ? 5 : 0);
@@ -102,9 +79,11 @@ FwdPlan fwd_plan(const FwdArgs& a) {
     } else if (p.route == 5) {
         p.ws_bytes = p.pp.bytes(a.B * a.Hkv, a.D);
     } else {
-        // short / non-causal windows, fewer than four KV tiles per Q block, D = 32, scale = 0, AULE_HIP_FWD_KERNEL=pp and the online
-        // softmax stay on the ping-pong kernel
-        const bool w4 = fwd_kernel_choice() == 0 && !fwd_softmax_classic();
+        // short / non-causal windows, fewer than four KV tiles per Q block, D = 32, scale = 0, AULE_HIP_FWD_KERNEL=pp (A/B against the
+        // one-wave-per-SIMD kernel) and the online softmax stay on the ping-pong kernel.  (AULE_HIP_FWD_SOFTMAX=classic asks for the
+        // online softmax throughout, default "raw" for bf16: the ping-pong kernel then runs its online instances; the one-wave-per-SIMD
+        // kernel has no online form -- its fall-back is a second pass with the exact row maximum.)
+        const bool w4 = switches().fwd_kernel != FwdKernel::pp && !switches().fwd_softmax_classic;
         if (w4 && fwd_w4_split_plan(a, p.split)) {
             p.route = 7;
             p.ws_bytes = p.split.bytes;

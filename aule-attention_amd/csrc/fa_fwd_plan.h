@@ -6,9 +6,8 @@
 // fa_fwd_gfx950.hip; what a kernel can take and its sub-plan are stated in the kernel's own file.  (A rope request the plan cannot
 // fuse is refused by launch_fwd; ws_bytes is then what the same call without the tables would use.)
 #pragma once
-#include <cstdlib>
-
 #include "fa_kernels.h"
+#include "fa_switches.h"
 
 namespace aule_hip {
 
@@ -62,16 +61,5 @@ int launch_fwd_w4(const FwdArgs& a, const W4Grid& g, hipStream_t stream);
 int launch_fwd_w4_split(const FwdArgs& a, const SplitPlan& s, hipStream_t stream);
 int launch_fwd_splitkv(const FwdArgs& a, const WaveChunkPlan& w, hipStream_t stream);
 int launch_fwd_d256(const FwdArgs& a, hipStream_t stream);   // fa_fwd_d256_gfx950.hip (every dtype)
-
-// AULE_HIP_FWD_SOFTMAX=classic asks for the online softmax throughout (default "raw" for bf16; A/B measurements): the ping-pong
-// kernel then runs its online instances, and the one-wave-per-SIMD kernel, which has no online form (its fall-back is a second pass
-// with the exact row maximum), is not chosen.
-inline bool fwd_softmax_classic() {
-    static const int v = [] {
-        const char* e = std::getenv("AULE_HIP_FWD_SOFTMAX");
-        return (e != nullptr && e[0] == 'c') ? 1 : 0;
-    }();
-    return v == 1;
-}
 
 }  // namespace aule_hip

@@ -591,7 +591,7 @@ int launch_pp(const FwdArgs& a, hipStream_t stream) {
         return (int)hipGetLastError();
     }
     if constexpr (std::is_same<T, Bf16Traits>::value) {
-        if (!fwd_softmax_classic()) {   // bf16: the raw softmax unless AULE_HIP_FWD_SOFTMAX=classic
+        if (!switches().fwd_softmax_classic) {   // bf16: the raw softmax unless AULE_HIP_FWD_SOFTMAX=classic
             if (a.causal)
                 hipLaunchKernelGGL((fa_fwd_pp_kernel<T, D, true, false, true>), grid, block, lds, stream, p);
             else
@@ -663,7 +663,7 @@ int launch_pp_split(const FwdArgs& a, const PPSplitPlan& s, hipStream_t stream) 
     } else {
         bool raw = false;
         if constexpr (std::is_same<T, Bf16Traits>::value) {
-            raw = !fwd_softmax_classic();
+            raw = !switches().fwd_softmax_classic;
             if (raw) hipLaunchKernelGGL((fa_fwd_pp_kernel<T, D, false, false, true, false, true>), grid, block, lds, stream, p);
         }
         if (!raw) hipLaunchKernelGGL((fa_fwd_pp_kernel<T, D, false, false, false, false, true>), grid, block, lds, stream, p);
@@ -716,14 +716,14 @@ int launch_fwd_pp_timeline(const FwdArgs& a, unsigned long long* dbg, hipStream_
     p.coff = 0;
     p.sq_orig = a.Sq; p.nbase = 1; p.chunk = 0; p.part_rows = 0; p.prow_per_unit = 0; p.part = nullptr;
     p.dbg = dbg;
-    p.dbg_flags = getenv("AULE_TL_FLAGS") ? atoi(getenv("AULE_TL_FLAGS")) : 0;
+    p.dbg_flags = switches().tl_flags;   // AULE_TL_FLAGS
     const dim3 grid((unsigned)(p.nwork * a.B * a.Hq)), block(512);
     const size_t lds = Cfg<128>::LDS + 16;
     auto go = [&](auto kern) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
     };
-    if (!fwd_softmax_classic()) {
+    if (!switches().fwd_softmax_classic) {
         if (a.causal) go(&fa_fwd_pp_kernel<Bf16Traits, 128, true, true, true>);
         else go(&fa_fwd_pp_kernel<Bf16Traits, 128, false, true, true>);
     } else {
@@ -751,11 +751,7 @@ int launch_fwd_pp(const FwdArgs& a, hipStream_t stream) {
 // Shapes for the SPLIT instances, and their plan (`s`, meaningful when the answer is yes).  AULE_HIP_FWD_PPSPLIT=0 turns the path
 // off (A/B measurements).
 bool fwd_pp_split_plan(const FwdArgs& a, PPSplitPlan& s) {
-    static const int on = [] {
-        const char* e = getenv("AULE_HIP_FWD_PPSPLIT");
-        return (e != nullptr && e[0] == '0') ? 0 : 1;
-    }();
-    if (!on) return false;
+    if (!switches().fwd_ppsplit) return false;
     if (a.dtype != kBF16 && a.dtype != kF16) return false;
     if (a.window > 0) return false;
     // causal: only the bottom-right aligned short chunk (decode / speculative verification / chunked prefill against a

@@ -14,6 +14,7 @@
 #include "fa_device.h"
 #include "fa_fwd_plan.h"
 #include "fa_kernels.h"
+#include "fa_switches.h"
 #include "fa_fwd_tile.h"
 
 namespace aule_hip {
@@ -103,26 +104,8 @@ __host__ __device__ inline void split_range(const SplitPair& r, int j, int which
     }
 }
 
-// AULE_HIP_FWD_SPLIT=<n>: at most n pieces per pair; 0 (or 1) turns the path off (A/B measurements)
-inline int split_max_pieces() {
-    static const int v = [] {
-        const char* e = getenv("AULE_HIP_FWD_SPLIT");
-        if (e == nullptr || e[0] < '0' || e[0] > '9') return kMaxPieces;
-        const int n = atoi(e);
-        return n < kMaxPieces ? n : kMaxPieces;
-    }();
-    return v;
-}
-
-// AULE_HIP_FWD_SPLIT_MIN=<tiles>: the shortest piece (A/B; default kSplitMinTiles)
-inline int split_min_tiles() {
-    static const int v = [] {
-        const char* e = getenv("AULE_HIP_FWD_SPLIT_MIN");
-        const int n = (e != nullptr && e[0] >= '0' && e[0] <= '9') ? atoi(e) : kSplitMinTiles;
-        return n < 4 ? 4 : n;
-    }();
-    return v;
-}
+// AULE_HIP_FWD_SPLIT=<n>: at most n pieces per pair, 0 (or 1) turns the path off; AULE_HIP_FWD_SPLIT_MIN=<tiles>: the shortest piece (A/B)
+static_assert(Switches{}.fwd_split == kMaxPieces && Switches{}.fwd_split_min == kSplitMinTiles, "the defaults of fa_switches.h");
 
 inline SplitPlan split_plan(const FwdArgs& a, int slots) {
     SplitPlan s{};
@@ -135,8 +118,9 @@ inline SplitPlan split_plan(const FwdArgs& a, int slots) {
     // D = 64: a piece costs a prologue, a partial row per query and its share of the merge launch.
     const int T = split_tiles(s.nqb - 1, a.Sk, pcoff) + (a.causal && s.nqb > 1 ? split_tiles(0, a.Sk, pcoff) : 0);
     long long n = slots / (pairs > 0 ? pairs : 1);
-    n = n < split_max_pieces() ? n : split_max_pieces();
-    n = n < T / split_min_tiles() ? n : T / split_min_tiles();
+    const int most = switches().fwd_split, least = switches().fwd_split_min;
+    n = n < most ? n : most;
+    n = n < T / least ? n : T / least;
     // Two pieces that fill the chip need twice the length: going from half the CUs to all of them the busy ones lose ~a quarter of
     // their clock (the socket's power limit, profiles/r4_power_trace.txt), so 2 x 18 tiles on 256 workgroups is SLOWER than 36 on 128
     // once a piece's prologue, its partial rows and the merge launch are paid (round 4, one-wave-per-SIMD kernel, same box: B1 32q/8kv

@@ -34,6 +34,7 @@
 #include "fa_device.h"
 #include "fa_fwd_plan.h"
 #include "fa_kernels.h"
+#include "fa_switches.h"
 
 namespace aule_hip {
 namespace {
@@ -292,11 +293,8 @@ int for_dtype_d(int dtype, int D, F&& f) {
 // C5c 29.8 -> 36.2 us).  `by_count` = false: the workgroup-per-row kernel whatever the count.
 template <class T, int D>
 int launch_combine(const SplitParams& p, bool by_count, hipStream_t stream) {
-    static const int lean = [] {   // AULE_HIP_FWD_COMBINE=wg selects the workgroup-per-row kernel (A/B measurements)
-        const char* e = getenv("AULE_HIP_FWD_COMBINE");
-        return (e != nullptr && e[0] == 'w') ? 0 : 1;
-    }();
-    if (by_count && lean && p.npart <= 16)
+    // (AULE_HIP_FWD_COMBINE=wg selects the workgroup-per-row kernel: A/B measurements)
+    if (by_count && !switches().fwd_combine_wg && p.npart <= 16)
         hipLaunchKernelGGL((fa_fwd_splitkv_combine_rows<T, D>), dim3((unsigned)((p.rows_total + 3) / 4)), dim3(256), 0, stream, p);
     else
         hipLaunchKernelGGL((fa_fwd_splitkv_combine<T, D>), dim3((unsigned)p.rows_total), dim3(256), 0, stream, p);

@@ -1189,15 +1189,6 @@ constexpr auto w4_kernel() {
 
 #pragma clang diagnostic pop
 
-// AULE_HIP_W4_BODIES=generic: the round-3 flow (generic bodies for step 0 and the masked steps, requests as separate statements)
-static int w4_generic_bodies() {
-    static const int v = [] {
-        const char* e = std::getenv("AULE_HIP_W4_BODIES");
-        return (e != nullptr && e[0] == 'g') ? 1 : 0;
-    }();
-    return v;
-}
-
 template <class T, int D, bool TL = false>
 int launch_w4(const FwdArgs& a, const W4Grid& g, hipStream_t stream, unsigned long long* dbg = nullptr) {
     FwdW4Params p;
@@ -1211,21 +1202,11 @@ int launch_w4(const FwdArgs& a, const W4Grid& g, hipStream_t stream, unsigned lo
     p.coff = a.causal ? a.coff : 0;
     p.dbg = dbg;
     p.npiece = 1; p.pcoff = 0; p.magic = 0; p.part = nullptr; p.part_rows = 0;
-    p.generic = w4_generic_bodies();
+    p.generic = switches().w4_generic_bodies;   // AULE_HIP_W4_BODIES=generic: the round-3 flow (generic bodies for step 0 and the masked steps, requests as separate statements)
     p.window = a.window > 0 ? a.window : 0;
-    {   // AULE_HIP_W4_WTAIL=<n> (A/B; default 4: profiles/r6_window_shapes.txt)
-        static const int wt = [] {
-            const char* e = std::getenv("AULE_HIP_W4_WTAIL");
-            return (e != nullptr && e[0] >= '0' && e[0] <= '9') ? std::atoi(e) : 4;
-        }();
-        p.wtail_min = wt;
-        // (AULE_HIP_W4_SUMLO=<x>: A/B of the verdict's lower bound)
-        static const float sl = [] {
-            const char* e = std::getenv("AULE_HIP_W4_SUMLO");
-            return e != nullptr ? (float)std::atof(e) : -1.0f;
-        }();
-        p.sum_lo = sl >= 0.f ? sl : ((p.window > 0 && a.dtype != kBF16) ? 0.5f : 0x1p-100f);
-    }
+    p.wtail_min = switches().w4_wtail;   // AULE_HIP_W4_WTAIL=<n> (A/B; default 4: profiles/r6_window_shapes.txt)
+    const float sl = switches().w4_sumlo;   // (AULE_HIP_W4_SUMLO=<x>: A/B of the verdict's lower bound)
+    p.sum_lo = sl >= 0.f ? sl : ((p.window > 0 && a.dtype != kBF16) ? 0.5f : 0x1p-100f);
     p.rcos = a.rope_cos; p.rsin = a.rope_sin;
     p.rrows = a.rope_rows; p.rpitch = a.rope_pitch; p.rpos = a.rope_pos;
     const dim3 grid((unsigned)g.G), block(256);
@@ -1256,7 +1237,7 @@ int launch_w4_split(const FwdArgs& a, const SplitPlan& s, hipStream_t stream) {
     p.npiece = s.n; p.pcoff = a.causal ? a.coff : kEverything; p.magic = split_magic(s.n);
     p.part = static_cast<float*>(ws.ptr);
     p.part_rows = a.B * a.Hq * a.Sq;
-    p.generic = w4_generic_bodies();
+    p.generic = switches().w4_generic_bodies;
     p.window = 0; p.wtail_min = 0; p.sum_lo = 0x1p-100f;
     const size_t lds = w4_lds_bytes<D>();
     if (a.causal)
@@ -1291,13 +1272,9 @@ bool fwd_w4_applicable(const FwdArgs& a) {
     if (a.window > 0) {
         // sliding window (round 6, WIN instances): causal, every query with its own diagonal key inside Sk (no row without a visible key: the
         // references are taken from real scores), tile indices that fit the part table's 16 bits; AULE_HIP_W4_WINDOW=0: the ping-pong kernel (A/B)
-        static const int on = [] {
-            const char* e = std::getenv("AULE_HIP_W4_WINDOW");
-            return (e != nullptr && e[0] == '0') ? 0 : 1;
-        }();
         // (windows shorter than two key tiles stay where they were: a wave would see two or three tiles of a five-tile part, and a tile could be
         // cut by the window's left edge AND the diagonal -- the streams carry no mask variant with both bounds)
-        if (!on || !a.causal || a.window < 2 * kKVTile || a.coff < 0 || (long long)a.Sq + a.coff > a.Sk || (long long)a.Sk >= 65535LL * kKVTile) return false;
+        if (!switches().w4_window || !a.causal || a.window < 2 * kKVTile || a.coff < 0 || (long long)a.Sq + a.coff > a.Sk || (long long)a.Sk >= 65535LL * kKVTile) return false;
     }
     if (a.rope_cos != nullptr) {   // fused query rotation: table geometry the 32-bit row offsets of the requests can address
         if (a.rope_sin == nullptr || a.rope_pitch < a.D / 2 || (a.rope_pitch & 3) != 0) return false;
@@ -1324,7 +1301,7 @@ bool fwd_w4_applicable(const FwdArgs& a) {
 
 // Small grids the forward cuts along the keys (route 7), and the plan of the cut (written to `s` only then).
 bool fwd_w4_split_plan(const FwdArgs& a, SplitPlan& s) {
-    if (split_max_pieces() < 2 || a.rope_cos != nullptr || a.window > 0 || !fwd_w4_applicable(a)) return false;
+    if (switches().fwd_split < 2 || a.rope_cos != nullptr || a.window > 0 || !fwd_w4_applicable(a)) return false;
     if ((long long)a.Sk >= 65535LL * kKVTile) return false;                               // tile indices are 16-bit in the part table
     if ((long long)a.Sq * (a.D + kPartPad) * 4 >= (1LL << 32)) return false;              // partial rows of a head: 32-bit offsets
     const SplitPlan plan = split_plan(a, device_cu_count(a.device));
@@ -1341,10 +1318,7 @@ W4Grid fwd_w4_grid(const FwdArgs& a) {
     // Half-empty causal grids (round 5; the reference harness's B 1 H 32 S 2048: 128 pairs on 256 CUs): when every Q block can have
     // a CU of its own, the blocks are NOT paired -- the launch then lasts as long as its largest block (32 tiles + one part's seam
     // instead of a pair's 36 tiles + two), on a chip that is ~56 % busy on average.  AULE_HIP_W4_UNPAIR=0 keeps the pairs (A/B).
-    static const int unpair = [] {
-        const char* e = std::getenv("AULE_HIP_W4_UNPAIR");
-        return (e != nullptr && e[0] == '0') ? 0 : 1;
-    }();
+    const bool unpair = switches().w4_unpair;
     // (a sliding window: every block's part has about W / 64 + 4 tiles -- nothing to balance by pairing)
     g.pair = a.causal && !(window > 0 || (unpair && nqb >= 2 && (long long)nqb * a.B * a.Hq <= ncu)) ? 1 : 0;
     g.nwork = g.pair ? (nqb + 1) / 2 : nqb;
@@ -1356,9 +1330,9 @@ W4Grid fwd_w4_grid(const FwdArgs& a) {
     g.rounds = 0;
     g.mper = 1;
     // round order (w4_body): needs whole rounds -- W a multiple of the heads' Q blocks -- and an even number of them
-    static const char* const order = std::getenv("AULE_HIP_W4_ORDER");   // "pairs": the item order everywhere (A/B)
+    const bool item_order = switches().w4_order_pairs;   // AULE_HIP_W4_ORDER=pairs: the item order everywhere (A/B)
     const int units = a.B * a.Hkv, W = (int)(G / 8), hg = a.Hq / a.Hkv;
-    if (a.causal && window == 0 && !(order != nullptr && order[0] == 'p') && G == ncu && (G & 7) == 0 && (units & 7) == 0 && nqb <= W && W % nqb == 0) {
+    if (a.causal && window == 0 && !item_order && G == ncu && (G & 7) == 0 && (units & 7) == 0 && nqb <= W && W % nqb == 0) {
         const int m = W / nqb, hx = units / 8 * hg;
         if (hx % (2 * m) == 0 && hx / m <= kW4MaxSlot) {
             g.rounds = hx / m;

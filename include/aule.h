@@ -415,6 +415,11 @@ int32_t aule_hip_debug_forward_split_plan(const aule_attn_desc* desc, int32_t* o
 /* Debug: the work item of workgroup `bid` of a grid of batch * heads_q * nblk workgroups -- out4 = {batch, kv head, q head,  */
 /* block}.  ranked = 0: unit by unit (flag: last block first), the 16-bit kernels; ranked = 1: block rank by block rank over  */
 /* all units (flag: descending), the fp32 kernels.  Host logic only; -3 on a bad argument.                                    */
+/* Debug: the run-time switches the library resolved from this process's environment (docs/SWITCHES.md; read once, on first use) as     */
+/* text, one line per switch: NAME=<value>\n with stable words (auto|recompute|spill, default|old|new, default|pp, integers, ...); an    */
+/* unset or unrecognised setting prints as the default it resolves to.  Writes at most cap bytes (NUL-terminated) and returns the bytes   */
+/* the whole text needs, NUL included.  No lock, no device, no aule_init().                                                               */
+uint64_t aule_hip_debug_switches(char* buf, uint64_t cap);
 int32_t aule_hip_debug_work_order(int32_t ranked, int32_t bid, int32_t batch, int32_t heads_q, int32_t heads_kv, int32_t nblk, int32_t flag, int32_t* out4);
 
 /* ---- Direct peer exchange between the per-GPU processes of one node (additive; no counterpart in the reference, which  */

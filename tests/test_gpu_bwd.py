@@ -281,18 +281,14 @@ def test_backward_on_the_one_wave_per_simd_kernels(which):
     import subprocess
     import sys
     from conftest import ROOT
-    e = dict(os.environ)
     if which == "spill":
-        e["AULE_HIP_BWD_DKV"] = "new"
-        e["AULE_HIP_BWD_MODE"] = "spill"
+        leg = {"AULE_HIP_BWD_DKV": "new", "AULE_HIP_BWD_MODE": "spill"}
     elif which in ("k2", "k1"):
-        e["AULE_HIP_BWD_MODE"] = "recompute"
-        e["AULE_HIP_BWD_DKV"] = e["AULE_HIP_BWD_DQ"] = "new"
-        e["AULE_HIP_BWD_DKV_K2"] = "1" if which == "k2" else "0"
+        leg = {"AULE_HIP_BWD_MODE": "recompute", "AULE_HIP_BWD_DKV": "new", "AULE_HIP_BWD_DQ": "new", "AULE_HIP_BWD_DKV_K2": "1" if which == "k2" else "0"}
     else:
-        e["AULE_HIP_BWD_MODE"] = "recompute"
-        e["AULE_HIP_BWD_DKV"] = which
-        e["AULE_HIP_BWD_DQ"] = which
+        leg = {"AULE_HIP_BWD_MODE": "recompute", "AULE_HIP_BWD_DKV": which, "AULE_HIP_BWD_DQ": which}
+    e = dict(os.environ)
+    e.update(leg)
     # (round 5: the one-wave-per-SIMD pair takes causal sliding windows too -- the window suite rides along in every leg)
     # (round 6: a leg runs what its switches can change -- the forward-only tests of the window file stay out (one of them is a child suite of its
     # own), the k2 / k1 legs keep to the cases with a 64 in their id (every D = 64 case, and some more), the predecessor leg to the backward file: the
@@ -303,7 +299,10 @@ def test_backward_on_the_one_wave_per_simd_kernels(which):
     sel = "not one_wave_per_simd and not ping_pong_route and not large_logits and not negative_scale and not goldens and not c_abi and not two_rounds"
     if which in ("k2", "k1"):
         sel += " and 64"
-    r = subprocess.run([sys.executable, "-m", "pytest"] + files + ["-q", "-x", "-m", "gpu", "-k", sel], env=e, capture_output=True, text=True, timeout=1500, cwd=ROOT)
+    # (the child's first step: the leg's switches are what the library resolved -- a misspelt one would be the default route)
+    import json
+    from util import LEG_CHILD
+    r = subprocess.run([sys.executable, "-c", LEG_CHILD, ROOT, json.dumps(leg)] + files + ["-q", "-x", "-m", "gpu", "-k", sel], env=e, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0 and "passed" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
 
 

@@ -29,7 +29,8 @@ sys.path.insert(0, os.path.join(%(root)r, "aule-attention_amd")); sys.path.inser
 import numpy as np, torch
 import oracle
 from aule import _torch as at
-from util import fwd_tol, LSE_TOL
+from util import fwd_tol, LSE_TOL, assert_switches
+assert_switches(json.loads(sys.argv[1]))   # the leg's switches are what the library resolved
 res = []
 cases = [  # B, Hq, Hkv, Sq, Sk, causal, magnitude, spike
     (1, 2, 2, 64, 64, True, 1.0, 0), (1, 2, 2, 300, 300, True, 1.0, 0), (2, 4, 1, 1024, 1024, True, 1.0, 0),
@@ -66,7 +67,7 @@ print("RESULT " + json.dumps(res))
 def test_forward_variant_matches_oracle(env):
     e = dict(os.environ)
     e.update(env)
-    r = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}], env=e, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}, json.dumps(env)], env=e, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
     for c in json.loads(line[7:]):
@@ -75,9 +76,11 @@ def test_forward_variant_matches_oracle(env):
 
 _BODIES_CHILD = r'''
 import hashlib, json, math, os, sys
-sys.path.insert(0, os.path.join(%(root)r, "aule-attention_amd"))
+sys.path.insert(0, os.path.join(%(root)r, "aule-attention_amd")); sys.path.insert(0, os.path.join(%(root)r, "tests"))
 import torch
 from aule import _torch as at
+from util import assert_switches
+assert_switches({"AULE_HIP_W4_BODIES": sys.argv[1]})   # the leg's switch is what the library resolved
 CASES = [  # dtype, B, Hq, Hkv, Sq, Sk, D, causal  -- every geometry of the embedded-request flow: short / long parts, ragged, pairs,
            # bottom-right aligned and not, Sq > Sk, GQA, D = 64, small grids (key-range split), no mask at all
     ("bf16", 1, 2, 2, 256, 256, 128, True), ("bf16", 1, 2, 2, 300, 300, 128, True), ("bf16", 2, 4, 1, 1024, 1024, 128, True),
@@ -124,7 +127,7 @@ def test_embedded_request_bodies_are_bit_identical_to_the_generic_ones():
         e = {k: v for k, v in os.environ.items() if k != "AULE_HIP_W4_BODIES"}
         if bodies:
             e["AULE_HIP_W4_BODIES"] = bodies
-        r = subprocess.run([sys.executable, "-c", _BODIES_CHILD % {"root": ROOT}], env=e, capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, "-c", _BODIES_CHILD % {"root": ROOT}, bodies or "default"], env=e, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         res.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:]))
     assert res[0].keys() == res[1].keys() and len(res[0]) >= 30

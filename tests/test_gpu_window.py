@@ -187,7 +187,10 @@ def test_window_suite_on_the_ping_pong_route():
     import sys
     e = dict(os.environ)
     e["AULE_HIP_W4_WINDOW"] = "0"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-m", "gpu", "-k",
+    # (the child's first step: the switch is what the library resolved)
+    from conftest import ROOT
+    from util import LEG_CHILD
+    r = subprocess.run([sys.executable, "-c", LEG_CHILD, ROOT, '{"AULE_HIP_W4_WINDOW": "0"}', os.path.abspath(__file__), "-x", "-q", "-m", "gpu", "-k",
                         "forward_backward_vs_oracle or goldens or large_logits"], env=e, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
 

@@ -84,3 +84,35 @@ def assert_close(got, ref, atol, rtol, what=""):
             f"{what}: {int(bad.sum())}/{bad.size} elements out of tolerance; worst at {idx}: "
             f"got {got[idx]:.6g} ref {ref[idx]:.6g} |err| {err[idx]:.3g} > {bound[idx]:.3g}; "
             f"max|err| {err.max():.3g}")
+
+
+def switches_in_force():
+    """{name: resolved value} of the library's run-time switches in THIS process (aule_hip_debug_switches; no GPU, no aule_init)."""
+    import ctypes
+    from aule import _capi
+    lib = _capi.load()
+    need = int(lib.aule_hip_debug_switches(None, 0))
+    buf = ctypes.create_string_buffer(need)
+    assert int(lib.aule_hip_debug_switches(buf, need)) == need
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
+
+
+def assert_switches(want):
+    """The first step of a child process that runs a forced leg: the leg's AULE_* settings are what the library resolved (a misspelt
+    name or value would silently be the default route, and the leg would pass while testing something else).  `want`: {name: word}."""
+    got = switches_in_force()
+    bad = {k: (v, got.get(k)) for k, v in want.items() if got.get(k) != v}
+    assert not bad, "switches not in force (name: wanted, resolved): %r" % (bad,)
+
+
+# A forced leg of a whole test file: a child that asserts its switches through the hook, then runs pytest with the arguments behind them.
+#   subprocess.run([sys.executable, "-c", LEG_CHILD, ROOT, json.dumps(want)] + pytest_args, env=...)
+LEG_CHILD = r'''
+import json, os, sys
+sys.path[:0] = [os.path.join(sys.argv[1], "aule-attention_amd"), os.path.join(sys.argv[1], "tests")]
+import torch   # (first: the library binds to the HIP runtime torch brings)
+from util import assert_switches
+assert_switches(json.loads(sys.argv[2]))
+import pytest
+sys.exit(pytest.main(sys.argv[3:]))
+'''
