@@ -165,7 +165,7 @@ def flash_attention_paged_query(q, k_cache, v_cache, block_tables, context_lens,
     query at a negative position (a sequence shorter than seq_q) gives a row of zeros.  Returns [batch, heads_q, seq_q,
     head_dim], or (out, lse) with return_lse=True: lse [batch, heads_q, seq_q] fp32, the natural log of the sum of
     exp(scaled score) over the visible keys (-inf where there is none).  seq_q = 1 equals flash_attention_paged_amd bit for
-    bit.  Out of scope: seq_q > 64, per-sequence query lengths, head_dim 256.  Argument errors are ValueErrors raised before
+    bit.  seq_q > 64 and per-sequence query lengths: flash_attention_paged_prefill.  Out of scope: head_dim 256.  Argument errors are ValueErrors raised before
     the device is touched; CPU tensors raise AuleError."""
     try:
         import torch  # noqa: F401
@@ -174,6 +174,40 @@ def flash_attention_paged_query(q, k_cache, v_cache, block_tables, context_lens,
     from ._torch import paged_query
     return paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=scale, window_size=window_size,
                        k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
+
+
+def flash_attention_paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None,
+                                  window_size=-1, k_scale=None, v_scale=None, return_lse=False):
+    """PagedAttention for a ragged batch: every sequence brings its own number of new tokens (a prompt chunk behind a cached
+    prefix, next to a short verify, next to plain decodes) -- the step of a continuous-batching engine, in one launch and
+    without gathering the pages.  Not in the reference.
+
+        q [total_tokens, heads_q, head_dim] fp16 / bf16: the new tokens of all sequences packed along the first axis (last
+          dimension contiguous, token stride free: a slice of a fused QKV projection is read in place);
+        k_cache, v_cache, block_tables, k_scale, v_scale as in flash_attention_paged_query (16-bit or float8_e4m3fn caches);
+        context_lens [batch]: the keys in the cache INCLUDING the new tokens -- append them first (paged_kv_append);
+        cu_seqlens_q [batch + 1] int32: sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 of q and of the result;
+        max_seqlen_q: the largest number of new tokens of a sequence.  None computes it from cu_seqlens_q with one
+          device->host synchronisation; passing it keeps the call free of synchronisation and capturable into a graph (a
+          replay then reads the current contents of cu_seqlens_q, context_lens and block_tables).
+
+    Token i of sequence b (n_b new tokens, L_b keys) sits at position p = L_b - n_b + i and sees key j iff j <= p, and with
+    window_size = W > 0 iff also p - j < W: the rule of flash_attention(causal="bottom-right") on the gathered K / V.  All
+    per-sequence values are clamped on the device (lengths to what the block table addresses, offsets to total_tokens, n_b
+    to max_seqlen_q), so a stale value cannot index outside a buffer.  A token at a negative position gives a row of zeros
+    (lse -inf); rows that belong to no sequence (a tail padded for graph capture) are never written.  Returns
+    [total_tokens, heads_q, head_dim], or (out, lse) with return_lse=True: lse [total_tokens, heads_q] fp32, the natural log
+    of the sum of exp(scaled score) over the visible keys.  Out of scope: head_dim 256; key-range splits -- a batch made
+    only of single-token sequences at very long context is better served by flash_attention_paged_amd /
+    flash_attention_paged_query; a backward pass.  Argument errors are ValueErrors raised before the device is touched; CPU
+    tensors raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_prefill
+    return paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=max_seqlen_q, scale=scale,
+                         window_size=window_size, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
 
 
 def quantize_kv_cache_fp8(cache, per_head=True):
@@ -403,7 +437,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

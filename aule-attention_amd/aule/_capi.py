@@ -122,6 +122,38 @@ class PagedQueryDesc(ctypes.Structure):
     ]
 
 
+class PagedPrefillDesc(ctypes.Structure):
+    """struct aule_paged_prefill_desc (include/aule.h): ragged per-sequence queries against the paged cache."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("cache_dtype", ctypes.c_int32),
+        ("batch", ctypes.c_uint32),
+        ("heads_q", ctypes.c_uint32),
+        ("heads_kv", ctypes.c_uint32),
+        ("head_dim", ctypes.c_uint32),
+        ("block_size", ctypes.c_uint32),
+        ("max_blocks", ctypes.c_uint32),
+        ("total_tokens", ctypes.c_uint32),
+        ("max_seqlen_q", ctypes.c_uint32),
+        ("scale", ctypes.c_float),
+        ("window_size", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("q_token_stride", ctypes.c_int64),
+        ("stream", ctypes.c_void_p),
+        ("q", ctypes.c_void_p),
+        ("k_cache", ctypes.c_void_p),
+        ("v_cache", ctypes.c_void_p),
+        ("block_tables", ctypes.c_void_p),
+        ("context_lens", ctypes.c_void_p),
+        ("cu_seqlens_q", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p),
+        ("k_scale", ctypes.c_void_p),
+        ("v_scale", ctypes.c_void_p),
+    ]
+
+
 class RopeDesc(ctypes.Structure):
     """struct aule_rope_desc (include/aule.h)."""
     _fields_ = [
@@ -250,6 +282,7 @@ SIGNATURES = [
     ("aule_attention_paged_decode_fp8_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedFp8Desc)]),
     ("aule_attention_paged_query_ex", _I32, [ctypes.POINTER(PagedQueryDesc)]),
     ("aule_attention_paged_query_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedQueryDesc)]),
+    ("aule_attention_paged_prefill_ex", _I32, [ctypes.POINTER(PagedPrefillDesc)]),
     ("aule_peer_alloc", _I32, [_I32, _U64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(IpcHandle)]),
     ("aule_peer_free", _I32, [_I32, ctypes.c_void_p]),
     ("aule_peer_open", _I32, [_I32, ctypes.POINTER(IpcHandle), ctypes.POINTER(ctypes.c_void_p)]),

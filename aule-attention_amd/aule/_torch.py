@@ -409,6 +409,7 @@ def _paged_cache_is_fp8(op, inputs, k_cache, v_cache, k_scale, v_scale):
         "decode": ("paged decode", "the FP8 paged decode takes", "query and caches", "an fp16 / bf16 query", "paged decode"),
         "append": ("paged KV append", "the paged KV append writes", "key, value and caches", "fp16 / bf16 key and value", "the paged KV cache"),
         "query": ("paged query", "the FP8 paged query takes", "query and caches", "an fp16 / bf16 query", "the paged query"),
+        "prefill": ("paged prefill", "the FP8 paged prefill takes", "query and caches", "an fp16 / bf16 query", "the paged prefill"),
     }[op]
     if k_cache.dtype != v_cache.dtype:
         raise ValueError(f"k_cache ({k_cache.dtype}) and v_cache ({v_cache.dtype}) must have the same dtype")
@@ -522,7 +523,7 @@ def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, win
         raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
     if not 1 <= Sq <= PAGED_QUERY_MAX_TOKENS:
         raise ValueError(f"the paged query takes 1 to {PAGED_QUERY_MAX_TOKENS} query tokens per sequence, got {Sq} "
-                         "(longer chunks: gather the pages and call flash_attention(causal='bottom-right'))")
+                         "(longer chunks and per-sequence lengths: flash_attention_paged_prefill)")
     fp8 = _paged_cache_is_fp8("query", (q,), k_cache, v_cache, k_scale, v_scale)
     if block_size == 0:
         raise ValueError("block_size must be positive")
@@ -566,6 +567,95 @@ def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, win
         vs = _fp8_scale(v_scale, Hkv, q.device, "v_scale")
         d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
     _capi.check(lib.aule_attention_paged_query_ex(ctypes.byref(d)), "aule_attention_paged_query_ex")
+    return (out, lse) if return_lse else out
+
+
+def paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None, window_size=-1,
+                  k_scale=None, v_scale=None, return_lse=False):
+    """Paged prefill: ragged per-sequence queries against the paged KV cache (the step of a continuous-batching engine: a
+    prompt chunk behind a cached prefix next to a short verify next to plain decodes); csrc/fa_fwd_paged_prefill_gfx950.hip
+    behind aule_attention_paged_prefill_ex:
+
+        q            [total_tokens, heads_q, head_dim] fp16 / bf16: the new tokens of all sequences packed along the first axis.
+                     The token stride is free (a slice of a fused QKV projection is read in place) as long as it and the storage
+                     offset are multiples of 8 elements; a q whose heads are not contiguous is copied.
+        k_cache, v_cache, block_tables, context_lens, k_scale, v_scale: as in paged_query (16-bit or float8_e4m3fn caches)
+        cu_seqlens_q [batch + 1] int32: sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1
+        max_seqlen_q the largest number of new tokens of a sequence (sizes the grid; a longer sequence is cut to it).  None
+                     reads it from cu_seqlens_q with ONE device->host synchronisation; pass it to keep the call free of
+                     synchronisation and capturable into a graph.
+    context_lens[b] counts the keys in the cache INCLUDING the new tokens (append them first: paged_kv_append).  With L_b, s_b
+    and n_b the values clamped on the device (include/aule.h), token i of sequence b is row s_b + i, sits at position
+    p = L_b - n_b + i and sees key j iff j <= p, and with window_size = W > 0 iff also p - j < W.  A token with p < 0 gives a
+    row of zeros and lse = -inf.  Rows that belong to no sequence are never written: out (and lse) come from torch.empty.
+    Returns out [total_tokens, heads_q, head_dim], or (out, lse) with lse [total_tokens, heads_q] fp32 when return_lse is
+    set.  All argument errors are ValueErrors raised before the device is touched."""
+    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError("expected q [T,Hq,D] and k_cache/v_cache [num_blocks, block_size, Hkv, D]")
+    T, Hq, D = q.shape
+    _, block_size, Hkv, Dk = k_cache.shape
+    if Dk != D:
+        raise ValueError(f"head_dim mismatch: query={D}, cache={Dk}")
+    if Hkv == 0 or Hq % Hkv != 0:
+        raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
+    fp8 = _paged_cache_is_fp8("prefill", (q,), k_cache, v_cache, k_scale, v_scale)
+    if block_size == 0:
+        raise ValueError("block_size must be positive")
+    if block_tables.dim() != 2 or block_tables.shape[1] == 0 or context_lens.dim() != 1 or context_lens.shape[0] != block_tables.shape[0]:
+        raise ValueError("block_tables must be [batch, max_blocks] and context_lens [batch]")
+    B = block_tables.shape[0]
+    if not torch.is_tensor(cu_seqlens_q) or cu_seqlens_q.shape != (B + 1,):
+        raise ValueError(f"cu_seqlens_q must be a [batch + 1] = [{B + 1}] tensor")
+    if cu_seqlens_q.dtype != torch.int32:
+        raise ValueError(f"cu_seqlens_q must be int32 (it is read on the device as it stands), got {cu_seqlens_q.dtype}")
+    if max_seqlen_q is not None and (isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 1):
+        raise ValueError(f"max_seqlen_q must be a positive int or None, got {max_seqlen_q!r}")
+    if fp8:
+        for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if torch.is_tensor(s) and not (s.dim() == 0 or s.shape == (1,) or s.shape == (Hkv,)):
+                raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
+    if T > 1 and (q.stride(2) != 1 or q.stride(1) != D) or T <= 1 and not q.is_contiguous():
+        q = q.contiguous()
+    q_stride = q.stride(0) if T > 1 else Hq * D
+    if q_stride < Hq * D or q_stride % 8 != 0 or q.storage_offset() % 8 != 0:
+        raise ValueError(f"q's token stride ({q_stride}) and storage offset ({q.storage_offset()}) must be multiples of 8 elements "
+                         f"and the stride at least heads_q * head_dim = {Hq * D} (16-byte loads); pass q.contiguous()")
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): the paged prefill needs ROCm device tensors; there is no CPU fallback")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    lib = _capi.get_lib()
+    k_cache, v_cache = k_cache.contiguous(), v_cache.contiguous()
+    _same_device("paged prefill", q, k_cache, v_cache)
+    bt = block_tables.to(device=q.device, dtype=torch.int32).contiguous()
+    cl = context_lens.to(device=q.device, dtype=torch.int32).contiguous()
+    cu = cu_seqlens_q.to(device=q.device).contiguous()
+    if max_seqlen_q is None:
+        # the one documented synchronisation
+        max_seqlen_q = max(int((cu[1:] - cu[:-1]).max().item()), 1) if B > 0 else 1
+    out = torch.empty((T, Hq, D), device=q.device, dtype=q.dtype)
+    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
+    if T * B * Hq == 0:
+        return (out, lse) if return_lse else out
+    d = _capi.PagedPrefillDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    d.batch, d.heads_q, d.heads_kv, d.head_dim = B, Hq, Hkv, D
+    d.block_size, d.max_blocks = block_size, bt.shape[1]
+    d.total_tokens, d.max_seqlen_q, d.q_token_stride = T, min(max_seqlen_q, T), q_stride
+    d.scale = _abi_scale(scale)
+    d.window_size = _window_arg(window_size)
+    d.device = _device_index(q.device)
+    d.stream = _stream_ptr(q.device)
+    d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
+    d.lse = lse.data_ptr() if lse is not None else None
+    d.block_tables, d.context_lens, d.cu_seqlens_q = bt.data_ptr(), cl.data_ptr(), cu.data_ptr()
+    if fp8:
+        ks = _fp8_scale(k_scale, Hkv, q.device, "k_scale")
+        vs = _fp8_scale(v_scale, Hkv, q.device, "v_scale")
+        d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
+    _capi.check(lib.aule_attention_paged_prefill_ex(ctypes.byref(d)), "aule_attention_paged_prefill_ex")
     return (out, lse) if return_lse else out
 
 

@@ -45,6 +45,18 @@ static_assert(sizeof(aule_paged_query_desc) == 152 && offsetof(aule_paged_query_
                   offsetof(aule_paged_query_desc, v_scale) == 128 && offsetof(aule_paged_query_desc, lse) == 136 &&
                   offsetof(aule_paged_query_desc, seq_q) == 144 && offsetof(aule_paged_query_desc, cache_dtype) == 148,
               "aule_paged_query_desc layout is part of the ABI");
+static_assert(sizeof(aule_paged_prefill_desc) == 152 && offsetof(aule_paged_prefill_desc, cache_dtype) == 8 &&
+                  offsetof(aule_paged_prefill_desc, batch) == 12 && offsetof(aule_paged_prefill_desc, block_size) == 28 &&
+                  offsetof(aule_paged_prefill_desc, max_blocks) == 32 && offsetof(aule_paged_prefill_desc, total_tokens) == 36 &&
+                  offsetof(aule_paged_prefill_desc, max_seqlen_q) == 40 && offsetof(aule_paged_prefill_desc, scale) == 44 &&
+                  offsetof(aule_paged_prefill_desc, window_size) == 48 && offsetof(aule_paged_prefill_desc, device) == 52 &&
+                  offsetof(aule_paged_prefill_desc, q_token_stride) == 56 && offsetof(aule_paged_prefill_desc, stream) == 64 &&
+                  offsetof(aule_paged_prefill_desc, q) == 72 && offsetof(aule_paged_prefill_desc, k_cache) == 80 &&
+                  offsetof(aule_paged_prefill_desc, v_cache) == 88 && offsetof(aule_paged_prefill_desc, block_tables) == 96 &&
+                  offsetof(aule_paged_prefill_desc, context_lens) == 104 && offsetof(aule_paged_prefill_desc, cu_seqlens_q) == 112 &&
+                  offsetof(aule_paged_prefill_desc, out) == 120 && offsetof(aule_paged_prefill_desc, lse) == 128 &&
+                  offsetof(aule_paged_prefill_desc, k_scale) == 136 && offsetof(aule_paged_prefill_desc, v_scale) == 144,
+              "aule_paged_prefill_desc layout is part of the ABI");
 static_assert(offsetof(aule_paged_query_desc, q) == offsetof(aule_paged_fp8_desc, q) &&
                   offsetof(aule_paged_query_desc, workspace_bytes) == offsetof(aule_paged_fp8_desc, workspace_bytes) &&
                   offsetof(aule_paged_query_desc, v_scale) == offsetof(aule_paged_fp8_desc, v_scale) &&
@@ -1001,6 +1013,83 @@ int32_t aule_attention_paged_query_ex(const aule_paged_query_desc* d) {
     rc = aule_hip::launch_paged_query(a, (hipStream_t)d->stream);
     if (rc != 0) {
         set_error("Paged query attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
+        return -4;
+    }
+    return 0;
+}
+
+// The paged prefill: a descriptor of its own (no workspace, packed ragged queries).  One checker, one reader; its only reader is
+// the launch entry, so the pointer rules of a call that has something to do are stated here too.  Host logic only, and the entry
+// asks it before it needs the device.
+static bool paged_prefill_nothing_to_do(const aule_paged_prefill_desc* d) {
+    return d->total_tokens == 0 || (uint64_t)d->batch * d->heads_q == 0;
+}
+
+static const char* paged_prefill_desc_error(const aule_paged_prefill_desc* d, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_paged_prefill_desc)) return kBadDescriptor;
+    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return "dtype (of q / out) must be fp16 or bf16";
+    if (d->cache_dtype != AULE_KV_CACHE_SAME && d->cache_dtype != AULE_KV_CACHE_FP8_E4M3)
+        return "cache_dtype must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3";
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return reasonf(why, "head_dim %u unsupported (32, 64 or 128)", d->head_dim);
+    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0)
+        return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
+    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return "bad block_size / max_blocks";
+    if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
+    if (d->q_token_stride < (int64_t)d->heads_q * d->head_dim)
+        return reasonf(why, "q_token_stride (%lld) is smaller than a token (heads_q * head_dim = %llu elements)", (long long)d->q_token_stride,
+                       (unsigned long long)d->heads_q * d->head_dim);
+    if (d->q_token_stride % 8 != 0) return reasonf(why, "q_token_stride (%lld) must be a multiple of 8 elements (16-byte loads)", (long long)d->q_token_stride);
+    if (d->batch >= (1u << 30) || d->total_tokens >= (1u << 30)) return "batch / total_tokens too large";
+    if (((uint64_t)d->total_tokens + 128) * (d->heads_q / d->heads_kv) > 0x7fffffffull) return "total_tokens * (heads_q / heads_kv) too large (packed rows are counted in 32 bits)";
+    if (paged_prefill_nothing_to_do(d)) return nullptr;
+    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->cu_seqlens_q || !d->out) return "null tensor pointer";
+    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
+    if (fp8 && (!d->k_scale || !d->v_scale)) return "null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)";
+    if (!fp8 && (d->k_scale || d->v_scale)) return "k_scale / v_scale apply to FP8 caches only; a 16-bit cache holds the values themselves";
+    const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
+    if (misaligned(d->q) || misaligned(d->out) || misaligned(d->k_cache) || misaligned(d->v_cache)) return "q, out and the caches must be 16-byte aligned";
+    return nullptr;
+}
+
+// (`d` passed paged_prefill_desc_error)
+static void fill_paged_prefill_args(const aule_paged_prefill_desc* d, aule_hip::PagedPrefillArgs& a) {
+    a.q = d->q; a.k_cache = d->k_cache; a.v_cache = d->v_cache; a.out = d->out; a.lse = d->lse;
+    a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
+    a.T = (int)d->total_tokens; a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
+    a.max_seqlen_q = (int)(d->max_seqlen_q < d->total_tokens ? d->max_seqlen_q : d->total_tokens);
+    a.q_token_stride = d->q_token_stride;
+    a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
+    a.scale = resolve_scale(d->scale, d->head_dim);
+    a.window = d->window_size;
+    a.dtype = d->dtype;
+    if (d->cache_dtype == AULE_KV_CACHE_FP8_E4M3) {
+        a.cache_kind = aule_hip::kCacheFp8E4M3;
+        a.k_scale = d->k_scale; a.v_scale = d->v_scale;
+    }
+}
+
+int32_t aule_attention_paged_prefill_ex(const aule_paged_prefill_desc* d) {
+    RoctxRange range("aule.paged_prefill");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = paged_prefill_desc_error(d, text)) {
+        set_error("Paged prefill attention failed: %s", why);
+        return -3;
+    }
+    if (paged_prefill_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::PagedPrefillArgs a;
+    fill_paged_prefill_args(d, a);
+    if (aule_hip::paged_prefill_grid(a) > 0x7fffffffll) {
+        set_error("Paged prefill attention failed: the grid (blocks * heads_kv * batch) exceeds 2^31 - 1 workgroups");
+        return -3;
+    }
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    rc = aule_hip::launch_paged_prefill(a, (hipStream_t)d->stream);
+    if (rc != 0) {
+        set_error("Paged prefill attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
         return -4;
     }
     return 0;

@@ -1,0 +1,354 @@
+// fa_fwd_paged_prefill_gfx950.hip -- paged prefill: ragged per-sequence queries against the paged KV cache.
+//
+// The step of a continuous-batching engine: sequence b brings n_b new tokens (a prompt chunk behind a cached prefix, a short
+// verify, a plain decode), packed along the first axis of q [T, Hq, D]; K / V live in the block pool
+// [num_blocks, block_size, Hkv, D] behind block_tables [B, max_blocks].  Everything per sequence is read and clamped HERE:
+//     L = clamp(context_lens[b], 0, max_blocks * block_size)        s = clamp(cu[b], 0, T)      e = clamp(cu[b + 1], s, T)
+//     n = min(e - s, max_seqlen_q);   token i < n is row s + i of q / out and sits at position p = L - n + i;
+//     it sees key j iff j <= p (and p - j < window when a window is set): the bottom-right rule of the paged query.
+// so a stale length or offset cannot index outside a buffer, and rows of out / lse outside every [s, s + n) are never written.
+//
+// Layout: the plain one of fa_fwd_d256_gfx950.hip / fa_d256_common.h, generalised over D:
+//   workgroup = (sequence, KV head, block of 128 PACKED rows), 4 waves x 32 rows, one wave per SIMD.  Packing is token-major:
+//   packed row r = token r / g, head hk g + r % g (g = Hq / Hkv) -- the g heads of a token are contiguous in [T, Hq, D], positions
+//   are monotone in r (a block's keys are one interval), K / V of a KV head stream once per 128 / g tokens x g heads;
+//   Q of the lane's row in registers, K / V tiles of 64 keys in LDS, the next tile prefetched into registers while this one is
+//   computed; S^T[key][row] = K.Q^T (2 accumulators), P^T as the B operand of O^T[d][row] += V^T.P^T (D / 32 accumulators).
+// Key row kv of the sequence is row ((table[b][kv / bs] * bs + kv % bs) * Hkv + hk) * D of the cache (64-bit; a shift when bs is a
+// power of two); rows at or beyond the block's last visible key are not read (zeros in LDS), table entries past them not touched.
+// FP8 caches: eight e4m3fn codes become one 16-byte chunk of q's 16-bit type on the way into LDS (exact), k_scale[hk] goes into the
+// log2-unit score factor and v_scale[hk] into the epilogue, so the MFMA loop is one family.
+// Online softmax in log2 units with fp32 m, l, acc; a row without a visible key writes O = 0 and LSE = -inf.
+// One launch, no workspace: grid = ceil(max_seqlen_q g / 128) x Hkv x B, decoded as (rank, sequence, KV head) with rank 0 the
+// sequence's own last (heaviest) block; a workgroup whose rank is past the sequence's blocks leaves before it touches the table or
+// the caches.  The table is walked one tile ahead of the K / V loads, which are one tile ahead of the MFMAs.
+#include <type_traits>
+
+#include "fa_d256_common.h"
+#include "fa_kernels.h"
+
+namespace aule_hip {
+namespace {
+
+struct Kv16 {};    // caches of q's dtype
+struct KvFp8 {};   // caches of e4m3fn codes
+
+struct PrefillParams {
+    const char* q;
+    const char* k;
+    const char* v;
+    char* o;
+    float* lse;
+    const int* table;
+    const int* ctx;
+    const int* cu;
+    const float* k_scale;
+    const float* v_scale;
+    long long q_stride;   // elements between tokens of q
+    int T, B, Hq, Hkv, g;
+    int bs, bs_shift;     // bs_shift >= 0: bs = 1 << bs_shift
+    int max_blocks, max_sq;
+    float c;              // scale * log2(e) (sign kept)
+    int window;           // > 0: on
+};
+
+constexpr int kPQ = 128;   // packed rows per workgroup
+constexpr int kPK = 64;    // keys per tile
+
+template <int D>
+struct PrefillCfg {
+    static constexpr int RB = D * 2;                       // bytes of a 16-bit row
+    static constexpr int G = D / 16;                       // operand chunk pairs per row
+    static constexpr int DT = D / 32;                      // O accumulators
+    static constexpr int PA = RB + 16;                     // K image pitch (ds_read_b128 rows shift by one slot)
+    static constexpr int PT = RB >= 256 ? RB + 64 : 192;   // V image pitch (transposed reads: four rows land in four 64-byte segments)
+    static constexpr int CPR = D / 8;                      // 8-element chunks per row
+    static constexpr int N = kPK * CPR / 256;              // chunks per thread and tile
+};
+
+// eight e4m3fn codes -> eight 16-bit elements, exact
+template <class T>
+__device__ __forceinline__ u32x4_t cvt8(u32x2_t x) {
+    u32x4_t e;
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+        const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[w], false);
+        const f32x2_t b = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[w], true);
+        e[2 * w] = T::pack2(a[0], a[1]);
+        e[2 * w + 1] = T::pack2(b[0], b[1]);
+    }
+    return e;
+}
+
+// One K and one V tile of 64 keys on their way from the block pool to LDS: chunk i of thread t is 8-element chunk t + 256 i
+// (row (t + 256 i) / CPR of the tile), 16 bytes of a 16-bit cache or 8 codes of an FP8 one.
+template <class T, int D, bool FP8>
+struct PagedTile {
+    using C = PrefillCfg<D>;
+    using Raw = typename std::conditional<FP8, u32x2_t, u32x4_t>::type;
+    static constexpr int EB = FP8 ? 1 : 2;
+    Raw k[C::N], v[C::N];
+    long long slot[C::N];   // cache slot (block * bs + offset) of this thread's rows of the tile load() takes next
+    // the table walk for keys k0 .. k0 + 63 of the sequence whose table row is `tab`, one tile ahead of the rows themselves: the
+    // loads of K / V then do not wait for a table entry.  Keys >= kend are neither looked up nor read.
+    __device__ __forceinline__ void lookup(const PrefillParams& p, const int* tab, int k0, int kend, int tid) {
+#pragma unroll
+        for (int i = 0; i < C::N; ++i) {
+            const int kv = k0 + (tid + 256 * i) / C::CPR;
+            long long at = 0;
+            if (kv < kend) {
+                const int lb = p.bs_shift >= 0 ? kv >> p.bs_shift : kv / p.bs;
+                at = (long long)tab[lb] * p.bs + (kv - lb * p.bs);
+            }
+            slot[i] = at;
+        }
+    }
+    // the rows lookup() found (same k0, kend)
+    __device__ __forceinline__ void load(const PrefillParams& p, int hk, int k0, int kend, int tid) {
+#pragma unroll
+        for (int i = 0; i < C::N; ++i) {
+            const int idx = tid + 256 * i;
+            const int kv = k0 + idx / C::CPR;
+            Raw kx = Raw{}, vx = Raw{};
+            if (kv < kend) {
+                const long long at = ((slot[i] * p.Hkv + hk) * D + (idx % C::CPR) * 8) * EB;
+                kx = *reinterpret_cast<const Raw*>(p.k + at);
+                vx = *reinterpret_cast<const Raw*>(p.v + at);
+            }
+            k[i] = kx;
+            v[i] = vx;
+        }
+    }
+    __device__ __forceinline__ void store(char* Ks, char* Vs, int tid) const {
+#pragma unroll
+        for (int i = 0; i < C::N; ++i) {
+            const int idx = tid + 256 * i;
+            const int row = idx / C::CPR, cc = idx % C::CPR;
+            u32x4_t kx, vx;
+            if constexpr (FP8) {
+                kx = cvt8<T>(k[i]);
+                vx = cvt8<T>(v[i]);
+            } else {
+                kx = k[i];
+                vx = v[i];
+            }
+            *reinterpret_cast<u32x4_t*>(Ks + row * C::PA + cc * 16) = kx;
+            *reinterpret_cast<u32x4_t*>(Vs + row * C::PT + cc * 16) = vx;
+        }
+    }
+};
+
+template <class T, int D, class KV>
+__global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_kernel(const PrefillParams p) {
+    using C = PrefillCfg<D>;
+    constexpr bool FP8 = std::is_same<KV, KvFp8>::value;
+    __shared__ __attribute__((aligned(16))) char Ks[kPK * C::PA];
+    __shared__ __attribute__((aligned(16))) char Vs[kPK * C::PT];
+
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // work item: rank i of (sequence, KV head) unit `unit`, the units side by side (with Hkv % 8 == 0 a KV head stays on one XCD)
+    const int bid = (int)blockIdx.x;
+    const int units = p.Hkv * p.B;
+    const int rank = bid / units, unit = bid - rank * units;
+    const int hk = unit % p.Hkv, b = unit / p.Hkv;
+
+    // the sequence, clamped
+    const int cap = p.max_blocks * p.bs;   // (< 2^30: the host checks)
+    const int L = min(max(p.ctx[b], 0), cap);
+    const int s = min(max(p.cu[b], 0), p.T);
+    const int e = min(max(p.cu[b + 1], s), p.T);
+    const int n = min(e - s, p.max_sq);
+    const int R = n * p.g;   // packed rows of this (sequence, KV head); T * g < 2^31: the host checks
+    // rank 0 is the sequence's last (heaviest) block, whatever its length: the one block of a decode starts with the first wave of
+    // workgroups, beside the last block of a long chunk
+    const int own = (R + kPQ - 1) / kPQ;
+    if (rank >= own) return;
+    const int r0 = (own - 1 - rank) * kPQ;
+    const int rows = min(kPQ, R - r0);   // of this block, >= 1
+
+    // this lane's row (a lane past the end works on the block's last row and stores nothing)
+    const int rl = wave * 32 + l31;
+    const bool live = rl < rows;
+    const int r = r0 + min(rl, rows - 1);
+    const int tok = r / p.g, head = hk * p.g + r % p.g;
+    const int pos = L - n + tok;
+    // wave-uniform position ranges: the block's decide the tiles, the wave's the tiles it computes and the unmasked path
+    const int bpos_lo = L - n + r0 / p.g, bpos_hi = L - n + (r0 + rows - 1) / p.g;
+    const bool wave_live = wave * 32 < rows;
+    const int wpos_lo = L - n + (r0 + min(wave * 32, rows - 1)) / p.g;
+    const int wpos_hi = L - n + (r0 + min(wave * 32 + 31, rows - 1)) / p.g;
+
+    const int kend = bpos_hi + 1;   // <= L
+    const int kbeg = p.window > 0 ? max(0, bpos_lo - p.window + 1) / kPK * kPK : 0;
+    const int ntiles = kend > kbeg ? (kend - kbeg + kPK - 1) / kPK : 0;
+    const int* tab = p.table + (long long)b * p.max_blocks;
+
+    // Q operand chunks of this lane's row
+    const char* qrow = p.q + (((long long)s + tok) * p.q_stride + (long long)head * D) * 2;
+    u32x4_t qf[C::G];
+#pragma unroll
+    for (int g = 0; g < C::G; ++g) qf[g] = *reinterpret_cast<const u32x4_t*>(qrow + 32 * g + 16 * hi);
+
+    float c = p.c;
+    if constexpr (FP8) c *= p.k_scale[hk];
+
+    f32x16_t o[C::DT];
+#pragma unroll
+    for (int i = 0; i < C::DT; ++i) o[i] = f32x16_t{};
+    float m = -__builtin_inff(), l = 0.f;
+
+    PagedTile<T, D, FP8> kt;
+    if (ntiles > 0) {
+        kt.lookup(p, tab, kbeg, kend, tid);
+        kt.load(p, hk, kbeg, kend, tid);
+        kt.lookup(p, tab, kbeg + kPK, kend, tid);
+    }
+    for (int t = 0; t < ntiles; ++t) {
+        const int k0 = kbeg + t * kPK;
+        __syncthreads();   // every wave is done with the previous tile
+        kt.store(Ks, Vs, tid);
+        __syncthreads();
+        if (t + 1 < ntiles) {
+            kt.load(p, hk, k0 + kPK, kend, tid);
+            kt.lookup(p, tab, k0 + 2 * kPK, kend, tid);
+        }
+        // a wave skips the tiles none of its rows sees: all keys after its last position, or all before its window
+        if (!wave_live || k0 > wpos_hi || (p.window > 0 && k0 + kPK - 1 < wpos_lo - p.window + 1)) continue;
+        // S^T[key][row] = K.Q^T over the 64 keys of the tile
+        f32x16_t sc[2] = {f32x16_t{}, f32x16_t{}};
+#pragma unroll
+        for (int g = 0; g < C::G; ++g)
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+                sc[kk] = mfma16<T>(lds_b128(Ks + (32 * kk + l31) * C::PA + 32 * g + 16 * hi), qf[g], sc[kk]);
+        // scale to log2 units, mask, running max over the lane pair (lanes l and l + 32 hold the same row)
+        float mx = -__builtin_inff();
+        const bool full = k0 + kPK - 1 <= wpos_lo && (p.window <= 0 || wpos_hi - k0 < p.window);   // every row sees every key of the tile
+        if (full) {
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) {
+                    const float x = sc[kk][rr] * c;
+                    sc[kk][rr] = x;
+                    mx = fmaxf(mx, x);
+                }
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) {
+                    const int j = k0 + 32 * kk + crow(rr, hi);
+                    const bool see = j <= pos && (p.window <= 0 || pos - j < p.window);
+                    const float x = see ? sc[kk][rr] * c : -__builtin_inff();
+                    sc[kk][rr] = x;
+                    mx = fmaxf(mx, x);
+                }
+        }
+        mx = fmaxf(mx, xhalf(mx));
+        const float mn = fmaxf(m, mx);
+        const float mu = mn == -__builtin_inff() ? 0.f : mn;
+        const float alpha = fast_exp2(m - mu);   // m = -inf: 0
+        m = mn;
+        l *= alpha;
+#pragma unroll
+        for (int i = 0; i < C::DT; ++i) o[i] *= alpha;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) {
+                const float ex = fast_exp2(sc[kk][rr] - mu);
+                sc[kk][rr] = ex;
+                l += ex;
+            }
+        // O^T[d][row] += V^T.P^T
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            const u32x4_t pb = pack_step<T>(sc[st >> 1], st & 1);
+#pragma unroll
+            for (int dt = 0; dt < C::DT; ++dt) o[dt] = mfma16<T>(lds_tr_step(Vs, C::PT, 16 * st, 32 * dt, lane), pb, o[dt]);
+        }
+    }
+    l += xhalf(l);
+    if (!live) return;
+    float inv = l > 0.f ? 1.f / l : 0.f;
+    if constexpr (FP8) inv *= p.v_scale[hk];
+    const long long orow = ((long long)s + tok) * p.Hq + head;
+    char* og = p.o + orow * (long long)C::RB;
+#pragma unroll
+    for (int dt = 0; dt < C::DT; ++dt)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const int d = 32 * dt + 8 * g4 + 4 * hi;
+            const float a0 = o[dt][4 * g4] * inv, a1 = o[dt][4 * g4 + 1] * inv, a2 = o[dt][4 * g4 + 2] * inv, a3 = o[dt][4 * g4 + 3] * inv;
+            *reinterpret_cast<u32x2_t*>(og + d * 2) = u32x2_t{T::pack2(a0, a1), T::pack2(a2, a3)};
+        }
+    if (p.lse != nullptr && hi == 0) {
+        const float mu = m == -__builtin_inff() ? 0.f : m;
+        p.lse[orow] = l > 0.f ? (mu + fast_log2(l)) * kLn2 : -__builtin_inff();
+    }
+}
+
+template <class T, int D, class KV>
+int launch_instance(const PrefillParams& p, long long nwg, hipStream_t stream) {
+    hipLaunchKernelGGL((fa_fwd_paged_prefill_kernel<T, D, KV>), dim3((unsigned)nwg), dim3(256), 0, stream, p);
+    return (int)hipGetLastError();
+}
+
+template <class T, int D>
+int launch_kind(const PrefillParams& p, bool fp8, long long nwg, hipStream_t stream) {
+    return fp8 ? launch_instance<T, D, KvFp8>(p, nwg, stream) : launch_instance<T, D, Kv16>(p, nwg, stream);
+}
+
+template <class T>
+int launch_dim(const PrefillParams& p, int D, bool fp8, long long nwg, hipStream_t stream) {
+    if (D == 32) return launch_kind<T, 32>(p, fp8, nwg, stream);
+    if (D == 64) return launch_kind<T, 64>(p, fp8, nwg, stream);
+    if (D == 128) return launch_kind<T, 128>(p, fp8, nwg, stream);
+    return -1;
+}
+
+}  // namespace
+
+// The grid rule: ceil(max_seqlen_q * g / 128) blocks per (sequence, KV head); the kernel decodes (rank, sequence, KV head) from
+// the 1-D index, KV head fastest, rank r = the sequence's own block count - 1 - r.
+long long paged_prefill_blocks_per_unit(const PagedPrefillArgs& a) {
+    if (a.Hkv <= 0 || a.max_seqlen_q <= 0) return 0;
+    const long long n = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T;   // no sequence has more tokens than the batch
+    return (n * (a.Hq / a.Hkv) + kPQ - 1) / kPQ;
+}
+
+long long paged_prefill_grid(const PagedPrefillArgs& a) {
+    return paged_prefill_blocks_per_unit(a) * a.Hkv * a.B;
+}
+
+int launch_paged_prefill(const PagedPrefillArgs& a, hipStream_t stream) {
+    const bool fp8 = a.cache_kind == kCacheFp8E4M3;
+    if (a.cache_kind != kCache16 && !fp8) return -1;
+    if (fp8 && (a.k_scale == nullptr || a.v_scale == nullptr)) return -1;
+    if (a.Hkv <= 0 || a.Hq % a.Hkv != 0 || a.block_size <= 0 || a.max_blocks <= 0) return -1;
+    if ((long long)a.block_size * a.max_blocks >= (1ll << 30)) return -1;
+    if (a.q_token_stride < (long long)a.Hq * a.D || a.q_token_stride % 8 != 0) return -1;
+    const long long nwg = paged_prefill_grid(a);
+    if (nwg <= 0 || a.T <= 0) return 0;
+    // the kernel counts packed rows in 32 bits
+    if (nwg > 0x7fffffffll || ((long long)a.T + kPQ) * (a.Hq / a.Hkv) > 0x7fffffffll) return -1;
+    PrefillParams p;
+    p.q = static_cast<const char*>(a.q); p.k = static_cast<const char*>(a.k_cache); p.v = static_cast<const char*>(a.v_cache);
+    p.o = static_cast<char*>(a.out); p.lse = a.lse;
+    p.table = a.block_tables; p.ctx = a.context_lens; p.cu = a.cu_seqlens_q;
+    p.k_scale = a.k_scale; p.v_scale = a.v_scale;
+    p.q_stride = a.q_token_stride;
+    p.T = a.T; p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.g = a.Hq / a.Hkv;
+    p.bs = a.block_size;
+    p.bs_shift = (a.block_size & (a.block_size - 1)) == 0 ? __builtin_ctz((unsigned)a.block_size) : -1;
+    p.max_blocks = a.max_blocks; p.max_sq = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T;
+    p.c = a.scale * kLog2e;
+    p.window = a.window > 0 ? a.window : 0;
+    if (a.dtype == kBF16) return launch_dim<Bf16Traits>(p, a.D, fp8, nwg, stream);
+    if (a.dtype == kF16) return launch_dim<F16Traits>(p, a.D, fp8, nwg, stream);
+    return -1;
+}
+
+}  // namespace aule_hip

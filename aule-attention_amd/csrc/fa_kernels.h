@@ -202,6 +202,37 @@ struct KvAppendArgs {
 };
 int launch_kv_append(const KvAppendArgs& a, hipStream_t stream);   // -1: unsupported arguments
 
+// Paged prefill (fa_fwd_paged_prefill_gfx950.hip): ragged per-sequence queries against the paged cache, one launch, no workspace.
+//   q [T, Hq, D] 16-bit, the new tokens of all sequences packed along the first axis (q_token_stride elements between tokens, the
+//   heads of a token contiguous), out [T, Hq, D] contiguous, lse [T, Hq] fp32 or null; caches, table, lengths and scales as PagedArgs;
+//   cu_seqlens_q [B + 1] int32 on the device.  Sequence b: L = clamp(context_lens[b], 0, max_blocks * block_size),
+//   s = clamp(cu[b], 0, T), e = clamp(cu[b + 1], s, T), n = min(e - s, max_seqlen_q); token i < n is row s + i, sits at position
+//   L - n + i and sees the keys at or before it (and inside the window measured from there).  Rows outside every [s, s + n) are
+//   never written.  The caller guarantees 16-byte aligned q / out / caches and q_token_stride % 8 == 0.
+struct PagedPrefillArgs {
+    const void* q;
+    const void* k_cache;
+    const void* v_cache;
+    void* out;
+    float* lse = nullptr;
+    const int* block_tables;
+    const int* context_lens;
+    const int* cu_seqlens_q;
+    int T, B, Hq, Hkv, D;
+    int max_seqlen_q;
+    long long q_token_stride;
+    int block_size, max_blocks;
+    float scale;
+    int window;
+    int dtype;
+    int cache_kind = kCache16;
+    const float* k_scale = nullptr;     // kCacheFp8E4M3 only
+    const float* v_scale = nullptr;
+};
+// workgroups of the launch: ceil(min(max_seqlen_q, T) * (Hq / Hkv) / 128) x Hkv x B (tests, tools)
+long long paged_prefill_grid(const PagedPrefillArgs& a);
+int launch_paged_prefill(const PagedPrefillArgs& a, hipStream_t stream);   // -1: unsupported arguments
+
 // Returns 0 on success, a hipError_t value on launch failure, -1 for an
 // unsupported (dtype, D) combination.
 int launch_paged_decode(const PagedArgs& a, hipStream_t stream);   // either cache_kind; kCacheFp8E4M3 with a null scale array is -1

@@ -246,8 +246,8 @@ uint64_t aule_attention_paged_decode_fp8_workspace_size(const aule_paged_fp8_des
 /* -- the bottom-right rule of AULE_CAUSAL_BOTTOM_RIGHT.  A query with p < 0 (a sequence shorter than seq_q) gives an output    */
 /* row of zeros.  lse (optional) is [batch, heads_q, seq_q] fp32: the natural log of the sum of exp(scaled score) over the     */
 /* visible keys, k_scale included; -inf for a row that sees no key.  seq_q = 1 gives aule_attention_paged_decode_ex /          */
-/* _fp8_ex bit for bit.  Not built: seq_q > 64, per-sequence query lengths, head_dim 256.  No host synchronisation, and no     */
-/* allocation when a workspace is passed: captures into a hipGraph.                                                            */
+/* _fp8_ex bit for bit.  seq_q > 64 and per-sequence query lengths: aule_attention_paged_prefill_ex.  Not built: head_dim 256. */
+/* No host synchronisation, and no allocation when a workspace is passed: captures into a hipGraph.                            */
 typedef struct aule_paged_query_desc {
     uint32_t struct_size;      /* = sizeof(aule_paged_query_desc) = 152 */
     int32_t dtype;             /* type of q / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
@@ -276,6 +276,57 @@ typedef struct aule_paged_query_desc {
 int32_t aule_attention_paged_query_ex(const aule_paged_query_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses on shape grounds. */
 uint64_t aule_attention_paged_query_workspace_size(const aule_paged_query_desc* desc);
+
+/* Paged PREFILL (additive): ragged per-sequence queries against the paged KV cache -- the step of a continuous-batching engine,  */
+/* whose sequences bring different numbers of new tokens (a prompt chunk behind a cached prefix next to a short verify next to    */
+/* plain decodes).  q is [total_tokens, heads_q, head_dim] fp16 / bf16: the new tokens of all sequences packed along the first    */
+/* axis, q_token_stride elements from one token to the next (the heads of a token contiguous; a slice of a fused QKV projection   */
+/* needs no copy).  out is [total_tokens, heads_q, head_dim] contiguous, lse (optional) [total_tokens, heads_q] fp32.  The two     */
+/* cache kinds, the cache layout and the scales are those of aule_paged_query_desc.  cu_seqlens_q is [batch + 1] int32 on the      */
+/* device; context_lens[b] counts the keys in the cache INCLUDING the new tokens (append them first: aule_kv_cache_append_ex).     */
+/* Every per-sequence value is read and clamped on the device (no host synchronisation; a stale value cannot index outside a      */
+/* buffer):  L_b = clamp(context_lens[b], 0, max_blocks * block_size),  s_b = clamp(cu[b], 0, total_tokens),                       */
+/* e_b = clamp(cu[b + 1], s_b, total_tokens),  n_b = min(e_b - s_b, max_seqlen_q).  Token i (0 <= i < n_b) of sequence b is row    */
+/* s_b + i of q / out / lse and sits at position p = L_b - n_b + i; it sees key j iff j <= p, and with window_size = W > 0 iff     */
+/* also p - j < W (the bottom-right rule of aule_attention_paged_query_ex).  A token with p < 0, or a sequence with L_b = 0,       */
+/* gives an output row of zeros and lse = -inf.  Rows that belong to no [s_b, s_b + n_b) -- a tail of total_tokens padded for     */
+/* graph capture, whatever hostile offsets leave over -- are NEVER written.  A table entry at logical block                        */
+/* >= ceil(L_b / block_size) is never dereferenced and a key row at or beyond L_b never read.  lse is the natural log of the sum   */
+/* of exp(scaled score) over the visible keys, k_scale included.  One launch of ceil(min(max_seqlen_q, total_tokens) * (heads_q /  */
+/* heads_kv) / 128) * heads_kv * batch workgroups, no workspace, no allocation: captures into a hipGraph, and a replay sees the    */
+/* CURRENT contents of cu_seqlens_q, context_lens and block_tables.  Alignment: q, out and the caches 16-byte aligned.            */
+/* Not built: head_dim 256; key-range splits (a batch made only of single-token sequences at very long context is better served    */
+/* by aule_attention_paged_decode_ex / aule_attention_paged_query_ex, which split the keys over the device); a backward pass.      */
+/* The descriptor is checked before the device is needed: -3 for a refused descriptor and 0 for one with nothing to do             */
+/* (total_tokens = 0, batch = 0 or heads_q = 0) are answered without aule_init().                                                   */
+typedef struct aule_paged_prefill_desc {
+    uint32_t struct_size;      /* = sizeof(aule_paged_prefill_desc) = 152 */
+    int32_t dtype;             /* type of q / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    int32_t cache_dtype;       /* offset 8; AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3 */
+    uint32_t batch;            /* offset 12; sequences */
+    uint32_t heads_q, heads_kv, head_dim;   /* head_dim 32, 64 or 128 */
+    uint32_t block_size;       /* offset 28; any value > 0 */
+    uint32_t max_blocks;       /* offset 32; columns of block_tables */
+    uint32_t total_tokens;     /* offset 36; rows of q / out; 0: returns 0 without a launch */
+    uint32_t max_seqlen_q;     /* offset 40; >= 1: sizes the grid, and caps every n_b */
+    float scale;               /* offset 44; 0 -> 1/sqrt(head_dim) */
+    int32_t window_size;       /* offset 48; > 0: the token at position p sees only the keys j with p - j < window_size */
+    int32_t device;            /* offset 52; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 56; elements, >= heads_q * head_dim, a multiple of 8 */
+    void* stream;              /* offset 64; hipStream_t */
+    const void* q;             /* offset 72; [total_tokens, heads_q, head_dim], 16-bit */
+    const void* k_cache;       /* offset 80; [num_blocks, block_size, heads_kv, head_dim]: 16-bit of q's dtype, or e4m3fn bytes */
+    const void* v_cache;       /* offset 88; same layout */
+    const int32_t* block_tables;   /* offset 96; [batch, max_blocks] */
+    const int32_t* context_lens;   /* offset 104; [batch]: keys per sequence, the new ones included */
+    const int32_t* cu_seqlens_q;   /* offset 112; [batch + 1], device */
+    void* out;                 /* offset 120; [total_tokens, heads_q, head_dim], 16-bit, contiguous */
+    float* lse;                /* offset 128; optional (NULL to skip): [total_tokens, heads_q] fp32 */
+    const float* k_scale;      /* offset 136; [heads_kv] fp32, device (AULE_KV_CACHE_FP8_E4M3), else NULL */
+    const float* v_scale;      /* offset 144 */
+} aule_paged_prefill_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_paged_prefill_ex(const aule_paged_prefill_desc* desc);
 
 /* Rotary position embedding pass (additive; SURVEY.md 8f row N1, second half).  Replaces the rotation the           */
 /* reference fuses into its kernels: python/aule/triton_flash.py:32-52,:112-131,:165-180 (layout HALF) and            */
