@@ -210,6 +210,54 @@ def flash_attention_paged_prefill(q, k_cache, v_cache, block_tables, context_len
                          window_size=window_size, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
 
 
+def flash_attention_paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tables, context_lens, cu_seqlens_q,
+                                  max_seqlen_q=None, scale=None, k_scale=None, v_scale=None, return_lse=False):
+    """flash_attention_paged_prefill for a batch whose sequences share a prefix (a system prompt, a few-shot header): the
+    shared keys are read once for the whole batch instead of once per sequence.  Not in the reference.
+
+        q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, k_scale, v_scale as in flash_attention_paged_prefill;
+        prefix_block_table [max_prefix_blocks] integer: the blocks that hold the shared prefix;
+        prefix_len: its length in keys -- an int32 [1] tensor on the device (read and clamped there to what the table
+          addresses; a graph replay sees its current value) or a Python int, which is wrapped;
+        block_tables [batch, max_blocks]: each sequence's OWN blocks; context_lens [batch]: its OWN keys, INCLUDING the new
+          tokens -- append them first (paged_kv_append).
+
+    The keys of sequence b are the prefix followed by its own keys: token i (n_b new tokens, L_b own keys) sits at own
+    position p = L_b - n_b + i, sees every prefix key and own key j iff j <= p.  A token with p < 0 gives zeros (lse -inf);
+    rows that belong to no sequence are never written; prefix_len = 0 equals flash_attention_paged_prefill bit for bit.
+    Three launches: the rows of all sequences packed into one dense problem per KV head against the prefix, split along the
+    keys (planned from the prefix table's capacity -- size the table to the prefix); the paged prefill on the own keys; a
+    merge (merge_attention_states' rule).  Returns [total_tokens, heads_q, head_dim], or (out, lse) with return_lse=True.
+    Out of scope: a sliding window, head_dim 256, a backward pass.  Argument errors are ValueErrors raised before the device
+    is touched; CPU tensors raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_cascade
+    return paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tables, context_lens, cu_seqlens_q,
+                         max_seqlen_q=max_seqlen_q, scale=scale, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
+
+
+def merge_attention_states(out_a, lse_a, out_b, lse_b):
+    """Merge two attention states of the same queries over DISJOINT key sets into the state over their union: the step that
+    combines partial results (a shared prefix and a private suffix, key ranges computed apart).  Not in the reference.
+
+        out_a, out_b [..., heads, head_dim] fp16 / bf16; lse_a, lse_b [..., heads] fp32 -- the (out, lse) pairs that
+        flash_attention_paged_query / _prefill / _cascade return with return_lse=True.
+
+    out = (w_a out_a + w_b out_b) / (w_a + w_b) and lse = M + log(w_a + w_b), with M = max(lse_a, lse_b) and
+    w_x = exp(lse_x - M).  A side with lse = -inf holds no key: the other side comes back bit for bit; both: zeros and -inf.
+    The order of the pair does not change the bits.  Returns (out, lse).  Argument errors are ValueErrors raised before the
+    device is touched; CPU tensors raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import merge_states
+    return merge_states(out_a, lse_a, out_b, lse_b)
+
+
 def quantize_kv_cache_fp8(cache, per_head=True):
     """(cache_fp8, scale) for the FP8 paged decode: float8_e4m3fn codes and a [heads_kv] fp32 scale = amax / 448 per KV
     head (per_head=False: one value, repeated), saturating.  Plain torch ops; works on CPU tensors."""
@@ -437,7 +485,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

@@ -154,6 +154,35 @@ class PagedPrefillDesc(ctypes.Structure):
     ]
 
 
+class PagedCascadeDesc(ctypes.Structure):
+    """struct aule_paged_cascade_desc (include/aule.h): the paged prefill behind a prefix every sequence shares."""
+    _fields_ = [(n, t) if n != "window_size" else ("max_prefix_blocks", ctypes.c_uint32) for n, t in PagedPrefillDesc._fields_] + [
+        ("prefix_block_table", ctypes.c_void_p),
+        ("prefix_len", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
+class MergeStatesDesc(ctypes.Structure):
+    """struct aule_merge_states_desc (include/aule.h): two attention states into one."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("rows", ctypes.c_uint32),
+        ("heads", ctypes.c_uint32),
+        ("head_dim", ctypes.c_uint32),
+        ("device", ctypes.c_int32),
+        ("stream", ctypes.c_void_p),
+        ("out_a", ctypes.c_void_p),
+        ("lse_a", ctypes.c_void_p),
+        ("out_b", ctypes.c_void_p),
+        ("lse_b", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p),
+    ]
+
+
 class RopeDesc(ctypes.Structure):
     """struct aule_rope_desc (include/aule.h)."""
     _fields_ = [
@@ -283,6 +312,9 @@ SIGNATURES = [
     ("aule_attention_paged_query_ex", _I32, [ctypes.POINTER(PagedQueryDesc)]),
     ("aule_attention_paged_query_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedQueryDesc)]),
     ("aule_attention_paged_prefill_ex", _I32, [ctypes.POINTER(PagedPrefillDesc)]),
+    ("aule_attention_paged_cascade_ex", _I32, [ctypes.POINTER(PagedCascadeDesc)]),
+    ("aule_attention_paged_cascade_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedCascadeDesc)]),
+    ("aule_attention_merge_states_ex", _I32, [ctypes.POINTER(MergeStatesDesc)]),
     ("aule_peer_alloc", _I32, [_I32, _U64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(IpcHandle)]),
     ("aule_peer_free", _I32, [_I32, ctypes.c_void_p]),
     ("aule_peer_open", _I32, [_I32, ctypes.POINTER(IpcHandle), ctypes.POINTER(ctypes.c_void_p)]),
@@ -292,6 +324,7 @@ SIGNATURES = [
     ("aule_hip_debug_forward_route", _I32, [ctypes.POINTER(AttnDesc)]),
     ("aule_hip_debug_last_forward_route", _I32, []),
     ("aule_hip_debug_forward_plan", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(_I32), _I32]),
+    ("aule_hip_debug_shared_prefix_plan", _I32, [ctypes.POINTER(PagedCascadeDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_last_backward_route", _I32, []),
     ("aule_hip_debug_backward_route", _I32, [ctypes.POINTER(AttnBwdDesc)]),
     ("aule_hip_debug_forward_split_plan", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(_I32), _I32]),

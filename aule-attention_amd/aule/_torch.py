@@ -410,6 +410,7 @@ def _paged_cache_is_fp8(op, inputs, k_cache, v_cache, k_scale, v_scale):
         "append": ("paged KV append", "the paged KV append writes", "key, value and caches", "fp16 / bf16 key and value", "the paged KV cache"),
         "query": ("paged query", "the FP8 paged query takes", "query and caches", "an fp16 / bf16 query", "the paged query"),
         "prefill": ("paged prefill", "the FP8 paged prefill takes", "query and caches", "an fp16 / bf16 query", "the paged prefill"),
+        "cascade": ("paged cascade", "the FP8 paged cascade takes", "query and caches", "an fp16 / bf16 query", "the paged cascade"),
     }[op]
     if k_cache.dtype != v_cache.dtype:
         raise ValueError(f"k_cache ({k_cache.dtype}) and v_cache ({v_cache.dtype}) must have the same dtype")
@@ -657,6 +658,152 @@ def paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q,
         d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
     _capi.check(lib.aule_attention_paged_prefill_ex(ctypes.byref(d)), "aule_attention_paged_prefill_ex")
     return (out, lse) if return_lse else out
+
+
+def paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None,
+                  scale=None, k_scale=None, v_scale=None, return_lse=False):
+    """Paged cascade: paged_prefill for a batch whose sequences share a prefix (a system prompt, a few-shot header), the prefix
+    read once for the whole batch; csrc/fa_fwd_paged_shared_prefix_gfx950.hip, the paged prefill and
+    csrc/fa_merge_states_gfx950.hip behind aule_attention_paged_cascade_ex:
+
+        q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, k_scale, v_scale: as in paged_prefill
+        prefix_block_table [max_prefix_blocks] integer: the blocks of the shared prefix
+        prefix_len   int32 [1] tensor on q's device, read and clamped on the device to what the table addresses; a Python int
+                     is wrapped (a constant of a captured graph then; pass a tensor to change it between replays)
+        block_tables [batch, max_blocks]: each sequence's OWN blocks;  context_lens [batch]: its OWN keys, the new tokens included
+    The keys of sequence b are the P prefix keys followed by its L_b own keys: token i sits at own position p = L_b - n_b + i,
+    sees every prefix key and own key j iff j <= p.  A token with p < 0 gives zeros and lse = -inf; P = 0 equals paged_prefill
+    bit for bit.  Rows that belong to no sequence are never written.  The key splits of the prefix are planned from the prefix
+    table's capacity (no device->host read): size the table to the prefix.  Returns out, or (out, lse) with return_lse; lse
+    covers prefix and own keys.  Not built: a sliding window, head_dim 256, a backward.  All argument errors are ValueErrors
+    raised before the device is touched."""
+    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError("expected q [T,Hq,D] and k_cache/v_cache [num_blocks, block_size, Hkv, D]")
+    T, Hq, D = q.shape
+    _, block_size, Hkv, Dk = k_cache.shape
+    if Dk != D:
+        raise ValueError(f"head_dim mismatch: query={D}, cache={Dk}")
+    if Hkv == 0 or Hq % Hkv != 0:
+        raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
+    fp8 = _paged_cache_is_fp8("cascade", (q,), k_cache, v_cache, k_scale, v_scale)
+    if block_size == 0:
+        raise ValueError("block_size must be positive")
+    if not torch.is_tensor(prefix_block_table) or prefix_block_table.dim() != 1 or prefix_block_table.shape[0] == 0 \
+            or prefix_block_table.dtype not in (torch.int32, torch.int64):
+        raise ValueError("prefix_block_table must be a non-empty integer [max_prefix_blocks] tensor")
+    if torch.is_tensor(prefix_len):
+        if prefix_len.shape != (1,) or prefix_len.dtype != torch.int32:
+            raise ValueError(f"prefix_len must be an int32 [1] tensor (it is read on the device as it stands) or a Python int, "
+                             f"got {prefix_len.dtype} {tuple(prefix_len.shape)}")
+    elif isinstance(prefix_len, bool) or not isinstance(prefix_len, int) or not -2 ** 31 <= prefix_len < 2 ** 31:
+        raise ValueError(f"prefix_len must be an int32 [1] tensor or a Python int, got {prefix_len!r}")
+    if block_tables.dim() != 2 or block_tables.shape[1] == 0 or context_lens.dim() != 1 or context_lens.shape[0] != block_tables.shape[0]:
+        raise ValueError("block_tables must be [batch, max_blocks] and context_lens [batch]")
+    B = block_tables.shape[0]
+    if not torch.is_tensor(cu_seqlens_q) or cu_seqlens_q.shape != (B + 1,):
+        raise ValueError(f"cu_seqlens_q must be a [batch + 1] = [{B + 1}] tensor")
+    if cu_seqlens_q.dtype != torch.int32:
+        raise ValueError(f"cu_seqlens_q must be int32 (it is read on the device as it stands), got {cu_seqlens_q.dtype}")
+    if max_seqlen_q is not None and (isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 1):
+        raise ValueError(f"max_seqlen_q must be a positive int or None, got {max_seqlen_q!r}")
+    if fp8:
+        for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if torch.is_tensor(s) and not (s.dim() == 0 or s.shape == (1,) or s.shape == (Hkv,)):
+                raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
+    if T > 1 and (q.stride(2) != 1 or q.stride(1) != D) or T <= 1 and not q.is_contiguous():
+        q = q.contiguous()
+    q_stride = q.stride(0) if T > 1 else Hq * D
+    if q_stride < Hq * D or q_stride % 8 != 0 or q.storage_offset() % 8 != 0:
+        raise ValueError(f"q's token stride ({q_stride}) and storage offset ({q.storage_offset()}) must be multiples of 8 elements "
+                         f"and the stride at least heads_q * head_dim = {Hq * D} (16-byte loads); pass q.contiguous()")
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): the paged cascade needs ROCm device tensors; there is no CPU fallback")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    lib = _capi.get_lib()
+    k_cache, v_cache = k_cache.contiguous(), v_cache.contiguous()
+    _same_device("paged cascade", q, k_cache, v_cache)
+    pbt = prefix_block_table.to(device=q.device, dtype=torch.int32).contiguous()
+    plen = prefix_len.to(device=q.device) if torch.is_tensor(prefix_len) else torch.tensor([prefix_len], device=q.device, dtype=torch.int32)
+    bt = block_tables.to(device=q.device, dtype=torch.int32).contiguous()
+    cl = context_lens.to(device=q.device, dtype=torch.int32).contiguous()
+    cu = cu_seqlens_q.to(device=q.device).contiguous()
+    if max_seqlen_q is None:
+        # the one documented synchronisation
+        max_seqlen_q = max(int((cu[1:] - cu[:-1]).max().item()), 1) if B > 0 else 1
+    out = torch.empty((T, Hq, D), device=q.device, dtype=q.dtype)
+    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
+    if T * B * Hq == 0:
+        return (out, lse) if return_lse else out
+    d = _capi.PagedCascadeDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    d.batch, d.heads_q, d.heads_kv, d.head_dim = B, Hq, Hkv, D
+    d.block_size, d.max_blocks, d.max_prefix_blocks = block_size, bt.shape[1], pbt.shape[0]
+    d.total_tokens, d.max_seqlen_q, d.q_token_stride = T, min(max_seqlen_q, T), q_stride
+    d.scale = _abi_scale(scale)
+    d.device = _device_index(q.device)
+    d.stream = _stream_ptr(q.device)
+    d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
+    d.lse = lse.data_ptr() if lse is not None else None
+    d.block_tables, d.context_lens, d.cu_seqlens_q = bt.data_ptr(), cl.data_ptr(), cu.data_ptr()
+    d.prefix_block_table, d.prefix_len = pbt.data_ptr(), plen.data_ptr()
+    ws = _workspace(lib.aule_attention_paged_cascade_workspace_size(ctypes.byref(d)), q.device)
+    if ws is not None:
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    if fp8:
+        ks = _fp8_scale(k_scale, Hkv, q.device, "k_scale")
+        vs = _fp8_scale(v_scale, Hkv, q.device, "v_scale")
+        d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
+    _capi.check(lib.aule_attention_paged_cascade_ex(ctypes.byref(d)), "aule_attention_paged_cascade_ex")
+    return (out, lse) if return_lse else out
+
+
+def merge_states(out_a, lse_a, out_b, lse_b):
+    """Two attention states of the same queries over disjoint key sets into the state over their union
+    (csrc/fa_merge_states_gfx950.hip behind aule_attention_merge_states_ex):
+
+        out_a, out_b [..., heads, head_dim] fp16 / bf16 of one shape and dtype (head_dim a multiple of 8)
+        lse_a, lse_b [..., heads] fp32: the natural log of each softmax denominator (the lse the attention calls return)
+    out = (w_a out_a + w_b out_b) / (w_a + w_b), lse = M + log(w_a + w_b) with M = max(lse_a, lse_b), w_x = exp(lse_x - M).  A
+    side with lse = -inf holds no key: the other side comes back bit for bit; both: zeros and -inf.  Returns (out, lse).  All
+    argument errors are ValueErrors raised before the device is touched."""
+    if not all(torch.is_tensor(t) for t in (out_a, lse_a, out_b, lse_b)):
+        raise ValueError("merge_attention_states takes four tensors (out_a, lse_a, out_b, lse_b)")
+    if out_a.dim() < 2 or out_b.shape != out_a.shape:
+        raise ValueError(f"expected out_a and out_b of one shape [..., heads, head_dim], got {tuple(out_a.shape)} and {tuple(out_b.shape)}")
+    if out_a.dtype not in (torch.float16, torch.bfloat16) or out_b.dtype != out_a.dtype:
+        raise ValueError(f"out_a and out_b must both be fp16 or both bf16, got {out_a.dtype} and {out_b.dtype}")
+    if lse_a.shape != out_a.shape[:-1] or lse_b.shape != out_a.shape[:-1]:
+        raise ValueError(f"lse_a and lse_b must have out's shape without head_dim, {tuple(out_a.shape[:-1])}, "
+                         f"got {tuple(lse_a.shape)} and {tuple(lse_b.shape)}")
+    if lse_a.dtype != torch.float32 or lse_b.dtype != torch.float32:
+        raise ValueError(f"lse_a and lse_b must be float32, got {lse_a.dtype} and {lse_b.dtype}")
+    D, H = out_a.shape[-1], out_a.shape[-2]
+    if D == 0 or D % 8 != 0 or D > 1024:
+        raise ValueError(f"head_dim must be a multiple of 8 (at most 1024), got {D}")
+    rows = out_a.numel() // (H * D) if H > 0 else 0
+    if rows >= 2 ** 31 or rows * H >= 2 ** 31:
+        raise ValueError("too many rows")
+    if not out_a.is_cuda:
+        raise _capi.AuleError("aule (HIP build): merge_attention_states needs ROCm device tensors; there is no CPU fallback")
+    lib = _capi.get_lib()
+    _same_device("merge_attention_states", out_a, lse_a, out_b, lse_b)
+    out_a, lse_a, out_b, lse_b = out_a.contiguous(), lse_a.contiguous(), out_b.contiguous(), lse_b.contiguous()
+    out, lse = torch.empty_like(out_a), torch.empty_like(lse_a)
+    if rows * H == 0:
+        return out, lse
+    d = _capi.MergeStatesDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[out_a.dtype]
+    d.rows, d.heads, d.head_dim = rows, H, D
+    d.device = _device_index(out_a.device)
+    d.stream = _stream_ptr(out_a.device)
+    d.out_a, d.lse_a, d.out_b, d.lse_b = out_a.data_ptr(), lse_a.data_ptr(), out_b.data_ptr(), lse_b.data_ptr()
+    d.out, d.lse = out.data_ptr(), lse.data_ptr()
+    _capi.check(lib.aule_attention_merge_states_ex(ctypes.byref(d)), "aule_attention_merge_states_ex")
+    return out, lse
 
 
 def paged_slot_mapping(block_tables, positions, block_size, seq_ids=None):

@@ -57,6 +57,27 @@ static_assert(sizeof(aule_paged_prefill_desc) == 152 && offsetof(aule_paged_pref
                   offsetof(aule_paged_prefill_desc, out) == 120 && offsetof(aule_paged_prefill_desc, lse) == 128 &&
                   offsetof(aule_paged_prefill_desc, k_scale) == 136 && offsetof(aule_paged_prefill_desc, v_scale) == 144,
               "aule_paged_prefill_desc layout is part of the ABI");
+static_assert(sizeof(aule_paged_cascade_desc) == 184 && offsetof(aule_paged_cascade_desc, cache_dtype) == 8 &&
+                  offsetof(aule_paged_cascade_desc, batch) == 12 && offsetof(aule_paged_cascade_desc, block_size) == 28 &&
+                  offsetof(aule_paged_cascade_desc, max_blocks) == 32 && offsetof(aule_paged_cascade_desc, total_tokens) == 36 &&
+                  offsetof(aule_paged_cascade_desc, max_seqlen_q) == 40 && offsetof(aule_paged_cascade_desc, scale) == 44 &&
+                  offsetof(aule_paged_cascade_desc, max_prefix_blocks) == 48 && offsetof(aule_paged_cascade_desc, device) == 52 &&
+                  offsetof(aule_paged_cascade_desc, q_token_stride) == 56 && offsetof(aule_paged_cascade_desc, stream) == 64 &&
+                  offsetof(aule_paged_cascade_desc, q) == 72 && offsetof(aule_paged_cascade_desc, k_cache) == 80 &&
+                  offsetof(aule_paged_cascade_desc, v_cache) == 88 && offsetof(aule_paged_cascade_desc, block_tables) == 96 &&
+                  offsetof(aule_paged_cascade_desc, context_lens) == 104 && offsetof(aule_paged_cascade_desc, cu_seqlens_q) == 112 &&
+                  offsetof(aule_paged_cascade_desc, out) == 120 && offsetof(aule_paged_cascade_desc, lse) == 128 &&
+                  offsetof(aule_paged_cascade_desc, k_scale) == 136 && offsetof(aule_paged_cascade_desc, v_scale) == 144 &&
+                  offsetof(aule_paged_cascade_desc, prefix_block_table) == 152 && offsetof(aule_paged_cascade_desc, prefix_len) == 160 &&
+                  offsetof(aule_paged_cascade_desc, workspace) == 168 && offsetof(aule_paged_cascade_desc, workspace_bytes) == 176,
+              "aule_paged_cascade_desc layout is part of the ABI");
+static_assert(sizeof(aule_merge_states_desc) == 80 && offsetof(aule_merge_states_desc, rows) == 8 &&
+                  offsetof(aule_merge_states_desc, heads) == 12 && offsetof(aule_merge_states_desc, head_dim) == 16 &&
+                  offsetof(aule_merge_states_desc, device) == 20 && offsetof(aule_merge_states_desc, stream) == 24 &&
+                  offsetof(aule_merge_states_desc, out_a) == 32 && offsetof(aule_merge_states_desc, lse_a) == 40 &&
+                  offsetof(aule_merge_states_desc, out_b) == 48 && offsetof(aule_merge_states_desc, lse_b) == 56 &&
+                  offsetof(aule_merge_states_desc, out) == 64 && offsetof(aule_merge_states_desc, lse) == 72,
+              "aule_merge_states_desc layout is part of the ABI");
 static_assert(offsetof(aule_paged_query_desc, q) == offsetof(aule_paged_fp8_desc, q) &&
                   offsetof(aule_paged_query_desc, workspace_bytes) == offsetof(aule_paged_fp8_desc, workspace_bytes) &&
                   offsetof(aule_paged_query_desc, v_scale) == offsetof(aule_paged_fp8_desc, v_scale) &&
@@ -1095,6 +1116,154 @@ int32_t aule_attention_paged_prefill_ex(const aule_paged_prefill_desc* d) {
     return 0;
 }
 
+// The paged cascade: the prefill's fields without the window, plus the shared prefix and the workspace.  One checker for its three
+// readers; `launch`: the pointer rules of a call that has something to do as well (the size query and the plan hook read no pointer).
+static bool paged_cascade_nothing_to_do(const aule_paged_cascade_desc* d) {
+    return d->total_tokens == 0 || (uint64_t)d->batch * d->heads_q == 0;
+}
+
+static const char* paged_cascade_desc_error(const aule_paged_cascade_desc* d, bool launch, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_paged_cascade_desc)) return kBadDescriptor;
+    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return "dtype (of q / out) must be fp16 or bf16";
+    if (d->cache_dtype != AULE_KV_CACHE_SAME && d->cache_dtype != AULE_KV_CACHE_FP8_E4M3)
+        return "cache_dtype must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3";
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return reasonf(why, "head_dim %u unsupported (32, 64 or 128)", d->head_dim);
+    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0)
+        return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
+    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return "bad block_size / max_blocks";
+    if (d->max_prefix_blocks == 0 || (uint64_t)d->block_size * d->max_prefix_blocks >= (1ull << 30)) return "bad block_size / max_prefix_blocks";
+    if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
+    if (d->q_token_stride < (int64_t)d->heads_q * d->head_dim)
+        return reasonf(why, "q_token_stride (%lld) is smaller than a token (heads_q * head_dim = %llu elements)", (long long)d->q_token_stride,
+                       (unsigned long long)d->heads_q * d->head_dim);
+    if (d->q_token_stride % 8 != 0) return reasonf(why, "q_token_stride (%lld) must be a multiple of 8 elements (16-byte loads)", (long long)d->q_token_stride);
+    if (d->batch >= (1u << 30) || d->total_tokens >= (1u << 30)) return "batch / total_tokens too large";
+    if (((uint64_t)d->total_tokens + 128) * (d->heads_q / d->heads_kv) > 0x7fffffffull) return "total_tokens * (heads_q / heads_kv) too large (packed rows are counted in 32 bits)";
+    if (!launch || paged_cascade_nothing_to_do(d)) return nullptr;
+    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->cu_seqlens_q || !d->out || !d->prefix_block_table || !d->prefix_len)
+        return "null tensor pointer";
+    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
+    if (fp8 && (!d->k_scale || !d->v_scale)) return "null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)";
+    if (!fp8 && (d->k_scale || d->v_scale)) return "k_scale / v_scale apply to FP8 caches only; a 16-bit cache holds the values themselves";
+    const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
+    if (misaligned(d->q) || misaligned(d->out) || misaligned(d->k_cache) || misaligned(d->v_cache)) return "q, out and the caches must be 16-byte aligned";
+    return nullptr;
+}
+
+// (`d` passed paged_cascade_desc_error) the two kernels' arguments; part / lse of the workspace are the launch entry's to set
+static void fill_paged_cascade_args(const aule_paged_cascade_desc* d, aule_hip::SharedPrefixArgs& x, aule_hip::PagedPrefillArgs& a) {
+    a.q = d->q; a.k_cache = d->k_cache; a.v_cache = d->v_cache; a.out = d->out; a.lse = d->lse;
+    a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
+    a.T = (int)d->total_tokens; a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
+    a.max_seqlen_q = (int)(d->max_seqlen_q < d->total_tokens ? d->max_seqlen_q : d->total_tokens);
+    a.q_token_stride = d->q_token_stride;
+    a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
+    a.scale = resolve_scale(d->scale, d->head_dim);
+    a.window = -1;
+    a.dtype = d->dtype;
+    if (d->cache_dtype == AULE_KV_CACHE_FP8_E4M3) {
+        a.cache_kind = aule_hip::kCacheFp8E4M3;
+        a.k_scale = d->k_scale; a.v_scale = d->v_scale;
+    }
+    x.q = a.q; x.k_cache = a.k_cache; x.v_cache = a.v_cache;
+    x.prefix_block_table = d->prefix_block_table; x.prefix_len = d->prefix_len;
+    x.T = a.T; x.Hq = a.Hq; x.Hkv = a.Hkv; x.D = a.D;
+    x.q_token_stride = a.q_token_stride;
+    x.block_size = a.block_size; x.max_prefix_blocks = (int)d->max_prefix_blocks;
+    x.scale = a.scale; x.dtype = a.dtype;
+    x.cache_kind = a.cache_kind; x.k_scale = a.k_scale; x.v_scale = a.v_scale;
+    x.device = d->device;
+}
+
+int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* d) {
+    RoctxRange range("aule.paged_cascade");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = paged_cascade_desc_error(d, true, text)) {
+        set_error("Paged cascade attention failed: %s", why);
+        return -3;
+    }
+    if (paged_cascade_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::SharedPrefixArgs x;
+    aule_hip::PagedPrefillArgs a;
+    fill_paged_cascade_args(d, x, a);
+    const aule_hip::SharedPrefixPlan plan = aule_hip::shared_prefix_plan(x);
+    aule_hip::CascadeMergeArgs m;
+    m.nsplit = plan.nsplit; m.out = d->out;
+    m.context_lens = d->context_lens; m.cu_seqlens_q = d->cu_seqlens_q;
+    m.T = a.T; m.B = a.B; m.Hq = a.Hq; m.D = a.D;
+    m.max_seqlen_q = a.max_seqlen_q; m.own_capacity = a.block_size * a.max_blocks; m.dtype = a.dtype;
+    if (plan.grid <= 0 || plan.grid > 0x7fffffffll || aule_hip::paged_prefill_grid(a) > 0x7fffffffll || aule_hip::cascade_merge_grid(m) > 0x7fffffffll) {
+        set_error("Paged cascade attention failed: a grid exceeds 2^31 - 1 workgroups");
+        return -3;
+    }
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)d->stream;
+    aule_hip::ScopedWorkspace ws(plan.ws_bytes, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
+    if (ws.err != hipSuccess) {
+        set_error("Paged cascade attention failed: workspace allocation (%llu bytes): %s", (unsigned long long)plan.ws_bytes, hipGetErrorString(ws.err));
+        return -4;
+    }
+    x.part = static_cast<float*>(ws.ptr);
+    if (a.lse == nullptr) a.lse = reinterpret_cast<float*>(static_cast<char*>(ws.ptr) + plan.lse_offset);
+    m.part = x.part; m.lse = a.lse;
+    rc = aule_hip::launch_shared_prefix(x, plan, stream);
+    if (rc == 0) rc = aule_hip::launch_paged_prefill(a, stream);
+    if (rc == 0) rc = aule_hip::launch_cascade_merge(m, stream);
+    if (rc != 0) {
+        set_error("Paged cascade attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
+        return -4;
+    }
+    return 0;
+}
+
+// The two-state merge.  One checker, one reader (the launch entry: the pointer rules are stated here too).
+static bool merge_states_nothing_to_do(const aule_merge_states_desc* d) { return (uint64_t)d->rows * d->heads == 0; }
+
+static const char* merge_states_desc_error(const aule_merge_states_desc* d, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_merge_states_desc)) return kBadDescriptor;
+    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return "dtype must be fp16 or bf16";
+    if (d->head_dim == 0 || d->head_dim % 8 != 0 || d->head_dim > 1024) return reasonf(why, "head_dim %u unsupported (a multiple of 8, at most 1024)", d->head_dim);
+    if ((uint64_t)d->rows * d->heads >= (1ull << 31)) return "rows * heads too large";
+    if (merge_states_nothing_to_do(d)) return nullptr;
+    if (!d->out_a || !d->lse_a || !d->out_b || !d->lse_b || !d->out || !d->lse) return "null tensor pointer";
+    const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
+    if (misaligned(d->out_a) || misaligned(d->out_b) || misaligned(d->out)) return "out_a, out_b and out must be 16-byte aligned";
+    // every thread of a row reads lse_a and lse_b, one of them writes lse: an lse inside either input would be read after it was written
+    const uint64_t lse_bytes = (uint64_t)d->rows * d->heads * 4;
+    const auto overlaps = [lse_bytes](const float* x, const float* y) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
+        return a < b + lse_bytes && b < a + lse_bytes;
+    };
+    if (overlaps(d->lse, d->lse_a) || overlaps(d->lse, d->lse_b)) return "lse must not overlap lse_a or lse_b (only out may alias an input)";
+    return nullptr;
+}
+
+int32_t aule_attention_merge_states_ex(const aule_merge_states_desc* d) {
+    RoctxRange range("aule.merge_states");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = merge_states_desc_error(d, text)) {
+        set_error("Merge of attention states failed: %s", why);
+        return -3;
+    }
+    if (merge_states_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MergeStatesArgs a;
+    a.out_a = d->out_a; a.lse_a = d->lse_a; a.out_b = d->out_b; a.lse_b = d->lse_b; a.out = d->out; a.lse = d->lse;
+    a.rows = (long long)d->rows * d->heads; a.D = (int)d->head_dim; a.dtype = d->dtype;
+    DeviceGuard g(d->device);
+    const int rc = aule_hip::launch_merge_states(a, (hipStream_t)d->stream);
+    if (rc != 0) {
+        set_error("Merge of attention states failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
+        return -4;
+    }
+    return 0;
+}
+
 static const char* rope_desc_error(const aule_rope_desc* d, Reason& why) {
     if (d == nullptr || d->struct_size != sizeof(aule_rope_desc)) return kBadDescriptor;
     if (d->dtype < 0 || d->dtype > 2) return reasonf(why, "unknown dtype %d", d->dtype);
@@ -1351,6 +1520,24 @@ uint64_t aule_attention_paged_query_workspace_size(const aule_paged_query_desc* 
     return aule_hip::paged_workspace_bytes(a);
 }
 
+// (the launch's plan: shared_prefix_plan reads the shape, none of the pointers)
+static bool cascade_plan(const aule_paged_cascade_desc* d, aule_hip::SharedPrefixPlan& plan) {
+    Reason text;
+    if (paged_cascade_desc_error(d, false, text)) return false;
+    plan = aule_hip::SharedPrefixPlan();
+    if (paged_cascade_nothing_to_do(d)) return true;
+    aule_hip::SharedPrefixArgs x;
+    aule_hip::PagedPrefillArgs a;
+    fill_paged_cascade_args(d, x, a);
+    plan = aule_hip::shared_prefix_plan(x);
+    return true;
+}
+
+uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_desc* d) {
+    aule_hip::SharedPrefixPlan plan;
+    return cascade_plan(d, plan) ? plan.ws_bytes : 0;
+}
+
 #ifdef AULE_DEBUG_HOOKS
 /* The timeline hooks exist only in the debug library (`make dbg` -> build/variants/libaule_dbg.so, -DAULE_DEBUG_HOOKS):
  * they launch instrumented kernel instances on caller-supplied pointers and are not part of the product libaule.so. */
@@ -1401,6 +1588,19 @@ int32_t aule_hip_debug_last_forward_route(void) { return aule_hip::fwd_last_rout
 int32_t aule_hip_debug_forward_plan(const aule_attn_desc* d, int32_t* out, int32_t cap) {
     FwdArgs a;
     return plan_hook_args(d, a) ? aule_hip::fwd_plan_dump(a, out, cap) : -3;
+}
+
+/* Debug hook: the launch plan of the paged cascade's shared-prefix kernel as integers (include/aule.h lists them): the plan the launch
+ * and the workspace query read.  Pure host logic like the forward hook. */
+int32_t aule_hip_debug_shared_prefix_plan(const aule_paged_cascade_desc* d, int32_t* out, int32_t cap) {
+    aule_hip::SharedPrefixPlan plan;
+    if (!cascade_plan(d, plan)) return -3;
+    if (plan.grid <= 0) return 0;
+    const int32_t v[7] = {plan.row_blocks, plan.tiles, plan.nsplit, plan.tiles_per_split, (int32_t)(plan.grid > 0x7fffffffll ? 0x7fffffff : plan.grid),
+                          (int32_t)(uint32_t)(plan.ws_bytes & 0xffffffffull), (int32_t)(uint32_t)(plan.ws_bytes >> 32)};
+    if (out == nullptr || cap < 7) return -7;
+    for (int i = 0; i < 7; ++i) out[i] = v[i];
+    return 7;
 }
 
 /* Debug hook: what the most recent backward launch of this process ran (bit mask, include/aule.h). */

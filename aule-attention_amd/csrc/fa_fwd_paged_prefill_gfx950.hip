@@ -22,16 +22,11 @@
 // One launch, no workspace: grid = ceil(max_seqlen_q g / 128) x Hkv x B, decoded as (rank, sequence, KV head) with rank 0 the
 // sequence's own last (heaviest) block; a workgroup whose rank is past the sequence's blocks leaves before it touches the table or
 // the caches.  The table is walked one tile ahead of the K / V loads, which are one tile ahead of the MFMAs.
-#include <type_traits>
-
-#include "fa_d256_common.h"
 #include "fa_kernels.h"
+#include "fa_paged_tile.h"
 
 namespace aule_hip {
 namespace {
-
-struct Kv16 {};    // caches of q's dtype
-struct KvFp8 {};   // caches of e4m3fn codes
 
 struct PrefillParams {
     const char* q;
@@ -50,92 +45,6 @@ struct PrefillParams {
     int max_blocks, max_sq;
     float c;              // scale * log2(e) (sign kept)
     int window;           // > 0: on
-};
-
-constexpr int kPQ = 128;   // packed rows per workgroup
-constexpr int kPK = 64;    // keys per tile
-
-template <int D>
-struct PrefillCfg {
-    static constexpr int RB = D * 2;                       // bytes of a 16-bit row
-    static constexpr int G = D / 16;                       // operand chunk pairs per row
-    static constexpr int DT = D / 32;                      // O accumulators
-    static constexpr int PA = RB + 16;                     // K image pitch (ds_read_b128 rows shift by one slot)
-    static constexpr int PT = RB >= 256 ? RB + 64 : 192;   // V image pitch (transposed reads: four rows land in four 64-byte segments)
-    static constexpr int CPR = D / 8;                      // 8-element chunks per row
-    static constexpr int N = kPK * CPR / 256;              // chunks per thread and tile
-};
-
-// eight e4m3fn codes -> eight 16-bit elements, exact
-template <class T>
-__device__ __forceinline__ u32x4_t cvt8(u32x2_t x) {
-    u32x4_t e;
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-        const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[w], false);
-        const f32x2_t b = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[w], true);
-        e[2 * w] = T::pack2(a[0], a[1]);
-        e[2 * w + 1] = T::pack2(b[0], b[1]);
-    }
-    return e;
-}
-
-// One K and one V tile of 64 keys on their way from the block pool to LDS: chunk i of thread t is 8-element chunk t + 256 i
-// (row (t + 256 i) / CPR of the tile), 16 bytes of a 16-bit cache or 8 codes of an FP8 one.
-template <class T, int D, bool FP8>
-struct PagedTile {
-    using C = PrefillCfg<D>;
-    using Raw = typename std::conditional<FP8, u32x2_t, u32x4_t>::type;
-    static constexpr int EB = FP8 ? 1 : 2;
-    Raw k[C::N], v[C::N];
-    long long slot[C::N];   // cache slot (block * bs + offset) of this thread's rows of the tile load() takes next
-    // the table walk for keys k0 .. k0 + 63 of the sequence whose table row is `tab`, one tile ahead of the rows themselves: the
-    // loads of K / V then do not wait for a table entry.  Keys >= kend are neither looked up nor read.
-    __device__ __forceinline__ void lookup(const PrefillParams& p, const int* tab, int k0, int kend, int tid) {
-#pragma unroll
-        for (int i = 0; i < C::N; ++i) {
-            const int kv = k0 + (tid + 256 * i) / C::CPR;
-            long long at = 0;
-            if (kv < kend) {
-                const int lb = p.bs_shift >= 0 ? kv >> p.bs_shift : kv / p.bs;
-                at = (long long)tab[lb] * p.bs + (kv - lb * p.bs);
-            }
-            slot[i] = at;
-        }
-    }
-    // the rows lookup() found (same k0, kend)
-    __device__ __forceinline__ void load(const PrefillParams& p, int hk, int k0, int kend, int tid) {
-#pragma unroll
-        for (int i = 0; i < C::N; ++i) {
-            const int idx = tid + 256 * i;
-            const int kv = k0 + idx / C::CPR;
-            Raw kx = Raw{}, vx = Raw{};
-            if (kv < kend) {
-                const long long at = ((slot[i] * p.Hkv + hk) * D + (idx % C::CPR) * 8) * EB;
-                kx = *reinterpret_cast<const Raw*>(p.k + at);
-                vx = *reinterpret_cast<const Raw*>(p.v + at);
-            }
-            k[i] = kx;
-            v[i] = vx;
-        }
-    }
-    __device__ __forceinline__ void store(char* Ks, char* Vs, int tid) const {
-#pragma unroll
-        for (int i = 0; i < C::N; ++i) {
-            const int idx = tid + 256 * i;
-            const int row = idx / C::CPR, cc = idx % C::CPR;
-            u32x4_t kx, vx;
-            if constexpr (FP8) {
-                kx = cvt8<T>(k[i]);
-                vx = cvt8<T>(v[i]);
-            } else {
-                kx = k[i];
-                vx = v[i];
-            }
-            *reinterpret_cast<u32x4_t*>(Ks + row * C::PA + cc * 16) = kx;
-            *reinterpret_cast<u32x4_t*>(Vs + row * C::PT + cc * 16) = vx;
-        }
-    }
 };
 
 template <class T, int D, class KV>

@@ -233,6 +233,78 @@ struct PagedPrefillArgs {
 long long paged_prefill_grid(const PagedPrefillArgs& a);
 int launch_paged_prefill(const PagedPrefillArgs& a, hipStream_t stream);   // -1: unsupported arguments
 
+// Shared-prefix pass of the paged cascade (fa_fwd_paged_shared_prefix_gfx950.hip): every one of the T tokens of q sees the first
+// P = clamp(prefix_len[0], 0, max_prefix_blocks * block_size) keys of ONE block table, no mask, no per-sequence data.  The rows of
+// the whole batch are packed token-major per KV head (row r = token r / g, head hk g + r % g) and the keys are split into nsplit
+// ranges of whole 64-key tiles; work item (KV head, 128 rows, split) writes the fp32 partial of its rows:
+//   part [nsplit][T * Hq][D + 2]: un-normalised O (v_scale applied), m (log2 units), l -- row = token * Hq + head; a split that
+//   holds no key of the prefix writes m = -inf, l = 0 and leaves O alone (a reader skips it).
+struct SharedPrefixArgs {
+    const void* q;
+    const void* k_cache;
+    const void* v_cache;
+    float* part = nullptr;
+    const int* prefix_block_table = nullptr;   // [max_prefix_blocks] int32
+    const int* prefix_len = nullptr;           // [1] int32, device
+    int T, Hq, Hkv, D;
+    long long q_token_stride;
+    int block_size, max_prefix_blocks;
+    float scale;
+    int dtype;
+    int cache_kind = kCache16;
+    const float* k_scale = nullptr;     // kCacheFp8E4M3 only
+    const float* v_scale = nullptr;
+    int device = -1;                    // as FwdArgs::device
+};
+// The launch plan of the pass, and of the cascade's workspace: the one statement of the rule (launch, workspace query, debug hook).
+// The key bound is the table's capacity -- prefix_len lives on the device and is not read here.
+constexpr int kSharedPrefixMaxSplit = 32;
+struct SharedPrefixPlan {
+    int row_blocks = 0;        // ceil(T * g / 128)
+    int tiles = 0;             // ceil(max_prefix_blocks * block_size / 64)
+    int nsplit = 0;            // 1 .. kSharedPrefixMaxSplit, every split non-empty by capacity
+    int tiles_per_split = 0;   // split k: tiles [k * tiles_per_split, min((k + 1) * tiles_per_split, tiles))
+    long long grid = 0;        // row_blocks * Hkv * nsplit
+    uint64_t part_bytes = 0;   // nsplit * T * Hq * (D + 2) * 4
+    uint64_t lse_offset = 0;   // part_bytes rounded up to 16: the suffix LSE [T * Hq] fp32 of a cascade call without an lse buffer
+    uint64_t ws_bytes = 0;     // lse_offset + T * Hq * 4, rounded up to 16
+};
+SharedPrefixPlan shared_prefix_plan(const SharedPrefixArgs& a);   // all zero: nothing to launch, or arguments the launch refuses
+int launch_shared_prefix(const SharedPrefixArgs& a, const SharedPrefixPlan& plan, hipStream_t stream);   // -1: unsupported arguments
+
+// Merges of attention states (fa_merge_states_gfx950.hip).
+// Two states (out 16-bit [rows, D], lse fp32 [rows], natural log) into one; out may alias out_a or out_b, lse must not overlap
+// lse_a or lse_b (the caller checks).  D % 8 == 0.
+struct MergeStatesArgs {
+    const void* out_a;
+    const float* lse_a;
+    const void* out_b;
+    const float* lse_b;
+    void* out;
+    float* lse;
+    long long rows;
+    int D;
+    int dtype;
+};
+int launch_merge_states(const MergeStatesArgs& a, hipStream_t stream);
+// The cascade's merge: the nsplit partials of launch_shared_prefix into the suffix state (out, lse) launch_paged_prefill left, in
+// place, for exactly the rows that launch wrote (its clamps of cu_seqlens_q / context_lens, own_capacity = max_blocks * block_size);
+// a token at a negative own position keeps its zeros and -inf, a row whose prefix holds no key keeps its bits.
+struct CascadeMergeArgs {
+    const float* part;
+    int nsplit;
+    void* out;
+    float* lse;
+    const int* context_lens;
+    const int* cu_seqlens_q;
+    int T, B, Hq, D;
+    int max_seqlen_q;
+    int own_capacity;
+    int dtype;
+};
+long long cascade_merge_grid(const CascadeMergeArgs& a);
+int launch_cascade_merge(const CascadeMergeArgs& a, hipStream_t stream);
+
 // Returns 0 on success, a hipError_t value on launch failure, -1 for an
 // unsupported (dtype, D) combination.
 int launch_paged_decode(const PagedArgs& a, hipStream_t stream);   // either cache_kind; kCacheFp8E4M3 with a null scale array is -1

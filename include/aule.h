@@ -328,6 +328,88 @@ typedef struct aule_paged_prefill_desc {
 /* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
 int32_t aule_attention_paged_prefill_ex(const aule_paged_prefill_desc* desc);
 
+/* Paged CASCADE (additive): the paged prefill for a batch whose sequences share a prefix -- a system prompt, a few-shot header.   */
+/* The shared keys live behind ONE table, prefix_block_table [max_prefix_blocks] int32, and are read once for the whole batch;     */
+/* block_tables[b] lists only the sequence's OWN blocks and context_lens[b] counts only its OWN keys, the new tokens included.     */
+/* prefix_len is [1] int32 on the DEVICE, read and clamped by the kernel: P = clamp(prefix_len[0], 0, max_prefix_blocks *          */
+/* block_size).  Every other field, every clamp (L_b, s_b, e_b, n_b) and the rows that are written are those of                    */
+/* aule_paged_prefill_desc.  The sequence's keys are the P prefix keys followed by its L_b own keys: token i of sequence b sits at  */
+/* own position p = L_b - n_b + i, sees every prefix key and own key j iff j <= p.  A token with p < 0 gives zeros and lse = -inf   */
+/* whatever the prefix holds; P = 0 gives aule_attention_paged_prefill_ex bit for bit, in out and lse.  A prefix table entry at     */
+/* logical block >= ceil(P / block_size) is never dereferenced, a prefix key row at or beyond P never read.                         */
+/* Three launches on `stream`: the shared-prefix kernel (the rows of all sequences packed densely per KV head, the prefix keys      */
+/* split into nsplit ranges of whole 64-key tiles, one fp32 partial of head_dim + 2 floats per row and split), the paged prefill    */
+/* unchanged on the own keys, and a merge of the partials into its result.  Workspace: at least                                     */
+/*     round16(nsplit * total_tokens * heads_q * (head_dim + 2) * 4) + round16(total_tokens * heads_q * 4)   bytes                   */
+/* (the partials, then the LSE of the own keys) with nsplit from the launch plan -- chosen on the host from the shape and the       */
+/* prefix table's CAPACITY so that row blocks * heads_kv * nsplit covers the device's compute units, at most 32; there is no        */
+/* device-to-host read: size the prefix table to the prefix.  aule_attention_paged_cascade_workspace_size() gives the number; a     */
+/* call without a workspace, or with one that is too small or not 16-byte aligned, allocates on the stream.  No host                */
+/* synchronisation, and no allocation when a workspace is passed: captures into a hipGraph, and a replay sees the CURRENT           */
+/* prefix_len, context_lens, cu_seqlens_q and tables.  With hostile cu_seqlens_q that make two sequences own the same row, that     */
+/* row's value is unspecified (and nothing outside out / lse is written).  Not built: a sliding window, head_dim 256, a backward.   */
+/* The descriptor is checked before the device is needed, like aule_paged_prefill_desc.                                             */
+typedef struct aule_paged_cascade_desc {
+    uint32_t struct_size;      /* = sizeof(aule_paged_cascade_desc) = 184 */
+    int32_t dtype;             /* type of q / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    int32_t cache_dtype;       /* offset 8; AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3 */
+    uint32_t batch;            /* offset 12; sequences */
+    uint32_t heads_q, heads_kv, head_dim;   /* head_dim 32, 64 or 128 */
+    uint32_t block_size;       /* offset 28; any value > 0, of both tables */
+    uint32_t max_blocks;       /* offset 32; columns of block_tables */
+    uint32_t total_tokens;     /* offset 36; rows of q / out; 0: returns 0 without a launch */
+    uint32_t max_seqlen_q;     /* offset 40; >= 1 */
+    float scale;               /* offset 44; 0 -> 1/sqrt(head_dim) */
+    uint32_t max_prefix_blocks;   /* offset 48; entries of prefix_block_table, >= 1 */
+    int32_t device;            /* offset 52; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 56; elements, >= heads_q * head_dim, a multiple of 8 */
+    void* stream;              /* offset 64; hipStream_t */
+    const void* q;             /* offset 72; [total_tokens, heads_q, head_dim], 16-bit */
+    const void* k_cache;       /* offset 80; [num_blocks, block_size, heads_kv, head_dim]: 16-bit of q's dtype, or e4m3fn bytes */
+    const void* v_cache;       /* offset 88; same layout */
+    const int32_t* block_tables;   /* offset 96; [batch, max_blocks]: own blocks */
+    const int32_t* context_lens;   /* offset 104; [batch]: own keys per sequence, the new ones included */
+    const int32_t* cu_seqlens_q;   /* offset 112; [batch + 1], device */
+    void* out;                 /* offset 120; [total_tokens, heads_q, head_dim], 16-bit, contiguous */
+    float* lse;                /* offset 128; optional (NULL to skip): [total_tokens, heads_q] fp32, over prefix and own keys */
+    const float* k_scale;      /* offset 136; [heads_kv] fp32, device (AULE_KV_CACHE_FP8_E4M3), else NULL */
+    const float* v_scale;      /* offset 144 */
+    const int32_t* prefix_block_table;   /* offset 152; [max_prefix_blocks] */
+    const int32_t* prefix_len; /* offset 160; [1], device */
+    void* workspace;           /* offset 168; optional, size from aule_attention_paged_cascade_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 176 */
+} aule_paged_cascade_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
+uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_desc* desc);
+
+/* Merge of two attention states (additive): out_a, out_b [rows, heads, head_dim] fp16 / bf16 are attention outputs of the same    */
+/* queries over two DISJOINT key sets, lse_a, lse_b [rows, heads] fp32 the natural logs of their softmax denominators (the lse of  */
+/* the calls above).  With M = max(lse_a, lse_b) and w_x = exp(lse_x - M):                                                          */
+/*     out = (w_a out_a + w_b out_b) / (w_a + w_b)        lse = M + log(w_a + w_b)                                                  */
+/* the state over the union of the keys.  A side with lse = -inf holds no key: the result is the other side bit for bit; both:     */
+/* zeros and -inf.  The result does not depend on the order of the pair.  out may alias out_a or out_b (a thread reads the 16   */
+/* bytes it writes); lse must NOT overlap lse_a or lse_b -- every thread of a row reads both -- and such a call is refused (-3).    */
+/* head_dim: any multiple of 8; everything contiguous, out_a / out_b / out 16-byte aligned.  One launch, no workspace.             */
+typedef struct aule_merge_states_desc {
+    uint32_t struct_size;      /* = sizeof(aule_merge_states_desc) = 80 */
+    int32_t dtype;             /* AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    uint32_t rows;             /* offset 8; 0: returns 0 without a launch */
+    uint32_t heads;            /* offset 12 */
+    uint32_t head_dim;         /* offset 16; a multiple of 8, at most 1024 */
+    int32_t device;            /* offset 20; HIP device ordinal, -1 = current */
+    void* stream;              /* offset 24; hipStream_t */
+    const void* out_a;         /* offset 32 */
+    const float* lse_a;        /* offset 40 */
+    const void* out_b;         /* offset 48 */
+    const float* lse_b;        /* offset 56 */
+    void* out;                 /* offset 64 */
+    float* lse;                /* offset 72 */
+} aule_merge_states_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_merge_states_ex(const aule_merge_states_desc* desc);
+
 /* Rotary position embedding pass (additive; SURVEY.md 8f row N1, second half).  Replaces the rotation the           */
 /* reference fuses into its kernels: python/aule/triton_flash.py:32-52,:112-131,:165-180 (layout HALF) and            */
 /* shaders/attention_f32.comp:98-111,:132-145 (layout INTERLEAVED).  x is [rows_bh, seq, head_dim] with               */
@@ -448,6 +530,12 @@ int32_t aule_hip_debug_last_forward_route(void);
 /* blocks, work items}; 8 {paired, work per head, work items, workgroups, rounds, heads per round}; 1 and 9 nothing}.     */
 /* Returns the ints written (negative: the capacity needed); -3 bad.  Host logic only, no aule_init().                    */
 int32_t aule_hip_debug_forward_plan(const aule_attn_desc* desc, int32_t* out, int32_t cap);
+/* Debug: the launch plan of the shared-prefix kernel of aule_attention_paged_cascade_ex(desc) as integers -- out = {row blocks    */
+/* of 128 packed rows, 64-key tiles of the prefix table's capacity, nsplit, tiles per split, workgroups, workspace bytes low 32     */
+/* bits, high 32 bits}: split k owns tiles [k * tiles per split, min((k + 1) * tiles per split, tiles)).  Returns the ints written  */
+/* (negative: the capacity needed), 0 for a descriptor with nothing to do; -3 bad.  Host logic only, no aule_init(), no pointer of  */
+/* the descriptor is read.                                                                                                         */
+int32_t aule_hip_debug_shared_prefix_plan(const aule_paged_cascade_desc* desc, int32_t* out, int32_t cap);
 /* Debug: bit mask of the kernels the most recent backward launch of this process ran -- 1 the 5-matmul mode (delta pass, dK/dV kernel  */
 /* spilling its dS, dQ = dS K), 2 / 4 the one-wave-per-SIMD dQ / dK/dV kernel, 8 / 16 their two-waves-per-SIMD predecessors, 32 the    */
 /* fp32 kernels, 64 (with 4) the D = 64 dK/dV instance with two key blocks per wave, 128 the head_dim 256 kernels (with 32 for fp32);  */
