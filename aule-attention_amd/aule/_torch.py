@@ -388,30 +388,39 @@ def quantize_kv_cache_fp8(cache, per_head=True):
     return y.to(torch.float8_e4m3fn), scale
 
 
+def _scale_shape(s, Hkv, name):
+    """The shape rule of k_scale / v_scale: None, a float, a 0-d or [1] tensor (one value for every head) or a [heads_kv] tensor.
+    Returns whether a tensor `s` holds one value."""
+    if not torch.is_tensor(s):
+        return False
+    one = s.dim() == 0 or s.shape == (1,)
+    if not one and s.shape != (Hkv,):
+        raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
+    return one
+
+
 def _fp8_scale(s, Hkv, device, name):
     """None / float / 0-d tensor / [heads_kv] tensor -> [heads_kv] fp32 on `device`, without a device->host copy."""
     if s is None:
         s = 1.0
     if not torch.is_tensor(s):
         return torch.full((Hkv,), float(s), dtype=torch.float32, device=device)
-    if s.dim() == 0 or s.shape == (1,):
+    if _scale_shape(s, Hkv, name):
         return s.to(device=device, dtype=torch.float32).reshape(1).expand(Hkv).contiguous()
-    if s.shape != (Hkv,):
-        raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
     return s.to(device=device, dtype=torch.float32).contiguous()
 
 
 def _paged_cache_is_fp8(op, inputs, k_cache, v_cache, k_scale, v_scale):
-    """The cache-kind rules paged_decode, paged_query and paged_kv_append share -- caches of one dtype, torch.float8_e4m3fn the only FP8 encoding,
+    """The cache-kind rules the paged operations share -- caches of one dtype, torch.float8_e4m3fn the only FP8 encoding,
     fp16 / bf16 inputs (and 16-bit caches) of one dtype, scales with FP8 caches only, head_dim in PAGED_HEAD_DIMS -- as ValueErrors
-    in that operation's words.  inputs: (q,) or (key, value).  Returns whether the caches are FP8."""
-    name, fp8_use, same, with_fp8, dims_of = {
-        "decode": ("paged decode", "the FP8 paged decode takes", "query and caches", "an fp16 / bf16 query", "paged decode"),
-        "append": ("paged KV append", "the paged KV append writes", "key, value and caches", "fp16 / bf16 key and value", "the paged KV cache"),
-        "query": ("paged query", "the FP8 paged query takes", "query and caches", "an fp16 / bf16 query", "the paged query"),
-        "prefill": ("paged prefill", "the FP8 paged prefill takes", "query and caches", "an fp16 / bf16 query", "the paged prefill"),
-        "cascade": ("paged cascade", "the FP8 paged cascade takes", "query and caches", "an fp16 / bf16 query", "the paged cascade"),
-    }[op]
+    in that operation's words.  op: "decode", "query", "prefill", "cascade" (inputs: (q,)) or "append" (inputs: (key, value)).
+    Returns whether the caches are FP8."""
+    if op == "append":
+        name, fp8_use, same, with_fp8, dims_of = ("paged KV append", "the paged KV append writes", "key, value and caches",
+                                                  "fp16 / bf16 key and value", "the paged KV cache")
+    else:
+        name, fp8_use, same, with_fp8 = f"paged {op}", f"the FP8 paged {op} takes", "query and caches", "an fp16 / bf16 query"
+        dims_of = name if op == "decode" else "the " + name
     if k_cache.dtype != v_cache.dtype:
         raise ValueError(f"k_cache ({k_cache.dtype}) and v_cache ({v_cache.dtype}) must have the same dtype")
     other_fp8 = tuple(t for t in (getattr(torch, n, None) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz"))
@@ -429,6 +438,90 @@ def _paged_cache_is_fp8(op, inputs, k_cache, v_cache, k_scale, v_scale):
     if D not in PAGED_HEAD_DIMS:
         raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS} for {dims_of}, got {D}")
     return fp8
+
+
+# What the four paged attention calls have in common, one step each; a call is its steps in its own order (the order of the checks is
+# part of what tests/golden/paged_contract.json records).  op: "decode", "query", "prefill" or "cascade".
+
+def _paged_shapes(q, axes, k_cache, v_cache):
+    """q [`axes`: heads second, head_dim last] against k_cache / v_cache [num_blocks, block_size, Hkv, D]; returns Hkv."""
+    if q.dim() != axes.count(",") + 1 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError(f"expected q [{axes}] and k_cache/v_cache [num_blocks, block_size, Hkv, D]")
+    Hq, D = q.shape[1], q.shape[-1]
+    Hkv, Dk = k_cache.shape[2:]
+    if Dk != D:
+        raise ValueError(f"head_dim mismatch: query={D}, cache={Dk}")
+    if Hkv == 0 or Hq % Hkv != 0:
+        raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
+    return Hkv
+
+
+def _paged_cache_kind(op, q, k_cache, v_cache, k_scale, v_scale):
+    """_paged_cache_is_fp8, then a positive block size (the decode leaves that one to the library)."""
+    fp8 = _paged_cache_is_fp8(op, (q,), k_cache, v_cache, k_scale, v_scale)
+    if k_cache.shape[1] == 0:
+        raise ValueError("block_size must be positive")
+    return fp8
+
+
+def _paged_tables(block_tables, context_lens, B=None):
+    """block_tables [batch, max_blocks >= 1] and context_lens [batch], wherever the caller has them; the batch is B where q states
+    one, else the tables' own.  Returns it."""
+    if not (block_tables.dim() == 2 and block_tables.shape[1] > 0 and B in (None, block_tables.shape[0])
+            and context_lens.shape == (block_tables.shape[0],)):
+        raise ValueError("block_tables must be [batch, max_blocks] and context_lens [batch]")
+    return block_tables.shape[0]
+
+
+def _scale_shapes(fp8, Hkv, k_scale, v_scale):
+    if fp8:
+        _scale_shape(k_scale, Hkv, "k_scale")
+        _scale_shape(v_scale, Hkv, "v_scale")
+
+
+def _needs_device(op, q):
+    if not q.is_cuda:
+        raise _capi.AuleError(f"aule (HIP build): the paged {op} needs ROCm device tensors; there is no CPU fallback")
+
+
+def _int32_on(device, *tensors):
+    """Tables and lengths are read by the kernels: a CPU (or other-GPU) tensor would hand them a foreign pointer."""
+    return [t.to(device=device, dtype=torch.int32).contiguous() for t in tensors]
+
+
+def _paged_problem(d, q, k_cache, v_cache, out, bt, cl, scale, fp8=None):
+    """The fields every paged descriptor has, from tensors on one device: heads and head_dim are q's second and last extent, the batch
+    the tables' first.  fp8: the cache kind, for the kinds that state it in a field.  Returns d."""
+    D = q.shape[-1]
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    if fp8 is not None:
+        d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    d.batch, d.heads_q, d.heads_kv, d.head_dim = bt.shape[0], q.shape[1], k_cache.shape[2], D
+    d.block_size, d.max_blocks = k_cache.shape[1], bt.shape[1]
+    d.scale = _abi_scale(1.0 / math.sqrt(D) if scale is None else scale)
+    d.device = _device_index(q.device)
+    d.stream = _stream_ptr(q.device)
+    d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
+    d.block_tables, d.context_lens = bt.data_ptr(), cl.data_ptr()
+    return d
+
+
+def _attach_workspace(d, size_query, device):
+    """The workspace the library asks for `d`, attached; the caller holds what this returns until the launch is queued."""
+    ws = _workspace(size_query(ctypes.byref(d)), device)
+    if ws is not None:
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    return ws
+
+
+def _attach_scales(d, fp8, k_scale, v_scale, Hkv, device):
+    """The [heads_kv] scale arrays of an FP8 cache, attached; the caller holds what this returns until the launch is queued."""
+    if not fp8:
+        return None
+    ks, vs = _fp8_scale(k_scale, Hkv, device, "k_scale"), _fp8_scale(v_scale, Hkv, device, "v_scale")
+    d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
+    return ks, vs
 
 
 def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1, k_scale=None, v_scale=None):
@@ -449,51 +542,28 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, wi
         if q.shape[2] != 1:
             raise ValueError("PagedAttention only supports single query token")
         q = q.squeeze(2)
-    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise ValueError("expected q [B,Hq,D] and k_cache/v_cache [num_blocks, block_size, Hkv, D]")
-    B, Hq, D = q.shape
-    _, block_size, Hkv, Dk = k_cache.shape
-    if Dk != D:
-        raise ValueError(f"head_dim mismatch: query={D}, cache={Dk}")
-    if Hq % Hkv != 0:
-        raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
+    Hkv = _paged_shapes(q, "B,Hq,D", k_cache, v_cache)
+    B, Hq, _ = q.shape
     fp8 = _paged_cache_is_fp8("decode", (q,), k_cache, v_cache, k_scale, v_scale)
-    if fp8:
-        ks = _fp8_scale(k_scale, Hkv, q.device, "k_scale")
-        vs = _fp8_scale(v_scale, Hkv, q.device, "v_scale")
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
+    d = _capi.PagedFp8Desc() if fp8 else _capi.PagedDesc()
+    held = [_attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device)]   # (what the launch reads, held until it is queued)
     lib = _capi.get_lib()
     q, k_cache, v_cache = q.contiguous(), k_cache.contiguous(), v_cache.contiguous()
     _same_device("paged decode", q, k_cache, v_cache)
-    # block tables / lengths are read by the kernel: a CPU (or other-GPU) tensor would hand it a foreign pointer
-    bt = block_tables.to(device=q.device, dtype=torch.int32).contiguous()
-    cl = context_lens.to(device=q.device, dtype=torch.int32).contiguous()
+    # (unlike its siblings the decode refuses no CPU tensor itself -- aule.flash_attention_paged_amd does -- and looks at the tables
+    # after the move, without a rule about max_blocks or block_size: those are the library's here)
+    bt, cl = _int32_on(q.device, block_tables, context_lens)
     if bt.dim() != 2 or bt.shape[0] != B or cl.shape != (B,):
         raise ValueError("block_tables must be [batch, max_blocks] and context_lens [batch]")
     out = torch.empty_like(q)
     if B * Hq == 0:
         return out
-    d = _capi.PagedFp8Desc() if fp8 else _capi.PagedDesc()
-    d.struct_size = ctypes.sizeof(d)
-    d.dtype = _DTYPES[q.dtype]
-    d.batch, d.heads_q, d.heads_kv, d.head_dim = B, Hq, Hkv, D
-    d.block_size, d.max_blocks = block_size, bt.shape[1]
-    d.scale = _abi_scale(scale)
+    _paged_problem(d, q, k_cache, v_cache, out, bt, cl, scale)
     d.window_size = _window_arg(window_size)
-    d.device = _device_index(q.device)
-    d.stream = _stream_ptr(q.device)
-    d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
-    ws_size = lib.aule_attention_paged_decode_fp8_workspace_size if fp8 else lib.aule_attention_paged_decode_workspace_size
-    ws = _workspace(ws_size(ctypes.byref(d)), q.device)
-    if ws is not None:
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    d.block_tables, d.context_lens = bt.data_ptr(), cl.data_ptr()
-    if fp8:
-        d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
-        _capi.check(lib.aule_attention_paged_decode_fp8_ex(ctypes.byref(d)), "aule_attention_paged_decode_fp8_ex")
-    else:
-        _capi.check(lib.aule_attention_paged_decode_ex(ctypes.byref(d)), "aule_attention_paged_decode_ex")
+    size_query, launch = ("aule_attention_paged_decode_fp8_workspace_size", "aule_attention_paged_decode_fp8_ex") if fp8 else \
+        ("aule_attention_paged_decode_workspace_size", "aule_attention_paged_decode_ex")
+    held.append(_attach_workspace(d, getattr(lib, size_query), q.device))
+    _capi.check(getattr(lib, launch)(ctypes.byref(d)), launch)
     return out
 
 
@@ -514,61 +584,83 @@ def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, win
     of the sum of exp(scaled score) over the visible keys, -inf for a row that sees none -- when return_lse is set.  No
     device->host synchronisation; captures into a graph.  All argument errors are ValueErrors raised before the device is
     touched."""
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise ValueError("expected q [B,Hq,Sq,D] and k_cache/v_cache [num_blocks, block_size, Hkv, D]")
-    B, Hq, Sq, D = q.shape
-    _, block_size, Hkv, Dk = k_cache.shape
-    if Dk != D:
-        raise ValueError(f"head_dim mismatch: query={D}, cache={Dk}")
-    if Hkv == 0 or Hq % Hkv != 0:
-        raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
+    Hkv = _paged_shapes(q, "B,Hq,Sq,D", k_cache, v_cache)
+    B, Hq, Sq, _ = q.shape
     if not 1 <= Sq <= PAGED_QUERY_MAX_TOKENS:
         raise ValueError(f"the paged query takes 1 to {PAGED_QUERY_MAX_TOKENS} query tokens per sequence, got {Sq} "
                          "(longer chunks and per-sequence lengths: flash_attention_paged_prefill)")
-    fp8 = _paged_cache_is_fp8("query", (q,), k_cache, v_cache, k_scale, v_scale)
-    if block_size == 0:
-        raise ValueError("block_size must be positive")
-    if block_tables.dim() != 2 or block_tables.shape[0] != B or block_tables.shape[1] == 0 or context_lens.shape != (B,):
-        raise ValueError("block_tables must be [batch, max_blocks] and context_lens [batch]")
-    if fp8:
-        for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
-            if torch.is_tensor(s) and not (s.dim() == 0 or s.shape == (1,) or s.shape == (Hkv,)):
-                raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
-    if not q.is_cuda:
-        raise _capi.AuleError("aule (HIP build): the paged query needs ROCm device tensors; there is no CPU fallback")
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
+    fp8 = _paged_cache_kind("query", q, k_cache, v_cache, k_scale, v_scale)
+    _paged_tables(block_tables, context_lens, B)
+    _scale_shapes(fp8, Hkv, k_scale, v_scale)
+    _needs_device("query", q)
     lib = _capi.get_lib()
     q, k_cache, v_cache = q.contiguous(), k_cache.contiguous(), v_cache.contiguous()
     _same_device("paged query", q, k_cache, v_cache)
-    bt = block_tables.to(device=q.device, dtype=torch.int32).contiguous()
-    cl = context_lens.to(device=q.device, dtype=torch.int32).contiguous()
+    bt, cl = _int32_on(q.device, block_tables, context_lens)
     out = torch.empty_like(q)
     lse = torch.empty((B, Hq, Sq), device=q.device, dtype=torch.float32) if return_lse else None
     if B * Hq == 0:
         return (out, lse) if return_lse else out
-    d = _capi.PagedQueryDesc()
-    d.struct_size = ctypes.sizeof(d)
-    d.dtype = _DTYPES[q.dtype]
-    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
-    d.batch, d.heads_q, d.heads_kv, d.head_dim, d.seq_q = B, Hq, Hkv, D, Sq
-    d.block_size, d.max_blocks = block_size, bt.shape[1]
-    d.scale = _abi_scale(scale)
-    d.window_size = _window_arg(window_size)
-    d.device = _device_index(q.device)
-    d.stream = _stream_ptr(q.device)
-    d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
+    d = _paged_problem(_capi.PagedQueryDesc(), q, k_cache, v_cache, out, bt, cl, scale, fp8)
+    d.seq_q, d.window_size = Sq, _window_arg(window_size)
     d.lse = lse.data_ptr() if lse is not None else None
-    ws = _workspace(lib.aule_attention_paged_query_workspace_size(ctypes.byref(d)), q.device)
-    if ws is not None:
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    d.block_tables, d.context_lens = bt.data_ptr(), cl.data_ptr()
-    if fp8:
-        ks = _fp8_scale(k_scale, Hkv, q.device, "k_scale")
-        vs = _fp8_scale(v_scale, Hkv, q.device, "v_scale")
-        d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
+    held = (_attach_workspace(d, lib.aule_attention_paged_query_workspace_size, q.device),   # noqa: F841 (until the launch is queued)
+            _attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device))
     _capi.check(lib.aule_attention_paged_query_ex(ctypes.byref(d)), "aule_attention_paged_query_ex")
     return (out, lse) if return_lse else out
+
+
+# The paged prefill in three steps; the paged cascade is the same three with its prefix between them.
+
+def _ragged_kind(op, q, k_cache, v_cache, k_scale, v_scale):
+    """Step 1, what the tensors are: heads_kv and whether the caches are FP8."""
+    Hkv = _paged_shapes(q, "T,Hq,D", k_cache, v_cache)
+    return Hkv, _paged_cache_kind(op, q, k_cache, v_cache, k_scale, v_scale)
+
+
+def _ragged_queries(op, q, fp8, Hkv, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, k_scale, v_scale):
+    """Step 2, the tables and the packed queries, the last rules before the device is needed.  Returns q as the kernels read it -- heads
+    contiguous, the token stride free -- and that stride in elements."""
+    B = _paged_tables(block_tables, context_lens)
+    if not torch.is_tensor(cu_seqlens_q) or cu_seqlens_q.shape != (B + 1,):
+        raise ValueError(f"cu_seqlens_q must be a [batch + 1] = [{B + 1}] tensor")
+    if cu_seqlens_q.dtype != torch.int32:
+        raise ValueError(f"cu_seqlens_q must be int32 (it is read on the device as it stands), got {cu_seqlens_q.dtype}")
+    if max_seqlen_q is not None and (isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 1):
+        raise ValueError(f"max_seqlen_q must be a positive int or None, got {max_seqlen_q!r}")
+    _scale_shapes(fp8, Hkv, k_scale, v_scale)
+    T, Hq, D = q.shape
+    if T > 1 and (q.stride(2) != 1 or q.stride(1) != D) or T <= 1 and not q.is_contiguous():
+        q = q.contiguous()
+    q_stride = q.stride(0) if T > 1 else Hq * D
+    if q_stride < Hq * D or q_stride % 8 != 0 or q.storage_offset() % 8 != 0:
+        raise ValueError(f"q's token stride ({q_stride}) and storage offset ({q.storage_offset()}) must be multiples of 8 elements "
+                         f"and the stride at least heads_q * head_dim = {Hq * D} (16-byte loads); pass q.contiguous()")
+    _needs_device(op, q)
+    return q, q_stride
+
+
+def _ragged_problem(op, d, q, q_stride, fp8, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse):
+    """Step 3, on the device: the tables next to q, max_seqlen_q (read from cu_seqlens_q where the caller gave none), out and lse,
+    and d filled with everything the two kinds share.  Returns (what the call returns, the tensors d points to -- to be held until
+    the launch is queued -- or None where there is nothing to launch)."""
+    k_cache, v_cache = k_cache.contiguous(), v_cache.contiguous()
+    _same_device("paged " + op, q, k_cache, v_cache)
+    bt, cl, cu = _int32_on(q.device, block_tables, context_lens, cu_seqlens_q)
+    B, (T, Hq, D) = bt.shape[0], q.shape
+    if max_seqlen_q is None:
+        # the one documented synchronisation
+        max_seqlen_q = max(int((cu[1:] - cu[:-1]).max().item()), 1) if B > 0 else 1
+    out = torch.empty((T, Hq, D), device=q.device, dtype=q.dtype)
+    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
+    result = (out, lse) if return_lse else out
+    if T * B * Hq == 0:
+        return result, None
+    _paged_problem(d, q, k_cache, v_cache, out, bt, cl, scale, fp8)
+    d.total_tokens, d.max_seqlen_q, d.q_token_stride = T, min(max_seqlen_q, T), q_stride
+    d.lse = lse.data_ptr() if lse is not None else None
+    d.cu_seqlens_q = cu.data_ptr()
+    return result, [k_cache, v_cache, bt, cl, cu]
 
 
 def paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None, window_size=-1,
@@ -591,73 +683,17 @@ def paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q,
     row of zeros and lse = -inf.  Rows that belong to no sequence are never written: out (and lse) come from torch.empty.
     Returns out [total_tokens, heads_q, head_dim], or (out, lse) with lse [total_tokens, heads_q] fp32 when return_lse is
     set.  All argument errors are ValueErrors raised before the device is touched."""
-    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise ValueError("expected q [T,Hq,D] and k_cache/v_cache [num_blocks, block_size, Hkv, D]")
-    T, Hq, D = q.shape
-    _, block_size, Hkv, Dk = k_cache.shape
-    if Dk != D:
-        raise ValueError(f"head_dim mismatch: query={D}, cache={Dk}")
-    if Hkv == 0 or Hq % Hkv != 0:
-        raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
-    fp8 = _paged_cache_is_fp8("prefill", (q,), k_cache, v_cache, k_scale, v_scale)
-    if block_size == 0:
-        raise ValueError("block_size must be positive")
-    if block_tables.dim() != 2 or block_tables.shape[1] == 0 or context_lens.dim() != 1 or context_lens.shape[0] != block_tables.shape[0]:
-        raise ValueError("block_tables must be [batch, max_blocks] and context_lens [batch]")
-    B = block_tables.shape[0]
-    if not torch.is_tensor(cu_seqlens_q) or cu_seqlens_q.shape != (B + 1,):
-        raise ValueError(f"cu_seqlens_q must be a [batch + 1] = [{B + 1}] tensor")
-    if cu_seqlens_q.dtype != torch.int32:
-        raise ValueError(f"cu_seqlens_q must be int32 (it is read on the device as it stands), got {cu_seqlens_q.dtype}")
-    if max_seqlen_q is not None and (isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 1):
-        raise ValueError(f"max_seqlen_q must be a positive int or None, got {max_seqlen_q!r}")
-    if fp8:
-        for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
-            if torch.is_tensor(s) and not (s.dim() == 0 or s.shape == (1,) or s.shape == (Hkv,)):
-                raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
-    if T > 1 and (q.stride(2) != 1 or q.stride(1) != D) or T <= 1 and not q.is_contiguous():
-        q = q.contiguous()
-    q_stride = q.stride(0) if T > 1 else Hq * D
-    if q_stride < Hq * D or q_stride % 8 != 0 or q.storage_offset() % 8 != 0:
-        raise ValueError(f"q's token stride ({q_stride}) and storage offset ({q.storage_offset()}) must be multiples of 8 elements "
-                         f"and the stride at least heads_q * head_dim = {Hq * D} (16-byte loads); pass q.contiguous()")
-    if not q.is_cuda:
-        raise _capi.AuleError("aule (HIP build): the paged prefill needs ROCm device tensors; there is no CPU fallback")
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
+    Hkv, fp8 = _ragged_kind("prefill", q, k_cache, v_cache, k_scale, v_scale)
+    q, q_stride = _ragged_queries("prefill", q, fp8, Hkv, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, k_scale, v_scale)
     lib = _capi.get_lib()
-    k_cache, v_cache = k_cache.contiguous(), v_cache.contiguous()
-    _same_device("paged prefill", q, k_cache, v_cache)
-    bt = block_tables.to(device=q.device, dtype=torch.int32).contiguous()
-    cl = context_lens.to(device=q.device, dtype=torch.int32).contiguous()
-    cu = cu_seqlens_q.to(device=q.device).contiguous()
-    if max_seqlen_q is None:
-        # the one documented synchronisation
-        max_seqlen_q = max(int((cu[1:] - cu[:-1]).max().item()), 1) if B > 0 else 1
-    out = torch.empty((T, Hq, D), device=q.device, dtype=q.dtype)
-    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
-    if T * B * Hq == 0:
-        return (out, lse) if return_lse else out
     d = _capi.PagedPrefillDesc()
-    d.struct_size = ctypes.sizeof(d)
-    d.dtype = _DTYPES[q.dtype]
-    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
-    d.batch, d.heads_q, d.heads_kv, d.head_dim = B, Hq, Hkv, D
-    d.block_size, d.max_blocks = block_size, bt.shape[1]
-    d.total_tokens, d.max_seqlen_q, d.q_token_stride = T, min(max_seqlen_q, T), q_stride
-    d.scale = _abi_scale(scale)
-    d.window_size = _window_arg(window_size)
-    d.device = _device_index(q.device)
-    d.stream = _stream_ptr(q.device)
-    d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
-    d.lse = lse.data_ptr() if lse is not None else None
-    d.block_tables, d.context_lens, d.cu_seqlens_q = bt.data_ptr(), cl.data_ptr(), cu.data_ptr()
-    if fp8:
-        ks = _fp8_scale(k_scale, Hkv, q.device, "k_scale")
-        vs = _fp8_scale(v_scale, Hkv, q.device, "v_scale")
-        d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
-    _capi.check(lib.aule_attention_paged_prefill_ex(ctypes.byref(d)), "aule_attention_paged_prefill_ex")
-    return (out, lse) if return_lse else out
+    result, held = _ragged_problem("prefill", d, q, q_stride, fp8, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q,
+                                   scale, return_lse)
+    if held is not None:
+        d.window_size = _window_arg(window_size)
+        held.append(_attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device))
+        _capi.check(lib.aule_attention_paged_prefill_ex(ctypes.byref(d)), "aule_attention_paged_prefill_ex")
+    return result
 
 
 def paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None,
@@ -677,17 +713,7 @@ def paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tab
     table's capacity (no device->host read): size the table to the prefix.  Returns out, or (out, lse) with return_lse; lse
     covers prefix and own keys.  Not built: a sliding window, head_dim 256, a backward.  All argument errors are ValueErrors
     raised before the device is touched."""
-    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise ValueError("expected q [T,Hq,D] and k_cache/v_cache [num_blocks, block_size, Hkv, D]")
-    T, Hq, D = q.shape
-    _, block_size, Hkv, Dk = k_cache.shape
-    if Dk != D:
-        raise ValueError(f"head_dim mismatch: query={D}, cache={Dk}")
-    if Hkv == 0 or Hq % Hkv != 0:
-        raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
-    fp8 = _paged_cache_is_fp8("cascade", (q,), k_cache, v_cache, k_scale, v_scale)
-    if block_size == 0:
-        raise ValueError("block_size must be positive")
+    Hkv, fp8 = _ragged_kind("cascade", q, k_cache, v_cache, k_scale, v_scale)
     if not torch.is_tensor(prefix_block_table) or prefix_block_table.dim() != 1 or prefix_block_table.shape[0] == 0 \
             or prefix_block_table.dtype not in (torch.int32, torch.int64):
         raise ValueError("prefix_block_table must be a non-empty integer [max_prefix_blocks] tensor")
@@ -697,67 +723,19 @@ def paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tab
                              f"got {prefix_len.dtype} {tuple(prefix_len.shape)}")
     elif isinstance(prefix_len, bool) or not isinstance(prefix_len, int) or not -2 ** 31 <= prefix_len < 2 ** 31:
         raise ValueError(f"prefix_len must be an int32 [1] tensor or a Python int, got {prefix_len!r}")
-    if block_tables.dim() != 2 or block_tables.shape[1] == 0 or context_lens.dim() != 1 or context_lens.shape[0] != block_tables.shape[0]:
-        raise ValueError("block_tables must be [batch, max_blocks] and context_lens [batch]")
-    B = block_tables.shape[0]
-    if not torch.is_tensor(cu_seqlens_q) or cu_seqlens_q.shape != (B + 1,):
-        raise ValueError(f"cu_seqlens_q must be a [batch + 1] = [{B + 1}] tensor")
-    if cu_seqlens_q.dtype != torch.int32:
-        raise ValueError(f"cu_seqlens_q must be int32 (it is read on the device as it stands), got {cu_seqlens_q.dtype}")
-    if max_seqlen_q is not None and (isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 1):
-        raise ValueError(f"max_seqlen_q must be a positive int or None, got {max_seqlen_q!r}")
-    if fp8:
-        for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
-            if torch.is_tensor(s) and not (s.dim() == 0 or s.shape == (1,) or s.shape == (Hkv,)):
-                raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
-    if T > 1 and (q.stride(2) != 1 or q.stride(1) != D) or T <= 1 and not q.is_contiguous():
-        q = q.contiguous()
-    q_stride = q.stride(0) if T > 1 else Hq * D
-    if q_stride < Hq * D or q_stride % 8 != 0 or q.storage_offset() % 8 != 0:
-        raise ValueError(f"q's token stride ({q_stride}) and storage offset ({q.storage_offset()}) must be multiples of 8 elements "
-                         f"and the stride at least heads_q * head_dim = {Hq * D} (16-byte loads); pass q.contiguous()")
-    if not q.is_cuda:
-        raise _capi.AuleError("aule (HIP build): the paged cascade needs ROCm device tensors; there is no CPU fallback")
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
+    q, q_stride = _ragged_queries("cascade", q, fp8, Hkv, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, k_scale, v_scale)
     lib = _capi.get_lib()
-    k_cache, v_cache = k_cache.contiguous(), v_cache.contiguous()
-    _same_device("paged cascade", q, k_cache, v_cache)
-    pbt = prefix_block_table.to(device=q.device, dtype=torch.int32).contiguous()
-    plen = prefix_len.to(device=q.device) if torch.is_tensor(prefix_len) else torch.tensor([prefix_len], device=q.device, dtype=torch.int32)
-    bt = block_tables.to(device=q.device, dtype=torch.int32).contiguous()
-    cl = context_lens.to(device=q.device, dtype=torch.int32).contiguous()
-    cu = cu_seqlens_q.to(device=q.device).contiguous()
-    if max_seqlen_q is None:
-        # the one documented synchronisation
-        max_seqlen_q = max(int((cu[1:] - cu[:-1]).max().item()), 1) if B > 0 else 1
-    out = torch.empty((T, Hq, D), device=q.device, dtype=q.dtype)
-    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
-    if T * B * Hq == 0:
-        return (out, lse) if return_lse else out
     d = _capi.PagedCascadeDesc()
-    d.struct_size = ctypes.sizeof(d)
-    d.dtype = _DTYPES[q.dtype]
-    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
-    d.batch, d.heads_q, d.heads_kv, d.head_dim = B, Hq, Hkv, D
-    d.block_size, d.max_blocks, d.max_prefix_blocks = block_size, bt.shape[1], pbt.shape[0]
-    d.total_tokens, d.max_seqlen_q, d.q_token_stride = T, min(max_seqlen_q, T), q_stride
-    d.scale = _abi_scale(scale)
-    d.device = _device_index(q.device)
-    d.stream = _stream_ptr(q.device)
-    d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()
-    d.lse = lse.data_ptr() if lse is not None else None
-    d.block_tables, d.context_lens, d.cu_seqlens_q = bt.data_ptr(), cl.data_ptr(), cu.data_ptr()
-    d.prefix_block_table, d.prefix_len = pbt.data_ptr(), plen.data_ptr()
-    ws = _workspace(lib.aule_attention_paged_cascade_workspace_size(ctypes.byref(d)), q.device)
-    if ws is not None:
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    if fp8:
-        ks = _fp8_scale(k_scale, Hkv, q.device, "k_scale")
-        vs = _fp8_scale(v_scale, Hkv, q.device, "v_scale")
-        d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
-    _capi.check(lib.aule_attention_paged_cascade_ex(ctypes.byref(d)), "aule_attention_paged_cascade_ex")
-    return (out, lse) if return_lse else out
+    result, held = _ragged_problem("cascade", d, q, q_stride, fp8, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q,
+                                   scale, return_lse)
+    if held is not None:
+        pbt, = _int32_on(q.device, prefix_block_table)
+        plen = prefix_len.to(device=q.device) if torch.is_tensor(prefix_len) else torch.tensor([prefix_len], device=q.device, dtype=torch.int32)
+        d.max_prefix_blocks, d.prefix_block_table, d.prefix_len = pbt.shape[0], pbt.data_ptr(), plen.data_ptr()
+        held += [pbt, plen, _attach_workspace(d, lib.aule_attention_paged_cascade_workspace_size, q.device),
+                 _attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device)]
+        _capi.check(lib.aule_attention_paged_cascade_ex(ctypes.byref(d)), "aule_attention_paged_cascade_ex")
+    return result
 
 
 def merge_states(out_a, lse_a, out_b, lse_b):
@@ -889,10 +867,7 @@ def paged_kv_append(key, value, k_cache, v_cache, slot_mapping, k_scale=None, v_
             raise ValueError(f"positions must be an integer tensor of shape [{T}]")
         if cos.shape[-1] != D // 2 or sin.shape[-1] != D // 2:
             raise ValueError(f"cos/sin must have shape [..., {D // 2}], got {tuple(cos.shape)} / {tuple(sin.shape)}")
-    if fp8:
-        for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
-            if torch.is_tensor(s) and not (s.dim() == 0 or s.shape == (1,) or s.shape == (Hkv,)):
-                raise ValueError(f"{name} must be a float, a 0-d tensor or a [heads_kv] = [{Hkv}] tensor, got shape {tuple(s.shape)}")
+    _scale_shapes(fp8, Hkv, k_scale, v_scale)
     if not key.is_cuda:
         raise _capi.AuleError("aule (HIP build): the paged KV append needs ROCm device tensors; there is no CPU fallback")
     _same_device("paged KV append", key, value, k_cache, v_cache)
@@ -915,10 +890,7 @@ def paged_kv_append(key, value, k_cache, v_cache, slot_mapping, k_scale=None, v_
     d.stream = _stream_ptr(dev)
     d.key, d.value, d.k_cache, d.v_cache = key.data_ptr(), value.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
     d.slot_mapping = slots.data_ptr()
-    if fp8:
-        ks = _fp8_scale(k_scale, Hkv, dev, "k_scale")
-        vs = _fp8_scale(v_scale, Hkv, dev, "v_scale")
-        d.k_scale, d.v_scale = ks.data_ptr(), vs.data_ptr()
+    scales = _attach_scales(d, fp8, k_scale, v_scale, Hkv, dev)   # noqa: F841 (held until the launch is queued)
     if rope:
         c, s = _rope_tables(cos, sin, D, dev)
         pos = positions.to(device=dev, dtype=torch.int64).contiguous()

@@ -71,6 +71,18 @@ static_assert(sizeof(aule_paged_cascade_desc) == 184 && offsetof(aule_paged_casc
                   offsetof(aule_paged_cascade_desc, prefix_block_table) == 152 && offsetof(aule_paged_cascade_desc, prefix_len) == 160 &&
                   offsetof(aule_paged_cascade_desc, workspace) == 168 && offsetof(aule_paged_cascade_desc, workspace_bytes) == 176,
               "aule_paged_cascade_desc layout is part of the ABI");
+#define AULE_SAME_OFFSET(field) (offsetof(aule_paged_cascade_desc, field) == offsetof(aule_paged_prefill_desc, field))
+static_assert(AULE_SAME_OFFSET(struct_size) && AULE_SAME_OFFSET(dtype) && AULE_SAME_OFFSET(cache_dtype) && AULE_SAME_OFFSET(batch) && AULE_SAME_OFFSET(heads_q) &&
+                  AULE_SAME_OFFSET(heads_kv) && AULE_SAME_OFFSET(head_dim) && AULE_SAME_OFFSET(block_size) && AULE_SAME_OFFSET(max_blocks) &&
+                  AULE_SAME_OFFSET(total_tokens) && AULE_SAME_OFFSET(max_seqlen_q) && AULE_SAME_OFFSET(scale) &&
+                  offsetof(aule_paged_cascade_desc, max_prefix_blocks) == offsetof(aule_paged_prefill_desc, window_size) && AULE_SAME_OFFSET(device) &&
+                  AULE_SAME_OFFSET(q_token_stride) && AULE_SAME_OFFSET(stream) && AULE_SAME_OFFSET(q) && AULE_SAME_OFFSET(k_cache) && AULE_SAME_OFFSET(v_cache) &&
+                  AULE_SAME_OFFSET(block_tables) && AULE_SAME_OFFSET(context_lens) && AULE_SAME_OFFSET(cu_seqlens_q) && AULE_SAME_OFFSET(out) &&
+                  AULE_SAME_OFFSET(lse) && AULE_SAME_OFFSET(k_scale) && AULE_SAME_OFFSET(v_scale) &&
+                  offsetof(aule_paged_cascade_desc, prefix_block_table) == sizeof(aule_paged_prefill_desc),
+              "aule_paged_cascade_desc starts with aule_paged_prefill_desc but for the word at 48, max_prefix_blocks where that has window_size "
+              "(its launch arguments are filled through that prefix, the window dropped)");
+#undef AULE_SAME_OFFSET
 static_assert(sizeof(aule_merge_states_desc) == 80 && offsetof(aule_merge_states_desc, rows) == 8 &&
                   offsetof(aule_merge_states_desc, heads) == 12 && offsetof(aule_merge_states_desc, head_dim) == 16 &&
                   offsetof(aule_merge_states_desc, device) == 20 && offsetof(aule_merge_states_desc, stream) == 24 &&
@@ -728,8 +740,8 @@ int32_t aule_attention_forward_gravity(aule_tensor_handle, aule_tensor_handle, a
 // The descriptor checkers, one per kind: pure host logic (no lock, no g_init, no pointer dereferenced).  Each answers nullptr
 // or the reason the descriptor is refused (kv_append_error further down is the model); a reason that carries values is
 // formatted into the caller's Reason.  What has nothing to do is a predicate of its own per kind; null pointers, workspace
-// sizes and the size limits of the launches are rules of the launch entries (paged_query_desc_error states the pointer rules
-// too, for its launch entry only, as kv_append_error does).
+// sizes and the size limits of the launches are rules of the launch entries (the paged checkers and kv_append_error state the
+// pointer rules too, for their launch entries only).  A rule that several kinds have is a function of its own, asked by each.
 struct Reason { char text[128]; };
 static const char kBadDescriptor[] = "bad descriptor (struct_size mismatch)";
 
@@ -741,9 +753,22 @@ static const char* reasonf(Reason& r, const char* fmt, ...) {
     return r.text;
 }
 
+// The end of every launch entry: 0, or -4 and "<what> failed: " the HIP error, or that no kernel takes the arguments (rc < 0).
+static int32_t launched(const char* what, int rc) {
+    if (rc == 0) return 0;
+    set_error("%s failed: %s", what, rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
+    return -4;
+}
+
 // aule_attn_desc and aule_attn_bwd_desc state the problem in the same leading fields (the layout asserts at the top of this file):
 // both are checked and read through the forward descriptor's; `size` is the kind's own sizeof.
 static const aule_attn_desc* attn_prefix(const aule_attn_bwd_desc* d) { return reinterpret_cast<const aule_attn_desc*>(d); }
+
+// (the dense and the paged kinds alike)
+static const char* head_ratio_error(uint32_t heads_q, uint32_t heads_kv, Reason& why) {
+    if (heads_kv == 0 || heads_q % heads_kv != 0) return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", heads_q, heads_kv);
+    return nullptr;
+}
 
 // plan_hook: the three forward plan hooks still answer for a bottom-right mask with seq_k < seq_q (tests/test_capi_sanitizers.py
 // pins what they say there); every other reader refuses it like the launch.
@@ -756,9 +781,7 @@ static const char* attn_desc_error(const aule_attn_desc* d, size_t size, Reason&
     if (d->dtype < 0 || d->dtype > 2) return reasonf(why, "unknown dtype %d", d->dtype);
     if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128 && d->head_dim != 256)
         return reasonf(why, "head_dim %u unsupported (32, 64, 128 or 256; pad to the next size)", d->head_dim);
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0)
-        return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
-    return nullptr;   // (window_size: any value is accepted, <= 0 means full attention)
+    return head_ratio_error(d->heads_q, d->heads_kv, why);   // (window_size: any value is accepted, <= 0 means full attention)
 }
 
 static bool fwd_nothing_to_do(const aule_attn_desc* d) { return (uint64_t)d->batch * d->heads_q * d->seq_q == 0; }  // no output element
@@ -880,12 +903,7 @@ static int32_t forward_impl(const aule_attn_desc* d, const aule_attn_rope* rope)
             return -3;
         }
     }
-    rc = aule_hip::launch_fwd(a, (hipStream_t)d->stream);
-    if (rc != 0) {
-        set_error("Attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
-        return -4;
-    }
-    return 0;
+    return launched("Attention", aule_hip::launch_fwd(a, (hipStream_t)d->stream));
 }
 
 int32_t aule_attention_forward_ex(const aule_attn_desc* d) {
@@ -912,21 +930,106 @@ int32_t aule_attention_forward_rope_fusable(const aule_attn_desc* d, const aule_
     return fill_rope_args(rope, d->head_dim, a) && aule_hip::fwd_rope_fusable(a) ? 1 : 0;
 }
 
-// The four paged entry points.  aule_paged_fp8_desc is aule_paged_desc field for field plus the two scale pointers (the
-// layout asserts at the top of this file), so both kinds are checked and read through the common prefix.
+// The paged entry points.  Each rule of their descriptors -- its condition and its message -- is stated once, in the pieces below, and
+// the checker of a kind is the pieces in that kind's order.  The kinds name their fields alike (the pieces are templates over the
+// descriptor); aule_paged_fp8_desc is aule_paged_desc field for field plus the two scale pointers, aule_paged_query_desc that plus
+// lse, seq_q and cache_dtype, and aule_paged_cascade_desc is aule_paged_prefill_desc but for the word at 48 plus the prefix and the
+// workspace (the layout asserts at the top of this file), so those kinds are read through the common prefix.
 static const aule_paged_desc* paged_prefix(const aule_paged_fp8_desc* d) { return reinterpret_cast<const aule_paged_desc*>(d); }
+static const aule_paged_prefill_desc* prefill_prefix(const aule_paged_cascade_desc* d) { return reinterpret_cast<const aule_paged_prefill_desc*>(d); }
 
-static const char* paged_desc_error(const aule_paged_desc* d, bool fp8, Reason& why) {
-    if (d == nullptr || d->struct_size != (fp8 ? sizeof(aule_paged_fp8_desc) : sizeof(aule_paged_desc))) return kBadDescriptor;
-    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return fp8 ? "dtype (of q / out) must be fp16 or bf16" : "dtype must be fp16 or bf16";
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return reasonf(why, "head_dim %u unsupported (32, 64 or 128)", d->head_dim);
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0)
-        return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
-    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return "bad block_size / max_blocks";
+static bool is_16_bit(int32_t dtype) { return dtype == AULE_DTYPE_F16 || dtype == AULE_DTYPE_BF16; }
+static const char kDtypeOfQ[] = "dtype (of q / out) must be fp16 or bf16";
+static bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+static const char* cache_dtype_error(int32_t cache_dtype) {
+    if (cache_dtype != AULE_KV_CACHE_SAME && cache_dtype != AULE_KV_CACHE_FP8_E4M3) return "cache_dtype must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3";
     return nullptr;
 }
 
+static const char* scale_pointer_error(bool fp8, const float* k_scale, const float* v_scale) {
+    if (fp8 && (!k_scale || !v_scale)) return "null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)";
+    if (!fp8 && (k_scale || v_scale)) return "k_scale / v_scale apply to FP8 caches only; a 16-bit cache holds the values themselves";
+    return nullptr;
+}
+
+extern "C++" {   // (templates, inside this file's extern "C")
+// the kinds with a cache_dtype field (every one but the decode's two)
+template <class Desc>
+static const char* paged_dtype_error(const Desc* d) {
+    if (!is_16_bit(d->dtype)) return kDtypeOfQ;
+    return cache_dtype_error(d->cache_dtype);
+}
+
+template <class Desc>
+static const char* paged_heads_error(const Desc* d, Reason& why) {
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return reasonf(why, "head_dim %u unsupported (32, 64 or 128)", d->head_dim);
+    return head_ratio_error(d->heads_q, d->heads_kv, why);
+}
+
+static bool bad_block_table(uint32_t block_size, uint32_t blocks) { return block_size == 0 || blocks == 0 || (uint64_t)block_size * blocks >= (1ull << 30); }
+
+template <class Desc>
+static const char* paged_blocks_error(const Desc* d) { return bad_block_table(d->block_size, d->max_blocks) ? "bad block_size / max_blocks" : nullptr; }
+
+// the packed ragged queries of the prefill and the cascade
+template <class Desc>
+static const char* ragged_query_error(const Desc* d, Reason& why) {
+    if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
+    if (d->q_token_stride < (int64_t)d->heads_q * d->head_dim)
+        return reasonf(why, "q_token_stride (%lld) is smaller than a token (heads_q * head_dim = %llu elements)", (long long)d->q_token_stride,
+                       (unsigned long long)d->heads_q * d->head_dim);
+    if (d->q_token_stride % 8 != 0) return reasonf(why, "q_token_stride (%lld) must be a multiple of 8 elements (16-byte loads)", (long long)d->q_token_stride);
+    if (d->batch >= (1u << 30) || d->total_tokens >= (1u << 30)) return "batch / total_tokens too large";
+    if (((uint64_t)d->total_tokens + 128) * (d->heads_q / d->heads_kv) > 0x7fffffffull) return "total_tokens * (heads_q / heads_kv) too large (packed rows are counted in 32 bits)";
+    return nullptr;
+}
+
+template <class Desc>
+static bool ragged_nothing_to_do(const Desc* d) { return d->total_tokens == 0 || (uint64_t)d->batch * d->heads_q == 0; }
+
+// The pointers of a call that has something to do: the six tensors every kind has (`more_tensors`: whether the kind's own are all
+// there), then the scale pair; paged_alignment_error: for the kernels that load 16 bytes at a time.
+template <class Desc>
+static const char* paged_pointer_error(const Desc* d, bool more_tensors, bool fp8, const float* k_scale, const float* v_scale) {
+    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->out || !more_tensors) return "null tensor pointer";
+    return scale_pointer_error(fp8, k_scale, v_scale);
+}
+
+template <class Desc>
+static const char* paged_alignment_error(const Desc* d) {
+    if (misaligned(d->q) || misaligned(d->out) || misaligned(d->k_cache) || misaligned(d->v_cache)) return "q, out and the caches must be 16-byte aligned";
+    return nullptr;
+}
+
+// what the prefill and the cascade share, before and after their own rules
+template <class Desc>
+static const char* ragged_desc_error(const Desc* d, Reason& why) {
+    if (const char* e = paged_dtype_error(d)) return e;
+    if (const char* e = paged_heads_error(d, why)) return e;
+    return paged_blocks_error(d);
+}
+
+template <class Desc>
+static const char* ragged_pointer_error(const Desc* d, bool more_tensors) {
+    if (const char* e = paged_pointer_error(d, d->cu_seqlens_q && more_tensors, d->cache_dtype == AULE_KV_CACHE_FP8_E4M3, d->k_scale, d->v_scale)) return e;
+    return paged_alignment_error(d);
+}
+}   // extern "C++"
+
 static bool paged_nothing_to_do(const aule_paged_desc* d) { return (uint64_t)d->batch * d->heads_q == 0; }
+
+// The decode's two kinds (no cache_dtype: the kind says it, and names the dtype in its own words).  One checker for their two readers;
+// `launch`: the pointer rules of a call that has something to do as well (the size queries read no pointer).
+static const char* paged_desc_error(const aule_paged_desc* d, bool fp8, bool launch, Reason& why) {
+    if (d == nullptr || d->struct_size != (fp8 ? sizeof(aule_paged_fp8_desc) : sizeof(aule_paged_desc))) return kBadDescriptor;
+    if (!is_16_bit(d->dtype)) return fp8 ? kDtypeOfQ : "dtype must be fp16 or bf16";
+    if (const char* e = paged_heads_error(d, why)) return e;
+    if (const char* e = paged_blocks_error(d)) return e;
+    if (!launch || paged_nothing_to_do(d)) return nullptr;
+    const aule_paged_fp8_desc* d8 = reinterpret_cast<const aule_paged_fp8_desc*>(d);   // (read where `d` is one)
+    return paged_pointer_error(d, true, fp8, fp8 ? d8->k_scale : nullptr, fp8 ? d8->v_scale : nullptr);
+}
 
 // (`d` passed paged_desc_error: an FP8 descriptor really is one)
 static void fill_paged_args(const aule_paged_desc* d, bool fp8, aule_hip::PagedArgs& a) {
@@ -950,30 +1053,17 @@ static int32_t paged_decode_impl(const aule_paged_desc* d, bool fp8) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (!initialised()) return -1;
     Reason text;
-    if (const char* why = paged_desc_error(d, fp8, text)) {
+    if (const char* why = paged_desc_error(d, fp8, true, text)) {
         set_error("%s failed: %s", what, why);
         return -3;
     }
     if (paged_nothing_to_do(d)) return 0;
-    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->out) {
-        set_error("%s failed: null tensor pointer", what);
-        return -3;
-    }
     aule_hip::PagedArgs a;
     fill_paged_args(d, fp8, a);
-    if (fp8 && (!a.k_scale || !a.v_scale)) {
-        set_error("%s failed: null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)", what);
-        return -3;
-    }
     DeviceGuard g(d->device);
     int rc = ensure_configured();
     if (rc) return rc;
-    rc = aule_hip::launch_paged_decode(a, (hipStream_t)d->stream);
-    if (rc != 0) {
-        set_error("%s failed: %s", what, rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
-        return -4;
-    }
-    return 0;
+    return launched(what, aule_hip::launch_paged_decode(a, (hipStream_t)d->stream));
 }
 
 int32_t aule_attention_paged_decode_ex(const aule_paged_desc* d) {
@@ -986,27 +1076,18 @@ int32_t aule_attention_paged_decode_fp8_ex(const aule_paged_fp8_desc* d) {
     return paged_decode_impl(paged_prefix(d), true);
 }
 
-// The paged query: aule_paged_fp8_desc field for field, then lse, seq_q and cache_dtype (the layout asserts at the top of this
-// file).  One checker for its two readers; `launch`: the pointer rules of a call that has something to do as well (the size
-// query reads no pointer).
+// The paged query.  One checker for its two readers; `launch`: the pointer rules of a call that has something to do as well (the
+// size query reads no pointer).
 static bool paged_query_nothing_to_do(const aule_paged_query_desc* d) { return (uint64_t)d->batch * d->heads_q == 0; }
 
 static const char* paged_query_desc_error(const aule_paged_query_desc* d, bool launch, Reason& why) {
     if (d == nullptr || d->struct_size != sizeof(aule_paged_query_desc)) return kBadDescriptor;
-    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return "dtype (of q / out) must be fp16 or bf16";
-    if (d->cache_dtype != AULE_KV_CACHE_SAME && d->cache_dtype != AULE_KV_CACHE_FP8_E4M3)
-        return "cache_dtype must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3";
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return reasonf(why, "head_dim %u unsupported (32, 64 or 128)", d->head_dim);
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0)
-        return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
+    if (const char* e = paged_dtype_error(d)) return e;
+    if (const char* e = paged_heads_error(d, why)) return e;
     if (d->seq_q == 0 || d->seq_q > 64) return reasonf(why, "seq_q %u unsupported (1 to 64 query tokens per sequence)", d->seq_q);
-    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return "bad block_size / max_blocks";
+    if (const char* e = paged_blocks_error(d)) return e;
     if (!launch || paged_query_nothing_to_do(d)) return nullptr;
-    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->out) return "null tensor pointer";
-    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
-    if (fp8 && (!d->k_scale || !d->v_scale)) return "null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)";
-    if (!fp8 && (d->k_scale || d->v_scale)) return "k_scale / v_scale apply to FP8 caches only; a 16-bit cache holds the values themselves";
-    return nullptr;
+    return paged_pointer_error(d, true, d->cache_dtype == AULE_KV_CACHE_FP8_E4M3, d->k_scale, d->v_scale);
 }
 
 // (`d` passed paged_query_desc_error)
@@ -1031,48 +1112,28 @@ int32_t aule_attention_paged_query_ex(const aule_paged_query_desc* d) {
     DeviceGuard g(d->device);
     int rc = ensure_configured();
     if (rc) return rc;
-    rc = aule_hip::launch_paged_query(a, (hipStream_t)d->stream);
-    if (rc != 0) {
-        set_error("Paged query attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
-        return -4;
-    }
-    return 0;
+    return launched("Paged query attention", aule_hip::launch_paged_query(a, (hipStream_t)d->stream));
 }
 
-// The paged prefill: a descriptor of its own (no workspace, packed ragged queries).  One checker, one reader; its only reader is
-// the launch entry, so the pointer rules of a call that has something to do are stated here too.  Host logic only, and the entry
-// asks it before it needs the device.
-static bool paged_prefill_nothing_to_do(const aule_paged_prefill_desc* d) {
-    return d->total_tokens == 0 || (uint64_t)d->batch * d->heads_q == 0;
-}
-
+// The paged prefill and the paged cascade: packed ragged queries, a descriptor family of its own.  `launch`: the pointer rules of a
+// call that has something to do as well (the cascade's size query and plan hook read no pointer).  Host logic only, and the launch
+// entries ask before they need the device.
 static const char* paged_prefill_desc_error(const aule_paged_prefill_desc* d, Reason& why) {
     if (d == nullptr || d->struct_size != sizeof(aule_paged_prefill_desc)) return kBadDescriptor;
-    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return "dtype (of q / out) must be fp16 or bf16";
-    if (d->cache_dtype != AULE_KV_CACHE_SAME && d->cache_dtype != AULE_KV_CACHE_FP8_E4M3)
-        return "cache_dtype must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3";
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return reasonf(why, "head_dim %u unsupported (32, 64 or 128)", d->head_dim);
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0)
-        return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
-    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return "bad block_size / max_blocks";
-    if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
-    if (d->q_token_stride < (int64_t)d->heads_q * d->head_dim)
-        return reasonf(why, "q_token_stride (%lld) is smaller than a token (heads_q * head_dim = %llu elements)", (long long)d->q_token_stride,
-                       (unsigned long long)d->heads_q * d->head_dim);
-    if (d->q_token_stride % 8 != 0) return reasonf(why, "q_token_stride (%lld) must be a multiple of 8 elements (16-byte loads)", (long long)d->q_token_stride);
-    if (d->batch >= (1u << 30) || d->total_tokens >= (1u << 30)) return "batch / total_tokens too large";
-    if (((uint64_t)d->total_tokens + 128) * (d->heads_q / d->heads_kv) > 0x7fffffffull) return "total_tokens * (heads_q / heads_kv) too large (packed rows are counted in 32 bits)";
-    if (paged_prefill_nothing_to_do(d)) return nullptr;
-    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->cu_seqlens_q || !d->out) return "null tensor pointer";
-    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
-    if (fp8 && (!d->k_scale || !d->v_scale)) return "null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)";
-    if (!fp8 && (d->k_scale || d->v_scale)) return "k_scale / v_scale apply to FP8 caches only; a 16-bit cache holds the values themselves";
-    const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
-    if (misaligned(d->q) || misaligned(d->out) || misaligned(d->k_cache) || misaligned(d->v_cache)) return "q, out and the caches must be 16-byte aligned";
-    return nullptr;
+    if (const char* e = ragged_desc_error(d, why)) return e;
+    if (const char* e = ragged_query_error(d, why)) return e;
+    return ragged_nothing_to_do(d) ? nullptr : ragged_pointer_error(d, true);
 }
 
-// (`d` passed paged_prefill_desc_error)
+static const char* paged_cascade_desc_error(const aule_paged_cascade_desc* d, bool launch, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_paged_cascade_desc)) return kBadDescriptor;
+    if (const char* e = ragged_desc_error(d, why)) return e;
+    if (bad_block_table(d->block_size, d->max_prefix_blocks)) return "bad block_size / max_prefix_blocks";
+    if (const char* e = ragged_query_error(d, why)) return e;
+    return !launch || ragged_nothing_to_do(d) ? nullptr : ragged_pointer_error(d, d->prefix_block_table && d->prefix_len);
+}
+
+// (`d` passed paged_prefill_desc_error, or is the prefix of a cascade descriptor that passed its checker: then the window is not `d`'s to state)
 static void fill_paged_prefill_args(const aule_paged_prefill_desc* d, aule_hip::PagedPrefillArgs& a) {
     a.q = d->q; a.k_cache = d->k_cache; a.v_cache = d->v_cache; a.out = d->out; a.lse = d->lse;
     a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
@@ -1097,7 +1158,7 @@ int32_t aule_attention_paged_prefill_ex(const aule_paged_prefill_desc* d) {
         set_error("Paged prefill attention failed: %s", why);
         return -3;
     }
-    if (paged_prefill_nothing_to_do(d)) return 0;
+    if (ragged_nothing_to_do(d)) return 0;
     if (!initialised()) return -1;
     aule_hip::PagedPrefillArgs a;
     fill_paged_prefill_args(d, a);
@@ -1108,63 +1169,15 @@ int32_t aule_attention_paged_prefill_ex(const aule_paged_prefill_desc* d) {
     DeviceGuard g(d->device);
     int rc = ensure_configured();
     if (rc) return rc;
-    rc = aule_hip::launch_paged_prefill(a, (hipStream_t)d->stream);
-    if (rc != 0) {
-        set_error("Paged prefill attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
-        return -4;
-    }
-    return 0;
+    return launched("Paged prefill attention", aule_hip::launch_paged_prefill(a, (hipStream_t)d->stream));
 }
 
-// The paged cascade: the prefill's fields without the window, plus the shared prefix and the workspace.  One checker for its three
-// readers; `launch`: the pointer rules of a call that has something to do as well (the size query and the plan hook read no pointer).
-static bool paged_cascade_nothing_to_do(const aule_paged_cascade_desc* d) {
-    return d->total_tokens == 0 || (uint64_t)d->batch * d->heads_q == 0;
-}
-
-static const char* paged_cascade_desc_error(const aule_paged_cascade_desc* d, bool launch, Reason& why) {
-    if (d == nullptr || d->struct_size != sizeof(aule_paged_cascade_desc)) return kBadDescriptor;
-    if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return "dtype (of q / out) must be fp16 or bf16";
-    if (d->cache_dtype != AULE_KV_CACHE_SAME && d->cache_dtype != AULE_KV_CACHE_FP8_E4M3)
-        return "cache_dtype must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3";
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return reasonf(why, "head_dim %u unsupported (32, 64 or 128)", d->head_dim);
-    if (d->heads_kv == 0 || d->heads_q % d->heads_kv != 0)
-        return reasonf(why, "heads_q (%u) must be divisible by heads_kv (%u)", d->heads_q, d->heads_kv);
-    if (d->block_size == 0 || d->max_blocks == 0 || (uint64_t)d->block_size * d->max_blocks >= (1ull << 30)) return "bad block_size / max_blocks";
-    if (d->max_prefix_blocks == 0 || (uint64_t)d->block_size * d->max_prefix_blocks >= (1ull << 30)) return "bad block_size / max_prefix_blocks";
-    if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
-    if (d->q_token_stride < (int64_t)d->heads_q * d->head_dim)
-        return reasonf(why, "q_token_stride (%lld) is smaller than a token (heads_q * head_dim = %llu elements)", (long long)d->q_token_stride,
-                       (unsigned long long)d->heads_q * d->head_dim);
-    if (d->q_token_stride % 8 != 0) return reasonf(why, "q_token_stride (%lld) must be a multiple of 8 elements (16-byte loads)", (long long)d->q_token_stride);
-    if (d->batch >= (1u << 30) || d->total_tokens >= (1u << 30)) return "batch / total_tokens too large";
-    if (((uint64_t)d->total_tokens + 128) * (d->heads_q / d->heads_kv) > 0x7fffffffull) return "total_tokens * (heads_q / heads_kv) too large (packed rows are counted in 32 bits)";
-    if (!launch || paged_cascade_nothing_to_do(d)) return nullptr;
-    if (!d->q || !d->k_cache || !d->v_cache || !d->block_tables || !d->context_lens || !d->cu_seqlens_q || !d->out || !d->prefix_block_table || !d->prefix_len)
-        return "null tensor pointer";
-    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
-    if (fp8 && (!d->k_scale || !d->v_scale)) return "null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)";
-    if (!fp8 && (d->k_scale || d->v_scale)) return "k_scale / v_scale apply to FP8 caches only; a 16-bit cache holds the values themselves";
-    const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
-    if (misaligned(d->q) || misaligned(d->out) || misaligned(d->k_cache) || misaligned(d->v_cache)) return "q, out and the caches must be 16-byte aligned";
-    return nullptr;
-}
-
-// (`d` passed paged_cascade_desc_error) the two kernels' arguments; part / lse of the workspace are the launch entry's to set
+// (`d` passed paged_cascade_desc_error) the two kernels' arguments: the suffix pass is the prefill's, read through the common prefix,
+// without a window (the word at 48 is max_prefix_blocks here); the prefix pass is derived from it.  part / lse of the workspace are the
+// launch entry's to set.
 static void fill_paged_cascade_args(const aule_paged_cascade_desc* d, aule_hip::SharedPrefixArgs& x, aule_hip::PagedPrefillArgs& a) {
-    a.q = d->q; a.k_cache = d->k_cache; a.v_cache = d->v_cache; a.out = d->out; a.lse = d->lse;
-    a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
-    a.T = (int)d->total_tokens; a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
-    a.max_seqlen_q = (int)(d->max_seqlen_q < d->total_tokens ? d->max_seqlen_q : d->total_tokens);
-    a.q_token_stride = d->q_token_stride;
-    a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
-    a.scale = resolve_scale(d->scale, d->head_dim);
+    fill_paged_prefill_args(prefill_prefix(d), a);
     a.window = -1;
-    a.dtype = d->dtype;
-    if (d->cache_dtype == AULE_KV_CACHE_FP8_E4M3) {
-        a.cache_kind = aule_hip::kCacheFp8E4M3;
-        a.k_scale = d->k_scale; a.v_scale = d->v_scale;
-    }
     x.q = a.q; x.k_cache = a.k_cache; x.v_cache = a.v_cache;
     x.prefix_block_table = d->prefix_block_table; x.prefix_len = d->prefix_len;
     x.T = a.T; x.Hq = a.Hq; x.Hkv = a.Hkv; x.D = a.D;
@@ -1183,15 +1196,15 @@ int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* d) {
         set_error("Paged cascade attention failed: %s", why);
         return -3;
     }
-    if (paged_cascade_nothing_to_do(d)) return 0;
+    if (ragged_nothing_to_do(d)) return 0;
     if (!initialised()) return -1;
     aule_hip::SharedPrefixArgs x;
     aule_hip::PagedPrefillArgs a;
     fill_paged_cascade_args(d, x, a);
     const aule_hip::SharedPrefixPlan plan = aule_hip::shared_prefix_plan(x);
     aule_hip::CascadeMergeArgs m;
-    m.nsplit = plan.nsplit; m.out = d->out;
-    m.context_lens = d->context_lens; m.cu_seqlens_q = d->cu_seqlens_q;
+    m.nsplit = plan.nsplit; m.out = a.out;
+    m.context_lens = a.context_lens; m.cu_seqlens_q = a.cu_seqlens_q;
     m.T = a.T; m.B = a.B; m.Hq = a.Hq; m.D = a.D;
     m.max_seqlen_q = a.max_seqlen_q; m.own_capacity = a.block_size * a.max_blocks; m.dtype = a.dtype;
     if (plan.grid <= 0 || plan.grid > 0x7fffffffll || aule_hip::paged_prefill_grid(a) > 0x7fffffffll || aule_hip::cascade_merge_grid(m) > 0x7fffffffll) {
@@ -1213,11 +1226,7 @@ int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* d) {
     rc = aule_hip::launch_shared_prefix(x, plan, stream);
     if (rc == 0) rc = aule_hip::launch_paged_prefill(a, stream);
     if (rc == 0) rc = aule_hip::launch_cascade_merge(m, stream);
-    if (rc != 0) {
-        set_error("Paged cascade attention failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
-        return -4;
-    }
-    return 0;
+    return launched("Paged cascade attention", rc);
 }
 
 // The two-state merge.  One checker, one reader (the launch entry: the pointer rules are stated here too).
@@ -1230,7 +1239,6 @@ static const char* merge_states_desc_error(const aule_merge_states_desc* d, Reas
     if ((uint64_t)d->rows * d->heads >= (1ull << 31)) return "rows * heads too large";
     if (merge_states_nothing_to_do(d)) return nullptr;
     if (!d->out_a || !d->lse_a || !d->out_b || !d->lse_b || !d->out || !d->lse) return "null tensor pointer";
-    const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
     if (misaligned(d->out_a) || misaligned(d->out_b) || misaligned(d->out)) return "out_a, out_b and out must be 16-byte aligned";
     // every thread of a row reads lse_a and lse_b, one of them writes lse: an lse inside either input would be read after it was written
     const uint64_t lse_bytes = (uint64_t)d->rows * d->heads * 4;
@@ -1256,12 +1264,7 @@ int32_t aule_attention_merge_states_ex(const aule_merge_states_desc* d) {
     a.out_a = d->out_a; a.lse_a = d->lse_a; a.out_b = d->out_b; a.lse_b = d->lse_b; a.out = d->out; a.lse = d->lse;
     a.rows = (long long)d->rows * d->heads; a.D = (int)d->head_dim; a.dtype = d->dtype;
     DeviceGuard g(d->device);
-    const int rc = aule_hip::launch_merge_states(a, (hipStream_t)d->stream);
-    if (rc != 0) {
-        set_error("Merge of attention states failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
-        return -4;
-    }
-    return 0;
+    return launched("Merge of attention states", aule_hip::launch_merge_states(a, (hipStream_t)d->stream));
 }
 
 static const char* rope_desc_error(const aule_rope_desc* d, Reason& why) {
@@ -1302,12 +1305,7 @@ int32_t aule_rope_ex(const aule_rope_desc* d) {
     r.nheads = (long long)d->rows_bh; r.S = (int)d->seq; r.D = (int)d->head_dim; r.pitch = (int)d->row_pitch;
     r.layout = d->layout; r.inverse = d->inverse != 0; r.pos_offset = (int)d->pos_offset; r.dtype = d->dtype;
     r.table_pitch = (int)d->table_pitch;
-    const int rc = aule_hip::launch_rope(r, (hipStream_t)d->stream);
-    if (rc != 0) {
-        set_error("RoPE failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
-        return -4;
-    }
-    return 0;
+    return launched("RoPE", aule_hip::launch_rope(r, (hipStream_t)d->stream));
 }
 
 static bool kv_append_nothing_to_do(const aule_kv_append_desc* d) { return d->num_tokens == 0; }
@@ -1317,8 +1315,7 @@ static bool kv_append_nothing_to_do(const aule_kv_append_desc* d) { return d->nu
 static const char* kv_append_error(const aule_kv_append_desc* d) {
     if (d == nullptr || d->struct_size != sizeof(aule_kv_append_desc)) return kBadDescriptor;
     if (d->dtype != AULE_DTYPE_F16 && d->dtype != AULE_DTYPE_BF16) return "dtype (of key / value) must be fp16 or bf16";
-    if (d->cache_dtype != AULE_KV_CACHE_SAME && d->cache_dtype != AULE_KV_CACHE_FP8_E4M3)
-        return "cache_dtype must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3";
+    if (const char* e = cache_dtype_error(d->cache_dtype)) return e;
     if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 128) return "head_dim unsupported (32, 64 or 128)";
     if (d->heads_kv == 0 || d->block_size == 0) return "heads_kv and block_size must be positive";
     const int64_t D = (int64_t)d->head_dim;
@@ -1337,10 +1334,7 @@ static const char* kv_append_error(const aule_kv_append_desc* d) {
     }
     if (kv_append_nothing_to_do(d)) return nullptr;
     if (!d->key || !d->value || !d->k_cache || !d->v_cache || !d->slot_mapping) return "null tensor pointer";
-    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
-    if (fp8 && (!d->k_scale || !d->v_scale)) return "null scale pointer (k_scale and v_scale are [heads_kv] fp32 device arrays)";
-    if (!fp8 && (d->k_scale || d->v_scale)) return "k_scale / v_scale apply to FP8 caches only; a 16-bit cache holds the values themselves";
-    const auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
+    if (const char* e = scale_pointer_error(d->cache_dtype == AULE_KV_CACHE_FP8_E4M3, d->k_scale, d->v_scale)) return e;
     if (misaligned(d->key) || misaligned(d->value) || misaligned(d->k_cache) || misaligned(d->v_cache) || misaligned(d->cos) || misaligned(d->sin))
         return "key, value, the caches and the tables must be 16-byte aligned";
     return nullptr;
@@ -1370,12 +1364,7 @@ int32_t aule_kv_cache_append_ex(const aule_kv_append_desc* d) {
     a.cos = d->cos; a.sin = d->sin; a.positions = reinterpret_cast<const long long*>(d->positions);
     a.table_len = (long long)d->table_len; a.table_pitch = (int)d->table_pitch;
     DeviceGuard g(d->device);
-    const int rc = aule_hip::launch_kv_append(a, (hipStream_t)d->stream);
-    if (rc != 0) {
-        set_error("KV cache append failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
-        return -4;
-    }
-    return 0;
+    return launched("KV cache append", aule_hip::launch_kv_append(a, (hipStream_t)d->stream));
 }
 
 uint64_t aule_attention_backward_workspace_size(const aule_attn_bwd_desc* d) {
@@ -1420,12 +1409,7 @@ int32_t aule_attention_backward_ex(const aule_attn_bwd_desc* d) {
     DeviceGuard g(d->device);
     int rc = ensure_configured();
     if (rc) return rc;
-    rc = aule_hip::launch_bwd(a, (hipStream_t)d->stream);
-    if (rc != 0) {
-        set_error("Backward failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported configuration");
-        return -4;
-    }
-    return 0;
+    return launched("Backward", aule_hip::launch_bwd(a, (hipStream_t)d->stream));
 }
 
 // ---- direct peer exchange (include/aule.h; consumer: aule/dist.py, transport="peer")
@@ -1499,7 +1483,7 @@ uint64_t aule_attention_forward_workspace_size(const aule_attn_desc* d) {
 // (the launcher's plan: it reads the shape, none of the pointers)
 static uint64_t paged_workspace_impl(const aule_paged_desc* d, bool fp8) {
     Reason text;
-    if (paged_desc_error(d, fp8, text) || paged_nothing_to_do(d)) return 0;
+    if (paged_desc_error(d, fp8, false, text) || paged_nothing_to_do(d)) return 0;
     aule_hip::PagedArgs a;
     fill_paged_args(d, fp8, a);
     return aule_hip::paged_workspace_bytes(a);
@@ -1525,7 +1509,7 @@ static bool cascade_plan(const aule_paged_cascade_desc* d, aule_hip::SharedPrefi
     Reason text;
     if (paged_cascade_desc_error(d, false, text)) return false;
     plan = aule_hip::SharedPrefixPlan();
-    if (paged_cascade_nothing_to_do(d)) return true;
+    if (ragged_nothing_to_do(d)) return true;
     aule_hip::SharedPrefixArgs x;
     aule_hip::PagedPrefillArgs a;
     fill_paged_cascade_args(d, x, a);
