@@ -239,6 +239,40 @@ def flash_attention_paged_cascade(q, k_cache, v_cache, prefix_block_table, prefi
                          max_seqlen_q=max_seqlen_q, scale=scale, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
 
 
+def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
+                           window_size=-1, return_lse=False):
+    """Attention over a batch of sequences of DIFFERENT lengths packed along one token axis, forward and backward (autograd-aware):
+    SFT with sequence packing, encoder batches without padding, prefill without a paged cache -- flash_attn_varlen_func's case.
+    Not in the reference.
+
+        q [total_q, heads_q, head_dim], k, v [total_k, heads_kv, head_dim] fp16 / bf16 ROCm tensors, heads_q % heads_kv == 0.
+          The heads of a token contiguous, the token stride free as long as it and the storage offset are multiples of 8
+          elements: the three slices of a fused [T, heads_q + 2 heads_kv, head_dim] projection are read in place.
+        cu_seqlens_q, cu_seqlens_k [batch + 1] int32: sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 of q and
+          rows cu_seqlens_k[b] .. cu_seqlens_k[b + 1] - 1 of k / v.  They are read and clamped on the device (offsets to the
+          totals, lengths to the maxima): a stale value cannot index outside a buffer.
+        max_seqlen_q, max_seqlen_k: the largest number of query / key tokens of a sequence (they size the grids; a longer
+          sequence is cut to its first max_seqlen_* tokens).  None reads it from the offsets with ONE device->host
+          synchronisation; passing both keeps the call free of synchronisation and capturable into a graph.
+        causal: False, True (top-left: token i sees keys j <= i) or "bottom-right" (token i of a sequence with n queries and L
+          keys sits at position i + L - n; L < n is allowed, tokens at negative positions see nothing), as flash_attention.
+        window_size: W > 0 keeps the keys j with position - j < W.
+
+    head_dim 32, 64 and 128 run as they are; other head dims up to 128 are zero-padded as flash_attention does.  A token that
+    sees no key gives a row of zeros (lse -inf, zero gradient).  Rows that belong to no sequence are never written: out (and
+    lse) come from torch.empty; the gradients are zero there.  Returns [total_q, heads_q, head_dim], or (out, lse) with
+    return_lse=True: lse [total_q, heads_q] fp32, the natural log of the softmax denominator.  Not built: head_dim > 128 and
+    fp32 (ValueError).  All argument errors are ValueErrors raised before the device is touched; CPU tensors that pass them
+    raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import flash_attention_varlen as impl
+    return impl(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k, causal=causal,
+                scale=scale, window_size=window_size, return_lse=return_lse)
+
+
 def merge_attention_states(out_a, lse_a, out_b, lse_b):
     """Merge two attention states of the same queries over DISJOINT key sets into the state over their union: the step that
     combines partial results (a shared prefix and a private suffix, key ranges computed apart).  Not in the reference.
@@ -485,7 +519,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

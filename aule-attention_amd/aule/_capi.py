@@ -164,6 +164,53 @@ class PagedCascadeDesc(ctypes.Structure):
     ]
 
 
+class VarlenDesc(ctypes.Structure):
+    """struct aule_varlen_desc (include/aule.h): forward over a variable-length packed batch."""
+    _problem_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("batch", ctypes.c_uint32),
+        ("heads_q", ctypes.c_uint32),
+        ("heads_kv", ctypes.c_uint32),
+        ("head_dim", ctypes.c_uint32),
+        ("total_q", ctypes.c_uint32),
+        ("total_k", ctypes.c_uint32),
+        ("max_seqlen_q", ctypes.c_uint32),
+        ("max_seqlen_k", ctypes.c_uint32),
+        ("scale", ctypes.c_float),
+        ("causal", ctypes.c_int32),
+        ("window_size", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("q_token_stride", ctypes.c_int64),
+        ("k_token_stride", ctypes.c_int64),
+        ("v_token_stride", ctypes.c_int64),
+        ("stream", ctypes.c_void_p),
+        ("q", ctypes.c_void_p),
+        ("k", ctypes.c_void_p),
+        ("v", ctypes.c_void_p),
+        ("cu_seqlens_q", ctypes.c_void_p),
+        ("cu_seqlens_k", ctypes.c_void_p),
+    ]
+    _fields_ = _problem_ + [
+        ("out", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p),
+    ]
+
+
+class VarlenBwdDesc(ctypes.Structure):
+    """struct aule_varlen_bwd_desc (include/aule.h): aule_varlen_desc's problem statement, then the backward's tensors."""
+    _fields_ = VarlenDesc._problem_ + [
+        ("out", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p),
+        ("dout", ctypes.c_void_p),
+        ("dq", ctypes.c_void_p),
+        ("dk", ctypes.c_void_p),
+        ("dv", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 class MergeStatesDesc(ctypes.Structure):
     """struct aule_merge_states_desc (include/aule.h): two attention states into one."""
     _fields_ = [
@@ -314,6 +361,9 @@ SIGNATURES = [
     ("aule_attention_paged_prefill_ex", _I32, [ctypes.POINTER(PagedPrefillDesc)]),
     ("aule_attention_paged_cascade_ex", _I32, [ctypes.POINTER(PagedCascadeDesc)]),
     ("aule_attention_paged_cascade_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedCascadeDesc)]),
+    ("aule_attention_varlen_forward_ex", _I32, [ctypes.POINTER(VarlenDesc)]),
+    ("aule_attention_varlen_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),
+    ("aule_attention_varlen_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenBwdDesc)]),
     ("aule_attention_merge_states_ex", _I32, [ctypes.POINTER(MergeStatesDesc)]),
     ("aule_peer_alloc", _I32, [_I32, _U64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(IpcHandle)]),
     ("aule_peer_free", _I32, [_I32, ctypes.c_void_p]),

@@ -610,6 +610,164 @@ def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, win
     return (out, lse) if return_lse else out
 
 
+# Variable-length packed batches: sequences of different lengths along one token axis, forward and backward
+# (aule_attention_varlen_forward_ex / _backward_ex; csrc/fa_fwd_varlen_gfx950.hip, csrc/fa_bwd_varlen_gfx950.hip).
+
+VARLEN_HEAD_DIMS = (32, 64, 128)
+
+
+def _varlen_max(name, m):
+    if m is not None and (isinstance(m, bool) or not isinstance(m, int) or m < 1):
+        raise ValueError(f"{name} must be a positive int or None, got {m!r}")
+
+
+def _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k):
+    """Every rule of the arguments that needs no device.  Returns the batch."""
+    if not (torch.is_tensor(q) and torch.is_tensor(k) and torch.is_tensor(v)) or q.dim() != 3 or k.dim() != 3 or v.shape != k.shape:
+        raise ValueError("expected q [total_q, heads_q, head_dim] and k, v [total_k, heads_kv, head_dim] of one shape")
+    (Hq, D), (Hkv, Dk) = q.shape[1:], k.shape[1:]
+    if Dk != D:
+        raise ValueError(f"head_dim mismatch: query={D}, key={Dk}")
+    if Hkv == 0 or Hq % Hkv != 0:
+        raise ValueError(f"heads_q ({Hq}) must be divisible by heads_kv ({Hkv})")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"variable-length attention is not built for {q.dtype}: fp16 and bf16 only")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"q, k and v must share one dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
+    if D == 0 or D > VARLEN_HEAD_DIMS[-1]:
+        raise ValueError(f"variable-length attention is not built for head_dim {D}: 1 to {VARLEN_HEAD_DIMS[-1]}")
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not torch.is_tensor(cu) or cu.dim() != 1 or cu.shape[0] < 1:
+            raise ValueError(f"{name} must be a [batch + 1] tensor")
+        if cu.dtype != torch.int32:
+            raise ValueError(f"{name} must be int32 (it is read on the device as it stands), got {cu.dtype}")
+    if cu_seqlens_k.shape != cu_seqlens_q.shape:
+        raise ValueError(f"cu_seqlens_q {tuple(cu_seqlens_q.shape)} and cu_seqlens_k {tuple(cu_seqlens_k.shape)} must both be [batch + 1]")
+    _varlen_max("max_seqlen_q", max_seqlen_q)
+    _varlen_max("max_seqlen_k", max_seqlen_k)
+    return cu_seqlens_q.shape[0] - 1
+
+
+def _varlen_rows(name, x):
+    """x [T, H, D] as the kernels read it -- the heads of a token contiguous, the token stride free -- and that stride in elements."""
+    T, H, D = x.shape
+    if T > 1 and (x.stride(2) != 1 or x.stride(1) != D) or T <= 1 and not x.is_contiguous():
+        x = x.contiguous()
+    stride = x.stride(0) if T > 1 else H * D
+    if stride < H * D or stride % 8 != 0 or x.storage_offset() % 8 != 0:
+        raise ValueError(f"{name}'s token stride ({stride}) and storage offset ({x.storage_offset()}) must be multiples of 8 elements "
+                         f"and the stride at least heads * head_dim = {H * D} (16-byte loads); pass {name}.contiguous()")
+    return x, stride
+
+
+def _varlen_problem(d, q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window):
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    d.batch, d.heads_q, d.heads_kv, d.head_dim = cu_q.shape[0] - 1, q.shape[1], k.shape[1], q.shape[2]
+    d.total_q, d.total_k = q.shape[0], k.shape[0]
+    d.max_seqlen_q, d.max_seqlen_k = max(min(max_seqlen_q, q.shape[0]), 1), max(min(max_seqlen_k, k.shape[0]), 1)
+    d.scale = _abi_scale(scale)
+    d.causal = causal
+    d.window_size = _window_arg(window)
+    d.device = _device_index(q.device)
+    d.q_token_stride, d.k_token_stride, d.v_token_stride = sq, sk, sv
+    d.stream = _stream_ptr(q.device)
+    d.q, d.k, d.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
+    d.cu_seqlens_q, d.cu_seqlens_k = cu_q.data_ptr(), cu_k.data_ptr()
+    return d
+
+
+def varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1, want_lse=True):
+    """q [Tq,Hq,D], k / v [Tk,Hkv,D] device tensors (heads contiguous, D in VARLEN_HEAD_DIMS), cu_q / cu_k int32 [B + 1] on the same
+    device, causal an AULE_CAUSAL_* code.  Returns (out, lse or None), both from torch.empty.  Asynchronous, no synchronisation."""
+    lib = _capi.get_lib()
+    _same_device("variable-length attention", q, k, v, cu_q, cu_k)
+    (q, sq), (k, sk), (v, sv) = _varlen_rows("q", q), _varlen_rows("k", k), _varlen_rows("v", v)
+    out = torch.empty(q.shape, device=q.device, dtype=q.dtype)
+    lse = torch.empty(q.shape[:2], device=q.device, dtype=torch.float32) if want_lse else None
+    if q.shape[0] * q.shape[1] * (cu_q.shape[0] - 1) == 0:
+        return out, lse
+    d = _varlen_problem(_capi.VarlenDesc(), q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window)
+    d.out = out.data_ptr()
+    d.lse = lse.data_ptr() if lse is not None else None
+    _capi.check(lib.aule_attention_varlen_forward_ex(ctypes.byref(d)), "aule_attention_varlen_forward_ex")
+    return out, lse
+
+
+def varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1):
+    """The gradients of varlen_fwd_raw: dq [Tq,Hq,D], dk, dv [Tk,Hkv,D], contiguous and ZERO in the rows no sequence owns (the
+    library never writes those; they are allocated zero-filled here).  out, dout, lse contiguous.  Asynchronous, no synchronisation."""
+    lib = _capi.get_lib()
+    _same_device("variable-length attention backward", q, k, v, out, dout, lse, cu_q, cu_k)
+    (q, sq), (k, sk), (v, sv) = _varlen_rows("q", q), _varlen_rows("k", k), _varlen_rows("v", v)
+    dq = torch.zeros(q.shape, device=q.device, dtype=q.dtype)
+    dk = torch.zeros(k.shape, device=k.device, dtype=k.dtype)
+    dv = torch.zeros(v.shape, device=v.device, dtype=v.dtype)
+    if q.shape[1] * (cu_q.shape[0] - 1) == 0 or q.shape[0] + k.shape[0] == 0:
+        return dq, dk, dv
+    d = _varlen_problem(_capi.VarlenBwdDesc(), q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window)
+    d.out, d.lse, d.dout = out.data_ptr(), lse.data_ptr(), dout.data_ptr()
+    d.dq, d.dk, d.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    ws = _attach_workspace(d, lib.aule_attention_varlen_backward_workspace_size, q.device)   # delta [Tq, Hq] fp32; held until the launch is queued
+    _capi.check(lib.aule_attention_varlen_backward_ex(ctypes.byref(d)), "aule_attention_varlen_backward_ex")
+    del ws
+    return dq, dk, dv
+
+
+class FlashAttentionVarlenHipFunc(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window):
+        out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window)
+        ctx.save_for_backward(q, k, v, out, lse, cu_q, cu_k)
+        ctx.problem = (max_seqlen_q, max_seqlen_k, causal, scale, window)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, _dlse):
+        q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors
+        max_seqlen_q, max_seqlen_k, causal, scale, window = ctx.problem
+        dout = dout.contiguous().to(q.dtype)
+        dq, dk, dv = varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window)
+        return dq, dk, dv, None, None, None, None, None, None, None
+
+
+def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
+                           window_size=-1, return_lse=False):
+    """Attention over a variable-length packed batch, autograd-aware (aule.flash_attention_varlen documents the arguments)."""
+    _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    code = causal_code(causal)
+    D = q.shape[2]
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if D in VARLEN_HEAD_DIMS:   # (a padded copy is contiguous: only tensors read in place have strides to refuse)
+        for name, x in (("q", q), ("k", k), ("v", v)):
+            _varlen_rows(name, x)
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): variable-length attention needs ROCm device tensors; there is no CPU fallback")
+    _same_device("variable-length attention", q, k, v)
+    cu_q, cu_k = _int32_on(q.device, cu_seqlens_q, cu_seqlens_k)
+    if max_seqlen_q is None or max_seqlen_k is None:
+        # the one documented synchronisation (both maxima in one read)
+        if cu_q.shape[0] > 1:
+            mq, mk = torch.stack(((cu_q[1:] - cu_q[:-1]).max(), (cu_k[1:] - cu_k[:-1]).max())).tolist()
+        else:
+            mq = mk = 1
+        max_seqlen_q = max(int(mq), 1) if max_seqlen_q is None else max_seqlen_q
+        max_seqlen_k = max(int(mk), 1) if max_seqlen_k is None else max_seqlen_k
+    Dp = next(x for x in VARLEN_HEAD_DIMS if x >= D)
+    if Dp != D:   # zero-padded head dim: dot products and outputs are unchanged
+        q, k, v = _pad_head_dim(q, Dp), _pad_head_dim(k, Dp), _pad_head_dim(v, Dp)
+    window = _window_arg(window_size)
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        out, lse = FlashAttentionVarlenHipFunc.apply(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window)
+    else:
+        out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window, want_lse=return_lse)
+    if Dp != D:
+        out = out[..., :D]
+    return (out, lse) if return_lse else out
+
+
 # The paged prefill in three steps; the paged cascade is the same three with its prefix between them.
 
 def _ragged_kind(op, q, k_cache, v_cache, k_scale, v_scale):

@@ -83,6 +83,31 @@ static_assert(AULE_SAME_OFFSET(struct_size) && AULE_SAME_OFFSET(dtype) && AULE_S
               "aule_paged_cascade_desc starts with aule_paged_prefill_desc but for the word at 48, max_prefix_blocks where that has window_size "
               "(its launch arguments are filled through that prefix, the window dropped)");
 #undef AULE_SAME_OFFSET
+static_assert(sizeof(aule_varlen_desc) == 144 && offsetof(aule_varlen_desc, batch) == 8 && offsetof(aule_varlen_desc, heads_q) == 12 &&
+                  offsetof(aule_varlen_desc, head_dim) == 20 && offsetof(aule_varlen_desc, total_q) == 24 &&
+                  offsetof(aule_varlen_desc, total_k) == 28 && offsetof(aule_varlen_desc, max_seqlen_q) == 32 &&
+                  offsetof(aule_varlen_desc, max_seqlen_k) == 36 && offsetof(aule_varlen_desc, scale) == 40 &&
+                  offsetof(aule_varlen_desc, causal) == 44 && offsetof(aule_varlen_desc, window_size) == 48 &&
+                  offsetof(aule_varlen_desc, device) == 52 && offsetof(aule_varlen_desc, q_token_stride) == 56 &&
+                  offsetof(aule_varlen_desc, k_token_stride) == 64 && offsetof(aule_varlen_desc, v_token_stride) == 72 &&
+                  offsetof(aule_varlen_desc, stream) == 80 && offsetof(aule_varlen_desc, q) == 88 && offsetof(aule_varlen_desc, k) == 96 &&
+                  offsetof(aule_varlen_desc, v) == 104 && offsetof(aule_varlen_desc, cu_seqlens_q) == 112 &&
+                  offsetof(aule_varlen_desc, cu_seqlens_k) == 120 && offsetof(aule_varlen_desc, out) == 128 &&
+                  offsetof(aule_varlen_desc, lse) == 136,
+              "aule_varlen_desc layout is part of the ABI");
+static_assert(sizeof(aule_varlen_bwd_desc) == 192 && offsetof(aule_varlen_bwd_desc, out) == 128 && offsetof(aule_varlen_bwd_desc, lse) == 136 &&
+                  offsetof(aule_varlen_bwd_desc, dout) == 144 && offsetof(aule_varlen_bwd_desc, dq) == 152 &&
+                  offsetof(aule_varlen_bwd_desc, dk) == 160 && offsetof(aule_varlen_bwd_desc, dv) == 168 &&
+                  offsetof(aule_varlen_bwd_desc, workspace) == 176 && offsetof(aule_varlen_bwd_desc, workspace_bytes) == 184,
+              "aule_varlen_bwd_desc layout is part of the ABI");
+#define AULE_VARLEN_SAME(field) (offsetof(aule_varlen_bwd_desc, field) == offsetof(aule_varlen_desc, field))
+static_assert(AULE_VARLEN_SAME(dtype) && AULE_VARLEN_SAME(batch) && AULE_VARLEN_SAME(heads_q) && AULE_VARLEN_SAME(heads_kv) && AULE_VARLEN_SAME(head_dim) &&
+                  AULE_VARLEN_SAME(total_q) && AULE_VARLEN_SAME(total_k) && AULE_VARLEN_SAME(max_seqlen_q) && AULE_VARLEN_SAME(max_seqlen_k) &&
+                  AULE_VARLEN_SAME(scale) && AULE_VARLEN_SAME(causal) && AULE_VARLEN_SAME(window_size) && AULE_VARLEN_SAME(device) &&
+                  AULE_VARLEN_SAME(q_token_stride) && AULE_VARLEN_SAME(k_token_stride) && AULE_VARLEN_SAME(v_token_stride) && AULE_VARLEN_SAME(stream) &&
+                  AULE_VARLEN_SAME(q) && AULE_VARLEN_SAME(k) && AULE_VARLEN_SAME(v) && AULE_VARLEN_SAME(cu_seqlens_q) && AULE_VARLEN_SAME(cu_seqlens_k),
+              "aule_varlen_bwd_desc states the problem in the fields of aule_varlen_desc, up to cu_seqlens_k: both are checked through that prefix");
+#undef AULE_VARLEN_SAME
 static_assert(sizeof(aule_merge_states_desc) == 80 && offsetof(aule_merge_states_desc, rows) == 8 &&
                   offsetof(aule_merge_states_desc, heads) == 12 && offsetof(aule_merge_states_desc, head_dim) == 16 &&
                   offsetof(aule_merge_states_desc, device) == 20 && offsetof(aule_merge_states_desc, stream) == 24 &&
@@ -1227,6 +1252,151 @@ int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* d) {
     if (rc == 0) rc = aule_hip::launch_paged_prefill(a, stream);
     if (rc == 0) rc = aule_hip::launch_cascade_merge(m, stream);
     return launched("Paged cascade attention", rc);
+}
+
+// The variable-length kinds: aule_varlen_bwd_desc states the problem in aule_varlen_desc's fields up to cu_seqlens_k (the layout asserts
+// at the top of this file), so both are checked and read through that prefix; what follows it is each kind's own.  One checker per
+// kind; `launch`: the pointer and workspace rules of a call that has something to do as well (the size query reads no pointer).  Host
+// logic only, and the launch entries ask before they need the device.
+static const aule_varlen_desc* varlen_prefix(const aule_varlen_bwd_desc* d) { return reinterpret_cast<const aule_varlen_desc*>(d); }
+
+static const char* varlen_stride_error(const char* name, int64_t stride, uint64_t token, const char* heads, Reason& why) {
+    if (stride < (int64_t)token)
+        return reasonf(why, "%s_token_stride (%lld) is smaller than a token (%s * head_dim = %llu elements)", name, (long long)stride, heads, (unsigned long long)token);
+    if (stride % 8 != 0) return reasonf(why, "%s_token_stride (%lld) must be a multiple of 8 elements (16-byte loads)", name, (long long)stride);
+    return nullptr;
+}
+
+// the problem statement (`size`: the kind's own sizeof)
+static const char* varlen_problem_error(const aule_varlen_desc* d, size_t size, Reason& why) {
+    if (d == nullptr || d->struct_size != size) return kBadDescriptor;
+    if (!is_16_bit(d->dtype)) return "dtype must be fp16 or bf16 (fp32 is not built for variable-length batches)";
+    if (const char* e = paged_heads_error(d, why)) return e;
+    if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return reasonf(why, "unknown causal mode %d (0 none, 1 top-left, 2 bottom-right)", d->causal);
+    if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
+    if (d->max_seqlen_k == 0) return "max_seqlen_k must be at least 1";
+    if (const char* e = varlen_stride_error("q", d->q_token_stride, (uint64_t)d->heads_q * d->head_dim, "heads_q", why)) return e;
+    if (const char* e = varlen_stride_error("k", d->k_token_stride, (uint64_t)d->heads_kv * d->head_dim, "heads_kv", why)) return e;
+    if (const char* e = varlen_stride_error("v", d->v_token_stride, (uint64_t)d->heads_kv * d->head_dim, "heads_kv", why)) return e;
+    if (d->batch >= (1u << 30) || d->total_q >= (1u << 30) || d->total_k >= (1u << 30)) return "batch / total_q / total_k too large";
+    if (((uint64_t)d->total_q + 128) * (d->heads_q / d->heads_kv) > 0x7fffffffull) return "(total_q + 128) * (heads_q / heads_kv) too large (packed rows are counted in 32 bits)";
+    return nullptr;
+}
+
+static bool varlen_fwd_nothing_to_do(const aule_varlen_desc* d) { return d->total_q == 0 || (uint64_t)d->batch * d->heads_q == 0; }
+static bool varlen_bwd_nothing_to_do(const aule_varlen_desc* d) { return (uint64_t)d->batch * d->heads_q == 0 || (d->total_q == 0 && d->total_k == 0); }
+
+// the pointers both kinds have: the offsets always, q with any query row, k and v with any key row
+static const char* varlen_input_error(const aule_varlen_desc* d) {
+    if (!d->cu_seqlens_q || !d->cu_seqlens_k) return "null cu_seqlens pointer";
+    if (d->total_q > 0 && !d->q) return "null tensor pointer";
+    if (d->total_k > 0 && (!d->k || !d->v)) return "null tensor pointer";
+    if (misaligned(d->q) || misaligned(d->k) || misaligned(d->v)) return "q, k and v must be 16-byte aligned";
+    return nullptr;
+}
+
+static const char* varlen_desc_error(const aule_varlen_desc* d, Reason& why) {
+    if (const char* e = varlen_problem_error(d, sizeof(aule_varlen_desc), why)) return e;
+    if (varlen_fwd_nothing_to_do(d)) return nullptr;
+    if (const char* e = varlen_input_error(d)) return e;
+    if (!d->out) return "null tensor pointer";
+    if (misaligned(d->out)) return "out must be 16-byte aligned";
+    return nullptr;
+}
+
+static uint64_t varlen_bwd_workspace(const aule_varlen_desc* d) { return aule_hip::varlen_bwd_workspace_bytes(d->total_q, (int)d->heads_q); }
+
+static const char* varlen_bwd_desc_error(const aule_varlen_bwd_desc* d, bool launch, Reason& why) {
+    const aule_varlen_desc* x = varlen_prefix(d);
+    if (const char* e = varlen_problem_error(x, sizeof(aule_varlen_bwd_desc), why)) return e;
+    if (!launch || varlen_bwd_nothing_to_do(x)) return nullptr;
+    if (const char* e = varlen_input_error(x)) return e;
+    if (d->total_q > 0 && (!d->out || !d->lse || !d->dout || !d->dq)) return "null tensor pointer";
+    if (d->total_k > 0 && (!d->dk || !d->dv)) return "null tensor pointer";
+    if (misaligned(d->out) || misaligned(d->dout) || misaligned(d->dq) || misaligned(d->dk) || misaligned(d->dv)) return "out, dout, dq, dk and dv must be 16-byte aligned";
+    if (d->workspace != nullptr) {
+        if (misaligned(d->workspace)) return "workspace must be 16-byte aligned";
+        if (d->workspace_bytes < varlen_bwd_workspace(x))
+            return reasonf(why, "workspace too small (%llu bytes, need %llu)", (unsigned long long)d->workspace_bytes, (unsigned long long)varlen_bwd_workspace(x));
+    }
+    return nullptr;
+}
+
+// (`d` passed its kind's checker) the problem statement; the tensors behind the prefix are the entry's to set
+static void fill_varlen_args(const aule_varlen_desc* d, aule_hip::VarlenArgs& a) {
+    a.q = d->q; a.k = d->k; a.v = d->v;
+    a.cu_seqlens_q = d->cu_seqlens_q; a.cu_seqlens_k = d->cu_seqlens_k;
+    a.Tq = (int)d->total_q; a.Tk = (int)d->total_k; a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
+    a.max_seqlen_q = (int)(d->max_seqlen_q < d->total_q ? d->max_seqlen_q : d->total_q);
+    a.max_seqlen_k = (int)(d->max_seqlen_k < d->total_k ? d->max_seqlen_k : d->total_k);
+    a.q_token_stride = d->q_token_stride; a.k_token_stride = d->k_token_stride; a.v_token_stride = d->v_token_stride;
+    a.scale = resolve_scale(d->scale, d->head_dim);
+    a.causal = d->causal;
+    a.window = d->window_size;
+    a.dtype = d->dtype;
+}
+
+int32_t aule_attention_varlen_forward_ex(const aule_varlen_desc* d) {
+    RoctxRange range("aule.varlen_forward");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = varlen_desc_error(d, text)) {
+        set_error("Variable-length attention failed: %s", why);
+        return -3;
+    }
+    if (varlen_fwd_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::VarlenArgs a;
+    fill_varlen_args(d, a);
+    a.out = d->out; a.lse = d->lse;
+    if (aule_hip::varlen_fwd_grid(a) > 0x7fffffffll) {
+        set_error("Variable-length attention failed: the grid (blocks * heads_kv * batch) exceeds 2^31 - 1 workgroups");
+        return -3;
+    }
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    return launched("Variable-length attention", aule_hip::launch_varlen_fwd(a, (hipStream_t)d->stream));
+}
+
+int32_t aule_attention_varlen_backward_ex(const aule_varlen_bwd_desc* d) {
+    RoctxRange range("aule.varlen_backward");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = varlen_bwd_desc_error(d, true, text)) {
+        set_error("Variable-length backward failed: %s", why);
+        return -3;
+    }
+    const aule_varlen_desc* x = varlen_prefix(d);
+    if (varlen_bwd_nothing_to_do(x)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::VarlenArgs a;
+    fill_varlen_args(x, a);
+    a.o = d->out; a.lse = const_cast<float*>(d->lse); a.dout = d->dout;
+    a.dq = d->dq; a.dk = d->dk; a.dv = d->dv;
+    if (aule_hip::varlen_fwd_grid(a) > 0x7fffffffll || aule_hip::varlen_dkdv_grid(a) > 0x7fffffffll) {
+        set_error("Variable-length backward failed: a grid exceeds 2^31 - 1 workgroups");
+        return -3;
+    }
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)d->stream;
+    const uint64_t need = varlen_bwd_workspace(x);
+    if (need == 0) return launched("Variable-length backward", aule_hip::launch_varlen_bwd(a, stream));
+    aule_hip::ScopedWorkspace ws(need, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
+    if (ws.err != hipSuccess) {
+        set_error("Variable-length backward failed: workspace allocation (%llu bytes): %s", (unsigned long long)need, hipGetErrorString(ws.err));
+        return -4;
+    }
+    a.delta = static_cast<float*>(ws.ptr);
+    return launched("Variable-length backward", aule_hip::launch_varlen_bwd(a, stream));
+}
+
+uint64_t aule_attention_varlen_backward_workspace_size(const aule_varlen_bwd_desc* d) {
+    Reason text;
+    if (varlen_bwd_desc_error(d, false, text)) return 0;
+    return varlen_bwd_nothing_to_do(varlen_prefix(d)) ? 0 : varlen_bwd_workspace(varlen_prefix(d));
 }
 
 // The two-state merge.  One checker, one reader (the launch entry: the pointer rules are stated here too).

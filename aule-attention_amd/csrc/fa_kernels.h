@@ -305,6 +305,51 @@ struct CascadeMergeArgs {
 long long cascade_merge_grid(const CascadeMergeArgs& a);
 int launch_cascade_merge(const CascadeMergeArgs& a, hipStream_t stream);
 
+// Variable-length packed batches (fa_fwd_varlen_gfx950.hip, fa_bwd_varlen_gfx950.hip): sequences of different lengths packed
+// along one token axis, forward and backward.
+//   q, out, dout, dq [Tq, Hq, D] and k, v, dk, dv [Tk, Hkv, D] 16-bit, lse / delta [Tq, Hq] fp32; the heads of a token contiguous,
+//   q / k / v with their own token strides (elements), everything else contiguous; cu_seqlens_q / cu_seqlens_k [B + 1] int32 on the
+//   device.  Sequence b: s_q = clamp(cu_q[b], 0, Tq), e_q = clamp(cu_q[b + 1], s_q, Tq), n = min(e_q - s_q, max_seqlen_q), and
+//   s_k, e_k, L the same from cu_k, Tk, max_seqlen_k.  Query i < n is row s_q + i and sits at position i (causal 0, 1) or
+//   i + L - n (causal 2); key j < L is row s_k + j and is visible iff (!causal || j <= pos) and, with a window W > 0, pos - j < W.
+//   Rows outside every [s_q, s_q + n) / [s_k, s_k + L) are never written.  The caller guarantees 16-byte aligned tensors and
+//   strides % 8 == 0.
+struct VarlenArgs {
+    const void* q;
+    const void* k;
+    const void* v;
+    void* out = nullptr;          // forward: written
+    float* lse = nullptr;         // forward: written (null: skipped); backward: read
+    const void* o = nullptr;      // backward: the forward's out
+    const void* dout = nullptr;
+    void* dq = nullptr;
+    void* dk = nullptr;
+    void* dv = nullptr;
+    float* delta = nullptr;       // backward workspace: [Tq, Hq] fp32
+    const int* cu_seqlens_q;
+    const int* cu_seqlens_k;
+    int Tq, Tk, B, Hq, Hkv, D;
+    int max_seqlen_q, max_seqlen_k;
+    long long q_token_stride, k_token_stride, v_token_stride;
+    float scale;
+    int causal;                   // 0 none, 1 top-left, 2 bottom-right
+    int window;
+    int dtype;
+};
+// The window the kernels run with: 0 (off) for window <= 0 and for a window that masks nothing -- no position differs from a key by
+// min(max_seqlen_q, Tq) + min(max_seqlen_k, Tk) or more under any of the three causal modes -- so that "effectively off" values up to
+// INT32_MAX never enter the kernels' range arithmetic.  The one statement of the rule, for both launchers.
+inline int varlen_window(const VarlenArgs& a) {
+    const long long span = (long long)(a.max_seqlen_q < a.Tq ? a.max_seqlen_q : a.Tq) + (a.max_seqlen_k < a.Tk ? a.max_seqlen_k : a.Tk);
+    return a.window > 0 && a.window < span ? a.window : 0;
+}
+// workgroups: forward and dQ ceil(min(max_seqlen_q, Tq) * (Hq / Hkv) / 128) x Hkv x B, dK/dV ceil(min(max_seqlen_k, Tk) / 128) x Hkv x B
+long long varlen_fwd_grid(const VarlenArgs& a);
+long long varlen_dkdv_grid(const VarlenArgs& a);
+uint64_t varlen_bwd_workspace_bytes(long long Tq, int Hq);   // delta
+int launch_varlen_fwd(const VarlenArgs& a, hipStream_t stream);   // -1: unsupported arguments
+int launch_varlen_bwd(const VarlenArgs& a, hipStream_t stream);   // delta, dQ, dK/dV on `stream`
+
 // Returns 0 on success, a hipError_t value on launch failure, -1 for an
 // unsupported (dtype, D) combination.
 int launch_paged_decode(const PagedArgs& a, hipStream_t stream);   // either cache_kind; kCacheFp8E4M3 with a null scale array is -1

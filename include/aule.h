@@ -384,6 +384,102 @@ int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
 uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_desc* desc);
 
+/* VARIABLE-LENGTH packed batches (additive): sequences of different lengths packed along one token axis, forward and backward --   */
+/* SFT with sequence packing, encoder batches without padding, prefill without a paged cache (flash_attn_varlen_func's case).        */
+/* Tensors: q, out, dout, dq are [total_q, heads_q, head_dim] and k, v, dk, dv [total_k, heads_kv, head_dim], fp16 or bf16, with     */
+/* heads_q % heads_kv == 0 and head_dim 32, 64 or 128; lse is [total_q, heads_q] fp32.  The heads of a token are contiguous; q, k    */
+/* and v each carry their own token stride in elements (q_token_stride >= heads_q * head_dim, k_token_stride and v_token_stride      */
+/* >= heads_kv * head_dim, all multiples of 8: slices of a fused QKV projection need no copy).  out, lse, dout, dq, dk and dv are    */
+/* contiguous; every tensor is 16-byte aligned.                                                                                      */
+/* Sequence bounds: cu_seqlens_q and cu_seqlens_k are [batch + 1] int32 on the DEVICE, read and clamped in the kernels (no host      */
+/* read, no host synchronisation; a stale value cannot index outside a buffer):                                                      */
+/*     s_q = clamp(cu_q[b], 0, total_q)   e_q = clamp(cu_q[b+1], s_q, total_q)   n = min(e_q - s_q, max_seqlen_q)                    */
+/*     s_k = clamp(cu_k[b], 0, total_k)   e_k = clamp(cu_k[b+1], s_k, total_k)   L = min(e_k - s_k, max_seqlen_k)                    */
+/* max_seqlen_q and max_seqlen_k are host integers >= 1: they size the grids and cut a longer sequence to its first max_seqlen_*     */
+/* tokens, as aule_paged_prefill_desc.max_seqlen_q does.                                                                             */
+/* Visibility: query token i of sequence b is row s_q + i, key j is row s_k + j.  The query's position is pos = i for                */
+/* AULE_CAUSAL_NONE and AULE_CAUSAL_TOP_LEFT and pos = i + L - n for AULE_CAUSAL_BOTTOM_RIGHT (L < n is allowed: tokens with         */
+/* pos < 0 see nothing).  Key j < L is visible iff (!causal || j <= pos), and with window_size = W > 0 iff also pos - j < W: the     */
+/* rules of aule_attn_desc, applied per sequence.                                                                                    */
+/* Empty and unowned rows: a query row with no visible key gives out = 0, lse = -inf and dq = 0 and contributes nothing to dk / dv.  */
+/* Every owned query row of out, lse and dq is written, every owned key row of dk and dv too (zeros if no query sees it, n = 0       */
+/* included).  Rows of out, lse, dq, dk and dv that belong to no [s_q, s_q + n) or [s_k, s_k + L) are NEVER written.  With hostile   */
+/* offsets that make two sequences own one row, that row's value is unspecified, and nothing outside the outputs is written.         */
+/* Softmax in log2 units with fp32 m, l and accumulators; lse is the natural log of the softmax denominator.                         */
+/* Forward: one launch of ceil(min(max_seqlen_q, total_q) * (heads_q / heads_kv) / 128) * heads_kv * batch workgroups, no workspace. */
+/* Backward: three launches on `stream` (delta, dQ, dK/dV); the workspace is delta [total_q, heads_q] fp32,                          */
+/* aule_attention_varlen_backward_workspace_size() bytes.  workspace NULL: the library allocates on the stream; a workspace that is  */
+/* given but too small or not 16-byte aligned is refused.  No host synchronisation, and no allocation when a workspace is passed:    */
+/* both capture into a hipGraph, and a replay sees the CURRENT contents of cu_seqlens_q / cu_seqlens_k.                              */
+/* The descriptors are checked before the device is needed: -3 with a reason (struct_size, dtype, head_dim, head ratio, causal code, */
+/* strides, alignment, null pointers, max_seqlen_* < 1, (total_q + 128) * (heads_q / heads_kv) beyond 32 bits, a workspace that is   */
+/* too small) and 0 for a call with nothing to do (forward: total_q = 0, batch = 0 or heads_q = 0; backward: batch = 0, heads_q = 0, */
+/* or total_q = 0 and total_k = 0) are answered without aule_init().  total_k = 0 with total_q > 0 writes zeros and -inf to the      */
+/* owned rows (k and v may then be NULL); a backward with total_q = 0 zeroes the owned dk and dv rows (the query-side pointers may   */
+/* then be NULL).  Not built: fp32, head_dim 256, FP8 inputs, key-range splits for one long sequence.                                */
+typedef struct aule_varlen_desc {
+    uint32_t struct_size;      /* = sizeof(aule_varlen_desc) = 144 */
+    int32_t dtype;             /* AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    uint32_t batch;            /* offset 8; sequences */
+    uint32_t heads_q, heads_kv, head_dim;   /* offsets 12, 16, 20; head_dim 32, 64 or 128 */
+    uint32_t total_q;          /* offset 24; rows of q / out */
+    uint32_t total_k;          /* offset 28; rows of k / v */
+    uint32_t max_seqlen_q;     /* offset 32; >= 1: sizes the grid, and caps every n */
+    uint32_t max_seqlen_k;     /* offset 36; >= 1: caps every L (and sizes the backward's dK/dV grid) */
+    float scale;               /* offset 40; 0 -> 1/sqrt(head_dim) */
+    int32_t causal;            /* offset 44; AULE_CAUSAL_* */
+    int32_t window_size;       /* offset 48; > 0: on; any value is accepted (one that masks nothing, INT32_MAX included, equals no window bit for bit) */
+    int32_t device;            /* offset 52; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 56; elements, >= heads_q * head_dim, a multiple of 8 */
+    int64_t k_token_stride;    /* offset 64; elements, >= heads_kv * head_dim, a multiple of 8 */
+    int64_t v_token_stride;    /* offset 72 */
+    void* stream;              /* offset 80; hipStream_t */
+    const void* q;             /* offset 88 */
+    const void* k;             /* offset 96 */
+    const void* v;             /* offset 104 */
+    const int32_t* cu_seqlens_q;   /* offset 112; [batch + 1], device */
+    const int32_t* cu_seqlens_k;   /* offset 120; [batch + 1], device */
+    void* out;                 /* offset 128; [total_q, heads_q, head_dim], contiguous */
+    float* lse;                /* offset 136; optional (NULL to skip): [total_q, heads_q] fp32 */
+} aule_varlen_desc;
+/* The same problem statement (every field up to cu_seqlens_k at the same offset), then the backward's tensors. */
+typedef struct aule_varlen_bwd_desc {
+    uint32_t struct_size;      /* = sizeof(aule_varlen_bwd_desc) = 192 */
+    int32_t dtype;
+    uint32_t batch;
+    uint32_t heads_q, heads_kv, head_dim;
+    uint32_t total_q;
+    uint32_t total_k;
+    uint32_t max_seqlen_q;
+    uint32_t max_seqlen_k;
+    float scale;
+    int32_t causal;
+    int32_t window_size;
+    int32_t device;
+    int64_t q_token_stride;
+    int64_t k_token_stride;
+    int64_t v_token_stride;
+    void* stream;              /* offset 80 */
+    const void* q;
+    const void* k;
+    const void* v;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k;   /* offset 120 */
+    const void* out;           /* offset 128; the forward's out */
+    const float* lse;          /* offset 136; the forward's lse (required) */
+    const void* dout;          /* offset 144; [total_q, heads_q, head_dim], contiguous */
+    void* dq;                  /* offset 152; [total_q, heads_q, head_dim], contiguous */
+    void* dk;                  /* offset 160; [total_k, heads_kv, head_dim], contiguous */
+    void* dv;                  /* offset 168 */
+    void* workspace;           /* offset 176; optional, size from aule_attention_varlen_backward_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 184 */
+} aule_varlen_bwd_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_varlen_forward_ex(const aule_varlen_desc* desc);
+int32_t aule_attention_varlen_backward_ex(const aule_varlen_bwd_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses. */
+uint64_t aule_attention_varlen_backward_workspace_size(const aule_varlen_bwd_desc* desc);
+
 /* Merge of two attention states (additive): out_a, out_b [rows, heads, head_dim] fp16 / bf16 are attention outputs of the same    */
 /* queries over two DISJOINT key sets, lse_a, lse_b [rows, heads] fp32 the natural logs of their softmax denominators (the lse of  */
 /* the calls above).  With M = max(lse_a, lse_b) and w_x = exp(lse_x - M):                                                          */
