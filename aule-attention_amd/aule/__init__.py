@@ -239,6 +239,44 @@ def flash_attention_paged_cascade(q, k_cache, v_cache, prefix_block_table, prefi
                          max_seqlen_q=max_seqlen_q, scale=scale, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
 
 
+def flash_attention_mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, scale=None,
+                              return_lse=False):
+    """Paged multi-head LATENT attention (MLA, the DeepSeek-V2 / V3 / R1 family in its absorbed decode form): decode and short
+    verify over a latent KV cache, without gathering the pages.  Not in the reference.  The contract is stated once, at
+    aule_mla_paged_desc in include/aule.h; in short:
+
+        q [total_tokens, heads_q, 576] fp16 / bf16: per head 512 compressed ("nope") dimensions, then 64 rotary ones; the token
+          stride is free as in flash_attention_paged_prefill;
+        kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576]) of q's dtype: ONE cache -- row pos of a
+          sequence is the key of every query head (all 576 elements) and the value (elements 0..511); the kernel reads it
+          from memory once for both products;
+        block_tables [batch, max_blocks], context_lens [batch] (the keys INCLUDING the new tokens -- write them first, see
+          below), cu_seqlens_q [batch + 1] int32 and max_seqlen_q as in flash_attention_paged_prefill, with the same
+          device-side clamps, positions (token i of sequence b at p = L_b - n_b + i sees key j iff j <= p), zeros and
+          lse = -inf for p < 0 or L_b = 0, and rows of no sequence never written;
+        cu_seqlens_q=None is plain decode: sequence b owns row b, q.shape[0] == batch;
+        max_seqlen_q=None with offsets given computes it with one device->host synchronisation; passing it keeps the call
+          free of synchronisation and capturable into a graph (a replay reads the current cu_seqlens_q, context_lens and
+          block_tables);
+        scale=None is 1/sqrt(576), the library's rule -- DeepSeek models pass their own, 1/sqrt(192) * mscale (the softmax
+          scale of the non-absorbed 128 + 64 head).
+
+    Returns [total_tokens, heads_q, 512], or (out, lse) with return_lse=True: lse [total_tokens, heads_q] fp32, the natural
+    log of the softmax denominator.  The keys of a sequence are split into ranges on the device from its own length (the
+    number of ranges comes from the shape alone; partials are combined in a fixed order, so two runs give the same bits).
+    There is no append kernel for the latent cache; with slots = paged_slot_mapping(block_tables, positions, block_size),
+    kv_cache.view(-1, 576).index_copy_(0, slots, new_rows) writes the new rows.  Out of scope: a sliding window, an FP8
+    latent cache, a backward pass, the non-absorbed prefill form (192 / 128).  Argument errors are ValueErrors raised
+    before the device is touched; CPU tensors raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_paged
+    return mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, scale=scale,
+                     return_lse=return_lse)
+
+
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
                            window_size=-1, return_lse=False):
     """Attention over a batch of sequences of DIFFERENT lengths packed along one token axis, forward and backward (autograd-aware):
@@ -519,7 +557,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

@@ -164,6 +164,35 @@ class PagedCascadeDesc(ctypes.Structure):
     ]
 
 
+class MlaPagedDesc(ctypes.Structure):
+    """struct aule_mla_paged_desc (include/aule.h): paged multi-head latent attention, one 576-wide cache, 512-wide values."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("batch", ctypes.c_uint32),
+        ("heads_q", ctypes.c_uint32),
+        ("qk_dim", ctypes.c_uint32),
+        ("v_dim", ctypes.c_uint32),
+        ("block_size", ctypes.c_uint32),
+        ("max_blocks", ctypes.c_uint32),
+        ("total_tokens", ctypes.c_uint32),
+        ("max_seqlen_q", ctypes.c_uint32),
+        ("scale", ctypes.c_float),
+        ("device", ctypes.c_int32),
+        ("q_token_stride", ctypes.c_int64),
+        ("stream", ctypes.c_void_p),
+        ("q", ctypes.c_void_p),
+        ("kv_cache", ctypes.c_void_p),
+        ("block_tables", ctypes.c_void_p),
+        ("context_lens", ctypes.c_void_p),
+        ("cu_seqlens_q", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 class VarlenDesc(ctypes.Structure):
     """struct aule_varlen_desc (include/aule.h): forward over a variable-length packed batch."""
     _problem_ = [
@@ -361,6 +390,8 @@ SIGNATURES = [
     ("aule_attention_paged_prefill_ex", _I32, [ctypes.POINTER(PagedPrefillDesc)]),
     ("aule_attention_paged_cascade_ex", _I32, [ctypes.POINTER(PagedCascadeDesc)]),
     ("aule_attention_paged_cascade_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedCascadeDesc)]),
+    ("aule_attention_mla_paged_ex", _I32, [ctypes.POINTER(MlaPagedDesc)]),
+    ("aule_attention_mla_paged_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedDesc)]),
     ("aule_attention_varlen_forward_ex", _I32, [ctypes.POINTER(VarlenDesc)]),
     ("aule_attention_varlen_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),
     ("aule_attention_varlen_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenBwdDesc)]),
@@ -375,6 +406,7 @@ SIGNATURES = [
     ("aule_hip_debug_last_forward_route", _I32, []),
     ("aule_hip_debug_forward_plan", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_shared_prefix_plan", _I32, [ctypes.POINTER(PagedCascadeDesc), ctypes.POINTER(_I32), _I32]),
+    ("aule_hip_debug_mla_plan", _I32, [ctypes.POINTER(MlaPagedDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_last_backward_route", _I32, []),
     ("aule_hip_debug_backward_route", _I32, [ctypes.POINTER(AttnBwdDesc)]),
     ("aule_hip_debug_forward_split_plan", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(_I32), _I32]),

@@ -776,17 +776,18 @@ def _ragged_kind(op, q, k_cache, v_cache, k_scale, v_scale):
     return Hkv, _paged_cache_kind(op, q, k_cache, v_cache, k_scale, v_scale)
 
 
-def _ragged_queries(op, q, fp8, Hkv, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, k_scale, v_scale):
-    """Step 2, the tables and the packed queries, the last rules before the device is needed.  Returns q as the kernels read it -- heads
-    contiguous, the token stride free -- and that stride in elements."""
-    B = _paged_tables(block_tables, context_lens)
+def _ragged_offsets(B, cu_seqlens_q, max_seqlen_q):
+    """The rules of cu_seqlens_q [batch + 1] int32 and of max_seqlen_q (a positive int, or None: read from the offsets)."""
     if not torch.is_tensor(cu_seqlens_q) or cu_seqlens_q.shape != (B + 1,):
         raise ValueError(f"cu_seqlens_q must be a [batch + 1] = [{B + 1}] tensor")
     if cu_seqlens_q.dtype != torch.int32:
         raise ValueError(f"cu_seqlens_q must be int32 (it is read on the device as it stands), got {cu_seqlens_q.dtype}")
     if max_seqlen_q is not None and (isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 1):
         raise ValueError(f"max_seqlen_q must be a positive int or None, got {max_seqlen_q!r}")
-    _scale_shapes(fp8, Hkv, k_scale, v_scale)
+
+
+def _packed_tokens(q):
+    """q [T, Hq, D] as the ragged kernels read it -- heads contiguous, the token stride free -- and that stride in elements."""
     T, Hq, D = q.shape
     if T > 1 and (q.stride(2) != 1 or q.stride(1) != D) or T <= 1 and not q.is_contiguous():
         q = q.contiguous()
@@ -794,6 +795,16 @@ def _ragged_queries(op, q, fp8, Hkv, block_tables, context_lens, cu_seqlens_q, m
     if q_stride < Hq * D or q_stride % 8 != 0 or q.storage_offset() % 8 != 0:
         raise ValueError(f"q's token stride ({q_stride}) and storage offset ({q.storage_offset()}) must be multiples of 8 elements "
                          f"and the stride at least heads_q * head_dim = {Hq * D} (16-byte loads); pass q.contiguous()")
+    return q, q_stride
+
+
+def _ragged_queries(op, q, fp8, Hkv, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, k_scale, v_scale):
+    """Step 2, the tables and the packed queries, the last rules before the device is needed.  Returns q as the kernels read it -- heads
+    contiguous, the token stride free -- and that stride in elements."""
+    B = _paged_tables(block_tables, context_lens)
+    _ragged_offsets(B, cu_seqlens_q, max_seqlen_q)
+    _scale_shapes(fp8, Hkv, k_scale, v_scale)
+    q, q_stride = _packed_tokens(q)
     _needs_device(op, q)
     return q, q_stride
 
@@ -893,6 +904,71 @@ def paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tab
         held += [pbt, plen, _attach_workspace(d, lib.aule_attention_paged_cascade_workspace_size, q.device),
                  _attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device)]
         _capi.check(lib.aule_attention_paged_cascade_ex(ctypes.byref(d)), "aule_attention_paged_cascade_ex")
+    return result
+
+
+def mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, scale=None, return_lse=False):
+    """Paged multi-head latent attention (DeepSeek-V2 / V3 / R1, absorbed form), decode and short verify over a latent KV cache;
+    csrc/fa_fwd_mla_paged_gfx950.hip behind aule_attention_mla_paged_ex, whose descriptor comment in include/aule.h is the contract:
+
+        q            [total_tokens, heads_q, 576] fp16 / bf16 (512 compressed dimensions, then 64 rotary ones); token stride free as
+                     in paged_prefill
+        kv_cache     [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576]) of q's dtype: ONE cache, a row is the key of
+                     every head and, in its first 512 elements, the value
+        block_tables, context_lens, cu_seqlens_q, max_seqlen_q: as in paged_prefill; cu_seqlens_q = None is plain decode (sequence
+                     b owns row b: q.shape[0] == batch), and max_seqlen_q = None with offsets given costs ONE device->host
+                     synchronisation
+        scale        None = 1/sqrt(576), the library's rule; DeepSeek models pass their own 1/sqrt(192) * mscale
+    Returns out [total_tokens, heads_q, 512], or (out, lse).  Rows that belong to no sequence are never written: out (and lse) come
+    from torch.empty.  All argument errors are ValueErrors raised before the device is touched."""
+    if kv_cache.dim() == 4 and kv_cache.shape[2] == 1:
+        kv_cache = kv_cache[:, :, 0]
+    if q.dim() != 3 or kv_cache.dim() != 3:
+        raise ValueError("expected q [T,Hq,576] and kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576])")
+    if q.shape[-1] != 576 or kv_cache.shape[-1] != 576:
+        raise ValueError(f"the latent width must be 576 (512 + 64): query={q.shape[-1]}, cache={kv_cache.shape[-1]}")
+    if q.dtype not in (torch.float16, torch.bfloat16) or kv_cache.dtype != q.dtype:
+        raise ValueError(f"q and kv_cache must share one of fp16 / bf16, got {q.dtype} and {kv_cache.dtype}")
+    if kv_cache.shape[1] == 0:
+        raise ValueError("block_size must be positive")
+    B = _paged_tables(block_tables, context_lens, None if cu_seqlens_q is not None else q.shape[0])
+    if cu_seqlens_q is not None:
+        _ragged_offsets(B, cu_seqlens_q, max_seqlen_q)
+    elif max_seqlen_q not in (None, 1):
+        raise ValueError(f"max_seqlen_q must be None or 1 without cu_seqlens_q (one token per sequence), got {max_seqlen_q!r}")
+    q, q_stride = _packed_tokens(q)
+    _needs_device("MLA", q)
+    lib = _capi.get_lib()
+    kv_cache = kv_cache.contiguous()
+    _same_device("paged MLA", q, kv_cache)
+    held = _int32_on(q.device, block_tables, context_lens) + ([] if cu_seqlens_q is None else _int32_on(q.device, cu_seqlens_q))
+    bt, cl, cu = held[0], held[1], held[2] if cu_seqlens_q is not None else None
+    T, Hq, _ = q.shape
+    if cu is None:
+        max_seqlen_q = 1
+    elif max_seqlen_q is None:
+        # the one documented synchronisation
+        max_seqlen_q = max(int((cu[1:] - cu[:-1]).max().item()), 1) if B > 0 else 1
+    out = torch.empty((T, Hq, 512), device=q.device, dtype=q.dtype)
+    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
+    result = (out, lse) if return_lse else out
+    if T * B * Hq == 0:
+        return result
+    d = _capi.MlaPagedDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    d.batch, d.heads_q, d.qk_dim, d.v_dim = B, Hq, 576, 512
+    d.block_size, d.max_blocks = kv_cache.shape[1], bt.shape[1]
+    d.total_tokens, d.max_seqlen_q, d.q_token_stride = T, min(max_seqlen_q, T), q_stride
+    d.scale = _abi_scale(1.0 / math.sqrt(576) if scale is None else scale)
+    d.device = _device_index(q.device)
+    d.stream = _stream_ptr(q.device)
+    d.q, d.kv_cache, d.out = q.data_ptr(), kv_cache.data_ptr(), out.data_ptr()
+    d.block_tables, d.context_lens = bt.data_ptr(), cl.data_ptr()
+    d.cu_seqlens_q = cu.data_ptr() if cu is not None else None
+    d.lse = lse.data_ptr() if lse is not None else None
+    held += [kv_cache, _attach_workspace(d, lib.aule_attention_mla_paged_workspace_size, q.device)]
+    _capi.check(lib.aule_attention_mla_paged_ex(ctypes.byref(d)), "aule_attention_mla_paged_ex")
     return result
 
 

@@ -71,6 +71,14 @@ static_assert(sizeof(aule_paged_cascade_desc) == 184 && offsetof(aule_paged_casc
                   offsetof(aule_paged_cascade_desc, prefix_block_table) == 152 && offsetof(aule_paged_cascade_desc, prefix_len) == 160 &&
                   offsetof(aule_paged_cascade_desc, workspace) == 168 && offsetof(aule_paged_cascade_desc, workspace_bytes) == 176,
               "aule_paged_cascade_desc layout is part of the ABI");
+static_assert(sizeof(aule_mla_paged_desc) == 136 && offsetof(aule_mla_paged_desc, batch) == 8 && offsetof(aule_mla_paged_desc, qk_dim) == 16 &&
+                  offsetof(aule_mla_paged_desc, block_size) == 24 && offsetof(aule_mla_paged_desc, total_tokens) == 32 &&
+                  offsetof(aule_mla_paged_desc, scale) == 40 && offsetof(aule_mla_paged_desc, q_token_stride) == 48 &&
+                  offsetof(aule_mla_paged_desc, stream) == 56 && offsetof(aule_mla_paged_desc, q) == 64 && offsetof(aule_mla_paged_desc, kv_cache) == 72 &&
+                  offsetof(aule_mla_paged_desc, block_tables) == 80 && offsetof(aule_mla_paged_desc, context_lens) == 88 &&
+                  offsetof(aule_mla_paged_desc, cu_seqlens_q) == 96 && offsetof(aule_mla_paged_desc, out) == 104 && offsetof(aule_mla_paged_desc, lse) == 112 &&
+                  offsetof(aule_mla_paged_desc, workspace) == 120 && offsetof(aule_mla_paged_desc, workspace_bytes) == 128,
+              "aule_mla_paged_desc layout is part of the ABI");
 #define AULE_SAME_OFFSET(field) (offsetof(aule_paged_cascade_desc, field) == offsetof(aule_paged_prefill_desc, field))
 static_assert(AULE_SAME_OFFSET(struct_size) && AULE_SAME_OFFSET(dtype) && AULE_SAME_OFFSET(cache_dtype) && AULE_SAME_OFFSET(batch) && AULE_SAME_OFFSET(heads_q) &&
                   AULE_SAME_OFFSET(heads_kv) && AULE_SAME_OFFSET(head_dim) && AULE_SAME_OFFSET(block_size) && AULE_SAME_OFFSET(max_blocks) &&
@@ -1254,6 +1262,70 @@ int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* d) {
     return launched("Paged cascade attention", rc);
 }
 
+// The paged MLA: one latent cache, 576 / 512, ragged queries as the prefill's or plain decode (null cu_seqlens_q).  One checker for its
+// three readers, built from the paged kinds' pieces where the fields are alike; `launch`: the pointer rules of a call that has
+// something to do as well (the size query and the plan hook read no pointer).  Host logic only, asked before the device is needed.
+static const char* varlen_stride_error(const char* name, int64_t stride, uint64_t token, const char* heads, Reason& why);   // (the token stride rule, below)
+static const char* mla_paged_desc_error(const aule_mla_paged_desc* d, bool launch, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_mla_paged_desc)) return kBadDescriptor;
+    if (!is_16_bit(d->dtype)) return "dtype (of q / out / kv_cache) must be fp16 or bf16";
+    if (d->qk_dim != 576 || d->v_dim != 512) return reasonf(why, "qk_dim %u / v_dim %u unsupported (576 / 512 only)", d->qk_dim, d->v_dim);
+    if (const char* e = paged_blocks_error(d)) return e;
+    if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
+    if (const char* e = varlen_stride_error("q", d->q_token_stride, (uint64_t)d->heads_q * d->qk_dim, "heads_q", why)) return e;
+    if (d->batch >= (1u << 30) || d->total_tokens >= (1u << 30)) return "batch / total_tokens too large";
+    if (((uint64_t)d->total_tokens + 64) * d->heads_q > 0x7fffffffull) return "total_tokens * heads_q too large (packed rows are counted in 32 bits)";
+    if (ragged_nothing_to_do(d)) return nullptr;
+    if (d->cu_seqlens_q == nullptr && d->total_tokens < d->batch) return "cu_seqlens_q is null (plain decode: sequence b owns row b) and total_tokens < batch";
+    if (!launch) return nullptr;
+    if (!d->q || !d->kv_cache || !d->block_tables || !d->context_lens || !d->out) return "null tensor pointer";
+    if (misaligned(d->q) || misaligned(d->out) || misaligned(d->kv_cache)) return "q, out and kv_cache must be 16-byte aligned";
+    return nullptr;
+}
+
+// (`d` passed mla_paged_desc_error)
+static void fill_mla_paged_args(const aule_mla_paged_desc* d, aule_hip::MlaArgs& a) {
+    a.q = d->q; a.kv_cache = d->kv_cache; a.out = d->out; a.lse = d->lse;
+    a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
+    a.T = (int)d->total_tokens; a.B = (int)d->batch; a.Hq = (int)d->heads_q;
+    a.max_seqlen_q = d->cu_seqlens_q == nullptr ? 1 : (int)(d->max_seqlen_q < d->total_tokens ? d->max_seqlen_q : d->total_tokens);
+    a.q_token_stride = d->q_token_stride;
+    a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
+    a.scale = resolve_scale(d->scale, d->qk_dim);
+    a.dtype = d->dtype;
+    a.device = d->device;
+}
+
+int32_t aule_attention_mla_paged_ex(const aule_mla_paged_desc* d) {
+    RoctxRange range("aule.mla_paged");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_paged_desc_error(d, true, text)) {
+        set_error("Paged MLA attention failed: %s", why);
+        return -3;
+    }
+    if (ragged_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaArgs a;
+    fill_mla_paged_args(d, a);
+    const aule_hip::MlaPlan plan = aule_hip::mla_plan(a);
+    if (plan.grid <= 0 || plan.grid > 0x7fffffffll) {
+        set_error("Paged MLA attention failed: the grid (row blocks * nsplit * batch) exceeds 2^31 - 1 workgroups");
+        return -3;
+    }
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)d->stream;
+    if (plan.nsplit == 1) return launched("Paged MLA attention", aule_hip::launch_mla_paged(a, plan, nullptr, stream));
+    aule_hip::ScopedWorkspace ws(plan.ws_bytes, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
+    if (ws.err != hipSuccess) {
+        set_error("Paged MLA attention failed: workspace allocation (%llu bytes): %s", (unsigned long long)plan.ws_bytes, hipGetErrorString(ws.err));
+        return -4;
+    }
+    return launched("Paged MLA attention", aule_hip::launch_mla_paged(a, plan, ws.ptr, stream));
+}
+
 // The variable-length kinds: aule_varlen_bwd_desc states the problem in aule_varlen_desc's fields up to cu_seqlens_k (the layout asserts
 // at the top of this file), so both are checked and read through that prefix; what follows it is each kind's own.  One checker per
 // kind; `launch`: the pointer and workspace rules of a call that has something to do as well (the size query reads no pointer).  Host
@@ -1692,6 +1764,23 @@ uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_de
     return cascade_plan(d, plan) ? plan.ws_bytes : 0;
 }
 
+// (the launch's plan: mla_plan reads the shape, none of the pointers)
+static bool mla_paged_plan(const aule_mla_paged_desc* d, aule_hip::MlaPlan& plan) {
+    Reason text;
+    if (mla_paged_desc_error(d, false, text)) return false;
+    plan = aule_hip::MlaPlan();
+    if (ragged_nothing_to_do(d)) return true;
+    aule_hip::MlaArgs a;
+    fill_mla_paged_args(d, a);
+    plan = aule_hip::mla_plan(a);
+    return plan.grid <= 0x7fffffffll;
+}
+
+uint64_t aule_attention_mla_paged_workspace_size(const aule_mla_paged_desc* d) {
+    aule_hip::MlaPlan plan;
+    return mla_paged_plan(d, plan) ? plan.ws_bytes : 0;
+}
+
 #ifdef AULE_DEBUG_HOOKS
 /* The timeline hooks exist only in the debug library (`make dbg` -> build/variants/libaule_dbg.so, -DAULE_DEBUG_HOOKS):
  * they launch instrumented kernel instances on caller-supplied pointers and are not part of the product libaule.so. */
@@ -1755,6 +1844,19 @@ int32_t aule_hip_debug_shared_prefix_plan(const aule_paged_cascade_desc* d, int3
     if (out == nullptr || cap < 7) return -7;
     for (int i = 0; i < 7; ++i) out[i] = v[i];
     return 7;
+}
+
+/* Debug hook: the launch plan of aule_attention_mla_paged_ex(d) as integers (include/aule.h lists them): the plan the launch and the
+ * workspace query read.  Pure host logic like the forward hook. */
+int32_t aule_hip_debug_mla_plan(const aule_mla_paged_desc* d, int32_t* out, int32_t cap) {
+    aule_hip::MlaPlan plan;
+    if (!mla_paged_plan(d, plan)) return -3;
+    if (plan.grid <= 0) return 0;
+    const int32_t v[6] = {plan.row_blocks, plan.rows_per_block, plan.nsplit, (int32_t)plan.grid,
+                          (int32_t)(uint32_t)(plan.ws_bytes & 0xffffffffull), (int32_t)(uint32_t)(plan.ws_bytes >> 32)};
+    if (out == nullptr || cap < 6) return -6;
+    for (int i = 0; i < 6; ++i) out[i] = v[i];
+    return 6;
 }
 
 /* Debug hook: what the most recent backward launch of this process ran (bit mask, include/aule.h). */

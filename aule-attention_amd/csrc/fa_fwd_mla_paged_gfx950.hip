@@ -1,0 +1,394 @@
+// fa_fwd_mla_paged_gfx950.hip -- paged multi-head LATENT attention (DeepSeek-V2 / V3 / R1, absorbed form): decode and short
+// verify over a latent KV cache (the contract is aule_mla_paged_desc in include/aule.h).
+//
+// One cache [num_blocks, block_size, 576] of q's dtype: row `pos` of a sequence is the key of ALL query heads (576 elements: 512
+// compressed dimensions, then 64 rotary ones) and its first 512 elements are the value.  q [T, Hq, 576], out [T, Hq, 512].
+// Per sequence, read and clamped HERE exactly as the paged prefill does:
+//     L = clamp(context_lens[b], 0, max_blocks * block_size)        s = clamp(cu[b], 0, T)      e = clamp(cu[b + 1], s, T)
+//     n = min(e - s, max_seqlen_q)  (cu == null: s = b, n = 1);   token i < n is row s + i, sits at p = L - n + i, sees key j iff j <= p.
+//
+// Layout.  The packed rows of a sequence are token-major (row r = token r / Hq, head r % Hq) and all share the latent, so a
+// workgroup owns a block of 64 rows and one key range, 4 waves, one per SIMD.  A tile of 64 latent rows (72 KB) is fetched from
+// global memory ONCE, into one LDS image (pitch 1152 + 80 bytes: fa_d256_common.h, "rows read both ways"), and serves both products:
+//   wave w = (rh = w & 1, ch = w >> 1) owns rows 32 rh .. 32 rh + 31 of the block.
+//   S^T[key][row] = K.Q^T: the wave sums over elements 288 ch .. 288 ch + 287 only (18 operand chunk pairs, its Q chunks in 72
+//     registers, 36 MFMAs of 32x32x16 per tile); the two waves of a row half exchange their partial sums through LDS (8 KB each,
+//     lane to lane: no layout involved) and both add own + other -- the same two numbers, so both hold the same bits;
+//   both do the rows' online softmax (log2 units, fp32 m / l), identically, and pack P^T as the B operand with no lane movement;
+//   O^T[d][row] += V^T.P^T: the wave accumulates value columns 256 ch .. 256 ch + 255 (8 accumulators, 32 MFMAs per tile), V read
+//     transposed (ds_read_b64_tr_b16) from the SAME image -- there is no second read of the cache for V.
+// 68 MFMAs per wave and 64-key tile with no product computed twice; LDS 78 848 + 32 768 = 111 616 bytes; the next tile sits in
+// 72 registers per thread while this one is computed (8 threads x 16 bytes = one 128-byte line of a latent row per request).
+//
+// Key ranges.  The host fixes nsplit from the shape alone (mla_plan below: the one place that decides row blocks, nsplit, grid and
+// workspace); every workgroup derives ITS sequence's range on the device from the clamped L: split k owns the 64-key tiles
+// [k * ceil(tiles(L) / nsplit), ...), so the work is balanced whatever the table's capacity.  nsplit == 1: one launch writes out /
+// lse.  nsplit > 1: fp32 partials in the workspace -- un-normalised O [nsplit][T * Hq][512], then {m (log2 units), l}
+// [nsplit][T * Hq][2], 514 floats per (split, token, head) -- and a combine kernel, one wave per row, that adds them in split order (no
+// atomics: two runs give the same bits).  A split with no tile, or whose rows see none of its keys, writes O = 0, m = -inf, l = 0.
+// Rows of no sequence are never written, by either kernel; a workspace is read only where this call wrote it.
+#include "fa_kernels.h"
+#include "fa_d256_common.h"
+
+namespace aule_hip {
+namespace {
+
+constexpr int kMlaQK = 576;                     // key / query width
+constexpr int kMlaV = 512;                      // value width
+constexpr int kMlaKeys = 64;                    // keys per tile
+constexpr int kMlaRB = kMlaQK * 2;              // bytes of a latent row
+constexpr int kMlaPitch = kMlaRB + 80;          // LDS pitch of the image: read as A operand rows AND transposed
+constexpr int kMlaG = kMlaQK / 16 / 2;          // operand chunk pairs of a wave's half of the reduction: 18
+constexpr int kMlaDT = kMlaV / 32 / 2;          // O accumulators of a wave's half of the value columns: 8
+constexpr int kMlaN = kMlaRB / 16 / 8;          // 16-byte chunks per thread and latent row: 9 (8 threads per row)
+
+struct MlaParams {
+    const char* q;
+    const char* kv;
+    char* o;
+    float* lse;
+    float* part_o;    // nsplit > 1: [nsplit][T * Hq][512]
+    float* part_ml;   //             [nsplit][T * Hq][2]
+    const int* table;
+    const int* ctx;
+    const int* cu;    // null: sequence b owns row b
+    long long q_stride;
+    long long rows_total;   // T * Hq
+    int T, B, Hq;
+    int bs, bs_shift;
+    int max_blocks, max_sq;
+    int row_blocks, nsplit;
+    float c;
+};
+
+// what both kernels derive for workgroup (rank, sequence b): the clamps of the contract and the block of packed rows
+struct MlaBlock {
+    int L, s, n;
+    int r0, rows;   // rows == 0: nothing to do
+    __device__ __forceinline__ MlaBlock(const MlaParams& p, int b, int rank) {
+        const int cap = p.max_blocks * p.bs;   // (< 2^30: the host checks)
+        L = min(max(p.ctx[b], 0), cap);
+        int e;
+        if (p.cu != nullptr) {
+            s = min(max(p.cu[b], 0), p.T);
+            e = min(max(p.cu[b + 1], s), p.T);
+        } else {
+            s = b;   // (b < T: the host checks)
+            e = b + 1;
+        }
+        n = min(e - s, p.max_sq);
+        const int R = n * p.Hq;   // (T + 64) * Hq < 2^31: the host checks
+        const int own = (R + kMlaRows - 1) / kMlaRows;
+        r0 = 0;
+        rows = 0;
+        if (rank < own) {
+            r0 = (own - 1 - rank) * kMlaRows;   // rank 0 is the sequence's last block, as in the paged prefill
+            rows = min(kMlaRows, R - r0);
+        }
+    }
+};
+
+// One latent tile of 64 keys on its way from the block pool to LDS: thread t takes rows (t >> 3) and (t >> 3) + 32 of the tile,
+// chunks (t & 7) + 8 i of each.
+struct MlaTile {
+    u32x4_t d[2][kMlaN];
+    long long slot[2];
+    __device__ __forceinline__ void lookup(const MlaParams& p, const int* tab, int k0, int kend, int tid) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int kv = k0 + (tid >> 3) + 32 * j;
+            long long at = 0;
+            if (kv < kend) {
+                const int lb = p.bs_shift >= 0 ? kv >> p.bs_shift : kv / p.bs;
+                at = (long long)tab[lb] * p.bs + (kv - lb * p.bs);
+            }
+            slot[j] = at;
+        }
+    }
+    __device__ __forceinline__ void load(const MlaParams& p, int k0, int kend, int tid) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int kv = k0 + (tid >> 3) + 32 * j;
+            const char* row = p.kv + slot[j] * kMlaRB + (tid & 7) * 16;
+#pragma unroll
+            for (int i = 0; i < kMlaN; ++i) d[j][i] = kv < kend ? *reinterpret_cast<const u32x4_t*>(row + 128 * i) : u32x4_t{};
+        }
+    }
+    __device__ __forceinline__ void store(char* img, int tid) const {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < kMlaN; ++i)
+                *reinterpret_cast<u32x4_t*>(img + ((tid >> 3) + 32 * j) * kMlaPitch + (tid & 7) * 16 + 128 * i) = d[j][i];
+    }
+};
+
+template <class T>
+__global__ void __launch_bounds__(256, 1) fa_fwd_mla_paged_kernel(const MlaParams p) {
+    __shared__ __attribute__((aligned(16))) char Ls[kMlaKeys * kMlaPitch];   // the latent image
+    __shared__ __attribute__((aligned(16))) char Xs[4 * 8 * 1024];           // partial scores: [wave][register quad][lane] 16 bytes
+
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int rh = wave & 1, ch = wave >> 1;
+    // work item: (split, rank, sequence), the sequences side by side
+    const int bid = (int)blockIdx.x;
+    const int b = bid % p.B, rest = bid / p.B;
+    const int rank = rest % p.row_blocks, split = rest / p.row_blocks;
+
+    const MlaBlock blk(p, b, rank);
+    if (blk.rows == 0) return;
+    const int L = blk.L, n = blk.n, r0 = blk.r0, rows = blk.rows;
+
+    // this lane's row (a lane past the end works on the block's last row and stores nothing)
+    const int rl = rh * 32 + l31;
+    const bool live = rl < rows;
+    const int r = r0 + min(rl, rows - 1);
+    const int tok = r / p.Hq, head = r - tok * p.Hq;
+    const int pos = L - n + tok;
+
+    // this split's keys of this block: whole tiles of the sequence's own length, cut at the block's last visible key
+    const int tiles = (L + kMlaKeys - 1) / kMlaKeys;
+    const int per = (tiles + p.nsplit - 1) / p.nsplit;
+    const int kbeg = split * per * kMlaKeys;
+    const int kend = min(min((split + 1) * per * kMlaKeys, L), L - n + (r0 + rows - 1) / p.Hq + 1);
+    const int ntiles = kend > kbeg ? (kend - kbeg + kMlaKeys - 1) / kMlaKeys : 0;
+    const int* tab = p.table + (long long)b * p.max_blocks;
+
+    // Q operand chunks of this lane's row, the wave's half of the reduction
+    const char* qrow = p.q + (((long long)blk.s + tok) * p.q_stride + (long long)head * kMlaQK) * 2 + ch * (kMlaRB / 2);
+    u32x4_t qf[kMlaG];
+#pragma unroll
+    for (int g = 0; g < kMlaG; ++g) qf[g] = *reinterpret_cast<const u32x4_t*>(qrow + 32 * g + 16 * hi);
+
+    f32x16_t o[kMlaDT];
+#pragma unroll
+    for (int i = 0; i < kMlaDT; ++i) o[i] = f32x16_t{};
+    float m = -__builtin_inff(), l = 0.f;
+
+    MlaTile kt;
+    if (ntiles > 0) {
+        kt.lookup(p, tab, kbeg, kend, tid);
+        kt.load(p, kbeg, kend, tid);
+        kt.lookup(p, tab, kbeg + kMlaKeys, kend, tid);
+    }
+    char* xmine = Xs + wave * 8192 + lane * 16;
+    const char* xother = Xs + (wave ^ 2) * 8192 + lane * 16;
+    for (int t = 0; t < ntiles; ++t) {
+        const int k0 = kbeg + t * kMlaKeys;
+        __syncthreads();   // every wave is done with the previous tile and the previous partial scores
+        kt.store(Ls, tid);
+        __syncthreads();
+        if (t + 1 < ntiles) {
+            kt.load(p, k0 + kMlaKeys, kend, tid);
+            kt.lookup(p, tab, k0 + 2 * kMlaKeys, kend, tid);
+        }
+        // partial S^T[key][row] over the wave's 288 elements
+        f32x16_t sc[2] = {f32x16_t{}, f32x16_t{}};
+        const char* kimg = Ls + l31 * kMlaPitch + ch * (kMlaRB / 2) + 16 * hi;
+#pragma unroll
+        for (int g = 0; g < kMlaG; ++g)
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) sc[kk] = mfma16<T>(lds_b128(kimg + 32 * kk * kMlaPitch + 32 * g), qf[g], sc[kk]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4)
+                *reinterpret_cast<f32x4_t*>(xmine + (4 * kk + q4) * 1024) = f32x4_t{sc[kk][4 * q4], sc[kk][4 * q4 + 1], sc[kk][4 * q4 + 2], sc[kk][4 * q4 + 3]};
+        __syncthreads();
+        // own + other, scale to log2 units, mask, running max over the lane pair (lanes l and l + 32 hold the same row)
+        float mx = -__builtin_inff();
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const f32x4_t y = *reinterpret_cast<const f32x4_t*>(xother + (4 * kk + q4) * 1024);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int rr = 4 * q4 + i;
+                    const int j = k0 + 32 * kk + crow(rr, hi);
+                    const float x = j <= pos && j < kend ? (sc[kk][rr] + y[i]) * p.c : -__builtin_inff();
+                    sc[kk][rr] = x;
+                    mx = fmaxf(mx, x);
+                }
+            }
+        mx = fmaxf(mx, xhalf(mx));
+        const float mn = fmaxf(m, mx);
+        const float mu = mn == -__builtin_inff() ? 0.f : mn;
+        const float alpha = fast_exp2(m - mu);   // m = -inf: 0
+        m = mn;
+        l *= alpha;
+#pragma unroll
+        for (int i = 0; i < kMlaDT; ++i) o[i] *= alpha;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) {
+                const float ex = fast_exp2(sc[kk][rr] - mu);
+                sc[kk][rr] = ex;
+                l += ex;
+            }
+        // O^T[d][row] += V^T.P^T over the wave's 256 value columns, V = the image's first 512 columns
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            const u32x4_t pb = pack_step<T>(sc[st >> 1], st & 1);
+#pragma unroll
+            for (int dt = 0; dt < kMlaDT; ++dt) o[dt] = mfma16<T>(lds_tr_step(Ls, kMlaPitch, 16 * st, 256 * ch + 32 * dt, lane), pb, o[dt]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    l += xhalf(l);
+    if (!live) return;
+    const long long orow = ((long long)blk.s + tok) * p.Hq + head;
+    if (p.nsplit > 1) {
+        const long long prow = (long long)split * p.rows_total + orow;
+        float* po = p.part_o + prow * kMlaV + 256 * ch;
+#pragma unroll
+        for (int dt = 0; dt < kMlaDT; ++dt)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4)
+                *reinterpret_cast<f32x4_t*>(po + 32 * dt + 8 * g4 + 4 * hi) = f32x4_t{o[dt][4 * g4], o[dt][4 * g4 + 1], o[dt][4 * g4 + 2], o[dt][4 * g4 + 3]};
+        if (ch == 0 && hi == 0) *reinterpret_cast<f32x2_t*>(p.part_ml + prow * 2) = f32x2_t{m, l};
+        return;
+    }
+    const float inv = l > 0.f ? 1.f / l : 0.f;
+    char* og = p.o + (orow * kMlaV + 256 * ch) * 2;
+#pragma unroll
+    for (int dt = 0; dt < kMlaDT; ++dt)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const int d = 32 * dt + 8 * g4 + 4 * hi;
+            const float a0 = o[dt][4 * g4] * inv, a1 = o[dt][4 * g4 + 1] * inv, a2 = o[dt][4 * g4 + 2] * inv, a3 = o[dt][4 * g4 + 3] * inv;
+            *reinterpret_cast<u32x2_t*>(og + d * 2) = u32x2_t{T::pack2(a0, a1), T::pack2(a2, a3)};
+        }
+    if (p.lse != nullptr && ch == 0 && hi == 0) {
+        const float mu = m == -__builtin_inff() ? 0.f : m;
+        p.lse[orow] = l > 0.f ? (mu + fast_log2(l)) * kLn2 : -__builtin_inff();
+    }
+}
+
+// The combine: workgroup (rank, sequence, sixteenth) takes four rows of the block the attention kernel's workgroups of that (rank,
+// sequence) wrote, one row per wave: lane k holds split k's {m, l} (nsplit <= 64 = a wave), the weights come from one wave
+// reduction, and the partial rows are added in split order with lane x on value columns 8 x .. 8 x + 7 (independent loads: the
+// splits are in flight together).  merge_attention_states' rule for empty sides: a split with m = -inf weighs nothing; all of
+// them empty gives zeros and lse = -inf.
+constexpr int kMlaCombineParts = kMlaRows / 4;
+static_assert(kMlaMaxSplit <= 64, "a lane per split");
+
+template <class T>
+__global__ void __launch_bounds__(256) fa_mla_combine_kernel(const MlaParams p) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int bid = (int)blockIdx.x;
+    const int sub = bid % kMlaCombineParts, rest = bid / kMlaCombineParts;
+    const int b = rest % p.B, rank = rest / p.B;
+    const MlaBlock blk(p, b, rank);
+    const int rl = 4 * sub + wave;
+    if (rl >= blk.rows) return;
+    const int r = blk.r0 + rl;
+    const int tok = r / p.Hq, head = r - tok * p.Hq;
+    const long long orow = ((long long)blk.s + tok) * p.Hq + head;
+    float mk = -__builtin_inff(), lk = 0.f;
+    if (lane < p.nsplit) {
+        const f32x2_t ml = *reinterpret_cast<const f32x2_t*>(p.part_ml + ((long long)lane * p.rows_total + orow) * 2);
+        mk = ml[0];
+        lk = ml[1];
+    }
+    float mm = mk;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mm = fmaxf(mm, __shfl_xor(mm, off, 64));
+    const float wk = mk == -__builtin_inff() ? 0.f : fast_exp2(mk - mm);
+    float ls = wk * lk;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ls += __shfl_xor(ls, off, 64);
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float* po = p.part_o + orow * kMlaV + 8 * lane;
+    for (int k = 0; k < p.nsplit; k += 4) {   // four splits in flight; lanes at or past nsplit hold weight 0
+        f32x4_t a[4], c[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float* src = po + (long long)min(k + i, p.nsplit - 1) * p.rows_total * kMlaV;
+            a[i] = *reinterpret_cast<const f32x4_t*>(src);
+            c[i] = *reinterpret_cast<const f32x4_t*>(src + 4);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float w = __shfl(wk, k + i, 64);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[e] += w == 0.f ? 0.f : w * a[i][e];
+                acc[4 + e] += w == 0.f ? 0.f : w * c[i][e];
+            }
+        }
+    }
+    const float inv = ls > 0.f ? 1.f / ls : 0.f;
+    *reinterpret_cast<u32x4_t*>(p.o + (orow * kMlaV + 8 * lane) * 2) =
+        u32x4_t{T::pack2(acc[0] * inv, acc[1] * inv), T::pack2(acc[2] * inv, acc[3] * inv), T::pack2(acc[4] * inv, acc[5] * inv),
+                T::pack2(acc[6] * inv, acc[7] * inv)};
+    if (p.lse != nullptr && lane == 0) p.lse[orow] = ls > 0.f ? (mm + fast_log2(ls)) * kLn2 : -__builtin_inff();
+}
+
+template <class T>
+int launch_type(const MlaParams& p, const MlaPlan& plan, hipStream_t stream) {
+    hipLaunchKernelGGL((fa_fwd_mla_paged_kernel<T>), dim3((unsigned)plan.grid), dim3(256), 0, stream, p);
+    int rc = (int)hipGetLastError();
+    if (rc != 0 || plan.nsplit == 1) return rc;
+    hipLaunchKernelGGL((fa_mla_combine_kernel<T>), dim3((unsigned)((long long)plan.row_blocks * p.B * kMlaCombineParts)), dim3(256), 0, stream, p);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+// The launch plan: the one place that decides row blocks, nsplit, grid and workspace (launch, size query, debug hook).  From the
+// shape alone: row blocks x batch x nsplit covers the device's compute units, nsplit at most kMlaMaxSplit and at most one split
+// per two 64-key tiles of the table's capacity (a split is worth a launch slot only with some keys to read); WHICH tiles a split
+// owns is decided on the device from each sequence's own length.
+MlaPlan mla_plan(const MlaArgs& a) {
+    MlaPlan plan;
+    if (a.T <= 0 || a.B <= 0 || a.Hq <= 0 || a.max_seqlen_q <= 0 || a.block_size <= 0 || a.max_blocks <= 0) return plan;
+    const long long n = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T;   // no sequence has more tokens than the batch
+    const long long rb = (n * a.Hq + kMlaRows - 1) / kMlaRows;
+    const long long base = rb * a.B;
+    const long long cus = device_cu_count(a.device);
+    const long long tiles = ((long long)a.block_size * a.max_blocks + kMlaKeys - 1) / kMlaKeys;
+    long long ns = (cus + base - 1) / base;
+    if (ns > kMlaMaxSplit) ns = kMlaMaxSplit;
+    if (ns > tiles / 2) ns = tiles / 2;
+    if (ns < 1) ns = 1;
+    plan.row_blocks = (int)rb;
+    plan.rows_per_block = kMlaRows;
+    plan.nsplit = (int)ns;
+    plan.grid = base * ns;
+    plan.ws_bytes = ns > 1 ? ((uint64_t)ns * (uint64_t)a.T * (uint64_t)a.Hq * (kMlaV + 2) * 4 + 15) & ~15ull : 0;
+    return plan;
+}
+
+// (`ws`: plan.ws_bytes bytes, 16-byte aligned, when plan.nsplit > 1)
+int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream) {
+    if (plan.grid <= 0 || plan.grid > 0x7fffffffll || (long long)plan.row_blocks * a.B * kMlaCombineParts > 0x7fffffffll) return -1;
+    if ((long long)a.block_size * a.max_blocks >= (1ll << 30)) return -1;
+    if (a.q_token_stride < (long long)a.Hq * kMlaQK || a.q_token_stride % 8 != 0) return -1;
+    if (((long long)a.T + kMlaRows) * a.Hq > 0x7fffffffll) return -1;   // the kernels count packed rows in 32 bits
+    if (a.cu_seqlens_q == nullptr && a.T < a.B) return -1;
+    if (plan.nsplit > 1 && ws == nullptr) return -1;
+    MlaParams p;
+    p.q = static_cast<const char*>(a.q); p.kv = static_cast<const char*>(a.kv_cache);
+    p.o = static_cast<char*>(a.out); p.lse = a.lse;
+    p.rows_total = (long long)a.T * a.Hq;
+    p.part_o = static_cast<float*>(ws);
+    p.part_ml = p.part_o != nullptr ? p.part_o + (long long)plan.nsplit * p.rows_total * kMlaV : nullptr;
+    p.table = a.block_tables; p.ctx = a.context_lens; p.cu = a.cu_seqlens_q;
+    p.q_stride = a.q_token_stride;
+    p.T = a.T; p.B = a.B; p.Hq = a.Hq;
+    p.bs = a.block_size;
+    p.bs_shift = (a.block_size & (a.block_size - 1)) == 0 ? __builtin_ctz((unsigned)a.block_size) : -1;
+    p.max_blocks = a.max_blocks;
+    p.max_sq = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T;
+    p.row_blocks = plan.row_blocks; p.nsplit = plan.nsplit;
+    p.c = a.scale * kLog2e;
+    if (a.dtype == kBF16) return launch_type<Bf16Traits>(p, plan, stream);
+    if (a.dtype == kF16) return launch_type<F16Traits>(p, plan, stream);
+    return -1;
+}
+
+}  // namespace aule_hip

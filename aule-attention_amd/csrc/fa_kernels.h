@@ -305,6 +305,40 @@ struct CascadeMergeArgs {
 long long cascade_merge_grid(const CascadeMergeArgs& a);
 int launch_cascade_merge(const CascadeMergeArgs& a, hipStream_t stream);
 
+// Paged multi-head latent attention (fa_fwd_mla_paged_gfx950.hip): ragged queries q [T, Hq, 576] against ONE latent cache
+//   kv_cache [num_blocks, block_size, 576] 16-bit of q's dtype -- row pos of a sequence is the key of all heads (576 elements) and,
+//   in its first 512 elements, the value; out [T, Hq, 512] contiguous, lse [T, Hq] fp32 or null.  Table, lengths, cu_seqlens_q,
+//   the clamps and the rows that are written as PagedPrefillArgs; cu_seqlens_q = null: sequence b owns row b, one token each
+//   (T >= B).  The caller guarantees 16-byte aligned q / out / kv_cache and q_token_stride % 8 == 0.
+struct MlaArgs {
+    const void* q;
+    const void* kv_cache;
+    void* out;
+    float* lse = nullptr;
+    const int* block_tables;
+    const int* context_lens;
+    const int* cu_seqlens_q = nullptr;
+    int T, B, Hq;
+    int max_seqlen_q;                   // (1 with a null cu_seqlens_q)
+    long long q_token_stride;
+    int block_size, max_blocks;
+    float scale;
+    int dtype;
+    int device = -1;                    // as FwdArgs::device
+};
+// The launch plan (mla_plan, beside the kernel: the one statement of the rule for launch, workspace query and debug hook).
+constexpr int kMlaRows = 64;       // packed rows (token-major, head-minor) per workgroup
+constexpr int kMlaMaxSplit = 64;   // key ranges per sequence, at most
+struct MlaPlan {
+    int row_blocks = 0;        // ceil(min(max_seqlen_q, T) * Hq / 64)
+    int rows_per_block = 0;    // 64
+    int nsplit = 0;            // 1 .. kMlaMaxSplit; split k of sequence b owns 64-key tiles [k * ceil(tiles(L_b) / nsplit), ...)
+    long long grid = 0;        // row_blocks * nsplit * B
+    uint64_t ws_bytes = 0;     // nsplit > 1: round16(nsplit * T * Hq * 514 * 4), else 0
+};
+MlaPlan mla_plan(const MlaArgs& a);   // all zero: nothing to launch; no pointer is read
+int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream);   // -1: unsupported arguments
+
 // Variable-length packed batches (fa_fwd_varlen_gfx950.hip, fa_bwd_varlen_gfx950.hip): sequences of different lengths packed
 // along one token axis, forward and backward.
 //   q, out, dout, dq [Tq, Hq, D] and k, v, dk, dv [Tk, Hkv, D] 16-bit, lse / delta [Tq, Hq] fp32; the heads of a token contiguous,

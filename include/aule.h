@@ -384,6 +384,69 @@ int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
 uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_desc* desc);
 
+/* Paged MLA (additive): multi-head LATENT attention in its absorbed form (DeepSeek-V2 / V3 / R1) -- decode and short verify over a */
+/* latent KV cache.  Dimensions: qk_dim = 576 (512 compressed dimensions, then 64 rotary ones) and v_dim = 512 are the only pair     */
+/* accepted (anything else: -3); dtype fp16 or bf16.                                                                                  */
+/* kv_cache is ONE cache, [num_blocks, block_size, 576] of q's dtype, contiguous, 16-byte aligned: row pos of sequence b is the key  */
+/* of ALL query heads (all 576 elements) and the value (elements 0..511); the kernel fetches it once for both products.  The block   */
+/* table rules are those of aule_attention_paged_decode_ex: block_tables [batch, max_blocks] int32, any block_size >= 1 (powers of   */
+/* two index with a shift); an entry at logical block >= ceil(L_b / block_size) is never dereferenced and a row at or beyond L_b     */
+/* never read.                                                                                                                        */
+/* q is [total_tokens, heads_q, 576] with q_token_stride elements from one token to the next (a multiple of 8, >= heads_q * 576, the */
+/* heads of a token contiguous); out is [total_tokens, heads_q, 512] contiguous; lse (optional) [total_tokens, heads_q] fp32, the    */
+/* natural log of the softmax denominator.  q and out are 16-byte aligned.                                                            */
+/* Ragged queries follow aule_paged_prefill_desc exactly: cu_seqlens_q [batch + 1] int32 on the device, context_lens[b] counts the   */
+/* keys INCLUDING the new tokens, and every clamp is made on the device (no host synchronisation; a stale or hostile value cannot     */
+/* index outside a buffer):  L_b = clamp(context_lens[b], 0, max_blocks * block_size),  s_b = clamp(cu[b], 0, total_tokens),          */
+/* e_b = clamp(cu[b + 1], s_b, total_tokens),  n_b = min(e_b - s_b, max_seqlen_q).  Token i of sequence b is row s_b + i, sits at     */
+/* p = L_b - n_b + i and sees key j iff j <= p.  A token with p < 0, or a sequence with L_b = 0, gives zeros and lse = -inf.  Rows    */
+/* of no sequence are NEVER written.  cu_seqlens_q = NULL means plain decode: sequence b owns row b, n_b = 1, max_seqlen_q is read    */
+/* as 1 (it must still be >= 1) and total_tokens >= batch is required.                                                                */
+/* scale = 0 means 1/sqrt(576), the library's rule; DeepSeek callers pass their own 1/sqrt(192) * mscale.                             */
+/* Launches: the packed rows of a sequence (token-major, head-minor) are cut into blocks of 64 and the keys of a sequence into        */
+/* nsplit ranges; nsplit is fixed on the host from the shape alone -- row blocks * batch * nsplit covers the device's compute units,  */
+/* at most 64 and at most one split per two 64-key tiles of the table's capacity -- and each workgroup derives its own sequence's     */
+/* range on the device from L_b: split k owns tiles [k * ceil(tiles(L_b) / nsplit), ...).  nsplit = 1: one launch.  nsplit > 1: fp32  */
+/* partials of 512 + 2 floats per (split, token, head) in the workspace and a combine kernel that adds them in split order (no        */
+/* atomics: two runs are bit-identical).  Workspace bytes = round16(nsplit * total_tokens * heads_q * 514 * 4), 0 for nsplit = 1:     */
+/* aule_attention_mla_paged_workspace_size() gives the number; a call without a workspace, or with one that is too small or not       */
+/* 16-byte aligned, allocates on the stream.  No host synchronisation, and no allocation when a workspace is passed: captures into a  */
+/* hipGraph, and a replay sees the CURRENT cu_seqlens_q, context_lens and block_tables.  With hostile cu_seqlens_q that make two      */
+/* sequences own the same row, that row's value is unspecified (and nothing outside out / lse is written).                            */
+/* Not built: a sliding window; an FP8 latent cache; a backward; the non-absorbed prefill form (192 / 128); a cache-append kernel    */
+/* for the latent cache (one index_copy_ of the new rows into the cache viewed as [num_blocks * block_size, 576] does it).            */
+/* The descriptor is checked before the device is needed: -3 for a refused descriptor and 0 for one with nothing to do               */
+/* (total_tokens = 0, batch = 0 or heads_q = 0) are answered without aule_init().                                                     */
+typedef struct aule_mla_paged_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_paged_desc) = 136 */
+    int32_t dtype;             /* offset 4; type of q / out / kv_cache: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    uint32_t batch;            /* offset 8; sequences */
+    uint32_t heads_q;          /* offset 12 */
+    uint32_t qk_dim;           /* offset 16; 576 */
+    uint32_t v_dim;            /* offset 20; 512 */
+    uint32_t block_size;       /* offset 24; any value > 0 */
+    uint32_t max_blocks;       /* offset 28; columns of block_tables */
+    uint32_t total_tokens;     /* offset 32; rows of q / out; 0: returns 0 without a launch */
+    uint32_t max_seqlen_q;     /* offset 36; >= 1: sizes the grid, and caps every n_b */
+    float scale;               /* offset 40; 0 -> 1/sqrt(576) */
+    int32_t device;            /* offset 44; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 48; elements, >= heads_q * 576, a multiple of 8 */
+    void* stream;              /* offset 56; hipStream_t */
+    const void* q;             /* offset 64; [total_tokens, heads_q, 576], 16-bit */
+    const void* kv_cache;      /* offset 72; [num_blocks, block_size, 576], q's dtype */
+    const int32_t* block_tables;   /* offset 80; [batch, max_blocks] */
+    const int32_t* context_lens;   /* offset 88; [batch]: keys per sequence, the new ones included */
+    const int32_t* cu_seqlens_q;   /* offset 96; [batch + 1], device; NULL: plain decode */
+    void* out;                 /* offset 104; [total_tokens, heads_q, 512], 16-bit, contiguous */
+    float* lse;                /* offset 112; optional (NULL to skip): [total_tokens, heads_q] fp32 */
+    void* workspace;           /* offset 120; optional, size from aule_attention_mla_paged_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 128 */
+} aule_mla_paged_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_mla_paged_ex(const aule_mla_paged_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
+uint64_t aule_attention_mla_paged_workspace_size(const aule_mla_paged_desc* desc);
+
 /* VARIABLE-LENGTH packed batches (additive): sequences of different lengths packed along one token axis, forward and backward --   */
 /* SFT with sequence packing, encoder batches without padding, prefill without a paged cache (flash_attn_varlen_func's case).        */
 /* Tensors: q, out, dout, dq are [total_q, heads_q, head_dim] and k, v, dk, dv [total_k, heads_kv, head_dim], fp16 or bf16, with     */
@@ -632,6 +695,11 @@ int32_t aule_hip_debug_forward_plan(const aule_attn_desc* desc, int32_t* out, in
 /* (negative: the capacity needed), 0 for a descriptor with nothing to do; -3 bad.  Host logic only, no aule_init(), no pointer of  */
 /* the descriptor is read.                                                                                                         */
 int32_t aule_hip_debug_shared_prefix_plan(const aule_paged_cascade_desc* desc, int32_t* out, int32_t cap);
+/* Debug: the launch plan of aule_attention_mla_paged_ex(desc) as integers -- out = {row blocks, rows per block (64), nsplit,       */
+/* workgroups (row blocks * nsplit * batch), workspace bytes low 32 bits, high 32 bits}.  Returns the ints written (negative: the   */
+/* capacity needed), 0 for a descriptor with nothing to do; -3 bad.  Host logic only, no aule_init(), no pointer of the descriptor  */
+/* is read (the pointer rules of the launch are not applied); without a device it plans for 256 compute units.                      */
+int32_t aule_hip_debug_mla_plan(const aule_mla_paged_desc* desc, int32_t* out, int32_t cap);
 /* Debug: bit mask of the kernels the most recent backward launch of this process ran -- 1 the 5-matmul mode (delta pass, dK/dV kernel  */
 /* spilling its dS, dQ = dS K), 2 / 4 the one-wave-per-SIMD dQ / dK/dV kernel, 8 / 16 their two-waves-per-SIMD predecessors, 32 the    */
 /* fp32 kernels, 64 (with 4) the D = 64 dK/dV instance with two key blocks per wave, 128 the head_dim 256 kernels (with 32 for fp32);  */
