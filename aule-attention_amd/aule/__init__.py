@@ -264,10 +264,10 @@ def flash_attention_mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlen
     Returns [total_tokens, heads_q, 512], or (out, lse) with return_lse=True: lse [total_tokens, heads_q] fp32, the natural
     log of the softmax denominator.  The keys of a sequence are split into ranges on the device from its own length (the
     number of ranges comes from the shape alone; partials are combined in a fixed order, so two runs give the same bits).
-    There is no append kernel for the latent cache; with slots = paged_slot_mapping(block_tables, positions, block_size),
-    kv_cache.view(-1, 576).index_copy_(0, slots, new_rows) writes the new rows.  Out of scope: a sliding window, an FP8
-    latent cache, a backward pass, the non-absorbed prefill form (192 / 128).  Argument errors are ValueErrors raised
-    before the device is touched; CPU tensors raise AuleError."""
+    mla_kv_append writes the new rows (one launch, with the rotation of the 64 rotary dimensions), with slots =
+    paged_slot_mapping(block_tables, positions, block_size); an FP8 latent cache is flash_attention_mla_paged_fp8.  Out of
+    scope: a sliding window, a backward pass, the non-absorbed prefill form (192 / 128).  Argument errors are ValueErrors
+    raised before the device is touched; CPU tensors raise AuleError."""
     try:
         import torch  # noqa: F401
     except ImportError as e:
@@ -275,6 +275,64 @@ def flash_attention_mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlen
     from ._torch import mla_paged
     return mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, scale=scale,
                      return_lse=return_lse)
+
+
+def flash_attention_mla_paged_fp8(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, scale=None,
+                                  return_lse=False, kv_scale=None):
+    """flash_attention_mla_paged over an FP8 latent cache: half the bytes per cached token, so twice the context or batch in
+    the same memory.  The contract is aule_mla_paged_fp8_desc in include/aule.h; in short:
+
+        kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576]) torch.float8_e4m3fn (OCP e4m3fn, the
+          format gfx950 converts in hardware; e4m3fnuz, e5m2 and 16-bit caches are ValueErrors);
+        kv_scale: ONE scale for the whole cache -- key = kv_scale * float(code row), value = its first 512 elements -- None
+          (1.0), a float, or a 0-d / [1] tensor, which stays on the device (no device->host copy; a graph replay reads its
+          current value).  quantize_mla_cache_fp8 makes (codes, scale) from a 16-bit cache; mla_kv_append writes the codes
+          of new tokens;
+        every other argument, the clamps, the rows that are written and the result: flash_attention_mla_paged.
+
+    The codes are converted exactly to q's dtype inside the kernel and kv_scale multiplies the score scale and the fp32
+    accumulators, never an element: with kv_scale = 1 the result equals flash_attention_mla_paged(q,
+    kv_cache.to(q.dtype), ...) bit for bit.  lse includes kv_scale (the log of the denominator over the dequantised keys)."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_paged_fp8
+    return mla_paged_fp8(q, kv_cache, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, scale=scale,
+                         return_lse=return_lse, kv_scale=kv_scale)
+
+
+def mla_kv_append(c_kv, k_pe, kv_cache, slot_mapping, kv_scale=None, cos=None, sin=None, positions=None, rope_layout="half"):
+    """The write side of the paged MLA's latent cache: put the rows [c_kv[t] | rope(k_pe[t])] of T new tokens into the cache
+    flash_attention_mla_paged / _fp8 read, in place, with one launch; returns None.
+
+        c_kv [T, 512], k_pe [T, 64] (or [T, 1, 64]) fp16 / bf16 (last dimension contiguous, token strides free multiples of
+          8 elements: slices of the fused down-projection are read in place);
+        kv_cache [num_blocks, block_size, 576] (or [..., 1, 576]) contiguous, c_kv's dtype (a copy of the bits) or
+          torch.float8_e4m3fn (code = cast(clamp(x / kv_scale, -448, 448)) -- quantize_mla_cache_fp8 with a given scale, bit
+          for bit; kv_scale None (1.0), a float, or a 0-d / [1] tensor that stays on the device);
+        slot_mapping [T] integer = block * block_size + offset (see paged_slot_mapping); negative or past the cache: the
+          token is skipped entirely; two tokens with the same slot in one call: which one wins is unspecified;
+        cos, sin [table_len, 32], positions [T] (all or none): rotate k_pe by table row positions[t] first, rope_layout
+          "half" (pairs (p, p + 32)) or "interleaved" (pairs (2p, 2p + 1), the layout of DeepSeek checkpoints); rounded to
+          the input's dtype, then quantised: bit-identical to the rotation pass followed by the plain append.  A position
+          outside the table skips the token entirely.
+
+    Argument errors are ValueErrors raised before the device is touched; CPU tensors raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_kv_append as impl
+    return impl(c_kv, k_pe, kv_cache, slot_mapping, kv_scale=kv_scale, cos=cos, sin=sin, positions=positions, rope_layout=rope_layout)
+
+
+def quantize_mla_cache_fp8(kv_cache):
+    """(codes, scale) for flash_attention_mla_paged_fp8: float8_e4m3fn codes of a latent cache and ONE scale, a [1] fp32 tensor
+    = amax / 448 (1.0 for an all-zero cache), saturating -- quantize_kv_cache_fp8's formula with one head.  Plain torch ops;
+    works on CPU tensors."""
+    from ._torch import quantize_mla_cache_fp8 as impl
+    return impl(kv_cache)
 
 
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
@@ -557,7 +615,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

@@ -193,6 +193,38 @@ class MlaPagedDesc(ctypes.Structure):
     ]
 
 
+class MlaPagedFp8Desc(ctypes.Structure):
+    """struct aule_mla_paged_fp8_desc (include/aule.h): aule_mla_paged_desc field for field, then the FP8 latent cache's one scale."""
+    _fields_ = MlaPagedDesc._fields_ + [("kv_scale", ctypes.c_void_p)]
+
+
+class MlaKvAppendDesc(ctypes.Structure):
+    """struct aule_mla_kv_append_desc (include/aule.h): the latent cache append of the paged MLA."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("cache_dtype", ctypes.c_int32),
+        ("rope_layout", ctypes.c_int32),
+        ("total_tokens", ctypes.c_uint32),
+        ("num_blocks", ctypes.c_uint32),
+        ("block_size", ctypes.c_uint32),
+        ("table_len", ctypes.c_uint32),
+        ("table_pitch", ctypes.c_uint32),
+        ("device", ctypes.c_int32),
+        ("c_kv_token_stride", ctypes.c_int64),
+        ("k_pe_token_stride", ctypes.c_int64),
+        ("stream", ctypes.c_void_p),
+        ("c_kv", ctypes.c_void_p),
+        ("k_pe", ctypes.c_void_p),
+        ("kv_cache", ctypes.c_void_p),
+        ("slot_mapping", ctypes.c_void_p),
+        ("kv_scale", ctypes.c_void_p),
+        ("cos", ctypes.c_void_p),
+        ("sin", ctypes.c_void_p),
+        ("positions", ctypes.c_void_p),
+    ]
+
+
 class VarlenDesc(ctypes.Structure):
     """struct aule_varlen_desc (include/aule.h): forward over a variable-length packed batch."""
     _problem_ = [
@@ -392,6 +424,9 @@ SIGNATURES = [
     ("aule_attention_paged_cascade_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedCascadeDesc)]),
     ("aule_attention_mla_paged_ex", _I32, [ctypes.POINTER(MlaPagedDesc)]),
     ("aule_attention_mla_paged_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedDesc)]),
+    ("aule_attention_mla_paged_fp8_ex", _I32, [ctypes.POINTER(MlaPagedFp8Desc)]),
+    ("aule_attention_mla_paged_fp8_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedFp8Desc)]),
+    ("aule_mla_kv_append_ex", _I32, [ctypes.POINTER(MlaKvAppendDesc)]),
     ("aule_attention_varlen_forward_ex", _I32, [ctypes.POINTER(VarlenDesc)]),
     ("aule_attention_varlen_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),
     ("aule_attention_varlen_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenBwdDesc)]),

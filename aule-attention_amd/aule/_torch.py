@@ -921,13 +921,43 @@ def mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_se
         scale        None = 1/sqrt(576), the library's rule; DeepSeek models pass their own 1/sqrt(192) * mscale
     Returns out [total_tokens, heads_q, 512], or (out, lse).  Rows that belong to no sequence are never written: out (and lse) come
     from torch.empty.  All argument errors are ValueErrors raised before the device is touched."""
+    return _mla_paged(False, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, None)
+
+
+def mla_paged_fp8(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, scale=None, return_lse=False, kv_scale=None):
+    """mla_paged over an FP8 latent cache (csrc/fa_fwd_mla_paged_fp8_gfx950.hip behind aule_attention_mla_paged_fp8_ex): kv_cache
+    [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576]) torch.float8_e4m3fn, key = kv_scale * float(code row), value =
+    its first 512 elements; kv_scale None (1.0), a float, or a 0-d / [1] tensor, which stays on the device (no device->host copy).
+    Every other argument, the result and the errors are mla_paged's; lse includes kv_scale."""
+    return _mla_paged(True, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale)
+
+
+def _latent_cache_kind(what, dtype, kv_cache, fp8, kv_scale, sixteen):
+    """The cache-kind rules of the two MLA readers and the latent append: a cache of the 16-bit `dtype`, or (fp8) torch.float8_e4m3fn
+    codes with ONE scale -- None, a float, a 0-d or [1] tensor.  sixteen: where a 16-bit cache goes, for the message."""
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{what} must be fp16 or bf16, got {dtype}")
+    if fp8:
+        if kv_cache.dtype != torch.float8_e4m3fn:
+            raise ValueError(f"an FP8 latent cache must be torch.float8_e4m3fn, got {kv_cache.dtype} (gfx950 converts OCP e4m3fn in "
+                             f"hardware; e4m3fnuz and e5m2 are not built; {sixteen})")
+        if torch.is_tensor(kv_scale) and not (kv_scale.dim() == 0 or kv_scale.shape == (1,)):
+            raise ValueError(f"kv_scale must be None, a float, or a 0-d / [1] tensor (one value for the whole cache), got shape {tuple(kv_scale.shape)}")
+    elif kv_scale is not None:
+        raise ValueError("kv_scale applies to a float8_e4m3fn cache only; a 16-bit cache holds the values themselves")
+
+
+def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale):
+    """Both cache kinds of the paged MLA: one validation, one descriptor (the FP8 kind's is the 16-bit kind's plus kv_scale)."""
     if kv_cache.dim() == 4 and kv_cache.shape[2] == 1:
         kv_cache = kv_cache[:, :, 0]
     if q.dim() != 3 or kv_cache.dim() != 3:
         raise ValueError("expected q [T,Hq,576] and kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576])")
     if q.shape[-1] != 576 or kv_cache.shape[-1] != 576:
         raise ValueError(f"the latent width must be 576 (512 + 64): query={q.shape[-1]}, cache={kv_cache.shape[-1]}")
-    if q.dtype not in (torch.float16, torch.bfloat16) or kv_cache.dtype != q.dtype:
+    if fp8:
+        _latent_cache_kind("q", q.dtype, kv_cache, True, kv_scale, "a 16-bit cache is flash_attention_mla_paged's")
+    elif q.dtype not in (torch.float16, torch.bfloat16) or kv_cache.dtype != q.dtype:
         raise ValueError(f"q and kv_cache must share one of fp16 / bf16, got {q.dtype} and {kv_cache.dtype}")
     if kv_cache.shape[1] == 0:
         raise ValueError("block_size must be positive")
@@ -954,7 +984,7 @@ def mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_se
     result = (out, lse) if return_lse else out
     if T * B * Hq == 0:
         return result
-    d = _capi.MlaPagedDesc()
+    d = _capi.MlaPagedFp8Desc() if fp8 else _capi.MlaPagedDesc()
     d.struct_size = ctypes.sizeof(d)
     d.dtype = _DTYPES[q.dtype]
     d.batch, d.heads_q, d.qk_dim, d.v_dim = B, Hq, 576, 512
@@ -967,9 +997,120 @@ def mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_se
     d.block_tables, d.context_lens = bt.data_ptr(), cl.data_ptr()
     d.cu_seqlens_q = cu.data_ptr() if cu is not None else None
     d.lse = lse.data_ptr() if lse is not None else None
+    if fp8:
+        ks = _fp8_scale(kv_scale, 1, q.device, "kv_scale")
+        d.kv_scale = ks.data_ptr()
+        held += [ks, kv_cache, _attach_workspace(d, lib.aule_attention_mla_paged_fp8_workspace_size, q.device)]
+        _capi.check(lib.aule_attention_mla_paged_fp8_ex(ctypes.byref(d)), "aule_attention_mla_paged_fp8_ex")
+        return result
     held += [kv_cache, _attach_workspace(d, lib.aule_attention_mla_paged_workspace_size, q.device)]
     _capi.check(lib.aule_attention_mla_paged_ex(ctypes.byref(d)), "aule_attention_mla_paged_ex")
     return result
+
+
+def quantize_mla_cache_fp8(kv_cache):
+    """(codes, scale) for the FP8 paged MLA: float8_e4m3fn codes of a [num_blocks, block_size, 576] (or [..., 1, 576]) latent cache and
+    ONE scale, a [1] fp32 tensor on the cache's device = amax / 448 (1.0 for an all-zero cache), with kv_cache ~= scale * codes.
+    quantize_kv_cache_fp8's formula with one head: divided, clamped to +-448 (torch's cast does not saturate), then cast.  Plain torch
+    ops; works on CPU tensors."""
+    if kv_cache.dim() not in (3, 4) or kv_cache.shape[-1] != 576 or (kv_cache.dim() == 4 and kv_cache.shape[2] != 1):
+        raise ValueError("expected a latent cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576])")
+    x = kv_cache.float()
+    amax = x.abs().amax().reshape(1) if x.numel() else x.new_zeros(1)
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax)).contiguous()
+    return (x / scale).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn), scale
+
+
+def mla_kv_append(c_kv, k_pe, kv_cache, slot_mapping, kv_scale=None, cos=None, sin=None, positions=None, rope_layout="half"):
+    """Write the latent rows of T new tokens into the paged MLA's cache, in place, with one launch (csrc/mla_kv_append_gfx950.hip
+    behind aule_mla_kv_append_ex, whose descriptor comment in include/aule.h is the contract):
+
+        c_kv [T, 512], k_pe [T, 64] (or [T, 1, 64]) fp16 / bf16 of one dtype; the last dimension contiguous, the token strides free
+                       multiples of 8 elements (slices of the fused down-projection's output are read in place)
+        kv_cache       [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576]), contiguous: c_kv's dtype (the bits are
+                       copied) or torch.float8_e4m3fn (code = cast(clamp(x / kv_scale, -448, 448)): quantize_mla_cache_fp8 with a
+                       given scale; kv_scale None (1.0), a float or a 0-d / [1] tensor, which stays on the device)
+        slot_mapping   [T] integer: block * block_size + offset (paged_slot_mapping); a negative slot or one past the cache skips the
+                       token entirely; two tokens with the same slot in one call: which one wins is unspecified
+        cos, sin, positions (all or none): rotate k_pe first -- tables [table_len, 32], token t uses row positions[t], rope_layout
+                       "half" pairs (p, p + 32) or "interleaved" pairs (2p, 2p + 1), the arithmetic of rope_raw, rounded to the
+                       input's dtype before any quantisation (bit-identical to rope_raw followed by the un-rotated append).  A
+                       position outside the table skips the token entirely.
+    Row slot_mapping[t] of the cache becomes [c_kv[t] | k_pe'[t]].  Returns None.  No device->host synchronisation; captures into a
+    graph.  All argument errors are ValueErrors raised before the device is touched; CPU tensors are an AuleError."""
+    if k_pe.dim() == 3 and k_pe.shape[1] == 1:
+        k_pe = k_pe[:, 0]
+    if kv_cache.dim() == 4 and kv_cache.shape[2] == 1:
+        kv_cache = kv_cache[:, :, 0]
+    if c_kv.dim() != 2 or k_pe.dim() != 2 or kv_cache.dim() != 3:
+        raise ValueError("expected c_kv [T,512], k_pe [T,64] (or [T,1,64]) and kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576])")
+    if c_kv.shape[1] != 512 or k_pe.shape[1] != 64 or kv_cache.shape[2] != 576:
+        raise ValueError(f"the latent row is 512 + 64 = 576 wide: c_kv={c_kv.shape[1]}, k_pe={k_pe.shape[1]}, cache={kv_cache.shape[2]}")
+    T = c_kv.shape[0]
+    if k_pe.shape[0] != T:
+        raise ValueError(f"c_kv has {T} tokens, k_pe {k_pe.shape[0]}")
+    if k_pe.dtype != c_kv.dtype:
+        raise ValueError(f"c_kv and k_pe must share one of fp16 / bf16, got {c_kv.dtype} and {k_pe.dtype}")
+    fp8 = kv_cache.dtype != c_kv.dtype
+    _latent_cache_kind("c_kv and k_pe", c_kv.dtype, kv_cache, fp8, kv_scale, "a 16-bit cache has c_kv's dtype")
+    if rope_layout not in _ROPE_LAYOUTS:
+        raise ValueError(f"unknown rope_layout {rope_layout!r} ('half' or 'interleaved')")
+    if not kv_cache.is_contiguous():
+        raise ValueError("kv_cache must be contiguous: the append writes in place and cannot copy it")
+    num_blocks, block_size, _ = kv_cache.shape
+    if block_size == 0:
+        raise ValueError("block_size must be positive")
+    for name, t, w in (("c_kv", c_kv, 512), ("k_pe", k_pe, 64)):
+        if t.stride(1) != 1:
+            raise ValueError(f"the last dimension of {name} must be contiguous, got stride {t.stride(1)}")
+        if T > 1 and t.stride(0) < w:
+            raise ValueError(f"{name}: the token stride {t.stride(0)} is smaller than a row of {w} elements")
+        if (T > 1 and t.stride(0) % 8) or t.storage_offset() % 8:
+            raise ValueError(f"{name}: rows must be 16-byte aligned (the token stride and the storage offset multiples of 8 elements)")
+    if slot_mapping.dim() != 1 or slot_mapping.shape[0] != T or slot_mapping.dtype.is_floating_point or slot_mapping.dtype == torch.bool:
+        raise ValueError(f"slot_mapping must be an integer tensor of shape [{T}]")
+    rope = cos is not None or sin is not None or positions is not None
+    if rope:
+        if cos is None or sin is None:
+            raise ValueError("cos and sin are required for RoPE (both or neither)")
+        if positions is None:
+            raise ValueError("positions are required with cos / sin: token t is rotated by table row positions[t]")
+        if positions.dim() != 1 or positions.shape[0] != T or positions.dtype.is_floating_point or positions.dtype == torch.bool:
+            raise ValueError(f"positions must be an integer tensor of shape [{T}]")
+        if cos.shape[-1] != 32 or sin.shape[-1] != 32:
+            raise ValueError(f"cos/sin must have shape [..., 32], got {tuple(cos.shape)} / {tuple(sin.shape)}")
+    if not c_kv.is_cuda:
+        raise _capi.AuleError("aule (HIP build): the MLA KV append needs ROCm device tensors; there is no CPU fallback")
+    _same_device("MLA KV append", c_kv, k_pe, kv_cache)
+    if T == 0 or num_blocks == 0:
+        return None
+    lib = _capi.get_lib()
+    dev = c_kv.device
+    slots = slot_mapping.to(device=dev, dtype=torch.int64).contiguous()
+    d = _capi.MlaKvAppendDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[c_kv.dtype]
+    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    d.rope_layout = _ROPE_LAYOUTS[rope_layout]
+    d.total_tokens, d.num_blocks, d.block_size = T, num_blocks, block_size
+    # (a stride of a dimension of extent 1 is never used: torch reports anything there)
+    d.c_kv_token_stride = c_kv.stride(0) if T > 1 else 512
+    d.k_pe_token_stride = k_pe.stride(0) if T > 1 else 64
+    d.device = _device_index(dev)
+    d.stream = _stream_ptr(dev)
+    d.c_kv, d.k_pe, d.kv_cache, d.slot_mapping = c_kv.data_ptr(), k_pe.data_ptr(), kv_cache.data_ptr(), slots.data_ptr()
+    held = [slots]
+    if fp8:
+        held.append(_fp8_scale(kv_scale, 1, dev, "kv_scale"))
+        d.kv_scale = held[-1].data_ptr()
+    if rope:
+        c, s_ = _rope_tables(cos, sin, 64, dev)
+        pos = positions.to(device=dev, dtype=torch.int64).contiguous()
+        d.table_len, d.table_pitch = c.shape[0], c.stride(0)
+        d.cos, d.sin, d.positions = c.data_ptr(), s_.data_ptr(), pos.data_ptr()
+        held += [c, s_, pos]
+    _capi.check(lib.aule_mla_kv_append_ex(ctypes.byref(d)), "aule_mla_kv_append_ex")
+    return None
 
 
 def merge_states(out_a, lse_a, out_b, lse_b):

@@ -79,6 +79,34 @@ static_assert(sizeof(aule_mla_paged_desc) == 136 && offsetof(aule_mla_paged_desc
                   offsetof(aule_mla_paged_desc, cu_seqlens_q) == 96 && offsetof(aule_mla_paged_desc, out) == 104 && offsetof(aule_mla_paged_desc, lse) == 112 &&
                   offsetof(aule_mla_paged_desc, workspace) == 120 && offsetof(aule_mla_paged_desc, workspace_bytes) == 128,
               "aule_mla_paged_desc layout is part of the ABI");
+static_assert(sizeof(aule_mla_paged_fp8_desc) == 144 && offsetof(aule_mla_paged_fp8_desc, kv_scale) == 136 &&
+                  offsetof(aule_mla_paged_fp8_desc, kv_scale) == sizeof(aule_mla_paged_desc) &&
+                  offsetof(aule_mla_paged_fp8_desc, batch) == offsetof(aule_mla_paged_desc, batch) &&
+                  offsetof(aule_mla_paged_fp8_desc, qk_dim) == offsetof(aule_mla_paged_desc, qk_dim) &&
+                  offsetof(aule_mla_paged_fp8_desc, total_tokens) == offsetof(aule_mla_paged_desc, total_tokens) &&
+                  offsetof(aule_mla_paged_fp8_desc, scale) == offsetof(aule_mla_paged_desc, scale) &&
+                  offsetof(aule_mla_paged_fp8_desc, q_token_stride) == offsetof(aule_mla_paged_desc, q_token_stride) &&
+                  offsetof(aule_mla_paged_fp8_desc, stream) == offsetof(aule_mla_paged_desc, stream) &&
+                  offsetof(aule_mla_paged_fp8_desc, q) == offsetof(aule_mla_paged_desc, q) &&
+                  offsetof(aule_mla_paged_fp8_desc, kv_cache) == offsetof(aule_mla_paged_desc, kv_cache) &&
+                  offsetof(aule_mla_paged_fp8_desc, cu_seqlens_q) == offsetof(aule_mla_paged_desc, cu_seqlens_q) &&
+                  offsetof(aule_mla_paged_fp8_desc, out) == offsetof(aule_mla_paged_desc, out) &&
+                  offsetof(aule_mla_paged_fp8_desc, lse) == offsetof(aule_mla_paged_desc, lse) &&
+                  offsetof(aule_mla_paged_fp8_desc, workspace) == offsetof(aule_mla_paged_desc, workspace) &&
+                  offsetof(aule_mla_paged_fp8_desc, workspace_bytes) == offsetof(aule_mla_paged_desc, workspace_bytes),
+              "aule_mla_paged_fp8_desc starts with aule_mla_paged_desc (the MLA entry points read both through that prefix)");
+static_assert(sizeof(aule_mla_kv_append_desc) == 128 && offsetof(aule_mla_kv_append_desc, dtype) == 4 &&
+                  offsetof(aule_mla_kv_append_desc, cache_dtype) == 8 && offsetof(aule_mla_kv_append_desc, rope_layout) == 12 &&
+                  offsetof(aule_mla_kv_append_desc, total_tokens) == 16 && offsetof(aule_mla_kv_append_desc, num_blocks) == 20 &&
+                  offsetof(aule_mla_kv_append_desc, block_size) == 24 && offsetof(aule_mla_kv_append_desc, table_len) == 28 &&
+                  offsetof(aule_mla_kv_append_desc, table_pitch) == 32 && offsetof(aule_mla_kv_append_desc, device) == 36 &&
+                  offsetof(aule_mla_kv_append_desc, c_kv_token_stride) == 40 && offsetof(aule_mla_kv_append_desc, k_pe_token_stride) == 48 &&
+                  offsetof(aule_mla_kv_append_desc, stream) == 56 && offsetof(aule_mla_kv_append_desc, c_kv) == 64 &&
+                  offsetof(aule_mla_kv_append_desc, k_pe) == 72 && offsetof(aule_mla_kv_append_desc, kv_cache) == 80 &&
+                  offsetof(aule_mla_kv_append_desc, slot_mapping) == 88 && offsetof(aule_mla_kv_append_desc, kv_scale) == 96 &&
+                  offsetof(aule_mla_kv_append_desc, cos) == 104 && offsetof(aule_mla_kv_append_desc, sin) == 112 &&
+                  offsetof(aule_mla_kv_append_desc, positions) == 120,
+              "aule_mla_kv_append_desc layout is part of the ABI");
 #define AULE_SAME_OFFSET(field) (offsetof(aule_paged_cascade_desc, field) == offsetof(aule_paged_prefill_desc, field))
 static_assert(AULE_SAME_OFFSET(struct_size) && AULE_SAME_OFFSET(dtype) && AULE_SAME_OFFSET(cache_dtype) && AULE_SAME_OFFSET(batch) && AULE_SAME_OFFSET(heads_q) &&
                   AULE_SAME_OFFSET(heads_kv) && AULE_SAME_OFFSET(head_dim) && AULE_SAME_OFFSET(block_size) && AULE_SAME_OFFSET(max_blocks) &&
@@ -1262,13 +1290,16 @@ int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* d) {
     return launched("Paged cascade attention", rc);
 }
 
-// The paged MLA: one latent cache, 576 / 512, ragged queries as the prefill's or plain decode (null cu_seqlens_q).  One checker for its
-// three readers, built from the paged kinds' pieces where the fields are alike; `launch`: the pointer rules of a call that has
-// something to do as well (the size query and the plan hook read no pointer).  Host logic only, asked before the device is needed.
+// The paged MLA: one latent cache, 576 / 512, ragged queries as the prefill's or plain decode (null cu_seqlens_q).  Two kinds:
+// aule_mla_paged_fp8_desc is aule_mla_paged_desc field for field plus kv_scale (the layout asserts at the top of this file), so both are
+// checked and read through that prefix; `fp8` says which one `d` is.  One checker for all their readers, built from the paged kinds'
+// pieces where the fields are alike; `launch`: the pointer rules of a call that has something to do as well (the size queries and the
+// plan hook read no pointer).  Host logic only, asked before the device is needed.
+static const aule_mla_paged_desc* mla_prefix(const aule_mla_paged_fp8_desc* d) { return reinterpret_cast<const aule_mla_paged_desc*>(d); }
 static const char* varlen_stride_error(const char* name, int64_t stride, uint64_t token, const char* heads, Reason& why);   // (the token stride rule, below)
-static const char* mla_paged_desc_error(const aule_mla_paged_desc* d, bool launch, Reason& why) {
-    if (d == nullptr || d->struct_size != sizeof(aule_mla_paged_desc)) return kBadDescriptor;
-    if (!is_16_bit(d->dtype)) return "dtype (of q / out / kv_cache) must be fp16 or bf16";
+static const char* mla_paged_desc_error(const aule_mla_paged_desc* d, bool fp8, bool launch, Reason& why) {
+    if (d == nullptr || d->struct_size != (fp8 ? sizeof(aule_mla_paged_fp8_desc) : sizeof(aule_mla_paged_desc))) return kBadDescriptor;
+    if (!is_16_bit(d->dtype)) return fp8 ? kDtypeOfQ : "dtype (of q / out / kv_cache) must be fp16 or bf16";
     if (d->qk_dim != 576 || d->v_dim != 512) return reasonf(why, "qk_dim %u / v_dim %u unsupported (576 / 512 only)", d->qk_dim, d->v_dim);
     if (const char* e = paged_blocks_error(d)) return e;
     if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
@@ -1280,11 +1311,16 @@ static const char* mla_paged_desc_error(const aule_mla_paged_desc* d, bool launc
     if (!launch) return nullptr;
     if (!d->q || !d->kv_cache || !d->block_tables || !d->context_lens || !d->out) return "null tensor pointer";
     if (misaligned(d->q) || misaligned(d->out) || misaligned(d->kv_cache)) return "q, out and kv_cache must be 16-byte aligned";
+    if (fp8) {
+        const float* kv_scale = reinterpret_cast<const aule_mla_paged_fp8_desc*>(d)->kv_scale;   // (read where `d` is one)
+        if (kv_scale == nullptr) return "null kv_scale (one fp32 value on the device)";
+        if ((reinterpret_cast<uintptr_t>(kv_scale) & 3) != 0) return "kv_scale must be 4-byte aligned";
+    }
     return nullptr;
 }
 
-// (`d` passed mla_paged_desc_error)
-static void fill_mla_paged_args(const aule_mla_paged_desc* d, aule_hip::MlaArgs& a) {
+// (`d` passed mla_paged_desc_error with the same `fp8`)
+static void fill_mla_paged_args(const aule_mla_paged_desc* d, bool fp8, aule_hip::MlaArgs& a) {
     a.q = d->q; a.kv_cache = d->kv_cache; a.out = d->out; a.lse = d->lse;
     a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
     a.T = (int)d->total_tokens; a.B = (int)d->batch; a.Hq = (int)d->heads_q;
@@ -1294,36 +1330,50 @@ static void fill_mla_paged_args(const aule_mla_paged_desc* d, aule_hip::MlaArgs&
     a.scale = resolve_scale(d->scale, d->qk_dim);
     a.dtype = d->dtype;
     a.device = d->device;
+    if (fp8) {
+        a.cache_kind = aule_hip::kCacheFp8E4M3;
+        a.kv_scale = reinterpret_cast<const aule_mla_paged_fp8_desc*>(d)->kv_scale;
+    }
 }
 
-int32_t aule_attention_mla_paged_ex(const aule_mla_paged_desc* d) {
-    RoctxRange range("aule.mla_paged");
+// (both kinds' launch entry; `what`: the kind's error prefix)
+static int32_t mla_paged_launch(const aule_mla_paged_desc* d, bool fp8, const char* what) {
     std::lock_guard<std::mutex> lk(g_mu);
     Reason text;
-    if (const char* why = mla_paged_desc_error(d, true, text)) {
-        set_error("Paged MLA attention failed: %s", why);
+    if (const char* why = mla_paged_desc_error(d, fp8, true, text)) {
+        set_error("%s failed: %s", what, why);
         return -3;
     }
     if (ragged_nothing_to_do(d)) return 0;
     if (!initialised()) return -1;
     aule_hip::MlaArgs a;
-    fill_mla_paged_args(d, a);
+    fill_mla_paged_args(d, fp8, a);
     const aule_hip::MlaPlan plan = aule_hip::mla_plan(a);
     if (plan.grid <= 0 || plan.grid > 0x7fffffffll) {
-        set_error("Paged MLA attention failed: the grid (row blocks * nsplit * batch) exceeds 2^31 - 1 workgroups");
+        set_error("%s failed: the grid (row blocks * nsplit * batch) exceeds 2^31 - 1 workgroups", what);
         return -3;
     }
     DeviceGuard g(d->device);
     int rc = ensure_configured();
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)d->stream;
-    if (plan.nsplit == 1) return launched("Paged MLA attention", aule_hip::launch_mla_paged(a, plan, nullptr, stream));
+    if (plan.nsplit == 1) return launched(what, aule_hip::launch_mla_paged(a, plan, nullptr, stream));
     aule_hip::ScopedWorkspace ws(plan.ws_bytes, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
     if (ws.err != hipSuccess) {
-        set_error("Paged MLA attention failed: workspace allocation (%llu bytes): %s", (unsigned long long)plan.ws_bytes, hipGetErrorString(ws.err));
+        set_error("%s failed: workspace allocation (%llu bytes): %s", what, (unsigned long long)plan.ws_bytes, hipGetErrorString(ws.err));
         return -4;
     }
-    return launched("Paged MLA attention", aule_hip::launch_mla_paged(a, plan, ws.ptr, stream));
+    return launched(what, aule_hip::launch_mla_paged(a, plan, ws.ptr, stream));
+}
+
+int32_t aule_attention_mla_paged_ex(const aule_mla_paged_desc* d) {
+    RoctxRange range("aule.mla_paged");
+    return mla_paged_launch(d, false, "Paged MLA attention");
+}
+
+int32_t aule_attention_mla_paged_fp8_ex(const aule_mla_paged_fp8_desc* d) {
+    RoctxRange range("aule.mla_paged_fp8");
+    return mla_paged_launch(mla_prefix(d), true, "Paged MLA FP8 attention");
 }
 
 // The variable-length kinds: aule_varlen_bwd_desc states the problem in aule_varlen_desc's fields up to cu_seqlens_k (the layout asserts
@@ -1609,6 +1659,63 @@ int32_t aule_kv_cache_append_ex(const aule_kv_append_desc* d) {
     return launched("KV cache append", aule_hip::launch_kv_append(a, (hipStream_t)d->stream));
 }
 
+static bool mla_kv_append_nothing_to_do(const aule_mla_kv_append_desc* d) { return d->total_tokens == 0; }
+
+// 0 fine, else the reason the descriptor is refused (host logic only: no pointer is dereferenced; its only reader is the launch
+// entry, so the pointer rules of a call that has something to do are stated here too)
+static const char* mla_kv_append_error(const aule_mla_kv_append_desc* d, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_mla_kv_append_desc)) return kBadDescriptor;
+    if (!is_16_bit(d->dtype)) return "dtype (of c_kv / k_pe) must be fp16 or bf16";
+    if (const char* e = cache_dtype_error(d->cache_dtype)) return e;
+    if (d->rope_layout != AULE_ROPE_HALF && d->rope_layout != AULE_ROPE_INTERLEAVED)
+        return reasonf(why, "unknown rope_layout %d (AULE_ROPE_HALF or AULE_ROPE_INTERLEAVED)", d->rope_layout);
+    if (d->block_size == 0) return "block_size must be positive";
+    if (d->c_kv_token_stride < 512) return reasonf(why, "c_kv_token_stride (%lld) is smaller than a row (512 elements)", (long long)d->c_kv_token_stride);
+    if (d->k_pe_token_stride < 64) return reasonf(why, "k_pe_token_stride (%lld) is smaller than a row (64 elements)", (long long)d->k_pe_token_stride);
+    if (d->c_kv_token_stride % 8 != 0 || d->k_pe_token_stride % 8 != 0) return "token strides must be multiples of 8 elements (16-byte loads)";
+    const bool any_rope = d->cos || d->sin || d->positions || d->table_len || d->table_pitch;
+    const bool all_rope = d->cos && d->sin && d->positions && d->table_len;
+    if (any_rope && !all_rope) return "RoPE group only partly given (cos, sin, positions and table_len go together)";
+    if (all_rope && d->table_pitch != 0 && (d->table_pitch < 32 || d->table_pitch % 4 != 0)) return "table_pitch must be 0 or a multiple of 4 that is >= 32";
+    if (mla_kv_append_nothing_to_do(d)) return nullptr;
+    if (!d->c_kv || !d->k_pe || !d->kv_cache || !d->slot_mapping) return "null tensor pointer";
+    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
+    if (fp8 && !d->kv_scale) return "null kv_scale (one fp32 value on the device)";
+    if (!fp8 && d->kv_scale) return "kv_scale applies to an FP8 cache only; a 16-bit cache holds the values themselves";
+    if ((reinterpret_cast<uintptr_t>(d->kv_scale) & 3) != 0) return "kv_scale must be 4-byte aligned";
+    if (misaligned(d->c_kv) || misaligned(d->k_pe) || misaligned(d->kv_cache) || misaligned(d->cos) || misaligned(d->sin))
+        return "c_kv, k_pe, kv_cache and the tables must be 16-byte aligned";
+    return nullptr;
+}
+
+int32_t aule_mla_kv_append_ex(const aule_mla_kv_append_desc* d) {
+    RoctxRange range("aule.mla_kv_append");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_kv_append_error(d, text)) {
+        set_error("MLA KV append failed: %s", why);
+        return -3;
+    }
+    if (mla_kv_append_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaKvAppendArgs a;
+    a.c_kv = d->c_kv; a.k_pe = d->k_pe; a.kv_cache = d->kv_cache;
+    a.slot_mapping = reinterpret_cast<const long long*>(d->slot_mapping);
+    a.T = (int)d->total_tokens;
+    a.num_blocks = (long long)d->num_blocks; a.block_size = (int)d->block_size;
+    a.c_kv_token_stride = d->c_kv_token_stride; a.k_pe_token_stride = d->k_pe_token_stride;
+    a.dtype = d->dtype;
+    if (d->cache_dtype == AULE_KV_CACHE_FP8_E4M3) {
+        a.cache_kind = aule_hip::kCacheFp8E4M3;
+        a.kv_scale = d->kv_scale;
+    }
+    a.cos = d->cos; a.sin = d->sin; a.positions = reinterpret_cast<const long long*>(d->positions);
+    a.table_len = (long long)d->table_len; a.table_pitch = (int)d->table_pitch;
+    a.rope_layout = d->rope_layout;
+    DeviceGuard g(d->device);
+    return launched("MLA KV append", aule_hip::launch_mla_kv_append(a, (hipStream_t)d->stream));
+}
+
 uint64_t aule_attention_backward_workspace_size(const aule_attn_bwd_desc* d) {
     Reason text;
     if (attn_desc_error(attn_prefix(d), sizeof(aule_attn_bwd_desc), text)) return 0;
@@ -1765,20 +1872,25 @@ uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_de
 }
 
 // (the launch's plan: mla_plan reads the shape, none of the pointers)
-static bool mla_paged_plan(const aule_mla_paged_desc* d, aule_hip::MlaPlan& plan) {
+static bool mla_paged_plan(const aule_mla_paged_desc* d, bool fp8, aule_hip::MlaPlan& plan) {
     Reason text;
-    if (mla_paged_desc_error(d, false, text)) return false;
+    if (mla_paged_desc_error(d, fp8, false, text)) return false;
     plan = aule_hip::MlaPlan();
     if (ragged_nothing_to_do(d)) return true;
     aule_hip::MlaArgs a;
-    fill_mla_paged_args(d, a);
+    fill_mla_paged_args(d, false, a);   // (the plan reads the shape: no pointer, not the cache kind)
     plan = aule_hip::mla_plan(a);
     return plan.grid <= 0x7fffffffll;
 }
 
 uint64_t aule_attention_mla_paged_workspace_size(const aule_mla_paged_desc* d) {
     aule_hip::MlaPlan plan;
-    return mla_paged_plan(d, plan) ? plan.ws_bytes : 0;
+    return mla_paged_plan(d, false, plan) ? plan.ws_bytes : 0;
+}
+
+uint64_t aule_attention_mla_paged_fp8_workspace_size(const aule_mla_paged_fp8_desc* d) {
+    aule_hip::MlaPlan plan;
+    return mla_paged_plan(mla_prefix(d), true, plan) ? plan.ws_bytes : 0;
 }
 
 #ifdef AULE_DEBUG_HOOKS
@@ -1850,7 +1962,7 @@ int32_t aule_hip_debug_shared_prefix_plan(const aule_paged_cascade_desc* d, int3
  * workspace query read.  Pure host logic like the forward hook. */
 int32_t aule_hip_debug_mla_plan(const aule_mla_paged_desc* d, int32_t* out, int32_t cap) {
     aule_hip::MlaPlan plan;
-    if (!mla_paged_plan(d, plan)) return -3;
+    if (!mla_paged_plan(d, false, plan)) return -3;
     if (plan.grid <= 0) return 0;
     const int32_t v[6] = {plan.row_blocks, plan.rows_per_block, plan.nsplit, (int32_t)plan.grid,
                           (int32_t)(uint32_t)(plan.ws_bytes & 0xffffffffull), (int32_t)(uint32_t)(plan.ws_bytes >> 32)};

@@ -3,6 +3,8 @@
 //
 // One cache [num_blocks, block_size, 576] of q's dtype: row `pos` of a sequence is the key of ALL query heads (576 elements: 512
 // compressed dimensions, then 64 rotary ones) and its first 512 elements are the value.  q [T, Hq, 576], out [T, Hq, 512].
+// (Or a cache of e4m3fn codes with one fp32 scale: its attention kernel is the same body, fa_mla_common.h, instantiated in
+// fa_fwd_mla_paged_fp8_gfx950.hip; plan, launch and combine are the ones here.)
 // Per sequence, read and clamped HERE exactly as the paged prefill does:
 //     L = clamp(context_lens[b], 0, max_blocks * block_size)        s = clamp(cu[b], 0, T)      e = clamp(cu[b + 1], s, T)
 //     n = min(e - s, max_seqlen_q)  (cu == null: s = b, n = 1);   token i < n is row s + i, sits at p = L - n + i, sees key j iff j <= p.
@@ -27,245 +29,16 @@
 // [nsplit][T * Hq][2], 514 floats per (split, token, head) -- and a combine kernel, one wave per row, that adds them in split order (no
 // atomics: two runs give the same bits).  A split with no tile, or whose rows see none of its keys, writes O = 0, m = -inf, l = 0.
 // Rows of no sequence are never written, by either kernel; a workspace is read only where this call wrote it.
-#include "fa_kernels.h"
-#include "fa_d256_common.h"
+#include "fa_mla_common.h"
 
 namespace aule_hip {
 namespace {
 
-constexpr int kMlaQK = 576;                     // key / query width
-constexpr int kMlaV = 512;                      // value width
-constexpr int kMlaKeys = 64;                    // keys per tile
-constexpr int kMlaRB = kMlaQK * 2;              // bytes of a latent row
-constexpr int kMlaPitch = kMlaRB + 80;          // LDS pitch of the image: read as A operand rows AND transposed
-constexpr int kMlaG = kMlaQK / 16 / 2;          // operand chunk pairs of a wave's half of the reduction: 18
-constexpr int kMlaDT = kMlaV / 32 / 2;          // O accumulators of a wave's half of the value columns: 8
-constexpr int kMlaN = kMlaRB / 16 / 8;          // 16-byte chunks per thread and latent row: 9 (8 threads per row)
-
-struct MlaParams {
-    const char* q;
-    const char* kv;
-    char* o;
-    float* lse;
-    float* part_o;    // nsplit > 1: [nsplit][T * Hq][512]
-    float* part_ml;   //             [nsplit][T * Hq][2]
-    const int* table;
-    const int* ctx;
-    const int* cu;    // null: sequence b owns row b
-    long long q_stride;
-    long long rows_total;   // T * Hq
-    int T, B, Hq;
-    int bs, bs_shift;
-    int max_blocks, max_sq;
-    int row_blocks, nsplit;
-    float c;
-};
-
-// what both kernels derive for workgroup (rank, sequence b): the clamps of the contract and the block of packed rows
-struct MlaBlock {
-    int L, s, n;
-    int r0, rows;   // rows == 0: nothing to do
-    __device__ __forceinline__ MlaBlock(const MlaParams& p, int b, int rank) {
-        const int cap = p.max_blocks * p.bs;   // (< 2^30: the host checks)
-        L = min(max(p.ctx[b], 0), cap);
-        int e;
-        if (p.cu != nullptr) {
-            s = min(max(p.cu[b], 0), p.T);
-            e = min(max(p.cu[b + 1], s), p.T);
-        } else {
-            s = b;   // (b < T: the host checks)
-            e = b + 1;
-        }
-        n = min(e - s, p.max_sq);
-        const int R = n * p.Hq;   // (T + 64) * Hq < 2^31: the host checks
-        const int own = (R + kMlaRows - 1) / kMlaRows;
-        r0 = 0;
-        rows = 0;
-        if (rank < own) {
-            r0 = (own - 1 - rank) * kMlaRows;   // rank 0 is the sequence's last block, as in the paged prefill
-            rows = min(kMlaRows, R - r0);
-        }
-    }
-};
-
-// One latent tile of 64 keys on its way from the block pool to LDS: thread t takes rows (t >> 3) and (t >> 3) + 32 of the tile,
-// chunks (t & 7) + 8 i of each.
-struct MlaTile {
-    u32x4_t d[2][kMlaN];
-    long long slot[2];
-    __device__ __forceinline__ void lookup(const MlaParams& p, const int* tab, int k0, int kend, int tid) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int kv = k0 + (tid >> 3) + 32 * j;
-            long long at = 0;
-            if (kv < kend) {
-                const int lb = p.bs_shift >= 0 ? kv >> p.bs_shift : kv / p.bs;
-                at = (long long)tab[lb] * p.bs + (kv - lb * p.bs);
-            }
-            slot[j] = at;
-        }
-    }
-    __device__ __forceinline__ void load(const MlaParams& p, int k0, int kend, int tid) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int kv = k0 + (tid >> 3) + 32 * j;
-            const char* row = p.kv + slot[j] * kMlaRB + (tid & 7) * 16;
-#pragma unroll
-            for (int i = 0; i < kMlaN; ++i) d[j][i] = kv < kend ? *reinterpret_cast<const u32x4_t*>(row + 128 * i) : u32x4_t{};
-        }
-    }
-    __device__ __forceinline__ void store(char* img, int tid) const {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < kMlaN; ++i)
-                *reinterpret_cast<u32x4_t*>(img + ((tid >> 3) + 32 * j) * kMlaPitch + (tid & 7) * 16 + 128 * i) = d[j][i];
-    }
-};
-
 template <class T>
 __global__ void __launch_bounds__(256, 1) fa_fwd_mla_paged_kernel(const MlaParams p) {
-    __shared__ __attribute__((aligned(16))) char Ls[kMlaKeys * kMlaPitch];   // the latent image
-    __shared__ __attribute__((aligned(16))) char Xs[4 * 8 * 1024];           // partial scores: [wave][register quad][lane] 16 bytes
-
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int rh = wave & 1, ch = wave >> 1;
-    // work item: (split, rank, sequence), the sequences side by side
-    const int bid = (int)blockIdx.x;
-    const int b = bid % p.B, rest = bid / p.B;
-    const int rank = rest % p.row_blocks, split = rest / p.row_blocks;
-
-    const MlaBlock blk(p, b, rank);
-    if (blk.rows == 0) return;
-    const int L = blk.L, n = blk.n, r0 = blk.r0, rows = blk.rows;
-
-    // this lane's row (a lane past the end works on the block's last row and stores nothing)
-    const int rl = rh * 32 + l31;
-    const bool live = rl < rows;
-    const int r = r0 + min(rl, rows - 1);
-    const int tok = r / p.Hq, head = r - tok * p.Hq;
-    const int pos = L - n + tok;
-
-    // this split's keys of this block: whole tiles of the sequence's own length, cut at the block's last visible key
-    const int tiles = (L + kMlaKeys - 1) / kMlaKeys;
-    const int per = (tiles + p.nsplit - 1) / p.nsplit;
-    const int kbeg = split * per * kMlaKeys;
-    const int kend = min(min((split + 1) * per * kMlaKeys, L), L - n + (r0 + rows - 1) / p.Hq + 1);
-    const int ntiles = kend > kbeg ? (kend - kbeg + kMlaKeys - 1) / kMlaKeys : 0;
-    const int* tab = p.table + (long long)b * p.max_blocks;
-
-    // Q operand chunks of this lane's row, the wave's half of the reduction
-    const char* qrow = p.q + (((long long)blk.s + tok) * p.q_stride + (long long)head * kMlaQK) * 2 + ch * (kMlaRB / 2);
-    u32x4_t qf[kMlaG];
-#pragma unroll
-    for (int g = 0; g < kMlaG; ++g) qf[g] = *reinterpret_cast<const u32x4_t*>(qrow + 32 * g + 16 * hi);
-
-    f32x16_t o[kMlaDT];
-#pragma unroll
-    for (int i = 0; i < kMlaDT; ++i) o[i] = f32x16_t{};
-    float m = -__builtin_inff(), l = 0.f;
-
-    MlaTile kt;
-    if (ntiles > 0) {
-        kt.lookup(p, tab, kbeg, kend, tid);
-        kt.load(p, kbeg, kend, tid);
-        kt.lookup(p, tab, kbeg + kMlaKeys, kend, tid);
-    }
-    char* xmine = Xs + wave * 8192 + lane * 16;
-    const char* xother = Xs + (wave ^ 2) * 8192 + lane * 16;
-    for (int t = 0; t < ntiles; ++t) {
-        const int k0 = kbeg + t * kMlaKeys;
-        __syncthreads();   // every wave is done with the previous tile and the previous partial scores
-        kt.store(Ls, tid);
-        __syncthreads();
-        if (t + 1 < ntiles) {
-            kt.load(p, k0 + kMlaKeys, kend, tid);
-            kt.lookup(p, tab, k0 + 2 * kMlaKeys, kend, tid);
-        }
-        // partial S^T[key][row] over the wave's 288 elements
-        f32x16_t sc[2] = {f32x16_t{}, f32x16_t{}};
-        const char* kimg = Ls + l31 * kMlaPitch + ch * (kMlaRB / 2) + 16 * hi;
-#pragma unroll
-        for (int g = 0; g < kMlaG; ++g)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) sc[kk] = mfma16<T>(lds_b128(kimg + 32 * kk * kMlaPitch + 32 * g), qf[g], sc[kk]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4)
-                *reinterpret_cast<f32x4_t*>(xmine + (4 * kk + q4) * 1024) = f32x4_t{sc[kk][4 * q4], sc[kk][4 * q4 + 1], sc[kk][4 * q4 + 2], sc[kk][4 * q4 + 3]};
-        __syncthreads();
-        // own + other, scale to log2 units, mask, running max over the lane pair (lanes l and l + 32 hold the same row)
-        float mx = -__builtin_inff();
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const f32x4_t y = *reinterpret_cast<const f32x4_t*>(xother + (4 * kk + q4) * 1024);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int rr = 4 * q4 + i;
-                    const int j = k0 + 32 * kk + crow(rr, hi);
-                    const float x = j <= pos && j < kend ? (sc[kk][rr] + y[i]) * p.c : -__builtin_inff();
-                    sc[kk][rr] = x;
-                    mx = fmaxf(mx, x);
-                }
-            }
-        mx = fmaxf(mx, xhalf(mx));
-        const float mn = fmaxf(m, mx);
-        const float mu = mn == -__builtin_inff() ? 0.f : mn;
-        const float alpha = fast_exp2(m - mu);   // m = -inf: 0
-        m = mn;
-        l *= alpha;
-#pragma unroll
-        for (int i = 0; i < kMlaDT; ++i) o[i] *= alpha;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const float ex = fast_exp2(sc[kk][rr] - mu);
-                sc[kk][rr] = ex;
-                l += ex;
-            }
-        // O^T[d][row] += V^T.P^T over the wave's 256 value columns, V = the image's first 512 columns
-#pragma unroll
-        for (int st = 0; st < 4; ++st) {
-            const u32x4_t pb = pack_step<T>(sc[st >> 1], st & 1);
-#pragma unroll
-            for (int dt = 0; dt < kMlaDT; ++dt) o[dt] = mfma16<T>(lds_tr_step(Ls, kMlaPitch, 16 * st, 256 * ch + 32 * dt, lane), pb, o[dt]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    l += xhalf(l);
-    if (!live) return;
-    const long long orow = ((long long)blk.s + tok) * p.Hq + head;
-    if (p.nsplit > 1) {
-        const long long prow = (long long)split * p.rows_total + orow;
-        float* po = p.part_o + prow * kMlaV + 256 * ch;
-#pragma unroll
-        for (int dt = 0; dt < kMlaDT; ++dt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-                *reinterpret_cast<f32x4_t*>(po + 32 * dt + 8 * g4 + 4 * hi) = f32x4_t{o[dt][4 * g4], o[dt][4 * g4 + 1], o[dt][4 * g4 + 2], o[dt][4 * g4 + 3]};
-        if (ch == 0 && hi == 0) *reinterpret_cast<f32x2_t*>(p.part_ml + prow * 2) = f32x2_t{m, l};
-        return;
-    }
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-    char* og = p.o + (orow * kMlaV + 256 * ch) * 2;
-#pragma unroll
-    for (int dt = 0; dt < kMlaDT; ++dt)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int d = 32 * dt + 8 * g4 + 4 * hi;
-            const float a0 = o[dt][4 * g4] * inv, a1 = o[dt][4 * g4 + 1] * inv, a2 = o[dt][4 * g4 + 2] * inv, a3 = o[dt][4 * g4 + 3] * inv;
-            *reinterpret_cast<u32x2_t*>(og + d * 2) = u32x2_t{T::pack2(a0, a1), T::pack2(a2, a3)};
-        }
-    if (p.lse != nullptr && ch == 0 && hi == 0) {
-        const float mu = m == -__builtin_inff() ? 0.f : m;
-        p.lse[orow] = l > 0.f ? (mu + fast_log2(l)) * kLn2 : -__builtin_inff();
-    }
+    __shared__ __attribute__((aligned(16))) char Ls[kMlaLdsImage];
+    __shared__ __attribute__((aligned(16))) char Xs[kMlaLdsScores];
+    mla_paged_body<T, Kv16>(p, Ls, Xs);
 }
 
 // The combine: workgroup (rank, sequence, sixteenth) takes four rows of the block the attention kernel's workgroups of that (rank,
@@ -329,9 +102,14 @@ __global__ void __launch_bounds__(256) fa_mla_combine_kernel(const MlaParams p) 
 }
 
 template <class T>
-int launch_type(const MlaParams& p, const MlaPlan& plan, hipStream_t stream) {
-    hipLaunchKernelGGL((fa_fwd_mla_paged_kernel<T>), dim3((unsigned)plan.grid), dim3(256), 0, stream, p);
-    int rc = (int)hipGetLastError();
+int launch_type(const MlaParams& p, const MlaPlan& plan, int dtype, hipStream_t stream) {
+    int rc;
+    if (p.kv_scale != nullptr) {
+        rc = launch_mla_fp8_kernel(p, plan.grid, dtype, stream);
+    } else {
+        hipLaunchKernelGGL((fa_fwd_mla_paged_kernel<T>), dim3((unsigned)plan.grid), dim3(256), 0, stream, p);
+        rc = (int)hipGetLastError();
+    }
     if (rc != 0 || plan.nsplit == 1) return rc;
     hipLaunchKernelGGL((fa_mla_combine_kernel<T>), dim3((unsigned)((long long)plan.row_blocks * p.B * kMlaCombineParts)), dim3(256), 0, stream, p);
     return (int)hipGetLastError();
@@ -371,6 +149,8 @@ int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_
     if (((long long)a.T + kMlaRows) * a.Hq > 0x7fffffffll) return -1;   // the kernels count packed rows in 32 bits
     if (a.cu_seqlens_q == nullptr && a.T < a.B) return -1;
     if (plan.nsplit > 1 && ws == nullptr) return -1;
+    const bool fp8 = a.cache_kind == kCacheFp8E4M3;
+    if (fp8 ? a.kv_scale == nullptr : a.cache_kind != kCache16) return -1;
     MlaParams p;
     p.q = static_cast<const char*>(a.q); p.kv = static_cast<const char*>(a.kv_cache);
     p.o = static_cast<char*>(a.out); p.lse = a.lse;
@@ -386,8 +166,9 @@ int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_
     p.max_sq = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T;
     p.row_blocks = plan.row_blocks; p.nsplit = plan.nsplit;
     p.c = a.scale * kLog2e;
-    if (a.dtype == kBF16) return launch_type<Bf16Traits>(p, plan, stream);
-    if (a.dtype == kF16) return launch_type<F16Traits>(p, plan, stream);
+    p.kv_scale = fp8 ? a.kv_scale : nullptr;
+    if (a.dtype == kBF16) return launch_type<Bf16Traits>(p, plan, a.dtype, stream);
+    if (a.dtype == kF16) return launch_type<F16Traits>(p, plan, a.dtype, stream);
     return -1;
 }
 

@@ -202,6 +202,33 @@ struct KvAppendArgs {
 };
 int launch_kv_append(const KvAppendArgs& a, hipStream_t stream);   // -1: unsupported arguments
 
+// Latent cache append (mla_kv_append_gfx950.hip), the write side of the paged MLA: row slot_mapping[t] of kv_cache
+// [num_blocks * block_size, 576] <- [c_kv[t] (512) | rope(k_pe[t] (64), table row positions[t])], 16-bit inputs with free token strides
+// (elements).  kCache16: the bits are copied; kCacheFp8E4M3: e4m3fn codes of x / kv_scale[0] (launch_kv_append's rules).  cos != null:
+// k_pe is rotated first, rope_layout 0 = pairs (p, p + 32), 1 = pairs (2p, 2p + 1); tables [table_len, 32] fp32.  A slot outside
+// [0, num_blocks * block_size), or with rotation a position outside [0, table_len), skips the whole token.  The caller guarantees
+// 16-byte aligned pointers, strides % 8 == 0 and table_pitch % 4 == 0.
+struct MlaKvAppendArgs {
+    const void* c_kv;
+    const void* k_pe;
+    void* kv_cache;
+    const long long* slot_mapping;   // [T] int64
+    int T;
+    long long num_blocks;
+    int block_size;
+    long long c_kv_token_stride, k_pe_token_stride;
+    int dtype;                          // of c_kv / k_pe: kF16 or kBF16
+    int cache_kind = kCache16;
+    const float* kv_scale = nullptr;    // kCacheFp8E4M3 only: [1] fp32, device
+    const float* cos = nullptr;         // [table_len, 32] fp32, table_pitch floats per row (0 = 32)
+    const float* sin = nullptr;
+    const long long* positions = nullptr;   // [T] int64
+    long long table_len = 0;
+    int table_pitch = 0;
+    int rope_layout = 0;
+};
+int launch_mla_kv_append(const MlaKvAppendArgs& a, hipStream_t stream);   // -1: unsupported arguments
+
 // Paged prefill (fa_fwd_paged_prefill_gfx950.hip): ragged per-sequence queries against the paged cache, one launch, no workspace.
 //   q [T, Hq, D] 16-bit, the new tokens of all sequences packed along the first axis (q_token_stride elements between tokens, the
 //   heads of a token contiguous), out [T, Hq, D] contiguous, lse [T, Hq] fp32 or null; caches, table, lengths and scales as PagedArgs;
@@ -306,7 +333,8 @@ long long cascade_merge_grid(const CascadeMergeArgs& a);
 int launch_cascade_merge(const CascadeMergeArgs& a, hipStream_t stream);
 
 // Paged multi-head latent attention (fa_fwd_mla_paged_gfx950.hip): ragged queries q [T, Hq, 576] against ONE latent cache
-//   kv_cache [num_blocks, block_size, 576] 16-bit of q's dtype -- row pos of a sequence is the key of all heads (576 elements) and,
+//   kv_cache [num_blocks, block_size, 576] 16-bit of q's dtype (kCache16), or e4m3fn codes with ONE fp32 device scale (kCacheFp8E4M3:
+//   key = kv_scale[0] * float(code), fa_fwd_mla_paged_fp8_gfx950.hip) -- row pos of a sequence is the key of all heads (576 elements) and,
 //   in its first 512 elements, the value; out [T, Hq, 512] contiguous, lse [T, Hq] fp32 or null.  Table, lengths, cu_seqlens_q,
 //   the clamps and the rows that are written as PagedPrefillArgs; cu_seqlens_q = null: sequence b owns row b, one token each
 //   (T >= B).  The caller guarantees 16-byte aligned q / out / kv_cache and q_token_stride % 8 == 0.
@@ -325,6 +353,8 @@ struct MlaArgs {
     float scale;
     int dtype;
     int device = -1;                    // as FwdArgs::device
+    int cache_kind = kCache16;          // element type of kv_cache (dtype is the type of q / out)
+    const float* kv_scale = nullptr;    // kCacheFp8E4M3 only: [1] fp32, device
 };
 // The launch plan (mla_plan, beside the kernel: the one statement of the rule for launch, workspace query and debug hook).
 constexpr int kMlaRows = 64;       // packed rows (token-major, head-minor) per workgroup

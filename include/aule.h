@@ -413,8 +413,8 @@ uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_de
 /* 16-byte aligned, allocates on the stream.  No host synchronisation, and no allocation when a workspace is passed: captures into a  */
 /* hipGraph, and a replay sees the CURRENT cu_seqlens_q, context_lens and block_tables.  With hostile cu_seqlens_q that make two      */
 /* sequences own the same row, that row's value is unspecified (and nothing outside out / lse is written).                            */
-/* Not built: a sliding window; an FP8 latent cache; a backward; the non-absorbed prefill form (192 / 128); a cache-append kernel    */
-/* for the latent cache (one index_copy_ of the new rows into the cache viewed as [num_blocks * block_size, 576] does it).            */
+/* An FP8 latent cache is aule_attention_mla_paged_fp8_ex below; the write side of both caches is aule_mla_kv_append_ex.              */
+/* Not built: a sliding window; a backward; the non-absorbed prefill form (192 / 128).                                                */
 /* The descriptor is checked before the device is needed: -3 for a refused descriptor and 0 for one with nothing to do               */
 /* (total_tokens = 0, batch = 0 or heads_q = 0) are answered without aule_init().                                                     */
 typedef struct aule_mla_paged_desc {
@@ -446,6 +446,48 @@ typedef struct aule_mla_paged_desc {
 int32_t aule_attention_mla_paged_ex(const aule_mla_paged_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
 uint64_t aule_attention_mla_paged_workspace_size(const aule_mla_paged_desc* desc);
+
+/* Paged MLA over an FP8 latent cache (additive).  aule_mla_paged_desc field for field -- the same offsets, the same rules, the same  */
+/* clamps, rows, launches, plan and workspace -- with two differences:                                                                */
+/*   kv_cache is [num_blocks, block_size, 576] OCP e4m3fn codes, one byte per element (contiguous, 16-byte aligned); dtype stays the  */
+/*   type of q / out;                                                                                                                 */
+/*   kv_scale is ONE fp32 value for the whole cache, a DEVICE array of 1 element read by the kernel (no host synchronisation; required,*/
+/*   4-byte aligned):  key = kv_scale * float(code row), value = its first 512 elements.                                              */
+/* The codes are converted exactly to q's 16-bit type on their way into the kernel's LDS image and everything after that is the       */
+/* 16-bit kernel's arithmetic; kv_scale multiplies the score scale and the fp32 accumulators, never an element.  So lse includes      */
+/* kv_scale (it is the log of the softmax denominator of the dequantised keys), and with kv_scale = 1 the call equals                 */
+/* aule_attention_mla_paged_ex on the codes converted to q's dtype bit for bit.  aule_hip_debug_mla_plan answers for both kinds (the  */
+/* plan depends on the shape alone).  The codes are what aule_mla_kv_append_ex writes with AULE_KV_CACHE_FP8_E4M3.                    */
+typedef struct aule_mla_paged_fp8_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_paged_fp8_desc) = 144 */
+    int32_t dtype;             /* offset 4; type of q / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    uint32_t batch;            /* offset 8; sequences */
+    uint32_t heads_q;          /* offset 12 */
+    uint32_t qk_dim;           /* offset 16; 576 */
+    uint32_t v_dim;            /* offset 20; 512 */
+    uint32_t block_size;       /* offset 24; any value > 0 */
+    uint32_t max_blocks;       /* offset 28; columns of block_tables */
+    uint32_t total_tokens;     /* offset 32; rows of q / out; 0: returns 0 without a launch */
+    uint32_t max_seqlen_q;     /* offset 36; >= 1: sizes the grid, and caps every n_b */
+    float scale;               /* offset 40; 0 -> 1/sqrt(576) */
+    int32_t device;            /* offset 44; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 48; elements, >= heads_q * 576, a multiple of 8 */
+    void* stream;              /* offset 56; hipStream_t */
+    const void* q;             /* offset 64; [total_tokens, heads_q, 576], 16-bit */
+    const void* kv_cache;      /* offset 72; [num_blocks, block_size, 576], e4m3fn codes */
+    const int32_t* block_tables;   /* offset 80; [batch, max_blocks] */
+    const int32_t* context_lens;   /* offset 88; [batch]: keys per sequence, the new ones included */
+    const int32_t* cu_seqlens_q;   /* offset 96; [batch + 1], device; NULL: plain decode */
+    void* out;                 /* offset 104; [total_tokens, heads_q, 512], 16-bit, contiguous */
+    float* lse;                /* offset 112; optional (NULL to skip): [total_tokens, heads_q] fp32 */
+    void* workspace;           /* offset 120; optional, size from aule_attention_mla_paged_fp8_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 128 */
+    const float* kv_scale;     /* offset 136; [1] fp32, device */
+} aule_mla_paged_fp8_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure.  Checked before the device is needed, as above. */
+int32_t aule_attention_mla_paged_fp8_ex(const aule_mla_paged_fp8_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  The number aule_attention_mla_paged_workspace_size gives for the shape. */
+uint64_t aule_attention_mla_paged_fp8_workspace_size(const aule_mla_paged_fp8_desc* desc);
 
 /* VARIABLE-LENGTH packed batches (additive): sequences of different lengths packed along one token axis, forward and backward --   */
 /* SFT with sequence packing, encoder batches without padding, prefill without a paged cache (flash_attn_varlen_func's case).        */
@@ -647,6 +689,51 @@ typedef struct aule_kv_append_desc {
 } aule_kv_append_desc;
 /* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
 int32_t aule_kv_cache_append_ex(const aule_kv_append_desc* desc);
+
+/* Latent cache append (additive; the write side of aule_attention_mla_paged_ex / _fp8_ex).  One launch writes the latent rows of    */
+/* total_tokens new tokens into the [num_blocks, block_size, 576] cache:                                                              */
+/*     row slot_mapping[t] of kv_cache viewed as [num_blocks * block_size, 576]  <-  [ c_kv[t] | rope(k_pe[t]) ]                      */
+/* c_kv is [total_tokens, 512] and k_pe [total_tokens, 64], fp16 / bf16, last dimension contiguous, each with a free token stride in  */
+/* elements (a multiple of 8, >= the row): slices of the fused down-projection's output are read in place.                            */
+/* A slot that is negative (padding) or >= num_blocks * block_size skips the token ENTIRELY: nothing of its row is written, the c_kv  */
+/* part included.  Two tokens of one call with the same slot: which of them the cache holds afterwards is unspecified.                */
+/* cache_dtype AULE_KV_CACHE_SAME: the cache holds the input's dtype, the bits are copied; kv_scale must be NULL.                     */
+/* AULE_KV_CACHE_FP8_E4M3: the cache holds OCP e4m3fn codes, code = cast_e4m3fn(clamp(x / kv_scale[0], -448, 448)) by the rules of    */
+/* aule_kv_cache_append_ex (correctly rounded division, round to nearest even, saturating, NaN stays NaN, -0 stays -0), kv_scale a    */
+/* DEVICE array of 1 fp32 read by the kernel.                                                                                         */
+/* Optional rotation of k_pe (all of cos, sin, positions given with table_len > 0; all NULL with table_len = table_pitch = 0: none):  */
+/* tables [table_len, 32] fp32 with table_pitch floats per row (0 = 32), token t uses row positions[t]; rope_layout AULE_ROPE_HALF    */
+/* pairs (p, p + 32), AULE_ROPE_INTERLEAVED pairs (2p, 2p + 1); aule_rope_ex's arithmetic, rounded once to the input's dtype and only */
+/* then quantised: the result equals aule_rope_ex() followed by the un-rotated append bit for bit.  With rotation, a position outside */
+/* [0, table_len) skips the token entirely as a bad slot does; a token whose slot is skipped needs no valid position.                 */
+/* Alignment: c_kv, k_pe, kv_cache, cos and sin 16-byte aligned; kv_scale 4-byte; table_pitch % 4 == 0.                                */
+/* Asynchronous on `stream`; device pointers; captures into a hipGraph (no allocation, no synchronisation).  The descriptor is       */
+/* checked before the device is needed: -3 for a refused one and 0 for total_tokens = 0 are answered without aule_init().             */
+typedef struct aule_mla_kv_append_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_kv_append_desc) = 128 */
+    int32_t dtype;             /* offset 4; of c_kv / k_pe: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    int32_t cache_dtype;       /* offset 8; AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3 */
+    int32_t rope_layout;       /* offset 12; AULE_ROPE_HALF or AULE_ROPE_INTERLEAVED (read with rotation only, but always checked) */
+    uint32_t total_tokens;     /* offset 16; 0: returns 0 without a launch */
+    uint32_t num_blocks;       /* offset 20 */
+    uint32_t block_size;       /* offset 24; any value > 0 */
+    uint32_t table_len;        /* offset 28; rows of cos / sin (0 without rotation) */
+    uint32_t table_pitch;      /* offset 32; floats per table row; 0 = 32 */
+    int32_t device;            /* offset 36; HIP device ordinal, -1 = current */
+    int64_t c_kv_token_stride; /* offset 40; elements, >= 512, a multiple of 8 */
+    int64_t k_pe_token_stride; /* offset 48; elements, >= 64, a multiple of 8 */
+    void* stream;              /* offset 56; hipStream_t */
+    const void* c_kv;          /* offset 64; [total_tokens, 512] */
+    const void* k_pe;          /* offset 72; [total_tokens, 64] */
+    void* kv_cache;            /* offset 80; [num_blocks, block_size, 576], contiguous */
+    const int64_t* slot_mapping;   /* offset 88; [total_tokens] */
+    const float* kv_scale;     /* offset 96; [1] fp32, device (AULE_KV_CACHE_FP8_E4M3), else NULL */
+    const float* cos;          /* offset 104; [table_len, 32] fp32, or NULL */
+    const float* sin;          /* offset 112 */
+    const int64_t* positions;  /* offset 120; [total_tokens], or NULL */
+} aule_mla_kv_append_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_mla_kv_append_ex(const aule_mla_kv_append_desc* desc);
 
 /* Attention with the query rotation fused into the kernel (additive; inference path).  Replaces the Q half of       */
 /* python/aule/triton_flash.py:112-131 (the reference rotates Q in its forward prologue); K must arrive rotated --   */

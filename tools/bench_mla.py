@@ -13,6 +13,16 @@ rounds and the spread (min .. max) of the three, the two ratios, the latent byte
 its arithmetic (2 (576 + 512) flops per visible (row, key) pair) over its time.  Before a leg is timed the two routes are compared
 (the forward bound of tests/util.py).
 
+--fp8: the same 36 shapes with the 16-bit call NEXT TO aule.flash_attention_mla_paged_fp8 on the cache quantised with
+aule.quantize_mla_cache_fp8 (the scale a device tensor), the two alternated round by round; the 16-bit kernel is the baseline of the
+same build.  Before a leg is timed the FP8 call with kv_scale = 1 is compared bit for bit with the 16-bit call on the converted codes.
+Per leg: both medians and spreads, 16-bit / FP8 (below 1: FP8 is slower) and the code bytes of the batch (B L 576) over the FP8 time.
+
+--append: aule.mla_kv_append against the torch ops it replaces -- cos[pos] / sin[pos] and rope_raw for a rotated k_pe, cat, divide /
+clamp / cast for an FP8 cache, index_copy_ -- T = 1 / 64 / 4096 / 65536 tokens, a 16-bit and an FP8 cache, with and without the
+(interleaved) rotation, bf16, block 64, random slots and positions.  The two are compared bit for bit before they are timed.  Per
+leg: medians and spreads, composed / fused, and from T = 4096 on the algorithmic bytes (T 576 (2 + cache element size)) over the time.
+
 Every leg runs under its own alarm (--leg-timeout seconds, default 120): a leg that hangs ends the process.  Legs run in this one
 process and the first failure stops the run.  A timed window repeats its call until it holds about 40 ms of device time.
 --out FILE also writes the table there.  --rounds N (default 5)."""
@@ -84,30 +94,104 @@ def leg(Hq, B, L, n, rounds, lines):
     flops, nbytes = 2.0 * (QK + VD) * pairs, B * L * QK * 2
     calls = {"mla": paged, "gather+sdpa": lambda: sdpa(gather()), "sdpa": lambda: sdpa(held)}
 
-    def window(f, iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            f()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / iters * 1e3
-
-    # warm, then size every timed window to about WINDOW_MS of device time (a shorter one measures the clock and the scheduler)
-    iters = {}
-    for key, f in calls.items():
-        window(f, 2)
-        iters[key] = min(400, max(3, int(WINDOW_MS * 1e3 / window(f, 2)) + 1))
-    t = {k: [] for k in calls}
-    for _ in range(rounds):
-        for key, f in calls.items():
-            t[key].append(window(f, iters[key]))
-    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
-    span = {k: f"{med[k]:9.1f} ({min(v):9.1f} .. {max(v):9.1f})" for k, v in t.items()}
+    res = _alternated(calls, rounds)
+    med, span = {k: v[0] for k, v in res.items()}, {k: v[1] for k, v in res.items()}
     rb, ns = plan(B, Hq, n, L)
     line = (f"  heads {Hq:3d} batch {B:2d} context {L:5d} tokens {n}: plan {rb} x {ns:2d} x {B:2d}   paged MLA {span['mla']} us   gather + SDPA {span['gather+sdpa']} us"
             f"   SDPA, latent gathered beforehand {span['sdpa']} us   with gather / MLA {med['gather+sdpa'] / med['mla']:6.2f}x   without gather / MLA "
             f"{med['sdpa'] / med['mla']:6.2f}x   {nbytes / (med['mla'] * 1e-6) / 1e12:5.2f} TB/s of latent   {flops / (med['mla'] * 1e-6) / 1e12:6.1f} TFLOP/s")
+    print(line, flush=True)
+    lines.append(line)
+
+
+def _window(f, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        f()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3
+
+
+def _alternated(calls, rounds):
+    """{name: (median, "median (min .. max)")} of `calls`, warm, alternated round by round, every window about WINDOW_MS long"""
+    iters = {}
+    for key, f in calls.items():
+        _window(f, 2)
+        iters[key] = min(400, max(3, int(WINDOW_MS * 1e3 / _window(f, 2)) + 1))
+    t = {k: [] for k in calls}
+    for _ in range(rounds):
+        for key, f in calls.items():
+            t[key].append(_window(f, iters[key]))
+    return {k: (sorted(v)[len(v) // 2], f"{sorted(v)[len(v) // 2]:9.1f} ({min(v):9.1f} .. {max(v):9.1f})") for k, v in t.items()}
+
+
+def leg_fp8(Hq, B, L, n, rounds, lines):
+    g = torch.Generator(device="cuda").manual_seed(Hq + B + L + n)
+    dt = torch.bfloat16
+    nblk = L // BS
+    q = torch.randn(B * n, Hq, QK, device="cuda", dtype=dt, generator=g)
+    kv = torch.randn(B * nblk, BS, QK, device="cuda", dtype=dt, generator=g)
+    bt = torch.randperm(B * nblk, device="cuda", generator=g).to(torch.int32).view(B, nblk)
+    cl = torch.full((B,), L, device="cuda", dtype=torch.int32)
+    cu = torch.arange(0, B * n + 1, n, device="cuda", dtype=torch.int32)
+    codes, ks = aule.quantize_mla_cache_fp8(kv)
+    exact = codes.to(dt)
+    a = aule.flash_attention_mla_paged_fp8(q, codes, bt, cl, cu, max_seqlen_q=n, scale=float(ks) * QK ** -0.5, return_lse=True)
+    b_ = aule.flash_attention_mla_paged(q, exact, bt, cl, cu, max_seqlen_q=n, scale=float(ks) * QK ** -0.5, return_lse=True)
+    torch.cuda.synchronize()
+    if not (torch.equal(a[0].view(torch.int16), b_[0].view(torch.int16)) and torch.equal(a[1].view(torch.int32), b_[1].view(torch.int32))):
+        raise SystemExit(f"heads {Hq} batch {B} context {L} tokens {n}: the FP8 call and the 16-bit call on the converted codes differ")
+    del exact, a, b_
+    r = _alternated({"16": lambda: aule.flash_attention_mla_paged(q, kv, bt, cl, cu, max_seqlen_q=n),
+                     "fp8": lambda: aule.flash_attention_mla_paged_fp8(q, codes, bt, cl, cu, max_seqlen_q=n, kv_scale=ks)}, rounds)
+    rb, ns = plan(B, Hq, n, L)
+    line = (f"  heads {Hq:3d} batch {B:2d} context {L:5d} tokens {n}: plan {rb} x {ns:2d} x {B:2d}   16-bit cache {r['16'][1]} us   FP8 cache {r['fp8'][1]} us"
+            f"   16-bit / FP8 {r['16'][0] / r['fp8'][0]:5.2f}x   {B * L * QK / (r['fp8'][0] * 1e-6) / 1e12:5.2f} TB/s of codes")
+    print(line, flush=True)
+    lines.append(line)
+
+
+def leg_append(T, fp8, rope, rounds, lines):
+    from aule._torch import rope_raw
+    g = torch.Generator(device="cuda").manual_seed(T + 2 * fp8 + rope)
+    dt = torch.bfloat16
+    nslots = (max(T, 1024) + BS - 1) // BS * BS * 2
+    c = torch.randn(T, VD, device="cuda", dtype=dt, generator=g)
+    r = torch.randn(T, QK - VD, device="cuda", dtype=dt, generator=g)
+    slots = torch.randperm(nslots, device="cuda", generator=g)[:T]
+    table_len = 8192
+    ang = torch.rand(table_len, 32, device="cuda", generator=g) * 6.2831853
+    cos, sin = torch.cos(ang), torch.sin(ang)
+    pos = torch.randint(0, table_len, (T,), device="cuda", generator=g)
+    ks = torch.tensor([6.0 / 448], device="cuda")
+    cache = [torch.zeros(nslots // BS, BS, QK, device="cuda", dtype=torch.float8_e4m3fn if fp8 else dt) for _ in range(2)]
+    kw = dict(kv_scale=ks) if fp8 else {}
+    if rope:
+        kw.update(cos=cos, sin=sin, positions=pos, rope_layout="interleaved")
+
+    def fused():
+        aule.mla_kv_append(c, r, cache[0], slots, **kw)
+
+    def composed():
+        rr = rope_raw(r.view(1, 1, T, QK - VD), cos[pos], sin[pos], layout="interleaved").view(T, QK - VD) if rope else r
+        rows = torch.cat([c, rr], 1)
+        if fp8:
+            cache[1].view(torch.uint8).view(-1, QK).index_copy_(0, slots, (rows.float() / ks).clamp_(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8))
+        else:
+            cache[1].view(-1, QK).index_copy_(0, slots, rows)
+
+    fused(); composed()
+    torch.cuda.synchronize()
+    if not torch.equal(cache[0].view(torch.uint8), cache[1].view(torch.uint8)):
+        raise SystemExit(f"T {T} fp8 {fp8} rope {rope}: the fused append and the composed one differ")
+    t = _alternated({"fused": fused, "composed": composed}, rounds)
+    line = (f"  T {T:6d} {'fp8' if fp8 else '16b'}  {'rope ' if rope else 'plain'}: fused {t['fused'][1]} us   composed {t['composed'][1]} us"
+            f"   composed / fused {t['composed'][0] / t['fused'][0]:6.2f}x")
+    if T >= 4096:
+        nbytes = T * QK * (2 + (1 if fp8 else 2))
+        line += f"   fused {nbytes / 1e6:6.1f} MB -> {nbytes / (t['fused'][0] * 1e-6) / 1e12:5.2f} TB/s"
     print(line, flush=True)
     lines.append(line)
 
@@ -117,7 +201,19 @@ def main():
         raise SystemExit("bench_mla needs a GPU: a timing taken anywhere else says nothing")
     rounds, budget = _arg("--rounds", 5), _arg("--leg-timeout", 120)
     signal.signal(signal.SIGALRM, signal.SIG_DFL)      # the default action ends the process, also from inside a blocked device call
-    head = (f"# tools/bench_mla.py   (one MI355X; latent 576 / 512, block_size {BS}, bf16, shuffled block table; plan = row blocks x nsplit x batch "
+    if "--append" in sys.argv:
+        head = (f"# tools/bench_mla.py --append   (one MI355X; latent rows 512 + 64, block_size {BS}, bf16 c_kv / k_pe, random slots and positions, interleaved "
+                f"rotation; {rounds} alternated rounds of ~{WINDOW_MS} ms windows, median (min .. max) us per call, host launch cost included)")
+        print(head, flush=True)
+        lines = [head]
+        for T in (1, 64, 4096, 65536):
+            for fp8 in (False, True):
+                for rope in (False, True):
+                    signal.alarm(budget)
+                    leg_append(T, fp8, rope, rounds, lines)
+                    signal.alarm(0)
+        return _write(lines)
+    head = (f"# tools/bench_mla.py{' --fp8' if '--fp8' in sys.argv else ''}   (one MI355X; latent 576 / 512, block_size {BS}, bf16, shuffled block table; plan = row blocks x nsplit x batch "
             f"workgroups; {rounds} alternated rounds of ~{WINDOW_MS} ms windows, median (min .. max) us per call, host launch cost included)")
     print(head, flush=True)
     lines = [head]
@@ -126,8 +222,12 @@ def main():
             for B in BATCH:
                 for L in CONTEXT:
                     signal.alarm(budget)
-                    leg(Hq, B, L, n, rounds, lines)
+                    (leg_fp8 if "--fp8" in sys.argv else leg)(Hq, B, L, n, rounds, lines)
                     signal.alarm(0)
+    _write(lines)
+
+
+def _write(lines):
     if "--out" in sys.argv:
         path = _arg("--out", "", str)
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
