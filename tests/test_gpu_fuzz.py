@@ -3,7 +3,8 @@ head_dim, causal mode (none / top-left / bottom-right), window and scale, forwar
 random paged-decode problems (shuffled block tables, lengths 0 and 1, power-of-two and other block sizes, window); random
 RoPE passes (both layouts, inverse, offsets, vector and scalar head dims, in place).  Deterministic: the seeds are fixed,
 so this is a regression test over ~150 configurations nobody enumerated by hand, not a flaky one.  The tool itself takes
-any seed and size (700 + 300 + 300 configurations were clean when it was written)."""
+any seed and size (700 + 300 + 300 configurations were clean when it was written).  The serving and packing
+entry points (paged prefill / query, cascade, MLA, varlen) are drawn by tools/fuzz_serving.py: tests/test_gpu_fuzz_serving.py."""
 import importlib.util
 import os
 

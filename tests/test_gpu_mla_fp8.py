@@ -28,16 +28,20 @@ NAN_CODE = 0x7F
 class Fp8Case(Case):
     """A Case whose latent cache is quantised: `codes` (float8_e4m3fn, CPU) and `kv_scale` ([1] fp32, CPU) are what the device sees;
     `kv` becomes the dequantised cache in float64 (what the oracle sees) and `vmax` its largest |V|.  offset > 0: latents
-    |N(0, 1)| + offset instead of N(0, 1) (every value, so every output that sees a key, is well away from zero)."""
+    |N(0, 1)| + offset instead of N(0, 1) (every value, so every output that sees a key, is well away from zero).  kv_scale given: the
+    codes are the latents themselves rounded to e4m3fn and the cache is kv_scale times them (logits of unit scale at any kv_scale near 1)."""
 
-    def __init__(self, *args, offset=0.0, **kw):
+    def __init__(self, *args, offset=0.0, kv_scale=None, **kw):
         import torch
         import aule
         super().__init__(*args, **kw)
         lat = torch.from_numpy(self.kv)
         if offset:
             lat = lat.abs() + offset
-        self.codes, self.kv_scale = aule.quantize_mla_cache_fp8(lat.to(torch_dtype(self.dtype)))
+        if kv_scale is None:
+            self.codes, self.kv_scale = aule.quantize_mla_cache_fp8(lat.to(torch_dtype(self.dtype)))
+        else:
+            self.codes, self.kv_scale = lat.to(torch.float8_e4m3fn), torch.tensor([kv_scale], dtype=torch.float32)
         self.kv = self.codes.double().numpy() * float(self.kv_scale)
         self.vmax = float(np.abs(self.kv[..., :VD]).max())
 

@@ -31,12 +31,13 @@ BIG, SMALL = 200, 64       # keys the two prefix tables are sized for (BIG: plus
 
 class Cascade:
     """A Ragged batch plus a prefix table into the same block pool (the prefix may share blocks with a sequence: they are only
-    read).  `keys`: what the table is sized for; `spare` more columns follow."""
+    read).  `keys`: what the table is sized for; `spare` more columns follow.  `blocks`: the table's length itself."""
 
-    def __init__(self, p, seed, keys=BIG, spare=2):
+    def __init__(self, p, seed, keys=BIG, spare=2, blocks=None):
         self.p = p
         rng = np.random.RandomState(seed)
         nb = (keys + p.bs - 1) // p.bs + spare if spare else max(keys // p.bs, 1)   # spare = 0: at most `keys` keys where a block allows
+        nb = nb if blocks is None else blocks
         assert nb <= p.kdev.shape[0]
         self.pbt = rng.permutation(p.kdev.shape[0])[:nb].astype(np.int32)
         self.cap = nb * p.bs
@@ -53,71 +54,95 @@ class Cascade:
             t[first:] = [INT32_MIN if i % 2 == 0 else 2 ** 31 - 1 - i for i in range(len(t) - first)]
         return t
 
-    def reference(self, oracle_mod, P, **kw):
-        """(out [T, Hq, D] float32, lse [T, Hq] float64) on the owned rows; once per (P, lengths)"""
+    def _slots(self, P, b, L):
+        """the cache rows of the P prefix keys, then of sequence b's L own keys (a block-size-1 view of the pool)"""
+        p, bs = self.p, self.p.bs
+        j, jo = np.arange(P), np.arange(L)
+        return np.concatenate([self.pbt[j // bs].astype(np.int64) * bs + j % bs, p.bt[b][jo // bs].astype(np.int64) * bs + jo % bs])
+
+    def lse_rows(self, P, b, s, n, L, scale=None, ft=np.float64):
+        """[n, Hq]: the log-sum-exp of the token rows s .. s + n - 1 over prefix plus own keys, -inf where a row sees none; formed in
+        `ft` (float64: the judge; float32: what plain fp32 arithmetic leaves of the same rows)"""
+        p = self.p
+        g = p.Hq // p.Hkv
+        scale = 1.0 / math.sqrt(p.D) if scale is None else scale
+        pos = L - n + np.arange(n)
+        ctx = np.where(pos >= 0, P + pos + 1, 0)
+        rows = np.full((n, p.Hq), -np.inf)
+        if P + L > 0:
+            k = p.K.reshape(-1, 1, p.Hkv, p.D)[self._slots(P, b, L), 0].astype(ft)
+            sc = np.einsum("nhgd,lhd->nhgl", p.q[s:s + n].astype(ft).reshape(n, p.Hkv, g, p.D), k) * ft(scale)
+            see = np.arange(P + L)[None, :] < ctx[:, None]
+            sc = np.where(see[:, None, None, :], sc, ft(-np.inf))
+            m = sc.max(axis=-1)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                v = m + np.log(np.exp(sc - np.where(np.isfinite(m), m, ft(0.0))[..., None]).sum(axis=-1))
+            rows = np.where(np.isfinite(m), v, -np.inf).reshape(n, p.Hq).astype(np.float64)
+        return rows
+
+    def reference(self, oracle_mod, P, scale=None, **kw):
+        """(out [T, Hq, D] float32, lse [T, Hq] float64) on the owned rows; once per (P, scale, lengths)"""
         p, P = self.p, self.clamp(P)
-        key = (P, tuple((k, tuple(np.asarray(v).tolist()) if k != "max_sq" else v) for k, v in sorted(kw.items())))
+        key = (P, scale, tuple((k, tuple(np.asarray(v).tolist()) if k != "max_sq" else v) for k, v in sorted(kw.items())))
         if key in self._ref:
             return self._ref[key]
-        bs, g, scale = p.bs, p.Hq // p.Hkv, 1.0 / math.sqrt(p.D)
         K1, V1 = (x.reshape(-1, 1, p.Hkv, p.D) for x in (p.K, p.V))
-        j = np.arange(P)
-        pslots = self.pbt[j // bs].astype(np.int64) * bs + j % bs
         out = np.zeros((p.T, p.Hq, p.D), dtype=np.float32)
         lse = np.full((p.T, p.Hq), np.nan)
         for b, s, n, L in p.sequences(**kw):
             if n == 0:
                 continue
-            j = np.arange(L)
-            slots = np.concatenate([pslots, p.bt[b][j // bs].astype(np.int64) * bs + j % bs])
+            slots = self._slots(P, b, L)
             pos = L - n + np.arange(n)
             ctx = np.where(pos >= 0, P + pos + 1, 0)
             if len(slots) == 0:
                 slots = np.zeros(1, dtype=np.int64)
-            out[s:s + n] = oracle_mod.paged_decode_f64(p.q[s:s + n], K1, V1, np.repeat(slots[None], n, axis=0), ctx, None, -1)
-            rows = np.full((n, p.Hq), -np.inf)
-            if P + L > 0:
-                k = K1[slots[:P + L], 0]
-                sc = np.einsum("nhgd,lhd->nhgl", p.q[s:s + n].astype(np.float64).reshape(n, p.Hkv, g, p.D), k) * scale
-                see = np.arange(P + L)[None, :] < ctx[:, None]
-                sc = np.where(see[:, None, None, :], sc, -np.inf)
-                m = sc.max(axis=-1)
-                with np.errstate(invalid="ignore", divide="ignore"):
-                    v = m + np.log(np.exp(sc - np.where(np.isfinite(m), m, 0.0)[..., None]).sum(axis=-1))
-                rows = np.where(np.isfinite(m), v, -np.inf).reshape(n, p.Hq)
-            lse[s:s + n] = rows
+            out[s:s + n] = oracle_mod.paged_decode_f64(p.q[s:s + n], K1, V1, np.repeat(slots[None], n, axis=0), ctx, scale, -1)
+            lse[s:s + n] = self.lse_rows(P, b, s, n, L, scale)
         self._ref[key] = (out, lse)
         return out, lse
 
-    def device(self, torch, P, cu=None, cl=None, hostile=True):
-        args, scales = self.p.device(torch, cu, cl)
+    def lse_f32_gap(self, P, scale=None, **kw):
+        """max |fp32 log-sum-exp - fp64 log-sum-exp| over the owned rows that see a key (Ragged.lse_f32_gap, with the prefix)"""
+        gap, P = 0.0, self.clamp(P)
+        for b, s, n, L in self.p.sequences(**kw):
+            if n and P + L:
+                a, r = self.lse_rows(P, b, s, n, L, scale, np.float32), self.lse_rows(P, b, s, n, L, scale)
+                fin = np.isfinite(r)
+                if fin.any():
+                    gap = max(gap, float(np.abs(a[fin] - r[fin]).max()))
+        return gap
+
+    def device(self, torch, P, cu=None, cl=None, hostile=True, q_pad=0):
+        args, scales = self.p.device(torch, cu, cl, q_pad)
         plen = P if torch.is_tensor(P) else torch.tensor([P], dtype=torch.int32, device="cuda")
         return args, scales, torch.from_numpy(self.table(int(plen[0]) if torch.is_tensor(P) else P, hostile)).cuda(), plen
 
-    def run(self, torch, P, max_sq=None, cu=None, cl=None):
+    def run(self, torch, P, max_sq=None, cu=None, cl=None, scale=None, hostile=True, q_pad=0):
         import aule
-        (q, kc, vc, bt, cl, cu), scales, pbt, plen = self.device(torch, P, cu, cl)
+        (q, kc, vc, bt, cl, cu), scales, pbt, plen = self.device(torch, P, cu, cl, hostile, q_pad)
         return aule.flash_attention_paged_cascade(q, kc, vc, pbt, plen, bt, cl, cu, max_seqlen_q=self.p.max_sq if max_sq is None else max_sq,
-                                                  return_lse=True, **scales)
+                                                  scale=scale, return_lse=True, **scales)
 
 
-def _judge(c, out, lse, oracle_mod, P, what, **kw):
-    """the owned rows of (out, lse) against the oracle; prints the measured maxima before it asserts"""
+def _judge(c, out, lse, oracle_mod, P, what, scale=None, lse_atol=LSE_ATOL, **kw):
+    """the owned rows of (out, lse) against the oracle; prints the measured maxima before it asserts and returns them"""
     p = c.p
     own = p.owned(**kw)
-    ref, lref = c.reference(oracle_mod, P, **kw)
+    ref, lref = c.reference(oracle_mod, P, scale, **kw)
     out, lse = out.float().cpu().numpy()[own], lse.cpu().numpy().astype(np.float64)[own]
     ref, lref = ref[own], lref[own]
     atol, rtol = fwd_tol(p.dtype, p.vmax, sides=2)
     none = np.isneginf(lref)
     lerr = float(np.abs(lse[~none] - lref[~none]).max()) if (~none).any() else 0.0
     print("%s: %d rows, max |out err| %.3g (atol %.3g), max |lse err| %.3g (bound %.3g), rows without a key %d"
-          % (what, int(own.sum()), np.abs(out - ref).max() if own.any() else 0.0, atol, lerr, LSE_ATOL, int(none.sum())))
+          % (what, int(own.sum()), np.abs(out - ref).max() if own.any() else 0.0, atol, lerr, lse_atol, int(none.sum())))
     assert not np.isnan(lse).any() and not np.isnan(out).any(), what
     assert_close(out, ref, atol, rtol, what)
     assert np.array_equal(np.isneginf(lse), none), "%s: lse must be -inf exactly where a row sees no key" % what
     assert bool((out[none] == 0).all()), "%s: a row that sees no key must be zeros" % what
-    assert lerr <= LSE_ATOL, (what, lerr)
+    assert lerr <= lse_atol, (what, lerr)
+    return float(np.abs(out - ref).max()) if own.any() else 0.0, lerr
 
 
 def _desc(torch, c, args, scales, pbt, plen, out, lse, max_sq, ws=None):

@@ -25,14 +25,15 @@ INT32_MIN = -(2 ** 31)
 
 class Ragged:
     """Seeded inputs of one ragged batch: sequence b has ns[b] new tokens and Ls[b] keys.  cu_seqlens_q starts at `lead`
-    and q has `tail` rows behind the last sequence.  The table is sized for table_lens (default: Ls)."""
+    and q has `tail` rows behind the last sequence.  The table is sized for table_lens (default: Ls); the block pool holds at
+    least `pool` blocks (default: what the tables need, plus 3)."""
 
-    def __init__(self, seed, dtype, kind, Hq, Hkv, D, bs, ns, Ls, lead=0, tail=0, table_lens=None, extra_cols=2):
+    def __init__(self, seed, dtype, kind, Hq, Hkv, D, bs, ns, Ls, lead=0, tail=0, table_lens=None, extra_cols=2, pool=None):
         rng = np.random.RandomState(seed)
         self.dtype, self.fp8, self.bs, self.B = dtype, kind == "fp8", bs, len(ns)
         self.Hq, self.Hkv, self.D = Hq, Hkv, D
         table_lens = [max(int(x), 0) for x in (Ls if table_lens is None else table_lens)]
-        num_blocks = sum((n + bs - 1) // bs for n in table_lens) + 3
+        num_blocks = max(sum((n + bs - 1) // bs for n in table_lens) + 3, pool or 0)
         shape = (num_blocks, bs, Hkv, D)
         self.cu = (lead + np.concatenate([[0], np.cumsum(ns)])).astype(np.int32)
         self.T = int(self.cu[-1]) + tail
@@ -76,40 +77,59 @@ class Ragged:
             m[s:s + n] = True
         return m
 
-    def reference(self, oracle_mod, window=-1, **kw):
+    def lse_rows(self, b, s, n, L, window=-1, scale=None, ft=np.float64):
+        """[n, Hq]: ln sum_j exp(scale q_i . k_j) over the keys the token rows s .. s + n - 1 of sequence b see, -inf where a row sees
+        none; formed in `ft` -- float64: the judge; float32: what plain fp32 arithmetic leaves of the same rows"""
+        g = self.Hq // self.Hkv
+        scale = 1.0 / math.sqrt(self.D) if scale is None else scale
+        rows = np.full((n, self.Hq), -np.inf)
+        if L > 0:
+            j = np.arange(L)
+            k = self.K[self.bt[b][j // self.bs], j % self.bs].astype(ft)               # [L, Hkv, D]
+            sc = np.einsum("nhgd,lhd->nhgl", self.q[s:s + n].astype(ft).reshape(n, self.Hkv, g, self.D), k) * ft(scale)
+            p = L - n + np.arange(n)
+            see = j[None, :] <= p[:, None]
+            if window > 0:
+                see &= p[:, None] - j[None, :] < window
+            sc = np.where(see[:, None, None, :], sc, ft(-np.inf))
+            m = sc.max(axis=-1)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                v = m + np.log(np.exp(sc - np.where(np.isfinite(m), m, ft(0.0))[..., None]).sum(axis=-1))
+            rows = np.where(np.isfinite(m), v, -np.inf).reshape(n, self.Hq).astype(np.float64)
+        return rows
+
+    def reference(self, oracle_mod, window=-1, scale=None, **kw):
         """(out [T, Hq, D] float32, lse [T, Hq] float64) on the owned rows, zeros / +inf markers elsewhere; computed once per
-        (window, lengths) and shared"""
-        key = (window, tuple((k, tuple(np.asarray(v).tolist()) if k != "max_sq" else v) for k, v in sorted(kw.items())))
+        (window, scale, lengths) and shared"""
+        key = (window, scale, tuple((k, tuple(np.asarray(v).tolist()) if k != "max_sq" else v) for k, v in sorted(kw.items())))
         if key in self._ref:
             return self._ref[key]
         out = np.zeros((self.T, self.Hq, self.D), dtype=np.float32)
         lse = np.full((self.T, self.Hq), np.nan)
-        g, scale = self.Hq // self.Hkv, 1.0 / math.sqrt(self.D)
         for b, s, n, L in self.sequences(**kw):
             if n == 0:
                 continue
             ctx = np.maximum(L - n + 1 + np.arange(n), 0)
-            out[s:s + n] = oracle_mod.paged_decode_f64(self.q[s:s + n], self.K, self.V, np.repeat(self.bt[b:b + 1], n, axis=0), ctx, None, window)
-            rows = np.full((n, self.Hq), -np.inf)
-            if L > 0:
-                j = np.arange(L)
-                k = self.K[self.bt[b][j // self.bs], j % self.bs]                          # [L, Hkv, D]
-                sc = np.einsum("nhgd,lhd->nhgl", self.q[s:s + n].astype(np.float64).reshape(n, self.Hkv, g, self.D), k) * scale
-                p = L - n + np.arange(n)
-                see = j[None, :] <= p[:, None]
-                if window > 0:
-                    see &= p[:, None] - j[None, :] < window
-                sc = np.where(see[:, None, None, :], sc, -np.inf)
-                m = sc.max(axis=-1)
-                with np.errstate(invalid="ignore", divide="ignore"):
-                    v = m + np.log(np.exp(sc - np.where(np.isfinite(m), m, 0.0)[..., None]).sum(axis=-1))
-                rows = np.where(np.isfinite(m), v, -np.inf).reshape(n, self.Hq)
-            lse[s:s + n] = rows
+            out[s:s + n] = oracle_mod.paged_decode_f64(self.q[s:s + n], self.K, self.V, np.repeat(self.bt[b:b + 1], n, axis=0), ctx, scale, window)
+            lse[s:s + n] = self.lse_rows(b, s, n, L, window, scale)
         self._ref[key] = (out, lse)
         return out, lse
 
+    def lse_f32_gap(self, window=-1, scale=None, **kw):
+        """max |fp32 log-sum-exp - fp64 log-sum-exp| over the owned rows that see a key: the error plain NumPy fp32 arithmetic has on
+        these inputs (what an LSE bound may follow when the logits are large)"""
+        gap = 0.0
+        for b, s, n, L in self.sequences(**kw):
+            if n and L:
+                a, r = self.lse_rows(b, s, n, L, window, scale, np.float32), self.lse_rows(b, s, n, L, window, scale)
+                fin = np.isfinite(r)
+                if fin.any():
+                    gap = max(gap, float(np.abs(a[fin] - r[fin]).max()))
+        return gap
+
     # ---- the device side
-    def device(self, torch, cu=None, cl=None):
+    def device(self, torch, cu=None, cl=None, q_pad=0):
+        """q_pad > 0: q is a slice of a [T, Hq D + q_pad] projection whose other columns hold NaN bits"""
         dt = torch_dtype(self.dtype)
         if self.fp8:
             kc, vc = (torch.from_numpy(x).cuda().view(torch.float8_e4m3fn) for x in (self.kdev, self.vdev))
@@ -120,31 +140,37 @@ class Ragged:
             scales = {}
         cu = torch.from_numpy(np.asarray(self.cu if cu is None else cu, dtype=np.int32)).cuda()
         cl = torch.from_numpy(np.asarray(self.cl if cl is None else cl, dtype=np.int32)).cuda()
-        return (torch.from_numpy(self.q).to("cuda", dt), kc, vc, torch.from_numpy(self.bt).cuda(), cl, cu), scales
+        q = torch.from_numpy(self.q).to("cuda", dt)
+        if q_pad:
+            wide = torch.full((self.T, self.Hq * self.D + q_pad), -1, dtype=torch.int16, device="cuda").view(dt)
+            wide[:, :self.Hq * self.D] = q.view(self.T, -1)
+            q = wide[:, :self.Hq * self.D].view(self.T, self.Hq, self.D)
+        return (q, kc, vc, torch.from_numpy(self.bt).cuda(), cl, cu), scales
 
-    def run(self, torch, window=-1, max_sq=None, cu=None, cl=None):
+    def run(self, torch, window=-1, max_sq=None, cu=None, cl=None, scale=None, q_pad=0):
         import aule
-        args, scales = self.device(torch, cu, cl)
-        return aule.flash_attention_paged_prefill(*args, max_seqlen_q=self.max_sq if max_sq is None else max_sq, window_size=window,
+        args, scales = self.device(torch, cu, cl, q_pad)
+        return aule.flash_attention_paged_prefill(*args, max_seqlen_q=self.max_sq if max_sq is None else max_sq, scale=scale, window_size=window,
                                                   return_lse=True, **scales)
 
 
-def _judge(p, out, lse, oracle_mod, window, what, **kw):
-    """the owned rows of (out, lse) against the oracle; prints the measured maxima before it asserts"""
+def _judge(p, out, lse, oracle_mod, window, what, scale=None, lse_atol=LSE_ATOL, **kw):
+    """the owned rows of (out, lse) against the oracle; prints the measured maxima before it asserts and returns them"""
     own = p.owned(**kw)
-    ref, lref = p.reference(oracle_mod, window, **kw)
+    ref, lref = p.reference(oracle_mod, window, scale, **kw)
     out, lse = out.float().cpu().numpy()[own], lse.cpu().numpy().astype(np.float64)[own]
     ref, lref = ref[own], lref[own]
     atol, rtol = fwd_tol(p.dtype, p.vmax)
     none = np.isneginf(lref)
     lerr = float(np.abs(lse[~none] - lref[~none]).max()) if (~none).any() else 0.0
     print("%s: %d rows, max |out err| %.3g (atol %.3g), max |lse err| %.3g (bound %.3g), rows without a key %d"
-          % (what, int(own.sum()), np.abs(out - ref).max() if own.any() else 0.0, atol, lerr, LSE_ATOL, int(none.sum())))
+          % (what, int(own.sum()), np.abs(out - ref).max() if own.any() else 0.0, atol, lerr, lse_atol, int(none.sum())))
     assert not np.isnan(lse).any() and not np.isnan(out).any(), what
     assert_close(out, ref, atol, rtol, what)
     assert np.array_equal(np.isneginf(lse), none), "%s: lse must be -inf exactly where a row sees no key" % what
     assert bool((out[none] == 0).all()), "%s: a row that sees no key must be zeros" % what
-    assert lerr <= LSE_ATOL, (what, lerr)
+    assert lerr <= lse_atol, (what, lerr)
+    return float(np.abs(out - ref).max()) if own.any() else 0.0, lerr
 
 
 # The ragged batch of every shape: new tokens 1, 37, 130, 0, 300 against lengths
@@ -192,7 +218,7 @@ def test_ragged_rows_and_lse_vs_oracle(case, oracle_mod):
     assert bool(np.isneginf(lse[1:1 + 17]).all()) and bool(np.isfinite(lse[1 + 17:38]).all())    # positions -17 .. -1, then 0 .. 19
 
 
-def _desc(torch, p, args, scales, out, lse, max_sq, window=-1, q_stride=None):
+def _desc(torch, p, args, scales, out, lse, max_sq, window=-1, q_stride=None, scale=0.0):
     from aule import _capi
     q, kc, vc, bt, cl, cu = args
     d = _capi.PagedPrefillDesc()
@@ -203,7 +229,7 @@ def _desc(torch, p, args, scales, out, lse, max_sq, window=-1, q_stride=None):
     d.block_size, d.max_blocks = p.bs, bt.shape[1]
     d.total_tokens, d.max_seqlen_q = p.T, max_sq
     d.q_token_stride = p.Hq * p.D if q_stride is None else q_stride
-    d.scale, d.window_size, d.device = 0.0, window, q.device.index or 0
+    d.scale, d.window_size, d.device = scale, window, q.device.index or 0
     d.stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     d.q, d.k_cache, d.v_cache, d.out = q.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr()
     d.lse = lse.data_ptr() if lse is not None else None
@@ -216,15 +242,16 @@ def _desc(torch, p, args, scales, out, lse, max_sq, window=-1, q_stride=None):
 PAD = 64   # rows of 0xFF in front of and behind out / lse
 
 
-def _run_capi(torch, p, max_sq=None, window=-1, cu=None, cl=None, with_lse=True):
+def _run_capi(torch, p, max_sq=None, window=-1, cu=None, cl=None, with_lse=True, scale=None, q_pad=0):
     """through the C-ABI into 0xFF-filled buffers with PAD rows of margin on both sides; returns (out, lse, margins intact)"""
     from aule import _capi
     lib = _capi.get_lib()
-    args, scales = p.device(torch, cu, cl)
+    args, scales = p.device(torch, cu, cl, q_pad)
     big_o = torch.full((p.T + 2 * PAD, p.Hq, p.D), -1, dtype=torch.int16, device="cuda")
     big_l = torch.full((p.T + 2 * PAD, p.Hq), -1, dtype=torch.int32, device="cuda")
     out, lse = big_o[PAD:PAD + p.T], big_l[PAD:PAD + p.T]
-    d = _desc(torch, p, args, scales, out, lse if with_lse else None, p.max_sq if max_sq is None else max_sq, window)
+    d = _desc(torch, p, args, scales, out, lse if with_lse else None, p.max_sq if max_sq is None else max_sq, window,
+              args[0].stride(0) if q_pad else None, 0.0 if scale is None else scale)
     assert lib.aule_attention_paged_prefill_ex(ctypes.byref(d)) == 0, lib.aule_get_error()
     torch.cuda.synchronize()
     intact = all(bool((t[:PAD] == -1).all()) and bool((t[PAD + p.T:] == -1).all()) for t in (big_o, big_l))

@@ -97,7 +97,7 @@ def _i32(a):
     return np.clip(np.asarray(a, dtype=np.int64), I32_MIN, I32_MAX).astype(np.int32)
 
 
-def _launch(torch, lib, p, ptr, causal, window, ws_bytes, backward=True, strides=None):
+def _launch(torch, lib, p, ptr, causal, window, ws_bytes, backward=True, strides=None, scale=0.0):
     """forward, then backward, on the pointers in `ptr` (name -> address); strides: the token strides of q, k, v in elements (None: contiguous)"""
     from aule import _capi
     code = CODE[causal]
@@ -106,7 +106,7 @@ def _launch(torch, lib, p, ptr, causal, window, ws_bytes, backward=True, strides
         d.struct_size = ctypes.sizeof(d)
         d.dtype, d.batch, d.heads_q, d.heads_kv, d.head_dim = hostile.DTYPE_CODE[p.dtype], p.B, p.Hq, p.Hkv, p.D
         d.total_q, d.total_k, d.max_seqlen_q, d.max_seqlen_k = p.Tq, p.Tk, p.max_sq, p.max_sk
-        d.scale, d.causal, d.window_size, d.device = 0.0, code, window, torch.cuda.current_device()
+        d.scale, d.causal, d.window_size, d.device = scale, code, window, torch.cuda.current_device()
         d.q_token_stride, d.k_token_stride, d.v_token_stride = strides or (p.Hq * p.D, p.Hkv * p.D, p.Hkv * p.D)
         d.stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         for n in ("q", "k", "v", "cu_seqlens_q", "cu_seqlens_k", "out", "lse"):
@@ -153,13 +153,13 @@ class Run:
         self.lse = poison((p.Tq, p.Hq * 4), torch.float32)
         self.ws = torch.full((max(_ws_bytes(p), 16),), POISON, dtype=torch.uint8, device="cuda")
 
-    def launch(self, causal, window, backward=True):
+    def launch(self, causal, window, backward=True, scale=None):
         from aule import _capi
         names = ("q", "k", "v", "cu_seqlens_q", "cu_seqlens_k", "out", "lse", "dout", "dq", "dk", "dv")
         tensors = (self.q, self.k, self.v, self.cu_q, self.cu_k, self.out, self.lse, self.dout, self.dq, self.dk, self.dv)
         ptr = {n: t.data_ptr() for n, t in zip(names, tensors)}
         ptr["workspace"] = self.ws.data_ptr()
-        _launch(self.torch, _capi.get_lib(), self.p, ptr, causal, window, _ws_bytes(self.p), backward, self.strides)
+        _launch(self.torch, _capi.get_lib(), self.p, ptr, causal, window, _ws_bytes(self.p), backward, self.strides, 0.0 if scale is None else scale)
         return self
 
     def results(self):
@@ -183,8 +183,8 @@ def _np(t):
     return t.detach().float().cpu().numpy()
 
 
-def _judge(p, res, oracle, causal, window, what, backward=True):
-    """res: name -> tensor (out, lse, dq, dk, dv over the whole packed axes).  Checks every owned row; returns nothing, prints maxima."""
+def _judge(p, res, oracle, causal, window, what, backward=True, scale=None):
+    """res: name -> tensor (out, lse, dq, dk, dv over the whole packed axes).  Checks every owned row; prints the maxima and returns them."""
     code = CODE[causal]
     out, lse = _np(res["out"]), _np(res["lse"])
     if backward:
@@ -210,7 +210,7 @@ def _judge(p, res, oracle, causal, window, what, backward=True):
         assert np.array_equal(oracle._vis_mask(e - a, L, sub, window), vis[a:e]), tag + ": the judge's sub-problem is another problem"
         t = lambda x: np.ascontiguousarray(x.transpose(1, 0, 2))[None]   # noqa: E731
         qs, ks, vs, ds = t(p.q[sq + a:sq + e]), t(p.k[sk:sk + L]), t(p.v[sk:sk + L]), t(p.dout[sq + a:sq + e])
-        ro, rl = oracle.np_fwd_f64(qs, ks, vs, causal=sub, window=window)
+        ro, rl = oracle.np_fwd_f64(qs, ks, vs, causal=sub, scale=scale, window=window)
         atol, rtol = fwd_tol(p.dtype, np.abs(vs).max())
         got = out[sq + a:sq + e].transpose(1, 0, 2)[None]
         assert_close(got, ro, atol, rtol, tag + " out")
@@ -218,12 +218,13 @@ def _judge(p, res, oracle, causal, window, what, backward=True):
         worst["out"] = max(worst["out"], float(np.abs(got - ro).max()))
         worst["lse"] = max(worst["lse"], float(np.abs(lse[sq + a:sq + e].T[None] - rl).max()))
         if backward:
-            rq, rk, rv = oracle.np_bwd_f64(qs, ks, vs, ds, causal=sub, window=window)
+            rq, rk, rv = oracle.np_bwd_f64(qs, ks, vs, ds, causal=sub, scale=scale, window=window)
             worst["dq"] = max(worst["dq"], _check_grad(dq[sq + a:sq + e].transpose(1, 0, 2)[None], rq, p.dtype, tag + " dq"))
             worst["dk"] = max(worst["dk"], _check_grad(dk[sk:sk + L].transpose(1, 0, 2)[None], rk, p.dtype, tag + " dk"))
             worst["dv"] = max(worst["dv"], _check_grad(dv[sk:sk + L].transpose(1, 0, 2)[None], rv, p.dtype, tag + " dv"))
     print("%s: max|err| out %.3e lse %.3e; of max(1, max|grad|): dq %.2e dk %.2e dv %.2e"
           % (what, worst["out"], worst["lse"], worst["dq"], worst["dk"], worst["dv"]))
+    return worst
 
 
 def _unowned_still_poisoned(torch, p, res):

@@ -3,7 +3,8 @@
 GQA ratio, Sq, Sk, head_dim, causal mode, window and scale sign -- the combinations nobody wrote a case for.
 Deterministic per seed; prints every failing configuration.   python tools/fuzz_parity.py [n=200] [seed=0]
 Other kinds: `paged`, `rope`, `split` (small grids + fused rotation), `long` (round 6: Sq 2048 / 4096, gradients judged head by head),
-`window` (round 6: the window instances of the one-wave-per-SIMD forward -- forward + LSE of every row)."""
+`window` (round 6: the window instances of the one-wave-per-SIMD forward -- forward + LSE of every row).
+The paged prefill / query, the paged cascade, the paged MLA and the varlen entries have a tool of their own: tools/fuzz_serving.py."""
 import ctypes, math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "aule-attention_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
