@@ -266,8 +266,8 @@ def flash_attention_mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlen
     number of ranges comes from the shape alone; partials are combined in a fixed order, so two runs give the same bits).
     mla_kv_append writes the new rows (one launch, with the rotation of the 64 rotary dimensions), with slots =
     paged_slot_mapping(block_tables, positions, block_size); an FP8 latent cache is flash_attention_mla_paged_fp8.  Out of
-    scope: a sliding window, a backward pass, the non-absorbed prefill form (192 / 128).  Argument errors are ValueErrors
-    raised before the device is touched; CPU tensors raise AuleError."""
+    scope: a sliding window, a backward pass; the non-absorbed 192 / 128 form of the prompt is flash_attention_mla_prefill.
+    Argument errors are ValueErrors raised before the device is touched; CPU tensors raise AuleError."""
     try:
         import torch  # noqa: F401
     except ImportError as e:
@@ -367,6 +367,38 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     from ._torch import flash_attention_varlen as impl
     return impl(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k, causal=causal,
                 scale=scale, window_size=window_size, return_lse=return_lse)
+
+
+def flash_attention_mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True,
+                                scale=None, return_lse=False):
+    """MLA prefill: multi-head latent attention (DeepSeek-V2 / V3 / R1) in its NON-ABSORBED form, the form the prompt runs in, over
+    a batch of sequences of different lengths packed along one token axis.  Forward only.  Not in the reference.  The contract is
+    stated once, at aule_mla_prefill_desc in include/aule.h; in short:
+
+        q [total_q, heads, 192] (q_nope | q_pe), k_nope and v [total_k, heads, 128], k_pe [total_k, 64] (or [total_k, 1, 64]),
+          fp16 / bf16 ROCm tensors of one dtype: key row j of head h is [k_nope[j, h] | k_pe[j]], the rotated k_pe shared by all
+          heads and never copied per head.  192 / 128 / 64 exactly: nothing is padded.
+        k_nope and v carry their own token AND head strides, k_pe and q their own token stride: the two halves of a
+          [total_k, heads, 256] kv_b output and columns 512.. of a [total_k, 576] down-projection are read in place.  A tensor
+          whose innermost stride is not 1, or whose strides or storage offset are not multiples of 8 elements, is copied.
+        cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal (False, True = top-left, "bottom-right"): as
+          flash_attention_varlen, with the same device-side clamps and cuts; "bottom-right" with more keys than queries is
+          chunked prefill.  There is no window.
+        scale=None is 1/sqrt(192); models with a YaRN mscale pass their own.
+
+    Returns [total_q, heads, 128], or (out, lse) with return_lse=True: lse [total_q, heads] fp32, the natural log of the softmax
+    denominator -- two calls over disjoint key chunks are combined by merge_attention_states.  A token that sees no key gives
+    zeros and lse = -inf; rows that belong to no sequence are never written (out and lse come from torch.empty).  One launch, no
+    workspace; with both maxima given there is no synchronisation and the call captures into a graph.  No autograd: inputs that
+    require grad are refused (ValueError).  Out of scope: a backward, a window, GQA, FP8 inputs, fused rotation.  Argument errors
+    are ValueErrors raised before the device is touched; CPU tensors that pass them raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_prefill
+    return mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k,
+                       causal=causal, scale=scale, return_lse=return_lse)
 
 
 def merge_attention_states(out_a, lse_a, out_b, lse_b):
@@ -615,7 +647,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_mla_prefill", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

@@ -291,6 +291,41 @@ class MergeStatesDesc(ctypes.Structure):
     ]
 
 
+class MlaPrefillDesc(ctypes.Structure):
+    """struct aule_mla_prefill_desc (include/aule.h): MLA prefill, the non-absorbed 192 / 128 form over a packed batch."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("batch", ctypes.c_uint32),
+        ("heads", ctypes.c_uint32),
+        ("qk_dim", ctypes.c_uint32),
+        ("v_dim", ctypes.c_uint32),
+        ("total_q", ctypes.c_uint32),
+        ("total_k", ctypes.c_uint32),
+        ("max_seqlen_q", ctypes.c_uint32),
+        ("max_seqlen_k", ctypes.c_uint32),
+        ("scale", ctypes.c_float),
+        ("causal", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("reserved", ctypes.c_uint32),
+        ("q_token_stride", ctypes.c_int64),
+        ("k_nope_token_stride", ctypes.c_int64),
+        ("k_nope_head_stride", ctypes.c_int64),
+        ("v_token_stride", ctypes.c_int64),
+        ("v_head_stride", ctypes.c_int64),
+        ("k_pe_token_stride", ctypes.c_int64),
+        ("stream", ctypes.c_void_p),
+        ("q", ctypes.c_void_p),
+        ("k_nope", ctypes.c_void_p),
+        ("k_pe", ctypes.c_void_p),
+        ("v", ctypes.c_void_p),
+        ("cu_seqlens_q", ctypes.c_void_p),
+        ("cu_seqlens_k", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p),
+    ]
+
+
 class RopeDesc(ctypes.Structure):
     """struct aule_rope_desc (include/aule.h)."""
     _fields_ = [
@@ -431,6 +466,7 @@ SIGNATURES = [
     ("aule_attention_varlen_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),
     ("aule_attention_varlen_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenBwdDesc)]),
     ("aule_attention_merge_states_ex", _I32, [ctypes.POINTER(MergeStatesDesc)]),
+    ("aule_attention_mla_prefill_ex", _I32, [ctypes.POINTER(MlaPrefillDesc)]),
     ("aule_peer_alloc", _I32, [_I32, _U64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(IpcHandle)]),
     ("aule_peer_free", _I32, [_I32, ctypes.c_void_p]),
     ("aule_peer_open", _I32, [_I32, ctypes.POINTER(IpcHandle), ctypes.POINTER(ctypes.c_void_p)]),

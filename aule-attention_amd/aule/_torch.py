@@ -636,6 +636,11 @@ def _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_
         raise ValueError(f"q, k and v must share one dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
     if D == 0 or D > VARLEN_HEAD_DIMS[-1]:
         raise ValueError(f"variable-length attention is not built for head_dim {D}: 1 to {VARLEN_HEAD_DIMS[-1]}")
+    return _varlen_offsets(cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+
+
+def _varlen_offsets(cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k):
+    """The rules of cu_seqlens_q / cu_seqlens_k [batch + 1] int32 and of the two maxima.  Returns the batch."""
     for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
         if not torch.is_tensor(cu) or cu.dim() != 1 or cu.shape[0] < 1:
             raise ValueError(f"{name} must be a [batch + 1] tensor")
@@ -646,6 +651,19 @@ def _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_
     _varlen_max("max_seqlen_q", max_seqlen_q)
     _varlen_max("max_seqlen_k", max_seqlen_k)
     return cu_seqlens_q.shape[0] - 1
+
+
+def _varlen_maxima(cu_q, cu_k, max_seqlen_q, max_seqlen_k):
+    """The maxima the caller did not give, read from the offsets (on the device) with the one documented synchronisation: both in
+    one read."""
+    if max_seqlen_q is None or max_seqlen_k is None:
+        if cu_q.shape[0] > 1:
+            mq, mk = torch.stack(((cu_q[1:] - cu_q[:-1]).max(), (cu_k[1:] - cu_k[:-1]).max())).tolist()
+        else:
+            mq = mk = 1
+        max_seqlen_q = max(int(mq), 1) if max_seqlen_q is None else max_seqlen_q
+        max_seqlen_k = max(int(mk), 1) if max_seqlen_k is None else max_seqlen_k
+    return max_seqlen_q, max_seqlen_k
 
 
 def _varlen_rows(name, x):
@@ -747,14 +765,7 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
         raise _capi.AuleError("aule (HIP build): variable-length attention needs ROCm device tensors; there is no CPU fallback")
     _same_device("variable-length attention", q, k, v)
     cu_q, cu_k = _int32_on(q.device, cu_seqlens_q, cu_seqlens_k)
-    if max_seqlen_q is None or max_seqlen_k is None:
-        # the one documented synchronisation (both maxima in one read)
-        if cu_q.shape[0] > 1:
-            mq, mk = torch.stack(((cu_q[1:] - cu_q[:-1]).max(), (cu_k[1:] - cu_k[:-1]).max())).tolist()
-        else:
-            mq = mk = 1
-        max_seqlen_q = max(int(mq), 1) if max_seqlen_q is None else max_seqlen_q
-        max_seqlen_k = max(int(mk), 1) if max_seqlen_k is None else max_seqlen_k
+    max_seqlen_q, max_seqlen_k = _varlen_maxima(cu_q, cu_k, max_seqlen_q, max_seqlen_k)
     Dp = next(x for x in VARLEN_HEAD_DIMS if x >= D)
     if Dp != D:   # zero-padded head dim: dot products and outputs are unchanged
         q, k, v = _pad_head_dim(q, Dp), _pad_head_dim(k, Dp), _pad_head_dim(v, Dp)
@@ -765,6 +776,100 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
         out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window, want_lse=return_lse)
     if Dp != D:
         out = out[..., :D]
+    return (out, lse) if return_lse else out
+
+
+# MLA prefill: the non-absorbed 192 / 128 form over a packed batch, forward only (aule_attention_mla_prefill_ex;
+# csrc/fa_fwd_mla_prefill_gfx950.hip).
+
+MLA_PREFILL_DIMS = (192, 128, 64)   # q / key, k_nope / v / out, k_pe
+
+
+def _mla_prefill_rows(x, free_head_stride):
+    """x [T, H, W] as the kernel reads it, and its (token stride, head stride) in elements: in place where the innermost stride is 1,
+    the head stride is W (or, free_head_stride, any multiple of 8 from W up), the token stride a multiple of 8 that holds the heads
+    and the storage offset a multiple of 8; else a contiguous copy."""
+    T, H, W = x.shape
+    hs = x.stride(1) if H > 1 else W
+    least = (max(H, 1) - 1) * hs + W
+    ts = x.stride(0) if T > 1 else least
+    ok = x.stride(2) == 1 and (hs == W or free_head_stride and hs >= W and hs % 8 == 0) and ts >= least and ts % 8 == 0 \
+        and x.storage_offset() % 8 == 0
+    if not ok:
+        x = x.contiguous()
+        if x.storage_offset() % 8 != 0:   # (contiguous as it stood, at an offset that is no 16-byte boundary)
+            x = x.clone()
+        ts, hs = H * W, W
+    return x, ts, hs
+
+
+def mla_prefill_raw(q, k_nope, k_pe, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, want_lse=True):
+    """q [Tq,H,192], k_nope / v [Tk,H,128], k_pe [Tk,64] device tensors, cu_q / cu_k int32 [B + 1] on the same device, causal an
+    AULE_CAUSAL_* code, scale a float.  Returns (out [Tq,H,128], lse [Tq,H] or None), both from torch.empty.  Asynchronous, no
+    synchronisation."""
+    lib = _capi.get_lib()
+    _same_device("MLA prefill", q, k_nope, k_pe, v, cu_q, cu_k)
+    q, sq, _ = _mla_prefill_rows(q, False)
+    k_nope, skn, hkn = _mla_prefill_rows(k_nope, True)
+    v, sv, hv = _mla_prefill_rows(v, True)
+    k_pe, skp, _ = _mla_prefill_rows(k_pe.unsqueeze(1), False)
+    Tq, H, _ = q.shape
+    out = torch.empty((Tq, H, MLA_PREFILL_DIMS[1]), device=q.device, dtype=q.dtype)
+    lse = torch.empty((Tq, H), device=q.device, dtype=torch.float32) if want_lse else None
+    if Tq * H * (cu_q.shape[0] - 1) == 0:
+        return out, lse
+    d = _capi.MlaPrefillDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    d.batch, d.heads, d.qk_dim, d.v_dim = cu_q.shape[0] - 1, H, MLA_PREFILL_DIMS[0], MLA_PREFILL_DIMS[1]
+    d.total_q, d.total_k = Tq, k_nope.shape[0]
+    d.max_seqlen_q, d.max_seqlen_k = max(min(max_seqlen_q, Tq), 1), max(min(max_seqlen_k, k_nope.shape[0]), 1)
+    d.scale = _abi_scale(scale)
+    d.causal = causal
+    d.device = _device_index(q.device)
+    d.q_token_stride, d.k_pe_token_stride = sq, skp
+    d.k_nope_token_stride, d.k_nope_head_stride, d.v_token_stride, d.v_head_stride = skn, hkn, sv, hv
+    d.stream = _stream_ptr(q.device)
+    d.q, d.k_nope, d.k_pe, d.v = q.data_ptr(), k_nope.data_ptr(), k_pe.data_ptr(), v.data_ptr()
+    d.cu_seqlens_q, d.cu_seqlens_k = cu_q.data_ptr(), cu_k.data_ptr()
+    d.out = out.data_ptr()
+    d.lse = lse.data_ptr() if lse is not None else None
+    _capi.check(lib.aule_attention_mla_prefill_ex(ctypes.byref(d)), "aule_attention_mla_prefill_ex")
+    return out, lse
+
+
+def mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
+                return_lse=False):
+    """MLA prefill (aule.flash_attention_mla_prefill documents the arguments; aule_mla_prefill_desc in include/aule.h is the
+    contract).  No autograd: inputs that require grad are refused."""
+    DQ, DV, DR = MLA_PREFILL_DIMS
+    if torch.is_tensor(k_pe) and k_pe.dim() == 3 and k_pe.shape[1] == 1:
+        k_pe = k_pe[:, 0]
+    if not all(torch.is_tensor(x) for x in (q, k_nope, k_pe, v)) or q.dim() != 3 or k_nope.dim() != 3 or v.dim() != 3 or k_pe.dim() != 2:
+        raise ValueError("expected q [total_q, heads, 192], k_nope and v [total_k, heads, 128] and k_pe [total_k, 64] (or [total_k, 1, 64])")
+    if (q.shape[2], k_nope.shape[2], v.shape[2], k_pe.shape[1]) != (DQ, DV, DV, DR):
+        raise ValueError(f"MLA prefill is built for 192 / 128 / 128 / 64 exactly (nothing is padded): q={q.shape[2]}, k_nope={k_nope.shape[2]}, "
+                         f"v={v.shape[2]}, k_pe={k_pe.shape[1]}")
+    if k_nope.shape[1] != q.shape[1] or v.shape[1] != q.shape[1]:
+        raise ValueError(f"MLA prefill is multi-head attention: q, k_nope and v must have one heads count, got {q.shape[1]}, {k_nope.shape[1]}, "
+                         f"{v.shape[1]} (GQA is not built)")
+    if v.shape[0] != k_nope.shape[0] or k_pe.shape[0] != k_nope.shape[0]:
+        raise ValueError(f"k_nope, k_pe and v must have one total_k, got {k_nope.shape[0]}, {k_pe.shape[0]}, {v.shape[0]}")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"MLA prefill is not built for {q.dtype}: fp16 and bf16 only")
+    if any(x.dtype != q.dtype for x in (k_nope, k_pe, v)):
+        raise ValueError(f"q, k_nope, k_pe and v must share one dtype, got {q.dtype}, {k_nope.dtype}, {k_pe.dtype}, {v.dtype}")
+    _varlen_offsets(cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    code = causal_code(causal)
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k_nope, k_pe, v)):
+        raise ValueError("MLA prefill has no backward (prefill is inference): detach the inputs or call it under torch.no_grad()")
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): MLA prefill needs ROCm device tensors; there is no CPU fallback")
+    _same_device("MLA prefill", q, k_nope, k_pe, v)
+    cu_q, cu_k = _int32_on(q.device, cu_seqlens_q, cu_seqlens_k)
+    max_seqlen_q, max_seqlen_k = _varlen_maxima(cu_q, cu_k, max_seqlen_q, max_seqlen_k)
+    out, lse = mla_prefill_raw(q, k_nope, k_pe, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code,
+                               float(1.0 / math.sqrt(DQ) if scale is None else scale), want_lse=return_lse)
     return (out, lse) if return_lse else out
 
 

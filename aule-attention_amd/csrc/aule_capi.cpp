@@ -144,6 +144,21 @@ static_assert(AULE_VARLEN_SAME(dtype) && AULE_VARLEN_SAME(batch) && AULE_VARLEN_
                   AULE_VARLEN_SAME(q) && AULE_VARLEN_SAME(k) && AULE_VARLEN_SAME(v) && AULE_VARLEN_SAME(cu_seqlens_q) && AULE_VARLEN_SAME(cu_seqlens_k),
               "aule_varlen_bwd_desc states the problem in the fields of aule_varlen_desc, up to cu_seqlens_k: both are checked through that prefix");
 #undef AULE_VARLEN_SAME
+static_assert(sizeof(aule_mla_prefill_desc) == 176 && offsetof(aule_mla_prefill_desc, dtype) == 4 && offsetof(aule_mla_prefill_desc, batch) == 8 &&
+                  offsetof(aule_mla_prefill_desc, heads) == 12 && offsetof(aule_mla_prefill_desc, qk_dim) == 16 &&
+                  offsetof(aule_mla_prefill_desc, v_dim) == 20 && offsetof(aule_mla_prefill_desc, total_q) == 24 &&
+                  offsetof(aule_mla_prefill_desc, total_k) == 28 && offsetof(aule_mla_prefill_desc, max_seqlen_q) == 32 &&
+                  offsetof(aule_mla_prefill_desc, max_seqlen_k) == 36 && offsetof(aule_mla_prefill_desc, scale) == 40 &&
+                  offsetof(aule_mla_prefill_desc, causal) == 44 && offsetof(aule_mla_prefill_desc, device) == 48 &&
+                  offsetof(aule_mla_prefill_desc, reserved) == 52 && offsetof(aule_mla_prefill_desc, q_token_stride) == 56 &&
+                  offsetof(aule_mla_prefill_desc, k_nope_token_stride) == 64 && offsetof(aule_mla_prefill_desc, k_nope_head_stride) == 72 &&
+                  offsetof(aule_mla_prefill_desc, v_token_stride) == 80 && offsetof(aule_mla_prefill_desc, v_head_stride) == 88 &&
+                  offsetof(aule_mla_prefill_desc, k_pe_token_stride) == 96 && offsetof(aule_mla_prefill_desc, stream) == 104 &&
+                  offsetof(aule_mla_prefill_desc, q) == 112 && offsetof(aule_mla_prefill_desc, k_nope) == 120 &&
+                  offsetof(aule_mla_prefill_desc, k_pe) == 128 && offsetof(aule_mla_prefill_desc, v) == 136 &&
+                  offsetof(aule_mla_prefill_desc, cu_seqlens_q) == 144 && offsetof(aule_mla_prefill_desc, cu_seqlens_k) == 152 &&
+                  offsetof(aule_mla_prefill_desc, out) == 160 && offsetof(aule_mla_prefill_desc, lse) == 168,
+              "aule_mla_prefill_desc layout is part of the ABI");
 static_assert(sizeof(aule_merge_states_desc) == 80 && offsetof(aule_merge_states_desc, rows) == 8 &&
                   offsetof(aule_merge_states_desc, heads) == 12 && offsetof(aule_merge_states_desc, head_dim) == 16 &&
                   offsetof(aule_merge_states_desc, device) == 20 && offsetof(aule_merge_states_desc, stream) == 24 &&
@@ -1519,6 +1534,79 @@ uint64_t aule_attention_varlen_backward_workspace_size(const aule_varlen_bwd_des
     Reason text;
     if (varlen_bwd_desc_error(d, false, text)) return 0;
     return varlen_bwd_nothing_to_do(varlen_prefix(d)) ? 0 : varlen_bwd_workspace(varlen_prefix(d));
+}
+
+// The MLA prefill (the non-absorbed 192 / 128 form over a packed batch): one checker, one reader (the launch entry).  Host logic
+// only, asked before the device is needed.  The stride rule: at least `least` elements and a multiple of 8.
+static const char* mla_prefill_stride_error(const char* field, int64_t stride, uint64_t least, const char* what, Reason& why) {
+    if (stride < 0 || (uint64_t)stride < least)
+        return reasonf(why, "%s (%lld) is smaller than %s = %llu elements", field, (long long)stride, what, (unsigned long long)least);
+    if (stride % 8 != 0) return reasonf(why, "%s (%lld) must be a multiple of 8 elements (16-byte loads)", field, (long long)stride);
+    return nullptr;
+}
+
+static bool mla_prefill_nothing_to_do(const aule_mla_prefill_desc* d) { return d->total_q == 0 || (uint64_t)d->batch * d->heads == 0; }
+
+static const char* mla_prefill_desc_error(const aule_mla_prefill_desc* d, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_mla_prefill_desc)) return kBadDescriptor;
+    if (!is_16_bit(d->dtype)) return "dtype must be fp16 or bf16";
+    if (d->qk_dim != 192 || d->v_dim != 128) return reasonf(why, "qk_dim %u / v_dim %u unsupported (192 / 128 only)", d->qk_dim, d->v_dim);
+    if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return reasonf(why, "unknown causal mode %d (0 none, 1 top-left, 2 bottom-right)", d->causal);
+    if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
+    if (d->max_seqlen_k == 0) return "max_seqlen_k must be at least 1";
+    if (d->batch >= (1u << 30) || d->heads >= (1u << 30) || d->total_q >= (1u << 30) || d->total_k >= (1u << 30)) return "batch / heads / total_q / total_k too large";
+    const uint64_t more = d->heads > 0 ? d->heads - 1 : 0;   // heads after the first
+    if (const char* e = mla_prefill_stride_error("q_token_stride", d->q_token_stride, (uint64_t)d->heads * 192, "a token, heads * 192", why)) return e;
+    if (const char* e = mla_prefill_stride_error("k_nope_head_stride", d->k_nope_head_stride, 128, "a head", why)) return e;
+    if (const char* e = mla_prefill_stride_error("v_head_stride", d->v_head_stride, 128, "a head", why)) return e;
+    if (d->k_nope_head_stride >= (1ll << 30) || d->v_head_stride >= (1ll << 30)) return "k_nope_head_stride / v_head_stride too large (below 2^30 elements)";
+    if (const char* e = mla_prefill_stride_error("k_nope_token_stride", d->k_nope_token_stride, more * (uint64_t)d->k_nope_head_stride + 128,
+                                                 "a token, (heads - 1) * k_nope_head_stride + 128", why)) return e;
+    if (const char* e = mla_prefill_stride_error("v_token_stride", d->v_token_stride, more * (uint64_t)d->v_head_stride + 128,
+                                                 "a token, (heads - 1) * v_head_stride + 128", why)) return e;
+    if (const char* e = mla_prefill_stride_error("k_pe_token_stride", d->k_pe_token_stride, 64, "a token", why)) return e;
+    if (mla_prefill_nothing_to_do(d)) return nullptr;
+    if (!d->cu_seqlens_q || !d->cu_seqlens_k) return "null cu_seqlens pointer";
+    if (!d->q || !d->out) return "null tensor pointer";
+    if (d->total_k > 0 && (!d->k_nope || !d->k_pe || !d->v)) return "null tensor pointer";
+    if (misaligned(d->q) || misaligned(d->k_nope) || misaligned(d->k_pe) || misaligned(d->v)) return "q, k_nope, k_pe and v must be 16-byte aligned";
+    if (misaligned(d->out)) return "out must be 16-byte aligned";
+    if ((reinterpret_cast<uintptr_t>(d->lse) & 3) != 0) return "lse must be 4-byte aligned";
+    return nullptr;
+}
+
+int32_t aule_attention_mla_prefill_ex(const aule_mla_prefill_desc* d) {
+    RoctxRange range("aule.mla_prefill");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_prefill_desc_error(d, text)) {
+        set_error("MLA prefill failed: %s", why);
+        return -3;
+    }
+    if (mla_prefill_nothing_to_do(d)) return 0;
+    aule_hip::MlaPrefillArgs a;
+    a.q = d->q; a.k_nope = d->k_nope; a.k_pe = d->k_pe; a.v = d->v;
+    a.out = d->out; a.lse = d->lse;
+    a.cu_seqlens_q = d->cu_seqlens_q; a.cu_seqlens_k = d->cu_seqlens_k;
+    a.Tq = (int)d->total_q; a.Tk = (int)d->total_k; a.B = (int)d->batch; a.H = (int)d->heads;
+    a.max_seqlen_q = (int)(d->max_seqlen_q < d->total_q ? d->max_seqlen_q : d->total_q);
+    a.max_seqlen_k = (int)(d->max_seqlen_k < d->total_k ? d->max_seqlen_k : d->total_k);
+    a.q_token_stride = d->q_token_stride;
+    a.k_nope_token_stride = d->k_nope_token_stride; a.k_nope_head_stride = d->k_nope_head_stride;
+    a.v_token_stride = d->v_token_stride; a.v_head_stride = d->v_head_stride;
+    a.k_pe_token_stride = d->k_pe_token_stride;
+    a.scale = resolve_scale(d->scale, d->qk_dim);
+    a.causal = d->causal;
+    a.dtype = d->dtype;
+    if (aule_hip::mla_prefill_grid(a) > 0x7fffffffll) {
+        set_error("MLA prefill failed: the grid (blocks * heads * batch) exceeds 2^31 - 1 workgroups (sizes beyond 32 bits)");
+        return -3;
+    }
+    if (!initialised()) return -1;
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    return launched("MLA prefill", aule_hip::launch_mla_prefill(a, (hipStream_t)d->stream));
 }
 
 // The two-state merge.  One checker, one reader (the launch entry: the pointer rules are stated here too).

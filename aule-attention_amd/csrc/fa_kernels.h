@@ -414,6 +414,33 @@ uint64_t varlen_bwd_workspace_bytes(long long Tq, int Hq);   // delta
 int launch_varlen_fwd(const VarlenArgs& a, hipStream_t stream);   // -1: unsupported arguments
 int launch_varlen_bwd(const VarlenArgs& a, hipStream_t stream);   // delta, dQ, dK/dV on `stream`
 
+// MLA prefill, the non-absorbed form (fa_fwd_mla_prefill_gfx950.hip): ragged 192 / 128 attention over a packed batch, forward only.
+//   q [Tq, H, 192] with its token stride, k_nope and v [Tk, H, 128] each with a token AND a head stride, k_pe [Tk, 64] with its
+//   token stride (all in elements); out [Tq, H, 128] contiguous, lse [Tq, H] fp32 or null.  Key row j of a sequence is
+//   [k_nope[s_k + j, h] | k_pe[s_k + j]] for head h.  cu_seqlens_*, the clamps, the cuts, the positions and the visibility rule as
+//   VarlenArgs with Hkv = Hq and no window.  The caller guarantees 16-byte aligned tensors and strides % 8 == 0.
+struct MlaPrefillArgs {
+    const void* q;
+    const void* k_nope;
+    const void* k_pe;
+    const void* v;
+    void* out = nullptr;
+    float* lse = nullptr;         // null: skipped
+    const int* cu_seqlens_q;
+    const int* cu_seqlens_k;
+    int Tq, Tk, B, H;
+    int max_seqlen_q, max_seqlen_k;
+    long long q_token_stride;
+    long long k_nope_token_stride, k_nope_head_stride;
+    long long v_token_stride, v_head_stride;
+    long long k_pe_token_stride;
+    float scale;
+    int causal;                   // 0 none, 1 top-left, 2 bottom-right
+    int dtype;
+};
+long long mla_prefill_grid(const MlaPrefillArgs& a);   // workgroups: ceil(min(max_seqlen_q, Tq) / 128) x H x B
+int launch_mla_prefill(const MlaPrefillArgs& a, hipStream_t stream);   // -1: unsupported arguments
+
 // Returns 0 on success, a hipError_t value on launch failure, -1 for an
 // unsupported (dtype, D) combination.
 int launch_paged_decode(const PagedArgs& a, hipStream_t stream);   // either cache_kind; kCacheFp8E4M3 with a null scale array is -1

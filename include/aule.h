@@ -414,7 +414,7 @@ uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_de
 /* hipGraph, and a replay sees the CURRENT cu_seqlens_q, context_lens and block_tables.  With hostile cu_seqlens_q that make two      */
 /* sequences own the same row, that row's value is unspecified (and nothing outside out / lse is written).                            */
 /* An FP8 latent cache is aule_attention_mla_paged_fp8_ex below; the write side of both caches is aule_mla_kv_append_ex.              */
-/* Not built: a sliding window; a backward; the non-absorbed prefill form (192 / 128).                                                */
+/* Not built: a sliding window; a backward.  The non-absorbed prefill form (192 / 128) is aule_attention_mla_prefill_ex below.       */
 /* The descriptor is checked before the device is needed: -3 for a refused descriptor and 0 for one with nothing to do               */
 /* (total_tokens = 0, batch = 0 or heads_q = 0) are answered without aule_init().                                                     */
 typedef struct aule_mla_paged_desc {
@@ -610,6 +610,71 @@ typedef struct aule_merge_states_desc {
 } aule_merge_states_desc;
 /* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
 int32_t aule_attention_merge_states_ex(const aule_merge_states_desc* desc);
+
+/* MLA PREFILL (additive): multi-head latent attention in its NON-ABSORBED form, the form the prompt runs in (DeepSeek-V2 / V3 / R1), */
+/* over a variable-length packed batch; forward only.  Every head has its own 128-wide k_nope and 128-wide v (the two slices of the  */
+/* kv_b up-projection), all heads of a token share one 64-wide rotated k_pe, queries are 192 wide (q_nope | q_pe), the output is 128  */
+/* wide: key row j of head h is [k_nope[j, h] | k_pe[j]].  It is MHA: one heads count.  This comment is the contract.                */
+/* Tensors (fp16 or bf16, one dtype), strides in ELEMENTS, each a multiple of 8; every pointer 16-byte aligned:                       */
+/*     q      [total_q, heads, 192]   q_token_stride >= heads * 192, the heads of a token contiguous                                  */
+/*     k_nope [total_k, heads, 128]   k_nope_head_stride >= 128, k_nope_token_stride >= (heads - 1) * k_nope_head_stride + 128        */
+/*     v      [total_k, heads, 128]   v_head_stride >= 128, v_token_stride >= (heads - 1) * v_head_stride + 128                       */
+/*     k_pe   [total_k, 64]           k_pe_token_stride >= 64                                                                         */
+/*     out    [total_q, heads, 128]   contiguous        lse [total_q, heads] fp32, contiguous, optional (NULL to skip)                */
+/* The head strides exist so that the two halves of a [total_k, heads, 256] kv_b output are read in place (head stride 256, token     */
+/* stride heads * 256, v = k_nope + 128 elements); the k_pe token stride so that columns 512.. of a [total_k, 576] down-projection    */
+/* are (token stride 576).  Head strides are below 2^30.  Nothing is padded: 192 / 128 / 64 exactly (qk_dim, v_dim state the first    */
+/* two).                                                                                                                              */
+/* Sequence bounds: cu_seqlens_q and cu_seqlens_k are [batch + 1] int32 on the DEVICE, max_seqlen_q and max_seqlen_k host integers   */
+/* >= 1; the clamps, the cuts to the first max_seqlen_* tokens, the rows that are written and the behaviour under hostile offsets are */
+/* EXACTLY those of aule_varlen_desc above (s_q, e_q, n, s_k, e_k, L): query i < n is row s_q + i, key j < L is row s_k + j.          */
+/* Mask: causal is AULE_CAUSAL_NONE, _TOP_LEFT (pos = i) or _BOTTOM_RIGHT (pos = i + L - n); key j < L is visible iff                 */
+/* (!causal || j <= pos).  L < n is allowed (tokens with pos < 0 see nothing); L > n with bottom-right is chunked prefill.  There is  */
+/* no window.  scale = 0 means 1/sqrt(192); callers with a YaRN mscale pass their own.                                                */
+/* A query row with no visible key gives out = 0 and lse = -inf; rows of no sequence are NEVER written.  Softmax in log2 units with   */
+/* fp32 m, l and accumulators; lse is the natural log of the softmax denominator, so two calls over disjoint key chunks are merged    */
+/* by aule_attention_merge_states_ex (chunked prefill against an up-projected context chunk: two calls and a merge).                  */
+/* One launch of ceil(min(max_seqlen_q, total_q) / 128) * heads * batch workgroups, no workspace, no host synchronisation: captures   */
+/* into a hipGraph, and a replay sees the CURRENT contents of cu_seqlens_q / cu_seqlens_k.                                            */
+/* The descriptor is checked before the device is needed: -3 with a reason (struct_size, dtype, qk_dim / v_dim, causal code, each     */
+/* stride too small or not a multiple of 8, alignment, null pointers, max_seqlen_* < 1, sizes beyond 32 bits) and 0 for a call with   */
+/* nothing to do (total_q = 0, batch = 0 or heads = 0) are answered without aule_init().  total_k = 0 with total_q > 0 writes zeros   */
+/* and -inf to the owned rows; k_nope, k_pe and v may then be NULL.                                                                   */
+/* Not built: a backward (prefill is inference); a sliding window; GQA (heads_kv != heads_q); FP8 inputs; the rotation of q_pe / k_pe */
+/* fused into the kernel; key-range splits for one long sequence.                                                                     */
+typedef struct aule_mla_prefill_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_prefill_desc) = 176 */
+    int32_t dtype;             /* offset 4; AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    uint32_t batch;            /* offset 8; sequences */
+    uint32_t heads;            /* offset 12 */
+    uint32_t qk_dim;           /* offset 16; 192 */
+    uint32_t v_dim;            /* offset 20; 128 */
+    uint32_t total_q;          /* offset 24; rows of q / out; 0: returns 0 without a launch */
+    uint32_t total_k;          /* offset 28; rows of k_nope / k_pe / v */
+    uint32_t max_seqlen_q;     /* offset 32; >= 1: sizes the grid, and caps every n */
+    uint32_t max_seqlen_k;     /* offset 36; >= 1: caps every L */
+    float scale;               /* offset 40; 0 -> 1/sqrt(192) */
+    int32_t causal;            /* offset 44; AULE_CAUSAL_* */
+    int32_t device;            /* offset 48; HIP device ordinal, -1 = current */
+    uint32_t reserved;         /* offset 52; not read */
+    int64_t q_token_stride;        /* offset 56 */
+    int64_t k_nope_token_stride;   /* offset 64 */
+    int64_t k_nope_head_stride;    /* offset 72 */
+    int64_t v_token_stride;        /* offset 80 */
+    int64_t v_head_stride;         /* offset 88 */
+    int64_t k_pe_token_stride;     /* offset 96 */
+    void* stream;              /* offset 104; hipStream_t */
+    const void* q;             /* offset 112 */
+    const void* k_nope;        /* offset 120 */
+    const void* k_pe;          /* offset 128 */
+    const void* v;             /* offset 136 */
+    const int32_t* cu_seqlens_q;   /* offset 144; [batch + 1], device */
+    const int32_t* cu_seqlens_k;   /* offset 152; [batch + 1], device */
+    void* out;                 /* offset 160; [total_q, heads, 128], contiguous */
+    float* lse;                /* offset 168; optional (NULL to skip): [total_q, heads] fp32 */
+} aule_mla_prefill_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_mla_prefill_ex(const aule_mla_prefill_desc* desc);
 
 /* Rotary position embedding pass (additive; SURVEY.md 8f row N1, second half).  Replaces the rotation the           */
 /* reference fuses into its kernels: python/aule/triton_flash.py:32-52,:112-131,:165-180 (layout HALF) and            */
