@@ -401,6 +401,32 @@ def flash_attention_mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, 
                        causal=causal, scale=scale, return_lse=return_lse)
 
 
+def flash_attention_mla_varlen(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True,
+                               scale=None, return_lse=False):
+    """MLA 192 / 128 attention over a variable-length packed batch WITH autograd: flash_attention_mla_prefill for training and
+    fine-tuning with sequence packing.  Not in the reference.  The arguments, their checks and the in-place rules are
+    flash_attention_mla_prefill's, and the forward is the same launch: out and lse are bit-identical to that entry's.  The backward's
+    contract is stated once, at aule_mla_prefill_bwd_desc in include/aule.h; in short:
+
+        dq like q; dk_nope and dv are the two halves of ONE [total_k, heads, 256] buffer, written in place by the kernels (so the
+          gradient of a fused kv_b output needs no concatenation); dk_pe -- the sum over the heads, accumulated in fp32 and
+          rounded once -- in the shape k_pe was given, [total_k, 64] or [total_k, 1, 64].
+        Rows that belong to no sequence are zero; a query that sees no key has dq = 0; a key that no query sees has zero gradients.
+        Deterministic: no floating-point atomics, two runs agree bit for bit.
+        Three or four launches (delta, dQ, dK/dV over head chunks, and the dk_pe reduce when the heads are cut into more than one
+          chunk) on the current stream; with both maxima given there is no synchronisation.
+
+    Returns [total_q, heads, 128], or (out, lse) with return_lse=True; lse is not differentiable.  Argument errors are ValueErrors
+    raised before the device is touched; CPU tensors that pass them raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import flash_attention_mla_varlen as impl
+    return impl(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k, causal=causal,
+                scale=scale, return_lse=return_lse)
+
+
 def merge_attention_states(out_a, lse_a, out_b, lse_b):
     """Merge two attention states of the same queries over DISJOINT key sets into the state over their union: the step that
     combines partial results (a shared prefix and a private suffix, key ranges computed apart).  Not in the reference.
@@ -647,7 +673,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_mla_prefill", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

@@ -326,6 +326,26 @@ class MlaPrefillDesc(ctypes.Structure):
     ]
 
 
+class MlaPrefillBwdDesc(ctypes.Structure):
+    """struct aule_mla_prefill_bwd_desc (include/aule.h): aule_mla_prefill_desc's problem statement (every field up to cu_seqlens_k),
+    then the backward's tensors, output strides and workspace."""
+    _fields_ = MlaPrefillDesc._fields_[:-2] + [
+        ("out", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p),
+        ("dout", ctypes.c_void_p),
+        ("dq", ctypes.c_void_p),
+        ("dk_nope", ctypes.c_void_p),
+        ("dk_pe", ctypes.c_void_p),
+        ("dv", ctypes.c_void_p),
+        ("dk_nope_token_stride", ctypes.c_int64),
+        ("dk_nope_head_stride", ctypes.c_int64),
+        ("dv_token_stride", ctypes.c_int64),
+        ("dv_head_stride", ctypes.c_int64),
+        ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 class RopeDesc(ctypes.Structure):
     """struct aule_rope_desc (include/aule.h)."""
     _fields_ = [
@@ -467,6 +487,8 @@ SIGNATURES = [
     ("aule_attention_varlen_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenBwdDesc)]),
     ("aule_attention_merge_states_ex", _I32, [ctypes.POINTER(MergeStatesDesc)]),
     ("aule_attention_mla_prefill_ex", _I32, [ctypes.POINTER(MlaPrefillDesc)]),
+    ("aule_attention_mla_prefill_backward_ex", _I32, [ctypes.POINTER(MlaPrefillBwdDesc)]),
+    ("aule_attention_mla_prefill_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPrefillBwdDesc)]),
     ("aule_peer_alloc", _I32, [_I32, _U64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(IpcHandle)]),
     ("aule_peer_free", _I32, [_I32, ctypes.c_void_p]),
     ("aule_peer_open", _I32, [_I32, ctypes.POINTER(IpcHandle), ctypes.POINTER(ctypes.c_void_p)]),
@@ -478,6 +500,7 @@ SIGNATURES = [
     ("aule_hip_debug_forward_plan", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_shared_prefix_plan", _I32, [ctypes.POINTER(PagedCascadeDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_plan", _I32, [ctypes.POINTER(MlaPagedDesc), ctypes.POINTER(_I32), _I32]),
+    ("aule_hip_debug_mla_prefill_backward_plan", _I32, [ctypes.POINTER(MlaPrefillBwdDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_last_backward_route", _I32, []),
     ("aule_hip_debug_backward_route", _I32, [ctypes.POINTER(AttnBwdDesc)]),
     ("aule_hip_debug_forward_split_plan", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(_I32), _I32]),

@@ -779,8 +779,8 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     return (out, lse) if return_lse else out
 
 
-# MLA prefill: the non-absorbed 192 / 128 form over a packed batch, forward only (aule_attention_mla_prefill_ex;
-# csrc/fa_fwd_mla_prefill_gfx950.hip).
+# MLA prefill: the non-absorbed 192 / 128 form over a packed batch (aule_attention_mla_prefill_ex; csrc/fa_fwd_mla_prefill_gfx950.hip),
+# and its differentiable twin flash_attention_mla_varlen (aule_attention_mla_prefill_backward_ex; csrc/fa_bwd_mla_prefill_gfx950.hip).
 
 MLA_PREFILL_DIMS = (192, 128, 64)   # q / key, k_nope / v / out, k_pe
 
@@ -803,6 +803,26 @@ def _mla_prefill_rows(x, free_head_stride):
     return x, ts, hs
 
 
+def _mla_prefill_problem(d, q, k_nope, k_pe, v, strides, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale):
+    """The problem statement both MLA prefill descriptors share (the tensors as _mla_prefill_rows returned them, with their strides)."""
+    sq, skn, hkn, sv, hv, skp = strides
+    Tq, H, _ = q.shape
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    d.batch, d.heads, d.qk_dim, d.v_dim = cu_q.shape[0] - 1, H, MLA_PREFILL_DIMS[0], MLA_PREFILL_DIMS[1]
+    d.total_q, d.total_k = Tq, k_nope.shape[0]
+    d.max_seqlen_q, d.max_seqlen_k = max(min(max_seqlen_q, Tq), 1), max(min(max_seqlen_k, k_nope.shape[0]), 1)
+    d.scale = _abi_scale(scale)
+    d.causal = causal
+    d.device = _device_index(q.device)
+    d.q_token_stride, d.k_pe_token_stride = sq, skp
+    d.k_nope_token_stride, d.k_nope_head_stride, d.v_token_stride, d.v_head_stride = skn, hkn, sv, hv
+    d.stream = _stream_ptr(q.device)
+    d.q, d.k_nope, d.k_pe, d.v = q.data_ptr(), k_nope.data_ptr(), k_pe.data_ptr(), v.data_ptr()
+    d.cu_seqlens_q, d.cu_seqlens_k = cu_q.data_ptr(), cu_k.data_ptr()
+    return d
+
+
 def mla_prefill_raw(q, k_nope, k_pe, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, want_lse=True):
     """q [Tq,H,192], k_nope / v [Tk,H,128], k_pe [Tk,64] device tensors, cu_q / cu_k int32 [B + 1] on the same device, causal an
     AULE_CAUSAL_* code, scale a float.  Returns (out [Tq,H,128], lse [Tq,H] or None), both from torch.empty.  Asynchronous, no
@@ -818,20 +838,8 @@ def mla_prefill_raw(q, k_nope, k_pe, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, 
     lse = torch.empty((Tq, H), device=q.device, dtype=torch.float32) if want_lse else None
     if Tq * H * (cu_q.shape[0] - 1) == 0:
         return out, lse
-    d = _capi.MlaPrefillDesc()
-    d.struct_size = ctypes.sizeof(d)
-    d.dtype = _DTYPES[q.dtype]
-    d.batch, d.heads, d.qk_dim, d.v_dim = cu_q.shape[0] - 1, H, MLA_PREFILL_DIMS[0], MLA_PREFILL_DIMS[1]
-    d.total_q, d.total_k = Tq, k_nope.shape[0]
-    d.max_seqlen_q, d.max_seqlen_k = max(min(max_seqlen_q, Tq), 1), max(min(max_seqlen_k, k_nope.shape[0]), 1)
-    d.scale = _abi_scale(scale)
-    d.causal = causal
-    d.device = _device_index(q.device)
-    d.q_token_stride, d.k_pe_token_stride = sq, skp
-    d.k_nope_token_stride, d.k_nope_head_stride, d.v_token_stride, d.v_head_stride = skn, hkn, sv, hv
-    d.stream = _stream_ptr(q.device)
-    d.q, d.k_nope, d.k_pe, d.v = q.data_ptr(), k_nope.data_ptr(), k_pe.data_ptr(), v.data_ptr()
-    d.cu_seqlens_q, d.cu_seqlens_k = cu_q.data_ptr(), cu_k.data_ptr()
+    d = _mla_prefill_problem(_capi.MlaPrefillDesc(), q, k_nope, k_pe, v, (sq, skn, hkn, sv, hv, skp), cu_q, cu_k, max_seqlen_q, max_seqlen_k,
+                             causal, scale)
     d.out = out.data_ptr()
     d.lse = lse.data_ptr() if lse is not None else None
     _capi.check(lib.aule_attention_mla_prefill_ex(ctypes.byref(d)), "aule_attention_mla_prefill_ex")
@@ -842,6 +850,21 @@ def mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
                 return_lse=False):
     """MLA prefill (aule.flash_attention_mla_prefill documents the arguments; aule_mla_prefill_desc in include/aule.h is the
     contract).  No autograd: inputs that require grad are refused."""
+    k_pe, code = _mla_prefill_check(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal)
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k_nope, k_pe, v)):
+        raise ValueError("MLA prefill has no backward (prefill is inference): detach the inputs or call it under torch.no_grad()")
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): MLA prefill needs ROCm device tensors; there is no CPU fallback")
+    _same_device("MLA prefill", q, k_nope, k_pe, v)
+    cu_q, cu_k = _int32_on(q.device, cu_seqlens_q, cu_seqlens_k)
+    max_seqlen_q, max_seqlen_k = _varlen_maxima(cu_q, cu_k, max_seqlen_q, max_seqlen_k)
+    out, lse = mla_prefill_raw(q, k_nope, k_pe, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code,
+                               float(1.0 / math.sqrt(MLA_PREFILL_DIMS[0]) if scale is None else scale), want_lse=return_lse)
+    return (out, lse) if return_lse else out
+
+
+def _mla_prefill_check(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal):
+    """Every rule of the MLA prefill arguments that needs no device.  Returns (k_pe as [total_k, 64], the causal code)."""
     DQ, DV, DR = MLA_PREFILL_DIMS
     if torch.is_tensor(k_pe) and k_pe.dim() == 3 and k_pe.shape[1] == 1:
         k_pe = k_pe[:, 0]
@@ -860,16 +883,74 @@ def mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     if any(x.dtype != q.dtype for x in (k_nope, k_pe, v)):
         raise ValueError(f"q, k_nope, k_pe and v must share one dtype, got {q.dtype}, {k_nope.dtype}, {k_pe.dtype}, {v.dtype}")
     _varlen_offsets(cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
-    code = causal_code(causal)
-    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k_nope, k_pe, v)):
-        raise ValueError("MLA prefill has no backward (prefill is inference): detach the inputs or call it under torch.no_grad()")
+    return k_pe, causal_code(causal)
+
+
+def mla_prefill_bwd_raw(q, k_nope, k_pe, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale):
+    """The gradients of mla_prefill_raw: dq [Tq,H,192], dkv [Tk,H,256] -- dk_nope its columns 0 .. 127 and dv 128 .. 255, written in
+    place through the output strides -- and dk_pe [Tk,64]; ZERO in the rows no sequence owns (the library never writes those; they
+    are allocated zero-filled here).  out, dout, lse contiguous.  Asynchronous, no synchronisation."""
+    lib = _capi.get_lib()
+    _same_device("MLA attention backward", q, k_nope, k_pe, v, out, dout, lse, cu_q, cu_k)
+    q, sq, _ = _mla_prefill_rows(q, False)
+    k_nope, skn, hkn = _mla_prefill_rows(k_nope, True)
+    v, sv, hv = _mla_prefill_rows(v, True)
+    k_pe, skp, _ = _mla_prefill_rows(k_pe.unsqueeze(1), False)
+    (Tq, H, _), Tk = q.shape, k_nope.shape[0]
+    DQ, DV, DR = MLA_PREFILL_DIMS
+    dq = torch.zeros((Tq, H, DQ), device=q.device, dtype=q.dtype)
+    dkv = torch.zeros((Tk, H, 2 * DV), device=q.device, dtype=q.dtype)
+    dk_pe = torch.zeros((Tk, DR), device=q.device, dtype=q.dtype)
+    if H * (cu_q.shape[0] - 1) == 0 or Tq + Tk == 0:
+        return dq, dkv, dk_pe
+    d = _mla_prefill_problem(_capi.MlaPrefillBwdDesc(), q, k_nope, k_pe, v, (sq, skn, hkn, sv, hv, skp), cu_q, cu_k, max_seqlen_q, max_seqlen_k,
+                             causal, scale)
+    d.out, d.lse, d.dout = out.data_ptr(), lse.data_ptr(), dout.data_ptr()
+    d.dq, d.dk_pe = dq.data_ptr(), dk_pe.data_ptr()
+    d.dk_nope, d.dv = dkv.data_ptr(), dkv.data_ptr() + DV * dkv.element_size()
+    d.dk_nope_token_stride = d.dv_token_stride = H * 2 * DV
+    d.dk_nope_head_stride = d.dv_head_stride = 2 * DV
+    ws = _attach_workspace(d, lib.aule_attention_mla_prefill_backward_workspace_size, q.device)   # held until the launch is queued
+    _capi.check(lib.aule_attention_mla_prefill_backward_ex(ctypes.byref(d)), "aule_attention_mla_prefill_backward_ex")
+    del ws
+    return dq, dkv, dk_pe
+
+
+class FlashAttentionMlaVarlenHipFunc(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k_nope, k_pe, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale):
+        out, lse = mla_prefill_raw(q, k_nope, k_pe, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale)
+        ctx.save_for_backward(q, k_nope, k_pe, v, out, lse, cu_q, cu_k)
+        ctx.problem = (max_seqlen_q, max_seqlen_k, causal, scale)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, _dlse):
+        q, k_nope, k_pe, v, out, lse, cu_q, cu_k = ctx.saved_tensors
+        max_seqlen_q, max_seqlen_k, causal, scale = ctx.problem
+        dout = dout.contiguous().to(q.dtype)
+        dq, dkv, dk_pe = mla_prefill_bwd_raw(q, k_nope, k_pe, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale)
+        DV = MLA_PREFILL_DIMS[1]
+        return dq, dkv[..., :DV], dk_pe, dkv[..., DV:], None, None, None, None, None, None
+
+
+def flash_attention_mla_varlen(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
+                               return_lse=False):
+    """MLA 192 / 128 attention over a variable-length packed batch, autograd-aware (aule.flash_attention_mla_varlen documents the
+    arguments; aule_mla_prefill_bwd_desc in include/aule.h is the backward's contract).  The forward is flash_attention_mla_prefill's
+    launch."""
+    k_pe, code = _mla_prefill_check(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal)
     if not q.is_cuda:
-        raise _capi.AuleError("aule (HIP build): MLA prefill needs ROCm device tensors; there is no CPU fallback")
-    _same_device("MLA prefill", q, k_nope, k_pe, v)
+        raise _capi.AuleError("aule (HIP build): MLA attention needs ROCm device tensors; there is no CPU fallback")
+    _same_device("MLA attention", q, k_nope, k_pe, v)
     cu_q, cu_k = _int32_on(q.device, cu_seqlens_q, cu_seqlens_k)
     max_seqlen_q, max_seqlen_k = _varlen_maxima(cu_q, cu_k, max_seqlen_q, max_seqlen_k)
-    out, lse = mla_prefill_raw(q, k_nope, k_pe, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code,
-                               float(1.0 / math.sqrt(DQ) if scale is None else scale), want_lse=return_lse)
+    scale = float(1.0 / math.sqrt(MLA_PREFILL_DIMS[0]) if scale is None else scale)
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k_nope, k_pe, v)):
+        out, lse = FlashAttentionMlaVarlenHipFunc.apply(q, k_nope, k_pe, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, scale)
+    else:
+        out, lse = mla_prefill_raw(q, k_nope, k_pe, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, scale, want_lse=return_lse)
     return (out, lse) if return_lse else out
 
 

@@ -159,6 +159,24 @@ static_assert(sizeof(aule_mla_prefill_desc) == 176 && offsetof(aule_mla_prefill_
                   offsetof(aule_mla_prefill_desc, cu_seqlens_q) == 144 && offsetof(aule_mla_prefill_desc, cu_seqlens_k) == 152 &&
                   offsetof(aule_mla_prefill_desc, out) == 160 && offsetof(aule_mla_prefill_desc, lse) == 168,
               "aule_mla_prefill_desc layout is part of the ABI");
+static_assert(sizeof(aule_mla_prefill_bwd_desc) == 264 && offsetof(aule_mla_prefill_bwd_desc, out) == 160 && offsetof(aule_mla_prefill_bwd_desc, lse) == 168 &&
+                  offsetof(aule_mla_prefill_bwd_desc, dout) == 176 && offsetof(aule_mla_prefill_bwd_desc, dq) == 184 &&
+                  offsetof(aule_mla_prefill_bwd_desc, dk_nope) == 192 && offsetof(aule_mla_prefill_bwd_desc, dk_pe) == 200 &&
+                  offsetof(aule_mla_prefill_bwd_desc, dv) == 208 && offsetof(aule_mla_prefill_bwd_desc, dk_nope_token_stride) == 216 &&
+                  offsetof(aule_mla_prefill_bwd_desc, dk_nope_head_stride) == 224 && offsetof(aule_mla_prefill_bwd_desc, dv_token_stride) == 232 &&
+                  offsetof(aule_mla_prefill_bwd_desc, dv_head_stride) == 240 && offsetof(aule_mla_prefill_bwd_desc, workspace) == 248 &&
+                  offsetof(aule_mla_prefill_bwd_desc, workspace_bytes) == 256,
+              "aule_mla_prefill_bwd_desc layout is part of the ABI");
+#define AULE_MLA_PREFILL_SAME(field) (offsetof(aule_mla_prefill_bwd_desc, field) == offsetof(aule_mla_prefill_desc, field))
+static_assert(AULE_MLA_PREFILL_SAME(dtype) && AULE_MLA_PREFILL_SAME(batch) && AULE_MLA_PREFILL_SAME(heads) && AULE_MLA_PREFILL_SAME(qk_dim) &&
+                  AULE_MLA_PREFILL_SAME(v_dim) && AULE_MLA_PREFILL_SAME(total_q) && AULE_MLA_PREFILL_SAME(total_k) && AULE_MLA_PREFILL_SAME(max_seqlen_q) &&
+                  AULE_MLA_PREFILL_SAME(max_seqlen_k) && AULE_MLA_PREFILL_SAME(scale) && AULE_MLA_PREFILL_SAME(causal) && AULE_MLA_PREFILL_SAME(device) &&
+                  AULE_MLA_PREFILL_SAME(reserved) && AULE_MLA_PREFILL_SAME(q_token_stride) && AULE_MLA_PREFILL_SAME(k_nope_token_stride) &&
+                  AULE_MLA_PREFILL_SAME(k_nope_head_stride) && AULE_MLA_PREFILL_SAME(v_token_stride) && AULE_MLA_PREFILL_SAME(v_head_stride) &&
+                  AULE_MLA_PREFILL_SAME(k_pe_token_stride) && AULE_MLA_PREFILL_SAME(stream) && AULE_MLA_PREFILL_SAME(q) && AULE_MLA_PREFILL_SAME(k_nope) &&
+                  AULE_MLA_PREFILL_SAME(k_pe) && AULE_MLA_PREFILL_SAME(v) && AULE_MLA_PREFILL_SAME(cu_seqlens_q) && AULE_MLA_PREFILL_SAME(cu_seqlens_k),
+              "aule_mla_prefill_bwd_desc states the problem in the fields of aule_mla_prefill_desc, up to cu_seqlens_k: both are checked through that prefix");
+#undef AULE_MLA_PREFILL_SAME
 static_assert(sizeof(aule_merge_states_desc) == 80 && offsetof(aule_merge_states_desc, rows) == 8 &&
                   offsetof(aule_merge_states_desc, heads) == 12 && offsetof(aule_merge_states_desc, head_dim) == 16 &&
                   offsetof(aule_merge_states_desc, device) == 20 && offsetof(aule_merge_states_desc, stream) == 24 &&
@@ -1547,8 +1565,9 @@ static const char* mla_prefill_stride_error(const char* field, int64_t stride, u
 
 static bool mla_prefill_nothing_to_do(const aule_mla_prefill_desc* d) { return d->total_q == 0 || (uint64_t)d->batch * d->heads == 0; }
 
-static const char* mla_prefill_desc_error(const aule_mla_prefill_desc* d, Reason& why) {
-    if (d == nullptr || d->struct_size != sizeof(aule_mla_prefill_desc)) return kBadDescriptor;
+// the problem statement, shared with the backward descriptor (`size`: the kind's own sizeof)
+static const char* mla_prefill_problem_error(const aule_mla_prefill_desc* d, size_t size, Reason& why) {
+    if (d == nullptr || d->struct_size != size) return kBadDescriptor;
     if (!is_16_bit(d->dtype)) return "dtype must be fp16 or bf16";
     if (d->qk_dim != 192 || d->v_dim != 128) return reasonf(why, "qk_dim %u / v_dim %u unsupported (192 / 128 only)", d->qk_dim, d->v_dim);
     if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return reasonf(why, "unknown causal mode %d (0 none, 1 top-left, 2 bottom-right)", d->causal);
@@ -1565,6 +1584,11 @@ static const char* mla_prefill_desc_error(const aule_mla_prefill_desc* d, Reason
     if (const char* e = mla_prefill_stride_error("v_token_stride", d->v_token_stride, more * (uint64_t)d->v_head_stride + 128,
                                                  "a token, (heads - 1) * v_head_stride + 128", why)) return e;
     if (const char* e = mla_prefill_stride_error("k_pe_token_stride", d->k_pe_token_stride, 64, "a token", why)) return e;
+    return nullptr;
+}
+
+static const char* mla_prefill_desc_error(const aule_mla_prefill_desc* d, Reason& why) {
+    if (const char* e = mla_prefill_problem_error(d, sizeof(aule_mla_prefill_desc), why)) return e;
     if (mla_prefill_nothing_to_do(d)) return nullptr;
     if (!d->cu_seqlens_q || !d->cu_seqlens_k) return "null cu_seqlens pointer";
     if (!d->q || !d->out) return "null tensor pointer";
@@ -1573,6 +1597,22 @@ static const char* mla_prefill_desc_error(const aule_mla_prefill_desc* d, Reason
     if (misaligned(d->out)) return "out must be 16-byte aligned";
     if ((reinterpret_cast<uintptr_t>(d->lse) & 3) != 0) return "lse must be 4-byte aligned";
     return nullptr;
+}
+
+// (`d` passed its kind's checker) the problem statement; the tensors behind the prefix are the entry's to set
+static void fill_mla_prefill_args(const aule_mla_prefill_desc* d, aule_hip::MlaPrefillArgs& a) {
+    a.q = d->q; a.k_nope = d->k_nope; a.k_pe = d->k_pe; a.v = d->v;
+    a.cu_seqlens_q = d->cu_seqlens_q; a.cu_seqlens_k = d->cu_seqlens_k;
+    a.Tq = (int)d->total_q; a.Tk = (int)d->total_k; a.B = (int)d->batch; a.H = (int)d->heads;
+    a.max_seqlen_q = (int)(d->max_seqlen_q < d->total_q ? d->max_seqlen_q : d->total_q);
+    a.max_seqlen_k = (int)(d->max_seqlen_k < d->total_k ? d->max_seqlen_k : d->total_k);
+    a.q_token_stride = d->q_token_stride;
+    a.k_nope_token_stride = d->k_nope_token_stride; a.k_nope_head_stride = d->k_nope_head_stride;
+    a.v_token_stride = d->v_token_stride; a.v_head_stride = d->v_head_stride;
+    a.k_pe_token_stride = d->k_pe_token_stride;
+    a.scale = resolve_scale(d->scale, d->qk_dim);
+    a.causal = d->causal;
+    a.dtype = d->dtype;
 }
 
 int32_t aule_attention_mla_prefill_ex(const aule_mla_prefill_desc* d) {
@@ -1585,19 +1625,8 @@ int32_t aule_attention_mla_prefill_ex(const aule_mla_prefill_desc* d) {
     }
     if (mla_prefill_nothing_to_do(d)) return 0;
     aule_hip::MlaPrefillArgs a;
-    a.q = d->q; a.k_nope = d->k_nope; a.k_pe = d->k_pe; a.v = d->v;
+    fill_mla_prefill_args(d, a);
     a.out = d->out; a.lse = d->lse;
-    a.cu_seqlens_q = d->cu_seqlens_q; a.cu_seqlens_k = d->cu_seqlens_k;
-    a.Tq = (int)d->total_q; a.Tk = (int)d->total_k; a.B = (int)d->batch; a.H = (int)d->heads;
-    a.max_seqlen_q = (int)(d->max_seqlen_q < d->total_q ? d->max_seqlen_q : d->total_q);
-    a.max_seqlen_k = (int)(d->max_seqlen_k < d->total_k ? d->max_seqlen_k : d->total_k);
-    a.q_token_stride = d->q_token_stride;
-    a.k_nope_token_stride = d->k_nope_token_stride; a.k_nope_head_stride = d->k_nope_head_stride;
-    a.v_token_stride = d->v_token_stride; a.v_head_stride = d->v_head_stride;
-    a.k_pe_token_stride = d->k_pe_token_stride;
-    a.scale = resolve_scale(d->scale, d->qk_dim);
-    a.causal = d->causal;
-    a.dtype = d->dtype;
     if (aule_hip::mla_prefill_grid(a) > 0x7fffffffll) {
         set_error("MLA prefill failed: the grid (blocks * heads * batch) exceeds 2^31 - 1 workgroups (sizes beyond 32 bits)");
         return -3;
@@ -1607,6 +1636,90 @@ int32_t aule_attention_mla_prefill_ex(const aule_mla_prefill_desc* d) {
     int rc = ensure_configured();
     if (rc) return rc;
     return launched("MLA prefill", aule_hip::launch_mla_prefill(a, (hipStream_t)d->stream));
+}
+
+// The MLA prefill backward: aule_mla_prefill_bwd_desc states the problem in aule_mla_prefill_desc's fields up to cu_seqlens_k (the
+// layout asserts at the top of this file), so it is checked and read through that prefix.  `launch`: the pointer and workspace rules
+// of a call that has something to do as well (the size query and the plan hook read no pointer).
+static const aule_mla_prefill_desc* mla_prefill_prefix(const aule_mla_prefill_bwd_desc* d) { return reinterpret_cast<const aule_mla_prefill_desc*>(d); }
+
+static bool mla_prefill_bwd_nothing_to_do(const aule_mla_prefill_bwd_desc* d) {
+    return (uint64_t)d->batch * d->heads == 0 || (d->total_q == 0 && d->total_k == 0);
+}
+
+static aule_hip::MlaPrefillBwdPlan mla_prefill_bwd_plan_of(const aule_mla_prefill_bwd_desc* d) {
+    return aule_hip::mla_prefill_bwd_plan((int)d->total_q, (int)d->total_k, (int)d->batch, (int)d->heads,
+                                          (int)(d->max_seqlen_q < d->total_q ? d->max_seqlen_q : d->total_q),
+                                          (int)(d->max_seqlen_k < d->total_k ? d->max_seqlen_k : d->total_k), d->device);
+}
+
+static const char* mla_prefill_bwd_desc_error(const aule_mla_prefill_bwd_desc* d, bool launch, Reason& why) {
+    if (const char* e = mla_prefill_problem_error(mla_prefill_prefix(d), sizeof(aule_mla_prefill_bwd_desc), why)) return e;
+    const uint64_t more = d->heads > 0 ? d->heads - 1 : 0;
+    if (const char* e = mla_prefill_stride_error("dk_nope_head_stride", d->dk_nope_head_stride, 128, "a head", why)) return e;
+    if (const char* e = mla_prefill_stride_error("dv_head_stride", d->dv_head_stride, 128, "a head", why)) return e;
+    if (d->dk_nope_head_stride >= (1ll << 30) || d->dv_head_stride >= (1ll << 30)) return "dk_nope_head_stride / dv_head_stride too large (below 2^30 elements)";
+    if (const char* e = mla_prefill_stride_error("dk_nope_token_stride", d->dk_nope_token_stride, more * (uint64_t)d->dk_nope_head_stride + 128,
+                                                 "a token, (heads - 1) * dk_nope_head_stride + 128", why)) return e;
+    if (const char* e = mla_prefill_stride_error("dv_token_stride", d->dv_token_stride, more * (uint64_t)d->dv_head_stride + 128,
+                                                 "a token, (heads - 1) * dv_head_stride + 128", why)) return e;
+    if (mla_prefill_bwd_nothing_to_do(d)) return nullptr;
+    if (!mla_prefill_bwd_plan_of(d).ok) return "a grid exceeds 2^31 - 1 workgroups (sizes beyond 32 bits)";
+    if (!launch) return nullptr;
+    if (!d->cu_seqlens_q || !d->cu_seqlens_k) return "null cu_seqlens pointer";
+    if (d->total_q > 0 && (!d->q || !d->out || !d->lse || !d->dout || !d->dq)) return "null tensor pointer";
+    if (d->total_k > 0 && (!d->k_nope || !d->k_pe || !d->v || !d->dk_nope || !d->dk_pe || !d->dv)) return "null tensor pointer";
+    if (misaligned(d->q) || misaligned(d->k_nope) || misaligned(d->k_pe) || misaligned(d->v)) return "q, k_nope, k_pe and v must be 16-byte aligned";
+    if (misaligned(d->out) || misaligned(d->dout) || misaligned(d->dq) || misaligned(d->dk_nope) || misaligned(d->dk_pe) || misaligned(d->dv))
+        return "out, dout, dq, dk_nope, dk_pe and dv must be 16-byte aligned";
+    if ((reinterpret_cast<uintptr_t>(d->lse) & 3) != 0) return "lse must be 4-byte aligned";
+    if (d->workspace != nullptr) {
+        if (misaligned(d->workspace)) return "workspace must be 16-byte aligned";
+        const uint64_t need = mla_prefill_bwd_plan_of(d).ws_bytes;
+        if (d->workspace_bytes < need)
+            return reasonf(why, "workspace too small (%llu bytes, need %llu)", (unsigned long long)d->workspace_bytes, (unsigned long long)need);
+    }
+    return nullptr;
+}
+
+int32_t aule_attention_mla_prefill_backward_ex(const aule_mla_prefill_bwd_desc* d) {
+    RoctxRange range("aule.mla_prefill_backward");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_prefill_bwd_desc_error(d, true, text)) {
+        set_error("MLA prefill backward failed: %s", why);
+        return -3;
+    }
+    if (mla_prefill_bwd_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaPrefillBwdArgs a;
+    fill_mla_prefill_args(mla_prefill_prefix(d), a.fwd);
+    a.o = d->out; a.lse = d->lse; a.dout = d->dout;
+    a.dq = d->dq; a.dk_nope = d->dk_nope; a.dk_pe = d->dk_pe; a.dv = d->dv;
+    a.dk_nope_token_stride = d->dk_nope_token_stride; a.dk_nope_head_stride = d->dk_nope_head_stride;
+    a.dv_token_stride = d->dv_token_stride; a.dv_head_stride = d->dv_head_stride;
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)d->stream;
+    const aule_hip::MlaPrefillBwdPlan plan = mla_prefill_bwd_plan_of(d);
+    if (d->workspace != nullptr && d->workspace_bytes < plan.ws_bytes) {   // (the plan asks the device now selected: the same one, stated again)
+        set_error("MLA prefill backward failed: workspace too small (%llu bytes, need %llu)", (unsigned long long)d->workspace_bytes, (unsigned long long)plan.ws_bytes);
+        return -3;
+    }
+    if (plan.ws_bytes == 0) return launched("MLA prefill backward", aule_hip::launch_mla_prefill_bwd(a, plan, nullptr, stream));
+    aule_hip::ScopedWorkspace ws(plan.ws_bytes, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
+    if (ws.err != hipSuccess) {
+        set_error("MLA prefill backward failed: workspace allocation (%llu bytes): %s", (unsigned long long)plan.ws_bytes, hipGetErrorString(ws.err));
+        return -4;
+    }
+    return launched("MLA prefill backward", aule_hip::launch_mla_prefill_bwd(a, plan, ws.ptr, stream));
+}
+
+uint64_t aule_attention_mla_prefill_backward_workspace_size(const aule_mla_prefill_bwd_desc* d) {
+    Reason text;
+    if (mla_prefill_bwd_desc_error(d, false, text)) return 0;
+    return mla_prefill_bwd_nothing_to_do(d) ? 0 : mla_prefill_bwd_plan_of(d).ws_bytes;
 }
 
 // The two-state merge.  One checker, one reader (the launch entry: the pointer rules are stated here too).
@@ -2057,6 +2170,20 @@ int32_t aule_hip_debug_mla_plan(const aule_mla_paged_desc* d, int32_t* out, int3
     if (out == nullptr || cap < 6) return -6;
     for (int i = 0; i < 6; ++i) out[i] = v[i];
     return 6;
+}
+
+/* Debug hook: the launch plan of aule_attention_mla_prefill_backward_ex(d) as integers (include/aule.h lists them): the plan the launch
+ * and the workspace query read.  Pure host logic like the forward hook. */
+int32_t aule_hip_debug_mla_prefill_backward_plan(const aule_mla_prefill_bwd_desc* d, int32_t* out, int32_t cap) {
+    Reason text;
+    if (mla_prefill_bwd_desc_error(d, false, text)) return -3;
+    if (mla_prefill_bwd_nothing_to_do(d)) return 0;
+    const aule_hip::MlaPrefillBwdPlan plan = mla_prefill_bwd_plan_of(d);
+    const int32_t v[10] = {plan.heads_per_chunk, plan.n_chunks, plan.max_chunks, (int32_t)plan.delta_grid, (int32_t)plan.dq_grid, (int32_t)plan.dkdv_grid,
+                           (int32_t)plan.reduce_grid, plan.reduce ? 1 : 0, (int32_t)(uint32_t)(plan.ws_bytes & 0xffffffffull), (int32_t)(uint32_t)(plan.ws_bytes >> 32)};
+    if (out == nullptr || cap < 10) return -10;
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return 10;
 }
 
 /* Debug hook: what the most recent backward launch of this process ran (bit mask, include/aule.h). */

@@ -441,6 +441,39 @@ struct MlaPrefillArgs {
 long long mla_prefill_grid(const MlaPrefillArgs& a);   // workgroups: ceil(min(max_seqlen_q, Tq) / 128) x H x B
 int launch_mla_prefill(const MlaPrefillArgs& a, hipStream_t stream);   // -1: unsupported arguments
 
+// Its backward (fa_bwd_mla_prefill_gfx950.hip): delta, dQ, dK/dV over head chunks and, with more than one chunk, the dk_pe reduce.
+//   fwd states the problem (out and lse there are not read); o, dout [Tq, H, 128] and dq [Tq, H, 192] contiguous, lse [Tq, H] fp32,
+//   dk_nope, dv [Tk, H, 128] each with a token AND a head stride (elements), dk_pe [Tk, 64] contiguous.
+struct MlaPrefillBwdArgs {
+    MlaPrefillArgs fwd;
+    const void* o = nullptr;
+    const float* lse = nullptr;
+    const void* dout = nullptr;
+    void* dq = nullptr;
+    void* dk_nope = nullptr;
+    void* dk_pe = nullptr;
+    void* dv = nullptr;
+    long long dk_nope_token_stride = 0, dk_nope_head_stride = 0;
+    long long dv_token_stride = 0, dv_head_stride = 0;
+};
+constexpr int kMlaBwdMaxChunks = 16;   // head chunks of the dK/dV kernel, at most: the dk_pe planes take at most 16 * Tk * 64 * 4 bytes
+struct MlaPrefillBwdPlan {
+    int heads_per_chunk = 0;   // chunk c owns heads [c * heads_per_chunk, min(H, (c + 1) * heads_per_chunk))
+    int n_chunks = 0;          // ceil(H / heads_per_chunk), 1 .. max_chunks
+    int max_chunks = 0;        // kMlaBwdMaxChunks
+    long long delta_grid = 0;  // ceil(Tq * H / 4)
+    long long dq_grid = 0;     // ceil(min(max_seqlen_q, Tq) / 128) x H x B
+    long long dkdv_grid = 0;   // ceil(min(max_seqlen_k, Tk) / 128) x B x n_chunks
+    long long reduce_grid = 0; // ceil(min(max_seqlen_k, Tk) / 128) x B when the reduce runs, else 0
+    bool reduce = false;       // n_chunks > 1: the chunks write fp32 planes and the reduce kernel writes dk_pe
+    bool ok = true;            // false: a grid beyond 31 bits
+    uint64_t delta_bytes = 0;  // [Tq, H] fp32 on a 256-byte boundary
+    uint64_t ws_bytes = 0;     // delta_bytes + (reduce ? n_chunks * Tk * 64 * 4 : 0)
+};
+// all grids zero: nothing to launch; no pointer is read; `device` (-1: the current one) supplies the CU count
+MlaPrefillBwdPlan mla_prefill_bwd_plan(int Tq, int Tk, int B, int H, int max_seqlen_q, int max_seqlen_k, int device);
+int launch_mla_prefill_bwd(const MlaPrefillBwdArgs& a, const MlaPrefillBwdPlan& plan, void* ws, hipStream_t stream);   // -1: unsupported arguments
+
 // Returns 0 on success, a hipError_t value on launch failure, -1 for an
 // unsupported (dtype, D) combination.
 int launch_paged_decode(const PagedArgs& a, hipStream_t stream);   // either cache_kind; kCacheFp8E4M3 with a null scale array is -1

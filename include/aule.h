@@ -640,8 +640,9 @@ int32_t aule_attention_merge_states_ex(const aule_merge_states_desc* desc);
 /* stride too small or not a multiple of 8, alignment, null pointers, max_seqlen_* < 1, sizes beyond 32 bits) and 0 for a call with   */
 /* nothing to do (total_q = 0, batch = 0 or heads = 0) are answered without aule_init().  total_k = 0 with total_q > 0 writes zeros   */
 /* and -inf to the owned rows; k_nope, k_pe and v may then be NULL.                                                                   */
-/* Not built: a backward (prefill is inference); a sliding window; GQA (heads_kv != heads_q); FP8 inputs; the rotation of q_pe / k_pe */
-/* fused into the kernel; key-range splits for one long sequence.                                                                     */
+/* Not built: a backward of THIS entry (it saves nothing for one; the differentiable form is aule_attention_mla_prefill_backward_ex   */
+/* below); a sliding window; GQA (heads_kv != heads_q); FP8 inputs; the rotation of q_pe / k_pe fused into the kernel;                */
+/* key-range splits for one long sequence.                                                                                            */
 typedef struct aule_mla_prefill_desc {
     uint32_t struct_size;      /* = sizeof(aule_mla_prefill_desc) = 176 */
     int32_t dtype;             /* offset 4; AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
@@ -675,6 +676,81 @@ typedef struct aule_mla_prefill_desc {
 } aule_mla_prefill_desc;
 /* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
 int32_t aule_attention_mla_prefill_ex(const aule_mla_prefill_desc* desc);
+
+/* MLA PREFILL BACKWARD (additive): the gradients of aule_attention_mla_prefill_ex for training and fine-tuning with sequence packing. */
+/* This comment is the contract.  The problem statement -- every field up to cu_seqlens_k -- is aule_mla_prefill_desc's, at the same  */
+/* offsets and under the same rules (tensors, strides, clamps of cu_seqlens_*, cuts by max_seqlen_*, the three causal modes, scale);  */
+/* then the backward's tensors, of the same dtype:                                                                                    */
+/*     out, dout [total_q, heads, 128]   contiguous; out and lse [total_q, heads] fp32 are the forward's results (lse is required)    */
+/*     dq        [total_q, heads, 192]   contiguous                                                                                   */
+/*     dk_nope   [total_k, heads, 128]   dk_nope_head_stride >= 128, dk_nope_token_stride >= (heads - 1) * dk_nope_head_stride + 128  */
+/*     dv        [total_k, heads, 128]   dv_head_stride >= 128, dv_token_stride >= (heads - 1) * dv_head_stride + 128                 */
+/*     dk_pe     [total_k, 64]           contiguous: the sum over the heads of the gradient of key columns 128 .. 191                 */
+/* The four output strides are in ELEMENTS, multiples of 8, head strides below 2^30: the input-side rules, so that the gradient of a  */
+/* [total_k, heads, 256] kv_b output is written in place into one buffer (head stride 256, token stride heads * 256,                  */
+/* dv = dk_nope + 128 elements).  Every pointer is 16-byte aligned (lse 4-byte).                                                      */
+/* Rows written: every owned row -- dq rows s_q .. s_q + n - 1 (zeros for a query without a visible key), dk_nope, dv and dk_pe rows  */
+/* s_k .. s_k + L - 1 (zeros for a key no query sees, n = 0 included) -- and only those 192 / 128 / 128 / 64 elements of them; rows   */
+/* of no sequence and the bytes between strided rows are NEVER written.  With hostile overlapping offsets the value of a doubly owned */
+/* row is unspecified; nothing outside the outputs and the workspace is written.                                                     */
+/* Launches, all on `stream`, no host synchronisation: delta = rowsum(dout * out), dQ, dK/dV and, when the plan cuts the heads into   */
+/* more than one chunk, the dk_pe reduce.  The dK/dV kernel sums dk_pe over the heads of a chunk in registers; chunk c writes an fp32 */
+/* partial to plane c of [n_chunks, total_k, 64] and the reduce adds the planes in chunk order.  There are no floating-point atomics: */
+/* two runs of one call agree bit for bit.  n_chunks is at most 16 (aule_hip_debug_mla_prefill_backward_plan reports the plan).       */
+/* Workspace: delta [total_q, heads] fp32 on a 256-byte boundary, then the planes when the reduce runs;                               */
+/* aule_attention_mla_prefill_backward_workspace_size() gives the bytes.  workspace = NULL: allocated and freed on the stream; with   */
+/* a workspace passed the call allocates nothing, captures into a hipGraph, and a replay sees the CURRENT cu_seqlens_*.               */
+/* Checked before the device is needed: -3 with a reason -- the forward descriptor's list, plus null out / lse / dout / gradient      */
+/* pointers, each output stride too small or not a multiple of 8, alignment, a workspace too small or not 16-byte aligned -- and 0    */
+/* for a call with nothing to do (batch = 0, heads = 0, or total_q = 0 and total_k = 0) are answered without aule_init().             */
+/* total_q = 0 with total_k > 0 zeroes the owned key rows (q, out, lse, dout, dq may then be NULL); total_k = 0 with total_q > 0      */
+/* zeroes the owned dq rows (the key-side pointers may then be NULL).                                                                 */
+typedef struct aule_mla_prefill_bwd_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_prefill_bwd_desc) = 264 */
+    int32_t dtype;
+    uint32_t batch;
+    uint32_t heads;
+    uint32_t qk_dim;
+    uint32_t v_dim;
+    uint32_t total_q;
+    uint32_t total_k;
+    uint32_t max_seqlen_q;
+    uint32_t max_seqlen_k;     /* also sizes the dK/dV grid */
+    float scale;
+    int32_t causal;
+    int32_t device;
+    uint32_t reserved;
+    int64_t q_token_stride;
+    int64_t k_nope_token_stride;
+    int64_t k_nope_head_stride;
+    int64_t v_token_stride;
+    int64_t v_head_stride;
+    int64_t k_pe_token_stride;
+    void* stream;
+    const void* q;
+    const void* k_nope;
+    const void* k_pe;
+    const void* v;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k;
+    const void* out;               /* offset 160; the forward's out */
+    const float* lse;              /* offset 168; the forward's lse (required) */
+    const void* dout;              /* offset 176; [total_q, heads, 128], contiguous */
+    void* dq;                      /* offset 184; [total_q, heads, 192], contiguous */
+    void* dk_nope;                 /* offset 192 */
+    void* dk_pe;                   /* offset 200; [total_k, 64], contiguous */
+    void* dv;                      /* offset 208 */
+    int64_t dk_nope_token_stride;  /* offset 216 */
+    int64_t dk_nope_head_stride;   /* offset 224 */
+    int64_t dv_token_stride;       /* offset 232 */
+    int64_t dv_head_stride;        /* offset 240 */
+    void* workspace;               /* offset 248; optional, size from aule_attention_mla_prefill_backward_workspace_size() */
+    uint64_t workspace_bytes;      /* offset 256 */
+} aule_mla_prefill_bwd_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_mla_prefill_backward_ex(const aule_mla_prefill_bwd_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
+uint64_t aule_attention_mla_prefill_backward_workspace_size(const aule_mla_prefill_bwd_desc* desc);
 
 /* Rotary position embedding pass (additive; SURVEY.md 8f row N1, second half).  Replaces the rotation the           */
 /* reference fuses into its kernels: python/aule/triton_flash.py:32-52,:112-131,:165-180 (layout HALF) and            */
@@ -852,6 +928,12 @@ int32_t aule_hip_debug_shared_prefix_plan(const aule_paged_cascade_desc* desc, i
 /* capacity needed), 0 for a descriptor with nothing to do; -3 bad.  Host logic only, no aule_init(), no pointer of the descriptor  */
 /* is read (the pointer rules of the launch are not applied); without a device it plans for 256 compute units.                      */
 int32_t aule_hip_debug_mla_plan(const aule_mla_paged_desc* desc, int32_t* out, int32_t cap);
+/* Debug: the launch plan of aule_attention_mla_prefill_backward_ex(desc) as integers -- out = {heads per chunk, n_chunks (the last    */
+/* chunk may be short), the bound of n_chunks (16), delta workgroups, dQ workgroups, dK/dV workgroups (key blocks * batch * n_chunks),  */
+/* reduce workgroups, 1 if the reduce runs (else the dK/dV kernel writes dk_pe itself), workspace bytes low 32 bits, high 32 bits}.     */
+/* Returns the ints written (negative: the capacity needed), 0 for a descriptor with nothing to do; -3 bad.  Host logic only, no       */
+/* aule_init(), no pointer of the descriptor is read; without a device it plans for 256 compute units.                                 */
+int32_t aule_hip_debug_mla_prefill_backward_plan(const aule_mla_prefill_bwd_desc* desc, int32_t* out, int32_t cap);
 /* Debug: bit mask of the kernels the most recent backward launch of this process ran -- 1 the 5-matmul mode (delta pass, dK/dV kernel  */
 /* spilling its dS, dQ = dS K), 2 / 4 the one-wave-per-SIMD dQ / dK/dV kernel, 8 / 16 their two-waves-per-SIMD predecessors, 32 the    */
 /* fp32 kernels, 64 (with 4) the D = 64 dK/dV instance with two key blocks per wave, 128 the head_dim 256 kernels (with 32 for fp32);  */
