@@ -3,9 +3,10 @@
 // The tensors, the clamps of cu_seqlens_q / cu_seqlens_k and the visibility rule are those of fa_fwd_mla_prefill_gfx950.hip:
 //     q [Tq, H, 192]   k_nope, v [Tk, H, 128] with token AND head strides   k_pe [Tk, 64] with its token stride
 //     out, dout [Tq, H, 128], lse [Tq, H], dq [Tq, H, 192], dk_pe [Tk, 64] contiguous   dk_nope, dv [Tk, H, 128] with token AND head strides
-// The trio of fa_bwd_varlen_gfx950.hip with a 192-wide key, a 128-wide value and one k_pe per token; three or four launches:
+// The trio of fa_bwd_varlen_gfx950.hip in the shape of fa_mla_prefill_common.h -- a 192-wide key, a 128-wide value and one k_pe per
+// token -- with the same dQ body and row store (fa_varlen_common.h, fa_tile_attention.h); three or four launches:
 //   delta     delta = rowsum(dO * O) in fp32 over 128 columns, one wave per (token, head) row, all Tq rows (workspace: [Tq, H] fp32)
-//   dQ        the forward's decomposition: workgroup = (rank, sequence, head), 4 waves x 32 rows, Q (12 chunk pairs) and dO (8) of the
+//   dQ        ragged_dq_body, the forward's decomposition: workgroup = (rank, sequence, head), 4 waves x 32 rows, Q (12 chunk pairs) and dO (8) of the
 //             lane's row in registers; K tiles of 64 keys assembled in LDS from k_nope (columns 0 .. 127) and k_pe (128 .. 191) at pitch
 //             464 (29 sixteen-byte slots: read as ds_read_b128 rows AND transposed), V tiles at pitch 272; S^T = K.Q^T over 192,
 //             dP^T = V.dO^T over 128, dS^T = P^T (dP^T - delta) with P = exp2(S c - L log2 e) on visible keys only,
@@ -23,15 +24,12 @@
 //             runs of one call agree bit for bit.
 // Every owned row of dq, dk_nope, dv and dk_pe is written (zeros where nothing is seen, n = 0 included); rows of no sequence never.
 #include "fa_kernels.h"
+#include "fa_mla_prefill_common.h"
 #include "fa_varlen_common.h"
 
 namespace aule_hip {
 namespace {
 
-constexpr int kDQK = 192;    // q / key width: 128 (nope) + 64 (rope)
-constexpr int kDN = 128;     // k_nope width
-constexpr int kDR = 64;      // k_pe width
-constexpr int kDV = 128;     // value / output width
 constexpr int kPQK = VarlenCfg<kDQK>::PAT;   // 464: 192-wide rows read both as b128 operands and transposed
 constexpr int kPVT = VarlenCfg<kDV>::PAT;    // 336: 128-wide rows read both ways
 constexpr int kPVA = PrefillCfg<kDV>::PA;    // 272: 128-wide rows read as b128 operands only
@@ -88,110 +86,11 @@ __global__ void __launch_bounds__(256) fa_bwd_mla_delta_kernel(const MlaBwdParam
     if (lane == 0) p.delta[row] = acc;
 }
 
-// One K tile (from its two sources) and one V tile of 64 keys of sequence rows sk .. on their way to LDS; rows at or beyond kend
-// (<= L: inside the tensors) are not read.
-struct MlaKeyTiles {
-    RowTile<kDN, kPK> kn;   // 4 chunks per thread
-    RowTile<kDR, kPK> kp;   // 2
-    RowTile<kDV, kPK> v;    // 4
-    const char* knbase;
-    const char* kpbase;
-    const char* vbase;
-    long long knpitch, kppitch, vpitch;
-    int kend;
-    __device__ __forceinline__ MlaKeyTiles(const MlaBwdParams& p, const QueryBlock& x, int head)
-        : knbase(p.k_nope + ((long long)x.sk * p.kn_stride + (long long)head * p.kn_hstride) * 2), kpbase(p.k_pe + (long long)x.sk * p.kp_stride * 2),
-          vbase(p.v + ((long long)x.sk * p.v_stride + (long long)head * p.v_hstride) * 2),
-          knpitch(p.kn_stride * 2), kppitch(p.kp_stride * 2), vpitch(p.v_stride * 2), kend(x.kend) {}
-    __device__ __forceinline__ void load(int k0, int tid) {
-        kn.load([&](int row) { return k0 + row < kend ? knbase + (long long)(k0 + row) * knpitch : nullptr; }, tid);
-        kp.load([&](int row) { return k0 + row < kend ? kpbase + (long long)(k0 + row) * kppitch : nullptr; }, tid);
-        v.load([&](int row) { return k0 + row < kend ? vbase + (long long)(k0 + row) * vpitch : nullptr; }, tid);
-    }
-};
-
 template <class T>
 __global__ void __launch_bounds__(256, 1) fa_bwd_mla_dq_kernel(const MlaBwdParams p) {
-    constexpr int GQ = kDQK / 16, GV = kDV / 16, DT = kDQK / 32;   // 12, 8, 6
     __shared__ __attribute__((aligned(16))) char Ks[kPK * kPQK];
     __shared__ __attribute__((aligned(16))) char Vs[kPK * kPVA];
-
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int bid = (int)blockIdx.x;
-    const int units = p.H * p.B;
-    const int rank = bid / units, unit = bid - rank * units;
-    const int head = unit % p.H, b = unit / p.H;
-
-    const QueryBlock x = query_block(p, rank, b, head, wave, l31);
-    if (x.rows == 0) return;
-    const int ntiles = x.ntiles;
-
-    // Q and dO operand chunks of this lane's row, its lse (log2 units) and delta
-    const long long orow = ((long long)x.sq + x.tok) * p.H + head;
-    const char* qrow = p.q + (((long long)x.sq + x.tok) * p.q_stride + (long long)head * kDQK) * 2;
-    const char* dorow = p.dout + orow * (kDV * 2);
-    u32x4_t qf[GQ], of[GV];
-#pragma unroll
-    for (int g = 0; g < GQ; ++g) qf[g] = *reinterpret_cast<const u32x4_t*>(qrow + 32 * g + 16 * hi);
-#pragma unroll
-    for (int g = 0; g < GV; ++g) of[g] = *reinterpret_cast<const u32x4_t*>(dorow + 32 * g + 16 * hi);
-    const float l2 = p.lse[orow] * kLog2e;
-    const float dl = p.delta[orow];
-
-    f32x16_t acc[DT];
-#pragma unroll
-    for (int i = 0; i < DT; ++i) acc[i] = f32x16_t{};
-
-    MlaKeyTiles kt(p, x, head);
-    if (ntiles > 0) kt.load(x.kbeg, tid);
-    for (int t = 0; t < ntiles; ++t) {
-        const int k0 = x.kbeg + t * kPK;
-        __syncthreads();
-        kt.kn.store(Ks, kPQK, tid);
-        kt.kp.store(Ks + kDN * 2, kPQK, tid);
-        kt.v.store(Vs, kPVA, tid);
-        __syncthreads();
-        if (t + 1 < ntiles) kt.load(k0 + kPK, tid);
-        if (x.skips(k0)) continue;
-        // S^T[key][row] = K.Q^T over 192, dP^T[key][row] = V.dO^T over 128
-        f32x16_t s[2] = {f32x16_t{}, f32x16_t{}}, dp[2] = {f32x16_t{}, f32x16_t{}};
-#pragma unroll
-        for (int g = 0; g < GQ; ++g)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) s[kk] = mfma16<T>(lds_b128(Ks + (32 * kk + l31) * kPQK + 32 * g + 16 * hi), qf[g], s[kk]);
-#pragma unroll
-        for (int g = 0; g < GV; ++g)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) dp[kk] = mfma16<T>(lds_b128(Vs + (32 * kk + l31) * kPVA + 32 * g + 16 * hi), of[g], dp[kk]);
-        // dS^T = P^T (dP^T - delta), P^T = exp2(S^T c - L log2 e) on visible keys
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const int j = k0 + 32 * kk + crow(rr, hi);
-                const float pr = x.visible(j) ? fast_exp2(s[kk][rr] * p.c - l2) : 0.f;
-                s[kk][rr] = pr * (dp[kk][rr] - dl);
-            }
-        // dQ^T[d][q] += K^T.dS^T over the 192 columns of the tile
-#pragma unroll
-        for (int st = 0; st < 4; ++st) {
-            const u32x4_t bs = pack_step<T>(s[st >> 1], st & 1);
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) acc[dt] = mfma16<T>(lds_tr_step(Ks, kPQK, 16 * st, 32 * dt, lane), bs, acc[dt]);
-        }
-    }
-    if (!x.live) return;
-    char* gq = p.dq + orow * (kDQK * 2);
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int d = 32 * dt + 8 * g4 + 4 * hi;
-            const float a0 = acc[dt][4 * g4] * p.scale, a1 = acc[dt][4 * g4 + 1] * p.scale;
-            const float a2 = acc[dt][4 * g4 + 2] * p.scale, a3 = acc[dt][4 * g4 + 3] * p.scale;
-            *reinterpret_cast<u32x2_t*>(gq + d * 2) = u32x2_t{T::pack2(a0, a1), T::pack2(a2, a3)};
-        }
+    ragged_dq_body<T, MlaShape>(p, Ks, Vs);
 }
 
 template <class T>
@@ -333,18 +232,7 @@ __global__ void __launch_bounds__(256, 1) fa_bwd_mla_dkdv_kernel(const MlaBwdPar
                     for (int dt = 0; dt < TR; ++dt) dkp[dt] = mfma16<T>(lds_tr_step(Qs, kPQK, 16 * st, kDN + 32 * dt, lane), db, dkp[dt]);
                 }
             }
-            if (live) {
-                char* gk = p.dkn + (((long long)sk.s + kj) * p.dkn_stride + (long long)h * p.dkn_hstride) * 2;
-#pragma unroll
-                for (int dt = 0; dt < TN; ++dt)
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const int d = 32 * dt + 8 * g4 + 4 * hi;
-                        const float k0v = dkn[dt][4 * g4] * p.scale, k1v = dkn[dt][4 * g4 + 1] * p.scale;
-                        const float k2v = dkn[dt][4 * g4 + 2] * p.scale, k3v = dkn[dt][4 * g4 + 3] * p.scale;
-                        *reinterpret_cast<u32x2_t*>(gk + d * 2) = u32x2_t{T::pack2(k0v, k1v), T::pack2(k2v, k3v)};
-                    }
-            }
+            if (live) store_row16<T, TN>(p.dkn + (((long long)sk.s + kj) * p.dkn_stride + (long long)h * p.dkn_hstride) * 2, dkn, p.scale, hi);
         }
         {   // pass 2: dV^T[d][key] += dO^T.P
             f32x16_t dv[TV];
@@ -366,17 +254,7 @@ __global__ void __launch_bounds__(256, 1) fa_bwd_mla_dkdv_kernel(const MlaBwdPar
                     for (int dt = 0; dt < TV; ++dt) dv[dt] = mfma16<T>(lds_tr_step(Os, kPVT, 16 * st, 32 * dt, lane), pb, dv[dt]);
                 }
             }
-            if (live) {
-                char* gv = p.dv + (((long long)sk.s + kj) * p.dv_stride + (long long)h * p.dv_hstride) * 2;
-#pragma unroll
-                for (int dt = 0; dt < TV; ++dt)
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const int d = 32 * dt + 8 * g4 + 4 * hi;
-                        *reinterpret_cast<u32x2_t*>(gv + d * 2) =
-                            u32x2_t{T::pack2(dv[dt][4 * g4], dv[dt][4 * g4 + 1]), T::pack2(dv[dt][4 * g4 + 2], dv[dt][4 * g4 + 3])};
-                    }
-            }
+            if (live) store_row16<T, TV>(p.dv + (((long long)sk.s + kj) * p.dv_stride + (long long)h * p.dv_hstride) * 2, dv, 1.f, hi);
         }
     }
     if (!live) return;
@@ -442,7 +320,7 @@ MlaPrefillBwdPlan mla_prefill_bwd_plan(int Tq, int Tk, int B, int H, int max_seq
     MlaPrefillBwdPlan pl;
     pl.max_chunks = kMlaBwdMaxChunks;
     if (B <= 0 || H <= 0 || (Tq <= 0 && Tk <= 0)) return pl;
-    const long long nq = max_seqlen_q < Tq ? max_seqlen_q : Tq, nk = max_seqlen_k < Tk ? max_seqlen_k : Tk;
+    const long long nq = seqlen_cut(max_seqlen_q, Tq), nk = seqlen_cut(max_seqlen_k, Tk);
     const long long qblocks = nq > 0 ? (nq + kPQ - 1) / kPQ : 0, kblocks = nk > 0 ? (nk + kVKB - 1) / kVKB : 0;
     pl.heads_per_chunk = H;
     pl.n_chunks = 1;
@@ -478,26 +356,16 @@ int launch_mla_prefill_bwd(const MlaPrefillBwdArgs& a, const MlaPrefillBwdPlan& 
     if (plan.dq_grid <= 0 && plan.dkdv_grid <= 0) return 0;
     if (plan.ws_bytes > 0 && ws == nullptr) return -1;
     MlaBwdParams p;
-    p.q = static_cast<const char*>(f.q); p.k_nope = static_cast<const char*>(f.k_nope); p.k_pe = static_cast<const char*>(f.k_pe);
-    p.v = static_cast<const char*>(f.v); p.o = static_cast<const char*>(a.o); p.dout = static_cast<const char*>(a.dout);
+    mla_inputs(p, f);
+    p.o = static_cast<const char*>(a.o); p.dout = static_cast<const char*>(a.dout);
     p.lse = a.lse;
     p.delta = static_cast<float*>(ws);
     p.part = reinterpret_cast<float*>(static_cast<char*>(ws) + plan.delta_bytes);
     p.dq = static_cast<char*>(a.dq); p.dkn = static_cast<char*>(a.dk_nope); p.dkp = static_cast<char*>(a.dk_pe); p.dv = static_cast<char*>(a.dv);
-    p.cu_q = f.cu_seqlens_q; p.cu_k = f.cu_seqlens_k;
-    p.q_stride = f.q_token_stride;
-    p.kn_stride = f.k_nope_token_stride; p.kn_hstride = f.k_nope_head_stride;
-    p.v_stride = f.v_token_stride; p.v_hstride = f.v_head_stride;
-    p.kp_stride = f.k_pe_token_stride;
     p.dkn_stride = a.dk_nope_token_stride; p.dkn_hstride = a.dk_nope_head_stride;
     p.dv_stride = a.dv_token_stride; p.dv_hstride = a.dv_head_stride;
-    p.Tq = f.Tq; p.Tk = f.Tk; p.B = f.B; p.H = f.H;
-    p.max_sq = f.max_seqlen_q < f.Tq ? f.max_seqlen_q : f.Tq;
-    p.max_sk = f.max_seqlen_k < f.Tk ? f.max_seqlen_k : f.Tk;
     p.hpc = plan.heads_per_chunk; p.nchunks = plan.n_chunks;
-    p.c = f.scale * kLog2e;
     p.scale = f.scale;
-    p.causal = f.causal;
     if (f.dtype == kBF16) return launch_instance<Bf16Traits>(p, plan, stream);
     if (f.dtype == kF16) return launch_instance<F16Traits>(p, plan, stream);
     return -1;

@@ -2,9 +2,9 @@
 //
 // The tensors, the clamps of cu_seqlens_q / cu_seqlens_k and the visibility rule are those of fa_fwd_varlen_gfx950.hip; out, lse,
 // dout, dq [Tq, Hq, D] / [Tq, Hq] and dk, dv [Tk, Hkv, D] are contiguous.  Three launches, the plain backward of
-// fa_bwd_d256_gfx950.hip generalised over D = 32, 64, 128:
+// fa_bwd_d256_gfx950.hip generalised over D = 32, 64, 128, the dQ kernel and the row stores from fa_varlen_common.h and fa_tile_attention.h:
 //   delta     delta = rowsum(dO * O) in fp32, one wave per (token, head) row, all Tq rows (the workspace: [Tq, Hq] fp32)
-//   dQ        the forward's work decomposition and tile walk: workgroup = (rank, sequence, KV head), 128 token-major packed rows,
+//   dQ        ragged_dq_body: the forward's work decomposition and tile walk: workgroup = (rank, sequence, KV head), 128 token-major packed rows,
 //             4 waves x 32 rows, Q and dO of the lane's row in registers; K / V tiles of 64 keys through LDS, the next one prefetched
 //             into registers; S^T = K.Q^T, dP^T = V.dO^T, dS^T = P^T (dP^T - delta) with P = exp2(S c - L log2 e) on visible keys
 //             only, dQ^T[d][q] += K^T.dS^T with K read transposed from the same LDS tile (pitch PAT).  dq = scale * acc.
@@ -68,82 +68,7 @@ __global__ void __launch_bounds__(256, 1) fa_bwd_varlen_dq_kernel(const VarlenBw
     using C = VarlenCfg<D>;
     __shared__ __attribute__((aligned(16))) char Ks[kPK * C::PAT];
     __shared__ __attribute__((aligned(16))) char Vs[kPK * C::PA];
-
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int bid = (int)blockIdx.x;
-    const int units = p.Hkv * p.B;
-    const int rank = bid / units, unit = bid - rank * units;
-    const int hk = unit % p.Hkv, b = unit / p.Hkv;
-
-    const QueryBlock x = query_block(p, rank, b, hk, wave, l31);
-    if (x.rows == 0) return;
-    const int ntiles = x.ntiles;
-
-    // Q and dO operand chunks of this lane's row, its lse (log2 units) and delta
-    const long long orow = ((long long)x.sq + x.tok) * p.Hq + x.head;
-    const char* qrow = p.q + (((long long)x.sq + x.tok) * p.q_stride + (long long)x.head * D) * 2;
-    const char* dorow = p.dout + orow * (long long)C::RB;
-    u32x4_t qf[C::G], of[C::G];
-#pragma unroll
-    for (int g = 0; g < C::G; ++g) {
-        qf[g] = *reinterpret_cast<const u32x4_t*>(qrow + 32 * g + 16 * hi);
-        of[g] = *reinterpret_cast<const u32x4_t*>(dorow + 32 * g + 16 * hi);
-    }
-    const float l2 = p.lse[orow] * kLog2e;
-    const float dl = p.delta[orow];
-
-    f32x16_t acc[C::DT];
-#pragma unroll
-    for (int i = 0; i < C::DT; ++i) acc[i] = f32x16_t{};
-
-    KeyTiles<D> kt(p, x, hk);
-    if (ntiles > 0) kt.load(x.kbeg, tid);
-    for (int t = 0; t < ntiles; ++t) {
-        const int k0 = x.kbeg + t * kPK;
-        __syncthreads();
-        kt.k.store(Ks, C::PAT, tid);
-        kt.v.store(Vs, C::PA, tid);
-        __syncthreads();
-        if (t + 1 < ntiles) kt.load(k0 + kPK, tid);
-        if (x.skips(k0)) continue;
-        // S^T[key][row] = K.Q^T, dP^T[key][row] = V.dO^T
-        f32x16_t s[2] = {f32x16_t{}, f32x16_t{}}, dp[2] = {f32x16_t{}, f32x16_t{}};
-#pragma unroll
-        for (int g = 0; g < C::G; ++g)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                s[kk] = mfma16<T>(lds_b128(Ks + (32 * kk + l31) * C::PAT + 32 * g + 16 * hi), qf[g], s[kk]);
-                dp[kk] = mfma16<T>(lds_b128(Vs + (32 * kk + l31) * C::PA + 32 * g + 16 * hi), of[g], dp[kk]);
-            }
-        // dS^T = P^T (dP^T - delta), P^T = exp2(S^T c - L log2 e) on visible keys
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const int j = k0 + 32 * kk + crow(rr, hi);
-                const float pr = x.visible(j) ? fast_exp2(s[kk][rr] * p.c - l2) : 0.f;
-                s[kk][rr] = pr * (dp[kk][rr] - dl);
-            }
-        // dQ^T[d][q] += K^T.dS^T
-#pragma unroll
-        for (int st = 0; st < 4; ++st) {
-            const u32x4_t bs = pack_step<T>(s[st >> 1], st & 1);
-#pragma unroll
-            for (int dt = 0; dt < C::DT; ++dt) acc[dt] = mfma16<T>(lds_tr_step(Ks, C::PAT, 16 * st, 32 * dt, lane), bs, acc[dt]);
-        }
-    }
-    if (!x.live) return;
-    char* gq = p.dq + orow * (long long)C::RB;
-#pragma unroll
-    for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int d = 32 * dt + 8 * g4 + 4 * hi;
-            const float a0 = acc[dt][4 * g4] * p.scale, a1 = acc[dt][4 * g4 + 1] * p.scale;
-            const float a2 = acc[dt][4 * g4 + 2] * p.scale, a3 = acc[dt][4 * g4 + 3] * p.scale;
-            *reinterpret_cast<u32x2_t*>(gq + d * 2) = u32x2_t{T::pack2(a0, a1), T::pack2(a2, a3)};
-        }
+    ragged_dq_body<T, VarlenShape<D>>(p, Ks, Vs);
 }
 
 template <class T, int D>
@@ -269,37 +194,8 @@ __global__ void __launch_bounds__(256, 1) fa_bwd_varlen_dkdv_kernel(const Varlen
     }
     if (!live) return;
     const long long krow_out = ((long long)sk.s + kj) * p.Hkv + hk;
-    char* gk = p.dk + krow_out * (long long)C::RB;
-    char* gv = p.dv + krow_out * (long long)C::RB;
-#pragma unroll
-    for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int d = 32 * dt + 8 * g4 + 4 * hi;
-            const float k0v = dk[dt][4 * g4] * p.scale, k1v = dk[dt][4 * g4 + 1] * p.scale;
-            const float k2v = dk[dt][4 * g4 + 2] * p.scale, k3v = dk[dt][4 * g4 + 3] * p.scale;
-            *reinterpret_cast<u32x2_t*>(gk + d * 2) = u32x2_t{T::pack2(k0v, k1v), T::pack2(k2v, k3v)};
-            *reinterpret_cast<u32x2_t*>(gv + d * 2) =
-                u32x2_t{T::pack2(dv[dt][4 * g4], dv[dt][4 * g4 + 1]), T::pack2(dv[dt][4 * g4 + 2], dv[dt][4 * g4 + 3])};
-        }
-}
-
-template <class T, int D>
-int launch_instance(const VarlenBwdParams& p, long long rows, long long dq_grid, long long dkdv_grid, hipStream_t stream) {
-    if (dq_grid > 0) {
-        hipLaunchKernelGGL((fa_bwd_varlen_delta_kernel<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, p, rows);
-        hipLaunchKernelGGL((fa_bwd_varlen_dq_kernel<T, D>), dim3((unsigned)dq_grid), dim3(256), 0, stream, p);
-    }
-    if (dkdv_grid > 0) hipLaunchKernelGGL((fa_bwd_varlen_dkdv_kernel<T, D>), dim3((unsigned)dkdv_grid), dim3(256), 0, stream, p);
-    return (int)hipGetLastError();
-}
-
-template <class T>
-int launch_dim(const VarlenBwdParams& p, long long rows, long long dq_grid, long long dkdv_grid, hipStream_t stream) {
-    if (p.D == 32) return launch_instance<T, 32>(p, rows, dq_grid, dkdv_grid, stream);
-    if (p.D == 64) return launch_instance<T, 64>(p, rows, dq_grid, dkdv_grid, stream);
-    if (p.D == 128) return launch_instance<T, 128>(p, rows, dq_grid, dkdv_grid, stream);
-    return -1;
+    store_row16<T, C::DT>(p.dk + krow_out * (long long)C::RB, dk, p.scale, hi);
+    store_row16<T, C::DT>(p.dv + krow_out * (long long)C::RB, dv, 1.f, hi);
 }
 
 }  // namespace
@@ -307,8 +203,7 @@ int launch_dim(const VarlenBwdParams& p, long long rows, long long dq_grid, long
 // ceil(min(max_seqlen_k, Tk) / 128) key blocks per (sequence, KV head)
 long long varlen_dkdv_grid(const VarlenArgs& a) {
     if (a.Hkv <= 0 || a.max_seqlen_k <= 0 || a.Tk <= 0) return 0;
-    const long long n = a.max_seqlen_k < a.Tk ? a.max_seqlen_k : a.Tk;
-    return (n + kVKB - 1) / kVKB * a.Hkv * a.B;
+    return ((long long)varlen_max_sk(a) + kVKB - 1) / kVKB * a.Hkv * a.B;
 }
 
 // delta [Tq, Hq] fp32, on a 256-byte boundary
@@ -317,10 +212,7 @@ uint64_t varlen_bwd_workspace_bytes(long long Tq, int Hq) {
 }
 
 int launch_varlen_bwd(const VarlenArgs& a, hipStream_t stream) {
-    if (a.Hkv <= 0 || a.Hq % a.Hkv != 0 || a.causal < 0 || a.causal > 2) return -1;
-    if (a.q_token_stride < (long long)a.Hq * a.D || a.q_token_stride % 8 != 0) return -1;
-    if (a.k_token_stride < (long long)a.Hkv * a.D || a.k_token_stride % 8 != 0) return -1;
-    if (a.v_token_stride < (long long)a.Hkv * a.D || a.v_token_stride % 8 != 0) return -1;
+    if (!varlen_args_ok(a)) return -1;
     const long long dq_grid = varlen_fwd_grid(a), dkdv_grid = varlen_dkdv_grid(a);
     if (dq_grid <= 0 && dkdv_grid <= 0) return 0;
     if (dq_grid > 0x7fffffffll || dkdv_grid > 0x7fffffffll || ((long long)a.Tq + kPQ) * (a.Hq / a.Hkv) > 0x7fffffffll) return -1;
@@ -333,15 +225,22 @@ int launch_varlen_bwd(const VarlenArgs& a, hipStream_t stream) {
     p.cu_q = a.cu_seqlens_q; p.cu_k = a.cu_seqlens_k;
     p.q_stride = a.q_token_stride; p.k_stride = a.k_token_stride; p.v_stride = a.v_token_stride;
     p.Tq = a.Tq; p.Tk = a.Tk; p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.g = a.Hq / a.Hkv; p.D = a.D;
-    p.max_sq = a.max_seqlen_q < a.Tq ? a.max_seqlen_q : a.Tq;
-    p.max_sk = a.max_seqlen_k < a.Tk ? a.max_seqlen_k : a.Tk;
+    p.max_sq = varlen_max_sq(a);
+    p.max_sk = varlen_max_sk(a);
     p.c = a.scale * kLog2e;
     p.scale = a.scale;
     p.causal = a.causal;
     p.window = varlen_window(a);
-    if (a.dtype == kBF16) return launch_dim<Bf16Traits>(p, rows, dq_grid, dkdv_grid, stream);
-    if (a.dtype == kF16) return launch_dim<F16Traits>(p, rows, dq_grid, dkdv_grid, stream);
-    return -1;
+    return dispatch_tile_instance(a.dtype, a.D, [&](auto t, auto d) {
+        using T = decltype(t);
+        constexpr int D = decltype(d)::value;
+        if (dq_grid > 0) {
+            hipLaunchKernelGGL((fa_bwd_varlen_delta_kernel<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, p, rows);
+            hipLaunchKernelGGL((fa_bwd_varlen_dq_kernel<T, D>), dim3((unsigned)dq_grid), dim3(256), 0, stream, p);
+        }
+        if (dkdv_grid > 0) hipLaunchKernelGGL((fa_bwd_varlen_dkdv_kernel<T, D>), dim3((unsigned)dkdv_grid), dim3(256), 0, stream, p);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace aule_hip

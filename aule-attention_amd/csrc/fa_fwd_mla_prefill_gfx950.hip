@@ -18,15 +18,11 @@
 // writes O = 0 and LSE = -inf; rows of no sequence are never written.  One launch, no workspace:
 // grid = ceil(min(max_seqlen_q, Tq) / 128) x H x B.  LDS 64 (400 + 320) = 46080 bytes.
 #include "fa_kernels.h"
+#include "fa_mla_prefill_common.h"
 #include "fa_varlen_common.h"
 
 namespace aule_hip {
 namespace {
-
-constexpr int kDQK = 192;    // q / key width: 128 (nope) + 64 (rope)
-constexpr int kDN = 128;     // k_nope width
-constexpr int kDR = 64;      // k_pe width
-constexpr int kDV = 128;     // value / output width
 
 struct MlaPrefillParams {
     const char* q;
@@ -48,28 +44,6 @@ struct MlaPrefillParams {
     // what query_block reads beside the above: MHA, no window
     static constexpr int g = 1;
     static constexpr int window = 0;
-};
-
-// One K tile (from its two sources) and one V tile of 64 keys of sequence rows sk .. on their way to LDS; rows at or beyond kend
-// (<= L: inside the tensors) are not read.
-struct MlaKeyTiles {
-    RowTile<kDN, kPK> kn;   // 4 chunks per thread
-    RowTile<kDR, kPK> kp;   // 2
-    RowTile<kDV, kPK> v;    // 4
-    const char* knbase;
-    const char* kpbase;
-    const char* vbase;
-    long long knpitch, kppitch, vpitch;
-    int kend;
-    __device__ __forceinline__ MlaKeyTiles(const MlaPrefillParams& p, const QueryBlock& x, int head)
-        : knbase(p.k_nope + ((long long)x.sk * p.kn_stride + (long long)head * p.kn_hstride) * 2), kpbase(p.k_pe + (long long)x.sk * p.kp_stride * 2),
-          vbase(p.v + ((long long)x.sk * p.v_stride + (long long)head * p.v_hstride) * 2),
-          knpitch(p.kn_stride * 2), kppitch(p.kp_stride * 2), vpitch(p.v_stride * 2), kend(x.kend) {}
-    __device__ __forceinline__ void load(int k0, int tid) {
-        kn.load([&](int row) { return k0 + row < kend ? knbase + (long long)(k0 + row) * knpitch : nullptr; }, tid);
-        kp.load([&](int row) { return k0 + row < kend ? kpbase + (long long)(k0 + row) * kppitch : nullptr; }, tid);
-        v.load([&](int row) { return k0 + row < kend ? vbase + (long long)(k0 + row) * vpitch : nullptr; }, tid);
-    }
 };
 
 template <class T>
@@ -109,9 +83,7 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_mla_prefill_kernel(const MlaPre
     for (int t = 0; t < ntiles; ++t) {
         const int k0 = x.kbeg + t * kPK;
         __syncthreads();   // every wave is done with the previous tile
-        kt.kn.store(Ks, PA, tid);
-        kt.kp.store(Ks + kDN * 2, PA, tid);
-        kt.v.store(Vs, CV::PT, tid);
+        kt.store(Ks, PA, Vs, CV::PT, tid);
         __syncthreads();
         if (t + 1 < ntiles) kt.load(k0 + kPK, tid);
         if (x.skips(k0)) continue;
@@ -193,8 +165,7 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_mla_prefill_kernel(const MlaPre
 // 1-D index, head fastest, rank r = the sequence's own block count - 1 - r.
 long long mla_prefill_grid(const MlaPrefillArgs& a) {
     if (a.H <= 0 || a.B <= 0 || a.max_seqlen_q <= 0 || a.Tq <= 0) return 0;
-    const long long n = a.max_seqlen_q < a.Tq ? a.max_seqlen_q : a.Tq;   // no sequence has more tokens than the batch
-    return (n + kPQ - 1) / kPQ * a.H * a.B;
+    return ((long long)seqlen_cut(a.max_seqlen_q, a.Tq) + kPQ - 1) / kPQ * a.H * a.B;
 }
 
 int launch_mla_prefill(const MlaPrefillArgs& a, hipStream_t stream) {
@@ -208,19 +179,8 @@ int launch_mla_prefill(const MlaPrefillArgs& a, hipStream_t stream) {
     // the kernel counts rows in 32 bits
     if (nwg > 0x7fffffffll || (long long)a.Tq + kPQ > 0x7fffffffll || a.Tk < 0) return -1;
     MlaPrefillParams p;
-    p.q = static_cast<const char*>(a.q); p.k_nope = static_cast<const char*>(a.k_nope); p.k_pe = static_cast<const char*>(a.k_pe);
-    p.v = static_cast<const char*>(a.v);
+    mla_inputs(p, a);
     p.o = static_cast<char*>(a.out); p.lse = a.lse;
-    p.cu_q = a.cu_seqlens_q; p.cu_k = a.cu_seqlens_k;
-    p.q_stride = a.q_token_stride;
-    p.kn_stride = a.k_nope_token_stride; p.kn_hstride = a.k_nope_head_stride;
-    p.v_stride = a.v_token_stride; p.v_hstride = a.v_head_stride;
-    p.kp_stride = a.k_pe_token_stride;
-    p.Tq = a.Tq; p.Tk = a.Tk; p.B = a.B; p.H = a.H;
-    p.max_sq = a.max_seqlen_q < a.Tq ? a.max_seqlen_q : a.Tq;
-    p.max_sk = a.max_seqlen_k < a.Tk ? a.max_seqlen_k : a.Tk;
-    p.c = a.scale * kLog2e;
-    p.causal = a.causal;
     const dim3 grid((unsigned)nwg), block(256);
     if (a.dtype == kBF16) hipLaunchKernelGGL((fa_fwd_mla_prefill_kernel<Bf16Traits>), grid, block, 0, stream, p);
     else if (a.dtype == kF16) hipLaunchKernelGGL((fa_fwd_mla_prefill_kernel<F16Traits>), grid, block, 0, stream, p);

@@ -23,7 +23,7 @@
 // sequence's own last (heaviest) block; a workgroup whose rank is past the sequence's blocks leaves before it touches the table or
 // the caches.  The table is walked one tile ahead of the K / V loads, which are one tile ahead of the MFMAs.
 #include "fa_kernels.h"
-#include "fa_paged_tile.h"
+#include "fa_tile_attention.h"
 
 namespace aule_hip {
 namespace {
@@ -199,33 +199,13 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_kernel(const Pref
     }
 }
 
-template <class T, int D, class KV>
-int launch_instance(const PrefillParams& p, long long nwg, hipStream_t stream) {
-    hipLaunchKernelGGL((fa_fwd_paged_prefill_kernel<T, D, KV>), dim3((unsigned)nwg), dim3(256), 0, stream, p);
-    return (int)hipGetLastError();
-}
-
-template <class T, int D>
-int launch_kind(const PrefillParams& p, bool fp8, long long nwg, hipStream_t stream) {
-    return fp8 ? launch_instance<T, D, KvFp8>(p, nwg, stream) : launch_instance<T, D, Kv16>(p, nwg, stream);
-}
-
-template <class T>
-int launch_dim(const PrefillParams& p, int D, bool fp8, long long nwg, hipStream_t stream) {
-    if (D == 32) return launch_kind<T, 32>(p, fp8, nwg, stream);
-    if (D == 64) return launch_kind<T, 64>(p, fp8, nwg, stream);
-    if (D == 128) return launch_kind<T, 128>(p, fp8, nwg, stream);
-    return -1;
-}
-
 }  // namespace
 
 // The grid rule: ceil(max_seqlen_q * g / 128) blocks per (sequence, KV head); the kernel decodes (rank, sequence, KV head) from
 // the 1-D index, KV head fastest, rank r = the sequence's own block count - 1 - r.
 long long paged_prefill_blocks_per_unit(const PagedPrefillArgs& a) {
     if (a.Hkv <= 0 || a.max_seqlen_q <= 0) return 0;
-    const long long n = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T;   // no sequence has more tokens than the batch
-    return (n * (a.Hq / a.Hkv) + kPQ - 1) / kPQ;
+    return ((long long)seqlen_cut(a.max_seqlen_q, a.T) * (a.Hq / a.Hkv) + kPQ - 1) / kPQ;
 }
 
 long long paged_prefill_grid(const PagedPrefillArgs& a) {
@@ -252,12 +232,13 @@ int launch_paged_prefill(const PagedPrefillArgs& a, hipStream_t stream) {
     p.T = a.T; p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.g = a.Hq / a.Hkv;
     p.bs = a.block_size;
     p.bs_shift = (a.block_size & (a.block_size - 1)) == 0 ? __builtin_ctz((unsigned)a.block_size) : -1;
-    p.max_blocks = a.max_blocks; p.max_sq = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T;
+    p.max_blocks = a.max_blocks; p.max_sq = seqlen_cut(a.max_seqlen_q, a.T);
     p.c = a.scale * kLog2e;
     p.window = a.window > 0 ? a.window : 0;
-    if (a.dtype == kBF16) return launch_dim<Bf16Traits>(p, a.D, fp8, nwg, stream);
-    if (a.dtype == kF16) return launch_dim<F16Traits>(p, a.D, fp8, nwg, stream);
-    return -1;
+    return dispatch_tile_instance(a.dtype, a.D, fp8, [&](auto t, auto d, auto kv) {
+        hipLaunchKernelGGL((fa_fwd_paged_prefill_kernel<decltype(t), decltype(d)::value, decltype(kv)>), dim3((unsigned)nwg), dim3(256), 0, stream, p);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace aule_hip

@@ -16,7 +16,7 @@
 // A table entry at logical block >= ceil(P / bs) is never dereferenced, a key row at or beyond P never read (zeros in LDS, masked),
 // lanes past R store nothing.
 #include "fa_kernels.h"
-#include "fa_paged_tile.h"
+#include "fa_tile_attention.h"
 
 namespace aule_hip {
 namespace {
@@ -173,25 +173,6 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_paged_shared_prefix_kernel(cons
     if (hi == 0) *reinterpret_cast<f32x2_t*>(pr + D) = f32x2_t{m, l};
 }
 
-template <class T, int D, class KV>
-int launch_instance(const SharedPrefixParams& p, long long nwg, hipStream_t stream) {
-    hipLaunchKernelGGL((fa_fwd_paged_shared_prefix_kernel<T, D, KV>), dim3((unsigned)nwg), dim3(256), 0, stream, p);
-    return (int)hipGetLastError();
-}
-
-template <class T, int D>
-int launch_kind(const SharedPrefixParams& p, bool fp8, long long nwg, hipStream_t stream) {
-    return fp8 ? launch_instance<T, D, KvFp8>(p, nwg, stream) : launch_instance<T, D, Kv16>(p, nwg, stream);
-}
-
-template <class T>
-int launch_dim(const SharedPrefixParams& p, int D, bool fp8, long long nwg, hipStream_t stream) {
-    if (D == 32) return launch_kind<T, 32>(p, fp8, nwg, stream);
-    if (D == 64) return launch_kind<T, 64>(p, fp8, nwg, stream);
-    if (D == 128) return launch_kind<T, 128>(p, fp8, nwg, stream);
-    return -1;
-}
-
 }  // namespace
 
 // The plan.  Row blocks x KV heads are the items one key range gives; the keys are split until the items cover the device's CUs
@@ -239,9 +220,10 @@ int launch_shared_prefix(const SharedPrefixArgs& a, const SharedPrefixPlan& pl, 
     p.max_blocks = a.max_prefix_blocks;
     p.nrb = pl.row_blocks; p.tps = pl.tiles_per_split;
     p.c = a.scale * kLog2e;
-    if (a.dtype == kBF16) return launch_dim<Bf16Traits>(p, a.D, fp8, pl.grid, stream);
-    if (a.dtype == kF16) return launch_dim<F16Traits>(p, a.D, fp8, pl.grid, stream);
-    return -1;
+    return dispatch_tile_instance(a.dtype, a.D, fp8, [&](auto t, auto d, auto kv) {
+        hipLaunchKernelGGL((fa_fwd_paged_shared_prefix_kernel<decltype(t), decltype(d)::value, decltype(kv)>), dim3((unsigned)pl.grid), dim3(256), 0, stream, p);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace aule_hip

@@ -148,31 +148,17 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_varlen_kernel(const VarlenFwdPa
     }
 }
 
-template <class T>
-int launch_dim(const VarlenFwdParams& p, int D, long long nwg, hipStream_t stream) {
-    const dim3 grid((unsigned)nwg), block(256);
-    if (D == 32) hipLaunchKernelGGL((fa_fwd_varlen_kernel<T, 32>), grid, block, 0, stream, p);
-    else if (D == 64) hipLaunchKernelGGL((fa_fwd_varlen_kernel<T, 64>), grid, block, 0, stream, p);
-    else if (D == 128) hipLaunchKernelGGL((fa_fwd_varlen_kernel<T, 128>), grid, block, 0, stream, p);
-    else return -1;
-    return (int)hipGetLastError();
-}
-
 }  // namespace
 
 // The grid rule: ceil(min(max_seqlen_q, Tq) * g / 128) blocks per (sequence, KV head); the kernel decodes (rank, sequence, KV head)
 // from the 1-D index, KV head fastest, rank r = the sequence's own block count - 1 - r.
 long long varlen_fwd_grid(const VarlenArgs& a) {
     if (a.Hkv <= 0 || a.max_seqlen_q <= 0 || a.Tq <= 0) return 0;
-    const long long n = a.max_seqlen_q < a.Tq ? a.max_seqlen_q : a.Tq;   // no sequence has more tokens than the batch
-    return (n * (a.Hq / a.Hkv) + kPQ - 1) / kPQ * a.Hkv * a.B;
+    return ((long long)varlen_max_sq(a) * (a.Hq / a.Hkv) + kPQ - 1) / kPQ * a.Hkv * a.B;
 }
 
 int launch_varlen_fwd(const VarlenArgs& a, hipStream_t stream) {
-    if (a.Hkv <= 0 || a.Hq % a.Hkv != 0 || a.causal < 0 || a.causal > 2) return -1;
-    if (a.q_token_stride < (long long)a.Hq * a.D || a.q_token_stride % 8 != 0) return -1;
-    if (a.k_token_stride < (long long)a.Hkv * a.D || a.k_token_stride % 8 != 0) return -1;
-    if (a.v_token_stride < (long long)a.Hkv * a.D || a.v_token_stride % 8 != 0) return -1;
+    if (!varlen_args_ok(a)) return -1;
     const long long nwg = varlen_fwd_grid(a);
     if (nwg <= 0) return 0;
     // the kernel counts packed rows in 32 bits
@@ -183,14 +169,15 @@ int launch_varlen_fwd(const VarlenArgs& a, hipStream_t stream) {
     p.cu_q = a.cu_seqlens_q; p.cu_k = a.cu_seqlens_k;
     p.q_stride = a.q_token_stride; p.k_stride = a.k_token_stride; p.v_stride = a.v_token_stride;
     p.Tq = a.Tq; p.Tk = a.Tk; p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.g = a.Hq / a.Hkv;
-    p.max_sq = a.max_seqlen_q < a.Tq ? a.max_seqlen_q : a.Tq;
-    p.max_sk = a.max_seqlen_k < a.Tk ? a.max_seqlen_k : a.Tk;
+    p.max_sq = varlen_max_sq(a);
+    p.max_sk = varlen_max_sk(a);
     p.c = a.scale * kLog2e;
     p.causal = a.causal;
     p.window = varlen_window(a);
-    if (a.dtype == kBF16) return launch_dim<Bf16Traits>(p, a.D, nwg, stream);
-    if (a.dtype == kF16) return launch_dim<F16Traits>(p, a.D, nwg, stream);
-    return -1;
+    return dispatch_tile_instance(a.dtype, a.D, [&](auto t, auto d) {
+        hipLaunchKernelGGL((fa_fwd_varlen_kernel<decltype(t), decltype(d)::value>), dim3((unsigned)nwg), dim3(256), 0, stream, p);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace aule_hip

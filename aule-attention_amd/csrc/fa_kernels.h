@@ -369,6 +369,10 @@ struct MlaPlan {
 MlaPlan mla_plan(const MlaArgs& a);   // all zero: nothing to launch; no pointer is read
 int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream);   // -1: unsupported arguments
 
+// The cut of a sequence's length every ragged entry applies (paged prefill, variable-length, MLA prefill): no sequence has more
+// tokens than the batch.
+inline int seqlen_cut(int max_seqlen, int total) { return max_seqlen < total ? max_seqlen : total; }
+
 // Variable-length packed batches (fa_fwd_varlen_gfx950.hip, fa_bwd_varlen_gfx950.hip): sequences of different lengths packed
 // along one token axis, forward and backward.
 //   q, out, dout, dq [Tq, Hq, D] and k, v, dk, dv [Tk, Hkv, D] 16-bit, lse / delta [Tq, Hq] fp32; the heads of a token contiguous,
@@ -400,12 +404,23 @@ struct VarlenArgs {
     int window;
     int dtype;
 };
+// The cuts the kernels and the grids run with
+inline int varlen_max_sq(const VarlenArgs& a) { return seqlen_cut(a.max_seqlen_q, a.Tq); }
+inline int varlen_max_sk(const VarlenArgs& a) { return seqlen_cut(a.max_seqlen_k, a.Tk); }
 // The window the kernels run with: 0 (off) for window <= 0 and for a window that masks nothing -- no position differs from a key by
 // min(max_seqlen_q, Tq) + min(max_seqlen_k, Tk) or more under any of the three causal modes -- so that "effectively off" values up to
 // INT32_MAX never enter the kernels' range arithmetic.  The one statement of the rule, for both launchers.
 inline int varlen_window(const VarlenArgs& a) {
-    const long long span = (long long)(a.max_seqlen_q < a.Tq ? a.max_seqlen_q : a.Tq) + (a.max_seqlen_k < a.Tk ? a.max_seqlen_k : a.Tk);
+    const long long span = (long long)varlen_max_sq(a) + varlen_max_sk(a);
     return a.window > 0 && a.window < span ? a.window : 0;
+}
+// What both launchers refuse: the head grouping, the causal mode, and token strides that overlap heads or break 16-byte rows.
+inline bool varlen_args_ok(const VarlenArgs& a) {
+    if (a.Hkv <= 0 || a.Hq % a.Hkv != 0 || a.causal < 0 || a.causal > 2) return false;
+    if (a.q_token_stride < (long long)a.Hq * a.D || a.q_token_stride % 8 != 0) return false;
+    if (a.k_token_stride < (long long)a.Hkv * a.D || a.k_token_stride % 8 != 0) return false;
+    if (a.v_token_stride < (long long)a.Hkv * a.D || a.v_token_stride % 8 != 0) return false;
+    return true;
 }
 // workgroups: forward and dQ ceil(min(max_seqlen_q, Tq) * (Hq / Hkv) / 128) x Hkv x B, dK/dV ceil(min(max_seqlen_k, Tk) / 128) x Hkv x B
 long long varlen_fwd_grid(const VarlenArgs& a);

@@ -1,11 +1,14 @@
 // fa_varlen_common.h -- what the variable-length kernels share (fa_fwd_varlen_gfx950.hip, fa_bwd_varlen_gfx950.hip):
 // the clamp of a sequence's bounds, the LDS pitches per head_dim, a tile of rows on its way from global memory to LDS, and the work
-// decomposition and K / V tile source of the forward and the dQ kernel (QueryBlock, KeyTiles).
+// decomposition and K / V tile source of the forward and the dQ kernel (QueryBlock, KeyTiles), and the dQ kernel's body
+// (ragged_dq_body), which the MLA 192 / 128 backward runs too.  The body is parameterised by a shape S: widths DQK (q / key rows)
+// and DV (value / output rows), the key-tile source S::Tiles(p, x, hk) with load(k0, tid) and store(Ks, kpitch, Vs, vpitch, tid),
+// and the head counts q_heads(p), kv_heads(p).
 // The layout is the plain one of fa_fwd_paged_prefill_gfx950.hip (tile sizes and pitches of fa_paged_tile.h) with a contiguous
 // tile source: row kv of a sequence's keys is row s_k + kv of k, k_token_stride elements from one token to the next.
 // Device code only.
 #pragma once
-#include "fa_paged_tile.h"
+#include "fa_tile_attention.h"
 
 namespace aule_hip {
 namespace {
@@ -138,7 +141,91 @@ struct KeyTiles {
         k.load([&](int row) { return k0 + row < kend ? kbase + (long long)(k0 + row) * kpitch : nullptr; }, tid);
         v.load([&](int row) { return k0 + row < kend ? vbase + (long long)(k0 + row) * vpitch : nullptr; }, tid);
     }
+    __device__ __forceinline__ void store(char* Ks, int kp, char* Vs, int vp, int tid) const {
+        k.store(Ks, kp, tid);
+        v.store(Vs, vp, tid);
+    }
 };
+
+// The shape of the variable-length kernels: q, k, v rows of D elements, the query heads of a KV head packed together
+template <int D>
+struct VarlenShape {
+    static constexpr int DQK = D, DV = D;
+    using Tiles = KeyTiles<D>;
+    template <class P>
+    static __device__ __forceinline__ int q_heads(const P& p) { return p.Hq; }
+    template <class P>
+    static __device__ __forceinline__ int kv_heads(const P& p) { return p.Hkv; }
+};
+
+// The dQ kernel: the forward's work decomposition and tile walk with Q and dO of the lane's row in registers; K tiles through Ks at
+// pitch VarlenCfg<DQK>::PAT (read as b128 rows AND transposed), V tiles through Vs at PrefillCfg<DV>::PA; S^T = K.Q^T,
+// dP^T = V.dO^T, dS^T = P^T (dP^T - delta) with P = exp2(S c - L log2 e) on visible keys only, dQ^T[d][q] += K^T.dS^T.
+// dq = scale * acc.  P supplies, beside the forward's, dout, lse, delta, dq and scale.
+template <class T, class S, class P>
+__device__ __forceinline__ void ragged_dq_body(const P& p, char* Ks, char* Vs) {
+    constexpr int GQ = S::DQK / 16, GV = S::DV / 16, DT = S::DQK / 32;
+    constexpr int KP = VarlenCfg<S::DQK>::PAT, VP = PrefillCfg<S::DV>::PA;
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bid = (int)blockIdx.x;
+    const int units = S::kv_heads(p) * p.B;
+    const int rank = bid / units, unit = bid - rank * units;
+    const int hk = unit % S::kv_heads(p), b = unit / S::kv_heads(p);
+
+    const QueryBlock x = query_block(p, rank, b, hk, wave, l31);
+    if (x.rows == 0) return;
+    const int ntiles = x.ntiles;
+
+    // Q and dO operand chunks of this lane's row, its lse (log2 units) and delta
+    const long long orow = ((long long)x.sq + x.tok) * S::q_heads(p) + x.head;
+    const char* qrow = p.q + (((long long)x.sq + x.tok) * p.q_stride + (long long)x.head * S::DQK) * 2;
+    const char* dorow = p.dout + orow * (long long)(S::DV * 2);
+    u32x4_t qf[GQ], of[GV];
+#pragma unroll
+    for (int g = 0; g < GQ; ++g) qf[g] = *reinterpret_cast<const u32x4_t*>(qrow + 32 * g + 16 * hi);
+#pragma unroll
+    for (int g = 0; g < GV; ++g) of[g] = *reinterpret_cast<const u32x4_t*>(dorow + 32 * g + 16 * hi);
+    const float l2 = p.lse[orow] * kLog2e;
+    const float dl = p.delta[orow];
+
+    f32x16_t acc[DT];
+#pragma unroll
+    for (int i = 0; i < DT; ++i) acc[i] = f32x16_t{};
+
+    typename S::Tiles kt(p, x, hk);
+    if (ntiles > 0) kt.load(x.kbeg, tid);
+    for (int t = 0; t < ntiles; ++t) {
+        const int k0 = x.kbeg + t * kPK;
+        __syncthreads();
+        kt.store(Ks, KP, Vs, VP, tid);
+        __syncthreads();
+        if (t + 1 < ntiles) kt.load(k0 + kPK, tid);
+        if (x.skips(k0)) continue;
+        // S^T[key][row] = K.Q^T, dP^T[key][row] = V.dO^T
+        f32x16_t s[2], dp[2];
+        tile_scores<T, GQ>(s, Ks, KP, qf, l31, hi);
+        tile_scores<T, GV>(dp, Vs, VP, of, l31, hi);
+        // dS^T = P^T (dP^T - delta), P^T = exp2(S^T c - L log2 e) on visible keys
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) {
+                const int j = k0 + 32 * kk + crow(rr, hi);
+                const float pr = x.visible(j) ? fast_exp2(s[kk][rr] * p.c - l2) : 0.f;
+                s[kk][rr] = pr * (dp[kk][rr] - dl);
+            }
+        // dQ^T[d][q] += K^T.dS^T
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            const u32x4_t bs = pack_step<T>(s[st >> 1], st & 1);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) acc[dt] = mfma16<T>(lds_tr_step(Ks, KP, 16 * st, 32 * dt, lane), bs, acc[dt]);
+        }
+    }
+    if (!x.live) return;
+    store_row16<T, DT>(p.dq + orow * (long long)(S::DQK * 2), acc, p.scale, hi);
+}
 
 }  // namespace
 }  // namespace aule_hip

@@ -15,7 +15,8 @@ from conftest import ROOT
 
 import aule
 from aule import _capi
-from test_mla_prefill_host import LAYOUT as FWD_LAYOUT, _resource_report
+from test_mla_prefill_host import LAYOUT as FWD_LAYOUT
+from util import resource_report
 
 CSRC = os.path.join(ROOT, "aule-attention_amd", "csrc")
 SRC = "fa_bwd_mla_prefill_gfx950.hip"
@@ -328,17 +329,21 @@ def test_build_rules_name_the_new_source():
     srcs = re.search(r"^SRCS := (.*)$", mk, re.M).group(1).split()
     assert SRC in srcs
     dep = re.search(r"^\$\(OBJDIR\)/fa_bwd_mla_prefill_gfx950\.o: (.*)$", mk, re.M).group(1).split()
-    assert {"fa_varlen_common.h", "fa_paged_tile.h", "fa_d256_common.h"} <= set(dep)
+    assert {"fa_mla_prefill_common.h", "fa_varlen_common.h", "fa_tile_attention.h", "fa_paged_tile.h", "fa_d256_common.h"} <= set(dep)
     src = open(os.path.join(CSRC, SRC)).read()
-    assert '#include "fa_varlen_common.h"' in src and "getenv" not in src and "fa_switches.h" not in src
-    assert "query_block(" in src and "seq_range(" in src and "RowTile<" in src and "atomicAdd" not in src and "__hip_atomic" not in src
+    assert '#include "fa_mla_prefill_common.h"' in src and "getenv" not in src and "fa_switches.h" not in src
+    body = open(os.path.join(CSRC, "fa_varlen_common.h")).read()
+    assert '#include "fa_varlen_common.h"' in src and "ragged_dq_body<" in src and "seq_range(" in src and "RowTile<" in src
+    assert "query_block(" in body[body.index("void ragged_dq_body("):]
+    for text in (src, body, open(os.path.join(CSRC, "fa_mla_prefill_common.h")).read(), open(os.path.join(CSRC, "fa_tile_attention.h")).read()):
+        assert "atomicAdd" not in text and "__hip_atomic" not in text
     assert "mla" not in open(os.path.join(CSRC, "fa_bwd_varlen_gfx950.hip")).read()
     assert "bwd" not in open(os.path.join(CSRC, "fa_fwd_mla_prefill_gfx950.hip")).read()
 
 
 def test_mla_backward_kernels_neither_spill_nor_use_scratch(tmp_path):
     """eight kernels (delta, dQ, dK/dV, reduce; fp16 and bf16): no scratch, no VGPR or SGPR spill, the LDS DESIGN.md 3.11 states"""
-    res = _resource_report(SRC, tmp_path)
+    res = resource_report(SRC, tmp_path)
     kinds = {"fa_bwd_mla_delta_kernel": 0, "fa_bwd_mla_dq_kernel": LDS_DQ, "fa_bwd_mla_dkdv_kernel": LDS_DKDV, "fa_bwd_mla_dkpe_reduce_kernel": 0}
     assert len(res) == 8, sorted(res)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()

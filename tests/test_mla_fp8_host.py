@@ -10,7 +10,7 @@ import re
 import pytest
 
 from conftest import ROOT
-from test_varlen_host import _resource_report
+from util import resource_report
 
 import aule
 from aule import _capi
@@ -431,7 +431,7 @@ def test_build_rule_names_the_new_sources():
 def test_fp8_attention_kernels_neither_spill_nor_use_scratch(tmp_path):
     """fp16 and bf16 of the FP8 attention kernel: no scratch, no VGPR or SGPR spill, the 16-bit kernel's 111 616 bytes of LDS; its name
     does not collide with the 16-bit kernel's, and the combine is not instantiated a second time"""
-    res = _resource_report("fa_fwd_mla_paged_fp8_gfx950.hip", tmp_path)
+    res = resource_report("fa_fwd_mla_paged_fp8_gfx950.hip", tmp_path)
     assert not [n for n in res if "fa_fwd_mla_paged_kernel" in n or "fa_mla_combine_kernel" in n], list(res)
     ks = [n for n in res if "fa_mla_fp8_latent_kernel" in n]
     assert len(ks) == 2 and sum("Bf16Traits" in n for n in ks) == 1 and sum("F16Traits" in n for n in ks) == 1, ks
@@ -445,7 +445,7 @@ def test_fp8_attention_kernels_neither_spill_nor_use_scratch(tmp_path):
 
 def test_append_kernels_neither_spill_nor_use_scratch_nor_lds(tmp_path):
     """fp16 / bf16 x 16-bit / FP8 cache x no rotation / half / interleaved: twelve instances, no scratch, no spill, no LDS"""
-    res = _resource_report("mla_kv_append_gfx950.hip", tmp_path)
+    res = resource_report("mla_kv_append_gfx950.hip", tmp_path)
     ks = [n for n in res if "mla_kv_append_kernel" in n]
     assert len(ks) == 12, ks
     for n in ks:

@@ -10,7 +10,7 @@ import re
 import pytest
 
 from conftest import ROOT
-from test_varlen_host import _resource_report
+from util import resource_report
 
 import aule
 from aule import _capi
@@ -294,7 +294,7 @@ def test_build_rule_names_the_new_source():
 def test_mla_kernels_neither_spill_nor_use_scratch(tmp_path):
     """fp16 and bf16 of the attention kernel and of the combine: no scratch, no VGPR or SGPR spill, LDS within a compute unit's 160 KiB
     (DESIGN.md 3.9 states the budget: 111 616 bytes)"""
-    res = _resource_report("fa_fwd_mla_paged_gfx950.hip", tmp_path)
+    res = resource_report("fa_fwd_mla_paged_gfx950.hip", tmp_path)
     for name in ("fa_fwd_mla_paged_kernel", "fa_mla_combine_kernel"):
         ks = [n for n in res if name in n]
         assert len(ks) == 2 and sum("Bf16Traits" in n for n in ks) == 1, (name, ks)

@@ -7,11 +7,11 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import pytest
 
 from conftest import ROOT
+from util import resource_report
 
 import aule
 from aule import _capi
@@ -286,44 +286,18 @@ def test_build_rules_name_the_new_source():
     srcs = re.search(r"^SRCS := (.*)$", mk, re.M).group(1).split()
     assert "fa_fwd_mla_prefill_gfx950.hip" in srcs
     dep = re.search(r"^\$\(OBJDIR\)/fa_fwd_mla_prefill_gfx950\.o: (.*)$", mk, re.M).group(1).split()
-    assert {"fa_varlen_common.h", "fa_paged_tile.h", "fa_d256_common.h"} <= set(dep)
+    assert {"fa_mla_prefill_common.h", "fa_varlen_common.h", "fa_tile_attention.h", "fa_paged_tile.h", "fa_d256_common.h"} <= set(dep)
     src = open(os.path.join(CSRC, "fa_fwd_mla_prefill_gfx950.hip")).read()
-    assert '#include "fa_varlen_common.h"' in src and "getenv" not in src and "fa_switches.h" not in src
-    assert "query_block(" in src and "RowTile<" in src and "x.visible(" in src
+    assert '#include "fa_mla_prefill_common.h"' in src and "getenv" not in src and "fa_switches.h" not in src
+    assert '#include "fa_varlen_common.h"' in src and "query_block(" in src and "x.visible(" in src
+    common = open(os.path.join(CSRC, "fa_mla_prefill_common.h")).read()      # the tile source the backward reads too
+    assert "MlaKeyTiles kt(" in src and "struct MlaKeyTiles" in common and "RowTile<" in common and "getenv" not in common
     assert "mla_prefill" not in open(os.path.join(CSRC, "fa_fwd_varlen_gfx950.hip")).read()
-
-
-def _makefile_compile_line():
-    """[compiler, flags ...] of the shipped objects (the mechanism of tests/test_varlen_host.py): HIPCC (the environment's, as make
-    takes it, else the Makefile's default) and the Makefile's CXXFLAGS with its ARCH"""
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    var = lambda name: re.search(r"^%s \?= (.*)$" % name, mk, re.M).group(1).strip()   # noqa: E731
-    flags = var("CXXFLAGS").replace("$(ARCH)", var("ARCH")).split()
-    assert "-O3" in flags and "--offload-arch=gfx950" in flags, flags
-    return [os.environ.get("HIPCC") or var("HIPCC")] + flags
-
-
-def _resource_report(src, tmp_path):
-    r = subprocess.run(_makefile_compile_line() + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-                                                   "-o", str(tmp_path / "k.o"), os.path.join(CSRC, src)],
-                       capture_output=True, text=True, timeout=900, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/lane\]| \[bytes/block\]| \[waves/SIMD\])?: (\d+)", line)
-        if m and cur is not None:
-            res[cur][m.group(1)] = int(m.group(2))
-    return res
 
 
 def test_mla_prefill_kernels_neither_spill_nor_use_scratch(tmp_path):
     """exactly two kernels (fp16, bf16): no scratch, no VGPR or SGPR spill, LDS = 46 080 bytes (DESIGN.md 3.10 states the budget)"""
-    res = _resource_report("fa_fwd_mla_prefill_gfx950.hip", tmp_path)
+    res = resource_report("fa_fwd_mla_prefill_gfx950.hip", tmp_path)
     ks = [n for n in res if "fa_fwd_mla_prefill_kernel" in n]
     assert len(res) == 2 and len(ks) == 2 and sum("Bf16Traits" in n for n in ks) == 1 and sum("F16Traits" in n for n in ks) == 1, sorted(res)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()

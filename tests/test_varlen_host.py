@@ -7,11 +7,11 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import pytest
 
 from conftest import ROOT
+from util import resource_report
 
 import aule
 from aule import _capi
@@ -319,37 +319,9 @@ def test_build_rules_name_the_new_sources():
     srcs = re.search(r"^SRCS := (.*)$", mk, re.M).group(1).split()
     assert "fa_fwd_varlen_gfx950.hip" in srcs and "fa_bwd_varlen_gfx950.hip" in srcs
     dep = re.search(r"^\$\(OBJDIR\)/fa_fwd_varlen_gfx950\.o \$\(OBJDIR\)/fa_bwd_varlen_gfx950\.o: (.*)$", mk, re.M).group(1).split()
-    assert {"fa_varlen_common.h", "fa_paged_tile.h", "fa_d256_common.h"} <= set(dep)
-    for f in ("fa_varlen_common.h", "fa_fwd_varlen_gfx950.hip", "fa_bwd_varlen_gfx950.hip"):
+    assert {"fa_varlen_common.h", "fa_tile_attention.h", "fa_paged_tile.h", "fa_d256_common.h"} <= set(dep)
+    for f in ("fa_varlen_common.h", "fa_tile_attention.h", "fa_fwd_varlen_gfx950.hip", "fa_bwd_varlen_gfx950.hip"):
         assert os.path.exists(os.path.join(CSRC, f))
-
-
-def _makefile_compile_line():
-    """[compiler, flags ...] of the shipped objects: HIPCC (the environment's, as make takes it, else the Makefile's default) and the
-    Makefile's CXXFLAGS with its ARCH"""
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    var = lambda name: re.search(r"^%s \?= (.*)$" % name, mk, re.M).group(1).strip()   # noqa: E731
-    flags = var("CXXFLAGS").replace("$(ARCH)", var("ARCH")).split()
-    assert "-O3" in flags and "--offload-arch=gfx950" in flags, flags
-    return [os.environ.get("HIPCC") or var("HIPCC")] + flags
-
-
-def _resource_report(src, tmp_path):
-    r = subprocess.run(_makefile_compile_line() + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-                                                   "-o", str(tmp_path / "k.o"), os.path.join(CSRC, src)],
-                       capture_output=True, text=True, timeout=900, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/lane\]| \[bytes/block\]| \[waves/SIMD\])?: (\d+)", line)
-        if m and cur is not None:
-            res[cur][m.group(1)] = int(m.group(2))
-    return res
 
 
 @pytest.mark.parametrize("src,kernels", [("fa_fwd_varlen_gfx950.hip", {"fa_fwd_varlen_kernel": 6}),
@@ -357,7 +329,7 @@ def _resource_report(src, tmp_path):
                                                                        "fa_bwd_varlen_dkdv_kernel": 6})], ids=["fwd", "bwd"])
 def test_varlen_kernels_neither_spill_nor_use_scratch(src, kernels, tmp_path):
     """fp16, bf16 x D 32, 64, 128 of every kernel: no scratch, no VGPR or SGPR spill, LDS below 45 KB (DESIGN.md 3.8 states the budget)"""
-    res = _resource_report(src, tmp_path)
+    res = resource_report(src, tmp_path)
     for name, count in kernels.items():
         ks = [n for n in res if name in n]
         assert len(ks) == count and sum("Bf16Traits" in n for n in ks) == count // 2, (name, ks)

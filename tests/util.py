@@ -1,5 +1,11 @@
-"""Shared helpers for the GPU parity tests."""
+"""Shared helpers for the GPU parity tests and for the host tests that compile a kernel file."""
+import os
+import re
+import subprocess
+
 import numpy as np
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "aule-attention_amd", "csrc")
 
 TORCH_DTYPES = {}
 
@@ -116,3 +122,32 @@ assert_switches(json.loads(sys.argv[2]))
 import pytest
 sys.exit(pytest.main(sys.argv[3:]))
 '''
+
+
+def makefile_compile_line():
+    """[compiler, flags ...] of the shipped objects: HIPCC (the environment's, as make takes it, else the Makefile's default) and the
+    Makefile's CXXFLAGS with its ARCH"""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    var = lambda name: re.search(r"^%s \?= (.*)$" % name, mk, re.M).group(1).strip()   # noqa: E731
+    flags = var("CXXFLAGS").replace("$(ARCH)", var("ARCH")).split()
+    assert "-O3" in flags and "--offload-arch=gfx950" in flags, flags
+    return [os.environ.get("HIPCC") or var("HIPCC")] + flags
+
+
+def resource_report(src, tmp_path):
+    """{kernel symbol: {resource: value}} of csrc/<src>, from the compiler's kernel-resource-usage remarks"""
+    r = subprocess.run(makefile_compile_line() + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
+                                                  "-o", str(tmp_path / "k.o"), os.path.join(CSRC, src)],
+                       capture_output=True, text=True, timeout=900, cwd=CSRC)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res, cur = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            cur = m.group(1)
+            res[cur] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/lane\]| \[bytes/block\]| \[waves/SIMD\])?: (\d+)", line)
+        if m and cur is not None:
+            res[cur][m.group(1)] = int(m.group(2))
+    return res
