@@ -369,6 +369,65 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
                 scale=scale, window_size=window_size, return_lse=return_lse)
 
 
+def flash_attention_varlen_sinks(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True,
+                                 scale=None, window_size=-1, return_lse=False):
+    """flash_attention_varlen for models with learned ATTENTION SINKS (gpt-oss and its derivatives): every query head carries one logit
+    that joins the softmax denominator and contributes no value.  Autograd-aware over q, k, v and sinks.  Not in the reference.
+
+        sinks [heads_q], fp32 or q's dtype, on q's device: a raw logit, multiplied by neither scale nor k_scale.  The kernels read it
+          on every launch (nothing copies it to the host: capturable, and a replay sees its current contents).
+        every other argument, check, stride rule and the head-dim padding as flash_attention_varlen.
+
+    For a query row of head h with visible keys j and scaled scores s_j:
+        Z = sum_j exp(s_j) + exp(sinks[h])      out = sum_j exp(s_j) v_j / Z      lse = ln Z
+    A row that sees no key gives out = 0 and lse = sinks[h].  sinks[h] = -inf means "no sink": that head's out and lse equal
+    flash_attention_varlen's bit for bit.  NaN or +inf logits give unspecified values for their head only.  The gradient of sinks
+    (in sinks' dtype) is -sum over the owned rows of exp(sinks[h] - lse) rowsum(dout * out): no atomics, the same bits on every run."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import flash_attention_varlen_sinks as impl
+    return impl(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k, causal=causal,
+                scale=scale, window_size=window_size, return_lse=return_lse)
+
+
+def flash_attention_paged_prefill_sinks(q, k_cache, v_cache, sinks, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None,
+                                        window_size=-1, k_scale=None, v_scale=None, return_lse=False):
+    """flash_attention_paged_prefill with per-head sink logits (flash_attention_varlen_sinks states the definition): sinks [heads_q], fp32
+    or q's dtype, on q's device; every other argument and rule as flash_attention_paged_prefill, k_scale of an FP8 cache in the
+    scores and not in the sink.  A token that sees no key gives zeros and lse = sinks[h]; sinks[h] = -inf equals the sinkless call
+    bit for bit.  Forward only."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_prefill
+    return paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=max_seqlen_q, scale=scale,
+                         window_size=window_size, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse, sinks=_required_sinks(sinks))
+
+
+def flash_attention_paged_query_sinks(q, k_cache, v_cache, sinks, block_tables, context_lens, scale=None, window_size=-1, k_scale=None,
+                                      v_scale=None, return_lse=False):
+    """flash_attention_paged_query with per-head sink logits (flash_attention_varlen_sinks states the definition): sinks [heads_q], fp32
+    or q's dtype, on q's device; every other argument and rule as flash_attention_paged_query.  seq_q = 1 is the decode step.  The
+    sink joins the merge of the key-range partials as one more partial.  A query that sees no key gives zeros and lse = sinks[h];
+    sinks[h] = -inf equals the sinkless call bit for bit.  Forward only."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_query
+    return paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=scale, window_size=window_size, k_scale=k_scale,
+                       v_scale=v_scale, return_lse=return_lse, sinks=_required_sinks(sinks))
+
+
+def _required_sinks(sinks):
+    if sinks is None:
+        raise ValueError("sinks must be a [heads_q] tensor (the sinkless call: flash_attention_paged_prefill / flash_attention_paged_query)")
+    return sinks
+
+
 def flash_attention_mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True,
                                 scale=None, return_lse=False):
     """MLA prefill: multi-head latent attention (DeepSeek-V2 / V3 / R1) in its NON-ABSORBED form, the form the prompt runs in, over
@@ -673,7 +732,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

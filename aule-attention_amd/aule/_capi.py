@@ -272,6 +272,28 @@ class VarlenBwdDesc(ctypes.Structure):
     ]
 
 
+# The sink kinds (attention sinks: include/aule.h): each is its twin field for field, then its own pointers.
+
+class VarlenSinkDesc(ctypes.Structure):
+    """struct aule_varlen_sink_desc (include/aule.h): aule_varlen_desc plus the [heads_q] fp32 sink logits."""
+    _fields_ = VarlenDesc._fields_ + [("sinks", ctypes.c_void_p)]
+
+
+class VarlenSinkBwdDesc(ctypes.Structure):
+    """struct aule_varlen_sink_bwd_desc (include/aule.h): aule_varlen_bwd_desc plus sinks and dsinks."""
+    _fields_ = VarlenBwdDesc._fields_ + [("sinks", ctypes.c_void_p), ("dsinks", ctypes.c_void_p)]
+
+
+class PagedPrefillSinkDesc(ctypes.Structure):
+    """struct aule_paged_prefill_sink_desc (include/aule.h): aule_paged_prefill_desc plus sinks."""
+    _fields_ = PagedPrefillDesc._fields_ + [("sinks", ctypes.c_void_p)]
+
+
+class PagedQuerySinkDesc(ctypes.Structure):
+    """struct aule_paged_query_sink_desc (include/aule.h): aule_paged_query_desc plus sinks."""
+    _fields_ = PagedQueryDesc._fields_ + [("sinks", ctypes.c_void_p)]
+
+
 class MergeStatesDesc(ctypes.Structure):
     """struct aule_merge_states_desc (include/aule.h): two attention states into one."""
     _fields_ = [
@@ -485,6 +507,12 @@ SIGNATURES = [
     ("aule_attention_varlen_forward_ex", _I32, [ctypes.POINTER(VarlenDesc)]),
     ("aule_attention_varlen_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),
     ("aule_attention_varlen_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenBwdDesc)]),
+    ("aule_attention_varlen_sink_forward_ex", _I32, [ctypes.POINTER(VarlenSinkDesc)]),
+    ("aule_attention_varlen_sink_backward_ex", _I32, [ctypes.POINTER(VarlenSinkBwdDesc)]),
+    ("aule_attention_varlen_sink_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenSinkBwdDesc)]),
+    ("aule_attention_paged_prefill_sink_ex", _I32, [ctypes.POINTER(PagedPrefillSinkDesc)]),
+    ("aule_attention_paged_query_sink_ex", _I32, [ctypes.POINTER(PagedQuerySinkDesc)]),
+    ("aule_attention_paged_query_sink_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedQuerySinkDesc)]),
     ("aule_attention_merge_states_ex", _I32, [ctypes.POINTER(MergeStatesDesc)]),
     ("aule_attention_mla_prefill_ex", _I32, [ctypes.POINTER(MlaPrefillDesc)]),
     ("aule_attention_mla_prefill_backward_ex", _I32, [ctypes.POINTER(MlaPrefillBwdDesc)]),

@@ -524,6 +524,26 @@ def _attach_scales(d, fp8, k_scale, v_scale, Hkv, device):
     return ks, vs
 
 
+def _sinks_check(sinks, q):
+    """The rules of the sink logits (attention sinks: aule.flash_attention_varlen_sinks documents them), none of which needs a device:
+    a [heads_q] tensor on q's device, fp32 or of q's dtype."""
+    Hq = q.shape[1]
+    if not torch.is_tensor(sinks) or sinks.shape != (Hq,):
+        raise ValueError(f"sinks must be a [heads_q] = [{Hq}] tensor, got "
+                         f"{tuple(sinks.shape) if torch.is_tensor(sinks) else type(sinks).__name__}")
+    if sinks.dtype not in (torch.float32, q.dtype):
+        raise ValueError(f"sinks must be float32 or of q's dtype ({q.dtype}), got {sinks.dtype}")
+    if sinks.device != q.device:
+        raise ValueError(f"sinks must be on q's device ({q.device}), got {sinks.device}: the kernels read it on every launch")
+
+
+def _sinks_f32(sinks):
+    """The logits as the kernels read them: fp32, contiguous (a differentiable conversion: the gradient comes back in sinks' dtype)."""
+    if sinks.dtype == torch.float32 and sinks.is_contiguous():
+        return sinks
+    return sinks.float().contiguous()
+
+
 def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1, k_scale=None, v_scale=None):
     """Paged-KV decode on the HIP backend; counterpart of flash_attention_paged_amd
     (python/aule/triton_flash_amd.py:656-737), same argument meaning:
@@ -571,7 +591,7 @@ PAGED_QUERY_MAX_TOKENS = 64   # packed rows of the wave-per-chunk kernel family 
 
 
 def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1, k_scale=None, v_scale=None,
-                return_lse=False):
+                return_lse=False, sinks=None):
     """Paged attention for a short multi-token query per sequence (speculative verify, multi-token heads, a short prompt
     tail against a cached prefix); the MQ instances of csrc/fa_fwd_splitkv_gfx950.hip behind aule_attention_paged_query_ex:
 
@@ -583,7 +603,7 @@ def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, win
     Returns out [batch, heads_q, seq_q, head_dim], or (out, lse) with lse [batch, heads_q, seq_q] fp32 -- the natural log
     of the sum of exp(scaled score) over the visible keys, -inf for a row that sees none -- when return_lse is set.  No
     device->host synchronisation; captures into a graph.  All argument errors are ValueErrors raised before the device is
-    touched."""
+    touched.  sinks: [heads_q] sink logits (aule.flash_attention_paged_query_sinks), behind aule_attention_paged_query_sink_ex."""
     Hkv = _paged_shapes(q, "B,Hq,Sq,D", k_cache, v_cache)
     B, Hq, Sq, _ = q.shape
     if not 1 <= Sq <= PAGED_QUERY_MAX_TOKENS:
@@ -592,6 +612,8 @@ def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, win
     fp8 = _paged_cache_kind("query", q, k_cache, v_cache, k_scale, v_scale)
     _paged_tables(block_tables, context_lens, B)
     _scale_shapes(fp8, Hkv, k_scale, v_scale)
+    if sinks is not None:
+        _sinks_check(sinks, q)
     _needs_device("query", q)
     lib = _capi.get_lib()
     q, k_cache, v_cache = q.contiguous(), k_cache.contiguous(), v_cache.contiguous()
@@ -601,12 +623,17 @@ def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, win
     lse = torch.empty((B, Hq, Sq), device=q.device, dtype=torch.float32) if return_lse else None
     if B * Hq == 0:
         return (out, lse) if return_lse else out
-    d = _paged_problem(_capi.PagedQueryDesc(), q, k_cache, v_cache, out, bt, cl, scale, fp8)
+    d = _paged_problem(_capi.PagedQueryDesc() if sinks is None else _capi.PagedQuerySinkDesc(), q, k_cache, v_cache, out, bt, cl, scale, fp8)
     d.seq_q, d.window_size = Sq, _window_arg(window_size)
     d.lse = lse.data_ptr() if lse is not None else None
-    held = (_attach_workspace(d, lib.aule_attention_paged_query_workspace_size, q.device),   # noqa: F841 (until the launch is queued)
-            _attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device))
-    _capi.check(lib.aule_attention_paged_query_ex(ctypes.byref(d)), "aule_attention_paged_query_ex")
+    size_query, launch = ("aule_attention_paged_query_workspace_size", "aule_attention_paged_query_ex") if sinks is None else \
+        ("aule_attention_paged_query_sink_workspace_size", "aule_attention_paged_query_sink_ex")
+    held = [_attach_workspace(d, getattr(lib, size_query), q.device),   # (until the launch is queued)
+            _attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device)]
+    if sinks is not None:
+        held.append(_sinks_f32(sinks))
+        d.sinks = held[-1].data_ptr()
+    _capi.check(getattr(lib, launch)(ctypes.byref(d)), launch)
     return (out, lse) if return_lse else out
 
 
@@ -695,9 +722,10 @@ def _varlen_problem(d, q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q, max_seqlen
     return d
 
 
-def varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1, want_lse=True):
+def varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1, want_lse=True, sinks=None):
     """q [Tq,Hq,D], k / v [Tk,Hkv,D] device tensors (heads contiguous, D in VARLEN_HEAD_DIMS), cu_q / cu_k int32 [B + 1] on the same
-    device, causal an AULE_CAUSAL_* code.  Returns (out, lse or None), both from torch.empty.  Asynchronous, no synchronisation."""
+    device, causal an AULE_CAUSAL_* code.  Returns (out, lse or None), both from torch.empty.  Asynchronous, no synchronisation.
+    sinks: [Hq] fp32 contiguous sink logits on the same device (aule_attention_varlen_sink_forward_ex), or None."""
     lib = _capi.get_lib()
     _same_device("variable-length attention", q, k, v, cu_q, cu_k)
     (q, sq), (k, sk), (v, sv) = _varlen_rows("q", q), _varlen_rows("k", k), _varlen_rows("v", v)
@@ -705,31 +733,43 @@ def varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scal
     lse = torch.empty(q.shape[:2], device=q.device, dtype=torch.float32) if want_lse else None
     if q.shape[0] * q.shape[1] * (cu_q.shape[0] - 1) == 0:
         return out, lse
-    d = _varlen_problem(_capi.VarlenDesc(), q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window)
+    d = _varlen_problem(_capi.VarlenDesc() if sinks is None else _capi.VarlenSinkDesc(), q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q,
+                        max_seqlen_k, causal, scale, window)
     d.out = out.data_ptr()
     d.lse = lse.data_ptr() if lse is not None else None
-    _capi.check(lib.aule_attention_varlen_forward_ex(ctypes.byref(d)), "aule_attention_varlen_forward_ex")
+    launch = "aule_attention_varlen_forward_ex"
+    if sinks is not None:
+        launch, d.sinks = "aule_attention_varlen_sink_forward_ex", sinks.data_ptr()
+    _capi.check(getattr(lib, launch)(ctypes.byref(d)), launch)
     return out, lse
 
 
-def varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1):
+def varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1, sinks=None):
     """The gradients of varlen_fwd_raw: dq [Tq,Hq,D], dk, dv [Tk,Hkv,D], contiguous and ZERO in the rows no sequence owns (the
-    library never writes those; they are allocated zero-filled here).  out, dout, lse contiguous.  Asynchronous, no synchronisation."""
+    library never writes those; they are allocated zero-filled here).  out, dout, lse contiguous.  Asynchronous, no synchronisation.
+    sinks (the forward's): returns (dq, dk, dv, dsinks [Hq] fp32) through aule_attention_varlen_sink_backward_ex."""
     lib = _capi.get_lib()
     _same_device("variable-length attention backward", q, k, v, out, dout, lse, cu_q, cu_k)
     (q, sq), (k, sk), (v, sv) = _varlen_rows("q", q), _varlen_rows("k", k), _varlen_rows("v", v)
     dq = torch.zeros(q.shape, device=q.device, dtype=q.dtype)
     dk = torch.zeros(k.shape, device=k.device, dtype=k.dtype)
     dv = torch.zeros(v.shape, device=v.device, dtype=v.dtype)
+    dsinks = None if sinks is None else torch.zeros(q.shape[1], device=q.device, dtype=torch.float32)
+    grads = (dq, dk, dv) if sinks is None else (dq, dk, dv, dsinks)
     if q.shape[1] * (cu_q.shape[0] - 1) == 0 or q.shape[0] + k.shape[0] == 0:
-        return dq, dk, dv
-    d = _varlen_problem(_capi.VarlenBwdDesc(), q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window)
+        return grads
+    d = _varlen_problem(_capi.VarlenBwdDesc() if sinks is None else _capi.VarlenSinkBwdDesc(), q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q,
+                        max_seqlen_k, causal, scale, window)
     d.out, d.lse, d.dout = out.data_ptr(), lse.data_ptr(), dout.data_ptr()
     d.dq, d.dk, d.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
-    ws = _attach_workspace(d, lib.aule_attention_varlen_backward_workspace_size, q.device)   # delta [Tq, Hq] fp32; held until the launch is queued
-    _capi.check(lib.aule_attention_varlen_backward_ex(ctypes.byref(d)), "aule_attention_varlen_backward_ex")
+    size_query, launch = "aule_attention_varlen_backward_workspace_size", "aule_attention_varlen_backward_ex"
+    if sinks is not None:
+        size_query, launch = "aule_attention_varlen_sink_backward_workspace_size", "aule_attention_varlen_sink_backward_ex"
+        d.sinks, d.dsinks = sinks.data_ptr(), dsinks.data_ptr()
+    ws = _attach_workspace(d, getattr(lib, size_query), q.device)   # delta [Tq, Hq] fp32 (and the dsinks partials); held until the launch is queued
+    _capi.check(getattr(lib, launch)(ctypes.byref(d)), launch)
     del ws
-    return dq, dk, dv
+    return grads
 
 
 class FlashAttentionVarlenHipFunc(torch.autograd.Function):
@@ -750,10 +790,48 @@ class FlashAttentionVarlenHipFunc(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None, None, None
 
 
+class FlashAttentionVarlenSinksHipFunc(torch.autograd.Function):
+    """FlashAttentionVarlenHipFunc with sink logits ([Hq] fp32, contiguous): the saved lse includes the sink, so dq, dk and dv are the
+    sinkless kernels' and dsinks is one reduction more."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, sinks, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window):
+        out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window, sinks=sinks)
+        ctx.save_for_backward(q, k, v, sinks, out, lse, cu_q, cu_k)
+        ctx.problem = (max_seqlen_q, max_seqlen_k, causal, scale, window)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, _dlse):
+        q, k, v, sinks, out, lse, cu_q, cu_k = ctx.saved_tensors
+        max_seqlen_q, max_seqlen_k, causal, scale, window = ctx.problem
+        dout = dout.contiguous().to(q.dtype)
+        dq, dk, dv, dsinks = varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window, sinks=sinks)
+        return dq, dk, dv, dsinks, None, None, None, None, None, None, None
+
+
+def flash_attention_varlen_sinks(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
+                                 window_size=-1, return_lse=False):
+    """flash_attention_varlen with per-head sink logits, autograd-aware over q, k, v and sinks (aule.flash_attention_varlen_sinks
+    documents the arguments)."""
+    return _varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, scale, window_size, return_lse, sinks)
+
+
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
                            window_size=-1, return_lse=False):
     """Attention over a variable-length packed batch, autograd-aware (aule.flash_attention_varlen documents the arguments)."""
+    return _varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, scale, window_size, return_lse)
+
+
+_NO_SINKS = object()
+
+
+def _varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, scale, window_size, return_lse, sinks=_NO_SINKS):
+    """The two calls above: one set of checks, stride rules and head-dim padding; with sinks the sink entries behind them."""
     _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    if sinks is not _NO_SINKS:
+        _sinks_check(sinks, q)
     code = causal_code(causal)
     D = q.shape[2]
     if scale is None:
@@ -770,10 +848,15 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     if Dp != D:   # zero-padded head dim: dot products and outputs are unchanged
         q, k, v = _pad_head_dim(q, Dp), _pad_head_dim(k, Dp), _pad_head_dim(v, Dp)
     window = _window_arg(window_size)
-    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        out, lse = FlashAttentionVarlenHipFunc.apply(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window)
+    sinks = None if sinks is _NO_SINKS else _sinks_f32(sinks)
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (sinks is not None and sinks.requires_grad)):
+        if sinks is None:
+            out, lse = FlashAttentionVarlenHipFunc.apply(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window)
+        else:
+            out, lse = FlashAttentionVarlenSinksHipFunc.apply(q, k, v, sinks, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window)
     else:
-        out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window, want_lse=return_lse)
+        out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window, want_lse=return_lse,
+                                  sinks=None if sinks is None else sinks.detach())
     if Dp != D:
         out = out[..., :D]
     return (out, lse) if return_lse else out
@@ -1019,7 +1102,7 @@ def _ragged_problem(op, d, q, q_stride, fp8, k_cache, v_cache, block_tables, con
 
 
 def paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None, window_size=-1,
-                  k_scale=None, v_scale=None, return_lse=False):
+                  k_scale=None, v_scale=None, return_lse=False, sinks=None):
     """Paged prefill: ragged per-sequence queries against the paged KV cache (the step of a continuous-batching engine: a
     prompt chunk behind a cached prefix next to a short verify next to plain decodes); csrc/fa_fwd_paged_prefill_gfx950.hip
     behind aule_attention_paged_prefill_ex:
@@ -1037,17 +1120,25 @@ def paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q,
     p = L_b - n_b + i and sees key j iff j <= p, and with window_size = W > 0 iff also p - j < W.  A token with p < 0 gives a
     row of zeros and lse = -inf.  Rows that belong to no sequence are never written: out (and lse) come from torch.empty.
     Returns out [total_tokens, heads_q, head_dim], or (out, lse) with lse [total_tokens, heads_q] fp32 when return_lse is
-    set.  All argument errors are ValueErrors raised before the device is touched."""
+    set.  All argument errors are ValueErrors raised before the device is touched.  sinks: [heads_q] sink logits
+    (aule.flash_attention_paged_prefill_sinks), behind aule_attention_paged_prefill_sink_ex."""
     Hkv, fp8 = _ragged_kind("prefill", q, k_cache, v_cache, k_scale, v_scale)
+    if sinks is not None:
+        _sinks_check(sinks, q)
     q, q_stride = _ragged_queries("prefill", q, fp8, Hkv, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, k_scale, v_scale)
     lib = _capi.get_lib()
-    d = _capi.PagedPrefillDesc()
+    d = _capi.PagedPrefillDesc() if sinks is None else _capi.PagedPrefillSinkDesc()
     result, held = _ragged_problem("prefill", d, q, q_stride, fp8, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q,
                                    scale, return_lse)
     if held is not None:
         d.window_size = _window_arg(window_size)
         held.append(_attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device))
-        _capi.check(lib.aule_attention_paged_prefill_ex(ctypes.byref(d)), "aule_attention_paged_prefill_ex")
+        launch = "aule_attention_paged_prefill_ex"
+        if sinks is not None:
+            launch = "aule_attention_paged_prefill_sink_ex"
+            held.append(_sinks_f32(sinks))
+            d.sinks = held[-1].data_ptr()
+        _capi.check(getattr(lib, launch)(ctypes.byref(d)), launch)
     return result
 
 

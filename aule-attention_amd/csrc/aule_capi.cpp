@@ -144,6 +144,50 @@ static_assert(AULE_VARLEN_SAME(dtype) && AULE_VARLEN_SAME(batch) && AULE_VARLEN_
                   AULE_VARLEN_SAME(q) && AULE_VARLEN_SAME(k) && AULE_VARLEN_SAME(v) && AULE_VARLEN_SAME(cu_seqlens_q) && AULE_VARLEN_SAME(cu_seqlens_k),
               "aule_varlen_bwd_desc states the problem in the fields of aule_varlen_desc, up to cu_seqlens_k: both are checked through that prefix");
 #undef AULE_VARLEN_SAME
+// The sink kinds: each repeats its twin field for field at the same offsets and appends its pointers, so it is checked and read through
+// the twin's type (the twin's own checker, with the sink kind's size).
+#define AULE_SINK_SAME(kind, twin, field) (offsetof(kind, field) == offsetof(twin, field))
+#define AULE_SINK_SAME_VARLEN(kind, twin)                                                                                                                   \
+    (AULE_SINK_SAME(kind, twin, dtype) && AULE_SINK_SAME(kind, twin, batch) && AULE_SINK_SAME(kind, twin, heads_q) && AULE_SINK_SAME(kind, twin, heads_kv) && \
+     AULE_SINK_SAME(kind, twin, head_dim) && AULE_SINK_SAME(kind, twin, total_q) && AULE_SINK_SAME(kind, twin, total_k) &&                                   \
+     AULE_SINK_SAME(kind, twin, max_seqlen_q) && AULE_SINK_SAME(kind, twin, max_seqlen_k) && AULE_SINK_SAME(kind, twin, scale) &&                            \
+     AULE_SINK_SAME(kind, twin, causal) && AULE_SINK_SAME(kind, twin, window_size) && AULE_SINK_SAME(kind, twin, device) &&                                  \
+     AULE_SINK_SAME(kind, twin, q_token_stride) && AULE_SINK_SAME(kind, twin, k_token_stride) && AULE_SINK_SAME(kind, twin, v_token_stride) &&               \
+     AULE_SINK_SAME(kind, twin, stream) && AULE_SINK_SAME(kind, twin, q) && AULE_SINK_SAME(kind, twin, k) && AULE_SINK_SAME(kind, twin, v) &&                \
+     AULE_SINK_SAME(kind, twin, cu_seqlens_q) && AULE_SINK_SAME(kind, twin, cu_seqlens_k) && AULE_SINK_SAME(kind, twin, out) && AULE_SINK_SAME(kind, twin, lse))
+static_assert(sizeof(aule_varlen_sink_desc) == 152 && offsetof(aule_varlen_sink_desc, sinks) == 144 && offsetof(aule_varlen_sink_desc, sinks) == sizeof(aule_varlen_desc) &&
+                  AULE_SINK_SAME_VARLEN(aule_varlen_sink_desc, aule_varlen_desc),
+              "aule_varlen_sink_desc is aule_varlen_desc plus sinks");
+static_assert(sizeof(aule_varlen_sink_bwd_desc) == 208 && offsetof(aule_varlen_sink_bwd_desc, sinks) == 192 && offsetof(aule_varlen_sink_bwd_desc, dsinks) == 200 &&
+                  offsetof(aule_varlen_sink_bwd_desc, sinks) == sizeof(aule_varlen_bwd_desc) && AULE_SINK_SAME_VARLEN(aule_varlen_sink_bwd_desc, aule_varlen_bwd_desc) &&
+                  AULE_SINK_SAME(aule_varlen_sink_bwd_desc, aule_varlen_bwd_desc, dout) && AULE_SINK_SAME(aule_varlen_sink_bwd_desc, aule_varlen_bwd_desc, dq) &&
+                  AULE_SINK_SAME(aule_varlen_sink_bwd_desc, aule_varlen_bwd_desc, dk) && AULE_SINK_SAME(aule_varlen_sink_bwd_desc, aule_varlen_bwd_desc, dv) &&
+                  AULE_SINK_SAME(aule_varlen_sink_bwd_desc, aule_varlen_bwd_desc, workspace) && AULE_SINK_SAME(aule_varlen_sink_bwd_desc, aule_varlen_bwd_desc, workspace_bytes),
+              "aule_varlen_sink_bwd_desc is aule_varlen_bwd_desc plus sinks and dsinks");
+#undef AULE_SINK_SAME_VARLEN
+#define AULE_PREFILL_SINK_SAME(field) AULE_SINK_SAME(aule_paged_prefill_sink_desc, aule_paged_prefill_desc, field)
+static_assert(sizeof(aule_paged_prefill_sink_desc) == 160 && offsetof(aule_paged_prefill_sink_desc, sinks) == 152 &&
+                  offsetof(aule_paged_prefill_sink_desc, sinks) == sizeof(aule_paged_prefill_desc) && AULE_PREFILL_SINK_SAME(dtype) && AULE_PREFILL_SINK_SAME(cache_dtype) &&
+                  AULE_PREFILL_SINK_SAME(batch) && AULE_PREFILL_SINK_SAME(heads_q) && AULE_PREFILL_SINK_SAME(heads_kv) && AULE_PREFILL_SINK_SAME(head_dim) &&
+                  AULE_PREFILL_SINK_SAME(block_size) && AULE_PREFILL_SINK_SAME(max_blocks) && AULE_PREFILL_SINK_SAME(total_tokens) && AULE_PREFILL_SINK_SAME(max_seqlen_q) &&
+                  AULE_PREFILL_SINK_SAME(scale) && AULE_PREFILL_SINK_SAME(window_size) && AULE_PREFILL_SINK_SAME(device) && AULE_PREFILL_SINK_SAME(q_token_stride) &&
+                  AULE_PREFILL_SINK_SAME(stream) && AULE_PREFILL_SINK_SAME(q) && AULE_PREFILL_SINK_SAME(k_cache) && AULE_PREFILL_SINK_SAME(v_cache) &&
+                  AULE_PREFILL_SINK_SAME(block_tables) && AULE_PREFILL_SINK_SAME(context_lens) && AULE_PREFILL_SINK_SAME(cu_seqlens_q) && AULE_PREFILL_SINK_SAME(out) &&
+                  AULE_PREFILL_SINK_SAME(lse) && AULE_PREFILL_SINK_SAME(k_scale) && AULE_PREFILL_SINK_SAME(v_scale),
+              "aule_paged_prefill_sink_desc is aule_paged_prefill_desc plus sinks");
+#undef AULE_PREFILL_SINK_SAME
+#define AULE_QUERY_SINK_SAME(field) AULE_SINK_SAME(aule_paged_query_sink_desc, aule_paged_query_desc, field)
+static_assert(sizeof(aule_paged_query_sink_desc) == 160 && offsetof(aule_paged_query_sink_desc, sinks) == 152 &&
+                  offsetof(aule_paged_query_sink_desc, sinks) == sizeof(aule_paged_query_desc) && AULE_QUERY_SINK_SAME(dtype) && AULE_QUERY_SINK_SAME(batch) &&
+                  AULE_QUERY_SINK_SAME(heads_q) && AULE_QUERY_SINK_SAME(heads_kv) && AULE_QUERY_SINK_SAME(head_dim) && AULE_QUERY_SINK_SAME(block_size) &&
+                  AULE_QUERY_SINK_SAME(max_blocks) && AULE_QUERY_SINK_SAME(scale) && AULE_QUERY_SINK_SAME(window_size) && AULE_QUERY_SINK_SAME(device) &&
+                  AULE_QUERY_SINK_SAME(stream) && AULE_QUERY_SINK_SAME(q) && AULE_QUERY_SINK_SAME(k_cache) && AULE_QUERY_SINK_SAME(v_cache) &&
+                  AULE_QUERY_SINK_SAME(block_tables) && AULE_QUERY_SINK_SAME(context_lens) && AULE_QUERY_SINK_SAME(out) && AULE_QUERY_SINK_SAME(workspace) &&
+                  AULE_QUERY_SINK_SAME(workspace_bytes) && AULE_QUERY_SINK_SAME(k_scale) && AULE_QUERY_SINK_SAME(v_scale) && AULE_QUERY_SINK_SAME(lse) &&
+                  AULE_QUERY_SINK_SAME(seq_q) && AULE_QUERY_SINK_SAME(cache_dtype),
+              "aule_paged_query_sink_desc is aule_paged_query_desc plus sinks");
+#undef AULE_QUERY_SINK_SAME
+#undef AULE_SINK_SAME
 static_assert(sizeof(aule_mla_prefill_desc) == 176 && offsetof(aule_mla_prefill_desc, dtype) == 4 && offsetof(aule_mla_prefill_desc, batch) == 8 &&
                   offsetof(aule_mla_prefill_desc, heads) == 12 && offsetof(aule_mla_prefill_desc, qk_dim) == 16 &&
                   offsetof(aule_mla_prefill_desc, v_dim) == 20 && offsetof(aule_mla_prefill_desc, total_q) == 24 &&
@@ -1174,8 +1218,9 @@ int32_t aule_attention_paged_decode_fp8_ex(const aule_paged_fp8_desc* d) {
 // size query reads no pointer).
 static bool paged_query_nothing_to_do(const aule_paged_query_desc* d) { return (uint64_t)d->batch * d->heads_q == 0; }
 
-static const char* paged_query_desc_error(const aule_paged_query_desc* d, bool launch, Reason& why) {
-    if (d == nullptr || d->struct_size != sizeof(aule_paged_query_desc)) return kBadDescriptor;
+// (`size`: the kind's own sizeof -- aule_paged_query_sink_desc is read through this type)
+static const char* paged_query_desc_error(const aule_paged_query_desc* d, bool launch, Reason& why, size_t size = sizeof(aule_paged_query_desc)) {
+    if (d == nullptr || d->struct_size != size) return kBadDescriptor;
     if (const char* e = paged_dtype_error(d)) return e;
     if (const char* e = paged_heads_error(d, why)) return e;
     if (d->seq_q == 0 || d->seq_q > 64) return reasonf(why, "seq_q %u unsupported (1 to 64 query tokens per sequence)", d->seq_q);
@@ -1209,11 +1254,41 @@ int32_t aule_attention_paged_query_ex(const aule_paged_query_desc* d) {
     return launched("Paged query attention", aule_hip::launch_paged_query(a, (hipStream_t)d->stream));
 }
 
+// The sink kinds (attention sinks: include/aule.h): each is its twin's descriptor plus pointers, checked by the twin's checker with its
+// own size and read through the twin's type (the layout asserts at the top of this file); a null sinks is refused once there is
+// something to do.  Host logic first: a refusal and a call with nothing to do are answered before the device is needed.
+static const char kNullSinks[] = "null sinks pointer (sinks is a [heads_q] fp32 device array; -inf entries mean no sink)";
+static const aule_paged_query_desc* query_prefix(const aule_paged_query_sink_desc* d) { return reinterpret_cast<const aule_paged_query_desc*>(d); }
+static const aule_paged_prefill_desc* prefill_sink_prefix(const aule_paged_prefill_sink_desc* d) { return reinterpret_cast<const aule_paged_prefill_desc*>(d); }
+
+int32_t aule_attention_paged_query_sink_ex(const aule_paged_query_sink_desc* d) {
+    RoctxRange range("aule.paged_query_sink");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    const aule_paged_query_desc* x = query_prefix(d);
+    const char* why = paged_query_desc_error(x, true, text, sizeof(aule_paged_query_sink_desc));
+    if (why == nullptr && !paged_query_nothing_to_do(x) && d->sinks == nullptr) why = kNullSinks;
+    if (why != nullptr) {
+        set_error("Paged query sink attention failed: %s", why);
+        return -3;
+    }
+    if (paged_query_nothing_to_do(x)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::PagedArgs a;
+    fill_paged_query_args(x, a);
+    a.sinks = d->sinks;
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    return launched("Paged query sink attention", aule_hip::launch_paged_query(a, (hipStream_t)d->stream));
+}
+
 // The paged prefill and the paged cascade: packed ragged queries, a descriptor family of its own.  `launch`: the pointer rules of a
 // call that has something to do as well (the cascade's size query and plan hook read no pointer).  Host logic only, and the launch
 // entries ask before they need the device.
-static const char* paged_prefill_desc_error(const aule_paged_prefill_desc* d, Reason& why) {
-    if (d == nullptr || d->struct_size != sizeof(aule_paged_prefill_desc)) return kBadDescriptor;
+// (`size`: the kind's own sizeof -- aule_paged_prefill_sink_desc is read through this type)
+static const char* paged_prefill_desc_error(const aule_paged_prefill_desc* d, Reason& why, size_t size = sizeof(aule_paged_prefill_desc)) {
+    if (d == nullptr || d->struct_size != size) return kBadDescriptor;
     if (const char* e = ragged_desc_error(d, why)) return e;
     if (const char* e = ragged_query_error(d, why)) return e;
     return ragged_nothing_to_do(d) ? nullptr : ragged_pointer_error(d, true);
@@ -1244,6 +1319,22 @@ static void fill_paged_prefill_args(const aule_paged_prefill_desc* d, aule_hip::
     }
 }
 
+// (`d` passed paged_prefill_desc_error with its kind's size; `sinks`: the sink kind's logits, checked by the caller)
+static int32_t paged_prefill_launch(const aule_paged_prefill_desc* d, const float* sinks, const char* what) {
+    if (!initialised()) return -1;
+    aule_hip::PagedPrefillArgs a;
+    fill_paged_prefill_args(d, a);
+    a.sinks = sinks;
+    if (aule_hip::paged_prefill_grid(a) > 0x7fffffffll) {
+        set_error("%s failed: the grid (blocks * heads_kv * batch) exceeds 2^31 - 1 workgroups", what);
+        return -3;
+    }
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    return launched(what, aule_hip::launch_paged_prefill(a, (hipStream_t)d->stream));
+}
+
 int32_t aule_attention_paged_prefill_ex(const aule_paged_prefill_desc* d) {
     RoctxRange range("aule.paged_prefill");
     std::lock_guard<std::mutex> lk(g_mu);
@@ -1253,17 +1344,22 @@ int32_t aule_attention_paged_prefill_ex(const aule_paged_prefill_desc* d) {
         return -3;
     }
     if (ragged_nothing_to_do(d)) return 0;
-    if (!initialised()) return -1;
-    aule_hip::PagedPrefillArgs a;
-    fill_paged_prefill_args(d, a);
-    if (aule_hip::paged_prefill_grid(a) > 0x7fffffffll) {
-        set_error("Paged prefill attention failed: the grid (blocks * heads_kv * batch) exceeds 2^31 - 1 workgroups");
+    return paged_prefill_launch(d, nullptr, "Paged prefill attention");
+}
+
+int32_t aule_attention_paged_prefill_sink_ex(const aule_paged_prefill_sink_desc* d) {
+    RoctxRange range("aule.paged_prefill_sink");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    const aule_paged_prefill_desc* x = prefill_sink_prefix(d);
+    const char* why = paged_prefill_desc_error(x, text, sizeof(aule_paged_prefill_sink_desc));
+    if (why == nullptr && !ragged_nothing_to_do(x) && d->sinks == nullptr) why = kNullSinks;
+    if (why != nullptr) {
+        set_error("Paged prefill sink attention failed: %s", why);
         return -3;
     }
-    DeviceGuard g(d->device);
-    int rc = ensure_configured();
-    if (rc) return rc;
-    return launched("Paged prefill attention", aule_hip::launch_paged_prefill(a, (hipStream_t)d->stream));
+    if (ragged_nothing_to_do(x)) return 0;
+    return paged_prefill_launch(x, d->sinks, "Paged prefill sink attention");
 }
 
 // (`d` passed paged_cascade_desc_error) the two kernels' arguments: the suffix pass is the prefill's, read through the common prefix,
@@ -1450,8 +1546,9 @@ static const char* varlen_input_error(const aule_varlen_desc* d) {
     return nullptr;
 }
 
-static const char* varlen_desc_error(const aule_varlen_desc* d, Reason& why) {
-    if (const char* e = varlen_problem_error(d, sizeof(aule_varlen_desc), why)) return e;
+// (`size`: the kind's own sizeof -- the sink kinds are read through their twins' types)
+static const char* varlen_desc_error(const aule_varlen_desc* d, Reason& why, size_t size = sizeof(aule_varlen_desc)) {
+    if (const char* e = varlen_problem_error(d, size, why)) return e;
     if (varlen_fwd_nothing_to_do(d)) return nullptr;
     if (const char* e = varlen_input_error(d)) return e;
     if (!d->out) return "null tensor pointer";
@@ -1461,9 +1558,10 @@ static const char* varlen_desc_error(const aule_varlen_desc* d, Reason& why) {
 
 static uint64_t varlen_bwd_workspace(const aule_varlen_desc* d) { return aule_hip::varlen_bwd_workspace_bytes(d->total_q, (int)d->heads_q); }
 
-static const char* varlen_bwd_desc_error(const aule_varlen_bwd_desc* d, bool launch, Reason& why) {
+// (`more`: the bytes the kind's workspace holds beyond delta)
+static const char* varlen_bwd_desc_error(const aule_varlen_bwd_desc* d, bool launch, Reason& why, size_t size = sizeof(aule_varlen_bwd_desc), uint64_t more = 0) {
     const aule_varlen_desc* x = varlen_prefix(d);
-    if (const char* e = varlen_problem_error(x, sizeof(aule_varlen_bwd_desc), why)) return e;
+    if (const char* e = varlen_problem_error(x, size, why)) return e;
     if (!launch || varlen_bwd_nothing_to_do(x)) return nullptr;
     if (const char* e = varlen_input_error(x)) return e;
     if (d->total_q > 0 && (!d->out || !d->lse || !d->dout || !d->dq)) return "null tensor pointer";
@@ -1471,8 +1569,8 @@ static const char* varlen_bwd_desc_error(const aule_varlen_bwd_desc* d, bool lau
     if (misaligned(d->out) || misaligned(d->dout) || misaligned(d->dq) || misaligned(d->dk) || misaligned(d->dv)) return "out, dout, dq, dk and dv must be 16-byte aligned";
     if (d->workspace != nullptr) {
         if (misaligned(d->workspace)) return "workspace must be 16-byte aligned";
-        if (d->workspace_bytes < varlen_bwd_workspace(x))
-            return reasonf(why, "workspace too small (%llu bytes, need %llu)", (unsigned long long)d->workspace_bytes, (unsigned long long)varlen_bwd_workspace(x));
+        if (d->workspace_bytes < varlen_bwd_workspace(x) + more)
+            return reasonf(why, "workspace too small (%llu bytes, need %llu)", (unsigned long long)d->workspace_bytes, (unsigned long long)(varlen_bwd_workspace(x) + more));
     }
     return nullptr;
 }
@@ -1491,6 +1589,22 @@ static void fill_varlen_args(const aule_varlen_desc* d, aule_hip::VarlenArgs& a)
     a.dtype = d->dtype;
 }
 
+// (`d` passed varlen_desc_error with its kind's size and has something to do; `sinks`: the sink kind's logits, checked by the caller)
+static int32_t varlen_forward_launch(const aule_varlen_desc* d, const float* sinks, const char* what) {
+    if (!initialised()) return -1;
+    aule_hip::VarlenArgs a;
+    fill_varlen_args(d, a);
+    a.out = d->out; a.lse = d->lse; a.sinks = sinks;
+    if (aule_hip::varlen_fwd_grid(a) > 0x7fffffffll) {
+        set_error("%s failed: the grid (blocks * heads_kv * batch) exceeds 2^31 - 1 workgroups", what);
+        return -3;
+    }
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    return launched(what, aule_hip::launch_varlen_fwd(a, (hipStream_t)d->stream));
+}
+
 int32_t aule_attention_varlen_forward_ex(const aule_varlen_desc* d) {
     RoctxRange range("aule.varlen_forward");
     std::lock_guard<std::mutex> lk(g_mu);
@@ -1500,18 +1614,57 @@ int32_t aule_attention_varlen_forward_ex(const aule_varlen_desc* d) {
         return -3;
     }
     if (varlen_fwd_nothing_to_do(d)) return 0;
+    return varlen_forward_launch(d, nullptr, "Variable-length attention");
+}
+
+int32_t aule_attention_varlen_sink_forward_ex(const aule_varlen_sink_desc* d) {
+    RoctxRange range("aule.varlen_sink_forward");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    const aule_varlen_desc* x = reinterpret_cast<const aule_varlen_desc*>(d);
+    const char* why = varlen_desc_error(x, text, sizeof(aule_varlen_sink_desc));
+    if (why == nullptr && !varlen_fwd_nothing_to_do(x) && d->sinks == nullptr) why = kNullSinks;
+    if (why != nullptr) {
+        set_error("Variable-length sink attention failed: %s", why);
+        return -3;
+    }
+    if (varlen_fwd_nothing_to_do(x)) return 0;
+    return varlen_forward_launch(x, d->sinks, "Variable-length sink attention");
+}
+
+// (`d` passed varlen_bwd_desc_error with its kind's size and has something to do; sinks / dsinks: the sink kind's, checked by the caller,
+// the partials of its reduction behind delta in the workspace)
+static int32_t varlen_backward_launch(const aule_varlen_bwd_desc* d, const float* sinks, float* dsinks, const char* what) {
+    const aule_varlen_desc* x = varlen_prefix(d);
     if (!initialised()) return -1;
     aule_hip::VarlenArgs a;
-    fill_varlen_args(d, a);
-    a.out = d->out; a.lse = d->lse;
-    if (aule_hip::varlen_fwd_grid(a) > 0x7fffffffll) {
-        set_error("Variable-length attention failed: the grid (blocks * heads_kv * batch) exceeds 2^31 - 1 workgroups");
+    fill_varlen_args(x, a);
+    a.o = d->out; a.lse = const_cast<float*>(d->lse); a.dout = d->dout;
+    a.dq = d->dq; a.dk = d->dk; a.dv = d->dv; a.sinks = sinks;
+    if (aule_hip::varlen_fwd_grid(a) > 0x7fffffffll || aule_hip::varlen_dkdv_grid(a) > 0x7fffffffll) {
+        set_error("%s failed: a grid exceeds 2^31 - 1 workgroups", what);
         return -3;
     }
     DeviceGuard g(d->device);
     int rc = ensure_configured();
     if (rc) return rc;
-    return launched("Variable-length attention", aule_hip::launch_varlen_fwd(a, (hipStream_t)d->stream));
+    hipStream_t stream = (hipStream_t)d->stream;
+    const uint64_t delta_bytes = varlen_bwd_workspace(x);
+    const uint64_t need = delta_bytes + (sinks ? aule_hip::varlen_dsinks_partial_bytes(a) : 0);
+    if (need == 0) {
+        rc = aule_hip::launch_varlen_bwd(a, stream);
+        if (rc == 0 && sinks) rc = aule_hip::launch_varlen_dsinks(a, dsinks, nullptr, stream);
+        return launched(what, rc);
+    }
+    aule_hip::ScopedWorkspace ws(need, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
+    if (ws.err != hipSuccess) {
+        set_error("%s failed: workspace allocation (%llu bytes): %s", what, (unsigned long long)need, hipGetErrorString(ws.err));
+        return -4;
+    }
+    a.delta = static_cast<float*>(ws.ptr);
+    rc = aule_hip::launch_varlen_bwd(a, stream);
+    if (rc == 0 && sinks) rc = aule_hip::launch_varlen_dsinks(a, dsinks, reinterpret_cast<float*>(static_cast<char*>(ws.ptr) + delta_bytes), stream);
+    return launched(what, rc);
 }
 
 int32_t aule_attention_varlen_backward_ex(const aule_varlen_bwd_desc* d) {
@@ -1522,36 +1675,51 @@ int32_t aule_attention_varlen_backward_ex(const aule_varlen_bwd_desc* d) {
         set_error("Variable-length backward failed: %s", why);
         return -3;
     }
-    const aule_varlen_desc* x = varlen_prefix(d);
-    if (varlen_bwd_nothing_to_do(x)) return 0;
-    if (!initialised()) return -1;
-    aule_hip::VarlenArgs a;
-    fill_varlen_args(x, a);
-    a.o = d->out; a.lse = const_cast<float*>(d->lse); a.dout = d->dout;
-    a.dq = d->dq; a.dk = d->dk; a.dv = d->dv;
-    if (aule_hip::varlen_fwd_grid(a) > 0x7fffffffll || aule_hip::varlen_dkdv_grid(a) > 0x7fffffffll) {
-        set_error("Variable-length backward failed: a grid exceeds 2^31 - 1 workgroups");
-        return -3;
-    }
-    DeviceGuard g(d->device);
-    int rc = ensure_configured();
-    if (rc) return rc;
-    hipStream_t stream = (hipStream_t)d->stream;
-    const uint64_t need = varlen_bwd_workspace(x);
-    if (need == 0) return launched("Variable-length backward", aule_hip::launch_varlen_bwd(a, stream));
-    aule_hip::ScopedWorkspace ws(need, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
-    if (ws.err != hipSuccess) {
-        set_error("Variable-length backward failed: workspace allocation (%llu bytes): %s", (unsigned long long)need, hipGetErrorString(ws.err));
-        return -4;
-    }
-    a.delta = static_cast<float*>(ws.ptr);
-    return launched("Variable-length backward", aule_hip::launch_varlen_bwd(a, stream));
+    if (varlen_bwd_nothing_to_do(varlen_prefix(d))) return 0;
+    return varlen_backward_launch(d, nullptr, nullptr, "Variable-length backward");
 }
 
 uint64_t aule_attention_varlen_backward_workspace_size(const aule_varlen_bwd_desc* d) {
     Reason text;
     if (varlen_bwd_desc_error(d, false, text)) return 0;
     return varlen_bwd_nothing_to_do(varlen_prefix(d)) ? 0 : varlen_bwd_workspace(varlen_prefix(d));
+}
+
+// the partials of the dsinks reduction for the problem `x` states (`x` passed varlen_problem_error)
+static uint64_t varlen_sink_partials(const aule_varlen_desc* x) {
+    aule_hip::VarlenArgs a;
+    fill_varlen_args(x, a);
+    return aule_hip::varlen_dsinks_partial_bytes(a);
+}
+
+static const char* varlen_sink_bwd_desc_error(const aule_varlen_sink_bwd_desc* d, bool launch, Reason& why) {
+    const aule_varlen_bwd_desc* y = reinterpret_cast<const aule_varlen_bwd_desc*>(d);
+    if (const char* e = varlen_problem_error(varlen_prefix(y), sizeof(aule_varlen_sink_bwd_desc), why)) return e;
+    if (const char* e = varlen_bwd_desc_error(y, launch, why, sizeof(aule_varlen_sink_bwd_desc), varlen_sink_partials(varlen_prefix(y)))) return e;
+    if (!launch || varlen_bwd_nothing_to_do(varlen_prefix(y))) return nullptr;
+    if (d->sinks == nullptr) return kNullSinks;
+    if (d->dsinks == nullptr) return "null dsinks pointer (dsinks is a [heads_q] fp32 device array)";
+    return nullptr;
+}
+
+int32_t aule_attention_varlen_sink_backward_ex(const aule_varlen_sink_bwd_desc* d) {
+    RoctxRange range("aule.varlen_sink_backward");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = varlen_sink_bwd_desc_error(d, true, text)) {
+        set_error("Variable-length sink backward failed: %s", why);
+        return -3;
+    }
+    const aule_varlen_bwd_desc* y = reinterpret_cast<const aule_varlen_bwd_desc*>(d);
+    if (varlen_bwd_nothing_to_do(varlen_prefix(y))) return 0;
+    return varlen_backward_launch(y, d->sinks, d->dsinks, "Variable-length sink backward");
+}
+
+uint64_t aule_attention_varlen_sink_backward_workspace_size(const aule_varlen_sink_bwd_desc* d) {
+    Reason text;
+    if (varlen_sink_bwd_desc_error(d, false, text)) return 0;
+    const aule_varlen_desc* x = varlen_prefix(reinterpret_cast<const aule_varlen_bwd_desc*>(d));
+    return varlen_bwd_nothing_to_do(x) ? 0 : varlen_bwd_workspace(x) + varlen_sink_partials(x);
 }
 
 // The MLA prefill (the non-absorbed 192 / 128 form over a packed batch): one checker, one reader (the launch entry).  Host logic
@@ -2051,6 +2219,16 @@ uint64_t aule_attention_paged_query_workspace_size(const aule_paged_query_desc* 
     if (paged_query_desc_error(d, false, text) || paged_query_nothing_to_do(d)) return 0;
     aule_hip::PagedArgs a;
     fill_paged_query_args(d, a);
+    return aule_hip::paged_workspace_bytes(a);
+}
+
+// (the sink is merged by the combine pass: the sinkless plan's bytes)
+uint64_t aule_attention_paged_query_sink_workspace_size(const aule_paged_query_sink_desc* d) {
+    Reason text;
+    const aule_paged_query_desc* x = query_prefix(d);
+    if (paged_query_desc_error(x, false, text, sizeof(aule_paged_query_sink_desc)) || paged_query_nothing_to_do(x)) return 0;
+    aule_hip::PagedArgs a;
+    fill_paged_query_args(x, a);
     return aule_hip::paged_workspace_bytes(a);
 }
 

@@ -18,7 +18,8 @@
 // power of two); rows at or beyond the block's last visible key are not read (zeros in LDS), table entries past them not touched.
 // FP8 caches: eight e4m3fn codes become one 16-byte chunk of q's 16-bit type on the way into LDS (exact), k_scale[hk] goes into the
 // log2-unit score factor and v_scale[hk] into the epilogue, so the MFMA loop is one family.
-// Online softmax in log2 units with fp32 m, l, acc; a row without a visible key writes O = 0 and LSE = -inf.
+// Online softmax in log2 units with fp32 m, l, acc; a row without a visible key writes O = 0 and LSE = -inf (PagedPrefillArgs::sinks
+// given: LSE = the head's sink logit).
 // One launch, no workspace: grid = ceil(max_seqlen_q g / 128) x Hkv x B, decoded as (rank, sequence, KV head) with rank 0 the
 // sequence's own last (heaviest) block; a workgroup whose rank is past the sequence's blocks leaves before it touches the table or
 // the caches.  The table is walked one tile ahead of the K / V loads, which are one tile ahead of the MFMAs.
@@ -39,6 +40,7 @@ struct PrefillParams {
     const int* cu;
     const float* k_scale;
     const float* v_scale;
+    const float* sinks;   // [Hq] fp32 sink logits or null
     long long q_stride;   // elements between tokens of q
     int T, B, Hq, Hkv, g;
     int bs, bs_shift;     // bs_shift >= 0: bs = 1 << bs_shift
@@ -182,6 +184,10 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_kernel(const Pref
     l += xhalf(l);
     if (!live) return;
     float inv = l > 0.f ? 1.f / l : 0.f;
+    // sink logits (a wave-uniform pointer; null: the line above is the whole story): the head's logit joins the denominator
+    const bool sink = p.sinks != nullptr;
+    float sink_lse = 0.f;
+    if (sink) sink_lse = sink_epilogue(p.sinks[head], m, l, inv);
     if constexpr (FP8) inv *= p.v_scale[hk];
     const long long orow = ((long long)s + tok) * p.Hq + head;
     char* og = p.o + orow * (long long)C::RB;
@@ -194,8 +200,12 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_kernel(const Pref
             *reinterpret_cast<u32x2_t*>(og + d * 2) = u32x2_t{T::pack2(a0, a1), T::pack2(a2, a3)};
         }
     if (p.lse != nullptr && hi == 0) {
-        const float mu = m == -__builtin_inff() ? 0.f : m;
-        p.lse[orow] = l > 0.f ? (mu + fast_log2(l)) * kLn2 : -__builtin_inff();
+        if (sink) {
+            p.lse[orow] = sink_lse;
+        } else {
+            const float mu = m == -__builtin_inff() ? 0.f : m;
+            p.lse[orow] = l > 0.f ? (mu + fast_log2(l)) * kLn2 : -__builtin_inff();
+        }
     }
 }
 
@@ -227,7 +237,7 @@ int launch_paged_prefill(const PagedPrefillArgs& a, hipStream_t stream) {
     p.q = static_cast<const char*>(a.q); p.k = static_cast<const char*>(a.k_cache); p.v = static_cast<const char*>(a.v_cache);
     p.o = static_cast<char*>(a.out); p.lse = a.lse;
     p.table = a.block_tables; p.ctx = a.context_lens; p.cu = a.cu_seqlens_q;
-    p.k_scale = a.k_scale; p.v_scale = a.v_scale;
+    p.k_scale = a.k_scale; p.v_scale = a.v_scale; p.sinks = a.sinks;
     p.q_stride = a.q_token_stride;
     p.T = a.T; p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.g = a.Hq / a.Hkv;
     p.bs = a.block_size;

@@ -60,6 +60,7 @@ struct SplitParams {
     int window;                // > 0: only the last `window` positions (context_len - 1 - pos < window; MQ: query position - pos < window)
     const float* k_scale;      // [Hkv] fp32, KvFp8 only
     const float* v_scale;
+    const float* sinks;        // the combine's SINK instances: [Hq] fp32 sink logits; null: the plain instances
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t skv_srd(const void* base, unsigned bytes) {
@@ -154,7 +155,9 @@ __global__ void __launch_bounds__(256) fa_fwd_paged_query_kernel(const SplitPara
 // One workgroup per packed row: log-sum-exp merge of the row's partials (there can be hundreds -- a serial loop per
 // thread made this kernel, not the split kernel, the bottleneck: 230 us for C5b), cast, LSE.  Threads are arranged as
 // G groups x D/4 column chunks; group j merges partials j, j+G, ...; the groups are then summed through LDS.
-template <class T, int D>
+// SINK: the head's sink logit is one more partial with m = sinks[head] log2 e, l = 1 and O = 0: it enters the maximum M and the sum;
+// a logit of -inf leaves M and the sum their bits, and a row whose partials hold no key gets lse = the logit itself.
+template <class T, int D, bool SINK>
 __global__ void __launch_bounds__(256) fa_fwd_splitkv_combine(const SplitParams p) {
     constexpr int C4 = D / 4, G = 256 / C4;
     __shared__ float red[256];
@@ -176,7 +179,13 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_combine(const SplitParams 
         if (tid < st) red[tid] = fmaxf(red[tid], red[tid + st]);
         __syncthreads();
     }
-    const float M = red[0];
+    const float Mk = red[0];   // of the keys
+    float M = Mk, s2 = -INFINITY, sink = -INFINITY;
+    if constexpr (SINK) {
+        sink = p.sinks[head];
+        s2 = sink * kLog2e;
+        M = fmaxf(Mk, s2);
+    }
     const int grp = tid / C4, c4 = tid % C4;
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
     float L = 0.f;
@@ -199,13 +208,17 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_combine(const SplitParams 
             t += *reinterpret_cast<const f32x4_t*>(&accs[j][4 * tid]);
             Lt += lsum[j];
         }
+        if constexpr (SINK) Lt += (M == -INFINITY) ? 0.f : fast_exp2(s2 - M);
         const float inv = Lt > 0.f ? 1.0f / Lt : 0.f;   // paged: a sequence with context_len 0 has no key -> O = 0
         const size_t orow = ((size_t)(b * p.Hq + head) * p.Sq + qi);
         u32x2_t u;
         u[0] = T::pack2(t[0] * inv, t[1] * inv);
         u[1] = T::pack2(t[2] * inv, t[3] * inv);
         *reinterpret_cast<u32x2_t*>(reinterpret_cast<char*>(p.o) + orow * (D * 2) + tid * 8) = u;
-        if (tid == 0 && p.lse != nullptr) p.lse[orow] = Lt > 0.f ? (M + fast_log2(Lt)) * kLn2 : -INFINITY;   // (a row that sees no key)
+        if (tid == 0 && p.lse != nullptr) {
+            if (SINK && Mk == -INFINITY) p.lse[orow] = sink;   // (no key: the logit itself)
+            else p.lse[orow] = Lt > 0.f ? (M + fast_log2(Lt)) * kLn2 : -INFINITY;   // (a row that sees no key)
+        }
     }
 }
 
@@ -214,8 +227,9 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_combine(const SplitParams 
 // M the row's maximum; wave reductions), then every lane accumulates its D/64 columns over the partials with w_i
 // broadcast from lane i.  The one-workgroup-per-row kernel above spends 256 threads and two block reductions on a row
 // with 4 partials: 26 us for B8 Hq32 Hkv8 Sq64 (34 MB, 1.3 TB/s) -- a quarter of that shape's time.  Used for <= 16
-// partials per row only: beyond that the serial walk over the partials is slower than the kernel above.
-template <class T, int D>
+// partials per row only: beyond that the serial walk over the partials is slower than the kernel above.  SINK: as above, the sink
+// merged after the last trip.
+template <class T, int D, bool SINK>
 __global__ void __launch_bounds__(256) fa_fwd_splitkv_combine_rows(const SplitParams p) {
     constexpr int CPL = (D + 63) / 64;            // columns per lane (D = 32: lanes 32..63 carry no column)
     const int lane = threadIdx.x & 63;
@@ -258,6 +272,18 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_combine_rows(const SplitPa
             }
         }
     }
+    const bool no_key = M == -INFINITY;
+    float sink = -INFINITY;
+    if constexpr (SINK) {
+        sink = p.sinks[head];
+        const float s2 = sink * kLog2e;
+        const float Mn = fmaxf(M, s2);
+        const float rescale = (M == -INFINITY) ? 0.f : fast_exp2(M - Mn);   // s2 = -inf: exactly 1
+        L = L * rescale + ((Mn == -INFINITY) ? 0.f : fast_exp2(s2 - Mn));
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) acc[c] *= rescale;
+        M = Mn;
+    }
     const float inv = L > 0.f ? 1.0f / L : 0.f;
     const size_t orow = ((size_t)(b * p.Hq + head) * p.Sq + qi);
     if (has_col) {
@@ -268,7 +294,10 @@ __global__ void __launch_bounds__(256) fa_fwd_splitkv_combine_rows(const SplitPa
             reinterpret_cast<unsigned short*>(p.o)[orow * D + lane] = (unsigned short)(u & 0xffffu);
         }
     }
-    if (lane == 0 && p.lse != nullptr) p.lse[orow] = L > 0.f ? (M + fast_log2(L)) * kLn2 : -INFINITY;
+    if (lane == 0 && p.lse != nullptr) {
+        if (SINK && no_key) p.lse[orow] = sink;   // (no key: the logit itself)
+        else p.lse[orow] = L > 0.f ? (M + fast_log2(L)) * kLn2 : -INFINITY;
+    }
 }
 
 // ---- host side ----
@@ -294,10 +323,15 @@ int for_dtype_d(int dtype, int D, F&& f) {
 template <class T, int D>
 int launch_combine(const SplitParams& p, bool by_count, hipStream_t stream) {
     // (AULE_HIP_FWD_COMBINE=wg selects the workgroup-per-row kernel: A/B measurements)
-    if (by_count && !switches().fwd_combine_wg && p.npart <= 16)
-        hipLaunchKernelGGL((fa_fwd_splitkv_combine_rows<T, D>), dim3((unsigned)((p.rows_total + 3) / 4)), dim3(256), 0, stream, p);
-    else
-        hipLaunchKernelGGL((fa_fwd_splitkv_combine<T, D>), dim3((unsigned)p.rows_total), dim3(256), 0, stream, p);
+    const bool rows = by_count && !switches().fwd_combine_wg && p.npart <= 16;
+    const dim3 grid(rows ? (unsigned)((p.rows_total + 3) / 4) : (unsigned)p.rows_total);
+    if (p.sinks != nullptr) {   // (the paged query with sink logits)
+        if (rows) hipLaunchKernelGGL((fa_fwd_splitkv_combine_rows<T, D, true>), grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((fa_fwd_splitkv_combine<T, D, true>), grid, dim3(256), 0, stream, p);
+    } else {
+        if (rows) hipLaunchKernelGGL((fa_fwd_splitkv_combine_rows<T, D, false>), grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((fa_fwd_splitkv_combine<T, D, false>), grid, dim3(256), 0, stream, p);
+    }
     return (int)hipGetLastError();
 }
 
@@ -347,6 +381,7 @@ int launch_paged(const PagedArgs& a, hipStream_t stream) {
     p.block_tables = a.block_tables; p.context_lens = a.context_lens;
     p.block_size = a.block_size; p.max_blocks = a.max_blocks; p.window = a.window > 0 ? a.window : 0;
     p.k_scale = a.k_scale; p.v_scale = a.v_scale;
+    p.sinks = MQ ? a.sinks : nullptr;
     // The two cache kinds differ in two places beyond the data format.  Both differences reach the results (the last
     // bits, or which kernel runs), so each is kept as it was introduced; making them one is a change of its own.
     //  * scale (KV::kSignInQ): the 16-bit cache takes the contiguous kernel's convention (set_abs_scale); the FP8 cache

@@ -14,7 +14,8 @@
 //   registers while this one is computed; a wave skips a tile none of its rows sees and runs unmasked where every row sees all of it.
 // Key row kv of the sequence is at byte ((s_k + kv) k_token_stride + hk D) 2 of k (64-bit); rows at or beyond the block's last
 // visible key are not read (zeros in LDS).  Online softmax in log2 units with fp32 m, l, acc; a row without a visible key writes
-// O = 0 and LSE = -inf.  One launch, no workspace: grid = ceil(min(max_seqlen_q, Tq) g / 128) x Hkv x B.
+// O = 0 and LSE = -inf (VarlenArgs::sinks given: LSE = the head's sink logit).  One launch, no workspace:
+// grid = ceil(min(max_seqlen_q, Tq) g / 128) x Hkv x B.
 #include "fa_kernels.h"
 #include "fa_varlen_common.h"
 
@@ -29,6 +30,7 @@ struct VarlenFwdParams {
     float* lse;
     const int* cu_q;
     const int* cu_k;
+    const float* sinks;   // [Hq] fp32 sink logits or null
     long long q_stride, k_stride, v_stride;   // elements between tokens
     int Tq, Tk, B, Hq, Hkv, g;
     int max_sq, max_sk;
@@ -131,7 +133,11 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_varlen_kernel(const VarlenFwdPa
     }
     l += xhalf(l);
     if (!x.live) return;
-    const float inv = l > 0.f ? 1.f / l : 0.f;
+    float inv = l > 0.f ? 1.f / l : 0.f;
+    // sink logits (a wave-uniform pointer; null: the line above is the whole story): the head's logit joins the denominator
+    const bool sink = p.sinks != nullptr;
+    float sink_lse = 0.f;
+    if (sink) sink_lse = sink_epilogue(p.sinks[x.head], m, l, inv);
     const long long orow = ((long long)x.sq + x.tok) * p.Hq + x.head;
     char* og = p.o + orow * (long long)C::RB;
 #pragma unroll
@@ -143,8 +149,12 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_varlen_kernel(const VarlenFwdPa
             *reinterpret_cast<u32x2_t*>(og + d * 2) = u32x2_t{T::pack2(a0, a1), T::pack2(a2, a3)};
         }
     if (p.lse != nullptr && hi == 0) {
-        const float mu = m == -__builtin_inff() ? 0.f : m;
-        p.lse[orow] = l > 0.f ? (mu + fast_log2(l)) * kLn2 : -__builtin_inff();
+        if (sink) {
+            p.lse[orow] = sink_lse;
+        } else {
+            const float mu = m == -__builtin_inff() ? 0.f : m;
+            p.lse[orow] = l > 0.f ? (mu + fast_log2(l)) * kLn2 : -__builtin_inff();
+        }
     }
 }
 
@@ -166,7 +176,7 @@ int launch_varlen_fwd(const VarlenArgs& a, hipStream_t stream) {
     VarlenFwdParams p;
     p.q = static_cast<const char*>(a.q); p.k = static_cast<const char*>(a.k); p.v = static_cast<const char*>(a.v);
     p.o = static_cast<char*>(a.out); p.lse = a.lse;
-    p.cu_q = a.cu_seqlens_q; p.cu_k = a.cu_seqlens_k;
+    p.cu_q = a.cu_seqlens_q; p.cu_k = a.cu_seqlens_k; p.sinks = a.sinks;
     p.q_stride = a.q_token_stride; p.k_stride = a.k_token_stride; p.v_stride = a.v_token_stride;
     p.Tq = a.Tq; p.Tk = a.Tk; p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.g = a.Hq / a.Hkv;
     p.max_sq = varlen_max_sq(a);

@@ -158,6 +158,9 @@ struct PagedArgs {
     // measured from there); a query at a negative position gives zeros.  lse [B, Hq, Sq] fp32 or null (-inf where no key is seen)
     int Sq = 1;
     float* lse = nullptr;
+    // launch_paged_query only: per-head sink logits [Hq] fp32 on the device, or null -- a raw logit (not scaled) that
+    // joins the softmax denominator and carries no value; a row that sees no key then gives out = 0 and lse = sinks[head]
+    const float* sinks = nullptr;
 };
 
 // Rotary embedding pass (rope_gfx950.hip): x [nheads, S, D] with `pitch` elements per row, tables [>= S + pos_offset, D/2]
@@ -255,6 +258,7 @@ struct PagedPrefillArgs {
     int cache_kind = kCache16;
     const float* k_scale = nullptr;     // kCacheFp8E4M3 only
     const float* v_scale = nullptr;
+    const float* sinks = nullptr;       // [Hq] fp32 sink logits or null, as PagedArgs::sinks
 };
 // workgroups of the launch: ceil(min(max_seqlen_q, T) * (Hq / Hkv) / 128) x Hkv x B (tests, tools)
 long long paged_prefill_grid(const PagedPrefillArgs& a);
@@ -403,6 +407,7 @@ struct VarlenArgs {
     int causal;                   // 0 none, 1 top-left, 2 bottom-right
     int window;
     int dtype;
+    const float* sinks = nullptr; // [Hq] fp32 sink logits or null, as PagedArgs::sinks: the forward's epilogue and launch_varlen_dsinks
 };
 // The cuts the kernels and the grids run with
 inline int varlen_max_sq(const VarlenArgs& a) { return seqlen_cut(a.max_seqlen_q, a.Tq); }
@@ -428,6 +433,11 @@ long long varlen_dkdv_grid(const VarlenArgs& a);
 uint64_t varlen_bwd_workspace_bytes(long long Tq, int Hq);   // delta
 int launch_varlen_fwd(const VarlenArgs& a, hipStream_t stream);   // -1: unsupported arguments
 int launch_varlen_bwd(const VarlenArgs& a, hipStream_t stream);   // delta, dQ, dK/dV on `stream`
+// The gradient of the sink logits (fa_bwd_sinks_gfx950.hip), after launch_varlen_bwd on the same stream: reads a.lse (the forward's, sinks
+// included), a.delta (that launch's workspace), a.sinks and a.cu_seqlens_q over the owned rows only; two launches, no atomics, a fixed
+// summation order; `partials` is varlen_dsinks_partial_bytes(a) bytes of workspace; exactly Hq floats of dsinks are written.
+uint64_t varlen_dsinks_partial_bytes(const VarlenArgs& a);
+int launch_varlen_dsinks(const VarlenArgs& a, float* dsinks, float* partials, hipStream_t stream);   // -1: unsupported arguments
 
 // MLA prefill, the non-absorbed form (fa_fwd_mla_prefill_gfx950.hip): ragged 192 / 128 attention over a packed batch, forward only.
 //   q [Tq, H, 192] with its token stride, k_nope and v [Tk, H, 128] each with a token AND a head stride, k_pe [Tk, 64] with its

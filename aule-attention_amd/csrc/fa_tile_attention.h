@@ -37,6 +37,21 @@ __device__ __forceinline__ void store_row16(char* dst, const f32x16_t (&a)[DT], 
         }
 }
 
+// The epilogue of a forward with attention sinks: the row's state (m in log2 units, l) and its head's sink logit -- raw,
+// natural units, a term of the denominator that carries no value -> the factor `inv` of the accumulators; returns lse = ln Z.
+// sink = -inf ("no sink"): a is exactly 1 and ls exactly l, so inv and the lse are the sinkless epilogue's bits.  A row without a
+// visible key (m = -inf): inv = 0 and lse = the logit itself, not its round trip through log2 units.
+__device__ __forceinline__ float sink_epilogue(float sink, float m, float l, float& inv) {
+    const float s2 = sink * kLog2e;
+    const float mn = fmaxf(m, s2);
+    const float top = mn == -__builtin_inff() ? 0.f : mn;
+    const float a = fast_exp2(m - top);   // m = -inf: 0
+    const float ls = l * a + fast_exp2(s2 - top);
+    inv = a * (ls > 0.f ? 1.f / ls : 0.f);
+    if (m == -__builtin_inff()) return sink;
+    return ls > 0.f ? (top + fast_log2(ls)) * kLn2 : -__builtin_inff();
+}
+
 // Host: the kernel instance for (dtype, head_dim in {32, 64, 128}): f(T{}, std::integral_constant<int, D>{}), -1 for anything else
 template <class F>
 int dispatch_tile_instance(int dtype, int D, F&& f) {

@@ -585,6 +585,147 @@ int32_t aule_attention_varlen_backward_ex(const aule_varlen_bwd_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses. */
 uint64_t aule_attention_varlen_backward_workspace_size(const aule_varlen_bwd_desc* desc);
 
+/* ATTENTION SINKS (additive): per-head sink logits for the variable-length, paged-prefill and paged-query entries above -- the    */
+/* models whose heads each carry a learned logit that joins the softmax denominator and contributes no value (gpt-oss and its      */
+/* derivatives).  sinks is [heads_q] fp32 on the DEVICE: a raw logit, multiplied by neither scale nor k_scale; the kernels read it   */
+/* on every launch and nothing copies it to the host, so a captured call replays with its CURRENT contents.  For a query row of     */
+/* head h with visible keys j and scaled scores s_j (scale, and k_scale of an FP8 cache, included):                                 */
+/*     Z = sum_j exp(s_j) + exp(sinks[h])        out = sum_j exp(s_j) v_j / Z        lse = ln Z                                     */
+/* Visibility, clamps, owned rows, alignment, workspaces and every other rule are EXACTLY those of the sinkless twin each           */
+/* descriptor repeats field for field at the same offsets (the new pointers are appended; the descriptors are checked through that  */
+/* prefix).  A row that sees no key gives out = 0 and lse = sinks[h] (the twin: -inf).  sinks[h] = -inf means "no sink": out and    */
+/* lse of that head equal the twin's bit for bit, a row without a key included (0 and -inf).  A NaN or +inf logit gives unspecified */
+/* values for that head only; a logit never takes part in an address.                                                               */
+/* Backward (variable-length): dq, dk and dv come from the kernels of aule_attention_varlen_backward_ex given the sink-inclusive    */
+/* lse; dsinks [heads_q] fp32 is  dsinks[h] = - sum over the rows some sequence owns of exp(sinks[h] - lse[row, h]) delta[row, h],  */
+/* delta = rowsum(dout * out): two more launches, no atomics, a fixed summation order (two runs agree bit for bit), exactly         */
+/* heads_q floats written; 0 for a head with sinks[h] = -inf.  The workspace is the sinkless backward's plus the reduction's        */
+/* partials.  A call with nothing to do (the twin's rule) returns 0 and leaves dsinks unwritten.                                    */
+/* A NULL sinks (or dsinks) is refused with -3 and a reason; refusals and calls with nothing to do are answered without aule_init() */
+/* (aule_attention_paged_query_sink_ex: refusals of a NULL sinks and of the descriptor's shape).  seq_q = 1 in the query entry is   */
+/* the decode call.  Not built: sinks for the dense aule_attention_forward_ex, the cascade, the MLA entries, head_dim 256.          */
+typedef struct aule_varlen_sink_desc {
+    uint32_t struct_size;      /* = sizeof(aule_varlen_sink_desc) = 152 */
+    int32_t dtype;
+    uint32_t batch;
+    uint32_t heads_q, heads_kv, head_dim;
+    uint32_t total_q;
+    uint32_t total_k;
+    uint32_t max_seqlen_q;
+    uint32_t max_seqlen_k;
+    float scale;
+    int32_t causal;
+    int32_t window_size;
+    int32_t device;
+    int64_t q_token_stride;
+    int64_t k_token_stride;
+    int64_t v_token_stride;
+    void* stream;              /* offset 80 */
+    const void* q;
+    const void* k;
+    const void* v;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k;   /* offset 120 */
+    void* out;                 /* offset 128 */
+    float* lse;                /* offset 136; optional (NULL to skip): ln Z, the sink included */
+    const float* sinks;        /* offset 144; [heads_q] fp32, device (required) */
+} aule_varlen_sink_desc;
+typedef struct aule_varlen_sink_bwd_desc {
+    uint32_t struct_size;      /* = sizeof(aule_varlen_sink_bwd_desc) = 208 */
+    int32_t dtype;
+    uint32_t batch;
+    uint32_t heads_q, heads_kv, head_dim;
+    uint32_t total_q;
+    uint32_t total_k;
+    uint32_t max_seqlen_q;
+    uint32_t max_seqlen_k;
+    float scale;
+    int32_t causal;
+    int32_t window_size;
+    int32_t device;
+    int64_t q_token_stride;
+    int64_t k_token_stride;
+    int64_t v_token_stride;
+    void* stream;              /* offset 80 */
+    const void* q;
+    const void* k;
+    const void* v;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k;   /* offset 120 */
+    const void* out;           /* offset 128; the sink forward's out */
+    const float* lse;          /* offset 136; the sink forward's lse (required) */
+    const void* dout;          /* offset 144 */
+    void* dq;                  /* offset 152 */
+    void* dk;                  /* offset 160 */
+    void* dv;                  /* offset 168 */
+    void* workspace;           /* offset 176; optional, size from aule_attention_varlen_sink_backward_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 184 */
+    const float* sinks;        /* offset 192; [heads_q] fp32, device (required) */
+    float* dsinks;             /* offset 200; [heads_q] fp32, device (required): written */
+} aule_varlen_sink_bwd_desc;
+typedef struct aule_paged_prefill_sink_desc {
+    uint32_t struct_size;      /* = sizeof(aule_paged_prefill_sink_desc) = 160 */
+    int32_t dtype;
+    int32_t cache_dtype;       /* offset 8 */
+    uint32_t batch;            /* offset 12 */
+    uint32_t heads_q, heads_kv, head_dim;
+    uint32_t block_size;       /* offset 28 */
+    uint32_t max_blocks;       /* offset 32 */
+    uint32_t total_tokens;     /* offset 36 */
+    uint32_t max_seqlen_q;     /* offset 40 */
+    float scale;               /* offset 44 */
+    int32_t window_size;       /* offset 48 */
+    int32_t device;            /* offset 52 */
+    int64_t q_token_stride;    /* offset 56 */
+    void* stream;              /* offset 64 */
+    const void* q;             /* offset 72 */
+    const void* k_cache;       /* offset 80 */
+    const void* v_cache;       /* offset 88 */
+    const int32_t* block_tables;   /* offset 96 */
+    const int32_t* context_lens;   /* offset 104 */
+    const int32_t* cu_seqlens_q;   /* offset 112 */
+    void* out;                 /* offset 120 */
+    float* lse;                /* offset 128; optional (NULL to skip): ln Z, the sink included */
+    const float* k_scale;      /* offset 136 */
+    const float* v_scale;      /* offset 144 */
+    const float* sinks;        /* offset 152; [heads_q] fp32, device (required) */
+} aule_paged_prefill_sink_desc;
+typedef struct aule_paged_query_sink_desc {
+    uint32_t struct_size;      /* = sizeof(aule_paged_query_sink_desc) = 160 */
+    int32_t dtype;
+    uint32_t batch, heads_q, heads_kv, head_dim;
+    uint32_t block_size;
+    uint32_t max_blocks;
+    float scale;
+    int32_t window_size;
+    int32_t device;
+    void* stream;              /* offset 48 */
+    const void* q;
+    const void* k_cache;
+    const void* v_cache;
+    const int32_t* block_tables;
+    const int32_t* context_lens;
+    void* out;
+    void* workspace;           /* offset 104; optional, size from aule_attention_paged_query_sink_workspace_size() */
+    uint64_t workspace_bytes;
+    const float* k_scale;      /* offset 120 */
+    const float* v_scale;      /* offset 128 */
+    float* lse;                /* offset 136; optional (NULL to skip): ln Z, the sink included */
+    uint32_t seq_q;            /* offset 144; 1 .. 64 (1: the decode) */
+    int32_t cache_dtype;       /* offset 148 */
+    const float* sinks;        /* offset 152; [heads_q] fp32, device (required) */
+} aule_paged_query_sink_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_varlen_sink_forward_ex(const aule_varlen_sink_desc* desc);
+int32_t aule_attention_varlen_sink_backward_ex(const aule_varlen_sink_bwd_desc* desc);
+int32_t aule_attention_paged_prefill_sink_ex(const aule_paged_prefill_sink_desc* desc);
+int32_t aule_attention_paged_query_sink_ex(const aule_paged_query_sink_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses on shape grounds.  The backward's  */
+/* is aule_attention_varlen_backward_workspace_size() of the same problem plus the partials of the dsinks reduction; the query's is   */
+/* aule_attention_paged_query_workspace_size() of the same problem.                                                                  */
+uint64_t aule_attention_varlen_sink_backward_workspace_size(const aule_varlen_sink_bwd_desc* desc);
+uint64_t aule_attention_paged_query_sink_workspace_size(const aule_paged_query_sink_desc* desc);
+
 /* Merge of two attention states (additive): out_a, out_b [rows, heads, head_dim] fp16 / bf16 are attention outputs of the same    */
 /* queries over two DISJOINT key sets, lse_a, lse_b [rows, heads] fp32 the natural logs of their softmax denominators (the lse of  */
 /* the calls above).  With M = max(lse_a, lse_b) and w_x = exp(lse_x - M):                                                          */
