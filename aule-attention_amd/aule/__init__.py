@@ -422,6 +422,71 @@ def flash_attention_paged_query_sinks(q, k_cache, v_cache, sinks, block_tables, 
                        v_scale=v_scale, return_lse=return_lse, sinks=_required_sinks(sinks))
 
 
+def flash_attention_paged_query_tree(q, k_cache, v_cache, tree_mask, block_tables, context_lens, scale=None, k_scale=None, v_scale=None,
+                                     return_lse=False):
+    """flash_attention_paged_query for a TREE of new tokens instead of a chain: the verify step of tree drafters (EAGLE, Medusa, SpecInfer).
+    All seq_q nodes are appended to the cache and verified in one call; a node sees the cached context and its ancestors, not its siblings
+    or cousins.  Not in the reference.
+
+        tree_mask [batch, seq_q] int64, contiguous, on q's device: one 64-bit word per new token (tree_mask_from_parents builds them).
+        The kernel reads the words on every launch: no host copy, no synchronisation, capturable; a graph replay sees the current words.
+        every other argument: as flash_attention_paged_query (16-bit or float8_e4m3fn caches); there is no window_size.
+    With L_b the clamped length and n = seq_q, new token t is key L_b - n + t.  Query i sees key j iff 0 <= j < L_b and
+        j < L_b - n  (a context key)      or      bit j - (L_b - n) of tree_mask[b, i] is set.
+    Any bit pattern is legal: no self bit is implied and no topological order required; bits at or above n and bits that name a key below
+    0 are ignored.  A query at a negative position gives a row of zeros; a row that sees no key gives out = 0 and lse = -inf.  The chain
+    words tree_mask[b, i] = (2 << i) - 1 give flash_attention_paged_query's out and lse bit for bit (finite cached data).  Wrong dtype,
+    shape, device or a non-contiguous tree_mask raise ValueError before any launch.
+    Out of scope: sliding windows over a tree, sink logits together with a tree, the cascade and the MLA entries, head_dim 256, more than
+    64 tree tokens per sequence, any backward."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_query
+    return paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=scale, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse,
+                       tree_mask=_required_tree_mask(tree_mask))
+
+
+def flash_attention_paged_prefill_tree(q, k_cache, v_cache, tree_mask, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None,
+                                       k_scale=None, v_scale=None, return_lse=False):
+    """flash_attention_paged_prefill with tree masks (flash_attention_paged_query_tree states the rule): tree_mask [total_tokens] int64,
+    contiguous, on q's device, indexed by packed token.  A sequence whose clamped number of new tokens n_b is at most 64 carries a tree --
+    decided on the device -- and token i of it reads the word of row s_b + i; a longer sequence (a prompt chunk in the same step) keeps the
+    causal rule of flash_attention_paged_prefill and its words are not read.  Every other argument and rule as
+    flash_attention_paged_prefill; there is no window_size.  Chain words give that call's out and lse bit for bit.
+    Out of scope: sliding windows over a tree, sink logits together with a tree, the cascade and the MLA entries, head_dim 256, more than
+    64 tree tokens per sequence, any backward."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_prefill
+    return paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=max_seqlen_q, scale=scale,
+                         k_scale=k_scale, v_scale=v_scale, return_lse=return_lse, tree_mask=_required_tree_mask(tree_mask))
+
+
+def tree_mask_from_parents(parents):
+    """The words of flash_attention_paged_query_tree / flash_attention_paged_prefill_tree for a tree given by parent indices.
+
+        parents [seq_q] or [batch, seq_q], any integer dtype, seq_q <= 64: parents[i] is the index of token i's parent among the new
+        tokens; anything outside [0, i) means "child of the context" (a root of the draft).
+    Returns int64 words of parents' shape with the self bit and all ancestor bits set; a chain (parents[i] = i - 1) gives (2 << i) - 1.
+    Torch ops only, on parents' device, no host synchronisation; works on CPU tensors."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import tree_mask_from_parents as impl
+    return impl(parents)
+
+
+def _required_tree_mask(tree_mask):
+    if tree_mask is None:
+        raise ValueError("tree_mask must be an int64 tensor (the call without a tree: flash_attention_paged_query / flash_attention_paged_prefill)")
+    return tree_mask
+
+
 def _required_sinks(sinks):
     if sinks is None:
         raise ValueError("sinks must be a [heads_q] tensor (the sinkless call: flash_attention_paged_prefill / flash_attention_paged_query)")
@@ -732,7 +797,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

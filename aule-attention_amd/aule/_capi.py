@@ -294,6 +294,18 @@ class PagedQuerySinkDesc(ctypes.Structure):
     _fields_ = PagedQueryDesc._fields_ + [("sinks", ctypes.c_void_p)]
 
 
+# The tree kinds (tree masks: include/aule.h): each is its twin field for field, then the int64 words.
+
+class PagedQueryTreeDesc(ctypes.Structure):
+    """struct aule_paged_query_tree_desc (include/aule.h): aule_paged_query_desc plus the [batch, seq_q] int64 tree words."""
+    _fields_ = PagedQueryDesc._fields_ + [("tree_mask", ctypes.c_void_p)]
+
+
+class PagedPrefillTreeDesc(ctypes.Structure):
+    """struct aule_paged_prefill_tree_desc (include/aule.h): aule_paged_prefill_desc plus the [total_tokens] int64 tree words."""
+    _fields_ = PagedPrefillDesc._fields_ + [("tree_mask", ctypes.c_void_p)]
+
+
 class MergeStatesDesc(ctypes.Structure):
     """struct aule_merge_states_desc (include/aule.h): two attention states into one."""
     _fields_ = [
@@ -513,6 +525,9 @@ SIGNATURES = [
     ("aule_attention_paged_prefill_sink_ex", _I32, [ctypes.POINTER(PagedPrefillSinkDesc)]),
     ("aule_attention_paged_query_sink_ex", _I32, [ctypes.POINTER(PagedQuerySinkDesc)]),
     ("aule_attention_paged_query_sink_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedQuerySinkDesc)]),
+    ("aule_attention_paged_query_tree_ex", _I32, [ctypes.POINTER(PagedQueryTreeDesc)]),
+    ("aule_attention_paged_prefill_tree_ex", _I32, [ctypes.POINTER(PagedPrefillTreeDesc)]),
+    ("aule_attention_paged_query_tree_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedQueryTreeDesc)]),
     ("aule_attention_merge_states_ex", _I32, [ctypes.POINTER(MergeStatesDesc)]),
     ("aule_attention_mla_prefill_ex", _I32, [ctypes.POINTER(MlaPrefillDesc)]),
     ("aule_attention_mla_prefill_backward_ex", _I32, [ctypes.POINTER(MlaPrefillBwdDesc)]),

@@ -544,6 +544,54 @@ def _sinks_f32(sinks):
     return sinks.float().contiguous()
 
 
+def _tree_mask_check(tree_mask, shape, what, q):
+    """The rules of the tree words (tree masks: aule.flash_attention_paged_query_tree documents them), none of which needs a device: an
+    int64 tensor of `shape`, contiguous (the kernels read it in place on every launch) and on q's device."""
+    if not torch.is_tensor(tree_mask) or tuple(tree_mask.shape) != tuple(shape):
+        raise ValueError(f"tree_mask must be a {what} = {list(shape)} tensor, got "
+                         f"{tuple(tree_mask.shape) if torch.is_tensor(tree_mask) else type(tree_mask).__name__}")
+    if tree_mask.dtype != torch.int64:
+        raise ValueError(f"tree_mask must be int64 (one 64-bit word per new token, read on the device as it stands), got {tree_mask.dtype}")
+    if not tree_mask.is_contiguous():
+        raise ValueError("tree_mask must be contiguous: the kernels read it in place on every launch (pass tree_mask.contiguous())")
+    if tree_mask.device != q.device:
+        raise ValueError(f"tree_mask must be on q's device ({q.device}), got {tree_mask.device}: the kernels read it on every launch")
+
+
+def _no_tree_extras(window_size, sinks):
+    if _window_arg(window_size) > 0:
+        raise ValueError("a sliding window is not defined over a tree (window_size must be off with tree_mask)")
+    if sinks is not None:
+        raise ValueError("sink logits together with a tree are not built")
+
+
+def tree_mask_from_parents(parents):
+    """aule.tree_mask_from_parents (documented there).  Torch ops only, on parents' device, no host synchronisation: the ancestor relation is
+    closed by repeated squaring of the boolean matrix (ceil(log2(seq_q)) products), and each word is assembled from its two 32-bit halves,
+    so that bit 63 never passes through a signed shift or a signed sum that overflows."""
+    if not torch.is_tensor(parents) or parents.dim() not in (1, 2) or parents.dtype.is_floating_point or parents.dtype.is_complex \
+            or parents.dtype == torch.bool:
+        raise ValueError("parents must be an integer tensor [seq_q] or [batch, seq_q]")
+    n = parents.shape[-1]
+    if n > PAGED_QUERY_MAX_TOKENS:
+        raise ValueError(f"a tree holds at most {PAGED_QUERY_MAX_TOKENS} new tokens per sequence, got {n}")
+    p = parents.to(torch.int64)
+    idx = torch.arange(n, device=p.device)
+    ok = (p >= 0) & (p < idx)                                   # anything else: a child of the context
+    # reach[.., i, j]: j is i itself or an ancestor of i
+    reach = (idx.unsqueeze(-1) == idx) | ((p.unsqueeze(-1) == idx) & ok.unsqueeze(-1))
+    steps = 1
+    while steps < n:
+        r = reach.to(torch.float32)
+        reach = (r @ r) > 0
+        steps *= 2
+    w = torch.where(idx < 32, torch.ones_like(idx) << (idx % 32), torch.zeros_like(idx))      # bit j as a value < 2^32, j < 32
+    lo = (reach.to(torch.int64) * w).sum(-1)
+    hi = (reach.to(torch.int64) * torch.where(idx >= 32, torch.ones_like(idx) << (idx % 32), torch.zeros_like(idx))).sum(-1)
+    hi = torch.where(hi >= (1 << 31), hi - (1 << 32), hi)       # the high half as a signed 32-bit value: the product below stays in range
+    return (hi * (1 << 32)) | lo
+
+
 def paged_decode(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1, k_scale=None, v_scale=None):
     """Paged-KV decode on the HIP backend; counterpart of flash_attention_paged_amd
     (python/aule/triton_flash_amd.py:656-737), same argument meaning:
@@ -591,7 +639,7 @@ PAGED_QUERY_MAX_TOKENS = 64   # packed rows of the wave-per-chunk kernel family 
 
 
 def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, window_size=-1, k_scale=None, v_scale=None,
-                return_lse=False, sinks=None):
+                return_lse=False, sinks=None, tree_mask=None):
     """Paged attention for a short multi-token query per sequence (speculative verify, multi-token heads, a short prompt
     tail against a cached prefix); the MQ instances of csrc/fa_fwd_splitkv_gfx950.hip behind aule_attention_paged_query_ex:
 
@@ -603,7 +651,8 @@ def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, win
     Returns out [batch, heads_q, seq_q, head_dim], or (out, lse) with lse [batch, heads_q, seq_q] fp32 -- the natural log
     of the sum of exp(scaled score) over the visible keys, -inf for a row that sees none -- when return_lse is set.  No
     device->host synchronisation; captures into a graph.  All argument errors are ValueErrors raised before the device is
-    touched.  sinks: [heads_q] sink logits (aule.flash_attention_paged_query_sinks), behind aule_attention_paged_query_sink_ex."""
+    touched.  sinks: [heads_q] sink logits (aule.flash_attention_paged_query_sinks), behind aule_attention_paged_query_sink_ex.
+    tree_mask: [batch, seq_q] int64 words (aule.flash_attention_paged_query_tree), behind aule_attention_paged_query_tree_ex."""
     Hkv = _paged_shapes(q, "B,Hq,Sq,D", k_cache, v_cache)
     B, Hq, Sq, _ = q.shape
     if not 1 <= Sq <= PAGED_QUERY_MAX_TOKENS:
@@ -614,6 +663,9 @@ def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, win
     _scale_shapes(fp8, Hkv, k_scale, v_scale)
     if sinks is not None:
         _sinks_check(sinks, q)
+    if tree_mask is not None:
+        _no_tree_extras(window_size, sinks)
+        _tree_mask_check(tree_mask, (B, Sq), "[batch, seq_q]", q)
     _needs_device("query", q)
     lib = _capi.get_lib()
     q, k_cache, v_cache = q.contiguous(), k_cache.contiguous(), v_cache.contiguous()
@@ -623,11 +675,15 @@ def paged_query(q, k_cache, v_cache, block_tables, context_lens, scale=None, win
     lse = torch.empty((B, Hq, Sq), device=q.device, dtype=torch.float32) if return_lse else None
     if B * Hq == 0:
         return (out, lse) if return_lse else out
-    d = _paged_problem(_capi.PagedQueryDesc() if sinks is None else _capi.PagedQuerySinkDesc(), q, k_cache, v_cache, out, bt, cl, scale, fp8)
+    kind = _capi.PagedQueryTreeDesc if tree_mask is not None else _capi.PagedQueryDesc if sinks is None else _capi.PagedQuerySinkDesc
+    d = _paged_problem(kind(), q, k_cache, v_cache, out, bt, cl, scale, fp8)
     d.seq_q, d.window_size = Sq, _window_arg(window_size)
     d.lse = lse.data_ptr() if lse is not None else None
     size_query, launch = ("aule_attention_paged_query_workspace_size", "aule_attention_paged_query_ex") if sinks is None else \
         ("aule_attention_paged_query_sink_workspace_size", "aule_attention_paged_query_sink_ex")
+    if tree_mask is not None:
+        size_query, launch = "aule_attention_paged_query_tree_workspace_size", "aule_attention_paged_query_tree_ex"
+        d.tree_mask = tree_mask.data_ptr()
     held = [_attach_workspace(d, getattr(lib, size_query), q.device),   # (until the launch is queued)
             _attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device)]
     if sinks is not None:
@@ -1102,7 +1158,7 @@ def _ragged_problem(op, d, q, q_stride, fp8, k_cache, v_cache, block_tables, con
 
 
 def paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None, window_size=-1,
-                  k_scale=None, v_scale=None, return_lse=False, sinks=None):
+                  k_scale=None, v_scale=None, return_lse=False, sinks=None, tree_mask=None):
     """Paged prefill: ragged per-sequence queries against the paged KV cache (the step of a continuous-batching engine: a
     prompt chunk behind a cached prefix next to a short verify next to plain decodes); csrc/fa_fwd_paged_prefill_gfx950.hip
     behind aule_attention_paged_prefill_ex:
@@ -1121,13 +1177,17 @@ def paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q,
     row of zeros and lse = -inf.  Rows that belong to no sequence are never written: out (and lse) come from torch.empty.
     Returns out [total_tokens, heads_q, head_dim], or (out, lse) with lse [total_tokens, heads_q] fp32 when return_lse is
     set.  All argument errors are ValueErrors raised before the device is touched.  sinks: [heads_q] sink logits
-    (aule.flash_attention_paged_prefill_sinks), behind aule_attention_paged_prefill_sink_ex."""
+    (aule.flash_attention_paged_prefill_sinks), behind aule_attention_paged_prefill_sink_ex.  tree_mask: [total_tokens] int64 words
+    (aule.flash_attention_paged_prefill_tree), behind aule_attention_paged_prefill_tree_ex."""
     Hkv, fp8 = _ragged_kind("prefill", q, k_cache, v_cache, k_scale, v_scale)
     if sinks is not None:
         _sinks_check(sinks, q)
+    if tree_mask is not None:
+        _no_tree_extras(window_size, sinks)
+        _tree_mask_check(tree_mask, (q.shape[0],), "[total_tokens]", q)
     q, q_stride = _ragged_queries("prefill", q, fp8, Hkv, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, k_scale, v_scale)
     lib = _capi.get_lib()
-    d = _capi.PagedPrefillDesc() if sinks is None else _capi.PagedPrefillSinkDesc()
+    d = _capi.PagedPrefillTreeDesc() if tree_mask is not None else _capi.PagedPrefillDesc() if sinks is None else _capi.PagedPrefillSinkDesc()
     result, held = _ragged_problem("prefill", d, q, q_stride, fp8, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q,
                                    scale, return_lse)
     if held is not None:
@@ -1138,6 +1198,9 @@ def paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q,
             launch = "aule_attention_paged_prefill_sink_ex"
             held.append(_sinks_f32(sinks))
             d.sinks = held[-1].data_ptr()
+        if tree_mask is not None:
+            launch = "aule_attention_paged_prefill_tree_ex"
+            d.tree_mask = tree_mask.data_ptr()
         _capi.check(getattr(lib, launch)(ctypes.byref(d)), launch)
     return result
 

@@ -187,6 +187,29 @@ static_assert(sizeof(aule_paged_query_sink_desc) == 160 && offsetof(aule_paged_q
                   AULE_QUERY_SINK_SAME(seq_q) && AULE_QUERY_SINK_SAME(cache_dtype),
               "aule_paged_query_sink_desc is aule_paged_query_desc plus sinks");
 #undef AULE_QUERY_SINK_SAME
+// The tree kinds (tree masks: include/aule.h), pinned the same way: the twin field for field, then tree_mask.
+#define AULE_PREFILL_TREE_SAME(field) AULE_SINK_SAME(aule_paged_prefill_tree_desc, aule_paged_prefill_desc, field)
+static_assert(sizeof(aule_paged_prefill_tree_desc) == 160 && offsetof(aule_paged_prefill_tree_desc, tree_mask) == 152 &&
+                  offsetof(aule_paged_prefill_tree_desc, tree_mask) == sizeof(aule_paged_prefill_desc) && AULE_PREFILL_TREE_SAME(dtype) && AULE_PREFILL_TREE_SAME(cache_dtype) &&
+                  AULE_PREFILL_TREE_SAME(batch) && AULE_PREFILL_TREE_SAME(heads_q) && AULE_PREFILL_TREE_SAME(heads_kv) && AULE_PREFILL_TREE_SAME(head_dim) &&
+                  AULE_PREFILL_TREE_SAME(block_size) && AULE_PREFILL_TREE_SAME(max_blocks) && AULE_PREFILL_TREE_SAME(total_tokens) && AULE_PREFILL_TREE_SAME(max_seqlen_q) &&
+                  AULE_PREFILL_TREE_SAME(scale) && AULE_PREFILL_TREE_SAME(window_size) && AULE_PREFILL_TREE_SAME(device) && AULE_PREFILL_TREE_SAME(q_token_stride) &&
+                  AULE_PREFILL_TREE_SAME(stream) && AULE_PREFILL_TREE_SAME(q) && AULE_PREFILL_TREE_SAME(k_cache) && AULE_PREFILL_TREE_SAME(v_cache) &&
+                  AULE_PREFILL_TREE_SAME(block_tables) && AULE_PREFILL_TREE_SAME(context_lens) && AULE_PREFILL_TREE_SAME(cu_seqlens_q) && AULE_PREFILL_TREE_SAME(out) &&
+                  AULE_PREFILL_TREE_SAME(lse) && AULE_PREFILL_TREE_SAME(k_scale) && AULE_PREFILL_TREE_SAME(v_scale),
+              "aule_paged_prefill_tree_desc is aule_paged_prefill_desc plus tree_mask");
+#undef AULE_PREFILL_TREE_SAME
+#define AULE_QUERY_TREE_SAME(field) AULE_SINK_SAME(aule_paged_query_tree_desc, aule_paged_query_desc, field)
+static_assert(sizeof(aule_paged_query_tree_desc) == 160 && offsetof(aule_paged_query_tree_desc, tree_mask) == 152 &&
+                  offsetof(aule_paged_query_tree_desc, tree_mask) == sizeof(aule_paged_query_desc) && AULE_QUERY_TREE_SAME(dtype) && AULE_QUERY_TREE_SAME(batch) &&
+                  AULE_QUERY_TREE_SAME(heads_q) && AULE_QUERY_TREE_SAME(heads_kv) && AULE_QUERY_TREE_SAME(head_dim) && AULE_QUERY_TREE_SAME(block_size) &&
+                  AULE_QUERY_TREE_SAME(max_blocks) && AULE_QUERY_TREE_SAME(scale) && AULE_QUERY_TREE_SAME(window_size) && AULE_QUERY_TREE_SAME(device) &&
+                  AULE_QUERY_TREE_SAME(stream) && AULE_QUERY_TREE_SAME(q) && AULE_QUERY_TREE_SAME(k_cache) && AULE_QUERY_TREE_SAME(v_cache) &&
+                  AULE_QUERY_TREE_SAME(block_tables) && AULE_QUERY_TREE_SAME(context_lens) && AULE_QUERY_TREE_SAME(out) && AULE_QUERY_TREE_SAME(workspace) &&
+                  AULE_QUERY_TREE_SAME(workspace_bytes) && AULE_QUERY_TREE_SAME(k_scale) && AULE_QUERY_TREE_SAME(v_scale) && AULE_QUERY_TREE_SAME(lse) &&
+                  AULE_QUERY_TREE_SAME(seq_q) && AULE_QUERY_TREE_SAME(cache_dtype),
+              "aule_paged_query_tree_desc is aule_paged_query_desc plus tree_mask");
+#undef AULE_QUERY_TREE_SAME
 #undef AULE_SINK_SAME
 static_assert(sizeof(aule_mla_prefill_desc) == 176 && offsetof(aule_mla_prefill_desc, dtype) == 4 && offsetof(aule_mla_prefill_desc, batch) == 8 &&
                   offsetof(aule_mla_prefill_desc, heads) == 12 && offsetof(aule_mla_prefill_desc, qk_dim) == 16 &&
@@ -1319,12 +1342,14 @@ static void fill_paged_prefill_args(const aule_paged_prefill_desc* d, aule_hip::
     }
 }
 
-// (`d` passed paged_prefill_desc_error with its kind's size; `sinks`: the sink kind's logits, checked by the caller)
-static int32_t paged_prefill_launch(const aule_paged_prefill_desc* d, const float* sinks, const char* what) {
+// (`d` passed paged_prefill_desc_error with its kind's size; `sinks` / `tree_mask`: the sink kind's logits and the tree kind's words, checked
+// by the caller)
+static int32_t paged_prefill_launch(const aule_paged_prefill_desc* d, const float* sinks, const char* what, const int64_t* tree_mask = nullptr) {
     if (!initialised()) return -1;
     aule_hip::PagedPrefillArgs a;
     fill_paged_prefill_args(d, a);
     a.sinks = sinks;
+    a.tree_mask = reinterpret_cast<const long long*>(tree_mask);
     if (aule_hip::paged_prefill_grid(a) > 0x7fffffffll) {
         set_error("%s failed: the grid (blocks * heads_kv * batch) exceeds 2^31 - 1 workgroups", what);
         return -3;
@@ -1360,6 +1385,52 @@ int32_t aule_attention_paged_prefill_sink_ex(const aule_paged_prefill_sink_desc*
     }
     if (ragged_nothing_to_do(x)) return 0;
     return paged_prefill_launch(x, d->sinks, "Paged prefill sink attention");
+}
+
+// The tree kinds (tree masks: include/aule.h), read like the sink kinds: the twin's checker with the kind's own size, then the two rules of
+// their own -- a window is not defined over a tree, and a null tree_mask is refused once there is something to do.  Host logic first.
+static const char kNullTreeMask[] = "null tree_mask pointer (tree_mask is an int64 device array, one word per new token)";
+static const char kTreeWindow[] = "window_size > 0: a sliding window is not defined over a tree";
+static const aule_paged_query_desc* query_tree_prefix(const aule_paged_query_tree_desc* d) { return reinterpret_cast<const aule_paged_query_desc*>(d); }
+static const aule_paged_prefill_desc* prefill_tree_prefix(const aule_paged_prefill_tree_desc* d) { return reinterpret_cast<const aule_paged_prefill_desc*>(d); }
+
+int32_t aule_attention_paged_query_tree_ex(const aule_paged_query_tree_desc* d) {
+    RoctxRange range("aule.paged_query_tree");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    const aule_paged_query_desc* x = query_tree_prefix(d);
+    const char* why = paged_query_desc_error(x, true, text, sizeof(aule_paged_query_tree_desc));
+    if (why == nullptr && x->window_size > 0) why = kTreeWindow;
+    if (why == nullptr && !paged_query_nothing_to_do(x) && d->tree_mask == nullptr) why = kNullTreeMask;
+    if (why != nullptr) {
+        set_error("Paged query tree attention failed: %s", why);
+        return -3;
+    }
+    if (paged_query_nothing_to_do(x)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::PagedArgs a;
+    fill_paged_query_args(x, a);
+    a.tree_mask = reinterpret_cast<const long long*>(d->tree_mask);
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    return launched("Paged query tree attention", aule_hip::launch_paged_query(a, (hipStream_t)d->stream));
+}
+
+int32_t aule_attention_paged_prefill_tree_ex(const aule_paged_prefill_tree_desc* d) {
+    RoctxRange range("aule.paged_prefill_tree");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    const aule_paged_prefill_desc* x = prefill_tree_prefix(d);
+    const char* why = paged_prefill_desc_error(x, text, sizeof(aule_paged_prefill_tree_desc));
+    if (why == nullptr && x->window_size > 0) why = kTreeWindow;
+    if (why == nullptr && !ragged_nothing_to_do(x) && d->tree_mask == nullptr) why = kNullTreeMask;
+    if (why != nullptr) {
+        set_error("Paged prefill tree attention failed: %s", why);
+        return -3;
+    }
+    if (ragged_nothing_to_do(x)) return 0;
+    return paged_prefill_launch(x, nullptr, "Paged prefill tree attention", d->tree_mask);
 }
 
 // (`d` passed paged_cascade_desc_error) the two kernels' arguments: the suffix pass is the prefill's, read through the common prefix,
@@ -2227,6 +2298,16 @@ uint64_t aule_attention_paged_query_sink_workspace_size(const aule_paged_query_s
     Reason text;
     const aule_paged_query_desc* x = query_prefix(d);
     if (paged_query_desc_error(x, false, text, sizeof(aule_paged_query_sink_desc)) || paged_query_nothing_to_do(x)) return 0;
+    aule_hip::PagedArgs a;
+    fill_paged_query_args(x, a);
+    return aule_hip::paged_workspace_bytes(a);
+}
+
+// (the tree kernel writes the twin's partials: the twin's plan and bytes; a window is refused as by the launch)
+uint64_t aule_attention_paged_query_tree_workspace_size(const aule_paged_query_tree_desc* d) {
+    Reason text;
+    const aule_paged_query_desc* x = query_tree_prefix(d);
+    if (paged_query_desc_error(x, false, text, sizeof(aule_paged_query_tree_desc)) || x->window_size > 0 || paged_query_nothing_to_do(x)) return 0;
     aule_hip::PagedArgs a;
     fill_paged_query_args(x, a);
     return aule_hip::paged_workspace_bytes(a);

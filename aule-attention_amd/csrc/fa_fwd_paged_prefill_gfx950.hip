@@ -23,34 +23,14 @@
 // One launch, no workspace: grid = ceil(max_seqlen_q g / 128) x Hkv x B, decoded as (rank, sequence, KV head) with rank 0 the
 // sequence's own last (heaviest) block; a workgroup whose rank is past the sequence's blocks leaves before it touches the table or
 // the caches.  The table is walked one tile ahead of the K / V loads, which are one tile ahead of the MFMAs.
-#include "fa_kernels.h"
-#include "fa_tile_attention.h"
-
-namespace aule_hip {
-namespace {
-
-struct PrefillParams {
-    const char* q;
-    const char* k;
-    const char* v;
-    char* o;
-    float* lse;
-    const int* table;
-    const int* ctx;
-    const int* cu;
-    const float* k_scale;
-    const float* v_scale;
-    const float* sinks;   // [Hq] fp32 sink logits or null (DESIGN.md 3.12)
-    long long q_stride;   // elements between tokens of q
-    int T, B, Hq, Hkv, g;
-    int bs, bs_shift;     // bs_shift >= 0: bs = 1 << bs_shift
-    int max_blocks, max_sq;
-    float c;              // scale * log2(e) (sign kept)
-    int window;           // > 0: on
-};
-
-template <class T, int D, class KV>
-__global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_kernel(const PrefillParams p) {
+//
+// The kernel body is written ONCE, in the first part of this file, and compiled into two kernels: fa_fwd_paged_prefill_kernel (TREE = false)
+// and fa_fwd_paged_prefill_tree_kernel (TREE = true) each include this file again with AULE_PAGED_PREFILL_BODY defined,
+// which yields the body alone.  Text, not a shared inline function, for the reason fa_fwd_splitkv_gfx950.hip gives: as a force-inlined
+// template the same statements compiled the existing instances to other register counts and schedules; included, they stay the code
+// they were, instruction for instruction (profiles/tree_resources.txt).
+#ifdef AULE_PAGED_PREFILL_BODY
+// ---- the body.  In scope: T, D, KV, the constant TREE and the kernel argument `const PrefillParams p`.
     using C = PrefillCfg<D>;
     constexpr bool FP8 = std::is_same<KV, KvFp8>::value;
     __shared__ __attribute__((aligned(16))) char Ks[kPK * C::PA];
@@ -90,7 +70,20 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_kernel(const Pref
     const int wpos_lo = L - n + (r0 + min(wave * 32, rows - 1)) / p.g;
     const int wpos_hi = L - n + (r0 + min(wave * 32 + 31, rows - 1)) / p.g;
 
-    const int kend = bpos_hi + 1;   // <= L
+    // TREE: a sequence of at most 64 new tokens carries a tree (wave-uniform: n is); a longer one keeps the causal rule.  The lane's word,
+    // bit t = new token t (key L - n + t) is visible, as two halves; a row at a negative position sees nothing (L < n: no context key)
+    bool tree = false;
+    unsigned tree_lo = 0u, tree_hi = 0u;
+    if constexpr (TREE) {
+        tree = n <= 64;
+        if (tree && pos >= 0) {
+            const unsigned long long w = (unsigned long long)p.tree_mask[(long long)s + tok];
+            tree_lo = (unsigned)w;
+            tree_hi = (unsigned)(w >> 32);
+        }
+    }
+
+    const int kend = tree ? L : bpos_hi + 1;   // <= L (a node may see a new token behind its own position)
     const int kbeg = p.window > 0 ? max(0, bpos_lo - p.window + 1) / kPK * kPK : 0;
     const int ntiles = kend > kbeg ? (kend - kbeg + kPK - 1) / kPK : 0;
     const int* tab = p.table + (long long)b * p.max_blocks;
@@ -125,7 +118,7 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_kernel(const Pref
             kt.lookup(p, tab, k0 + 2 * kPK, kend, tid);
         }
         // a wave skips the tiles none of its rows sees: all keys after its last position, or all before its window
-        if (!wave_live || k0 > wpos_hi || (p.window > 0 && k0 + kPK - 1 < wpos_lo - p.window + 1)) continue;
+        if (!wave_live || (!tree && k0 > wpos_hi) || (p.window > 0 && k0 + kPK - 1 < wpos_lo - p.window + 1)) continue;
         // S^T[key][row] = K.Q^T over the 64 keys of the tile
         f32x16_t sc[2] = {f32x16_t{}, f32x16_t{}};
 #pragma unroll
@@ -135,13 +128,27 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_kernel(const Pref
                 sc[kk] = mfma16<T>(lds_b128(Ks + (32 * kk + l31) * C::PA + 32 * g + 16 * hi), qf[g], sc[kk]);
         // scale to log2 units, mask, running max over the lane pair (lanes l and l + 32 hold the same row)
         float mx = -__builtin_inff();
-        const bool full = k0 + kPK - 1 <= wpos_lo && (p.window <= 0 || wpos_hi - k0 < p.window);   // every row sees every key of the tile
+        // every row sees every key of the tile (a tree: the tile lies below the new tokens)
+        const bool full = tree ? k0 + kPK - 1 < L - n : (k0 + kPK - 1 <= wpos_lo && (p.window <= 0 || wpos_hi - k0 < p.window));
         if (full) {
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
                 for (int rr = 0; rr < 16; ++rr) {
                     const float x = sc[kk][rr] * c;
+                    sc[kk][rr] = x;
+                    mx = fmaxf(mx, x);
+                }
+        } else if (tree) {
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) {
+                    const int j = k0 + 32 * kk + crow(rr, hi);
+                    const int bit = j - (L - n);   // of the word: a context key (bit < 0) is visible, a new token iff it lies below L and its bit is set
+                    const unsigned half = (bit & 32) ? tree_hi : tree_lo;
+                    const bool see = bit < 0 || (j < L && ((half >> (bit & 31)) & 1u) != 0u);
+                    const float x = see ? sc[kk][rr] * c : -__builtin_inff();
                     sc[kk][rr] = x;
                     mx = fmaxf(mx, x);
                 }
@@ -207,7 +214,51 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_kernel(const Pref
             p.lse[orow] = l > 0.f ? (mu + fast_log2(l)) * kLn2 : -__builtin_inff();
         }
     }
+#else
+// ---- the file proper
+#include "fa_kernels.h"
+#include "fa_tile_attention.h"
+
+namespace aule_hip {
+namespace {
+
+struct PrefillParams {
+    const char* q;
+    const char* k;
+    const char* v;
+    char* o;
+    float* lse;
+    const int* table;
+    const int* ctx;
+    const int* cu;
+    const float* k_scale;
+    const float* v_scale;
+    const float* sinks;   // [Hq] fp32 sink logits or null (DESIGN.md 3.12)
+    long long q_stride;   // elements between tokens of q
+    int T, B, Hq, Hkv, g;
+    int bs, bs_shift;     // bs_shift >= 0: bs = 1 << bs_shift
+    int max_blocks, max_sq;
+    float c;              // scale * log2(e) (sign kept)
+    int window;           // > 0: on
+    // (last: the fields above keep the kernel-argument offsets the existing instances were compiled with)
+    const long long* tree_mask;   // the TREE instances: [T] words, bit t of token s + i = new token t of its sequence is visible
+};
+
+#define AULE_PAGED_PREFILL_BODY
+template <class T, int D, class KV>
+__global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_kernel(const PrefillParams p) {
+    constexpr bool TREE = false;
+#include "fa_fwd_paged_prefill_gfx950.hip"
 }
+
+// The TREE instances (PagedPrefillArgs::tree_mask given).  A sequence with n <= 64 new tokens carries a tree: every block of it walks the
+// keys up to L, the tiles below L - n keep the unmasked path and the others test the lane's word.  A longer sequence is the kernel above.
+template <class T, int D, class KV>
+__global__ void __launch_bounds__(256, 1) fa_fwd_paged_prefill_tree_kernel(const PrefillParams p) {
+    constexpr bool TREE = true;
+#include "fa_fwd_paged_prefill_gfx950.hip"
+}
+#undef AULE_PAGED_PREFILL_BODY
 
 }  // namespace
 
@@ -226,6 +277,7 @@ int launch_paged_prefill(const PagedPrefillArgs& a, hipStream_t stream) {
     const bool fp8 = a.cache_kind == kCacheFp8E4M3;
     if (a.cache_kind != kCache16 && !fp8) return -1;
     if (fp8 && (a.k_scale == nullptr || a.v_scale == nullptr)) return -1;
+    if (a.tree_mask != nullptr && (a.window > 0 || a.sinks != nullptr)) return -1;   // (neither is defined over a tree)
     if (a.Hkv <= 0 || a.Hq % a.Hkv != 0 || a.block_size <= 0 || a.max_blocks <= 0) return -1;
     if ((long long)a.block_size * a.max_blocks >= (1ll << 30)) return -1;
     if (a.q_token_stride < (long long)a.Hq * a.D || a.q_token_stride % 8 != 0) return -1;
@@ -237,7 +289,7 @@ int launch_paged_prefill(const PagedPrefillArgs& a, hipStream_t stream) {
     p.q = static_cast<const char*>(a.q); p.k = static_cast<const char*>(a.k_cache); p.v = static_cast<const char*>(a.v_cache);
     p.o = static_cast<char*>(a.out); p.lse = a.lse;
     p.table = a.block_tables; p.ctx = a.context_lens; p.cu = a.cu_seqlens_q;
-    p.k_scale = a.k_scale; p.v_scale = a.v_scale; p.sinks = a.sinks;
+    p.k_scale = a.k_scale; p.v_scale = a.v_scale; p.sinks = a.sinks; p.tree_mask = a.tree_mask;
     p.q_stride = a.q_token_stride;
     p.T = a.T; p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.g = a.Hq / a.Hkv;
     p.bs = a.block_size;
@@ -246,9 +298,11 @@ int launch_paged_prefill(const PagedPrefillArgs& a, hipStream_t stream) {
     p.c = a.scale * kLog2e;
     p.window = a.window > 0 ? a.window : 0;
     return dispatch_tile_instance(a.dtype, a.D, fp8, [&](auto t, auto d, auto kv) {
-        hipLaunchKernelGGL((fa_fwd_paged_prefill_kernel<decltype(t), decltype(d)::value, decltype(kv)>), dim3((unsigned)nwg), dim3(256), 0, stream, p);
+        if (a.tree_mask != nullptr) hipLaunchKernelGGL((fa_fwd_paged_prefill_tree_kernel<decltype(t), decltype(d)::value, decltype(kv)>), dim3((unsigned)nwg), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((fa_fwd_paged_prefill_kernel<decltype(t), decltype(d)::value, decltype(kv)>), dim3((unsigned)nwg), dim3(256), 0, stream, p);
         return (int)hipGetLastError();
     });
 }
 
 }  // namespace aule_hip
+#endif   // AULE_PAGED_PREFILL_BODY

@@ -1,6 +1,8 @@
-// fa_fwd_splitkv_body.inc -- the body of fa_fwd_splitkv_kernel and fa_fwd_paged_query_kernel (fa_fwd_splitkv_gfx950.hip, which
-// says why it is an include).  In scope: T, D, KV, the constants PAGED and MQ, and the kernel argument `const SplitParams p`.
+// fa_fwd_splitkv_body.inc -- the body of fa_fwd_splitkv_kernel, fa_fwd_paged_query_kernel and fa_fwd_paged_tree_kernel
+// (fa_fwd_splitkv_gfx950.hip, which says why it is an include).  In scope: T, D, KV, the constants PAGED, MQ and TREE, and the kernel
+// argument `const SplitParams p`.
     static_assert(PAGED || !MQ, "the multi-query instances are paged");
+    static_assert(MQ || !TREE, "the tree instances are multi-query");
     using v8 = typename T::v8;
     constexpr int EB = KV::EB;
     constexpr int RB = D * EB;            // bytes of a K/V row
@@ -32,6 +34,16 @@
         const bool one_head = r0 / Sq == r1 / Sq;
         pos_lo = Sk - Sq + (one_head ? r0 % Sq : 0);
         pos_hi = Sk - Sq + (one_head ? r1 % Sq : Sq - 1);
+    }
+    // TREE: the row's word, bit t = new token t (key Sk - Sq + t) is visible; as two halves, so that the test in the loop is a select and
+    // a 32-bit shift.  A row at a negative position sees nothing (it has no context key either: Sk < Sq)
+    unsigned tree_lo = 0u, tree_hi = 0u;
+    if constexpr (TREE) {
+        if (valid && pos >= 0) {
+            const unsigned long long w = (unsigned long long)p.tree_mask[(size_t)b * Sq + qi];
+            tree_lo = (unsigned)w;
+            tree_hi = (unsigned)(w >> 32);
+        }
     }
 
     const size_t kvoff = PAGED ? 0 : (size_t)(b * p.Hkv + hk) * Sk * RB;
@@ -101,7 +113,9 @@
     const int ntiles = (Sk + 31) / 32;
     int t0 = (blockIdx.x * 4 + wave) * p.chunk_tiles;
     int t1 = min(t0 + p.chunk_tiles, ntiles);
-    if constexpr (MQ) {
+    if constexpr (TREE) {
+        // every tile below Sk: a node may see a new token behind its own position; no window over a tree
+    } else if constexpr (MQ) {
         if (p.window > 0) t0 = max(t0, max(0, pos_lo - p.window + 1) / 32);   // tiles entirely before the window of every row
         t1 = min(t1, pos_hi < 0 ? 0 : pos_hi / 32 + 1);                       // tiles entirely behind the last row's position
     } else if constexpr (PAGED) {
@@ -163,15 +177,21 @@
 
         // online softmax over this tile's 32 keys (16 per lane half), exp2 domain
         // (MQ: some row of the tile has a key behind its position -- the tile reaches past pos_lo -- or in front of its window)
-        const bool ragged = MQ ? (kv0 + 31 > pos_lo || (p.window > 0 && pos_hi - kv0 >= p.window))
-                               : (kv0 + 32 > Sk || (PAGED && p.window > 0 && Sk - 1 - kv0 >= p.window));
+        // (TREE: the tile reaches the new tokens)
+        const bool ragged = TREE ? kv0 + 31 >= Sk - Sq
+                          : MQ ? (kv0 + 31 > pos_lo || (p.window > 0 && pos_hi - kv0 >= p.window))
+                          : (kv0 + 32 > Sk || (PAGED && p.window > 0 && Sk - 1 - kv0 >= p.window));
         float mx = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float x = s[r] * c;
             if (ragged) {
                 const int kv = kv0 + crow(r, hi);
-                if constexpr (MQ) {
+                if constexpr (TREE) {
+                    const int bit = kv - (Sk - Sq);   // of the word: a new token (bit >= 0) is visible iff it lies below Sk and its bit is set
+                    const unsigned half = (bit & 32) ? tree_hi : tree_lo;
+                    if (bit >= 0 && (kv >= Sk || ((half >> (bit & 31)) & 1u) == 0u)) x = -INFINITY;
+                } else if constexpr (MQ) {
                     if (kv > pos || (p.window > 0 && pos - kv >= p.window)) x = -INFINITY;   // (pos < Sk: keys past Sk included)
                 } else {
                     if (kv >= Sk || (PAGED && p.window > 0 && Sk - 1 - kv >= p.window)) x = -INFINITY;

@@ -29,6 +29,11 @@
 // the cache (speculative verify, multi-token heads, a short prompt tail).  Query qi sits at position pos = Sk - Sq + qi and sees
 // key kv iff kv <= pos (and pos - kv < window): a per-lane limit, since a lane owns one packed row.  A row may see nothing of a
 // tile -- or nothing at all (pos < 0) -- so the softmax step keeps m = -inf, l = 0, O = 0 for it: an empty partial.
+//
+// TREE instances (fa_fwd_paged_tree_kernel: the MQ instances with a tree of draft tokens instead of a chain): the row
+// of query qi carries one 64-bit word; it sees every context key (kv < Sk - Sq) and new token t (key Sk - Sq + t < Sk) iff bit t of
+// its word is set.  The tiles run to Sk for every row, no window; only the tiles that reach Sk - Sq test the word.  Plan, workspace
+// and combine are the MQ instances'.
 #include <type_traits>
 
 #include "fa_device.h"
@@ -61,6 +66,7 @@ struct SplitParams {
     const float* k_scale;      // [Hkv] fp32, KvFp8 only
     const float* v_scale;
     const float* sinks;        // the combine's SINK instances: [Hq] fp32 sink logits; null: the plain instances
+    const long long* tree_mask;   // the TREE instances: [B, Sq] words, bit t of row (b, qi) = new token t is visible
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t skv_srd(const void* base, unsigned bytes) {
@@ -142,13 +148,19 @@ struct KvFp8 {
 // they stay the code they were, instruction for instruction.
 template <class T, int D, class KV, bool PAGED>
 __global__ void __launch_bounds__(256) fa_fwd_splitkv_kernel(const SplitParams p) {
-    constexpr bool MQ = false;
+    constexpr bool MQ = false, TREE = false;
 #include "fa_fwd_splitkv_body.inc"
 }
 
 template <class T, int D, class KV>
 __global__ void __launch_bounds__(256) fa_fwd_paged_query_kernel(const SplitParams p) {
-    constexpr bool PAGED = true, MQ = true;
+    constexpr bool PAGED = true, MQ = true, TREE = false;
+#include "fa_fwd_splitkv_body.inc"
+}
+
+template <class T, int D, class KV>
+__global__ void __launch_bounds__(256) fa_fwd_paged_tree_kernel(const SplitParams p) {
+    constexpr bool PAGED = true, MQ = true, TREE = true;
 #include "fa_fwd_splitkv_body.inc"
 }
 
@@ -344,7 +356,10 @@ int launch_wave_chunk(SplitParams p, const WaveChunkPlan& w, void* user_ws, uint
     if (ws.err != hipSuccess) return (int)ws.err;
     p.part = static_cast<float*>(ws.ptr);
     const dim3 grid((unsigned)w.nsplit, (unsigned)(w.rows_total / 32));
-    if constexpr (MQ) hipLaunchKernelGGL((fa_fwd_paged_query_kernel<T, D, KV>), grid, dim3(256), 0, stream, p);
+    if constexpr (MQ) {
+        if (p.tree_mask != nullptr) hipLaunchKernelGGL((fa_fwd_paged_tree_kernel<T, D, KV>), grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((fa_fwd_paged_query_kernel<T, D, KV>), grid, dim3(256), 0, stream, p);
+    }
     else hipLaunchKernelGGL((fa_fwd_splitkv_kernel<T, D, KV, PAGED>), grid, dim3(256), 0, stream, p);
     const int rc = (int)hipGetLastError();
     return rc != 0 ? rc : launch_combine<T, D>(p, combine_by_count, stream);
@@ -382,6 +397,7 @@ int launch_paged(const PagedArgs& a, hipStream_t stream) {
     p.block_size = a.block_size; p.max_blocks = a.max_blocks; p.window = a.window > 0 ? a.window : 0;
     p.k_scale = a.k_scale; p.v_scale = a.v_scale;
     p.sinks = MQ ? a.sinks : nullptr;
+    p.tree_mask = MQ ? a.tree_mask : nullptr;
     // The two cache kinds differ in two places beyond the data format.  Both differences reach the results (the last
     // bits, or which kernel runs), so each is kept as it was introduced; making them one is a change of its own.
     //  * scale (KV::kSignInQ): the 16-bit cache takes the contiguous kernel's convention (set_abs_scale); the FP8 cache
@@ -434,6 +450,7 @@ int launch_paged_decode(const PagedArgs& a, hipStream_t stream) { return launch_
 // PagedArgs::Sq query tokens per sequence (1 .. 64: the packed-row bound of this kernel family), PagedArgs::lse optional
 int launch_paged_query(const PagedArgs& a, hipStream_t stream) {
     if (a.Sq < 1 || a.Sq > 64) return -1;
+    if (a.tree_mask != nullptr && (a.window > 0 || a.sinks != nullptr)) return -1;   // (neither is defined over a tree)
     return launch_paged_kind<true>(a, stream);
 }
 

@@ -161,6 +161,10 @@ struct PagedArgs {
     // launch_paged_query only: per-head sink logits [Hq] fp32 on the device, or null -- a raw logit (not scaled) that
     // joins the softmax denominator and carries no value; a row that sees no key then gives out = 0 and lse = sinks[head]
     const float* sinks = nullptr;
+    // launch_paged_query only: a tree of new tokens instead of a chain.  [B, Sq] int64 words on the device or null; query i
+    // sees every context key (j < context_len - Sq) and new token t (key context_len - Sq + t) iff bit t of word (b, i) is set.  No window,
+    // no sinks (-1).  The chain words (2 << i) - 1 give the bits of the call without a tree
+    const long long* tree_mask = nullptr;
 };
 
 // Rotary embedding pass (rope_gfx950.hip): x [nheads, S, D] with `pitch` elements per row, tables [>= S + pos_offset, D/2]
@@ -259,6 +263,9 @@ struct PagedPrefillArgs {
     const float* k_scale = nullptr;     // kCacheFp8E4M3 only
     const float* v_scale = nullptr;
     const float* sinks = nullptr;       // [Hq] fp32 sink logits or null, as PagedArgs::sinks
+    // [T] int64 words or null: a sequence with n <= 64 carries a tree -- token i sees every context key (j < L - n) and
+    // new token t iff bit t of word s + i is set; a longer one keeps the causal rule and its words are not read.  No window, no sinks (-1)
+    const long long* tree_mask = nullptr;
 };
 // workgroups of the launch: ceil(min(max_seqlen_q, T) * (Hq / Hkv) / 128) x Hkv x B (tests, tools)
 long long paged_prefill_grid(const PagedPrefillArgs& a);

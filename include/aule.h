@@ -726,6 +726,79 @@ int32_t aule_attention_paged_query_sink_ex(const aule_paged_query_sink_desc* des
 uint64_t aule_attention_varlen_sink_backward_workspace_size(const aule_varlen_sink_bwd_desc* desc);
 uint64_t aule_attention_paged_query_sink_workspace_size(const aule_paged_query_sink_desc* desc);
 
+/* TREE MASKS (additive): the paged query and the paged prefill with a TREE of new tokens instead of a chain -- the verify step of   */
+/* tree drafters (EAGLE, Medusa, SpecInfer): all nodes are appended to the cache and verified in one call; a node sees the cached    */
+/* context and its ancestors, not its siblings or cousins.  tree_mask holds one int64 word per new token on the DEVICE, read as 64   */
+/* bits by the kernel on every launch (no host copy, no synchronisation, capturable).  For a sequence with L keys in the cache      */
+/* (after the twin's clamps) and n new tokens, new token t is key L - n + t; query token i sees key j iff 0 <= j < L and             */
+/*     j < L - n  (a context key)        or        bit j - (L - n) of tree_mask[row i] is set.                                       */
+/* Any bit pattern is legal: no self bit is implied, no order required; bits at or above n and bits that name a key below 0 are      */
+/* ignored.  A query at a negative position gives zeros, a row that sees no key out = 0 and lse = -inf, keys at or beyond L are      */
+/* never read.  The chain words tree_mask[i] = (2 << i) - 1 give out and lse of the twin entry BIT FOR BIT (finite cached data).    */
+/* Query entry: tree_mask [batch, seq_q], row b * seq_q + i.  Prefill entry: tree_mask [total_tokens], indexed by packed token; a   */
+/* sequence carries a tree iff its clamped n <= 64 (decided on the device), a longer one (a prompt chunk in the same step) keeps the */
+/* twin's causal rule and its words are not read.  Every other rule, the workspace included, is the twin's: each descriptor is its   */
+/* twin field for field plus tree_mask and is checked by the twin's checker.  Refused with -3 and a reason, without aule_init():     */
+/* a NULL tree_mask when there is work, and window_size > 0 (a window is not defined over a tree).  Not built: sliding windows or    */
+/* sink logits with a tree, the cascade and the MLA entries, head_dim 256, more than 64 tree tokens per sequence, any backward.      */
+typedef struct aule_paged_query_tree_desc {
+    uint32_t struct_size;      /* = sizeof(aule_paged_query_tree_desc) = 160 */
+    int32_t dtype;
+    uint32_t batch, heads_q, heads_kv, head_dim;
+    uint32_t block_size;
+    uint32_t max_blocks;
+    float scale;
+    int32_t window_size;       /* <= 0 (a window is refused) */
+    int32_t device;
+    void* stream;              /* offset 48 */
+    const void* q;
+    const void* k_cache;
+    const void* v_cache;
+    const int32_t* block_tables;
+    const int32_t* context_lens;
+    void* out;
+    void* workspace;           /* offset 104; optional, size from aule_attention_paged_query_tree_workspace_size() */
+    uint64_t workspace_bytes;
+    const float* k_scale;      /* offset 120 */
+    const float* v_scale;      /* offset 128 */
+    float* lse;                /* offset 136; optional (NULL to skip) */
+    uint32_t seq_q;            /* offset 144; 1 .. 64 */
+    int32_t cache_dtype;       /* offset 148 */
+    const int64_t* tree_mask;  /* offset 152; [batch, seq_q] int64, device (required) */
+} aule_paged_query_tree_desc;
+typedef struct aule_paged_prefill_tree_desc {
+    uint32_t struct_size;      /* = sizeof(aule_paged_prefill_tree_desc) = 160 */
+    int32_t dtype;
+    int32_t cache_dtype;       /* offset 8 */
+    uint32_t batch;            /* offset 12 */
+    uint32_t heads_q, heads_kv, head_dim;
+    uint32_t block_size;       /* offset 28 */
+    uint32_t max_blocks;       /* offset 32 */
+    uint32_t total_tokens;     /* offset 36 */
+    uint32_t max_seqlen_q;     /* offset 40 */
+    float scale;               /* offset 44 */
+    int32_t window_size;       /* offset 48; <= 0 (a window is refused) */
+    int32_t device;            /* offset 52 */
+    int64_t q_token_stride;    /* offset 56 */
+    void* stream;              /* offset 64 */
+    const void* q;             /* offset 72 */
+    const void* k_cache;       /* offset 80 */
+    const void* v_cache;       /* offset 88 */
+    const int32_t* block_tables;   /* offset 96 */
+    const int32_t* context_lens;   /* offset 104 */
+    const int32_t* cu_seqlens_q;   /* offset 112 */
+    void* out;                 /* offset 120 */
+    float* lse;                /* offset 128; optional (NULL to skip) */
+    const float* k_scale;      /* offset 136 */
+    const float* v_scale;      /* offset 144 */
+    const int64_t* tree_mask;  /* offset 152; [total_tokens] int64, device (required) */
+} aule_paged_prefill_tree_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_paged_query_tree_ex(const aule_paged_query_tree_desc* desc);
+int32_t aule_attention_paged_prefill_tree_ex(const aule_paged_prefill_tree_desc* desc);
+/* Host logic only; pointers in the descriptor are not read: aule_attention_paged_query_workspace_size() of the same problem.        */
+uint64_t aule_attention_paged_query_tree_workspace_size(const aule_paged_query_tree_desc* desc);
+
 /* Merge of two attention states (additive): out_a, out_b [rows, heads, head_dim] fp16 / bf16 are attention outputs of the same    */
 /* queries over two DISJOINT key sets, lse_a, lse_b [rows, heads] fp32 the natural logs of their softmax denominators (the lse of  */
 /* the calls above).  With M = max(lse_a, lse_b) and w_x = exp(lse_x - M):                                                          */
