@@ -204,3 +204,7 @@ def test_aule_backend_env(monkeypatch):
             monkeypatch.setenv("AULE_BACKEND", name)
             assert lib.aule_init() == -1
             assert b"no HIP device" in lib.aule_get_error()    # went on to the device probe: the variable was a no-op
+    # The library was shut down above.  Where a GPU is present and an earlier test of the same process (tests/test_api_contract.py) went
+    # through get_lib(), the Python flag would still say "initialised" and the first in-process GPU test after this one would get
+    # "Library not initialized" (pytest tests without -m gpu on a GPU machine; -m gpu never runs this test).  The next get_lib() initialises.
+    _capi._initialized = False

@@ -166,8 +166,38 @@ class Run:
 GRADS = ("dq", "dk_nope", "dk_pe", "dv")
 
 
-def _judge(p, res, oracle, causal, what, scale=None, forward=True):
-    """res: name -> tensor over the whole packed axes.  Checks every owned row; prints the maxima and returns them."""
+def rounding_model(p, causal, scale=None):
+    """per sequence {name: max |g_model - g|} for dq, dk_nope, dk_pe, and {name: max(1, max|g|)}: g the fp64 gradient formula
+    dS = P (dP - delta) and g_model the same with delta = rowsum(dO * O) taken from O rounded to the storage dtype, which is what the backward
+    entry is given (dv = P^T dO does not read delta).  NumPy on the quantised inputs alone: no GPU, no library call."""
+    code, res = CODE[causal], []
+    scale = DQ ** -0.5 if scale is None else scale
+    for sq, n, sk, L in p.sequences():
+        err, norm = dict.fromkeys(GRADS, 0.0), dict.fromkeys(GRADS, 1.0)
+        if n and L:
+            q, do, v = (x.astype(np.float64) for x in (p.q[sq:sq + n], p.dout[sq:sq + n], p.v[sk:sk + L]))
+            key = np.concatenate([p.kn[sk:sk + L], np.repeat(p.kp[sk:sk + L, None, :], p.H, axis=1)], axis=2).astype(np.float64)
+            s = np.where(fw._visible(n, L, code)[None], np.einsum("nhd,lhd->hnl", q, key) * scale, -np.inf)
+            m = s.max(axis=-1, keepdims=True)
+            e = np.exp(s - np.where(np.isfinite(m), m, 0.0))
+            den = e.sum(axis=-1, keepdims=True)
+            P = e / np.where(den > 0, den, 1.0)
+            O, dP = np.einsum("hnl,lhd->nhd", P, v), np.einsum("nhd,lhd->hnl", do, v)
+            g = []
+            for Ouse in (O, quantize(O, p.dtype).astype(np.float64)):
+                dS = P * (dP - (do * Ouse).sum(axis=-1).T[..., None])
+                dk = np.einsum("hnl,nhd->lhd", dS, q) * scale
+                g.append(dict(dq=np.einsum("hnl,lhd->nhd", dS, key) * scale, dk_nope=dk[..., :DN], dk_pe=dk[..., DN:].sum(axis=1)))
+            for name in g[0]:
+                err[name] = float(np.abs(g[1][name] - g[0][name]).max())
+                norm[name] = max(1.0, float(np.abs(g[0][name]).max()))
+        res.append((err, norm))
+    return res
+
+
+def _judge(p, res, oracle, causal, what, scale=None, forward=True, floors=None):
+    """res: name -> tensor over the whole packed axes.  Checks every owned row; prints the maxima and returns them.
+    floors: per sequence {name: absolute error allowed whatever the element} (the randomised draws: 4 x rounding_model's error)"""
     code = CODE[causal]
     if forward:
         fw._judge(p, res, oracle, causal, what, scale=scale)
@@ -196,10 +226,11 @@ def _judge(p, res, oracle, causal, what, scale=None, forward=True):
         rq, rk, rv = oracle.np_bwd_f64(t(p.q[sq + a:sq + e]), t(key), t(wide(p.v[sk:sk + L])), t(wide(p.dout[sq + a:sq + e])), causal=sub, scale=scale)
         assert not rv[..., DV:].any()
         rv = rv[..., :DV]
-        worst["dq"] = max(worst["dq"], _check_grad(dq[sq + a:sq + e].transpose(1, 0, 2)[None], rq, p.dtype, tag + " dq"))
-        worst["dk_nope"] = max(worst["dk_nope"], _check_grad(dkn[sk:sk + L].transpose(1, 0, 2)[None], rk[..., :DN], p.dtype, tag + " dk_nope"))
+        fl = floors[b] if floors is not None else dict.fromkeys(GRADS, 0.0)
+        worst["dq"] = max(worst["dq"], _check_grad(dq[sq + a:sq + e].transpose(1, 0, 2)[None], rq, p.dtype, tag + " dq", fl["dq"]))
+        worst["dk_nope"] = max(worst["dk_nope"], _check_grad(dkn[sk:sk + L].transpose(1, 0, 2)[None], rk[..., :DN], p.dtype, tag + " dk_nope", fl["dk_nope"]))
         worst["dv"] = max(worst["dv"], _check_grad(dv[sk:sk + L].transpose(1, 0, 2)[None], rv, p.dtype, tag + " dv"))
-        worst["dk_pe"] = max(worst["dk_pe"], _check_grad(dkp[sk:sk + L], rk[0, :, :, DN:].sum(axis=0), p.dtype, tag + " dk_pe"))
+        worst["dk_pe"] = max(worst["dk_pe"], _check_grad(dkp[sk:sk + L], rk[0, :, :, DN:].sum(axis=0), p.dtype, tag + " dk_pe", fl["dk_pe"]))
     print("%s: of max(1, max|grad|): dq %.2e dk_nope %.2e dk_pe %.2e dv %.2e" % (what, worst["dq"], worst["dk_nope"], worst["dk_pe"], worst["dv"]))
     return worst
 

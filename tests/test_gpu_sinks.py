@@ -61,9 +61,10 @@ def _visible(n, L, code, window):
     return vis
 
 
-def _sink_values(Hq, lmax):
+def _sink_values(Hq, lmax, rot=0):
+    """head h takes entry (h + rot) % 5 of the cycle"""
     cycle = [NINF, -30.0, 0.0, math.log(lmax) + 0.5, math.log(lmax) + 6.0]
-    return [cycle[h % 5] for h in range(Hq)]
+    return [cycle[(h + rot) % 5] for h in range(Hq)]
 
 
 def _ref_seq(q, k, v, sinks, code, window, scale):
@@ -88,23 +89,28 @@ def _ref_seq(q, k, v, sinks, code, window, scale):
 
 
 class Batch:
-    """A packed batch: quantised inputs as fp64 CPU tensors, the owned ranges after the clamps, the sink logits."""
+    """A packed batch: quantised inputs as fp64 CPU tensors, the owned ranges after the clamps, the sink logits.
+    scale: None for 1 / sqrt(D) (scale_arg is what a call is given); rot: the cycle of sink logits starts that many entries in;
+    sinks_dtype: the logits rounded to that storage dtype, which is what the judge then sees."""
 
-    def __init__(self, seed, dtype, Hq, Hkv, D, code, window, ns=NS, ls=LS, ns_raw=NS_RAW, max_sq=MAX_SQ, lead=LEAD, tail=TAIL):
+    def __init__(self, seed, dtype, Hq, Hkv, D, code, window, ns=NS, ls=LS, ns_raw=NS_RAW, max_sq=MAX_SQ, lead=LEAD, tail=TAIL, scale=None,
+                 rot=0, sinks_dtype=None):
         import torch
         gen = torch.Generator().manual_seed(seed)
         self.dtype, self.tdt, self.Hq, self.Hkv, self.D, self.code, self.window = dtype, torch_dtype(dtype), Hq, Hkv, D, code, window
-        self.scale = 1.0 / math.sqrt(D)
+        self.scale_arg, self.scale = scale, 1.0 / math.sqrt(D) if scale is None else scale
         self.cu_q = [lead + int(x) for x in np.concatenate([[0], np.cumsum(ns_raw)])]
         self.cu_k = [2 + int(x) for x in np.concatenate([[0], np.cumsum(ls)])]
         self.Tq, self.Tk = self.cu_q[-1] + tail, self.cu_k[-1] + 4
-        self.max_sq, self.max_sk = max_sq, max(ls)
+        self.max_sq, self.max_sk = max_sq, max(max(ls), 1)
         self.seqs = [(self.cu_q[b], min(ns_raw[b], max_sq), self.cu_k[b], ls[b]) for b in range(len(ns))]
         assert [s[1] for s in self.seqs] == list(ns)
         rnd = lambda *shape: torch.randn(*shape, generator=gen).to(self.tdt)   # noqa: E731
         self.q, self.k, self.v, self.dout = rnd(self.Tq, Hq, D), rnd(self.Tk, Hkv, D), rnd(self.Tk, Hkv, D), rnd(self.Tq, Hq, D)
         self.lmax = max(int(_visible(n, L, code, window).sum(dim=1).max()) if n and L else 0 for _, n, _, L in self.seqs)
-        self.sinks = torch.tensor(_sink_values(Hq, max(self.lmax, 1)), dtype=torch.float32)
+        self.sinks = torch.tensor(_sink_values(Hq, max(self.lmax, 1), rot), dtype=torch.float32)
+        if sinks_dtype is not None:
+            self.sinks = self.sinks.to(torch_dtype(sinks_dtype)).float()
         self.vmax = float(self.v.float().abs().max())
 
     def owned(self):
@@ -188,17 +194,18 @@ def _check_forward(b, ref, out, lse, what, rows=None):
     assert torch.equal(lse[blind], want[blind]), what + ": lse of a row without a key must be sinks[h] exactly"
     print("%s: max|out err| %.3e (atol %.2e), max|lse err| %.3e, %d rows x heads without a key"
           % (what, float(err.max()), atol, float(lerr.max()) if lerr.numel() else 0.0, int(blind.sum())))
+    return float(err.max()) if err.numel() else 0.0, float(lerr.max()) if lerr.numel() else 0.0
 
 
-def _check_grad(got, ref, dtype, what):
-    """tests/test_gpu_varlen.py::_check_grad"""
+def _check_grad(got, ref, dtype, what, floor=0.0):
+    """tests/test_gpu_varlen.py::_check_grad (floor: as there, 0 in this file)"""
     atol, rtol = BWD_TOL[dtype]
     ref = ref.numpy()
     scale = max(1.0, float(np.abs(ref).max())) if ref.size else 1.0
     got = got.detach().double().cpu().numpy()
     assert np.isfinite(got).all(), what + ": non-finite gradient"
     err = np.abs(got - ref)
-    bad = err > atol * scale + rtol * np.abs(ref)
+    bad = err > np.maximum(atol * scale + rtol * np.abs(ref), floor)
     assert not bad.any(), "%s: %d elements out of bound, max err %.3e (max|grad| %.3g)" % (what, int(bad.sum()), err.max(), scale)
     return float(err.max() / scale) if ref.size else 0.0
 
@@ -250,15 +257,15 @@ def test_varlen_forward_padded_head_dim():
 
 
 class Paged:
-    """the sequences of a Batch behind a paged cache: block size 16, the blocks handed out in a shuffled order, 16-bit or FP8 (per-head
-    scales: aule.quantize_kv_cache_fp8 on the CPU; the reference reads the dequantised values)"""
+    """the sequences of a Batch behind a paged cache: block size `bs`, the blocks handed out in a shuffled order, 16-bit or FP8 (per-head
+    scales: aule.quantize_kv_cache_fp8 on the CPU; the reference reads the dequantised values).  device="cpu": the reference side alone"""
 
-    def __init__(self, b, fp8, bs=16, seed=3):
+    def __init__(self, b, fp8, bs=16, seed=3, extra_cols=1, device="cuda"):
         import torch
         import aule
         self.b, self.fp8 = b, fp8
         nblk = [-(-L // bs) for _, _, _, L in b.seqs]
-        self.max_blocks = max(nblk) + 1
+        self.bs, self.max_blocks = bs, max(nblk) + extra_cols
         order = torch.randperm(sum(nblk) + 2, generator=torch.Generator().manual_seed(seed)).tolist()
         kc = torch.zeros(len(order), bs, b.Hkv, b.D, dtype=b.tdt)
         vc = torch.zeros_like(kc)
@@ -275,7 +282,7 @@ class Paged:
         if fp8:
             kc, ks = aule.quantize_kv_cache_fp8(kc)
             vc, vs = aule.quantize_kv_cache_fp8(vc)
-            self.scales = dict(k_scale=ks.cuda(), v_scale=vs.cuda())
+            self.scales = dict(k_scale=ks.to(device), v_scale=vs.to(device))
             kd, vd = kc.float() * ks.view(1, 1, -1, 1), vc.float() * vs.view(1, 1, -1, 1)
             self.k_ref, self.v_ref = torch.zeros(b.Tk, b.Hkv, b.D), torch.zeros(b.Tk, b.Hkv, b.D)
             for i, (_, _, sk, L) in enumerate(b.seqs):
@@ -283,10 +290,82 @@ class Paged:
                     rows = min(bs, L - j * bs)
                     self.k_ref[sk + j * bs:sk + j * bs + rows] = kd[self.bt[i, j], :rows]
                     self.v_ref[sk + j * bs:sk + j * bs + rows] = vd[self.bt[i, j], :rows]
-        self.kc, self.vc = kc.cuda(), vc.cuda()
+        self.kc, self.vc = kc.to(device), vc.to(device)
 
     def reference(self, **kw):
         return self.b.reference(k=self.k_ref, v=self.v_ref, **kw)
+
+
+def _raw_prefill(torch, b, p, q_pad=0):
+    """aule_attention_paged_prefill_sink_ex on the Batch b behind the Paged p, into out / lse pre-filled with 0xFF; q_pad > 0: q is a slice
+    of a projection that much wider per token whose other columns hold NaN bits.  Returns (out, lse) over all Tq rows."""
+    from aule import _capi
+    lib = _capi.get_lib()
+    w = b.Hq * b.D
+    wide = torch.full((b.Tq, w + q_pad), -1, dtype=torch.int16, device="cuda").view(b.tdt)
+    wide[:, :w] = b.q.cuda().view(b.Tq, w)
+    out = torch.full((b.Tq, b.Hq, b.D), -1, dtype=torch.int16, device="cuda").view(b.tdt)
+    lse = torch.full((b.Tq, b.Hq), -1, dtype=torch.int32, device="cuda").view(torch.float32)
+    bt, cl, cu, sinks = p.bt.cuda(), p.cl.cuda(), torch.tensor(b.cu_q, dtype=torch.int32, device="cuda"), b.sinks.cuda()
+    d = _capi.PagedPrefillSinkDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype, d.cache_dtype = hostile.DTYPE_CODE[b.dtype], 1 if p.fp8 else 0
+    d.batch, d.heads_q, d.heads_kv, d.head_dim = len(b.seqs), b.Hq, b.Hkv, b.D
+    d.block_size, d.max_blocks, d.total_tokens, d.max_seqlen_q = p.bs, p.max_blocks, b.Tq, b.max_sq
+    d.scale, d.window_size, d.device = 0.0 if b.scale_arg is None else b.scale_arg, b.window, torch.cuda.current_device()
+    d.q_token_stride = w + q_pad
+    d.stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    d.q, d.k_cache, d.v_cache, d.out, d.lse = wide.data_ptr(), p.kc.data_ptr(), p.vc.data_ptr(), out.data_ptr(), lse.data_ptr()
+    d.block_tables, d.context_lens, d.cu_seqlens_q, d.sinks = bt.data_ptr(), cl.data_ptr(), cu.data_ptr(), sinks.data_ptr()
+    if p.fp8:
+        d.k_scale, d.v_scale = p.scales["k_scale"].data_ptr(), p.scales["v_scale"].data_ptr()
+    _capi.check(lib.aule_attention_paged_prefill_sink_ex(ctypes.byref(d)), "paged prefill sink")
+    torch.cuda.synchronize()
+    return out, lse
+
+
+def _unowned_still_poisoned(torch, b, tensors):
+    """the rows of no sequence still hold the 0xFF they were filled with"""
+    free = ~b.owned().cuda()
+    for name, t in tensors.items():
+        assert bool((hostile.as_bytes(torch, t[free]) == POISON).all()), name + ": a row that belongs to no sequence was written"
+
+
+def dsinks_model(b, ref):
+    """(exact, model) [Hq] fp64 from the reference alone: dsinks[h] = -sum over the owned rows of w[row, h] * delta[row, h], w the sink
+    weight and delta = rowsum(dO * O) -- with O in fp64, which is autograd's dsinks, and with O rounded to the storage dtype first, which is
+    what a backward that reads the stored O computes (the dominant term of the kernel's error)"""
+    own = b.owned()
+    dout, w = b.dout.double()[own], ref["w"][own]
+    exact = -(w * (dout * ref["out"][own]).sum(dim=-1)).sum(dim=0)
+    model = -(w * (dout * ref["out"][own].to(b.tdt).double()).sum(dim=-1)).sum(dim=0)
+    return exact, model
+
+
+def grads_model(b, ref):
+    """(dq, dk) fp64 from the reference alone: the gradient formula dS = P (dP - delta), dq = scale dS K, dk = scale dS^T Q with
+    delta = rowsum(dO * O) taken from O rounded to the storage dtype, which is what the backward entry is given (dv = P^T dO does not read
+    delta).  With the unrounded O the same formula is autograd's gradient, so both are returned: ((dq, dk) exact, (dq, dk) model)."""
+    import torch
+
+    def run(rounded):
+        dq, dk = torch.zeros_like(ref["dq"]), torch.zeros_like(ref["dk"])
+        g = b.Hq // b.Hkv
+        for sq, n, sk, L in b.seqs:
+            if n == 0 or L == 0:
+                continue
+            q, do = b.q[sq:sq + n].double(), b.dout[sq:sq + n].double()
+            kk, vv = (x[sk:sk + L].double().repeat_interleave(g, dim=1) for x in (b.k, b.v))
+            s = torch.einsum("nhd,lhd->hnl", q, kk) * b.scale
+            vis = _visible(n, L, b.code, b.window)[None] & torch.isfinite(ref["lse"][sq:sq + n].T)[..., None]
+            P = torch.where(vis, torch.exp(s - ref["lse"][sq:sq + n].T[..., None]), torch.zeros_like(s))
+            O = ref["out"][sq:sq + n]
+            delta = (do * (O.to(b.tdt).double() if rounded else O)).sum(dim=-1).T[..., None]
+            dS = P * (torch.einsum("nhd,lhd->hnl", do, vv) - delta)
+            dq[sq:sq + n] = torch.einsum("hnl,lhd->nhd", dS, kk) * b.scale
+            dk[sk:sk + L] = (torch.einsum("hnl,nhd->lhd", dS, q) * b.scale).view(L, b.Hkv, g, b.D).sum(dim=2)
+        return dq, dk
+    return run(False), run(True)
 
 
 PREFILL_CASES = [(dt, Hq, Hkv, D, window, fp8) for (Hq, Hkv, D) in HEADS for dt in ("bf16", "fp16") for window in (-1, 17) for fp8 in (False, True)]
@@ -456,6 +535,7 @@ def _raw_run(torch, b, pattern):
     d.dtype, d.batch, d.heads_q, d.heads_kv, d.head_dim = hostile.DTYPE_CODE[b.dtype], len(b.seqs), b.Hq, b.Hkv, b.D
     d.total_q, d.total_k, d.max_seqlen_q, d.max_seqlen_k = b.Tq, b.Tk, b.max_sq, b.max_sk
     d.causal, d.window_size, d.device = b.code, b.window, torch.cuda.current_device()
+    d.scale = 0.0 if b.scale_arg is None else b.scale_arg
     d.q_token_stride, d.k_token_stride, d.v_token_stride = b.Hq * b.D, b.Hkv * b.D, b.Hkv * b.D
     ws = int(lib.aule_attention_varlen_sink_backward_workspace_size(ctypes.byref(d)))
     assert ws > (b.Tq * b.Hq * 4 + 255) // 256 * 256

@@ -34,24 +34,30 @@ def random_parents(torch, g, n):
     return (torch.rand(n, generator=g) * (torch.arange(n) + 1)).long() - 1
 
 
+WORD_KINDS = ("tree", "random", "emptied", "ones", "chain")
+
+
+def words_of_kind(torch, g, kind, Sq):
+    """[Sq] int64 from the generator g: a random tree, uniform random words, random words with emptied rows, all ones, or the chain"""
+    import aule
+    kind = WORD_KINDS.index(kind) if isinstance(kind, str) else kind
+    if kind == 0:
+        return aule.tree_mask_from_parents(random_parents(torch, g, Sq))
+    if kind == 3:
+        return torch.full((Sq,), -1, dtype=torch.int64)
+    if kind == 4:
+        return chain_words(torch, Sq)
+    w = torch.randint(-2 ** 63, 2 ** 63 - 1, (Sq,), generator=g, dtype=torch.int64)
+    if kind == 2:
+        w[torch.rand(Sq, generator=g) < 0.4] = 0
+        w[Sq // 2] = 0
+    return w
+
+
 def draw_words(torch, seed, B, Sq):
     """[B, Sq] int64: sequence b takes pattern b % 4 -- a random tree, uniform random words, random words with emptied rows, all ones"""
-    import aule
     g = torch.Generator().manual_seed(seed)
-    rows = []
-    for b in range(B):
-        kind = b % 4
-        if kind == 0:
-            w = aule.tree_mask_from_parents(random_parents(torch, g, Sq))
-        elif kind == 3:
-            w = torch.full((Sq,), -1, dtype=torch.int64)
-        else:
-            w = torch.randint(-2 ** 63, 2 ** 63 - 1, (Sq,), generator=g, dtype=torch.int64)
-            if kind == 2:
-                w[torch.rand(Sq, generator=g) < 0.4] = 0
-                w[Sq // 2] = 0
-        rows.append(w)
-    return torch.stack(rows)
+    return torch.stack([words_of_kind(torch, g, b % 4, Sq) for b in range(B)])
 
 
 def words_are_not_trivial(seqs):
@@ -86,7 +92,7 @@ def make_kv(torch, g, dtype, kind, lens, Hkv, D):
     return dev, f64, scales
 
 
-def paginate(torch, g, dev, bs, shared=None):
+def paginate(torch, g, dev, bs, shared=None, extra_cols=2):
     """scatter the sequences' rows into shuffled pages: (k_cache, v_cache, block_tables) on the CPU; unused table columns point at block 0,
     unused rows of a page hold finite junk"""
     nblk = [(k.shape[0] + bs - 1) // bs for k, _ in dev]
@@ -96,7 +102,7 @@ def paginate(torch, g, dev, bs, shared=None):
         caches = [torch.randint(0, CODE_8 + 1, (num_blocks, bs) + tuple(proto.shape[1:]), generator=g).to(torch.uint8) for _ in range(2)]
     else:
         caches = [torch.randn((num_blocks, bs) + tuple(proto.shape[1:]), generator=g).to(proto.dtype) for _ in range(2)]
-    bt = torch.zeros(len(dev), max(max(nblk), 1) + 2, dtype=torch.int32)
+    bt = torch.zeros(len(dev), max(max(nblk), 1) + extra_cols, dtype=torch.int32)
     perm = torch.randperm(num_blocks, generator=g)
     used = 0
     for b, pair in enumerate(dev):
@@ -110,11 +116,11 @@ def paginate(torch, g, dev, bs, shared=None):
     return caches[0], caches[1], bt
 
 
-def to_device(torch, kc, vc, scales):
+def to_device(torch, kc, vc, scales, device="cuda"):
     if kc.dtype == torch.uint8:
-        kc, vc = kc.cuda().view(torch.float8_e4m3fn), vc.cuda().view(torch.float8_e4m3fn)
-        return kc, vc, dict(k_scale=scales[0].float().cuda(), v_scale=scales[1].float().cuda())
-    return kc.cuda(), vc.cuda(), {}
+        kc, vc = kc.to(device).view(torch.float8_e4m3fn), vc.to(device).view(torch.float8_e4m3fn)
+        return kc, vc, dict(k_scale=scales[0].float().to(device), v_scale=scales[1].float().to(device))
+    return kc.to(device), vc.to(device), {}
 
 
 def visibility(torch, L, n, words, causal=False):
@@ -171,33 +177,36 @@ def compare(torch, out, lse, ref, lref, dtype, vmax, what, factor=1.0, lse_atol=
 
 
 class QueryProblem:
-    """B sequences of Sq new tokens each; q [B, Hq, Sq, D]"""
+    """B sequences of Sq new tokens each; q [B, Hq, Sq, D].  scale: None for 1 / sqrt(D); device="cpu": the judge's side alone"""
 
-    def __init__(self, torch, seed, dtype, kind, Hq, Hkv, Sq, D, bs, lens):
+    def __init__(self, torch, seed, dtype, kind, Hq, Hkv, Sq, D, bs, lens, scale=None, extra_cols=2, device="cuda"):
         g = torch.Generator().manual_seed(seed)
-        self.dtype, self.Sq, self.lens, self.D = dtype, Sq, list(lens), D
+        self.dtype, self.Sq, self.lens, self.D, self.scale = dtype, Sq, list(lens), D, scale
         dev, self.f64, scales = make_kv(torch, g, dtype, kind, lens, Hkv, D)
-        kc, vc, bt = paginate(torch, g, dev, bs)
-        self.kc, self.vc, self.scales = to_device(torch, kc, vc, scales)
+        kc, vc, bt = paginate(torch, g, dev, bs, extra_cols=extra_cols)
+        self.kc, self.vc, self.scales = to_device(torch, kc, vc, scales, device)
         qs = 0.25 if kind == "fp8" else 1.0
-        self.q = (qs * torch.randn(len(lens), Hq, Sq, D, generator=g)).to(torch_dtype(dtype)).cuda()
-        self.bt, self.cl = bt.cuda(), torch.tensor(lens, dtype=torch.int32).cuda()
+        self.q = (qs * torch.randn(len(lens), Hq, Sq, D, generator=g)).to(torch_dtype(dtype)).to(device)
+        self.bt, self.cl = bt.to(device), torch.tensor(lens, dtype=torch.int32).to(device)
         self.vmax = max(float(v.abs().max()) for _, v in self.f64 if v.numel()) if any(lens) else 1.0
 
     def run(self, words):
         import aule
-        return aule.flash_attention_paged_query_tree(self.q, self.kc, self.vc, words, self.bt, self.cl, return_lse=True, **self.scales)
+        return aule.flash_attention_paged_query_tree(self.q, self.kc, self.vc, words, self.bt, self.cl, scale=self.scale, return_lse=True,
+                                                     **self.scales)
 
     def twin(self):
         import aule
-        return aule.flash_attention_paged_query(self.q, self.kc, self.vc, self.bt, self.cl, return_lse=True, **self.scales)
+        return aule.flash_attention_paged_query(self.q, self.kc, self.vc, self.bt, self.cl, scale=self.scale, return_lse=True, **self.scales)
 
-    def judge(self, torch, words):
+    def judge(self, torch, words, causal=False):
+        """causal: the chain's rule for every sequence instead of its words"""
         outs, lses = [], []
         for b, L in enumerate(self.lens):
-            K, V = (x.cuda() for x in self.f64[b])
-            vis = visibility(torch, L, self.Sq, words[b])
-            o, l = judge(torch, self.q[b].double().permute(1, 0, 2).contiguous(), K, V, vis, 1.0 / math.sqrt(self.D))
+            K, V = (x.to(self.q.device) for x in self.f64[b])
+            vis = visibility(torch, L, self.Sq, words[b], causal=causal)
+            o, l = judge(torch, self.q[b].double().permute(1, 0, 2).contiguous(), K, V, vis,
+                         1.0 / math.sqrt(self.D) if self.scale is None else self.scale)
             outs.append(o.permute(1, 0, 2))
             lses.append(l.permute(1, 0))
         return torch.stack(outs), torch.stack(lses)
@@ -242,23 +251,30 @@ class PrefillProblem:
     that no sequence owns"""
     NL = [(100, 300), (64, 141), (7, 200), (1, 50), (0, 30), (20, 11)]   # L - n = 200, 77, 193, 49, 30, -9
 
-    def __init__(self, torch, seed, dtype, kind, Hq=8, Hkv=2, D=64, bs=16, tail=5, nl=None):
+    def __init__(self, torch, seed, dtype, kind, Hq=8, Hkv=2, D=64, bs=16, tail=5, nl=None, lead=0, q_pad=0, scale=None, extra_cols=2,
+                 device="cuda"):
+        """lead: rows of q in front of the first sequence (the owned rows are lead .. lead + owned); q_pad > 0: q is a slice of a projection
+        that much wider per token whose other columns hold NaN bits; scale: None for 1 / sqrt(D); device="cpu": the judge's side alone"""
         g = torch.Generator().manual_seed(seed)
         self.nl = list(self.NL if nl is None else nl)
-        self.dtype, self.D, self.Hq = dtype, D, Hq
+        self.dtype, self.D, self.Hq, self.scale, self.lead = dtype, D, Hq, scale, lead
         ns, lens = [n for n, _ in self.nl], [L for _, L in self.nl]
         dev, self.f64, scales = make_kv(torch, g, dtype, kind, lens, Hkv, D)
-        kc, vc, bt = paginate(torch, g, dev, bs)
-        self.kc, self.vc, self.scales = to_device(torch, kc, vc, scales)
+        kc, vc, bt = paginate(torch, g, dev, bs, extra_cols=extra_cols)
+        self.kc, self.vc, self.scales = to_device(torch, kc, vc, scales, device)
         self.owned = sum(ns)
-        self.T = self.owned + tail
+        self.T = lead + self.owned + tail
         qs = 0.25 if kind == "fp8" else 1.0
-        self.q = (qs * torch.randn(self.T, Hq, D, generator=g)).to(torch_dtype(dtype)).cuda()
-        self.starts = [sum(ns[:b]) for b in range(len(ns) + 1)]
-        self.bt, self.cl = bt.cuda(), torch.tensor(lens, dtype=torch.int32).cuda()
-        self.cu = torch.tensor(self.starts, dtype=torch.int32).cuda()
-        self.max_n = max(ns)
-        self.vmax = max(float(v.abs().max()) for _, v in self.f64 if v.numel())
+        self.q = (qs * torch.randn(self.T, Hq, D, generator=g)).to(torch_dtype(dtype)).to(device)
+        if q_pad:
+            wide = torch.full((self.T, Hq * D + q_pad), -1, dtype=torch.int16, device=device).view(self.q.dtype)
+            wide[:, :Hq * D] = self.q.view(self.T, -1)
+            self.q = wide[:, :Hq * D].view(self.T, Hq, D)
+        self.starts = [lead + sum(ns[:b]) for b in range(len(ns) + 1)]
+        self.bt, self.cl = bt.to(device), torch.tensor(lens, dtype=torch.int32).to(device)
+        self.cu = torch.tensor(self.starts, dtype=torch.int32).to(device)
+        self.max_n = max(max(ns), 1)
+        self.vmax = max([float(v.abs().max()) for _, v in self.f64 if v.numel()] or [1.0])
 
     def words(self, torch, seed, chain=False):
         """[T] int64: garbage for the sequences with more than 64 tokens and for the tail; the others draw_words' patterns, or the chain"""
@@ -272,21 +288,21 @@ class PrefillProblem:
     def run(self, words):
         import aule
         return aule.flash_attention_paged_prefill_tree(self.q, self.kc, self.vc, words, self.bt, self.cl, self.cu, max_seqlen_q=self.max_n,
-                                                       return_lse=True, **self.scales)
+                                                       scale=self.scale, return_lse=True, **self.scales)
 
     def twin(self):
         import aule
         return aule.flash_attention_paged_prefill(self.q, self.kc, self.vc, self.bt, self.cl, self.cu, max_seqlen_q=self.max_n,
-                                                  return_lse=True, **self.scales)
+                                                  scale=self.scale, return_lse=True, **self.scales)
 
-    def judge(self, torch, words):
-        """[owned, Hq, D], [owned, Hq]: a sequence with more than 64 tokens under the causal rule"""
+    def judge(self, torch, words, causal=False):
+        """[owned, Hq, D], [owned, Hq]: a sequence with more than 64 tokens under the causal rule (causal: every sequence)"""
         outs, lses = [], []
         for b, (n, L) in enumerate(self.nl):
-            K, V = (x.cuda() for x in self.f64[b])
+            K, V = (x.to(self.q.device) for x in self.f64[b])
             s = self.starts[b]
-            vis = visibility(torch, L, n, words[s:s + n], causal=n > 64)
-            o, l = judge(torch, self.q[s:s + n].double(), K, V, vis, 1.0 / math.sqrt(self.D))
+            vis = visibility(torch, L, n, words[s:s + n], causal=causal or n > 64)
+            o, l = judge(torch, self.q[s:s + n].double(), K, V, vis, 1.0 / math.sqrt(self.D) if self.scale is None else self.scale)
             outs.append(o)
             lses.append(l)
         return torch.cat(outs), torch.cat(lses)
@@ -300,8 +316,8 @@ def prefill_desc(torch, p, words, out, lse):
     d.cache_dtype = 1 if p.scales else 0
     d.batch, d.heads_q, d.heads_kv, d.head_dim = p.bt.shape[0], p.Hq, p.kc.shape[2], p.D
     d.block_size, d.max_blocks = p.kc.shape[1], p.bt.shape[1]
-    d.total_tokens, d.max_seqlen_q, d.q_token_stride = p.T, p.max_n, p.Hq * p.D
-    d.scale, d.window_size, d.device = 0.0, -1, p.q.device.index or 0
+    d.total_tokens, d.max_seqlen_q, d.q_token_stride = p.T, p.max_n, p.q.stride(0)
+    d.scale, d.window_size, d.device = 0.0 if p.scale is None else p.scale, -1, p.q.device.index or 0
     d.stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     d.q, d.k_cache, d.v_cache, d.out = p.q.data_ptr(), p.kc.data_ptr(), p.vc.data_ptr(), out.data_ptr()
     d.lse = lse.data_ptr() if lse is not None else None

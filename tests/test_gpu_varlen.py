@@ -167,14 +167,15 @@ class Run:
         return {n: getattr(self, n) for n in ("out", "lse", "dq", "dk", "dv")}
 
 
-def _check_grad(got, ref, dtype, what):
-    """tests/test_gpu_d256.py::_check_grad"""
+def _check_grad(got, ref, dtype, what, floor=0.0):
+    """tests/test_gpu_d256.py::_check_grad; floor: an absolute error allowed whatever the element (the randomised draws pass 4 x the
+    error of the fp64 gradient that reads O rounded to storage; 0 everywhere else)"""
     atol, rtol = BWD_TOL[dtype]
     scale = max(1.0, float(np.abs(ref).max())) if ref.size else 1.0
     got = np.asarray(got, dtype=np.float64)
     assert np.isfinite(got).all(), what + ": non-finite gradient"
     err = np.abs(got - ref)
-    bad = err > atol * scale + rtol * np.abs(ref)
+    bad = err > np.maximum(atol * scale + rtol * np.abs(ref), floor)
     assert not bad.any(), "%s: %d elements out of bound, max err %.3e (max|grad| %.3g)" % (what, int(bad.sum()), err.max(), scale)
     return float(err.max() / scale) if ref.size else 0.0
 

@@ -6,6 +6,9 @@ forward / backward, the paged DECODE, RoPE, split-KV and windows):
     cascade   flash_attention_paged_cascade and merge_attention_states
     mla       flash_attention_mla_paged and flash_attention_mla_paged_fp8
     varlen    aule_attention_varlen_forward_ex / _backward_ex, and the Python wrapper for head dims that are padded
+    sinks     flash_attention_varlen_sinks (forward and backward), _paged_prefill_sinks, _paged_query_sinks and the C entries behind them
+    tree      flash_attention_paged_query_tree and flash_attention_paged_prefill_tree
+    mlapf     aule_attention_mla_prefill_ex / _backward_ex (192 / 128) and flash_attention_mla_varlen
 
     python tools/fuzz_serving.py KIND [n=100] [seed=0]          deterministic per seed; prints every failing configuration
     python tools/fuzz_serving.py one KIND "<cfg as printed>" SEED    one printed configuration again
@@ -13,8 +16,9 @@ forward / backward, the paged DECODE, RoPE, split-KV and windows):
 Each kind is a pure draw and a run.  draw_KIND(rng) -> cfg (a dict of plain values; no torch, no GPU, no library call) and
 run_KIND(cfg, seed) -> (cfg, errs) calls the library.  Every drawn call is a VALID call: hostile offsets, stale lengths and refusals belong to
 tests/test_gpu_hostile_*.py, the *_refusals tests and the *_host.py files.  The judges are those of the hand-written test files
-(Ragged, Cascade, Problem's conventions, Case, Fp8Case, Packed / Run and their _judge functions): the fp64 oracle on the same quantised
-inputs, -inf / zeros / never-written rows exactly.
+(Ragged, Cascade, Problem's conventions, Case, Fp8Case, Packed / Run and their _judge functions; for the newer kinds Batch / Paged,
+QueryProblem / PrefillProblem and the MLA backward's Packed / Run): the fp64 oracle on the same quantised inputs, -inf / zeros /
+never-written rows exactly.
 
 Every kind caps the cost of its judge (shrinking batch, then heads, then lengths) near 0.2 s of fp64 work per draw.
 
@@ -23,7 +27,33 @@ it) -- m = 20, or 8 for MLA: a logit in the hundreds at a random place of the ke
 one KV head (MLA: to the 64 rotary columns), which moves all logits of a row alike.  `out` keeps fwd_tol; the LSE bound becomes
 max(LSE_ATOL, 4 x the error a plain NumPy fp32 log-sum-exp of the same rows has against the fp64 judge): fp32 arithmetic error grows
 with |S|, and the kernels take two hardware transcendental steps on top of fp32 sums.  The bound never looks at the kernel's result.
-Gradients under a sharp softmax are out of scope (the varlen kind stays on Gaussian data and BWD_TOL)."""
+Gradients under a sharp softmax are out of scope (the varlen kind stays on Gaussian data and BWD_TOL).
+
+sinks: one draw picks the entry (varlen / prefill / query) and everything else.  sinks[h] = cycle[(h + rot) % 5] with the cycle (-inf, -30,
+0, ln(Lmax) + 0.5, ln(Lmax) + 6), Lmax the most keys a row of the draw sees; one draw in six passes them in q's dtype and the judge sees the
+rounded values.  Bars: fwd_tol, LSE 1e-3, BWD_TOL; rows without a key out == 0 and lse == sinks[h] exactly; the prefill and varlen legs
+run the C entries into 0xFF-filled buffers.  Relations: the -inf heads are the sinkless entry bit for bit; two runs give the same bits; a
+uniform batch (n <= 64) agrees between the prefill and the query entry within 2 x fwd_tol.  dsinks is held to max(DSINKS_BAR[dtype],
+4 x e_model): e_model = |dsinks_model - dsinks_ref| / max(1, max|dsinks_ref|), dsinks_model the fp64 reduction with O rounded to the storage
+dtype before delta = rowsum(dO * O) is formed -- the term DESIGN.md 3.12 names as the dominant one; the bound is computed from the reference
+alone (sinks_reference, no GPU) and never reads the kernel's result.
+
+The gradient floor (sinks: dq, dk; mlapf: dq, dk_nope, dk_pe): the backward entries are given O in 16 bits and form delta from it, and on
+rows of a few keys dS = P (dP - delta) cancels down to that rounding, which BWD_TOL does not cover (two draws of the 150-draw runs at seed 1
+showed it).  So an element may miss the judge by max(BWD_TOL's bound, 4 x e) where e is the largest difference between the
+fp64 gradient formula on the exact O and on O rounded to storage (test_gpu_sinks.grads_model, test_gpu_mla_backward.rounding_model; per
+draw for the sinks, per sequence for MLA).  From the reference alone; the hand files pass no floor and keep plain BWD_TOL.
+
+tree: the entry (query / prefill), both caches, page sizes 1 .. 128, scale, lead / tail rows and a strided q for the prefill.  The words of
+a sequence are drawn by kind (a random tree, random words, random words with emptied rows, all ones, the chain) from the data seed;
+behind the drawn sequences every draw carries one more, a probe -- emptied rows in front of at most one key of context -- so that on the
+reference alone the judge under the words is far from the judge under the chain.  Relations: chain sequences and sequences of more than 64 tokens (whose words are
+garbage, as those of unowned rows) equal the plain entry bit for bit; two runs give the same bits.
+
+mlapf: heads 1 .. 32, three masks, scale, lead / tail rows on both axes, cuts by max_seqlen_*, the three memory layouts of
+tests/test_gpu_mla_backward.py::Run, and one draw in five through flash_attention_mla_varlen with autograd on slices of wider projections.
+Relations: two runs give the same bits in all six outputs; sequence 0 alone equals the same sequence in the batch bit for bit (dk_pe where
+both launches cut the heads into the same chunks)."""
 import ast, contextlib, importlib, io, math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "aule-attention_amd"), ROOT):
@@ -255,10 +285,232 @@ def draw_varlen(rng):
     return c
 
 
-DRAW = dict(prefill=draw_prefill, cascade=draw_cascade, mla=draw_mla, varlen=draw_varlen)
+# --------------------------------------------------------------------------------------------------------------------------- sinks: the draw
+GROUPS = [1, 2, 3, 4, 5, 8, 16]
+SINK_SQ = [1, 2, 5, 13, 33, 64]
+SINK_CTX = [0, 1, "Sq-1", 45, 257, 1000, 2048]
+SINK_CTX_LENS = [0, 1, 4, 12, 32, 45, 63, 257, 1000, 2048]
+MASK_CODE = {"none": 0, "top": 1, "br": 2}
+
+
+def keys_per_row(n, L, code, window):
+    """how many keys each of the n rows of a sequence with L keys sees under the rule of csrc/fa_fwd_varlen_gfx950.hip (pure)"""
+    res = []
+    for i in range(n):
+        pos = i + (L - n if code == 2 else 0)
+        hi = min(pos, L - 1) if code else L - 1
+        lo = max(0, pos - window + 1) if window > 0 else 0
+        res.append(max(0, hi - lo + 1))
+    return res
+
+
+def sinks_sequences(c):
+    """[(n, L)] as the entry sees them (after the max_seqlen_q cut), and the mask code of the draw (pure)"""
+    if c["entry"] == "query":
+        return [(c["Sq"], L) for L in c["Ls"]], 2
+    cut = c["max_sq"] if c["max_sq"] is not None else max(max(c["ns"]), 1)
+    return [(min(n, cut), L) for n, L in zip(c["ns"], c["Ls"])], MASK_CODE[c["mask"]]
+
+
+def sinks_row_keys(c):
+    """the key counts of all owned rows of the draw (pure)"""
+    seqs, code = sinks_sequences(c)
+    return [k for n, L in seqs for k in keys_per_row(n, L, code, c["window"])]
+
+
+def _sinks_cost(c):
+    """~ flops of the torch fp64 reference: per sequence two products of Hq n L D and a softmax over Hq n L, the forward twice (with the
+    sinks and with none) and for the varlen entry the autograd backward on top"""
+    seqs, _ = sinks_sequences(c)
+    passes = 5 if c["entry"] == "varlen" else 2
+    return passes * sum(c["Hq"] * (n * L * (4 * c["D"] + 40) + 3000) for n, L in seqs)
+
+
+def draw_sinks(rng):
+    c = {}
+    c["entry"] = _pick(rng, ["varlen", "prefill", "query"])
+    varlen = c["entry"] == "varlen"
+    c["dtype"] = _pick(rng, ["bf16", "fp16"])
+    c["wrapper"] = int(rng.randint(5)) == 0 and varlen           # through aule.flash_attention_varlen_sinks at a head dim that is padded
+    c["D"] = _pick(rng, [40, 96]) if c["wrapper"] else _pick(rng, [32, 64, 128])
+    c["Hkv"] = _pick(rng, [1, 2, 3, 8])
+    g = _pick(rng, [x for x in GROUPS if x * c["Hkv"] <= 32])
+    c["scale_mul"] = _pick(rng, [None, None, 0.5, 1.5])
+    c["window"] = _pick(rng, [-1, -1, 1, 17, 64, 128, 300])
+    cache, bs, cols = _pick(rng, ["16", "fp8"]), _pick(rng, BLOCK_SIZES), _pick(rng, [1, 3])
+    c["cache"], c["bs"], c["extra_cols"] = (None, None, None) if varlen else (cache, bs, cols)
+    mask = _pick(rng, ["none", "top", "br"])
+    c["mask"] = mask if varlen else "br"
+    lead, tail, q_pad = _pick(rng, [0, 3]), _pick(rng, [0, 5]), _pick(rng, [8, 24, 64]) if int(rng.randint(3)) == 0 else 0
+    c["lead"], c["tail"] = (0, 0) if c["entry"] == "query" else (lead, tail)
+    c["q_pad"] = q_pad if c["entry"] == "prefill" else 0
+    c["sinks_in_q_dtype"] = int(rng.randint(6)) == 0             # sinks passed in q's dtype: the judge sees the rounded values
+    rot = int(rng.randint(5))
+    cut = int(rng.randint(5)) == 0 and varlen
+    cut_to = _pick(rng, [1, 40, 100])
+    c["Sq"] = c["max_sq"] = None
+    B = int(rng.randint(1, 7))
+    if varlen:
+        ns, Ls = [_pick(rng, VARLEN_NS) for _ in range(B)], [_pick(rng, VARLEN_LS) for _ in range(B)]
+    elif c["entry"] == "prefill":
+        shape = int(rng.randint(8))       # one batch in eight is uniform, as _draw_ragged's: the paged query's problem
+        ns = [_pick(rng, [1, 2, 3, 31, 32, 33, 43, 64])] * B if shape == 0 else [_pick(rng, NS_RAGGED) for _ in range(B)]
+        Ls = []
+        for n in ns:
+            how = int(rng.randint(4))
+            Ls.append(0 if how == 0 or (how == 1 and n == 0) else n - int(rng.randint(1, n + 1)) if how == 1 else n if how == 2 else n + _pick(rng, AHEAD))
+    else:
+        c["Sq"] = _pick(rng, SINK_SQ)
+        ns = [c["Sq"]] * B
+        Ls = [max(c["Sq"] - 1, 0) if L == "Sq-1" else L for L in (_pick(rng, SINK_CTX) for _ in range(B))]
+    while True:      # the judge's budget: batch, then heads, then lengths; and some row sees a key
+        if not any(n >= 1 and L >= 1 for n, L in zip(ns, Ls)):
+            ns[0], Ls[0] = max(ns[0], 1), max(Ls[0], 1)
+        c["Hq"], c["ns"], c["Ls"] = c["Hkv"] * g, list(ns), list(Ls)
+        if _sinks_cost(c) <= 6e8 * JUDGE_BUDGET:
+            break
+        big = max(range(len(ns)), key=lambda b: ns[b] * Ls[b])
+        if len(ns) > 1: ns.pop(); Ls.pop()
+        elif g > 1: g = _smaller(GROUPS, g)
+        elif c["Hkv"] > 1: c["Hkv"] = _smaller([1, 2, 3, 8], c["Hkv"])
+        elif Ls[big] > 1: Ls[big] = _smaller(sorted(set(VARLEN_LS + SINK_CTX_LENS)), Ls[big])
+        else: break
+    if cut and max(c["ns"]) > 1: c["max_sq"] = min(cut_to, max(c["ns"]) - 1)             # below the longest sequence: that one is cut
+    # head h takes entry (h + rot) % 5 of the cycle; with fewer than five heads some head must take entry 3, ln(Lmax) + 0.5
+    c["rot"] = rot if c["Hq"] >= 5 else (3 - rot % c["Hq"]) % 5
+    return c
+
+
+def sinks_half_head(c):
+    """the first head whose sink logit is ln(Lmax) + 0.5 (pure)"""
+    return next(h for h in range(c["Hq"]) if (h + c["rot"]) % 5 == 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- tree: the draw
+TREE_BS = [1, 7, 16, 24, 32, 64, 100, 128]
+TREE_SQ = [1, 2, 5, 13, 31, 32, 33, 63, 64]
+TREE_CTX = ["Sq//2", "Sq", "Sq+1", 45, 100, 257, 1000]
+TREE_NS = [0, 1, 7, 20, 33, 63, 64, 65, 100]
+TREE_AHEAD = [0, 1, 49, 64, 77, 200]
+WORD_KINDS = ["tree", "random", "emptied", "ones", "chain"]
+
+
+def _tree_cost(c):
+    """~ flops of the fp64 judge: two products of Hq n L D per sequence and a softmax"""
+    return sum(c["Hq"] * (n * L * (4 * c["D"] + 40) + 3000) for n, L in zip(c["ns"], c["Ls"]))
+
+
+def draw_tree(rng):
+    c = {}
+    c["entry"] = _pick(rng, ["query", "prefill"])
+    query = c["entry"] == "query"
+    c["dtype"], c["cache"] = _pick(rng, ["bf16", "fp16"]), _pick(rng, ["16", "fp8"])
+    c["D"] = _pick(rng, [32, 64, 128])
+    c["Hkv"] = _pick(rng, [1, 2, 3, 8])
+    g = _pick(rng, [x for x in GROUPS if x * c["Hkv"] <= 32])
+    c["bs"] = _pick(rng, TREE_BS)
+    c["scale_mul"] = _pick(rng, [None, None, 0.5, 1.5])
+    c["extra_cols"] = _pick(rng, [0, 2])
+    lead, tail, q_pad = _pick(rng, [0, 3]), _pick(rng, [0, 5]), _pick(rng, [8, 24, 64]) if int(rng.randint(3)) == 0 else 0
+    c["lead"], c["tail"], c["q_pad"] = (0, 0, 0) if query else (lead, tail, q_pad)
+    c["Sq"] = _pick(rng, TREE_SQ) if query else None
+    B = int(rng.randint(1, 7))
+    sym = lambda L: {"Sq//2": c["Sq"] // 2, "Sq": c["Sq"], "Sq+1": c["Sq"] + 1}.get(L, L)   # noqa: E731
+    if query:
+        ns = [c["Sq"]] * B
+        Ls = [sym(_pick(rng, TREE_CTX)) for _ in range(B)]
+    else:
+        ns = [_pick(rng, TREE_NS) for _ in range(B)]
+        Ls = []
+        for n in ns:
+            how = int(rng.randint(7))
+            Ls.append(n - int(rng.randint(1, n + 1)) if how == 0 and n > 0 else n + TREE_AHEAD[max(how - 1, 0)])
+    kinds = [_pick(rng, WORD_KINDS) for _ in range(B)]           # the words of a sequence: by kind, from the data seed
+    # One more sequence behind the drawn ones, the draw's probe: words with emptied rows in front of at most one key of context, so that its
+    # rows see few keys and the judge under the words is far from the judge under the chain whatever the drawn sequences hold.  The
+    # budget below shrinks the drawn sequences only.
+    if query:
+        probe = (c["Sq"], sym(_pick(rng, TREE_CTX[:3])))
+    else:
+        n = _pick(rng, [7, 20, 33, 63, 64])
+        probe = (n, n - int(rng.randint(1, n + 1)) if int(rng.randint(3)) == 0 else n + int(rng.randint(2)))
+    while True:
+        c["Hq"], c["ns"], c["Ls"], c["words"] = c["Hkv"] * g, ns + [probe[0]], Ls + [probe[1]], kinds + ["emptied"]
+        if _tree_cost(c) <= 3e8 * JUDGE_BUDGET:
+            break
+        if len(ns) > 1: ns.pop(); Ls.pop(); kinds.pop()
+        elif g > 1: g = _smaller(GROUPS, g)
+        elif c["Hkv"] > 1: c["Hkv"] = _smaller([1, 2, 3, 8], c["Hkv"])
+        elif Ls[0] - ns[0] > 1: Ls[0] = ns[0] + _smaller(TREE_AHEAD, Ls[0] - ns[0])
+        else: break
+    return c
+
+
+def tree_geometry(c):
+    """what the descriptors of a tree draw hold beyond the cfg (pure)"""
+    cols = max(max((L + c["bs"] - 1) // c["bs"] for L in c["Ls"]), 1) + c["extra_cols"]
+    return dict(T=c["lead"] + sum(c["ns"]) + c["tail"], B=len(c["ns"]), max_blocks=cols)
+
+
+# --------------------------------------------------------------------------------------------------------------------------- mlapf: the draw
+MLAPF_HEADS = [1, 2, 3, 5, 8, 16, 17, 32]
+MLAPF_NS = [0, 1, 2, 31, 32, 33, 64, 127, 128, 129, 200, 257]
+MLAPF_LS = VARLEN_LS
+
+
+def _mlapf_sequences(c):
+    cut = lambda x, m: x if m is None else min(x, m)   # noqa: E731
+    return [(cut(n, c["max_sq"]), cut(L, c["max_sk"])) for n, L in zip(c["ns"], c["ls"])]
+
+
+def _mlapf_cost(c):
+    """~ flops of np_fwd_f64 + np_bwd_f64: seven products of H n L 192 each per sequence"""
+    return sum(7 * c["H"] * (n * L * 192 + 3000) for n, L in _mlapf_sequences(c))
+
+
+def draw_mlapf(rng):
+    c = {}
+    c["dtype"] = _pick(rng, ["bf16", "fp16"])
+    c["wrapper"] = int(rng.randint(5)) == 0                      # aule.flash_attention_mla_varlen with autograd on slices of the projections
+    c["H"] = _pick(rng, MLAPF_HEADS)
+    B = int(rng.randint(1, 7))
+    ns, ls = [_pick(rng, MLAPF_NS) for _ in range(B)], [_pick(rng, MLAPF_LS) for _ in range(B)]
+    c["mask"] = _pick(rng, ["none", "top", "br"])
+    c["scale_mul"] = _pick(rng, [None, None, 0.5, 1.5])          # scale = scale_mul / sqrt(192)
+    c["lead"], c["tail"] = (_pick(rng, [0, 3]), _pick(rng, [0, 2])), (_pick(rng, [0, 5]), _pick(rng, [0, 7]))
+    layout = _pick(rng, ["contiguous", "in_place", "wide"])
+    c["layout"] = None if c["wrapper"] else layout
+    cut = _pick(rng, ["q", "k"]) if int(rng.randint(5)) == 0 else None
+    cut_to = _pick(rng, [1, 40, 100])
+    c["max_sq"] = c["max_sk"] = None
+    while True:
+        if sum(ns) == 0: ns[0] = 1
+        if sum(ls) == 0: ls[0] = 1
+        c["ns"], c["ls"] = list(ns), list(ls)
+        if _mlapf_cost(c) <= 2.5e8 * JUDGE_BUDGET:
+            break
+        big = max(range(len(ns)), key=lambda b: ns[b] * ls[b])
+        if len(ns) > 1: ns.pop(); ls.pop()
+        elif c["H"] > 1: c["H"] = _smaller(MLAPF_HEADS, c["H"])
+        elif ls[big] >= ns[big] and ls[big] > 1: ls[big] = _smaller(MLAPF_LS, ls[big])
+        elif ns[big] > 1: ns[big] = _smaller(MLAPF_NS, ns[big])
+        else: break
+    if cut == "q" and max(c["ns"]) > 1: c["max_sq"] = min(cut_to, max(c["ns"]) - 1)      # below the longest sequence: that one is cut
+    if cut == "k" and max(c["ls"]) > 1: c["max_sk"] = min(cut_to, max(c["ls"]) - 1)
+    return c
+
+
+def mlapf_geometry(c):
+    """the totals and maxima the descriptor of a draw holds (pure)"""
+    return dict(B=len(c["ns"]), Tq=c["lead"][0] + sum(c["ns"]) + c["tail"][0], Tk=c["lead"][1] + sum(c["ls"]) + c["tail"][1],
+                max_sq=c["max_sq"] if c["max_sq"] is not None else max(1, max(c["ns"])),
+                max_sk=c["max_sk"] if c["max_sk"] is not None else max(1, max(c["ls"])))
+
+
+DRAW = dict(prefill=draw_prefill, cascade=draw_cascade, mla=draw_mla, varlen=draw_varlen, sinks=draw_sinks, tree=draw_tree, mlapf=draw_mlapf)
 # The fixed-seed slices of the suite: kind -> (draws, seed).  tests/test_gpu_fuzz_serving.py runs them, tests/test_fuzz_serving_draws.py
 # asserts (without a GPU) that they reach what they are for; a seed is chosen so that the latter holds.
-SLICES = dict(prefill=(30, 2), cascade=(20, 3), mla=(20, 5), varlen=(20, 4))
+SLICES = dict(prefill=(30, 2), cascade=(20, 3), mla=(20, 5), varlen=(20, 4), sinks=(20, 24), tree=(20, 2), mlapf=(20, 4))
 
 
 def draws(kind, n, seed):
@@ -502,8 +754,364 @@ def run_varlen(cfg, seed, stats=None):
     return cfg, errs
 
 
-RUN = dict(prefill=run_prefill, cascade=run_cascade, mla=run_mla, varlen=run_varlen)
-SEED0 = dict(prefill=31000, cascade=32000, mla=33000, varlen=34000)      # data seed of draw i: SEED0[kind] + i
+# ------------------------------------------------------------------------------------------------------------------------------------ sinks
+def sinks_problem(cfg, seed, device="cuda"):
+    """(Batch, Paged or None) of tests/test_gpu_sinks.py for a draw; device="cpu": the reference side, which needs no GPU"""
+    ts = importlib.import_module("test_gpu_sinks")
+    c = cfg
+    seqs, code = sinks_sequences(c)
+    b = ts.Batch(seed, c["dtype"], c["Hq"], c["Hkv"], c["D"], code, c["window"], ns=[n for n, _ in seqs], ls=c["Ls"], ns_raw=c["ns"],
+                 max_sq=c["max_sq"] if c["max_sq"] is not None else max(max(c["ns"]), 1), lead=c["lead"], tail=c["tail"],
+                 scale=None if c["scale_mul"] is None else c["scale_mul"] / math.sqrt(c["D"]), rot=c["rot"],
+                 sinks_dtype=c["dtype"] if c["sinks_in_q_dtype"] else None)
+    assert sorted(k for _, n, _, L in b.seqs for k in keys_per_row(n, L, code, c["window"])) == sorted(sinks_row_keys(c)) and b.lmax == max(sinks_row_keys(c))
+    if c["entry"] == "varlen":
+        return b, None
+    p = ts.Paged(b, c["cache"] == "fp8", bs=c["bs"], seed=seed + 1, extra_cols=c["extra_cols"], device=device)
+    if p.fp8:
+        b.vmax = float(p.v_ref.abs().max())
+    return b, p
+
+
+def sinks_reference(cfg, seed):
+    """The reference side of a sinks draw; no GPU.  Returns (b, p, ref, plain, facts): ref with the draw's sinks (and the fp64 gradients for
+    the varlen entry), plain with every sink -inf, and the facts the conditions of tests/test_fuzz_serving_draws.py read -- gap =
+    max|out_ref(sinks) - out_ref(no sinks)| over the owned rows, tol = atol + rtol max|out_ref| of fwd_tol, weight = the sink weight of the
+    ln(Lmax) + 0.5 head at a row with Lmax keys, and for the varlen entry e_model (the dsinks error of a backward that reads O rounded to
+    storage, |model - ref| / max(1, max|ref|)), bar (DSINKS_BAR) and bound = max(bar, 4 e_model)"""
+    import torch
+    ts, util = importlib.import_module("test_gpu_sinks"), importlib.import_module("util")
+    b, p = sinks_problem(cfg, seed, device="cpu")
+    src = b if p is None else p
+    ref = src.reference(grads=cfg["entry"] == "varlen")
+    plain = src.reference(sinks=b.sinks.new_full(b.sinks.shape, ts.NINF))
+    own = b.owned()
+    atol, rtol = util.fwd_tol(b.dtype, b.vmax)
+    nkeys = torch.zeros(b.Tq, dtype=torch.long)
+    for sq, n, _, L in b.seqs:
+        nkeys[sq:sq + n] = ts._visible(n, L, b.code, b.window).sum(dim=1)
+    row = int(torch.where(own, nkeys, torch.full_like(nkeys, -1)).argmax())
+    assert int(nkeys[row]) == b.lmax >= 1
+    facts = dict(gap=float((ref["out"][own] - plain["out"][own]).abs().max()), tol=atol + rtol * float(ref["out"][own].abs().max()),
+                 weight=float(ref["w"][row, sinks_half_head(cfg)]), blind=int((own[:, None] & ~ref["seen"]).sum()))
+    if cfg["entry"] == "varlen":
+        exact, model = ts.dsinks_model(b, ref)
+        rds = ref["dsinks"]
+        norm = max(1.0, float(rds.abs().max()))
+        assert float((exact - rds).abs().max()) <= 1e-9 * norm, "the closed form of dsinks is not autograd's"
+        facts["e_model"] = float((model - rds).abs().max()) / norm
+        facts["bar"] = ts.DSINKS_BAR[b.dtype]
+        facts["bound"] = max(facts["bar"], 4.0 * facts["e_model"])
+        # dq and dk the same way: the fp64 gradient formula with delta from O rounded to storage, against the same formula on the exact O
+        exact, model = ts.grads_model(b, ref)
+        facts["grad_model"], facts["grad_rel"] = {}, {}
+        for name, ex, mo in zip(("dq", "dk"), exact, model):
+            gnorm = max(1.0, float(ref[name].abs().max()))
+            assert float((ex - ref[name]).abs().max()) <= 1e-9 * gnorm, "the closed form of %s is not autograd's" % name
+            facts["grad_model"][name] = float((mo - ex).abs().max())
+            facts["grad_rel"][name] = facts["grad_model"][name] / gnorm
+        facts["grad_binds"] = 4.0 * max(facts["grad_rel"].values()) > util.BWD_TOL[b.dtype][0]
+    return b, p, ref, plain, facts
+
+
+def run_sinks(cfg, seed, stats=None):
+    import torch
+    import aule
+    _, ts, util, hostile = _mods("test_gpu_sinks", "util", "hostile")
+    c = cfg
+    errs, stats = [], {} if stats is None else stats      # (stats: the caller's dict, filled with the maxima this draw measured)
+    b, _, ref, _, facts = sinks_reference(c, seed)
+    _, p = sinks_problem(c, seed)                         # (the same seeds: the same problem, its cache on the device)
+    if p is not None and p.fp8:
+        b.vmax = float(p.v_ref.abs().max())
+    W, scale, causal = c["window"], b.scale_arg, {"none": False, "top": True, "br": "bottom-right"}[c["mask"]]
+    own = b.owned().cuda()
+    ninf = [h for h in range(b.Hq) if b.sinks[h] == ts.NINF]
+    sinks_arg = b.sinks.to(b.tdt).cuda() if c["sinks_in_q_dtype"] else b.sinks.cuda()     # (b.sinks holds the rounded values then)
+    atol, rtol = util.fwd_tol(b.dtype, b.vmax)
+
+    def forward(what, out, lse, rows=None):
+        res = _checked(errs, ts._check_forward, b, ref, out, lse, what, rows)
+        if res: stats["out"], stats["lse"] = max(stats.get("out", 0.0), res[0]), max(stats.get("lse", 0.0), res[1])
+
+    def minus_inf_heads(what, out, lse, plain, plain_lse, rows):
+        for h in ninf:
+            if not (_same(torch, out[rows][:, h], plain[rows][:, h]) and _same(torch, lse[rows][:, h], plain_lse[rows][:, h])):
+                errs.append("%s: head %d with sink -inf is not the sinkless entry bit for bit" % (what, h)); break
+
+    if c["entry"] == "varlen":
+        q, k, v, _, cu_q, cu_k = ts._cuda(b)
+        kw = dict(causal=causal, scale=scale, window_size=W)
+        if not c["wrapper"]:
+            # the C entries, forward and backward, into one arena of 0xFF and again into one of zeros
+            dirty, _ = ts._raw_run(torch, b, hostile.POISON)
+            clean, _ = ts._raw_run(torch, b, hostile.FRIENDLY)
+            shapes = dict(out=(b.tdt, (b.Tq, b.Hq, b.D)), lse=(torch.float32, (b.Tq, b.Hq)), dq=(b.tdt, (b.Tq, b.Hq, b.D)),
+                          dk=(b.tdt, (b.Tk, b.Hkv, b.D)), dv=(b.tdt, (b.Tk, b.Hkv, b.D)), dsinks=(torch.float32, (b.Hq,)))
+            got, again = ({n: a.view(n, dt, shape) for n, (dt, shape) in shapes.items()} for a in (dirty, clean))
+            if not (dirty.guards_intact() and clean.guards_intact()): errs.append("guard bytes written")
+            own_k = torch.zeros(b.Tk, dtype=torch.bool)
+            for _, _, sk, L in b.seqs:
+                own_k[sk:sk + L] = True
+            own_k = own_k.cuda()
+            for n in shapes:
+                rows = slice(None) if n == "dsinks" else own_k if n in ("dk", "dv") else own
+                if not _same(torch, got[n][rows], again[n][rows]): errs.append("two runs give different bits in " + n)
+                if n != "dsinks" and not bool((hostile.as_bytes(torch, got[n][~rows]) == hostile.POISON).all()):
+                    errs.append(n + ": a row of no sequence was written")
+            out, lse = got["out"], got["lse"]
+            # the Python entry: the same launch; sinks in q's dtype convert exactly
+            o2, l2 = aule.flash_attention_varlen_sinks(q, k, v, sinks_arg, cu_q, cu_k, b.max_sq, b.max_sk, return_lse=True, **kw)
+            if not (_same(torch, o2[own], out[own]) and _same(torch, l2[own], lse[own])): errs.append("Python entry != C entry")
+        else:
+            sinks_arg = sinks_arg.clone()
+            for t in (q, k, v, sinks_arg):
+                t.requires_grad_(True)
+            out, lse = aule.flash_attention_varlen_sinks(q, k, v, sinks_arg, cu_q, cu_k, b.max_sq, b.max_sk, return_lse=True, **kw)
+            dout = torch.zeros_like(out)
+            dout[own] = b.dout.cuda()[own]
+            dq, dk, dv, ds = torch.autograd.grad(out, (q, k, v, sinks_arg), dout)
+            o2, l2 = aule.flash_attention_varlen_sinks(q.detach(), k.detach(), v.detach(), sinks_arg.detach(), cu_q, cu_k, b.max_sq, b.max_sk,
+                                                       return_lse=True, **kw)
+            if not (_same(torch, o2[own], out.detach()[own]) and _same(torch, l2[own], lse[own])): errs.append("two runs give different bits")
+            got = dict(dq=dq, dk=dk, dv=dv, dsinks=ds.float())
+            out, q, k, v = out.detach(), q.detach(), k.detach(), v.detach()
+            own_k = torch.zeros(b.Tk, dtype=torch.bool)
+            for _, _, sk, L in b.seqs:
+                own_k[sk:sk + L] = True
+            own_k = own_k.cuda()
+            if bool(dq[~own].any()) or bool(dk[~own_k].any()) or bool(dv[~own_k].any()): errs.append("a gradient row of no sequence is not zero")
+        torch.cuda.synchronize()
+        forward("varlen sinks", out, lse)
+        plain, plain_lse = aule.flash_attention_varlen(q, k, v, cu_q, cu_k, b.max_sq, b.max_sk, return_lse=True, **kw)
+        minus_inf_heads("varlen", out, lse, plain, plain_lse, own)
+        for n in ("dq", "dk", "dv"):      # (the owned rows: the others hold the arena's 0xFF, or zeros from the wrapper)
+            rows = own if n == "dq" else own_k
+            res = _checked(errs, ts._check_grad, got[n][rows], ref[n][rows.cpu()], b.dtype, n, 4.0 * facts["grad_model"].get(n, 0.0))
+            if res is not None: stats[n] = res
+        stats["grad_model"] = max(facts["grad_rel"].values())
+        rds = ref["dsinks"].numpy()
+        ds = got["dsinks"].double().cpu().numpy()
+        stats["dsinks"] = float(np.abs(ds - rds).max() / max(1.0, np.abs(rds).max())) if np.isfinite(ds).all() else float("inf")
+        stats["dsinks_model"] = facts["e_model"]
+        if not stats["dsinks"] <= facts["bound"]: errs.append("dsinks off by %.3e of max(1, max|ref|) (bound %.3e)" % (stats["dsinks"], facts["bound"]))
+        if any(ds[h] != 0.0 or rds[h] != 0.0 for h in ninf): errs.append("dsinks of a head with sink -inf is not zero")
+        return cfg, errs
+
+    bt, cl = p.bt.cuda(), p.cl.cuda()
+    B, Sq, Hq, D = len(b.seqs), c["Sq"], b.Hq, b.D
+    kw = dict(scale=scale, window_size=W, return_lse=True, **p.scales)
+    if c["entry"] == "prefill":
+        cu = torch.tensor(b.cu_q, dtype=torch.int32, device="cuda")
+        out, lse = ts._raw_prefill(torch, b, p, c["q_pad"])
+        _checked(errs, ts._unowned_still_poisoned, torch, b, dict(out=out, lse=lse))
+        forward("paged prefill sinks", out, lse)
+        q = b.q.cuda()
+        o2, l2 = aule.flash_attention_paged_prefill_sinks(q, p.kc, p.vc, sinks_arg, bt, cl, cu, max_seqlen_q=b.max_sq, **kw)
+        if not (_same(torch, o2[own], out[own]) and _same(torch, l2[own], lse[own])): errs.append("Python entry != C entry")
+        plain, plain_lse = aule.flash_attention_paged_prefill(q, p.kc, p.vc, bt, cl, cu, max_seqlen_q=b.max_sq, **kw)
+        minus_inf_heads("prefill", out, lse, plain, plain_lse, own)
+        n, lead = c["ns"][0], c["lead"]
+        if all(x == n for x in c["ns"]) and 1 <= n <= 64:
+            # the same problem by the other kernel (tests/test_gpu_tree.py::test_query_tree_and_prefill_tree_agree's relation)
+            q4 = q[lead:lead + B * n].view(B, n, Hq, D).permute(0, 2, 1, 3).contiguous()
+            want, wl = aule.flash_attention_paged_query_sinks(q4, p.kc, p.vc, sinks_arg, bt, cl, **kw)
+            torch.cuda.synchronize()
+            _close(errs, "prefill vs paged query", out[lead:lead + B * n], want.permute(0, 2, 1, 3).reshape(B * n, Hq, D), 2 * atol, 2 * rtol)
+            _lse_close(errs, torch, "prefill vs paged query", lse[lead:lead + B * n], wl.permute(0, 2, 1).reshape(B * n, Hq), 2 * ts.LSE_ATOL)
+    else:
+        q4 = b.q.view(B, Sq, Hq, D).permute(0, 2, 1, 3).contiguous().cuda()      # [B, Hq, Sq, D]
+        flat = lambda o: o.permute(0, 2, 1, 3).reshape(B * Sq, Hq, D)             # noqa: E731
+        flat_lse = lambda x: x.permute(0, 2, 1).reshape(B * Sq, Hq)               # noqa: E731
+        out, lse = aule.flash_attention_paged_query_sinks(q4, p.kc, p.vc, sinks_arg, bt, cl, **kw)
+        o2, l2 = aule.flash_attention_paged_query_sinks(q4, p.kc, p.vc, sinks_arg, bt, cl, **kw)
+        torch.cuda.synchronize()
+        if not (_same(torch, o2, out) and _same(torch, l2, lse)): errs.append("two runs give different bits")
+        forward("paged query sinks", flat(out), flat_lse(lse))
+        plain, plain_lse = aule.flash_attention_paged_query(q4, p.kc, p.vc, bt, cl, **kw)
+        minus_inf_heads("query", flat(out), flat_lse(lse), flat(plain), flat_lse(plain_lse), own)
+        cu = (torch.arange(B + 1, dtype=torch.int32) * Sq).cuda()
+        want, wl = aule.flash_attention_paged_prefill_sinks(b.q.cuda(), p.kc, p.vc, sinks_arg, bt, cl, cu, max_seqlen_q=Sq, **kw)
+        torch.cuda.synchronize()
+        _close(errs, "paged query vs prefill", flat(out), want, 2 * atol, 2 * rtol)
+        _lse_close(errs, torch, "paged query vs prefill", flat_lse(lse), wl, 2 * ts.LSE_ATOL)
+    torch.cuda.synchronize()
+    return cfg, errs
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------- tree
+def tree_problem(cfg, seed, device="cuda"):
+    """(QueryProblem or PrefillProblem of tests/test_gpu_tree.py, words, [(start, n, kind)] per sequence) for a draw.  words: [B, Sq] or [T]
+    int64 on `device`, per sequence of its kind from the data seed; garbage for a sequence of more than 64 tokens and for the rows of no
+    sequence.  device="cpu": the judge's side, which needs no GPU"""
+    import torch
+    tt = importlib.import_module("test_gpu_tree")
+    c, geo = cfg, tree_geometry(cfg)
+    scale = None if c["scale_mul"] is None else c["scale_mul"] / math.sqrt(c["D"])
+    g = torch.Generator().manual_seed(seed + 500)
+    if c["entry"] == "query":
+        p = tt.QueryProblem(torch, seed, c["dtype"], c["cache"], c["Hq"], c["Hkv"], c["Sq"], c["D"], c["bs"], c["Ls"], scale=scale,
+                            extra_cols=c["extra_cols"], device=device)
+        words = torch.stack([tt.words_of_kind(torch, g, kind, c["Sq"]) for kind in c["words"]])
+        seqs = [(b, c["Sq"], kind) for b, kind in enumerate(c["words"])]
+    else:
+        p = tt.PrefillProblem(torch, seed, c["dtype"], c["cache"], Hq=c["Hq"], Hkv=c["Hkv"], D=c["D"], bs=c["bs"], tail=c["tail"],
+                              nl=list(zip(c["ns"], c["Ls"])), lead=c["lead"], q_pad=c["q_pad"], scale=scale, extra_cols=c["extra_cols"], device=device)
+        assert p.T == geo["T"]
+        words = torch.randint(-2 ** 63, 2 ** 63 - 1, (p.T,), generator=g, dtype=torch.int64)
+        seqs = []
+        for b, (n, kind) in enumerate(zip(c["ns"], c["words"])):
+            if 0 < n <= 64:
+                words[p.starts[b]:p.starts[b] + n] = tt.words_of_kind(torch, g, kind, n)
+            seqs.append((p.starts[b], n, kind if n <= 64 else "causal"))
+    assert p.bt.shape == (geo["B"], geo["max_blocks"])
+    return p, words.to(device), seqs
+
+
+def tree_reference(cfg, seed):
+    """The judge's side of a tree draw; no GPU.  Returns (ref, lref, facts): the judge under the words, and what the conditions of
+    tests/test_fuzz_serving_draws.py read -- trees = the word tensors of the sequences that carry a tree other than the chain, gap = max|tree
+    judge - chain judge| and tol = atol + rtol max|out_ref| of fwd_tol"""
+    import torch
+    util = importlib.import_module("util")
+    p, words, seqs = tree_problem(cfg, seed, device="cpu")
+    ref, lref = p.judge(torch, words)
+    chain, _ = p.judge(torch, words, causal=True)
+    atol, rtol = util.fwd_tol(p.dtype, p.vmax)
+    trees = [words[s, :n] if cfg["entry"] == "query" else words[s:s + n] for s, n, kind in seqs if n > 0 and kind not in ("chain", "causal")]
+    return ref, lref, dict(trees=trees, gap=float((ref - chain).abs().max()) if ref.numel() else 0.0,
+                           tol=atol + rtol * (float(ref.abs().max()) if ref.numel() else 0.0))
+
+
+def run_tree(cfg, seed, stats=None):
+    import torch
+    _, tt, util = _mods("test_gpu_tree", "util")
+    c = cfg
+    errs, stats = [], {} if stats is None else stats      # (stats: the caller's dict, filled with the maxima this draw measured)
+    p, words, seqs = tree_problem(c, seed)
+    ref, lref, _ = tree_reference(c, seed)
+    ref, lref = ref.cuda(), lref.cuda()
+
+    def compare(what, out, lse):
+        _checked(errs, tt.compare, torch, out, lse, ref, lref, c["dtype"], p.vmax, what)
+        if out.numel():
+            stats["out"] = float((out.double() - ref).abs().max())
+            fin = torch.isfinite(lref) & torch.isfinite(lse)
+            stats["lse"] = float((lse.double()[fin] - lref[fin]).abs().max()) if bool(fin.any()) else 0.0
+
+    if c["entry"] == "query":
+        out, lse = p.run(words)
+        o2, l2 = p.run(words)
+        tout, tlse = p.twin()
+        torch.cuda.synchronize()
+        compare("query tree", out, lse)
+        if not (_same(torch, out, o2) and _same(torch, lse, l2)): errs.append("two runs give different bits")
+        for b, _, kind in seqs:
+            if kind == "chain" and not (_same(torch, out[b], tout[b]) and _same(torch, lse[b], tlse[b])):
+                errs.append("sequence %d: chain words are not the plain entry bit for bit" % b)
+        return cfg, errs
+    # the C entry into poisoned out / lse
+    from aule import _capi
+    import ctypes
+    poison = torch.randn(p.T, p.Hq, p.D, generator=torch.Generator().manual_seed(1)).to(p.q.dtype).cuda()
+    out, lse = poison.clone(), torch.full((p.T, p.Hq), 7.25, device="cuda")
+    rc = _capi.get_lib().aule_attention_paged_prefill_tree_ex(ctypes.byref(tt.prefill_desc(torch, p, words, out, lse)))
+    torch.cuda.synchronize()
+    if rc != 0:
+        raise RuntimeError("aule_attention_paged_prefill_tree_ex refused a valid call: %s" % tt._error(_capi.get_lib()))
+    lo, hi = p.lead, p.lead + p.owned
+    free = torch.ones(p.T, dtype=torch.bool, device="cuda")
+    free[lo:hi] = False
+    if not (torch.equal(out[free], poison[free]) and bool((lse[free] == 7.25).all())): errs.append("a row of no sequence was written")
+    compare("prefill tree", out[lo:hi], lse[lo:hi])
+    o2, l2 = p.run(words)
+    tout, tlse = p.twin()
+    torch.cuda.synchronize()
+    if not (_same(torch, o2[lo:hi], out[lo:hi]) and _same(torch, l2[lo:hi], lse[lo:hi])): errs.append("two runs (the Python entry, the C entry) give different bits")
+    for s, n, kind in seqs:
+        if kind in ("chain", "causal") and not (_same(torch, out[s:s + n], tout[s:s + n]) and _same(torch, lse[s:s + n], tlse[s:s + n])):
+            errs.append("the sequence at row %d (%s, n = %d) is not the plain entry bit for bit" % (s, kind, n))
+    return cfg, errs
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------ mlapf
+def mlapf_reference(cfg, seed):
+    """The reference side of an mlapf draw; no GPU.  Returns (Packed, causal, scale, floors, facts): floors per sequence {name: 4 x the
+    error of the fp64 gradient that reads O rounded to storage} (tests/test_gpu_mla_backward.py::rounding_model; 0 for dv), which a gradient
+    element may miss the judge by whatever BWD_TOL says, and facts = dict(rel: the largest model error over sequences and gradients as a
+    share of max(1, max|grad|), binds: 4 x rel exceeds BWD_TOL's atol, i.e. the model term is the wider one somewhere)"""
+    tb, util = importlib.import_module("test_gpu_mla_backward"), importlib.import_module("util")
+    c = cfg
+    p = tb.Packed(seed, c["dtype"], c["H"], c["ns"], c["ls"], lead=c["lead"], tail=c["tail"], max_sq=c["max_sq"], max_sk=c["max_sk"])
+    geo = mlapf_geometry(c)
+    assert (p.B, p.Tq, p.Tk, p.max_sq, p.max_sk) == (geo["B"], geo["Tq"], geo["Tk"], geo["max_sq"], geo["max_sk"])
+    causal = {"none": False, "top": True, "br": "bottom-right"}[c["mask"]]
+    scale = None if c["scale_mul"] is None else c["scale_mul"] / math.sqrt(192.0)
+    model = tb.rounding_model(p, causal, scale)
+    floors = [{n: 4.0 * err[n] for n in tb.GRADS} for err, _ in model]
+    rel = max(err[n] / norm[n] for err, norm in model for n in tb.GRADS)
+    return p, causal, scale, floors, dict(rel=rel, binds=4.0 * rel > util.BWD_TOL[c["dtype"]][0])
+
+
+def run_mlapf(cfg, seed, stats=None):
+    import torch
+    import aule
+    oracle, tb, util = _mods("test_gpu_mla_backward", "util")
+    c = cfg
+    errs, stats = [], {} if stats is None else stats      # (stats: the caller's dict, filled with the maxima this draw measured)
+    p, causal, scale, floors, facts = mlapf_reference(c, seed)
+    stats["grad_model"] = facts["rel"]
+    names = ("out", "lse") + tb.GRADS
+
+    def wrapper():
+        tdt = util.torch_dtype(c["dtype"])
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda", tdt)   # noqa: E731
+        q = up(p.q).requires_grad_(True)
+        kvb = up(np.concatenate([p.kn, p.v], axis=2)).requires_grad_(True)
+        down = torch.cat([torch.zeros(p.Tk, 512, dtype=tdt, device="cuda"), up(p.kp)], dim=1).requires_grad_(True)
+        cu_q, cu_k = (torch.from_numpy(tb._i32(x)).cuda() for x in (p.cu_q, p.cu_k))
+        out, lse = aule.flash_attention_mla_varlen(q, kvb[..., :tb.DN], down[:, 512:].unsqueeze(1), kvb[..., tb.DN:], cu_q, cu_k, max_seqlen_q=p.max_sq,
+                                                   max_seqlen_k=p.max_sk, causal=causal, scale=scale, return_lse=True)
+        (out.float() * up(p.dout).float()).sum().backward()
+        torch.cuda.synchronize()
+        oq, ok = (torch.from_numpy(~m).cuda() for m in (p.owned(), p.owned_k()))
+        if bool(q.grad[oq].any()) or bool(kvb.grad[ok].any()) or bool(down.grad[ok].any()) or bool(down.grad[:, :512].any()):
+            errs.append("a gradient outside the sequences' rows and slices is not zero")
+        return dict(out=out.detach(), lse=lse, dq=q.grad, dk_nope=kvb.grad[..., :tb.DN], dk_pe=down.grad[:, 512:], dv=kvb.grad[..., tb.DN:])
+
+    def direct(pp):
+        run = tb.Run(torch, pp, in_place=c["layout"] == "in_place", wide=c["layout"] == "wide").launch(causal, scale=scale)
+        return run, run.results()
+
+    if c["wrapper"]:
+        res, again = wrapper(), wrapper()
+    else:
+        run, res = direct(p)
+        _checked(errs, tb._unowned_still_poisoned, torch, p, res, run)
+        again = direct(p)[1]
+    worst = _checked(errs, tb.fw._judge, p, res, oracle, causal, "mlapf", scale=scale)      # (the forward's judge, which tb._judge runs first)
+    if worst: stats.update(worst)
+    worst = _checked(errs, tb._judge, p, res, oracle, causal, "mlapf", scale=scale, forward=False, floors=floors)
+    if worst: stats.update(worst)
+    oq, ok = (torch.from_numpy(m).cuda() for m in (p.owned(), p.owned_k()))
+    for n in names:
+        rows = oq if n in ("out", "lse", "dq") else ok
+        if not _same(torch, res[n][rows], again[n][rows]): errs.append("two runs give different bits in " + n)
+    # sequence 0 alone: the same bits as in the batch (dk_pe where both runs cut the heads into the same chunks)
+    sq, n, sk, L = p.sequences()[0]
+    if not c["wrapper"] and n + L > 0 and p.B > 1:
+        one_p = p.alone(0)
+        one = direct(one_p)[1]
+        same_chunks = tb._plan(torch, one_p, causal)["heads_per_chunk"] == tb._plan(torch, p, causal)["heads_per_chunk"]
+        for name in names:
+            a, e = (sq, sq + n) if name in ("out", "lse", "dq") else (sk, sk + L)
+            if name == "dk_pe" and not same_chunks: continue
+            if not _same(torch, one[name], res[name][a:e]): errs.append("sequence 0 alone differs from the same sequence in the batch in " + name)
+    return cfg, errs
+
+
+RUN = dict(prefill=run_prefill, cascade=run_cascade, mla=run_mla, varlen=run_varlen, sinks=run_sinks, tree=run_tree, mlapf=run_mlapf)
+SEED0 = dict(prefill=31000, cascade=32000, mla=33000, varlen=34000, sinks=35000, tree=36000, mlapf=37000)      # data seed of draw i: SEED0[kind] + i
 
 
 def run_slice(kind, n, seed):
