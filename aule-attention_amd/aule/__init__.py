@@ -302,6 +302,44 @@ def flash_attention_mla_paged_fp8(q, kv_cache, block_tables, context_lens, cu_se
                          return_lse=return_lse, kv_scale=kv_scale)
 
 
+def flash_attention_mla_sparse(q, kv_cache, indices, scale=None, return_lse=False, kv_scale=None):
+    """Sparse multi-head latent attention (DeepSeek-V3.2 "DSA" and its derivatives, absorbed form): every query token attends
+    to the rows of the latent cache that ITS OWN list names -- what the model's indexer picked, typically 2048 keys -- in
+    decode and in prefill.  The contract is stated once, at aule_mla_sparse_desc in include/aule.h; in short:
+
+        q        [T, Hq, 576] fp16 / bf16, the last dimension contiguous; the token stride is free (a multiple of 8 elements,
+                 at least Hq * 576: a slice of a wider projection is read in place), as in flash_attention_mla_paged
+        kv_cache [num_blocks, block_size, 576] (or [..., 1, 576]), contiguous: q's dtype, or torch.float8_e4m3fn with kv_scale
+                 (None = 1.0, a float, or a 0-d / [1] tensor that stays on the device) by flash_attention_mla_paged_fp8's rule;
+                 a scale with a 16-bit cache is a ValueError.  The cache is addressed as a flat array of S = num_blocks *
+                 block_size rows ("slots"), so a contiguous [L, 576] latent is the cache latent.view(L, 1, 576): sparse
+                 prefill over an un-paged latent
+        indices  [T, topk] (or [T, 1, topk]) int32, contiguous, on q's device, 1 <= topk <= 65536: indices[t, i] is a slot,
+                 block * block_size + offset -- mla_kv_append's slot_mapping; from logical positions,
+                 paged_slot_mapping(...).to(torch.int32).  Any other integer dtype is a ValueError (nothing is converted
+                 silently)
+        scale    None = 1/sqrt(576); DeepSeek models pass their own
+
+    Token t, every head: the keys are the multiset { kv_cache.flat[indices[t, i]] : 0 <= indices[t, i] < S }.  Entries outside
+    [0, S) are skipped (-1 is the conventional pad); a slot listed twice counts twice; there is NO causal rule -- the indexer
+    is responsible for visibility.  scores = scale * q . key over 576 elements, values are the keys' first 512 elements.
+    Returns out [T, Hq, 512], or (out, lse) with lse [T, Hq] fp32 (natural log of the denominator, kv_scale included); a
+    token with no valid entry gives zeros and lse = -inf.  Every row of out / lse is written, and a cache row that no valid
+    entry names is never read.  indices and a tensor kv_scale are read by the kernel on every launch: no host copy, no
+    synchronisation, capturable, and a graph replay sees their current contents.  All argument errors are ValueErrors raised
+    before the device is touched; CPU tensors that pass them are an AuleError; T = 0 returns empty tensors without a launch;
+    tensors that require grad are refused.
+    Out of scope: the indexer itself (the top-k selection), a causal rule inside the kernel, packing several tokens' heads
+    into one row block when Hq < 64, logical-position indices resolved through a block table inside the kernel, a backward,
+    sink logits or tree masks with a list, a fuzz_serving kind."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_sparse
+    return mla_sparse(q, kv_cache, indices, scale=scale, return_lse=return_lse, kv_scale=kv_scale)
+
+
 def mla_kv_append(c_kv, k_pe, kv_cache, slot_mapping, kv_scale=None, cos=None, sin=None, positions=None, rope_layout="half"):
     """The write side of the paged MLA's latent cache: put the rows [c_kv[t] | rope(k_pe[t])] of T new tokens into the cache
     flash_attention_mla_paged / _fp8 read, in place, with one launch; returns None.
@@ -797,7 +835,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_sparse", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

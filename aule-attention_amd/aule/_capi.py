@@ -198,6 +198,32 @@ class MlaPagedFp8Desc(ctypes.Structure):
     _fields_ = MlaPagedDesc._fields_ + [("kv_scale", ctypes.c_void_p)]
 
 
+class MlaSparseDesc(ctypes.Structure):
+    """struct aule_mla_sparse_desc (include/aule.h): absorbed MLA over per-token key lists, both cache kinds."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("cache_dtype", ctypes.c_int32),
+        ("heads_q", ctypes.c_int32),
+        ("num_blocks", ctypes.c_uint32),
+        ("block_size", ctypes.c_uint32),
+        ("total_tokens", ctypes.c_int32),
+        ("topk", ctypes.c_int32),
+        ("scale", ctypes.c_float),
+        ("device", ctypes.c_int32),
+        ("q_token_stride", ctypes.c_int64),
+        ("stream", ctypes.c_void_p),
+        ("q", ctypes.c_void_p),
+        ("kv_cache", ctypes.c_void_p),
+        ("indices", ctypes.c_void_p),
+        ("kv_scale", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 class MlaKvAppendDesc(ctypes.Structure):
     """struct aule_mla_kv_append_desc (include/aule.h): the latent cache append of the paged MLA."""
     _fields_ = [
@@ -515,6 +541,8 @@ SIGNATURES = [
     ("aule_attention_mla_paged_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedDesc)]),
     ("aule_attention_mla_paged_fp8_ex", _I32, [ctypes.POINTER(MlaPagedFp8Desc)]),
     ("aule_attention_mla_paged_fp8_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedFp8Desc)]),
+    ("aule_attention_mla_sparse_ex", _I32, [ctypes.POINTER(MlaSparseDesc)]),
+    ("aule_attention_mla_sparse_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaSparseDesc)]),
     ("aule_mla_kv_append_ex", _I32, [ctypes.POINTER(MlaKvAppendDesc)]),
     ("aule_attention_varlen_forward_ex", _I32, [ctypes.POINTER(VarlenDesc)]),
     ("aule_attention_varlen_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),
@@ -543,6 +571,8 @@ SIGNATURES = [
     ("aule_hip_debug_forward_plan", _I32, [ctypes.POINTER(AttnDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_shared_prefix_plan", _I32, [ctypes.POINTER(PagedCascadeDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_plan", _I32, [ctypes.POINTER(MlaPagedDesc), ctypes.POINTER(_I32), _I32]),
+    ("aule_hip_debug_mla_sparse_plan", _I32, [ctypes.POINTER(MlaSparseDesc), ctypes.POINTER(_I32), _I32]),
+    ("aule_hip_debug_mla_sparse_launch_nsplit", _I32, [ctypes.POINTER(MlaSparseDesc), _I32]),
     ("aule_hip_debug_mla_prefill_backward_plan", _I32, [ctypes.POINTER(MlaPrefillBwdDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_last_backward_route", _I32, []),
     ("aule_hip_debug_backward_route", _I32, [ctypes.POINTER(AttnBwdDesc)]),

@@ -1348,6 +1348,77 @@ def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_s
     return result
 
 
+MLA_SPARSE_MAX_TOPK = 65536
+
+
+def mla_sparse(q, kv_cache, indices, scale=None, return_lse=False, kv_scale=None):
+    """Sparse multi-head latent attention (DeepSeek-V3.2 "DSA", absorbed form): every token attends to the cache rows its own list
+    names; csrc/fa_fwd_mla_sparse_gfx950.hip behind aule_attention_mla_sparse_ex, whose descriptor comment in include/aule.h is the
+    contract (aule.flash_attention_mla_sparse documents the arguments).  One launch (plus the combine when the list is split), no
+    device->host copy, no synchronisation.  All argument errors are ValueErrors raised before the device is touched; CPU tensors
+    that pass them are an AuleError."""
+    if kv_cache.dim() == 4 and kv_cache.shape[2] == 1:
+        kv_cache = kv_cache[:, :, 0]
+    if torch.is_tensor(indices) and indices.dim() == 3 and indices.shape[1] == 1:
+        indices = indices[:, 0]
+    if q.dim() != 3 or kv_cache.dim() != 3:
+        raise ValueError("expected q [T,Hq,576] and kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576])")
+    if q.shape[-1] != 576 or kv_cache.shape[-1] != 576:
+        raise ValueError(f"the latent width must be 576 (512 + 64): query={q.shape[-1]}, cache={kv_cache.shape[-1]}")
+    T, Hq, _ = q.shape
+    fp8 = kv_cache.dtype != q.dtype
+    _latent_cache_kind("q", q.dtype, kv_cache, fp8, kv_scale, "a 16-bit cache has q's dtype")
+    if Hq == 0:
+        raise ValueError("q has no heads")
+    if not torch.is_tensor(indices) or indices.dim() != 2 or indices.shape[0] != T:
+        raise ValueError(f"indices must be a [{T}, topk] (or [{T}, 1, topk]) int32 tensor of slots")
+    if indices.dtype != torch.int32:
+        raise ValueError(f"indices must be int32 (the kernel reads them as they stand; nothing is converted silently), got {indices.dtype}: "
+                         f"pass indices.to(torch.int32)")
+    topk = indices.shape[1]
+    if not 1 <= topk <= MLA_SPARSE_MAX_TOPK:
+        raise ValueError(f"topk (indices.shape[-1]) must be in 1 .. {MLA_SPARSE_MAX_TOPK}, got {topk}")
+    if not indices.is_contiguous():
+        raise ValueError("indices must be contiguous: the kernel reads them in place on every launch")
+    if not kv_cache.is_contiguous():
+        raise ValueError("kv_cache must be contiguous: it is addressed as a flat array of num_blocks * block_size slots")
+    slots = kv_cache.shape[0] * kv_cache.shape[1]
+    if not 1 <= slots <= 2 ** 31 - 1:
+        raise ValueError(f"the cache must hold 1 .. 2^31 - 1 slots (num_blocks * block_size), got {slots}")
+    if (T + 64) * Hq > 2 ** 31 - 1:
+        raise ValueError(f"total_tokens * heads_q = {T} * {Hq} is too large (packed rows are counted in 32 bits)")
+    if torch.is_grad_enabled() and (q.requires_grad or kv_cache.requires_grad):
+        raise ValueError("sparse MLA attention has no backward: detach the inputs or call it under torch.no_grad()")
+    q, q_stride = _packed_tokens(q)
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): sparse MLA attention needs ROCm device tensors; there is no CPU fallback")
+    _same_device("sparse MLA", q, kv_cache, indices)
+    out = torch.empty((T, Hq, 512), device=q.device, dtype=q.dtype)
+    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
+    result = (out, lse) if return_lse else out
+    if T == 0:
+        return result
+    lib = _capi.get_lib()
+    d = _capi.MlaSparseDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    d.heads_q, d.num_blocks, d.block_size = Hq, kv_cache.shape[0], kv_cache.shape[1]
+    d.total_tokens, d.topk, d.q_token_stride = T, topk, q_stride
+    d.scale = _abi_scale(1.0 / math.sqrt(576) if scale is None else scale)
+    d.device = _device_index(q.device)
+    d.stream = _stream_ptr(q.device)
+    d.q, d.kv_cache, d.indices, d.out = q.data_ptr(), kv_cache.data_ptr(), indices.data_ptr(), out.data_ptr()
+    d.lse = lse.data_ptr() if lse is not None else None
+    held = [q]
+    if fp8:
+        held.append(_fp8_scale(kv_scale, 1, q.device, "kv_scale"))
+        d.kv_scale = held[-1].data_ptr()
+    held.append(_attach_workspace(d, lib.aule_attention_mla_sparse_workspace_size, q.device))   # held until the launch is queued
+    _capi.check(lib.aule_attention_mla_sparse_ex(ctypes.byref(d)), "aule_attention_mla_sparse_ex")
+    return result
+
+
 def quantize_mla_cache_fp8(kv_cache):
     """(codes, scale) for the FP8 paged MLA: float8_e4m3fn codes of a [num_blocks, block_size, 576] (or [..., 1, 576]) latent cache and
     ONE scale, a [1] fp32 tensor on the cache's device = amax / 448 (1.0 for an all-zero cache), with kv_cache ~= scale * codes.

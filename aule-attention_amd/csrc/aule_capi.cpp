@@ -95,6 +95,15 @@ static_assert(sizeof(aule_mla_paged_fp8_desc) == 144 && offsetof(aule_mla_paged_
                   offsetof(aule_mla_paged_fp8_desc, workspace) == offsetof(aule_mla_paged_desc, workspace) &&
                   offsetof(aule_mla_paged_fp8_desc, workspace_bytes) == offsetof(aule_mla_paged_desc, workspace_bytes),
               "aule_mla_paged_fp8_desc starts with aule_mla_paged_desc (the MLA entry points read both through that prefix)");
+static_assert(sizeof(aule_mla_sparse_desc) == 120 && offsetof(aule_mla_sparse_desc, dtype) == 4 && offsetof(aule_mla_sparse_desc, cache_dtype) == 8 &&
+                  offsetof(aule_mla_sparse_desc, heads_q) == 12 && offsetof(aule_mla_sparse_desc, num_blocks) == 16 &&
+                  offsetof(aule_mla_sparse_desc, block_size) == 20 && offsetof(aule_mla_sparse_desc, total_tokens) == 24 &&
+                  offsetof(aule_mla_sparse_desc, topk) == 28 && offsetof(aule_mla_sparse_desc, scale) == 32 && offsetof(aule_mla_sparse_desc, device) == 36 &&
+                  offsetof(aule_mla_sparse_desc, q_token_stride) == 40 && offsetof(aule_mla_sparse_desc, stream) == 48 &&
+                  offsetof(aule_mla_sparse_desc, q) == 56 && offsetof(aule_mla_sparse_desc, kv_cache) == 64 && offsetof(aule_mla_sparse_desc, indices) == 72 &&
+                  offsetof(aule_mla_sparse_desc, kv_scale) == 80 && offsetof(aule_mla_sparse_desc, out) == 88 && offsetof(aule_mla_sparse_desc, lse) == 96 &&
+                  offsetof(aule_mla_sparse_desc, workspace) == 104 && offsetof(aule_mla_sparse_desc, workspace_bytes) == 112,
+              "aule_mla_sparse_desc layout is part of the ABI");
 static_assert(sizeof(aule_mla_kv_append_desc) == 128 && offsetof(aule_mla_kv_append_desc, dtype) == 4 &&
                   offsetof(aule_mla_kv_append_desc, cache_dtype) == 8 && offsetof(aule_mla_kv_append_desc, rope_layout) == 12 &&
                   offsetof(aule_mla_kv_append_desc, total_tokens) == 16 && offsetof(aule_mla_kv_append_desc, num_blocks) == 20 &&
@@ -1576,6 +1585,97 @@ int32_t aule_attention_mla_paged_fp8_ex(const aule_mla_paged_fp8_desc* d) {
     return mla_paged_launch(mla_prefix(d), true, "Paged MLA FP8 attention");
 }
 
+// The sparse MLA: per-token key lists over the latent cache, both cache kinds in one descriptor.  One checker for all its readers;
+// `launch`: the pointer and workspace rules of a call that has something to do as well (the size query and the plan hook read no
+// pointer).  Host logic only, asked before the device is needed.
+static bool mla_sparse_nothing_to_do(const aule_mla_sparse_desc* d) { return d->total_tokens == 0; }
+
+// (`d` passed the field rules of mla_sparse_desc_error: mla_sparse_plan reads the shape, none of the pointers)
+// (force_nsplit > 0: the bench's debug launch alone, aule_hip_debug_mla_sparse_launch_nsplit)
+static aule_hip::MlaPlan mla_sparse_plan_of(const aule_mla_sparse_desc* d, int force_nsplit = 0) {
+    return aule_hip::mla_sparse_plan((int)d->total_tokens, (int)d->heads_q, (int)d->topk, d->device, force_nsplit);
+}
+
+static const char* mla_sparse_desc_error(const aule_mla_sparse_desc* d, bool launch, Reason& why, int force_nsplit = 0) {
+    if (d == nullptr || d->struct_size != sizeof(aule_mla_sparse_desc)) return kBadDescriptor;
+    if (!is_16_bit(d->dtype)) return reasonf(why, "dtype %d (of q / out) must be fp16 or bf16", d->dtype);
+    if (cache_dtype_error(d->cache_dtype)) return reasonf(why, "cache_dtype %d must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3", d->cache_dtype);
+    if (d->heads_q < 1) return reasonf(why, "heads_q (%d) must be at least 1", d->heads_q);
+    if (d->topk < 1 || d->topk > aule_hip::kMlaSparseMaxTopk) return reasonf(why, "topk (%d) must be in 1 .. %d", d->topk, aule_hip::kMlaSparseMaxTopk);
+    const uint64_t slots = (uint64_t)d->num_blocks * d->block_size;
+    if (slots < 1 || slots > 0x7fffffffull)
+        return reasonf(why, "num_blocks * block_size (%u * %u) must be in 1 .. 2^31 - 1 (slots are int32)", d->num_blocks, d->block_size);
+    if (d->total_tokens < 0) return reasonf(why, "total_tokens (%d) must not be negative", d->total_tokens);
+    if (const char* e = varlen_stride_error("q", d->q_token_stride, (uint64_t)d->heads_q * 576, "heads_q", why)) return e;
+    if (((uint64_t)d->total_tokens + 64) * (uint64_t)d->heads_q > 0x7fffffffull)
+        return reasonf(why, "total_tokens * heads_q (%d * %d) too large (packed rows are counted in 32 bits)", d->total_tokens, d->heads_q);
+    if (mla_sparse_nothing_to_do(d)) return nullptr;
+    const aule_hip::MlaPlan plan = mla_sparse_plan_of(d, force_nsplit);
+    // (not reachable while (total_tokens + 64) * heads_q fits 32 bits and nsplit > 1 needs total_tokens * row blocks below the CU
+    // count: kept as the statement of the rule, should either bound move)
+    if (plan.grid > 0x7fffffffll || (long long)plan.row_blocks * d->total_tokens * 16 > 0x7fffffffll)
+        return reasonf(why, "the grid (total_tokens %d * row blocks %d * nsplit %d, or * 16 for the combine) exceeds 2^31 - 1 workgroups",
+                       d->total_tokens, plan.row_blocks, plan.nsplit);
+    if (!launch) return nullptr;
+    if (!d->q || !d->kv_cache || !d->indices || !d->out) return "null tensor pointer (q, kv_cache, indices and out are required)";
+    if (misaligned(d->q) || misaligned(d->out) || misaligned(d->kv_cache)) return "q, out and kv_cache must be 16-byte aligned";
+    if ((reinterpret_cast<uintptr_t>(d->indices) & 3) != 0) return "indices must be 4-byte aligned";
+    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
+    if (fp8 && !d->kv_scale) return "null kv_scale (an FP8 cache needs one fp32 value on the device)";
+    if (!fp8 && d->kv_scale) return "kv_scale applies to an FP8 cache only; a 16-bit cache holds the values themselves";
+    if ((reinterpret_cast<uintptr_t>(d->kv_scale) & 3) != 0) return "kv_scale must be 4-byte aligned";
+    if (d->workspace != nullptr) {
+        if (d->workspace_bytes < plan.ws_bytes)
+            return reasonf(why, "workspace_bytes (%llu) is smaller than the plan's %llu", (unsigned long long)d->workspace_bytes, (unsigned long long)plan.ws_bytes);
+        if (misaligned(d->workspace)) return "workspace must be 16-byte aligned";
+    }
+    return nullptr;
+}
+
+// (the launch entry, and with force_nsplit > 0 the bench's debug launch)
+static int32_t mla_sparse_launch(const aule_mla_sparse_desc* d, int force_nsplit) {
+    const char* what = "Sparse MLA attention";
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_sparse_desc_error(d, true, text, force_nsplit)) {
+        set_error("%s failed: %s", what, why);
+        return -3;
+    }
+    if (mla_sparse_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaSparseArgs a;
+    a.q = d->q; a.kv_cache = d->kv_cache; a.out = d->out; a.lse = d->lse;
+    a.indices = d->indices;
+    a.T = (int)d->total_tokens; a.Hq = (int)d->heads_q;
+    a.topk = (int)d->topk;
+    a.slots = (int)((uint64_t)d->num_blocks * d->block_size);
+    a.q_token_stride = d->q_token_stride;
+    a.scale = resolve_scale(d->scale, 576);
+    a.dtype = d->dtype;
+    a.device = d->device;
+    if (d->cache_dtype == AULE_KV_CACHE_FP8_E4M3) {
+        a.cache_kind = aule_hip::kCacheFp8E4M3;
+        a.kv_scale = d->kv_scale;
+    }
+    const aule_hip::MlaPlan plan = mla_sparse_plan_of(d, force_nsplit);
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)d->stream;
+    if (plan.nsplit == 1) return launched(what, aule_hip::launch_mla_sparse(a, plan, nullptr, stream));
+    aule_hip::ScopedWorkspace ws(plan.ws_bytes, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
+    if (ws.err != hipSuccess) {
+        set_error("%s failed: workspace allocation (%llu bytes): %s", what, (unsigned long long)plan.ws_bytes, hipGetErrorString(ws.err));
+        return -4;
+    }
+    return launched(what, aule_hip::launch_mla_sparse(a, plan, ws.ptr, stream));
+}
+
+int32_t aule_attention_mla_sparse_ex(const aule_mla_sparse_desc* d) {
+    RoctxRange range("aule.mla_sparse");
+    return mla_sparse_launch(d, 0);
+}
+
 // The variable-length kinds: aule_varlen_bwd_desc states the problem in aule_varlen_desc's fields up to cu_seqlens_k (the layout asserts
 // at the top of this file), so both are checked and read through that prefix; what follows it is each kind's own.  One checker per
 // kind; `launch`: the pointer and workspace rules of a call that has something to do as well (the size query reads no pointer).  Host
@@ -2353,6 +2453,12 @@ uint64_t aule_attention_mla_paged_fp8_workspace_size(const aule_mla_paged_fp8_de
     return mla_paged_plan(mla_prefix(d), true, plan) ? plan.ws_bytes : 0;
 }
 
+uint64_t aule_attention_mla_sparse_workspace_size(const aule_mla_sparse_desc* d) {
+    Reason text;
+    if (mla_sparse_desc_error(d, false, text)) return 0;
+    return mla_sparse_nothing_to_do(d) ? 0 : mla_sparse_plan_of(d).ws_bytes;
+}
+
 #ifdef AULE_DEBUG_HOOKS
 /* The timeline hooks exist only in the debug library (`make dbg` -> build/variants/libaule_dbg.so, -DAULE_DEBUG_HOOKS):
  * they launch instrumented kernel instances on caller-supplied pointers and are not part of the product libaule.so. */
@@ -2429,6 +2535,31 @@ int32_t aule_hip_debug_mla_plan(const aule_mla_paged_desc* d, int32_t* out, int3
     if (out == nullptr || cap < 6) return -6;
     for (int i = 0; i < 6; ++i) out[i] = v[i];
     return 6;
+}
+
+/* Debug hook: the launch plan of aule_attention_mla_sparse_ex(d) as integers (include/aule.h lists them): the plan the launch and the
+ * workspace query read.  Pure host logic like the forward hook. */
+int32_t aule_hip_debug_mla_sparse_plan(const aule_mla_sparse_desc* d, int32_t* out, int32_t cap) {
+    Reason text;
+    if (mla_sparse_desc_error(d, false, text)) return -3;
+    if (mla_sparse_nothing_to_do(d)) return 0;
+    const aule_hip::MlaPlan plan = mla_sparse_plan_of(d);
+    const int32_t v[6] = {plan.row_blocks, plan.rows_per_block, plan.nsplit, (int32_t)plan.grid,
+                          (int32_t)(uint32_t)(plan.ws_bytes & 0xffffffffull), (int32_t)(uint32_t)(plan.ws_bytes >> 32)};
+    if (out == nullptr || cap < 6) return -6;
+    for (int i = 0; i < 6; ++i) out[i] = v[i];
+    return 6;
+}
+
+/* Debug hook (not part of the drop-in ABI): aule_attention_mla_sparse_ex(d) with `nsplit` key ranges (within 1 .. min(64, tiles)) instead
+ * of the plan's -- what tools/bench_mla_sparse.py measures the plan's "one split per two tiles" cap with.  Every rule of the entry
+ * holds; a caller workspace is sized for THIS nsplit (round16(nsplit * total_tokens * heads_q * 514 * 4)).  nsplit < 1: -3. */
+int32_t aule_hip_debug_mla_sparse_launch_nsplit(const aule_mla_sparse_desc* d, int32_t nsplit) {
+    if (nsplit < 1) {
+        set_error("Sparse MLA attention failed: nsplit (%d) must be at least 1", nsplit);
+        return -3;
+    }
+    return mla_sparse_launch(d, nsplit);
 }
 
 /* Debug hook: the launch plan of aule_attention_mla_prefill_backward_ex(d) as integers (include/aule.h lists them): the plan the launch

@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(256) fa_mla_combine_kernel(const MlaParams p) 
     const int bid = (int)blockIdx.x;
     const int sub = bid % kMlaCombineParts, rest = bid / kMlaCombineParts;
     const int b = rest % p.B, rank = rest / p.B;
-    const MlaBlock blk(p, b, rank);
+    const MlaBlock blk = p.list != nullptr ? MlaBlock(p, b, rank, MlaBlock::ListRows{}) : MlaBlock(p, b, rank);   // (the sparse call's partials)
     const int rl = 4 * sub + wave;
     if (rl >= blk.rows) return;
     const int r = blk.r0 + rl;
@@ -111,11 +111,23 @@ int launch_type(const MlaParams& p, const MlaPlan& plan, int dtype, hipStream_t 
         rc = (int)hipGetLastError();
     }
     if (rc != 0 || plan.nsplit == 1) return rc;
-    hipLaunchKernelGGL((fa_mla_combine_kernel<T>), dim3((unsigned)((long long)plan.row_blocks * p.B * kMlaCombineParts)), dim3(256), 0, stream, p);
-    return (int)hipGetLastError();
+    return launch_mla_combine(p, plan.row_blocks, dtype, stream);
 }
 
 }  // namespace
+
+int launch_mla_combine(const MlaParams& p, int row_blocks, int dtype, hipStream_t stream) {
+    const long long grid = (long long)row_blocks * p.B * kMlaCombineParts;
+    if (grid <= 0 || grid > 0x7fffffffll) return -1;
+    if (dtype == kBF16) {
+        hipLaunchKernelGGL((fa_mla_combine_kernel<Bf16Traits>), dim3((unsigned)grid), dim3(256), 0, stream, p);
+    } else if (dtype == kF16) {
+        hipLaunchKernelGGL((fa_mla_combine_kernel<F16Traits>), dim3((unsigned)grid), dim3(256), 0, stream, p);
+    } else {
+        return -1;
+    }
+    return (int)hipGetLastError();
+}
 
 // The launch plan: the one place that decides row blocks, nsplit, grid and workspace (launch, size query, debug hook).  From the
 // shape alone: row blocks x batch x nsplit covers the device's compute units, nsplit at most kMlaMaxSplit and at most one split
@@ -151,7 +163,7 @@ int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_
     if (plan.nsplit > 1 && ws == nullptr) return -1;
     const bool fp8 = a.cache_kind == kCacheFp8E4M3;
     if (fp8 ? a.kv_scale == nullptr : a.cache_kind != kCache16) return -1;
-    MlaParams p;
+    MlaParams p;   // (list stays null, its default: that is what tells the combine kernel that these are a dense call's partials)
     p.q = static_cast<const char*>(a.q); p.kv = static_cast<const char*>(a.kv_cache);
     p.o = static_cast<char*>(a.out); p.lse = a.lse;
     p.rows_total = (long long)a.T * a.Hq;

@@ -380,6 +380,35 @@ struct MlaPlan {
 MlaPlan mla_plan(const MlaArgs& a);   // all zero: nothing to launch; no pointer is read
 int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream);   // -1: unsupported arguments
 
+// Sparse latent attention (fa_fwd_mla_sparse_gfx950.hip): q [T, Hq, 576] against the rows of the latent cache that a per-token list
+//   names -- indices [T, topk] int32, entry = a slot (row of the cache read as a flat [slots, 576] array); an entry outside [0, slots)
+//   is skipped, a slot listed twice counts twice, and there is no causal rule.  Cache kinds, kv_scale, out, lse and the caller's
+//   guarantees as MlaArgs.  The contract is aule_mla_sparse_desc in include/aule.h.
+struct MlaSparseArgs {
+    const void* q;
+    const void* kv_cache;
+    void* out;
+    float* lse = nullptr;
+    const int* indices;
+    int T, Hq;
+    int topk;                           // 1 .. kMlaSparseMaxTopk
+    int slots;                          // num_blocks * block_size, 1 .. 2^31 - 1
+    long long q_token_stride;
+    float scale;
+    int dtype;
+    int device = -1;                    // as FwdArgs::device
+    int cache_kind = kCache16;
+    const float* kv_scale = nullptr;    // kCacheFp8E4M3 only: [1] fp32, device
+};
+constexpr int kMlaSparseMaxTopk = 65536;
+// The launch plan (mla_sparse_plan, beside the kernel: the one statement of row blocks, nsplit, grid and workspace for launch, size
+// query and debug hook).  MlaPlan's fields with a token in a sequence's place: row_blocks = ceil(Hq / 64) blocks of ONE token's heads,
+// nsplit from ceil(topk / 64) tiles, grid = T * row_blocks * nsplit.  All zero: nothing to launch; no pointer is read.
+// force_nsplit > 0 (the bench's debug entry alone, to measure what the rule's cap costs): that many ranges instead of the rule's,
+// within 1 .. min(kMlaMaxSplit, tiles).
+MlaPlan mla_sparse_plan(int T, int Hq, int topk, int device, int force_nsplit = 0);
+int launch_mla_sparse(const MlaSparseArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream);   // -1: unsupported arguments
+
 // The cut of a sequence's length every ragged entry applies (paged prefill, variable-length, MLA prefill): no sequence has more
 // tokens than the batch.
 inline int seqlen_cut(int max_seqlen, int total) { return max_seqlen < total ? max_seqlen : total; }

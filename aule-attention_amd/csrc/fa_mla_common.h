@@ -1,7 +1,8 @@
-// fa_mla_common.h -- what the two translation units of the paged MLA share (fa_fwd_mla_paged_gfx950.hip: caches of q's dtype, the
-// combine, the plan and the launch; fa_fwd_mla_paged_fp8_gfx950.hip: caches of e4m3fn codes): the sizes, the kernels' parameter
-// struct, the clamps of the contract, the latent tile per cache kind and the ONE body of the attention kernel.  The layout and the
-// arithmetic are described at the top of fa_fwd_mla_paged_gfx950.hip.  Device code only.
+// fa_mla_common.h -- what the translation units of the absorbed MLA share (fa_fwd_mla_paged_gfx950.hip: caches of q's dtype, the
+// combine, the plan and the launch; fa_fwd_mla_paged_fp8_gfx950.hip: caches of e4m3fn codes; fa_fwd_mla_sparse_gfx950.hip: keys from a
+// per-token list): the sizes, the kernels' parameter struct, the clamps of the contract, the latent tile per cache kind, the list's
+// key source and the ONE body of the attention kernel.  The layout and the arithmetic are described at the top of
+// fa_fwd_mla_paged_gfx950.hip.  Device code only.
 #pragma once
 #include "fa_kernels.h"
 #include "fa_paged_tile.h"
@@ -26,11 +27,20 @@ struct MlaParams {
     int row_blocks, nsplit;
     float c;
     const float* kv_scale;   // FP8 cache: [1] fp32 on the device, key = kv_scale * float(code); else null
+    // The sparse call (fa_fwd_mla_sparse_gfx950.hip): token b's keys are the cache rows that list[b * topk + i] names.  table, ctx and
+    // cu are null there and B = T; the dense call leaves these three as they stand.
+    const int* list = nullptr;   // [T][topk] slots; an entry outside [0, slots) is skipped
+    int topk = 0;
+    int slots = 0;               // rows of the cache read as a flat array
 };
 
 
 // The FP8 attention kernel for `p` (fa_fwd_mla_paged_fp8_gfx950.hip; dtype: of q / out); partials and combine are the 16-bit call's.
 int launch_mla_fp8_kernel(const MlaParams& p, long long grid, int dtype, hipStream_t stream);
+// ... and the sparse call's (`p` as launch_mla_sparse fills it, kv_scale set), beside it in that translation unit.
+int launch_mla_sparse_fp8_kernel(const MlaParams& p, long long grid, int dtype, hipStream_t stream);
+// The combine of either call's partials (fa_fwd_mla_paged_gfx950.hip): row_blocks * p.B * 16 workgroups, after the attention kernel.
+int launch_mla_combine(const MlaParams& p, int row_blocks, int dtype, hipStream_t stream);
 
 namespace {
 
@@ -70,6 +80,71 @@ struct MlaBlock {
             rows = min(kMlaRows, R - r0);
         }
     }
+    // the sparse call: token b is a sequence of its own, its Hq heads cut into blocks in rank order; no length is read
+    struct ListRows {};
+    __device__ __forceinline__ MlaBlock(const MlaParams& p, int b, int rank, ListRows) {
+        L = 0;
+        s = b;   // (b < T: the grid)
+        n = 1;
+        r0 = rank * kMlaRows;
+        rows = max(min(kMlaRows, p.Hq - r0), 0);
+    }
+};
+
+// the block of workgroup (rank, b) for the body's key source
+template <bool kList>
+__device__ __forceinline__ MlaBlock mla_block(const MlaParams& p, int b, int rank) {
+    if constexpr (kList) return MlaBlock(p, b, rank, MlaBlock::ListRows{});
+    else return MlaBlock(p, b, rank);
+}
+
+// The sparse call's key source: key k of token b is entry k of its list, a slot of the flat cache; an entry outside [0, slots) names
+// no row -- its image row is zeros and its score masked.  The mask of a tile is ONE wave-uniform word: lane i holds entry k0 + i (one
+// coalesced 256-byte request, made a tile ahead) and the wave ballots its validity; each lane shifts the word once by its half's row
+// offset (4 hi) into two 32-bit words, so that element rr of sc[kk] tests the COMPILE-TIME bit crow(rr, 0) of word kk.  (A
+// per-element 64-bit shift by 32 kk + crow(rr, hi) spills 51 registers; this costs the entry and, while a tile is masked, two words.)
+struct MlaListKeys {
+    const int* list;
+    int kbeg, kend;
+    unsigned slots;
+    int entry;       // lane i: entry k0 + i of the tile whose scores are masked next
+    unsigned w[2];   // validity of the tile's keys 32 kk + 4 hi + (0 .. 31 - 4 hi)
+    // this split's entries: whole tiles of the list
+    __device__ __forceinline__ MlaListKeys(const MlaParams& p, int b, int split) {
+        const int tiles = (p.topk + kMlaKeys - 1) / kMlaKeys;
+        const int per = (tiles + p.nsplit - 1) / p.nsplit;
+        kbeg = split * per * kMlaKeys;
+        kend = min((split + 1) * per * kMlaKeys, p.topk);
+        list = p.list + (long long)b * p.topk;
+        slots = (unsigned)p.slots;
+        entry = -1;
+    }
+    // the cache row of key kv, -1: none (past the range, or an entry outside the cache)
+    __device__ __forceinline__ long long slot(int kv) const {
+        long long at = -1;
+        if (kv < kend) {
+            const int e = list[kv];
+            if ((unsigned)e < slots) at = e;
+        }
+        return at;
+    }
+    __device__ __forceinline__ void fetch_mask(int k0, int lane) {
+        const int k = k0 + lane;
+        entry = k < kend ? list[k] : -1;
+    }
+    __device__ __forceinline__ void tile_mask(int hi) {
+        const unsigned long long vm = __builtin_amdgcn_ballot_w64((unsigned)entry < slots);
+        w[0] = (unsigned)(vm >> (4 * hi));
+        w[1] = (unsigned)(vm >> (32 + 4 * hi));
+    }
+    __device__ __forceinline__ bool visible(int kk, int rr) const { return ((w[kk] >> crow(rr, 0)) & 1u) != 0; }
+};
+
+// (what the dense instances hold in its place: nothing)
+struct MlaNoList {
+    static constexpr int kbeg = 0, kend = 0;
+    __device__ __forceinline__ MlaNoList(const MlaParams&, int, int) {}
+    __device__ __forceinline__ bool visible(int, int) const { return false; }
 };
 
 // One latent tile of 64 keys on its way from the block pool to LDS: thread t takes rows (t >> 3) and (t >> 3) + 32 of the tile,
@@ -103,6 +178,19 @@ struct MlaTile {
             for (int i = 0; i < kMlaN; ++i) d[j][i] = kv < kend ? *reinterpret_cast<const Raw*>(row + 64 * EB * i) : Raw{};
         }
     }
+    // the same two steps for a list's tile: the slots are the entries themselves, and a row without one (slot -1) is zeros
+    __device__ __forceinline__ void lookup(const MlaListKeys& keys, int k0, int tid) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) slot[j] = keys.slot(k0 + (tid >> 3) + 32 * j);
+    }
+    __device__ __forceinline__ void load(const MlaParams& p, int tid) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const char* row = p.kv + slot[j] * (kMlaQK * EB) + (tid & 7) * (8 * EB);
+#pragma unroll
+            for (int i = 0; i < kMlaN; ++i) d[j][i] = slot[j] >= 0 ? *reinterpret_cast<const Raw*>(row + 64 * EB * i) : Raw{};
+        }
+    }
     __device__ __forceinline__ void store(char* img, int tid) const {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -115,21 +203,23 @@ struct MlaTile {
     }
 };
 
-// The attention kernel's body, one for both cache kinds (KV: Kv16 / KvFp8 of fa_paged_tile.h): they differ in how a tile reaches the
-// image (MlaTile) and in where the FP8 scale enters.  Ls: the latent image (kMlaLdsImage bytes), Xs: the partial scores
-// (kMlaLdsScores bytes), both 16-byte aligned LDS of the calling kernel.
-template <class T, class KV>
+// The attention kernel's body, one for both cache kinds (KV: Kv16 / KvFp8 of fa_paged_tile.h) and both key sources (kList: the sparse
+// call's list instead of a sequence's positions): the kinds differ in how a tile reaches the image (MlaTile) and in where the FP8
+// scale enters, the sources in the block of rows, the key range, the cache row behind a key and the scores that count -- each a
+// compile-time choice at its one place, so that the dense instances compile to what they were without the list.  Ls: the latent image
+// (kMlaLdsImage bytes), Xs: the partial scores (kMlaLdsScores bytes), both 16-byte aligned LDS of the calling kernel.
+template <class T, class KV, bool kList = false>
 __device__ __forceinline__ void mla_paged_body(const MlaParams& p, char* Ls, char* Xs) {
 
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rh = wave & 1, ch = wave >> 1;
-    // work item: (split, rank, sequence), the sequences side by side
+    // work item: (split, rank, sequence), the sequences side by side (the sparse call: a token is a sequence of its own)
     const int bid = (int)blockIdx.x;
     const int b = bid % p.B, rest = bid / p.B;
     const int rank = rest % p.row_blocks, split = rest / p.row_blocks;
 
-    const MlaBlock blk(p, b, rank);
+    const MlaBlock blk = mla_block<kList>(p, b, rank);
     if (blk.rows == 0) return;
     const int L = blk.L, n = blk.n, r0 = blk.r0, rows = blk.rows;
 
@@ -140,11 +230,13 @@ __device__ __forceinline__ void mla_paged_body(const MlaParams& p, char* Ls, cha
     const int tok = r / p.Hq, head = r - tok * p.Hq;
     const int pos = L - n + tok;
 
-    // this split's keys of this block: whole tiles of the sequence's own length, cut at the block's last visible key
+    // this split's keys of this block: whole tiles of the sequence's own length, cut at the block's last visible key (or whole
+    // tiles of the token's list: `keys`)
+    typename std::conditional<kList, MlaListKeys, MlaNoList>::type keys(p, b, split);
     const int tiles = (L + kMlaKeys - 1) / kMlaKeys;
     const int per = (tiles + p.nsplit - 1) / p.nsplit;
-    const int kbeg = split * per * kMlaKeys;
-    const int kend = min(min((split + 1) * per * kMlaKeys, L), L - n + (r0 + rows - 1) / p.Hq + 1);
+    const int kbeg = kList ? keys.kbeg : split * per * kMlaKeys;
+    const int kend = kList ? keys.kend : min(min((split + 1) * per * kMlaKeys, L), L - n + (r0 + rows - 1) / p.Hq + 1);
     const int ntiles = kend > kbeg ? (kend - kbeg + kMlaKeys - 1) / kMlaKeys : 0;
     const int* tab = p.table + (long long)b * p.max_blocks;
 
@@ -168,7 +260,14 @@ __device__ __forceinline__ void mla_paged_body(const MlaParams& p, char* Ls, cha
     float m = -__builtin_inff(), l = 0.f;
 
     MlaTile<T, KV> kt;
-    if (ntiles > 0) {
+    if constexpr (kList) {
+        if (ntiles > 0) {
+            kt.lookup(keys, kbeg, tid);
+            kt.load(p, tid);
+            kt.lookup(keys, kbeg + kMlaKeys, tid);
+            keys.fetch_mask(kbeg, lane);
+        }
+    } else if (ntiles > 0) {
         kt.lookup(p, tab, kbeg, kend, tid);
         kt.load(p, kbeg, kend, tid);
         kt.lookup(p, tab, kbeg + kMlaKeys, kend, tid);
@@ -180,7 +279,12 @@ __device__ __forceinline__ void mla_paged_body(const MlaParams& p, char* Ls, cha
         __syncthreads();   // every wave is done with the previous tile and the previous partial scores
         kt.store(Ls, tid);
         __syncthreads();
-        if (t + 1 < ntiles) {
+        if constexpr (kList) {
+            if (t + 1 < ntiles) {
+                kt.load(p, tid);
+                kt.lookup(keys, k0 + 2 * kMlaKeys, tid);
+            }
+        } else if (t + 1 < ntiles) {
             kt.load(p, k0 + kMlaKeys, kend, tid);
             kt.lookup(p, tab, k0 + 2 * kMlaKeys, kend, tid);
         }
@@ -199,6 +303,10 @@ __device__ __forceinline__ void mla_paged_body(const MlaParams& p, char* Ls, cha
                 *reinterpret_cast<f32x4_t*>(xmine + (4 * kk + q4) * 1024) = f32x4_t{sc[kk][4 * q4], sc[kk][4 * q4 + 1], sc[kk][4 * q4 + 2], sc[kk][4 * q4 + 3]};
         __syncthreads();
         // own + other, scale to log2 units, mask, running max over the lane pair (lanes l and l + 32 hold the same row)
+        if constexpr (kList) {
+            keys.tile_mask(hi);                     // this tile's validity word, from the entries fetched a tile ago
+            keys.fetch_mask(k0 + kMlaKeys, lane);   // ... and the next tile's entries
+        }
         float mx = -__builtin_inff();
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
@@ -209,7 +317,7 @@ __device__ __forceinline__ void mla_paged_body(const MlaParams& p, char* Ls, cha
                 for (int i = 0; i < 4; ++i) {
                     const int rr = 4 * q4 + i;
                     const int j = k0 + 32 * kk + crow(rr, hi);
-                    const float x = j <= pos && j < kend ? (sc[kk][rr] + y[i]) * c : -__builtin_inff();
+                    const float x = (kList ? keys.visible(kk, rr) : j <= pos && j < kend) ? (sc[kk][rr] + y[i]) * c : -__builtin_inff();
                     sc[kk][rr] = x;
                     mx = fmaxf(mx, x);
                 }

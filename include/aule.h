@@ -489,6 +489,72 @@ int32_t aule_attention_mla_paged_fp8_ex(const aule_mla_paged_fp8_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  The number aule_attention_mla_paged_workspace_size gives for the shape. */
 uint64_t aule_attention_mla_paged_fp8_workspace_size(const aule_mla_paged_fp8_desc* desc);
 
+/* SPARSE MLA (additive): absorbed multi-head latent attention over PER-TOKEN KEY LISTS (DeepSeek-V3.2 "DSA" and its derivatives: an    */
+/* indexer picks a fixed number of keys per query token, typically 2048, and the attention runs over only those rows of the latent     */
+/* cache, in decode and in prefill).  This comment is the contract.                                                                    */
+/* q is [total_tokens, heads_q, 576], fp16 or bf16, q_token_stride elements from one token to the next (a multiple of 8, >= heads_q *  */
+/* 576, the heads of a token contiguous: aule_mla_paged_desc's rule); out is [total_tokens, heads_q, 512] contiguous; lse (optional)   */
+/* [total_tokens, heads_q] fp32.  q, out and kv_cache are 16-byte aligned.                                                             */
+/* kv_cache is [num_blocks, block_size, 576], contiguous: of q's dtype (cache_dtype AULE_KV_CACHE_SAME, kv_scale NULL) or OCP e4m3fn   */
+/* codes with ONE fp32 scale on the device (AULE_KV_CACHE_FP8_E4M3, kv_scale required, 4-byte aligned; key = kv_scale * float(code     */
+/* row): exactly aule_mla_paged_fp8_desc's rule -- the scale multiplies the score scale and the fp32 accumulators, never an element,   */
+/* and with kv_scale = 1 the call equals the 16-bit call on the converted codes bit for bit).  The cache is addressed as a FLAT array  */
+/* of S = num_blocks * block_size rows ("slots"), so a contiguous [L, 576] latent is the cache [L, 1, 576]: sparse prefill over an     */
+/* un-paged latent.                                                                                                                    */
+/* indices is [total_tokens, topk] int32, contiguous, on the device, 1 <= topk <= 65536.  indices[t][i] is a slot, block * block_size  */
+/* + offset: the convention of slot_mapping in aule_mla_kv_append_desc.                                                                */
+/* RULE.  Token t, every head h: the key set is the multiset { kv_cache.flat[indices[t][i]] : 0 <= indices[t][i] < S }.  Entries       */
+/* outside [0, S) are skipped (-1 is the conventional pad; INT32_MIN and INT32_MAX are legal); a slot listed twice counts twice; there */
+/* is NO causal rule -- the indexer is responsible for visibility.  scores = scale * q . key over all 576 elements (scale = 0 means    */
+/* 1/sqrt(576)), values are the key's first 512 elements, lse is the natural log of the softmax denominator (kv_scale included).  A    */
+/* token with no valid entry gives zeros and lse = -inf.                                                                               */
+/* READS AND WRITES.  Every one of the total_tokens rows of out / lse is written.  A cache row that no valid entry names is never read */
+/* and cannot influence the result (an invalid entry contributes a row of zeros with weight 0, not some other row).  indices and       */
+/* kv_scale are read by the kernel on every launch: no host copy, no synchronisation, and no allocation when a workspace is passed, so */
+/* the call captures into a hipGraph and a replay sees their CURRENT contents.                                                         */
+/* LAUNCHES.  Work item (split, row block, token): a row block is 64 heads of ONE token, row_blocks = ceil(heads_q / 64); the list is  */
+/* cut into tiles = ceil(topk / 64) tiles of 64 entries and nsplit ranges, nsplit fixed on the host from the shape alone:              */
+/* nsplit = clamp(ceil(CUs / (total_tokens * row_blocks)), 1, min(64, max(1, tiles / 2))); split k owns tiles [k * ceil(tiles /        */
+/* nsplit), ...).  nsplit = 1: one launch.  nsplit > 1: fp32 partials of 512 + 2 floats per (split, token, head) in the workspace,     */
+/* aule_mla_paged_desc's layout, added by its combine kernel in split order (no atomics: two runs are bit-identical).  Workspace bytes */
+/* = round16(nsplit * total_tokens * heads_q * 514 * 4), 0 for nsplit = 1: aule_attention_mla_sparse_workspace_size() gives the        */
+/* number.  workspace = NULL: allocated and freed on the stream; a workspace that is given but smaller than that (or not 16-byte       */
+/* aligned) is refused with -3 and nothing is launched.                                                                                */
+/* REFUSED with -3 and a reason naming the field (aule_get_error), before the device is needed: a wrong struct_size; dtype outside     */
+/* {fp16, bf16}; cache_dtype outside {0, 1}; an FP8 cache without kv_scale, kv_scale with a 16-bit cache; heads_q < 1; topk outside    */
+/* 1..65536; num_blocks * block_size outside 1..2^31-1; total_tokens < 0; q_token_stride too small or not a multiple of 8;             */
+/* (total_tokens + 64) * heads_q or the grid past 2^31-1; a null or misaligned required pointer; a caller workspace smaller than the   */
+/* plan's.  The size query and the plan hook give the same verdict on every field and read no pointer.  total_tokens = 0 returns 0     */
+/* without a launch and without aule_init().                                                                                           */
+/* Not built: the indexer (the top-k selection); a causal rule in the kernel; packing several tokens' heads into one row block when    */
+/* heads_q < 64; logical positions resolved through a block table in the kernel; a backward; sink logits or tree masks with a list.    */
+typedef struct aule_mla_sparse_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_sparse_desc) = 120 */
+    int32_t dtype;             /* offset 4; type of q / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    int32_t cache_dtype;       /* offset 8; AULE_KV_CACHE_SAME (q's dtype) or AULE_KV_CACHE_FP8_E4M3 */
+    int32_t heads_q;           /* offset 12; >= 1 */
+    uint32_t num_blocks;       /* offset 16; num_blocks * block_size = S, 1 .. 2^31 - 1 */
+    uint32_t block_size;       /* offset 20 */
+    int32_t total_tokens;      /* offset 24; rows of q / out / indices; 0: returns 0 without a launch */
+    int32_t topk;              /* offset 28; entries per token, 1 .. 65536 */
+    float scale;               /* offset 32; 0 -> 1/sqrt(576) */
+    int32_t device;            /* offset 36; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 40; elements, >= heads_q * 576, a multiple of 8 */
+    void* stream;              /* offset 48; hipStream_t */
+    const void* q;             /* offset 56; [total_tokens, heads_q, 576], 16-bit */
+    const void* kv_cache;      /* offset 64; [num_blocks, block_size, 576], q's dtype or e4m3fn codes */
+    const int32_t* indices;    /* offset 72; [total_tokens, topk] slots, device */
+    const float* kv_scale;     /* offset 80; [1] fp32, device (AULE_KV_CACHE_FP8_E4M3), else NULL */
+    void* out;                 /* offset 88; [total_tokens, heads_q, 512], 16-bit, contiguous */
+    float* lse;                /* offset 96; optional (NULL to skip): [total_tokens, heads_q] fp32 */
+    void* workspace;           /* offset 104; optional, size from aule_attention_mla_sparse_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 112 */
+} aule_mla_sparse_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_mla_sparse_ex(const aule_mla_sparse_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
+uint64_t aule_attention_mla_sparse_workspace_size(const aule_mla_sparse_desc* desc);
+
 /* VARIABLE-LENGTH packed batches (additive): sequences of different lengths packed along one token axis, forward and backward --   */
 /* SFT with sequence packing, encoder batches without padding, prefill without a paged cache (flash_attn_varlen_func's case).        */
 /* Tensors: q, out, dout, dq are [total_q, heads_q, head_dim] and k, v, dk, dv [total_k, heads_kv, head_dim], fp16 or bf16, with     */
@@ -1142,6 +1208,17 @@ int32_t aule_hip_debug_shared_prefix_plan(const aule_paged_cascade_desc* desc, i
 /* capacity needed), 0 for a descriptor with nothing to do; -3 bad.  Host logic only, no aule_init(), no pointer of the descriptor  */
 /* is read (the pointer rules of the launch are not applied); without a device it plans for 256 compute units.                      */
 int32_t aule_hip_debug_mla_plan(const aule_mla_paged_desc* desc, int32_t* out, int32_t cap);
+/* Debug: the launch plan of aule_attention_mla_sparse_ex(desc) as integers -- out = {row blocks (ceil(heads_q / 64)), rows per     */
+/* block (64), nsplit, workgroups (total_tokens * row blocks * nsplit), workspace bytes low 32 bits, high 32 bits}.  Returns the    */
+/* ints written (negative: the capacity needed), 0 for a descriptor with nothing to do; -3 bad.  Host logic only, no aule_init(),   */
+/* no pointer of the descriptor is read (the pointer and workspace rules of the launch are not applied); without a device it plans  */
+/* for 256 compute units.                                                                                                           */
+int32_t aule_hip_debug_mla_sparse_plan(const aule_mla_sparse_desc* desc, int32_t* out, int32_t cap);
+/* Debug: aule_attention_mla_sparse_ex(desc) with `nsplit` key ranges instead of the plan's, clamped to 1 .. min(64, ceil(topk /    */
+/* 64)); nsplit < 1: -3.  Every other rule and return value of the entry; a caller workspace is sized for this nsplit.  For the     */
+/* bench that measures the plan's "one split per two tiles" cap (tools/bench_mla_sparse.py); results equal the entry's within the   */
+/* forward bounds, bit for bit only at the plan's own nsplit.                                                                       */
+int32_t aule_hip_debug_mla_sparse_launch_nsplit(const aule_mla_sparse_desc* desc, int32_t nsplit);
 /* Debug: the launch plan of aule_attention_mla_prefill_backward_ex(desc) as integers -- out = {heads per chunk, n_chunks (the last    */
 /* chunk may be short), the bound of n_chunks (16), delta workgroups, dQ workgroups, dK/dV workgroups (key blocks * batch * n_chunks),  */
 /* reduce workgroups, 1 if the reduce runs (else the dK/dV kernel writes dk_pe itself), workspace bytes low 32 bits, high 32 bits}.     */
