@@ -329,7 +329,7 @@ def flash_attention_mla_sparse(q, kv_cache, indices, scale=None, return_lse=Fals
     synchronisation, capturable, and a graph replay sees their current contents.  All argument errors are ValueErrors raised
     before the device is touched; CPU tensors that pass them are an AuleError; T = 0 returns empty tensors without a launch;
     tensors that require grad are refused.
-    Out of scope: the indexer itself (the top-k selection), a causal rule inside the kernel, packing several tokens' heads
+    Out of scope: the indexer itself lives in aule.mla_indexer (its result is `indices`), a causal rule inside the kernel, packing several tokens' heads
     into one row block when Hq < 64, logical-position indices resolved through a block table inside the kernel, a backward,
     sink logits or tree masks with a list, a fuzz_serving kind."""
     try:
@@ -338,6 +338,80 @@ def flash_attention_mla_sparse(q, kv_cache, indices, scale=None, return_lse=Fals
         raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
     from ._torch import mla_sparse
     return mla_sparse(q, kv_cache, indices, scale=scale, return_lse=return_lse, kv_scale=kv_scale)
+
+
+def mla_indexer_logits(q, weights, k_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, k_scale=None):
+    """The index logits of the sparse MLA's indexer (DeepSeek-V3.2 "DSA"), with the head sum fused into the tile that made the
+    scores:  logits[t, s] = sum_h weights[t, h] * relu(q[t, h, :] . k[s, :]).  The contract is stated once, at
+    aule_mla_indexer_logits_desc in include/aule.h; in short:
+
+        q        [T, H, 128] fp16 / bf16, 1 <= H <= 64, the last dimension contiguous; the token stride is free (a multiple of 8
+                 elements, at least H * 128: a slice of a wider projection is read in place)
+        weights  [T, H] fp32, contiguous: the caller folds H^-1/2, the softmax scale and any q scale into it
+        k_cache  [num_blocks, block_size, 128] (or [..., 1, 128]), contiguous, one key row per position for all heads: q's dtype,
+                 or torch.float8_e4m3fn codes with k_scale [num_blocks, block_size] fp32, one scale per row
+                 (quantize_indexer_cache_fp8).  The scale multiplies the finished logit, never an element: with every scale 1
+                 the FP8 call equals the 16-bit call on the converted codes bit for bit
+        block_tables [batch, max_blocks], context_lens [batch], cu_seqlens_q [batch + 1]: int32, contiguous, on q's device, read
+                 IN PLACE on every launch (nothing is converted: another dtype is a ValueError); the rules and device-side clamps
+                 of flash_attention_mla_paged.  cu_seqlens_q = None is plain decode (sequence b owns row b, T == batch)
+        max_seqlen_q  None = T with offsets (no synchronisation; it only sizes the grid and caps every sequence's new tokens)
+
+    Token i of sequence b sits at position p = L_b - n_b + i and sees key j iff 0 <= j <= p.  Returns logits [T, W] fp32 with
+    W = max_blocks * block_size: for a row that belongs to a sequence every column is written, the logit where the key is visible
+    and -inf elsewhere; rows of no sequence are never written (torch.empty).  A cache row no token sees is never read.  Memory:
+    T * W * 4 bytes -- 1 GB at 2048 tokens x 128 K columns: chunk T or size the table.  No host synchronisation, capturable, two
+    runs are bit-identical.  All argument errors are ValueErrors raised before the device is touched; CPU tensors that pass
+    them are an AuleError; tensors that require grad are refused.
+    Out of scope: FP8 queries and FP8 MFMAs, a fused streaming top-k that never writes [T, W], an append kernel for the index
+    keys, H > 64, a backward."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_indexer_logits as impl
+    return impl(q, weights, k_cache, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, k_scale=k_scale)
+
+
+def mla_indexer_topk(logits, topk, block_tables, context_lens, block_size, cu_seqlens_q=None, max_seqlen_q=None, output="slots"):
+    """The per-token key lists of the sparse MLA's indexer from ANY fp32 logits [T, max_blocks * block_size] (row stride free).  The
+    contract is stated once, at aule_mla_indexer_topk_desc in include/aule.h; in short: visibility comes from the positions
+    (key j iff 0 <= j <= p, the arithmetic of mla_indexer_logits), not from -inf marks; among token t's visible keys the order
+    is logit descending by numeric value (-0 == +0, a NaN ranks as -inf), then position ascending; the first min(topk, p + 1)
+    are emitted in ASCENDING position order and the tail is -1; a token with p < 0 gets all -1; rows of no sequence are never
+    written.  1 <= topk <= 65536.  output "slots": block_tables[b][pos // block_size] * block_size + pos % block_size, what
+    flash_attention_mla_sparse consumes when the latent cache shares the table and the block size; "positions": the raw
+    positions (map them with paged_slot_mapping for a latent cache of another block size).  Returns indices [T, topk] int32.
+    Deterministic, no synchronisation, capturable.  Tables as in mla_indexer_logits: int32, contiguous, read in place.  All
+    argument errors are ValueErrors raised before the device is touched; CPU tensors that pass them are an AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_indexer_topk as impl
+    return impl(logits, topk, block_tables, context_lens, block_size, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, output=output)
+
+
+def mla_indexer(q, weights, k_cache, block_tables, context_lens, topk, cu_seqlens_q=None, max_seqlen_q=None, k_scale=None, output="slots",
+                return_logits=False):
+    """The sparse MLA's indexer: mla_indexer_logits, then mla_indexer_topk on its result -- two launches in a row.  Returns
+    indices [T, topk] int32 (or (indices, logits) with return_logits), which go straight into
+    flash_attention_mla_sparse(q_latent, kv_cache, indices) when the latent cache shares block_tables and the block size."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_indexer as impl
+    return impl(q, weights, k_cache, block_tables, context_lens, topk, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, k_scale=k_scale,
+                output=output, return_logits=return_logits)
+
+
+def quantize_indexer_cache_fp8(k_cache):
+    """(codes, k_scale) for mla_indexer_logits' FP8 cache: float8_e4m3fn codes of an index key cache [num_blocks, block_size, 128]
+    and one scale per row, k_scale [num_blocks, block_size] fp32 = the row's amax / 448 (1.0 for an all-zero row), saturating.
+    Plain torch ops; works on CPU tensors."""
+    from ._torch import quantize_indexer_cache_fp8 as impl
+    return impl(k_cache)
 
 
 def mla_kv_append(c_kv, k_pe, kv_cache, slot_mapping, kv_scale=None, cos=None, sin=None, positions=None, rope_layout="half"):
@@ -835,7 +909,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_sparse", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

@@ -224,6 +224,61 @@ class MlaSparseDesc(ctypes.Structure):
     ]
 
 
+class MlaIndexerLogitsDesc(ctypes.Structure):
+    """struct aule_mla_indexer_logits_desc (include/aule.h): the index logits of the sparse MLA's indexer, both cache kinds."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("cache_dtype", ctypes.c_int32),
+        ("heads", ctypes.c_uint32),
+        ("head_dim", ctypes.c_uint32),
+        ("batch", ctypes.c_uint32),
+        ("num_blocks", ctypes.c_uint32),
+        ("block_size", ctypes.c_uint32),
+        ("max_blocks", ctypes.c_uint32),
+        ("total_tokens", ctypes.c_uint32),
+        ("max_seqlen_q", ctypes.c_uint32),
+        ("device", ctypes.c_int32),
+        ("q_token_stride", ctypes.c_int64),
+        ("logits_stride", ctypes.c_int64),
+        ("stream", ctypes.c_void_p),
+        ("q", ctypes.c_void_p),
+        ("weights", ctypes.c_void_p),
+        ("k_cache", ctypes.c_void_p),
+        ("k_scale", ctypes.c_void_p),
+        ("block_tables", ctypes.c_void_p),
+        ("context_lens", ctypes.c_void_p),
+        ("cu_seqlens_q", ctypes.c_void_p),
+        ("logits", ctypes.c_void_p),
+    ]
+
+
+INDEXER_SLOTS, INDEXER_POSITIONS = 0, 1
+
+
+class MlaIndexerTopkDesc(ctypes.Structure):
+    """struct aule_mla_indexer_topk_desc (include/aule.h): the per-token top-k key lists of the sparse MLA's indexer."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("output", ctypes.c_int32),
+        ("topk", ctypes.c_int32),
+        ("batch", ctypes.c_uint32),
+        ("block_size", ctypes.c_uint32),
+        ("max_blocks", ctypes.c_uint32),
+        ("total_tokens", ctypes.c_uint32),
+        ("max_seqlen_q", ctypes.c_uint32),
+        ("device", ctypes.c_int32),
+        ("reserved", ctypes.c_uint32),
+        ("logits_stride", ctypes.c_int64),
+        ("stream", ctypes.c_void_p),
+        ("logits", ctypes.c_void_p),
+        ("block_tables", ctypes.c_void_p),
+        ("context_lens", ctypes.c_void_p),
+        ("cu_seqlens_q", ctypes.c_void_p),
+        ("indices", ctypes.c_void_p),
+    ]
+
+
 class MlaKvAppendDesc(ctypes.Structure):
     """struct aule_mla_kv_append_desc (include/aule.h): the latent cache append of the paged MLA."""
     _fields_ = [
@@ -543,6 +598,8 @@ SIGNATURES = [
     ("aule_attention_mla_paged_fp8_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedFp8Desc)]),
     ("aule_attention_mla_sparse_ex", _I32, [ctypes.POINTER(MlaSparseDesc)]),
     ("aule_attention_mla_sparse_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaSparseDesc)]),
+    ("aule_mla_indexer_logits_ex", _I32, [ctypes.POINTER(MlaIndexerLogitsDesc)]),
+    ("aule_mla_indexer_topk_ex", _I32, [ctypes.POINTER(MlaIndexerTopkDesc)]),
     ("aule_mla_kv_append_ex", _I32, [ctypes.POINTER(MlaKvAppendDesc)]),
     ("aule_attention_varlen_forward_ex", _I32, [ctypes.POINTER(VarlenDesc)]),
     ("aule_attention_varlen_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),
@@ -573,6 +630,7 @@ SIGNATURES = [
     ("aule_hip_debug_mla_plan", _I32, [ctypes.POINTER(MlaPagedDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_sparse_plan", _I32, [ctypes.POINTER(MlaSparseDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_sparse_launch_nsplit", _I32, [ctypes.POINTER(MlaSparseDesc), _I32]),
+    ("aule_hip_debug_mla_indexer_plan", _I32, [ctypes.POINTER(MlaIndexerLogitsDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_prefill_backward_plan", _I32, [ctypes.POINTER(MlaPrefillBwdDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_last_backward_route", _I32, []),
     ("aule_hip_debug_backward_route", _I32, [ctypes.POINTER(AttnBwdDesc)]),

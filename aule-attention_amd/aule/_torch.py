@@ -1419,6 +1419,172 @@ def mla_sparse(q, kv_cache, indices, scale=None, return_lse=False, kv_scale=None
     return result
 
 
+MLA_INDEXER_MAX_HEADS = 64
+MLA_INDEXER_MAX_TOPK = 65536
+_INDEXER_OUTPUTS = {"slots": _capi.INDEXER_SLOTS, "positions": _capi.INDEXER_POSITIONS}
+
+
+def _indexer_tables(T, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, block_size):
+    """The table, length and offset rules the two indexer entries share.  The kernels read these tensors IN PLACE on every launch (a
+    graph replay sees their current contents), so nothing is converted or copied: int32 and contiguous or a ValueError.  Returns
+    (batch, max_seqlen_q as the descriptor takes it); max_seqlen_q = None with offsets is total_tokens -- no sequence has more -- and
+    costs no synchronisation, only a larger grid."""
+    for name, t in (("block_tables", block_tables), ("context_lens", context_lens)) + ((("cu_seqlens_q", cu_seqlens_q),) if cu_seqlens_q is not None else ()):
+        if not torch.is_tensor(t) or t.dtype != torch.int32:
+            raise ValueError(f"{name} must be an int32 tensor (it is read on the device as it stands), got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous: the kernel reads it in place on every launch")
+    B = _paged_tables(block_tables, context_lens, None if cu_seqlens_q is not None else T)
+    if cu_seqlens_q is not None:
+        _ragged_offsets(B, cu_seqlens_q, max_seqlen_q)
+        max_seqlen_q = max(min(T if max_seqlen_q is None else max_seqlen_q, T), 1)
+    elif max_seqlen_q not in (None, 1):
+        raise ValueError(f"max_seqlen_q must be None or 1 without cu_seqlens_q (one token per sequence), got {max_seqlen_q!r}")
+    else:
+        max_seqlen_q = 1
+    if isinstance(block_size, bool) or not isinstance(block_size, int) or block_size < 1:
+        raise ValueError(f"block_size must be a positive int, got {block_size!r}")
+    if block_size * block_tables.shape[1] >= 2 ** 30:
+        raise ValueError(f"max_blocks * block_size = {block_tables.shape[1]} * {block_size} must stay below 2^30")
+    return B, max_seqlen_q
+
+
+def mla_indexer_logits(q, weights, k_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, k_scale=None):
+    """The index logits of the sparse MLA's indexer, logits[t, s] = sum_h weights[t, h] * relu(q[t, h] . k[s]) over a paged cache of
+    index keys; csrc/fa_mla_indexer_gfx950.hip behind aule_mla_indexer_logits_ex, whose descriptor comment in include/aule.h is the
+    contract (aule.mla_indexer_logits documents the arguments).  One launch, no device->host copy, no synchronisation.  All argument
+    errors are ValueErrors raised before the device is touched; CPU tensors that pass them are an AuleError."""
+    if torch.is_tensor(k_cache) and k_cache.dim() == 4 and k_cache.shape[2] == 1:
+        k_cache = k_cache[:, :, 0]
+    if not torch.is_tensor(q) or not torch.is_tensor(k_cache) or q.dim() != 3 or k_cache.dim() != 3:
+        raise ValueError("expected q [T,H,128] and k_cache [num_blocks, block_size, 128] (or [num_blocks, block_size, 1, 128])")
+    if q.shape[-1] != 128 or k_cache.shape[-1] != 128:
+        raise ValueError(f"the index head width must be 128: query={q.shape[-1]}, cache={k_cache.shape[-1]}")
+    T, H, _ = q.shape
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"q must be fp16 or bf16, got {q.dtype}")
+    if not 1 <= H <= MLA_INDEXER_MAX_HEADS:
+        raise ValueError(f"the indexer takes 1 .. {MLA_INDEXER_MAX_HEADS} index heads, got {H}")
+    fp8 = k_cache.dtype != q.dtype
+    if fp8 and k_cache.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"k_cache must have q's dtype ({q.dtype}) or be torch.float8_e4m3fn codes with k_scale, got {k_cache.dtype}")
+    if fp8 and k_scale is None:
+        raise ValueError("a float8_e4m3fn k_cache needs k_scale, the per-row scales [num_blocks, block_size] fp32 (quantize_indexer_cache_fp8)")
+    if not fp8 and k_scale is not None:
+        raise ValueError("k_scale applies to a float8_e4m3fn cache only; a 16-bit cache holds the values themselves")
+    if fp8 and (not torch.is_tensor(k_scale) or k_scale.dtype != torch.float32 or tuple(k_scale.shape) != tuple(k_cache.shape[:2])
+                or not k_scale.is_contiguous()):
+        raise ValueError(f"k_scale must be a contiguous fp32 tensor [num_blocks, block_size] = {list(k_cache.shape[:2])} (one scale per cache row)")
+    if not torch.is_tensor(weights) or weights.dtype != torch.float32 or tuple(weights.shape) != (T, H) or not weights.is_contiguous():
+        raise ValueError(f"weights must be a contiguous fp32 tensor [T, H] = [{T}, {H}]")
+    if not k_cache.is_contiguous():
+        raise ValueError("k_cache must be contiguous")
+    if k_cache.shape[0] == 0 or k_cache.shape[1] == 0 or k_cache.shape[0] * k_cache.shape[1] > 2 ** 31 - 1:
+        raise ValueError(f"the cache must hold 1 .. 2^31 - 1 rows (num_blocks * block_size), got {k_cache.shape[0]} * {k_cache.shape[1]}")
+    B, max_sq = _indexer_tables(T, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, k_cache.shape[1])
+    if torch.is_grad_enabled() and (q.requires_grad or weights.requires_grad or k_cache.requires_grad):
+        raise ValueError("the MLA indexer has no backward: detach the inputs or call it under torch.no_grad()")
+    q, q_stride = _packed_tokens(q)
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): the MLA indexer needs ROCm device tensors; there is no CPU fallback")
+    tensors = [weights, k_cache, block_tables, context_lens] + ([k_scale] if fp8 else []) + ([cu_seqlens_q] if cu_seqlens_q is not None else [])
+    _same_device("MLA indexer", q, *tensors)
+    W = block_tables.shape[1] * k_cache.shape[1]
+    logits = torch.empty((T, W), device=q.device, dtype=torch.float32)
+    if T == 0 or B == 0:
+        return logits
+    lib = _capi.get_lib()
+    d = _capi.MlaIndexerLogitsDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[q.dtype]
+    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    d.heads, d.head_dim, d.batch = H, 128, B
+    d.num_blocks, d.block_size, d.max_blocks = k_cache.shape[0], k_cache.shape[1], block_tables.shape[1]
+    d.total_tokens, d.max_seqlen_q = T, max_sq
+    d.q_token_stride, d.logits_stride = q_stride, W
+    d.device = _device_index(q.device)
+    d.stream = _stream_ptr(q.device)
+    d.q, d.weights, d.k_cache, d.logits = q.data_ptr(), weights.data_ptr(), k_cache.data_ptr(), logits.data_ptr()
+    d.k_scale = k_scale.data_ptr() if fp8 else None
+    d.block_tables, d.context_lens = block_tables.data_ptr(), context_lens.data_ptr()
+    d.cu_seqlens_q = cu_seqlens_q.data_ptr() if cu_seqlens_q is not None else None
+    _capi.check(lib.aule_mla_indexer_logits_ex(ctypes.byref(d)), "aule_mla_indexer_logits_ex")
+    return logits
+
+
+def mla_indexer_topk(logits, topk, block_tables, context_lens, block_size, cu_seqlens_q=None, max_seqlen_q=None, output="slots"):
+    """The per-token top-k key lists of the sparse MLA's indexer from fp32 logits [T, max_blocks * block_size];
+    csrc/fa_mla_indexer_gfx950.hip behind aule_mla_indexer_topk_ex, whose descriptor comment in include/aule.h is the contract
+    (aule.mla_indexer_topk documents the arguments).  One launch, no synchronisation, deterministic.  All argument errors are
+    ValueErrors raised before the device is touched; CPU tensors that pass them are an AuleError."""
+    if not torch.is_tensor(logits) or logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"logits must be an fp32 [T, max_blocks * block_size] tensor, got {logits.dtype if torch.is_tensor(logits) else type(logits).__name__}")
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= MLA_INDEXER_MAX_TOPK:
+        raise ValueError(f"topk must be an int in 1 .. {MLA_INDEXER_MAX_TOPK}, got {topk!r}")
+    if output not in _INDEXER_OUTPUTS:
+        raise ValueError(f"output must be 'slots' or 'positions', got {output!r}")
+    T = logits.shape[0]
+    B, max_sq = _indexer_tables(T, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, block_size)
+    W = block_tables.shape[1] * block_size
+    if logits.shape[1] != W:
+        raise ValueError(f"logits must have max_blocks * block_size = {block_tables.shape[1]} * {block_size} = {W} columns, got {logits.shape[1]}")
+    if W > 1 and logits.stride(1) != 1 or T > 1 and logits.stride(0) < W:
+        raise ValueError("the rows of logits must be contiguous (any row stride >= the width): pass logits.contiguous()")
+    if torch.is_grad_enabled() and logits.requires_grad:
+        raise ValueError("the MLA indexer has no backward: detach the inputs or call it under torch.no_grad()")
+    if not logits.is_cuda:
+        raise _capi.AuleError("aule (HIP build): the MLA indexer needs ROCm device tensors; there is no CPU fallback")
+    _same_device("MLA indexer", logits, block_tables, context_lens, *([cu_seqlens_q] if cu_seqlens_q is not None else []))
+    indices = torch.empty((T, topk), device=logits.device, dtype=torch.int32)
+    if T == 0 or B == 0:
+        return indices
+    lib = _capi.get_lib()
+    d = _capi.MlaIndexerTopkDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.output, d.topk, d.batch = _INDEXER_OUTPUTS[output], topk, B
+    d.block_size, d.max_blocks = block_size, block_tables.shape[1]
+    d.total_tokens, d.max_seqlen_q = T, max_sq
+    d.logits_stride = logits.stride(0) if T > 1 else W
+    d.device = _device_index(logits.device)
+    d.stream = _stream_ptr(logits.device)
+    d.logits, d.indices = logits.data_ptr(), indices.data_ptr()
+    d.block_tables, d.context_lens = block_tables.data_ptr(), context_lens.data_ptr()
+    d.cu_seqlens_q = cu_seqlens_q.data_ptr() if cu_seqlens_q is not None else None
+    _capi.check(lib.aule_mla_indexer_topk_ex(ctypes.byref(d)), "aule_mla_indexer_topk_ex")
+    return indices
+
+
+def mla_indexer(q, weights, k_cache, block_tables, context_lens, topk, cu_seqlens_q=None, max_seqlen_q=None, k_scale=None, output="slots",
+                return_logits=False):
+    """mla_indexer_logits, then mla_indexer_topk on its result: the two launches in a row.  topk and output are checked before the
+    first launch.  Returns indices [T, topk] int32, or (indices, logits)."""
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= MLA_INDEXER_MAX_TOPK:
+        raise ValueError(f"topk must be an int in 1 .. {MLA_INDEXER_MAX_TOPK}, got {topk!r}")
+    if output not in _INDEXER_OUTPUTS:
+        raise ValueError(f"output must be 'slots' or 'positions', got {output!r}")
+    logits = mla_indexer_logits(q, weights, k_cache, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q,
+                                k_scale=k_scale)
+    block_size = k_cache.shape[1]
+    indices = mla_indexer_topk(logits, topk, block_tables, context_lens, block_size, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q,
+                               output=output)
+    return (indices, logits) if return_logits else indices
+
+
+def quantize_indexer_cache_fp8(k_cache):
+    """(codes, k_scale) for the indexer's FP8 key cache: float8_e4m3fn codes of an index key cache [num_blocks, block_size, 128] (or
+    [..., 1, 128]) and one scale PER ROW, k_scale [num_blocks, block_size] fp32 = the row's amax / 448 (1.0 for an all-zero row), with
+    k_cache ~= k_scale[..., None] * codes.  Divided, clamped to +-448 (torch's cast does not saturate), then cast.  Plain torch ops;
+    works on CPU tensors."""
+    if torch.is_tensor(k_cache) and k_cache.dim() == 4 and k_cache.shape[2] == 1:
+        k_cache = k_cache[:, :, 0]
+    if not torch.is_tensor(k_cache) or k_cache.dim() != 3 or k_cache.shape[-1] != 128:
+        raise ValueError("expected an index key cache [num_blocks, block_size, 128] (or [num_blocks, block_size, 1, 128])")
+    x = k_cache.float()
+    amax = x.abs().amax(dim=-1)
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax)).contiguous()
+    return (x / scale[..., None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn), scale
+
+
 def quantize_mla_cache_fp8(kv_cache):
     """(codes, scale) for the FP8 paged MLA: float8_e4m3fn codes of a [num_blocks, block_size, 576] (or [..., 1, 576]) latent cache and
     ONE scale, a [1] fp32 tensor on the cache's device = amax / 448 (1.0 for an all-zero cache), with kv_cache ~= scale * codes.

@@ -104,6 +104,29 @@ static_assert(sizeof(aule_mla_sparse_desc) == 120 && offsetof(aule_mla_sparse_de
                   offsetof(aule_mla_sparse_desc, kv_scale) == 80 && offsetof(aule_mla_sparse_desc, out) == 88 && offsetof(aule_mla_sparse_desc, lse) == 96 &&
                   offsetof(aule_mla_sparse_desc, workspace) == 104 && offsetof(aule_mla_sparse_desc, workspace_bytes) == 112,
               "aule_mla_sparse_desc layout is part of the ABI");
+static_assert(sizeof(aule_mla_indexer_logits_desc) == 136 && offsetof(aule_mla_indexer_logits_desc, dtype) == 4 &&
+                  offsetof(aule_mla_indexer_logits_desc, cache_dtype) == 8 && offsetof(aule_mla_indexer_logits_desc, heads) == 12 &&
+                  offsetof(aule_mla_indexer_logits_desc, head_dim) == 16 && offsetof(aule_mla_indexer_logits_desc, batch) == 20 &&
+                  offsetof(aule_mla_indexer_logits_desc, num_blocks) == 24 && offsetof(aule_mla_indexer_logits_desc, block_size) == 28 &&
+                  offsetof(aule_mla_indexer_logits_desc, max_blocks) == 32 && offsetof(aule_mla_indexer_logits_desc, total_tokens) == 36 &&
+                  offsetof(aule_mla_indexer_logits_desc, max_seqlen_q) == 40 && offsetof(aule_mla_indexer_logits_desc, device) == 44 &&
+                  offsetof(aule_mla_indexer_logits_desc, q_token_stride) == 48 && offsetof(aule_mla_indexer_logits_desc, logits_stride) == 56 &&
+                  offsetof(aule_mla_indexer_logits_desc, stream) == 64 && offsetof(aule_mla_indexer_logits_desc, q) == 72 &&
+                  offsetof(aule_mla_indexer_logits_desc, weights) == 80 && offsetof(aule_mla_indexer_logits_desc, k_cache) == 88 &&
+                  offsetof(aule_mla_indexer_logits_desc, k_scale) == 96 && offsetof(aule_mla_indexer_logits_desc, block_tables) == 104 &&
+                  offsetof(aule_mla_indexer_logits_desc, context_lens) == 112 && offsetof(aule_mla_indexer_logits_desc, cu_seqlens_q) == 120 &&
+                  offsetof(aule_mla_indexer_logits_desc, logits) == 128,
+              "aule_mla_indexer_logits_desc layout is part of the ABI");
+static_assert(sizeof(aule_mla_indexer_topk_desc) == 96 && offsetof(aule_mla_indexer_topk_desc, output) == 4 &&
+                  offsetof(aule_mla_indexer_topk_desc, topk) == 8 && offsetof(aule_mla_indexer_topk_desc, batch) == 12 &&
+                  offsetof(aule_mla_indexer_topk_desc, block_size) == 16 && offsetof(aule_mla_indexer_topk_desc, max_blocks) == 20 &&
+                  offsetof(aule_mla_indexer_topk_desc, total_tokens) == 24 && offsetof(aule_mla_indexer_topk_desc, max_seqlen_q) == 28 &&
+                  offsetof(aule_mla_indexer_topk_desc, device) == 32 && offsetof(aule_mla_indexer_topk_desc, reserved) == 36 &&
+                  offsetof(aule_mla_indexer_topk_desc, logits_stride) == 40 && offsetof(aule_mla_indexer_topk_desc, stream) == 48 &&
+                  offsetof(aule_mla_indexer_topk_desc, logits) == 56 && offsetof(aule_mla_indexer_topk_desc, block_tables) == 64 &&
+                  offsetof(aule_mla_indexer_topk_desc, context_lens) == 72 && offsetof(aule_mla_indexer_topk_desc, cu_seqlens_q) == 80 &&
+                  offsetof(aule_mla_indexer_topk_desc, indices) == 88,
+              "aule_mla_indexer_topk_desc layout is part of the ABI");
 static_assert(sizeof(aule_mla_kv_append_desc) == 128 && offsetof(aule_mla_kv_append_desc, dtype) == 4 &&
                   offsetof(aule_mla_kv_append_desc, cache_dtype) == 8 && offsetof(aule_mla_kv_append_desc, rope_layout) == 12 &&
                   offsetof(aule_mla_kv_append_desc, total_tokens) == 16 && offsetof(aule_mla_kv_append_desc, num_blocks) == 20 &&
@@ -1676,6 +1699,142 @@ int32_t aule_attention_mla_sparse_ex(const aule_mla_sparse_desc* d) {
     return mla_sparse_launch(d, 0);
 }
 
+// The MLA indexer: index logits and top-k key lists, one checker per kind; `launch`: the pointer rules of a call that has something to
+// do as well (the plan hook reads no pointer).  Host logic only, asked before the device is needed.  What the two kinds share -- the
+// table, the ragged queries, the logits' row stride -- is stated once.
+extern "C++" {
+template <class Desc>
+static bool indexer_nothing_to_do(const Desc* d) { return d->total_tokens == 0 || d->batch == 0; }
+
+template <class Desc>
+static const char* indexer_shape_error(const Desc* d, Reason& why) {
+    if (bad_block_table(d->block_size, d->max_blocks))
+        return reasonf(why, "block_size (%u) and max_blocks (%u) must be positive and block_size * max_blocks below 2^30", d->block_size, d->max_blocks);
+    if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
+    const int64_t W = (int64_t)d->block_size * d->max_blocks;
+    if (d->logits_stride < W)
+        return reasonf(why, "logits_stride (%lld) is smaller than a row (max_blocks * block_size = %lld columns)", (long long)d->logits_stride, (long long)W);
+    if (d->batch >= (1u << 30)) return reasonf(why, "batch (%u) too large", d->batch);
+    if (d->total_tokens >= (1u << 30)) return reasonf(why, "total_tokens (%u) too large", d->total_tokens);
+    if (indexer_nothing_to_do(d)) return nullptr;
+    if (d->cu_seqlens_q == nullptr && d->total_tokens < d->batch)
+        return reasonf(why, "cu_seqlens_q is null (plain decode: sequence b owns row b) and total_tokens (%u) < batch (%u)", d->total_tokens, d->batch);
+    return nullptr;
+}
+
+// (plain decode reads max_seqlen_q as 1; no sequence has more tokens than the batch)
+template <class Desc>
+static int indexer_max_sq(const Desc* d) {
+    return d->cu_seqlens_q == nullptr ? 1 : (int)(d->max_seqlen_q < d->total_tokens ? d->max_seqlen_q : d->total_tokens);
+}
+}   // extern "C++"
+
+// (`d` passed the field rules of mla_indexer_logits_desc_error: the plan reads the shape, none of the pointers but whether cu_seqlens_q is there)
+static aule_hip::MlaIndexerPlan mla_indexer_plan_of(const aule_mla_indexer_logits_desc* d) {
+    return aule_hip::mla_indexer_plan((int)d->batch, indexer_max_sq(d), (long long)d->block_size * d->max_blocks, d->device);
+}
+
+static const char* mla_indexer_logits_desc_error(const aule_mla_indexer_logits_desc* d, bool launch, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_mla_indexer_logits_desc)) return kBadDescriptor;
+    if (!is_16_bit(d->dtype)) return reasonf(why, "dtype %d (of q) must be fp16 or bf16", d->dtype);
+    if (cache_dtype_error(d->cache_dtype)) return reasonf(why, "cache_dtype %d must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3", d->cache_dtype);
+    if (d->heads < 1 || d->heads > (uint32_t)aule_hip::kMlaIndexerMaxHeads) return reasonf(why, "heads (%u) must be in 1 .. %d", d->heads, aule_hip::kMlaIndexerMaxHeads);
+    if (d->head_dim != 128) return reasonf(why, "head_dim (%u) must be 128", d->head_dim);
+    if (d->num_blocks == 0 || (uint64_t)d->num_blocks * d->block_size > 0x7fffffffull)
+        return reasonf(why, "num_blocks * block_size (%u * %u) must be in 1 .. 2^31 - 1", d->num_blocks, d->block_size);
+    if (const char* e = indexer_shape_error(d, why)) return e;
+    if (const char* e = varlen_stride_error("q", d->q_token_stride, (uint64_t)d->heads * 128, "heads", why)) return e;
+    if (indexer_nothing_to_do(d)) return nullptr;
+    const aule_hip::MlaIndexerPlan plan = mla_indexer_plan_of(d);
+    if (plan.grid > 0x7fffffffll)
+        return reasonf(why, "the grid (batch %u * token groups %d * key chunks %d) exceeds 2^31 - 1 workgroups", d->batch, plan.token_groups, plan.key_chunks);
+    if (!launch) return nullptr;
+    if (!d->q || !d->weights || !d->k_cache || !d->block_tables || !d->context_lens || !d->logits)
+        return "null tensor pointer (q, weights, k_cache, block_tables, context_lens and logits are required)";
+    if (misaligned(d->q) || misaligned(d->k_cache)) return "q and k_cache must be 16-byte aligned";
+    const bool fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
+    if (fp8 && !d->k_scale) return "null k_scale (an FP8 cache needs [num_blocks, block_size] fp32 values on the device)";
+    if (!fp8 && d->k_scale) return "k_scale applies to an FP8 cache only; a 16-bit cache holds the values themselves";
+    if (((reinterpret_cast<uintptr_t>(d->weights) | reinterpret_cast<uintptr_t>(d->k_scale) | reinterpret_cast<uintptr_t>(d->logits) |
+          reinterpret_cast<uintptr_t>(d->block_tables) | reinterpret_cast<uintptr_t>(d->context_lens) | reinterpret_cast<uintptr_t>(d->cu_seqlens_q)) & 3) != 0)
+        return "weights, k_scale, logits, block_tables, context_lens and cu_seqlens_q must be 4-byte aligned";
+    return nullptr;
+}
+
+int32_t aule_mla_indexer_logits_ex(const aule_mla_indexer_logits_desc* d) {
+    RoctxRange range("aule.mla_indexer_logits");
+    const char* what = "MLA indexer logits";
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_indexer_logits_desc_error(d, true, text)) {
+        set_error("%s failed: %s", what, why);
+        return -3;
+    }
+    if (indexer_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaIndexerArgs a;
+    a.q = d->q; a.weights = d->weights; a.k_cache = d->k_cache; a.logits = d->logits;
+    a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
+    a.T = (int)d->total_tokens; a.B = (int)d->batch; a.H = (int)d->heads;
+    a.num_blocks = (int)d->num_blocks; a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
+    a.max_seqlen_q = indexer_max_sq(d);
+    a.q_token_stride = d->q_token_stride; a.logits_stride = d->logits_stride;
+    a.dtype = d->dtype;
+    a.device = d->device;
+    if (d->cache_dtype == AULE_KV_CACHE_FP8_E4M3) {
+        a.cache_kind = aule_hip::kCacheFp8E4M3;
+        a.k_scale = d->k_scale;
+    }
+    const aule_hip::MlaIndexerPlan plan = mla_indexer_plan_of(d);
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    return launched(what, aule_hip::launch_mla_indexer_logits(a, plan, (hipStream_t)d->stream));
+}
+
+static const char* mla_indexer_topk_desc_error(const aule_mla_indexer_topk_desc* d, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_mla_indexer_topk_desc)) return kBadDescriptor;
+    if (d->output != AULE_INDEXER_SLOTS && d->output != AULE_INDEXER_POSITIONS)
+        return reasonf(why, "output %d must be AULE_INDEXER_SLOTS or AULE_INDEXER_POSITIONS", d->output);
+    if (d->topk < 1 || d->topk > aule_hip::kMlaIndexerMaxTopk) return reasonf(why, "topk (%d) must be in 1 .. %d", d->topk, aule_hip::kMlaIndexerMaxTopk);
+    if (d->reserved != 0) return reasonf(why, "reserved (%u) must be 0", d->reserved);
+    if (const char* e = indexer_shape_error(d, why)) return e;
+    if (indexer_nothing_to_do(d)) return nullptr;
+    if ((uint64_t)d->batch * (uint64_t)indexer_max_sq(d) > 0x7fffffffull)
+        return reasonf(why, "the grid (batch %u * max_seqlen_q %d) exceeds 2^31 - 1 workgroups", d->batch, indexer_max_sq(d));
+    if (!d->logits || !d->block_tables || !d->context_lens || !d->indices)
+        return "null tensor pointer (logits, block_tables, context_lens and indices are required)";
+    if (((reinterpret_cast<uintptr_t>(d->logits) | reinterpret_cast<uintptr_t>(d->indices) | reinterpret_cast<uintptr_t>(d->block_tables) |
+          reinterpret_cast<uintptr_t>(d->context_lens) | reinterpret_cast<uintptr_t>(d->cu_seqlens_q)) & 3) != 0)
+        return "logits, indices, block_tables, context_lens and cu_seqlens_q must be 4-byte aligned";
+    return nullptr;
+}
+
+int32_t aule_mla_indexer_topk_ex(const aule_mla_indexer_topk_desc* d) {
+    RoctxRange range("aule.mla_indexer_topk");
+    const char* what = "MLA indexer top-k";
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_indexer_topk_desc_error(d, text)) {
+        set_error("%s failed: %s", what, why);
+        return -3;
+    }
+    if (indexer_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaIndexerTopkArgs a;
+    a.logits = d->logits; a.indices = d->indices;
+    a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
+    a.T = (int)d->total_tokens; a.B = (int)d->batch; a.topk = (int)d->topk;
+    a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
+    a.max_seqlen_q = indexer_max_sq(d);
+    a.logits_stride = d->logits_stride;
+    a.positions = d->output == AULE_INDEXER_POSITIONS;
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    return launched(what, aule_hip::launch_mla_indexer_topk(a, (hipStream_t)d->stream));
+}
+
 // The variable-length kinds: aule_varlen_bwd_desc states the problem in aule_varlen_desc's fields up to cu_seqlens_k (the layout asserts
 // at the top of this file), so both are checked and read through that prefix; what follows it is each kind's own.  One checker per
 // kind; `launch`: the pointer and workspace rules of a call that has something to do as well (the size query reads no pointer).  Host
@@ -2560,6 +2719,19 @@ int32_t aule_hip_debug_mla_sparse_launch_nsplit(const aule_mla_sparse_desc* d, i
         return -3;
     }
     return mla_sparse_launch(d, nsplit);
+}
+
+/* Debug hook: the launch plan of aule_mla_indexer_logits_ex(d) as integers (include/aule.h lists them): the plan the launch reads.
+ * Pure host logic like the forward hook. */
+int32_t aule_hip_debug_mla_indexer_plan(const aule_mla_indexer_logits_desc* d, int32_t* out, int32_t cap) {
+    Reason text;
+    if (mla_indexer_logits_desc_error(d, false, text)) return -3;
+    if (indexer_nothing_to_do(d)) return 0;
+    const aule_hip::MlaIndexerPlan plan = mla_indexer_plan_of(d);
+    const int32_t v[5] = {plan.group_tokens, plan.token_groups, plan.chunk_keys, plan.key_chunks, (int32_t)plan.grid};
+    if (out == nullptr || cap < 5) return -5;
+    for (int i = 0; i < 5; ++i) out[i] = v[i];
+    return 5;
 }
 
 /* Debug hook: the launch plan of aule_attention_mla_prefill_backward_ex(d) as integers (include/aule.h lists them): the plan the launch

@@ -409,6 +409,54 @@ constexpr int kMlaSparseMaxTopk = 65536;
 MlaPlan mla_sparse_plan(int T, int Hq, int topk, int device, int force_nsplit = 0);
 int launch_mla_sparse(const MlaSparseArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream);   // -1: unsupported arguments
 
+// The indexer of the sparse MLA (fa_mla_indexer_gfx950.hip): the index logits I[t, s] = sum_h w[t, h] * relu(q[t, h, :] . k[s, :]) of
+//   ragged query tokens over a paged cache of index keys (one 128-wide row per position), and the top-k key list of every token.  The
+//   tables, lengths, offsets and their device-side clamps are MlaArgs'; the contracts are aule_mla_indexer_logits_desc and
+//   aule_mla_indexer_topk_desc in include/aule.h.
+struct MlaIndexerArgs {
+    const void* q;                      // [T, H, 128] 16-bit, q_token_stride elements per token
+    const float* weights;               // [T, H]
+    const void* k_cache;                // [num_blocks, block_size, 128]: q's dtype, or e4m3fn codes
+    const float* k_scale = nullptr;     // kCacheFp8E4M3 only: [num_blocks, block_size] fp32, device
+    const int* block_tables;
+    const int* context_lens;
+    const int* cu_seqlens_q = nullptr;  // null: sequence b owns row b
+    float* logits;                      // [T, logits_stride >= max_blocks * block_size]
+    int T, B, H;
+    int num_blocks, block_size, max_blocks;
+    int max_seqlen_q;
+    long long q_token_stride, logits_stride;
+    int dtype;
+    int device = -1;                    // as FwdArgs::device
+    int cache_kind = kCache16;
+};
+constexpr int kMlaIndexerMaxHeads = 64;
+constexpr int kMlaIndexerMaxTopk = 65536;
+// The launch plan of the logits (mla_indexer_plan, beside the kernel: the one statement of the grid for the launch and the debug
+// hook): work item (sequence, group of group_tokens tokens, chunk of chunk_keys keys), token_groups = ceil(max_seqlen_q /
+// group_tokens), key_chunks * chunk_keys >= W = max_blocks * block_size, grid = B * token_groups * key_chunks.  From the shape alone;
+// all zero: nothing to launch.
+struct MlaIndexerPlan {
+    int group_tokens = 0, token_groups = 0;
+    int chunk_keys = 0, key_chunks = 0;
+    long long grid = 0;
+};
+MlaIndexerPlan mla_indexer_plan(int B, int max_seqlen_q, long long W, int device);
+int launch_mla_indexer_logits(const MlaIndexerArgs& a, const MlaIndexerPlan& plan, hipStream_t stream);   // -1: unsupported arguments
+struct MlaIndexerTopkArgs {
+    const float* logits;                // [T, logits_stride]
+    int* indices;                       // [T, topk]
+    const int* block_tables;
+    const int* context_lens;
+    const int* cu_seqlens_q = nullptr;
+    int T, B, topk;
+    int block_size, max_blocks;
+    int max_seqlen_q;
+    long long logits_stride;
+    bool positions = false;             // raw positions instead of slots through the table
+};
+int launch_mla_indexer_topk(const MlaIndexerTopkArgs& a, hipStream_t stream);   // one workgroup per (sequence, token); -1: unsupported
+
 // The cut of a sequence's length every ragged entry applies (paged prefill, variable-length, MLA prefill): no sequence has more
 // tokens than the batch.
 inline int seqlen_cut(int max_seqlen, int total) { return max_seqlen < total ? max_seqlen : total; }

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "fa_d256_common.h"
+#include "kv_quant.h"
 
 namespace aule_hip {
 namespace {
@@ -27,19 +28,7 @@ struct PrefillCfg {
     static constexpr int N = kPK * CPR / 256;              // chunks per thread and tile
 };
 
-// eight e4m3fn codes -> eight 16-bit elements, exact
-template <class T>
-__device__ __forceinline__ u32x4_t cvt8(u32x2_t x) {
-    u32x4_t e;
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-        const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[w], false);
-        const f32x2_t b = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[w], true);
-        e[2 * w] = T::pack2(a[0], a[1]);
-        e[2 * w + 1] = T::pack2(b[0], b[1]);
-    }
-    return e;
-}
+// (cvt8, eight e4m3fn codes -> eight 16-bit elements: kv_quant.h, beside the quantiser)
 
 // One K and one V tile of 64 keys on their way from the block pool to LDS: chunk i of thread t is 8-element chunk t + 256 i
 // (row (t + 256 i) / CPR of the tile), 16 bytes of a 16-bit cache or 8 codes of an FP8 one.

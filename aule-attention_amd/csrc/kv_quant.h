@@ -1,6 +1,7 @@
 // kv_quant.h -- what the cache append kernels share (kv_append_gfx950.hip, mla_kv_append_gfx950.hip): a 16-byte chunk of eight
 // 16-bit elements and its way into a cache, as a copy of the bits or as eight e4m3fn codes.  The quantisation rules are stated in
-// kv_append_gfx950.hip's header comment.  Device code only.
+// kv_append_gfx950.hip's header comment.  The readers of an FP8 cache (fa_paged_tile.h's tiles, fa_mla_indexer_gfx950.hip) take the
+// exact way back, cvt8, from here.  Device code only.
 #pragma once
 #include "fa_device.h"
 
@@ -34,6 +35,21 @@ __device__ __forceinline__ u32x2_t quant8(const Chunk<E>& x, float scale) {
         out[w] = (unsigned)word;
     }
     return out;
+}
+
+// the way back, for every reader of an FP8 cache: eight e4m3fn codes -> eight 16-bit elements of T (Bf16Traits / F16Traits), exact
+// (every e4m3fn value is a bf16 and an fp16 value)
+template <class T>
+__device__ __forceinline__ u32x4_t cvt8(u32x2_t x) {
+    u32x4_t e;
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+        const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[w], false);
+        const f32x2_t b = __builtin_amdgcn_cvt_pk_f32_fp8((int)x[w], true);
+        e[2 * w] = T::pack2(a[0], a[1]);
+        e[2 * w + 1] = T::pack2(b[0], b[1]);
+    }
+    return e;
 }
 
 // chunk `x` to element offset `elem` of a cache of E (a copy) or of codes (x / scale)

@@ -526,8 +526,9 @@ uint64_t aule_attention_mla_paged_fp8_workspace_size(const aule_mla_paged_fp8_de
 /* (total_tokens + 64) * heads_q or the grid past 2^31-1; a null or misaligned required pointer; a caller workspace smaller than the   */
 /* plan's.  The size query and the plan hook give the same verdict on every field and read no pointer.  total_tokens = 0 returns 0     */
 /* without a launch and without aule_init().                                                                                           */
-/* Not built: the indexer (the top-k selection); a causal rule in the kernel; packing several tokens' heads into one row block when    */
-/* heads_q < 64; logical positions resolved through a block table in the kernel; a backward; sink logits or tree masks with a list.    */
+/* The lists come from the indexer, aule_mla_indexer_logits_ex + aule_mla_indexer_topk_ex below.                                       */
+/* Not built: a causal rule in the kernel; packing several tokens' heads into one row block when heads_q < 64; logical positions       */
+/* resolved through a block table in the kernel; a backward; sink logits or tree masks with a list.                                    */
 typedef struct aule_mla_sparse_desc {
     uint32_t struct_size;      /* = sizeof(aule_mla_sparse_desc) = 120 */
     int32_t dtype;             /* offset 4; type of q / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
@@ -554,6 +555,110 @@ typedef struct aule_mla_sparse_desc {
 int32_t aule_attention_mla_sparse_ex(const aule_mla_sparse_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
 uint64_t aule_attention_mla_sparse_workspace_size(const aule_mla_sparse_desc* desc);
+
+/* MLA INDEXER (additive): the producer of aule_mla_sparse_desc's key lists (DeepSeek-V3.2 "DSA"): index logits over a paged cache of  */
+/* index keys, then the top-k key list of every query token.  Two entries, two launches; these two comments are the contract.           */
+/* LOGITS.  logits[t][s] = sum_h weights[t][h] * relu(q[t][h][:] . k[s][:]), fp32.                                                       */
+/* q is [total_tokens, heads, 128], fp16 or bf16, 1 <= heads <= 64, q_token_stride elements from one token to the next (a multiple of  */
+/* 8, >= heads * 128, the heads of a token contiguous: a slice of a wider projection is read in place); weights is [total_tokens,      */
+/* heads] fp32, contiguous -- the caller folds heads^-1/2, the softmax scale and any q scale into it.  k_cache is [num_blocks,         */
+/* block_size, 128], contiguous, ONE key row per position shared by all heads: of q's dtype (cache_dtype AULE_KV_CACHE_SAME, k_scale   */
+/* NULL) or OCP e4m3fn codes (AULE_KV_CACHE_FP8_E4M3) with a PER-ROW scale k_scale [num_blocks, block_size] fp32 on the device, key =  */
+/* k_scale[row] * float(code row).  The codes are converted exactly to q's type and the row scale multiplies the finished logit,       */
+/* never an element (relu commutes with a positive scale): with every scale 1 the call equals the 16-bit call on the converted codes   */
+/* bit for bit.  q and k_cache are 16-byte aligned, weights, k_scale and logits 4-byte.                                                 */
+/* block_tables [batch, max_blocks], context_lens [batch], cu_seqlens_q [batch + 1] (NULL: plain decode, sequence b owns row b,        */
+/* max_seqlen_q read as 1, total_tokens >= batch) and max_seqlen_q follow aule_mla_paged_desc exactly, every clamp made on the device: */
+/* L_b = clamp(context_lens[b], 0, W) with W = max_blocks * block_size, s_b = clamp(cu[b], 0, total_tokens), e_b = clamp(cu[b + 1],    */
+/* s_b, total_tokens), n_b = min(e_b - s_b, max_seqlen_q).  Token i of sequence b is row s_b + i, sits at p = L_b - n_b + i and sees   */
+/* key j iff 0 <= j <= p.  A table entry is clamped to [0, num_blocks) before it is used; an entry at logical block >= ceil(L_b /      */
+/* block_size) is never dereferenced.  No host synchronisation, no allocation: the call captures into a hipGraph and a replay sees the */
+/* CURRENT tables, lengths, offsets and weights.                                                                                        */
+/* OUTPUT.  logits is [total_tokens, W] fp32 with logits_stride >= W elements from row to row.  For a row that belongs to a sequence   */
+/* EVERY one of the W columns is written: the logit where the key is visible, -inf elsewhere.  A cache row (and a k_scale entry) that  */
+/* no token sees is never read.  Rows of no sequence are NEVER written.  Cost: total_tokens * W * 4 bytes (1 GB at 2048 x 128 K):     */
+/* callers chunk total_tokens or size the table.                                                                                        */
+/* LAUNCH.  Work item (sequence, group of 4 tokens, chunk of keys); every column of every owned row belongs to exactly one item: no    */
+/* workspace, no combine, no atomics, two runs are bit-identical.  The grid is fixed on the host from (batch, max_seqlen_q, W, compute */
+/* units): token groups = ceil(max_seqlen_q / 4), key chunks = clamp(ceil(4 * CUs / (batch * token groups)), 1, ceil(W / 128)) evened  */
+/* out to chunks of a multiple of 128 keys; aule_hip_debug_mla_indexer_plan() gives the numbers.                                        */
+/* REFUSED with -3 and a reason naming the field (aule_get_error), before the device is needed: a wrong struct_size; dtype outside     */
+/* {fp16, bf16}; cache_dtype outside {0, 1}; heads outside 1..64; head_dim != 128; num_blocks = 0; block_size / max_blocks zero or W   */
+/* >= 2^30; max_seqlen_q = 0; q_token_stride too small or not a multiple of 8; logits_stride < W; batch / total_tokens >= 2^30; plain  */
+/* decode with total_tokens < batch; a grid past 2^31 - 1; and, by the launch alone, a null or misaligned pointer, an FP8 cache        */
+/* without k_scale, k_scale with a 16-bit cache.  The plan hook gives the same verdict on every field and reads no pointer.            */
+/* total_tokens = 0 or batch = 0 returns 0 without a launch and without aule_init().                                                   */
+/* Not built: FP8 queries and FP8 MFMAs; a fused streaming top-k that never writes [total_tokens, W]; an append kernel for the index   */
+/* keys; heads > 64; a backward.                                                                                                        */
+typedef struct aule_mla_indexer_logits_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_indexer_logits_desc) = 136 */
+    int32_t dtype;             /* offset 4; type of q: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    int32_t cache_dtype;       /* offset 8; AULE_KV_CACHE_SAME (q's dtype) or AULE_KV_CACHE_FP8_E4M3 */
+    uint32_t heads;            /* offset 12; index heads, 1 .. 64 */
+    uint32_t head_dim;         /* offset 16; 128 */
+    uint32_t batch;            /* offset 20; sequences; 0: returns 0 without a launch */
+    uint32_t num_blocks;       /* offset 24; blocks of k_cache, >= 1 */
+    uint32_t block_size;       /* offset 28; any value > 0 */
+    uint32_t max_blocks;       /* offset 32; columns of block_tables; W = max_blocks * block_size < 2^30 */
+    uint32_t total_tokens;     /* offset 36; rows of q / weights / logits; 0: returns 0 without a launch */
+    uint32_t max_seqlen_q;     /* offset 40; >= 1: sizes the grid, and caps every n_b */
+    int32_t device;            /* offset 44; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 48; elements, >= heads * 128, a multiple of 8 */
+    int64_t logits_stride;     /* offset 56; elements, >= W */
+    void* stream;              /* offset 64; hipStream_t */
+    const void* q;             /* offset 72; [total_tokens, heads, 128], 16-bit */
+    const float* weights;      /* offset 80; [total_tokens, heads] fp32 */
+    const void* k_cache;       /* offset 88; [num_blocks, block_size, 128], q's dtype or e4m3fn codes */
+    const float* k_scale;      /* offset 96; [num_blocks, block_size] fp32, device (AULE_KV_CACHE_FP8_E4M3), else NULL */
+    const int32_t* block_tables;   /* offset 104; [batch, max_blocks] */
+    const int32_t* context_lens;   /* offset 112; [batch]: keys per sequence, the new ones included */
+    const int32_t* cu_seqlens_q;   /* offset 120; [batch + 1], device; NULL: plain decode */
+    float* logits;             /* offset 128; [total_tokens, logits_stride] fp32 */
+} aule_mla_indexer_logits_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_mla_indexer_logits_ex(const aule_mla_indexer_logits_desc* desc);
+
+/* TOP-K.  indices[t][:] = the key list of token t from logits [total_tokens, W] fp32 (logits_stride >= W; ANY such tensor, not       */
+/* necessarily aule_mla_indexer_logits_ex's), 1 <= topk <= 65536, with the tables, lengths, offsets and clamps of the logits entry.    */
+/* RULE, fully canonical.  Visibility comes from the position arithmetic (key j iff 0 <= j <= p), NOT from -inf marks: a visible -inf  */
+/* still counts as visible, and columns past p are never read.  Among token t's visible keys, order by logit descending, then by       */
+/* position ascending; logits compare by numeric value (-0 == +0) and a NaN ranks as -inf.  The first min(topk, p + 1) keys are        */
+/* emitted in ASCENDING POSITION order; the tail is padded with -1.  A token with p < 0 gets all -1.  Rows of no sequence are NEVER    */
+/* written.  The result is deterministic: no atomics on global memory, two runs are bit-identical.                                     */
+/* output AULE_INDEXER_SLOTS: entry = block_tables[b][pos / block_size] * block_size + pos % block_size (the table entry as it stands: */
+/* nothing is dereferenced through it), the slot_mapping convention aule_mla_sparse_desc consumes when the latent cache shares the     */
+/* table and the block size.  AULE_INDEXER_POSITIONS: the raw positions, for a latent cache with another block size.                   */
+/* LAUNCH.  One workgroup per (sequence, token below max_seqlen_q): batch * max_seqlen_q workgroups.  p + 1 <= topk: every visible key, */
+/* no logit is read.  Else a radix select over an order-preserving 32-bit key (4 passes of 8 bits, histograms in LDS) finds the        */
+/* threshold, ties at the threshold go to the lowest positions, and one ordered compaction pass writes the list.  No host              */
+/* synchronisation, no allocation, capturable; a replay sees the current logits, tables, lengths and offsets.                          */
+/* REFUSED with -3 and a reason naming the field, before the device is needed: a wrong struct_size; output outside {0, 1}; topk        */
+/* outside 1..65536; reserved != 0; block_size / max_blocks zero or W >= 2^30; max_seqlen_q = 0; logits_stride < W; batch /            */
+/* total_tokens >= 2^30; plain decode with total_tokens < batch; batch * max_seqlen_q past 2^31 - 1; a null or misaligned pointer.     */
+/* total_tokens = 0 or batch = 0 returns 0 without a launch and without aule_init().                                                   */
+#define AULE_INDEXER_SLOTS 0      /* cache slots through the block table */
+#define AULE_INDEXER_POSITIONS 1  /* logical positions */
+typedef struct aule_mla_indexer_topk_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_indexer_topk_desc) = 96 */
+    int32_t output;            /* offset 4; AULE_INDEXER_SLOTS or AULE_INDEXER_POSITIONS */
+    int32_t topk;              /* offset 8; entries per token, 1 .. 65536 */
+    uint32_t batch;            /* offset 12; sequences; 0: returns 0 without a launch */
+    uint32_t block_size;       /* offset 16; any value > 0 */
+    uint32_t max_blocks;       /* offset 20; columns of block_tables; W = max_blocks * block_size < 2^30 */
+    uint32_t total_tokens;     /* offset 24; rows of logits / indices; 0: returns 0 without a launch */
+    uint32_t max_seqlen_q;     /* offset 28; >= 1: sizes the grid, and caps every n_b */
+    int32_t device;            /* offset 32; HIP device ordinal, -1 = current */
+    uint32_t reserved;         /* offset 36; 0 */
+    int64_t logits_stride;     /* offset 40; elements, >= W */
+    void* stream;              /* offset 48; hipStream_t */
+    const float* logits;       /* offset 56; [total_tokens, logits_stride] fp32 */
+    const int32_t* block_tables;   /* offset 64; [batch, max_blocks] */
+    const int32_t* context_lens;   /* offset 72; [batch] */
+    const int32_t* cu_seqlens_q;   /* offset 80; [batch + 1], device; NULL: plain decode */
+    int32_t* indices;          /* offset 88; [total_tokens, topk] int32, contiguous */
+} aule_mla_indexer_topk_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_mla_indexer_topk_ex(const aule_mla_indexer_topk_desc* desc);
 
 /* VARIABLE-LENGTH packed batches (additive): sequences of different lengths packed along one token axis, forward and backward --   */
 /* SFT with sequence packing, encoder batches without padding, prefill without a paged cache (flash_attn_varlen_func's case).        */
@@ -1219,6 +1324,13 @@ int32_t aule_hip_debug_mla_sparse_plan(const aule_mla_sparse_desc* desc, int32_t
 /* bench that measures the plan's "one split per two tiles" cap (tools/bench_mla_sparse.py); results equal the entry's within the   */
 /* forward bounds, bit for bit only at the plan's own nsplit.                                                                       */
 int32_t aule_hip_debug_mla_sparse_launch_nsplit(const aule_mla_sparse_desc* desc, int32_t nsplit);
+/* Debug: the launch plan of aule_mla_indexer_logits_ex(desc) as integers -- out = {tokens per group (4), token groups              */
+/* (ceil(max_seqlen_q / 4); plain decode: 1), keys per chunk (a multiple of 128), key chunks, workgroups (batch * token groups *    */
+/* key chunks)}.  Chunk c owns columns [c * keys per chunk, ...) cut at W, so every (token group, column) has one owner.  Returns   */
+/* the ints written (negative: the capacity needed), 0 for a descriptor with nothing to do; -3 bad.  Host logic only, no            */
+/* aule_init(), no pointer of the descriptor is read (the pointer rules of the launch are not applied); without a device it plans   */
+/* for 256 compute units.                                                                                                           */
+int32_t aule_hip_debug_mla_indexer_plan(const aule_mla_indexer_logits_desc* desc, int32_t* out, int32_t cap);
 /* Debug: the launch plan of aule_attention_mla_prefill_backward_ex(desc) as integers -- out = {heads per chunk, n_chunks (the last    */
 /* chunk may be short), the bound of n_chunks (16), delta workgroups, dQ workgroups, dK/dV workgroups (key blocks * batch * n_chunks),  */
 /* reduce workgroups, 1 if the reduce runs (else the dK/dV kernel writes dk_pe itself), workspace bytes low 32 bits, high 32 bits}.     */
