@@ -1111,6 +1111,37 @@ def _ragged_offsets(B, cu_seqlens_q, max_seqlen_q):
         raise ValueError(f"max_seqlen_q must be a positive int or None, got {max_seqlen_q!r}")
 
 
+def _single_token_offsets(max_seqlen_q):
+    """The rule of max_seqlen_q without cu_seqlens_q: plain decode, one token per sequence."""
+    if max_seqlen_q not in (None, 1):
+        raise ValueError(f"max_seqlen_q must be None or 1 without cu_seqlens_q (one token per sequence), got {max_seqlen_q!r}")
+
+
+def _longest_sequence(cu, B):
+    """max_seqlen_q read from the offsets on the device: the one documented synchronisation of the entries that take None for it."""
+    return max(int((cu[1:] - cu[:-1]).max().item()), 1) if B > 0 else 1
+
+
+def _ragged_result(q, width, return_lse):
+    """out [T, Hq, width] of q's dtype and lse [T, Hq] fp32 (or None) from torch.empty, and what the call returns."""
+    T, Hq, _ = q.shape
+    out = torch.empty((T, Hq, width), device=q.device, dtype=q.dtype)
+    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
+    return out, lse, (out, lse) if return_lse else out
+
+
+def _latent_shapes(q, kv_cache):
+    """The latent cache as the MLA readers take it: [num_blocks, block_size, 1, 576] is read as [num_blocks, block_size, 576]; q and the
+    cache are 3-d and 576 wide."""
+    if kv_cache.dim() == 4 and kv_cache.shape[2] == 1:
+        kv_cache = kv_cache[:, :, 0]
+    if q.dim() != 3 or kv_cache.dim() != 3:
+        raise ValueError("expected q [T,Hq,576] and kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576])")
+    if q.shape[-1] != 576 or kv_cache.shape[-1] != 576:
+        raise ValueError(f"the latent width must be 576 (512 + 64): query={q.shape[-1]}, cache={kv_cache.shape[-1]}")
+    return kv_cache
+
+
 def _packed_tokens(q):
     """q [T, Hq, D] as the ragged kernels read it -- heads contiguous, the token stride free -- and that stride in elements."""
     T, Hq, D = q.shape
@@ -1143,11 +1174,8 @@ def _ragged_problem(op, d, q, q_stride, fp8, k_cache, v_cache, block_tables, con
     bt, cl, cu = _int32_on(q.device, block_tables, context_lens, cu_seqlens_q)
     B, (T, Hq, D) = bt.shape[0], q.shape
     if max_seqlen_q is None:
-        # the one documented synchronisation
-        max_seqlen_q = max(int((cu[1:] - cu[:-1]).max().item()), 1) if B > 0 else 1
-    out = torch.empty((T, Hq, D), device=q.device, dtype=q.dtype)
-    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
-    result = (out, lse) if return_lse else out
+        max_seqlen_q = _longest_sequence(cu, B)
+    out, lse, result = _ragged_result(q, D, return_lse)
     if T * B * Hq == 0:
         return result, None
     _paged_problem(d, q, k_cache, v_cache, out, bt, cl, scale, fp8)
@@ -1289,12 +1317,7 @@ def _latent_cache_kind(what, dtype, kv_cache, fp8, kv_scale, sixteen):
 
 def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale):
     """Both cache kinds of the paged MLA: one validation, one descriptor (the FP8 kind's is the 16-bit kind's plus kv_scale)."""
-    if kv_cache.dim() == 4 and kv_cache.shape[2] == 1:
-        kv_cache = kv_cache[:, :, 0]
-    if q.dim() != 3 or kv_cache.dim() != 3:
-        raise ValueError("expected q [T,Hq,576] and kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576])")
-    if q.shape[-1] != 576 or kv_cache.shape[-1] != 576:
-        raise ValueError(f"the latent width must be 576 (512 + 64): query={q.shape[-1]}, cache={kv_cache.shape[-1]}")
+    kv_cache = _latent_shapes(q, kv_cache)
     if fp8:
         _latent_cache_kind("q", q.dtype, kv_cache, True, kv_scale, "a 16-bit cache is flash_attention_mla_paged's")
     elif q.dtype not in (torch.float16, torch.bfloat16) or kv_cache.dtype != q.dtype:
@@ -1304,8 +1327,8 @@ def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_s
     B = _paged_tables(block_tables, context_lens, None if cu_seqlens_q is not None else q.shape[0])
     if cu_seqlens_q is not None:
         _ragged_offsets(B, cu_seqlens_q, max_seqlen_q)
-    elif max_seqlen_q not in (None, 1):
-        raise ValueError(f"max_seqlen_q must be None or 1 without cu_seqlens_q (one token per sequence), got {max_seqlen_q!r}")
+    else:
+        _single_token_offsets(max_seqlen_q)
     q, q_stride = _packed_tokens(q)
     _needs_device("MLA", q)
     lib = _capi.get_lib()
@@ -1317,11 +1340,8 @@ def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_s
     if cu is None:
         max_seqlen_q = 1
     elif max_seqlen_q is None:
-        # the one documented synchronisation
-        max_seqlen_q = max(int((cu[1:] - cu[:-1]).max().item()), 1) if B > 0 else 1
-    out = torch.empty((T, Hq, 512), device=q.device, dtype=q.dtype)
-    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
-    result = (out, lse) if return_lse else out
+        max_seqlen_q = _longest_sequence(cu, B)
+    out, lse, result = _ragged_result(q, 512, return_lse)
     if T * B * Hq == 0:
         return result
     d = _capi.MlaPagedFp8Desc() if fp8 else _capi.MlaPagedDesc()
@@ -1357,14 +1377,9 @@ def mla_sparse(q, kv_cache, indices, scale=None, return_lse=False, kv_scale=None
     contract (aule.flash_attention_mla_sparse documents the arguments).  One launch (plus the combine when the list is split), no
     device->host copy, no synchronisation.  All argument errors are ValueErrors raised before the device is touched; CPU tensors
     that pass them are an AuleError."""
-    if kv_cache.dim() == 4 and kv_cache.shape[2] == 1:
-        kv_cache = kv_cache[:, :, 0]
+    kv_cache = _latent_shapes(q, kv_cache)
     if torch.is_tensor(indices) and indices.dim() == 3 and indices.shape[1] == 1:
         indices = indices[:, 0]
-    if q.dim() != 3 or kv_cache.dim() != 3:
-        raise ValueError("expected q [T,Hq,576] and kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576])")
-    if q.shape[-1] != 576 or kv_cache.shape[-1] != 576:
-        raise ValueError(f"the latent width must be 576 (512 + 64): query={q.shape[-1]}, cache={kv_cache.shape[-1]}")
     T, Hq, _ = q.shape
     fp8 = kv_cache.dtype != q.dtype
     _latent_cache_kind("q", q.dtype, kv_cache, fp8, kv_scale, "a 16-bit cache has q's dtype")
@@ -1393,9 +1408,7 @@ def mla_sparse(q, kv_cache, indices, scale=None, return_lse=False, kv_scale=None
     if not q.is_cuda:
         raise _capi.AuleError("aule (HIP build): sparse MLA attention needs ROCm device tensors; there is no CPU fallback")
     _same_device("sparse MLA", q, kv_cache, indices)
-    out = torch.empty((T, Hq, 512), device=q.device, dtype=q.dtype)
-    lse = torch.empty((T, Hq), device=q.device, dtype=torch.float32) if return_lse else None
-    result = (out, lse) if return_lse else out
+    out, lse, result = _ragged_result(q, 512, return_lse)
     if T == 0:
         return result
     lib = _capi.get_lib()
@@ -1438,9 +1451,8 @@ def _indexer_tables(T, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, b
     if cu_seqlens_q is not None:
         _ragged_offsets(B, cu_seqlens_q, max_seqlen_q)
         max_seqlen_q = max(min(T if max_seqlen_q is None else max_seqlen_q, T), 1)
-    elif max_seqlen_q not in (None, 1):
-        raise ValueError(f"max_seqlen_q must be None or 1 without cu_seqlens_q (one token per sequence), got {max_seqlen_q!r}")
     else:
+        _single_token_offsets(max_seqlen_q)
         max_seqlen_q = 1
     if isinstance(block_size, bool) or not isinstance(block_size, int) or block_size < 1:
         raise ValueError(f"block_size must be a positive int, got {block_size!r}")
@@ -1512,6 +1524,14 @@ def mla_indexer_logits(q, weights, k_cache, block_tables, context_lens, cu_seqle
     return logits
 
 
+def _indexer_topk_args(topk, output):
+    """The rules of topk and output, which mla_indexer checks before its first launch."""
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= MLA_INDEXER_MAX_TOPK:
+        raise ValueError(f"topk must be an int in 1 .. {MLA_INDEXER_MAX_TOPK}, got {topk!r}")
+    if output not in _INDEXER_OUTPUTS:
+        raise ValueError(f"output must be 'slots' or 'positions', got {output!r}")
+
+
 def mla_indexer_topk(logits, topk, block_tables, context_lens, block_size, cu_seqlens_q=None, max_seqlen_q=None, output="slots"):
     """The per-token top-k key lists of the sparse MLA's indexer from fp32 logits [T, max_blocks * block_size];
     csrc/fa_mla_indexer_gfx950.hip behind aule_mla_indexer_topk_ex, whose descriptor comment in include/aule.h is the contract
@@ -1519,10 +1539,7 @@ def mla_indexer_topk(logits, topk, block_tables, context_lens, block_size, cu_se
     ValueErrors raised before the device is touched; CPU tensors that pass them are an AuleError."""
     if not torch.is_tensor(logits) or logits.dim() != 2 or logits.dtype != torch.float32:
         raise ValueError(f"logits must be an fp32 [T, max_blocks * block_size] tensor, got {logits.dtype if torch.is_tensor(logits) else type(logits).__name__}")
-    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= MLA_INDEXER_MAX_TOPK:
-        raise ValueError(f"topk must be an int in 1 .. {MLA_INDEXER_MAX_TOPK}, got {topk!r}")
-    if output not in _INDEXER_OUTPUTS:
-        raise ValueError(f"output must be 'slots' or 'positions', got {output!r}")
+    _indexer_topk_args(topk, output)
     T = logits.shape[0]
     B, max_sq = _indexer_tables(T, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, block_size)
     W = block_tables.shape[1] * block_size
@@ -1558,10 +1575,7 @@ def mla_indexer(q, weights, k_cache, block_tables, context_lens, topk, cu_seqlen
                 return_logits=False):
     """mla_indexer_logits, then mla_indexer_topk on its result: the two launches in a row.  topk and output are checked before the
     first launch.  Returns indices [T, topk] int32, or (indices, logits)."""
-    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= MLA_INDEXER_MAX_TOPK:
-        raise ValueError(f"topk must be an int in 1 .. {MLA_INDEXER_MAX_TOPK}, got {topk!r}")
-    if output not in _INDEXER_OUTPUTS:
-        raise ValueError(f"output must be 'slots' or 'positions', got {output!r}")
+    _indexer_topk_args(topk, output)
     logits = mla_indexer_logits(q, weights, k_cache, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q,
                                 k_scale=k_scale)
     block_size = k_cache.shape[1]

@@ -13,12 +13,14 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstddef>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 
 #include <dlfcn.h>
@@ -1362,7 +1364,7 @@ static void fill_paged_prefill_args(const aule_paged_prefill_desc* d, aule_hip::
     a.q = d->q; a.k_cache = d->k_cache; a.v_cache = d->v_cache; a.out = d->out; a.lse = d->lse;
     a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
     a.T = (int)d->total_tokens; a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
-    a.max_seqlen_q = (int)(d->max_seqlen_q < d->total_tokens ? d->max_seqlen_q : d->total_tokens);
+    a.max_seqlen_q = aule_hip::seqlen_cut(d->max_seqlen_q, d->total_tokens);
     a.q_token_stride = d->q_token_stride;
     a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
     a.scale = resolve_scale(d->scale, d->head_dim);
@@ -1527,6 +1529,29 @@ int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* d) {
 // checked and read through that prefix; `fp8` says which one `d` is.  One checker for all their readers, built from the paged kinds'
 // pieces where the fields are alike; `launch`: the pointer rules of a call that has something to do as well (the size queries and the
 // plan hook read no pointer).  Host logic only, asked before the device is needed.
+extern "C++" {
+// (the kinds whose cu_seqlens_q may be null -- plain decode, sequence b owns row b -- read max_seqlen_q as 1 then; else the cut)
+template <class Desc>
+static int max_sq_or_one(const Desc* d) { return d->cu_seqlens_q == nullptr ? 1 : aule_hip::seqlen_cut(d->max_seqlen_q, d->total_tokens); }
+
+// (the tail of both MLA launch entries: the device, the workspace of a split plan -- the caller's buffer when it is large enough, else a
+// stream-ordered allocation -- and the launch; `launch(ws, stream)`: the kind's launcher with its arguments and `plan`)
+template <class Desc, class Launch>
+static int32_t mla_launch_tail(const Desc* d, const aule_hip::MlaPlan& plan, const char* what, Launch&& launch) {
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)d->stream;
+    if (plan.nsplit == 1) return launched(what, launch(nullptr, stream));
+    aule_hip::ScopedWorkspace ws(plan.ws_bytes, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
+    if (ws.err != hipSuccess) {
+        set_error("%s failed: workspace allocation (%llu bytes): %s", what, (unsigned long long)plan.ws_bytes, hipGetErrorString(ws.err));
+        return -4;
+    }
+    return launched(what, launch(ws.ptr, stream));
+}
+}   // extern "C++"
+
 static const aule_mla_paged_desc* mla_prefix(const aule_mla_paged_fp8_desc* d) { return reinterpret_cast<const aule_mla_paged_desc*>(d); }
 static const char* varlen_stride_error(const char* name, int64_t stride, uint64_t token, const char* heads, Reason& why);   // (the token stride rule, below)
 static const char* mla_paged_desc_error(const aule_mla_paged_desc* d, bool fp8, bool launch, Reason& why) {
@@ -1556,7 +1581,7 @@ static void fill_mla_paged_args(const aule_mla_paged_desc* d, bool fp8, aule_hip
     a.q = d->q; a.kv_cache = d->kv_cache; a.out = d->out; a.lse = d->lse;
     a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
     a.T = (int)d->total_tokens; a.B = (int)d->batch; a.Hq = (int)d->heads_q;
-    a.max_seqlen_q = d->cu_seqlens_q == nullptr ? 1 : (int)(d->max_seqlen_q < d->total_tokens ? d->max_seqlen_q : d->total_tokens);
+    a.max_seqlen_q = max_sq_or_one(d);
     a.q_token_stride = d->q_token_stride;
     a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
     a.scale = resolve_scale(d->scale, d->qk_dim);
@@ -1585,17 +1610,7 @@ static int32_t mla_paged_launch(const aule_mla_paged_desc* d, bool fp8, const ch
         set_error("%s failed: the grid (row blocks * nsplit * batch) exceeds 2^31 - 1 workgroups", what);
         return -3;
     }
-    DeviceGuard g(d->device);
-    int rc = ensure_configured();
-    if (rc) return rc;
-    hipStream_t stream = (hipStream_t)d->stream;
-    if (plan.nsplit == 1) return launched(what, aule_hip::launch_mla_paged(a, plan, nullptr, stream));
-    aule_hip::ScopedWorkspace ws(plan.ws_bytes, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
-    if (ws.err != hipSuccess) {
-        set_error("%s failed: workspace allocation (%llu bytes): %s", what, (unsigned long long)plan.ws_bytes, hipGetErrorString(ws.err));
-        return -4;
-    }
-    return launched(what, aule_hip::launch_mla_paged(a, plan, ws.ptr, stream));
+    return mla_launch_tail(d, plan, what, [&](void* ws, hipStream_t stream) { return aule_hip::launch_mla_paged(a, plan, ws, stream); });
 }
 
 int32_t aule_attention_mla_paged_ex(const aule_mla_paged_desc* d) {
@@ -1681,17 +1696,7 @@ static int32_t mla_sparse_launch(const aule_mla_sparse_desc* d, int force_nsplit
         a.kv_scale = d->kv_scale;
     }
     const aule_hip::MlaPlan plan = mla_sparse_plan_of(d, force_nsplit);
-    DeviceGuard g(d->device);
-    int rc = ensure_configured();
-    if (rc) return rc;
-    hipStream_t stream = (hipStream_t)d->stream;
-    if (plan.nsplit == 1) return launched(what, aule_hip::launch_mla_sparse(a, plan, nullptr, stream));
-    aule_hip::ScopedWorkspace ws(plan.ws_bytes, d->workspace, d->workspace ? d->workspace_bytes : 0, stream);
-    if (ws.err != hipSuccess) {
-        set_error("%s failed: workspace allocation (%llu bytes): %s", what, (unsigned long long)plan.ws_bytes, hipGetErrorString(ws.err));
-        return -4;
-    }
-    return launched(what, aule_hip::launch_mla_sparse(a, plan, ws.ptr, stream));
+    return mla_launch_tail(d, plan, what, [&](void* ws, hipStream_t stream) { return aule_hip::launch_mla_sparse(a, plan, ws, stream); });
 }
 
 int32_t aule_attention_mla_sparse_ex(const aule_mla_sparse_desc* d) {
@@ -1721,17 +1726,11 @@ static const char* indexer_shape_error(const Desc* d, Reason& why) {
         return reasonf(why, "cu_seqlens_q is null (plain decode: sequence b owns row b) and total_tokens (%u) < batch (%u)", d->total_tokens, d->batch);
     return nullptr;
 }
-
-// (plain decode reads max_seqlen_q as 1; no sequence has more tokens than the batch)
-template <class Desc>
-static int indexer_max_sq(const Desc* d) {
-    return d->cu_seqlens_q == nullptr ? 1 : (int)(d->max_seqlen_q < d->total_tokens ? d->max_seqlen_q : d->total_tokens);
-}
 }   // extern "C++"
 
 // (`d` passed the field rules of mla_indexer_logits_desc_error: the plan reads the shape, none of the pointers but whether cu_seqlens_q is there)
 static aule_hip::MlaIndexerPlan mla_indexer_plan_of(const aule_mla_indexer_logits_desc* d) {
-    return aule_hip::mla_indexer_plan((int)d->batch, indexer_max_sq(d), (long long)d->block_size * d->max_blocks, d->device);
+    return aule_hip::mla_indexer_plan((int)d->batch, max_sq_or_one(d), (long long)d->block_size * d->max_blocks, d->device);
 }
 
 static const char* mla_indexer_logits_desc_error(const aule_mla_indexer_logits_desc* d, bool launch, Reason& why) {
@@ -1777,7 +1776,7 @@ int32_t aule_mla_indexer_logits_ex(const aule_mla_indexer_logits_desc* d) {
     a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
     a.T = (int)d->total_tokens; a.B = (int)d->batch; a.H = (int)d->heads;
     a.num_blocks = (int)d->num_blocks; a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
-    a.max_seqlen_q = indexer_max_sq(d);
+    a.max_seqlen_q = max_sq_or_one(d);
     a.q_token_stride = d->q_token_stride; a.logits_stride = d->logits_stride;
     a.dtype = d->dtype;
     a.device = d->device;
@@ -1800,8 +1799,8 @@ static const char* mla_indexer_topk_desc_error(const aule_mla_indexer_topk_desc*
     if (d->reserved != 0) return reasonf(why, "reserved (%u) must be 0", d->reserved);
     if (const char* e = indexer_shape_error(d, why)) return e;
     if (indexer_nothing_to_do(d)) return nullptr;
-    if ((uint64_t)d->batch * (uint64_t)indexer_max_sq(d) > 0x7fffffffull)
-        return reasonf(why, "the grid (batch %u * max_seqlen_q %d) exceeds 2^31 - 1 workgroups", d->batch, indexer_max_sq(d));
+    if ((uint64_t)d->batch * (uint64_t)max_sq_or_one(d) > 0x7fffffffull)
+        return reasonf(why, "the grid (batch %u * max_seqlen_q %d) exceeds 2^31 - 1 workgroups", d->batch, max_sq_or_one(d));
     if (!d->logits || !d->block_tables || !d->context_lens || !d->indices)
         return "null tensor pointer (logits, block_tables, context_lens and indices are required)";
     if (((reinterpret_cast<uintptr_t>(d->logits) | reinterpret_cast<uintptr_t>(d->indices) | reinterpret_cast<uintptr_t>(d->block_tables) |
@@ -1826,7 +1825,7 @@ int32_t aule_mla_indexer_topk_ex(const aule_mla_indexer_topk_desc* d) {
     a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
     a.T = (int)d->total_tokens; a.B = (int)d->batch; a.topk = (int)d->topk;
     a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
-    a.max_seqlen_q = indexer_max_sq(d);
+    a.max_seqlen_q = max_sq_or_one(d);
     a.logits_stride = d->logits_stride;
     a.positions = d->output == AULE_INDEXER_POSITIONS;
     DeviceGuard g(d->device);
@@ -1910,8 +1909,8 @@ static void fill_varlen_args(const aule_varlen_desc* d, aule_hip::VarlenArgs& a)
     a.q = d->q; a.k = d->k; a.v = d->v;
     a.cu_seqlens_q = d->cu_seqlens_q; a.cu_seqlens_k = d->cu_seqlens_k;
     a.Tq = (int)d->total_q; a.Tk = (int)d->total_k; a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv; a.D = (int)d->head_dim;
-    a.max_seqlen_q = (int)(d->max_seqlen_q < d->total_q ? d->max_seqlen_q : d->total_q);
-    a.max_seqlen_k = (int)(d->max_seqlen_k < d->total_k ? d->max_seqlen_k : d->total_k);
+    a.max_seqlen_q = aule_hip::seqlen_cut(d->max_seqlen_q, d->total_q);
+    a.max_seqlen_k = aule_hip::seqlen_cut(d->max_seqlen_k, d->total_k);
     a.q_token_stride = d->q_token_stride; a.k_token_stride = d->k_token_stride; a.v_token_stride = d->v_token_stride;
     a.scale = resolve_scale(d->scale, d->head_dim);
     a.causal = d->causal;
@@ -2102,8 +2101,8 @@ static void fill_mla_prefill_args(const aule_mla_prefill_desc* d, aule_hip::MlaP
     a.q = d->q; a.k_nope = d->k_nope; a.k_pe = d->k_pe; a.v = d->v;
     a.cu_seqlens_q = d->cu_seqlens_q; a.cu_seqlens_k = d->cu_seqlens_k;
     a.Tq = (int)d->total_q; a.Tk = (int)d->total_k; a.B = (int)d->batch; a.H = (int)d->heads;
-    a.max_seqlen_q = (int)(d->max_seqlen_q < d->total_q ? d->max_seqlen_q : d->total_q);
-    a.max_seqlen_k = (int)(d->max_seqlen_k < d->total_k ? d->max_seqlen_k : d->total_k);
+    a.max_seqlen_q = aule_hip::seqlen_cut(d->max_seqlen_q, d->total_q);
+    a.max_seqlen_k = aule_hip::seqlen_cut(d->max_seqlen_k, d->total_k);
     a.q_token_stride = d->q_token_stride;
     a.k_nope_token_stride = d->k_nope_token_stride; a.k_nope_head_stride = d->k_nope_head_stride;
     a.v_token_stride = d->v_token_stride; a.v_head_stride = d->v_head_stride;
@@ -2147,8 +2146,7 @@ static bool mla_prefill_bwd_nothing_to_do(const aule_mla_prefill_bwd_desc* d) {
 
 static aule_hip::MlaPrefillBwdPlan mla_prefill_bwd_plan_of(const aule_mla_prefill_bwd_desc* d) {
     return aule_hip::mla_prefill_bwd_plan((int)d->total_q, (int)d->total_k, (int)d->batch, (int)d->heads,
-                                          (int)(d->max_seqlen_q < d->total_q ? d->max_seqlen_q : d->total_q),
-                                          (int)(d->max_seqlen_k < d->total_k ? d->max_seqlen_k : d->total_k), d->device);
+                                          aule_hip::seqlen_cut(d->max_seqlen_q, d->total_q), aule_hip::seqlen_cut(d->max_seqlen_k, d->total_k), d->device);
 }
 
 static const char* mla_prefill_bwd_desc_error(const aule_mla_prefill_bwd_desc* d, bool launch, Reason& why) {
@@ -2670,17 +2668,26 @@ int32_t aule_hip_debug_forward_plan(const aule_attn_desc* d, int32_t* out, int32
     return plan_hook_args(d, a) ? aule_hip::fwd_plan_dump(a, out, cap) : -3;
 }
 
+/* What the plan hooks below answer: the integers of `v`, then the low and the high word of *ws_bytes where the plan has a workspace; their
+ * count, or minus their count when `out` cannot hold them. */
+static int32_t dump_plan(std::initializer_list<int32_t> v, const uint64_t* ws_bytes, int32_t* out, int32_t cap) {
+    const int32_t n = (int32_t)v.size() + (ws_bytes != nullptr ? 2 : 0);
+    if (out == nullptr || cap < n) return -n;
+    out = std::copy(v.begin(), v.end(), out);
+    if (ws_bytes != nullptr) {
+        out[0] = (int32_t)(uint32_t)(*ws_bytes & 0xffffffffull);
+        out[1] = (int32_t)(uint32_t)(*ws_bytes >> 32);
+    }
+    return n;
+}
+
 /* Debug hook: the launch plan of the paged cascade's shared-prefix kernel as integers (include/aule.h lists them): the plan the launch
  * and the workspace query read.  Pure host logic like the forward hook. */
 int32_t aule_hip_debug_shared_prefix_plan(const aule_paged_cascade_desc* d, int32_t* out, int32_t cap) {
     aule_hip::SharedPrefixPlan plan;
     if (!cascade_plan(d, plan)) return -3;
     if (plan.grid <= 0) return 0;
-    const int32_t v[7] = {plan.row_blocks, plan.tiles, plan.nsplit, plan.tiles_per_split, (int32_t)(plan.grid > 0x7fffffffll ? 0x7fffffff : plan.grid),
-                          (int32_t)(uint32_t)(plan.ws_bytes & 0xffffffffull), (int32_t)(uint32_t)(plan.ws_bytes >> 32)};
-    if (out == nullptr || cap < 7) return -7;
-    for (int i = 0; i < 7; ++i) out[i] = v[i];
-    return 7;
+    return dump_plan({plan.row_blocks, plan.tiles, plan.nsplit, plan.tiles_per_split, (int32_t)(plan.grid > 0x7fffffffll ? 0x7fffffff : plan.grid)}, &plan.ws_bytes, out, cap);
 }
 
 /* Debug hook: the launch plan of aule_attention_mla_paged_ex(d) as integers (include/aule.h lists them): the plan the launch and the
@@ -2689,11 +2696,7 @@ int32_t aule_hip_debug_mla_plan(const aule_mla_paged_desc* d, int32_t* out, int3
     aule_hip::MlaPlan plan;
     if (!mla_paged_plan(d, false, plan)) return -3;
     if (plan.grid <= 0) return 0;
-    const int32_t v[6] = {plan.row_blocks, plan.rows_per_block, plan.nsplit, (int32_t)plan.grid,
-                          (int32_t)(uint32_t)(plan.ws_bytes & 0xffffffffull), (int32_t)(uint32_t)(plan.ws_bytes >> 32)};
-    if (out == nullptr || cap < 6) return -6;
-    for (int i = 0; i < 6; ++i) out[i] = v[i];
-    return 6;
+    return dump_plan({plan.row_blocks, plan.rows_per_block, plan.nsplit, (int32_t)plan.grid}, &plan.ws_bytes, out, cap);
 }
 
 /* Debug hook: the launch plan of aule_attention_mla_sparse_ex(d) as integers (include/aule.h lists them): the plan the launch and the
@@ -2703,11 +2706,7 @@ int32_t aule_hip_debug_mla_sparse_plan(const aule_mla_sparse_desc* d, int32_t* o
     if (mla_sparse_desc_error(d, false, text)) return -3;
     if (mla_sparse_nothing_to_do(d)) return 0;
     const aule_hip::MlaPlan plan = mla_sparse_plan_of(d);
-    const int32_t v[6] = {plan.row_blocks, plan.rows_per_block, plan.nsplit, (int32_t)plan.grid,
-                          (int32_t)(uint32_t)(plan.ws_bytes & 0xffffffffull), (int32_t)(uint32_t)(plan.ws_bytes >> 32)};
-    if (out == nullptr || cap < 6) return -6;
-    for (int i = 0; i < 6; ++i) out[i] = v[i];
-    return 6;
+    return dump_plan({plan.row_blocks, plan.rows_per_block, plan.nsplit, (int32_t)plan.grid}, &plan.ws_bytes, out, cap);
 }
 
 /* Debug hook (not part of the drop-in ABI): aule_attention_mla_sparse_ex(d) with `nsplit` key ranges (within 1 .. min(64, tiles)) instead
@@ -2728,10 +2727,7 @@ int32_t aule_hip_debug_mla_indexer_plan(const aule_mla_indexer_logits_desc* d, i
     if (mla_indexer_logits_desc_error(d, false, text)) return -3;
     if (indexer_nothing_to_do(d)) return 0;
     const aule_hip::MlaIndexerPlan plan = mla_indexer_plan_of(d);
-    const int32_t v[5] = {plan.group_tokens, plan.token_groups, plan.chunk_keys, plan.key_chunks, (int32_t)plan.grid};
-    if (out == nullptr || cap < 5) return -5;
-    for (int i = 0; i < 5; ++i) out[i] = v[i];
-    return 5;
+    return dump_plan({plan.group_tokens, plan.token_groups, plan.chunk_keys, plan.key_chunks, (int32_t)plan.grid}, nullptr, out, cap);
 }
 
 /* Debug hook: the launch plan of aule_attention_mla_prefill_backward_ex(d) as integers (include/aule.h lists them): the plan the launch
@@ -2741,11 +2737,8 @@ int32_t aule_hip_debug_mla_prefill_backward_plan(const aule_mla_prefill_bwd_desc
     if (mla_prefill_bwd_desc_error(d, false, text)) return -3;
     if (mla_prefill_bwd_nothing_to_do(d)) return 0;
     const aule_hip::MlaPrefillBwdPlan plan = mla_prefill_bwd_plan_of(d);
-    const int32_t v[10] = {plan.heads_per_chunk, plan.n_chunks, plan.max_chunks, (int32_t)plan.delta_grid, (int32_t)plan.dq_grid, (int32_t)plan.dkdv_grid,
-                           (int32_t)plan.reduce_grid, plan.reduce ? 1 : 0, (int32_t)(uint32_t)(plan.ws_bytes & 0xffffffffull), (int32_t)(uint32_t)(plan.ws_bytes >> 32)};
-    if (out == nullptr || cap < 10) return -10;
-    for (int i = 0; i < 10; ++i) out[i] = v[i];
-    return 10;
+    return dump_plan({plan.heads_per_chunk, plan.n_chunks, plan.max_chunks, (int32_t)plan.delta_grid, (int32_t)plan.dq_grid, (int32_t)plan.dkdv_grid,
+                      (int32_t)plan.reduce_grid, plan.reduce ? 1 : 0}, &plan.ws_bytes, out, cap);
 }
 
 /* Debug hook: what the most recent backward launch of this process ran (bit mask, include/aule.h). */

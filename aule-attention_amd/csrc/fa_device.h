@@ -65,6 +65,14 @@ struct F16Traits {
     }
 };
 
+// Host: the kernel instance for a 16-bit dtype code (DType of fa_kernels.h): f(Bf16Traits{}) or f(F16Traits{}), -1 for anything else
+template <class F>
+int dispatch_16bit(int dtype, F&& f) {
+    if (dtype == Bf16Traits::kDType) return f(Bf16Traits{});
+    if (dtype == F16Traits::kDType) return f(F16Traits{});
+    return -1;
+}
+
 template <class T>
 __device__ __forceinline__ typename T::v8 as_v8(u32x4_t x) {
     return __builtin_bit_cast(typename T::v8, x);
@@ -118,6 +126,33 @@ __device__ __forceinline__ float xhalf_fast(float x) {
     return x;
 #endif
 }
+
+// The clamps of the ragged entries' memory-safety contract (include/aule.h), stated once for every kernel that reads cu_seqlens,
+// context_lens or a block table: whatever those arrays hold, no kernel indexes outside its buffers.
+// Sequence b of a packed axis of `total` rows: first row s and length n = min(e - s, cap), every value clamped so that
+// [s, s + n) lies inside [0, total) whatever cu holds.  kRowPerSeq: cu may be null, and then sequence b owns row b (b < total: the
+// host checks).  s and e are set in the branches and n formed after them: with n formed inside each branch the MLA kernels'
+// scalar prologue compiled to another order (profiles/ragged_rules_resources.txt).
+struct SeqRange {
+    int s, n;
+};
+template <bool kRowPerSeq = false>
+__host__ __device__ __forceinline__ SeqRange seq_range(const int* cu, int b, int total, int cap) {
+    int s, e;
+    if (!kRowPerSeq || cu != nullptr) {
+        s = min(max(cu[b], 0), total);
+        e = min(max(cu[b + 1], s), total);
+    } else {
+        s = b;
+        e = b + 1;
+    }
+    return SeqRange{s, min(e - s, cap)};
+}
+__host__ __device__ __forceinline__ SeqRange seq_range_or_row(const int* cu, int b, int total, int cap) { return seq_range<true>(cu, b, total, cap); }
+// The keys of sequence b: its context length inside [0, cap], cap the capacity of its block table row.
+__host__ __device__ __forceinline__ int seq_len(const int* ctx, int b, int cap) { return min(max(ctx[b], 0), cap); }
+// The logical block of key j under block size bs (bs_shift >= 0: bs = 1 << bs_shift; the host's shift_of, fa_kernels.h).
+__host__ __device__ __forceinline__ int block_of(int j, int bs, int bs_shift) { return bs_shift >= 0 ? j >> bs_shift : j / bs; }
 
 // Work decode shared by fwd and bwd kernels: blockIdx.x -> (batch, kv head,
 // q head, block index inside the sequence), heaviest causal blocks first, and

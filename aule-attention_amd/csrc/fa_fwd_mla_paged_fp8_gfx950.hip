@@ -35,27 +35,19 @@ __global__ void __launch_bounds__(256, 1) fa_mla_sparse_fp8_kernel(const MlaPara
 // (`p` as launch_mla_paged fills it, kv_scale set; grid: the plan's)
 int launch_mla_fp8_kernel(const MlaParams& p, long long grid, int dtype, hipStream_t stream) {
     if (p.kv_scale == nullptr || grid <= 0 || grid > 0x7fffffffll) return -1;
-    if (dtype == kBF16) {
-        hipLaunchKernelGGL((fa_mla_fp8_latent_kernel<Bf16Traits>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-    } else if (dtype == kF16) {
-        hipLaunchKernelGGL((fa_mla_fp8_latent_kernel<F16Traits>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-    } else {
-        return -1;
-    }
-    return (int)hipGetLastError();
+    return dispatch_16bit(dtype, [&](auto t) {
+        hipLaunchKernelGGL((fa_mla_fp8_latent_kernel<decltype(t)>), dim3((unsigned)grid), dim3(256), 0, stream, p);
+        return (int)hipGetLastError();
+    });
 }
 
 // (`p` as launch_mla_sparse fills it, kv_scale set; grid: the plan's)
 int launch_mla_sparse_fp8_kernel(const MlaParams& p, long long grid, int dtype, hipStream_t stream) {
     if (p.kv_scale == nullptr || p.list == nullptr || grid <= 0 || grid > 0x7fffffffll) return -1;
-    if (dtype == kBF16) {
-        hipLaunchKernelGGL((fa_mla_sparse_fp8_kernel<Bf16Traits>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-    } else if (dtype == kF16) {
-        hipLaunchKernelGGL((fa_mla_sparse_fp8_kernel<F16Traits>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-    } else {
-        return -1;
-    }
-    return (int)hipGetLastError();
+    return dispatch_16bit(dtype, [&](auto t) {
+        hipLaunchKernelGGL((fa_mla_sparse_fp8_kernel<decltype(t)>), dim3((unsigned)grid), dim3(256), 0, stream, p);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace aule_hip

@@ -22,7 +22,7 @@
 // 68 MFMAs per wave and 64-key tile with no product computed twice; LDS 78 848 + 32 768 = 111 616 bytes; the next tile sits in
 // 72 registers per thread while this one is computed (8 threads x 16 bytes = one 128-byte line of a latent row per request).
 //
-// Key ranges.  The host fixes nsplit from the shape alone (mla_plan below: the one place that decides row blocks, nsplit, grid and
+// Key ranges.  The host fixes nsplit from the shape alone (mla_split_plan below: the one place that decides row blocks, nsplit, grid and
 // workspace); every workgroup derives ITS sequence's range on the device from the clamped L: split k owns the 64-key tiles
 // [k * ceil(tiles(L) / nsplit), ...), so the work is balanced whatever the table's capacity.  nsplit == 1: one launch writes out /
 // lse.  nsplit > 1: fp32 partials in the workspace -- un-normalised O [nsplit][T * Hq][512], then {m (log2 units), l}
@@ -101,87 +101,68 @@ __global__ void __launch_bounds__(256) fa_mla_combine_kernel(const MlaParams p) 
     if (p.lse != nullptr && lane == 0) p.lse[orow] = ls > 0.f ? (mm + fast_log2(ls)) * kLn2 : -__builtin_inff();
 }
 
-template <class T>
-int launch_type(const MlaParams& p, const MlaPlan& plan, int dtype, hipStream_t stream) {
-    int rc;
-    if (p.kv_scale != nullptr) {
-        rc = launch_mla_fp8_kernel(p, plan.grid, dtype, stream);
-    } else {
-        hipLaunchKernelGGL((fa_fwd_mla_paged_kernel<T>), dim3((unsigned)plan.grid), dim3(256), 0, stream, p);
-        rc = (int)hipGetLastError();
-    }
-    if (rc != 0 || plan.nsplit == 1) return rc;
-    return launch_mla_combine(p, plan.row_blocks, dtype, stream);
-}
-
 }  // namespace
 
 int launch_mla_combine(const MlaParams& p, int row_blocks, int dtype, hipStream_t stream) {
     const long long grid = (long long)row_blocks * p.B * kMlaCombineParts;
     if (grid <= 0 || grid > 0x7fffffffll) return -1;
-    if (dtype == kBF16) {
-        hipLaunchKernelGGL((fa_mla_combine_kernel<Bf16Traits>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-    } else if (dtype == kF16) {
-        hipLaunchKernelGGL((fa_mla_combine_kernel<F16Traits>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-    } else {
-        return -1;
-    }
-    return (int)hipGetLastError();
+    return dispatch_16bit(dtype, [&](auto t) {
+        hipLaunchKernelGGL((fa_mla_combine_kernel<decltype(t)>), dim3((unsigned)grid), dim3(256), 0, stream, p);
+        return (int)hipGetLastError();
+    });
 }
 
-// The launch plan: the one place that decides row blocks, nsplit, grid and workspace (launch, size query, debug hook).  From the
-// shape alone: row blocks x batch x nsplit covers the device's compute units, nsplit at most kMlaMaxSplit and at most one split
-// per two 64-key tiles of the table's capacity (a split is worth a launch slot only with some keys to read); WHICH tiles a split
-// owns is decided on the device from each sequence's own length.
-MlaPlan mla_plan(const MlaArgs& a) {
+// The launch plans: the one place that decides row blocks, nsplit, grid and workspace (launch, size query, debug hook), from the
+// shape alone; WHICH tiles a split owns is decided on the device from each sequence's own length.  The rule is fa_mla_common.h's.
+MlaPlan mla_split_plan(long long row_blocks, long long units, long long tiles, int T, int Hq, int device, long long nsplit) {
+    const long long base = row_blocks * units;
+    long long ns = nsplit;
+    if (ns <= 0) {
+        ns = (device_cu_count(device) + base - 1) / base;
+        if (ns > kMlaMaxSplit) ns = kMlaMaxSplit;
+        if (ns > tiles / 2) ns = tiles / 2;
+        if (ns < 1) ns = 1;
+    }
     MlaPlan plan;
-    if (a.T <= 0 || a.B <= 0 || a.Hq <= 0 || a.max_seqlen_q <= 0 || a.block_size <= 0 || a.max_blocks <= 0) return plan;
-    const long long n = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T;   // no sequence has more tokens than the batch
-    const long long rb = (n * a.Hq + kMlaRows - 1) / kMlaRows;
-    const long long base = rb * a.B;
-    const long long cus = device_cu_count(a.device);
-    const long long tiles = ((long long)a.block_size * a.max_blocks + kMlaKeys - 1) / kMlaKeys;
-    long long ns = (cus + base - 1) / base;
-    if (ns > kMlaMaxSplit) ns = kMlaMaxSplit;
-    if (ns > tiles / 2) ns = tiles / 2;
-    if (ns < 1) ns = 1;
-    plan.row_blocks = (int)rb;
+    plan.row_blocks = (int)row_blocks;
     plan.rows_per_block = kMlaRows;
     plan.nsplit = (int)ns;
     plan.grid = base * ns;
-    plan.ws_bytes = ns > 1 ? ((uint64_t)ns * (uint64_t)a.T * (uint64_t)a.Hq * (kMlaV + 2) * 4 + 15) & ~15ull : 0;
+    plan.ws_bytes = ns > 1 ? ((uint64_t)ns * (uint64_t)T * (uint64_t)Hq * (kMlaV + 2) * 4 + 15) & ~15ull : 0;
     return plan;
+}
+
+// The dense call: row blocks of a sequence's packed rows, the tiles of the table's capacity.
+MlaPlan mla_plan(const MlaArgs& a) {
+    if (a.T <= 0 || a.B <= 0 || a.Hq <= 0 || a.max_seqlen_q <= 0 || a.block_size <= 0 || a.max_blocks <= 0) return MlaPlan();
+    const long long rb = ((long long)seqlen_cut(a.max_seqlen_q, a.T) * a.Hq + kMlaRows - 1) / kMlaRows;
+    return mla_split_plan(rb, a.B, ((long long)a.block_size * a.max_blocks + kMlaKeys - 1) / kMlaKeys, a.T, a.Hq, a.device);
 }
 
 // (`ws`: plan.ws_bytes bytes, 16-byte aligned, when plan.nsplit > 1)
 int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream) {
-    if (plan.grid <= 0 || plan.grid > 0x7fffffffll || (long long)plan.row_blocks * a.B * kMlaCombineParts > 0x7fffffffll) return -1;
+    if ((long long)plan.row_blocks * a.B * kMlaCombineParts > 0x7fffffffll) return -1;
     if ((long long)a.block_size * a.max_blocks >= (1ll << 30)) return -1;
-    if (a.q_token_stride < (long long)a.Hq * kMlaQK || a.q_token_stride % 8 != 0) return -1;
-    if (((long long)a.T + kMlaRows) * a.Hq > 0x7fffffffll) return -1;   // the kernels count packed rows in 32 bits
     if (a.cu_seqlens_q == nullptr && a.T < a.B) return -1;
-    if (plan.nsplit > 1 && ws == nullptr) return -1;
-    const bool fp8 = a.cache_kind == kCacheFp8E4M3;
-    if (fp8 ? a.kv_scale == nullptr : a.cache_kind != kCache16) return -1;
     MlaParams p;   // (list stays null, its default: that is what tells the combine kernel that these are a dense call's partials)
-    p.q = static_cast<const char*>(a.q); p.kv = static_cast<const char*>(a.kv_cache);
-    p.o = static_cast<char*>(a.out); p.lse = a.lse;
-    p.rows_total = (long long)a.T * a.Hq;
-    p.part_o = static_cast<float*>(ws);
-    p.part_ml = p.part_o != nullptr ? p.part_o + (long long)plan.nsplit * p.rows_total * kMlaV : nullptr;
+    if (mla_common_params(a, plan, ws, p) != 0) return -1;
     p.table = a.block_tables; p.ctx = a.context_lens; p.cu = a.cu_seqlens_q;
-    p.q_stride = a.q_token_stride;
-    p.T = a.T; p.B = a.B; p.Hq = a.Hq;
+    p.B = a.B;
     p.bs = a.block_size;
-    p.bs_shift = (a.block_size & (a.block_size - 1)) == 0 ? __builtin_ctz((unsigned)a.block_size) : -1;
+    p.bs_shift = shift_of(a.block_size);
     p.max_blocks = a.max_blocks;
-    p.max_sq = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T;
-    p.row_blocks = plan.row_blocks; p.nsplit = plan.nsplit;
-    p.c = a.scale * kLog2e;
-    p.kv_scale = fp8 ? a.kv_scale : nullptr;
-    if (a.dtype == kBF16) return launch_type<Bf16Traits>(p, plan, a.dtype, stream);
-    if (a.dtype == kF16) return launch_type<F16Traits>(p, plan, a.dtype, stream);
-    return -1;
+    p.max_sq = seqlen_cut(a.max_seqlen_q, a.T);
+    int rc;
+    if (p.kv_scale != nullptr) {
+        rc = launch_mla_fp8_kernel(p, plan.grid, a.dtype, stream);
+    } else {
+        rc = dispatch_16bit(a.dtype, [&](auto t) {
+            hipLaunchKernelGGL((fa_fwd_mla_paged_kernel<decltype(t)>), dim3((unsigned)plan.grid), dim3(256), 0, stream, p);
+            return (int)hipGetLastError();
+        });
+    }
+    if (rc != 0 || plan.nsplit == 1) return rc;
+    return launch_mla_combine(p, plan.row_blocks, a.dtype, stream);
 }
 
 }  // namespace aule_hip

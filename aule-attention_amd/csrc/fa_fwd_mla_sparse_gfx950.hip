@@ -14,11 +14,13 @@
 //     slot is not read but zero-filled, so a NaN in a row nobody names cannot reach P.V through p = 0;
 //   mask: one wave-uniform validity word per tile, tested at compile-time bit positions (fa_mla_common.h, MlaListKeys).
 //
-// Key ranges: mla_sparse_plan below is the one statement of row blocks, nsplit, grid and workspace -- the dense rule applied to the
+// Key ranges: mla_sparse_plan below states row blocks, nsplit, grid and workspace by the dense rule (mla_split_plan) applied to the
 // list: tiles = ceil(topk / 64), nsplit covers the compute units with T * row blocks * nsplit workgroups, at most kMlaMaxSplit and at
 // most one split per two tiles.  Split k owns tiles [k * ceil(tiles / nsplit), ...); the partials have the dense layout and the dense
 // combine kernel adds them in split order (no atomics: two runs give the same bits).  A split whose tiles hold no valid entry writes
 // O = 0, m = -inf, l = 0.  Every one of the T rows is written.
+#include <algorithm>
+
 #include "fa_mla_common.h"
 
 namespace aule_hip {
@@ -31,65 +33,37 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_mla_sparse_kernel(const MlaPara
     mla_paged_body<T, Kv16, true>(p, Ls, Xs);
 }
 
-int launch_16(const MlaParams& p, long long grid, int dtype, hipStream_t stream) {
-    if (dtype == kBF16) {
-        hipLaunchKernelGGL((fa_fwd_mla_sparse_kernel<Bf16Traits>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-    } else if (dtype == kF16) {
-        hipLaunchKernelGGL((fa_fwd_mla_sparse_kernel<F16Traits>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-    } else {
-        return -1;
-    }
-    return (int)hipGetLastError();
-}
-
 }  // namespace
 
+// The sparse call: row blocks of ONE token's heads, the tiles of its list.
 MlaPlan mla_sparse_plan(int T, int Hq, int topk, int device, int force_nsplit) {
-    MlaPlan plan;
-    if (T <= 0 || Hq <= 0 || topk <= 0) return plan;
-    const long long rb = ((long long)Hq + kMlaRows - 1) / kMlaRows;
-    const long long base = rb * T;
-    const long long cus = device_cu_count(device);
+    if (T <= 0 || Hq <= 0 || topk <= 0) return MlaPlan();
     const long long tiles = ((long long)topk + kMlaKeys - 1) / kMlaKeys;
-    long long ns = (cus + base - 1) / base;
-    if (ns > kMlaMaxSplit) ns = kMlaMaxSplit;
-    if (ns > tiles / 2) ns = tiles / 2;
-    if (ns < 1) ns = 1;
-    if (force_nsplit > 0) ns = force_nsplit < kMlaMaxSplit ? (force_nsplit < tiles ? force_nsplit : tiles) : (kMlaMaxSplit < tiles ? kMlaMaxSplit : tiles);
-    plan.row_blocks = (int)rb;
-    plan.rows_per_block = kMlaRows;
-    plan.nsplit = (int)ns;
-    plan.grid = base * ns;
-    plan.ws_bytes = ns > 1 ? ((uint64_t)ns * (uint64_t)T * (uint64_t)Hq * (kMlaV + 2) * 4 + 15) & ~15ull : 0;
-    return plan;
+    const long long forced = force_nsplit > 0 ? std::min<long long>({force_nsplit, kMlaMaxSplit, tiles}) : 0;
+    return mla_split_plan(((long long)Hq + kMlaRows - 1) / kMlaRows, T, tiles, T, Hq, device, forced);
 }
 
 // (`ws`: plan.ws_bytes bytes, 16-byte aligned, when plan.nsplit > 1)
 int launch_mla_sparse(const MlaSparseArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream) {
-    if (plan.grid <= 0 || plan.grid > 0x7fffffffll || (long long)plan.row_blocks * a.T * 16 > 0x7fffffffll) return -1;   // (attention and combine grids)
+    if ((long long)plan.row_blocks * a.T * 16 > 0x7fffffffll) return -1;   // (the combine's grid)
     if (a.topk < 1 || a.topk > kMlaSparseMaxTopk || a.slots < 1) return -1;
-    if (a.q_token_stride < (long long)a.Hq * kMlaQK || a.q_token_stride % 8 != 0) return -1;
-    if (((long long)a.T + kMlaRows) * a.Hq > 0x7fffffffll) return -1;   // the kernels count packed rows in 32 bits
-    if (plan.nsplit > 1 && ws == nullptr) return -1;
     if (a.indices == nullptr) return -1;
-    const bool fp8 = a.cache_kind == kCacheFp8E4M3;
-    if (fp8 ? a.kv_scale == nullptr : a.cache_kind != kCache16) return -1;
     MlaParams p;
-    p.q = static_cast<const char*>(a.q); p.kv = static_cast<const char*>(a.kv_cache);
-    p.o = static_cast<char*>(a.out); p.lse = a.lse;
-    p.rows_total = (long long)a.T * a.Hq;
-    p.part_o = static_cast<float*>(ws);
-    p.part_ml = p.part_o != nullptr ? p.part_o + (long long)plan.nsplit * p.rows_total * kMlaV : nullptr;
+    if (mla_common_params(a, plan, ws, p) != 0) return -1;
     p.table = nullptr; p.ctx = nullptr; p.cu = nullptr;
-    p.q_stride = a.q_token_stride;
-    p.T = a.T; p.B = a.T; p.Hq = a.Hq;
+    p.B = a.T;
     p.bs = 1; p.bs_shift = 0;
     p.max_blocks = 0; p.max_sq = 1;
-    p.row_blocks = plan.row_blocks; p.nsplit = plan.nsplit;
-    p.c = a.scale * kLog2e;
-    p.kv_scale = fp8 ? a.kv_scale : nullptr;
     p.list = a.indices; p.topk = a.topk; p.slots = a.slots;
-    const int rc = fp8 ? launch_mla_sparse_fp8_kernel(p, plan.grid, a.dtype, stream) : launch_16(p, plan.grid, a.dtype, stream);
+    int rc;
+    if (p.kv_scale != nullptr) {
+        rc = launch_mla_sparse_fp8_kernel(p, plan.grid, a.dtype, stream);
+    } else {
+        rc = dispatch_16bit(a.dtype, [&](auto t) {
+            hipLaunchKernelGGL((fa_fwd_mla_sparse_kernel<decltype(t)>), dim3((unsigned)plan.grid), dim3(256), 0, stream, p);
+            return (int)hipGetLastError();
+        });
+    }
     if (rc != 0 || plan.nsplit == 1) return rc;
     return launch_mla_combine(p, plan.row_blocks, a.dtype, stream);
 }

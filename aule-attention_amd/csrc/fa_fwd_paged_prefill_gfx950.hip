@@ -44,12 +44,10 @@
     const int rank = bid / units, unit = bid - rank * units;
     const int hk = unit % p.Hkv, b = unit / p.Hkv;
 
-    // the sequence, clamped
-    const int cap = p.max_blocks * p.bs;   // (< 2^30: the host checks)
-    const int L = min(max(p.ctx[b], 0), cap);
-    const int s = min(max(p.cu[b], 0), p.T);
-    const int e = min(max(p.cu[b + 1], s), p.T);
-    const int n = min(e - s, p.max_sq);
+    // the sequence, clamped (fa_device.h)
+    const int L = seq_len(p.ctx, b, p.max_blocks * p.bs);   // (the capacity < 2^30: the host checks)
+    const SeqRange own_rows = seq_range(p.cu, b, p.T, p.max_sq);
+    const int s = own_rows.s, n = own_rows.n;
     const int R = n * p.g;   // packed rows of this (sequence, KV head); T * g < 2^31: the host checks
     // rank 0 is the sequence's last (heaviest) block, whatever its length: the one block of a decode starts with the first wave of
     // workgroups, beside the last block of a long chunk
@@ -293,7 +291,7 @@ int launch_paged_prefill(const PagedPrefillArgs& a, hipStream_t stream) {
     p.q_stride = a.q_token_stride;
     p.T = a.T; p.B = a.B; p.Hq = a.Hq; p.Hkv = a.Hkv; p.g = a.Hq / a.Hkv;
     p.bs = a.block_size;
-    p.bs_shift = (a.block_size & (a.block_size - 1)) == 0 ? __builtin_ctz((unsigned)a.block_size) : -1;
+    p.bs_shift = shift_of(a.block_size);
     p.max_blocks = a.max_blocks; p.max_sq = seqlen_cut(a.max_seqlen_q, a.T);
     p.c = a.scale * kLog2e;
     p.window = a.window > 0 ? a.window : 0;

@@ -216,7 +216,7 @@ int launch_shared_prefix(const SharedPrefixArgs& a, const SharedPrefixPlan& pl, 
     p.part_stride = (long long)a.T * a.Hq * (a.D + 2);
     p.Hq = a.Hq; p.Hkv = a.Hkv; p.g = a.Hq / a.Hkv; p.R = a.T * p.g;
     p.bs = a.block_size;
-    p.bs_shift = (a.block_size & (a.block_size - 1)) == 0 ? __builtin_ctz((unsigned)a.block_size) : -1;
+    p.bs_shift = shift_of(a.block_size);
     p.max_blocks = a.max_prefix_blocks;
     p.nrb = pl.row_blocks; p.tps = pl.tiles_per_split;
     p.c = a.scale * kLog2e;

@@ -459,7 +459,12 @@ int launch_mla_indexer_topk(const MlaIndexerTopkArgs& a, hipStream_t stream);   
 
 // The cut of a sequence's length every ragged entry applies (paged prefill, variable-length, MLA prefill): no sequence has more
 // tokens than the batch.
-inline int seqlen_cut(int max_seqlen, int total) { return max_seqlen < total ? max_seqlen : total; }
+// I: int, or a descriptor's uint32_t fields compared as they stand (total < 2^30: the checkers) -- a max_seqlen of 2^31 or more cuts
+// to the batch there, not to a negative number.
+template <class I>
+inline int seqlen_cut(I max_seqlen, I total) { return (int)(max_seqlen < total ? max_seqlen : total); }
+// The kernels' block lookup (block_of, fa_device.h) shifts when the block size is a power of two: its shift, -1 for any other size
+inline int shift_of(int block_size) { return (block_size & (block_size - 1)) == 0 ? __builtin_ctz((unsigned)block_size) : -1; }
 
 // Variable-length packed batches (fa_fwd_varlen_gfx950.hip, fa_bwd_varlen_gfx950.hip): sequences of different lengths packed
 // along one token axis, forward and backward.

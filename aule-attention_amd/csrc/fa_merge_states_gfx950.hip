@@ -90,11 +90,10 @@ template <class T, int D>
 __global__ void __launch_bounds__(256) fa_cascade_merge_kernel(const CascadeParams p) {
     constexpr int CPR = D / 8;
     const int b = (int)blockIdx.x / p.nchunk, chunk = (int)blockIdx.x % p.nchunk;
-    // the sequence, clamped as the prefill clamps it
-    const int L = min(max(p.ctx[b], 0), p.cap);
-    const int s = min(max(p.cu[b], 0), p.T);
-    const int e = min(max(p.cu[b + 1], s), p.T);
-    const int n = min(e - s, p.max_sq);
+    // the sequence, clamped as the prefill clamps it (fa_device.h)
+    const int L = seq_len(p.ctx, b, p.cap);
+    const SeqRange own_rows = seq_range(p.cu, b, p.T, p.max_sq);
+    const int s = own_rows.s, n = own_rows.n;
     const int i0 = chunk * kMergeTokens;
     if (i0 >= n) return;
     const int items = (min(n, i0 + kMergeTokens) - i0) * p.Hq * CPR;
@@ -162,17 +161,16 @@ int launch_merge_states(const MergeStatesArgs& a, hipStream_t stream) {
     p.rows = a.rows; p.cpr = a.D / 8;
     const long long nwg = (a.rows * p.cpr + 255) / 256;
     if (nwg > 0x7fffffffll) return -1;
-    if (a.dtype == kBF16) hipLaunchKernelGGL(fa_merge_states_kernel<Bf16Traits>, dim3((unsigned)nwg), dim3(256), 0, stream, p);
-    else if (a.dtype == kF16) hipLaunchKernelGGL(fa_merge_states_kernel<F16Traits>, dim3((unsigned)nwg), dim3(256), 0, stream, p);
-    else return -1;
-    return (int)hipGetLastError();
+    return dispatch_16bit(a.dtype, [&](auto t) {
+        hipLaunchKernelGGL(fa_merge_states_kernel<decltype(t)>, dim3((unsigned)nwg), dim3(256), 0, stream, p);
+        return (int)hipGetLastError();
+    });
 }
 
 // one workgroup per (sequence, chunk of kMergeTokens tokens); a chunk past the sequence's tokens leaves at once
 long long cascade_merge_grid(const CascadeMergeArgs& a) {
     if (a.B <= 0 || a.max_seqlen_q <= 0 || a.T <= 0) return 0;
-    const long long n = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T;
-    return (n + kMergeTokens - 1) / kMergeTokens * a.B;
+    return ((long long)seqlen_cut(a.max_seqlen_q, a.T) + kMergeTokens - 1) / kMergeTokens * a.B;
 }
 
 int launch_cascade_merge(const CascadeMergeArgs& a, hipStream_t stream) {
@@ -185,10 +183,8 @@ int launch_cascade_merge(const CascadeMergeArgs& a, hipStream_t stream) {
     p.part_stride = (long long)a.T * a.Hq * (a.D + 2);
     p.nsplit = a.nsplit; p.nchunk = (int)(nwg / a.B);
     p.T = a.T; p.Hq = a.Hq;
-    p.max_sq = a.max_seqlen_q < a.T ? a.max_seqlen_q : a.T; p.cap = a.own_capacity;
-    if (a.dtype == kBF16) return launch_cascade_dim<Bf16Traits>(p, a.D, nwg, stream);
-    if (a.dtype == kF16) return launch_cascade_dim<F16Traits>(p, a.D, nwg, stream);
-    return -1;
+    p.max_sq = seqlen_cut(a.max_seqlen_q, a.T); p.cap = a.own_capacity;
+    return dispatch_16bit(a.dtype, [&](auto t) { return launch_cascade_dim<decltype(t)>(p, a.D, nwg, stream); });
 }
 
 }  // namespace aule_hip

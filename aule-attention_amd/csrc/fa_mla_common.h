@@ -42,6 +42,12 @@ int launch_mla_sparse_fp8_kernel(const MlaParams& p, long long grid, int dtype, 
 // The combine of either call's partials (fa_fwd_mla_paged_gfx950.hip): row_blocks * p.B * 16 workgroups, after the attention kernel.
 int launch_mla_combine(const MlaParams& p, int row_blocks, int dtype, hipStream_t stream);
 
+// The split rule of both plans (fa_fwd_mla_paged_gfx950.hip): `row_blocks` blocks of rows per unit, `units` sequences or tokens, `tiles`
+// 64-key tiles a split could own at most.  nsplit covers the device's compute units with row_blocks * units * nsplit workgroups, at most
+// kMlaMaxSplit and at most one split per two tiles (a split is worth a launch slot only with some keys to read); nsplit > 0 (the sparse
+// debug path's force_nsplit alone): that many instead.  The workspace is round16(nsplit * T * Hq * 514 * 4) bytes when nsplit > 1.
+MlaPlan mla_split_plan(long long row_blocks, long long units, long long tiles, int T, int Hq, int device, long long nsplit = 0);
+
 namespace {
 
 constexpr int kMlaQK = 576;                     // key / query width
@@ -55,22 +61,39 @@ constexpr int kMlaN = kMlaRB / 16 / 8;          // 16-byte chunks per thread and
 constexpr int kMlaLdsImage = kMlaKeys * kMlaPitch;   // bytes of the latent image
 constexpr int kMlaLdsScores = 4 * 8 * 1024;           // partial scores: [wave][register quad][lane] 16 bytes
 
+// Host: what launch_mla_paged and launch_mla_sparse (A: MlaArgs, MlaSparseArgs) refuse alike, and the fields of `p` they fill alike --
+// the tensors, the workspace's two parts (`ws`: plan.ws_bytes bytes, 16-byte aligned, when plan.nsplit > 1), the row counts, the plan,
+// the score scale and the FP8 scale.  The key source's fields (table, lengths and offsets, or the list) are the caller's.  -1: refused.
+template <class A>
+int mla_common_params(const A& a, const MlaPlan& plan, void* ws, MlaParams& p) {
+    if (plan.grid <= 0 || plan.grid > 0x7fffffffll) return -1;
+    if (a.q_token_stride < (long long)a.Hq * kMlaQK || a.q_token_stride % 8 != 0) return -1;
+    if (((long long)a.T + kMlaRows) * a.Hq > 0x7fffffffll) return -1;   // the kernels count packed rows in 32 bits
+    if (plan.nsplit > 1 && ws == nullptr) return -1;
+    const bool fp8 = a.cache_kind == kCacheFp8E4M3;
+    if (fp8 ? a.kv_scale == nullptr : a.cache_kind != kCache16) return -1;
+    p.q = static_cast<const char*>(a.q); p.kv = static_cast<const char*>(a.kv_cache);
+    p.o = static_cast<char*>(a.out); p.lse = a.lse;
+    p.rows_total = (long long)a.T * a.Hq;
+    p.part_o = static_cast<float*>(ws);
+    p.part_ml = p.part_o != nullptr ? p.part_o + (long long)plan.nsplit * p.rows_total * kMlaV : nullptr;
+    p.q_stride = a.q_token_stride;
+    p.T = a.T; p.Hq = a.Hq;
+    p.row_blocks = plan.row_blocks; p.nsplit = plan.nsplit;
+    p.c = a.scale * kLog2e;
+    p.kv_scale = fp8 ? a.kv_scale : nullptr;
+    return 0;
+}
+
 // what both kernels derive for workgroup (rank, sequence b): the clamps of the contract and the block of packed rows
 struct MlaBlock {
     int L, s, n;
     int r0, rows;   // rows == 0: nothing to do
     __device__ __forceinline__ MlaBlock(const MlaParams& p, int b, int rank) {
-        const int cap = p.max_blocks * p.bs;   // (< 2^30: the host checks)
-        L = min(max(p.ctx[b], 0), cap);
-        int e;
-        if (p.cu != nullptr) {
-            s = min(max(p.cu[b], 0), p.T);
-            e = min(max(p.cu[b + 1], s), p.T);
-        } else {
-            s = b;   // (b < T: the host checks)
-            e = b + 1;
-        }
-        n = min(e - s, p.max_sq);
+        L = seq_len(p.ctx, b, p.max_blocks * p.bs);   // (the capacity < 2^30: the host checks)
+        const SeqRange q = seq_range_or_row(p.cu, b, p.T, p.max_sq);   // (a null cu: b < T, the host checks)
+        s = q.s;
+        n = q.n;
         const int R = n * p.Hq;   // (T + 64) * Hq < 2^31: the host checks
         const int own = (R + kMlaRows - 1) / kMlaRows;
         r0 = 0;
@@ -163,7 +186,7 @@ struct MlaTile {
             const int kv = k0 + (tid >> 3) + 32 * j;
             long long at = 0;
             if (kv < kend) {
-                const int lb = p.bs_shift >= 0 ? kv >> p.bs_shift : kv / p.bs;
+                const int lb = block_of(kv, p.bs, p.bs_shift);
                 at = (long long)tab[lb] * p.bs + (kv - lb * p.bs);
             }
             slot[j] = at;

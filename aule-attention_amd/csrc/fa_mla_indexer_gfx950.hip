@@ -79,28 +79,10 @@ struct TopkParams {
     int positions;       // 1: raw positions, 0: slots through the table
 };
 
-// aule_mla_paged_desc's clamps, made on the device: L_b, s_b, n_b
-template <class P>
-__device__ __forceinline__ void seq_of(const P& p, int b, int& L, int& s, int& n) {
-    L = min(max(p.ctx[b], 0), p.W);
-    int e;
-    if (p.cu != nullptr) {
-        s = min(max(p.cu[b], 0), p.T);
-        e = min(max(p.cu[b + 1], s), p.T);
-    } else {
-        s = b;   // (b < T: the host checks)
-        e = b + 1;
-    }
-    n = min(e - s, p.max_sq);
-}
-
-template <class P>
-__device__ __forceinline__ int block_of(const P& p, int j) { return p.bs_shift >= 0 ? j >> p.bs_shift : j / p.bs; }
-
 // the cache row of position j of the sequence whose table row is `tab` (j < L_b: the entry is one of the used blocks); the entry is
 // clamped into the cache, so a stale table cannot send a load outside it
 __device__ __forceinline__ long long cache_row(const IdxParams& p, const int* tab, int j) {
-    const int lb = block_of(p, j);
+    const int lb = block_of(j, p.bs, p.bs_shift);
     const unsigned blk = min((unsigned)tab[lb], (unsigned)(p.nb - 1));
     return (long long)blk * p.bs + (j - lb * p.bs);
 }
@@ -161,8 +143,10 @@ __global__ void __launch_bounds__(256) fa_mla_indexer_logits_kernel(const IdxPar
     const int chunk = bid % p.chunks, rest = bid / p.chunks;
     const int grp = rest % p.groups, b = rest / p.groups;
 
-    int L, s, n;
-    seq_of(p, b, L, s, n);
+    // aule_mla_paged_desc's clamps (fa_device.h): L_b, s_b, n_b
+    const int L = seq_len(p.ctx, b, p.W);
+    const SeqRange own_rows = seq_range_or_row(p.cu, b, p.T, p.max_sq);   // (a null cu: b < T, the host checks)
+    const int s = own_rows.s, n = own_rows.n;
     const int i0 = grp * kIdxGroup;
     const int live = min(kIdxGroup, n - i0);
     if (live <= 0) return;
@@ -292,8 +276,10 @@ __global__ void __launch_bounds__(kTopkThreads) fa_mla_indexer_topk_kernel(const
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = (int)blockIdx.x / p.max_sq, i = (int)blockIdx.x % p.max_sq;
-    int L, s, n;
-    seq_of(p, b, L, s, n);
+    // aule_mla_paged_desc's clamps (fa_device.h): L_b, s_b, n_b
+    const int L = seq_len(p.ctx, b, p.W);
+    const SeqRange own_rows = seq_range_or_row(p.cu, b, p.T, p.max_sq);   // (a null cu: b < T, the host checks)
+    const int s = own_rows.s, n = own_rows.n;
     if (i >= n) return;
     int* out = p.out + (long long)(s + i) * p.topk;
     const int V = L - n + i + 1;   // visible keys: positions 0 .. V - 1
@@ -413,7 +399,7 @@ __global__ void __launch_bounds__(kTopkThreads) fa_mla_indexer_topk_kernel(const
                 const int j = j0 + e;
                 int v = j;
                 if (!p.positions) {
-                    const int lb = block_of(p, j);
+                    const int lb = block_of(j, p.bs, p.bs_shift);
                     v = (int)((unsigned)tab[lb] * (unsigned)p.bs + (unsigned)(j - lb * p.bs));
                 }
                 if (at < (unsigned)k) out[at] = v;
@@ -425,15 +411,6 @@ __global__ void __launch_bounds__(kTopkThreads) fa_mla_indexer_topk_kernel(const
         eq_run += total >> 16;
         if (gt_run + min(eq_run, need_eq) >= (unsigned)k) break;   // (uniform: the list is complete)
     }
-}
-
-int shift_of(int bs) { return (bs & (bs - 1)) == 0 ? __builtin_ctz((unsigned)bs) : -1; }
-
-template <class T>
-int launch_logits(const IdxParams& p, long long grid, bool fp8, hipStream_t stream) {
-    if (fp8) hipLaunchKernelGGL((fa_mla_indexer_logits_kernel<T, true>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((fa_mla_indexer_logits_kernel<T, false>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -478,9 +455,11 @@ int launch_mla_indexer_logits(const MlaIndexerArgs& a, const MlaIndexerPlan& pla
     p.max_blocks = a.max_blocks; p.max_sq = a.max_seqlen_q;
     p.W = (int)W;
     p.groups = plan.token_groups; p.chunks = plan.key_chunks; p.chunk_keys = plan.chunk_keys;
-    if (a.dtype == kBF16) return launch_logits<Bf16Traits>(p, plan.grid, fp8, stream);
-    if (a.dtype == kF16) return launch_logits<F16Traits>(p, plan.grid, fp8, stream);
-    return -1;
+    return dispatch_16bit(a.dtype, [&](auto t) {
+        if (fp8) hipLaunchKernelGGL((fa_mla_indexer_logits_kernel<decltype(t), true>), dim3((unsigned)plan.grid), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((fa_mla_indexer_logits_kernel<decltype(t), false>), dim3((unsigned)plan.grid), dim3(256), 0, stream, p);
+        return (int)hipGetLastError();
+    });
 }
 
 int launch_mla_indexer_topk(const MlaIndexerTopkArgs& a, hipStream_t stream) {

@@ -48,7 +48,7 @@ struct PagedTile {
             const int kv = k0 + (tid + 256 * i) / C::CPR;
             long long at = 0;
             if (kv < kend) {
-                const int lb = p.bs_shift >= 0 ? kv >> p.bs_shift : kv / p.bs;
+                const int lb = block_of(kv, p.bs, p.bs_shift);
                 at = (long long)tab[lb] * p.bs + (kv - lb * p.bs);
             }
             slot[i] = at;

@@ -1,5 +1,5 @@
 // fa_varlen_common.h -- what the variable-length kernels share (fa_fwd_varlen_gfx950.hip, fa_bwd_varlen_gfx950.hip):
-// the clamp of a sequence's bounds, the LDS pitches per head_dim, a tile of rows on its way from global memory to LDS, and the work
+// the LDS pitches per head_dim, a tile of rows on its way from global memory to LDS, and the work
 // decomposition and K / V tile source of the forward and the dQ kernel (QueryBlock, KeyTiles), and the dQ kernel's body
 // (ragged_dq_body), which the MLA 192 / 128 backward runs too.  The body is parameterised by a shape S: widths DQK (q / key rows)
 // and DV (value / output rows), the key-tile source S::Tiles(p, x, hk) with load(k0, tid) and store(Ks, kpitch, Vs, vpitch, tid),
@@ -23,16 +23,7 @@ struct VarlenCfg : PrefillCfg<D> {
     static constexpr int PAT = PrefillCfg<D>::PT + 16;
 };
 
-// Sequence b of a packed axis of `total` rows: first row s and length n = min(e - s, cap), every value clamped so that
-// [s, s + n) lies inside [0, total) whatever cu holds.
-struct SeqRange {
-    int s, n;
-};
-__device__ __forceinline__ SeqRange seq_range(const int* cu, int b, int total, int cap) {
-    const int s = min(max(cu[b], 0), total);
-    const int e = min(max(cu[b + 1], s), total);
-    return SeqRange{s, min(e - s, cap)};
-}
+// (the clamp of a sequence's bounds, seq_range: fa_device.h, beside the other clamps of the contract)
 
 // key j < L visible to the query at position pos
 __device__ __forceinline__ bool varlen_visible(int pos, int j, int L, bool causal, int window) {

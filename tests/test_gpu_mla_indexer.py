@@ -50,14 +50,16 @@ class Tables:
     whose used blocks are a shuffle of the pool and whose other entries are poison.  full_table: every entry of those sequences is a
     real block (for lengths beyond the capacity, which clamp to it)."""
 
-    def __init__(self, seed, bs, ctx, ns=None, max_sq=None, cap=None, extra_rows=0, full_table=()):
+    def __init__(self, seed, bs, ctx, ns=None, max_sq=None, cap=None, extra_rows=0, full_table=(), cu=None):
         rng = np.random.RandomState(seed)
         self.bs, self.B = bs, len(ctx)
         self.ctx = np.asarray(ctx, dtype=np.int32)
         top = max([int(c) for b, c in enumerate(ctx) if b not in full_table] + [1])
         self.mb = -(-(cap if cap is not None else top) // bs)
         self.W = self.mb * bs
-        if ns is None:
+        if cu is not None:   # offsets as given (hostile values included) over extra_rows rows
+            self.cu, self.T, self.max_sq = np.asarray(cu, dtype=np.int32), extra_rows, max_sq
+        elif ns is None:
             self.cu, self.T, self.max_sq = None, self.B + extra_rows, 1
         else:
             self.cu = np.concatenate([[0], np.cumsum(ns)]).astype(np.int32)
@@ -392,7 +394,7 @@ class TopkLaunch:
         self.cu = a.view("cu", torch.int32, (cu.size,)) if tab.cu is not None else None
         self.idx = a.view("idx", torch.int32, (tab.T, topk))
 
-    def run(self, positions):
+    def run(self, positions, fill=POISON):
         from aule import _capi
         torch, a, tab = self.torch, self.arena, self.tab
         lib = _capi.get_lib()
@@ -404,7 +406,7 @@ class TopkLaunch:
         d.stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         d.logits, d.block_tables, d.context_lens, d.indices = a.ptr("lg"), a.ptr("bt"), a.ptr("cl"), a.ptr("idx")
         d.cu_seqlens_q = a.ptr("cu") if tab.cu is not None else None
-        a.fill(POISON)
+        a.fill(fill)
         rc = lib.aule_mla_indexer_topk_ex(ctypes.byref(d))
         torch.cuda.synchronize()
         assert rc == 0, (rc, lib.aule_get_error())
@@ -469,6 +471,28 @@ def test_topk_block_sizes_both_outputs_and_a_ragged_batch(bs, mb):
     logits = np.stack([hand_made(rng, ROW_KINDS[(r * 3 + 1) % 8], W) for r in range(tab.T)])
     for topk in (1, 16, 64, W // 2 + 1, W, W + 5):
         check_topk(torch, tab, logits, topk, "bs=%d topk=%d" % (bs, topk), pad=5)
+
+
+def test_topk_hostile_offsets_and_lengths():
+    """cu_seqlens_q = [-5, 2, 9, 3] (negative, past the end, decreasing) and context_lens = [-7, 1000, 5] over 6 rows of 2 blocks of 16:
+    after the clamps sequence 0 owns rows 0 - 1 with no key (lists of -1), sequence 1 rows 2 - 4 with the table's 32 keys, sequence 2 no
+    row, and row 5 belongs to nobody.  Both outputs against the contract; the list is pre-filled once with 0xFF and once with 0x00, so
+    that row 5 shows the fill's bytes both times (-1 is also the pad value); guards intact and inputs unchanged in every run."""
+    import torch
+    from hostile import FRIENDLY
+    tab = Tables(950, 16, [-7, 1000, 5], max_sq=3, cap=32, extra_rows=6, full_table=(1,), cu=[-5, 2, 9, 3])
+    assert (tab.T, tab.B, tab.mb, tab.W) == (6, 3, 2, 32) and tab.seqs == [(0, 0, 2), (32, 2, 3), (5, 6, 0)]
+    assert [(r, b, p) for r, b, p in tab.rows()] == [(0, 0, -2), (1, 0, -1), (2, 1, 29), (3, 1, 30), (4, 1, 31)]
+    rng = np.random.RandomState(951)
+    logits = np.stack([hand_made(rng, ROW_KINDS[(r * 3 + 1) % 8], tab.W) for r in range(tab.T)])
+    run = TopkLaunch(torch, tab, logits, 4)
+    for positions in (False, True):
+        want = topk_contract(logits, tab, 4, positions)
+        assert (want[:2] == -1).all() and (want[2:5] >= 0).all()
+        for fill, word in ((POISON, -1), (FRIENDLY, 0)):
+            got = run.run(positions, fill).numpy()
+            assert np.array_equal(got[:5], want[:5]), (positions, got, want)
+            assert (got[5] == word).all(), "row 5 belongs to no sequence and was written: %s" % got[5]
 
 
 # ------------------------------------------------------------------------------------------------------------------------ 3. end to end

@@ -255,16 +255,17 @@ def test_hostile_prefix_len_behaves_as_its_clamp(hostile, like, oracle_mod):
     _judge(c, got[0], got[1], oracle_mod, hostile, "prefix_len %d" % hostile)
 
 
-def _arena_run(torch, c, P, nan_outside=False):
+def _arena_run(torch, c, P, nan_outside=False, cu=None, cl=None):
     """through the C entry with every tensor, the workspace included, inside one poisoned arena; returns (arena, inputs kept,
-    out, lse)"""
+    out, lse).  cu, cl: in place of the problem's offsets and lengths"""
     from aule import _capi
     lib = _capi.get_lib()
     p = c.p
     q = p.q.copy()
     if nan_outside:
-        q[~p.owned()] = np.nan
-    tensors = {"q": q, "bt": p.bt, "cl": p.cl, "cu": p.cu, "pbt": c.table(P), "plen": np.array([P], dtype=np.int32)}
+        q[~p.owned(cu=cu, cl=cl)] = np.nan
+    cu, cl = (np.asarray(have if given is None else given, dtype=np.int32) for have, given in ((p.cu, cu), (p.cl, cl)))
+    tensors = {"q": q, "bt": p.bt, "cl": cl, "cu": cu, "pbt": c.table(P), "plen": np.array([P], dtype=np.int32)}
     dt = torch_dtype(p.dtype)
     dev = {k: torch.from_numpy(v) for k, v in tensors.items()}
     dev["q"] = dev["q"].to(dt)
@@ -316,6 +317,28 @@ def test_inside_a_poisoned_arena_with_rows_of_no_sequence(kind, oracle_mod):
     free = torch.from_numpy(~own).cuda()
     assert bool((out.view(torch.int16)[free] == -1).all()) and bool((lse.view(torch.int32)[free] == -1).all())
     _judge(c, out, lse, oracle_mod, 100, "arena, lead 5, tail 40")
+
+
+def test_hostile_offsets_and_lengths_inside_a_poisoned_arena(oracle_mod):
+    """cu_seqlens_q negative, past the end and decreasing, context_lens negative, INT32_MIN and far beyond the table (every table entry a
+    real block), through the shared-prefix pass, the prefill AND the merge kernel, which clamps for itself.  After the clamps sequence 0
+    owns rows 0 .. 2 with no own key (negative positions: zeros and -inf, whatever the prefix holds), sequence 2 rows 3 .. 142 with the
+    table's 208 keys, the others nothing; the 46 rows behind them belong to nobody and keep their poison, the guards stay intact."""
+    import torch
+    p = Ragged(76, "bf16", "16", 8, 2, 64, 16, [3, 0, 140, 1], [70, 9, 140, 200], tail=45, table_lens=[208] * 4, extra_cols=0)
+    c = Cascade(p, 77, keys=100)
+    cu, cl = [-5, 3, 3, p.T + 7, 20], [-7, 9, 100000, INT32_MIN]
+    assert p.T == 189 and p.sequences(cu=cu, cl=cl) == [(0, 0, 3, 0), (1, 3, 0, 9), (2, 3, 140, 208), (3, 189, 0, 0)]
+    a, kept, out, lse = _arena_run(torch, c, 100, nan_outside=True, cu=cu, cl=cl)
+    assert a.guards_intact(), a.damage()
+    for name, was in kept.items():
+        assert a.unchanged(name, was), name
+    own = p.owned(cu=cu, cl=cl)
+    assert own.sum() == 143 and own[:143].all()
+    free = torch.from_numpy(~own).cuda()
+    assert bool((out.view(torch.int16)[free] == -1).all()) and bool((lse.view(torch.int32)[free] == -1).all())
+    assert bool((out[:3] == 0).all()) and bool(torch.isneginf(lse[:3]).all())
+    _judge(c, out, lse, oracle_mod, 100, "arena, hostile offsets and lengths", cu=cu, cl=cl)
 
 
 @pytest.mark.parametrize("kind", ["16", "fp8"])
