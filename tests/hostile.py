@@ -131,6 +131,7 @@ FWD_CASES = [
     (8, "fp16", 1, 4, 2, 515, 771, 64, 0, -1, "rope"),
     (9, "fp16", 1, 4, 2, 257, 333, 256, 2, -1, ""),
     (9, "bf16", 1, 4, 1, 65, 1025, 256, 1, 100, ""),
+    (9, "bf16", 2, 6, 2, 130, 129, 256, 0, 64, ""),          # a window without a causal mask: two query blocks, a ragged third key tile
     # route 4 is taken from the tiled split only with 32 units, at most 16 packed rows and 100 MB of K + V (short_query_route,
     # fa_fwd_gfx950.hip): 2 * 32 * Sk * 128 * 2 B >= 100e6 from Sk = 6104 on; 6105 is the first odd length
     (4, "bf16", 32, 1, 1, 1, 6105, 128, 0, -1, ""),
@@ -141,6 +142,7 @@ BWD_CASES = [
     (32, "fp32", 2, 8, 2, 333, 700, 64, 1, -1, ""),          # small-grid pieces
     (128 | 32, "fp32", 1, 2, 1, 70, 150, 256, 1, -1, ""),
     (128, "bf16", 1, 4, 2, 70, 150, 256, 2, -1, ""),
+    (128, "fp16", 1, 6, 2, 200, 300, 256, 1, 100, ""),       # two query blocks, three key blocks, a group of three, a window
     (8 | 16, "bf16", 1, 4, 4, 197, 203, 32, 1, -1, ""),
     (8 | 16, "bf16", 1, 4, 2, 130, 70, 128, 1, -1, ""),
     (8 | 16, "bf16", 1, 8, 2, 333, 1100, 128, 2, 300, ""),

@@ -2,6 +2,8 @@
 
 Judges: the fp64 oracle (fwd_f64 / bwd_f64 on small shapes, fwd_rows_f64 / bwd_head_f64 at full size).  Bounds: the existing ones
 of tests/util.py -- assert_close_rows / fwd_tol and LSE_TOL for the forward, BWD_TOL for the gradients (as test_gpu_bwd.py).
+Random shapes at the kernels' tile seams, hard data and the other padded sizes: the d256 and pad kinds of tools/fuzz_parity.py
+(tests/test_gpu_fuzz.py).
 """
 import ctypes
 import math
@@ -126,6 +128,67 @@ def test_forward_and_lse(torch_cuda, oracle_mod, case):
     assert_close(got_l[~empty], ref_l[~empty], LSE_TOL[dtype], LSE_TOL[dtype], "LSE")
     if dtype != "fp32":
         assert _fwd_route(dtype, B, Hq, Hkv, Sq, Sk, causal, W, scale) == ROUTE_D256
+
+
+_PREFIX = {}
+
+
+def _prefix_problem(torch, dtype):
+    """B1 H2 kv1 Sq = Sk = 300, top-left causal: the inputs on the device and the long call's (out, lse), computed once per dtype"""
+    from aule import _torch as at
+    if dtype not in _PREFIX:
+        q, k, v, _ = _inputs(8, 1, 2, 1, 300, 300, 256, dtype)
+        t = tuple(_dev(torch, x, dtype) for x in (q, k, v))
+        out, lse = at.fwd_raw(*t, 1, 1.0 / 16.0, want_lse=True)
+        torch.cuda.synchronize()
+        _PREFIX[dtype] = (t, out, lse)
+    return _PREFIX[dtype]
+
+
+@pytest.mark.parametrize("n", [65, 128, 129])
+@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
+def test_top_left_causal_prefix_is_the_short_call_bit_for_bit(torch_cuda, dtype, n):
+    """Under the top-left rule rows 0 .. n - 1 see keys 0 .. n - 1 only, so the first n rows of the 300 x 300 call are the call on the first
+    n rows and keys.  The long call walks more key tiles for those rows' query block (kend follows the block's last row: fa_fwd_d256_gfx950.hip),
+    every one of them fully masked for these rows: a masked tile leaves m, l and O as they are (alpha = exp2(0) = 1, every weight
+    exp2(-inf) = 0), so the bits agree -- n = 65: the ragged second key tile; 128: a whole query block; 129: one row of the second block,
+    whose long call runs four key tiles against three."""
+    from aule import _torch as at
+    torch = torch_cuda
+    (tq, tk, tv), out, lse = _prefix_problem(torch, dtype)
+    o, l = at.fwd_raw(tq[:, :, :n].contiguous(), tk[:, :, :n].contiguous(), tv[:, :, :n].contiguous(), 1, 1.0 / 16.0, want_lse=True)
+    torch.cuda.synchronize()
+    view = torch.int32 if dtype == "fp32" else torch.int16
+    assert torch.equal(o.view(view), out[:, :, :n].contiguous().view(view))
+    assert torch.equal(l.view(torch.int32), lse[:, :, :n].contiguous().view(torch.int32))
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
+def test_online_softmax_rescale_is_exercised_at_d256(torch_cuda, oracle_mod, dtype):
+    """The twin of test_gpu_fwd.py::test_online_softmax_rescale_is_exercised: a key in the LAST 64-key tile of row 295 (key 290 of 300)
+    whose logit (24 in natural units) towers over the row's, so that the running maximum jumps after O and l were accumulated, and a key
+    with a large negative logit; causal and not.  On the reference alone the spike moves row 295 by more than 20 x the tolerance."""
+    from aule import _torch as at
+    rng = np.random.RandomState(5)
+    q = rng.randn(1, 2, 300, 256).astype(np.float32) * 0.5
+    k = rng.randn(1, 2, 300, 256).astype(np.float32) * 0.5
+    v = rng.randn(1, 2, 300, 256).astype(np.float32)
+    plain = quantize(k.copy(), dtype)      # (a copy: for fp32 the round trip hands the same memory back)
+    k[:, :, 290, :] = 6.0 * q[:, :, 295, :]
+    k[:, :, 100, :] = -4.0 * q[:, :, 120, :]
+    q, k, v = (quantize(x, dtype) for x in (q, k, v))
+    atol, rtol = fwd_tol(dtype, np.abs(v).max())
+    for causal in (True, False):
+        case = (dtype, 1, 2, 2, 300, 300, causal, -1, None)
+        out, lse = at.fwd_raw(*(_dev(torch_cuda, x, dtype) for x in (q, k, v)), at.causal_code(causal), 1.0 / 16.0, want_lse=True)
+        torch_cuda.cuda.synchronize()
+        ref, ref_lse = oracle_mod.fwd_f64(q, k, v, causal, None)
+        without, _ = oracle_mod.fwd_f64(q, plain, v, causal, None)
+        assert (np.abs(without[:, :, 295] - ref[:, :, 295]) > 20 * (atol + rtol * np.abs(ref[:, :, 295]))).any()
+        assert_close(out.float().cpu().numpy(), ref, atol, rtol, "spike %s causal=%s" % (dtype, causal))
+        assert_close(lse.cpu().numpy(), ref_lse, LSE_TOL[dtype] * 4, 1e-5, "spike lse")
+        if dtype != "fp32":
+            assert _fwd_route(*case) == ROUTE_D256
 
 
 def _check_grad(got, ref, dtype, what):
