@@ -210,6 +210,41 @@ def flash_attention_paged_prefill(q, k_cache, v_cache, block_tables, context_len
                          window_size=window_size, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
 
 
+def flash_attention_paged_prefill_fp8mma(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None,
+                                         window_size=-1, k_scale=None, v_scale=None, return_lse=False):
+    """flash_attention_paged_prefill over a float8_e4m3fn cache with BOTH matrix products in FP8: the cache's codes are multiplied as
+    they are (gfx950's block-scaled e4m3 MFMA at scale 1), nothing is turned back into 16 bits.  Not in the reference.  Opt-in: nothing
+    routes here by itself.
+
+    Every argument, clamp, mask and result as flash_attention_paged_prefill, except: the caches must be float8_e4m3fn, k_scale and
+    v_scale must be given, head_dim is 64 or 128, and there are no sink or tree twins.  What differs is the arithmetic.  Each row
+    (token, head) of q is quantised in the kernel by the rule of quantize_rows_fp8 -- codes of q / s with s = amax|q| / 448 -- and s joins
+    the score scale; the softmax weights are rounded to e4m3 after a factor 2^8, which cancels in out and is taken out of lse.  lse is
+    exactly that of the quantised q over the dequantised cache (the weights' rounding never reaches it); out carries the weights' e4m3
+    rounding (2^-4 relative per weight, averaged over the keys) on top.  Use it where the FP8 cache's own accuracy is already accepted.
+    Argument errors are ValueErrors raised before the device is touched; CPU tensors raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_prefill_fp8mma
+    return paged_prefill_fp8mma(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=max_seqlen_q, scale=scale,
+                                window_size=window_size, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
+
+
+def quantize_rows_fp8(x):
+    """The per-row e4m3 quantisation flash_attention_paged_prefill_fp8mma applies to q, stated in torch ops (any device, the CPU included):
+    over the last axis, a = max |x|, s = a / 448 in fp32 (1 where a = 0), codes = (x.float() / s) as float8_e4m3fn (round to nearest even;
+    |x / s| <= 448 up to one fp32 rounding, which rounds back to 448).  Returns (codes, scales): codes of x's shape, scales fp32 [..., 1];
+    codes.float() * scales is what the kernel multiplies with."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import quantize_rows_fp8 as impl
+    return impl(x)
+
+
 def flash_attention_paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tables, context_lens, cu_seqlens_q,
                                   max_seqlen_q=None, scale=None, k_scale=None, v_scale=None, return_lse=False):
     """flash_attention_paged_prefill for a batch whose sequences share a prefix (a system prompt, a few-shot header): the
@@ -909,7 +944,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

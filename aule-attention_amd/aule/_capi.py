@@ -612,6 +612,7 @@ SIGNATURES = [
     ("aule_attention_paged_query_sink_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedQuerySinkDesc)]),
     ("aule_attention_paged_query_tree_ex", _I32, [ctypes.POINTER(PagedQueryTreeDesc)]),
     ("aule_attention_paged_prefill_tree_ex", _I32, [ctypes.POINTER(PagedPrefillTreeDesc)]),
+    ("aule_attention_paged_prefill_fp8mma_ex", _I32, [ctypes.POINTER(PagedPrefillDesc)]),
     ("aule_attention_paged_query_tree_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedQueryTreeDesc)]),
     ("aule_attention_merge_states_ex", _I32, [ctypes.POINTER(MergeStatesDesc)]),
     ("aule_attention_mla_prefill_ex", _I32, [ctypes.POINTER(MlaPrefillDesc)]),

@@ -1233,6 +1233,47 @@ def paged_prefill(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q,
     return result
 
 
+FP8MMA_HEAD_DIMS = (64, 128)
+
+
+def quantize_rows_fp8(x):
+    """aule.quantize_rows_fp8: per-row e4m3 codes and fp32 scales over the last axis, the rule csrc/fa_fwd_paged_prefill_fp8mma_gfx950.hip
+    applies to q in registers (a true fp32 division by s = amax / 448, s = 1 for a zero row, round to nearest even)."""
+    if not torch.is_tensor(x) or not x.is_floating_point() or x.dim() < 1:
+        raise ValueError("quantize_rows_fp8 takes a floating-point tensor with at least one axis")
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1, keepdim=True)
+    scales = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    return (xf / scales).clamp(-448.0, 448.0).to(torch.float8_e4m3fn), scales
+
+
+def paged_prefill_fp8mma(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None, window_size=-1,
+                         k_scale=None, v_scale=None, return_lse=False):
+    """paged_prefill over an FP8 cache with both matrix products in FP8 (aule.flash_attention_paged_prefill_fp8mma states the
+    arithmetic); csrc/fa_fwd_paged_prefill_fp8mma_gfx950.hip behind aule_attention_paged_prefill_fp8mma_ex.  The twin's steps and rules,
+    plus this entry's own three: float8_e4m3fn caches, both scales given, head_dim 64 or 128."""
+    Hkv, fp8 = _ragged_kind("prefill", q, k_cache, v_cache, k_scale, v_scale)
+    if not fp8:
+        raise ValueError(f"flash_attention_paged_prefill_fp8mma multiplies float8_e4m3fn codes: the caches must be float8_e4m3fn, got "
+                         f"{k_cache.dtype} (a 16-bit cache: flash_attention_paged_prefill)")
+    if k_scale is None or v_scale is None:
+        raise ValueError("flash_attention_paged_prefill_fp8mma needs k_scale and v_scale, the scales the cache was written with "
+                         "(flash_attention_paged_prefill takes 1.0 for a missing one)")
+    if q.shape[-1] not in FP8MMA_HEAD_DIMS:
+        raise ValueError(f"head_dim must be one of {FP8MMA_HEAD_DIMS} for flash_attention_paged_prefill_fp8mma, got {q.shape[-1]} "
+                         "(head_dim 32: flash_attention_paged_prefill)")
+    q, q_stride = _ragged_queries("prefill", q, fp8, Hkv, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, k_scale, v_scale)
+    lib = _capi.get_lib()
+    d = _capi.PagedPrefillDesc()
+    result, held = _ragged_problem("prefill", d, q, q_stride, fp8, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q,
+                                   scale, return_lse)
+    if held is not None:
+        d.window_size = _window_arg(window_size)
+        held.append(_attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device))
+        _capi.check(lib.aule_attention_paged_prefill_fp8mma_ex(ctypes.byref(d)), "aule_attention_paged_prefill_fp8mma_ex")
+    return result
+
+
 def paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None,
                   scale=None, k_scale=None, v_scale=None, return_lse=False):
     """Paged cascade: paged_prefill for a batch whose sequences share a prefix (a system prompt, a few-shot header), the prefix

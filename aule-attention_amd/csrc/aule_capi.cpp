@@ -1378,7 +1378,10 @@ static void fill_paged_prefill_args(const aule_paged_prefill_desc* d, aule_hip::
 
 // (`d` passed paged_prefill_desc_error with its kind's size; `sinks` / `tree_mask`: the sink kind's logits and the tree kind's words, checked
 // by the caller)
-static int32_t paged_prefill_launch(const aule_paged_prefill_desc* d, const float* sinks, const char* what, const int64_t* tree_mask = nullptr) {
+// `launch`: the kernel family behind the entry (the FP8-product twin passes its own)
+using PagedPrefillLauncher = int (*)(const aule_hip::PagedPrefillArgs&, hipStream_t);
+static int32_t paged_prefill_launch(const aule_paged_prefill_desc* d, const float* sinks, const char* what, const int64_t* tree_mask = nullptr,
+                                    PagedPrefillLauncher launch = aule_hip::launch_paged_prefill) {
     if (!initialised()) return -1;
     aule_hip::PagedPrefillArgs a;
     fill_paged_prefill_args(d, a);
@@ -1391,7 +1394,7 @@ static int32_t paged_prefill_launch(const aule_paged_prefill_desc* d, const floa
     DeviceGuard g(d->device);
     int rc = ensure_configured();
     if (rc) return rc;
-    return launched(what, aule_hip::launch_paged_prefill(a, (hipStream_t)d->stream));
+    return launched(what, launch(a, (hipStream_t)d->stream));
 }
 
 int32_t aule_attention_paged_prefill_ex(const aule_paged_prefill_desc* d) {
@@ -1465,6 +1468,27 @@ int32_t aule_attention_paged_prefill_tree_ex(const aule_paged_prefill_tree_desc*
     }
     if (ragged_nothing_to_do(x)) return 0;
     return paged_prefill_launch(x, nullptr, "Paged prefill tree attention", d->tree_mask);
+}
+
+// The FP8-product twin of the paged prefill: the same descriptor through the same checker, then this kind's own two
+// rules -- an FP8 cache is the only kind, head_dim 64 or 128 -- and its own launcher.  Host logic first, as above.
+static const char kFp8mmaCache[] = "cache_dtype must be AULE_KV_CACHE_FP8_E4M3: this entry multiplies the cache's e4m3fn codes as they are "
+                                   "(a 16-bit cache: aule_attention_paged_prefill_ex)";
+
+int32_t aule_attention_paged_prefill_fp8mma_ex(const aule_paged_prefill_desc* d) {
+    RoctxRange range("aule.paged_prefill_fp8mma");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    const char* why = paged_prefill_desc_error(d, text);
+    if (why == nullptr && d->cache_dtype != AULE_KV_CACHE_FP8_E4M3) why = kFp8mmaCache;
+    if (why == nullptr && d->head_dim != 64 && d->head_dim != 128)
+        why = reasonf(text, "head_dim %u unsupported by the FP8-product prefill (64 or 128; head_dim 32: aule_attention_paged_prefill_ex)", d->head_dim);
+    if (why != nullptr) {
+        set_error("Paged prefill FP8-product attention failed: %s", why);
+        return -3;
+    }
+    if (ragged_nothing_to_do(d)) return 0;
+    return paged_prefill_launch(d, nullptr, "Paged prefill FP8-product attention", nullptr, aule_hip::launch_paged_prefill_fp8mma);
 }
 
 // (`d` passed paged_cascade_desc_error) the two kernels' arguments: the suffix pass is the prefill's, read through the common prefix,

@@ -270,6 +270,10 @@ struct PagedPrefillArgs {
 // workgroups of the launch: ceil(min(max_seqlen_q, T) * (Hq / Hkv) / 128) x Hkv x B (tests, tools)
 long long paged_prefill_grid(const PagedPrefillArgs& a);
 int launch_paged_prefill(const PagedPrefillArgs& a, hipStream_t stream);   // -1: unsupported arguments
+// The same over an FP8 cache with both matrix products in FP8 (fa_fwd_paged_prefill_fp8mma_gfx950.hip): q is quantised per
+// row in the kernel, K / V codes are multiplied as they are.  Same arguments, clamps and grid; -1 also for cache_kind != kCacheFp8E4M3,
+// null scales, sinks, tree_mask and D outside {64, 128}.
+int launch_paged_prefill_fp8mma(const PagedPrefillArgs& a, hipStream_t stream);
 
 // Shared-prefix pass of the paged cascade (fa_fwd_paged_shared_prefix_gfx950.hip): every one of the T tokens of q sees the first
 // P = clamp(prefix_len[0], 0, max_prefix_blocks * block_size) keys of ONE block table, no mask, no per-sequence data.  The rows of

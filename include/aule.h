@@ -328,6 +328,18 @@ typedef struct aule_paged_prefill_desc {
 /* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
 int32_t aule_attention_paged_prefill_ex(const aule_paged_prefill_desc* desc);
 
+/* Paged prefill with FP8 matrix products (additive): aule_attention_paged_prefill_ex over an FP8 cache with BOTH products in e4m3 --   */
+/* the cache's codes are multiplied as they are (v_mfma_scale_f32_32x32x64_f8f6f4, block scales 1.0), nothing is turned back into     */
+/* 16-bit.  The same descriptor, the same rules, clamps, masks, grid and memory-safety contract; what differs is the arithmetic:      */
+/* each row (token, head) of q is quantised in the kernel to e4m3 with its own scale amax|q| / 448 (1 for a zero row), which joins    */
+/* the score scale, and the softmax weights are rounded to e4m3 after a factor 2^8 (the row's largest weight is 256; the factor       */
+/* cancels in out and is taken out of lse).  lse is that of the quantised q: it never sees the rounding of the weights.  out carries  */
+/* the e4m3 rounding of q and of the weights (2^-4 relative per weight) on top of the cache's own: use it where the FP8 cache's       */
+/* accuracy is already accepted.  Refused (-3, with a reason): cache_dtype other than AULE_KV_CACHE_FP8_E4M3, head_dim 32 (64 and 128 */
+/* are built), null scales.  No sinks, no tree masks.  Opt-in: nothing routes here by itself.  Nothing-to-do answers (0) and refusals  */
+/* come before the device is needed, as for the twin.                                                                                 */
+int32_t aule_attention_paged_prefill_fp8mma_ex(const aule_paged_prefill_desc* desc);
+
 /* Paged CASCADE (additive): the paged prefill for a batch whose sequences share a prefix -- a system prompt, a few-shot header.   */
 /* The shared keys live behind ONE table, prefix_block_table [max_prefix_blocks] int32, and are read once for the whole batch;     */
 /* block_tables[b] lists only the sequence's OWN blocks and context_lens[b] counts only its OWN keys, the new tokens included.     */
