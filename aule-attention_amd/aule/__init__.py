@@ -220,7 +220,8 @@ def flash_attention_paged_prefill_fp8mma(q, k_cache, v_cache, block_tables, cont
     v_scale must be given, head_dim is 64 or 128, and there are no sink or tree twins.  What differs is the arithmetic.  Each row
     (token, head) of q is quantised in the kernel by the rule of quantize_rows_fp8 -- codes of q / s with s = amax|q| / 448 -- and s joins
     the score scale; the softmax weights are rounded to e4m3 after a factor 2^8, which cancels in out and is taken out of lse.  lse is
-    exactly that of the quantised q over the dequantised cache (the weights' rounding never reaches it); out carries the weights' e4m3
+    that of the quantised q over the dequantised cache (the weights' rounding never reaches it) up to the matrix instruction's accumulation
+    of the scores: it keeps about 20 bits below the largest product q_d k_d of a row, 2^-12 of that product at head_dim 128; out carries the weights' e4m3
     rounding (2^-4 relative per weight, averaged over the keys) on top.  Use it where the FP8 cache's own accuracy is already accepted.
     Argument errors are ValueErrors raised before the device is touched; CPU tensors raise AuleError."""
     try:
@@ -366,7 +367,7 @@ def flash_attention_mla_sparse(q, kv_cache, indices, scale=None, return_lse=Fals
     tensors that require grad are refused.
     Out of scope: the indexer itself lives in aule.mla_indexer (its result is `indices`), a causal rule inside the kernel, packing several tokens' heads
     into one row block when Hq < 64, logical-position indices resolved through a block table inside the kernel, a backward,
-    sink logits or tree masks with a list, a fuzz_serving kind."""
+    sink logits or tree masks with a list."""
     try:
         import torch  # noqa: F401
     except ImportError as e:

@@ -353,3 +353,170 @@ def test_the_rounding_model_on_the_two_draws_that_found_it():
          'max_sq': None, 'max_sk': None, 'ns': [33, 32, 129, 2, 0], 'ls': [2, 63, 127, 129, 128]}
     _, _, _, floors, f = fz.mlapf_reference(c, 37085)
     assert f["binds"] and 1.0e-2 < floors[0]["dk_pe"] < 1.2e-2, (f, floors[0])
+
+
+# ---- the three kinds added for the sparse MLA, the MLA indexer and the FP8-product prefill
+NEW_KINDS = ("sparse", "indexer", "fp8mma")
+
+# ... and of the next three, taken at the commit before the sparse, indexer and fp8mma kinds were added
+OLDER_LISTS = dict(OLD_LISTS, sinks="cac82a517105e6a5", tree="5a4d03920c452911", mlapf="40f4e698ee4e5d04")
+
+
+def test_the_new_slices_are_the_sizes_the_suite_promises():
+    assert {k: fz.SLICES[k][0] for k in NEW_KINDS} == dict(sparse=24, indexer=20, fp8mma=20)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_seven_older_kinds_draw_the_lists_they_drew(kind):
+    assert hashlib.sha256(repr(_draws(kind)).encode()).hexdigest()[:16] == OLDER_LISTS[kind]
+
+
+@pytest.mark.parametrize("kind", NEW_KINDS)
+def test_every_new_kind_draws_both_dtypes_plain_values_and_the_same_list_twice(kind):
+    cfgs = _draws(kind)
+    assert cfgs == _draws(kind)
+    assert {c["dtype"] for c in cfgs} == {"bf16", "fp16"}
+    for c in cfgs:
+        assert eval(repr(c), {}) == c
+
+
+@functools.lru_cache(maxsize=None)
+def _sparse_refs():
+    """(info, facts) of the reference side of every draw of the sparse slice, computed once"""
+    return [fz.sparse_reference(c, fz.SEED0["sparse"] + i)[2::2] for i, c in enumerate(_draws("sparse"))]
+
+
+def test_sparse_slice():
+    cfgs = _draws("sparse")
+    refs = _sparse_refs()
+    assert {c["cache"] for c in cfgs} == {"16", "fp8"}
+    hq = {c["Hq"] for c in cfgs}
+    assert len(hq) >= 6 and any(h <= 16 for h in hq) and any(17 <= h <= 64 for h in hq) and any(65 <= h <= 127 for h in hq) and 128 in hq, hq
+    assert all(c["Hq"] in fz.SPARSE_HEADS and c["topk"] in fz.SPARSE_TOPKS + [192] and 1 <= c["T"] <= 6 for c in cfgs)
+    assert sum(1 for info, _ in refs if info["planned"] > 1) >= 5, [info["planned"] for info, _ in refs]      # (the plan hook: host-only)
+    assert sum(1 for c in cfgs if c["force_nsplit"] is not None) >= 4
+    assert any(c["force_nsplit"] is not None and info["nsplit"] not in (1, info["planned"]) for c, (info, _) in zip(cfgs, refs))
+    hard = [c["hard"][0] for c in cfgs if c["hard"] is not None]
+    assert len(hard) >= 5 and set(hard) == {"seam", "offset"} and all(c["cache"] == "16" for c in cfgs if c["hard"] is not None), hard
+    assert {k for c in cfgs for k in c["invalid"]} == set(fz.SPARSE_INVALID)
+    assert any(v == 0 for _, f in refs for v in f["valid"]) and any(v > 0 for _, f in refs for v in f["valid"])      # a token with no valid entry
+    assert any(r for c in cfgs for r in c["repeat"]) and any(c["topk"] > c["nb"] * c["bs"] for c in cfgs)         # repeated slots
+    assert any(c["nb"] * c["bs"] >= 4096 for c in cfgs) and {c["bs"] for c in cfgs} >= {1, 16} and any(c["bs"] & (c["bs"] - 1) for c in cfgs)
+    assert {c["q_pad"] for c in cfgs} == {0, 8, 24} and {c["scale_mul"] for c in cfgs} == {None, 0.5, 1.5, -1.0}
+    assert {c["ws"] for c in cfgs} == {"caller", "own"}
+    dense = [c for c in cfgs if c["dense"] is not None]
+    assert dense and all(info["planned"] == 1 and c["topk"] == 192 and max(c["dense"]) <= 191 for c, (info, _) in zip(cfgs, refs) if c["dense"] is not None)
+    # a seam probe on the first and on the last entry of a key range other than the list's own ends, and a slot listed twice
+    first = last = twice = False
+    for c, (info, _) in zip(cfgs, refs):
+        at = {pos for _, pos, _, _ in info["probes"]}
+        first |= any(a in at for a, _ in info["ranges"][1:])
+        last |= any(b in at for _, b in info["ranges"][:-1])
+        twice |= any(t is not None for _, _, _, t in info["probes"])
+        for _, pos, _, t in info["probes"]:
+            assert t is None or t // 64 != pos // 64
+    assert first and last and twice
+
+
+def test_sparse_slice_the_judge_alone_shows_every_probe_and_gaussian_lists_hide_an_entry():
+    """(a) for every probe head of every seam draw, the judge without the spiked entry is more than 20 x the out bound away on that head;
+    (b) a slot listed twice raises the judge's lse by ln 2; (c) on the slice's plain draws with more than 200 valid entries on a token,
+    removing one entry moves the judge by less than one bound in some: the gap the probe closes, kept checked"""
+    import math
+    probes = [x for _, f in _sparse_refs() for x in f["probes"]]
+    assert len(probes) >= 20 and all(units > 20.0 for units, _ in probes), sorted(probes)[:3]
+    doubled = [d for _, d in probes if d is not None]
+    assert doubled and all(abs(d - math.log(2.0)) <= 1e-9 for d in doubled), doubled
+    long = [f["one_entry"] for _, f in _sparse_refs() if f["one_entry"] is not None and max(f["valid"]) > 200]
+    share = sum(1 for u in long if u < 1.0) / len(long)
+    print("plain draws with more than 200 valid entries: %d, one entry removed moves the judge by less than one bound in %.0f %%: %s"
+          % (len(long), 100 * share, ["%.2f" % u for u in long]))
+    assert share > 0.0, long
+
+
+def test_indexer_slice():
+    cfgs = _draws("indexer")
+    Hs = {c["H"] for c in cfgs}
+    assert len(Hs) >= 12 and all(1 <= h <= 64 for h in Hs), Hs
+    assert all(any(lo <= h <= hi for h in Hs) for lo, hi in ((1, 15), (17, 31), (33, 47), (49, 63))), Hs
+    assert {c["fp8"] for c in cfgs} == {None, "unit", "rows"} and {c["positions"] for c in cfgs} == {False, True}
+    assert {c["ns"] is None for c in cfgs} == {False, True}                      # decode and ragged
+    ragged = [c for c in cfgs if c["ns"] is not None]
+    assert any(n > L for c in ragged for n, L in zip(c["ns"], c["ctx"])) and any(L == 0 for c in cfgs for L in c["ctx"])
+    assert any(c["max_sq"] is not None and c["max_sq"] < max(c["ns"]) for c in ragged)       # a cut sequence
+    assert {c["weights"] for c in cfgs} == set(fz.INDEXER_WEIGHTS) and set(fz.INDEXER_SOURCES) == {"own", "hand", "ladder", "bits"}
+    assert {c["topk"] for c in cfgs} == set(fz.INDEXER_TOPKS) and len({c["bs"] for c in cfgs}) >= 5
+    assert any(c["cap"] is not None for c in cfgs) and any(c["extra_rows"] for c in cfgs) and any(c["q_pad"] for c in cfgs) and {c["pad"] for c in cfgs} == {0, 3, 8}
+    pipe = [c for c in cfgs if c["pipeline"] is not None]
+    assert len(pipe) >= 4 and all(not c["positions"] and c["H"] <= 64 for c in pipe)
+    both = 0
+    for i, c in enumerate(cfgs):      # every draw is a valid problem; topk above and below p + 1 in the same draw
+        tab, p, topk = fz.indexer_problem(c, fz.SEED0["indexer"] + i)
+        ps = [pos for _, _, pos in tab.rows() if pos >= 0]
+        assert tab.T >= 1 and 1 <= topk <= 65536 and p.w.shape == (tab.T, c["H"])
+        both += any(topk > pos + 1 for pos in ps) and any(topk < pos + 1 for pos in ps)
+        src = fz.indexer_logit_sources(c, fz.SEED0["indexer"] + i, tab)
+        assert set(src) | {"own"} == set(fz.INDEXER_SOURCES) and all(x.shape == (tab.T, tab.W) and x.dtype == "float32" for x in src.values())
+    assert both >= 1
+
+
+def test_indexer_new_row_kinds_are_what_they_are_for():
+    """ladder: the values of a row differ in the last byte alone and repeat; bits: both signs, denormals, +-inf and NaN"""
+    import numpy as np
+    c = next(c for c in _draws("indexer") if max(c["ctx"]) >= 1000)
+    tab, _, _ = fz.indexer_problem(c, 1)
+    src = fz.indexer_logit_sources(c, 1, tab)
+    lad = src["ladder"].view(np.uint32)
+    assert ((lad >> 8) == (lad[:, :1] >> 8)).all() and all(len(set(r.tolist())) < len(r) for r in lad) and len(set(lad[0].tolist())) > 200
+    bits = src["bits"]
+    raw = bits.view(np.uint32)
+    assert np.isnan(bits).any() and np.isposinf(bits).any() and np.isneginf(bits).any() and (bits > 0).any() and (bits < 0).any()
+    assert (((raw >> 23) & 0xff == 0) & (raw & 0x7fffff != 0)).any()
+
+
+@functools.lru_cache(maxsize=None)
+def _fp8mma_facts():
+    return [fz.fp8mma_reference(c, fz.SEED0["fp8mma"] + i)[3] for i, c in enumerate(_draws("fp8mma"))]
+
+
+def test_fp8mma_slice():
+    cfgs = _draws("fp8mma")
+    assert {c["D"] for c in cfgs} == {64, 128}
+    bss = {c["bs"] for c in cfgs}
+    assert any(b > 1 and b & (b - 1) == 0 for b in bss) and any(b & (b - 1) for b in bss) and 1 in bss and any(b > 64 for b in bss), bss
+    assert {c["window"] > 0 for c in cfgs} == {False, True}
+    assert {c["Hq"] // c["Hkv"] for c in cfgs} >= {1, 2, 4, 8}
+    assert {c["qrow"][0] if c["qrow"] is not None else "plain" for c in cfgs} == set(fz.FP8MMA_QROWS)
+    hard = [c["hard"][0] for c in cfgs if c["hard"] is not None]
+    assert len(hard) >= 5 and set(hard) == {"spike", "offset"}, hard
+    assert any(len(c["ns"]) > 1 and len(set(c["ns"])) == 1 and c["ns"][0] > 1 for c in cfgs) and any(set(c["ns"]) == {1} for c in cfgs)      # uniform, all decode
+    assert any(c["q_pad"] for c in cfgs) and any(c["lead"] for c in cfgs) and any(c["tail"] for c in cfgs) and any(c["scale_mul"] is not None for c in cfgs)
+    assert any(c["table_len"] is not None for c in cfgs) and {c["extra_cols"] for c in cfgs} == {0, 2}
+    seqs = _seqs(cfgs)
+    assert any(L < n for _, n, L in seqs) and any(L == 0 for _, n, L in seqs) and any(n == 0 for _, n, L in seqs)
+    for c in cfgs:      # every draw is a valid call of the entry
+        assert sum(c["ns"]) >= 1 and c["Hq"] <= 32 and c["Hq"] % c["Hkv"] == 0 and all(L >= 0 for L in c["Ls"])
+        if c["qrow"] is not None:
+            kind, b, i, head = c["qrow"]
+            assert c["Ls"][b] - c["ns"][b] + i >= 0 and head < c["Hq"] and (kind != "near6e4" or c["dtype"] == "fp16")
+        if c["hard"] is not None and c["hard"][0] == "spike":
+            _, _, b, i, head, _, j = c["hard"]
+            p = c["Ls"][b] - c["ns"][b] + i
+            assert c["qrow"] is None and p >= 0 and head < c["Hq"] and j <= p and (c["window"] <= 0 or p - j < c["window"])
+
+
+def test_fp8mma_slice_the_reference_alone():
+    """in at least three spike draws the q-rounded judge without the spiked key is more than 20 x (atol + 2 E_P) away on the spiked row; on
+    the all-zero q row the judge's lse is ln(visible keys); and the fp32 term of the LSE bound (hard draws) and the storage-rounding term
+    of the out bound (rtol |judge| over atol + 2 E_P) are each the wider one in at most a quarter of the slice"""
+    facts = _fp8mma_facts()
+    spikes = [f["spike_units"] for f in facts if f["spike_units"] is not None]
+    assert sum(1 for u in spikes if u > 20.0) >= 3, spikes
+    zero = [f["zero_row"] for f in facts if f["zero_row"] is not None]
+    assert zero and all(abs(a - b) <= 1e-12 for a, b in zero), zero
+    assert all(f["lse_atol"] == max(1e-3, 4 * f["lse_f32_gap"]) for f in facts)
+    assert 4 * sum(1 for f in facts if f["lse_binds"]) <= len(facts), [f["lse_f32_gap"] for f in facts]
+    assert 4 * sum(1 for f in facts if f["round_binds"]) <= len(facts), [f["round_binds"] for f in facts]
+    # ... and so is 2 E_acc, the matrix instruction's accumulation, of the LSE bound; on the draws whose q rows are all as drawn it stays below 1e-3
+    assert 4 * sum(1 for f in facts if f["acc_binds"]) <= len(facts), [f["e_acc"] for f in facts]
+    assert all(not f["acc_binds"] for c, f in zip(_draws("fp8mma"), facts) if c["qrow"] is None or c["qrow"][0] in ("plain", "zero"))

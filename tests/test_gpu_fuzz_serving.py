@@ -1,10 +1,11 @@
 """Fixed-seed slices of tools/fuzz_serving.py inside the suite, as tests/test_gpu_fuzz.py holds those of tools/fuzz_parity.py: random valid
 calls of the paged prefill (with the paged query and the paged decode where the batch is theirs), the paged cascade and
 merge_attention_states, the paged MLA over 16-bit and FP8 latent caches, the varlen forward and backward, the three attention-sink entries
-and the sink backward, the two tree-mask entries, and the MLA 192 / 128 prefill forward and backward -- every owned row of every draw
+and the sink backward, the two tree-mask entries, the MLA 192 / 128 prefill forward and backward, the sparse MLA, the MLA indexer (logits, top-k and the lists
+through the sparse MLA) and the FP8-product paged prefill -- every owned row of every draw
 against the fp64 oracle through the judges of the hand-written files, plus the exact relations between the entries.  The seeds and
 counts are tools/fuzz_serving.py's SLICES; tests/test_fuzz_serving_draws.py asserts, without a GPU, what these draws reach.  Deterministic:
-a regression test over 150 configurations nobody enumerated by hand.  Each test prints the maxima it measured (pytest -s)."""
+a regression test over 214 configurations nobody enumerated by hand.  Each test prints the maxima it measured (pytest -s)."""
 import importlib.util
 import os
 
@@ -75,3 +76,30 @@ def test_random_mla_prefill_batches_forward_and_backward(fuzz):
     projections: all six outputs vs the judge of tests/test_gpu_mla_backward.py; two runs the same bits; sequence 0 alone the same bits as in
     the batch"""
     _slice(fuzz, "mlapf", 20)
+
+
+def test_random_sparse_mla_calls(fuzz):
+    """24 draws of aule_attention_mla_sparse_ex in the arena (0xFF outputs, guards, inputs unchanged, NaN bits in every unnamed cache row)
+    and of flash_attention_mla_sparse: rows and LSE vs the judge of tests/test_gpu_mla_sparse.py over lists with invalid entries, whole
+    invalid tiles and key ranges, repeated slots; one draw in three with a seam probe (a key 8 x q[t, h] at the ends of the list, the
+    tiles and the key ranges; one probe head in two lists it twice) or an offset; the Python entry and two runs the same bits, forced
+    key-range counts, contiguous lists equal to flash_attention_mla_paged bit for bit"""
+    _slice(fuzz, "sparse", 24)
+
+
+def test_random_mla_indexer_calls(fuzz):
+    """20 draws of aule_mla_indexer_logits_ex / _topk_ex: every logit within the per-element bound of tests/test_gpu_mla_indexer.py, the
+    Python entry and two runs the same bits, unit FP8 scales the 16-bit call; the top-k contract exactly on the kernel's own logits, the
+    hand file's row kinds, ladders of last-place steps and random bit patterns; every selected key within two bounds of the k-th
+    largest fp64 logit; one draw in four feeds the lists to the sparse MLA"""
+    _slice(fuzz, "indexer", 20)
+
+
+def test_random_paged_prefill_fp8mma_batches(fuzz):
+    """20 draws of aule_attention_paged_prefill_fp8mma_ex into 0xFF-filled out / lse: LSE vs the q-rounded judge, out within atol + 2 E_P
+    and the rms rule of tests/test_gpu_paged_prefill_fp8mma.py; zero, one-large-element and near-6e4 rows of q, spiked and offset keys
+    through the cache's quantisation; the Python entry, two runs and sequence 0 alone the same bits; the plain entry on the same cache
+    within its bound plus the distance between the two judges.  The LSE bound of a row is LSE_ATOL (hard draws: the fp32 rule) plus 2 E_acc,
+    the accumulation of the FP8 matrix instruction (tools/fuzz_serving.py::fp8mma_acc_term): on the first slice the `big` and `near6e4` rows
+    missed LSE_ATOL by 1.4 .. 3.0e-3 and 0.9 .. 2.1, and one-key rows showed the instruction itself 2^-12.4 of the largest product off."""
+    _slice(fuzz, "fp8mma", 20)

@@ -79,8 +79,9 @@ class Problem:
         return out, lse
 
 
-def check(p, got, idx, what, scale=None, ref=None):
-    """out / lse against the judge with the project's bounds; prints and returns the maxima"""
+def check(p, got, idx, what, scale=None, ref=None, lse_atol=LSE_ATOL):
+    """out / lse against the judge with the project's bounds; prints and returns the maxima.  (lse_atol: tools/fuzz_serving.py's hard-data
+    draws pass a bound computed from the reference alone; every test of this file keeps LSE_ATOL.)"""
     out, lse = got[0].float().cpu().numpy().astype(np.float64), got[1].cpu().numpy().astype(np.float64)
     ref, lref = p.judge(idx, scale) if ref is None else ref
     atol, rtol = fwd_tol(p.dtype, p.vmax)
@@ -88,12 +89,12 @@ def check(p, got, idx, what, scale=None, ref=None):
     oerr = float(np.abs(out - ref).max())
     lerr = float(np.abs(lse[~none] - lref[~none]).max()) if (~none).any() else 0.0
     print("%s: max |out err| %.3g (atol %.3g + %.3g |ref|), max |lse err| %.3g (bound %.3g), rows without a key %d of %d"
-          % (what, oerr, atol, rtol, lerr, LSE_ATOL, int(none.sum()), none.size))
+          % (what, oerr, atol, rtol, lerr, lse_atol, int(none.sum()), none.size))
     assert not np.isnan(out).any() and not np.isnan(lse).any(), what
     assert_close(out, ref, atol, rtol, what)
     assert np.array_equal(np.isneginf(lse), none), "%s: lse must be -inf exactly where a token has no valid entry" % what
     assert bool((out[none] == 0).all()), "%s: a token without a valid entry must give zeros" % what
-    assert lerr <= LSE_ATOL, (what, lerr)
+    assert lerr <= lse_atol, (what, lerr)
     return oerr, lerr
 
 

@@ -242,8 +242,9 @@ def _desc(torch, p, args, scales, out, lse, max_sq, window=-1, q_stride=None, sc
 PAD = 64   # rows of 0xFF in front of and behind out / lse
 
 
-def _run_capi(torch, p, max_sq=None, window=-1, cu=None, cl=None, with_lse=True, scale=None, q_pad=0):
-    """through the C-ABI into 0xFF-filled buffers with PAD rows of margin on both sides; returns (out, lse, margins intact)"""
+def _run_capi(torch, p, max_sq=None, window=-1, cu=None, cl=None, with_lse=True, scale=None, q_pad=0, entry="aule_attention_paged_prefill_ex"):
+    """through the C-ABI into 0xFF-filled buffers with PAD rows of margin on both sides; returns (out, lse, margins intact).  (entry: the
+    FP8-product twin takes the same descriptor)"""
     from aule import _capi
     lib = _capi.get_lib()
     args, scales = p.device(torch, cu, cl, q_pad)
@@ -252,7 +253,7 @@ def _run_capi(torch, p, max_sq=None, window=-1, cu=None, cl=None, with_lse=True,
     out, lse = big_o[PAD:PAD + p.T], big_l[PAD:PAD + p.T]
     d = _desc(torch, p, args, scales, out, lse if with_lse else None, p.max_sq if max_sq is None else max_sq, window,
               args[0].stride(0) if q_pad else None, 0.0 if scale is None else scale)
-    assert lib.aule_attention_paged_prefill_ex(ctypes.byref(d)) == 0, lib.aule_get_error()
+    assert getattr(lib, entry)(ctypes.byref(d)) == 0, lib.aule_get_error()
     torch.cuda.synchronize()
     intact = all(bool((t[:PAD] == -1).all()) and bool((t[PAD + p.T:] == -1).all()) for t in (big_o, big_l))
     return out.view(torch_dtype(p.dtype)), lse.view(torch.float32), intact

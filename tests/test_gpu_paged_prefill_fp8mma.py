@@ -42,17 +42,18 @@ def _e4m3(x):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.float8_e4m3fn).float().numpy().astype(np.float64)
 
 
-def _models(p, window=-1, **kw):
+def _models(p, window=-1, scale=None, rounded=True, **kw):
     """(judge out [T, Hq, D], judge lse [T, Hq], P-model out) in fp64 on the owned rows (zeros / -inf where a row sees no key; rows of no
-    sequence: zeros and NaN); computed once per (window, lengths) and kept on the problem"""
+    sequence: zeros and NaN); computed once per (window, scale, lengths) and kept on the problem.  rounded=False (tools/fuzz_serving.py):
+    the same three with q as it is, not its e4m3 codes"""
     import torch
     import aule
-    key = ("fp8mma", window, tuple((k, tuple(np.asarray(v).tolist()) if k != "max_sq" else v) for k, v in sorted(kw.items())))
+    key = ("fp8mma", window, scale, rounded, tuple((k, tuple(np.asarray(v).tolist()) if k != "max_sq" else v) for k, v in sorted(kw.items())))
     if key in p._ref:
         return p._ref[key]
     codes, scales = aule.quantize_rows_fp8(torch.from_numpy(p.q))
-    qh = (codes.float() * scales).numpy().astype(np.float64)
-    g, scale = p.Hq // p.Hkv, 1.0 / math.sqrt(p.D)
+    qh = (codes.float() * scales).numpy().astype(np.float64) if rounded else p.q.astype(np.float64)
+    g, scale = p.Hq // p.Hkv, 1.0 / math.sqrt(p.D) if scale is None else scale
     out_j = np.zeros((p.T, p.Hq, p.D))
     out_p = np.zeros((p.T, p.Hq, p.D))
     lse_j = np.full((p.T, p.Hq), np.nan)
@@ -87,26 +88,33 @@ def _rms(x):
     return float(np.sqrt(np.mean(np.square(x)))) if x.size else 0.0
 
 
-def _judge(p, out, lse, window, what, **kw):
-    """test 1's rules on the owned rows; prints the measured figures before it asserts"""
+def _judge(p, out, lse, window, what, scale=None, lse_atol=LSE_ATOL, out_rtol=0.0, **kw):
+    """test 1's rules on the owned rows; prints the measured figures before it asserts and returns (max |out - judge|, max |lse err|, the
+    largest |out - judge| as a share of its bound).  (scale, lse_atol, out_rtol: tools/fuzz_serving.py's draws, whose rows of one or two
+    keys have E_P = 0 and are left with the rounding of out to storage alone, fwd_tol's rtol |judge|; every test of this file keeps the
+    defaults.)"""
     own = p.owned(**kw)
-    out_j, lse_j, out_p = (x[own] for x in _models(p, window, **kw))
+    out_j, lse_j, out_p = (x[own] for x in _models(p, window, scale, **kw))
     out, lse = out.float().cpu().numpy().astype(np.float64)[own], lse.cpu().numpy().astype(np.float64)[own]
     atol = fwd_tol(p.dtype, p.vmax)[0]
     none = np.isneginf(lse_j)
     lerr = float(np.abs(lse[~none] - lse_j[~none]).max()) if (~none).any() else 0.0
+    lse_bound = np.broadcast_to(np.asarray(lse_atol, dtype=np.float64), (p.T, p.Hq))[own]      # (a scalar, or a bound per row [T, Hq])
+    lse_atol = float(lse_bound.max()) if lse_bound.size else 0.0
     e_p, err = float(np.abs(out_p - out_j).max()), float(np.abs(out - out_j).max())
     rms_p, rms_k = _rms(out_p - out_j), _rms(out - out_j)
     print("%s: %d rows, |lse err| %.3g (bound %.3g); max |out - judge| %.4g, E_P %.4g, ratio %.3f (bound atol %.3g + 2 E_P); "
           "rms %.4g, model rms %.4g, ratio %.3f; rows without a key %d"
-          % (what, int(own.sum()), lerr, LSE_ATOL, err, e_p, err / e_p if e_p else 0.0, atol, rms_k, rms_p, rms_k / rms_p if rms_p else 0.0,
+          % (what, int(own.sum()), lerr, lse_atol, err, e_p, err / e_p if e_p else 0.0, atol, rms_k, rms_p, rms_k / rms_p if rms_p else 0.0,
              int(none.sum())))
     assert not np.isnan(lse).any() and not np.isnan(out).any(), what
     assert np.array_equal(np.isneginf(lse), none), "%s: lse must be -inf exactly where a row sees no key" % what
     assert bool((out[none] == 0).all()), "%s: a row that sees no key must be zeros" % what
-    assert lerr <= LSE_ATOL, (what, lerr)
-    assert err <= atol + 2.0 * e_p, (what, err, atol, e_p)
+    assert bool((np.abs(lse[~none] - lse_j[~none]) <= lse_bound[~none]).all()), (what, lerr, lse_atol)
+    share = float((np.abs(out - out_j) / (atol + out_rtol * np.abs(out_j) + 2.0 * e_p)).max()) if out.size else 0.0
+    assert share <= 1.0, (what, err, atol, e_p, share)
     assert rms_k <= 2.0 * rms_p + atol, (what, rms_k, rms_p, atol)
+    return err, lerr, share
 
 
 def _run(torch, p, window=-1, max_sq=None, cu=None, cl=None, caches=None):

@@ -9,6 +9,9 @@ forward / backward, the paged DECODE, RoPE, split-KV and windows):
     sinks     flash_attention_varlen_sinks (forward and backward), _paged_prefill_sinks, _paged_query_sinks and the C entries behind them
     tree      flash_attention_paged_query_tree and flash_attention_paged_prefill_tree
     mlapf     aule_attention_mla_prefill_ex / _backward_ex (192 / 128) and flash_attention_mla_varlen
+    sparse    aule_attention_mla_sparse_ex and flash_attention_mla_sparse
+    indexer   aule_mla_indexer_logits_ex / _topk_ex, mla_indexer_logits / _topk / mla_indexer, and their lists through the sparse MLA
+    fp8mma    aule_attention_paged_prefill_fp8mma_ex and flash_attention_paged_prefill_fp8mma
 
     python tools/fuzz_serving.py KIND [n=100] [seed=0]          deterministic per seed; prints every failing configuration
     python tools/fuzz_serving.py one KIND "<cfg as printed>" SEED    one printed configuration again
@@ -53,7 +56,55 @@ garbage, as those of unowned rows) equal the plain entry bit for bit; two runs g
 mlapf: heads 1 .. 32, three masks, scale, lead / tail rows on both axes, cuts by max_seqlen_*, the three memory layouts of
 tests/test_gpu_mla_backward.py::Run, and one draw in five through flash_attention_mla_varlen with autograd on slices of wider projections.
 Relations: two runs give the same bits in all six outputs; sequence 0 alone equals the same sequence in the batch bit for bit (dk_pe where
-both launches cut the heads into the same chunks)."""
+both launches cut the heads into the same chunks).
+
+sparse: dtype, a 16-bit or FP8 latent cache, 1 .. 6 tokens, heads 1 .. 128, lists of 1 .. 2048 entries over caches of 5 .. 4096 slots (block
+size 1, powers of two and others; the small caches make every longer list repeat slots), scale (a negative one included), a padded q, the
+caller's workspace at exactly the queried size or the library's.  Per token a share of invalid entries (none, scattered, one whole 64-entry
+tile, one whole key range of the launch, all; the values -1, S, INT32_MIN, INT32_MAX) and whether its list is drawn from a few slots.  Gaussian
+data hides a single list entry once a list is long (one entry of 2048 moves `out` by half its bound; tests/test_fuzz_serving_draws.py keeps
+that measured), so one draw in three is hard (16-bit caches): a SEAM PROBE -- on one token, heads 0 .. min(Hq, 16) - 1 each take one
+list position from the seam set (0, 63, 64, topk - 1, the first and last entry of every key range of the launch -- the plan's, from
+aule_hip_debug_mla_sparse_plan, or the forced count's -- the valid entries next to an invalid run, then random ones), and the slot named
+there holds 8 sign(scale) q[t, h]: a logit near 190, so that losing or misreading that one entry moves that head by hundreds of bounds; one
+probe head in two lists its slot a second time in another tile (the judge's lse rises by ln 2, out stays) -- or the mla kind's OFFSET on
+the 64 rotary columns.  The draw names the probe token; the positions are resolved by the reference side (sparse_problem), which reads the
+plan hook -- host logic, no GPU.  Checks: test_gpu_mla_sparse.check on the C entry's result inside the Arena (0xFF pre-fill, guards,
+inputs unchanged, NaN bits in every cache row no valid entry names): fwd_tol, LSE_ATOL (hard draws: the bound above, from
+sparse_lse_f32_gap), exact zeros / -inf.  Relations: the Python entry and a second run give the C entry's bits; a forced key-range count
+(aule_hip_debug_mla_sparse_launch_nsplit) stays within the bounds and the planned count, forced, gives the entry's bits; about one draw in
+eight lists the contiguous slots of a block table (at most 191 keys: both plans say one split) and equals flash_attention_mla_paged bit for
+bit.
+
+indexer: heads 1 .. 64, block sizes 1 .. 128, a decode or ragged batch (n_b 1 .. 70, contexts around 1 / 63 / 64 / 65 / 129 / 1100, L_b = 0,
+n_b > L_b, rows of no sequence, a max_seqlen_q cut, table columns beyond the used blocks), a 16-bit cache or FP8 codes with unit or per-row
+scales, a padded q and logits stride, four kinds of weights (randn / sqrt(H), one head carries all, all negative, one zero head).  Logits:
+check_logits unchanged (every element within the derived bound, -inf past p, 0xFF elsewhere); the Python entry and a second run the same
+bits; unit scales the 16-bit call on the converted codes.  Top-k: topk_contract exactly (check_topk: the C entry twice and the Python
+entry), at the drawn topk and output, on four sources of logits: the kernel's own, the hand file's row kinds, `ladder` (a base value plus
+0 .. 255 units in the last place, shuffled, with repeats: only the last radix pass separates them) and `bits` (random 32-bit patterns of
+both signs with denormals, +-inf and NaN planted).  Selection against fp64: every selected key's fp64 logit is at least the k-th largest
+fp64 logit minus the row's two largest per-element bounds.  One draw in four feeds the slot lists to flash_attention_mla_sparse over a
+latent cache that shares the table and the block size, judged by the sparse judge on those lists, and compares aule.mla_indexer.
+
+fp8mma: _draw_ragged's axes on the entry's domain (FP8 cache, D 64 / 128), from a stream of its own, plus one row of q rewritten: all
+zero (the judge's lse is ln(visible keys)), one element 100 x the rest, or an fp16 row near 6e4.  One draw in three is hard: _draw_ragged's
+spike (one key = 20 x a query row that sees it) or offset, planted in the dequantised keys, which are then quantised again with the head's
+k_scale -- the judge reads what survives.  Bounds are the hand file's: lse within LSE_ATOL of the q-rounded judge (hard draws: max(LSE_ATOL,
+4 x lse_f32_gap) of the q-rounded rows), out within atol + 2 E_P of it, the rms rule, exact zeros / -inf, unowned rows of the 0xFF-filled
+out / lse untouched.  Two terms grow a bound, both from the reference alone, each held by tests/test_fuzz_serving_draws.py to the wider
+term in at most a quarter of the slice.  The LSE bound of a row gains 2 E_acc, E_acc = D 2^-20 |scale| x the row's largest single product
+|q_d k_jd| (fp8mma_acc_term): the FP8 matrix instruction adds the products of a step aligned to the largest and keeps about 20 bits below
+its leading bit, so the kernel's scores -- and its lse, which the entry's docstring calls exact -- are off by up to 2^-12.4 of the
+largest product at D = 128.  The first slice found it on the `big` and `near6e4` rows (1.4 .. 3.0e-3 and 0.9 .. 2.1 against LSE_ATOL); rows
+that see ONE key, whose lse is the scaled dot product itself, showed where it comes from: nothing when a single product is non-zero,
+2^-12.4 of the largest product otherwise, 500 times fp32's own spacing (profiles/fuzz_new_serving_kinds.txt).  On plain rows 2 E_acc is
+below 4e-4.  And the out bound gains rtol |judge| with fwd_tol's rtol, the rounding of out to storage.  A row that sees one
+key has E_P = 0 and returns that value row exactly (the hand file's test 2), which is up to half a unit in the last place from the fp64
+value -- 2^-8.9 of 15.1 in bf16 where atol allows 2^-9 max|V| (draws #12 and #14 of the first slice, seed 12, found it); from the reference alone, and
+tests/test_fuzz_serving_draws.py holds it to the wider term in at most a quarter of the slice.  Relations: the Python entry, a second run and sequence 0 alone give the same bits; flash_attention_paged_prefill on
+the same cache agrees with the same q-rounded judge within fwd_tol plus the largest distance between the q-rounded and the unrounded judge
+(out and lse each), which ties the twin's masks and clamps to this kernel's."""
 import ast, contextlib, importlib, io, math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "aule-attention_amd"), ROOT):
@@ -507,10 +558,225 @@ def mlapf_geometry(c):
                 max_sk=c["max_sk"] if c["max_sk"] is not None else max(1, max(c["ls"])))
 
 
-DRAW = dict(prefill=draw_prefill, cascade=draw_cascade, mla=draw_mla, varlen=draw_varlen, sinks=draw_sinks, tree=draw_tree, mlapf=draw_mlapf)
+# -------------------------------------------------------------------------------------------------------------------------- sparse: the draw
+SPARSE_HEADS = [1, 2, 8, 16, 17, 63, 64, 65, 96, 127, 128]
+SPARSE_TOPKS = [1, 2, 63, 64, 65, 127, 129, 200, 500, 2048]
+# (block_size, num_blocks): caches so small that every longer list repeats slots, caches of a few hundred slots, one of 4096
+SPARSE_CACHES = [(1, 5), (16, 2), (7, 3), (1, 300), (16, 19), (48, 7), (24, 11), (64, 64)]
+SPARSE_INVALID = ["none", "none", "scattered", "scattered", "tile", "split", "all"]      # a token's share of invalid entries
+SPARSE_DENSE_LS = {1: [191, 1, 64, 100], 16: [176, 1, 64, 100]}      # the contiguous-list draw: block size -> context lengths (the first: the capacity)
+
+
+def _sparse_cost(c):
+    """~ flops of the per-token judge: scores over 576 columns and P @ rows over 512 per (head, entry), the gather of the rows, and some
+    2e5 flops' worth of interpreter per token"""
+    return c["T"] * (c["Hq"] * c["topk"] * 2200 + c["topk"] * 576 * 4 + 200000)
+
+
+def draw_sparse(rng):
+    c = {}
+    c["dtype"] = _pick(rng, ["bf16", "fp16"])
+    hard = int(rng.randint(3)) == 0
+    dense = not hard and int(rng.randint(5)) == 0                 # (two draws in fifteen: the contiguous lists of a block table)
+    c["cache"] = "16" if hard or dense else _pick(rng, ["16", "fp8"])
+    T, Hq, topk = int(rng.randint(1, 7)), _pick(rng, SPARSE_HEADS), _pick(rng, SPARSE_TOPKS)
+    c["bs"], c["nb"] = _pick(rng, SPARSE_CACHES)
+    c["scale_mul"] = _pick(rng, [None, None, 0.5, 1.5, -1.0])    # scale = scale_mul / sqrt(576)
+    c["q_pad"] = _pick(rng, [0, 0, 8, 24])                       # q a slice of a projection that many heads wider per token
+    invalid = [_pick(rng, SPARSE_INVALID) for _ in range(6)]
+    repeat = [int(rng.randint(3)) == 0 for _ in range(6)]
+    c["force_nsplit"] = _pick(rng, [None, None, 1, 2, 3, 7])
+    c["ws"] = _pick(rng, ["caller", "own"])                       # the caller's workspace at exactly the queried size, or the library's
+    kind, probe, add, dense_bs = int(rng.randint(2)), int(rng.randint(6)), float(_pick(rng, [2, 4])), _pick(rng, [1, 16])
+    dense_ls = [int(rng.randint(1, 4)) for _ in range(6)]
+    c["dense"] = None
+    if dense:
+        # tests/test_gpu_mla_sparse.py::test_contiguous_lists_equal_the_paged_decode_bit_for_bit: token t lists the slots of positions
+        # 0 .. L_t - 1 of sequence t, padded with -1 to a multiple of 64; at most 191 keys of table, so that both plans say one split
+        ls = SPARSE_DENSE_LS[dense_bs]
+        c["bs"], topk = dense_bs, 192
+        c["force_nsplit"], invalid, repeat = None, ["none"] * 6, [False] * 6
+    while True:      # the judge's budget: tokens, then heads, then the list
+        c["T"], c["Hq"], c["topk"] = T, Hq, topk
+        if _sparse_cost(c) <= 1e9 * JUDGE_BUDGET:
+            break
+        if T > 1: T -= 1
+        elif Hq > 1: Hq = _smaller(SPARSE_HEADS, Hq)
+        elif topk > 1: topk = _smaller(SPARSE_TOPKS, topk)
+        else: break
+    if dense:
+        c["dense"] = [ls[0]] + [ls[i] for i in dense_ls[1:c["T"]]]
+        c["nb"] = c["T"] * (ls[0] // c["bs"]) + 3
+    c["invalid"], c["repeat"] = invalid[:c["T"]], repeat[:c["T"]]
+    # hard data, against the final shapes: ("seam", the probe token) -- the positions come from the split plan, which the reference side
+    # reads (sparse_problem) -- or ("offset", c)
+    c["hard"] = None
+    if hard:
+        if kind == 0:
+            t = probe % c["T"]
+            c["hard"] = ("seam", t)
+            if c["invalid"][t] in ("split", "all") or (c["invalid"][t] == "tile" and c["topk"] <= 64):
+                c["invalid"][t] = "scattered"                     # (the probe token keeps valid entries at the seams)
+        else:
+            c["hard"] = ("offset", add)
+    return c
+
+
+# -------------------------------------------------------------------------------------------------------------------------- fp8mma: the draw
+FP8MMA_QROWS = ["plain", "zero", "big", "near6e4"]      # one (token, head) row of q: as drawn, all zero, one element x 100, fp16 near 6e4
+
+
+def _fp8mma_cost(c):
+    """~ flops of tests/test_gpu_paged_prefill_fp8mma.py::_models: per sequence three einsum products of n L Hq D, the exponentials and the
+    e4m3 rounding of n L Hq weights"""
+    return sum(c["Hq"] * (n * max(L, 0) * (6 * c["D"] + 60) + 3000) for n, L in zip(c["ns"], c["Ls"]))
+
+
+def draw_fp8mma(rng):
+    """_draw_ragged's axes on the FP8-product entry's domain (an FP8 cache, D 64 / 128, no sinks), from a stream of its own"""
+    c = {}
+    c["dtype"] = _pick(rng, ["bf16", "fp16"])
+    hard = int(rng.randint(3)) == 0
+    c["D"] = _pick(rng, [64, 128])
+    c["Hkv"] = _pick(rng, [1, 2, 3, 8])
+    g = _pick(rng, [x for x in (1, 2, 3, 4, 5, 8, 16) if x * c["Hkv"] <= 32])
+    c["bs"] = _pick(rng, BLOCK_SIZES)
+    B = int(rng.randint(1, 7))
+    shape = int(rng.randint(8))       # one batch in eight is uniform, one in eight all decode
+    if shape == 0:
+        ns = [_pick(rng, [1, 2, 3, 31, 32, 33, 43, 64])] * B
+    elif shape == 1:
+        ns = [1] * B
+    else:
+        ns = [_pick(rng, NS_RAGGED) for _ in range(B)]
+    if sum(ns) == 0:
+        ns[0] = 1
+    ds = []      # L_b - n_b, or None for L_b = 0
+    for n in ns:
+        how = int(rng.randint(4))
+        ds.append(None if how == 0 or (how == 1 and n == 0) else -int(rng.randint(1, n + 1)) if how == 1 else 0 if how == 2 else _pick(rng, AHEAD))
+    c["window"] = _pick(rng, [-1, -1, 1, 16, 64, 65, 300])
+    c["scale_mul"] = _pick(rng, [None, None, 0.5, 1.5])          # scale = scale_mul / sqrt(D)
+    c["lead"], c["tail"] = _pick(rng, [0, 3]), _pick(rng, [0, 5])
+    c["q_pad"] = _pick(rng, [8, 24, 64]) if int(rng.randint(3)) == 0 else 0
+    c["extra_cols"] = _pick(rng, [0, 2])
+    room = _pick(rng, [1, 64, 700]) if int(rng.randint(4)) == 0 else 0
+    qrow = _pick(rng, FP8MMA_QROWS)
+    lens = lambda: [0 if d is None else max(n + d, 0) for n, d in zip(ns, ds)]   # noqa: E731
+    while True:      # the judge's budget: batch, then heads, then lengths
+        c["Hq"], c["ns"], c["Ls"] = c["Hkv"] * g, list(ns), lens()
+        if _fp8mma_cost(c) <= 1e8 * JUDGE_BUDGET:
+            break
+        if len(ns) > 1:
+            ns.pop(); ds.pop()
+            if sum(ns) == 0: ns[0] = 1
+        elif g > 1: g = _smaller([1, 2, 3, 4, 5, 8, 16], g)
+        elif c["Hkv"] > 1: c["Hkv"] = _smaller([1, 2, 3, 8], c["Hkv"])
+        elif ds[0] is not None and ds[0] > 1: ds[0] = _smaller(AHEAD, ds[0])
+        elif ns[0] > 1:
+            ns[0] = _smaller(NS_RAGGED, ns[0])
+            if ds[0] is not None and ds[0] < 0: ds[0] = max(ds[0], -ns[0])
+        else: break
+    c["table_len"] = max(c["Ls"]) + room if room else None
+    # the q row and the hard data, against the final shapes: a token that sees a key
+    live = [(b, i) for b, (n, L) in enumerate(zip(c["ns"], c["Ls"])) for i in range(n) if L - n + i >= 0]
+    c["qrow"], c["hard"] = None, None
+    spike = hard and int(rng.randint(2)) == 0 and bool(live)
+    if qrow == "near6e4" and c["dtype"] != "fp16":
+        qrow = "big"
+    if qrow != "plain" and live and not spike:                   # (a spiked key is m x a plain row of q)
+        b, i = _pick(rng, live)
+        c["qrow"] = (qrow, b, i, int(rng.randint(c["Hq"])))
+    if spike:
+        b, i = _pick(rng, live)
+        p = c["Ls"][b] - c["ns"][b] + i
+        lo = max(0, p - c["window"] + 1) if c["window"] > 0 else 0
+        c["hard"] = ("spike", 20.0, b, i, int(rng.randint(c["Hq"])), "own", int(rng.randint(lo, p + 1)))
+    elif hard:
+        c["hard"] = ("offset", float(_pick(rng, [2, 4])), int(rng.randint(c["Hkv"])))
+    return c
+
+
+# ------------------------------------------------------------------------------------------------------------------------- indexer: the draw
+INDEXER_BS = [1, 2, 7, 16, 48, 64, 128]
+INDEXER_NS = [1, 2, 3, 4, 5, 63, 64, 70]
+INDEXER_CTX = [0, 1, 63, 64, 65, 129, 1100, "n-k"]      # "n-k": fewer keys than new tokens (p < 0 for the first rows)
+INDEXER_CTX_LENS = [0, 1, 63, 64, 65, 129, 1100]
+INDEXER_TOPKS = [1, 63, 64, 65, 200, 2048, "above"]     # "above": three more than the table is wide -- every visible key and the -1 tail
+INDEXER_WEIGHTS = ["randn", "one", "negative", "zero"]  # randn / sqrt(H); one head carries all the weight; all negative; one zero head
+INDEXER_SOURCES = ["own", "hand", "ladder", "bits"]     # the logits a top-k call is given (indexer_logit_sources)
+
+
+def _indexer_rows(c):
+    """[(n rows after the cut, L)] per sequence (pure)"""
+    if c["ns"] is None:
+        return [(1, L) for L in c["ctx"]]
+    cut = c["max_sq"] if c["max_sq"] is not None else max(c["ns"])
+    return [(min(n, cut), L) for n, L in zip(c["ns"], c["ctx"])]
+
+
+def _indexer_cost(c):
+    """~ flops of Problem.judge (two products of H x 128 per visible key of every row), of the exact top-k contract on four logit sources
+    (a sort of the row), and of the sparse judge on the selected keys of a pipeline draw"""
+    cost = 0
+    for n, L in _indexer_rows(c):
+        seen = sum(max(L - n + i + 1, 0) for i in range(n))
+        cost += seen * (c["H"] * 512 + 400) + n * 20000
+        if c["pipeline"] is not None:
+            cost += n * c["pipeline"] * min(L, 2051) * 2200
+    return cost
+
+
+def draw_indexer(rng):
+    c = {}
+    c["dtype"] = _pick(rng, ["bf16", "fp16"])
+    c["H"] = int(rng.randint(1, 65))
+    c["bs"] = _pick(rng, INDEXER_BS)
+    c["fp8"] = _pick(rng, [None, "unit", "rows"])
+    c["q_pad"] = _pick(rng, [0, 0, 8, 16])                       # q a slice of a projection that many heads wider per token
+    c["pad"] = _pick(rng, [0, 3, 8])                             # logits_stride = the table's width + pad
+    c["weights"] = _pick(rng, INDEXER_WEIGHTS)
+    c["topk"] = _pick(rng, INDEXER_TOPKS)
+    c["positions"] = int(rng.randint(2)) == 1                    # the list holds positions, else cache slots
+    pipeline = int(rng.randint(4)) == 0
+    lat_heads = _pick(rng, [2, 16])
+    ragged = int(rng.randint(3)) > 0
+    B = int(rng.randint(1, 6))
+    ns = [_pick(rng, INDEXER_NS) for _ in range(B)]
+    ctx = [_pick(rng, INDEXER_CTX) for _ in range(B)]
+    below = [int(rng.randint(1, 71)) for _ in range(B)]
+    extra_rows = _pick(rng, [0, 0, 2, 3])
+    c["extra_rows"] = extra_rows if ragged else 0                 # (plain decode: the Python entries take one row per sequence)
+    cut = int(rng.randint(5)) == 0
+    room = _pick(rng, [0, 0, 1, 5])                              # table columns beyond the longest context: that many blocks
+    if pipeline:
+        c["positions"] = False
+    c["pipeline"] = lat_heads if pipeline else None               # the heads of the latent attention the lists are fed to
+    while True:      # the judge's budget: batch, then heads, then lengths
+        toks = ns if ragged else [1] * len(ns)
+        c["ns"] = list(ns) if ragged else None
+        c["ctx"] = [max(n - min(k, n), 0) if L == "n-k" else L for n, L, k in zip(toks, ctx, below)]
+        c["max_sq"] = None
+        if _indexer_cost(c) <= 3e8 * JUDGE_BUDGET:
+            break
+        big = max(range(len(ns)), key=lambda b: toks[b] * (c["ctx"][b] + 1))
+        if len(ns) > 1: ns.pop(); ctx.pop(); below.pop()
+        elif c["H"] > 1: c["H"] = max(1, c["H"] // 2)
+        elif ctx[big] != "n-k" and ctx[big] > 1: ctx[big] = _smaller(INDEXER_CTX_LENS, ctx[big])
+        elif ns[big] > 1: ns[big] = _smaller(INDEXER_NS, ns[big])
+        else: break
+    if cut and ragged and max(c["ns"]) > 1:
+        c["max_sq"] = max(1, max(c["ns"]) - _pick(rng, [1, 6]))  # below the longest sequence: its last rows belong to no sequence
+    c["cap"] = max(max(c["ctx"]), 1) + room * c["bs"] if room else None
+    return c
+
+
+DRAW = dict(indexer=draw_indexer, prefill=draw_prefill, cascade=draw_cascade, mla=draw_mla, varlen=draw_varlen, sinks=draw_sinks, tree=draw_tree, mlapf=draw_mlapf,
+            sparse=draw_sparse, fp8mma=draw_fp8mma)
 # The fixed-seed slices of the suite: kind -> (draws, seed).  tests/test_gpu_fuzz_serving.py runs them, tests/test_fuzz_serving_draws.py
 # asserts (without a GPU) that they reach what they are for; a seed is chosen so that the latter holds.
-SLICES = dict(prefill=(30, 2), cascade=(20, 3), mla=(20, 5), varlen=(20, 4), sinks=(20, 24), tree=(20, 2), mlapf=(20, 4))
+SLICES = dict(prefill=(30, 2), cascade=(20, 3), mla=(20, 5), varlen=(20, 4), sinks=(20, 24), tree=(20, 2), mlapf=(20, 4),
+              sparse=(24, 25), fp8mma=(20, 128), indexer=(20, 1))
 
 
 def draws(kind, n, seed):
@@ -1110,8 +1376,523 @@ def run_mlapf(cfg, seed, stats=None):
     return cfg, errs
 
 
-RUN = dict(prefill=run_prefill, cascade=run_cascade, mla=run_mla, varlen=run_varlen, sinks=run_sinks, tree=run_tree, mlapf=run_mlapf)
-SEED0 = dict(prefill=31000, cascade=32000, mla=33000, varlen=34000, sinks=35000, tree=36000, mlapf=37000)      # data seed of draw i: SEED0[kind] + i
+# ----------------------------------------------------------------------------------------------------------------------------------- sparse
+def sparse_plan(cfg):
+    """(planned nsplit, workspace bytes) of a sparse draw from aule_hip_debug_mla_sparse_plan: host logic over the shape, no GPU"""
+    import ctypes
+    from aule import _capi
+    c = cfg
+    d = _capi.MlaSparseDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype, d.cache_dtype, d.heads_q = {"fp16": 1, "bf16": 2}[c["dtype"]], int(c["cache"] == "fp8"), c["Hq"]
+    d.num_blocks, d.block_size, d.total_tokens, d.topk = c["nb"], c["bs"], c["T"], c["topk"]
+    d.q_token_stride = (c["Hq"] + c["q_pad"]) * 576
+    out = (ctypes.c_int32 * 6)()
+    assert _capi.load().aule_hip_debug_mla_sparse_plan(ctypes.byref(d), out, 6) == 6, c
+    return out[2], (out[5] << 32) | (out[4] & 0xffffffff)
+
+
+def sparse_ranges(topk, nsplit):
+    """[(first entry, last entry)] of the key ranges that hold an entry: split k owns the 64-entry tiles [k ceil(tiles / nsplit), ...)
+    (csrc/fa_fwd_mla_sparse_gfx950.hip); a forced count is clamped to the tiles as mla_sparse_plan clamps it"""
+    tiles = (topk + 63) // 64
+    nsplit = max(1, min(nsplit, 64, tiles))
+    per = (tiles + nsplit - 1) // nsplit
+    return [(k * per * 64, min((k + 1) * per * 64, topk) - 1) for k in range(nsplit) if k * per * 64 < topk]
+
+
+def sparse_problem(cfg, seed):
+    """(Problem of tests/test_gpu_mla_sparse.py, indices [T, topk] int32, info) of a draw; no GPU.  info: planned (the plan's nsplit),
+    nsplit (the count the draw's launch runs: the forced one after its clamp, else the planned), ws_bytes, scale, bt (the block table of
+    a contiguous-list draw) and probes [(head, position, slot, position of the second listing or None)] of a seam draw"""
+    ts, util = importlib.import_module("test_gpu_mla_sparse"), importlib.import_module("util")
+    c = cfg
+    T, topk = c["T"], c["topk"]
+    p = ts.Problem(seed, c["dtype"], T, c["Hq"], c["nb"], c["bs"], fp8=c["cache"] == "fp8", q_pad=c["q_pad"])
+    rng, S = p.rng, p.S
+    planned, ws_bytes = sparse_plan(c)
+    ranges = sparse_ranges(topk, c["force_nsplit"] or planned)
+    info = dict(planned=planned, nsplit=len(ranges), ws_bytes=ws_bytes, bt=None, probes=[], ranges=ranges,
+                scale=None if c["scale_mul"] is None else c["scale_mul"] / math.sqrt(576.0))
+    if c["dense"] is not None:
+        mb = c["dense"][0] // c["bs"]
+        info["bt"] = bt = np.stack([rng.permutation(c["nb"])[:mb] for _ in range(T)]).astype(np.int32)
+        idx = np.full((T, topk), -1, dtype=np.int32)
+        for t, L in enumerate(c["dense"]):
+            j = np.arange(L)
+            idx[t, :L] = bt[t, j // c["bs"]] * c["bs"] + j % c["bs"]
+        return p, idx, info
+    bad = np.array([-1, S, ts.I32_MIN, ts.I32_MAX], dtype=np.int64)
+    hard = c["hard"]
+    probe_t = hard[1] if hard is not None and hard[0] == "seam" else None
+    nprobe = min(c["Hq"], 16, S - 1)
+    spiked = rng.choice(S, size=nprobe, replace=False) if probe_t is not None else np.zeros(0, dtype=np.int64)
+    idx = np.empty((T, topk), dtype=np.int64)
+    dead = np.zeros((T, topk), dtype=bool)
+    for t in range(T):
+        pool = np.setdiff1d(np.arange(S), spiked) if t == probe_t else np.arange(S)
+        if c["repeat"][t] and t != probe_t:
+            pool = rng.choice(pool, size=max(1, min(len(pool), topk) // 3), replace=False)
+        idx[t] = rng.choice(pool, size=topk, replace=topk > len(pool) or (c["repeat"][t] and t != probe_t))
+        how = c["invalid"][t]
+        if how == "scattered":
+            dead[t] = rng.rand(topk) < 0.25
+        elif how == "tile":
+            k = int(rng.randint((topk + 63) // 64))
+            dead[t, 64 * k:64 * k + 64] = True
+        elif how == "split":      # one whole key range of the launch; a launch of one range: the second half of the tiles
+            first, last = ranges[int(rng.randint(len(ranges)))] if len(ranges) > 1 else (((topk + 63) // 64 + 1) // 2 * 64, topk - 1)
+            dead[t, first:last + 1] = True
+        elif how == "all":
+            dead[t] = True
+    if probe_t is not None:
+        t = probe_t
+        if c["invalid"][t] == "scattered":      # (the list's, the first tile's and the key ranges' ends stay valid: a whole tile would not)
+            dead[t, [s for s in [0, 63, 64, topk - 1] + [e for r in ranges for e in r] if s < topk]] = False
+        live = np.flatnonzero(~dead[t])
+        nprobe = min(nprobe, len(live))
+        # the seam set, in this order and deduplicated: the list's and the first tile's ends, the ends of the key ranges (in a shuffled order,
+        # so that over the draws every range is reached), the edges of the invalid runs, then random entries
+        seams = [0, 63, 64, topk - 1]
+        for k in rng.permutation(len(ranges)):
+            seams += list(ranges[k])
+        d = dead[t].astype(np.int8)
+        seams += list(np.flatnonzero((d[:-1] == 0) & (d[1:] == 1))[:3]) + list(np.flatnonzero((d[:-1] == 1) & (d[1:] == 0))[:3] + 1)
+        seams += list(rng.permutation(live))
+        at = []
+        for s in seams:
+            if 0 <= s < topk and not dead[t, s] and int(s) not in at:
+                at.append(int(s))
+        at = at[:nprobe]
+        taken = set(at)
+        m = -8.0 if info["scale"] is not None and info["scale"] < 0 else 8.0      # (the spiked logit is +8 |q|^2 |scale| under either sign)
+        flat = p.kv.reshape(S, ts.QK)
+        for h, pos in enumerate(at):
+            slot, twice = int(spiked[h]), None
+            idx[t, pos] = slot
+            flat[slot] = util.quantize((m * p.q[t, h]).astype(np.float32), c["dtype"])
+            if h % 2 == 1:       # one probe head in two lists its slot once more, in another tile: lse rises by ln 2, out stays
+                other = [int(s) for s in live if s // 64 != pos // 64 and int(s) not in taken]
+                if other:
+                    twice = other[int(rng.randint(len(other)))]
+                    idx[t, twice] = slot
+                    taken.add(twice)
+            info["probes"].append((h, pos, slot, twice))
+    elif hard is not None:
+        p.kv[..., ts.VD:] = util.quantize((p.kv[..., ts.VD:] + hard[1]).astype(np.float32), c["dtype"])
+    idx[dead] = bad[rng.randint(len(bad), size=int(dead.sum()))]
+    p.vmax = float(np.abs(p.kv[..., :ts.VD]).max())
+    return p, idx.astype(np.int32), info
+
+
+def _sparse_alone(p, t):
+    """the problem of token t alone (the hand file's construction: the same cache, one row of q)"""
+    import copy
+    one = copy.copy(p)
+    one.q, one.T = p.q[t:t + 1], 1
+    return one
+
+
+def sparse_lse_f32_gap(p, idx, scale=None):
+    """max |fp32 log-sum-exp - fp64 log-sum-exp| over the tokens with a valid entry: the error plain NumPy fp32 arithmetic has on these
+    inputs (the hard-data LSE bound of this module follows 4 x this; it never sees a kernel's result)"""
+    sc = np.float32(1.0 / math.sqrt(576.0) if scale is None else scale)
+    flat = p.kv.reshape(p.S, 576).astype(np.float32)
+    _, lref = p.judge(idx, scale)
+    gap = 0.0
+    for t in range(p.T):
+        rows = flat[idx[t][p.valid(idx[t])]]
+        if len(rows):
+            s = p.q[t].astype(np.float32) @ rows.T * sc
+            m = s.max(axis=-1, keepdims=True)
+            lse = m[:, 0] + np.log(np.exp(s - m).sum(axis=-1, dtype=np.float32))
+            gap = max(gap, float(np.abs(lse.astype(np.float64) - lref[t]).max()))
+    return gap
+
+
+def sparse_reference(cfg, seed):
+    """The reference side of a sparse draw; no GPU.  Returns (p, idx, info, (out, lse), facts).  facts: valid = valid entries per token;
+    probes = per probe head (units, dlse): the largest |judge without the spiked entry - judge| over the head's 512 outputs in units of
+    fwd_tol's bound there, and for a slot listed twice lse(judge) - lse(judge without the second listing), else None; one_entry = on a
+    plain draw, the same units for the last valid entry of the token with the most valid entries (None on a hard draw)"""
+    util = importlib.import_module("util")
+    p, idx, info = sparse_problem(cfg, seed)
+    ref = p.judge(idx, info["scale"])
+    atol, rtol = util.fwd_tol(p.dtype, p.vmax)
+    valid = [int(p.valid(idx[t]).sum()) for t in range(p.T)]
+
+    def without(t, pos, h=None):
+        lean = idx[t:t + 1].copy()
+        lean[0, pos] = -1
+        o, l = _sparse_alone(p, t).judge(lean, info["scale"])
+        hs = slice(None) if h is None else h
+        return float((np.abs(o[0][hs] - ref[0][t][hs]) / (atol + rtol * np.abs(ref[0][t][hs]))).max()), l[0]
+
+    facts = dict(valid=valid, probes=[], one_entry=None)
+    if info["probes"]:
+        t = cfg["hard"][1]
+        for h, pos, _, twice in info["probes"]:
+            if twice is None:
+                facts["probes"].append((without(t, pos, h)[0], None))
+            else:      # both listings away: the spike is gone; the second alone away: ln 2 less
+                lean = idx[t:t + 1].copy()
+                lean[0, [pos, twice]] = -1
+                o, _ = _sparse_alone(p, t).judge(lean, info["scale"])
+                units = float((np.abs(o[0][h] - ref[0][t][h]) / (atol + rtol * np.abs(ref[0][t][h]))).max())
+                facts["probes"].append((units, float(ref[1][t][h] - without(t, twice, h)[1][h])))
+    elif cfg["hard"] is None and max(valid) >= 1:
+        t = int(np.argmax(valid))
+        facts["one_entry"] = without(t, int(np.flatnonzero(p.valid(idx[t]))[-1]))[0]
+    return p, idx, info, ref, facts
+
+
+def run_sparse(cfg, seed, stats=None):
+    import ctypes
+    import torch
+    import aule
+    from aule import _capi
+    _, ts, hostile = _mods("test_gpu_mla_sparse", "hostile")
+    c = cfg
+    errs, stats = [], {} if stats is None else stats      # (stats: the caller's dict, filled with the maxima this draw measured)
+    p, idx, info, ref, _ = sparse_reference(c, seed)
+    scale, T, topk, Hq = info["scale"], c["T"], c["topk"], c["Hq"]
+    lse_atol = ts.LSE_ATOL
+    if c["hard"] is not None:
+        stats["lse_f32_gap"] = sparse_lse_f32_gap(p, idx, scale)
+        lse_atol = max(lse_atol, 4.0 * stats["lse_f32_gap"])
+    lib = _capi.get_lib()
+    assert int(lib.aule_attention_mla_sparse_workspace_size(ctypes.byref(ts._desc(torch, p, T, topk)))) == info["ws_bytes"]
+    assert ts.plan_of(torch, p, T, topk)[2] == info["planned"], "the device's plan is not the one the reference side read"
+    run = ts.Launch(torch, p, idx, scale=scale, ws_bytes=info["ws_bytes"] if c["ws"] == "caller" else 0)
+    got = _checked(errs, run.run)
+    if got is None:
+        return cfg, errs
+    res = _checked(errs, ts.check, p, got, idx, "sparse", scale, ref, lse_atol)
+    if res: stats["out"], stats["lse"] = res
+    again = _checked(errs, run.run)
+    if again is not None and not ts._same(torch, again, got): errs.append("two runs give different bits")
+    if not ts._same(torch, run.python(), got): errs.append("Python entry != C entry")
+
+    def forced(n):
+        eff = max(1, min(n, 64, (topk + 63) // 64))      # (mla_sparse_plan's clamp: the workspace is sized for it, ranges without a tile included)
+        ws = (eff * T * Hq * 514 * 4 + 15) // 16 * 16 if c["ws"] == "caller" and eff > 1 else 0
+        f = ts.Launch(torch, p, idx, scale=scale, ws_bytes=ws)
+        f.arena.fill(hostile.POISON)
+        rc = lib.aule_hip_debug_mla_sparse_launch_nsplit(ctypes.byref(f.desc()), n)
+        torch.cuda.synchronize()
+        if rc != 0:
+            raise RuntimeError("aule_hip_debug_mla_sparse_launch_nsplit(%d) refused a valid call: %s" % (n, lib.aule_get_error()))
+        if not f.arena.guards_intact(): errs.append("forced nsplit %d: guard bytes written" % n)
+        if not all(f.arena.unchanged(name, was) for name, was in f.inputs.items()): errs.append("forced nsplit %d: an input was written" % n)
+        return f.out.clone(), f.lse.clone()
+
+    if c["force_nsplit"] is not None:
+        other = forced(c["force_nsplit"])
+        res = _checked(errs, ts.check, p, other, idx, "sparse, forced nsplit %d" % c["force_nsplit"], scale, ref, lse_atol)
+        if res: stats["out"], stats["lse"] = max(stats.get("out", 0.0), res[0]), max(stats.get("lse", 0.0), res[1])
+        if not ts._same(torch, forced(info["planned"]), got): errs.append("the planned nsplit, forced, is not the entry bit for bit")
+    if c["dense"] is not None:
+        dd = _capi.MlaPagedDesc()
+        dd.struct_size = ctypes.sizeof(dd)
+        dd.dtype, dd.batch, dd.heads_q, dd.qk_dim, dd.v_dim = ts.DTYPE_CODE[c["dtype"]], T, Hq, 576, 512
+        dd.block_size, dd.max_blocks, dd.total_tokens, dd.max_seqlen_q, dd.q_token_stride = c["bs"], info["bt"].shape[1], T, 1, (Hq + c["q_pad"]) * 576
+        plan = (ctypes.c_int32 * 6)()
+        assert _capi.load().aule_hip_debug_mla_plan(ctypes.byref(dd), plan, 6) == 6 and plan[2] == 1 and info["planned"] == 1
+        want = aule.flash_attention_mla_paged(run.q, run.kv, torch.from_numpy(info["bt"]).cuda(), torch.tensor(c["dense"], dtype=torch.int32).cuda(),
+                                              scale=scale, return_lse=True)
+        torch.cuda.synchronize()
+        if not ts._same(torch, got, want): errs.append("contiguous lists are not flash_attention_mla_paged bit for bit")
+    return cfg, errs
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------- fp8mma
+def _e4m3_codes(x):
+    """e4m3fn codes (uint8) of an array, round to nearest even, saturating at +-448 as a cache writer does"""
+    import torch
+    return torch.from_numpy(np.clip(np.asarray(x, dtype=np.float32), -448.0, 448.0)).to(torch.float8_e4m3fn).view(torch.uint8).numpy()
+
+
+def fp8mma_problem(cfg, seed):
+    """(Ragged of tests/test_gpu_paged_prefill.py over an FP8 cache, window, scale, the q row (row, head) or None, the spiked (row, head,
+    block, slot, KV head) or None) of a draw; no GPU.  The q row is rewritten in the dtype; hard data is planted in the dequantised keys
+    and those keys are quantised again with the head's k_scale, so the device's codes and the judge's K are what survives of it"""
+    tp, tq, util = (importlib.import_module(n) for n in ("test_gpu_paged_prefill", "test_gpu_paged_query", "util"))
+    c, geo = cfg, ragged_geometry(cfg)
+    p = tp.Ragged(seed, c["dtype"], "fp8", c["Hq"], c["Hkv"], c["D"], c["bs"], c["ns"], c["Ls"], lead=c["lead"], tail=c["tail"],
+                  table_lens=None if c["table_len"] is None else geo["table_lens"], extra_cols=c["extra_cols"])
+    assert (p.T, p.bt.shape[1], p.max_sq) == (geo["T"], geo["max_blocks"], geo["max_sq"])
+    g, qrow, spiked = p.Hq // p.Hkv, None, None
+    if c["qrow"] is not None:
+        kind, b, i, head = c["qrow"]
+        row = int(p.cu[b]) + i
+        x = p.q[row, head].copy()
+        if kind == "zero":
+            x[:] = 0.0
+        elif kind == "big":
+            x[int(np.abs(x).argmax())] *= 100.0
+        else:      # fp16 near its largest finite value, the signs as drawn
+            x = np.where(x < 0, -1.0, 1.0) * (60000.0 - 4000.0 * np.abs(x))
+        p.q[row, head] = util.quantize(x.astype(np.float32), c["dtype"])
+        qrow = (row, head)
+
+    def requantise(sel, values):
+        hk = sel[2]
+        p.kdev[sel] = _e4m3_codes(values / p.ks[hk])
+        p.K[sel] = tq._decode(p.kdev[sel]) * p.ks[hk]
+
+    h = c["hard"]
+    if h is not None and h[0] == "spike":
+        _, m, b, i, head, _, j = h
+        row, blk = int(p.cu[b]) + i, int(p.bt[b][j // p.bs])
+        requantise((blk, j % p.bs, head // g), m * p.q[row, head].astype(np.float64))
+        spiked = (row, head, blk, j % p.bs, head // g)
+    elif h is not None:
+        _, add, hk = h
+        requantise((slice(None), slice(None), hk), p.K[:, :, hk] + add)
+    p._ref = {}
+    return p, c["window"], None if c["scale_mul"] is None else c["scale_mul"] / math.sqrt(c["D"]), qrow, spiked
+
+
+def _fp8mma_rounded(p):
+    """the problem with q replaced by what the kernel multiplies: codes * scales of aule.quantize_rows_fp8 (fp32 values)"""
+    import copy
+    import torch
+    import aule
+    codes, scales = aule.quantize_rows_fp8(torch.from_numpy(p.q))
+    r = copy.copy(p)
+    r.q, r._ref = (codes.float() * scales).numpy(), {}
+    return r
+
+
+def fp8mma_acc_term(p, window, scale):
+    """E_acc [T, Hq]: per row, D 2^-20 |scale| x the largest single product |q_d k_jd| over the keys the row sees (q as the kernel
+    multiplies it: p is _fp8mma_rounded's problem); 0 where a row sees no key and on the rows of no sequence.  The FP8 matrix instruction
+    adds the products of a step aligned to the largest of them and keeps about 20 bits below its leading bit, so a score can be off by
+    D times that unit (measured on rows that see ONE key, where lse is the scaled dot product itself: up to 2^-12.4 of the largest product
+    at D = 128, and nothing when a single product is non-zero; profiles/fuzz_new_serving_kinds.txt), and a log-sum-exp moves by at most the
+    largest error of its scores."""
+    g = p.Hq // p.Hkv
+    sc = abs(1.0 / math.sqrt(p.D) if scale is None else scale)
+    term = np.zeros((p.T, p.Hq))
+    for b, s, n, L in p.sequences():
+        if n == 0 or L == 0:
+            continue
+        j = np.arange(L)
+        k = np.abs(p.K[p.bt[b][j // p.bs], j % p.bs])                          # [L, Hkv, D]
+        pos = L - n + np.arange(n)
+        see = j[None, :] <= pos[:, None]
+        if window > 0:
+            see &= pos[:, None] - j[None, :] < window
+        q = np.abs(p.q[s:s + n].astype(np.float64)).reshape(n, p.Hkv, g, p.D)
+        for i in range(n):
+            if see[i].any():
+                term[s + i] = (q[i][None, :, :, :] * k[see[i]][:, :, None, :]).max(axis=(0, 3)).reshape(p.Hq)
+    return p.D * 2.0 ** -20 * sc * term
+
+
+def fp8mma_reference(cfg, seed):
+    """The reference side of an fp8mma draw; no GPU.  Returns (p, window, scale, facts).  facts: lse_atol -- LSE_ATOL, or on a hard draw
+    max(LSE_ATOL, 4 x lse_f32_gap) with lse_f32_gap the error of a NumPy fp32 log-sum-exp of the q-rounded rows against the fp64 judge;
+    lse_binds -- that term is the wider one; lse_bound [T, Hq] -- lse_atol + 2 E_acc (fp8mma_acc_term), e_acc its largest value on an
+    owned row and acc_binds -- 2 E_acc exceeds lse_atol on some owned row; out_rtol / round_binds -- fwd_tol's rtol, which joins the out bound as rtol |judge|, and
+    whether that is the wider term of the draw; plain_lse_bound -- the bound of the plain entry's LSE against the q-rounded judge; q_gap / lse_q_gap -- the largest distance between the q-rounded and the unrounded judge in out
+    / lse over the owned rows; zero_row -- (the judge's lse on the all-zero q row, ln(visible keys)) or None; spike_units -- on a spike draw
+    the largest |judge with the spiked key's codes zeroed - judge| on the spiked row in units of atol + 2 E_P, else None"""
+    f8, tq, util = (importlib.import_module(n) for n in ("test_gpu_paged_prefill_fp8mma", "test_gpu_paged_query", "util"))
+    c = cfg
+    p, W, scale, qrow, spiked = fp8mma_problem(c, seed)
+    out_j, lse_j, out_p = f8._models(p, W, scale)
+    out_u, lse_u, _ = f8._models(p, W, scale, rounded=False)
+    own = p.owned()
+    fin = own[:, None] & np.isfinite(lse_j)
+    facts = dict(lse_atol=tq.LSE_ATOL, lse_binds=False, lse_f32_gap=0.0, zero_row=None, spike_units=None,
+                 q_gap=float(np.abs(out_j - out_u)[own].max()) if own.any() else 0.0,
+                 lse_q_gap=float(np.abs(lse_j[fin] - lse_u[fin]).max()) if fin.any() else 0.0)
+    if c["hard"] is not None:
+        facts["lse_f32_gap"] = _fp8mma_rounded(p).lse_f32_gap(W, scale)
+        facts["lse_atol"] = max(tq.LSE_ATOL, 4.0 * facts["lse_f32_gap"])
+        facts["lse_binds"] = 4.0 * facts["lse_f32_gap"] > tq.LSE_ATOL
+    # the LSE bound per row: the scalar above + 2 E_acc, the accumulation of the FP8 matrix instruction (fp8mma_acc_term; the factor of E_P)
+    e_acc = fp8mma_acc_term(_fp8mma_rounded(p), W, scale)
+    facts["acc_binds"] = bool((2.0 * e_acc[own] > facts["lse_atol"]).any()) if own.any() else False
+    facts["e_acc"] = float(e_acc[own].max()) if own.any() else 0.0
+    facts["lse_bound"] = facts["lse_atol"] + 2.0 * e_acc
+    atol, rtol = util.fwd_tol(p.dtype, p.vmax)
+    e_p = float(np.abs(out_p - out_j)[own].max()) if own.any() else 0.0
+    # the rounding of out to storage (fwd_tol's rtol |judge|) on top of atol + 2 E_P: the wider term where rows see so few keys that E_P ~ 0
+    facts["out_rtol"], facts["round_binds"] = rtol, bool(own.any()) and rtol * float(np.abs(out_j[own]).max()) > atol + 2.0 * e_p
+    # the plain entry's LSE: its own bound (fp32: LSE_ATOL, 4 x the fp32 gap of the unrounded rows, and 2^-21 of the largest |lse|, four
+    # spacings of fp32 there) plus the distance between the two judges
+    plain_gap = p.lse_f32_gap(W, scale)
+    facts["plain_lse_bound"] = max(tq.LSE_ATOL, 4.0 * plain_gap, 2.0 ** -21 * (float(np.abs(lse_u[fin]).max()) if fin.any() else 0.0)) + facts["lse_q_gap"]
+    if qrow is not None and c["qrow"][0] == "zero":
+        _, b, i, _ = c["qrow"]
+        pos = c["Ls"][b] - c["ns"][b] + i
+        facts["zero_row"] = (float(lse_j[qrow]), math.log(min(pos + 1, W) if W > 0 else pos + 1))
+    if spiked is not None:
+        row, head, blk, slot, hk = spiked
+        lean = _fp8mma_lean(p, blk, slot, hk, row, head)
+        facts["spike_units"] = float(np.abs(f8._models(lean, W, scale)[0][row, head] - out_j[row, head]).max()) / (atol + 2.0 * e_p)
+    return p, W, scale, facts
+
+
+def _fp8mma_lean(p, blk, slot, hk, row, head):
+    """the problem without one key, as q's row (row, head) sees it: the key becomes -1e4 x that row, whose weight is exp(-1e4 |q|^2 scale) = 0"""
+    import copy
+    lean = copy.copy(p)
+    lean.K, lean._ref = p.K.copy(), {}
+    lean.K[blk, slot, hk] = -1e4 * p.q[row, head]
+    return lean
+
+
+def run_fp8mma(cfg, seed, stats=None):
+    import torch
+    import aule
+    _, tp, f8, util = _mods("test_gpu_paged_prefill", "test_gpu_paged_prefill_fp8mma", "util")
+    c = cfg
+    errs, stats = [], {} if stats is None else stats      # (stats: the caller's dict, filled with the maxima this draw measured)
+    p, W, scale, facts = fp8mma_reference(c, seed)
+    lse_atol = facts["lse_atol"]
+    if facts["lse_f32_gap"]: stats["lse_f32_gap"] = facts["lse_f32_gap"]
+    out, lse, intact = tp._run_capi(torch, p, window=W, scale=scale, q_pad=c["q_pad"], entry="aule_attention_paged_prefill_fp8mma_ex")
+    own = p.owned()
+    if not intact: errs.append("wrote in front of or behind out / lse")
+    if not tp._untouched(torch, out, lse, own): errs.append("a row of no sequence was written")
+    res = _checked(errs, f8._judge, p, out, lse, W, "fp8mma", scale=scale, lse_atol=facts["lse_bound"], out_rtol=facts["out_rtol"])
+    stats["e_acc"] = facts["e_acc"]
+    if res: stats["out"], stats["lse"], stats["out_of_bound"] = res
+    (q, kc, vc, bt, cl, cu), scales = p.device(torch, q_pad=c["q_pad"])
+    kw = dict(scale=scale, window_size=W, return_lse=True, **scales)
+    town = torch.from_numpy(own).cuda()
+    for what in ("Python entry != C entry", "two runs give different bits"):
+        o2, l2 = aule.flash_attention_paged_prefill_fp8mma(q, kc, vc, bt, cl, cu, max_seqlen_q=p.max_sq, **kw)
+        torch.cuda.synchronize()
+        if not (_same(torch, o2[town], out[town]) and _same(torch, l2[town], lse[town])): errs.append(what)
+    # sequence 0 alone: rows are quantised independently and a workgroup serves one sequence
+    s, e = int(p.cu[0]), int(p.cu[1])
+    if e > s and p.B > 1:
+        one = torch.tensor([0, e - s], dtype=torch.int32, device="cuda")
+        a, al = aule.flash_attention_paged_prefill_fp8mma(q[s:e], kc, vc, bt[:1], cl[:1], one, **kw)
+        torch.cuda.synchronize()
+        if not (_same(torch, a, out[s:e]) and _same(torch, al, lse[s:e])): errs.append("sequence 0 alone differs from the same sequence in the batch")
+    # the plain entry on the same cache, against the same q-rounded judge: its bound plus the distance between the two judges (from the
+    # reference alone) -- the twin's masks and clamps are this kernel's
+    to, tl = aule.flash_attention_paged_prefill(q, kc, vc, bt, cl, cu, max_seqlen_q=p.max_sq, **kw)
+    torch.cuda.synchronize()
+    out_j, lse_j, _ = f8._models(p, W, scale)
+    atol, rtol = util.fwd_tol(p.dtype, p.vmax)
+    _close(errs, "plain entry vs the q-rounded judge", to[town], torch.from_numpy(out_j[own]), atol + facts["q_gap"], rtol)
+    _lse_close(errs, torch, "plain entry vs the q-rounded judge", tl[town].double().cpu(), torch.from_numpy(lse_j[own]), facts["plain_lse_bound"])
+    return cfg, errs
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------- indexer
+def indexer_problem(cfg, seed):
+    """(Tables, Problem of tests/test_gpu_mla_indexer.py, topk) of a draw, the weights rewritten by the draw's kind; no GPU"""
+    ti = importlib.import_module("test_gpu_mla_indexer")
+    c = cfg
+    tab = ti.Tables(seed, c["bs"], c["ctx"], ns=c["ns"], max_sq=c["max_sq"], cap=c["cap"], extra_rows=c["extra_rows"])
+    p = ti.Problem(seed + 1, c["dtype"], c["H"], tab, fp8=c["fp8"], q_pad=c["q_pad"])
+    h0 = seed % c["H"]
+    if c["weights"] == "one":
+        w = np.zeros_like(p.w)
+        w[:, h0] = np.abs(p.w[:, h0]) * np.sqrt(c["H"]) + 0.5
+        p.w = w
+    elif c["weights"] == "negative":
+        p.w = -np.abs(p.w)
+    elif c["weights"] == "zero":
+        p.w[:, h0] = 0.0
+    return tab, p, min(tab.W + 3, 65536) if c["topk"] == "above" else c["topk"]
+
+
+def indexer_logit_sources(cfg, seed, tab):
+    """{name: float32 [T, W]} -- the logits the top-k kernel is given besides the logits kernel's own: "hand", the row kinds of the hand file
+    rotating over the rows; "ladder", per row a base value plus 0 .. 255 units in the last place, shuffled and with repeats (only the last
+    radix pass separates them); "bits", random 32-bit patterns of both signs with denormals, +-inf and NaN planted"""
+    ti = importlib.import_module("test_gpu_mla_indexer")
+    rng = np.random.RandomState(seed + 7)
+    T, W = tab.T, tab.W
+    hand = np.stack([ti.hand_made(rng, ti.ROW_KINDS[(r + seed) % len(ti.ROW_KINDS)], W) for r in range(T)])
+    base = (rng.randn(T, 1) * np.exp(rng.uniform(-3, 3, size=(T, 1)))).astype(np.float32)
+    base[base == 0] = 1.0
+    ladder = ((base.view(np.int32) & ~0xff) + rng.randint(0, 256, size=(T, W)).astype(np.int32)).view(np.float32)      # (the upper 24 bits shared)
+    bits = rng.randint(0, 2 ** 32, size=(T, W), dtype=np.uint64).astype(np.uint32)
+    special = np.array([0x7f800000, 0xff800000, 0x7fc00000, 0xffc00001, 0x00000001, 0x807fffff, 0x00000000, 0x80000000], dtype=np.uint32)
+    plant = rng.rand(T, W) < 0.1
+    bits[plant] = special[rng.randint(len(special), size=int(plant.sum()))]
+    return dict(hand=hand, ladder=np.ascontiguousarray(ladder), bits=bits.view(np.float32))
+
+
+def indexer_selection_slack(judge_row, topk):
+    """(fp64 logits [p + 1], the floor a selected key's fp64 logit may not fall below): the fp64 value of the k-th largest, k = min(topk,
+    p + 1), minus the row's two largest per-element bounds (a key is selected over another on logits that are each within its bound)"""
+    pos, val, bound = judge_row
+    k = min(topk, pos + 1)
+    two = np.sort(bound)[-2:].sum()
+    return val, np.sort(val)[-k] - two
+
+
+def run_indexer(cfg, seed, stats=None):
+    import torch
+    import aule
+    _, ti, ts = _mods("test_gpu_mla_indexer", "test_gpu_mla_sparse")
+    c = cfg
+    errs, stats = [], {} if stats is None else stats      # (stats: the caller's dict, filled with the maxima this draw measured)
+    tab, p, topk = indexer_problem(c, seed)
+    run = ti.LogitsLaunch(torch, p, pad=c["pad"])
+    got = _checked(errs, run.run)
+    if got is None:
+        return cfg, errs
+    worst = _checked(errs, ti.check_logits, p, got, "indexer")
+    if worst is not None: stats["logits_of_bound"] = worst
+    if not ti.same_owned(torch, p, got, run.python()): errs.append("logits: Python entry != C entry")
+    again = _checked(errs, run.run)
+    if again is not None and not ti.same_bits(torch, got, again): errs.append("logits: two runs give different bits")
+    if c["fp8"] == "unit":
+        as16 = _checked(errs, ti.LogitsLaunch(torch, p, as_codes=False, pad=c["pad"]).run)
+        if as16 is not None and not ti.same_bits(torch, got, as16): errs.append("the FP8 call with unit scales != the 16-bit call on the converted codes")
+    # top-k, judged exactly on four sources of logits (the rows of no sequence of the kernel's own logits hold 0xFF: NaN bits, never read)
+    own = got.numpy()[:, :tab.W].copy()
+    sources = dict(indexer_logit_sources(c, seed, tab), own=own)
+    for name in INDEXER_SOURCES:
+        _checked(errs, ti.check_topk, torch, tab, sources[name], topk, "top-k on %s logits" % name, pad=c["pad"], kinds=(c["positions"],))
+    # the selection against fp64: every selected key's fp64 logit is at least the k-th largest fp64 logit minus the row's two largest bounds
+    lists = ti.TopkLaunch(torch, tab, own, topk, c["pad"]).run(c["positions"]).numpy()
+    judge = p.judge()
+    short = 0.0
+    for row, b, pos in tab.rows():
+        if pos < 0:
+            continue
+        mine = lists[row][lists[row] >= 0].astype(np.int64)
+        if not c["positions"]:
+            back = np.full(tab.nb * tab.bs, -1, dtype=np.int64)
+            back[tab.slots(b, pos + 1)] = np.arange(pos + 1)
+            mine = back[mine]
+        if len(mine) != min(topk, pos + 1) or (mine < 0).any() or (mine > pos).any():
+            errs.append("row %d: the list does not hold min(topk, p + 1) visible keys" % row); break
+        val, floor = indexer_selection_slack(judge[row], topk)
+        short = max(short, float((floor - val[mine]).max()))
+    stats["selection_short"] = max(short, 0.0)
+    if short > 0.0: errs.append("a selected key's fp64 logit is %.3g below the k-th largest minus the two largest bounds" % short)
+    if c["pipeline"] is not None:
+        # the lists through the sparse MLA over a latent cache that shares the table and the block size, judged on those lists
+        sp = ts.Problem(seed + 2, c["dtype"], tab.T, c["pipeline"], tab.nb, tab.bs)
+        idx = lists.astype(np.int32)
+        res = _checked(errs, lambda: ts.check(sp, ts.Launch(torch, sp, idx).run(), idx, "indexer lists through the sparse MLA"))
+        if res: stats["out"], stats["lse"] = res
+        dev = aule.mla_indexer(run.q, run.w, run.k, run.bt, run.cl, topk, cu_seqlens_q=run.cu, max_seqlen_q=tab.max_sq if tab.cu is not None else None,
+                               k_scale=run.ks if run.fp8 else None) if tab.cu is not None or tab.T == tab.B else None
+        if dev is not None:
+            torch.cuda.synchronize()
+            owned = sorted(r for r, _, _ in tab.rows())
+            if not np.array_equal(dev.cpu().numpy()[owned], lists[owned]): errs.append("aule.mla_indexer != the two C entries")
+    return cfg, errs
+
+
+RUN = dict(indexer=run_indexer, prefill=run_prefill, cascade=run_cascade, mla=run_mla, varlen=run_varlen, sinks=run_sinks, tree=run_tree, mlapf=run_mlapf,
+           sparse=run_sparse, fp8mma=run_fp8mma)
+# data seed of draw i: SEED0[kind] + i
+SEED0 = dict(prefill=31000, cascade=32000, mla=33000, varlen=34000, sinks=35000, tree=36000, mlapf=37000, sparse=38000, indexer=39000, fp8mma=40000)
 
 
 def run_slice(kind, n, seed):
