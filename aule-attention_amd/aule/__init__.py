@@ -338,6 +338,40 @@ def flash_attention_mla_paged_fp8(q, kv_cache, block_tables, context_lens, cu_se
                          return_lse=return_lse, kv_scale=kv_scale)
 
 
+def flash_attention_mla_paged_tree(q, kv_cache, tree_mask, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None,
+                                   return_lse=False, kv_scale=None):
+    """flash_attention_mla_paged / _fp8 for a TREE of new tokens per sequence instead of a chain: the verify step of tree drafters (MTP
+    heads, EAGLE, Medusa) on the DeepSeek-V2 / V3 / R1 family, over the latent cache, in one call -- the latent is read once per
+    sequence, not once per root-to-leaf path.  Not in the reference.  The contract is aule_mla_paged_tree_desc in include/aule.h; in short:
+
+        kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576]): of q's dtype, or torch.float8_e4m3fn codes with
+          kv_scale (None = 1.0, a float, or a 0-d / [1] tensor that stays on the device) -- the kind is read from kv_cache.dtype, and
+          kv_scale with a 16-bit cache is a ValueError;
+        tree_mask [total_tokens] int64, contiguous, on q's device, indexed by packed token: one 64-bit word per new token
+          (tree_mask_from_parents builds them).  The kernel reads the words on every launch: no host copy, no synchronisation,
+          capturable; a graph replay sees the current words;
+        cu_seqlens_q [batch + 1] int32 is required (a tree of one node per sequence is the decode call);
+        every other argument, the clamps, the rows that are written and the result: flash_attention_mla_paged.
+    The rule is flash_attention_paged_prefill_tree's.  With L_b and n_b the clamped length and number of new tokens, a sequence with
+    n_b <= 64 carries a tree (decided on the device): new token t is key L_b - n_b + t, and token i sees key j iff 0 <= j < L_b and
+        j < L_b - n_b  (a context key)      or      bit j - (L_b - n_b) of tree_mask[s_b + i] is set.
+    Any bit pattern is legal; a set bit at or beyond L_b is ignored; a token at a negative position (L_b < n_b) sees nothing; a row that
+    sees no key gives out = 0 and lse = -inf.  A sequence with n_b > 64 (a prompt chunk in the same step) keeps the causal rule and its
+    words are not read.  The chain words tree_mask[s_b + i] = (2 << i) - 1 give flash_attention_mla_paged's / _fp8's out and lse bit
+    for bit (finite cached data).  Argument errors are ValueErrors raised before the device is touched; the only device->host
+    synchronisation is max_seqlen_q=None's.
+    Out of scope: more than 64 tree tokens per sequence, a window or sink logits (the MLA entries have neither), the cascade, any
+    backward, and tree visibility inside mla_indexer: callers on DSA models filter the lists it emits by the tree themselves and
+    pass them to flash_attention_mla_sparse."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_paged_tree
+    return mla_paged_tree(q, kv_cache, _required_tree_mask(tree_mask), block_tables, context_lens, cu_seqlens_q, max_seqlen_q=max_seqlen_q,
+                          scale=scale, return_lse=return_lse, kv_scale=kv_scale)
+
+
 def flash_attention_mla_sparse(q, kv_cache, indices, scale=None, return_lse=False, kv_scale=None):
     """Sparse multi-head latent attention (DeepSeek-V3.2 "DSA" and its derivatives, absorbed form): every query token attends
     to the rows of the latent cache that ITS OWN list names -- what the model's indexer picked, typically 2048 keys -- in
@@ -585,8 +619,8 @@ def flash_attention_paged_query_tree(q, k_cache, v_cache, tree_mask, block_table
     0 are ignored.  A query at a negative position gives a row of zeros; a row that sees no key gives out = 0 and lse = -inf.  The chain
     words tree_mask[b, i] = (2 << i) - 1 give flash_attention_paged_query's out and lse bit for bit (finite cached data).  Wrong dtype,
     shape, device or a non-contiguous tree_mask raise ValueError before any launch.
-    Out of scope: sliding windows over a tree, sink logits together with a tree, the cascade and the MLA entries, head_dim 256, more than
-    64 tree tokens per sequence, any backward."""
+    Out of scope: sliding windows over a tree, sink logits together with a tree, the cascade, head_dim 256, more than 64 tree tokens per
+    sequence, any backward.  A tree over the latent cache of the MLA models is flash_attention_mla_paged_tree."""
     try:
         import torch  # noqa: F401
     except ImportError as e:
@@ -603,8 +637,8 @@ def flash_attention_paged_prefill_tree(q, k_cache, v_cache, tree_mask, block_tab
     decided on the device -- and token i of it reads the word of row s_b + i; a longer sequence (a prompt chunk in the same step) keeps the
     causal rule of flash_attention_paged_prefill and its words are not read.  Every other argument and rule as
     flash_attention_paged_prefill; there is no window_size.  Chain words give that call's out and lse bit for bit.
-    Out of scope: sliding windows over a tree, sink logits together with a tree, the cascade and the MLA entries, head_dim 256, more than
-    64 tree tokens per sequence, any backward."""
+    Out of scope: sliding windows over a tree, sink logits together with a tree, the cascade, head_dim 256, more than 64 tree tokens per
+    sequence, any backward.  A tree over the latent cache of the MLA models is flash_attention_mla_paged_tree."""
     try:
         import torch  # noqa: F401
     except ImportError as e:
@@ -631,7 +665,8 @@ def tree_mask_from_parents(parents):
 
 def _required_tree_mask(tree_mask):
     if tree_mask is None:
-        raise ValueError("tree_mask must be an int64 tensor (the call without a tree: flash_attention_paged_query / flash_attention_paged_prefill)")
+        raise ValueError("tree_mask must be an int64 tensor (the call without a tree: flash_attention_paged_query / flash_attention_paged_prefill / "
+                         "flash_attention_mla_paged)")
     return tree_mask
 
 
@@ -945,7 +980,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

@@ -198,6 +198,11 @@ class MlaPagedFp8Desc(ctypes.Structure):
     _fields_ = MlaPagedDesc._fields_ + [("kv_scale", ctypes.c_void_p)]
 
 
+class MlaPagedTreeDesc(ctypes.Structure):
+    """struct aule_mla_paged_tree_desc (include/aule.h): aule_mla_paged_fp8_desc field for field, then the tree words and the cache kind."""
+    _fields_ = MlaPagedFp8Desc._fields_ + [("tree_mask", ctypes.c_void_p), ("cache_dtype", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
 class MlaSparseDesc(ctypes.Structure):
     """struct aule_mla_sparse_desc (include/aule.h): absorbed MLA over per-token key lists, both cache kinds."""
     _fields_ = [
@@ -596,6 +601,8 @@ SIGNATURES = [
     ("aule_attention_mla_paged_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedDesc)]),
     ("aule_attention_mla_paged_fp8_ex", _I32, [ctypes.POINTER(MlaPagedFp8Desc)]),
     ("aule_attention_mla_paged_fp8_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedFp8Desc)]),
+    ("aule_attention_mla_paged_tree_ex", _I32, [ctypes.POINTER(MlaPagedTreeDesc)]),
+    ("aule_attention_mla_paged_tree_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedTreeDesc)]),
     ("aule_attention_mla_sparse_ex", _I32, [ctypes.POINTER(MlaSparseDesc)]),
     ("aule_attention_mla_sparse_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaSparseDesc)]),
     ("aule_mla_indexer_logits_ex", _I32, [ctypes.POINTER(MlaIndexerLogitsDesc)]),

@@ -1356,10 +1356,31 @@ def _latent_cache_kind(what, dtype, kv_cache, fp8, kv_scale, sixteen):
         raise ValueError("kv_scale applies to a float8_e4m3fn cache only; a 16-bit cache holds the values themselves")
 
 
-def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale):
-    """Both cache kinds of the paged MLA: one validation, one descriptor (the FP8 kind's is the 16-bit kind's plus kv_scale)."""
+_NO_TREE = object()   # (None is a caller's mistake where words are expected)
+
+
+def mla_paged_tree(q, kv_cache, tree_mask, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None, return_lse=False,
+                   kv_scale=None):
+    """mla_paged / mla_paged_fp8 with a tree of new tokens per sequence (csrc/fa_fwd_mla_verify_gfx950.hip behind
+    aule_attention_mla_paged_tree_ex; aule.flash_attention_mla_paged_tree documents the arguments).  The cache kind is kv_cache's dtype;
+    tree_mask [total_tokens] int64 on q's device is read by the kernel on every launch.  Validation, descriptor prefix, workspace and the
+    one possible synchronisation (max_seqlen_q = None) are mla_paged's."""
+    return _mla_paged(None, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale, tree_mask)
+
+
+def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale, tree_mask=_NO_TREE):
+    """Both cache kinds of the paged MLA: one validation, one descriptor (the FP8 kind's is the 16-bit kind's plus kv_scale; the tree
+    kind's is the FP8 kind's plus the words and the cache kind, which it reads from kv_cache's dtype: fp8 = None)."""
     kv_cache = _latent_shapes(q, kv_cache)
-    if fp8:
+    tree = tree_mask is not _NO_TREE
+    if tree:
+        fp8 = kv_cache.dtype != q.dtype
+        _latent_cache_kind("q", q.dtype, kv_cache, fp8, kv_scale, "a 16-bit cache has q's dtype")
+        if cu_seqlens_q is None:
+            raise ValueError("cu_seqlens_q is required with tree_mask: a tree of one node per sequence is the decode call "
+                             "(flash_attention_mla_paged / _fp8)")
+        _tree_mask_check(tree_mask, (q.shape[0],), "[total_tokens]", q)
+    elif fp8:
         _latent_cache_kind("q", q.dtype, kv_cache, True, kv_scale, "a 16-bit cache is flash_attention_mla_paged's")
     elif q.dtype not in (torch.float16, torch.bfloat16) or kv_cache.dtype != q.dtype:
         raise ValueError(f"q and kv_cache must share one of fp16 / bf16, got {q.dtype} and {kv_cache.dtype}")
@@ -1385,7 +1406,7 @@ def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_s
     out, lse, result = _ragged_result(q, 512, return_lse)
     if T * B * Hq == 0:
         return result
-    d = _capi.MlaPagedFp8Desc() if fp8 else _capi.MlaPagedDesc()
+    d = _capi.MlaPagedTreeDesc() if tree else _capi.MlaPagedFp8Desc() if fp8 else _capi.MlaPagedDesc()
     d.struct_size = ctypes.sizeof(d)
     d.dtype = _DTYPES[q.dtype]
     d.batch, d.heads_q, d.qk_dim, d.v_dim = B, Hq, 576, 512
@@ -1398,14 +1419,15 @@ def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_s
     d.block_tables, d.context_lens = bt.data_ptr(), cl.data_ptr()
     d.cu_seqlens_q = cu.data_ptr() if cu is not None else None
     d.lse = lse.data_ptr() if lse is not None else None
+    entry = "aule_attention_mla_paged_tree" if tree else "aule_attention_mla_paged_fp8" if fp8 else "aule_attention_mla_paged"
     if fp8:
-        ks = _fp8_scale(kv_scale, 1, q.device, "kv_scale")
-        d.kv_scale = ks.data_ptr()
-        held += [ks, kv_cache, _attach_workspace(d, lib.aule_attention_mla_paged_fp8_workspace_size, q.device)]
-        _capi.check(lib.aule_attention_mla_paged_fp8_ex(ctypes.byref(d)), "aule_attention_mla_paged_fp8_ex")
-        return result
-    held += [kv_cache, _attach_workspace(d, lib.aule_attention_mla_paged_workspace_size, q.device)]
-    _capi.check(lib.aule_attention_mla_paged_ex(ctypes.byref(d)), "aule_attention_mla_paged_ex")
+        held.append(_fp8_scale(kv_scale, 1, q.device, "kv_scale"))
+        d.kv_scale = held[-1].data_ptr()
+    if tree:
+        d.tree_mask = tree_mask.data_ptr()
+        d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    held += [kv_cache, _attach_workspace(d, getattr(lib, entry + "_workspace_size"), q.device)]   # held until the launch is queued
+    _capi.check(getattr(lib, entry + "_ex")(ctypes.byref(d)), entry + "_ex")
     return result
 
 

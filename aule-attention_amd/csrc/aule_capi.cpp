@@ -97,6 +97,20 @@ static_assert(sizeof(aule_mla_paged_fp8_desc) == 144 && offsetof(aule_mla_paged_
                   offsetof(aule_mla_paged_fp8_desc, workspace) == offsetof(aule_mla_paged_desc, workspace) &&
                   offsetof(aule_mla_paged_fp8_desc, workspace_bytes) == offsetof(aule_mla_paged_desc, workspace_bytes),
               "aule_mla_paged_fp8_desc starts with aule_mla_paged_desc (the MLA entry points read both through that prefix)");
+// The tree kind of the paged MLA: the FP8 kind field for field (so the 16-bit kind too), then tree_mask and cache_dtype.
+#define AULE_MLA_TREE_SAME(f) (offsetof(aule_mla_paged_tree_desc, f) == offsetof(aule_mla_paged_fp8_desc, f))
+static_assert(sizeof(aule_mla_paged_tree_desc) == 160 && offsetof(aule_mla_paged_tree_desc, tree_mask) == 144 &&
+                  offsetof(aule_mla_paged_tree_desc, tree_mask) == sizeof(aule_mla_paged_fp8_desc) &&
+                  offsetof(aule_mla_paged_tree_desc, cache_dtype) == 152 && offsetof(aule_mla_paged_tree_desc, reserved) == 156 &&
+                  offsetof(aule_mla_paged_tree_desc, kv_scale) == 136 && AULE_MLA_TREE_SAME(dtype) && AULE_MLA_TREE_SAME(batch) &&
+                  AULE_MLA_TREE_SAME(heads_q) && AULE_MLA_TREE_SAME(qk_dim) && AULE_MLA_TREE_SAME(v_dim) && AULE_MLA_TREE_SAME(block_size) &&
+                  AULE_MLA_TREE_SAME(max_blocks) && AULE_MLA_TREE_SAME(total_tokens) && AULE_MLA_TREE_SAME(max_seqlen_q) && AULE_MLA_TREE_SAME(scale) &&
+                  AULE_MLA_TREE_SAME(device) && AULE_MLA_TREE_SAME(q_token_stride) && AULE_MLA_TREE_SAME(stream) && AULE_MLA_TREE_SAME(q) &&
+                  AULE_MLA_TREE_SAME(kv_cache) && AULE_MLA_TREE_SAME(block_tables) && AULE_MLA_TREE_SAME(context_lens) &&
+                  AULE_MLA_TREE_SAME(cu_seqlens_q) && AULE_MLA_TREE_SAME(out) && AULE_MLA_TREE_SAME(lse) && AULE_MLA_TREE_SAME(workspace) &&
+                  AULE_MLA_TREE_SAME(workspace_bytes) && AULE_MLA_TREE_SAME(kv_scale),
+              "aule_mla_paged_tree_desc is aule_mla_paged_fp8_desc plus tree_mask and cache_dtype");
+#undef AULE_MLA_TREE_SAME
 static_assert(sizeof(aule_mla_sparse_desc) == 120 && offsetof(aule_mla_sparse_desc, dtype) == 4 && offsetof(aule_mla_sparse_desc, cache_dtype) == 8 &&
                   offsetof(aule_mla_sparse_desc, heads_q) == 12 && offsetof(aule_mla_sparse_desc, num_blocks) == 16 &&
                   offsetof(aule_mla_sparse_desc, block_size) == 20 && offsetof(aule_mla_sparse_desc, total_tokens) == 24 &&
@@ -1548,9 +1562,10 @@ int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* d) {
     return launched("Paged cascade attention", rc);
 }
 
-// The paged MLA: one latent cache, 576 / 512, ragged queries as the prefill's or plain decode (null cu_seqlens_q).  Two kinds:
-// aule_mla_paged_fp8_desc is aule_mla_paged_desc field for field plus kv_scale (the layout asserts at the top of this file), so both are
-// checked and read through that prefix; `fp8` says which one `d` is.  One checker for all their readers, built from the paged kinds'
+// The paged MLA: one latent cache, 576 / 512, ragged queries as the prefill's or plain decode (null cu_seqlens_q).  Three kinds:
+// aule_mla_paged_fp8_desc is aule_mla_paged_desc field for field plus kv_scale, aule_mla_paged_tree_desc is that plus tree_mask and
+// cache_dtype (the layout asserts at the top of this file), so all are checked and read through that prefix; `kind` says which one
+// `d` is.  One checker for all their readers, built from the paged kinds'
 // pieces where the fields are alike; `launch`: the pointer rules of a call that has something to do as well (the size queries and the
 // plan hook read no pointer).  Host logic only, asked before the device is needed.
 extern "C++" {
@@ -1576,11 +1591,25 @@ static int32_t mla_launch_tail(const Desc* d, const aule_hip::MlaPlan& plan, con
 }
 }   // extern "C++"
 
+enum MlaKind { kMla16, kMlaFp8, kMlaTree };
 static const aule_mla_paged_desc* mla_prefix(const aule_mla_paged_fp8_desc* d) { return reinterpret_cast<const aule_mla_paged_desc*>(d); }
+static const aule_mla_paged_desc* mla_tree_prefix(const aule_mla_paged_tree_desc* d) { return reinterpret_cast<const aule_mla_paged_desc*>(d); }
+// (`d` read as the larger kinds, where `kind` says it is one)
+static const aule_mla_paged_tree_desc* mla_tree(const aule_mla_paged_desc* d) { return reinterpret_cast<const aule_mla_paged_tree_desc*>(d); }
+static size_t mla_desc_size(MlaKind kind) {
+    return kind == kMlaTree ? sizeof(aule_mla_paged_tree_desc) : kind == kMlaFp8 ? sizeof(aule_mla_paged_fp8_desc) : sizeof(aule_mla_paged_desc);
+}
+// (the cache holds e4m3fn codes: the FP8 kind, or the tree kind with that cache_dtype; `d` has its kind's size)
+static bool mla_cache_is_fp8(const aule_mla_paged_desc* d, MlaKind kind) {
+    return kind == kMlaFp8 || (kind == kMlaTree && mla_tree(d)->cache_dtype == AULE_KV_CACHE_FP8_E4M3);
+}
 static const char* varlen_stride_error(const char* name, int64_t stride, uint64_t token, const char* heads, Reason& why);   // (the token stride rule, below)
-static const char* mla_paged_desc_error(const aule_mla_paged_desc* d, bool fp8, bool launch, Reason& why) {
-    if (d == nullptr || d->struct_size != (fp8 ? sizeof(aule_mla_paged_fp8_desc) : sizeof(aule_mla_paged_desc))) return kBadDescriptor;
-    if (!is_16_bit(d->dtype)) return fp8 ? kDtypeOfQ : "dtype (of q / out / kv_cache) must be fp16 or bf16";
+static const char* mla_paged_desc_error(const aule_mla_paged_desc* d, MlaKind kind, bool launch, Reason& why) {
+    if (d == nullptr || d->struct_size != mla_desc_size(kind)) return kBadDescriptor;
+    if (!is_16_bit(d->dtype)) return kind != kMla16 ? kDtypeOfQ : "dtype (of q / out / kv_cache) must be fp16 or bf16";
+    if (kind == kMlaTree && cache_dtype_error(mla_tree(d)->cache_dtype))
+        return reasonf(why, "cache_dtype %d must be AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3", mla_tree(d)->cache_dtype);
+    const bool fp8 = mla_cache_is_fp8(d, kind);
     if (d->qk_dim != 576 || d->v_dim != 512) return reasonf(why, "qk_dim %u / v_dim %u unsupported (576 / 512 only)", d->qk_dim, d->v_dim);
     if (const char* e = paged_blocks_error(d)) return e;
     if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
@@ -1588,6 +1617,8 @@ static const char* mla_paged_desc_error(const aule_mla_paged_desc* d, bool fp8, 
     if (d->batch >= (1u << 30) || d->total_tokens >= (1u << 30)) return "batch / total_tokens too large";
     if (((uint64_t)d->total_tokens + 64) * d->heads_q > 0x7fffffffull) return "total_tokens * heads_q too large (packed rows are counted in 32 bits)";
     if (ragged_nothing_to_do(d)) return nullptr;
+    if (kind == kMlaTree && d->cu_seqlens_q == nullptr)
+        return "null cu_seqlens_q (a tree of one node per sequence is the decode call: aule_attention_mla_paged_ex / _fp8_ex)";
     if (d->cu_seqlens_q == nullptr && d->total_tokens < d->batch) return "cu_seqlens_q is null (plain decode: sequence b owns row b) and total_tokens < batch";
     if (!launch) return nullptr;
     if (!d->q || !d->kv_cache || !d->block_tables || !d->context_lens || !d->out) return "null tensor pointer";
@@ -1597,11 +1628,16 @@ static const char* mla_paged_desc_error(const aule_mla_paged_desc* d, bool fp8, 
         if (kv_scale == nullptr) return "null kv_scale (one fp32 value on the device)";
         if ((reinterpret_cast<uintptr_t>(kv_scale) & 3) != 0) return "kv_scale must be 4-byte aligned";
     }
+    if (kind == kMlaTree) {
+        if (!fp8 && mla_tree(d)->kv_scale != nullptr) return "kv_scale applies to an FP8 cache only (cache_dtype AULE_KV_CACHE_FP8_E4M3)";
+        if (mla_tree(d)->tree_mask == nullptr) return kNullTreeMask;
+        if ((reinterpret_cast<uintptr_t>(mla_tree(d)->tree_mask) & 7) != 0) return "tree_mask must be 8-byte aligned";
+    }
     return nullptr;
 }
 
-// (`d` passed mla_paged_desc_error with the same `fp8`)
-static void fill_mla_paged_args(const aule_mla_paged_desc* d, bool fp8, aule_hip::MlaArgs& a) {
+// (`d` passed mla_paged_desc_error with the same `kind`)
+static void fill_mla_paged_args(const aule_mla_paged_desc* d, MlaKind kind, aule_hip::MlaArgs& a) {
     a.q = d->q; a.kv_cache = d->kv_cache; a.out = d->out; a.lse = d->lse;
     a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
     a.T = (int)d->total_tokens; a.B = (int)d->batch; a.Hq = (int)d->heads_q;
@@ -1611,24 +1647,25 @@ static void fill_mla_paged_args(const aule_mla_paged_desc* d, bool fp8, aule_hip
     a.scale = resolve_scale(d->scale, d->qk_dim);
     a.dtype = d->dtype;
     a.device = d->device;
-    if (fp8) {
+    if (mla_cache_is_fp8(d, kind)) {
         a.cache_kind = aule_hip::kCacheFp8E4M3;
         a.kv_scale = reinterpret_cast<const aule_mla_paged_fp8_desc*>(d)->kv_scale;
     }
+    if (kind == kMlaTree) a.tree_mask = reinterpret_cast<const long long*>(mla_tree(d)->tree_mask);
 }
 
-// (both kinds' launch entry; `what`: the kind's error prefix)
-static int32_t mla_paged_launch(const aule_mla_paged_desc* d, bool fp8, const char* what) {
+// (every kind's launch entry; `what`: the kind's error prefix)
+static int32_t mla_paged_launch(const aule_mla_paged_desc* d, MlaKind kind, const char* what) {
     std::lock_guard<std::mutex> lk(g_mu);
     Reason text;
-    if (const char* why = mla_paged_desc_error(d, fp8, true, text)) {
+    if (const char* why = mla_paged_desc_error(d, kind, true, text)) {
         set_error("%s failed: %s", what, why);
         return -3;
     }
     if (ragged_nothing_to_do(d)) return 0;
     if (!initialised()) return -1;
     aule_hip::MlaArgs a;
-    fill_mla_paged_args(d, fp8, a);
+    fill_mla_paged_args(d, kind, a);
     const aule_hip::MlaPlan plan = aule_hip::mla_plan(a);
     if (plan.grid <= 0 || plan.grid > 0x7fffffffll) {
         set_error("%s failed: the grid (row blocks * nsplit * batch) exceeds 2^31 - 1 workgroups", what);
@@ -1639,12 +1676,17 @@ static int32_t mla_paged_launch(const aule_mla_paged_desc* d, bool fp8, const ch
 
 int32_t aule_attention_mla_paged_ex(const aule_mla_paged_desc* d) {
     RoctxRange range("aule.mla_paged");
-    return mla_paged_launch(d, false, "Paged MLA attention");
+    return mla_paged_launch(d, kMla16, "Paged MLA attention");
 }
 
 int32_t aule_attention_mla_paged_fp8_ex(const aule_mla_paged_fp8_desc* d) {
     RoctxRange range("aule.mla_paged_fp8");
-    return mla_paged_launch(mla_prefix(d), true, "Paged MLA FP8 attention");
+    return mla_paged_launch(mla_prefix(d), kMlaFp8, "Paged MLA FP8 attention");
+}
+
+int32_t aule_attention_mla_paged_tree_ex(const aule_mla_paged_tree_desc* d) {
+    RoctxRange range("aule.mla_paged_tree");
+    return mla_paged_launch(mla_tree_prefix(d), kMlaTree, "Paged MLA tree attention");
 }
 
 // The sparse MLA: per-token key lists over the latent cache, both cache kinds in one descriptor.  One checker for all its readers;
@@ -2613,25 +2655,30 @@ uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_de
 }
 
 // (the launch's plan: mla_plan reads the shape, none of the pointers)
-static bool mla_paged_plan(const aule_mla_paged_desc* d, bool fp8, aule_hip::MlaPlan& plan) {
+static bool mla_paged_plan(const aule_mla_paged_desc* d, MlaKind kind, aule_hip::MlaPlan& plan) {
     Reason text;
-    if (mla_paged_desc_error(d, fp8, false, text)) return false;
+    if (mla_paged_desc_error(d, kind, false, text)) return false;
     plan = aule_hip::MlaPlan();
     if (ragged_nothing_to_do(d)) return true;
     aule_hip::MlaArgs a;
-    fill_mla_paged_args(d, false, a);   // (the plan reads the shape: no pointer, not the cache kind)
+    fill_mla_paged_args(d, kMla16, a);   // (the plan reads the shape: no pointer, not the cache kind, not the words)
     plan = aule_hip::mla_plan(a);
     return plan.grid <= 0x7fffffffll;
 }
 
 uint64_t aule_attention_mla_paged_workspace_size(const aule_mla_paged_desc* d) {
     aule_hip::MlaPlan plan;
-    return mla_paged_plan(d, false, plan) ? plan.ws_bytes : 0;
+    return mla_paged_plan(d, kMla16, plan) ? plan.ws_bytes : 0;
 }
 
 uint64_t aule_attention_mla_paged_fp8_workspace_size(const aule_mla_paged_fp8_desc* d) {
     aule_hip::MlaPlan plan;
-    return mla_paged_plan(mla_prefix(d), true, plan) ? plan.ws_bytes : 0;
+    return mla_paged_plan(mla_prefix(d), kMlaFp8, plan) ? plan.ws_bytes : 0;
+}
+
+uint64_t aule_attention_mla_paged_tree_workspace_size(const aule_mla_paged_tree_desc* d) {
+    aule_hip::MlaPlan plan;
+    return mla_paged_plan(mla_tree_prefix(d), kMlaTree, plan) ? plan.ws_bytes : 0;
 }
 
 uint64_t aule_attention_mla_sparse_workspace_size(const aule_mla_sparse_desc* d) {
@@ -2718,7 +2765,7 @@ int32_t aule_hip_debug_shared_prefix_plan(const aule_paged_cascade_desc* d, int3
  * workspace query read.  Pure host logic like the forward hook. */
 int32_t aule_hip_debug_mla_plan(const aule_mla_paged_desc* d, int32_t* out, int32_t cap) {
     aule_hip::MlaPlan plan;
-    if (!mla_paged_plan(d, false, plan)) return -3;
+    if (!mla_paged_plan(d, kMla16, plan)) return -3;
     if (plan.grid <= 0) return 0;
     return dump_plan({plan.row_blocks, plan.rows_per_block, plan.nsplit, (int32_t)plan.grid}, &plan.ws_bytes, out, cap);
 }

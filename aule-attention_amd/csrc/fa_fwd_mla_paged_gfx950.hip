@@ -4,7 +4,8 @@
 // One cache [num_blocks, block_size, 576] of q's dtype: row `pos` of a sequence is the key of ALL query heads (576 elements: 512
 // compressed dimensions, then 64 rotary ones) and its first 512 elements are the value.  q [T, Hq, 576], out [T, Hq, 512].
 // (Or a cache of e4m3fn codes with one fp32 scale: its attention kernel is the same body, fa_mla_common.h, instantiated in
-// fa_fwd_mla_paged_fp8_gfx950.hip; plan, launch and combine are the ones here.)
+// fa_fwd_mla_paged_fp8_gfx950.hip; plan, launch and combine are the ones here.  With tree masks -- a tree of new tokens per sequence
+// instead of the chain -- the same body once more, fa_fwd_mla_verify_gfx950.hip, behind the same plan, launch and combine.)
 // Per sequence, read and clamped HERE exactly as the paged prefill does:
 //     L = clamp(context_lens[b], 0, max_blocks * block_size)        s = clamp(cu[b], 0, T)      e = clamp(cu[b + 1], s, T)
 //     n = min(e - s, max_seqlen_q)  (cu == null: s = b, n = 1);   token i < n is row s + i, sits at p = L - n + i, sees key j iff j <= p.
@@ -153,7 +154,11 @@ int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_
     p.max_blocks = a.max_blocks;
     p.max_sq = seqlen_cut(a.max_seqlen_q, a.T);
     int rc;
-    if (p.kv_scale != nullptr) {
+    if (a.tree_mask != nullptr) {   // (either cache kind; fa_fwd_mla_verify_gfx950.hip)
+        if (a.cu_seqlens_q == nullptr) return -1;
+        p.tree_mask = a.tree_mask;
+        rc = launch_mla_verify_kernel(p, plan.grid, a.dtype, stream);
+    } else if (p.kv_scale != nullptr) {
         rc = launch_mla_fp8_kernel(p, plan.grid, a.dtype, stream);
     } else {
         rc = dispatch_16bit(a.dtype, [&](auto t) {

@@ -370,6 +370,10 @@ struct MlaArgs {
     int device = -1;                    // as FwdArgs::device
     int cache_kind = kCache16;          // element type of kv_cache (dtype is the type of q / out)
     const float* kv_scale = nullptr;    // kCacheFp8E4M3 only: [1] fp32, device
+    // Tree masks (fa_fwd_mla_verify_gfx950.hip; the contract is aule_mla_paged_tree_desc): [T] int64 on the device, one word per packed
+    // token -- a sequence with at most 64 new tokens sees the context and the new tokens its words name, a longer one stays causal.
+    // Needs cu_seqlens_q; null: the causal chain.  Plan, workspace and combine do not depend on it.
+    const long long* tree_mask = nullptr;
 };
 // The launch plan (mla_plan, beside the kernel: the one statement of the rule for launch, workspace query and debug hook).
 constexpr int kMlaRows = 64;       // packed rows (token-major, head-minor) per workgroup

@@ -1,7 +1,8 @@
 // fa_mla_common.h -- what the translation units of the absorbed MLA share (fa_fwd_mla_paged_gfx950.hip: caches of q's dtype, the
 // combine, the plan and the launch; fa_fwd_mla_paged_fp8_gfx950.hip: caches of e4m3fn codes; fa_fwd_mla_sparse_gfx950.hip: keys from a
-// per-token list): the sizes, the kernels' parameter struct, the clamps of the contract, the latent tile per cache kind, the list's
-// key source and the ONE body of the attention kernel.  The layout and the arithmetic are described at the top of
+// per-token list; fa_fwd_mla_verify_gfx950.hip: the dense call with a tree of new tokens): the sizes, the kernels' parameter struct, the
+// clamps of the contract, the latent tile per cache kind, the list's key source, the tree's visibility words and the ONE body of the
+// attention kernel.  The layout and the arithmetic are described at the top of
 // fa_fwd_mla_paged_gfx950.hip.  Device code only.
 #pragma once
 #include "fa_kernels.h"
@@ -32,6 +33,9 @@ struct MlaParams {
     const int* list = nullptr;   // [T][topk] slots; an entry outside [0, slots) is skipped
     int topk = 0;
     int slots = 0;               // rows of the cache read as a flat array
+    // The dense call with tree masks (fa_fwd_mla_verify_gfx950.hip): one word per packed token, read by those instances alone.  The LAST
+    // field: every other instance, the combine included, keeps its argument offsets.
+    const long long* tree_mask = nullptr;   // [T] int64
 };
 
 
@@ -39,6 +43,9 @@ struct MlaParams {
 int launch_mla_fp8_kernel(const MlaParams& p, long long grid, int dtype, hipStream_t stream);
 // ... and the sparse call's (`p` as launch_mla_sparse fills it, kv_scale set), beside it in that translation unit.
 int launch_mla_sparse_fp8_kernel(const MlaParams& p, long long grid, int dtype, hipStream_t stream);
+// The dense call's attention kernel with tree masks, either cache kind (fa_fwd_mla_verify_gfx950.hip; `p` as launch_mla_paged fills it,
+// tree_mask and cu set).
+int launch_mla_verify_kernel(const MlaParams& p, long long grid, int dtype, hipStream_t stream);
 // The combine of either call's partials (fa_fwd_mla_paged_gfx950.hip): row_blocks * p.B * 16 workgroups, after the attention kernel.
 int launch_mla_combine(const MlaParams& p, int row_blocks, int dtype, hipStream_t stream);
 
@@ -170,6 +177,59 @@ struct MlaNoList {
     __device__ __forceinline__ bool visible(int, int) const { return false; }
 };
 
+// The tree call's visibility (tree masks: DESIGN.md 3.18; the rule is aule_mla_paged_tree_desc's in include/aule.h).  A sequence with
+// n <= 64 new tokens carries a tree: its token at position base + i, base = L - n, sees key j < L iff j < base or bit j - base of ITS
+// word is set; a longer sequence keeps the causal rule and no word is read.  Either way the lane states what its row sees of a tile
+// as ONE 64-bit word, built once per tile from the lane's word (kept as two 32-bit halves; 64-bit shifts happen here, a handful per
+// tile, never per element), and shifted by the lane half's row offset into two 32-bit words exactly as MlaListKeys does -- so the
+// per-element test is the list's: the COMPILE-TIME bit crow(rr, 0) of word kk, one test where the dense twin has two compares, in a
+// tile of pure context as in a tile of new tokens.
+struct MlaTreeKeys {
+    unsigned lo, hi32;   // the lane's word; a causal row: unused
+    int base;            // tree: L - n, the first new token's position; causal: the row's last visible key + 1
+    bool tree;           // wave-uniform: the sequence carries a tree
+    unsigned w[2];
+    // (pos: the row's position, L - n + token; word: where the row's word lies)
+    __device__ __forceinline__ MlaTreeKeys(const long long* word, int L, int n, int pos) {
+        tree = n <= 64;
+        lo = 0; hi32 = 0;
+        base = pos + 1;
+        if (tree) {
+            const unsigned long long x = (unsigned long long)*word;
+            // a row at a negative position sees nothing, whatever its word says
+            lo = pos < 0 ? 0u : (unsigned)x;
+            hi32 = pos < 0 ? 0u : (unsigned)(x >> 32);
+            base = L - n;
+        }
+    }
+    // the low `count` bits set, count clamped to 0 .. 64
+    static __device__ __forceinline__ unsigned long long low_bits(int count) {
+        return count >= 64 ? ~0ull : count <= 0 ? 0ull : (1ull << count) - 1ull;
+    }
+    // bit t of the tile's word: key k0 + t counts for this row (kend: the end of the workgroup's key range, at most L)
+    __device__ __forceinline__ void tile_mask(int k0, int kend, int hi) {
+        const int d = base - k0;   // keys of the tile below base: context keys (tree), or every visible key (causal)
+        unsigned long long vm = low_bits(d);
+        if (tree) {
+            const unsigned long long x = ((unsigned long long)hi32 << 32) | lo;
+            // bit b of the word is key base + b = bit d + b of the tile (b < n <= 64)
+            vm |= d >= 64 || d <= -64 ? 0ull : d >= 0 ? x << d : x >> -d;
+        }
+        vm &= low_bits(kend - k0);
+        w[0] = (unsigned)(vm >> (4 * hi));
+        w[1] = (unsigned)(vm >> (32 + 4 * hi));
+    }
+    __device__ __forceinline__ bool visible(int kk, int rr) const { return ((w[kk] >> crow(rr, 0)) & 1u) != 0; }
+};
+
+// (what the other instances hold in its place: nothing)
+struct MlaNoTree {
+    static constexpr bool tree = false;
+    __device__ __forceinline__ MlaNoTree(const long long*, int, int, int) {}
+    __device__ __forceinline__ void tile_mask(int, int, int) {}
+    __device__ __forceinline__ bool visible(int, int) const { return false; }
+};
+
 // One latent tile of 64 keys on its way from the block pool to LDS: thread t takes rows (t >> 3) and (t >> 3) + 32 of the tile,
 // 8-element chunks (t & 7) + 8 i of each -- 16 bytes of a 16-bit cache (Kv16), 8 codes of an FP8 one (KvFp8), which store() converts
 // exactly (cvt8) to the 16-bit type, so the image in LDS is the same for both kinds.
@@ -229,9 +289,11 @@ struct MlaTile {
 // The attention kernel's body, one for both cache kinds (KV: Kv16 / KvFp8 of fa_paged_tile.h) and both key sources (kList: the sparse
 // call's list instead of a sequence's positions): the kinds differ in how a tile reaches the image (MlaTile) and in where the FP8
 // scale enters, the sources in the block of rows, the key range, the cache row behind a key and the scores that count -- each a
-// compile-time choice at its one place, so that the dense instances compile to what they were without the list.  Ls: the latent image
-// (kMlaLdsImage bytes), Xs: the partial scores (kMlaLdsScores bytes), both 16-byte aligned LDS of the calling kernel.
-template <class T, class KV, bool kList = false>
+// compile-time choice at its one place, so that the dense instances compile to what they were without the list.  kTree (the dense
+// source only): the tree call -- the end of the key range and the scores that count are MlaTreeKeys', again one compile-time choice
+// each.  Ls: the latent image (kMlaLdsImage bytes), Xs: the partial scores (kMlaLdsScores bytes), both 16-byte aligned LDS of the
+// calling kernel.
+template <class T, class KV, bool kList = false, bool kTree = false>
 __device__ __forceinline__ void mla_paged_body(const MlaParams& p, char* Ls, char* Xs) {
 
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
@@ -254,12 +316,15 @@ __device__ __forceinline__ void mla_paged_body(const MlaParams& p, char* Ls, cha
     const int pos = L - n + tok;
 
     // this split's keys of this block: whole tiles of the sequence's own length, cut at the block's last visible key (or whole
-    // tiles of the token's list: `keys`)
+    // tiles of the token's list: `keys`).  A sequence with a tree is NOT cut at the block's last position: a node may see a new token
+    // behind its own.
+    static_assert(!(kList && kTree), "a tree is a rule over a sequence's positions");
     typename std::conditional<kList, MlaListKeys, MlaNoList>::type keys(p, b, split);
+    typename std::conditional<kTree, MlaTreeKeys, MlaNoTree>::type tree(kTree ? p.tree_mask + (blk.s + tok) : nullptr, L, n, pos);
     const int tiles = (L + kMlaKeys - 1) / kMlaKeys;
     const int per = (tiles + p.nsplit - 1) / p.nsplit;
     const int kbeg = kList ? keys.kbeg : split * per * kMlaKeys;
-    const int kend = kList ? keys.kend : min(min((split + 1) * per * kMlaKeys, L), L - n + (r0 + rows - 1) / p.Hq + 1);
+    const int kend = kList ? keys.kend : min(min((split + 1) * per * kMlaKeys, L), kTree && tree.tree ? L : L - n + (r0 + rows - 1) / p.Hq + 1);
     const int ntiles = kend > kbeg ? (kend - kbeg + kMlaKeys - 1) / kMlaKeys : 0;
     const int* tab = p.table + (long long)b * p.max_blocks;
 
@@ -330,6 +395,7 @@ __device__ __forceinline__ void mla_paged_body(const MlaParams& p, char* Ls, cha
             keys.tile_mask(hi);                     // this tile's validity word, from the entries fetched a tile ago
             keys.fetch_mask(k0 + kMlaKeys, lane);   // ... and the next tile's entries
         }
+        if constexpr (kTree) tree.tile_mask(k0, kend, hi);
         float mx = -__builtin_inff();
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
@@ -340,7 +406,7 @@ __device__ __forceinline__ void mla_paged_body(const MlaParams& p, char* Ls, cha
                 for (int i = 0; i < 4; ++i) {
                     const int rr = 4 * q4 + i;
                     const int j = k0 + 32 * kk + crow(rr, hi);
-                    const float x = (kList ? keys.visible(kk, rr) : j <= pos && j < kend) ? (sc[kk][rr] + y[i]) * c : -__builtin_inff();
+                    const float x = (kList ? keys.visible(kk, rr) : kTree ? tree.visible(kk, rr) : j <= pos && j < kend) ? (sc[kk][rr] + y[i]) * c : -__builtin_inff();
                     sc[kk][rr] = x;
                     mx = fmaxf(mx, x);
                 }

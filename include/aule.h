@@ -425,7 +425,8 @@ uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_de
 /* 16-byte aligned, allocates on the stream.  No host synchronisation, and no allocation when a workspace is passed: captures into a  */
 /* hipGraph, and a replay sees the CURRENT cu_seqlens_q, context_lens and block_tables.  With hostile cu_seqlens_q that make two      */
 /* sequences own the same row, that row's value is unspecified (and nothing outside out / lse is written).                            */
-/* An FP8 latent cache is aule_attention_mla_paged_fp8_ex below; the write side of both caches is aule_mla_kv_append_ex.              */
+/* An FP8 latent cache is aule_attention_mla_paged_fp8_ex below; the write side of both caches is aule_mla_kv_append_ex; a tree of   */
+/* new tokens instead of the chain (tree drafters) is aule_attention_mla_paged_tree_ex below.                                        */
 /* Not built: a sliding window; a backward.  The non-absorbed prefill form (192 / 128) is aule_attention_mla_prefill_ex below.       */
 /* The descriptor is checked before the device is needed: -3 for a refused descriptor and 0 for one with nothing to do               */
 /* (total_tokens = 0, batch = 0 or heads_q = 0) are answered without aule_init().                                                     */
@@ -500,6 +501,61 @@ typedef struct aule_mla_paged_fp8_desc {
 int32_t aule_attention_mla_paged_fp8_ex(const aule_mla_paged_fp8_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  The number aule_attention_mla_paged_workspace_size gives for the shape. */
 uint64_t aule_attention_mla_paged_fp8_workspace_size(const aule_mla_paged_fp8_desc* desc);
+
+/* Paged MLA with TREE MASKS (additive): the verify step of tree drafters (MTP heads, EAGLE, Medusa, SpecInfer) over the latent cache   */
+/* of either kind -- all nodes of a sequence's tree are appended to the cache and verified in one call, the latent read once per      */
+/* sequence instead of once per root-to-leaf path.  The rule is the paged prefill tree's (TREE MASKS below), unchanged: tree_mask      */
+/* holds one int64 word per packed token on the DEVICE, read as 64 bits by the kernel on every launch (no host copy, no                */
+/* synchronisation, capturable: a replay sees the current words).  With L_b, s_b and n_b the values aule_mla_paged_desc clamps on the  */
+/* device, a sequence with n_b <= 64 carries a tree (decided on the device): its token i is row s_b + i, sits at p = L_b - n_b + i,    */
+/* and sees key j iff 0 <= j < L_b and                                                                                                 */
+/*     j < L_b - n_b  (a context key)        or        bit j - (L_b - n_b) of tree_mask[s_b + i] is set.                                */
+/* Any bit pattern is legal: no self bit is implied, no order required; a set bit at or beyond L_b is ignored; a token at a negative   */
+/* position (L_b < n_b) sees nothing.  A sequence with n_b > 64 (a prompt chunk in the same step) keeps aule_mla_paged_desc's causal   */
+/* rule and its words are not read.  A row without a visible key gives zeros and lse = -inf; rows of no sequence are never written.    */
+/* The chain words tree_mask[s_b + i] = (2 << i) - 1 give out and lse of aule_attention_mla_paged_ex / _fp8_ex BIT FOR BIT (finite     */
+/* cached data).  There is no window and there are no sinks: the MLA entries have neither.                                             */
+/* The descriptor is aule_mla_paged_fp8_desc field for field through offset 143 -- the same rules, clamps, rows, launches, plan,       */
+/* workspace and combine (aule_hip_debug_mla_plan answers for this kind too: the plan depends on the shape alone) -- and then          */
+/* tree_mask and cache_dtype: AULE_KV_CACHE_SAME (kv_cache of q's dtype; kv_scale must be NULL) or AULE_KV_CACHE_FP8_E4M3 (e4m3fn      */
+/* codes; kv_scale required, aule_mla_paged_fp8_desc's rule).  Refused with -3 and a reason, without aule_init(), beyond what the      */
+/* twins refuse: a NULL cu_seqlens_q (a tree of one node per sequence is the decode call: aule_attention_mla_paged_ex), a NULL or not  */
+/* 8-byte aligned tree_mask when there is work, a cache_dtype that is neither, kv_scale given with a 16-bit cache.                     */
+/* Not built: more than 64 tree tokens per sequence; the cascade; tree visibility inside the MLA indexer (callers on DSA models filter */
+/* the emitted lists and call aule_attention_mla_sparse_ex); any backward.                                                             */
+typedef struct aule_mla_paged_tree_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_paged_tree_desc) = 160 */
+    int32_t dtype;             /* offset 4; type of q / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    uint32_t batch;            /* offset 8; sequences */
+    uint32_t heads_q;          /* offset 12 */
+    uint32_t qk_dim;           /* offset 16; 576 */
+    uint32_t v_dim;            /* offset 20; 512 */
+    uint32_t block_size;       /* offset 24; any value > 0 */
+    uint32_t max_blocks;       /* offset 28; columns of block_tables */
+    uint32_t total_tokens;     /* offset 32; rows of q / out; 0: returns 0 without a launch */
+    uint32_t max_seqlen_q;     /* offset 36; >= 1: sizes the grid, and caps every n_b */
+    float scale;               /* offset 40; 0 -> 1/sqrt(576) */
+    int32_t device;            /* offset 44; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 48; elements, >= heads_q * 576, a multiple of 8 */
+    void* stream;              /* offset 56; hipStream_t */
+    const void* q;             /* offset 64; [total_tokens, heads_q, 576], 16-bit */
+    const void* kv_cache;      /* offset 72; [num_blocks, block_size, 576], q's dtype or e4m3fn codes (cache_dtype) */
+    const int32_t* block_tables;   /* offset 80; [batch, max_blocks] */
+    const int32_t* context_lens;   /* offset 88; [batch]: keys per sequence, the new ones included */
+    const int32_t* cu_seqlens_q;   /* offset 96; [batch + 1], device; required */
+    void* out;                 /* offset 104; [total_tokens, heads_q, 512], 16-bit, contiguous */
+    float* lse;                /* offset 112; optional (NULL to skip): [total_tokens, heads_q] fp32 */
+    void* workspace;           /* offset 120; optional, size from aule_attention_mla_paged_tree_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 128 */
+    const float* kv_scale;     /* offset 136; [1] fp32, device (AULE_KV_CACHE_FP8_E4M3), else NULL */
+    const int64_t* tree_mask;  /* offset 144; [total_tokens] int64, device, 8-byte aligned (required when there is work) */
+    int32_t cache_dtype;       /* offset 152; AULE_KV_CACHE_SAME (q's dtype) or AULE_KV_CACHE_FP8_E4M3 */
+    uint32_t reserved;         /* offset 156; padding, not read */
+} aule_mla_paged_tree_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure.  Checked before the device is needed, as above. */
+int32_t aule_attention_mla_paged_tree_ex(const aule_mla_paged_tree_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  The number aule_attention_mla_paged_workspace_size gives for the shape. */
+uint64_t aule_attention_mla_paged_tree_workspace_size(const aule_mla_paged_tree_desc* desc);
 
 /* SPARSE MLA (additive): absorbed multi-head latent attention over PER-TOKEN KEY LISTS (DeepSeek-V3.2 "DSA" and its derivatives: an    */
 /* indexer picks a fixed number of keys per query token, typically 2048, and the attention runs over only those rows of the latent     */
@@ -923,7 +979,8 @@ uint64_t aule_attention_paged_query_sink_workspace_size(const aule_paged_query_s
 /* twin's causal rule and its words are not read.  Every other rule, the workspace included, is the twin's: each descriptor is its   */
 /* twin field for field plus tree_mask and is checked by the twin's checker.  Refused with -3 and a reason, without aule_init():     */
 /* a NULL tree_mask when there is work, and window_size > 0 (a window is not defined over a tree).  Not built: sliding windows or    */
-/* sink logits with a tree, the cascade and the MLA entries, head_dim 256, more than 64 tree tokens per sequence, any backward.      */
+/* sink logits with a tree, the cascade, head_dim 256, more than 64 tree tokens per sequence, any backward.  The same rule over    */
+/* the latent cache of the MLA models is aule_attention_mla_paged_tree_ex above.                                                    */
 typedef struct aule_paged_query_tree_desc {
     uint32_t struct_size;      /* = sizeof(aule_paged_query_tree_desc) = 160 */
     int32_t dtype;
