@@ -338,6 +338,24 @@ def flash_attention_mla_paged_fp8(q, kv_cache, block_tables, context_lens, cu_se
                          return_lse=return_lse, kv_scale=kv_scale)
 
 
+def flash_attention_mla_paged_fp8mma(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, scale=None,
+                                     return_lse=False, kv_scale=None):
+    """flash_attention_mla_paged_fp8 with BOTH matrix products in FP8 (v_mfma_scale_f32_32x32x64_f8f6f4 on the cache's codes as
+    they are; csrc/fa_fwd_mla_paged_fp8mma_gfx950.hip).  Opt-in: nothing routes here.  The arguments, the clamps,
+    the rows that are written and the result are flash_attention_mla_paged_fp8's, with two rounding rules added: each packed row of
+    q is quantised inside the kernel by quantize_rows_fp8's rule (one scale over its 576 elements), and the softmax weights are
+    rounded to e4m3 before the PV product (the denominator sums the fp32 values).  Its own ValueErrors: a cache that is not
+    torch.float8_e4m3fn, and kv_scale = None (pass the scale quantize_mla_cache_fp8 returned, or 1.0).  No host synchronisation
+    beyond the twin's (max_seqlen_q = None with offsets given); capturable."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_paged_fp8mma
+    return mla_paged_fp8mma(q, kv_cache, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, scale=scale,
+                            return_lse=return_lse, kv_scale=kv_scale)
+
+
 def flash_attention_mla_paged_tree(q, kv_cache, tree_mask, block_tables, context_lens, cu_seqlens_q, max_seqlen_q=None, scale=None,
                                    return_lse=False, kv_scale=None):
     """flash_attention_mla_paged / _fp8 for a TREE of new tokens per sequence instead of a chain: the verify step of tree drafters (MTP
@@ -980,7 +998,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

@@ -601,6 +601,8 @@ SIGNATURES = [
     ("aule_attention_mla_paged_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedDesc)]),
     ("aule_attention_mla_paged_fp8_ex", _I32, [ctypes.POINTER(MlaPagedFp8Desc)]),
     ("aule_attention_mla_paged_fp8_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedFp8Desc)]),
+    ("aule_attention_mla_paged_fp8mma_ex", _I32, [ctypes.POINTER(MlaPagedFp8Desc)]),
+    ("aule_attention_mla_paged_fp8mma_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedFp8Desc)]),
     ("aule_attention_mla_paged_tree_ex", _I32, [ctypes.POINTER(MlaPagedTreeDesc)]),
     ("aule_attention_mla_paged_tree_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedTreeDesc)]),
     ("aule_attention_mla_sparse_ex", _I32, [ctypes.POINTER(MlaSparseDesc)]),

@@ -1341,6 +1341,18 @@ def mla_paged_fp8(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, ma
     return _mla_paged(True, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale)
 
 
+def mla_paged_fp8mma(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, scale=None, return_lse=False, kv_scale=None):
+    """mla_paged_fp8 through the kernel with FP8 matrix products (csrc/fa_fwd_mla_paged_fp8mma_gfx950.hip behind
+    aule_attention_mla_paged_fp8mma_ex): the twin's descriptor, validation and workspace.  kv_scale is required here: the products run on
+    the codes, and a caller who has none has no FP8 cache."""
+    if torch.is_tensor(kv_cache) and kv_cache.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"flash_attention_mla_paged_fp8mma needs a torch.float8_e4m3fn latent cache, got {kv_cache.dtype} "
+                         f"(a 16-bit cache is flash_attention_mla_paged's)")
+    if kv_scale is None:
+        raise ValueError("flash_attention_mla_paged_fp8mma needs kv_scale (a float, or a 0-d / [1] tensor): the scale of the codes")
+    return _mla_paged(True, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale, entry="aule_attention_mla_paged_fp8mma")
+
+
 def _latent_cache_kind(what, dtype, kv_cache, fp8, kv_scale, sixteen):
     """The cache-kind rules of the two MLA readers and the latent append: a cache of the 16-bit `dtype`, or (fp8) torch.float8_e4m3fn
     codes with ONE scale -- None, a float, a 0-d or [1] tensor.  sixteen: where a 16-bit cache goes, for the message."""
@@ -1368,9 +1380,11 @@ def mla_paged_tree(q, kv_cache, tree_mask, block_tables, context_lens, cu_seqlen
     return _mla_paged(None, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale, tree_mask)
 
 
-def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale, tree_mask=_NO_TREE):
+def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, scale, return_lse, kv_scale, tree_mask=_NO_TREE,
+               entry=None):
     """Both cache kinds of the paged MLA: one validation, one descriptor (the FP8 kind's is the 16-bit kind's plus kv_scale; the tree
-    kind's is the FP8 kind's plus the words and the cache kind, which it reads from kv_cache's dtype: fp8 = None)."""
+    kind's is the FP8 kind's plus the words and the cache kind, which it reads from kv_cache's dtype: fp8 = None).  entry: another
+    C entry over the kind's descriptor (the FP8-product twin of the FP8 kind)."""
     kv_cache = _latent_shapes(q, kv_cache)
     tree = tree_mask is not _NO_TREE
     if tree:
@@ -1419,7 +1433,7 @@ def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_s
     d.block_tables, d.context_lens = bt.data_ptr(), cl.data_ptr()
     d.cu_seqlens_q = cu.data_ptr() if cu is not None else None
     d.lse = lse.data_ptr() if lse is not None else None
-    entry = "aule_attention_mla_paged_tree" if tree else "aule_attention_mla_paged_fp8" if fp8 else "aule_attention_mla_paged"
+    entry = entry or ("aule_attention_mla_paged_tree" if tree else "aule_attention_mla_paged_fp8" if fp8 else "aule_attention_mla_paged")
     if fp8:
         held.append(_fp8_scale(kv_scale, 1, q.device, "kv_scale"))
         d.kv_scale = held[-1].data_ptr()

@@ -1654,8 +1654,8 @@ static void fill_mla_paged_args(const aule_mla_paged_desc* d, MlaKind kind, aule
     if (kind == kMlaTree) a.tree_mask = reinterpret_cast<const long long*>(mla_tree(d)->tree_mask);
 }
 
-// (every kind's launch entry; `what`: the kind's error prefix)
-static int32_t mla_paged_launch(const aule_mla_paged_desc* d, MlaKind kind, const char* what) {
+// (every kind's launch entry; `what`: the kind's error prefix; fp8mma: the FP8 kind through the kernel with FP8 matrix products)
+static int32_t mla_paged_launch(const aule_mla_paged_desc* d, MlaKind kind, const char* what, bool fp8mma = false) {
     std::lock_guard<std::mutex> lk(g_mu);
     Reason text;
     if (const char* why = mla_paged_desc_error(d, kind, true, text)) {
@@ -1671,7 +1671,9 @@ static int32_t mla_paged_launch(const aule_mla_paged_desc* d, MlaKind kind, cons
         set_error("%s failed: the grid (row blocks * nsplit * batch) exceeds 2^31 - 1 workgroups", what);
         return -3;
     }
-    return mla_launch_tail(d, plan, what, [&](void* ws, hipStream_t stream) { return aule_hip::launch_mla_paged(a, plan, ws, stream); });
+    return mla_launch_tail(d, plan, what, [&](void* ws, hipStream_t stream) {
+        return fp8mma ? aule_hip::launch_mla_paged_fp8mma(a, plan, ws, stream) : aule_hip::launch_mla_paged(a, plan, ws, stream);
+    });
 }
 
 int32_t aule_attention_mla_paged_ex(const aule_mla_paged_desc* d) {
@@ -1682,6 +1684,11 @@ int32_t aule_attention_mla_paged_ex(const aule_mla_paged_desc* d) {
 int32_t aule_attention_mla_paged_fp8_ex(const aule_mla_paged_fp8_desc* d) {
     RoctxRange range("aule.mla_paged_fp8");
     return mla_paged_launch(mla_prefix(d), kMlaFp8, "Paged MLA FP8 attention");
+}
+
+int32_t aule_attention_mla_paged_fp8mma_ex(const aule_mla_paged_fp8_desc* d) {
+    RoctxRange range("aule.mla_paged_fp8mma");
+    return mla_paged_launch(mla_prefix(d), kMlaFp8, "Paged MLA FP8-product attention", true);
 }
 
 int32_t aule_attention_mla_paged_tree_ex(const aule_mla_paged_tree_desc* d) {
@@ -2674,6 +2681,10 @@ uint64_t aule_attention_mla_paged_workspace_size(const aule_mla_paged_desc* d) {
 uint64_t aule_attention_mla_paged_fp8_workspace_size(const aule_mla_paged_fp8_desc* d) {
     aule_hip::MlaPlan plan;
     return mla_paged_plan(mla_prefix(d), kMlaFp8, plan) ? plan.ws_bytes : 0;
+}
+
+uint64_t aule_attention_mla_paged_fp8mma_workspace_size(const aule_mla_paged_fp8_desc* d) {
+    return aule_attention_mla_paged_fp8_workspace_size(d);   // (one plan)
 }
 
 uint64_t aule_attention_mla_paged_tree_workspace_size(const aule_mla_paged_tree_desc* d) {

@@ -140,12 +140,13 @@ MlaPlan mla_plan(const MlaArgs& a) {
     return mla_split_plan(rb, a.B, ((long long)a.block_size * a.max_blocks + kMlaKeys - 1) / kMlaKeys, a.T, a.Hq, a.device);
 }
 
-// (`ws`: plan.ws_bytes bytes, 16-byte aligned, when plan.nsplit > 1)
-int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream) {
+// What every dense launcher refuses and fills (this file's and fa_fwd_mla_paged_fp8mma_gfx950.hip's): `p` for the attention kernel and
+// the combine, tree_mask apart.  -1: refused.
+int mla_paged_params(const MlaArgs& a, const MlaPlan& plan, void* ws, MlaParams& p) {
     if ((long long)plan.row_blocks * a.B * kMlaCombineParts > 0x7fffffffll) return -1;
     if ((long long)a.block_size * a.max_blocks >= (1ll << 30)) return -1;
     if (a.cu_seqlens_q == nullptr && a.T < a.B) return -1;
-    MlaParams p;   // (list stays null, its default: that is what tells the combine kernel that these are a dense call's partials)
+    // (list stays null, its default: that is what tells the combine kernel that these are a dense call's partials)
     if (mla_common_params(a, plan, ws, p) != 0) return -1;
     p.table = a.block_tables; p.ctx = a.context_lens; p.cu = a.cu_seqlens_q;
     p.B = a.B;
@@ -153,6 +154,13 @@ int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_
     p.bs_shift = shift_of(a.block_size);
     p.max_blocks = a.max_blocks;
     p.max_sq = seqlen_cut(a.max_seqlen_q, a.T);
+    return 0;
+}
+
+// (`ws`: plan.ws_bytes bytes, 16-byte aligned, when plan.nsplit > 1)
+int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream) {
+    MlaParams p;
+    if (mla_paged_params(a, plan, ws, p) != 0) return -1;
     int rc;
     if (a.tree_mask != nullptr) {   // (either cache kind; fa_fwd_mla_verify_gfx950.hip)
         if (a.cu_seqlens_q == nullptr) return -1;

@@ -387,6 +387,10 @@ struct MlaPlan {
 };
 MlaPlan mla_plan(const MlaArgs& a);   // all zero: nothing to launch; no pointer is read
 int launch_mla_paged(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream);   // -1: unsupported arguments
+// The same call over an FP8 cache with both matrix products in FP8 (fa_fwd_mla_paged_fp8mma_gfx950.hip): q's rows are
+// quantised in the kernel, the weights rounded to e4m3.  The same plan, workspace and combine.  -1 also for a 16-bit cache, a null
+// kv_scale and a tree mask.
+int launch_mla_paged_fp8mma(const MlaArgs& a, const MlaPlan& plan, void* ws, hipStream_t stream);
 
 // Sparse latent attention (fa_fwd_mla_sparse_gfx950.hip): q [T, Hq, 576] against the rows of the latent cache that a per-token list
 //   names -- indices [T, topk] int32, entry = a slot (row of the cache read as a flat [slots, 576] array); an entry outside [0, slots)

@@ -46,6 +46,9 @@ int launch_mla_sparse_fp8_kernel(const MlaParams& p, long long grid, int dtype, 
 // The dense call's attention kernel with tree masks, either cache kind (fa_fwd_mla_verify_gfx950.hip; `p` as launch_mla_paged fills it,
 // tree_mask and cu set).
 int launch_mla_verify_kernel(const MlaParams& p, long long grid, int dtype, hipStream_t stream);
+// The dense call's `p` for MlaArgs `a` (fa_fwd_mla_paged_gfx950.hip: its refusals and every field but tree_mask), for its launcher and
+// for the FP8-product kernel's (fa_fwd_mla_paged_fp8mma_gfx950.hip, which declares nothing here: launch_mla_paged_fp8mma is fa_kernels.h's).
+int mla_paged_params(const MlaArgs& a, const MlaPlan& plan, void* ws, MlaParams& p);
 // The combine of either call's partials (fa_fwd_mla_paged_gfx950.hip): row_blocks * p.B * 16 workgroups, after the attention kernel.
 int launch_mla_combine(const MlaParams& p, int row_blocks, int dtype, hipStream_t stream);
 

@@ -502,6 +502,16 @@ int32_t aule_attention_mla_paged_fp8_ex(const aule_mla_paged_fp8_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  The number aule_attention_mla_paged_workspace_size gives for the shape. */
 uint64_t aule_attention_mla_paged_fp8_workspace_size(const aule_mla_paged_fp8_desc* desc);
 
+/* The same call with BOTH matrix products in FP8 (additive, opt-in: nothing routes here).  The descriptor, its rules, the clamps, the */
+/* rows that are written, the plan, the workspace and every refusal are aule_attention_mla_paged_fp8_ex's; two rounding rules are      */
+/* added.  Each packed row of q is quantised in the kernel with one scale over its 576 elements, s_q = max|q| / 448 (1 for a zero    */
+/* row), codes = e4m3(sat448(q / s_q)); and the softmax weights are rounded to e4m3 as exp2((s - m) + 8) before the PV product, the   */
+/* denominator summing the fp32 values.  So out and lse differ from the twin's by those two roundings and no more; lse is that of the */
+/* scores of the quantised q.  NaN codes in cache slots that no visible key names are never read.                                     */
+int32_t aule_attention_mla_paged_fp8mma_ex(const aule_mla_paged_fp8_desc* desc);
+/* aule_attention_mla_paged_fp8_workspace_size's number. */
+uint64_t aule_attention_mla_paged_fp8mma_workspace_size(const aule_mla_paged_fp8_desc* desc);
+
 /* Paged MLA with TREE MASKS (additive): the verify step of tree drafters (MTP heads, EAGLE, Medusa, SpecInfer) over the latent cache   */
 /* of either kind -- all nodes of a sequence's tree are appended to the cache and verified in one call, the latent read once per      */
 /* sequence instead of once per root-to-leaf path.  The rule is the paged prefill tree's (TREE MASKS below), unchanged: tree_mask      */

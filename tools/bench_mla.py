@@ -18,6 +18,12 @@ aule.quantize_mla_cache_fp8 (the scale a device tensor), the two alternated roun
 same build.  Before a leg is timed the FP8 call with kv_scale = 1 is compared bit for bit with the 16-bit call on the converted codes.
 Per leg: both medians and spreads, 16-bit / FP8 (below 1: FP8 is slower) and the code bytes of the batch (B L 576) over the FP8 time.
 
+--fp8mma: the same 36 shapes with aule.flash_attention_mla_paged_fp8 (16-bit MFMAs on converted codes) NEXT TO
+aule.flash_attention_mla_paged_fp8mma (FP8 MFMAs on the codes as they are) on the same codes and scale, alternated.
+Before a leg is timed the two are compared as a sanity check: lse within 0.25 (the twin's q is not rounded to e4m3), out within the forward
+bound plus 2^-4 of the largest |V| (the tests hold the kernel to its bounds, against fp64 models).  Per leg: both medians and spreads, twin / FP8 products (below 1: the new kernel is
+slower) and the arithmetic over the new kernel's time.
+
 --append: aule.mla_kv_append against the torch ops it replaces -- cos[pos] / sin[pos] and rope_raw for a rotated k_pe, cat, divide /
 clamp / cast for an FP8 cache, index_copy_ -- T = 1 / 64 / 4096 / 65536 tokens, a 16-bit and an FP8 cache, with and without the
 (interleaved) rotation, bf16, block 64, random slots and positions.  The two are compared bit for bit before they are timed.  Per
@@ -153,6 +159,35 @@ def leg_fp8(Hq, B, L, n, rounds, lines):
     lines.append(line)
 
 
+def leg_fp8mma(Hq, B, L, n, rounds, lines):
+    g = torch.Generator(device="cuda").manual_seed(Hq + B + L + n)
+    dt = torch.bfloat16
+    nblk = L // BS
+    q = torch.randn(B * n, Hq, QK, device="cuda", dtype=dt, generator=g)
+    kv = torch.randn(B * nblk, BS, QK, device="cuda", dtype=dt, generator=g)
+    bt = torch.randperm(B * nblk, device="cuda", generator=g).to(torch.int32).view(B, nblk)
+    cl = torch.full((B,), L, device="cuda", dtype=torch.int32)
+    cu = torch.arange(0, B * n + 1, n, device="cuda", dtype=torch.int32)
+    codes, ks = aule.quantize_mla_cache_fp8(kv)
+    vmax = float(kv[..., :VD].float().abs().max())
+    del kv
+    calls = {"twin": lambda **kw: aule.flash_attention_mla_paged_fp8(q, codes, bt, cl, cu, max_seqlen_q=n, kv_scale=ks, **kw),
+             "mma": lambda **kw: aule.flash_attention_mla_paged_fp8mma(q, codes, bt, cl, cu, max_seqlen_q=n, kv_scale=ks, **kw)}
+    a, b_ = calls["mma"](return_lse=True), calls["twin"](return_lse=True)
+    torch.cuda.synchronize()
+    bound = 1e-3 + (2.0 ** -9 + 2.0 ** -4) * vmax + 2.0 ** -8 * b_[0].float().abs()
+    if not (bool(((a[0].float() - b_[0].float()).abs() <= bound).all()) and bool(((a[1] - b_[1]).abs() <= 0.25).all())):
+        raise SystemExit(f"heads {Hq} batch {B} context {L} tokens {n}: the FP8-product call and its twin disagree")
+    del a, b_
+    r = _alternated(calls, rounds)
+    rb, ns = plan(B, Hq, n, L)
+    flops = 2.0 * (QK + VD) * B * Hq * sum(L - n + i + 1 for i in range(n))
+    line = (f"  heads {Hq:3d} batch {B:2d} context {L:5d} tokens {n}: plan {rb} x {ns:2d} x {B:2d}   16-bit MFMAs {r['twin'][1]} us   FP8 MFMAs {r['mma'][1]} us"
+            f"   twin / FP8 products {r['twin'][0] / r['mma'][0]:5.2f}x   {flops / (r['mma'][0] * 1e-6) / 1e12:6.1f} TFLOP/s")
+    print(line, flush=True)
+    lines.append(line)
+
+
 def leg_append(T, fp8, rope, rounds, lines):
     from aule._torch import rope_raw
     g = torch.Generator(device="cuda").manual_seed(T + 2 * fp8 + rope)
@@ -213,7 +248,8 @@ def main():
                     leg_append(T, fp8, rope, rounds, lines)
                     signal.alarm(0)
         return _write(lines)
-    head = (f"# tools/bench_mla.py{' --fp8' if '--fp8' in sys.argv else ''}   (one MI355X; latent 576 / 512, block_size {BS}, bf16, shuffled block table; plan = row blocks x nsplit x batch "
+    mode = "--fp8mma" if "--fp8mma" in sys.argv else "--fp8" if "--fp8" in sys.argv else ""
+    head = (f"# tools/bench_mla.py{' ' + mode if mode else ''}   (one MI355X; latent 576 / 512, block_size {BS}, bf16, shuffled block table; plan = row blocks x nsplit x batch "
             f"workgroups; {rounds} alternated rounds of ~{WINDOW_MS} ms windows, median (min .. max) us per call, host launch cost included)")
     print(head, flush=True)
     lines = [head]
@@ -222,7 +258,7 @@ def main():
             for B in BATCH:
                 for L in CONTEXT:
                     signal.alarm(budget)
-                    (leg_fp8 if "--fp8" in sys.argv else leg)(Hq, B, L, n, rounds, lines)
+                    {"--fp8mma": leg_fp8mma, "--fp8": leg_fp8, "": leg}[mode](Hq, B, L, n, rounds, lines)
                     signal.alarm(0)
     _write(lines)
 
