@@ -275,6 +275,40 @@ def flash_attention_paged_cascade(q, k_cache, v_cache, prefix_block_table, prefi
                          max_seqlen_q=max_seqlen_q, scale=scale, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
 
 
+def flash_attention_paged_d256(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=1, scale=None,
+                               window_size=-1, k_scale=None, v_scale=None, return_lse=False):
+    """PagedAttention at head_dim 256 (Gemma-2, Gemma-3, Qwen3-Next heads): plain decode, short verify and prompt chunks of a ragged
+    batch against the paged KV cache, without gathering the pages and with every sequence's keys split over the device.  Not in the
+    reference.  The contract is stated once, at aule_paged_d256_desc in include/aule.h; in short:
+
+        q [total_tokens, heads_q, 256] fp16 / bf16: the new tokens of all sequences packed along the first axis (token stride free,
+          as in flash_attention_paged_prefill);
+        k_cache, v_cache [num_blocks, block_size, heads_kv, 256] of q's dtype, or torch.float8_e4m3fn codes -- then k_scale and
+          v_scale are both required, each a [heads_kv] fp32 tensor (or a float / 0-d tensor for all heads): key = k_scale[hk] *
+          float(code).  Any block_size the other paged entries accept;
+        block_tables [batch, max_blocks], context_lens [batch] (the keys INCLUDING the new tokens: append them first);
+        cu_seqlens_q [batch + 1] int32 and max_seqlen_q as in flash_attention_paged_prefill (max_seqlen_q sizes the grid and cuts a
+          longer sequence; None reads it from cu_seqlens_q with one device->host synchronisation); cu_seqlens_q=None is plain decode:
+          sequence b owns row b, q.shape[0] == batch.
+
+    Lengths, offsets and token counts are read and clamped on the device exactly as flash_attention_paged_prefill does; token i of
+    sequence b sits at p = L_b - n_b + i and sees key j iff j <= p and, with window_size = W > 0, p - j < W.  A row without a visible
+    key is zeros (lse -inf); rows of no sequence are never written; lengths past the table's capacity are clamped; no device->host
+    synchronisation (max_seqlen_q given), capturable into a graph.  Returns [total_tokens, heads_q, 256], or (out, lse) with
+    return_lse=True: lse [total_tokens, heads_q] fp32, the natural log of the softmax denominator.  The number of key ranges comes
+    from the shape alone and the partials are combined in a fixed order: two runs give the same bits.  Out of scope: sinks, tree
+    masks, a shared prefix (cascade), FP8 matrix products, fp32, a backward pass, head_dim between 128 and 256 (pad the cache).
+    head_dim 32 / 64 / 128 is flash_attention_paged_prefill.  Argument errors are ValueErrors raised before the device is touched;
+    CPU tensors raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_d256
+    return paged_d256(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, scale=scale,
+                      window_size=window_size, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
+
+
 def flash_attention_mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, scale=None,
                               return_lse=False):
     """Paged multi-head LATENT attention (MLA, the DeepSeek-V2 / V3 / R1 family in its absorbed decode form): decode and short
@@ -998,7 +1032,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

@@ -154,6 +154,14 @@ class PagedPrefillDesc(ctypes.Structure):
     ]
 
 
+class PagedD256Desc(ctypes.Structure):
+    """struct aule_paged_d256_desc (include/aule.h): aule_paged_prefill_desc field for field, then the optional workspace."""
+    _fields_ = list(PagedPrefillDesc._fields_) + [
+        ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 class PagedCascadeDesc(ctypes.Structure):
     """struct aule_paged_cascade_desc (include/aule.h): the paged prefill behind a prefix every sequence shares."""
     _fields_ = [(n, t) if n != "window_size" else ("max_prefix_blocks", ctypes.c_uint32) for n, t in PagedPrefillDesc._fields_] + [
@@ -597,6 +605,8 @@ SIGNATURES = [
     ("aule_attention_paged_prefill_ex", _I32, [ctypes.POINTER(PagedPrefillDesc)]),
     ("aule_attention_paged_cascade_ex", _I32, [ctypes.POINTER(PagedCascadeDesc)]),
     ("aule_attention_paged_cascade_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedCascadeDesc)]),
+    ("aule_attention_paged_d256_ex", _I32, [ctypes.POINTER(PagedD256Desc)]),
+    ("aule_attention_paged_d256_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedD256Desc)]),
     ("aule_attention_mla_paged_ex", _I32, [ctypes.POINTER(MlaPagedDesc)]),
     ("aule_attention_mla_paged_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedDesc)]),
     ("aule_attention_mla_paged_fp8_ex", _I32, [ctypes.POINTER(MlaPagedFp8Desc)]),
@@ -640,6 +650,8 @@ SIGNATURES = [
     ("aule_hip_debug_mla_plan", _I32, [ctypes.POINTER(MlaPagedDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_sparse_plan", _I32, [ctypes.POINTER(MlaSparseDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_sparse_launch_nsplit", _I32, [ctypes.POINTER(MlaSparseDesc), _I32]),
+    ("aule_hip_debug_paged_d256_plan", _I32, [ctypes.POINTER(PagedD256Desc), ctypes.POINTER(_I32), _I32]),
+    ("aule_hip_debug_paged_d256_launch_nsplit", _I32, [ctypes.POINTER(PagedD256Desc), _I32]),
     ("aule_hip_debug_mla_indexer_plan", _I32, [ctypes.POINTER(MlaIndexerLogitsDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_prefill_backward_plan", _I32, [ctypes.POINTER(MlaPrefillBwdDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_last_backward_route", _I32, []),

@@ -410,11 +410,11 @@ def _fp8_scale(s, Hkv, device, name):
     return s.to(device=device, dtype=torch.float32).contiguous()
 
 
-def _paged_cache_is_fp8(op, inputs, k_cache, v_cache, k_scale, v_scale):
+def _paged_cache_is_fp8(op, inputs, k_cache, v_cache, k_scale, v_scale, head_dims=PAGED_HEAD_DIMS):
     """The cache-kind rules the paged operations share -- caches of one dtype, torch.float8_e4m3fn the only FP8 encoding,
     fp16 / bf16 inputs (and 16-bit caches) of one dtype, scales with FP8 caches only, head_dim in PAGED_HEAD_DIMS -- as ValueErrors
     in that operation's words.  op: "decode", "query", "prefill", "cascade" (inputs: (q,)) or "append" (inputs: (key, value)).
-    Returns whether the caches are FP8."""
+    head_dims None: the caller states its own head_dim rule (paged_d256).  Returns whether the caches are FP8."""
     if op == "append":
         name, fp8_use, same, with_fp8, dims_of = ("paged KV append", "the paged KV append writes", "key, value and caches",
                                                   "fp16 / bf16 key and value", "the paged KV cache")
@@ -435,8 +435,8 @@ def _paged_cache_is_fp8(op, inputs, k_cache, v_cache, k_scale, v_scale):
     if not fp8 and (k_scale is not None or v_scale is not None):
         raise ValueError("k_scale / v_scale apply to float8_e4m3fn caches only; a 16-bit cache holds the values themselves")
     D = inputs[0].shape[-1]
-    if D not in PAGED_HEAD_DIMS:
-        raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS} for {dims_of}, got {D}")
+    if head_dims is not None and D not in head_dims:
+        raise ValueError(f"head_dim must be one of {head_dims} for {dims_of}, got {D}")
     return fp8
 
 
@@ -456,9 +456,9 @@ def _paged_shapes(q, axes, k_cache, v_cache):
     return Hkv
 
 
-def _paged_cache_kind(op, q, k_cache, v_cache, k_scale, v_scale):
+def _paged_cache_kind(op, q, k_cache, v_cache, k_scale, v_scale, head_dims=PAGED_HEAD_DIMS):
     """_paged_cache_is_fp8, then a positive block size (the decode leaves that one to the library)."""
-    fp8 = _paged_cache_is_fp8(op, (q,), k_cache, v_cache, k_scale, v_scale)
+    fp8 = _paged_cache_is_fp8(op, (q,), k_cache, v_cache, k_scale, v_scale, head_dims)
     if k_cache.shape[1] == 0:
         raise ValueError("block_size must be positive")
     return fp8
@@ -1313,6 +1313,55 @@ def paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tab
         held += [pbt, plen, _attach_workspace(d, lib.aule_attention_paged_cascade_workspace_size, q.device),
                  _attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device)]
         _capi.check(lib.aule_attention_paged_cascade_ex(ctypes.byref(d)), "aule_attention_paged_cascade_ex")
+    return result
+
+
+def paged_d256(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=1, scale=None, window_size=-1,
+               k_scale=None, v_scale=None, return_lse=False, force_nsplit=None):
+    """Paged attention at head_dim 256 (aule.flash_attention_paged_d256 documents the arguments; aule_paged_d256_desc in include/aule.h
+    is the contract); csrc/fa_fwd_paged_d256_gfx950.hip behind aule_attention_paged_d256_ex.  The steps and the shared rules are
+    paged_prefill's; this entry's own are head_dim == 256, cu_seqlens_q = None for plain decode (mla_paged's rule) and both scales
+    with an FP8 cache.  force_nsplit (tests, tools/bench_paged_d256.py): that many key ranges instead of the plan's, through
+    aule_hip_debug_paged_d256_launch_nsplit."""
+    Hkv = _paged_shapes(q, "T,Hq,D", k_cache, v_cache)
+    if q.shape[-1] != 256:
+        raise ValueError(f"flash_attention_paged_d256 is built for head_dim 256 only, got {q.shape[-1]} "
+                         f"(head_dim 32, 64 and 128: flash_attention_paged_prefill)")
+    fp8 = _paged_cache_kind("prefill", q, k_cache, v_cache, k_scale, v_scale, head_dims=None)
+    if fp8 and (k_scale is None or v_scale is None):
+        raise ValueError("flash_attention_paged_d256 needs k_scale and v_scale with a float8_e4m3fn cache, the scales the cache was written with")
+    B = _paged_tables(block_tables, context_lens, None if cu_seqlens_q is not None else q.shape[0])
+    if cu_seqlens_q is not None:
+        _ragged_offsets(B, cu_seqlens_q, max_seqlen_q)
+    else:
+        _single_token_offsets(max_seqlen_q)
+    _scale_shapes(fp8, Hkv, k_scale, v_scale)
+    q, q_stride = _packed_tokens(q)
+    _needs_device("head_dim 256 attention", q)
+    lib = _capi.get_lib()
+    k_cache, v_cache = k_cache.contiguous(), v_cache.contiguous()
+    _same_device("paged head_dim 256 attention", q, k_cache, v_cache)
+    held = _int32_on(q.device, block_tables, context_lens) + ([] if cu_seqlens_q is None else _int32_on(q.device, cu_seqlens_q))
+    bt, cl, cu = held[0], held[1], held[2] if cu_seqlens_q is not None else None
+    T, Hq, D = q.shape
+    if cu is None:
+        max_seqlen_q = 1
+    elif max_seqlen_q is None:
+        max_seqlen_q = _longest_sequence(cu, B)
+    out, lse, result = _ragged_result(q, D, return_lse)
+    if T * B * Hq == 0:
+        return result
+    d = _paged_problem(_capi.PagedD256Desc(), q, k_cache, v_cache, out, bt, cl, scale, fp8)
+    d.total_tokens, d.max_seqlen_q, d.q_token_stride = T, min(max_seqlen_q, T), q_stride
+    d.window_size = _window_arg(window_size)
+    d.lse = lse.data_ptr() if lse is not None else None
+    d.cu_seqlens_q = cu.data_ptr() if cu is not None else None
+    held += [k_cache, v_cache, _attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device)]   # held until the launch is queued
+    if force_nsplit is None:
+        held.append(_attach_workspace(d, lib.aule_attention_paged_d256_workspace_size, q.device))
+        _capi.check(lib.aule_attention_paged_d256_ex(ctypes.byref(d)), "aule_attention_paged_d256_ex")
+    else:   # (no workspace of the caller's: the library allocates on the stream for this nsplit)
+        _capi.check(lib.aule_hip_debug_paged_d256_launch_nsplit(ctypes.byref(d), int(force_nsplit)), "aule_hip_debug_paged_d256_launch_nsplit")
     return result
 
 

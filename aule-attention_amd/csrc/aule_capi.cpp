@@ -27,6 +27,7 @@
 
 #include "fa_bwd_plan.h"
 #include "fa_kernels.h"
+#include "fa_paged_d256.h"
 #include "fa_switches.h"
 
 // abi2: optional workspace / workspace_bytes appended to the forward and paged descriptors (96 -> 112, 104 -> 120)
@@ -59,6 +60,16 @@ static_assert(sizeof(aule_paged_prefill_desc) == 152 && offsetof(aule_paged_pref
                   offsetof(aule_paged_prefill_desc, out) == 120 && offsetof(aule_paged_prefill_desc, lse) == 128 &&
                   offsetof(aule_paged_prefill_desc, k_scale) == 136 && offsetof(aule_paged_prefill_desc, v_scale) == 144,
               "aule_paged_prefill_desc layout is part of the ABI");
+#define AULE_D256_SAME(field) (offsetof(aule_paged_d256_desc, field) == offsetof(aule_paged_prefill_desc, field))
+static_assert(sizeof(aule_paged_d256_desc) == 168 && offsetof(aule_paged_d256_desc, workspace) == 152 && offsetof(aule_paged_d256_desc, workspace_bytes) == 160 &&
+                  offsetof(aule_paged_d256_desc, workspace) == sizeof(aule_paged_prefill_desc) && AULE_D256_SAME(struct_size) && AULE_D256_SAME(dtype) &&
+                  AULE_D256_SAME(cache_dtype) && AULE_D256_SAME(batch) && AULE_D256_SAME(heads_q) && AULE_D256_SAME(heads_kv) && AULE_D256_SAME(head_dim) &&
+                  AULE_D256_SAME(block_size) && AULE_D256_SAME(max_blocks) && AULE_D256_SAME(total_tokens) && AULE_D256_SAME(max_seqlen_q) &&
+                  AULE_D256_SAME(scale) && AULE_D256_SAME(window_size) && AULE_D256_SAME(device) && AULE_D256_SAME(q_token_stride) && AULE_D256_SAME(stream) &&
+                  AULE_D256_SAME(q) && AULE_D256_SAME(k_cache) && AULE_D256_SAME(v_cache) && AULE_D256_SAME(block_tables) && AULE_D256_SAME(context_lens) &&
+                  AULE_D256_SAME(cu_seqlens_q) && AULE_D256_SAME(out) && AULE_D256_SAME(lse) && AULE_D256_SAME(k_scale) && AULE_D256_SAME(v_scale),
+              "aule_paged_d256_desc is aule_paged_prefill_desc field for field, then workspace and workspace_bytes");
+#undef AULE_D256_SAME
 static_assert(sizeof(aule_paged_cascade_desc) == 184 && offsetof(aule_paged_cascade_desc, cache_dtype) == 8 &&
                   offsetof(aule_paged_cascade_desc, batch) == 12 && offsetof(aule_paged_cascade_desc, block_size) == 28 &&
                   offsetof(aule_paged_cascade_desc, max_blocks) == 32 && offsetof(aule_paged_cascade_desc, total_tokens) == 36 &&
@@ -1573,10 +1584,11 @@ extern "C++" {
 template <class Desc>
 static int max_sq_or_one(const Desc* d) { return d->cu_seqlens_q == nullptr ? 1 : aule_hip::seqlen_cut(d->max_seqlen_q, d->total_tokens); }
 
-// (the tail of both MLA launch entries: the device, the workspace of a split plan -- the caller's buffer when it is large enough, else a
-// stream-ordered allocation -- and the launch; `launch(ws, stream)`: the kind's launcher with its arguments and `plan`)
-template <class Desc, class Launch>
-static int32_t mla_launch_tail(const Desc* d, const aule_hip::MlaPlan& plan, const char* what, Launch&& launch) {
+// (the tail of both MLA launch entries and of the head_dim 256 paged entry: the device, the workspace of a split plan -- the caller's
+// buffer when it is large enough, else a stream-ordered allocation -- and the launch; `launch(ws, stream)`: the kind's launcher with its
+// arguments and `plan` (MlaPlan or PagedD256Plan: nsplit and ws_bytes))
+template <class Desc, class Plan, class Launch>
+static int32_t mla_launch_tail(const Desc* d, const Plan& plan, const char* what, Launch&& launch) {
     DeviceGuard g(d->device);
     int rc = ensure_configured();
     if (rc) return rc;
@@ -1775,6 +1787,78 @@ static int32_t mla_sparse_launch(const aule_mla_sparse_desc* d, int force_nsplit
 int32_t aule_attention_mla_sparse_ex(const aule_mla_sparse_desc* d) {
     RoctxRange range("aule.mla_sparse");
     return mla_sparse_launch(d, 0);
+}
+
+// The paged attention at head_dim 256: aule_paged_prefill_desc's fields and shared rules, a head_dim and an offsets rule of its own (a
+// null cu_seqlens_q is plain decode, as for the MLA) and a workspace.  One checker for all its readers; `launch`: the pointer and
+// workspace rules of a call that has something to do as well (the size query and the plan hook read no pointer but cu_seqlens_q's
+// being null).  Host logic only, asked before the device is needed.
+static void fill_paged_d256_args(const aule_paged_d256_desc* d, aule_hip::PagedD256Args& a) {
+    a.q = d->q; a.k_cache = d->k_cache; a.v_cache = d->v_cache; a.out = d->out; a.lse = d->lse;
+    a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
+    a.T = (int)d->total_tokens; a.B = (int)d->batch; a.Hq = (int)d->heads_q; a.Hkv = (int)d->heads_kv;
+    a.max_seqlen_q = max_sq_or_one(d);
+    a.q_token_stride = d->q_token_stride;
+    a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
+    a.scale = resolve_scale(d->scale, 256);
+    a.window = d->window_size;
+    a.dtype = d->dtype;
+    a.device = d->device;
+    if (d->cache_dtype == AULE_KV_CACHE_FP8_E4M3) {
+        a.cache_kind = aule_hip::kCacheFp8E4M3;
+        a.k_scale = d->k_scale; a.v_scale = d->v_scale;
+    }
+}
+
+// (force_nsplit > 0: the debug launch alone, aule_hip_debug_paged_d256_launch_nsplit; `plan`: the launch's, where there is one)
+static const char* paged_d256_desc_error(const aule_paged_d256_desc* d, bool launch, Reason& why, aule_hip::PagedD256Plan& plan, int force_nsplit = 0) {
+    plan = aule_hip::PagedD256Plan();
+    if (d == nullptr || d->struct_size != sizeof(aule_paged_d256_desc)) return kBadDescriptor;
+    if (const char* e = paged_dtype_error(d)) return e;
+    if (d->head_dim != 256)
+        return reasonf(why, "head_dim %u unsupported by the head_dim 256 entry (256 only; 32, 64 and 128: aule_attention_paged_prefill_ex)", d->head_dim);
+    if (const char* e = head_ratio_error(d->heads_q, d->heads_kv, why)) return e;
+    if (const char* e = paged_blocks_error(d)) return e;
+    if (const char* e = ragged_query_error(d, why)) return e;
+    if (ragged_nothing_to_do(d)) return nullptr;
+    if (d->cu_seqlens_q == nullptr && d->total_tokens < d->batch) return "cu_seqlens_q is null (plain decode: sequence b owns row b) and total_tokens < batch";
+    aule_hip::PagedD256Args a;
+    fill_paged_d256_args(d, a);
+    plan = aule_hip::paged_d256_plan(a, force_nsplit);
+    if (plan.grid <= 0 || plan.grid > 0x7fffffffll || (long long)plan.row_blocks * d->heads_kv * d->batch * (aule_hip::kPagedD256Rows / 4) > 0x7fffffffll)
+        return reasonf(why, "the grid (row blocks %d * nsplit %d * heads_kv * batch, or row blocks * 16 * heads_kv * batch for the combine) exceeds 2^31 - 1 workgroups",
+                       plan.row_blocks, plan.nsplit);
+    if (!launch) return nullptr;
+    if (const char* e = paged_pointer_error(d, true, d->cache_dtype == AULE_KV_CACHE_FP8_E4M3, d->k_scale, d->v_scale)) return e;
+    if (const char* e = paged_alignment_error(d)) return e;
+    if (d->workspace != nullptr) {
+        if (d->workspace_bytes < plan.ws_bytes)
+            return reasonf(why, "workspace_bytes (%llu) is smaller than the plan's %llu", (unsigned long long)d->workspace_bytes, (unsigned long long)plan.ws_bytes);
+        if (misaligned(d->workspace)) return "workspace must be 16-byte aligned";
+    }
+    return nullptr;
+}
+
+// (the launch entry, and with force_nsplit > 0 the debug launch)
+static const char kPagedD256[] = "Paged head_dim 256 attention";
+static int32_t paged_d256_launch(const aule_paged_d256_desc* d, int force_nsplit) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    aule_hip::PagedD256Plan plan;
+    if (const char* why = paged_d256_desc_error(d, true, text, plan, force_nsplit)) {
+        set_error("%s failed: %s", kPagedD256, why);
+        return -3;
+    }
+    if (ragged_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::PagedD256Args a;
+    fill_paged_d256_args(d, a);
+    return mla_launch_tail(d, plan, kPagedD256, [&](void* ws, hipStream_t stream) { return aule_hip::launch_paged_d256(a, plan, ws, stream); });
+}
+
+int32_t aule_attention_paged_d256_ex(const aule_paged_d256_desc* d) {
+    RoctxRange range("aule.paged_d256");
+    return paged_d256_launch(d, 0);
 }
 
 // The MLA indexer: index logits and top-k key lists, one checker per kind; `launch`: the pointer rules of a call that has something to
@@ -2692,6 +2776,12 @@ uint64_t aule_attention_mla_paged_tree_workspace_size(const aule_mla_paged_tree_
     return mla_paged_plan(mla_tree_prefix(d), kMlaTree, plan) ? plan.ws_bytes : 0;
 }
 
+uint64_t aule_attention_paged_d256_workspace_size(const aule_paged_d256_desc* d) {
+    Reason text;
+    aule_hip::PagedD256Plan plan;
+    return paged_d256_desc_error(d, false, text, plan) ? 0 : plan.ws_bytes;   // (nothing to do: the empty plan)
+}
+
 uint64_t aule_attention_mla_sparse_workspace_size(const aule_mla_sparse_desc* d) {
     Reason text;
     if (mla_sparse_desc_error(d, false, text)) return 0;
@@ -2800,6 +2890,28 @@ int32_t aule_hip_debug_mla_sparse_launch_nsplit(const aule_mla_sparse_desc* d, i
         return -3;
     }
     return mla_sparse_launch(d, nsplit);
+}
+
+/* Debug hook: the launch plan of aule_attention_paged_d256_ex(d) as integers (include/aule.h lists them): the plan the launch and the
+ * workspace query read.  Pure host logic like the forward hook. */
+int32_t aule_hip_debug_paged_d256_plan(const aule_paged_d256_desc* d, int32_t* out, int32_t cap) {
+    Reason text;
+    aule_hip::PagedD256Plan plan;
+    if (paged_d256_desc_error(d, false, text, plan)) return -3;
+    if (plan.grid <= 0) return 0;
+    const std::initializer_list<int32_t> ints = {plan.row_blocks, plan.rows_per_block, plan.nsplit, (int32_t)plan.grid};
+    return dump_plan(ints, &plan.ws_bytes, out, cap);
+}
+
+/* Debug hook (not part of the drop-in ABI): aule_attention_paged_d256_ex(d) with `nsplit` key ranges (cut to at most 64) instead of the
+ * plan's -- what the tests force a split count with and tools/bench_paged_d256.py measures the plan's rule with.  Every rule of the
+ * entry holds; a caller workspace is sized for THIS nsplit.  nsplit < 1: -3. */
+int32_t aule_hip_debug_paged_d256_launch_nsplit(const aule_paged_d256_desc* d, int32_t nsplit) {
+    if (nsplit < 1) {
+        set_error("%s failed: nsplit (%d) must be at least 1", kPagedD256, nsplit);
+        return -3;
+    }
+    return paged_d256_launch(d, nsplit);
 }
 
 /* Debug hook: the launch plan of aule_mla_indexer_logits_ex(d) as integers (include/aule.h lists them): the plan the launch reads.

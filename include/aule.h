@@ -396,6 +396,67 @@ int32_t aule_attention_paged_cascade_ex(const aule_paged_cascade_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
 uint64_t aule_attention_paged_cascade_workspace_size(const aule_paged_cascade_desc* desc);
 
+/* Paged attention at head_dim 256 (additive): decode, short verify and prompt chunks of ragged sequences against the paged KV cache  */
+/* for the models with 256-wide heads (Gemma-2, Gemma-3, Qwen3-Next), with the keys of every sequence split over the device.  The     */
+/* descriptor is aule_paged_prefill_desc field for field -- the same offsets, the same two cache kinds, the same clamps (L_b, s_b,    */
+/* e_b, n_b, all made on the device), the same position and window rule (token i of sequence b is row s_b + i, sits at                */
+/* p = L_b - n_b + i, sees key j iff j <= p and, with window_size = W > 0, p - j < W), the same rows that are written (a token with   */
+/* p < 0 or without a visible key: zeros and lse = -inf; rows of no sequence: NEVER written) and the same table guarantee (an entry   */
+/* at logical block >= ceil(L_b / block_size) is never dereferenced, a key row at or beyond L_b never read) -- followed by an         */
+/* optional workspace, with these differences:                                                                                        */
+/*   * head_dim must be 256 (32, 64 and 128 are aule_attention_paged_prefill_ex's); nothing is padded: a cache of a width between     */
+/*     128 and 256 is the caller's to pad;                                                                                            */
+/*   * cu_seqlens_q = NULL means plain decode, as in aule_mla_paged_desc: sequence b owns row b, n_b = 1, max_seqlen_q is read as 1   */
+/*     (it must still be >= 1) and total_tokens >= batch is required.                                                                 */
+/* Launches: the packed rows of a (sequence, KV head) -- token-major, row r = token r / g, head hk * g + r % g, g = heads_q /         */
+/* heads_kv -- are cut into blocks of 64 and the keys a block sees into nsplit ranges; nsplit is fixed on the host from the shape     */
+/* alone -- row blocks * heads_kv * batch * nsplit covers the device's compute units, at most 64 and at most one split per 128 keys   */
+/* of what a block can see (the table's capacity, or window_size + the block's tokens) -- and each workgroup derives its              */
+/* own range on the device: split k owns tiles [tb + k * ceil((te - tb) / nsplit), ...) of the tiles [tb, te) that hold the block's   */
+/* visible keys, from L_b, the block's positions and the window.  nsplit = 1: one launch.  nsplit > 1: fp32 partials of 256 + 2       */
+/* floats per (split, token, head) in the workspace and a combine kernel that adds them in split order (no atomics: two runs are      */
+/* bit-identical).  Workspace bytes = round16(nsplit * total_tokens * heads_q * 258 * 4), 0 for nsplit = 1:                           */
+/* aule_attention_paged_d256_workspace_size() gives the number; a call without a workspace allocates on the stream; a workspace that  */
+/* is given must be large enough and 16-byte aligned (-3 otherwise).  No host synchronisation, and no allocation when a workspace is  */
+/* passed: captures into a hipGraph, and a replay sees the CURRENT cu_seqlens_q, context_lens, block_tables and scales.               */
+/* Not built: sinks, tree masks, a shared prefix (cascade), FP8 matrix products, fp32, a backward, head_dim between 128 and 256.      */
+/* The descriptor is checked before the device is needed: -3 for a refused descriptor and 0 for one with nothing to do                */
+/* (total_tokens = 0, batch = 0 or heads_q = 0) are answered without aule_init().                                                     */
+typedef struct aule_paged_d256_desc {
+    uint32_t struct_size;      /* = sizeof(aule_paged_d256_desc) = 168 */
+    int32_t dtype;             /* offset 4; type of q / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    int32_t cache_dtype;       /* offset 8; AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3 */
+    uint32_t batch;            /* offset 12; sequences */
+    uint32_t heads_q;          /* offset 16 */
+    uint32_t heads_kv;         /* offset 20 */
+    uint32_t head_dim;         /* offset 24; 256 */
+    uint32_t block_size;       /* offset 28; any value > 0 */
+    uint32_t max_blocks;       /* offset 32; columns of block_tables */
+    uint32_t total_tokens;     /* offset 36; rows of q / out; 0: returns 0 without a launch */
+    uint32_t max_seqlen_q;     /* offset 40; >= 1: sizes the grid, and caps every n_b */
+    float scale;               /* offset 44; 0 -> 1/sqrt(256) */
+    int32_t window_size;       /* offset 48; > 0: the token at position p sees only the keys j with p - j < window_size */
+    int32_t device;            /* offset 52; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 56; elements, >= heads_q * 256, a multiple of 8 */
+    void* stream;              /* offset 64; hipStream_t */
+    const void* q;             /* offset 72; [total_tokens, heads_q, 256], 16-bit */
+    const void* k_cache;       /* offset 80; [num_blocks, block_size, heads_kv, 256]: 16-bit of q's dtype, or e4m3fn bytes */
+    const void* v_cache;       /* offset 88; same layout */
+    const int32_t* block_tables;   /* offset 96; [batch, max_blocks] */
+    const int32_t* context_lens;   /* offset 104; [batch]: keys per sequence, the new ones included */
+    const int32_t* cu_seqlens_q;   /* offset 112; [batch + 1], device; NULL: plain decode */
+    void* out;                 /* offset 120; [total_tokens, heads_q, 256], 16-bit, contiguous */
+    float* lse;                /* offset 128; optional (NULL to skip): [total_tokens, heads_q] fp32 */
+    const float* k_scale;      /* offset 136; [heads_kv] fp32, device (AULE_KV_CACHE_FP8_E4M3), else NULL */
+    const float* v_scale;      /* offset 144 */
+    void* workspace;           /* offset 152; optional, size from aule_attention_paged_d256_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 160 */
+} aule_paged_d256_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_paged_d256_ex(const aule_paged_d256_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
+uint64_t aule_attention_paged_d256_workspace_size(const aule_paged_d256_desc* desc);
+
 /* Paged MLA (additive): multi-head LATENT attention in its absorbed form (DeepSeek-V2 / V3 / R1) -- decode and short verify over a */
 /* latent KV cache.  Dimensions: qk_dim = 576 (512 compressed dimensions, then 64 rotary ones) and v_dim = 512 are the only pair     */
 /* accepted (anything else: -3); dtype fp16 or bf16.                                                                                  */
@@ -1403,6 +1464,18 @@ int32_t aule_hip_debug_mla_sparse_plan(const aule_mla_sparse_desc* desc, int32_t
 /* bench that measures the plan's "one split per two tiles" cap (tools/bench_mla_sparse.py); results equal the entry's within the   */
 /* forward bounds, bit for bit only at the plan's own nsplit.                                                                       */
 int32_t aule_hip_debug_mla_sparse_launch_nsplit(const aule_mla_sparse_desc* desc, int32_t nsplit);
+/* Debug: the launch plan of aule_attention_paged_d256_ex(desc) as integers -- out = {row blocks, rows per block (64), nsplit,      */
+/* workgroups (row blocks * nsplit * heads_kv * batch), workspace bytes low 32 bits, high 32 bits}.  Returns the ints written       */
+/* (negative: the capacity needed), 0 for a descriptor with nothing to do; -3 bad.  Host logic only, no aule_init(), no pointer of  */
+/* the descriptor is read but cu_seqlens_q's being NULL or not (the pointer and workspace rules of the launch are not applied);     */
+/* without a device it plans for 256 compute units.                                                                                 */
+int32_t aule_hip_debug_paged_d256_plan(const aule_paged_d256_desc* desc, int32_t* out, int32_t cap);
+/* Debug: aule_attention_paged_d256_ex(desc) with `nsplit` key ranges instead of the plan's, cut to at most 64; nsplit < 1: -3.     */
+/* More ranges than a block has tiles are allowed (the surplus is empty).  Every other rule and return value of the entry; a caller */
+/* workspace is sized for this nsplit (round16(nsplit * total_tokens * heads_q * 258 * 4)).  For the tests and the bench that       */
+/* measures the plan's rule (tools/bench_paged_d256.py); results equal the entry's within the forward bounds, bit for bit only at   */
+/* the plan's own nsplit.                                                                                                           */
+int32_t aule_hip_debug_paged_d256_launch_nsplit(const aule_paged_d256_desc* desc, int32_t nsplit);
 /* Debug: the launch plan of aule_mla_indexer_logits_ex(desc) as integers -- out = {tokens per group (4), token groups              */
 /* (ceil(max_seqlen_q / 4); plain decode: 1), keys per chunk (a multiple of 128), key chunks, workgroups (batch * token groups *    */
 /* key chunks)}.  Chunk c owns columns [c * keys per chunk, ...) cut at W, so every (token group, column) has one owner.  Returns   */
