@@ -603,6 +603,33 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
                 scale=scale, window_size=window_size, return_lse=return_lse)
 
 
+def flash_attention_varlen_d256(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
+                                window_size=-1, return_lse=False):
+    """flash_attention_varlen for heads that are 256 wide (Gemma-2, Gemma-3, Qwen3-Next), forward and backward (autograd-aware):
+    SFT with sequence packing, encoder batches without padding and prefill without a paged cache at head_dim 256, which
+    flash_attention_varlen refuses.  Not in the reference.
+
+        q [total_q, heads_q, 256], k, v [total_k, heads_kv, 256] fp16 / bf16 ROCm tensors, heads_q % heads_kv == 0 (any group
+          size).  head_dim must be exactly 256: any other value is a ValueError that points to flash_attention_varlen, and
+          nothing is padded.
+        cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, scale, window_size, return_lse: flash_attention_varlen's,
+          rule for rule -- token strides that read the slices of a fused [T, heads_q + 2 heads_kv, 256] projection in place,
+          int32 offsets read and clamped on the device, the max_seqlen_* cuts, the three causal modes (L < n allowed under
+          "bottom-right"), any window_size, no synchronisation and capturable when both maxima are given.
+
+    A token that sees no key gives a row of zeros (lse -inf, zero gradient).  Rows that belong to no sequence are never written:
+    out (and lse) come from torch.empty; the gradients are zero there.  The kernels use no atomics: two runs give the same bits.
+    Returns [total_q, heads_q, 256], or (out, lse) with return_lse=True.  Not built: sinks, fp32, FP8 inputs.  All argument
+    errors are ValueErrors raised before the device is touched; CPU tensors that pass them raise AuleError."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import flash_attention_varlen_d256 as impl
+    return impl(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k, causal=causal,
+                scale=scale, window_size=window_size, return_lse=return_lse)
+
+
 def flash_attention_varlen_sinks(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True,
                                  scale=None, window_size=-1, return_lse=False):
     """flash_attention_varlen for models with learned ATTENTION SINKS (gpt-oss and its derivatives): every query head carries one logit
@@ -1032,7 +1059,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_d256", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

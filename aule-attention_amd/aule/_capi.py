@@ -623,6 +623,9 @@ SIGNATURES = [
     ("aule_attention_varlen_forward_ex", _I32, [ctypes.POINTER(VarlenDesc)]),
     ("aule_attention_varlen_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),
     ("aule_attention_varlen_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenBwdDesc)]),
+    ("aule_attention_varlen_d256_forward_ex", _I32, [ctypes.POINTER(VarlenDesc)]),
+    ("aule_attention_varlen_d256_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),
+    ("aule_attention_varlen_d256_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenBwdDesc)]),
     ("aule_attention_varlen_sink_forward_ex", _I32, [ctypes.POINTER(VarlenSinkDesc)]),
     ("aule_attention_varlen_sink_backward_ex", _I32, [ctypes.POINTER(VarlenSinkBwdDesc)]),
     ("aule_attention_varlen_sink_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenSinkBwdDesc)]),

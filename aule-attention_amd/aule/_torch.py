@@ -704,8 +704,9 @@ def _varlen_max(name, m):
         raise ValueError(f"{name} must be a positive int or None, got {m!r}")
 
 
-def _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k):
-    """Every rule of the arguments that needs no device.  Returns the batch."""
+def _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, head_dims=VARLEN_HEAD_DIMS):
+    """Every rule of the arguments that needs no device (head_dims: the widths the entry is built for, the last the largest).  Returns
+    the batch."""
     if not (torch.is_tensor(q) and torch.is_tensor(k) and torch.is_tensor(v)) or q.dim() != 3 or k.dim() != 3 or v.shape != k.shape:
         raise ValueError("expected q [total_q, heads_q, head_dim] and k, v [total_k, heads_kv, head_dim] of one shape")
     (Hq, D), (Hkv, Dk) = q.shape[1:], k.shape[1:]
@@ -717,8 +718,8 @@ def _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_
         raise ValueError(f"variable-length attention is not built for {q.dtype}: fp16 and bf16 only")
     if k.dtype != q.dtype or v.dtype != q.dtype:
         raise ValueError(f"q, k and v must share one dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
-    if D == 0 or D > VARLEN_HEAD_DIMS[-1]:
-        raise ValueError(f"variable-length attention is not built for head_dim {D}: 1 to {VARLEN_HEAD_DIMS[-1]}")
+    if D == 0 or D > head_dims[-1]:
+        raise ValueError(f"variable-length attention is not built for head_dim {D}: 1 to {head_dims[-1]}")
     return _varlen_offsets(cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
 
 
@@ -778,10 +779,19 @@ def _varlen_problem(d, q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q, max_seqlen
     return d
 
 
-def varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1, want_lse=True, sinks=None):
+# the entries of the two varlen Functions: forward, and (size query, launch) of the backward
+VARLEN_FWD = "aule_attention_varlen_forward_ex"
+VARLEN_BWD = ("aule_attention_varlen_backward_workspace_size", "aule_attention_varlen_backward_ex")
+VARLEN_D256_FWD = "aule_attention_varlen_d256_forward_ex"
+VARLEN_D256_BWD = ("aule_attention_varlen_d256_backward_workspace_size", "aule_attention_varlen_d256_backward_ex")
+
+
+def varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1, want_lse=True, sinks=None,
+                   launch=VARLEN_FWD):
     """q [Tq,Hq,D], k / v [Tk,Hkv,D] device tensors (heads contiguous, D in VARLEN_HEAD_DIMS), cu_q / cu_k int32 [B + 1] on the same
     device, causal an AULE_CAUSAL_* code.  Returns (out, lse or None), both from torch.empty.  Asynchronous, no synchronisation.
-    sinks: [Hq] fp32 contiguous sink logits on the same device (aule_attention_varlen_sink_forward_ex), or None."""
+    sinks: [Hq] fp32 contiguous sink logits on the same device (aule_attention_varlen_sink_forward_ex), or None.
+    launch: the entry (aule_attention_varlen_d256_forward_ex takes the same descriptor at D = 256)."""
     lib = _capi.get_lib()
     _same_device("variable-length attention", q, k, v, cu_q, cu_k)
     (q, sq), (k, sk), (v, sv) = _varlen_rows("q", q), _varlen_rows("k", k), _varlen_rows("v", v)
@@ -793,17 +803,18 @@ def varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scal
                         max_seqlen_k, causal, scale, window)
     d.out = out.data_ptr()
     d.lse = lse.data_ptr() if lse is not None else None
-    launch = "aule_attention_varlen_forward_ex"
     if sinks is not None:
         launch, d.sinks = "aule_attention_varlen_sink_forward_ex", sinks.data_ptr()
     _capi.check(getattr(lib, launch)(ctypes.byref(d)), launch)
     return out, lse
 
 
-def varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1, sinks=None):
+def varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1, sinks=None,
+                   entries=VARLEN_BWD):
     """The gradients of varlen_fwd_raw: dq [Tq,Hq,D], dk, dv [Tk,Hkv,D], contiguous and ZERO in the rows no sequence owns (the
     library never writes those; they are allocated zero-filled here).  out, dout, lse contiguous.  Asynchronous, no synchronisation.
-    sinks (the forward's): returns (dq, dk, dv, dsinks [Hq] fp32) through aule_attention_varlen_sink_backward_ex."""
+    sinks (the forward's): returns (dq, dk, dv, dsinks [Hq] fp32) through aule_attention_varlen_sink_backward_ex.
+    entries: (size query, launch) -- VARLEN_D256_BWD takes the same descriptor at D = 256."""
     lib = _capi.get_lib()
     _same_device("variable-length attention backward", q, k, v, out, dout, lse, cu_q, cu_k)
     (q, sq), (k, sk), (v, sv) = _varlen_rows("q", q), _varlen_rows("k", k), _varlen_rows("v", v)
@@ -818,7 +829,7 @@ def varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen
                         max_seqlen_k, causal, scale, window)
     d.out, d.lse, d.dout = out.data_ptr(), lse.data_ptr(), dout.data_ptr()
     d.dq, d.dk, d.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
-    size_query, launch = "aule_attention_varlen_backward_workspace_size", "aule_attention_varlen_backward_ex"
+    size_query, launch = entries
     if sinks is not None:
         size_query, launch = "aule_attention_varlen_sink_backward_workspace_size", "aule_attention_varlen_sink_backward_ex"
         d.sinks, d.dsinks = sinks.data_ptr(), dsinks.data_ptr()
@@ -828,22 +839,60 @@ def varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen
     return grads
 
 
+def _varlen_func_forward(ctx, fwd, bwd, q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window):
+    """forward of both varlen Functions: `fwd` the forward entry, `bwd` the (size query, launch) pair their backward goes through"""
+    out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window, launch=fwd)
+    ctx.save_for_backward(q, k, v, out, lse, cu_q, cu_k)
+    ctx.problem = (max_seqlen_q, max_seqlen_k, causal, scale, window, bwd)
+    ctx.mark_non_differentiable(lse)
+    return out, lse
+
+
 class FlashAttentionVarlenHipFunc(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window):
-        out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window)
-        ctx.save_for_backward(q, k, v, out, lse, cu_q, cu_k)
-        ctx.problem = (max_seqlen_q, max_seqlen_k, causal, scale, window)
-        ctx.mark_non_differentiable(lse)
-        return out, lse
+    def forward(ctx, *args):
+        return _varlen_func_forward(ctx, VARLEN_FWD, VARLEN_BWD, *args)
 
     @staticmethod
     def backward(ctx, dout, _dlse):
         q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors
-        max_seqlen_q, max_seqlen_k, causal, scale, window = ctx.problem
+        max_seqlen_q, max_seqlen_k, causal, scale, window, entries = ctx.problem
         dout = dout.contiguous().to(q.dtype)
-        dq, dk, dv = varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window)
+        dq, dk, dv = varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window, entries=entries)
         return dq, dk, dv, None, None, None, None, None, None, None
+
+
+class FlashAttentionVarlenD256HipFunc(FlashAttentionVarlenHipFunc):
+    """FlashAttentionVarlenHipFunc through the head_dim 256 entries."""
+    @staticmethod
+    def forward(ctx, *args):
+        return _varlen_func_forward(ctx, VARLEN_D256_FWD, VARLEN_D256_BWD, *args)
+
+
+def flash_attention_varlen_d256(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
+                                window_size=-1, return_lse=False):
+    """Variable-length attention at head_dim 256, autograd-aware (aule.flash_attention_varlen_d256 documents the arguments)."""
+    if torch.is_tensor(q) and q.dim() == 3 and q.shape[2] != 256:
+        raise ValueError(f"flash_attention_varlen_d256 takes head_dim 256 alone, got {q.shape[2]}: flash_attention_varlen serves head dims up to "
+                         f"{VARLEN_HEAD_DIMS[-1]}")
+    _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, head_dims=(256,))
+    code = causal_code(causal)
+    if scale is None:
+        scale = 1.0 / math.sqrt(256)
+    for name, x in (("q", q), ("k", k), ("v", v)):
+        _varlen_rows(name, x)
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): variable-length attention needs ROCm device tensors; there is no CPU fallback")
+    _same_device("variable-length attention", q, k, v)
+    cu_q, cu_k = _int32_on(q.device, cu_seqlens_q, cu_seqlens_k)
+    max_seqlen_q, max_seqlen_k = _varlen_maxima(cu_q, cu_k, max_seqlen_q, max_seqlen_k)
+    window = _window_arg(window_size)
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        out, lse = FlashAttentionVarlenD256HipFunc.apply(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window)
+    else:
+        out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window, want_lse=return_lse,
+                                  launch=VARLEN_D256_FWD)
+    return (out, lse) if return_lse else out
 
 
 class FlashAttentionVarlenSinksHipFunc(torch.autograd.Function):

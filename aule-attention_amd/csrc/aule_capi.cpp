@@ -2004,11 +2004,16 @@ static const char* varlen_stride_error(const char* name, int64_t stride, uint64_
     return nullptr;
 }
 
-// the problem statement (`size`: the kind's own sizeof)
-static const char* varlen_problem_error(const aule_varlen_desc* d, size_t size, Reason& why) {
+// the problem statement (`size`: the kind's own sizeof; `d256`: the head_dim 256 entries, which take that width alone)
+static const char* varlen_problem_error(const aule_varlen_desc* d, size_t size, Reason& why, bool d256 = false) {
     if (d == nullptr || d->struct_size != size) return kBadDescriptor;
     if (!is_16_bit(d->dtype)) return "dtype must be fp16 or bf16 (fp32 is not built for variable-length batches)";
-    if (const char* e = paged_heads_error(d, why)) return e;
+    if (d256) {
+        if (d->head_dim != 256) return reasonf(why, "head_dim %u unsupported (256 alone; 32, 64 and 128 are aule_attention_varlen_forward_ex / _backward_ex)", d->head_dim);
+        if (const char* e = head_ratio_error(d->heads_q, d->heads_kv, why)) return e;
+    } else if (const char* e = paged_heads_error(d, why)) {
+        return e;
+    }
     if (d->causal < 0 || d->causal > AULE_CAUSAL_BOTTOM_RIGHT) return reasonf(why, "unknown causal mode %d (0 none, 1 top-left, 2 bottom-right)", d->causal);
     if (d->max_seqlen_q == 0) return "max_seqlen_q must be at least 1";
     if (d->max_seqlen_k == 0) return "max_seqlen_k must be at least 1";
@@ -2033,8 +2038,8 @@ static const char* varlen_input_error(const aule_varlen_desc* d) {
 }
 
 // (`size`: the kind's own sizeof -- the sink kinds are read through their twins' types)
-static const char* varlen_desc_error(const aule_varlen_desc* d, Reason& why, size_t size = sizeof(aule_varlen_desc)) {
-    if (const char* e = varlen_problem_error(d, size, why)) return e;
+static const char* varlen_desc_error(const aule_varlen_desc* d, Reason& why, size_t size = sizeof(aule_varlen_desc), bool d256 = false) {
+    if (const char* e = varlen_problem_error(d, size, why, d256)) return e;
     if (varlen_fwd_nothing_to_do(d)) return nullptr;
     if (const char* e = varlen_input_error(d)) return e;
     if (!d->out) return "null tensor pointer";
@@ -2045,9 +2050,10 @@ static const char* varlen_desc_error(const aule_varlen_desc* d, Reason& why, siz
 static uint64_t varlen_bwd_workspace(const aule_varlen_desc* d) { return aule_hip::varlen_bwd_workspace_bytes(d->total_q, (int)d->heads_q); }
 
 // (`more`: the bytes the kind's workspace holds beyond delta)
-static const char* varlen_bwd_desc_error(const aule_varlen_bwd_desc* d, bool launch, Reason& why, size_t size = sizeof(aule_varlen_bwd_desc), uint64_t more = 0) {
+static const char* varlen_bwd_desc_error(const aule_varlen_bwd_desc* d, bool launch, Reason& why, size_t size = sizeof(aule_varlen_bwd_desc), uint64_t more = 0,
+                                         bool d256 = false) {
     const aule_varlen_desc* x = varlen_prefix(d);
-    if (const char* e = varlen_problem_error(x, size, why)) return e;
+    if (const char* e = varlen_problem_error(x, size, why, d256)) return e;
     if (!launch || varlen_bwd_nothing_to_do(x)) return nullptr;
     if (const char* e = varlen_input_error(x)) return e;
     if (d->total_q > 0 && (!d->out || !d->lse || !d->dout || !d->dq)) return "null tensor pointer";
@@ -2075,8 +2081,9 @@ static void fill_varlen_args(const aule_varlen_desc* d, aule_hip::VarlenArgs& a)
     a.dtype = d->dtype;
 }
 
-// (`d` passed varlen_desc_error with its kind's size and has something to do; `sinks`: the sink kind's logits, checked by the caller)
-static int32_t varlen_forward_launch(const aule_varlen_desc* d, const float* sinks, const char* what) {
+// (`d` passed varlen_desc_error with its kind's size and has something to do; `sinks`: the sink kind's logits, checked by the caller;
+// `d256`: the head_dim 256 kernels)
+static int32_t varlen_forward_launch(const aule_varlen_desc* d, const float* sinks, const char* what, bool d256 = false) {
     if (!initialised()) return -1;
     aule_hip::VarlenArgs a;
     fill_varlen_args(d, a);
@@ -2088,7 +2095,7 @@ static int32_t varlen_forward_launch(const aule_varlen_desc* d, const float* sin
     DeviceGuard g(d->device);
     int rc = ensure_configured();
     if (rc) return rc;
-    return launched(what, aule_hip::launch_varlen_fwd(a, (hipStream_t)d->stream));
+    return launched(what, d256 ? aule_hip::launch_varlen_d256_fwd(a, (hipStream_t)d->stream) : aule_hip::launch_varlen_fwd(a, (hipStream_t)d->stream));
 }
 
 int32_t aule_attention_varlen_forward_ex(const aule_varlen_desc* d) {
@@ -2120,14 +2127,15 @@ int32_t aule_attention_varlen_sink_forward_ex(const aule_varlen_sink_desc* d) {
 
 // (`d` passed varlen_bwd_desc_error with its kind's size and has something to do; sinks / dsinks: the sink kind's, checked by the caller,
 // the partials of its reduction behind delta in the workspace)
-static int32_t varlen_backward_launch(const aule_varlen_bwd_desc* d, const float* sinks, float* dsinks, const char* what) {
+static int32_t varlen_backward_launch(const aule_varlen_bwd_desc* d, const float* sinks, float* dsinks, const char* what, bool d256 = false) {
+    const auto launch = d256 ? aule_hip::launch_varlen_d256_bwd : aule_hip::launch_varlen_bwd;
     const aule_varlen_desc* x = varlen_prefix(d);
     if (!initialised()) return -1;
     aule_hip::VarlenArgs a;
     fill_varlen_args(x, a);
     a.o = d->out; a.lse = const_cast<float*>(d->lse); a.dout = d->dout;
     a.dq = d->dq; a.dk = d->dk; a.dv = d->dv; a.sinks = sinks;
-    if (aule_hip::varlen_fwd_grid(a) > 0x7fffffffll || aule_hip::varlen_dkdv_grid(a) > 0x7fffffffll) {
+    if (aule_hip::varlen_fwd_grid(a) > 0x7fffffffll || (d256 ? aule_hip::varlen_d256_dkdv_grid(a) : aule_hip::varlen_dkdv_grid(a)) > 0x7fffffffll) {
         set_error("%s failed: a grid exceeds 2^31 - 1 workgroups", what);
         return -3;
     }
@@ -2138,7 +2146,7 @@ static int32_t varlen_backward_launch(const aule_varlen_bwd_desc* d, const float
     const uint64_t delta_bytes = varlen_bwd_workspace(x);
     const uint64_t need = delta_bytes + (sinks ? aule_hip::varlen_dsinks_partial_bytes(a) : 0);
     if (need == 0) {
-        rc = aule_hip::launch_varlen_bwd(a, stream);
+        rc = launch(a, stream);
         if (rc == 0 && sinks) rc = aule_hip::launch_varlen_dsinks(a, dsinks, nullptr, stream);
         return launched(what, rc);
     }
@@ -2148,7 +2156,7 @@ static int32_t varlen_backward_launch(const aule_varlen_bwd_desc* d, const float
         return -4;
     }
     a.delta = static_cast<float*>(ws.ptr);
-    rc = aule_hip::launch_varlen_bwd(a, stream);
+    rc = launch(a, stream);
     if (rc == 0 && sinks) rc = aule_hip::launch_varlen_dsinks(a, dsinks, reinterpret_cast<float*>(static_cast<char*>(ws.ptr) + delta_bytes), stream);
     return launched(what, rc);
 }
@@ -2168,6 +2176,38 @@ int32_t aule_attention_varlen_backward_ex(const aule_varlen_bwd_desc* d) {
 uint64_t aule_attention_varlen_backward_workspace_size(const aule_varlen_bwd_desc* d) {
     Reason text;
     if (varlen_bwd_desc_error(d, false, text)) return 0;
+    return varlen_bwd_nothing_to_do(varlen_prefix(d)) ? 0 : varlen_bwd_workspace(varlen_prefix(d));
+}
+
+// The same at head_dim 256 (fa_fwd_varlen_d256_gfx950.hip, fa_bwd_varlen_d256_gfx950.hip): the descriptors, checkers, nothing-to-do rules,
+// launch helpers and workspace of the entries above with the one head_dim rule, the launchers and the error prefixes of their own.
+int32_t aule_attention_varlen_d256_forward_ex(const aule_varlen_desc* d) {
+    RoctxRange range("aule.varlen_d256_forward");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = varlen_desc_error(d, text, sizeof(aule_varlen_desc), true)) {
+        set_error("Variable-length attention (head_dim 256) failed: %s", why);
+        return -3;
+    }
+    if (varlen_fwd_nothing_to_do(d)) return 0;
+    return varlen_forward_launch(d, nullptr, "Variable-length attention (head_dim 256)", true);
+}
+
+int32_t aule_attention_varlen_d256_backward_ex(const aule_varlen_bwd_desc* d) {
+    RoctxRange range("aule.varlen_d256_backward");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = varlen_bwd_desc_error(d, true, text, sizeof(aule_varlen_bwd_desc), 0, true)) {
+        set_error("Variable-length backward (head_dim 256) failed: %s", why);
+        return -3;
+    }
+    if (varlen_bwd_nothing_to_do(varlen_prefix(d))) return 0;
+    return varlen_backward_launch(d, nullptr, nullptr, "Variable-length backward (head_dim 256)", true);
+}
+
+uint64_t aule_attention_varlen_d256_backward_workspace_size(const aule_varlen_bwd_desc* d) {
+    Reason text;
+    if (varlen_bwd_desc_error(d, false, text, sizeof(aule_varlen_bwd_desc), 0, true)) return 0;
     return varlen_bwd_nothing_to_do(varlen_prefix(d)) ? 0 : varlen_bwd_workspace(varlen_prefix(d));
 }
 

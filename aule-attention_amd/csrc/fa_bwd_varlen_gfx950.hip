@@ -15,6 +15,8 @@
 //             tokens that can see the block (from token k0 - coff under the causal rule, up to klast + W - coff with a window).
 //             A workgroup past its sequence's blocks returns before it touches memory.
 // Every owned row of dq, dk and dv is written (zeros where nothing is seen, n = 0 included); rows that belong to no sequence never.
+// The dK/dV kernel has a twin at head_dim 256, fa_bwd_varlen_d256_dkdv_kernel (fa_bwd_varlen_d256_gfx950.hip: the same ranges, masks and
+// walk over a column half): a fix to the clamps, the row range, the skips or the mask here belongs there too.
 #include "fa_kernels.h"
 #include "fa_varlen_common.h"
 
@@ -211,13 +213,29 @@ uint64_t varlen_bwd_workspace_bytes(long long Tq, int Hq) {
     return ((uint64_t)Tq * Hq * sizeof(float) + 255) / 256 * 256;
 }
 
+// The delta kernel alone, over all Tq rows of the contiguous out / dout: any D % 8 == 0 (the head_dim 256 backward,
+// fa_bwd_varlen_d256_gfx950.hip, starts with it)
+int launch_varlen_delta(const VarlenArgs& a, hipStream_t stream) {
+    const long long rows = (long long)a.Tq * a.Hq;
+    if (rows <= 0) return 0;
+    if (a.D <= 0 || a.D % 8 != 0 || (rows + 3) / 4 > 0x7fffffffll) return -1;
+    VarlenBwdParams p = {};
+    p.o = static_cast<const char*>(a.o); p.dout = static_cast<const char*>(a.dout); p.delta = a.delta;
+    p.D = a.D;
+    return dispatch_16bit(a.dtype, [&](auto t) {
+        hipLaunchKernelGGL((fa_bwd_varlen_delta_kernel<decltype(t)>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, p, rows);
+        return (int)hipGetLastError();
+    });
+}
+
 int launch_varlen_bwd(const VarlenArgs& a, hipStream_t stream) {
     if (!varlen_args_ok(a)) return -1;
     const long long dq_grid = varlen_fwd_grid(a), dkdv_grid = varlen_dkdv_grid(a);
     if (dq_grid <= 0 && dkdv_grid <= 0) return 0;
     if (dq_grid > 0x7fffffffll || dkdv_grid > 0x7fffffffll || ((long long)a.Tq + kPQ) * (a.Hq / a.Hkv) > 0x7fffffffll) return -1;
-    const long long rows = (long long)a.Tq * a.Hq;
-    if ((rows + 3) / 4 > 0x7fffffffll) return -1;
+    if (dq_grid > 0) {   // queued before the dispatch below accepts (dtype, D): where that refuses, delta (the workspace) is already written
+        if (const int rc = launch_varlen_delta(a, stream)) return rc;
+    }
     VarlenBwdParams p;
     p.q = static_cast<const char*>(a.q); p.k = static_cast<const char*>(a.k); p.v = static_cast<const char*>(a.v);
     p.o = static_cast<const char*>(a.o); p.dout = static_cast<const char*>(a.dout); p.lse = a.lse; p.delta = a.delta;
@@ -234,10 +252,7 @@ int launch_varlen_bwd(const VarlenArgs& a, hipStream_t stream) {
     return dispatch_tile_instance(a.dtype, a.D, [&](auto t, auto d) {
         using T = decltype(t);
         constexpr int D = decltype(d)::value;
-        if (dq_grid > 0) {
-            hipLaunchKernelGGL((fa_bwd_varlen_delta_kernel<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, p, rows);
-            hipLaunchKernelGGL((fa_bwd_varlen_dq_kernel<T, D>), dim3((unsigned)dq_grid), dim3(256), 0, stream, p);
-        }
+        if (dq_grid > 0) hipLaunchKernelGGL((fa_bwd_varlen_dq_kernel<T, D>), dim3((unsigned)dq_grid), dim3(256), 0, stream, p);
         if (dkdv_grid > 0) hipLaunchKernelGGL((fa_bwd_varlen_dkdv_kernel<T, D>), dim3((unsigned)dkdv_grid), dim3(256), 0, stream, p);
         return (int)hipGetLastError();
     });

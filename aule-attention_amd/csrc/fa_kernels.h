@@ -534,6 +534,13 @@ long long varlen_dkdv_grid(const VarlenArgs& a);
 uint64_t varlen_bwd_workspace_bytes(long long Tq, int Hq);   // delta
 int launch_varlen_fwd(const VarlenArgs& a, hipStream_t stream);   // -1: unsupported arguments
 int launch_varlen_bwd(const VarlenArgs& a, hipStream_t stream);   // delta, dQ, dK/dV on `stream`
+// The same at head_dim 256 (fa_fwd_varlen_d256_gfx950.hip, fa_bwd_varlen_d256_gfx950.hip): VarlenArgs with D = 256 and
+// no sinks, the same clamps, cuts, window rule and forward / dQ grid; the dK/dV grid holds two column halves per key block of 128.
+// The workspace is delta, varlen_bwd_workspace_bytes.  launch_varlen_delta is the backward's first launch, shared by both widths.
+long long varlen_d256_dkdv_grid(const VarlenArgs& a);   // 2 ceil(min(max_seqlen_k, Tk) / 128) x Hkv x B
+int launch_varlen_delta(const VarlenArgs& a, hipStream_t stream);      // delta = rowsum(dout * o) over all Tq rows, any D % 8 == 0
+int launch_varlen_d256_fwd(const VarlenArgs& a, hipStream_t stream);   // -1: unsupported arguments
+int launch_varlen_d256_bwd(const VarlenArgs& a, hipStream_t stream);   // delta, dQ, dK/dV on `stream`
 // The gradient of the sink logits (fa_bwd_sinks_gfx950.hip), after launch_varlen_bwd on the same stream: reads a.lse (the forward's, sinks
 // included), a.delta (that launch's workspace), a.sinks and a.cu_seqlens_q over the owned rows only; two launches, no atomics, a fixed
 // summation order; `partials` is varlen_dsinks_partial_bytes(a) bytes of workspace; exactly Hq floats of dsinks are written.

@@ -895,6 +895,19 @@ int32_t aule_attention_varlen_backward_ex(const aule_varlen_bwd_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses. */
 uint64_t aule_attention_varlen_backward_workspace_size(const aule_varlen_bwd_desc* desc);
 
+/* VARIABLE-LENGTH packed batches at head_dim 256 (additive): the contract above, word for word, for the models whose heads are 256 */
+/* wide (Gemma-2, Gemma-3, Qwen3-Next) -- the same two descriptors, the same token strides, device-side clamps, max_seqlen_* cuts,  */
+/* causal modes, window rule, empty and unowned rows, capture behaviour, answers before aule_init() and workspace (delta alone,      */
+/* [total_q, heads_q] fp32 rounded up to 256 bytes).  What differs: head_dim must be 256 (any other value is -3; nothing is padded), */
+/* and the kernels are their own: the forward and the dQ launch have the grid stated above, the dK/dV launch        */
+/* 2 * ceil(min(max_seqlen_k, total_k) / 128) * heads_kv * batch workgroups (two column halves per key block).  No atomics: two runs  */
+/* give the same bits.  The entries above keep refusing head_dim 256.  Not built: sinks, fp32, FP8 inputs, key-range splits.         */
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_varlen_d256_forward_ex(const aule_varlen_desc* desc);
+int32_t aule_attention_varlen_d256_backward_ex(const aule_varlen_bwd_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses. */
+uint64_t aule_attention_varlen_d256_backward_workspace_size(const aule_varlen_bwd_desc* desc);
+
 /* ATTENTION SINKS (additive): per-head sink logits for the variable-length, paged-prefill and paged-query entries above -- the    */
 /* models whose heads each carry a learned logit that joins the softmax denominator and contributes no value (gpt-oss and its      */
 /* derivatives).  sinks is [heads_q] fp32 on the DEVICE: a raw logit, multiplied by neither scale nor k_scale; the kernels read it   */

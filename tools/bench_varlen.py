@@ -26,7 +26,6 @@ import torch  # noqa: E402
 
 import aule  # noqa: E402
 
-HQ, HKV, D = 32, 8, 128
 WINDOW_MS = 40
 
 
@@ -48,7 +47,7 @@ def _arg(name, default, cast=int):
     return cast(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
 
 
-def leg(name, ns, backward, rounds, lines):
+def leg(name, ns, backward, rounds, lines, HQ, HKV, D, varlen_entry):
     g = torch.Generator(device="cuda").manual_seed(len(ns) + ns[0])
     dt = torch.bfloat16
     B, T, S = len(ns), sum(ns), max(ns)
@@ -71,7 +70,7 @@ def leg(name, ns, backward, rounds, lines):
             x.requires_grad_(True)
 
     def varlen():
-        out = aule.flash_attention_varlen(q, k, v, cu, cu, max_seqlen_q=S, max_seqlen_k=S, causal=True)
+        out = varlen_entry(q, k, v, cu, cu, max_seqlen_q=S, max_seqlen_k=S, causal=True)
         return torch.autograd.grad(out, (q, k, v), dout) if backward else out
 
     def per_sequence():
@@ -132,19 +131,20 @@ def leg(name, ns, backward, rounds, lines):
     lines.append(line)
 
 
-def main():
+def main(HQ=32, HKV=8, D=128, varlen_entry=aule.flash_attention_varlen, TOOL="tools/bench_varlen.py", batches=None):
+    """(tools/bench_varlen_d256.py runs the same legs with its own heads, head_dim, entry and order of batches)"""
     if not torch.cuda.is_available():
         raise SystemExit("bench_varlen needs a GPU: a timing taken anywhere else says nothing")
     rounds, budget = _arg("--rounds", 5), _arg("--leg-timeout", 180)
     signal.signal(signal.SIGALRM, signal.SIG_DFL)      # the default action ends the process, also from inside a blocked device call
-    head = (f"# tools/bench_varlen.py   (one MI355X; causal self-attention, {HQ} q / {HKV} kv heads, head_dim {D}, bf16; {rounds} alternated rounds of "
+    head = (f"# {TOOL}   (one MI355X; causal self-attention, {HQ} q / {HKV} kv heads, head_dim {D}, bf16; {rounds} alternated rounds of "
             f"~{WINDOW_MS} ms windows, median (min .. max) us per call, host launch cost included; the padded route's padding is not timed)")
     print(head, flush=True)
     lines = [head]
-    for name, ns in BATCHES:
+    for name, ns in batches or BATCHES:
         for backward in (False, True):
             signal.alarm(budget)
-            leg(name, ns, backward, rounds, lines)
+            leg(name, ns, backward, rounds, lines, HQ, HKV, D, varlen_entry)
             signal.alarm(0)
     if "--out" in sys.argv:
         path = _arg("--out", "", str)
