@@ -309,6 +309,26 @@ def flash_attention_paged_d256(q, k_cache, v_cache, block_tables, context_lens, 
                       window_size=window_size, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
 
 
+def flash_attention_paged_d256_softcap(q, k_cache, v_cache, softcap, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=1, scale=None,
+                                       window_size=-1, k_scale=None, v_scale=None, return_lse=False):
+    """flash_attention_paged_d256 with LOGIT SOFT-CAPPING (Gemma-2: softcap = 50.0): for a token and its visible keys
+
+        s_j = softcap * tanh(scale * q.k_j / softcap),   out = softmax_j(s_j) . V,   lse = ln sum_j exp(s_j)
+
+    in one HIP kernel of its own (csrc/fa_fwd_paged_d256_softcap_gfx950.hip).  softcap is a finite Python float > 0, a
+    model constant passed by value; anything else is a ValueError (0 names flash_attention_paged_d256, the call without a cap).  The
+    mask is applied after the cap; with a float8_e4m3fn cache k_scale is part of the key and sits inside the tanh.  Every other
+    argument, rule and return value is flash_attention_paged_d256's: 16-bit and FP8 caches, plain decode with cu_seqlens_q=None, the
+    window, the device-side clamps, no synchronisation, capturable, two runs bit-identical."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import paged_d256_softcap
+    return paged_d256_softcap(q, k_cache, v_cache, softcap, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q,
+                              scale=scale, window_size=window_size, k_scale=k_scale, v_scale=v_scale, return_lse=return_lse)
+
+
 def flash_attention_mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, scale=None,
                               return_lse=False):
     """Paged multi-head LATENT attention (MLA, the DeepSeek-V2 / V3 / R1 family in its absorbed decode form): decode and short
@@ -627,6 +647,25 @@ def flash_attention_varlen_d256(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_
         raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
     from ._torch import flash_attention_varlen_d256 as impl
     return impl(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k, causal=causal,
+                scale=scale, window_size=window_size, return_lse=return_lse)
+
+
+def flash_attention_varlen_d256_softcap(q, k, v, softcap, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True,
+                                        scale=None, window_size=-1, return_lse=False):
+    """flash_attention_varlen_d256 with LOGIT SOFT-CAPPING (Gemma-2: softcap = 50.0), forward and backward (autograd over q, k, v):
+
+        s_ij = softcap * tanh(scale * q_i.k_j / softcap),   out = softmax_j(s_ij) . V,   lse_i = ln sum_j exp(s_ij)
+
+    in HIP kernels of their own (csrc/fa_varlen_d256_softcap_gfx950.hip); the backward carries the factor
+    1 - tanh^2 of the cap.  softcap is a finite Python float > 0, a model constant passed by value; anything else is a ValueError (0
+    names flash_attention_varlen_d256, the call without a cap).  The mask is applied after the cap: a token that sees no key gives a
+    row of zeros (lse -inf, zero gradient).  Every other argument, rule and return value is flash_attention_varlen_d256's."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import flash_attention_varlen_d256_softcap as impl
+    return impl(q, k, v, softcap, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k, causal=causal,
                 scale=scale, window_size=window_size, return_lse=return_lse)
 
 
@@ -1059,7 +1098,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_d256", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_d256", "flash_attention_varlen_d256_softcap", "flash_attention_paged_d256_softcap", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

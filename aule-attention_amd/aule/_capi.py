@@ -378,6 +378,25 @@ class VarlenSinkBwdDesc(ctypes.Structure):
     _fields_ = VarlenBwdDesc._fields_ + [("sinks", ctypes.c_void_p), ("dsinks", ctypes.c_void_p)]
 
 
+# The soft-cap kinds (logit soft-capping at head_dim 256: include/aule.h): each is its twin field for field, then softcap and its padding.
+_SOFTCAP = [("softcap", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+
+class VarlenSoftcapDesc(ctypes.Structure):
+    """struct aule_varlen_softcap_desc (include/aule.h): aule_varlen_desc plus softcap."""
+    _fields_ = VarlenDesc._fields_ + _SOFTCAP
+
+
+class VarlenSoftcapBwdDesc(ctypes.Structure):
+    """struct aule_varlen_softcap_bwd_desc (include/aule.h): aule_varlen_bwd_desc plus softcap."""
+    _fields_ = VarlenBwdDesc._fields_ + _SOFTCAP
+
+
+class PagedD256SoftcapDesc(ctypes.Structure):
+    """struct aule_paged_d256_softcap_desc (include/aule.h): aule_paged_d256_desc plus softcap."""
+    _fields_ = PagedD256Desc._fields_ + _SOFTCAP
+
+
 class PagedPrefillSinkDesc(ctypes.Structure):
     """struct aule_paged_prefill_sink_desc (include/aule.h): aule_paged_prefill_desc plus sinks."""
     _fields_ = PagedPrefillDesc._fields_ + [("sinks", ctypes.c_void_p)]
@@ -626,6 +645,11 @@ SIGNATURES = [
     ("aule_attention_varlen_d256_forward_ex", _I32, [ctypes.POINTER(VarlenDesc)]),
     ("aule_attention_varlen_d256_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),
     ("aule_attention_varlen_d256_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenBwdDesc)]),
+    ("aule_attention_varlen_d256_softcap_forward_ex", _I32, [ctypes.POINTER(VarlenSoftcapDesc)]),
+    ("aule_attention_varlen_d256_softcap_backward_ex", _I32, [ctypes.POINTER(VarlenSoftcapBwdDesc)]),
+    ("aule_attention_varlen_d256_softcap_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenSoftcapBwdDesc)]),
+    ("aule_attention_paged_d256_softcap_ex", _I32, [ctypes.POINTER(PagedD256SoftcapDesc)]),
+    ("aule_attention_paged_d256_softcap_workspace_size", ctypes.c_uint64, [ctypes.POINTER(PagedD256SoftcapDesc)]),
     ("aule_attention_varlen_sink_forward_ex", _I32, [ctypes.POINTER(VarlenSinkDesc)]),
     ("aule_attention_varlen_sink_backward_ex", _I32, [ctypes.POINTER(VarlenSinkBwdDesc)]),
     ("aule_attention_varlen_sink_backward_workspace_size", ctypes.c_uint64, [ctypes.POINTER(VarlenSinkBwdDesc)]),

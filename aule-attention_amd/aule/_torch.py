@@ -784,14 +784,29 @@ VARLEN_FWD = "aule_attention_varlen_forward_ex"
 VARLEN_BWD = ("aule_attention_varlen_backward_workspace_size", "aule_attention_varlen_backward_ex")
 VARLEN_D256_FWD = "aule_attention_varlen_d256_forward_ex"
 VARLEN_D256_BWD = ("aule_attention_varlen_d256_backward_workspace_size", "aule_attention_varlen_d256_backward_ex")
+VARLEN_D256_SOFTCAP_FWD = "aule_attention_varlen_d256_softcap_forward_ex"
+VARLEN_D256_SOFTCAP_BWD = ("aule_attention_varlen_d256_softcap_backward_workspace_size", "aule_attention_varlen_d256_softcap_backward_ex")
+
+
+def _softcap_arg(softcap, twin):
+    """the soft-cap kinds' one argument of their own: a finite Python number > 0 (a model constant, passed by value); `twin`: the call
+    for attention without a cap"""
+    if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
+        raise ValueError(f"softcap must be a Python float (a model constant, e.g. 50.0 for Gemma-2), got {type(softcap).__name__}")
+    if softcap == 0:
+        raise ValueError(f"softcap is 0: for attention without a cap call {twin}")
+    if not (softcap > 0 and math.isfinite(softcap)):
+        raise ValueError(f"softcap must be a finite value > 0, got {softcap}")
+    return float(softcap)
 
 
 def varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1, want_lse=True, sinks=None,
-                   launch=VARLEN_FWD):
+                   launch=VARLEN_FWD, softcap=None):
     """q [Tq,Hq,D], k / v [Tk,Hkv,D] device tensors (heads contiguous, D in VARLEN_HEAD_DIMS), cu_q / cu_k int32 [B + 1] on the same
     device, causal an AULE_CAUSAL_* code.  Returns (out, lse or None), both from torch.empty.  Asynchronous, no synchronisation.
     sinks: [Hq] fp32 contiguous sink logits on the same device (aule_attention_varlen_sink_forward_ex), or None.
-    launch: the entry (aule_attention_varlen_d256_forward_ex takes the same descriptor at D = 256)."""
+    launch: the entry (aule_attention_varlen_d256_forward_ex takes the same descriptor at D = 256).
+    softcap: a float > 0 (D = 256, no sinks): the logits are capped, through aule_attention_varlen_d256_softcap_forward_ex."""
     lib = _capi.get_lib()
     _same_device("variable-length attention", q, k, v, cu_q, cu_k)
     (q, sq), (k, sk), (v, sv) = _varlen_rows("q", q), _varlen_rows("k", k), _varlen_rows("v", v)
@@ -799,22 +814,25 @@ def varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scal
     lse = torch.empty(q.shape[:2], device=q.device, dtype=torch.float32) if want_lse else None
     if q.shape[0] * q.shape[1] * (cu_q.shape[0] - 1) == 0:
         return out, lse
-    d = _varlen_problem(_capi.VarlenDesc() if sinks is None else _capi.VarlenSinkDesc(), q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q,
-                        max_seqlen_k, causal, scale, window)
+    desc = _capi.VarlenSoftcapDesc if softcap is not None else _capi.VarlenDesc if sinks is None else _capi.VarlenSinkDesc
+    d = _varlen_problem(desc(), q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window)
     d.out = out.data_ptr()
     d.lse = lse.data_ptr() if lse is not None else None
     if sinks is not None:
         launch, d.sinks = "aule_attention_varlen_sink_forward_ex", sinks.data_ptr()
+    if softcap is not None:
+        launch, d.softcap = VARLEN_D256_SOFTCAP_FWD, softcap
     _capi.check(getattr(lib, launch)(ctypes.byref(d)), launch)
     return out, lse
 
 
 def varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window=-1, sinks=None,
-                   entries=VARLEN_BWD):
+                   entries=VARLEN_BWD, softcap=None):
     """The gradients of varlen_fwd_raw: dq [Tq,Hq,D], dk, dv [Tk,Hkv,D], contiguous and ZERO in the rows no sequence owns (the
     library never writes those; they are allocated zero-filled here).  out, dout, lse contiguous.  Asynchronous, no synchronisation.
     sinks (the forward's): returns (dq, dk, dv, dsinks [Hq] fp32) through aule_attention_varlen_sink_backward_ex.
-    entries: (size query, launch) -- VARLEN_D256_BWD takes the same descriptor at D = 256."""
+    entries: (size query, launch) -- VARLEN_D256_BWD takes the same descriptor at D = 256.
+    softcap: the capped forward's (D = 256, no sinks), through VARLEN_D256_SOFTCAP_BWD."""
     lib = _capi.get_lib()
     _same_device("variable-length attention backward", q, k, v, out, dout, lse, cu_q, cu_k)
     (q, sq), (k, sk), (v, sv) = _varlen_rows("q", q), _varlen_rows("k", k), _varlen_rows("v", v)
@@ -825,14 +843,16 @@ def varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen
     grads = (dq, dk, dv) if sinks is None else (dq, dk, dv, dsinks)
     if q.shape[1] * (cu_q.shape[0] - 1) == 0 or q.shape[0] + k.shape[0] == 0:
         return grads
-    d = _varlen_problem(_capi.VarlenBwdDesc() if sinks is None else _capi.VarlenSinkBwdDesc(), q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q,
-                        max_seqlen_k, causal, scale, window)
+    desc = _capi.VarlenSoftcapBwdDesc if softcap is not None else _capi.VarlenBwdDesc if sinks is None else _capi.VarlenSinkBwdDesc
+    d = _varlen_problem(desc(), q, k, v, sq, sk, sv, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window)
     d.out, d.lse, d.dout = out.data_ptr(), lse.data_ptr(), dout.data_ptr()
     d.dq, d.dk, d.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
     size_query, launch = entries
     if sinks is not None:
         size_query, launch = "aule_attention_varlen_sink_backward_workspace_size", "aule_attention_varlen_sink_backward_ex"
         d.sinks, d.dsinks = sinks.data_ptr(), dsinks.data_ptr()
+    if softcap is not None:
+        (size_query, launch), d.softcap = VARLEN_D256_SOFTCAP_BWD, softcap
     ws = _attach_workspace(d, getattr(lib, size_query), q.device)   # delta [Tq, Hq] fp32 (and the dsinks partials); held until the launch is queued
     _capi.check(getattr(lib, launch)(ctypes.byref(d)), launch)
     del ws
@@ -869,11 +889,40 @@ class FlashAttentionVarlenD256HipFunc(FlashAttentionVarlenHipFunc):
         return _varlen_func_forward(ctx, VARLEN_D256_FWD, VARLEN_D256_BWD, *args)
 
 
+class FlashAttentionVarlenD256SoftcapHipFunc(torch.autograd.Function):
+    """The head_dim 256 Function with capped logits: softcap (a float) rides with the problem statement."""
+    @staticmethod
+    def forward(ctx, q, k, v, softcap, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window):
+        out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window, softcap=softcap)
+        ctx.save_for_backward(q, k, v, out, lse, cu_q, cu_k)
+        ctx.problem = (max_seqlen_q, max_seqlen_k, causal, scale, window, softcap)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, _dlse):
+        q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors
+        max_seqlen_q, max_seqlen_k, causal, scale, window, softcap = ctx.problem
+        dout = dout.contiguous().to(q.dtype)
+        dq, dk, dv = varlen_bwd_raw(q, k, v, out, dout, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale, window, softcap=softcap)
+        return dq, dk, dv, None, None, None, None, None, None, None, None
+
+
+def flash_attention_varlen_d256_softcap(q, k, v, softcap, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True,
+                                        scale=None, window_size=-1, return_lse=False):
+    """flash_attention_varlen_d256 with capped logits, autograd-aware (aule.flash_attention_varlen_d256_softcap documents the arguments)."""
+    softcap = _softcap_arg(softcap, "flash_attention_varlen_d256")
+    return flash_attention_varlen_d256(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, scale, window_size, return_lse,
+                                       _softcap=softcap)
+
+
 def flash_attention_varlen_d256(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
-                                window_size=-1, return_lse=False):
-    """Variable-length attention at head_dim 256, autograd-aware (aule.flash_attention_varlen_d256 documents the arguments)."""
+                                window_size=-1, return_lse=False, _softcap=None):
+    """Variable-length attention at head_dim 256, autograd-aware (aule.flash_attention_varlen_d256 documents the arguments).
+    _softcap: flash_attention_varlen_d256_softcap's checked cap."""
+    name = "flash_attention_varlen_d256" + ("_softcap" if _softcap is not None else "")
     if torch.is_tensor(q) and q.dim() == 3 and q.shape[2] != 256:
-        raise ValueError(f"flash_attention_varlen_d256 takes head_dim 256 alone, got {q.shape[2]}: flash_attention_varlen serves head dims up to "
+        raise ValueError(f"{name} takes head_dim 256 alone, got {q.shape[2]}: flash_attention_varlen serves head dims up to "
                          f"{VARLEN_HEAD_DIMS[-1]}")
     _varlen_check(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, head_dims=(256,))
     code = causal_code(causal)
@@ -888,10 +937,13 @@ def flash_attention_varlen_d256(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_
     max_seqlen_q, max_seqlen_k = _varlen_maxima(cu_q, cu_k, max_seqlen_q, max_seqlen_k)
     window = _window_arg(window_size)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        out, lse = FlashAttentionVarlenD256HipFunc.apply(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window)
+        if _softcap is not None:
+            out, lse = FlashAttentionVarlenD256SoftcapHipFunc.apply(q, k, v, _softcap, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window)
+        else:
+            out, lse = FlashAttentionVarlenD256HipFunc.apply(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window)
     else:
         out, lse = varlen_fwd_raw(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k, code, float(scale), window, want_lse=return_lse,
-                                  launch=VARLEN_D256_FWD)
+                                  launch=VARLEN_D256_FWD, softcap=_softcap)
     return (out, lse) if return_lse else out
 
 
@@ -1366,15 +1418,18 @@ def paged_cascade(q, k_cache, v_cache, prefix_block_table, prefix_len, block_tab
 
 
 def paged_d256(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=1, scale=None, window_size=-1,
-               k_scale=None, v_scale=None, return_lse=False, force_nsplit=None):
+               k_scale=None, v_scale=None, return_lse=False, force_nsplit=None, softcap=None):
     """Paged attention at head_dim 256 (aule.flash_attention_paged_d256 documents the arguments; aule_paged_d256_desc in include/aule.h
     is the contract); csrc/fa_fwd_paged_d256_gfx950.hip behind aule_attention_paged_d256_ex.  The steps and the shared rules are
     paged_prefill's; this entry's own are head_dim == 256, cu_seqlens_q = None for plain decode (mla_paged's rule) and both scales
     with an FP8 cache.  force_nsplit (tests, tools/bench_paged_d256.py): that many key ranges instead of the plan's, through
-    aule_hip_debug_paged_d256_launch_nsplit."""
+    aule_hip_debug_paged_d256_launch_nsplit.  softcap (aule.flash_attention_paged_d256_softcap): a checked float > 0, the logits are
+    capped, through aule_attention_paged_d256_softcap_ex (the plan's key ranges alone)."""
+    if softcap is not None and force_nsplit is not None:
+        raise ValueError("force_nsplit is the uncapped entry's debug launch")
     Hkv = _paged_shapes(q, "T,Hq,D", k_cache, v_cache)
     if q.shape[-1] != 256:
-        raise ValueError(f"flash_attention_paged_d256 is built for head_dim 256 only, got {q.shape[-1]} "
+        raise ValueError(f"flash_attention_paged_d256{'_softcap' if softcap is not None else ''} is built for head_dim 256 only, got {q.shape[-1]} "
                          f"(head_dim 32, 64 and 128: flash_attention_paged_prefill)")
     fp8 = _paged_cache_kind("prefill", q, k_cache, v_cache, k_scale, v_scale, head_dims=None)
     if fp8 and (k_scale is None or v_scale is None):
@@ -1400,18 +1455,27 @@ def paged_d256(q, k_cache, v_cache, block_tables, context_lens, cu_seqlens_q=Non
     out, lse, result = _ragged_result(q, D, return_lse)
     if T * B * Hq == 0:
         return result
-    d = _paged_problem(_capi.PagedD256Desc(), q, k_cache, v_cache, out, bt, cl, scale, fp8)
+    d = _paged_problem(_capi.PagedD256Desc() if softcap is None else _capi.PagedD256SoftcapDesc(), q, k_cache, v_cache, out, bt, cl, scale, fp8)
     d.total_tokens, d.max_seqlen_q, d.q_token_stride = T, min(max_seqlen_q, T), q_stride
     d.window_size = _window_arg(window_size)
     d.lse = lse.data_ptr() if lse is not None else None
     d.cu_seqlens_q = cu.data_ptr() if cu is not None else None
     held += [k_cache, v_cache, _attach_scales(d, fp8, k_scale, v_scale, Hkv, q.device)]   # held until the launch is queued
-    if force_nsplit is None:
+    if softcap is not None:
+        d.softcap = softcap
+        held.append(_attach_workspace(d, lib.aule_attention_paged_d256_softcap_workspace_size, q.device))
+        _capi.check(lib.aule_attention_paged_d256_softcap_ex(ctypes.byref(d)), "aule_attention_paged_d256_softcap_ex")
+    elif force_nsplit is None:
         held.append(_attach_workspace(d, lib.aule_attention_paged_d256_workspace_size, q.device))
         _capi.check(lib.aule_attention_paged_d256_ex(ctypes.byref(d)), "aule_attention_paged_d256_ex")
     else:   # (no workspace of the caller's: the library allocates on the stream for this nsplit)
         _capi.check(lib.aule_hip_debug_paged_d256_launch_nsplit(ctypes.byref(d), int(force_nsplit)), "aule_hip_debug_paged_d256_launch_nsplit")
     return result
+
+
+def paged_d256_softcap(q, k_cache, v_cache, softcap, block_tables, context_lens, **kwargs):
+    """paged_d256 with capped logits (aule.flash_attention_paged_d256_softcap documents the arguments)."""
+    return paged_d256(q, k_cache, v_cache, block_tables, context_lens, softcap=_softcap_arg(softcap, "flash_attention_paged_d256"), **kwargs)
 
 
 def mla_paged(q, kv_cache, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, scale=None, return_lse=False):

@@ -203,6 +203,22 @@ static_assert(AULE_VARLEN_SAME(dtype) && AULE_VARLEN_SAME(batch) && AULE_VARLEN_
                   AULE_VARLEN_SAME(q) && AULE_VARLEN_SAME(k) && AULE_VARLEN_SAME(v) && AULE_VARLEN_SAME(cu_seqlens_q) && AULE_VARLEN_SAME(cu_seqlens_k),
               "aule_varlen_bwd_desc states the problem in the fields of aule_varlen_desc, up to cu_seqlens_k: both are checked through that prefix");
 #undef AULE_VARLEN_SAME
+// The soft-cap kinds (head_dim 256): each is its twin plus one float, padded to the struct's alignment, and is read through the twin's type.
+static_assert(sizeof(aule_varlen_softcap_desc) == 152 && offsetof(aule_varlen_softcap_desc, softcap) == sizeof(aule_varlen_desc) &&
+                  offsetof(aule_varlen_softcap_desc, stream) == offsetof(aule_varlen_desc, stream) && offsetof(aule_varlen_softcap_desc, lse) == offsetof(aule_varlen_desc, lse),
+              "aule_varlen_softcap_desc is aule_varlen_desc plus softcap");
+static_assert(sizeof(aule_varlen_softcap_bwd_desc) == 200 && offsetof(aule_varlen_softcap_bwd_desc, softcap) == sizeof(aule_varlen_bwd_desc) &&
+                  offsetof(aule_varlen_softcap_bwd_desc, stream) == offsetof(aule_varlen_bwd_desc, stream) &&
+                  offsetof(aule_varlen_softcap_bwd_desc, dout) == offsetof(aule_varlen_bwd_desc, dout) &&
+                  offsetof(aule_varlen_softcap_bwd_desc, workspace_bytes) == offsetof(aule_varlen_bwd_desc, workspace_bytes),
+              "aule_varlen_softcap_bwd_desc is aule_varlen_bwd_desc plus softcap");
+static_assert(sizeof(aule_paged_d256_softcap_desc) == 176 && offsetof(aule_paged_d256_softcap_desc, softcap) == sizeof(aule_paged_d256_desc) &&
+                  offsetof(aule_paged_d256_softcap_desc, stream) == offsetof(aule_paged_d256_desc, stream) &&
+                  offsetof(aule_paged_d256_softcap_desc, cu_seqlens_q) == offsetof(aule_paged_d256_desc, cu_seqlens_q) &&
+                  offsetof(aule_paged_d256_softcap_desc, v_scale) == offsetof(aule_paged_d256_desc, v_scale) &&
+                  offsetof(aule_paged_d256_softcap_desc, workspace_bytes) == offsetof(aule_paged_d256_desc, workspace_bytes),
+              "aule_paged_d256_softcap_desc is aule_paged_d256_desc plus softcap");
+
 // The sink kinds: each repeats its twin field for field at the same offsets and appends its pointers, so it is checked and read through
 // the twin's type (the twin's own checker, with the sink kind's size).
 #define AULE_SINK_SAME(kind, twin, field) (offsetof(kind, field) == offsetof(twin, field))
@@ -1811,9 +1827,11 @@ static void fill_paged_d256_args(const aule_paged_d256_desc* d, aule_hip::PagedD
 }
 
 // (force_nsplit > 0: the debug launch alone, aule_hip_debug_paged_d256_launch_nsplit; `plan`: the launch's, where there is one)
-static const char* paged_d256_desc_error(const aule_paged_d256_desc* d, bool launch, Reason& why, aule_hip::PagedD256Plan& plan, int force_nsplit = 0) {
+// (`size`: the kind's own sizeof -- aule_paged_d256_softcap_desc is read through this type)
+static const char* paged_d256_desc_error(const aule_paged_d256_desc* d, bool launch, Reason& why, aule_hip::PagedD256Plan& plan, int force_nsplit = 0,
+                                         size_t size = sizeof(aule_paged_d256_desc)) {
     plan = aule_hip::PagedD256Plan();
-    if (d == nullptr || d->struct_size != sizeof(aule_paged_d256_desc)) return kBadDescriptor;
+    if (d == nullptr || d->struct_size != size) return kBadDescriptor;
     if (const char* e = paged_dtype_error(d)) return e;
     if (d->head_dim != 256)
         return reasonf(why, "head_dim %u unsupported by the head_dim 256 entry (256 only; 32, 64 and 128: aule_attention_paged_prefill_ex)", d->head_dim);
@@ -1839,26 +1857,47 @@ static const char* paged_d256_desc_error(const aule_paged_d256_desc* d, bool lau
     return nullptr;
 }
 
-// (the launch entry, and with force_nsplit > 0 the debug launch)
+// The soft-cap kinds' one rule of their own: a finite cap > 0 (0 is "no cap": the twin's call).
+static const char* softcap_error(float softcap, const char* twin, Reason& why) {
+    if (softcap == 0.f) return reasonf(why, "softcap is 0: for attention without a cap call %s", twin);
+    if (!(softcap > 0.f) || !std::isfinite(softcap)) return reasonf(why, "softcap (%g) must be a finite value > 0", (double)softcap);
+    return nullptr;
+}
+
+// (the launch entry, and with force_nsplit > 0 the debug launch; `capped`: the soft-cap kind, read through its twin's type -- its size,
+// its prefix, its cap and its kernel)
 static const char kPagedD256[] = "Paged head_dim 256 attention";
-static int32_t paged_d256_launch(const aule_paged_d256_desc* d, int force_nsplit) {
+static const char kPagedD256Softcap[] = "Paged head_dim 256 soft-cap attention";
+static int32_t paged_d256_launch(const aule_paged_d256_desc* d, int force_nsplit, const aule_paged_d256_softcap_desc* capped = nullptr) {
+    const char* what = capped ? kPagedD256Softcap : kPagedD256;
     std::lock_guard<std::mutex> lk(g_mu);
     Reason text;
     aule_hip::PagedD256Plan plan;
-    if (const char* why = paged_d256_desc_error(d, true, text, plan, force_nsplit)) {
-        set_error("%s failed: %s", kPagedD256, why);
+    const char* why = paged_d256_desc_error(d, true, text, plan, force_nsplit, capped ? sizeof(aule_paged_d256_softcap_desc) : sizeof(aule_paged_d256_desc));
+    if (why == nullptr && capped) why = softcap_error(capped->softcap, "aule_attention_paged_d256_ex", text);
+    if (why != nullptr) {
+        set_error("%s failed: %s", what, why);
         return -3;
     }
     if (ragged_nothing_to_do(d)) return 0;
     if (!initialised()) return -1;
     aule_hip::PagedD256Args a;
     fill_paged_d256_args(d, a);
+    if (capped) {
+        const float softcap = capped->softcap;
+        return mla_launch_tail(d, plan, kPagedD256Softcap, [&](void* ws, hipStream_t stream) { return aule_hip::launch_paged_d256_softcap(a, softcap, plan, ws, stream); });
+    }
     return mla_launch_tail(d, plan, kPagedD256, [&](void* ws, hipStream_t stream) { return aule_hip::launch_paged_d256(a, plan, ws, stream); });
 }
 
 int32_t aule_attention_paged_d256_ex(const aule_paged_d256_desc* d) {
     RoctxRange range("aule.paged_d256");
     return paged_d256_launch(d, 0);
+}
+
+int32_t aule_attention_paged_d256_softcap_ex(const aule_paged_d256_softcap_desc* d) {
+    RoctxRange range("aule.paged_d256_softcap");
+    return paged_d256_launch(reinterpret_cast<const aule_paged_d256_desc*>(d), 0, d);
 }
 
 // The MLA indexer: index logits and top-k key lists, one checker per kind; `launch`: the pointer rules of a call that has something to
@@ -2082,8 +2121,8 @@ static void fill_varlen_args(const aule_varlen_desc* d, aule_hip::VarlenArgs& a)
 }
 
 // (`d` passed varlen_desc_error with its kind's size and has something to do; `sinks`: the sink kind's logits, checked by the caller;
-// `d256`: the head_dim 256 kernels)
-static int32_t varlen_forward_launch(const aule_varlen_desc* d, const float* sinks, const char* what, bool d256 = false) {
+// `d256`: the head_dim 256 kernels; `softcap` > 0: their soft-capped instances)
+static int32_t varlen_forward_launch(const aule_varlen_desc* d, const float* sinks, const char* what, bool d256 = false, float softcap = 0.f) {
     if (!initialised()) return -1;
     aule_hip::VarlenArgs a;
     fill_varlen_args(d, a);
@@ -2095,6 +2134,7 @@ static int32_t varlen_forward_launch(const aule_varlen_desc* d, const float* sin
     DeviceGuard g(d->device);
     int rc = ensure_configured();
     if (rc) return rc;
+    if (softcap > 0.f) return launched(what, aule_hip::launch_varlen_d256_softcap_fwd(a, softcap, (hipStream_t)d->stream));
     return launched(what, d256 ? aule_hip::launch_varlen_d256_fwd(a, (hipStream_t)d->stream) : aule_hip::launch_varlen_fwd(a, (hipStream_t)d->stream));
 }
 
@@ -2127,8 +2167,13 @@ int32_t aule_attention_varlen_sink_forward_ex(const aule_varlen_sink_desc* d) {
 
 // (`d` passed varlen_bwd_desc_error with its kind's size and has something to do; sinks / dsinks: the sink kind's, checked by the caller,
 // the partials of its reduction behind delta in the workspace)
-static int32_t varlen_backward_launch(const aule_varlen_bwd_desc* d, const float* sinks, float* dsinks, const char* what, bool d256 = false) {
-    const auto launch = d256 ? aule_hip::launch_varlen_d256_bwd : aule_hip::launch_varlen_bwd;
+static int32_t varlen_backward_launch(const aule_varlen_bwd_desc* d, const float* sinks, float* dsinks, const char* what, bool d256 = false,
+                                      float softcap = 0.f) {
+    // (`softcap` > 0: the soft-capped head_dim 256 kernels)
+    const auto launch = [&](const aule_hip::VarlenArgs& a, hipStream_t stream) {
+        if (softcap > 0.f) return aule_hip::launch_varlen_d256_softcap_bwd(a, softcap, stream);
+        return d256 ? aule_hip::launch_varlen_d256_bwd(a, stream) : aule_hip::launch_varlen_bwd(a, stream);
+    };
     const aule_varlen_desc* x = varlen_prefix(d);
     if (!initialised()) return -1;
     aule_hip::VarlenArgs a;
@@ -2209,6 +2254,51 @@ uint64_t aule_attention_varlen_d256_backward_workspace_size(const aule_varlen_bw
     Reason text;
     if (varlen_bwd_desc_error(d, false, text, sizeof(aule_varlen_bwd_desc), 0, true)) return 0;
     return varlen_bwd_nothing_to_do(varlen_prefix(d)) ? 0 : varlen_bwd_workspace(varlen_prefix(d));
+}
+
+// ... and with logit soft-capping (fa_varlen_d256_softcap_gfx950.hip): the head_dim 256 entries' checkers with the kind's own size, read
+// through the twins' types (the layout asserts at the top of this file), then the one rule of the cap.
+int32_t aule_attention_varlen_d256_softcap_forward_ex(const aule_varlen_softcap_desc* d) {
+    RoctxRange range("aule.varlen_d256_softcap_forward");
+    const char* what = "Variable-length soft-cap attention (head_dim 256)";
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    const aule_varlen_desc* x = reinterpret_cast<const aule_varlen_desc*>(d);
+    const char* why = varlen_desc_error(x, text, sizeof(aule_varlen_softcap_desc), true);
+    if (why == nullptr) why = softcap_error(d->softcap, "aule_attention_varlen_d256_forward_ex", text);
+    if (why != nullptr) {
+        set_error("%s failed: %s", what, why);
+        return -3;
+    }
+    if (varlen_fwd_nothing_to_do(x)) return 0;
+    return varlen_forward_launch(x, nullptr, what, true, d->softcap);
+}
+
+static const char* varlen_softcap_bwd_desc_error(const aule_varlen_softcap_bwd_desc* d, bool launch, Reason& why) {
+    const aule_varlen_bwd_desc* y = reinterpret_cast<const aule_varlen_bwd_desc*>(d);
+    if (const char* e = varlen_bwd_desc_error(y, launch, why, sizeof(aule_varlen_softcap_bwd_desc), 0, true)) return e;
+    return softcap_error(d->softcap, "aule_attention_varlen_d256_backward_ex", why);
+}
+
+int32_t aule_attention_varlen_d256_softcap_backward_ex(const aule_varlen_softcap_bwd_desc* d) {
+    RoctxRange range("aule.varlen_d256_softcap_backward");
+    const char* what = "Variable-length soft-cap backward (head_dim 256)";
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = varlen_softcap_bwd_desc_error(d, true, text)) {
+        set_error("%s failed: %s", what, why);
+        return -3;
+    }
+    const aule_varlen_bwd_desc* y = reinterpret_cast<const aule_varlen_bwd_desc*>(d);
+    if (varlen_bwd_nothing_to_do(varlen_prefix(y))) return 0;
+    return varlen_backward_launch(y, nullptr, nullptr, what, true, d->softcap);
+}
+
+uint64_t aule_attention_varlen_d256_softcap_backward_workspace_size(const aule_varlen_softcap_bwd_desc* d) {
+    Reason text;
+    if (varlen_softcap_bwd_desc_error(d, false, text)) return 0;
+    const aule_varlen_desc* x = varlen_prefix(reinterpret_cast<const aule_varlen_bwd_desc*>(d));
+    return varlen_bwd_nothing_to_do(x) ? 0 : varlen_bwd_workspace(x);
 }
 
 // the partials of the dsinks reduction for the problem `x` states (`x` passed varlen_problem_error)
@@ -2814,6 +2904,13 @@ uint64_t aule_attention_mla_paged_fp8mma_workspace_size(const aule_mla_paged_fp8
 uint64_t aule_attention_mla_paged_tree_workspace_size(const aule_mla_paged_tree_desc* d) {
     aule_hip::MlaPlan plan;
     return mla_paged_plan(mla_tree_prefix(d), kMlaTree, plan) ? plan.ws_bytes : 0;
+}
+
+uint64_t aule_attention_paged_d256_softcap_workspace_size(const aule_paged_d256_softcap_desc* d) {
+    Reason text;
+    aule_hip::PagedD256Plan plan;
+    if (paged_d256_desc_error(reinterpret_cast<const aule_paged_d256_desc*>(d), false, text, plan, 0, sizeof(aule_paged_d256_softcap_desc))) return 0;
+    return softcap_error(d->softcap, "aule_attention_paged_d256_ex", text) ? 0 : plan.ws_bytes;   // (the twin's plan: the cap changes no size)
 }
 
 uint64_t aule_attention_paged_d256_workspace_size(const aule_paged_d256_desc* d) {

@@ -23,8 +23,6 @@
 namespace aule_hip {
 namespace {
 
-constexpr int kHalfDT = CV256::DT / 2;   // accumulators of a column half: 4
-
 template <class T>
 __global__ void __launch_bounds__(256, 1) fa_bwd_varlen_d256_dq_kernel(const VarlenD256Params p) {
     using C = CV256;
@@ -107,137 +105,10 @@ __global__ void __launch_bounds__(256, 1) fa_bwd_varlen_d256_dq_kernel(const Var
     store_row16<T, C::DT>(p.dq + orow * (long long)C::RB, acc, p.scale, hi);
 }
 
-// The twin of fa_bwd_varlen_dkdv_kernel (fa_bwd_varlen_gfx950.hip) over a column half: the clamps, the row range, the per-wave skips and the
-// mask are that kernel's statements, and a fix to them there belongs here too.  (Shared as one template the D <= 128 instances would have to
-// be recompiled from changed text; fa_tile_attention.h says what that has cost before.)
+// (the body: fa_varlen_d256.h)
 template <class T>
 __global__ void __launch_bounds__(256, 1) fa_bwd_varlen_d256_dkdv_kernel(const VarlenD256Params p) {
-    using C = CV256;
-    __shared__ __attribute__((aligned(16))) char Qs[kVQT * C::PAT];
-    __shared__ __attribute__((aligned(16))) char Os[kVQT * C::PAT];
-    __shared__ float Ls[kVQT], Dl[kVQT];
-
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // blockIdx -> (key block, column half, sequence, KV head): the two halves of a key block side by side (they read the same rows),
-    // key block 0 first (under the top-left rule it sees the most queries)
-    const int bid = (int)blockIdx.x;
-    const int units = p.Hkv * p.B;
-    const int kbh = bid / units, unit = bid - kbh * units;
-    const int kb = kbh >> 1, ch = kbh & 1;
-    const int hk = unit % p.Hkv, b = unit / p.Hkv;
-
-    const SeqRange sk = seq_range(p.cu_k, b, p.Tk, p.max_sk);
-    const int L = sk.n;
-    const int k0 = kb * kVKB;
-    if (k0 >= L) return;
-    const SeqRange sq = seq_range(p.cu_q, b, p.Tq, p.max_sq);
-    const int n = sq.n;
-    const bool causal = p.causal != 0;
-    const int coff = p.causal == 2 ? L - n : 0;
-
-    // this lane's key (a lane past the end works on the sequence's last key and stores nothing)
-    const int kj = k0 + wave * 32 + l31;
-    const bool live = kj < L;
-    const int kjc = min(kj, L - 1);
-    const int wkey_lo = k0 + wave * 32, wkey_hi = min(wkey_lo + 31, L - 1);   // (wave-uniform)
-
-    // tokens that see any key of the block, as packed rows
-    const int klast = min(k0 + kVKB, L) - 1;
-    int tbeg = 0, tend = n;
-    if (causal) tbeg = min(n, max(0, k0 - coff));
-    if (p.window > 0) tend = (int)min((long long)n, max(0ll, (long long)klast + p.window - coff));   // (64-bit: the sum may pass 2^31)
-    const int rbeg = (int)((long long)tbeg * p.g / kVQT * kVQT);
-    const int rend = tend * p.g;
-    const int ntiles = rend > rbeg ? (rend - rbeg + kVQT - 1) / kVQT : 0;
-
-    const char* krow = p.k + (((long long)sk.s + kjc) * p.k_stride + (long long)hk * kVD) * 2;
-    const char* vrow = p.v + (((long long)sk.s + kjc) * p.v_stride + (long long)hk * kVD) * 2;
-    u32x4_t kf[C::G], vf[C::G];
-#pragma unroll
-    for (int g = 0; g < C::G; ++g) {
-        kf[g] = *reinterpret_cast<const u32x4_t*>(krow + 32 * g + 16 * hi);
-        vf[g] = *reinterpret_cast<const u32x4_t*>(vrow + 32 * g + 16 * hi);
-    }
-    f32x16_t dk[kHalfDT], dv[kHalfDT];
-#pragma unroll
-    for (int i = 0; i < kHalfDT; ++i) dk[i] = dv[i] = f32x16_t{};
-
-    // packed row rr of the sequence (rr < rend <= n g): token rr / g, head hk g + rr % g
-    const int hq0 = hk * p.g;
-    RowTile<kVD, kVQT> qt, ot;
-    float pl = 0.f, pd = 0.f;   // threads 0 .. 31: lse log2 e and delta of row tid of the tile in flight
-    const auto load_tile = [&](int t0) {
-        qt.load([&](int row) -> const char* {
-            const int rr = t0 + row;
-            if (rr >= rend) return nullptr;
-            return p.q + (((long long)sq.s + rr / p.g) * p.q_stride + (long long)(hq0 + rr % p.g) * kVD) * 2;
-        }, tid);
-        ot.load([&](int row) -> const char* {
-            const int rr = t0 + row;
-            if (rr >= rend) return nullptr;
-            return p.dout + (((long long)sq.s + rr / p.g) * p.Hq + hq0 + rr % p.g) * (long long)C::RB;
-        }, tid);
-        if (tid < kVQT) {
-            const int rr = t0 + tid;
-            pl = 0.f;
-            pd = 0.f;
-            if (rr < rend) {
-                const long long at = ((long long)sq.s + rr / p.g) * p.Hq + hq0 + rr % p.g;
-                pl = p.lse[at] * kLog2e;
-                pd = p.delta[at];
-            }
-        }
-    };
-    const int c0 = 128 * ch;   // the first column of this workgroup's half
-    if (ntiles > 0) load_tile(rbeg);
-    for (int t = 0; t < ntiles; ++t) {
-        const int t0 = rbeg + t * kVQT;
-        __syncthreads();
-        qt.store(Qs, C::PAT, tid);
-        ot.store(Os, C::PAT, tid);
-        if (tid < kVQT) {
-            Ls[tid] = pl;
-            Dl[tid] = pd;
-        }
-        __syncthreads();
-        if (t + 1 < ntiles) load_tile(t0 + kVQT);
-        // a wave skips the tiles whose rows see none of its keys: every position before its first key, or its last key outside every window
-        const int tpos_lo = coff + t0 / p.g, tpos_hi = coff + (min(t0 + kVQT, rend) - 1) / p.g;
-        if (wkey_lo >= L || (causal && tpos_hi < wkey_lo) || (p.window > 0 && tpos_lo - wkey_hi >= p.window)) continue;
-        // S[row][key] = Q.K^T, dP[row][key] = dO.V^T over the full width
-        f32x16_t s = f32x16_t{}, dp = f32x16_t{};
-#pragma unroll
-        for (int g = 0; g < C::G; ++g) {
-            s = mfma16<T>(lds_b128(Qs + l31 * C::PAT + 32 * g + 16 * hi), kf[g], s);
-            dp = mfma16<T>(lds_b128(Os + l31 * C::PAT + 32 * g + 16 * hi), vf[g], dp);
-        }
-        // P and dS (rows crow(r, hi) of the tile)
-        f32x16_t ds;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int qr = crow(r, hi);
-            const int rr = t0 + qr;
-            const bool vis = rr < rend && varlen_visible(coff + rr / p.g, kj, L, causal, p.window);
-            const float pr = vis ? fast_exp2(s[r] * p.c - Ls[qr]) : 0.f;
-            s[r] = pr;
-            ds[r] = pr * (dp[r] - Dl[qr]);
-        }
-        // dV^T[d][key] += dO^T.P, dK^T[d][key] += Q^T.dS over the half's columns
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-            const u32x4_t pb = pack_step<T>(s, st), db = pack_step<T>(ds, st);
-#pragma unroll
-            for (int dt = 0; dt < kHalfDT; ++dt) {
-                dv[dt] = mfma16<T>(lds_tr_step(Os, C::PAT, 16 * st, c0 + 32 * dt, lane), pb, dv[dt]);
-                dk[dt] = mfma16<T>(lds_tr_step(Qs, C::PAT, 16 * st, c0 + 32 * dt, lane), db, dk[dt]);
-            }
-        }
-    }
-    if (!live) return;
-    const long long at = (((long long)sk.s + kj) * p.Hkv + hk) * (long long)C::RB + c0 * 2;
-    store_row16<T, kHalfDT>(p.dk + at, dk, p.scale, hi);
-    store_row16<T, kHalfDT>(p.dv + at, dv, 1.f, hi);
+    varlen_d256_dkdv_body<T, false>(p, 0.f);
 }
 
 }  // namespace

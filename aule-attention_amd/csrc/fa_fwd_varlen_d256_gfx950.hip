@@ -22,99 +22,7 @@ namespace {
 
 template <class T>
 __global__ void __launch_bounds__(256, 1) fa_fwd_varlen_d256_kernel(const VarlenD256Params p) {
-    using C = CV256;
-    __shared__ __attribute__((aligned(16))) char Ks[kPK * C::PA];
-    __shared__ __attribute__((aligned(16))) char Vs[kPK * C::PT];
-
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int bid = (int)blockIdx.x;
-    const int units = p.Hkv * p.B;
-    const int rank = bid / units, unit = bid - rank * units;
-    const int hk = unit % p.Hkv, b = unit / p.Hkv;
-
-    const QueryBlock x = query_block(p, rank, b, hk, wave, l31);   // the sequence, clamped; this block of it; this lane's row
-    if (x.rows == 0) return;
-    const int ntiles = x.ntiles;
-
-    const char* qrow = p.q + (((long long)x.sq + x.tok) * p.q_stride + (long long)x.head * kVD) * 2;
-    u32x4_t qf[C::G];
-#pragma unroll
-    for (int g = 0; g < C::G; ++g) qf[g] = *reinterpret_cast<const u32x4_t*>(qrow + 32 * g + 16 * hi);
-
-    const float c = p.c;
-    f32x16_t o[C::DT];
-#pragma unroll
-    for (int i = 0; i < C::DT; ++i) o[i] = f32x16_t{};
-    float m = -__builtin_inff(), l = 0.f;
-
-    KeyTiles<kVD> kt(p, x, hk);
-    if (ntiles > 0) kt.load(x.kbeg, tid);
-    for (int t = 0; t < ntiles; ++t) {
-        const int k0 = x.kbeg + t * kPK;
-        __syncthreads();   // every wave is done with the previous tile
-        kt.store(Ks, C::PA, Vs, C::PT, tid);
-        __syncthreads();
-        if (t + 1 < ntiles) kt.load(k0 + kPK, tid);
-        if (x.skips(k0)) continue;
-        f32x16_t sc[2];
-        tile_scores<T, C::G>(sc, Ks, C::PA, qf, l31, hi);
-        __builtin_amdgcn_sched_barrier(0);
-        // scale to log2 units, mask, running max over the lane pair
-        float mx = -__builtin_inff();
-        if (x.sees_all(k0)) {
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) {
-                    const float y = sc[kk][rr] * c;
-                    sc[kk][rr] = y;
-                    mx = fmaxf(mx, y);
-                }
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) {
-                    const int j = k0 + 32 * kk + crow(rr, hi);
-                    const float y = x.visible(j) ? sc[kk][rr] * c : -__builtin_inff();
-                    sc[kk][rr] = y;
-                    mx = fmaxf(mx, y);
-                }
-        }
-        mx = fmaxf(mx, xhalf(mx));
-        const float mn = fmaxf(m, mx);
-        const float top = mn == -__builtin_inff() ? 0.f : mn;
-        const float alpha = fast_exp2(m - top);   // m = -inf: 0
-        m = mn;
-        l *= alpha;
-#pragma unroll
-        for (int i = 0; i < C::DT; ++i) o[i] *= alpha;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const float ex = fast_exp2(sc[kk][rr] - top);
-                sc[kk][rr] = ex;
-                l += ex;
-            }
-        // O^T[d][row] += V^T.P^T
-#pragma unroll
-        for (int st = 0; st < 4; ++st) {
-            const u32x4_t pb = pack_step<T>(sc[st >> 1], st & 1);
-#pragma unroll
-            for (int dt = 0; dt < C::DT; ++dt) o[dt] = mfma16<T>(lds_tr_step(Vs, C::PT, 16 * st, 32 * dt, lane), pb, o[dt]);
-            __builtin_amdgcn_sched_barrier(0);   // (the transposed reads of one step at a time: hoisted further they cost registers)
-        }
-    }
-    l += xhalf(l);
-    if (!x.live) return;
-    const long long orow = ((long long)x.sq + x.tok) * p.Hq + x.head;
-    store_row16<T, C::DT>(p.o + orow * (long long)C::RB, o, l > 0.f ? 1.f / l : 0.f, hi);
-    if (p.lse_out != nullptr && hi == 0) {
-        const float top = m == -__builtin_inff() ? 0.f : m;
-        p.lse_out[orow] = l > 0.f ? (top + fast_log2(l)) * kLn2 : -__builtin_inff();
-    }
+    varlen_d256_fwd_body<T, false>(p, 0.f);   // (the body: fa_varlen_d256.h)
 }
 
 }  // namespace

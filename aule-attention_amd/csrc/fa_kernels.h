@@ -541,6 +541,10 @@ long long varlen_d256_dkdv_grid(const VarlenArgs& a);   // 2 ceil(min(max_seqlen
 int launch_varlen_delta(const VarlenArgs& a, hipStream_t stream);      // delta = rowsum(dout * o) over all Tq rows, any D % 8 == 0
 int launch_varlen_d256_fwd(const VarlenArgs& a, hipStream_t stream);   // -1: unsupported arguments
 int launch_varlen_d256_bwd(const VarlenArgs& a, hipStream_t stream);   // delta, dQ, dK/dV on `stream`
+// ... and with logit soft-capping, s = softcap tanh(scale q.k / softcap) (fa_varlen_d256_softcap_gfx950.hip): `softcap`
+// finite and > 0, the grids and the workspace (delta) those of the two launches above.
+int launch_varlen_d256_softcap_fwd(const VarlenArgs& a, float softcap, hipStream_t stream);
+int launch_varlen_d256_softcap_bwd(const VarlenArgs& a, float softcap, hipStream_t stream);
 // The gradient of the sink logits (fa_bwd_sinks_gfx950.hip), after launch_varlen_bwd on the same stream: reads a.lse (the forward's, sinks
 // included), a.delta (that launch's workspace), a.sinks and a.cu_seqlens_q over the owned rows only; two launches, no atomics, a fixed
 // summation order; `partials` is varlen_dsinks_partial_bytes(a) bytes of workspace; exactly Hq floats of dsinks are written.

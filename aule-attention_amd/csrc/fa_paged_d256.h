@@ -48,5 +48,8 @@ struct PagedD256Plan {
 PagedD256Plan paged_d256_plan(const PagedD256Args& a, int force_nsplit = 0);
 // (`ws`: plan.ws_bytes bytes, 16-byte aligned, when plan.nsplit > 1)  -1: unsupported arguments
 int launch_paged_d256(const PagedD256Args& a, const PagedD256Plan& plan, void* ws, hipStream_t stream);
+// The same with logit soft-capping, s = softcap tanh(scale q.k / softcap) (fa_fwd_paged_d256_softcap_gfx950.hip):
+// `softcap` finite and > 0, the plan and the workspace those of the plain launch.
+int launch_paged_d256_softcap(const PagedD256Args& a, float softcap, const PagedD256Plan& plan, void* ws, hipStream_t stream);
 
 }  // namespace aule_hip

@@ -908,6 +908,115 @@ int32_t aule_attention_varlen_d256_backward_ex(const aule_varlen_bwd_desc* desc)
 /* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses. */
 uint64_t aule_attention_varlen_d256_backward_workspace_size(const aule_varlen_bwd_desc* desc);
 
+/* LOGIT SOFT-CAPPING at head_dim 256 (additive): the variable-length entries above and aule_attention_paged_d256_ex for the models  */
+/* that cap their attention logits (Gemma-2: softcap = 50).  For a query row i and its visible keys j:                                */
+/*     s_ij = softcap * tanh(scale * q_i.k_j / softcap)     P = softmax_j(s_ij)     out = P.V     lse_i = ln sum_j exp(s_ij)          */
+/* The mask is applied after the cap: an invisible key stays -inf, and a row without a key writes zeros and lse = -inf.  With an FP8 */
+/* cache k_scale multiplies q.k INSIDE the tanh (it is part of the key).  softcap is a model constant that travels by value: a       */
+/* finite float > 0; 0, a negative value, inf and NaN are refused with -3 (the uncapped twin is the call for "no cap").  Every other  */
+/* rule -- shapes, strides, clamps, causal modes, window, owned rows, workspaces, capture behaviour, answers before aule_init() -- is */
+/* EXACTLY the uncapped twin's: each descriptor repeats its twin field for field at the same offsets and appends softcap (padded to   */
+/* the struct's alignment), and is checked through that prefix; the size queries equal the twins'.  The kernels are new instances     */
+/* under their own names; the twins are untouched.  Backward: dS = P * (dP - delta) * (1 - tanh^2), delta as above.  */
+/* Not built: soft-capping for head_dim <= 128, for the dense aule_attention_forward_ex, with sinks, tree masks or the cascade.       */
+typedef struct aule_varlen_softcap_desc {
+    uint32_t struct_size;      /* = sizeof(aule_varlen_softcap_desc) = 152 */
+    int32_t dtype;
+    uint32_t batch;
+    uint32_t heads_q, heads_kv, head_dim;   /* head_dim 256 */
+    uint32_t total_q;
+    uint32_t total_k;
+    uint32_t max_seqlen_q;
+    uint32_t max_seqlen_k;
+    float scale;
+    int32_t causal;
+    int32_t window_size;
+    int32_t device;
+    int64_t q_token_stride;
+    int64_t k_token_stride;
+    int64_t v_token_stride;
+    void* stream;              /* offset 80 */
+    const void* q;
+    const void* k;
+    const void* v;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k;   /* offset 120 */
+    void* out;                 /* offset 128 */
+    float* lse;                /* offset 136; optional (NULL to skip) */
+    float softcap;             /* offset 144; finite, > 0 */
+    uint32_t reserved;         /* offset 148; padding, not read */
+} aule_varlen_softcap_desc;
+typedef struct aule_varlen_softcap_bwd_desc {
+    uint32_t struct_size;      /* = sizeof(aule_varlen_softcap_bwd_desc) = 200 */
+    int32_t dtype;
+    uint32_t batch;
+    uint32_t heads_q, heads_kv, head_dim;
+    uint32_t total_q;
+    uint32_t total_k;
+    uint32_t max_seqlen_q;
+    uint32_t max_seqlen_k;
+    float scale;
+    int32_t causal;
+    int32_t window_size;
+    int32_t device;
+    int64_t q_token_stride;
+    int64_t k_token_stride;
+    int64_t v_token_stride;
+    void* stream;              /* offset 80 */
+    const void* q;
+    const void* k;
+    const void* v;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k;   /* offset 120 */
+    const void* out;           /* offset 128; the capped forward's out */
+    const float* lse;          /* offset 136; the capped forward's lse (required) */
+    const void* dout;          /* offset 144 */
+    void* dq;                  /* offset 152 */
+    void* dk;                  /* offset 160 */
+    void* dv;                  /* offset 168 */
+    void* workspace;           /* offset 176; optional, size from aule_attention_varlen_d256_softcap_backward_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 184 */
+    float softcap;             /* offset 192; the forward's */
+    uint32_t reserved;         /* offset 196; padding, not read */
+} aule_varlen_softcap_bwd_desc;
+typedef struct aule_paged_d256_softcap_desc {
+    uint32_t struct_size;      /* = sizeof(aule_paged_d256_softcap_desc) = 176 */
+    int32_t dtype;
+    int32_t cache_dtype;       /* offset 8 */
+    uint32_t batch;            /* offset 12 */
+    uint32_t heads_q, heads_kv, head_dim;
+    uint32_t block_size;       /* offset 28 */
+    uint32_t max_blocks;
+    uint32_t total_tokens;     /* offset 36 */
+    uint32_t max_seqlen_q;
+    float scale;               /* offset 44 */
+    int32_t window_size;
+    int32_t device;
+    int64_t q_token_stride;    /* offset 56 */
+    void* stream;              /* offset 64 */
+    const void* q;
+    const void* k_cache;
+    const void* v_cache;
+    const int32_t* block_tables;   /* offset 96 */
+    const int32_t* context_lens;
+    const int32_t* cu_seqlens_q;   /* offset 112; NULL: plain decode */
+    void* out;                 /* offset 120 */
+    float* lse;                /* offset 128; optional */
+    const float* k_scale;      /* offset 136 */
+    const float* v_scale;      /* offset 144 */
+    void* workspace;           /* offset 152; optional, size from aule_attention_paged_d256_softcap_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 160 */
+    float softcap;             /* offset 168; finite, > 0 */
+    uint32_t reserved;         /* offset 172; padding, not read */
+} aule_paged_d256_softcap_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_varlen_d256_softcap_forward_ex(const aule_varlen_softcap_desc* desc);
+int32_t aule_attention_varlen_d256_softcap_backward_ex(const aule_varlen_softcap_bwd_desc* desc);
+int32_t aule_attention_paged_d256_softcap_ex(const aule_paged_d256_softcap_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
+uint64_t aule_attention_varlen_d256_softcap_backward_workspace_size(const aule_varlen_softcap_bwd_desc* desc);
+uint64_t aule_attention_paged_d256_softcap_workspace_size(const aule_paged_d256_softcap_desc* desc);
+
 /* ATTENTION SINKS (additive): per-head sink logits for the variable-length, paged-prefill and paged-query entries above -- the    */
 /* models whose heads each carry a learned logit that joins the softmax denominator and contributes no value (gpt-oss and its      */
 /* derivatives).  sinks is [heads_q] fp32 on the DEVICE: a raw logit, multiplied by neither scale nor k_scale; the kernels read it   */
