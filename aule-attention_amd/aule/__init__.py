@@ -455,7 +455,11 @@ def flash_attention_mla_sparse(q, kv_cache, indices, scale=None, return_lse=Fals
                  (None = 1.0, a float, or a 0-d / [1] tensor that stays on the device) by flash_attention_mla_paged_fp8's rule;
                  a scale with a 16-bit cache is a ValueError.  The cache is addressed as a flat array of S = num_blocks *
                  block_size rows ("slots"), so a contiguous [L, 576] latent is the cache latent.view(L, 1, 576): sparse
-                 prefill over an un-paged latent
+                 prefill over an un-paged latent.  Or torch.uint8 [num_blocks, block_size, 656] (or [..., 1, 656]): the
+                 per-128-scaled FP8 rows of DeepSeek-V3.2's serving kernels (512 e4m3fn codes | 4 fp32 scales | 64 bf16 rotary
+                 elements; quantize_mla_cache_fp8_ds, mla_kv_append).  Then q is bf16 and kv_scale None, keys are dequantised
+                 to bf16 on their way into LDS, and the call equals the bf16 call over dequantize_mla_cache_fp8_ds(kv_cache)
+                 bit for bit; a uint8 cache of another width is a ValueError
         indices  [T, topk] (or [T, 1, topk]) int32, contiguous, on q's device, 1 <= topk <= 65536: indices[t, i] is a slot,
                  block * block_size + offset -- mla_kv_append's slot_mapping; from logical positions,
                  paged_slot_mapping(...).to(torch.int32).  Any other integer dtype is a ValueError (nothing is converted
@@ -564,7 +568,9 @@ def mla_kv_append(c_kv, k_pe, kv_cache, slot_mapping, kv_scale=None, cos=None, s
           8 elements: slices of the fused down-projection are read in place);
         kv_cache [num_blocks, block_size, 576] (or [..., 1, 576]) contiguous, c_kv's dtype (a copy of the bits) or
           torch.float8_e4m3fn (code = cast(clamp(x / kv_scale, -448, 448)) -- quantize_mla_cache_fp8 with a given scale, bit
-          for bit; kv_scale None (1.0), a float, or a 0-d / [1] tensor that stays on the device);
+          for bit; kv_scale None (1.0), a float, or a 0-d / [1] tensor that stays on the device); or torch.uint8
+          [num_blocks, block_size, 656] (or [..., 1, 656]), the per-128-scaled FP8 rows: bf16 inputs, kv_scale None, the row
+          is quantize_mla_cache_fp8_ds([c_kv | rope(k_pe)]) byte for byte;
         slot_mapping [T] integer = block * block_size + offset (see paged_slot_mapping); negative or past the cache: the
           token is skipped entirely; two tokens with the same slot in one call: which one wins is unspecified;
         cos, sin [table_len, 32], positions [T] (all or none): rotate k_pe by table row positions[t] first, rope_layout
@@ -587,6 +593,24 @@ def quantize_mla_cache_fp8(kv_cache):
     works on CPU tensors."""
     from ._torch import quantize_mla_cache_fp8 as impl
     return impl(kv_cache)
+
+
+def quantize_mla_cache_fp8_ds(kv_cache):
+    """A latent cache [..., 576] as the per-128-scaled FP8 layout of DeepSeek-V3.2's serving kernels, uint8 [..., 656] per
+    row: 512 e4m3fn codes | 4 fp32 scales (one per 128 columns) | the 64 rotary elements as bf16.  Per group: amax = max |x|,
+    scale = 2^max(ceil(log2(amax / 448)), -126) (a power of two; 1 for a group of zeros), code = e4m3fn(clamp(x / scale,
+    -448, 448)) -- what mla_kv_append writes into such a cache, byte for byte.  Plain torch ops; works on CPU tensors."""
+    from ._torch import quantize_mla_cache_fp8_ds as impl
+    return impl(kv_cache)
+
+
+def dequantize_mla_cache_fp8_ds(cache, dtype=None):
+    """The keys flash_attention_mla_sparse multiplies for a uint8 [..., 656] cache, as [..., 576]: bf16(float(code) * its group's
+    scale) for the first 512 columns, then the stored bf16; dtype None is bf16, another dtype is converted from that.  Plain
+    torch ops; works on CPU tensors."""
+    import torch
+    from ._torch import dequantize_mla_cache_fp8_ds as impl
+    return impl(cache, torch.bfloat16 if dtype is None else dtype)
 
 
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=True, scale=None,
@@ -1098,7 +1122,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "flash_attention_varlen", "flash_attention_varlen_d256", "flash_attention_varlen_d256_softcap", "flash_attention_paged_d256_softcap", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "quantize_mla_cache_fp8_ds", "dequantize_mla_cache_fp8_ds", "flash_attention_varlen", "flash_attention_varlen_d256", "flash_attention_varlen_d256_softcap", "flash_attention_paged_d256_softcap", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

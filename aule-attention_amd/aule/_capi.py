@@ -237,6 +237,11 @@ class MlaSparseDesc(ctypes.Structure):
     ]
 
 
+class MlaSparseDsDesc(ctypes.Structure):
+    """struct aule_mla_sparse_ds_desc (include/aule.h): MlaSparseDesc without kv_scale, over the cache of 656-byte rows."""
+    _fields_ = [("reserved", t) if n == "cache_dtype" else (n, t) for n, t in MlaSparseDesc._fields_ if n != "kv_scale"]
+
+
 class MlaIndexerLogitsDesc(ctypes.Structure):
     """struct aule_mla_indexer_logits_desc (include/aule.h): the index logits of the sparse MLA's indexer, both cache kinds."""
     _fields_ = [
@@ -317,6 +322,11 @@ class MlaKvAppendDesc(ctypes.Structure):
         ("sin", ctypes.c_void_p),
         ("positions", ctypes.c_void_p),
     ]
+
+
+class MlaKvAppendDsDesc(ctypes.Structure):
+    """struct aule_mla_kv_append_ds_desc (include/aule.h): MlaKvAppendDesc without kv_scale, into the cache of 656-byte rows."""
+    _fields_ = [("reserved", t) if n == "cache_dtype" else (n, t) for n, t in MlaKvAppendDesc._fields_ if n != "kv_scale"]
 
 
 class VarlenDesc(ctypes.Structure):
@@ -636,6 +646,9 @@ SIGNATURES = [
     ("aule_attention_mla_paged_tree_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaPagedTreeDesc)]),
     ("aule_attention_mla_sparse_ex", _I32, [ctypes.POINTER(MlaSparseDesc)]),
     ("aule_attention_mla_sparse_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaSparseDesc)]),
+    ("aule_attention_mla_sparse_ds_ex", _I32, [ctypes.POINTER(MlaSparseDsDesc)]),
+    ("aule_attention_mla_sparse_ds_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaSparseDsDesc)]),
+    ("aule_mla_kv_append_ds_ex", _I32, [ctypes.POINTER(MlaKvAppendDsDesc)]),
     ("aule_mla_indexer_logits_ex", _I32, [ctypes.POINTER(MlaIndexerLogitsDesc)]),
     ("aule_mla_indexer_topk_ex", _I32, [ctypes.POINTER(MlaIndexerTopkDesc)]),
     ("aule_mla_kv_append_ex", _I32, [ctypes.POINTER(MlaKvAppendDesc)]),
@@ -677,6 +690,7 @@ SIGNATURES = [
     ("aule_hip_debug_mla_plan", _I32, [ctypes.POINTER(MlaPagedDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_sparse_plan", _I32, [ctypes.POINTER(MlaSparseDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_sparse_launch_nsplit", _I32, [ctypes.POINTER(MlaSparseDesc), _I32]),
+    ("aule_hip_debug_mla_sparse_ds_plan", _I32, [ctypes.POINTER(MlaSparseDsDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_paged_d256_plan", _I32, [ctypes.POINTER(PagedD256Desc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_paged_d256_launch_nsplit", _I32, [ctypes.POINTER(PagedD256Desc), _I32]),
     ("aule_hip_debug_mla_indexer_plan", _I32, [ctypes.POINTER(MlaIndexerLogitsDesc), ctypes.POINTER(_I32), _I32]),

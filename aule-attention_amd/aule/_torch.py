@@ -1608,6 +1608,55 @@ def _mla_paged(fp8, q, kv_cache, block_tables, context_lens, cu_seqlens_q, max_s
 
 
 MLA_SPARSE_MAX_TOPK = 65536
+MLA_DS_ROW = 656   # bytes of a row of the per-128-scaled FP8 latent cache: 512 codes + 4 fp32 scales + 64 bf16 rotary elements
+
+
+def _ds_cache(kv_cache, kv_scale, what, x):
+    """A uint8 latent cache as its reader and its writer take it: [num_blocks, block_size, 656] (a [.., 1, 656] cache is read as that),
+    no kv_scale (the scales are in the rows) and bf16 on the other side (`what`: the name of `x` for the message)."""
+    if kv_cache.dim() == 4 and kv_cache.shape[2] == 1:
+        kv_cache = kv_cache[:, :, 0]
+    if kv_cache.dim() != 3 or kv_cache.shape[-1] != MLA_DS_ROW:
+        raise ValueError(f"a uint8 latent cache must be [num_blocks, block_size, 656] (or [num_blocks, block_size, 1, 656]): rows of 512 "
+                         f"e4m3fn codes, 4 fp32 scales and 64 bf16 rotary elements, got {tuple(kv_cache.shape)}")
+    if kv_scale is not None:
+        raise ValueError("kv_scale must be None with a uint8 [.., 656] cache: its scales are in its rows")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"{what} must be bf16 with a uint8 [.., 656] cache (its rotary part is bf16 and is not converted), got {x.dtype}")
+    return kv_cache
+
+
+def quantize_mla_cache_fp8_ds(kv_cache):
+    """A latent cache [..., 576] (any float dtype) as rows of the per-128-scaled FP8 layout, uint8 [..., 656], by the rule of
+    csrc/mla_kv_append_ds_gfx950.hip: per group of 128 of the first 512 columns amax = max |x| in fp32, scale =
+    2^max(ceil(log2(amax / 448)), -126) (1 for a group of zeros), code = e4m3fn(clamp(x / scale, -448, 448)); then the 4 scales as
+    fp32 and columns 512 .. 575 as bf16.  Plain torch ops; works on CPU tensors."""
+    if not torch.is_tensor(kv_cache) or kv_cache.dim() < 1 or kv_cache.shape[-1] != 576 or not kv_cache.dtype.is_floating_point:
+        raise ValueError("expected a floating-point latent cache [..., 576]")
+    lead = kv_cache.shape[:-1]
+    x = kv_cache[..., :512].float().reshape(*lead, 4, 128)
+    amax = x.abs().amax(dim=-1)
+    # amax = m * 2^e with 0.5 <= m < 1, and 448 = 0.875 * 2^9: ceil(log2(amax / 448)) = e - 9, + 1 when m > 0.875
+    m, e = torch.frexp(amax)
+    k = (e - 9 + (m > 0.875).to(e.dtype)).clamp_(min=-126)
+    scale = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), k), torch.ones_like(amax))
+    codes = (x / scale[..., None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).reshape(*lead, 512)
+    rope = kv_cache[..., 512:].to(torch.bfloat16).contiguous()
+    return torch.cat([codes.view(torch.uint8), scale.contiguous().view(torch.uint8), rope.view(torch.uint8)], dim=-1)
+
+
+def dequantize_mla_cache_fp8_ds(cache, dtype=torch.bfloat16):
+    """The keys flash_attention_mla_sparse works with for a uint8 [..., 656] cache, as [..., 576] of `dtype`: bf16(float(code) * its
+    group's scale) for the first 512 columns (rounded to nearest even, the kernel's rule), then the 64 stored bf16; converted from
+    bf16 when another dtype is asked for.  Plain torch ops; works on CPU tensors."""
+    if not torch.is_tensor(cache) or cache.dtype != torch.uint8 or cache.dim() < 1 or cache.shape[-1] != MLA_DS_ROW:
+        raise ValueError("expected a uint8 cache [..., 656]")
+    lead = cache.shape[:-1]
+    codes = cache[..., :512].contiguous().view(torch.float8_e4m3fn).float().reshape(*lead, 4, 128)
+    scale = cache[..., 512:528].contiguous().view(torch.float32)
+    latent = (codes * scale[..., None]).reshape(*lead, 512).to(torch.bfloat16)
+    rope = cache[..., 528:].contiguous().view(torch.bfloat16)
+    return torch.cat([latent, rope], dim=-1).to(dtype)
 
 
 def mla_sparse(q, kv_cache, indices, scale=None, return_lse=False, kv_scale=None):
@@ -1616,12 +1665,16 @@ def mla_sparse(q, kv_cache, indices, scale=None, return_lse=False, kv_scale=None
     contract (aule.flash_attention_mla_sparse documents the arguments).  One launch (plus the combine when the list is split), no
     device->host copy, no synchronisation.  All argument errors are ValueErrors raised before the device is touched; CPU tensors
     that pass them are an AuleError."""
-    kv_cache = _latent_shapes(q, kv_cache)
+    ds = torch.is_tensor(kv_cache) and kv_cache.dtype == torch.uint8   # the cache of 656-byte rows: aule_attention_mla_sparse_ds_ex
+    kv_cache = _ds_cache(kv_cache, kv_scale, "q", q) if ds else _latent_shapes(q, kv_cache)
+    if ds and (q.dim() != 3 or q.shape[-1] != 576):
+        raise ValueError(f"expected q [T,Hq,576] with a uint8 [.., 656] cache, got {tuple(q.shape)}")
     if torch.is_tensor(indices) and indices.dim() == 3 and indices.shape[1] == 1:
         indices = indices[:, 0]
     T, Hq, _ = q.shape
-    fp8 = kv_cache.dtype != q.dtype
-    _latent_cache_kind("q", q.dtype, kv_cache, fp8, kv_scale, "a 16-bit cache has q's dtype")
+    fp8 = not ds and kv_cache.dtype != q.dtype
+    if not ds:
+        _latent_cache_kind("q", q.dtype, kv_cache, fp8, kv_scale, "a 16-bit cache has q's dtype")
     if Hq == 0:
         raise ValueError("q has no heads")
     if not torch.is_tensor(indices) or indices.dim() != 2 or indices.shape[0] != T:
@@ -1651,10 +1704,11 @@ def mla_sparse(q, kv_cache, indices, scale=None, return_lse=False, kv_scale=None
     if T == 0:
         return result
     lib = _capi.get_lib()
-    d = _capi.MlaSparseDesc()
+    d = _capi.MlaSparseDsDesc() if ds else _capi.MlaSparseDesc()
     d.struct_size = ctypes.sizeof(d)
     d.dtype = _DTYPES[q.dtype]
-    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    if not ds:
+        d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
     d.heads_q, d.num_blocks, d.block_size = Hq, kv_cache.shape[0], kv_cache.shape[1]
     d.total_tokens, d.topk, d.q_token_stride = T, topk, q_stride
     d.scale = _abi_scale(1.0 / math.sqrt(576) if scale is None else scale)
@@ -1666,8 +1720,9 @@ def mla_sparse(q, kv_cache, indices, scale=None, return_lse=False, kv_scale=None
     if fp8:
         held.append(_fp8_scale(kv_scale, 1, q.device, "kv_scale"))
         d.kv_scale = held[-1].data_ptr()
-    held.append(_attach_workspace(d, lib.aule_attention_mla_sparse_workspace_size, q.device))   # held until the launch is queued
-    _capi.check(lib.aule_attention_mla_sparse_ex(ctypes.byref(d)), "aule_attention_mla_sparse_ex")
+    entry = "aule_attention_mla_sparse_ds" if ds else "aule_attention_mla_sparse"
+    held.append(_attach_workspace(d, getattr(lib, entry + "_workspace_size"), q.device))   # held until the launch is queued
+    _capi.check(getattr(lib, entry + "_ex")(ctypes.byref(d)), entry + "_ex")
     return result
 
 
@@ -1870,19 +1925,23 @@ def mla_kv_append(c_kv, k_pe, kv_cache, slot_mapping, kv_scale=None, cos=None, s
     graph.  All argument errors are ValueErrors raised before the device is touched; CPU tensors are an AuleError."""
     if k_pe.dim() == 3 and k_pe.shape[1] == 1:
         k_pe = k_pe[:, 0]
+    ds = kv_cache.dtype == torch.uint8   # the cache of 656-byte rows: aule_mla_kv_append_ds_ex
+    if ds:
+        kv_cache = _ds_cache(kv_cache, kv_scale, "c_kv and k_pe", c_kv)
     if kv_cache.dim() == 4 and kv_cache.shape[2] == 1:
         kv_cache = kv_cache[:, :, 0]
     if c_kv.dim() != 2 or k_pe.dim() != 2 or kv_cache.dim() != 3:
         raise ValueError("expected c_kv [T,512], k_pe [T,64] (or [T,1,64]) and kv_cache [num_blocks, block_size, 576] (or [num_blocks, block_size, 1, 576])")
-    if c_kv.shape[1] != 512 or k_pe.shape[1] != 64 or kv_cache.shape[2] != 576:
+    if c_kv.shape[1] != 512 or k_pe.shape[1] != 64 or kv_cache.shape[2] != (MLA_DS_ROW if ds else 576):
         raise ValueError(f"the latent row is 512 + 64 = 576 wide: c_kv={c_kv.shape[1]}, k_pe={k_pe.shape[1]}, cache={kv_cache.shape[2]}")
     T = c_kv.shape[0]
     if k_pe.shape[0] != T:
         raise ValueError(f"c_kv has {T} tokens, k_pe {k_pe.shape[0]}")
     if k_pe.dtype != c_kv.dtype:
         raise ValueError(f"c_kv and k_pe must share one of fp16 / bf16, got {c_kv.dtype} and {k_pe.dtype}")
-    fp8 = kv_cache.dtype != c_kv.dtype
-    _latent_cache_kind("c_kv and k_pe", c_kv.dtype, kv_cache, fp8, kv_scale, "a 16-bit cache has c_kv's dtype")
+    fp8 = not ds and kv_cache.dtype != c_kv.dtype
+    if not ds:
+        _latent_cache_kind("c_kv and k_pe", c_kv.dtype, kv_cache, fp8, kv_scale, "a 16-bit cache has c_kv's dtype")
     if rope_layout not in _ROPE_LAYOUTS:
         raise ValueError(f"unknown rope_layout {rope_layout!r} ('half' or 'interleaved')")
     if not kv_cache.is_contiguous():
@@ -1917,10 +1976,11 @@ def mla_kv_append(c_kv, k_pe, kv_cache, slot_mapping, kv_scale=None, cos=None, s
     lib = _capi.get_lib()
     dev = c_kv.device
     slots = slot_mapping.to(device=dev, dtype=torch.int64).contiguous()
-    d = _capi.MlaKvAppendDesc()
+    d = _capi.MlaKvAppendDsDesc() if ds else _capi.MlaKvAppendDesc()
     d.struct_size = ctypes.sizeof(d)
     d.dtype = _DTYPES[c_kv.dtype]
-    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    if not ds:
+        d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
     d.rope_layout = _ROPE_LAYOUTS[rope_layout]
     d.total_tokens, d.num_blocks, d.block_size = T, num_blocks, block_size
     # (a stride of a dimension of extent 1 is never used: torch reports anything there)
@@ -1939,7 +1999,8 @@ def mla_kv_append(c_kv, k_pe, kv_cache, slot_mapping, kv_scale=None, cos=None, s
         d.table_len, d.table_pitch = c.shape[0], c.stride(0)
         d.cos, d.sin, d.positions = c.data_ptr(), s_.data_ptr(), pos.data_ptr()
         held += [c, s_, pos]
-    _capi.check(lib.aule_mla_kv_append_ex(ctypes.byref(d)), "aule_mla_kv_append_ex")
+    entry = "aule_mla_kv_append_ds_ex" if ds else "aule_mla_kv_append_ex"
+    _capi.check(getattr(lib, entry)(ctypes.byref(d)), entry)
     return None
 
 

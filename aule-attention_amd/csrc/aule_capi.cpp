@@ -131,6 +131,16 @@ static_assert(sizeof(aule_mla_sparse_desc) == 120 && offsetof(aule_mla_sparse_de
                   offsetof(aule_mla_sparse_desc, kv_scale) == 80 && offsetof(aule_mla_sparse_desc, out) == 88 && offsetof(aule_mla_sparse_desc, lse) == 96 &&
                   offsetof(aule_mla_sparse_desc, workspace) == 104 && offsetof(aule_mla_sparse_desc, workspace_bytes) == 112,
               "aule_mla_sparse_desc layout is part of the ABI");
+static_assert(sizeof(aule_mla_sparse_ds_desc) == 112 && offsetof(aule_mla_sparse_ds_desc, dtype) == 4 && offsetof(aule_mla_sparse_ds_desc, reserved) == 8 &&
+                  offsetof(aule_mla_sparse_ds_desc, heads_q) == 12 && offsetof(aule_mla_sparse_ds_desc, num_blocks) == 16 &&
+                  offsetof(aule_mla_sparse_ds_desc, block_size) == 20 && offsetof(aule_mla_sparse_ds_desc, total_tokens) == 24 &&
+                  offsetof(aule_mla_sparse_ds_desc, topk) == 28 && offsetof(aule_mla_sparse_ds_desc, scale) == 32 &&
+                  offsetof(aule_mla_sparse_ds_desc, device) == 36 && offsetof(aule_mla_sparse_ds_desc, q_token_stride) == 40 &&
+                  offsetof(aule_mla_sparse_ds_desc, stream) == 48 && offsetof(aule_mla_sparse_ds_desc, q) == 56 &&
+                  offsetof(aule_mla_sparse_ds_desc, kv_cache) == 64 && offsetof(aule_mla_sparse_ds_desc, indices) == 72 &&
+                  offsetof(aule_mla_sparse_ds_desc, out) == 80 && offsetof(aule_mla_sparse_ds_desc, lse) == 88 &&
+                  offsetof(aule_mla_sparse_ds_desc, workspace) == 96 && offsetof(aule_mla_sparse_ds_desc, workspace_bytes) == 104,
+              "aule_mla_sparse_ds_desc layout is part of the ABI");
 static_assert(sizeof(aule_mla_indexer_logits_desc) == 136 && offsetof(aule_mla_indexer_logits_desc, dtype) == 4 &&
                   offsetof(aule_mla_indexer_logits_desc, cache_dtype) == 8 && offsetof(aule_mla_indexer_logits_desc, heads) == 12 &&
                   offsetof(aule_mla_indexer_logits_desc, head_dim) == 16 && offsetof(aule_mla_indexer_logits_desc, batch) == 20 &&
@@ -166,6 +176,17 @@ static_assert(sizeof(aule_mla_kv_append_desc) == 128 && offsetof(aule_mla_kv_app
                   offsetof(aule_mla_kv_append_desc, cos) == 104 && offsetof(aule_mla_kv_append_desc, sin) == 112 &&
                   offsetof(aule_mla_kv_append_desc, positions) == 120,
               "aule_mla_kv_append_desc layout is part of the ABI");
+static_assert(sizeof(aule_mla_kv_append_ds_desc) == 120 && offsetof(aule_mla_kv_append_ds_desc, dtype) == 4 &&
+                  offsetof(aule_mla_kv_append_ds_desc, reserved) == 8 && offsetof(aule_mla_kv_append_ds_desc, rope_layout) == 12 &&
+                  offsetof(aule_mla_kv_append_ds_desc, total_tokens) == 16 && offsetof(aule_mla_kv_append_ds_desc, num_blocks) == 20 &&
+                  offsetof(aule_mla_kv_append_ds_desc, block_size) == 24 && offsetof(aule_mla_kv_append_ds_desc, table_len) == 28 &&
+                  offsetof(aule_mla_kv_append_ds_desc, table_pitch) == 32 && offsetof(aule_mla_kv_append_ds_desc, device) == 36 &&
+                  offsetof(aule_mla_kv_append_ds_desc, c_kv_token_stride) == 40 && offsetof(aule_mla_kv_append_ds_desc, k_pe_token_stride) == 48 &&
+                  offsetof(aule_mla_kv_append_ds_desc, stream) == 56 && offsetof(aule_mla_kv_append_ds_desc, c_kv) == 64 &&
+                  offsetof(aule_mla_kv_append_ds_desc, k_pe) == 72 && offsetof(aule_mla_kv_append_ds_desc, kv_cache) == 80 &&
+                  offsetof(aule_mla_kv_append_ds_desc, slot_mapping) == 88 && offsetof(aule_mla_kv_append_ds_desc, cos) == 96 &&
+                  offsetof(aule_mla_kv_append_ds_desc, sin) == 104 && offsetof(aule_mla_kv_append_ds_desc, positions) == 112,
+              "aule_mla_kv_append_ds_desc layout is part of the ABI");
 #define AULE_SAME_OFFSET(field) (offsetof(aule_paged_cascade_desc, field) == offsetof(aule_paged_prefill_desc, field))
 static_assert(AULE_SAME_OFFSET(struct_size) && AULE_SAME_OFFSET(dtype) && AULE_SAME_OFFSET(cache_dtype) && AULE_SAME_OFFSET(batch) && AULE_SAME_OFFSET(heads_q) &&
                   AULE_SAME_OFFSET(heads_kv) && AULE_SAME_OFFSET(head_dim) && AULE_SAME_OFFSET(block_size) && AULE_SAME_OFFSET(max_blocks) &&
@@ -1771,18 +1792,8 @@ static const char* mla_sparse_desc_error(const aule_mla_sparse_desc* d, bool lau
     return nullptr;
 }
 
-// (the launch entry, and with force_nsplit > 0 the bench's debug launch)
-static int32_t mla_sparse_launch(const aule_mla_sparse_desc* d, int force_nsplit) {
-    const char* what = "Sparse MLA attention";
-    std::lock_guard<std::mutex> lk(g_mu);
-    Reason text;
-    if (const char* why = mla_sparse_desc_error(d, true, text, force_nsplit)) {
-        set_error("%s failed: %s", what, why);
-        return -3;
-    }
-    if (mla_sparse_nothing_to_do(d)) return 0;
-    if (!initialised()) return -1;
-    aule_hip::MlaSparseArgs a;
+// (`d` passed mla_sparse_desc_error)
+static void fill_mla_sparse_args(const aule_mla_sparse_desc* d, aule_hip::MlaSparseArgs& a) {
     a.q = d->q; a.kv_cache = d->kv_cache; a.out = d->out; a.lse = d->lse;
     a.indices = d->indices;
     a.T = (int)d->total_tokens; a.Hq = (int)d->heads_q;
@@ -1796,6 +1807,21 @@ static int32_t mla_sparse_launch(const aule_mla_sparse_desc* d, int force_nsplit
         a.cache_kind = aule_hip::kCacheFp8E4M3;
         a.kv_scale = d->kv_scale;
     }
+}
+
+// (the launch entry, and with force_nsplit > 0 the bench's debug launch)
+static int32_t mla_sparse_launch(const aule_mla_sparse_desc* d, int force_nsplit) {
+    const char* what = "Sparse MLA attention";
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_sparse_desc_error(d, true, text, force_nsplit)) {
+        set_error("%s failed: %s", what, why);
+        return -3;
+    }
+    if (mla_sparse_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaSparseArgs a;
+    fill_mla_sparse_args(d, a);
     const aule_hip::MlaPlan plan = mla_sparse_plan_of(d, force_nsplit);
     return mla_launch_tail(d, plan, what, [&](void* ws, hipStream_t stream) { return aule_hip::launch_mla_sparse(a, plan, ws, stream); });
 }
@@ -1803,6 +1829,44 @@ static int32_t mla_sparse_launch(const aule_mla_sparse_desc* d, int force_nsplit
 int32_t aule_attention_mla_sparse_ex(const aule_mla_sparse_desc* d) {
     RoctxRange range("aule.mla_sparse");
     return mla_sparse_launch(d, 0);
+}
+
+// The sparse MLA over the per-128-scaled FP8 cache.  Its descriptor is the twin's without kv_scale, so its rules are the twin's: the
+// descriptor is read as the twin with a 16-bit cache kind (the kind of the image the kernel multiplies) and no scale, by the one
+// checker above, after the two rules of its own.  `twin`: filled whenever `d` has its size.
+static const char* mla_sparse_ds_desc_error(const aule_mla_sparse_ds_desc* d, bool launch, Reason& why, aule_mla_sparse_desc& twin) {
+    if (d == nullptr || d->struct_size != sizeof(aule_mla_sparse_ds_desc)) return kBadDescriptor;
+    twin = aule_mla_sparse_desc{};
+    twin.struct_size = sizeof(twin);
+    twin.dtype = d->dtype; twin.cache_dtype = AULE_KV_CACHE_SAME;
+    twin.heads_q = d->heads_q; twin.num_blocks = d->num_blocks; twin.block_size = d->block_size;
+    twin.total_tokens = d->total_tokens; twin.topk = d->topk;
+    twin.scale = d->scale; twin.device = d->device; twin.q_token_stride = d->q_token_stride; twin.stream = d->stream;
+    twin.q = d->q; twin.kv_cache = d->kv_cache; twin.indices = d->indices; twin.kv_scale = nullptr;
+    twin.out = d->out; twin.lse = d->lse; twin.workspace = d->workspace; twin.workspace_bytes = d->workspace_bytes;
+    if (d->dtype != AULE_DTYPE_BF16)
+        return reasonf(why, "dtype %d (of q / out) must be bf16: the rotary part of a 656-byte cache row is bf16 and is multiplied as stored", d->dtype);
+    if (d->reserved != 0) return reasonf(why, "reserved (%d) must be 0", d->reserved);
+    return mla_sparse_desc_error(&twin, launch, why);
+}
+
+int32_t aule_attention_mla_sparse_ds_ex(const aule_mla_sparse_ds_desc* d) {
+    RoctxRange range("aule.mla_sparse_ds");
+    const char* what = "Sparse MLA attention (656-byte rows)";
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    aule_mla_sparse_desc twin;
+    if (const char* why = mla_sparse_ds_desc_error(d, true, text, twin)) {
+        set_error("%s failed: %s", what, why);
+        return -3;
+    }
+    if (mla_sparse_nothing_to_do(&twin)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaSparseArgs a;
+    fill_mla_sparse_args(&twin, a);
+    a.ds_rows = true;
+    const aule_hip::MlaPlan plan = mla_sparse_plan_of(&twin);
+    return mla_launch_tail(&twin, plan, what, [&](void* ws, hipStream_t stream) { return aule_hip::launch_mla_sparse(a, plan, ws, stream); });
 }
 
 // The paged attention at head_dim 256: aule_paged_prefill_desc's fields and shared rules, a head_dim and an offsets rule of its own (a
@@ -2672,17 +2736,8 @@ static const char* mla_kv_append_error(const aule_mla_kv_append_desc* d, Reason&
     return nullptr;
 }
 
-int32_t aule_mla_kv_append_ex(const aule_mla_kv_append_desc* d) {
-    RoctxRange range("aule.mla_kv_append");
-    std::lock_guard<std::mutex> lk(g_mu);
-    Reason text;
-    if (const char* why = mla_kv_append_error(d, text)) {
-        set_error("MLA KV append failed: %s", why);
-        return -3;
-    }
-    if (mla_kv_append_nothing_to_do(d)) return 0;
-    if (!initialised()) return -1;
-    aule_hip::MlaKvAppendArgs a;
+// (`d` passed mla_kv_append_error)
+static void fill_mla_kv_append_args(const aule_mla_kv_append_desc* d, aule_hip::MlaKvAppendArgs& a) {
     a.c_kv = d->c_kv; a.k_pe = d->k_pe; a.kv_cache = d->kv_cache;
     a.slot_mapping = reinterpret_cast<const long long*>(d->slot_mapping);
     a.T = (int)d->total_tokens;
@@ -2696,8 +2751,55 @@ int32_t aule_mla_kv_append_ex(const aule_mla_kv_append_desc* d) {
     a.cos = d->cos; a.sin = d->sin; a.positions = reinterpret_cast<const long long*>(d->positions);
     a.table_len = (long long)d->table_len; a.table_pitch = (int)d->table_pitch;
     a.rope_layout = d->rope_layout;
+}
+
+int32_t aule_mla_kv_append_ex(const aule_mla_kv_append_desc* d) {
+    RoctxRange range("aule.mla_kv_append");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_kv_append_error(d, text)) {
+        set_error("MLA KV append failed: %s", why);
+        return -3;
+    }
+    if (mla_kv_append_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaKvAppendArgs a;
+    fill_mla_kv_append_args(d, a);
     DeviceGuard g(d->device);
     return launched("MLA KV append", aule_hip::launch_mla_kv_append(a, (hipStream_t)d->stream));
+}
+
+// The append into the per-128-scaled FP8 cache: the twin's descriptor without kv_scale, read as the twin (16-bit cache kind, no scale)
+// by the one checker above after the two rules of its own, as mla_sparse_ds_desc_error does.
+int32_t aule_mla_kv_append_ds_ex(const aule_mla_kv_append_ds_desc* d) {
+    RoctxRange range("aule.mla_kv_append_ds");
+    const char* what = "MLA KV append (656-byte rows)";
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    aule_mla_kv_append_desc twin{};
+    const char* why = kBadDescriptor;
+    if (d != nullptr && d->struct_size == sizeof(aule_mla_kv_append_ds_desc)) {
+        twin.struct_size = sizeof(twin);
+        twin.dtype = d->dtype; twin.cache_dtype = AULE_KV_CACHE_SAME; twin.rope_layout = d->rope_layout;
+        twin.total_tokens = d->total_tokens; twin.num_blocks = d->num_blocks; twin.block_size = d->block_size;
+        twin.table_len = d->table_len; twin.table_pitch = d->table_pitch; twin.device = d->device;
+        twin.c_kv_token_stride = d->c_kv_token_stride; twin.k_pe_token_stride = d->k_pe_token_stride; twin.stream = d->stream;
+        twin.c_kv = d->c_kv; twin.k_pe = d->k_pe; twin.kv_cache = d->kv_cache; twin.slot_mapping = d->slot_mapping;
+        twin.cos = d->cos; twin.sin = d->sin; twin.positions = d->positions;
+        why = d->dtype != AULE_DTYPE_BF16 ? reasonf(text, "dtype %d (of c_kv / k_pe) must be bf16: the rotary part of a 656-byte cache row is bf16", d->dtype)
+              : d->reserved != 0          ? reasonf(text, "reserved (%d) must be 0", d->reserved)
+                                          : mla_kv_append_error(&twin, text);
+    }
+    if (why != nullptr) {
+        set_error("%s failed: %s", what, why);
+        return -3;
+    }
+    if (mla_kv_append_nothing_to_do(&twin)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaKvAppendArgs a;
+    fill_mla_kv_append_args(&twin, a);
+    DeviceGuard g(twin.device);
+    return launched(what, aule_hip::launch_mla_kv_append_ds(a, (hipStream_t)twin.stream));
 }
 
 uint64_t aule_attention_backward_workspace_size(const aule_attn_bwd_desc* d) {
@@ -2925,6 +3027,13 @@ uint64_t aule_attention_mla_sparse_workspace_size(const aule_mla_sparse_desc* d)
     return mla_sparse_nothing_to_do(d) ? 0 : mla_sparse_plan_of(d).ws_bytes;
 }
 
+uint64_t aule_attention_mla_sparse_ds_workspace_size(const aule_mla_sparse_ds_desc* d) {
+    Reason text;
+    aule_mla_sparse_desc twin;
+    if (mla_sparse_ds_desc_error(d, false, text, twin)) return 0;
+    return mla_sparse_nothing_to_do(&twin) ? 0 : mla_sparse_plan_of(&twin).ws_bytes;
+}
+
 #ifdef AULE_DEBUG_HOOKS
 /* The timeline hooks exist only in the debug library (`make dbg` -> build/variants/libaule_dbg.so, -DAULE_DEBUG_HOOKS):
  * they launch instrumented kernel instances on caller-supplied pointers and are not part of the product libaule.so. */
@@ -3016,6 +3125,14 @@ int32_t aule_hip_debug_mla_sparse_plan(const aule_mla_sparse_desc* d, int32_t* o
     if (mla_sparse_nothing_to_do(d)) return 0;
     const aule_hip::MlaPlan plan = mla_sparse_plan_of(d);
     return dump_plan({plan.row_blocks, plan.rows_per_block, plan.nsplit, (int32_t)plan.grid}, &plan.ws_bytes, out, cap);
+}
+
+/* Debug hook: the launch plan of aule_attention_mla_sparse_ds_ex(d): the twin's plan, by the twin's hook. */
+int32_t aule_hip_debug_mla_sparse_ds_plan(const aule_mla_sparse_ds_desc* d, int32_t* out, int32_t cap) {
+    Reason text;
+    aule_mla_sparse_desc twin;
+    if (mla_sparse_ds_desc_error(d, false, text, twin)) return -3;
+    return aule_hip_debug_mla_sparse_plan(&twin, out, cap);
 }
 
 /* Debug hook (not part of the drop-in ABI): aule_attention_mla_sparse_ex(d) with `nsplit` key ranges (within 1 .. min(64, tiles)) instead

@@ -35,6 +35,10 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_mla_sparse_kernel(const MlaPara
 
 }  // namespace
 
+// The attention kernel over the per-128-scaled FP8 cache of 656-byte rows (fa_fwd_mla_sparse_ds_gfx950.hip, which holds that tile and
+// instance; `p` as launch_mla_sparse fills it, no kv_scale; bf16 only: -1 otherwise); partials and combine are this call's.
+int launch_mla_sparse_ds_kernel(const MlaParams& p, long long grid, int dtype, hipStream_t stream);
+
 // The sparse call: row blocks of ONE token's heads, the tiles of its list.
 MlaPlan mla_sparse_plan(int T, int Hq, int topk, int device, int force_nsplit) {
     if (T <= 0 || Hq <= 0 || topk <= 0) return MlaPlan();
@@ -56,7 +60,10 @@ int launch_mla_sparse(const MlaSparseArgs& a, const MlaPlan& plan, void* ws, hip
     p.max_blocks = 0; p.max_sq = 1;
     p.list = a.indices; p.topk = a.topk; p.slots = a.slots;
     int rc;
-    if (p.kv_scale != nullptr) {
+    if (a.ds_rows) {
+        if (p.kv_scale != nullptr) return -1;   // (the scales are in the rows)
+        rc = launch_mla_sparse_ds_kernel(p, plan.grid, a.dtype, stream);
+    } else if (p.kv_scale != nullptr) {
         rc = launch_mla_sparse_fp8_kernel(p, plan.grid, a.dtype, stream);
     } else {
         rc = dispatch_16bit(a.dtype, [&](auto t) {

@@ -235,6 +235,9 @@ struct MlaKvAppendArgs {
     int rope_layout = 0;
 };
 int launch_mla_kv_append(const MlaKvAppendArgs& a, hipStream_t stream);   // -1: unsupported arguments
+// The same append into the per-128-scaled FP8 latent cache (mla_kv_append_ds_gfx950.hip, where the quantisation rule is stated):
+// kv_cache is [num_blocks * block_size][656] bytes; dtype kBF16, no kv_scale.
+int launch_mla_kv_append_ds(const MlaKvAppendArgs& a, hipStream_t stream);   // -1: unsupported arguments
 
 // Paged prefill (fa_fwd_paged_prefill_gfx950.hip): ragged per-sequence queries against the paged cache, one launch, no workspace.
 //   q [T, Hq, D] 16-bit, the new tokens of all sequences packed along the first axis (q_token_stride elements between tokens, the
@@ -411,6 +414,10 @@ struct MlaSparseArgs {
     int device = -1;                    // as FwdArgs::device
     int cache_kind = kCache16;
     const float* kv_scale = nullptr;    // kCacheFp8E4M3 only: [1] fp32, device
+    // The per-128-scaled FP8 latent cache (fa_fwd_mla_sparse_ds_gfx950.hip; the contract is aule_mla_sparse_ds_desc):
+    // kv_cache is a flat array of 656-byte rows (512 e4m3fn codes | 4 fp32 scales | 64 bf16 rotary elements), dequantised to bf16 on
+    // its way into LDS.  dtype kBF16, cache_kind kCache16 (the kind of the image) and no kv_scale: the scales are the rows'.
+    bool ds_rows = false;
 };
 constexpr int kMlaSparseMaxTopk = 65536;
 // The launch plan (mla_sparse_plan, beside the kernel: the one statement of row blocks, nsplit, grid and workspace for launch, size

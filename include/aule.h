@@ -695,6 +695,47 @@ int32_t aule_attention_mla_sparse_ex(const aule_mla_sparse_desc* desc);
 /* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
 uint64_t aule_attention_mla_sparse_workspace_size(const aule_mla_sparse_desc* desc);
 
+/* SPARSE MLA OVER THE PER-128-SCALED FP8 LATENT CACHE (additive): aule_attention_mla_sparse_ex in every respect but where a key row     */
+/* comes from.  kv_cache is [num_blocks, block_size] rows of 656 BYTES, contiguous, 16-byte aligned -- the row DeepSeek-V3.2's serving  */
+/* kernels keep per cached token:                                                                                                      */
+/*     bytes   0 .. 511   512 OCP e4m3fn codes of the compressed latent                                                                 */
+/*     bytes 512 .. 527   4 fp32 scales; scale g belongs to codes 128 g .. 128 g + 127                                                  */
+/*     bytes 528 .. 655   the 64 rotary elements (already rotated) as bf16, not quantised                                               */
+/* The key of slot s is k[s][c] = bf16_rne(float(code[s][c]) * scale[s][c / 128]) for c < 512 and the stored bf16 for c >= 512; the     */
+/* value is its first 512 elements.  Keys are dequantised to bf16 on their way into LDS, so the call equals                             */
+/* aule_attention_mla_sparse_ex over the dequantised bf16 cache bit for bit, out and lse: no scale is folded into the score scale or   */
+/* the accumulators.  q / out are bf16 (dtype AULE_DTYPE_BF16; fp16 is refused: the rotary part is multiplied as stored).               */
+/* indices, the RULE, READS AND WRITES, LAUNCHES, the workspace formula and the fixed-order combine are aule_mla_sparse_desc's, word    */
+/* for word; the descriptor is its twin without kv_scale, and `reserved` (where the twin has cache_dtype) must be 0.  Rows are what     */
+/* aule_mla_kv_append_ds_ex writes.  REFUSED with -3 and a reason before the device is needed: what the twin refuses, a non-zero       */
+/* `reserved`, a dtype other than bf16.                                                                                                 */
+/* Not built: the dense aule_attention_mla_paged* entries, tree masks and FP8 matrix products over this row; fp16 queries.              */
+typedef struct aule_mla_sparse_ds_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_sparse_ds_desc) = 112 */
+    int32_t dtype;             /* offset 4; type of q / out: AULE_DTYPE_BF16 */
+    int32_t reserved;          /* offset 8; 0 */
+    int32_t heads_q;           /* offset 12; >= 1 */
+    uint32_t num_blocks;       /* offset 16; num_blocks * block_size = S, 1 .. 2^31 - 1 */
+    uint32_t block_size;       /* offset 20 */
+    int32_t total_tokens;      /* offset 24; rows of q / out / indices; 0: returns 0 without a launch */
+    int32_t topk;              /* offset 28; entries per token, 1 .. 65536 */
+    float scale;               /* offset 32; 0 -> 1/sqrt(576) */
+    int32_t device;            /* offset 36; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 40; elements, >= heads_q * 576, a multiple of 8 */
+    void* stream;              /* offset 48; hipStream_t */
+    const void* q;             /* offset 56; [total_tokens, heads_q, 576] bf16 */
+    const void* kv_cache;      /* offset 64; [num_blocks, block_size, 656] bytes */
+    const int32_t* indices;    /* offset 72; [total_tokens, topk] slots, device */
+    void* out;                 /* offset 80; [total_tokens, heads_q, 512] bf16, contiguous */
+    float* lse;                /* offset 88; optional (NULL to skip): [total_tokens, heads_q] fp32 */
+    void* workspace;           /* offset 96; optional, size from aule_attention_mla_sparse_ds_workspace_size() */
+    uint64_t workspace_bytes;  /* offset 104 */
+} aule_mla_sparse_ds_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_attention_mla_sparse_ds_ex(const aule_mla_sparse_ds_desc* desc);
+/* Host logic only; pointers in the descriptor are not read.  0 for a descriptor the launch refuses or that has nothing to do. */
+uint64_t aule_attention_mla_sparse_ds_workspace_size(const aule_mla_sparse_ds_desc* desc);
+
 /* MLA INDEXER (additive): the producer of aule_mla_sparse_desc's key lists (DeepSeek-V3.2 "DSA"): index logits over a paged cache of  */
 /* index keys, then the top-k key list of every query token.  Two entries, two launches; these two comments are the contract.           */
 /* LOGITS.  logits[t][s] = sum_h weights[t][h] * relu(q[t][h][:] . k[s][:]), fp32.                                                       */
@@ -1523,6 +1564,39 @@ typedef struct aule_mla_kv_append_desc {
 /* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
 int32_t aule_mla_kv_append_ex(const aule_mla_kv_append_desc* desc);
 
+/* Latent cache append into the per-128-scaled FP8 cache (additive; the write side of aule_attention_mla_sparse_ds_ex, whose comment   */
+/* states the 656-byte row).  aule_mla_kv_append_ex's call -- slots, skipped tokens, token strides, the optional rotation of k_pe and  */
+/* its two layouts, alignment, one capturable launch -- with another row:                                                              */
+/*     row slot_mapping[t]  <-  codes(c_kv[t]) | the four scales | bf16(rope(k_pe[t]))                                                  */
+/* Per group g of 128 columns of c_kv[t]: amax = max |x| in fp32; scale = 2^max(ceil(log2(amax / 448)), -126), a power of two (so code  */
+/* * scale is exact), 1 for a group of zeros; code = cast_e4m3fn(clamp(x / scale, -448, 448)), round to nearest even.  NaN and          */
+/* infinite inputs are the caller's business.  c_kv and k_pe are bf16 (dtype AULE_DTYPE_BF16; fp16 is refused: the rotary part of the   */
+/* row is bf16).  The descriptor is the twin's without kv_scale; `reserved` (where the twin has cache_dtype) must be 0.                 */
+typedef struct aule_mla_kv_append_ds_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_kv_append_ds_desc) = 120 */
+    int32_t dtype;             /* offset 4; of c_kv / k_pe: AULE_DTYPE_BF16 */
+    int32_t reserved;          /* offset 8; 0 */
+    int32_t rope_layout;       /* offset 12; AULE_ROPE_HALF or AULE_ROPE_INTERLEAVED (read with rotation only, but always checked) */
+    uint32_t total_tokens;     /* offset 16; 0: returns 0 without a launch */
+    uint32_t num_blocks;       /* offset 20 */
+    uint32_t block_size;       /* offset 24; any value > 0 */
+    uint32_t table_len;        /* offset 28; rows of cos / sin (0 without rotation) */
+    uint32_t table_pitch;      /* offset 32; floats per table row; 0 = 32 */
+    int32_t device;            /* offset 36; HIP device ordinal, -1 = current */
+    int64_t c_kv_token_stride; /* offset 40; elements, >= 512, a multiple of 8 */
+    int64_t k_pe_token_stride; /* offset 48; elements, >= 64, a multiple of 8 */
+    void* stream;              /* offset 56; hipStream_t */
+    const void* c_kv;          /* offset 64; [total_tokens, 512] */
+    const void* k_pe;          /* offset 72; [total_tokens, 64] */
+    void* kv_cache;            /* offset 80; [num_blocks, block_size, 656] bytes, contiguous */
+    const int64_t* slot_mapping;   /* offset 88; [total_tokens] */
+    const float* cos;          /* offset 96; [table_len, 32] fp32, or NULL */
+    const float* sin;          /* offset 104 */
+    const int64_t* positions;  /* offset 112; [total_tokens], or NULL */
+} aule_mla_kv_append_ds_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_mla_kv_append_ds_ex(const aule_mla_kv_append_ds_desc* desc);
+
 /* Attention with the query rotation fused into the kernel (additive; inference path).  Replaces the Q half of       */
 /* python/aule/triton_flash.py:112-131 (the reference rotates Q in its forward prologue); K must arrive rotated --   */
 /* once per key by aule_rope_ex(), e.g. when it is appended to a KV cache -- because the tiled kernel re-reads every */
@@ -1586,6 +1660,9 @@ int32_t aule_hip_debug_mla_sparse_plan(const aule_mla_sparse_desc* desc, int32_t
 /* bench that measures the plan's "one split per two tiles" cap (tools/bench_mla_sparse.py); results equal the entry's within the   */
 /* forward bounds, bit for bit only at the plan's own nsplit.                                                                       */
 int32_t aule_hip_debug_mla_sparse_launch_nsplit(const aule_mla_sparse_desc* desc, int32_t nsplit);
+/* Debug: the launch plan of aule_attention_mla_sparse_ds_ex(desc), aule_hip_debug_mla_sparse_plan's six integers by its rules: the    */
+/* plan of the twin descriptor with the same total_tokens, heads_q and topk.                                                           */
+int32_t aule_hip_debug_mla_sparse_ds_plan(const aule_mla_sparse_ds_desc* desc, int32_t* out, int32_t cap);
 /* Debug: the launch plan of aule_attention_paged_d256_ex(desc) as integers -- out = {row blocks, rows per block (64), nsplit,      */
 /* workgroups (row blocks * nsplit * heads_kv * batch), workspace bytes low 32 bits, high 32 bits}.  Returns the ints written       */
 /* (negative: the capacity needed), 0 for a descriptor with nothing to do; -3 bad.  Host logic only, no aule_init(), no pointer of  */

@@ -21,7 +21,13 @@ Cap legs (T = 1, context 32 K, after the table): what the plan's "at most one sp
 same call through aule_hip_debug_mla_sparse_launch_nsplit (the C entry with the split count forced; descriptor and workspace made once,
 so these figures hold no torch-layer cost and are lower than the table's) at nsplit 4 / 8 / 16 / 32: 16 is the plan's and 32 is one
 tile per workgroup -- what the cap forbids (there are 32 tiles: more ranges would be empty).  Each result is first compared with the
-entry's (bit for bit at the plan's nsplit, the forward bound elsewhere)."""
+entry's (bit for bit at the plan's nsplit, the forward bound elsewhere).
+
+--ds: instead of all of the above, the grid's decode and prefill shapes on the per-128-scaled FP8 cache (uint8 [.., 656] rows,
+aule.quantize_mla_cache_fp8_ds of the same latent), the sparse call over it against (a) the sparse call over the
+single-scale FP8 cache and (b) the route there was: aule.dequantize_mla_cache_fp8_ds of the whole cache, then the bf16 sparse call.
+Before a leg is timed the new call is compared with route (b) bit for bit.  Ratios above 1: the new call is faster; a leg below 1 is
+marked LOSS.  Default --out: profiles/mla_sparse_ds_bench.txt."""
 import ctypes
 import os
 import signal
@@ -114,6 +120,34 @@ def _routes(q, kv, idx, fp8, dense):
     return {"sparse": sparse, "dense": lambda: dense(cache, kw), "gather+sdpa": gather_sdpa}
 
 
+def _routes_ds(q, kv, idx):
+    """the --ds calls on one problem; kv the bf16 cache [nb, bs, 576], idx [T, topk] int32 valid slots"""
+    ds = aule.quantize_mla_cache_fp8_ds(kv)
+    codes, ks = aule.quantize_mla_cache_fp8(kv)
+
+    def dequant_bf16():
+        return aule.flash_attention_mla_sparse(q, aule.dequantize_mla_cache_fp8_ds(ds), idx)
+
+    a, b_ = aule.flash_attention_mla_sparse(q, ds, idx), dequant_bf16()
+    torch.cuda.synchronize()
+    if not torch.equal(a, b_):
+        raise SystemExit("the sparse MLA over 656-byte rows and the bf16 call over the dequantised cache disagree")
+    del a, b_
+    return {"ds": lambda: aule.flash_attention_mla_sparse(q, ds, idx), "fp8": lambda: aule.flash_attention_mla_sparse(q, codes, idx, kv_scale=ks),
+            "dequant+bf16": dequant_bf16}
+
+
+def _report_ds(what, T, Hq, res, lines):
+    med, span = {k: v[0] for k, v in res.items()}, {k: v[1] for k, v in res.items()}
+    rb, ns = plan(T, Hq, TOPK)
+    ra, rb_ = med["fp8"] / med["ds"], med["dequant+bf16"] / med["ds"]
+    line = (f"  {what} ds   heads {Hq:3d}: plan {T:4d} x {rb} x {ns:2d}   656-byte rows {span['ds']} us   (a) single-scale fp8 {span['fp8']} us   "
+            f"(b) dequantise + bf16 {span['dequant+bf16']} us   (a) / ds {ra:6.2f}x{' LOSS' if ra < 1 else ''}   (b) / ds {rb_:6.2f}x{' LOSS' if rb_ < 1 else ''}   "
+            f"{T * TOPK * 656 / (med['ds'] * 1e-6) / 1e12:5.2f} TB/s of listed rows")
+    print(line, flush=True)
+    lines.append(line)
+
+
 def _report(what, T, Hq, fp8, res, lines):
     med, span = {k: v[0] for k, v in res.items()}, {k: v[1] for k, v in res.items()}
     rb, ns = plan(T, Hq, TOPK)
@@ -125,7 +159,7 @@ def _report(what, T, Hq, fp8, res, lines):
     lines.append(line)
 
 
-def leg_decode(Hq, T, L, fp8, rounds, lines):
+def leg_decode(Hq, T, L, fp8, rounds, lines, ds=False):
     g = torch.Generator(device="cuda").manual_seed(Hq + T + L + fp8)
     dt = torch.bfloat16
     nblk = L // BS
@@ -140,11 +174,14 @@ def leg_decode(Hq, T, L, fp8, rounds, lines):
     def dense(cache, kw):
         return (aule.flash_attention_mla_paged_fp8 if fp8 else aule.flash_attention_mla_paged)(q, cache, bt, cl, **kw)
 
+    what = f"decode  T {T:2d} context {L:6d}"
+    if ds:
+        return _report_ds(what, T, Hq, _alternated(_routes_ds(q, kv, idx), rounds), lines)
     res = _alternated(_routes(q, kv, idx, fp8, dense), rounds)
-    _report(f"decode  T {T:2d} context {L:6d}", T, Hq, fp8, res, lines)
+    _report(what, T, Hq, fp8, res, lines)
 
 
-def leg_prefill(Hq, fp8, rounds, lines):
+def leg_prefill(Hq, fp8, rounds, lines, ds=False):
     g = torch.Generator(device="cuda").manual_seed(Hq + fp8)
     dt = torch.bfloat16
     T, L = PREFILL_CHUNK, PREFILL_LATENT
@@ -159,8 +196,11 @@ def leg_prefill(Hq, fp8, rounds, lines):
     def dense(cache, kw):
         return (aule.flash_attention_mla_paged_fp8 if fp8 else aule.flash_attention_mla_paged)(q, cache.view(L // BS, BS, QK), bt, cl, cu, max_seqlen_q=T, **kw)
 
+    what = f"prefill T {T} latent {L:6d}"
+    if ds:
+        return _report_ds(what, T, Hq, _alternated(_routes_ds(q, latent.view(L, 1, QK), idx), rounds), lines)
     res = _alternated(_routes(q, latent.view(L, 1, QK), idx, fp8, dense), rounds)
-    _report(f"prefill T {T} latent {L:6d}", T, Hq, fp8, res, lines)
+    _report(what, T, Hq, fp8, res, lines)
 
 
 def leg_cap(Hq, fp8, rounds, lines):
@@ -215,22 +255,28 @@ def main():
     rounds, budget = _arg("--rounds", 5), _arg("--leg-timeout", 120)
     signal.signal(signal.SIGALRM, signal.SIG_DFL)      # the default action ends the process, also from inside a blocked device call
     only_cap = "--cap-only" in sys.argv    # (the cap legs alone)
+    ds = "--ds" in sys.argv                # (the legs on the cache of 656-byte rows alone)
     head = (f"# tools/bench_mla_sparse.py   (one MI355X; latent 576 / 512, topk {TOPK}, bf16 queries; plan = tokens x row blocks x nsplit workgroups; "
             f"{rounds} alternated rounds of ~{WINDOW_MS} ms windows, median (min .. max) us per call, host launch cost included)")
     print(head, flush=True)
     lines = [head]
-    for fp8 in (() if only_cap else (False, True)):
+    for fp8 in (() if only_cap else (False,) if ds else (False, True)):
         for Hq in HEADS:
             for T in TOKENS:
                 for L in CONTEXT:
                     signal.alarm(budget)
-                    leg_decode(Hq, T, L, fp8, rounds, lines)
+                    leg_decode(Hq, T, L, fp8, rounds, lines, ds)
                     signal.alarm(0)
                     torch.cuda.empty_cache()
             signal.alarm(budget)
-            leg_prefill(Hq, fp8, rounds, lines)
+            leg_prefill(Hq, fp8, rounds, lines, ds)
             signal.alarm(0)
             torch.cuda.empty_cache()
+    if ds:
+        path = _arg("--out", os.path.join(ROOT, "profiles", "mla_sparse_ds_bench.txt"), str)
+        with open(path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+        return
     lines.append("# the split cap at T = 1 (C entry with the split count forced, descriptor and workspace made once: no torch-layer cost)")
     print(lines[-1], flush=True)
     for fp8 in (False, True):
