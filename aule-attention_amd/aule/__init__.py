@@ -509,8 +509,8 @@ def mla_indexer_logits(q, weights, k_cache, block_tables, context_lens, cu_seqle
     T * W * 4 bytes -- 1 GB at 2048 tokens x 128 K columns: chunk T or size the table.  No host synchronisation, capturable, two
     runs are bit-identical.  All argument errors are ValueErrors raised before the device is touched; CPU tensors that pass
     them are an AuleError; tensors that require grad are refused.
-    Out of scope: FP8 queries and FP8 MFMAs, a fused streaming top-k that never writes [T, W], an append kernel for the index
-    keys, H > 64, a backward."""
+    The append kernel for the index keys is mla_indexer_k_append, the queries' rotation mla_indexer_q_rotate.
+    Out of scope: FP8 queries and FP8 MFMAs, a fused streaming top-k that never writes [T, W], H > 64, a backward."""
     try:
         import torch  # noqa: F401
     except ImportError as e:
@@ -558,6 +558,56 @@ def quantize_indexer_cache_fp8(k_cache):
     Plain torch ops; works on CPU tensors."""
     from ._torch import quantize_indexer_cache_fp8 as impl
     return impl(k_cache)
+
+
+def mla_indexer_k_append(k, k_cache, slot_mapping, k_scale=None, norm_weight=None, norm_bias=None, eps=1e-6, cos=None, sin=None,
+                         positions=None, rope_layout="half", rope_offset=0, hadamard=True, scale_format="amax"):
+    """The write side of the indexer's key cache: the index keys of T new tokens through LayerNorm, RoPE and the 128-point Hadamard
+    rotation into the paged cache mla_indexer_logits reads, in place, with one launch; returns None.  The contract is stated once, at
+    aule_mla_indexer_rows_desc in include/aule.h; in short, per row, in fp32 through every enabled stage:
+
+        norm      (norm_weight given) x <- (x - mean) / sqrt(biased var + eps) * norm_weight + norm_bias; both [128] fp32
+                  contiguous, norm_bias None is zero
+        RoPE      (cos, sin [table_len, 32] and positions [T], all or none) the 64 elements from rope_offset (0: the indexer's
+                  rotary half comes first; 64: last) by table row positions[t]; rope_layout "half" pairs (p, p + 32),
+                  "interleaved" pairs (2p, 2p + 1); rope_raw's arithmetic
+        hadamard  y[i] = 2^-3.5 * sum_j (-1)^popcount(i & j) x[j]
+        then ONE rounding to k's dtype, and the store to cache row slot_mapping[t]
+
+        k        [T, 128] (or [T, 1, 128]) fp16 / bf16, last dimension contiguous, the token stride a free multiple of 8 elements
+                 (a slice of the fused projection is read in place)
+        k_cache  [num_blocks, block_size, 128] (or [..., 1, 128]), contiguous: k's dtype (the bits), or torch.float8_e4m3fn with
+                 k_scale [num_blocks, block_size] fp32, which receives each written row's scale: amax / 448 (1.0 for a row of
+                 zeros) with scale_format "amax" -- quantize_indexer_cache_fp8 of the 16-bit row, bit for bit -- or the power of
+                 two at or above it with "ue8m0"; code = cast(clamp(r / scale, -448, 448))
+        slot_mapping [T] integer = block * block_size + offset (paged_slot_mapping); negative or past the cache: the token is
+                 skipped entirely, scale included, and so is, with RoPE, a token whose position is outside the table; two tokens
+                 with the same slot in one call: which one wins is unspecified
+
+    No synchronisation, capturable (int64 slot_mapping / positions on the device are read in place).  Argument errors are
+    ValueErrors raised before the device is touched; CPU tensors raise AuleError; tensors that require grad are refused."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_indexer_k_append as impl
+    return impl(k, k_cache, slot_mapping, k_scale=k_scale, norm_weight=norm_weight, norm_bias=norm_bias, eps=eps, cos=cos, sin=sin,
+                positions=positions, rope_layout=rope_layout, rope_offset=rope_offset, hadamard=hadamard, scale_format=scale_format)
+
+
+def mla_indexer_q_rotate(q, cos=None, sin=None, positions=None, rope_layout="half", rope_offset=0, hadamard=True, out=None):
+    """The index queries q [T, H, 128] (fp16 / bf16; last dimension contiguous, token and head strides free multiples of 8
+    elements) through the RoPE and Hadamard stages of mla_indexer_k_append -- the same kernel, the same arithmetic, every head of a
+    token rotated by table row positions[t] -- rounded once to q's dtype, with one launch.  Returns out: a new contiguous tensor, or
+    the tensor given (q's shape and dtype, the same stride rules); out may be q itself, which runs in place, any other overlap with
+    q is undefined.  The result is what mla_indexer_logits takes as q.  No synchronisation, capturable.  Argument errors are
+    ValueErrors raised before the device is touched; CPU tensors raise AuleError; tensors that require grad are refused."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_indexer_q_rotate as impl
+    return impl(q, cos=cos, sin=sin, positions=positions, rope_layout=rope_layout, rope_offset=rope_offset, hadamard=hadamard, out=out)
 
 
 def mla_kv_append(c_kv, k_pe, kv_cache, slot_mapping, kv_scale=None, cos=None, sin=None, positions=None, rope_layout="half"):
@@ -1122,7 +1172,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "quantize_mla_cache_fp8_ds", "dequantize_mla_cache_fp8_ds", "flash_attention_varlen", "flash_attention_varlen_d256", "flash_attention_varlen_d256_softcap", "flash_attention_paged_d256_softcap", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer_k_append", "mla_indexer_q_rotate", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "quantize_mla_cache_fp8_ds", "dequantize_mla_cache_fp8_ds", "flash_attention_varlen", "flash_attention_varlen_d256", "flash_attention_varlen_d256_softcap", "flash_attention_paged_d256_softcap", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

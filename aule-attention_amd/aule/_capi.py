@@ -329,6 +329,47 @@ class MlaKvAppendDsDesc(ctypes.Structure):
     _fields_ = [("reserved", t) if n == "cache_dtype" else (n, t) for n, t in MlaKvAppendDesc._fields_ if n != "kv_scale"]
 
 
+INDEXER_SCALE_AMAX, INDEXER_SCALE_UE8M0 = 0, 1
+INDEXER_ROWS_NORM, INDEXER_ROWS_HADAMARD = 1, 2
+
+
+class MlaIndexerRowsDesc(ctypes.Structure):
+    """struct aule_mla_indexer_rows_desc (include/aule.h): the indexer's write side, dense rows or the paged index-key cache."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("cache_dtype", ctypes.c_int32),
+        ("scale_format", ctypes.c_int32),
+        ("rope_layout", ctypes.c_int32),
+        ("rope_offset", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("eps", ctypes.c_float),
+        ("total_tokens", ctypes.c_uint32),
+        ("heads", ctypes.c_uint32),
+        ("num_blocks", ctypes.c_uint32),
+        ("block_size", ctypes.c_uint32),
+        ("table_len", ctypes.c_uint32),
+        ("table_pitch", ctypes.c_uint32),
+        ("device", ctypes.c_int32),
+        ("reserved", ctypes.c_uint32),
+        ("x_token_stride", ctypes.c_int64),
+        ("x_head_stride", ctypes.c_int64),
+        ("out_token_stride", ctypes.c_int64),
+        ("out_head_stride", ctypes.c_int64),
+        ("stream", ctypes.c_void_p),
+        ("x", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("k_cache", ctypes.c_void_p),
+        ("k_scale", ctypes.c_void_p),
+        ("slot_mapping", ctypes.c_void_p),
+        ("norm_weight", ctypes.c_void_p),
+        ("norm_bias", ctypes.c_void_p),
+        ("cos", ctypes.c_void_p),
+        ("sin", ctypes.c_void_p),
+        ("positions", ctypes.c_void_p),
+    ]
+
+
 class VarlenDesc(ctypes.Structure):
     """struct aule_varlen_desc (include/aule.h): forward over a variable-length packed batch."""
     _problem_ = [
@@ -651,6 +692,7 @@ SIGNATURES = [
     ("aule_mla_kv_append_ds_ex", _I32, [ctypes.POINTER(MlaKvAppendDsDesc)]),
     ("aule_mla_indexer_logits_ex", _I32, [ctypes.POINTER(MlaIndexerLogitsDesc)]),
     ("aule_mla_indexer_topk_ex", _I32, [ctypes.POINTER(MlaIndexerTopkDesc)]),
+    ("aule_mla_indexer_rows_ex", _I32, [ctypes.POINTER(MlaIndexerRowsDesc)]),
     ("aule_mla_kv_append_ex", _I32, [ctypes.POINTER(MlaKvAppendDesc)]),
     ("aule_attention_varlen_forward_ex", _I32, [ctypes.POINTER(VarlenDesc)]),
     ("aule_attention_varlen_backward_ex", _I32, [ctypes.POINTER(VarlenBwdDesc)]),

@@ -1893,6 +1893,168 @@ def quantize_indexer_cache_fp8(k_cache):
     return (x / scale[..., None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn), scale
 
 
+_INDEXER_SCALE_FORMATS = {"amax": _capi.INDEXER_SCALE_AMAX, "ue8m0": _capi.INDEXER_SCALE_UE8M0}
+
+
+def _indexer_rows_args(name, x, norm_weight, norm_bias, eps, cos, sin, positions, rope_layout, rope_offset, hadamard):
+    """The rules the two entries of the indexer's write side share, on x [T, H, 128]: dtype, strides, the norm vectors and the rotation
+    group.  Returns (token stride, head stride) of x in elements."""
+    T, H, W = x.shape
+    if W != 128:
+        raise ValueError(f"the index head width must be 128: {name} has {W}")
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{name} must be fp16 or bf16, got {x.dtype}")
+    strides = _indexer_rows_strides(name, x)
+    for what, v in (("norm_weight", norm_weight), ("norm_bias", norm_bias)):
+        if v is not None and (not torch.is_tensor(v) or v.dtype != torch.float32 or tuple(v.shape) != (128,) or not v.is_contiguous()
+                              or v.storage_offset() % 4):
+            raise ValueError(f"{what} must be a contiguous fp32 tensor [128], 16-byte aligned")
+    if norm_bias is not None and norm_weight is None:
+        raise ValueError("norm_bias without norm_weight: the norm is switched on by its weight")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps >= 0:
+        raise ValueError(f"eps must be a number >= 0, got {eps!r}")
+    if rope_layout not in _ROPE_LAYOUTS:
+        raise ValueError(f"unknown rope_layout {rope_layout!r} ('half' or 'interleaved')")
+    if isinstance(rope_offset, bool) or rope_offset not in (0, 64):
+        raise ValueError(f"rope_offset must be 0 or 64 (the rotary half of the row), got {rope_offset!r}")
+    if not isinstance(hadamard, bool):
+        raise ValueError(f"hadamard must be a bool, got {hadamard!r}")
+    if cos is not None or sin is not None or positions is not None:
+        if cos is None or sin is None or positions is None:
+            raise ValueError("cos, sin and positions go together: all three for RoPE, or none")
+        if not torch.is_tensor(positions) or positions.dim() != 1 or positions.shape[0] != T or positions.dtype.is_floating_point \
+                or positions.dtype == torch.bool:
+            raise ValueError(f"positions must be an integer tensor of shape [{T}]")
+        if not torch.is_tensor(cos) or not torch.is_tensor(sin) or cos.shape[-1] != 32 or sin.shape[-1] != 32 or cos.shape != sin.shape:
+            raise ValueError("cos / sin must be tensors of one shape [..., 32]")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise ValueError("the MLA indexer has no backward: detach the inputs or call it under torch.no_grad()")
+    return strides
+
+
+def _indexer_rows_strides(name, x):
+    """(token stride, head stride) of x [T, H, 128] in elements, after the 16-byte rules; a dimension of extent 1 has no stride."""
+    T, H, _ = x.shape
+    if x.stride(2) != 1:
+        raise ValueError(f"the last dimension of {name} must be contiguous, got stride {x.stride(2)}")
+    ts = x.stride(0) if T > 1 else H * 128
+    hs = x.stride(1) if H > 1 else 128
+    if ts % 8 or hs % 8 or hs < 128 or x.storage_offset() % 8:
+        raise ValueError(f"{name}: rows must be 16-byte aligned and apart (token stride {ts}, head stride {hs} and the storage offset "
+                         f"multiples of 8 elements, the head stride at least 128)")
+    return ts, hs
+
+
+def _indexer_rows_launch(x, strides, d, held, norm_weight, norm_bias, eps, cos, sin, positions, rope_layout, rope_offset, hadamard):
+    """Fill the part of the descriptor both entries share and launch; `held` keeps converted tensors alive over the call."""
+    dev = x.device
+    T, H, _ = x.shape
+    d.struct_size = ctypes.sizeof(d)
+    d.dtype = _DTYPES[x.dtype]
+    d.rope_layout, d.rope_offset = _ROPE_LAYOUTS[rope_layout], rope_offset
+    d.flags = (_capi.INDEXER_ROWS_NORM if norm_weight is not None else 0) | (_capi.INDEXER_ROWS_HADAMARD if hadamard else 0)
+    d.eps = float(eps)
+    d.total_tokens, d.heads = T, H
+    d.x_token_stride, d.x_head_stride = strides
+    d.device = _device_index(dev)
+    d.stream = _stream_ptr(dev)
+    d.x = x.data_ptr()
+    if norm_weight is not None:
+        d.norm_weight = norm_weight.data_ptr()
+        d.norm_bias = norm_bias.data_ptr() if norm_bias is not None else None
+    if cos is not None:
+        c, s_ = _rope_tables(cos, sin, 64, dev)
+        pos = positions.to(device=dev, dtype=torch.int64).contiguous()
+        d.table_len, d.table_pitch = c.shape[0], c.stride(0)
+        d.cos, d.sin, d.positions = c.data_ptr(), s_.data_ptr(), pos.data_ptr()
+        held += [c, s_, pos]
+    _capi.check(_capi.get_lib().aule_mla_indexer_rows_ex(ctypes.byref(d)), "aule_mla_indexer_rows_ex")
+
+
+def mla_indexer_k_append(k, k_cache, slot_mapping, k_scale=None, norm_weight=None, norm_bias=None, eps=1e-6, cos=None, sin=None,
+                         positions=None, rope_layout="half", rope_offset=0, hadamard=True, scale_format="amax"):
+    """The index keys of T new tokens through norm, RoPE and the Hadamard rotation into the paged index-key cache, in place, with one
+    launch (csrc/mla_indexer_append_gfx950.hip behind aule_mla_indexer_rows_ex, whose descriptor comment in include/aule.h is the
+    contract; aule.mla_indexer_k_append documents the arguments).  Returns None.  No device->host synchronisation; captures into a
+    graph.  All argument errors are ValueErrors raised before the device is touched; CPU tensors are an AuleError."""
+    if torch.is_tensor(k) and k.dim() == 2:
+        k = k[:, None]
+    if torch.is_tensor(k_cache) and k_cache.dim() == 4 and k_cache.shape[2] == 1:
+        k_cache = k_cache[:, :, 0]
+    if not torch.is_tensor(k) or not torch.is_tensor(k_cache) or k.dim() != 3 or k_cache.dim() != 3:
+        raise ValueError("expected k [T,128] (or [T,1,128]) and k_cache [num_blocks, block_size, 128] (or [num_blocks, block_size, 1, 128])")
+    if k.shape[1] != 1:
+        raise ValueError(f"the index key cache holds one key row per token for all heads: k has {k.shape[1]} heads")
+    if k_cache.shape[-1] != 128:
+        raise ValueError(f"the index head width must be 128: cache={k_cache.shape[-1]}")
+    strides = _indexer_rows_args("k", k, norm_weight, norm_bias, eps, cos, sin, positions, rope_layout, rope_offset, hadamard)
+    T = k.shape[0]
+    fp8 = k_cache.dtype != k.dtype
+    if fp8 and k_cache.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"k_cache must have k's dtype ({k.dtype}) or be torch.float8_e4m3fn codes with k_scale, got {k_cache.dtype}")
+    if fp8 and k_scale is None:
+        raise ValueError("a float8_e4m3fn k_cache needs k_scale, the per-row scales [num_blocks, block_size] fp32 the append writes")
+    if not fp8 and k_scale is not None:
+        raise ValueError("k_scale applies to a float8_e4m3fn cache only; a 16-bit cache holds the values themselves")
+    if fp8 and (not torch.is_tensor(k_scale) or k_scale.dtype != torch.float32 or tuple(k_scale.shape) != tuple(k_cache.shape[:2])
+                or not k_scale.is_contiguous()):
+        raise ValueError(f"k_scale must be a contiguous fp32 tensor [num_blocks, block_size] = {list(k_cache.shape[:2])} (one scale per cache row)")
+    if scale_format not in _INDEXER_SCALE_FORMATS:
+        raise ValueError(f"unknown scale_format {scale_format!r} ('amax' or 'ue8m0')")
+    if not k_cache.is_contiguous():
+        raise ValueError("k_cache must be contiguous: the append writes in place and cannot copy it")
+    num_blocks, block_size, _ = k_cache.shape
+    if block_size == 0 or num_blocks * block_size > 2 ** 31 - 1:
+        raise ValueError(f"the cache must hold at most 2^31 - 1 rows of a positive block size, got {num_blocks} * {block_size}")
+    if not torch.is_tensor(slot_mapping) or slot_mapping.dim() != 1 or slot_mapping.shape[0] != T or slot_mapping.dtype.is_floating_point \
+            or slot_mapping.dtype == torch.bool:
+        raise ValueError(f"slot_mapping must be an integer tensor of shape [{T}]")
+    if not k.is_cuda:
+        raise _capi.AuleError("aule (HIP build): the MLA indexer key append needs ROCm device tensors; there is no CPU fallback")
+    _same_device("MLA indexer key append", k, k_cache, *[t for t in (k_scale, norm_weight, norm_bias) if t is not None])
+    if T == 0 or num_blocks == 0:
+        return None
+    slots = slot_mapping.to(device=k.device, dtype=torch.int64).contiguous()
+    d = _capi.MlaIndexerRowsDesc()
+    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3 if fp8 else _capi.KV_CACHE_SAME
+    d.scale_format = _INDEXER_SCALE_FORMATS[scale_format]
+    d.num_blocks, d.block_size = num_blocks, block_size
+    d.k_cache, d.slot_mapping = k_cache.data_ptr(), slots.data_ptr()
+    d.k_scale = k_scale.data_ptr() if fp8 else None
+    _indexer_rows_launch(k, strides, d, [slots], norm_weight, norm_bias, eps, cos, sin, positions, rope_layout, rope_offset, hadamard)
+    return None
+
+
+def mla_indexer_q_rotate(q, cos=None, sin=None, positions=None, rope_layout="half", rope_offset=0, hadamard=True, out=None):
+    """The index queries [T, H, 128] through RoPE and the Hadamard rotation, with one launch (csrc/mla_indexer_append_gfx950.hip behind
+    aule_mla_indexer_rows_ex; aule.mla_indexer_q_rotate documents the arguments).  Returns out (a new contiguous tensor, or the one
+    given, which may be q).  No device->host synchronisation; captures into a graph.  All argument errors are ValueErrors raised
+    before the device is touched; CPU tensors are an AuleError."""
+    if not torch.is_tensor(q) or q.dim() != 3:
+        raise ValueError("expected q [T,H,128]")
+    strides = _indexer_rows_args("q", q, None, None, 0.0, cos, sin, positions, rope_layout, rope_offset, hadamard)
+    if out is not None:
+        if not torch.is_tensor(out) or out.shape != q.shape or out.dtype != q.dtype:
+            raise ValueError(f"out must be a tensor of q's shape {tuple(q.shape)} and dtype {q.dtype} (q itself runs in place)")
+        if torch.is_grad_enabled() and out.requires_grad:
+            raise ValueError("the MLA indexer has no backward: out must not require grad")
+        out_strides = _indexer_rows_strides("out", out)
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): the MLA indexer query rotation needs ROCm device tensors; there is no CPU fallback")
+    if out is None:
+        out = torch.empty(q.shape, device=q.device, dtype=q.dtype)
+        out_strides = (q.shape[1] * 128, 128)
+    _same_device("MLA indexer query rotation", q, out)
+    if q.shape[0] == 0 or q.shape[1] == 0:
+        return out
+    d = _capi.MlaIndexerRowsDesc()
+    d.cache_dtype = _capi.KV_CACHE_SAME
+    d.out = out.data_ptr()
+    d.out_token_stride, d.out_head_stride = out_strides
+    _indexer_rows_launch(q, strides, d, [], None, None, 0.0, cos, sin, positions, rope_layout, rope_offset, hadamard)
+    return out
+
+
 def quantize_mla_cache_fp8(kv_cache):
     """(codes, scale) for the FP8 paged MLA: float8_e4m3fn codes of a [num_blocks, block_size, 576] (or [..., 1, 576]) latent cache and
     ONE scale, a [1] fp32 tensor on the cache's device = amax / 448 (1.0 for an all-zero cache), with kv_cache ~= scale * codes.

@@ -187,6 +187,23 @@ static_assert(sizeof(aule_mla_kv_append_ds_desc) == 120 && offsetof(aule_mla_kv_
                   offsetof(aule_mla_kv_append_ds_desc, slot_mapping) == 88 && offsetof(aule_mla_kv_append_ds_desc, cos) == 96 &&
                   offsetof(aule_mla_kv_append_ds_desc, sin) == 104 && offsetof(aule_mla_kv_append_ds_desc, positions) == 112,
               "aule_mla_kv_append_ds_desc layout is part of the ABI");
+static_assert(sizeof(aule_mla_indexer_rows_desc) == 184 && offsetof(aule_mla_indexer_rows_desc, dtype) == 4 &&
+                  offsetof(aule_mla_indexer_rows_desc, cache_dtype) == 8 && offsetof(aule_mla_indexer_rows_desc, scale_format) == 12 &&
+                  offsetof(aule_mla_indexer_rows_desc, rope_layout) == 16 && offsetof(aule_mla_indexer_rows_desc, rope_offset) == 20 &&
+                  offsetof(aule_mla_indexer_rows_desc, flags) == 24 && offsetof(aule_mla_indexer_rows_desc, eps) == 28 &&
+                  offsetof(aule_mla_indexer_rows_desc, total_tokens) == 32 && offsetof(aule_mla_indexer_rows_desc, heads) == 36 &&
+                  offsetof(aule_mla_indexer_rows_desc, num_blocks) == 40 && offsetof(aule_mla_indexer_rows_desc, block_size) == 44 &&
+                  offsetof(aule_mla_indexer_rows_desc, table_len) == 48 && offsetof(aule_mla_indexer_rows_desc, table_pitch) == 52 &&
+                  offsetof(aule_mla_indexer_rows_desc, device) == 56 && offsetof(aule_mla_indexer_rows_desc, reserved) == 60 &&
+                  offsetof(aule_mla_indexer_rows_desc, x_token_stride) == 64 && offsetof(aule_mla_indexer_rows_desc, x_head_stride) == 72 &&
+                  offsetof(aule_mla_indexer_rows_desc, out_token_stride) == 80 && offsetof(aule_mla_indexer_rows_desc, out_head_stride) == 88 &&
+                  offsetof(aule_mla_indexer_rows_desc, stream) == 96 && offsetof(aule_mla_indexer_rows_desc, x) == 104 &&
+                  offsetof(aule_mla_indexer_rows_desc, out) == 112 && offsetof(aule_mla_indexer_rows_desc, k_cache) == 120 &&
+                  offsetof(aule_mla_indexer_rows_desc, k_scale) == 128 && offsetof(aule_mla_indexer_rows_desc, slot_mapping) == 136 &&
+                  offsetof(aule_mla_indexer_rows_desc, norm_weight) == 144 && offsetof(aule_mla_indexer_rows_desc, norm_bias) == 152 &&
+                  offsetof(aule_mla_indexer_rows_desc, cos) == 160 && offsetof(aule_mla_indexer_rows_desc, sin) == 168 &&
+                  offsetof(aule_mla_indexer_rows_desc, positions) == 176,
+              "aule_mla_indexer_rows_desc layout is part of the ABI");
 #define AULE_SAME_OFFSET(field) (offsetof(aule_paged_cascade_desc, field) == offsetof(aule_paged_prefill_desc, field))
 static_assert(AULE_SAME_OFFSET(struct_size) && AULE_SAME_OFFSET(dtype) && AULE_SAME_OFFSET(cache_dtype) && AULE_SAME_OFFSET(batch) && AULE_SAME_OFFSET(heads_q) &&
                   AULE_SAME_OFFSET(heads_kv) && AULE_SAME_OFFSET(head_dim) && AULE_SAME_OFFSET(block_size) && AULE_SAME_OFFSET(max_blocks) &&
@@ -2800,6 +2817,85 @@ int32_t aule_mla_kv_append_ds_ex(const aule_mla_kv_append_ds_desc* d) {
     fill_mla_kv_append_args(&twin, a);
     DeviceGuard g(twin.device);
     return launched(what, aule_hip::launch_mla_kv_append_ds(a, (hipStream_t)twin.stream));
+}
+
+static bool mla_indexer_rows_nothing_to_do(const aule_mla_indexer_rows_desc* d) { return d->total_tokens == 0; }
+
+// 0 fine, else the reason the descriptor is refused (host logic only: no pointer is dereferenced; its only reader is the launch
+// entry, so the pointer rules of a call that has something to do are stated here too)
+static const char* mla_indexer_rows_error(const aule_mla_indexer_rows_desc* d, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_mla_indexer_rows_desc)) return kBadDescriptor;
+    if (!is_16_bit(d->dtype)) return "dtype (of x / out) must be fp16 or bf16";
+    if (const char* e = cache_dtype_error(d->cache_dtype)) return e;
+    if (d->scale_format != AULE_INDEXER_SCALE_AMAX && d->scale_format != AULE_INDEXER_SCALE_UE8M0)
+        return reasonf(why, "unknown scale_format %d (AULE_INDEXER_SCALE_AMAX or AULE_INDEXER_SCALE_UE8M0)", d->scale_format);
+    if (d->rope_layout != AULE_ROPE_HALF && d->rope_layout != AULE_ROPE_INTERLEAVED)
+        return reasonf(why, "unknown rope_layout %d (AULE_ROPE_HALF or AULE_ROPE_INTERLEAVED)", d->rope_layout);
+    if (d->rope_offset != 0 && d->rope_offset != 64) return reasonf(why, "rope_offset (%u) must be 0 or 64", d->rope_offset);
+    if ((d->flags & ~(AULE_INDEXER_ROWS_NORM | AULE_INDEXER_ROWS_HADAMARD)) != 0 || d->reserved != 0) return "unknown flags, or reserved is not 0";
+    const bool norm = (d->flags & AULE_INDEXER_ROWS_NORM) != 0;
+    if (norm && !(d->eps >= 0.0f)) return "eps must be >= 0";
+    if (d->heads == 0) return "heads must be positive";
+    if ((d->out != nullptr) == (d->k_cache != nullptr) && !mla_indexer_rows_nothing_to_do(d)) return "exactly one of out and k_cache must be given";
+    const bool cache = d->k_cache != nullptr, fp8 = d->cache_dtype == AULE_KV_CACHE_FP8_E4M3;
+    if (cache && d->heads != 1) return reasonf(why, "a cache destination takes one head per token, got heads = %u", d->heads);
+    if (cache && d->block_size == 0) return "block_size must be positive";
+    if (cache && (uint64_t)d->num_blocks * d->block_size > 0x7fffffffull) return "num_blocks * block_size must stay within 2^31 - 1";
+    if (!cache && fp8) return "cache_dtype AULE_KV_CACHE_FP8_E4M3 needs k_cache: the dense output has the input's dtype";
+    if ((uint64_t)d->total_tokens * d->heads > 0x7fffffffull) return "total_tokens * heads must stay within 2^31 - 1";
+    if (d->x_token_stride % 8 != 0 || (d->heads > 1 && (d->x_head_stride < 128 || d->x_head_stride % 8 != 0)))
+        return "the strides of x must be multiples of 8 elements (16-byte loads), the head stride at least a row";
+    if (!cache && (d->out_token_stride % 8 != 0 || (d->heads > 1 && (d->out_head_stride < 128 || d->out_head_stride % 8 != 0))))
+        return "the strides of out must be multiples of 8 elements (16-byte stores), the head stride at least a row";
+    const bool any_rope = d->cos || d->sin || d->positions || d->table_len || d->table_pitch;
+    const bool all_rope = d->cos && d->sin && d->positions && d->table_len;
+    if (any_rope && !all_rope) return "RoPE group only partly given (cos, sin, positions and table_len go together)";
+    if (all_rope && d->table_pitch != 0 && (d->table_pitch < 32 || d->table_pitch % 4 != 0)) return "table_pitch must be 0 or a multiple of 4 that is >= 32";
+    if (norm != (d->norm_weight != nullptr)) return "norm_weight goes with AULE_INDEXER_ROWS_NORM, and only with it";
+    if (!norm && d->norm_bias) return "norm_bias without AULE_INDEXER_ROWS_NORM";
+    if (mla_indexer_rows_nothing_to_do(d)) return nullptr;
+    if (!d->x) return "null tensor pointer";
+    if (cache && !d->slot_mapping) return "null slot_mapping";
+    if (fp8 && !d->k_scale) return "null k_scale (one fp32 value per cache row, [num_blocks, block_size])";
+    if (!fp8 && d->k_scale) return "k_scale applies to an FP8 cache only; a 16-bit cache holds the values themselves";
+    if ((reinterpret_cast<uintptr_t>(d->k_scale) & 3) != 0) return "k_scale must be 4-byte aligned";
+    if (misaligned(d->x) || misaligned(d->out) || misaligned(d->k_cache) || misaligned(d->norm_weight) || misaligned(d->norm_bias) ||
+        misaligned(d->cos) || misaligned(d->sin))
+        return "x, out, k_cache, the norm vectors and the tables must be 16-byte aligned";
+    return nullptr;
+}
+
+int32_t aule_mla_indexer_rows_ex(const aule_mla_indexer_rows_desc* d) {
+    RoctxRange range("aule.mla_indexer_rows");
+    const char* what = "MLA indexer rows";
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_indexer_rows_error(d, text)) {
+        set_error("%s failed: %s", what, why);
+        return -3;
+    }
+    if (mla_indexer_rows_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaIndexerRowsArgs a;
+    a.x = d->x; a.out = d->out; a.k_cache = d->k_cache;
+    a.slot_mapping = reinterpret_cast<const long long*>(d->slot_mapping);
+    a.T = (int)d->total_tokens; a.heads = (int)d->heads;
+    a.x_token_stride = d->x_token_stride; a.x_head_stride = d->x_head_stride;
+    a.out_token_stride = d->out_token_stride; a.out_head_stride = d->out_head_stride;
+    a.num_blocks = (long long)d->num_blocks; a.block_size = (int)d->block_size;
+    a.dtype = d->dtype;
+    if (d->cache_dtype == AULE_KV_CACHE_FP8_E4M3) {
+        a.cache_kind = aule_hip::kCacheFp8E4M3;
+        a.k_scale = d->k_scale;
+    }
+    a.scale_format = d->scale_format;
+    a.norm_weight = d->norm_weight; a.norm_bias = d->norm_bias; a.eps = d->eps;
+    a.hadamard = (d->flags & AULE_INDEXER_ROWS_HADAMARD) != 0;
+    a.cos = d->cos; a.sin = d->sin; a.positions = reinterpret_cast<const long long*>(d->positions);
+    a.table_len = (long long)d->table_len; a.table_pitch = (int)d->table_pitch;
+    a.rope_layout = d->rope_layout; a.rope_offset = (int)d->rope_offset;
+    DeviceGuard g(d->device);
+    return launched(what, aule_hip::launch_mla_indexer_rows(a, (hipStream_t)d->stream));
 }
 
 uint64_t aule_attention_backward_workspace_size(const aule_attn_bwd_desc* d) {

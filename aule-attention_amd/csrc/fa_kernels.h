@@ -239,6 +239,42 @@ int launch_mla_kv_append(const MlaKvAppendArgs& a, hipStream_t stream);   // -1:
 // kv_cache is [num_blocks * block_size][656] bytes; dtype kBF16, no kv_scale.
 int launch_mla_kv_append_ds(const MlaKvAppendArgs& a, hipStream_t stream);   // -1: unsupported arguments
 
+// The write side of the sparse MLA's indexer (mla_indexer_append_gfx950.hip, where the row transform is stated): rows of 128 16-bit
+// elements x[t, h, :] (free token / head strides, elements) through an optional LayerNorm (norm_weight != null; norm_bias may be
+// null), an optional rotation of the 64 elements from rope_offset (cos != null; rope_layout 0 = pairs (p, p + 32), 1 = (2p, 2p + 1);
+// tables [table_len, 32] fp32, row positions[t]) and an optional 128-point Hadamard rotation, rounded once to the input's type, then
+// stored to exactly one of: out[t, h, :] (dense; may be x), or row slot_mapping[t] of k_cache [num_blocks * block_size, 128] (heads = 1)
+// as the bits (kCache16) or as e4m3fn codes with the row's scale in k_scale[slot] (kCacheFp8E4M3; scale_format 0 = amax / 448,
+// 1 = the power of two at or above it).  A slot outside the cache, or with rotation a position outside the table, skips the token.
+// The caller guarantees 16-byte aligned pointers, strides % 8 == 0, table_pitch % 4 == 0.
+struct MlaIndexerRowsArgs {
+    const void* x;
+    void* out = nullptr;
+    void* k_cache = nullptr;
+    float* k_scale = nullptr;               // kCacheFp8E4M3 only: [num_blocks * block_size] fp32
+    const long long* slot_mapping = nullptr;   // [T] int64 (cache destination)
+    int T, heads;
+    long long x_token_stride, x_head_stride;
+    long long out_token_stride = 0, out_head_stride = 0;   // dense destination
+    long long num_blocks = 0;
+    int block_size = 0;
+    int dtype;                              // of x / out: kF16 or kBF16
+    int cache_kind = kCache16;
+    int scale_format = 0;
+    const float* norm_weight = nullptr;     // [128] fp32
+    const float* norm_bias = nullptr;
+    float eps = 0.f;
+    bool hadamard = false;
+    const float* cos = nullptr;             // [table_len, 32] fp32, table_pitch floats per row (0 = 32)
+    const float* sin = nullptr;
+    const long long* positions = nullptr;   // [T] int64
+    long long table_len = 0;
+    int table_pitch = 0;
+    int rope_layout = 0;
+    int rope_offset = 0;                    // 0 or 64
+};
+int launch_mla_indexer_rows(const MlaIndexerRowsArgs& a, hipStream_t stream);   // -1: unsupported arguments
+
 // Paged prefill (fa_fwd_paged_prefill_gfx950.hip): ragged per-sequence queries against the paged cache, one launch, no workspace.
 //   q [T, Hq, D] 16-bit, the new tokens of all sequences packed along the first axis (q_token_stride elements between tokens, the
 //   heads of a token contiguous), out [T, Hq, D] contiguous, lse [T, Hq] fp32 or null; caches, table, lengths and scales as PagedArgs;

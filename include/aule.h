@@ -1597,6 +1597,73 @@ typedef struct aule_mla_kv_append_ds_desc {
 /* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
 int32_t aule_mla_kv_append_ds_ex(const aule_mla_kv_append_ds_desc* desc);
 
+/* The write side of the sparse MLA's indexer (additive; what aule_mla_indexer_logits_ex reads).  One launch transforms rows of 128    */
+/* 16-bit elements x[t, h, :] (fp16 / bf16; token and head strides free multiples of 8 elements: slices of a fused projection are      */
+/* read in place) and stores them densely (the index queries) or into the paged index-key cache (the index key of each new token).   */
+/* Per row, loaded and carried in fp32 through every enabled stage:                                                                    */
+/*   1. norm (AULE_INDEXER_ROWS_NORM): mu = mean(x); var = mean((x - mu)^2) (biased); x <- (x - mu) / sqrt(var + eps) * w + b, with    */
+/*      norm_weight w and norm_bias b [128] fp32; norm_bias NULL is zero.                                                              */
+/*   2. RoPE (all of cos, sin, positions given with table_len > 0; all NULL with table_len = table_pitch = 0: none): the 64 elements   */
+/*      [rope_offset, rope_offset + 64), rope_offset 0 or 64 (the indexer keeps the rotary half first, the latent keeps it last), by   */
+/*      table row positions[t] of cos / sin [table_len, 32] fp32 with table_pitch floats per row (0 = 32); every head of a token uses  */
+/*      the same row.  AULE_ROPE_HALF pairs (p, p + 32), AULE_ROPE_INTERLEAVED pairs (2p, 2p + 1), both relative to rope_offset;       */
+/*      aule_rope_ex's arithmetic.                                                                                                     */
+/*   3. Hadamard (AULE_INDEXER_ROWS_HADAMARD): y[i] = 2^-3.5 * sum_j (-1)^popcount(i & j) * x[j], the Sylvester H_128 in natural order */
+/*      scaled by 128^-0.5, fp32 sums.                                                                                                 */
+/*   4. The row is rounded ONCE to the input's 16-bit type: r.                                                                         */
+/*   5. Exactly one destination.  out given: out[t, h, :] = r, with its own token / head strides; out may be x with x's strides (in    */
+/*      place).  k_cache given (heads must be 1): row slot_mapping[t] of k_cache viewed as [num_blocks * block_size, 128] --            */
+/*      AULE_KV_CACHE_SAME: the bits of r; k_scale NULL.  AULE_KV_CACHE_FP8_E4M3: amax = max |r|; s0 = amax > 0 ? amax / 448 : 1       */
+/*      (correctly rounded fp32 division); scale = s0 (AULE_INDEXER_SCALE_AMAX) or the power of two >= s0 (AULE_INDEXER_SCALE_UE8M0:   */
+/*      bits(scale) = max((bits(s0) + 0x007FFFFF) & 0x7F800000, 0x00800000)); code = cast_e4m3fn(clamp(r / scale, -448, 448)) by the   */
+/*      rules of aule_kv_cache_append_ex; k_scale[slot] = scale, k_scale [num_blocks * block_size] fp32.                               */
+/* A slot that is negative (padding) or >= num_blocks * block_size skips the token ENTIRELY, and so does, with RoPE, a position         */
+/* outside [0, table_len): nothing of its row and nothing of its scale is written.  Two tokens of one call with the same slot: which   */
+/* of them the cache holds afterwards is unspecified.                                                                                  */
+/* Alignment: x, out, k_cache, norm_weight, norm_bias, cos and sin 16-byte aligned; k_scale 4-byte; table_pitch % 4 == 0.              */
+/* total_tokens * heads and num_blocks * block_size at most 2^31 - 1.  Asynchronous on `stream`; device pointers; captures into a      */
+/* hipGraph (no allocation, no synchronisation).  The descriptor is checked before the device is needed: -3 for a refused one and 0   */
+/* for total_tokens = 0 are answered without aule_init().                                                                              */
+#define AULE_INDEXER_SCALE_AMAX 0
+#define AULE_INDEXER_SCALE_UE8M0 1
+#define AULE_INDEXER_ROWS_NORM 1u
+#define AULE_INDEXER_ROWS_HADAMARD 2u
+typedef struct aule_mla_indexer_rows_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_indexer_rows_desc) = 184 */
+    int32_t dtype;             /* offset 4; of x / out: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
+    int32_t cache_dtype;       /* offset 8; AULE_KV_CACHE_SAME or AULE_KV_CACHE_FP8_E4M3 (AULE_KV_CACHE_SAME with out) */
+    int32_t scale_format;      /* offset 12; AULE_INDEXER_SCALE_AMAX or _UE8M0 (read for an FP8 cache only, but always checked) */
+    int32_t rope_layout;       /* offset 16; AULE_ROPE_HALF or AULE_ROPE_INTERLEAVED (read with RoPE only, but always checked) */
+    uint32_t rope_offset;      /* offset 20; 0 or 64 */
+    uint32_t flags;            /* offset 24; AULE_INDEXER_ROWS_NORM | AULE_INDEXER_ROWS_HADAMARD */
+    float eps;                 /* offset 28; of the norm */
+    uint32_t total_tokens;     /* offset 32; 0: returns 0 without a launch */
+    uint32_t heads;            /* offset 36; >= 1; 1 with k_cache */
+    uint32_t num_blocks;       /* offset 40; with k_cache */
+    uint32_t block_size;       /* offset 44; with k_cache: any value > 0 */
+    uint32_t table_len;        /* offset 48; rows of cos / sin (0 without RoPE) */
+    uint32_t table_pitch;      /* offset 52; floats per table row; 0 = 32 */
+    int32_t device;            /* offset 56; HIP device ordinal, -1 = current */
+    uint32_t reserved;         /* offset 60; 0 */
+    int64_t x_token_stride;    /* offset 64; elements, a multiple of 8 */
+    int64_t x_head_stride;     /* offset 72; elements, >= 128, a multiple of 8 (read with heads > 1) */
+    int64_t out_token_stride;  /* offset 80; with out */
+    int64_t out_head_stride;   /* offset 88; with out */
+    void* stream;              /* offset 96; hipStream_t */
+    const void* x;             /* offset 104; [total_tokens, heads, 128] */
+    void* out;                 /* offset 112; [total_tokens, heads, 128], or NULL */
+    void* k_cache;             /* offset 120; [num_blocks, block_size, 128], contiguous, or NULL */
+    float* k_scale;            /* offset 128; [num_blocks, block_size] fp32 (AULE_KV_CACHE_FP8_E4M3), else NULL */
+    const int64_t* slot_mapping;   /* offset 136; [total_tokens] (with k_cache), else NULL */
+    const float* norm_weight;  /* offset 144; [128] fp32 (AULE_INDEXER_ROWS_NORM), else NULL */
+    const float* norm_bias;    /* offset 152; [128] fp32 or NULL */
+    const float* cos;          /* offset 160; [table_len, 32] fp32, or NULL */
+    const float* sin;          /* offset 168 */
+    const int64_t* positions;  /* offset 176; [total_tokens], or NULL */
+} aule_mla_indexer_rows_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_mla_indexer_rows_ex(const aule_mla_indexer_rows_desc* desc);
+
 /* Attention with the query rotation fused into the kernel (additive; inference path).  Replaces the Q half of       */
 /* python/aule/triton_flash.py:112-131 (the reference rotates Q in its forward prologue); K must arrive rotated --   */
 /* once per key by aule_rope_ex(), e.g. when it is appended to a KV cache -- because the tiled kernel re-reads every */
