@@ -510,13 +510,36 @@ def mla_indexer_logits(q, weights, k_cache, block_tables, context_lens, cu_seqle
     runs are bit-identical.  All argument errors are ValueErrors raised before the device is touched; CPU tensors that pass
     them are an AuleError; tensors that require grad are refused.
     The append kernel for the index keys is mla_indexer_k_append, the queries' rotation mla_indexer_q_rotate.
-    Out of scope: FP8 queries and FP8 MFMAs, a fused streaming top-k that never writes [T, W], H > 64, a backward."""
+    FP8 queries and FP8 MFMAs are mla_indexer_logits_fp8mma's.
+    Out of scope: a fused streaming top-k that never writes [T, W], H > 64, a backward."""
     try:
         import torch  # noqa: F401
     except ImportError as e:
         raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
     from ._torch import mla_indexer_logits as impl
     return impl(q, weights, k_cache, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, k_scale=k_scale)
+
+
+def mla_indexer_logits_fp8mma(q, weights, k_cache, k_scale, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, q_scale=None):
+    """mla_indexer_logits for callers whose index queries are FP8 as well, the products on FP8 matrix instructions (opt-in; the
+    contract is aule_mla_indexer_logits_fp8mma_desc in include/aule.h):
+
+        logits[t, s] = k_scale[row(s)] * sum_h (weights[t, h] * q_scale[t, h]) * relu(sum_d float(q[t, h, d]) * float(k[row(s), d]))
+
+        q        [T, H, 128] torch.float8_e4m3fn codes, 1 <= H <= 64, read in place: the token stride is free (a multiple of 16
+                 bytes, at least H * 128: a slice of a wider tensor keeps its stride)
+        q_scale  None (= 1) or [T, H] fp32, contiguous: the scale of each (token, head) row of codes -- what
+                 quantize_rows_fp8(q16) returns second, reshaped to [T, H].  It multiplies the weight, never an element
+        k_cache, k_scale  the FP8 index-key cache of mla_indexer_logits: float8_e4m3fn codes and [num_blocks, block_size] fp32
+
+    Everything else -- weights, the tables, the visibility rule, the -inf columns, the rows never written, determinism, capture, the
+    errors -- is mla_indexer_logits'; the result feeds mla_indexer_topk unchanged.  aule.mla_indexer does not route here."""
+    try:
+        import torch  # noqa: F401
+    except ImportError as e:
+        raise AuleError("aule (HIP build) needs PyTorch-ROCm for device memory") from e
+    from ._torch import mla_indexer_logits_fp8mma as impl
+    return impl(q, weights, k_cache, k_scale, block_tables, context_lens, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, q_scale=q_scale)
 
 
 def mla_indexer_topk(logits, topk, block_tables, context_lens, block_size, cu_seqlens_q=None, max_seqlen_q=None, output="slots"):
@@ -1172,7 +1195,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_topk", "mla_indexer_k_append", "mla_indexer_q_rotate", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "quantize_mla_cache_fp8_ds", "dequantize_mla_cache_fp8_ds", "flash_attention_varlen", "flash_attention_varlen_d256", "flash_attention_varlen_d256_softcap", "flash_attention_paged_d256_softcap", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
+__all__ = ["flash_attention", "attention", "flash_attention_paged_amd", "flash_attention_paged", "flash_attention_paged_query", "flash_attention_paged_prefill", "flash_attention_paged_prefill_fp8mma", "quantize_rows_fp8", "flash_attention_paged_cascade", "flash_attention_paged_d256", "flash_attention_mla_paged", "flash_attention_mla_paged_fp8", "flash_attention_mla_paged_fp8mma", "flash_attention_mla_paged_tree", "flash_attention_mla_sparse", "mla_indexer_logits", "mla_indexer_logits_fp8mma", "mla_indexer_topk", "mla_indexer_k_append", "mla_indexer_q_rotate", "mla_indexer", "quantize_indexer_cache_fp8", "mla_kv_append", "quantize_mla_cache_fp8", "quantize_mla_cache_fp8_ds", "dequantize_mla_cache_fp8_ds", "flash_attention_varlen", "flash_attention_varlen_d256", "flash_attention_varlen_d256_softcap", "flash_attention_paged_d256_softcap", "flash_attention_varlen_sinks", "flash_attention_paged_prefill_sinks", "flash_attention_paged_query_sinks", "flash_attention_paged_query_tree", "flash_attention_paged_prefill_tree", "tree_mask_from_parents", "flash_attention_mla_prefill", "flash_attention_mla_varlen", "merge_attention_states", "quantize_kv_cache_fp8", "paged_kv_append", "paged_slot_mapping",
            "flash_attention_rope", "precompute_rope_frequencies", "apply_rope_separate", "AuleError", "scaled_dot_product_attention", "install", "uninstall",
            "get_available_backends", "get_backend_errors", "get_backend_info", "print_backend_info", "Aule", "GpuTensor", "set_verbose",
            "__version__"]

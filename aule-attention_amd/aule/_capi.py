@@ -271,6 +271,13 @@ class MlaIndexerLogitsDesc(ctypes.Structure):
     ]
 
 
+class MlaIndexerLogitsFp8mmaDesc(ctypes.Structure):
+    """struct aule_mla_indexer_logits_fp8mma_desc (include/aule.h): the index logits with e4m3 queries and FP8 matrix products --
+    the logits descriptor with `reserved` for `dtype`, q's stride in bytes, and q_scale behind it."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32)] + MlaIndexerLogitsDesc._fields_[2:] + [
+        ("q_scale", ctypes.c_void_p)]
+
+
 INDEXER_SLOTS, INDEXER_POSITIONS = 0, 1
 
 
@@ -691,6 +698,7 @@ SIGNATURES = [
     ("aule_attention_mla_sparse_ds_workspace_size", ctypes.c_uint64, [ctypes.POINTER(MlaSparseDsDesc)]),
     ("aule_mla_kv_append_ds_ex", _I32, [ctypes.POINTER(MlaKvAppendDsDesc)]),
     ("aule_mla_indexer_logits_ex", _I32, [ctypes.POINTER(MlaIndexerLogitsDesc)]),
+    ("aule_mla_indexer_logits_fp8mma_ex", _I32, [ctypes.POINTER(MlaIndexerLogitsFp8mmaDesc)]),
     ("aule_mla_indexer_topk_ex", _I32, [ctypes.POINTER(MlaIndexerTopkDesc)]),
     ("aule_mla_indexer_rows_ex", _I32, [ctypes.POINTER(MlaIndexerRowsDesc)]),
     ("aule_mla_kv_append_ex", _I32, [ctypes.POINTER(MlaKvAppendDesc)]),
@@ -736,6 +744,7 @@ SIGNATURES = [
     ("aule_hip_debug_paged_d256_plan", _I32, [ctypes.POINTER(PagedD256Desc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_paged_d256_launch_nsplit", _I32, [ctypes.POINTER(PagedD256Desc), _I32]),
     ("aule_hip_debug_mla_indexer_plan", _I32, [ctypes.POINTER(MlaIndexerLogitsDesc), ctypes.POINTER(_I32), _I32]),
+    ("aule_hip_debug_mla_indexer_fp8mma_plan", _I32, [ctypes.POINTER(MlaIndexerLogitsFp8mmaDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_mla_prefill_backward_plan", _I32, [ctypes.POINTER(MlaPrefillBwdDesc), ctypes.POINTER(_I32), _I32]),
     ("aule_hip_debug_last_backward_route", _I32, []),
     ("aule_hip_debug_backward_route", _I32, [ctypes.POINTER(AttnBwdDesc)]),

@@ -1818,6 +1818,70 @@ def mla_indexer_logits(q, weights, k_cache, block_tables, context_lens, cu_seqle
     return logits
 
 
+def mla_indexer_logits_fp8mma(q, weights, k_cache, k_scale, block_tables, context_lens, cu_seqlens_q=None, max_seqlen_q=None, q_scale=None):
+    """The index logits with e4m3 queries and FP8 matrix products; csrc/fa_mla_indexer_fp8mma_gfx950.hip behind
+    aule_mla_indexer_logits_fp8mma_ex (aule.mla_indexer_logits_fp8mma documents the arguments).  q is read in place: its token stride
+    goes to the kernel in bytes.  All argument errors are ValueErrors raised before the device is touched."""
+    if torch.is_tensor(k_cache) and k_cache.dim() == 4 and k_cache.shape[2] == 1:
+        k_cache = k_cache[:, :, 0]
+    if not torch.is_tensor(q) or not torch.is_tensor(k_cache) or q.dim() != 3 or k_cache.dim() != 3:
+        raise ValueError("expected q [T,H,128] and k_cache [num_blocks, block_size, 128] (or [num_blocks, block_size, 1, 128])")
+    if q.shape[-1] != 128 or k_cache.shape[-1] != 128:
+        raise ValueError(f"the index head width must be 128: query={q.shape[-1]}, cache={k_cache.shape[-1]}")
+    T, H, _ = q.shape
+    if q.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"mla_indexer_logits_fp8mma needs torch.float8_e4m3fn queries (quantize_rows_fp8), got {q.dtype}; 16-bit queries are mla_indexer_logits'")
+    if not 1 <= H <= MLA_INDEXER_MAX_HEADS:
+        raise ValueError(f"the indexer takes 1 .. {MLA_INDEXER_MAX_HEADS} index heads, got {H}")
+    if k_cache.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"mla_indexer_logits_fp8mma needs a torch.float8_e4m3fn k_cache (quantize_indexer_cache_fp8), got {k_cache.dtype}")
+    if k_scale is None:
+        raise ValueError("a float8_e4m3fn k_cache needs k_scale, the per-row scales [num_blocks, block_size] fp32 (quantize_indexer_cache_fp8)")
+    if not torch.is_tensor(k_scale) or k_scale.dtype != torch.float32 or tuple(k_scale.shape) != tuple(k_cache.shape[:2]) or not k_scale.is_contiguous():
+        raise ValueError(f"k_scale must be a contiguous fp32 tensor [num_blocks, block_size] = {list(k_cache.shape[:2])} (one scale per cache row)")
+    for name, t in (("weights", weights),) + ((("q_scale", q_scale),) if q_scale is not None else ()):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (T, H) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous fp32 tensor [T, H] = [{T}, {H}]")
+    if not k_cache.is_contiguous():
+        raise ValueError("k_cache must be contiguous")
+    if k_cache.shape[0] == 0 or k_cache.shape[1] == 0 or k_cache.shape[0] * k_cache.shape[1] > 2 ** 31 - 1:
+        raise ValueError(f"the cache must hold 1 .. 2^31 - 1 rows (num_blocks * block_size), got {k_cache.shape[0]} * {k_cache.shape[1]}")
+    B, max_sq = _indexer_tables(T, block_tables, context_lens, cu_seqlens_q, max_seqlen_q, k_cache.shape[1])
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (weights, k_scale) + ((q_scale,) if q_scale is not None else ())):
+        raise ValueError("the MLA indexer has no backward: detach the inputs or call it under torch.no_grad()")
+    if T > 1 and (q.stride(2) != 1 or q.stride(1) != 128) or T <= 1 and not q.is_contiguous():
+        q = q.contiguous()
+    q_stride = q.stride(0) if T > 1 else H * 128
+    if q_stride < H * 128 or q_stride % 16 != 0 or q.storage_offset() % 16 != 0:
+        raise ValueError(f"q's token stride ({q_stride}) and storage offset ({q.storage_offset()}) must be multiples of 16 bytes and the "
+                         f"stride at least heads * 128 = {H * 128} (16-byte loads); pass q.contiguous()")
+    if not q.is_cuda:
+        raise _capi.AuleError("aule (HIP build): the MLA indexer needs ROCm device tensors; there is no CPU fallback")
+    tensors = [weights, k_cache, k_scale, block_tables, context_lens] + [t for t in (q_scale, cu_seqlens_q) if t is not None]
+    _same_device("MLA indexer", q, *tensors)
+    W = block_tables.shape[1] * k_cache.shape[1]
+    logits = torch.empty((T, W), device=q.device, dtype=torch.float32)
+    if T == 0 or B == 0:
+        return logits
+    lib = _capi.get_lib()
+    d = _capi.MlaIndexerLogitsFp8mmaDesc()
+    d.struct_size = ctypes.sizeof(d)
+    d.cache_dtype = _capi.KV_CACHE_FP8_E4M3
+    d.heads, d.head_dim, d.batch = H, 128, B
+    d.num_blocks, d.block_size, d.max_blocks = k_cache.shape[0], k_cache.shape[1], block_tables.shape[1]
+    d.total_tokens, d.max_seqlen_q = T, max_sq
+    d.q_token_stride, d.logits_stride = q_stride, W
+    d.device = _device_index(q.device)
+    d.stream = _stream_ptr(q.device)
+    d.q, d.weights, d.k_cache, d.logits = q.data_ptr(), weights.data_ptr(), k_cache.data_ptr(), logits.data_ptr()
+    d.k_scale = k_scale.data_ptr()
+    d.q_scale = q_scale.data_ptr() if q_scale is not None else None
+    d.block_tables, d.context_lens = block_tables.data_ptr(), context_lens.data_ptr()
+    d.cu_seqlens_q = cu_seqlens_q.data_ptr() if cu_seqlens_q is not None else None
+    _capi.check(lib.aule_mla_indexer_logits_fp8mma_ex(ctypes.byref(d)), "aule_mla_indexer_logits_fp8mma_ex")
+    return logits
+
+
 def _indexer_topk_args(topk, output):
     """The rules of topk and output, which mla_indexer checks before its first launch."""
     if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= MLA_INDEXER_MAX_TOPK:

@@ -154,6 +154,19 @@ static_assert(sizeof(aule_mla_indexer_logits_desc) == 136 && offsetof(aule_mla_i
                   offsetof(aule_mla_indexer_logits_desc, context_lens) == 112 && offsetof(aule_mla_indexer_logits_desc, cu_seqlens_q) == 120 &&
                   offsetof(aule_mla_indexer_logits_desc, logits) == 128,
               "aule_mla_indexer_logits_desc layout is part of the ABI");
+static_assert(sizeof(aule_mla_indexer_logits_fp8mma_desc) == 144 && offsetof(aule_mla_indexer_logits_fp8mma_desc, reserved) == 4 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, cache_dtype) == 8 && offsetof(aule_mla_indexer_logits_fp8mma_desc, heads) == 12 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, head_dim) == 16 && offsetof(aule_mla_indexer_logits_fp8mma_desc, batch) == 20 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, num_blocks) == 24 && offsetof(aule_mla_indexer_logits_fp8mma_desc, block_size) == 28 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, max_blocks) == 32 && offsetof(aule_mla_indexer_logits_fp8mma_desc, total_tokens) == 36 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, max_seqlen_q) == 40 && offsetof(aule_mla_indexer_logits_fp8mma_desc, device) == 44 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, q_token_stride) == 48 && offsetof(aule_mla_indexer_logits_fp8mma_desc, logits_stride) == 56 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, stream) == 64 && offsetof(aule_mla_indexer_logits_fp8mma_desc, q) == 72 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, weights) == 80 && offsetof(aule_mla_indexer_logits_fp8mma_desc, k_cache) == 88 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, k_scale) == 96 && offsetof(aule_mla_indexer_logits_fp8mma_desc, block_tables) == 104 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, context_lens) == 112 && offsetof(aule_mla_indexer_logits_fp8mma_desc, cu_seqlens_q) == 120 &&
+                  offsetof(aule_mla_indexer_logits_fp8mma_desc, logits) == 128 && offsetof(aule_mla_indexer_logits_fp8mma_desc, q_scale) == 136,
+              "aule_mla_indexer_logits_fp8mma_desc layout is part of the ABI");
 static_assert(sizeof(aule_mla_indexer_topk_desc) == 96 && offsetof(aule_mla_indexer_topk_desc, output) == 4 &&
                   offsetof(aule_mla_indexer_topk_desc, topk) == 8 && offsetof(aule_mla_indexer_topk_desc, batch) == 12 &&
                   offsetof(aule_mla_indexer_topk_desc, block_size) == 16 && offsetof(aule_mla_indexer_topk_desc, max_blocks) == 20 &&
@@ -2068,6 +2081,69 @@ int32_t aule_mla_indexer_logits_ex(const aule_mla_indexer_logits_desc* d) {
     return launched(what, aule_hip::launch_mla_indexer_logits(a, plan, (hipStream_t)d->stream));
 }
 
+// The logits with FP8 queries: aule_mla_indexer_logits_desc's rules on the shared fields, the FP8 cache alone, q's stride in bytes.
+static aule_hip::MlaIndexerPlan mla_indexer_fp8mma_plan_of(const aule_mla_indexer_logits_fp8mma_desc* d) {
+    return aule_hip::mla_indexer_fp8mma_plan((int)d->batch, max_sq_or_one(d), (long long)d->block_size * d->max_blocks, d->device);
+}
+
+static const char* mla_indexer_fp8mma_desc_error(const aule_mla_indexer_logits_fp8mma_desc* d, bool launch, Reason& why) {
+    if (d == nullptr || d->struct_size != sizeof(aule_mla_indexer_logits_fp8mma_desc)) return kBadDescriptor;
+    if (d->reserved != 0) return reasonf(why, "reserved (%u) must be 0", d->reserved);
+    if (d->cache_dtype != AULE_KV_CACHE_FP8_E4M3) return reasonf(why, "cache_dtype %d must be AULE_KV_CACHE_FP8_E4M3", d->cache_dtype);
+    if (d->heads < 1 || d->heads > (uint32_t)aule_hip::kMlaIndexerMaxHeads) return reasonf(why, "heads (%u) must be in 1 .. %d", d->heads, aule_hip::kMlaIndexerMaxHeads);
+    if (d->head_dim != 128) return reasonf(why, "head_dim (%u) must be 128", d->head_dim);
+    if (d->num_blocks == 0 || (uint64_t)d->num_blocks * d->block_size > 0x7fffffffull)
+        return reasonf(why, "num_blocks * block_size (%u * %u) must be in 1 .. 2^31 - 1", d->num_blocks, d->block_size);
+    if (const char* e = indexer_shape_error(d, why)) return e;
+    if (d->q_token_stride < (int64_t)d->heads * 128)
+        return reasonf(why, "q_token_stride (%lld) is smaller than a token (heads * head_dim = %u bytes)", (long long)d->q_token_stride, d->heads * 128);
+    if (d->q_token_stride % 16 != 0) return reasonf(why, "q_token_stride (%lld) must be a multiple of 16 bytes (16-byte loads)", (long long)d->q_token_stride);
+    if (indexer_nothing_to_do(d)) return nullptr;
+    const aule_hip::MlaIndexerPlan plan = mla_indexer_fp8mma_plan_of(d);
+    if (plan.grid > 0x7fffffffll)
+        return reasonf(why, "the grid (batch %u * token groups %d * key chunks %d) exceeds 2^31 - 1 workgroups", d->batch, plan.token_groups, plan.key_chunks);
+    if (!launch) return nullptr;
+    if (!d->q || !d->weights || !d->k_cache || !d->block_tables || !d->context_lens || !d->logits)
+        return "null tensor pointer (q, weights, k_cache, block_tables, context_lens and logits are required)";
+    if (misaligned(d->q) || misaligned(d->k_cache)) return "q and k_cache must be 16-byte aligned";
+    if (!d->k_scale) return "null k_scale (the FP8 cache needs [num_blocks, block_size] fp32 values on the device)";
+    if (((reinterpret_cast<uintptr_t>(d->weights) | reinterpret_cast<uintptr_t>(d->k_scale) | reinterpret_cast<uintptr_t>(d->q_scale) |
+          reinterpret_cast<uintptr_t>(d->logits) | reinterpret_cast<uintptr_t>(d->block_tables) | reinterpret_cast<uintptr_t>(d->context_lens) |
+          reinterpret_cast<uintptr_t>(d->cu_seqlens_q)) & 3) != 0)
+        return "weights, k_scale, q_scale, logits, block_tables, context_lens and cu_seqlens_q must be 4-byte aligned";
+    return nullptr;
+}
+
+int32_t aule_mla_indexer_logits_fp8mma_ex(const aule_mla_indexer_logits_fp8mma_desc* d) {
+    RoctxRange range("aule.mla_indexer_logits_fp8mma");
+    const char* what = "MLA indexer FP8-product logits";
+    std::lock_guard<std::mutex> lk(g_mu);
+    Reason text;
+    if (const char* why = mla_indexer_fp8mma_desc_error(d, true, text)) {
+        set_error("%s failed: %s", what, why);
+        return -3;
+    }
+    if (indexer_nothing_to_do(d)) return 0;
+    if (!initialised()) return -1;
+    aule_hip::MlaIndexerArgs a;
+    a.q = d->q; a.weights = d->weights; a.k_cache = d->k_cache; a.logits = d->logits;
+    a.block_tables = d->block_tables; a.context_lens = d->context_lens; a.cu_seqlens_q = d->cu_seqlens_q;
+    a.T = (int)d->total_tokens; a.B = (int)d->batch; a.H = (int)d->heads;
+    a.num_blocks = (int)d->num_blocks; a.block_size = (int)d->block_size; a.max_blocks = (int)d->max_blocks;
+    a.max_seqlen_q = max_sq_or_one(d);
+    a.q_token_stride = d->q_token_stride; a.logits_stride = d->logits_stride;
+    a.dtype = 0;
+    a.device = d->device;
+    a.cache_kind = aule_hip::kCacheFp8E4M3;
+    a.k_scale = d->k_scale;
+    a.q_scale = d->q_scale;
+    const aule_hip::MlaIndexerPlan plan = mla_indexer_fp8mma_plan_of(d);
+    DeviceGuard g(d->device);
+    int rc = ensure_configured();
+    if (rc) return rc;
+    return launched(what, aule_hip::launch_mla_indexer_logits_fp8mma(a, plan, (hipStream_t)d->stream));
+}
+
 static const char* mla_indexer_topk_desc_error(const aule_mla_indexer_topk_desc* d, Reason& why) {
     if (d == nullptr || d->struct_size != sizeof(aule_mla_indexer_topk_desc)) return kBadDescriptor;
     if (d->output != AULE_INDEXER_SLOTS && d->output != AULE_INDEXER_POSITIONS)
@@ -3264,14 +3340,26 @@ int32_t aule_hip_debug_paged_d256_launch_nsplit(const aule_paged_d256_desc* d, i
     return paged_d256_launch(d, nsplit);
 }
 
+/* the five integers both indexer plan hooks answer */
+static int32_t dump_indexer_plan(const aule_hip::MlaIndexerPlan& plan, int32_t* out, int32_t cap) {
+    return dump_plan({plan.group_tokens, plan.token_groups, plan.chunk_keys, plan.key_chunks, (int32_t)plan.grid}, nullptr, out, cap);
+}
+
 /* Debug hook: the launch plan of aule_mla_indexer_logits_ex(d) as integers (include/aule.h lists them): the plan the launch reads.
  * Pure host logic like the forward hook. */
 int32_t aule_hip_debug_mla_indexer_plan(const aule_mla_indexer_logits_desc* d, int32_t* out, int32_t cap) {
     Reason text;
     if (mla_indexer_logits_desc_error(d, false, text)) return -3;
     if (indexer_nothing_to_do(d)) return 0;
-    const aule_hip::MlaIndexerPlan plan = mla_indexer_plan_of(d);
-    return dump_plan({plan.group_tokens, plan.token_groups, plan.chunk_keys, plan.key_chunks, (int32_t)plan.grid}, nullptr, out, cap);
+    return dump_indexer_plan(mla_indexer_plan_of(d), out, cap);
+}
+
+/* Debug hook: the same for aule_mla_indexer_logits_fp8mma_ex(d). */
+int32_t aule_hip_debug_mla_indexer_fp8mma_plan(const aule_mla_indexer_logits_fp8mma_desc* d, int32_t* out, int32_t cap) {
+    Reason text;
+    if (mla_indexer_fp8mma_desc_error(d, false, text)) return -3;
+    if (indexer_nothing_to_do(d)) return 0;
+    return dump_indexer_plan(mla_indexer_fp8mma_plan_of(d), out, cap);
 }
 
 /* Debug hook: the launch plan of aule_attention_mla_prefill_backward_ex(d) as integers (include/aule.h lists them): the plan the launch

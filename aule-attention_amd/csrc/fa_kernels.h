@@ -484,6 +484,7 @@ struct MlaIndexerArgs {
     int dtype;
     int device = -1;                    // as FwdArgs::device
     int cache_kind = kCache16;
+    const float* q_scale = nullptr;     // the FP8-query launch only: [T, H] fp32, device; null: 1
 };
 constexpr int kMlaIndexerMaxHeads = 64;
 constexpr int kMlaIndexerMaxTopk = 65536;
@@ -498,6 +499,11 @@ struct MlaIndexerPlan {
 };
 MlaIndexerPlan mla_indexer_plan(int B, int max_seqlen_q, long long W, int device);
 int launch_mla_indexer_logits(const MlaIndexerArgs& a, const MlaIndexerPlan& plan, hipStream_t stream);   // -1: unsupported arguments
+// The logits with e4m3 queries and FP8 matrix products (fa_mla_indexer_fp8mma_gfx950.hip; aule_mla_indexer_logits_fp8mma_desc): q is
+//   [T, H, 128] e4m3fn codes (q_token_stride bytes per token, a multiple of 16), q_scale their per-(token, head) scales, the cache
+//   kCacheFp8E4M3; `dtype` is not read.  The plan is mla_indexer_plan's rule with this kernel's tokens per work item.
+MlaIndexerPlan mla_indexer_fp8mma_plan(int B, int max_seqlen_q, long long W, int device);
+int launch_mla_indexer_logits_fp8mma(const MlaIndexerArgs& a, const MlaIndexerPlan& plan, hipStream_t stream);   // -1: unsupported arguments
 struct MlaIndexerTopkArgs {
     const float* logits;                // [T, logits_stride]
     int* indices;                       // [T, topk]

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "fa_kernels.h"
+#include "fa_mla_indexer.h"
 #include "kv_quant.h"
 
 namespace aule_hip {
@@ -47,23 +48,6 @@ constexpr int kTopkThreads = 1024;
 constexpr int kTopkWaves = kTopkThreads / 64;
 constexpr int kTopkRun = 8;                            // consecutive positions per thread and step
 constexpr int kTopkStep = kTopkThreads * kTopkRun;     // positions per step of the workgroup
-
-struct IdxParams {
-    const char* q;
-    const float* w;
-    const char* k;
-    const float* ks;     // FP8 cache: [num_blocks * block_size] fp32; else null
-    const int* table;
-    const int* ctx;
-    const int* cu;       // null: sequence b owns row b
-    float* out;
-    long long q_stride, out_stride;
-    int T, B, H;
-    int nb, bs, bs_shift;
-    int max_blocks, max_sq;
-    int W;               // max_blocks * bs
-    int groups, chunks, chunk_keys;
-};
 
 struct TopkParams {
     const float* logits;
@@ -416,9 +400,13 @@ __global__ void __launch_bounds__(kTopkThreads) fa_mla_indexer_topk_kernel(const
 }  // namespace
 
 MlaIndexerPlan mla_indexer_plan(int B, int max_seqlen_q, long long W, int device) {
+    return mla_indexer_plan_grouped(B, max_seqlen_q, W, device, kIdxGroup);
+}
+
+MlaIndexerPlan mla_indexer_plan_grouped(int B, int max_seqlen_q, long long W, int device, int group_tokens) {
     MlaIndexerPlan plan;
-    if (B <= 0 || max_seqlen_q <= 0 || W <= 0) return plan;
-    const long long groups = ((long long)max_seqlen_q + kIdxGroup - 1) / kIdxGroup;
+    if (B <= 0 || max_seqlen_q <= 0 || W <= 0 || group_tokens <= 0) return plan;
+    const long long groups = ((long long)max_seqlen_q + group_tokens - 1) / group_tokens;
     const long long units = (W + kIdxUnit - 1) / kIdxUnit;
     const long long base = (long long)B * groups;
     const long long target = 4ll * device_cu_count(device);   // a few workgroups per compute unit
@@ -427,7 +415,7 @@ MlaIndexerPlan mla_indexer_plan(int B, int max_seqlen_q, long long W, int device
     if (chunks < 1) chunks = 1;
     const long long per = (units + chunks - 1) / chunks;
     chunks = (units + per - 1) / per;
-    plan.group_tokens = kIdxGroup;
+    plan.group_tokens = group_tokens;
     plan.token_groups = (int)groups;
     plan.chunk_keys = (int)(per * kIdxUnit);
     plan.key_chunks = (int)chunks;
@@ -435,16 +423,15 @@ MlaIndexerPlan mla_indexer_plan(int B, int max_seqlen_q, long long W, int device
     return plan;
 }
 
-int launch_mla_indexer_logits(const MlaIndexerArgs& a, const MlaIndexerPlan& plan, hipStream_t stream) {
+int mla_indexer_params(const MlaIndexerArgs& a, const MlaIndexerPlan& plan, IdxParams& p) {
     if (plan.grid <= 0 || plan.grid > 0x7fffffffll) return -1;
     if (a.H < 1 || a.H > kMlaIndexerMaxHeads || a.block_size < 1 || a.max_blocks < 1 || a.num_blocks < 1) return -1;
     const long long W = (long long)a.max_blocks * a.block_size;
     if (W >= (1ll << 30) || a.logits_stride < W) return -1;
-    if (a.q_token_stride < (long long)a.H * kIdxD || a.q_token_stride % 8 != 0) return -1;
+    if (a.q_token_stride < (long long)a.H * kIdxD) return -1;
     if (a.cu_seqlens_q == nullptr && a.T < a.B) return -1;
     const bool fp8 = a.cache_kind == kCacheFp8E4M3;
     if (fp8 ? a.k_scale == nullptr : a.cache_kind != kCache16) return -1;
-    IdxParams p;
     p.q = static_cast<const char*>(a.q); p.w = a.weights; p.k = static_cast<const char*>(a.k_cache);
     p.ks = fp8 ? a.k_scale : nullptr;
     p.table = a.block_tables; p.ctx = a.context_lens; p.cu = a.cu_seqlens_q;
@@ -455,6 +442,13 @@ int launch_mla_indexer_logits(const MlaIndexerArgs& a, const MlaIndexerPlan& pla
     p.max_blocks = a.max_blocks; p.max_sq = a.max_seqlen_q;
     p.W = (int)W;
     p.groups = plan.token_groups; p.chunks = plan.key_chunks; p.chunk_keys = plan.chunk_keys;
+    return 0;
+}
+
+int launch_mla_indexer_logits(const MlaIndexerArgs& a, const MlaIndexerPlan& plan, hipStream_t stream) {
+    IdxParams p;
+    if (mla_indexer_params(a, plan, p) != 0 || a.q_token_stride % 8 != 0) return -1;
+    const bool fp8 = a.cache_kind == kCacheFp8E4M3;
     return dispatch_16bit(a.dtype, [&](auto t) {
         if (fp8) hipLaunchKernelGGL((fa_mla_indexer_logits_kernel<decltype(t), true>), dim3((unsigned)plan.grid), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((fa_mla_indexer_logits_kernel<decltype(t), false>), dim3((unsigned)plan.grid), dim3(256), 0, stream, p);

@@ -768,8 +768,8 @@ uint64_t aule_attention_mla_sparse_ds_workspace_size(const aule_mla_sparse_ds_de
 /* decode with total_tokens < batch; a grid past 2^31 - 1; and, by the launch alone, a null or misaligned pointer, an FP8 cache        */
 /* without k_scale, k_scale with a 16-bit cache.  The plan hook gives the same verdict on every field and reads no pointer.            */
 /* total_tokens = 0 or batch = 0 returns 0 without a launch and without aule_init().                                                   */
-/* Not built: FP8 queries and FP8 MFMAs; a fused streaming top-k that never writes [total_tokens, W]; an append kernel for the index   */
-/* keys; heads > 64; a backward.                                                                                                        */
+/* FP8 queries and FP8 MFMAs are aule_mla_indexer_logits_fp8mma_ex's, below.  Not built: a fused streaming top-k that never writes     */
+/* [total_tokens, W]; heads > 64; a backward.                                                                                           */
 typedef struct aule_mla_indexer_logits_desc {
     uint32_t struct_size;      /* = sizeof(aule_mla_indexer_logits_desc) = 136 */
     int32_t dtype;             /* offset 4; type of q: AULE_DTYPE_F16 or AULE_DTYPE_BF16 */
@@ -797,6 +797,50 @@ typedef struct aule_mla_indexer_logits_desc {
 } aule_mla_indexer_logits_desc;
 /* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
 int32_t aule_mla_indexer_logits_ex(const aule_mla_indexer_logits_desc* desc);
+
+/* LOGITS WITH FP8 QUERIES (additive, opt-in): the logits entry above for callers whose index queries are OCP e4m3fn codes, the        */
+/* products on FP8 matrix instructions (v_mfma_scale_f32_32x32x64_f8f6f4, both block scales 1).                                         */
+/*   logits[t][s] = k_scale[row(s)] * sum_h (weights[t][h] * q_scale[t][h]) * relu(sum_d float(q[t][h][d]) * float(k[row(s)][d]))      */
+/* q is [total_tokens, heads, 128] codes, q_token_stride BYTES (= elements) from one token to the next, a multiple of 16 and >= heads  */
+/* * 128; q_scale is [total_tokens, heads] fp32, contiguous, device, NULL = 1: the per-(token, head) scale of the codes, multiplied    */
+/* into the weight once per token -- no element is ever scaled.  The cache is the FP8 index-key cache of the entry above:              */
+/* cache_dtype must be AULE_KV_CACHE_FP8_E4M3 and k_scale is required.  Every other field, clamp, visibility rule, the -inf columns,  */
+/* the rows never written, what is never read, capture and determinism are aule_mla_indexer_logits_desc's.  Accumulation is fp32 in a  */
+/* fixed order; on data whose partial sums are exact in fp32 the result equals the 16-bit entry's on the converted codes with weights  */
+/* * q_scale bit for bit.  Work item (sequence, group of 4 tokens, chunk of keys), the plan rule of the entry above;                   */
+/* aule_hip_debug_mla_indexer_fp8mma_plan() gives the numbers.                                                                         */
+/* REFUSED with -3 and a reason naming the field, before the device is needed: what the entry above refuses on the shared fields, a    */
+/* nonzero reserved, cache_dtype != AULE_KV_CACHE_FP8_E4M3, q_token_stride not a multiple of 16; and, by the launch alone, a null or   */
+/* misaligned pointer (q and k_cache 16-byte, the rest 4-byte), a null k_scale.  The plan hook gives the same verdict on every field   */
+/* and reads no pointer.  total_tokens = 0 or batch = 0 returns 0 without a launch and without aule_init().                            */
+typedef struct aule_mla_indexer_logits_fp8mma_desc {
+    uint32_t struct_size;      /* = sizeof(aule_mla_indexer_logits_fp8mma_desc) = 144 */
+    uint32_t reserved;         /* offset 4; must be 0 */
+    int32_t cache_dtype;       /* offset 8; AULE_KV_CACHE_FP8_E4M3 */
+    uint32_t heads;            /* offset 12; index heads, 1 .. 64 */
+    uint32_t head_dim;         /* offset 16; 128 */
+    uint32_t batch;            /* offset 20; sequences; 0: returns 0 without a launch */
+    uint32_t num_blocks;       /* offset 24; blocks of k_cache, >= 1 */
+    uint32_t block_size;       /* offset 28; any value > 0 */
+    uint32_t max_blocks;       /* offset 32; columns of block_tables; W = max_blocks * block_size < 2^30 */
+    uint32_t total_tokens;     /* offset 36; rows of q / weights / q_scale / logits; 0: returns 0 without a launch */
+    uint32_t max_seqlen_q;     /* offset 40; >= 1: sizes the grid, and caps every n_b */
+    int32_t device;            /* offset 44; HIP device ordinal, -1 = current */
+    int64_t q_token_stride;    /* offset 48; bytes, >= heads * 128, a multiple of 16 */
+    int64_t logits_stride;     /* offset 56; elements, >= W */
+    void* stream;              /* offset 64; hipStream_t */
+    const void* q;             /* offset 72; [total_tokens, heads, 128] e4m3fn codes */
+    const float* weights;      /* offset 80; [total_tokens, heads] fp32 */
+    const void* k_cache;       /* offset 88; [num_blocks, block_size, 128] e4m3fn codes */
+    const float* k_scale;      /* offset 96; [num_blocks, block_size] fp32, device */
+    const int32_t* block_tables;   /* offset 104; [batch, max_blocks] */
+    const int32_t* context_lens;   /* offset 112; [batch]: keys per sequence, the new ones included */
+    const int32_t* cu_seqlens_q;   /* offset 120; [batch + 1], device; NULL: plain decode */
+    float* logits;             /* offset 128; [total_tokens, logits_stride] fp32 */
+    const float* q_scale;      /* offset 136; [total_tokens, heads] fp32, device; NULL: 1 */
+} aule_mla_indexer_logits_fp8mma_desc;
+/* 0 ok; -1 uninitialised; -3 invalid/unsupported arguments; -4 launch failure. */
+int32_t aule_mla_indexer_logits_fp8mma_ex(const aule_mla_indexer_logits_fp8mma_desc* desc);
 
 /* TOP-K.  indices[t][:] = the key list of token t from logits [total_tokens, W] fp32 (logits_stride >= W; ANY such tensor, not       */
 /* necessarily aule_mla_indexer_logits_ex's), 1 <= topk <= 65536, with the tables, lengths, offsets and clamps of the logits entry.    */
@@ -1749,6 +1793,8 @@ int32_t aule_hip_debug_paged_d256_launch_nsplit(const aule_paged_d256_desc* desc
 /* aule_init(), no pointer of the descriptor is read (the pointer rules of the launch are not applied); without a device it plans   */
 /* for 256 compute units.                                                                                                           */
 int32_t aule_hip_debug_mla_indexer_plan(const aule_mla_indexer_logits_desc* desc, int32_t* out, int32_t cap);
+/* Debug: the same five integers for aule_mla_indexer_logits_fp8mma_ex(desc), by the same rule with that kernel's tokens per group.  */
+int32_t aule_hip_debug_mla_indexer_fp8mma_plan(const aule_mla_indexer_logits_fp8mma_desc* desc, int32_t* out, int32_t cap);
 /* Debug: the launch plan of aule_attention_mla_prefill_backward_ex(desc) as integers -- out = {heads per chunk, n_chunks (the last    */
 /* chunk may be short), the bound of n_chunks (16), delta workgroups, dQ workgroups, dK/dV workgroups (key blocks * batch * n_chunks),  */
 /* reduce workgroups, 1 if the reduce runs (else the dK/dV kernel writes dk_pe itself), workspace bytes low 32 bits, high 32 bits}.     */

@@ -18,7 +18,10 @@ through the Python layer for logits, top-k and both, ours and torch's, the three
 marked LOSES), the achieved TFLOP/s of our logits (2 * visible (token, key) pairs * 64 * 128 flop) and the GB/s of visible logits our
 top-k reads once (4 bytes each; it reads them up to five times).  Every leg runs under its own alarm (--leg-timeout seconds, default
 120): a leg that hangs ends the process; the first failure stops the run.  --out FILE also writes the table there.  --rounds N
-(default 5)."""
+(default 5).
+
+--fp8mma: the ten FP8-cache logits shapes with aule.mla_indexer_logits_fp8mma (e4m3 queries) against aule.mla_indexer_logits with the
+same queries as bf16, alternated the same way; --heads N (default 64) sets the head count of that mode."""
 import ctypes
 import os
 import signal
@@ -155,11 +158,60 @@ def leg(what, B, n, L, fp8, rounds, lines):
     lines.append(line)
 
 
+def leg_fp8mma(what, B, n, L, rounds, lines):
+    """--fp8mma: aule.mla_indexer_logits_fp8mma against aule.mla_indexer_logits (bf16 queries) over the SAME FP8 cache and the same
+    queries -- the codes, and the codes times their scales rounded to bf16 -- alternated; ratio = 16-bit-query call / FP8-query call"""
+    g = torch.Generator(device="cuda").manual_seed(B + n + L)
+    T, nblk = B * n, L // BS
+    qc, qs = aule.quantize_rows_fp8(torch.randn(T, H, D, device="cuda", dtype=torch.bfloat16, generator=g))
+    qs = qs.view(T, H).contiguous()
+    q16 = (qc.float() * qs[..., None]).to(torch.bfloat16)
+    w = torch.randn(T, H, device="cuda", generator=g) * H ** -0.5
+    cache, ks = aule.quantize_indexer_cache_fp8(torch.randn(B * nblk, BS, D, device="cuda", dtype=torch.bfloat16, generator=g))
+    bt = torch.randperm(B * nblk, device="cuda", generator=g).to(torch.int32).view(B, nblk)
+    cl = torch.full((B,), L, device="cuda", dtype=torch.int32)
+    ragged = dict(cu_seqlens_q=torch.arange(B + 1, device="cuda", dtype=torch.int32) * n, max_seqlen_q=n) if n > 1 else {}
+    new = lambda: aule.mla_indexer_logits_fp8mma(qc, w, cache, ks, bt, cl, q_scale=qs, **ragged)   # noqa: E731
+    old = lambda: aule.mla_indexer_logits(q16, w, cache, bt, cl, k_scale=ks, **ragged)   # noqa: E731
+    a, b = new(), old()
+    fin = torch.isfinite(b)
+    if not torch.equal(fin, torch.isfinite(a)):
+        raise SystemExit(f"{what}: the -inf marks of the two calls differ")
+    rel = float((a[fin] - b[fin]).norm() / b[fin].norm())   # (the bf16 rounding of q16 is the difference)
+    if not rel < 2e-2:
+        raise SystemExit(f"{what}: the two calls disagree (relative error {rel:.3g})")
+    del a, b, fin
+    res = _alternated({"fp8mma": new, "16-bit q": old}, rounds)
+    visible = B * sum(L - n + i + 1 for i in range(n))
+    ratio = res["16-bit q"][0] / res["fp8mma"][0]
+    line = (f"  {what}: fp8mma {res['fp8mma'][1]} us, 16-bit q {res['16-bit q'][1]} us, {ratio:6.2f}x   "
+            f"{2.0 * visible * H * D / (res['fp8mma'][0] * 1e-6) / 1e12:7.2f} TFLOP/s   (rel. diff {rel:.1e})" + ("   LOSES" if ratio < 1.0 else ""))
+    print(line, flush=True)
+    lines.append(line)
+
+
 def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_mla_indexer needs a GPU: a timing taken anywhere else says nothing")
     rounds, budget = _arg("--rounds", 5), _arg("--leg-timeout", 120)
     signal.signal(signal.SIGALRM, signal.SIG_DFL)      # the default action ends the process, also from inside a blocked device call
+    if "--fp8mma" in sys.argv:
+        global H
+        H = _arg("--heads", H)   # (32: the head count at which the 8-tokens-per-item build fits its registers)
+        lines = [f"# tools/bench_mla_indexer.py --fp8mma   (one MI355X; {H} index heads x {D}, block {BS}, FP8 key cache; e4m3 queries through "
+                 f"aule.mla_indexer_logits_fp8mma against the same queries as bf16 through aule.mla_indexer_logits; {rounds} alternated rounds of "
+                 f"~{WINDOW_MS} ms windows, median (min .. max) us per call, host launch cost included; ratio = 16-bit-query call / FP8-query call)"]
+        print(lines[0], flush=True)
+        for what, B, n, L in [(f"decode  T {T:4d} context {L:6d}", T, 1, L) for T in TOKENS for L in CONTEXT] + [
+                (f"prefill T {PREFILL_CHUNK:4d} context {PREFILL_CONTEXT:6d}", 1, PREFILL_CHUNK, PREFILL_CONTEXT)]:
+            signal.alarm(budget)
+            leg_fp8mma(what, B, n, L, rounds, lines)
+            signal.alarm(0)
+            torch.cuda.empty_cache()
+        if "--out" in sys.argv:
+            with open(_arg("--out", "", str), "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     head = (f"# tools/bench_mla_indexer.py   (one MI355X; {H} index heads x {D}, block {BS}, topk {TOPK}, bf16 queries; plan = sequences x token groups x "
             f"key chunks workgroups; {rounds} alternated rounds of ~{WINDOW_MS} ms windows, median (min .. max) us per call, host launch cost included; "
             f"ratio = torch / ours)")
